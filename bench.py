@@ -3,6 +3,12 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: this process starts the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py --full                                 (+ the side legs below: configs, modes, cpu_baseline, parity, io, timers)
+    python bench.py --dump-outputs DIR                     (+ a fixed sample of the last timed step's frames as DIR/*.npy)
+
+A plain run sets up, warms up, times --steps steps and prints the line (metric, value, unit, dtype, ms_per_step, roofline from the
+timed region); every object below that takes runs of its own (roofline.detail / families / shader_clock, roofline_warp, modes,
+cpu_baseline, parity, io, with_io, configs, host) is measured with --full only.
 
 Workload = BASELINE configs[1] (superslomo_original.ini inference): synthetic Adobe240-shaped 1280x720 frame pairs
 (zero-padded to 736x1280 in normalised space, resident in HBM) -> 7 intermediate frames t = 1/8..7/8 each; stage 1
@@ -60,6 +66,7 @@ PEAK_F32_MFMA_TFLOPS = 157.3      # /opt/skills/guides/MI355X_MICROARCH.md, chip
 PEAK_F16_MFMA_TFLOPS = 2500.0     # dense fp16/bf16 MFMA
 PEAK_HBM_GBS = 8000.0
 HEADLINE_PRECISION = "f32w"
+FULL_MODES = "f32,f16x3,f16f8"      # side modes of a --full inference line
 DTYPE_NOTE = {"f32": "f32",
               "f32w": "f32",
               "f16": "f16 (f32 accumulate) - reduced precision",
@@ -161,7 +168,7 @@ def collect_configs(timeout_s=300):
             env.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", LOCAL_WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(free_port()))
         t0 = time.perf_counter()
         try:
-            pr = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-configs"] + argv, env=env, stdout=subprocess.PIPE,
+            pr = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-configs", "--full"] + argv, env=env, stdout=subprocess.PIPE,
                                 stderr=subprocess.PIPE, timeout=timeout_s)
             line = [ln for ln in pr.stdout.decode().splitlines() if ln.startswith("{")]
             if pr.returncode != 0 or not line:
@@ -932,6 +939,18 @@ def streamed_with_io(pipe, dev, h, w, P, PB, t_dev, steps, sdist, sync, cfg=None
                     "steps; `value` itself has its inputs resident in HBM (SURVEY 8d)"}
 
 
+def dump_frames(path, outs, n_pairs, hp, wp):
+    """--dump-outputs: the frames of the last timed step (PairPipeline.submit results, [pairs_per_batch * 7,3,Hp,Wp] each, pair-major)
+    at K pixel positions drawn once with a fixed seed, the same in every frame -> path/frames_sample.npy, float32 [pairs, 7, 3, K],
+    K sized to 8 Mi values (32 MiB)."""
+    import numpy as np
+    k = min(hp * wp, (8 << 20) // (n_pairs * N_T * 3))
+    pos = torch.randperm(hp * wp, generator=torch.Generator().manual_seed(1234))[:k].sort().values.to(outs[0].device)
+    sample = torch.cat([o.reshape(o.shape[0], 3, hp * wp).index_select(2, pos) for o in outs], 0)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "frames_sample.npy"), sample.reshape(n_pairs, N_T, 3, k).float().cpu().numpy())
+
+
 def infer_bench(args):
     from ssm_amd import dist as sdist
     from ssm_amd.config import load_config, synthetic_weight_overrides
@@ -962,12 +981,17 @@ def infer_bench(args):
     def sync():
         torch.cuda.synchronize(dev)
 
-    def run_mode(precision, steps, warmup, timers):
+    def run_mode(precision, steps, warmup, timers, dump=None):
         pipe = PairPipeline(sd1d, sd2d, N_T, Hp, Wp, dev, True, precision, args.streams, graphs=bool(args.graphs), pairs_per_batch=PB)
+        calls = [0]
 
         def step():                 # P pairs -> 7 frames each; consecutive batches of PB pairs alternate between the streams
+            calls[0] += 1
+            keep = dump is not None and calls[0] == warmup + steps      # the last timed step: private copies of its frames
             for img6 in pairs:
-                pipe.submit(img6, t_dev, want_aux=False)
+                out = pipe.submit(img6, t_dev, want_aux=False, clone=keep)
+                if keep:
+                    dump.append(out)
 
         for _ in range(warmup):
             step()
@@ -976,15 +1000,16 @@ def infer_bench(args):
         elapsed = sdist.timed_steps(step, steps, 0, sync)
         ms_step = 1e3 * elapsed / steps
         res = {"value": N_T * P * world * steps / elapsed, "ms_per_step": ms_step, "ms_per_pair": ms_step / P, "elapsed_s": elapsed}
-        # host time to ISSUE a step's launches (outside the timed region; the queues are empty when it starts, so nothing blocks the host)
-        enq = 0.0
-        for _ in range(3):
+        if args.full:
+            # host time to ISSUE a step's launches (outside the timed region; the queues are empty when it starts, so nothing blocks the host)
+            enq = 0.0
+            for _ in range(3):
+                sync()
+                t0 = time.perf_counter()
+                step()
+                enq += time.perf_counter() - t0
             sync()
-            t0 = time.perf_counter()
-            step()
-            enq += time.perf_counter() - t0
-        sync()
-        res["host_enqueue_ms_per_step"] = 1e3 * enq / 3
+            res["host_enqueue_ms_per_step"] = 1e3 * enq / 3
         peak = PEAK_F32_MFMA_TFLOPS if precision in ("f32", "f32w") else PEAK_F16_MFMA_TFLOPS
         ach = flops_pair * P / (ms_step * 1e-3) / 1e12
         kname = {"f32w": "wino4_kernel<*, ups 0|1> (3x3 layers, F(4x4,3x3), v_mfma_f32_16x16x4_f32) + wino2_kernel<*> (3x3 layers on the 1/32 maps, "
@@ -1086,7 +1111,12 @@ def infer_bench(args):
         return res
 
     timers = not args.no_kernel_timers
-    main_res = run_mode(headline, args.steps, args.warmup, timers)
+    last = [] if (args.dump_outputs and rank == 0) else None
+    main_res = run_mode(headline, args.steps, args.warmup, timers, last)
+    if last is not None:
+        sync()
+        dump_frames(args.dump_outputs, last, P, Hp, Wp)
+        del last[:]
     out = {
         "metric": "interpolated 1280x720 frames/sec" if args.size == "720p" else "interpolated 3840x2160 frames/sec",
         "value": round(main_res["value"], 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1103,13 +1133,14 @@ def infer_bench(args):
     for k in ("roofline", "roofline_warp", "time_split_ms_per_pair"):
         if k in main_res:
             out[k] = main_res[k]
-    he = main_res["host_enqueue_ms_per_step"]
-    out["host_enqueue_ms_per_step"] = round(he, 3)
-    out["host"] = {"enqueue_ms_per_step": round(he, 3), "enqueue_share_of_step": round(he / main_res["ms_per_step"], 3),
-                   "usable_cpus": usable_cpus(), "cpus_of_this_rank": args.rank_cpus,
-                   "hbm": dict(getattr(args, "hbm", {}), peak_allocated_gb=round(torch.cuda.max_memory_allocated(dev) / 1e9, 1)),
-                   "note": "one host thread per rank issues the launches; at N ranks per host the ranks need N x this share of a core each "
-                           "(DESIGN 6): the step is GPU-bound as long as the share stays below 1"}
+    if "host_enqueue_ms_per_step" in main_res:
+        he = main_res["host_enqueue_ms_per_step"]
+        out["host_enqueue_ms_per_step"] = round(he, 3)
+        out["host"] = {"enqueue_ms_per_step": round(he, 3), "enqueue_share_of_step": round(he / main_res["ms_per_step"], 3),
+                       "usable_cpus": usable_cpus(), "cpus_of_this_rank": args.rank_cpus,
+                       "hbm": dict(getattr(args, "hbm", {}), peak_allocated_gb=round(torch.cuda.max_memory_allocated(dev) / 1e9, 1)),
+                       "note": "one host thread per rank issues the launches; at N ranks per host the ranks need N x this share of a core each "
+                               "(DESIGN 6): the step is GPU-bound as long as the share stays below 1"}
     if rank == 0 and world == 1 and not args.no_io and args.size == "720p":
         wio = streamed_with_io(main_res["_pipe"], dev, h_in, w_in, P, PB, t_dev, args.steps, sdist, sync, cfg)
         wio["vs_value"] = round(wio["value_with_io"] / out["value"], 4)
@@ -1239,7 +1270,9 @@ def main():
                          "rocprofv3 kernel-stats runs, whose per-kernel sums are divided by the number of pairs)")
     ap.add_argument("--precision", default=None, choices=["f32", "f32w", "f16x3", "f16", "f16f8"],
                     help="headline conv arithmetic (default f32 = the reference's arithmetic)")
-    ap.add_argument("--modes", default="f32,f16x3,f16f8", help="comma list of further modes reported under `modes` (N=1, 720p only); '' = none")
+    ap.add_argument("--modes", default=None,
+                    help="comma list of further modes reported under `modes` (N=1, 720p only); '' = none (default: %s with --full, none "
+                         "without)" % FULL_MODES)
     ap.add_argument("--modes-4k", default="", help="--size 4k: comma list of further modes run after the headline one (e.g. f16: BASELINE config 5 as worded)")
     ap.add_argument("--mode", default="infer", choices=["infer", "train", "recurrent"],
                     help="infer = the headline (BASELINE configs[1]); train = configs[2]: training step on 352x352 crops, "
@@ -1257,7 +1290,21 @@ def main():
     ap.add_argument("--stub-fail-rank", type=int, default=None, help="--stub: this rank exits with an error before the rendezvous (launcher test)")
     ap.add_argument("--no-configs", action="store_true", help="skip the short runs of BASELINE configs 3, 4, 5 reported under `configs` (N = 1, 720p)")
     ap.add_argument("--parity-4k", action="store_true", help="--size 4k: one t of one pair against the CPU oracle (about a minute of host time)")
+    ap.add_argument("--full", action="store_true",
+                    help="inference line: also run what the headline does not need - the configs 3-5 children, the side modes, cpu_baseline, "
+                         "parity, io / with_io, the per-kernel event timers, the shader-clock probes and the host-enqueue steps (the --no-* "
+                         "flags above leave single legs out again).  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="inference: write what the timed path computed in its last timed step to DIR/frames_sample.npy (float32 "
+                         "[pairs, 7, 3, K]: every frame at the same K pixel positions, a fixed seeded sample, <= 32 MiB; rank 0's pairs).  "
+                         "The last timed step then also copies its frames on the device")
     args = ap.parse_args()
+    if args.dump_outputs and (args.mode != "infer" or args.stub):
+        ap.error("--dump-outputs: the inference path (--mode infer, no --stub) only")
+    if args.modes is None:
+        args.modes = FULL_MODES if args.full else ""
+    if args.mode == "infer" and not args.full:
+        args.no_configs = args.no_cpu_baseline = args.no_io = args.no_kernel_timers = args.no_clock_probes = True
     # the CPU-oracle legs (parity, cpu_baseline; world 1 only) run on the host: at most the 16 CPUs a one-GPU job owns on a GPU box - torch's
     # default of one thread per visible core oversubscribes that share 8x (cpu_baseline() sweeps the count itself and reports what it used)
     torch.set_num_threads(max(1, min(16, usable_cpus())))

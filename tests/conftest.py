@@ -57,6 +57,11 @@ def golden():
     def load(name):
         if name not in cache:
             cache[name] = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+            # a fixture too large for one archive continues in <name>.part2.npz, <name>.part3.npz, ... (make_golden.save_fixture)
+            i = 2
+            while os.path.exists(os.path.join(GOLDEN, "%s.part%d.npz" % (name, i))):
+                cache[name].update(np.load(os.path.join(GOLDEN, "%s.part%d.npz" % (name, i))))
+                i += 1
         return cache[name]
 
     return load

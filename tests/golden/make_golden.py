@@ -26,6 +26,24 @@ sys.path.insert(0, os.path.join(ROOT, "superslomo-videointerpolation-pytorch_amd
 from ssm_amd.weights import normalize_and_pad, synthetic_frames_u8, synthetic_state_dict  # noqa: E402
 
 
+def save_fixture(name, arrays, limit=768 << 10):
+    """np.savez_compressed into HERE/<name>.npz, continued in <name>.part2.npz, ... so that no archive passes 1 MiB: members in
+    order, a new part where the next one would take the current part past `limit` compressed bytes (tests/conftest.py merges them)."""
+    import io
+    parts, cur, size = [], {}, 0
+    for k, v in arrays.items():
+        buf = io.BytesIO()
+        np.savez_compressed(buf, v=v)
+        if cur and size + buf.tell() > limit:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += buf.tell()
+    parts.append(cur)
+    for i, p in enumerate(parts):
+        np.savez_compressed(os.path.join(HERE, name + (".npz" if i == 0 else ".part%d.npz" % (i + 1))), **p)
+
+
 def import_reference():
     for name, attrs in (("models.CLSTM", {}), ("models.CLSTM.convgru", {"ConvBGRU": None}),
                         ("models.CLSTM.convlstm", {"ConvBLSTM": None})):
@@ -153,7 +171,7 @@ def main():
         in16 = s2.compute_inputs(img6, flow4, t)
         ops["fi_in16_%d" % i] = npy(in16)
         ops["fi_img_%d" % i] = npy(s2.compute_output_image(img6, in16, out5, t))
-    np.savez_compressed(os.path.join(HERE, "ops.npz"), **ops)
+    save_fixture("ops", ops)
 
     # ---------------- stage fixtures (64x64) -------------------------------
     st = {}
@@ -211,7 +229,7 @@ def main():
     for i in (1, 4, 7):
         img, _ = fm(xc, torch.full((1, 1, 1, 1, 1), i / 8.0), inference_mode=True)
         full["c_img_t%d" % i] = npy(img)
-    np.savez_compressed(os.path.join(HERE, "fullmodel_small.npz"), **full)
+    save_fixture("fullmodel_small", full)
 
     # ---------------- config 1: 256x256, t=0.5 ------------------------------
     c1 = {}
