@@ -525,6 +525,24 @@ int ssm_frames_from_u8_fwd(const unsigned char *frames_hwc, ssm_view out, int N,
 int ssm_frames_to_u8_fwd(ssm_view in, unsigned char *frames_hwc, int N, int H, int W, int top, int left,
                          const float *mean3, const float *std3, int mode, void *stream);
 
+/* ---- evaluator metrics of uint8 frames (an exception to the fp32-tensor convention: uint8 in, float64 out) ----
+ * ssm_frame_metrics_fwd: per frame of two contiguous [N,H,W,3] uint8 stacks (what ssm_frames_to_u8_fwd
+ *   writes) the sums behind Evaluator.eval_single_image (scripts/evaluate_interpolation_results.py:101-108:
+ *   skimage's peak_signal_noise_ratio, structural_similarity(..., multichannel=True, gaussian_weights=True)
+ *   and the interpolation error).  out is a DEVICE array [N][5] of float64:
+ *     out[n][0] = SSE, the sum of squared differences over all H*W*3 values (an exact integer)
+ *     out[n][1] = IE sum, sum over pixels of sqrt(sum_c d_c^2)
+ *     out[n][2..4] = SSIM sum of channel 0, 1, 2 over the cropped interior [5,H-5) x [5,W-5): Gaussian
+ *       sigma 1.5, 11 taps, scipy mode="reflect", sample covariance (121/120), K1 0.01, K2 0.03, range 255
+ *   PSNR = 10 log10(255^2 / (SSE / (H*W*3))), SSIM = mean_c SSIM sum / ((H-10)(W-10)), IE = IE sum / (H*W).
+ *   fp64 throughout; two launches, no atomics: bitwise repeatable, and frame n's sums do not depend on N.
+ *   The workspace (device memory, ssm_frame_metrics_workspace_bytes(N, H, W) bytes at least) is the caller's.
+ *   SSM_E_ARG for null pointers, N < 1, H or W < 11 (skimage's smallest image for its window) or a short
+ *   workspace. */
+size_t ssm_frame_metrics_workspace_bytes(int N, int H, int W);
+int ssm_frame_metrics_fwd(const unsigned char *target_hwc, const unsigned char *output_hwc, int N, int H, int W,
+                          void *workspace, size_t workspace_bytes, double *out, void *stream);
+
 /* ---- backward kernels of the training step (fp32 planes; BASELINE config 3) ------------------------------
  * The data gradient of a convolution is ssm_conv2d_fwd on the transposed, spatially flipped filter.
  * ssm_lrelu_bwd           dz = (dy + 1/4 dpool[y/2][x/2]) * (y > 0 ? 1 : slope)   (dy or dpool may be NULL views;

@@ -6,11 +6,13 @@ stage 1 once per pair), crop/denormalise/quantise (HIP kernels in ssm_amd.frames
 PSNR and IE follow the reference's call sites exactly.  SSIM restates skimage's `structural_similarity(...,
 multichannel=True, gaussian_weights=True)` (Wang et al. 2004 with skimage's conventions: sigma 1.5, 11x11 support,
 sample covariance, border crop); skimage is not installed in this image, so SSIM is NOT pinned against it.
+`frame_metrics` computes the same three metrics on the GPU (csrc/ssm_metrics.hip); the host functions stay the yardstick.
 """
 import numpy as np
 import torch
 
 from . import frames as F
+from . import hipbind as hb
 
 
 def sliding_window(n_images, n_frames=2, is_fps_240=False):
@@ -137,6 +139,50 @@ def eval_single_image(target_u8, output_u8):
     return psnr(target_u8, output_u8), ssim(target_u8, output_u8), interpolation_error(target_u8, output_u8)
 
 
+# ---- the same three metrics on the device (csrc/ssm_metrics.hip) --------------------------------------------------------------------
+
+def frame_metric_sums(target_u8, output_u8):
+    """Per-frame sums of two device uint8 stacks [N,H,W,3] (ssm_frame_metrics_fwd): float64 [N,5] on the device = (SSE, IE sum,
+    SSIM sum of channel 0, 1, 2 over the cropped interior).  Launched on the current stream; no synchronisation."""
+    for t in (target_u8, output_u8):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 4 and t.shape[3] == 3):
+            raise RuntimeError("frames must be [N,H,W,3] uint8 tensors on the GPU; got %s %s on %s"
+                               % (getattr(t, "dtype", type(t)), tuple(getattr(t, "shape", ())), getattr(t, "device", "?")))
+    if target_u8.shape != output_u8.shape or target_u8.device != output_u8.device:
+        raise RuntimeError("target %s on %s and output %s on %s differ" % (tuple(target_u8.shape), target_u8.device,
+                                                                          tuple(output_u8.shape), output_u8.device))
+    tgt, out = target_u8.contiguous(), output_u8.contiguous()
+    n, h, w, _ = tgt.shape
+    lib = hb.load()
+    with torch.cuda.device(tgt.device):
+        nbytes = lib.ssm_frame_metrics_workspace_bytes(n, h, w)
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=tgt.device)
+        sums = torch.empty(n, 5, dtype=torch.float64, device=tgt.device)
+        hb.check(lib.ssm_frame_metrics_fwd(tgt.data_ptr(), out.data_ptr(), n, h, w, ws.data_ptr(), nbytes, sums.data_ptr(),
+                                           hb.stream_ptr()))
+    return sums
+
+
+def metrics_from_sums(sums, h, w):
+    """[N,5] float64 sums (frame_metric_sums) of H x W frames -> [N,3] float64 (PSNR, SSIM, IE) in the order of eval_single_image,
+    formed with the host functions' own float64 expressions (the SSE is an exact integer, so PSNR equals psnr() bit for bit)."""
+    sums = np.asarray(sums, dtype=np.float64)
+    res = np.empty((sums.shape[0], 3), dtype=np.float64)
+    for k, (sse, ie, s0, s1, s2) in enumerate(sums):
+        err = sse / np.float64(h * w * 3)
+        res[k, 0] = float("inf") if err == 0 else 10.0 * np.log10(255.0 ** 2 / err)
+        n_in = np.float64((h - 10) * (w - 10))
+        res[k, 1] = np.mean([s0 / n_in, s1 / n_in, s2 / n_in])
+        res[k, 2] = ie / np.float64(h * w)
+    return res
+
+
+def frame_metrics(target_u8, output_u8):
+    """eval_single_image over two device uint8 stacks [N,H,W,3] on the GPU: host float64 array [N,3] of (PSNR, SSIM, IE)."""
+    _, h, w, _ = target_u8.shape
+    return metrics_from_sums(frame_metric_sums(target_u8, output_u8).cpu().numpy(), h, w)
+
+
 @torch.no_grad()
 def interpolate_clip(model, frames_u8, upsample_rate=8, cfg=None, pad_before_norm=True, saturate=False, n_streams=2):
     """The visualiser's loop (scripts/visualize_interpolation.py:105-221) for N_FRAMES=2 on device-resident uint8
@@ -166,11 +212,14 @@ class Evaluator:
     (:213-244, hoisted - stage 1 once per window), trimming of the last window to its valid targets (:110-141), crop ->
     denormalise -> uint8 (:143-163,192-202; one HIP kernel), PSNR / IE / SSIM per frame (:101-108,165-190), running lists and
     their means (:246-278).  `samples`: an iterable of (input [B,N,3,Hp,Wp], target [B,T,3,Hp,Wp], n_avail[B]) - the reference
-    builds it from its dataset classes (file readers: out of scope); `clip_samples` builds it from a device-resident clip."""
+    builds it from its dataset classes (file readers: out of scope); `clip_samples` builds it from a device-resident clip.
+    metrics="host" scores with eval_single_image on host copies of the frames (the reference's path); "device" keeps the uint8 frames
+    on the GPU and scores them with frame_metrics (csrc/ssm_metrics.hip), copying back [frames, 3] float64 per batch."""
 
-    def __init__(self, cfg, model, h_in, w_in, dataset="ADOBE"):
+    def __init__(self, cfg, model, h_in, w_in, dataset="ADOBE", metrics="host"):
         assert dataset in ["SINTEL_HFR", "ADOBE", "SLOWFLOW", "VIMEO"], "Invalid dataset."
-        self.cfg, self.model, self.dataset = cfg, model, dataset
+        assert metrics in ("host", "device"), "metrics must be 'host' or 'device', got %r" % (metrics,)
+        self.cfg, self.model, self.dataset, self.metrics = cfg, model, dataset, metrics
         self.video_PSNR, self.video_IE, self.video_SSIM = [], [], []
         (self.H_REF, self.W_REF), (self.H_START, self.W_START) = F.padded_dims(h_in, w_in)
         self.H_IN, self.W_IN = h_in, w_in
@@ -205,6 +254,11 @@ class Evaluator:
         return F.frames_to_u8(batch, self.H_IN, self.W_IN, self.cfg, saturate=False).cpu().numpy()
 
     def get_scores(self, output_batch, target_batch):
+        if self.metrics == "device":
+            out = F.frames_to_u8(output_batch, self.H_IN, self.W_IN, self.cfg, saturate=False)
+            tgt = F.frames_to_u8(target_batch, self.H_IN, self.W_IN, self.cfg, saturate=False)
+            m = frame_metrics(tgt, out)
+            return [float(v) for v in m[:, 0]], [float(v) for v in m[:, 2]], [float(v) for v in m[:, 1]]
         out, tgt = self.convert_tensor_to_numpy_image(output_batch), self.convert_tensor_to_numpy_image(target_batch)
         ps, ies, ss = [], [], []
         for k in range(out.shape[0]):
