@@ -2,12 +2,12 @@
 """Build-time fence (called by check_isa.sh on the disassembly of every object): on gfx9 a scalar register written by a VECTOR
 instruction (v_readfirstlane_b32 - what the compiler emits when a wave-uniform value lives in a vector register) needs 5 wait states
 before a vector-memory instruction uses it as its scalar base.  The compiler's hazard recogniser covers its own instructions but not
-the global_load_lds / global_store instructions of this library's asm statements; one such pair sent stores to a stale address
-(memory access fault) when a register-allocation change moved a store base into vector registers.  The asm statements whose base may
-come from a readfirstlane carry their own s_nop; this script fails the build if any vector-memory instruction still reads a scalar
-register within 5 wait states of the v_readfirstlane that wrote it.
+the global_load_lds / global_store instructions of this library's asm statements (all of them in ssm_device.h: lds_dma16, store_sbase,
+store_sbase_nop); one such pair sent stores to a stale address (memory access fault) when a register-allocation change moved a store
+base into vector registers.  The statements carry no wait states for this (their bases are meant to be formed on the scalar unit); this
+script fails the build if any vector-memory instruction reads a scalar register within 5 wait states of the v_readfirstlane that wrote it.
 Second rule (gfx940+): a vector-memory store of more than 64 bits (dwordx3 / dwordx4) followed by a VALU write of its data registers needs
-2 wait states; the epilogues' stores are opaque asm statements, so the compiler does not see the pair either.
+2 wait states; the epilogues' stores are opaque asm statements, so the compiler does not see the pair either (store_sbase_nop carries them).
 usage: llvm-objdump -d dev.co | check_hazard.py <name>"""
 import re
 import sys

@@ -13,6 +13,7 @@
 //   inputs_bwd      adjoint of compute_inputs (flow approximation + the two warps wrt their flows), fused with the
 //                   two stage-1 warp-loss terms
 #include "ssm_common.h"
+#include "ssm_device.h"
 
 #include <cstdlib>
 
@@ -76,13 +77,6 @@ __global__ __launch_bounds__(256) void lrelu_bwd_flat_kernel(ssm_view dy, ssm_vi
 
 // lrelu_bwd that ALSO writes dZ in the Q8 operand form (include/ssm_hip.h) for the data-gradient convolution on the fp16 + fp8
 // matrix path; a thread's 4 channels are half of an 8-channel group.
-typedef _Float16 bh4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ int bwd_pack4_fp8(float a, float b, float c, float d) {
-    const float lim = 448.0f;
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(a, -lim, lim), __builtin_amdgcn_fmed3f(b, -lim, lim), 0, false);
-    return __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(c, -lim, lim), __builtin_amdgcn_fmed3f(d, -lim, lim), w, true);
-}
-
 __global__ __launch_bounds__(256) void lrelu_bwd_q8_kernel(ssm_view dy, ssm_view dpool, ssm_view yv, ssm_view dz, ssm_hview dq, int C,
                                                            int H, int W, float slope, int has_act, int cgroups) {
     const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
@@ -103,14 +97,14 @@ __global__ __launch_bounds__(256) void lrelu_bwd_q8_kernel(ssm_view dy, ssm_view
     }
     const int grp = cg >> 1, half = cg & 1, odd = grp & 1;
     char *rec = (char *)dq.ptr + ((long long)b * dq.sb + (long long)grp * dq.sg + (long long)y * dq.sh + x) * 16;
-    bh4 hi;
+    h4 hi;
 #pragma unroll
     for (int i = 0; i < 4; ++i) hi[i] = (_Float16)v[i];
-    *reinterpret_cast<bh4 *>(rec + half * 8) = hi;
+    *reinterpret_cast<h4 *>(rec + half * 8) = hi;
     char *even_rec = rec - odd * dq.sg * 16 + dq.sp * 16;
-    *reinterpret_cast<int *>(even_rec + odd * 8 + half * 4) = bwd_pack4_fp8(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<int *>(even_rec + odd * 8 + half * 4) = pack4_fp8(v[0], v[1], v[2], v[3]);
     *reinterpret_cast<int *>(even_rec + dq.sg * 16 + odd * 8 + half * 4) =
-        bwd_pack4_fp8((v[0] - (float)hi[0]) * 2048.f, (v[1] - (float)hi[1]) * 2048.f, (v[2] - (float)hi[2]) * 2048.f, (v[3] - (float)hi[3]) * 2048.f);
+        pack4_fp8((v[0] - (float)hi[0]) * 2048.f, (v[1] - (float)hi[1]) * 2048.f, (v[2] - (float)hi[2]) * 2048.f, (v[3] - (float)hi[3]) * 2048.f);
 }
 
 __global__ __launch_bounds__(256) void bias_grad_kernel(ssm_view dz, float *__restrict__ db, int B, int H, int W) {
@@ -148,9 +142,6 @@ __global__ __launch_bounds__(256) void bias_grad_kernel(ssm_view dz, float *__re
 // the first version recomputed that index arithmetic every step - 5-11 vector instructions per MFMA on the training step's layers
 // (tools/pmc_wgrad.sh), and a vector instruction beside the fp32 MFMA costs ~3 matrix cycles (profiles/DESIGN_history_r1-r3.md 3.2g).  SEG x RR = 64x2,
 // 32x4 or 16x8 by the map's width: the deep layers' 22- and 11-pixel rows fill a step with more rows instead of padding.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float wg_f4 __attribute__((ext_vector_type(4)));
-
 template <int KS, int XC, int NTC, int SEG, int RR>
 __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(ssm_view x, ssm_view dz, float *__restrict__ dw, float *__restrict__ db, int B,
                                                             int Cin, int Cout, int H, int W, int cin_total, int ci_offset) {
@@ -228,7 +219,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(ssm_view x, ssm_view
 
     const int rgroups = (H + RR - 1) / RR, nseg = (W + SEG - 1) / SEG;
     const int nsteps_total = B * rgroups * nseg;     // staging steps of the whole image batch; this workgroup takes every gridDim.z-th
-    wg_f4 pdz[LDZ], px[LX];
+    f32x4 pdz[LDZ], px[LX];
     auto decode = [&](int s, int &b, int &y, int &xs) {
         const int rp = s / nseg;
         xs = (s - rp * nseg) * SEG;
@@ -242,11 +233,11 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(ssm_view x, ssm_view
         const float *xb = xb0 + (long long)b * x.sb + (long long)y * x.sh + xs;
 #pragma unroll
         for (int i = 0; i < LDZ; ++i) {
-            wg_f4 v = {0.f, 0.f, 0.f, 0.f};
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
             const int rr = dzq[i] & 255, xq4 = dzq[i] >> 8;
             const int left = W - xs - xq4;            // pixels of this float4 inside the row
             if (dzq[i] >= 0 && y + rr < H && left > 0) {
-                v = *reinterpret_cast<const wg_f4 *>(dzb + dzo[i]);
+                v = *reinterpret_cast<const f32x4 *>(dzb + dzo[i]);
                 if (left < 4) {                       // zero tail: those products vanish
                     if (left < 2) v[1] = 0.f;
                     if (left < 3) v[2] = 0.f;
@@ -257,16 +248,16 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(ssm_view x, ssm_view
         }
 #pragma unroll
         for (int i = 0; i < LX; ++i) {
-            wg_f4 v = {0.f, 0.f, 0.f, 0.f};
+            f32x4 v = {0.f, 0.f, 0.f, 0.f};
             // rows / columns outside the image come from the padded-plane zero frame; columns past the frame only meet zeroed dZ
-            if (xq[i] >= 0 && y + xq[i] - PAD < H + PAD) v = *reinterpret_cast<const wg_f4 *>(xb + xo[i]);
+            if (xq[i] >= 0 && y + xq[i] - PAD < H + PAD) v = *reinterpret_cast<const f32x4 *>(xb + xo[i]);
             px[i] = v;
         }
     };
     auto commit = [&]() {
 #pragma unroll
         for (int i = 0; i < LDZ; ++i)
-            if (dzl[i] >= 0) *reinterpret_cast<wg_f4 *>(sdz + dzl[i]) = pdz[i];
+            if (dzl[i] >= 0) *reinterpret_cast<f32x4 *>(sdz + dzl[i]) = pdz[i];
 #pragma unroll
         for (int i = 0; i < LX; ++i)
             if (xl[i] >= 0) {
@@ -278,7 +269,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(ssm_view x, ssm_view
             }
     };
 
-    const wg_f4 *sdz4 = reinterpret_cast<const wg_f4 *>(sdz);
+    const f32x4 *sdz4 = reinterpret_cast<const f32x4 *>(sdz);
     const int aBase = (l31 * DS) / 4 + half;          // quad index of this lane's A values of pixel group 0 (row n*32 + l31)
     int s = blockIdx.z;
     if (s < nsteps_total) prefetch(s);
@@ -293,9 +284,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(ssm_view x, ssm_view
 #pragma unroll
         for (int rr = 0; rr < RR; ++rr) {
             const float *bp0 = sx + colOff[0] + rr * rstride[0], *bp1 = sx + colOff[1] + rr * rstride[1];
-            const wg_f4 *ap = sdz4 + aBase + (rr * SEG) / 4;
+            const f32x4 *ap = sdz4 + aBase + (rr * SEG) / 4;
             for (int g = 0; g < ngrp; ++g) {
-                wg_f4 av[NTC];
+                f32x4 av[NTC];
 #pragma unroll
                 for (int n = 0; n < NTC; ++n) av[n] = ap[n * (32 * DS / 4) + 2 * g];
                 float bv[CT][4];
@@ -348,20 +339,17 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(ssm_view x, ssm_view
 // step s+1 are issued before the MFMAs of step s).  Image rows are split over gridDim.z; partial sums are added with fp32 atomics.
 typedef __bf16 wg_bf8 __attribute__((ext_vector_type(8)));
 typedef __bf16 wg_bf2 __attribute__((ext_vector_type(2)));
-typedef float wg_f2 __attribute__((ext_vector_type(2)));
-typedef int wg_i4 __attribute__((ext_vector_type(4)));
-typedef int wg_i2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ unsigned wg_pk_bf16(float a, float b) {        // low half = bf16(a), high half = bf16(b), round to nearest even
-    const wg_f2 v = {a, b};
+    const f32x2 v = {a, b};
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, wg_bf2));
 }
 
 // 4 fp32 -> hi (2 dwords) and lo (2 dwords)
-__device__ __forceinline__ void wg_split4(const float4 &v, wg_i2 &hi, wg_i2 &lo) {
+__device__ __forceinline__ void wg_split4(const float4 &v, i32x2 &hi, i32x2 &lo) {
     const unsigned h0 = wg_pk_bf16(v.x, v.y), h1 = wg_pk_bf16(v.z, v.w);
-    hi = wg_i2{(int)h0, (int)h1};
-    lo = wg_i2{(int)wg_pk_bf16(v.x - __uint_as_float(h0 << 16), v.y - __uint_as_float(h0 & 0xffff0000u)),
+    hi = i32x2{(int)h0, (int)h1};
+    lo = i32x2{(int)wg_pk_bf16(v.x - __uint_as_float(h0 << 16), v.y - __uint_as_float(h0 & 0xffff0000u)),
                (int)wg_pk_bf16(v.z - __uint_as_float(h1 << 16), v.w - __uint_as_float(h1 & 0xffff0000u))};
 }
 
@@ -428,11 +416,11 @@ __global__ __launch_bounds__(256, (KS == 7 && SEG == 128) ? 1 : 2) void wgrad_bf
     };
     auto store_x4 = [&](int slot, int f, const float4 &v) {
         const int c = f / (XE / 4), x4 = f - c * (XE / 4);
-        wg_i2 hi, lo;
+        i32x2 hi, lo;
         wg_split4(v, hi, lo);
         const int off = (slot * CIT + c) * XB + 8 * x4;
-        *reinterpret_cast<wg_i2 *>(s_xh + off) = hi;
-        *reinterpret_cast<wg_i2 *>(s_xl + off) = lo;
+        *reinterpret_cast<i32x2 *>(s_xh + off) = hi;
+        *reinterpret_cast<i32x2 *>(s_xl + off) = lo;
     };
     float4 pdz[LDZ], px[LX];
     auto prefetch = [&](int s) {
@@ -471,10 +459,10 @@ __global__ __launch_bounds__(256, (KS == 7 && SEG == 128) ? 1 : 2) void wgrad_bf
             const int f = tid + 256 * i;
             if (f < NDZ4) {
                 const int c = f / (SEG / 4), x4 = f - c * (SEG / 4);
-                wg_i2 hi, lo;
+                i32x2 hi, lo;
                 wg_split4(pdz[i], hi, lo);
-                *reinterpret_cast<wg_i2 *>(s_dzh + c * DZB + 8 * x4) = hi;
-                *reinterpret_cast<wg_i2 *>(s_dzl + c * DZB + 8 * x4) = lo;
+                *reinterpret_cast<i32x2 *>(s_dzh + c * DZB + 8 * x4) = hi;
+                *reinterpret_cast<i32x2 *>(s_dzl + c * DZB + 8 * x4) = lo;
             }
         }
         const int slot = (y + ky0 + TY - 1 - P + 3) % TY;
@@ -507,8 +495,8 @@ __global__ __launch_bounds__(256, (KS == 7 && SEG == 128) ? 1 : 2) void wgrad_bf
         for (int j = wk; j < nk; j += WKN) {
             const int q = 16 * j + 8 * half;               // this lane's 8 pixels: columns xs+q .. xs+q+7
             const int arow = (wa * 32 + l31) * DZB + 2 * q;
-            const wg_i4 ah = *reinterpret_cast<const wg_i4 *>(s_dzh + arow);
-            const wg_i4 al = *reinterpret_cast<const wg_i4 *>(s_dzl + arow);
+            const i32x4 ah = *reinterpret_cast<const i32x4 *>(s_dzh + arow);
+            const i32x4 al = *reinterpret_cast<const i32x4 *>(s_dzl + arow);
             const wg_bf8 Ah = __builtin_bit_cast(wg_bf8, ah), Al = __builtin_bit_cast(wg_bf8, al);
 #pragma unroll
             for (int a = 0; a < TY; ++a) {
@@ -516,9 +504,9 @@ __global__ __launch_bounds__(256, (KS == 7 && SEG == 128) ? 1 : 2) void wgrad_bf
                 const int xrow = (slot * CIT + wb * 32 + l31) * XB + 2 * (q + 8);      // staged column 0 = image column xs-8
                 int wh[8], wl[8];                          // window: pixels q-4 .. q+11 of this lane's channel, 2 per dword
                 {
-                    const wg_i2 h0 = *reinterpret_cast<const wg_i2 *>(s_xh + xrow - 8), l0 = *reinterpret_cast<const wg_i2 *>(s_xl + xrow - 8);
-                    const wg_i4 h1 = *reinterpret_cast<const wg_i4 *>(s_xh + xrow), l1 = *reinterpret_cast<const wg_i4 *>(s_xl + xrow);
-                    const wg_i2 h2 = *reinterpret_cast<const wg_i2 *>(s_xh + xrow + 16), l2 = *reinterpret_cast<const wg_i2 *>(s_xl + xrow + 16);
+                    const i32x2 h0 = *reinterpret_cast<const i32x2 *>(s_xh + xrow - 8), l0 = *reinterpret_cast<const i32x2 *>(s_xl + xrow - 8);
+                    const i32x4 h1 = *reinterpret_cast<const i32x4 *>(s_xh + xrow), l1 = *reinterpret_cast<const i32x4 *>(s_xl + xrow);
+                    const i32x2 h2 = *reinterpret_cast<const i32x2 *>(s_xh + xrow + 16), l2 = *reinterpret_cast<const i32x2 *>(s_xl + xrow + 16);
                     wh[0] = h0[0]; wh[1] = h0[1]; wh[2] = h1[0]; wh[3] = h1[1]; wh[4] = h1[2]; wh[5] = h1[3]; wh[6] = h2[0]; wh[7] = h2[1];
                     wl[0] = l0[0]; wl[1] = l0[1]; wl[2] = l1[0]; wl[3] = l1[1]; wl[4] = l1[2]; wl[5] = l1[3]; wl[6] = l2[0]; wl[7] = l2[1];
                 }
@@ -526,10 +514,10 @@ __global__ __launch_bounds__(256, (KS == 7 && SEG == 128) ? 1 : 2) void wgrad_bf
                 for (int t = 0; t < KS; ++t) {
                     const int idx = t - P + 4;             // window element of the first pixel this tap needs (compile-time after unrolling)
                     const int d = idx >> 1;
-                    wg_i4 bh, bl;
+                    i32x4 bh, bl;
                     if ((idx & 1) == 0) {
-                        bh = wg_i4{wh[d], wh[d + 1], wh[d + 2], wh[d + 3]};
-                        bl = wg_i4{wl[d], wl[d + 1], wl[d + 2], wl[d + 3]};
+                        bh = i32x4{wh[d], wh[d + 1], wh[d + 2], wh[d + 3]};
+                        bl = i32x4{wl[d], wl[d + 1], wl[d + 2], wl[d + 3]};
                     } else {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {

@@ -33,13 +33,12 @@
 // meanwhile), and the concatenated, upsampled tensor - the largest activation of
 // every decoder level - never touches HBM.
 #include "ssm_common.h"
+#include "ssm_device.h"
 
 #include <atomic>
 #include <mutex>
 #include <type_traits>
 #include <cstdlib>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -116,10 +115,6 @@ struct Lds {
     static constexpr int BYTES = (2 * STAGE + (UPS ? C::PSZ : 0)) * 4;
     static_assert(BYTES <= 65536, "LDS budget (two workgroups per CU)");
 };
-
-#define SSM_GLDS16(gp, lp)                                                                      \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gp),      \
-                                     (__attribute__((address_space(3))) void *)(lp), 16, 0, 0)
 
 // SPLIT: the split-K instantiation (ssm_conv2d_splitk_fwd; compiled for the tile configurations of CONV_SPLIT_OK only - the large-tile
 // configurations sit at the register cap, and the split's three extra scalars tip them into scratch)
@@ -201,8 +196,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p) {
                 if (SSM_DMA_SADDR && (pure_w || pure_p)) {
                     const float *base = pure_w ? wb : pb;
                     const unsigned m0v = lsb + (unsigned)g * 1024u;
-                    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                                 :: "v"(off[k] * 4), "s"(base), "s"(m0v) : "memory", "m0");
+                    lds_dma16(base, off[k] * 4, m0v);
                 } else {
                     const float *gp = (isw[k] ? wb : pb) + off[k];
                     SSM_GLDS16(gp, ls + g * 256);
@@ -252,7 +246,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p) {
     issue(0, 0);
     for (int ch = 0; ch < nchunks; ++ch) {
         // chunk ch has landed for every wave; every wave is done reading chunk ch-1
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();
         // the DMA of chunk ch+1 is issued from inside the MFMA loop below, one instruction per macro-step (SSM_DMA_SPREAD): the
         // requests do not hit the memory system as one burst behind the barrier, and the first MFMA does not wait for their issue
@@ -280,7 +274,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p) {
             int tl = tid;
             // big tiles (several channels per thread) recompute the geometry per chunk: hoisted out of the k-loop it would hold ~12
             // VGPRs across the MFMAs = one resident workgroup less per CU; the small tiles have the registers and let it hoist
-            if constexpr (CPT > 1) asm volatile("" : "+v"(tl));
+            if constexpr (CPT > 1) pin(tl);
             const int cg = tl / NPOS, pos = tl - cg * NPOS;
             if (cg < CG) {
                 const int ly0 = y0 / 2 - 1, lx0 = x0 / 2 - 1;
@@ -406,9 +400,6 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p) {
     // (BYTE offsets, < 2^31: one batch entry of a 32-cout block; the stores use the saddr form: 64-bit SGPR base + 32-bit VGPR offset)
     const unsigned pbase = 4u * ((unsigned)(4 * half) * (unsigned)p.dsc + (unsigned)ybase * (unsigned)p.dsh + (unsigned)xbase);
     const unsigned qbase = 4u * ((unsigned)(4 * half) * (unsigned)p.psc + (unsigned)(ybase >> 1) * (unsigned)p.psh + (unsigned)(xbase >> 1));
-    auto st = [](const float *base, unsigned off_bytes, float val) {
-        asm volatile("global_store_dword %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-    };
     const bool even = (GW == 32) ? !(l31 & 1) : (!(gx & 1) && !(gy & 1));      // the lane that writes a 2x2 mean
     bool pok[MT];
 #pragma unroll
@@ -428,7 +419,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p) {
                     const float t = acc[n][m][r];
                     v[m] = fmaxf(t, t * sl);
                     float *bpm = bp + ((m / C::MTX) * GH) * p.dsh + (m % C::MTX) * GW;        // uniform
-                    if (pok[m] && cok) st(bpm, pbase, v[m]);
+                    if (pok[m] && cok) store_sbase(bpm, pbase, v[m]);
                 }
                 if (poolb) {
                     float *qp = poolb + (long long)cu * p.psc;
@@ -441,7 +432,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p) {
                                     float sm = v[my * C::MTX + mx] + v[(my + 1) * C::MTX + mx];
                                     sm += __shfl_xor(sm, 1);
                                     float *qpm = qp + (my / 2) * p.psh + mx * (GW / 2);
-                                    if (pok[my * C::MTX + mx] && even && cok) st(qpm, qbase, sm * 0.25f);
+                                    if (pok[my * C::MTX + mx] && even && cok) store_sbase(qpm, qbase, sm * 0.25f);
                                 }
                         }
                     } else {   // 8x4 group: the 2x2 neighbours are lanes ^GW (y) and ^1 (x); same association as the 32x1 form
@@ -450,7 +441,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p) {
                             float sm = v[m] + __shfl_xor(v[m], GW);
                             sm += __shfl_xor(sm, 1);
                             float *qpm = qp + ((m / C::MTX) * GH / 2) * p.psh + (m % C::MTX) * (GW / 2);
-                            if (pok[m] && even && cok) st(qpm, qbase, sm * 0.25f);
+                            if (pok[m] && even && cok) store_sbase(qpm, qbase, sm * 0.25f);
                         }
                     }
                 }

@@ -19,6 +19,7 @@
 // [KYS*k taps][2][2][BN] x 16 B per iteration, both by LDS-DMA; the next chunk's patch is
 // fetched in slices spread over the current chunk's iterations.  One barrier per iteration.
 #include "ssm_common.h"
+#include "ssm_device.h"
 
 #include <mutex>
 #include <set>
@@ -36,10 +37,6 @@
 #ifndef SSM_C16_ABL      // diagnostics (wrong results): 1 = no DMA in the loop, 2 = also no barriers, 3 = also no LDS reads
 #define SSM_C16_ABL 0
 #endif
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
@@ -120,10 +117,6 @@ struct Cfg16 {
     static_assert(WST_PIECES % 64 == 0, "filter stage is whole DMA instructions");
 };
 
-#define SSM_GLDS16B(gp, lp)                                                                      \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gp),       \
-                                     (__attribute__((address_space(3))) void *)(lp), 16, 0, 0)
-
 __device__ __forceinline__ void hi_store(char *plane_hi, float v0, float v1, float v2, float v3) {          // mode FAST: the hi plane only
     h4 hi;
     hi[0] = (_Float16)v0; hi[1] = (_Float16)v1; hi[2] = (_Float16)v2; hi[3] = (_Float16)v3;
@@ -140,13 +133,6 @@ __device__ __forceinline__ void split_store(char *plane_hi, long long sp_bytes, 
 }
 
 // ---- Q8 layout: plane 1 of a pixel group holds [8 x fp8(x) | 8 x fp8((x - fp16(x)) * 2^11)] instead of 8 x fp16(lo) ----
-__device__ __forceinline__ float clamp448(float v) { return __builtin_amdgcn_fmed3f(v, -448.0f, 448.0f); }      // e4m3fn: beyond 448 -> NaN
-
-__device__ __forceinline__ int pack4_fp8(float a, float b, float c, float d) {
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(clamp448(a), clamp448(b), 0, false);
-    return __builtin_amdgcn_cvt_pk_fp8_f32(clamp448(c), clamp448(d), w, true);
-}
-
 // 4 consecutive channels (offset half*4 inside 8-channel group g) of one pixel.  `pix_hi` = the pixel's 16-byte record in the
 // hi plane of group g.  Second planes are shared by a PAIR of groups (16 channels = one K chunk): the even group's holds
 // [fp8(x) of the even group | fp8(x) of the odd group], the odd group's [fp8(lo*2^11) even | fp8(lo*2^11) odd], so that one
@@ -163,7 +149,6 @@ __device__ __forceinline__ void split_store_q8(char *pix_hi, long long sp_bytes,
         pack4_fp8((v0 - (float)hi[0]) * 2048.0f, (v1 - (float)hi[1]) * 2048.0f, (v2 - (float)hi[2]) * 2048.0f, (v3 - (float)hi[3]) * 2048.0f);
 }
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ float fp8_byte(int word, int i) {          // byte i of a word of four e4m3 values -> fp32
@@ -519,7 +504,7 @@ __device__ __forceinline__ void conv16_body(const Conv16Params &p, const int blk
         for (int m = 0; m < C::PM; ++m) {
             const int ii = lw + NL * m;
             const int j = m % C::NIT;
-            if (ii < C::PNI && j >= jlo && j < jhi) SSM_GLDS16B(ps + poff[m], pb + ii * 1024);
+            if (ii < C::PNI && j >= jlo && j < jhi) SSM_GLDS16(ps + poff[m], pb + ii * 1024);
         }
     };
     auto issue_w = [&](int it) {
@@ -528,7 +513,7 @@ __device__ __forceinline__ void conv16_body(const Conv16Params &p, const int blk
 #pragma unroll
         for (int m = 0; m < C::WM; ++m) {
             const int ii = lw + NL * m;
-            if (ii < C::WNI) SSM_GLDS16B(ws + m * (NL * 1024), wb + ii * 1024);
+            if (ii < C::WNI) SSM_GLDS16(ws + m * (NL * 1024), wb + ii * 1024);
         }
     };
     // Per iteration `it` (chunk ch, filter-row stage j), after the barrier that makes stage `it` visible: the loaders
@@ -551,7 +536,7 @@ __device__ __forceinline__ void conv16_body(const Conv16Params &p, const int blk
                     __syncthreads();                   // every matrix wave is done reading the previous chunk's patch
                     issue_patch(ch, 0, C::NIT);
                 }
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                wait_vmcnt<0>();
                 __syncthreads();
                 load_step(it, ch, j);
                 if (++j == C::NIT) j = 0, ++ch;
@@ -583,7 +568,7 @@ __device__ __forceinline__ void conv16_body(const Conv16Params &p, const int blk
             __syncthreads();
             if (C::NP == 0) issue_patch(ch, 0, C::NIT);
         }
-        if (C::NP == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (C::NP == 0) wait_vmcnt<0>();
         __syncthreads();
         if (C::NP == 0) load_step(it, ch, j);
         const char *pb = pbuf0 + (C::PBUFS == 2 ? (ch & 1) : 0) * C::PATCH_BYTES + j * (KYS * PW * 16);
@@ -708,7 +693,7 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void conv16_ups_kernel(const Conv16
 #pragma unroll
         for (int m = 0; m < C::RM; ++m) {
             const int ii = ew + C::NWE * m;
-            if (ii < C::RNI) SSM_GLDS16B(rs + roff[m], rb + ii * 1024);
+            if (ii < C::RNI) SSM_GLDS16(rs + roff[m], rb + ii * 1024);
         }
     };
     auto issue_w = [&](int it) {
@@ -717,7 +702,7 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void conv16_ups_kernel(const Conv16
 #pragma unroll
         for (int m = 0; m < C::WM; ++m) {
             const int ii = ew + C::NWE * m;
-            if (ii < C::WNI) SSM_GLDS16B(ws + m * (C::NWE * 1024), wb + ii * 1024);
+            if (ii < C::WNI) SSM_GLDS16(ws + m * (C::NWE * 1024), wb + ii * 1024);
         }
     };
     // Bilinear x2 of chunk ch: raw[ch&1] -> patch[ch&1].  Work unit = one 2x2 output block of 4 channels (half a
@@ -820,7 +805,7 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void conv16_ups_kernel(const Conv16
         issue_raw(0);
         if (nchunks > 1) issue_raw(1);
         issue_w(0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
     }
     __syncthreads();
     if (!is_mfma) expand(0, 0, 1);
@@ -858,7 +843,7 @@ __global__ __launch_bounds__(C::NTHREADS, 1) void conv16_ups_kernel(const Conv16
             if (it + 1 < total_it) issue_w(it + 1);
             if (j == 0 && ch + 2 < nchunks) issue_raw(ch + 2);
             if (ch + 1 < nchunks) expand(ch + 1, j, C::NIT);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
             __syncthreads();
         }
     }
@@ -1512,11 +1497,10 @@ __global__ __launch_bounds__(256) void gather_cols_kernel(ssm_hview a, int Ga, s
     const int col = r < ncols ? col0 + r : col1 + (r - ncols - 1);
     const ssm_hview &s = g < Ga ? a : bsrc;
     const int gg = g < Ga ? g : g - Ga;
-    typedef int gi4 __attribute__((ext_vector_type(4)));
     const char *sp = (const char *)s.ptr + ((long long)b * s.sb + (long long)gg * s.sg + (long long)i * s.sh + col) * 16;
     char *dp = (char *)dst.ptr + ((long long)b * dst.sb + (long long)g * dst.sg + (long long)r * dst.sh + i) * 16;
-    *reinterpret_cast<gi4 *>(dp) = *reinterpret_cast<const gi4 *>(sp);
-    *reinterpret_cast<gi4 *>(dp + dst.sp * 16) = *reinterpret_cast<const gi4 *>(sp + s.sp * 16);
+    *reinterpret_cast<i32x4 *>(dp) = *reinterpret_cast<const i32x4 *>(sp);
+    *reinterpret_cast<i32x4 *>(dp + dst.sp * 16) = *reinterpret_cast<const i32x4 *>(sp + s.sp * 16);
 }
 
 extern "C" int ssm_hl8_gather_cols(ssm_hview a, int Ga, ssm_hview b, int Gb, ssm_hview dst, int B, int H, int col0, int ncols, int col1,

@@ -5,6 +5,7 @@
 // L2/MALL (displacements are a few pixels).  Compiled with -ffp-contract=off so the
 // coordinate arithmetic rounds exactly like the reference's unfused fp32 CPU ops.
 #include "ssm_common.h"
+#include "ssm_device.h"
 
 #include <cstdlib>
 
@@ -153,10 +154,6 @@ __global__ __launch_bounds__(256) void synthesize_kernel(ssm_view img6, ssm_view
 // holds a pixel's five sums runs the synthesis arithmetic on them directly.
 // Tile 8 rows x 64 columns, 4 waves x 2 rows; per chunk of 4 input channels the [4][10][72] patch arrives by LDS-DMA
 // (double-buffered), each wave keeps the chunk's 36 x NG4 filter values in registers for both of its rows.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define SSM_GLDS16(gp, lp)                                                                      \
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gp),      \
-                                     (__attribute__((address_space(3))) void *)(lp), 16, 0, 0)
 
 struct FinalParams {
     ssm_view x;               // [B,32,H,W] padded planes
@@ -218,7 +215,7 @@ __global__ __launch_bounds__(256, 2) void final_conv_kernel(const FinalParams p)
 
     issue(0, 0);
     for (int ch = 0; ch < CIN / CK; ++ch) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();                      // chunk ch (and, first time, the filter) is in LDS; chunk ch-1 is consumed
         if (ch + 1 < CIN / CK) issue(ch + 1, (ch + 1) & 1);
         // macro-step = one filter row of one input channel (3 taps x 2 rows x NG4 MFMAs); its operands are fetched into the
@@ -336,7 +333,7 @@ __global__ __launch_bounds__(256, 4) void final_conv_valu_kernel(const FinalPara
 
     issue(0, 0);
     for (int ch = 0; ch < CIN / CK; ++ch) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();                      // chunk ch (and, first time, the filter) is in LDS; chunk ch-1 is consumed
         if (ch + 1 < CIN / CK) issue(ch + 1, (ch + 1) & 1);
         const float *sb = lds + (ch & 1) * STAGE + (RPT * wid) * PW + lane + 3;
@@ -541,8 +538,6 @@ __global__ __launch_bounds__(256) void upsample2x_cat_kernel(ssm_view a, int Ca,
 }
 
 // ---- HL8 (fp16 hi/lo, 8-channel groups) variants ------------------------------------------------------
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ const char *hp(const ssm_hview &v, int b, int g, int y, int x) {
     return (const char *)v.ptr + ((long long)b * v.sb + (long long)g * v.sg + (long long)y * v.sh + x) * 16;
 }
@@ -608,11 +603,6 @@ __global__ __launch_bounds__(256) void upsample2x_cat_hl8_kernel(ssm_hview a, in
 
 // Q8 form of a PAIR of channel groups (include/ssm_hip.h): hi planes as fp16; the even group's second plane holds the fp8 values of
 // both groups, the odd group's the fp8 (lo * 2^11) of both.
-__device__ __forceinline__ int pack4_fp8(float a, float b, float c, float d) {
-    const float lim = 448.0f;                     // e4m3fn: beyond 448 -> NaN
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(a, -lim, lim), __builtin_amdgcn_fmed3f(b, -lim, lim), 0, false);
-    return __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(c, -lim, lim), __builtin_amdgcn_fmed3f(d, -lim, lim), w, true);
-}
 
 __device__ __forceinline__ void hq8_store_pair(const ssm_hview &v, int b, int g_even, int y, int x, const float (&a)[8], const float (&c)[8]) {
     h8 ha, hc;
@@ -628,10 +618,9 @@ __device__ __forceinline__ void hq8_store_pair(const ssm_hview &v, int b, int g_
     char *d1 = d0 + v.sg * 16;
     *reinterpret_cast<h8 *>(d0) = ha;
     *reinterpret_cast<h8 *>(d1) = hc;
-    typedef int i4 __attribute__((ext_vector_type(4)));
-    *reinterpret_cast<i4 *>(d0 + v.sp * 16) = i4{pack4_fp8(a[0], a[1], a[2], a[3]), pack4_fp8(a[4], a[5], a[6], a[7]),
+    *reinterpret_cast<i32x4 *>(d0 + v.sp * 16) = i32x4{pack4_fp8(a[0], a[1], a[2], a[3]), pack4_fp8(a[4], a[5], a[6], a[7]),
                                                   pack4_fp8(c[0], c[1], c[2], c[3]), pack4_fp8(c[4], c[5], c[6], c[7])};
-    *reinterpret_cast<i4 *>(d1 + v.sp * 16) = i4{pack4_fp8(la[0], la[1], la[2], la[3]), pack4_fp8(la[4], la[5], la[6], la[7]),
+    *reinterpret_cast<i32x4 *>(d1 + v.sp * 16) = i32x4{pack4_fp8(la[0], la[1], la[2], la[3]), pack4_fp8(la[4], la[5], la[6], la[7]),
                                                   pack4_fp8(lc[0], lc[1], lc[2], lc[3]), pack4_fp8(lc[4], lc[5], lc[6], lc[7])};
 }
 

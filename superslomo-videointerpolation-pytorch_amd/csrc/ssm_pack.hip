@@ -11,6 +11,7 @@
 // ssm_amd.backward.transposed_filter materialises), read straight from the OIHW tensor; such jobs have no bias (zeros).  Every
 // element is computed by the same arithmetic as the per-layer kernels (tests/test_hip_pack_batch.py holds them bit-identical).
 #include "ssm_common.h"
+#include "ssm_device.h"
 
 #include <type_traits>
 #include "ssm_wino5_pack.h"
@@ -27,13 +28,11 @@ struct Src {          // logical filter W'(co, ci, ky, kx) of a job
     }
 };
 
-typedef float pk_f4 __attribute__((ext_vector_type(4)));
-
 // A thread produces FOUR consecutive packed elements (every form keeps 4 values of one (cout block, cin, ...) adjacent: 4 couts of the
 // direct form, the 4 frequencies of a quad in the Winograd forms) and stores them as one 16-byte piece: the filter values they share are
 // read once, and the job lookup is paid per quad.  The first version (one element per thread) spent 1.6 ms of a 20 ms training step in
 // this kernel (profiles/r7g: 4 launches of 0.41 ms).  The arithmetic per element is unchanged (bit-identical to the per-layer kernels).
-__device__ pk_f4 pack_direct4(const Src &s, const ssm_pack32_job &j, long long i) {
+__device__ f32x4 pack_direct4(const Src &s, const ssm_pack32_job &j, long long i) {
     long long r = i;
     const int n = (int)(r % j.BN);          // multiple of 4 (BN is)
     r /= j.BN;
@@ -42,7 +41,7 @@ __device__ pk_f4 pack_direct4(const Src &s, const ssm_pack32_job &j, long long i
     r /= KS2;
     const int cin = (int)(r % j.CinP);
     const int nb = (int)(r / j.CinP);
-    pk_f4 v;
+    f32x4 v;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int co = nb * j.BN + n + q;
@@ -51,7 +50,7 @@ __device__ pk_f4 pack_direct4(const Src &s, const ssm_pack32_job &j, long long i
     return v;
 }
 
-__device__ pk_f4 pack_wino_4(const Src &s, const ssm_pack32_job &j, long long i) {      // as wino_pack_kernel; i: e = 0
+__device__ f32x4 pack_wino_4(const Src &s, const ssm_pack32_job &j, long long i) {      // as wino_pack_kernel; i: e = 0
     long long r = i / 4;
     const int n = (int)(r % j.BN);
     r /= j.BN;
@@ -60,17 +59,17 @@ __device__ pk_f4 pack_wino_4(const Src &s, const ssm_pack32_job &j, long long i)
     const int cin = (int)(r % j.Cin);
     const int nb = (int)(r / j.Cin);
     const int co = nb * j.BN + n;
-    if (co >= j.Cout) return pk_f4{0.f, 0.f, 0.f, 0.f};
+    if (co >= j.Cout) return f32x4{0.f, 0.f, 0.f, 0.f};
     float row[3];      // row q of G g
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float g0 = s.at(co, cin, 0, c), g1 = s.at(co, cin, 1, c), g2 = s.at(co, cin, 2, c);
         row[c] = q == 0 ? g0 : (q == 1 ? 0.5f * (g0 + g1 + g2) : (q == 2 ? 0.5f * (g0 - g1 + g2) : g2));
     }
-    return pk_f4{row[0], 0.5f * (row[0] + row[1] + row[2]), 0.5f * (row[0] - row[1] + row[2]), row[2]};
+    return f32x4{row[0], 0.5f * (row[0] + row[1] + row[2]), 0.5f * (row[0] - row[1] + row[2]), row[2]};
 }
 
-__device__ pk_f4 pack_wino1d_4(const Src &s, const ssm_pack32_job &j, long long i) {    // as wino1d_pack_kernel; i: e = 0
+__device__ f32x4 pack_wino1d_4(const Src &s, const ssm_pack32_job &j, long long i) {    // as wino1d_pack_kernel; i: e = 0
     long long r = i / 4;
     const int n = (int)(r % j.BN);
     r /= j.BN;
@@ -81,7 +80,7 @@ __device__ pk_f4 pack_wino1d_4(const Src &s, const ssm_pack32_job &j, long long 
     const int cin = (int)(r % j.CinP);
     const int nb = (int)(r / j.CinP);
     const int co = nb * j.BN + n;
-    pk_f4 out = {0.f, 0.f, 0.f, 0.f};
+    f32x4 out = {0.f, 0.f, 0.f, 0.f};
     if (co < j.Cout && cin < j.Cin) {
         double g[7];
         for (int kx = 0; kx < j.k; ++kx) g[kx] = (double)s.at(co, cin, ky, kx);
@@ -126,7 +125,7 @@ constexpr W4G w4g_table() {
     return t;
 }
 
-__device__ pk_f4 pack_wino4_4(const Src &s, const ssm_pack32_job &j, long long idx) {   // as wino4_pack_kernel (points 0, +-5/8, +-8/5, inf); idx: e = 0
+__device__ f32x4 pack_wino4_4(const Src &s, const ssm_pack32_job &j, long long idx) {   // as wino4_pack_kernel (points 0, +-5/8, +-8/5, inf); idx: e = 0
     long long r = idx / 4;
     const int n = (int)(r % 32);
     r /= 32;
@@ -135,7 +134,7 @@ __device__ pk_f4 pack_wino4_4(const Src &s, const ssm_pack32_job &j, long long i
     const int cin = (int)(r % j.Cin);
     const int nb = (int)(r / j.Cin);
     const int co = nb * 32 + n;
-    pk_f4 out = {0.f, 0.f, 0.f, 0.f};
+    f32x4 out = {0.f, 0.f, 0.f, 0.f};
     if (co < j.Cout) {
         // G = [1 p p^2] / prod_{q != p}(p - q) per point, [0 0 1] for the point at infinity: a compile-time table (r6: every thread used to
         // evaluate it - five fp64 divisions and three more per row - for its four values; the step's repack of the F(4x4) filters took 96 us)
@@ -169,7 +168,7 @@ __global__ void pack32_batch_kernel(const ssm_pack32_job *__restrict__ jobs, int
     const long long e = i - j.first;
     const Src s{j.w, j.transposed ? j.Cin : j.Cout, j.transposed ? j.Cout : j.Cin, j.k, j.transposed};
     if (e < j.total) {
-        pk_f4 v;
+        f32x4 v;
         switch (j.algo) {
             case SSM_PACK_WINO: v = pack_wino_4(s, j, e); break;
             case SSM_PACK_WINO1D: v = pack_wino1d_4(s, j, e); break;
@@ -177,18 +176,18 @@ __global__ void pack32_batch_kernel(const ssm_pack32_job *__restrict__ jobs, int
             case SSM_PACK_WINO5: {
                 float o4[4];
                 ssm_w5_pack_quad([&](int co, int ci, int ky, int kx) { return s.at(co, ci, ky, kx); }, j.Cout, j.Cin, j.CinP, e, o4);
-                v = pk_f4{o4[0], o4[1], o4[2], o4[3]};
+                v = f32x4{o4[0], o4[1], o4[2], o4[3]};
                 break;
             }
             case SSM_PACK_WINO7: {
                 float o4[4];
                 ssm_w7_pack_quad([&](int co, int ci, int ky, int kx) { return s.at(co, ci, ky, kx); }, j.Cout, j.Cin, e, o4);
-                v = pk_f4{o4[0], o4[1], o4[2], o4[3]};
+                v = f32x4{o4[0], o4[1], o4[2], o4[3]};
                 break;
             }
             default: v = pack_direct4(s, j, e); break;
         }
-        *reinterpret_cast<pk_f4 *>(j.wp + e) = v;
+        *reinterpret_cast<f32x4 *>(j.wp + e) = v;
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q)
@@ -226,7 +225,7 @@ __global__ __launch_bounds__(256) void pack32_wino_tiles_kernel(const ssm_pack32
             const int r = idx / RL4, c4 = idx - r * RL4;
             const float *src = j.transposed ? j.w + ((long long)(cin0 + r) * j.Cout + (long long)nb * BN) * 9
                                             : j.w + ((long long)(nb * BN + r) * j.Cin + cin0) * 9;
-            reinterpret_cast<pk_f4 *>(wl)[idx] = reinterpret_cast<const pk_f4 *>(src)[c4];
+            reinterpret_cast<f32x4 *>(wl)[idx] = reinterpret_cast<const f32x4 *>(src)[c4];
         }
     };
     if (!j.transposed) stage(std::integral_constant<int, 36>{});
@@ -239,10 +238,10 @@ __global__ __launch_bounds__(256) void pack32_wino_tiles_kernel(const ssm_pack32
         for (int qd = tid; qd < 16 * 9 * nq; qd += 256) {
             const int n4 = (qd & (nq - 1)) * 4, tap = (qd >> shq) % 9, cl = (qd >> shq) / 9;
             const int tp = j.transposed ? 8 - tap : tap;
-            pk_f4 v;
+            f32x4 v;
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] = (j.transposed ? wl + (cl * BN + n4 + q) * 9 : wl + ((n4 + q) * 16 + cl) * 9)[tp];
-            *reinterpret_cast<pk_f4 *>(outd + ((long long)(cl * 9 + tap) * BN + n4)) = v;
+            *reinterpret_cast<f32x4 *>(outd + ((long long)(cl * 9 + tap) * BN + n4)) = v;
         }
         if (tl == 0)
             for (int i = tid; i < j.nbias; i += 256) j.bp[i] = (j.bias && i < j.Cout) ? j.bias[i] : 0.f;
@@ -259,7 +258,7 @@ __global__ __launch_bounds__(256) void pack32_wino_tiles_kernel(const ssm_pack32
             for (int a = 0; a < 3; ++a)
 #pragma unroll
                 for (int c = 0; c < 3; ++c) g[a][c] = (double)(j.transposed ? gl[8 - (3 * a + c)] : gl[3 * a + c]);
-            pk_f4 o;
+            f32x4 o;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {          // the expressions of pack_wino4_4 (bit-identical)
                 const int f = 4 * fq + e, fi = (f % 18) / 3, fj = 3 * (f / 18) + f % 3;
@@ -268,7 +267,7 @@ __global__ __launch_bounds__(256) void pack32_wino_tiles_kernel(const ssm_pack32
                     for (int c = 0; c < 3; ++c) val += T.g[fi][a] * g[a][c] * T.g[fj][c];
                 o[e] = (float)val;
             }
-            *reinterpret_cast<pk_f4 *>(out4 + (long long)qd * 4) = o;
+            *reinterpret_cast<f32x4 *>(out4 + (long long)qd * 4) = o;
         }
         if (tl == 0)
             for (int i = tid; i < j.nbias; i += 256) j.bp[i] = (j.bias && i < j.Cout) ? j.bias[i] : 0.f;
@@ -285,7 +284,7 @@ __global__ __launch_bounds__(256) void pack32_wino_tiles_kernel(const ssm_pack32
             const float g0 = j.transposed ? g[8 - c] : g[c], g1 = j.transposed ? g[5 - c] : g[3 + c], g2 = j.transposed ? g[2 - c] : g[6 + c];
             row[c] = q == 0 ? g0 : (q == 1 ? 0.5f * (g0 + g1 + g2) : (q == 2 ? 0.5f * (g0 - g1 + g2) : g2));
         }
-        *reinterpret_cast<pk_f4 *>(out + (long long)qd * 4) = pk_f4{row[0], 0.5f * (row[0] + row[1] + row[2]), 0.5f * (row[0] - row[1] + row[2]), row[2]};
+        *reinterpret_cast<f32x4 *>(out + (long long)qd * 4) = f32x4{row[0], 0.5f * (row[0] + row[1] + row[2]), 0.5f * (row[0] - row[1] + row[2]), row[2]};
     }
     if (tl == 0)
         for (int i = tid; i < j.nbias; i += 256) j.bp[i] = (j.bias && i < j.Cout) ? j.bias[i] : 0.f;

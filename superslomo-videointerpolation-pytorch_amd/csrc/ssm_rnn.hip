@@ -7,19 +7,12 @@
 // published ConvLSTM / ConvGRU cells of SreenivasVRao/ConvGRU-ConvLSTM-PyTorch (an un-vendored submodule of
 // the reference: parity UNPINNED).
 #include "ssm_common.h"
+#include "ssm_device.h"
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ float *vp(const ssm_view &v, int b, int c, int y) {
     return v.ptr + (long long)b * v.sb + (long long)c * v.sc + (long long)y * v.sh;
-}
-
-__device__ __forceinline__ int pack4_fp8(float a, float b, float c, float d) {
-    const float lim = 448.0f;                     // e4m3fn: beyond 448 -> NaN
-    int w = __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(a, -lim, lim), __builtin_amdgcn_fmed3f(b, -lim, lim), 0, false);
-    return __builtin_amdgcn_cvt_pk_fp8_f32(__builtin_amdgcn_fmed3f(c, -lim, lim), __builtin_amdgcn_fmed3f(d, -lim, lim), w, true);
 }
 
 // q8 = 0: HL8 (second plane = fp16 lo).  q8 = 1: Q8 form (include/ssm_hip.h): second planes shared by the pair of groups
@@ -36,11 +29,10 @@ __device__ __forceinline__ void hl8_store(const ssm_hview &v, int b, int g, int 
     *reinterpret_cast<h8 *>(d) = hi;
     if (q8) {
         const int odd = g & 1;
-        typedef int i2 __attribute__((ext_vector_type(2)));
         char *even_rec = d - odd * v.sg * 16 + v.sp * 16;
-        *reinterpret_cast<i2 *>(even_rec + odd * 8) = i2{pack4_fp8(o[0], o[1], o[2], o[3]), pack4_fp8(o[4], o[5], o[6], o[7])};
-        *reinterpret_cast<i2 *>(even_rec + v.sg * 16 + odd * 8) =
-            i2{pack4_fp8(lo[0] * 2048.f, lo[1] * 2048.f, lo[2] * 2048.f, lo[3] * 2048.f),
+        *reinterpret_cast<i32x2 *>(even_rec + odd * 8) = i32x2{pack4_fp8(o[0], o[1], o[2], o[3]), pack4_fp8(o[4], o[5], o[6], o[7])};
+        *reinterpret_cast<i32x2 *>(even_rec + v.sg * 16 + odd * 8) =
+            i32x2{pack4_fp8(lo[0] * 2048.f, lo[1] * 2048.f, lo[2] * 2048.f, lo[3] * 2048.f),
                pack4_fp8(lo[4] * 2048.f, lo[5] * 2048.f, lo[6] * 2048.f, lo[7] * 2048.f)};
     } else {
         h8 l16;

@@ -27,6 +27,7 @@
 // Signs: A's last row is (0, -1); the kernel computes that row / column with +1 and the finishing launch flips the sign of the
 // frequencies with exactly one index equal to 3.
 #include "ssm_common.h"
+#include "ssm_device.h"
 
 #include <cstdlib>
 
@@ -37,9 +38,6 @@
 #endif
 
 namespace {
-
-typedef float ww_f16 __attribute__((ext_vector_type(16)));
-typedef float ww_f4 __attribute__((ext_vector_type(4)));
 
 template <int MB_, int NB_, int OCC_>
 struct WwCfg {
@@ -73,7 +71,7 @@ __global__ __launch_bounds__(256, C::OCC) void wgradw_kernel(const WwParams p) {
     const int rb = fi == 0 ? 2 : (fi == 1 ? 2 : (fi == 2 ? 1 : 3));
     const float sgn = fi == 1 ? 1.f : -1.f;
 
-    ww_f16 acc[MB][NB][4];
+    f32x16 acc[MB][NB][4];
 #pragma unroll
     for (int a = 0; a < MB; ++a)
 #pragma unroll
@@ -104,7 +102,7 @@ __global__ __launch_bounds__(256, C::OCC) void wgradw_kernel(const WwParams p) {
     const int xl0 = 4 * (xcl * C::XCHQ + xpos), zl0 = C::X_FLOATS + 4 * (zcl * C::DZCHQ + zpos);
     const unsigned xcs = 4u * XSTEP * (unsigned)p.x.sc, zcs = 4u * 16u * (unsigned)p.dz.sc;
 
-    ww_f4 px[NXI], pz[NZI];
+    f32x4 px[NXI], pz[NZI];
     auto prefetch = [&](int s) {
         // s -> (batch entry, pair of tile rows, group) without integer division
         int t = (int)(((float)s + 0.5f) * p.inv_gpr), g = s - t * p.GPR;
@@ -121,22 +119,22 @@ __global__ __launch_bounds__(256, C::OCC) void wgradw_kernel(const WwParams p) {
         for (int i = 0; i < NXI; ++i) {
             const int c = xcl + XSTEP * i;
             const bool ok = xin && c < C::CI && ci0 + c < p.Cin;
-            px[i] = *reinterpret_cast<const ww_f4 *>(xbase + (ok ? xo + i * xcs : 0u));
+            px[i] = *reinterpret_cast<const f32x4 *>(xbase + (ok ? xo + i * xcs : 0u));
         }
         const bool zin = y0 + zr < H && x0 + 4 * zqd < W;
         const unsigned zo = zoff0 + 4u * (unsigned)(b * (int)p.dz.sb + y0 * p.dz.sh + x0);
 #pragma unroll
         for (int i = 0; i < NZI; ++i) {
             const bool ok = zin && co0 + zcl + 16 * i < p.Cout;
-            pz[i] = *reinterpret_cast<const ww_f4 *>(zbase + (ok ? zo + i * zcs : 0u));
+            pz[i] = *reinterpret_cast<const f32x4 *>(zbase + (ok ? zo + i * zcs : 0u));
         }
     };
     auto commit = [&](float *buf) {
 #pragma unroll
         for (int i = 0; i < NXI; ++i)
-            if (xcl < XSTEP && xcl + XSTEP * i < C::CI) *reinterpret_cast<ww_f4 *>(buf + xl0 + i * (4 * XSTEP * C::XCHQ)) = px[i];
+            if (xcl < XSTEP && xcl + XSTEP * i < C::CI) *reinterpret_cast<f32x4 *>(buf + xl0 + i * (4 * XSTEP * C::XCHQ)) = px[i];
 #pragma unroll
-        for (int i = 0; i < NZI; ++i) *reinterpret_cast<ww_f4 *>(buf + zl0 + i * (4 * 16 * C::DZCHQ)) = pz[i];
+        for (int i = 0; i < NZI; ++i) *reinterpret_cast<f32x4 *>(buf + zl0 + i * (4 * 16 * C::DZCHQ)) = pz[i];
     };
 
     // ---- this lane's operand sources inside a staged buffer (floats), raw rows -> MFMA operands.
@@ -151,23 +149,23 @@ __global__ __launch_bounds__(256, C::OCC) void wgradw_kernel(const WwParams p) {
     const float qz = fi == 2 ? -1.f : 1.f;
     struct RawV {
         float a0, b0, a9, b9;
-        ww_f4 a1, a5, b1, b5;
+        f32x4 a1, a5, b1, b5;
     };
     struct RawA {
-        ww_f4 a0, a1, b0, b1;
+        f32x4 a0, a1, b0, b1;
     };
     auto load_v = [&](const float *buf, int u, int b, RawV &r) {
         const float *xa = buf + xlane + b * (128 * C::XCHQ) + (2 * u + ra) * 24;
         const float *xb = buf + xlane + b * (128 * C::XCHQ) + (2 * u + rb) * 24;
         r.a0 = xa[0], r.b0 = xb[0], r.a9 = xa[9], r.b9 = xb[9];
-        r.a1 = *reinterpret_cast<const ww_f4 *>(xa + 1), r.a5 = *reinterpret_cast<const ww_f4 *>(xa + 5);
-        r.b1 = *reinterpret_cast<const ww_f4 *>(xb + 1), r.b5 = *reinterpret_cast<const ww_f4 *>(xb + 5);
+        r.a1 = *reinterpret_cast<const f32x4 *>(xa + 1), r.a5 = *reinterpret_cast<const f32x4 *>(xa + 5);
+        r.b1 = *reinterpret_cast<const f32x4 *>(xb + 1), r.b5 = *reinterpret_cast<const f32x4 *>(xb + 5);
     };
     auto load_a = [&](const float *buf, int cur_off, int u, int a, RawA &r) {
         const float *z0 = buf + zlane + a * (128 * C::DZCHQ) + (2 * u) * 16 + za_row;
         const float *z1 = zb_zero ? ww_lds + ZERO_AT : buf + zlane + a * (128 * C::DZCHQ) + (2 * u) * 16 + 16;
-        r.a0 = *reinterpret_cast<const ww_f4 *>(z0), r.a1 = *reinterpret_cast<const ww_f4 *>(z0 + 4);
-        r.b0 = *reinterpret_cast<const ww_f4 *>(z1), r.b1 = *reinterpret_cast<const ww_f4 *>(z1 + 4);
+        r.a0 = *reinterpret_cast<const f32x4 *>(z0), r.a1 = *reinterpret_cast<const f32x4 *>(z0 + 4);
+        r.b0 = *reinterpret_cast<const f32x4 *>(z1), r.b1 = *reinterpret_cast<const f32x4 *>(z1 + 4);
     };
     // the transforms in PIECES of 4-5 vector instructions, dealt between the MFMAs of the previous phase (pieces in order)
     auto xform_v_piece = [&](int k, const RawV &r, float (&d)[10], float (&v)[4][4]) {          // 6 pieces; v[tile m][column-frequency j]

@@ -28,6 +28,7 @@
 // Two kernel forms share this file: wino_kernel (this description: 16 frequencies per wave, one workgroup per CU) and wino2_kernel
 // (further down: 8 frequencies per wave, two workgroups per CU - what the plan picks for most layers; profiles/DESIGN_history_r1-r3.md 3.2d says why).
 #include "ssm_common.h"
+#include "ssm_device.h"
 
 #include <cstring>
 
@@ -39,10 +40,6 @@
 #ifndef WS_B64
 #define WS_B64 1        // B-operand rows as two aligned ds_read_b64 (patch stored one float in); 0: ds_read2_b32 on the aligned patch
 #endif
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -180,7 +177,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             if (g < L::NGU) {
                 const float *base = wbase + (long long)c0 * (16 * BN) + g * 256;
                 const unsigned m0v = lsb + (unsigned)g * 1024u;
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(uoff), "s"(base), "s"(m0v) : "memory", "m0");
+                lds_dma16(base, uoff, m0v);
             }
         } else {
             const int kk = k - L::NIU;
@@ -188,7 +185,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             if (g < L::NGP) {
                 const float *base = (c0 < p.C1) ? pbase1 + (long long)c0 * p.sc : pbase2 + (long long)(c0 - p.C1) * p.sc;
                 const unsigned m0v = lsb + (unsigned)(L::NGU + g) * 1024u + ((UPS || !WS_B64) ? 0u : 4u);
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(poff[kk]), "s"(base), "s"(m0v) : "memory", "m0");
+                lds_dma16(base, poff[kk], m0v);
             }
         }
     };
@@ -245,8 +242,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         // the patch values arrive as 8-byte pairs: pin each as a scalar HERE (where the wait for the loads belongs anyway), so that no
         // packed-fp32 arithmetic is formed on the pairs (profiles/DESIGN_history_r1-r3.md 3.3 fence).  Pinning at the load would put an s_waitcnt lgkmcnt(0)
         // behind every ds_read_b64 - the full LDS latency, eight times per k-step.
-#pragma unroll
-        for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(d[i]));
+        pin(d);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             t[j] = d[j] - d[8 + j];
@@ -265,8 +261,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
         // pin the results here: without this the optimizer sinks each subtraction next to the MFMA that consumes it (a dependent
         // VALU -> MFMA pair with wait states in front of every matrix instruction of the next k-step)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(v[buf][i]));
+        pin(v[buf]);
     };
 
     // fused upsample: low-res raw chunk -> hi-res patch; one thread = one 2x2 hi-res block position, walking CPT channels (ssm_conv.hip)
@@ -328,7 +323,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const float ab = half ? 0.f : bv0, ones = half ? 0.f : 1.f;
         acc[5] = __builtin_amdgcn_mfma_f32_32x32x2f32(ab, ones, acc[5], 0, 0, 0);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
     expand(lds);
     constexpr int PO = UPS ? L::HIP : C::USZ;          // patch offset: inside the stage, or the expanded patch
@@ -428,12 +423,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const unsigned pb1 = pb0 + 4u * (unsigned)p.dsh;
     const unsigned qb = 4u * ((unsigned)(4 * half) * (unsigned)p.psc + (unsigned)(py >> 1) * (unsigned)p.psh + (unsigned)(px >> 1));
     const bool ok0 = py < p.H && px < p.W, ok1 = py + 1 < p.H && px < p.W, x1ok = px + 1 < p.W;
-    auto st2 = [](const float *base, unsigned off_bytes, f32x2 val) {
-        asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-    };
-    auto st1 = [](const float *base, unsigned off_bytes, float val) {
-        asm volatile("global_store_dword %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-    };
     const float *addb = p.add ? p.add + (long long)(b / p.adiv) * p.asb + (long long)(4 * half) * p.asc + (long long)py * p.ash + px : nullptr;
     auto store_all = [&](auto full_tag) {
         constexpr bool FULL = decltype(full_tag)::value;
@@ -473,17 +462,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             float *bp = dstb + (long long)cu * p.dsc;
             f32x2 r0 = {y00, y01}, r1 = {y10, y11};
             if (ok0 && cok) {
-                if (x1ok) st2(bp, pb0, r0);
-                else st1(bp, pb0, y00);          // odd map width: the tile's second column is the zero frame - never written
+                if (x1ok) store_sbase(bp, pb0, r0);
+                else store_sbase(bp, pb0, y00);          // odd map width: the tile's second column is the zero frame - never written
             }
             if (ok1 && cok) {
-                if (x1ok) st2(bp, pb1, r1);
-                else st1(bp, pb1, y10);
+                if (x1ok) store_sbase(bp, pb1, r1);
+                else store_sbase(bp, pb1, y10);
             }
             if (poolb) {
                 float *qp = poolb + (long long)cu * p.psc;
                 const float sm = ((y00 + y10) + (y01 + y11)) * 0.25f;
-                if (ok1 && cok) st1(qp, qb, sm);
+                if (ok1 && cok) store_sbase(qp, qb, sm);
             }
             __builtin_amdgcn_sched_barrier(0);      // one cout at a time: 16 accumulator reads live, not 256
         }
@@ -559,7 +548,7 @@ __device__ __forceinline__ void wino2_body(const WinoParams &p, float *lds) {
             if (g < L::NGU) {
                 const float *base = wbase + (long long)c0 * (16 * BN) + g * 256;
                 const unsigned m0v = lsb + (unsigned)g * 1024u;
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(uoff), "s"(base), "s"(m0v) : "memory", "m0");
+                lds_dma16(base, uoff, m0v);
             }
         } else {
             const int kk = k - L::NIU;
@@ -567,7 +556,7 @@ __device__ __forceinline__ void wino2_body(const WinoParams &p, float *lds) {
             if (g < L::NGP) {
                 const float *base = (c0 < p.C1) ? pbase1 + (long long)c0 * p.sc : pbase2 + (long long)(c0 - p.C1) * p.sc;
                 const unsigned m0v = lsb + (unsigned)(L::NGU + g) * 1024u + ((UPS || !WS_B64) ? 0u : 4u);
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(poff[kk]), "s"(base), "s"(m0v) : "memory", "m0");
+                lds_dma16(base, poff[kk], m0v);
             }
         }
     };
@@ -604,8 +593,7 @@ __device__ __forceinline__ void wino2_body(const WinoParams &p, float *lds) {
     };
     // rows 2FH, 2FH+1 of B^T d from patch rows e0, e1, e2 = d rows FH, FH+1, FH+2
     auto transform_rows = [&]() {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) asm volatile("" : "+v"(d[i]));      // scalars from here on (see wino_kernel)
+        pin(d);      // scalars from here on (see wino_kernel)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if constexpr (FH == 0) {
@@ -625,8 +613,7 @@ __device__ __forceinline__ void wino2_body(const WinoParams &p, float *lds) {
             v[buf][4 * i + 2] = t[4 * i + 2] - t[4 * i + 1];
             v[buf][4 * i + 3] = t[4 * i + 1] - t[4 * i + 3];
         }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(v[buf][i]));
+        pin(v[buf]);
     };
 
     auto expand = [&](const float *stg) {
@@ -678,10 +665,10 @@ __device__ __forceinline__ void wino2_body(const WinoParams &p, float *lds) {
     // NMIN instructions per chunk, vmcnt retires in order), so with NST > 2 a chunk has NST - 1 chunk times to land instead of one -
     // on boxes / layers where the L2 / MALL answers slowly the double buffer loses 10 %.
     auto wait_newer = [&](int k) {        // wait until at most the k newest chunks of this wave's DMAs are outstanding (k uniform)
-        if (k <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (k == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(L::NMIN) : "memory");
-        else if (k == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * L::NMIN) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * L::NMIN) : "memory");
+        if (k <= 0) wait_vmcnt<0>();
+        else if (k == 1) wait_vmcnt<L::NMIN>();
+        else if (k == 2) wait_vmcnt<2 * L::NMIN>();
+        else wait_vmcnt<3 * L::NMIN>();
     };
     // The counted waits rely on the chunk loop issuing NO other VMEM instruction (global load / store) than these DMAs: any such
     // instruction would shift the vmcnt positions.  Stores happen only in the epilogue, after the last wait.
@@ -843,12 +830,6 @@ __device__ __forceinline__ void wino2_body(const WinoParams &p, float *lds) {
         const unsigned pb1 = pb0 + 4u * (unsigned)p.dsh;
         const unsigned qb = 4u * ((unsigned)(4 * half) * (unsigned)p.psc + (unsigned)(py >> 1) * (unsigned)p.psh + (unsigned)(px >> 1));
         const bool ok0 = py < p.H && px < p.W, ok1 = py + 1 < p.H && px < p.W, x1ok = px + 1 < p.W;
-        auto st2 = [](const float *base, unsigned off_bytes, f32x2 val) {
-            asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-        };
-        auto st1 = [](const float *base, unsigned off_bytes, float val) {
-            asm volatile("global_store_dword %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-        };
         const float *addb = p.add ? p.add + (long long)(b / p.adiv) * p.asb + (long long)(4 * half) * p.asc + (long long)py * p.ash + px : nullptr;
         auto store_all = [&](auto full_tag) {
             constexpr bool FULL = decltype(full_tag)::value;
@@ -883,17 +864,17 @@ __device__ __forceinline__ void wino2_body(const WinoParams &p, float *lds) {
                 float *bp = dstb + (long long)cu * p.dsc;
                 f32x2 r0 = {y00, y01}, r1 = {y10, y11};
                 if (ok0 && cok) {
-                    if (x1ok) st2(bp, pb0, r0);
-                    else st1(bp, pb0, y00);          // odd map width: the tile's second column is the zero frame - never written
+                    if (x1ok) store_sbase(bp, pb0, r0);
+                    else store_sbase(bp, pb0, y00);          // odd map width: the tile's second column is the zero frame - never written
                 }
                 if (ok1 && cok) {
-                    if (x1ok) st2(bp, pb1, r1);
-                    else st1(bp, pb1, y10);
+                    if (x1ok) store_sbase(bp, pb1, r1);
+                    else store_sbase(bp, pb1, y10);
                 }
                 if (poolb) {
                     float *qp = poolb + (long long)cu * p.psc;
                     const float sm = ((y00 + y10) + (y01 + y11)) * 0.25f;
-                    if (ok1 && cok) st1(qp, qb, sm);
+                    if (ok1 && cok) store_sbase(qp, qb, sm);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }

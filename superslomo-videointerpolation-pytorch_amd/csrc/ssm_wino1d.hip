@@ -28,15 +28,12 @@
 // workgroup transforms the raw rows into V [CK][rows][2][tiles][4] (both operands of a macro-step are two conflict-free ds_read_b128
 // for 8 MFMAs).  The raw patch lands SHIFT floats into its LDS region so that every tile's 8-float window is 8- / 16-byte aligned.
 #include "ssm_common.h"
+#include "ssm_device.h"
 
 #include <atomic>
 #include <mutex>
 #include <type_traits>
 #include <cstdlib>
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -155,7 +152,7 @@ __global__ __launch_bounds__(256, 2) void wino1d_kernel(const W1Params p) {
             if (g < L::NGU) {
                 const float *base = wbase + (long long)c0 * (KS * 2 * BN * 4) + g * 256;
                 const unsigned m0v = lsb + (unsigned)g * 1024u;
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(uoff), "s"(base), "s"(m0v) : "memory", "m0");
+                lds_dma16(base, uoff, m0v);
             }
         } else {
             const int kk = k - L::NIU;
@@ -163,7 +160,7 @@ __global__ __launch_bounds__(256, 2) void wino1d_kernel(const W1Params p) {
             if (g < L::NGP) {
                 const float *base = pbase + (long long)c0 * p.sc;
                 const unsigned m0v = lsb + (unsigned)(L::NGU + g) * 1024u + 4u * C::SHIFT;
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(poff[kk]), "s"(base), "s"(m0v) : "memory", "m0");
+                lds_dma16(base, poff[kk], m0v);
             }
         }
     };
@@ -208,7 +205,7 @@ __global__ __launch_bounds__(256, 2) void wino1d_kernel(const W1Params p) {
     for (int ch = 0; ch < nchunks; ++ch) {
         const int stage = ch & 1;
         // chunk ch has landed for every wave; every wave is done with the MFMAs of chunk ch-1 (V and the other stage are free)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();
         const bool dma_next = ch + 1 < nchunks && !(W1ABL(1) && ch >= 1);
 #ifndef W1_DMA_EARLY
@@ -310,15 +307,6 @@ __global__ __launch_bounds__(256, 2) void wino1d_kernel(const W1Params p) {
         const unsigned qb = 4u * ((unsigned)(4 * half) * (unsigned)p.psc + (unsigned)(py >> 1) * (unsigned)p.psh + (unsigned)(px >> 1));
         const bool rok = py < p.H;
         const bool vok = rok && px + M <= p.W && p.vec;          // whole tile inside the map, as one aligned piece
-        auto st4 = [](const float *base, unsigned off_bytes, f32x4 val) {
-            asm volatile("global_store_dwordx4 %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-        };
-        auto st2 = [](const float *base, unsigned off_bytes, f32x2 val) {
-            asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-        };
-        auto st1 = [](const float *base, unsigned off_bytes, float val) {
-            asm volatile("global_store_dword %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-        };
         const float *addb = p.add ? p.add + (long long)(b / p.adiv) * p.asb + (long long)(4 * half) * p.asc + (long long)py * p.ash + px : nullptr;
         // M = 2: the addend pair of output register r + 4 is fetched at the top of iteration r (the stores below are ordered asm
         // statements: a load issued behind one cannot move above it, and fetched in its own iteration every addend would wait out its
@@ -377,15 +365,15 @@ __global__ __launch_bounds__(256, 2) void wino1d_kernel(const W1Params p) {
             if (vok) {
                 if constexpr (M == 2) {
                     const f32x2 o = {y[0], y[1]};
-                    st2(bp, pb, o);
+                    store_sbase(bp, pb, o);
                 } else {
                     const f32x4 o = {y[0], y[1], y[2], y[3]};
-                    st4(bp, pb, o);
+                    store_sbase(bp, pb, o);
                 }
             } else {
 #pragma unroll
                 for (int e = 0; e < M; ++e)
-                    if (rok && px + e < p.W) st1(bp + e, pb, y[e]);
+                    if (rok && px + e < p.W) store_sbase(bp + e, pb, y[e]);
             }
             if (poolb) {
                 // 2x2 mean: vertical pairs first (lane l and l ^ 16 hold rows y, y + 1 of the same tile), then the horizontal pair -
@@ -396,13 +384,13 @@ __global__ __launch_bounds__(256, 2) void wino1d_kernel(const W1Params p) {
                 for (int e = 0; e < M; ++e) sv[e] = y[e] + __shfl_xor(y[e], 16);
                 const bool pok = tyl == 0 && rok;          // H, W even (checked on the host)
                 if constexpr (M == 2) {
-                    if (pok && px + 2 <= p.W) st1(qp, qb, (sv[0] + sv[1]) * 0.25f);
+                    if (pok && px + 2 <= p.W) store_sbase(qp, qb, (sv[0] + sv[1]) * 0.25f);
                 } else {
                     const f32x2 o = {(sv[0] + sv[1]) * 0.25f, (sv[2] + sv[3]) * 0.25f};
-                    if (pok && px + 4 <= p.W && p.vec) st2(qp, qb, o);
+                    if (pok && px + 4 <= p.W && p.vec) store_sbase(qp, qb, o);
                     else if (pok) {
-                        if (px + 2 <= p.W) st1(qp, qb, o[0]);
-                        if (px + 4 <= p.W) st1(qp + 1, qb, o[1]);
+                        if (px + 2 <= p.W) store_sbase(qp, qb, o[0]);
+                        if (px + 4 <= p.W) store_sbase(qp + 1, qb, o[1]);
                     }
                 }
             }

@@ -37,14 +37,12 @@
 // Whatever is wave-uniform at run time (which part of a (cin, tile) a thread transforms, whether later chunks exist) selects a
 // straight-line INSTANCE of the loop instead of being tested inside it: a scalar branch in front of an LDS read exposes its latency.
 #include "ssm_common.h"
+#include "ssm_device.h"
 
 #include <atomic>
 #include <mutex>
 #include <type_traits>
 #include <cstdlib>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -254,15 +252,6 @@ __device__ __forceinline__ void w4_epilogue(const W4Params &p, const f32x4 (&acc
                 const unsigned pb = 4u * ((unsigned)(4 * q) * (unsigned)p.dsc + (unsigned)py * (unsigned)p.dsh + (unsigned)px);
         const unsigned qb = 4u * ((unsigned)(4 * q) * (unsigned)p.psc + (unsigned)(py >> 1) * (unsigned)p.psh + (unsigned)(px >> 1));
         const bool vok = py + 4 <= p.H && px + 4 <= p.W && p.vec;          // whole tile inside the map, rows as aligned 16-byte pieces
-        auto st4 = [](const float *base, unsigned off_bytes, f32x4 val) {
-            asm volatile("global_store_dwordx4 %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-        };
-        auto st2 = [](const float *base, unsigned off_bytes, f32x2 val) {
-            asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-        };
-        auto st1 = [](const float *base, unsigned off_bytes, float val) {
-            asm volatile("global_store_dword %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-        };
         const float *addb = p.add ? p.add + (long long)(b / p.adiv) * p.asb + (long long)(4 * q) * p.asc + (long long)py * p.ash + px : nullptr;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -321,11 +310,11 @@ __device__ __forceinline__ void w4_epilogue(const W4Params &p, const f32x4 (&acc
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (vok) {
-                    st4(bp + (long long)i * p.dsh, pb, f32x4{y[i][0], y[i][1], y[i][2], y[i][3]});
+                    store_sbase(bp + (long long)i * p.dsh, pb, f32x4{y[i][0], y[i][1], y[i][2], y[i][3]});
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        if (py + i < p.H && px + e < p.W) st1(bp + (long long)i * p.dsh + e, pb, y[i][e]);
+                        if (py + i < p.H && px + e < p.W) store_sbase(bp + (long long)i * p.dsh + e, pb, y[i][e]);
                 }
             }
             if (poolb) {
@@ -336,10 +325,10 @@ __device__ __forceinline__ void w4_epilogue(const W4Params &p, const f32x4 (&acc
                     const float o0 = ((y[2 * i][0] + y[2 * i + 1][0]) + (y[2 * i][1] + y[2 * i + 1][1])) * 0.25f;
                     const float o1 = ((y[2 * i][2] + y[2 * i + 1][2]) + (y[2 * i][3] + y[2 * i + 1][3])) * 0.25f;
                     const bool rok = py + 2 * i < p.H;
-                    if (rok && px + 4 <= p.W && p.vec) st2(qp + (long long)i * p.psh, qb, f32x2{o0, o1});
+                    if (rok && px + 4 <= p.W && p.vec) store_sbase(qp + (long long)i * p.psh, qb, f32x2{o0, o1});
                     else if (rok) {
-                        if (px + 2 <= p.W) st1(qp + (long long)i * p.psh, qb, o0);
-                        if (px + 4 <= p.W) st1(qp + (long long)i * p.psh + 1, qb, o1);
+                        if (px + 2 <= p.W) store_sbase(qp + (long long)i * p.psh, qb, o0);
+                        if (px + 4 <= p.W) store_sbase(qp + (long long)i * p.psh + 1, qb, o1);
                     }
                 }
             }
@@ -380,14 +369,6 @@ __device__ __forceinline__ void w4_epilogue_shuffle<true>(const W4Params &p, con
     float *dstb = p.dst + (long long)b * p.dsb + (long long)(cu0 >> 2) * p.dsc;          // real channel cu0 / 4 (+ q per lane)
     const unsigned pb = 4u * ((unsigned)q * (unsigned)p.dsc + (unsigned)(2 * py) * (unsigned)p.dsh + (unsigned)(2 * px));
     const bool vok = py + 4 <= p.H && px + 4 <= p.W && p.vec;          // whole low-res tile inside the region, output rows as aligned 16-byte pieces
-    auto st4 = [](const float *base, unsigned off_bytes, f32x4 val) {
-        // (s_nop 1: a store of more than 64 bits followed by a vector write of its data registers needs 2 wait states on gfx940+, and the
-        // compiler does not see inside the asm - csrc/check_hazard.py caught exactly that here)
-        asm volatile("global_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-    };
-    auto st1 = [](const float *base, unsigned off_bytes, float val) {
-        asm volatile("global_store_dword %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-    };
 #pragma unroll
     for (int a = 0; a < 2; ++a) {          // output rows 2 (py + i) + a: the parities (a, 0) and (a, 1) interleave along x
         float y0[4][4], y1[4][4];
@@ -397,14 +378,14 @@ __device__ __forceinline__ void w4_epilogue_shuffle<true>(const W4Params &p, con
         for (int i = 0; i < 4; ++i) {
             const float *rowp = dstb + (long long)(2 * i + a) * p.dsh;
             if (vok) {
-                st4(rowp, pb, f32x4{y0[i][0], y1[i][0], y0[i][1], y1[i][1]});
-                st4(rowp + 4, pb, f32x4{y0[i][2], y1[i][2], y0[i][3], y1[i][3]});
+                store_sbase_nop(rowp, pb, f32x4{y0[i][0], y1[i][0], y0[i][1], y1[i][1]});
+                store_sbase_nop(rowp + 4, pb, f32x4{y0[i][2], y1[i][2], y0[i][3], y1[i][3]});
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     if (py + i < p.H && px + e < p.W) {
-                        st1(rowp + 2 * e, pb, y0[i][e]);
-                        st1(rowp + 2 * e + 1, pb, y1[i][e]);
+                        store_sbase(rowp + 2 * e, pb, y0[i][e]);
+                        store_sbase(rowp + 2 * e + 1, pb, y1[i][e]);
                     }
                 }
             }
@@ -491,7 +472,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void wino4_kernel(const W4Params p) 
                 const int gb = NCB == 1 ? 0 : g / G1;
                 const float *base = wbase + ((long long)gb * p.Cin + c0) * (9 * 32 * 4) + (g - gb * G1) * 256;
                 const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(L::UOFF + stage * C::USZ) * 4u + (unsigned)g * 1024u);
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(uoff), "s"(base), "s"(m0v) : "memory", "m0");
+                lds_dma16(base, uoff, m0v);
             }
         } else {
             const int kk = k - L::NIU;
@@ -499,7 +480,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void wino4_kernel(const W4Params p) 
             if (NW * kk + NW - 1 < L::NGP || g < L::NGP) {
                 const float *base = (c0 < p.C1) ? pbase1 + (long long)c0 * p.sc : pbase2 + (long long)(c0 - p.C1) * p.sc;
                 const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(L::DOFF + pbuf * L::DCAP) * 4u + (unsigned)g * 1024u + (UPS ? 0u : 4u * C::SHIFT));
-                asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(poff[kk]), "s"(base), "s"(m0v) : "memory", "m0");
+                lds_dma16(base, poff[kk], m0v);
             }
         }
     };
@@ -757,8 +738,8 @@ __global__ __launch_bounds__(C::THREADS, 2) void wino4_kernel(const W4Params p) 
         auto chunk1 = [&](int ch, auto N1, auto N2) __attribute__((always_inline)) {
             constexpr bool n1 = decltype(N1)::value, n2 = decltype(N2)::value;
             const int stage = ch & 1;
-            if (u_full) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(L::NIU + (n1 ? L::NIP : 0)) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(L::NIU - 1 + (n1 ? L::NIP : 0)) : "memory");
+            if (u_full) wait_vmcnt<L::NIU + (n1 ? L::NIP : 0)>();
+            else wait_vmcnt<L::NIU - 1 + (n1 ? L::NIP : 0)>();
             __syncthreads();
             W4STAMP(0)
             if constexpr (UPS) {
@@ -767,7 +748,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void wino4_kernel(const W4Params p) 
             }
             if (!W4ABL(4) || ch == 0) transform(UPS ? 0 : stage, 0);
             W4STAMP(1)
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n1 ? L::NIP : 0) : "memory");          // the filter of chunk ch
+            wait_vmcnt<n1 ? L::NIP : 0>();          // the filter of chunk ch
             __syncthreads();
             W4STAMP(2)
             const int (&uk)[L::NIU] = uoffk;          // (named here: the nested lambda of a generic lambda does not capture it implicitly)
@@ -783,11 +764,11 @@ __global__ __launch_bounds__(C::THREADS, 2) void wino4_kernel(const W4Params p) 
                 if (n < L::NIU) {
                     if constexpr (n1) {
                         if (NW * n + NW - 1 < L::NGU || NW * n + wid < L::NGU)
-                            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(uk[n]), "s"(fb), "s"(mu + (unsigned)(n * NW * 1024)) : "memory", "m0");
+                            lds_dma16(fb, uk[n], mu + (unsigned)(n * NW * 1024));
                     }
                 } else if constexpr (n2) {
                     const int k = n - L::NIU;
-                    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(pk[k]), "s"(pb), "s"(mp + (unsigned)(k * NW * 1024)) : "memory", "m0");
+                    lds_dma16(pb, pk[k], mp + (unsigned)(k * NW * 1024));
                 }
             }, [](int) {});
             W4STAMP(3)
@@ -813,7 +794,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void wino4_kernel(const W4Params p) 
 #pragma unroll
             for (int k = L::NIU; k < L::NI; ++k) issue_k(1, 0, k, 1);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();
         using C0 = std::integral_constant<int, 0>;
         using C2 = std::integral_constant<int, 2>;
@@ -894,7 +875,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void wino4_kernel(const W4Params p) 
             const bool m1 = steady || ch + 1 < nchunks, m2 = steady || ch + 2 < nchunks, m3 = steady || ch + 3 < nchunks;
             const int st = ch & 1;
             // V(ch) complete, filter of chunk ch and (raw) patch of the next chunk(s) landed, every wave done with chunk ch-1
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
             if (!W4ABL(16) || ch == 0) __syncthreads();          // (tuning builds, bit 16: no chunk barrier - wrong results, timing only)
             W4STAMP(0)
             W4TRACE(ch, 0)
@@ -963,7 +944,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void wino4_kernel(const W4Params p) 
 #if defined(W4_TRACE) && !defined(SSM_WINO_ABLATE)
     if (trace) {
         if (lane == 0) ltrace[(wid * 16 + 1) * 4 + 1] = __builtin_amdgcn_s_memtime();          // epilogue issued (slot 1 of chunk 1)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         if (lane == 0) ltrace[(wid * 16 + 2) * 4 + 1] = __builtin_amdgcn_s_memtime();          // ... and its stores complete (slot 1 of chunk 2)
         __syncthreads();
         for (int i = tid; i < NW * 64; i += C::THREADS) p.dbg[16 + i] = ltrace[i];
@@ -971,7 +952,7 @@ __global__ __launch_bounds__(C::THREADS, 2) void wino4_kernel(const W4Params p) 
 #endif
 #ifdef SSM_WINO_ABLATE
     if (stamp) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         W4STAMP(4)
         if (tid == 0) {
             for (int i = 0; i < 5; ++i) atomicAdd(p.dbg + i, tph[i]);

@@ -25,15 +25,13 @@
 // instructions) cost ~2000 cycles per k-step beside 2048 of MFMA: the form runs at ~0.33 of the matrix pipe and still beats F(4,5)
 // along x (0.71 of the pipe at 2.5 x the multiplies) by 1.27 x.
 #include "ssm_common.h"
+#include "ssm_device.h"
 #include "ssm_wino5_pack.h"
 
 #include <atomic>
 #include <mutex>
 #include <type_traits>
 #include <cstdlib>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
@@ -128,15 +126,6 @@ __device__ __forceinline__ void w5_epilogue(const W5Params &p, const f32x4 (&acc
     const unsigned pb = 4u * ((unsigned)(4 * q) * (unsigned)p.dsc + (unsigned)py * (unsigned)p.dsh + (unsigned)px);
     const unsigned qb = 4u * ((unsigned)(4 * q) * (unsigned)p.psc + (unsigned)(py >> 1) * (unsigned)p.psh + (unsigned)(px >> 1));
     const bool vok = FAST || (py + 4 <= p.H && px + 4 <= p.W && p.vec);          // whole tile inside the map, rows as aligned 16-byte pieces
-    auto st4 = [](const float *base, unsigned off_bytes, f32x4 val) {
-        asm volatile("global_store_dwordx4 %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-    };
-    auto st2 = [](const float *base, unsigned off_bytes, f32x2 val) {
-        asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-    };
-    auto st1 = [](const float *base, unsigned off_bytes, float val) {
-        asm volatile("global_store_dword %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-    };
     const float *addb = p.add ? p.add + (long long)(b / p.adiv) * p.asb + (long long)(4 * q) * p.asc + (long long)py * p.ash + px : nullptr;
     // the addend rows of cout r + 1 are requested while cout r is transformed (four independent 16-byte loads, one cout ahead): their
     // latency runs beside the output transform instead of in front of each cout's stores
@@ -201,18 +190,17 @@ __device__ __forceinline__ void w5_epilogue(const W5Params &p, const f32x4 (&acc
         // the wait for the prefetched addend rows of cout r + 1 goes in front of the inline-assembly stores, which the compiler's wait-count
         // pass does not see (ssm_wino7.hip, w7_epilogue)
         if (zvec && r + 1 < 4) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(zadd[(r + 1) & 1][i]));
+            pin(zadd[(r + 1) & 1]);
         }
         float *bp = dstb + (long long)cu * p.dsc;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             if (vok) {
-                st4(bp + (long long)i * p.dsh, pb, f32x4{y[i][0], y[i][1], y[i][2], y[i][3]});
+                store_sbase(bp + (long long)i * p.dsh, pb, f32x4{y[i][0], y[i][1], y[i][2], y[i][3]});
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)
-                    if (py + i < p.H && px + e < p.W) st1(bp + (long long)i * p.dsh + e, pb, y[i][e]);
+                    if (py + i < p.H && px + e < p.W) store_sbase(bp + (long long)i * p.dsh + e, pb, y[i][e]);
             }
         }
         if (poolb) {
@@ -223,10 +211,10 @@ __device__ __forceinline__ void w5_epilogue(const W5Params &p, const f32x4 (&acc
                 const float o0 = ((y[2 * i][0] + y[2 * i + 1][0]) + (y[2 * i][1] + y[2 * i + 1][1])) * 0.25f;
                 const float o1 = ((y[2 * i][2] + y[2 * i + 1][2]) + (y[2 * i][3] + y[2 * i + 1][3])) * 0.25f;
                 const bool rok = FAST || py + 2 * i < p.H;
-                if (FAST || (rok && px + 4 <= p.W && p.vec)) st2(qp + (long long)i * p.psh, qb, f32x2{o0, o1});
+                if (FAST || (rok && px + 4 <= p.W && p.vec)) store_sbase(qp + (long long)i * p.psh, qb, f32x2{o0, o1});
                 else if (rok) {
-                    if (px + 2 <= p.W) st1(qp + (long long)i * p.psh, qb, o0);
-                    if (px + 4 <= p.W) st1(qp + (long long)i * p.psh + 1, qb, o1);
+                    if (px + 2 <= p.W) store_sbase(qp + (long long)i * p.psh, qb, o0);
+                    if (px + 4 <= p.W) store_sbase(qp + (long long)i * p.psh + 1, qb, o1);
                 }
             }
         }
@@ -275,9 +263,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     }
     const int uoff = lane * 16;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void *)lds;
-    auto dma = [](const float *base, int voff_bytes, unsigned m0v) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_bytes), "s"(base), "s"(m0v) : "memory", "m0");
-    };
     // the n-th DMA instruction of this wave for k-step s (into filter stage / patch buffer s & 1): n < NIP a patch piece, else a filter piece
     auto issue_n = [&](int s, int n) {
         const int buf = s & 1;
@@ -286,13 +271,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             if (4 * n + 3 < C::NGP || g < C::NGP) {
                 const float *base = pbase + (long long)(s * CK) * p.sc;
                 const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(C::POFF + buf * C::PCAP + C::SHIFT) * 4u + (unsigned)g * 1024u);
-                dma(base, poff[n], m0v);
+                lds_dma16(base, poff[n], m0v);
             }
         } else {
             const int g = 4 * (n - C::NIP) + wid;
             const float *base = wbase + (long long)s * C::USZ + g * 256;
             const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(C::UOFF + buf * C::USZ) * 4u + (unsigned)g * 1024u);
-            dma(base, uoff, m0v);
+            lds_dma16(base, uoff, m0v);
         }
     };
     static_assert(C::NIP + C::NIU <= 16, "one DMA slot per quad of the matrix phase");
@@ -349,7 +334,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     for (int s = 0; s < nsteps; ++s) {
         const bool more = s + 1 < nsteps;
         W5STAMP(3)          // [3] matrix phase (incl. the DMA issue)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();          // filter and patch of k-step s landed; the MFMAs of k-step s - 1 are done with V and the other filter stage
         W5STAMP(0)          // [0] DMA wait + top barrier
         // ---- row pass ---------------------------------------------------------------------------------------------------------------
@@ -385,8 +370,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 float d[8] = {cx[0][e], cx[1][e], cx[2][e], cx[3][e], cx[4][e], cx[5][e], cx[6][e], cx[7][e]};
                 // the values arrive as 16-byte quads: pin each as a scalar so that no packed-fp32 arithmetic is formed on neighbours
                 // (check_isa.sh fences v_pk_*_f32; the four passes are the same arithmetic on the four elements of every quad)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(d[i]));
+                pin(d);
                 w5_bt(d, f[e]);
             }
 #pragma unroll
@@ -436,7 +420,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         w5_epilogue<false>(p, acc, bv, b, nb * 32 + cb * 16, q, px, py);
     }
 #ifdef W5_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     if (p.dbg && lane == 0 && (blockIdx.x % 64) == 0) {          // a sample of the workgroups
         const unsigned long long tn = __builtin_amdgcn_s_memtime();
         for (int i = 0; i < 6; ++i) atomicAdd(p.dbg + wid * 8 + i, tph[i]);
@@ -537,9 +521,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     const int uoff = lane * 16;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void *)lds;
-    auto dma = [](const float *base, int voff_bytes, unsigned m0v) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_bytes), "s"(base), "s"(m0v) : "memory", "m0");
-    };
     // The LDS-DMA of a k-step rides in the matrix phases, one instruction per quad (a burst costs ~200 cycles a piece); its bases are formed
     // once per phase - a wave cannot issue beside its own MFMAs, so every scalar instruction in a matrix phase lengthens it by its issue
     // time (the first split kernel recomputed 64-bit bases per piece: 12 scalar instructions each).  Issued by the transforming waves
@@ -558,9 +539,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         return DmaBase{pbase + (long long)(s * CK) * p.sc,
                        (unsigned)__builtin_amdgcn_readfirstlane(lds0 + (unsigned)(L::POFF + pb * C::PCAP + C::SHIFT) * 4u + (unsigned)w4 * 1024u)};
     };
-    auto dma_u = [&](const DmaBase &bs, int k) { dma(bs.src + k * 1024, uoff, bs.m0 + (unsigned)k * 4096u); };
+    auto dma_u = [&](const DmaBase &bs, int k) { lds_dma16(bs.src + k * 1024, uoff, bs.m0 + (unsigned)k * 4096u); };
     auto dma_p = [&](const DmaBase &bs, int k) {
-        if (4 * k + 3 < C::NGP || 4 * k + w4 < C::NGP) dma(bs.src, poff[k], bs.m0 + (unsigned)k * 4096u);
+        if (4 * k + 3 < C::NGP || 4 * k + w4 < C::NGP) lds_dma16(bs.src, poff[k], bs.m0 + (unsigned)k * 4096u);
     };
     static_assert(C::NGU == 32, "8 filter pieces per wave of half 1: the transform's 8 DMA slots");
 
@@ -631,8 +612,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             for (int e = 0; e < 2; ++e) {
                 float d[8] = {cx[0][e], cx[1][e], cx[2][e], cx[3][e], cx[4][e], cx[5][e], cx[6][e], cx[7][e]};
                 // (pinned as scalars: no packed-fp32 arithmetic on the two elements of a pair - check_isa.sh fences v_pk_*_f32)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) asm volatile("" : "+v"(d[i]));
+                pin(d);
                 w5_bt(d, f[e]);
                 __builtin_amdgcn_sched_barrier(0);
                 slot(5 + e);
@@ -705,7 +685,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             for (int k = 0; k < C::NIP; ++k) dma_p(pbs, k);
         }
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
@@ -731,7 +711,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             if (more) transform(I0{}, pb1, noslot);
             pb1 = pb1 + 1 == L::NPB ? 0 : pb1 + 1;
             W5S(1)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the filter of k-step s + 1 (a whole phase old)
+            wait_vmcnt<0>();          // the filter of k-step s + 1 (a whole phase old)
             __syncthreads();
             W5S(3)
         }
@@ -743,10 +723,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             W5S(1)
             // patch(s + 1) is read from phase B(s) on: it must have landed; patch(s + 2), requested in B(s - 1), may still be in flight
             if (s >= 1 && s + 2 < nsteps) {
-                if (first) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::NIP) : "memory");
-                else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(C::NIP - 1) : "memory");
+                if (first) wait_vmcnt<C::NIP>();
+                else wait_vmcnt<C::NIP - 1>();
             } else {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                wait_vmcnt<0>();
             }
             __syncthreads();
             W5S(3)
@@ -817,15 +797,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const unsigned pbo = 4u * ((unsigned)(4 * q) * (unsigned)p.dsc + (unsigned)py * (unsigned)p.dsh + (unsigned)px);
         const unsigned qbo = 4u * ((unsigned)(4 * q) * (unsigned)p.psc + (unsigned)(py >> 1) * (unsigned)p.psh + (unsigned)(px >> 1));
         const bool vok = py + 4 <= p.H && px + 4 <= p.W && p.vec;          // whole tile inside the map, rows as aligned 16-byte pieces
-        auto st4 = [](const float *base, unsigned off_bytes, f32x4 val) {
-            asm volatile("global_store_dwordx4 %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-        };
-        auto st2 = [](const float *base, unsigned off_bytes, f32x2 val) {
-            asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-        };
-        auto st1 = [](const float *base, unsigned off_bytes, float val) {
-            asm volatile("global_store_dword %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-        };
         const float *addb = p.add ? p.add + (long long)(b / p.adiv) * p.asb + (long long)(4 * q) * p.asc + (long long)py * p.ash + px : nullptr;
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
@@ -874,11 +845,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 if (vok) {
-                    st4(bp + (long long)i * p.dsh, pbo, f32x4{y[i][0], y[i][1], y[i][2], y[i][3]});
+                    store_sbase(bp + (long long)i * p.dsh, pbo, f32x4{y[i][0], y[i][1], y[i][2], y[i][3]});
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        if (py + i < p.H && px + e < p.W) st1(bp + (long long)i * p.dsh + e, pbo, y[i][e]);
+                        if (py + i < p.H && px + e < p.W) store_sbase(bp + (long long)i * p.dsh + e, pbo, y[i][e]);
                 }
             }
             if (poolb) {
@@ -889,10 +860,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                     const float o0 = ((y[2 * i][0] + y[2 * i + 1][0]) + (y[2 * i][1] + y[2 * i + 1][1])) * 0.25f;
                     const float o1 = ((y[2 * i][2] + y[2 * i + 1][2]) + (y[2 * i][3] + y[2 * i + 1][3])) * 0.25f;
                     const bool rok = py + 2 * i < p.H;
-                    if (rok && px + 4 <= p.W && p.vec) st2(qp + (long long)i * p.psh, qbo, f32x2{o0, o1});
+                    if (rok && px + 4 <= p.W && p.vec) store_sbase(qp + (long long)i * p.psh, qbo, f32x2{o0, o1});
                     else if (rok) {
-                        if (px + 2 <= p.W) st1(qp + (long long)i * p.psh, qbo, o0);
-                        if (px + 4 <= p.W) st1(qp + (long long)i * p.psh + 1, qbo, o1);
+                        if (px + 2 <= p.W) store_sbase(qp + (long long)i * p.psh, qbo, o0);
+                        if (px + 4 <= p.W) store_sbase(qp + (long long)i * p.psh + 1, qbo, o1);
                     }
                 }
             }
@@ -903,7 +874,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (fh == 0) epilogue(I0{});
     else epilogue(I1{});
 #ifdef W5_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     W5S(4)
     if (p.dbg && lane == 0 && (blockIdx.x % 64) == 0) {          // a sample of the workgroups
         for (int i = 0; i < 6; ++i) atomicAdd(p.dbg + wid * 8 + i, tph[i]);

@@ -35,15 +35,13 @@
 // Pipeline, one barrier per input channel:  [barrier]  DMA U(c+1), patch(c+3) | row pass (c+2) | column pass (c+1) | 49 MFMAs of channel c,
 // the transform pieces and the LDS-DMA instructions placed in the slots behind the MFMAs (everything double-buffered; 97 KiB of LDS).
 #include "ssm_common.h"
+#include "ssm_device.h"
 #include "ssm_wino7_pack.h"
 
 #include <atomic>
 #include <mutex>
 #include <type_traits>
 #include <cstdlib>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 #ifndef W7_VPAD
 #define W7_VPAD 0            // 1: position rows of V padded against the operand reads' bank conflict - measured 1 % SLOWER (profiles/r11d_wino7_vpad_ab.txt): off
@@ -162,15 +160,6 @@ __device__ __forceinline__ void w7_epilogue(const W7Params &p, Tile tile, const 
     const unsigned pb = 4u * ((unsigned)(4 * q) * (unsigned)p.dsc + (unsigned)py * (unsigned)p.dsh + (unsigned)px);
     const unsigned qb = 4u * ((unsigned)(4 * q) * (unsigned)p.psc + (unsigned)(py >> 1) * (unsigned)p.psh + (unsigned)(px >> 1));
     const bool vok = FAST || (py + 4 <= p.H && px + 4 <= p.W && p.vec);          // whole tile inside the map, rows as aligned 16-byte pieces
-    auto st4 = [](const float *base, unsigned off_bytes, f32x4 val) {
-        asm volatile("global_store_dwordx4 %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-    };
-    auto st2 = [](const float *base, unsigned off_bytes, f32x2 val) {
-        asm volatile("global_store_dwordx2 %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-    };
-    auto st1 = [](const float *base, unsigned off_bytes, float val) {
-        asm volatile("global_store_dword %0, %1, %2" ::"v"(off_bytes), "v"(val), "s"(base) : "memory");
-    };
     const float *addb = p.add ? p.add + (long long)(b / p.adiv) * p.asb + (long long)(4 * q) * p.asc + (long long)py * p.ash + px : nullptr;
     // the addend rows of cout r + 1 are requested while cout r is transformed (four independent 16-byte loads, one cout ahead): their
     // latency runs beside the output transform instead of in front of each cout's stores
@@ -203,11 +192,11 @@ __device__ __forceinline__ void w7_epilogue(const W7Params &p, Tile tile, const 
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             if (vok) {
-                st4(bp + (long long)i * p.dsh, pb, f32x4{y[i][0], y[i][1], y[i][2], y[i][3]});
+                store_sbase(bp + (long long)i * p.dsh, pb, f32x4{y[i][0], y[i][1], y[i][2], y[i][3]});
             } else {
 #pragma unroll
                 for (int e = 0; e < 4; ++e)      // edge path: one scalar base per cout (16 (row, element) bases at once overflow the scalar registers)
-                    if (py + i < p.H && px + e < p.W) st1(bp, pb + 4u * ((unsigned)i * (unsigned)p.dsh + (unsigned)e), y[i][e]);
+                    if (py + i < p.H && px + e < p.W) store_sbase(bp, pb + 4u * ((unsigned)i * (unsigned)p.dsh + (unsigned)e), y[i][e]);
             }
         }
         if (poolb) {
@@ -218,10 +207,10 @@ __device__ __forceinline__ void w7_epilogue(const W7Params &p, Tile tile, const 
                 const float o0 = ((y[2 * i][0] + y[2 * i + 1][0]) + (y[2 * i][1] + y[2 * i + 1][1])) * 0.25f;
                 const float o1 = ((y[2 * i][2] + y[2 * i + 1][2]) + (y[2 * i][3] + y[2 * i + 1][3])) * 0.25f;
                 const bool rok = FAST || py + 2 * i < p.H;
-                if (FAST || (rok && px + 4 <= p.W && p.vec)) st2(qp + (long long)i * p.psh, qb, f32x2{o0, o1});
+                if (FAST || (rok && px + 4 <= p.W && p.vec)) store_sbase(qp + (long long)i * p.psh, qb, f32x2{o0, o1});
                 else if (rok) {
-                    if (px + 2 <= p.W) st1(qp, qb + 4u * (unsigned)i * (unsigned)p.psh, o0);
-                    if (px + 4 <= p.W) st1(qp, qb + 4u * ((unsigned)i * (unsigned)p.psh + 1u), o1);
+                    if (px + 2 <= p.W) store_sbase(qp, qb + 4u * (unsigned)i * (unsigned)p.psh, o0);
+                    if (px + 4 <= p.W) store_sbase(qp, qb + 4u * ((unsigned)i * (unsigned)p.psh + 1u), o1);
                 }
             }
         }
@@ -340,21 +329,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int uoff = lane * 16;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void *)lds;
 
-    auto dma = [](const float *base, int voff_bytes, unsigned m0v) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_bytes), "s"(base), "s"(m0v) : "memory", "m0");
-    };
     // k-th filter piece of this wave for channel c into stage buf (= c & 1; k = 0 .. NIU-1); the patch piece of channel c into buffer buf
     auto dma_u = [&](int c, int k, int buf) {
         const int g = 4 * k + wid;
         const float *base = wbase + (long long)c * C::USZ + g * 256;
         const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(C::UOFF + buf * C::USZ) * 4u + (unsigned)g * 1024u);
-        dma(base, uoff, m0v);
+        lds_dma16(base, uoff, m0v);
     };
     auto dma_p = [&](int c, int buf) {
         if (wid < C::NGP) {
             const float *base = pbase + (long long)c * p.sc;
             const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(C::POFF + buf * C::PCAP + C::SHIFT) * 4u + (unsigned)wid * 1024u);
-            dma(base, poff, m0v);
+            lds_dma16(base, poff, m0v);
         }
     };
 
@@ -544,7 +530,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         const bool doR = steady || c + 2 < n;
         const bool doP = steady || c + 3 < n;
         W7STAMP(0)          // -> [0]: the iteration's work (matrix loop + transform pieces)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         W7STAMP(1)          // -> [1]: waiting for this wave's LDS-DMA
         __syncthreads();
         W7STAMP(2)          // -> [2]: waiting at the barrier
@@ -612,7 +598,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         else w7_epilogue<true, false, 4>(p, tile, bv, b, nb * 32 + cb * 16, 0, q, px, py);
     }
 #ifdef W7_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     W7STAMP(3)          // -> [3]: epilogue
     if (p.dbg && lane == 0 && (blockIdx.x % 64) == 0) {          // a sample of the workgroups
         for (int i = 0; i < 4; ++i) atomicAdd(p.dbg + wid * 8 + i, tph[i]);
@@ -706,20 +692,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int uoff = lane * 16;
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void *)lds;
 
-    auto dma = [](const float *base, int voff_bytes, unsigned m0v) {
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff_bytes), "s"(base), "s"(m0v) : "memory", "m0");
-    };
     auto dma_u = [&](int c, int k, int buf) {
         const int g = 4 * k + w4;
         const float *base = wbase + (long long)c * C::USZ + g * 256;
         const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(C::UOFF + buf * C::USZ) * 4u + (unsigned)g * 1024u);
-        dma(base, uoff, m0v);
+        lds_dma16(base, uoff, m0v);
     };
     auto dma_p = [&](int c, int buf) {
         if (w4 < C::NGP) {
             const float *base = pbase + (long long)c * p.sc;
             const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(C::POFF + buf * C::PCAP + C::SHIFT) * 4u + (unsigned)w4 * 1024u);
-            dma(base, poff, m0v);
+            lds_dma16(base, poff, m0v);
         }
     };
 
@@ -881,7 +864,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         const bool doP = steady || (c + 3 < n && c > -2);          // (the patch of channel 1 and the filter of channel 0 are requested up
         const bool doU = steady || (c + 1 < n && c >= 0);          //  front, with channel 0's patch)
         W7STAMP(0)
-        if (FH == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (FH == 0) wait_vmcnt<0>();
         W7STAMP(1)
         __syncthreads();
         W7STAMP(2)
@@ -985,7 +968,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         else fin(std::integral_constant<int, 2>{});
     }
 #ifdef W7_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     W7STAMP(3)
     if (p.dbg && lane == 0 && (blockIdx.x % 64) == 0) {
         for (int i = 0; i < 4; ++i) atomicAdd(p.dbg + wid * 8 + i, tph[i]);
