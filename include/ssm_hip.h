@@ -543,6 +543,41 @@ size_t ssm_frame_metrics_workspace_bytes(int N, int H, int W);
 int ssm_frame_metrics_fwd(const unsigned char *target_hwc, const unsigned char *output_hwc, int N, int H, int W,
                           void *workspace, size_t workspace_bytes, double *out, void *stream);
 
+/* ---- optical-flow evaluation (csrc/ssm_flow.hip; fp32 flow in, float64 records / uint8 RGB out) -----------
+ * Both entry points read `flow`, a planar fp32 [N,2,*,*] view (channel 0 = u, 1 = v; a 2-channel slice of
+ * the 4-channel stage-1 output works through the view's strides), cropped at (top, left) to H x W: the crop of
+ * scripts/evaluate_optical_flow_results.py:63-65 (rows 6:442 of the 448-row Sintel canvas).  Two launches each,
+ * no atomics: bitwise repeatable, and field n's result does not depend on N, the stream or the run.  The
+ * workspaces are device memory of the caller, *_workspace_bytes(N, H, W) bytes at least.
+ *
+ * ssm_flow_metrics_fwd: per field the sums behind compute_metrics (scripts/evaluate_optical_flow_results.py:
+ *   18-28; mode 0: every pixel counts) or behind the convention of flow_error (scripts/utils/flo_utils.py:
+ *   86-138; mode 1: pixels whose ground truth is unknown, |gt| > 1e7 in either component, or exactly zero in
+ *   both components are left out).  gt_hw2: contiguous [N,H,W,2] fp32, the layout of a .flo payload, 8-byte
+ *   aligned.  out is a DEVICE array [N][3] of float64:
+ *     out[n][0] = sum over the counted pixels of sqrt(du^2 + dv^2), every operation of the per-pixel error
+ *                 rounded to fp32 as numpy rounds it (no fused multiply-add), the sum in fp64
+ *     out[n][1] = number of counted pixels whose error is > 3 (an exact integer)
+ *     out[n][2] = number of counted pixels (an exact integer)
+ *   EPE = out[0] / out[2], share of pixels more than 3 px off = out[1] / out[2].
+ *   SSM_E_ARG for null pointers, N < 1 or > 65535, H or W < 1, a negative crop origin, a row stride shorter
+ *   than left + W, a mode other than 0 / 1, a misaligned gt_hw2 or a short workspace.
+ * ssm_flow_to_rgb_fwd: flow_to_image + compute_color + make_color_wheel (scripts/utils/flo_utils.py:141-272)
+ *   per field -> contiguous [N,H,W,3] uint8 RGB.  Unknown pixels (|u| or |v| > 1e7) are flow 0 and black, NaN
+ *   pixels black, as there.  Launch 1 reduces the field's maximum fp32 radius; launch 2 normalises by
+ *   (double)maxrad + 2^-52 and evaluates the map in fp64 like the reference does on numpy >= 2, the radius
+ *   un-fused so the `rad <= 1` branch is the reference's decision bit for bit; only atan2 may differ from
+ *   numpy's in its last bits.  A field that holds a NaN is divided by -1 + 2^-52 instead of its maximum
+ *   radius: np.max is NaN there and Python's max(-1, nan) returns -1 (flo_utils.py:166).
+ *   SSM_E_ARG for null pointers, N < 1 or > 65535, H or W < 1, a negative crop origin, a row stride shorter
+ *   than left + W or a short workspace. */
+size_t ssm_flow_metrics_workspace_bytes(int N, int H, int W);
+int ssm_flow_metrics_fwd(ssm_view flow, const float *gt_hw2, int N, int H, int W, int top, int left, int mode,
+                         void *workspace, size_t workspace_bytes, double *out, void *stream);
+size_t ssm_flow_to_rgb_workspace_bytes(int N, int H, int W);
+int ssm_flow_to_rgb_fwd(ssm_view flow, unsigned char *rgb_hwc, int N, int H, int W, int top, int left,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- backward kernels of the training step (fp32 planes; BASELINE config 3) ------------------------------
  * The data gradient of a convolution is ssm_conv2d_fwd on the transposed, spatially flipped filter.
  * ssm_lrelu_bwd           dz = (dy + 1/4 dpool[y/2][x/2]) * (y > 0 ? 1 : slope)   (dy or dpool may be NULL views;

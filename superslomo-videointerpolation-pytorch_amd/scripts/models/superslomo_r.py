@@ -144,6 +144,7 @@ class FullModel(nn.Module):
         self._engine = None
         self._pipe = None
         self._train = None
+        self._flow = None
 
     def load_weights(self):
         # quirk kept for drop-in behaviour: BOTH paths are gated on STAGE1.LOADPREV (superslomo_r.py:46-52)
@@ -224,6 +225,35 @@ class FullModel(nn.Module):
         t = _t_vector(t_values, img6.device)
         eng = self.engine_for(1, t.numel(), img6.shape[2], img6.shape[3], img6.device)
         return eng.run(img6, t, want_aux=False).clone()
+
+    def flow_plan_for(self, B, H, W, device):
+        """The stage-1 plan of estimate_flow(): built like PairEngine builds its own (same precision modes, same weight stamp as
+        engine_for), kept beside the pair engine so neither rebuilds nor overwrites the other.  Stage 2 is neither planned nor allocated."""
+        from ssm_amd.engine import UNetPlan
+        mode = self.precision or os.environ.get("SSM_PRECISION", DEFAULT_PRECISION)
+        key = ("flow", B, H, W, str(device), mode, self._stamp())
+        if getattr(self, "_flow", None) is None or self._flow[0] != key:
+            sd1 = {k: v.detach() for k, v in self.stage1_model.state_dict().items()}
+            self._flow = None
+            self._flow = (key, UNetPlan(1, sd1, B, H, W, device, self.cross_skip, mode))
+        return self._flow[1]
+
+    @torch.no_grad()
+    def estimate_flow(self, image_pair, want_planes=False):
+        """Stage 1 only, for N_FRAMES = 2: pairs [B,2,3,H,W] (or [B,6,H,W]) -> [B,4,H,W] = flowC_01 | flowC_10, bit for bit
+        `intermediate_outputs[0]` | `[1]` of forward(..., inference_mode=True) in the same precision mode - what
+        scripts/evaluate_optical_flow_results.py:57-59 keeps of a full forward.  want_planes=True returns the plan's own padded
+        planes (hipbind.Planes, 4 channels, no copy; valid until the next estimate_flow on this model) for the kernels of
+        ssm_amd.flow_eval, which read the flow where stage 1 left it."""
+        hb.require_device(image_pair, "image pair")
+        assert not self.recurrent, "estimate_flow() is for the CONV bottleneck (N_FRAMES = 2)"
+        assert image_pair.dim() in (4, 5) and image_pair.shape[1:-2].numel() == 6, \
+            "estimate_flow() takes pairs [B,2,3,H,W] or [B,6,H,W]; got %s" % (tuple(image_pair.shape),)
+        img6 = image_pair.reshape(image_pair.shape[0], 6, *image_pair.shape[-2:]).contiguous()
+        plan = self.flow_plan_for(img6.shape[0], img6.shape[2], img6.shape[3], img6.device)
+        plan.t["in"].load(img6)
+        out = plan.run()
+        return out if want_planes else out.to_nchw()
 
     @torch.no_grad()
     def interpolate_many(self, pairs, t_values, n_streams=2, pairs_per_batch=1):

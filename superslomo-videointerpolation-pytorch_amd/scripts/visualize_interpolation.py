@@ -8,7 +8,9 @@ naming: <output_dir>/<expt>/images/img_00000.png, originals and intermediates in
 
 Differences from the reference, on purpose: frames are cropped back to their original size before they are written
 (the reference writes the zero-padded canvas), PIL replaces cv2 (not installed here), flow maps are saved as raw .npy
-instead of colour-wheel PNGs (flo_utils is out of scope), and N_FRAMES must be 2 (CONV bottleneck).
+(with --flow_png also as the reference's colour-wheel PNGs, colour-coded on the GPU by ssm_amd.flow_eval.flow_to_rgb under the
+reference's directory names; the files are true RGB, where the reference hands flow_to_image's RGB array to cv2.imwrite, which
+takes it as BGR, so its colour maps have R and B swapped), and N_FRAMES must be 2 (CONV bottleneck).
 """
 import argparse
 import configparser
@@ -45,6 +47,8 @@ def getargs(argv=None):
     parser.add_argument("--show_intermediate_outputs", action="store_true",
                         help="Save occlusion maps, optical flow maps etc.?")
     parser.add_argument("--output_dir", required=True, help="Directory to output.")
+    parser.add_argument("--flow_png", action="store_true",
+                        help="With --show_intermediate_outputs: also save the flows as Middlebury colour-wheel PNGs.")
     return parser.parse_args(argv)
 
 
@@ -64,6 +68,13 @@ class Interpolator:
         if args.show_intermediate_outputs:
             os.makedirs(self.visibility_dir, exist_ok=True)
             os.makedirs(self.flow_dir, exist_ok=True)
+        # the reference's colour-map directories (visualize_interpolation.py:90-103), opt-in
+        self.flow_png = bool(getattr(args, "flow_png", False)) and args.show_intermediate_outputs
+        self.flow_png_dirs = {name: os.path.join(base, name)
+                              for name in ("estimated_flow_01", "estimated_flow_10", "refined_flow_t1", "refined_flow_t0")}
+        if self.flow_png:
+            for d in self.flow_png_dirs.values():
+                os.makedirs(d, exist_ok=True)
 
     @staticmethod
     def load_frames(paths):
@@ -73,6 +84,11 @@ class Interpolator:
     def save(self, img_u8, count, out_dir, prefix="img"):
         from PIL import Image
         Image.fromarray(img_u8).save(os.path.join(out_dir, prefix + "_" + str(count).zfill(5) + ".png"))
+
+    def save_flow_png(self, flow, h, w, top, left, count, name, prefix):
+        """save_img_from_tensor(..., flo_img=True) (visualize_interpolation.py:223-232): the cropped [1,2,*,*] flow as a colour map."""
+        from ssm_amd.flow_eval import flow_to_rgb
+        self.save(flow_to_rgb(flow, h, w, top, left)[0].cpu().numpy(), count, self.flow_png_dirs[name], prefix)
 
     @torch.no_grad()
     def interpolate_frames(self):
@@ -113,9 +129,17 @@ class Interpolator:
                             inter[4][0, :, top:top + h, left:left + w].cpu().numpy())
                     np.save(os.path.join(self.flow_dir, "flow_t0_%05d.npy" % count),
                             inter[5][0, :, top:top + h, left:left + w].cpu().numpy())
+                    if self.flow_png:          # refined flows per t (:168-182)
+                        self.save_flow_png(inter[4], h, w, top, left, count, "refined_flow_t1", "flow_t1")
+                        self.save_flow_png(inter[5], h, w, top, left, count, "refined_flow_t0", "flow_t0")
                     self.save(F.frames_to_u8(img, h, w, self.cfg)[0].cpu().numpy(), count, self.img_dir)
                     log.info("Interpolated frame: %s", count)
                     count += 1
+                if self.flow_png and outs[k]:          # the pair's stage-1 flows, once, under the next original's number (:203-210)
+                    inter = outs[k][-1][1]
+                    top, left = (inter[0].shape[2] - h) // 2, (inter[0].shape[3] - w) // 2
+                    self.save_flow_png(inter[0], h, w, top, left, count, "estimated_flow_01", "Flow_01")
+                    self.save_flow_png(inter[1], h, w, top, left, count, "estimated_flow_10", "Flow_10")
             else:
                 u8 = F.frames_to_u8(outs[k], h, w, self.cfg).cpu().numpy()
                 for j in range(u8.shape[0]):
