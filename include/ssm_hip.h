@@ -525,6 +525,53 @@ int ssm_frames_from_u8_fwd(const unsigned char *frames_hwc, ssm_view out, int N,
 int ssm_frames_to_u8_fwd(ssm_view in, unsigned char *frames_hwc, int N, int H, int W, int top, int left,
                          const float *mean3, const float *std3, int mode, void *stream);
 
+/* ---- video frame formats (csrc/ssm_video.hip; 8-bit planar Y'CbCr on the device) -----------------------
+ * The streamed video loop (ssm_amd/video.py) serves the visualiser's convention, scripts/visualize_interpolation.py:
+ * 61-88 (load_batch: frames padded to a multiple of 32, then normalised) and :223-268 (save_img_from_tensor,
+ * normalize_tensor, denormalize), for frames that arrive as YUV4MPEG2 payloads instead of decoded RGB files.
+ * A frame is the Y plane H x W, then U, then V, each ceil(H/2) x ceil(W/2) (SSM_YUV_420_*) or H x W (SSM_YUV_444),
+ * rows unpadded; N frames are contiguous.  `table` is a HOST pointer to [2 matrices][2 ranges][SSM_YUV_ROW] floats,
+ * built once in float64 and rounded to fp32 by ssm_amd.video.yuv_table(); row (matrix, range) holds
+ *   [0..2] Kr Kg Kb    [3..6] rv = 2(1-Kr), gu = 2(1-Kb)Kb/Kg, gv = 2(1-Kr)Kr/Kg, bu = 2(1-Kb)
+ *   [7..8] cbs = 1/(2(1-Kb)), crs = 1/(2(1-Kr))    [9..10] ys, cs = 255/219, 255/224 (limited) or 1, 1 (full)
+ *   [11..12] iys, ics = 219/255, 224/255 or 1, 1    [13..14] yoff = 16 or 0, coff = 128
+ *   [15..18] ylo yhi clo chi = 16 235 16 240 or 0 255 0 255    [19] 0
+ * mean3 / std3 as for ssm_frames_from_u8_fwd.  Every operation below is one fp32 operation, rounded (no fused
+ * multiply-add), in the order written.
+ * ssm_frames_from_yuv_fwd: -> normalised fp32 [N,3,Hp,Wp] behind `out`, image at (top,left), pad value as
+ *   ssm_frames_from_u8_fwd (pad_before_norm).  Per pixel (y,x):
+ *     chroma: 4:4:4 c = C[y][x].  4:2:0, with i = y/2, j = x/2 and indices clamped to the plane:
+ *       h(r, x even) = a0 C[r][j-1] + a1 C[r][j],   h(r, x odd) = b1 C[r][j] + b2 C[r][j+1]
+ *       (a0 a1 b1 b2) = (.25 .75 .75 .25) SSM_YUV_420_CENTRED (420jpeg, 420), (0 1 .5 .5) SSM_YUV_420_COSITED (420mpeg2)
+ *       c = .25 h(i-1) + .75 h(i) (y even),   .75 h(i) + .25 h(i+1) (y odd)
+ *     y' = (Y - yoff) ys;  cb = (c_u - coff) cs;  cr = (c_v - coff) cs
+ *     R = y' + rv cr;  G = (y' - gu cb) - gv cr;  B = y' + bu cb
+ *     out = (min(max(v, 0), 255) / 255 - mean) / std   for v = R, G, B
+ * ssm_frames_to_yuv_fwd: normalised fp32 [N,3,*,*] -> the H x W crop at (top,left) as N contiguous payloads.
+ *   INPUTS MUST BE FINITE.  Per pixel: v = (in std + mean) 255 for R, G, B;
+ *     Yf = (Kr R + Kg G) + Kb B;  Cb = (B - Yf) cbs;  Cr = (R - Yf) crs
+ *     chroma sample (cy,cx) of 4:2:0, luma indices clamped to the crop:
+ *       SSM_YUV_420_CENTRED  ((C[2cy][2cx] + C[2cy][2cx+1]) + (C[2cy+1][2cx] + C[2cy+1][2cx+1])) .25
+ *       SSM_YUV_420_COSITED  h(r) = ((C[r][2cx-1] + 2 C[r][2cx]) + C[r][2cx+1]) .25;  (h(2cy) + h(2cy+1)) .5
+ *     code = min(max(rint(Yf iys + yoff), ylo), yhi),   min(max(rint(C ics + coff), clo), chi)   (round half to even)
+ * SSM_E_ARG for null pointers, N < 1 or > 65535, H or W < 1, a negative offset, a canvas smaller than the image
+ * plus its offset, a row stride shorter than the canvas (ingest) or than left + W (egress), or a matrix, range
+ * or siting outside the values below. */
+#define SSM_YUV_ROW 20
+#define SSM_YUV_BT601 0
+#define SSM_YUV_BT709 1
+#define SSM_YUV_LIMITED 0
+#define SSM_YUV_FULL 1
+#define SSM_YUV_420_CENTRED 0
+#define SSM_YUV_420_COSITED 1
+#define SSM_YUV_444 2
+int ssm_frames_from_yuv_fwd(const unsigned char *frames_yuv, ssm_view out, int N, int H, int W, int Hp, int Wp,
+                            int top, int left, const float *mean3, const float *std3, int pad_before_norm,
+                            const float *table, int matrix, int range, int siting, void *stream);
+int ssm_frames_to_yuv_fwd(ssm_view in, unsigned char *frames_yuv, int N, int H, int W, int top, int left,
+                          const float *mean3, const float *std3, const float *table, int matrix, int range,
+                          int siting, void *stream);
+
 /* ---- evaluator metrics of uint8 frames (an exception to the fp32-tensor convention: uint8 in, float64 out) ----
  * ssm_frame_metrics_fwd: per frame of two contiguous [N,H,W,3] uint8 stacks (what ssm_frames_to_u8_fwd
  *   writes) the sums behind Evaluator.eval_single_image (scripts/evaluate_interpolation_results.py:101-108:

@@ -1,0 +1,332 @@
+// 8-bit planar Y'CbCr video frames <-> the path's normalised, padded fp32 planes: the two conversions either side of the streamed
+// video loop (ssm_amd/video.py), next to frames_from_u8_kernel / frames_to_u8_kernel of ssm_elem.hip, whose geometry (centred pad to
+// x32, pad_before_norm in both conventions: scripts/visualize_interpolation.py:61-88, scripts/utils/dataloaders/augmentations.py:
+// 141-200) and whose normalise / denormalise expressions they keep.  A frame is the payload of a YUV4MPEG2 FRAME record: the Y plane
+// H x W, then U, then V, each ceil(H/2) x ceil(W/2) (4:2:0) or H x W (4:4:4), no row padding; N frames are contiguous.
+//   frames_from_yuv_kernel   one thread per 2 x 2 luma block: 3 x 3 chroma samples per plane (clamped at the edges) give the block's
+//                            four bilinearly upsampled chroma values; range, matrix, clamp, normalise; two floats per row and plane
+//                            go out as one 8-byte store when the view allows it
+//   frames_to_yuv_kernel     one thread per 4 x 2 luma block = two chroma samples: denormalise, matrix, chroma filtered and subsampled
+//                            in float, range, round half to even, saturate; four Y codes of a row go out as one 32-bit store, the two
+//                            chroma codes of a plane as one 16-bit store, when the frame size allows it
+// Both are HBM-bound (1.5 B in + 12 B out per pixel, and the reverse).  The chroma siting enters as four horizontal weights (ingest)
+// or one switch (egress); matrix and range enter as one row of the constant table built by ssm_amd/video.py, which the host yardsticks
+// read too.  Inputs of the egress kernel are finite.
+// NO CONTRACTION (as ssm_flow.hip): the numpy yardsticks round every operation, and so must the kernels.
+#include "ssm_common.h"
+#include "ssm_device.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+// one row of the constant table (include/ssm_hip.h: SSM_YUV_ROW floats per (matrix, range))
+struct YuvRow {
+    float kr, kg, kb;            // luma weights
+    float rv, gu, gv, bu;        // Y'CbCr -> R'G'B'
+    float cbs, crs;              // 1 / (2 (1 - Kb)), 1 / (2 (1 - Kr))
+    float ys, cs;                // code -> full scale: 255/219, 255/224 (limited) or 1
+    float iys, ics;              // full scale -> code: 219/255, 224/255 or 1
+    float yoff, coff;            // 16 | 0, 128
+    float ylo, yhi, clo, chi;    // saturation bounds of the codes
+    float reserved;
+};
+static_assert(sizeof(YuvRow) == SSM_YUV_ROW * sizeof(float), "table row");
+
+struct Norm3 {
+    float m[3], s[3];
+};
+
+__device__ __forceinline__ float *vp(const ssm_view &v, int b, int c, int y) {
+    return v.ptr + (long long)b * v.sb + (long long)c * v.sc + (long long)y * v.sh;
+}
+
+__device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+
+// ---- ingest ------------------------------------------------------------------------------------------------------------------------
+// wx = {a0, a1, b1, b2}: chroma at an even luma column 2j = a0 c[j-1] + a1 c[j], at an odd one = b1 c[j] + b2 c[j+1]
+// (centred siting .25 .75 .75 .25; co-sited with the even columns 0 1 .5 .5).  Rows are centred in both sitings.
+// Thread (bx, by) owns the luma block at source (2 by - T2, 2 bx - L2), T2 / L2 = top / left rounded up to even, so that blocks are
+// aligned with the chroma grid wherever the image sits in the canvas; canvas pixels outside the image get the pad value.
+template <bool C444>
+__global__ __launch_bounds__(256) void frames_from_yuv_kernel(const unsigned char *__restrict__ in, ssm_view out, int H, int W, int Hp, int Wp,
+                                                              int top, int left, long long frame_bytes, YuvRow k, Norm3 nm, float a0,
+                                                              float a1, float b1, float b2, int pad_before_norm, int vec2) {
+    const int bx = blockIdx.x * 64 + threadIdx.x, by = blockIdx.y * 4 + threadIdx.y, b = blockIdx.z;
+    const int sx0 = 2 * bx - ((left + 1) & ~1), sy0 = 2 * by - ((top + 1) & ~1);          // source position of the block
+    const int ox0 = sx0 + left, oy0 = sy0 + top;                                         // canvas position (-1 possible)
+    if (ox0 >= Wp || oy0 >= Hp) return;
+    const int cw = C444 ? W : (W + 1) >> 1, ch = C444 ? H : (H + 1) >> 1;
+    const unsigned char *yp = in + (long long)b * frame_bytes;
+    const unsigned char *up = yp + (long long)H * W, *vpl = up + (long long)ch * cw;
+    float o[3][2][2];          // [plane][row][col]
+    const bool any = sx0 + 1 >= 0 && sx0 < W && sy0 + 1 >= 0 && sy0 < H;
+    float cu[2][2], cv[2][2];  // upsampled chroma of the block
+    if (any) {
+        if (C444) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {
+                    const int y = min(max(sy0 + r, 0), H - 1), x = min(max(sx0 + c, 0), W - 1);
+                    cu[r][c] = (float)up[(long long)y * W + x];
+                    cv[r][c] = (float)vpl[(long long)y * W + x];
+                }
+        } else {
+            const int j = sx0 >> 1, i = sy0 >> 1;          // sx0, sy0 even (arithmetic shift: -2 -> -1)
+            int xs[3], ys[3];
+#pragma unroll
+            for (int t = 0; t < 3; ++t) {
+                xs[t] = min(max(j - 1 + t, 0), cw - 1);
+                ys[t] = min(max(i - 1 + t, 0), ch - 1);
+            }
+            float hu[3][2], hv[3][2];          // horizontally interpolated: [chroma row][even | odd luma column]
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const unsigned char *ur = up + (long long)ys[r] * cw, *vr = vpl + (long long)ys[r] * cw;
+                const float u0 = (float)ur[xs[0]], u1 = (float)ur[xs[1]], u2 = (float)ur[xs[2]];
+                const float v0 = (float)vr[xs[0]], v1 = (float)vr[xs[1]], v2 = (float)vr[xs[2]];
+                hu[r][0] = a0 * u0 + a1 * u1;
+                hu[r][1] = b1 * u1 + b2 * u2;
+                hv[r][0] = a0 * v0 + a1 * v1;
+                hv[r][1] = b1 * v1 + b2 * v2;
+            }
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                cu[0][c] = 0.25f * hu[0][c] + 0.75f * hu[1][c];
+                cu[1][c] = 0.75f * hu[1][c] + 0.25f * hu[2][c];
+                cv[0][c] = 0.25f * hv[0][c] + 0.75f * hv[1][c];
+                cv[1][c] = 0.75f * hv[1][c] + 0.25f * hv[2][c];
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int sy = sy0 + r, sx = sx0 + c;
+            const bool inside = any && sy >= 0 && sy < H && sx >= 0 && sx < W;
+            if (inside) {
+                const float yl = ((float)yp[(long long)sy * W + sx] - k.yoff) * k.ys;
+                const float cb = (cu[r][c] - k.coff) * k.cs, cr = (cv[r][c] - k.coff) * k.cs;
+                float rgb[3];
+                rgb[0] = yl + k.rv * cr;
+                rgb[1] = (yl - k.gu * cb) - k.gv * cr;
+                rgb[2] = yl + k.bu * cb;
+#pragma unroll
+                for (int p = 0; p < 3; ++p) o[p][r][c] = (clampf(rgb[p], 0.0f, 255.0f) / 255.0f - nm.m[p]) / nm.s[p];
+            } else {
+#pragma unroll
+                for (int p = 0; p < 3; ++p) o[p][r][c] = pad_before_norm ? (0.0f / 255.0f - nm.m[p]) / nm.s[p] : 0.0f;
+            }
+        }
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int oy = oy0 + r;
+            if (oy < 0 || oy >= Hp) continue;
+            float *row = vp(out, b, p, oy);
+            if (vec2 && ox0 + 1 < Wp) {          // vec2: left even (ox0 >= 0 and even), 8-byte aligned view
+                f32x2 v;
+                v.x = o[p][r][0];
+                v.y = o[p][r][1];
+                *reinterpret_cast<f32x2 *>(row + ox0) = v;
+            } else {
+                if (ox0 >= 0) row[ox0] = o[p][r][0];
+                if (ox0 + 1 < Wp) row[ox0 + 1] = o[p][r][1];
+            }
+        }
+}
+
+// ---- egress ------------------------------------------------------------------------------------------------------------------------
+// Thread (bx, by) owns the luma block at (2 by, 4 bx) of the H x W crop.  Columns / rows past the crop (odd sizes) repeat the last one.
+struct Ycc {
+    float y, cb, cr;
+};
+__device__ __forceinline__ Ycc to_ycc(float r, float g, float b, const YuvRow &k) {
+    Ycc o;
+    o.y = (k.kr * r + k.kg * g) + k.kb * b;
+    o.cb = (b - o.y) * k.cbs;
+    o.cr = (r - o.y) * k.crs;
+    return o;
+}
+__device__ __forceinline__ float denorm(float v, float sd, float mean) {
+    float t = v * sd + mean;
+    t = t * 255.0f;
+    return t;
+}
+__device__ __forceinline__ unsigned code_of(float v, float scale, float off, float lo, float hi) {
+    return (unsigned)(int)clampf(rintf(v * scale + off), lo, hi);
+}
+
+template <bool C444>
+__global__ __launch_bounds__(256) void frames_to_yuv_kernel(ssm_view in, unsigned char *__restrict__ out, int H, int W, int top, int left,
+                                                            long long frame_bytes, YuvRow k, Norm3 nm, int cosited, int vec_in, int vec_out) {
+    const int bx = blockIdx.x * 64 + threadIdx.x, by = blockIdx.y * 4 + threadIdx.y, b = blockIdx.z;
+    const int x0 = 4 * bx, y0 = 2 * by;
+    if (x0 >= W || y0 >= H) return;
+    const int cw = C444 ? W : (W + 1) >> 1, ch = C444 ? H : (H + 1) >> 1;
+    unsigned char *yp = out + (long long)b * frame_bytes;
+    unsigned char *up = yp + (long long)H * W, *vpl = up + (long long)ch * cw;
+    const bool whole = x0 + 3 < W;
+    Ycc px[2][5];          // [row][column x0-1 (co-sited only), x0 .. x0+3]
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int y = min(y0 + r, H - 1) + top;
+        float v[3][5];
+#pragma unroll
+        for (int p = 0; p < 3; ++p) {
+            const float *row = vp(in, b, p, y) + left;
+            if (vec_in && whole) {          // vec_in: 16-byte aligned rows at x0
+                const f32x4 q = *reinterpret_cast<const f32x4 *>(row + x0);
+                v[p][1] = q.x, v[p][2] = q.y, v[p][3] = q.z, v[p][4] = q.w;
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) v[p][1 + c] = row[min(x0 + c, W - 1)];
+            }
+            v[p][0] = (cosited && !C444) ? row[max(x0 - 1, 0)] : 0.0f;
+        }
+#pragma unroll
+        for (int c = 0; c < 5; ++c)
+            px[r][c] = to_ycc(denorm(v[0][c], nm.s[0], nm.m[0]), denorm(v[1][c], nm.s[1], nm.m[1]), denorm(v[2][c], nm.s[2], nm.m[2]), k);
+    }
+    // luma (and, 4:4:4, chroma) codes: four per row
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const int y = y0 + r;
+        if (y >= H) continue;
+#pragma unroll
+        for (int p = 0; p < (C444 ? 3 : 1); ++p) {
+            unsigned q[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const Ycc &s = px[r][1 + c];
+                q[c] = p == 0 ? code_of(s.y, k.iys, k.yoff, k.ylo, k.yhi) : code_of(p == 1 ? s.cb : s.cr, k.ics, k.coff, k.clo, k.chi);
+            }
+            unsigned char *dst = (p == 0 ? yp : (p == 1 ? up : vpl)) + (long long)y * W + x0;
+            if (vec_out && whole) {          // vec_out: W % 4 == 0 and 4-byte aligned planes
+                *reinterpret_cast<unsigned *>(dst) = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (x0 + c < W) dst[c] = (unsigned char)q[c];
+            }
+        }
+    }
+    if (C444) return;
+    // the block's two chroma samples: filter in float, then range, rounding, saturation
+    unsigned qu[2], qv[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int c = 1 + 2 * j;          // px column of luma column 2 (cx) = x0 + 2 j
+        float cb, cr;
+        if (cosited) {                    // [1 2 1] / 4 over columns 2 cx - 1 .. 2 cx + 1, then the mean of the two rows
+            float hb[2], hr[2];
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                hb[r] = ((px[r][c - 1].cb + 2.0f * px[r][c].cb) + px[r][c + 1].cb) * 0.25f;
+                hr[r] = ((px[r][c - 1].cr + 2.0f * px[r][c].cr) + px[r][c + 1].cr) * 0.25f;
+            }
+            cb = (hb[0] + hb[1]) * 0.5f;
+            cr = (hr[0] + hr[1]) * 0.5f;
+        } else {                          // 2 x 2 mean
+            cb = ((px[0][c].cb + px[0][c + 1].cb) + (px[1][c].cb + px[1][c + 1].cb)) * 0.25f;
+            cr = ((px[0][c].cr + px[0][c + 1].cr) + (px[1][c].cr + px[1][c + 1].cr)) * 0.25f;
+        }
+        qu[j] = code_of(cb, k.ics, k.coff, k.clo, k.chi);
+        qv[j] = code_of(cr, k.ics, k.coff, k.clo, k.chi);
+    }
+    const int cx = x0 >> 1, cy = y0 >> 1;
+    unsigned char *du = up + (long long)cy * cw + cx, *dv = vpl + (long long)cy * cw + cx;
+    if (vec_out && cx + 1 < cw) {          // W % 4 == 0: cw even, cx even
+        *reinterpret_cast<unsigned short *>(du) = (unsigned short)(qu[0] | (qu[1] << 8));
+        *reinterpret_cast<unsigned short *>(dv) = (unsigned short)(qv[0] | (qv[1] << 8));
+    } else {
+        du[0] = (unsigned char)qu[0];
+        dv[0] = (unsigned char)qv[0];
+        if (cx + 1 < cw) {
+            du[1] = (unsigned char)qu[1];
+            dv[1] = (unsigned char)qv[1];
+        }
+    }
+}
+
+inline bool view_aligned(const ssm_view &v, int floats) {
+    return (reinterpret_cast<size_t>(v.ptr) % (floats * sizeof(float))) == 0 && v.sh % floats == 0 && v.sc % floats == 0 && v.sb % floats == 0;
+}
+
+inline Norm3 norm_of(const float *mean3, const float *std3) {
+    Norm3 n;
+    for (int c = 0; c < 3; ++c) n.m[c] = mean3[c], n.s[c] = std3[c];
+    return n;
+}
+
+inline YuvRow row_of(const float *table, int matrix, int range) {
+    YuvRow r;
+    const float *src = table + (matrix * 2 + range) * SSM_YUV_ROW;
+    float *dst = reinterpret_cast<float *>(&r);
+    for (int i = 0; i < SSM_YUV_ROW; ++i) dst[i] = src[i];
+    return r;
+}
+
+}  // namespace
+
+#define SSM_CHECK_YUV(name)                                                                                                       \
+    SSM_REQUIRE((matrix == SSM_YUV_BT601 || matrix == SSM_YUV_BT709) && (range == SSM_YUV_LIMITED || range == SSM_YUV_FULL),      \
+                name ": matrix %d / range %d not in {0, 1}", matrix, range);                                                      \
+    SSM_REQUIRE(siting == SSM_YUV_420_CENTRED || siting == SSM_YUV_420_COSITED || siting == SSM_YUV_444,                          \
+                name ": chroma siting %d not in {0, 1, 2}", siting)
+
+// bytes of one frame's payload
+static long long yuv_frame_bytes(int H, int W, int siting) {
+    const long long c = siting == SSM_YUV_444 ? (long long)H * W : (long long)((H + 1) / 2) * ((W + 1) / 2);
+    return (long long)H * W + 2 * c;
+}
+
+extern "C" int ssm_frames_from_yuv_fwd(const unsigned char *frames_yuv, ssm_view out, int N, int H, int W, int Hp, int Wp, int top, int left,
+                                       const float *mean3, const float *std3, int pad_before_norm, const float *table, int matrix,
+                                       int range, int siting, void *stream) {
+    SSM_REQUIRE(frames_yuv && out.ptr && mean3 && std3 && table, "frames_from_yuv: null pointer");
+    SSM_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && top >= 0 && left >= 0 && Hp >= H + top && Wp >= W + left && out.sh >= Wp &&
+                    (Hp + 9) / 8 <= 65535,
+                "frames_from_yuv: bad geometry %dx%d -> %dx%d at (%d,%d), row stride %d", H, W, Hp, Wp, top, left, out.sh);
+    SSM_CHECK_YUV("frames_from_yuv");
+    const bool cos = siting == SSM_YUV_420_COSITED;
+    const float a0 = cos ? 0.0f : 0.25f, a1 = cos ? 1.0f : 0.75f, b1 = cos ? 0.5f : 0.75f, b2 = cos ? 0.5f : 0.25f;
+    const int vec2 = (left % 2 == 0 && view_aligned(out, 2)) ? 1 : 0;
+    // blocks per axis: the canvas plus the one-pixel shift of an odd offset
+    const int nbx = (Wp + (left & 1) + 1) / 2, nby = (Hp + (top & 1) + 1) / 2;
+    const dim3 grid((nbx + 63) / 64, (nby + 3) / 4, N);
+    const long long fb = yuv_frame_bytes(H, W, siting);
+    if (siting == SSM_YUV_444)
+        SSM_LAUNCH(frames_from_yuv_kernel<true>, grid, dim3(64, 4), 0, (hipStream_t)stream, frames_yuv, out, H, W, Hp, Wp, top, left, fb,
+                   row_of(table, matrix, range), norm_of(mean3, std3), a0, a1, b1, b2, pad_before_norm ? 1 : 0, vec2);
+    else
+        SSM_LAUNCH(frames_from_yuv_kernel<false>, grid, dim3(64, 4), 0, (hipStream_t)stream, frames_yuv, out, H, W, Hp, Wp, top, left, fb,
+                   row_of(table, matrix, range), norm_of(mean3, std3), a0, a1, b1, b2, pad_before_norm ? 1 : 0, vec2);
+    return ssm::check_launch("ssm_frames_from_yuv_fwd");
+}
+
+extern "C" int ssm_frames_to_yuv_fwd(ssm_view in, unsigned char *frames_yuv, int N, int H, int W, int top, int left, const float *mean3,
+                                     const float *std3, const float *table, int matrix, int range, int siting, void *stream) {
+    SSM_REQUIRE(frames_yuv && in.ptr && mean3 && std3 && table, "frames_to_yuv: null pointer");
+    SSM_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && top >= 0 && left >= 0 && in.sh >= W + left && (H + 7) / 8 <= 65535,
+                "frames_to_yuv: bad geometry %dx%d at (%d,%d), row stride %d", H, W, top, left, in.sh);
+    SSM_CHECK_YUV("frames_to_yuv");
+    const long long fb = yuv_frame_bytes(H, W, siting);
+    const int vec_in = (left % 4 == 0 && view_aligned(in, 4)) ? 1 : 0;
+    // W % 4 == 0 keeps every row of every plane (chroma rows are W / 2 bytes, and 16-bit stores need only W / 2 even) and every frame aligned
+    const int vec_out = (W % 4 == 0 && reinterpret_cast<size_t>(frames_yuv) % 4 == 0 && ((long long)H * W) % 4 == 0 && fb % 4 == 0 &&
+                         (((long long)((H + 1) / 2) * (W / 2)) % 2 == 0 || siting == SSM_YUV_444))
+                            ? 1
+                            : 0;
+    const dim3 grid(((W + 3) / 4 + 63) / 64, ((H + 1) / 2 + 3) / 4, N);
+    if (siting == SSM_YUV_444)
+        SSM_LAUNCH(frames_to_yuv_kernel<true>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, frames_yuv, H, W, top, left, fb,
+                   row_of(table, matrix, range), norm_of(mean3, std3), 0, vec_in, vec_out);
+    else
+        SSM_LAUNCH(frames_to_yuv_kernel<false>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, frames_yuv, H, W, top, left, fb,
+                   row_of(table, matrix, range), norm_of(mean3, std3), siting == SSM_YUV_420_COSITED ? 1 : 0, vec_in, vec_out);
+    return ssm::check_launch("ssm_frames_to_yuv_fwd");
+}

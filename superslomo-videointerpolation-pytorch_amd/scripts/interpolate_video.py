@@ -1,0 +1,71 @@
+#!/usr/bin/env python3
+"""Slow-motion video, streamed: a YUV4MPEG2 (.y4m) file or pipe in, one out, with upsample_rate - 1 interpolated frames between every two
+input frames.  Y4M is the container every player and ffmpeg read and write without a codec, pipes included:
+
+    ffmpeg -i clip.mp4 -f yuv4mpegpipe - | interpolate_video.py -c cfg.ini --expt e --log run.log --input - --output - | ffplay -
+
+  Y4M payload -> pinned host memory -> GPU -> ingest kernel (chroma upsampling, range, matrix, normalise, pad to x32)   [ssm_amd.video]
+      -> the pair pipeline (stage 1 once per pair, all t batched, passes on 2 HIP streams)
+      -> egress kernel (crop, denormalise, matrix, chroma subsampling, range, rounding) -> pinned host memory -> Y4M payload
+
+Memory does not grow with the clip (scripts/visualize_interpolation.py, the PNG tool, holds the whole clip on the GPU).  Input frames
+pass to the output as their own bytes.  The output's frame rate is the input's times upsample_rate - the same duration, smoother - or,
+with --slowmo, the input's: the same frames played upsample_rate times slower.  8-bit 4:2:0 (both sitings) and 4:4:4 only; N_FRAMES must
+be 2, as for the PNG tool.
+"""
+import argparse
+import configparser
+import logging
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+for _p in (os.path.dirname(HERE), HERE):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+from models import superslomo_r as ssm  # noqa: E402
+from ssm_amd import video as V  # noqa: E402
+
+log = logging.getLogger(__name__)
+
+
+def getargs(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument("-c", "--config", required=True, default="config.ini", help="Path to config.ini file.")
+    parser.add_argument("--expt", required=True, help="Experiment Name.")
+    parser.add_argument("--log", required=True, help="Path to logfile.")
+    parser.add_argument("--input", required=True, help="Input .y4m file, or - for stdin.")
+    parser.add_argument("--output", required=True, help="Output .y4m file, or - for stdout.")
+    parser.add_argument("--upsample_rate", type=int, default=8,
+                        help="Integer upsampling rate. For 30FPS -> 240FP, use 8. For 1080FPS, use 36.")
+    parser.add_argument("--matrix", choices=sorted(V.MATRICES), default=None, help="Y'CbCr matrix (default: bt709 from 720 rows up, else bt601).")
+    parser.add_argument("--range", choices=sorted(V.RANGES), default=None, dest="color_range",
+                        help="Code range (default: the header's XCOLORRANGE tag, else limited).")
+    parser.add_argument("--slowmo", action="store_true", help="Keep the input's frame rate in the output header: slow motion.")
+    return parser.parse_args(argv)
+
+
+def main(argv=None, model=None):
+    args = getargs(argv)
+    config = configparser.RawConfigParser()
+    logging.basicConfig(filename=args.log, level=logging.INFO)
+    if not config.read(args.config):
+        raise FileNotFoundError(args.config)
+    matrix = None if args.matrix is None else V.MATRICES[args.matrix]
+    crange = None if args.color_range is None else V.RANGES[args.color_range]
+    model = (model if model is not None else ssm.FullModel(config)).cuda().eval()
+    vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate, matrix=matrix, color_range=crange)
+    with V.Y4MReader(args.input) as reader:
+        rate = V.output_rate(reader.rate, args.upsample_rate, args.slowmo)
+        out_range = crange if crange is not None else (reader.color_range if reader.color_range is not None else V.LIMITED)
+        log.info("[%s] %s: %dx%d C%s at %d:%d frames/s -> %s at %d:%d", args.expt, args.input, reader.width, reader.height, reader.chroma,
+                 reader.rate[0], reader.rate[1], args.output, rate[0], rate[1])
+        with V.Y4MWriter.like(args.output, reader, rate=rate, color_range=out_range) as writer:
+            n = vi.run(reader, writer)
+    log.info("Interpolation complete: %d frames written.", n)
+    return n
+
+
+if __name__ == "__main__":
+    main()

@@ -130,6 +130,11 @@ SIGNATURES = {
                                         ctypes.POINTER(_c_float), ctypes.POINTER(_c_float), _c_int, _vp]),
     "ssm_frames_to_u8_fwd": (_c_int, [SsmView, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_float),
                                       ctypes.POINTER(_c_float), _c_int, _vp]),
+    "ssm_frames_from_yuv_fwd": (_c_int, [_vp, SsmView, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                         ctypes.POINTER(_c_float), ctypes.POINTER(_c_float), _c_int, ctypes.POINTER(_c_float), _c_int,
+                                         _c_int, _c_int, _vp]),
+    "ssm_frames_to_yuv_fwd": (_c_int, [SsmView, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_float),
+                                       ctypes.POINTER(_c_float), ctypes.POINTER(_c_float), _c_int, _c_int, _c_int, _vp]),
     "ssm_frame_metrics_workspace_bytes": (_sz, [_c_int, _c_int, _c_int]),
     "ssm_frame_metrics_fwd": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _sz, _vp, _vp]),
     "ssm_flow_metrics_workspace_bytes": (_sz, [_c_int, _c_int, _c_int]),
