@@ -572,6 +572,54 @@ int ssm_frames_to_yuv_fwd(ssm_view in, unsigned char *frames_yuv, int N, int H, 
                           const float *mean3, const float *std3, const float *table, int matrix, int range,
                           int siting, void *stream);
 
+/* ---- training ingest (csrc/ssm_data.hip; whole decoded uint8 HWC RGB frames on the device) --------------
+ * The clip loader (ssm_amd/data.py) serves the reference's training transform, RandomCrop, then RandomMirrorRotate,
+ * then Normalize and ToTensor (scripts/utils/dataloaders/default_reader.py:182-207,250-286, augmentations.py:
+ * 39-92,181-200), for frames that arrive undecorated in one staging buffer: `frames` is that buffer on the device,
+ * `frames_bytes` long, and sample b of the batch is described by record b of a table of B ssm_clip_record, which
+ * the caller passes twice: `table_dev` on the device (normally the head of the same buffer, so that one copy moves
+ * everything) and `table_host`, the host copy the argument checks read.  A sample's F frames, each hs x ws x 3
+ * bytes, are contiguous from `offset` (bytes from `frames`); samples of one batch may differ in hs, ws.
+ *   flags & SSM_CLIP_TRANSPOSE  the LOGICAL frame is the transpose of the stored one (the reference swaps the axes of
+ *                               a stored frame with h > w): logical (y, x) = stored (x, y), h = ws, w = hs; else h = hs, w = ws
+ *   (y1, x1)                    origin of the th x tw crop in the logical frame; crop pixel (y, x) = logical (y1 + y, x1 + x)
+ *   flags & SSM_CLIP_HFLIP      the crop is mirrored: flipped crop pixel (y, x) = crop pixel (y, tw - 1 - x)
+ *   flags & SSM_CLIP_AFFINE     the (flipped) crop is resampled through the inverse affine map a[0..5]
+ * ssm_clip_batch_from_u8_fwd: frames 0 .. n_in - 1 of every sample -> `input`, contiguous fp32 [B, n_in, 3, th, tw];
+ *   frames n_in .. F - 1 -> `target`, contiguous [B, F - n_in, 3, th, tw] (the tensors of Trainer.train_step with
+ *   n_in = N_FRAMES, F = 2 N_FRAMES - 1; no padding).  With C the flipped crop of a frame as 8-bit values, per
+ *   output pixel (y, x) and channel c, every operation one fp32 operation, rounded (no fused multiply-add), in the
+ *   order written:
+ *     integer mode (SSM_CLIP_AFFINE clear):  s = (float) C[y][x][c]
+ *     affine mode:  u = (a[0] x + a[1] y) + a[2];  v = (a[3] x + a[4] y) + a[5]      (x, y as floats)
+ *       i = floor(u), j = floor(v);  ax = u - i, ay = v - j;  bx = 1 - ax, by = 1 - ay
+ *       top = C[j][i] bx + C[j][i+1] ax;  bot = C[j+1][i] bx + C[j+1][i+1] ax;  s = top by + bot ay
+ *       with C = 0 outside [0,th) x [0,tw) (cv2.warpAffine's constant border, applied before normalisation; s = 0
+ *       where u or v is not a number).  The host builds a[] in float64 as the inverse of cv2.getRotationMatrix2D(
+ *       (cx, cy), theta, 1) and rounds it once to fp32; no transcendental runs on the device.  This is a stated
+ *       definition, not cv2's fixed-point interpolation.
+ *     out = (s / 255 - mean[c]) / std[c]          (the expression of ssm_frames_from_u8_fwd; mean3 / std3 as there)
+ *   Integer mode is bit-equal to ssm_frames_from_u8_fwd of the host-cropped (and flipped) frames.
+ * SSM_E_ARG (nothing is launched) for null pointers; B, F, th, tw or frames_bytes < 1; B F > 65535;
+ * th ceil(tw / 4) > 2^31 - 1; n_in outside
+ * 1 .. F - 1; and, read from table_host, a record with hs or ws < 1, a negative offset or an unknown flag, a
+ * sample whose F frames leave the buffer, or a crop that leaves the logical frame (y1 < 0, x1 < 0, y1 + th > h,
+ * x1 + tw > w). */
+#define SSM_CLIP_TRANSPOSE 1
+#define SSM_CLIP_HFLIP 2
+#define SSM_CLIP_AFFINE 4
+typedef struct {
+    long long offset; /* bytes from `frames` to the sample's first frame */
+    int hs, ws;       /* stored frame size */
+    int flags;        /* SSM_CLIP_* */
+    int y1, x1;       /* crop origin in the logical frame */
+    float a[6];       /* inverse affine map (SSM_CLIP_AFFINE) */
+    int reserved[3];  /* 0: records are 64 bytes */
+} ssm_clip_record;
+int ssm_clip_batch_from_u8_fwd(const unsigned char *frames, long long frames_bytes, const ssm_clip_record *table_dev,
+                               const ssm_clip_record *table_host, float *input, float *target, int B, int F, int n_in,
+                               int th, int tw, const float *mean3, const float *std3, void *stream);
+
 /* ---- evaluator metrics of uint8 frames (an exception to the fp32-tensor convention: uint8 in, float64 out) ----
  * ssm_frame_metrics_fwd: per frame of two contiguous [N,H,W,3] uint8 stacks (what ssm_frames_to_u8_fwd
  *   writes) the sums behind Evaluator.eval_single_image (scripts/evaluate_interpolation_results.py:101-108:

@@ -3,9 +3,10 @@
 (launch with `python -m torch.distributed.run --nproc-per-node N scripts/main.py ...` for data parallelism: the gradient
 all-reduce over RCCL replaces torch.nn.DataParallel, scripts/main.py:74-76 of the reference).
 
-The dataset layer of the reference (scripts/utils/dataset.py, dataloaders/*) is out of scope, so
-batches come from `--synthetic_batches N` (deterministic synthetic clips with the dataloader's tensor contract); plug a
-real loader into ssm_amd.training.Trainer.train for actual data.  Checkpoints use the reference's layout
+Batches come from the clip lists of the ini (DATA.DATASET = ADOBE | NFS | VIMEO | ALL; ssm_amd.data.ClipLoader: decode threads, uint8
+over PCIe, crop + augment + normalise in one HIP kernel; `--flip` / `--rotate` opt into the two halves of the reference's
+RandomMirrorRotate, which it ships commented out), or from `--synthetic_batches N` (deterministic synthetic clips with the
+dataloader's tensor contract).  Checkpoints use the reference's layout
 (<CKPT_DIR>/<expt>/<expt>_EPOCH_0001.pt, scripts/main.py:218-245) and load back through models.unetflow.get_model.
 """
 import argparse
@@ -23,6 +24,7 @@ for _p in (os.path.dirname(HERE), HERE):
 
 from models import superslomo_r as ssm  # noqa: E402
 from ssm_amd import dist as sdist  # noqa: E402
+from ssm_amd.data import ClipLoader  # noqa: E402
 from ssm_amd.training import Trainer  # noqa: E402
 from ssm_amd.weights import synthetic_frames  # noqa: E402
 
@@ -36,6 +38,8 @@ def getargs(argv=None):
     parser.add_argument("--log", required=True, help="Path to logfile.")
     parser.add_argument("--msg", default=None, help="(Optional) Details of experiment stored with logfile.")
     parser.add_argument("--synthetic_batches", type=int, default=0, help="train on this many synthetic batches per epoch")
+    parser.add_argument("--flip", action="store_true", help="mirror a sample's crop with probability 1/2")
+    parser.add_argument("--rotate", action="store_true", help="rotate a sample's crop by -5..5 degrees about a random centre")
     return parser.parse_args(argv)
 
 
@@ -63,14 +67,18 @@ def main(argv=None, model=None):
     sdist.init("nccl")
     model = (model if model is not None else ssm.FullModel(cfg)).to(dev).train()
     trainer = Trainer(model, cfg)
+    loader = None
     if args.synthetic_batches <= 0:
-        raise NotImplementedError("the reference's dataset readers are out of scope here; pass --synthetic_batches N, or "
-                                  "feed ssm_amd.training.Trainer.train your own (input, target, t_interp) batches")
+        loader = ClipLoader(cfg, "TRAIN", dev, rank, world, seed=cfg.getint("SEED", "VALUE"), flip=args.flip, rotate=args.rotate)
+        if len(loader) == 0:
+            raise ValueError("%d clips do not fill one batch of %d on each of %d rank(s)" % (len(loader.clips), loader.batch, world))
     n_epochs, save_every = cfg.getint("TRAIN", "N_EPOCHS"), cfg.getint("TRAIN", "SAVE_EVERY")
     ckpt_dir = os.path.join(cfg.get("TRAIN", "CKPT_DIR"), args.expt)
     last = None
     for epoch in range(trainer.start, n_epochs + 1):          # trainer.start: 1, or the checkpoint's epoch when resuming (main.py:263-284)
-        trainer.train(synthetic_batches(cfg, args.synthetic_batches, dev, rank), n_epochs=1,
+        if loader is not None:
+            loader.set_epoch(epoch)
+        trainer.train(loader if loader is not None else synthetic_batches(cfg, args.synthetic_batches, dev, rank), n_epochs=1,
                       on_step=lambda e, it, losses: log.info("epoch %d it %d losses %s", epoch, it, losses.tolist()))
         if rank == 0 and epoch % save_every == 0:
             last = os.path.join(ckpt_dir, args.expt + "_EPOCH_" + str(epoch).zfill(4) + ".pt")

@@ -135,6 +135,8 @@ SIGNATURES = {
                                          _c_int, _c_int, _vp]),
     "ssm_frames_to_yuv_fwd": (_c_int, [SsmView, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_float),
                                        ctypes.POINTER(_c_float), ctypes.POINTER(_c_float), _c_int, _c_int, _c_int, _vp]),
+    "ssm_clip_batch_from_u8_fwd": (_c_int, [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                            ctypes.POINTER(_c_float), ctypes.POINTER(_c_float), _vp]),
     "ssm_frame_metrics_workspace_bytes": (_sz, [_c_int, _c_int, _c_int]),
     "ssm_frame_metrics_fwd": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _vp, _sz, _vp, _vp]),
     "ssm_flow_metrics_workspace_bytes": (_sz, [_c_int, _c_int, _c_int]),

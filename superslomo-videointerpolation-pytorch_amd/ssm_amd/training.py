@@ -1,8 +1,8 @@
 """Trainer around the hot path: the optimisation recipe and checkpoint format of the reference's scripts/main.py
 (Adam + StepLR :255-262, `losses.mean(0)[0]` as the scalar loss :138-144, checkpoint dict :218-245), one process per
-GPU with an RCCL gradient all-reduce instead of torch.nn.DataParallel (:74-76).  Datasets are out of scope (SURVEY
-section 2, #11): `train` consumes any iterable of (input [B,2,3,H,W], target [B,1,3,H,W], t_interp [B,1,1,1,1])
-batches already on the device."""
+GPU with an RCCL gradient all-reduce instead of torch.nn.DataParallel (:74-76).  `train` consumes any iterable of
+(input [B,2,3,H,W], target [B,1,3,H,W], t_interp [B,1,1,1,1]) batches already on the device: ssm_amd.data.ClipLoader
+reads them from the clip lists of the ini."""
 import logging
 import os
 
