@@ -669,6 +669,7 @@ __global__ __launch_bounds__(256) void upsample_cat_bwd2_kernel(ssm_view du, ssm
 struct TapsD {
     int o00, o01, o10, o11;
     float fx, fy;                // ix - x0, iy - y0
+    float kx, ky;                // d ix / d u, d iy / d v: 1, or 0 on an axis of one pixel
 };
 
 __device__ __forceinline__ TapsD make_taps_d(int x, int y, float u, float v, int H, int W, int sh) {
@@ -687,18 +688,21 @@ __device__ __forceinline__ TapsD make_taps_d(int x, int y, float u, float v, int
     t.o11 = (bx1 && by1) ? yi1 * sh + xi1 : -1;
     t.fx = ix - x0;
     t.fy = iy - y0;
+    t.kx = W > 1 ? 1.0f : 0.0f;
+    t.ky = H > 1 ? 1.0f : 0.0f;
     return t;
 }
 
-// value and d/d(ix), d/d(iy) of the zero-padded bilinear sample (d ix / d u = 1: the reference's normalise /
-// un-normalise pair is the identity map)
+// value and d/du, d/dv of the zero-padded bilinear sample.  d ix / d u = (W - 1) / max(W - 1, 1): the reference's normalise /
+// un-normalise pair is the identity map, except on an axis of one pixel, where ix = 0 * (...) whatever the flow and the
+// sample does not depend on that flow component (scripts/models/layers.py:112-113; the x1 tap is outside, so (b - a) is not 0)
 __device__ __forceinline__ void sample_d(const float *__restrict__ plane, const TapsD &t, float &val, float &dvx, float &dvy) {
     const float a = t.o00 >= 0 ? plane[t.o00] : 0.f, b = t.o01 >= 0 ? plane[t.o01] : 0.f;
     const float c = t.o10 >= 0 ? plane[t.o10] : 0.f, d = t.o11 >= 0 ? plane[t.o11] : 0.f;
     const float gx = 1.0f - t.fx, gy = 1.0f - t.fy;
     val = a * gx * gy + b * t.fx * gy + c * gx * t.fy + d * t.fx * t.fy;
-    dvx = (b - a) * gy + (d - c) * t.fy;
-    dvy = (c - a) * gx + (d - b) * t.fx;
+    dvx = ((b - a) * gy + (d - c) * t.fy) * t.kx;
+    dvy = ((c - a) * gx + (d - b) * t.fx) * t.ky;
 }
 
 __device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
@@ -850,7 +854,13 @@ __global__ __launch_bounds__(256) void maxpool2_kernel(ssm_view xin, ssm_view yo
     SSM_PIXEL_CGROUP();
     for (int c = c0; c < c1; ++c) {
         const float *r0 = vp(xin, b, c, 2 * y) + 2 * x, *r1 = vp(xin, b, c, 2 * y + 1) + 2 * x;
-        vp(yout, b, c, y)[x] = fmaxf(fmaxf(r0[0], r0[1]), fmaxf(r1[0], r1[1]));
+        // the FIRST maximum of the row-major scan, like the backward below and torch's kernel: fmaxf orders -0 below +0, so a
+        // window holding both (ReLU as LeakyReLU(slope 0) writes -0 for every negative input) came out +0 whichever stood first
+        float m = r0[0];
+        if (r0[1] > m) m = r0[1];
+        if (r1[0] > m) m = r1[0];
+        if (r1[1] > m) m = r1[1];
+        vp(yout, b, c, y)[x] = m;
     }
 }
 

@@ -1,0 +1,189 @@
+"""Float64 references for the element-wise kernels of the training step (csrc/ssm_bwd.hip, csrc/ssm_rnn.hip).
+
+A plain helper module (no fixtures, no collection hooks).  Everything here is the CPU oracle (oracle/ssm_oracle.py) evaluated
+under torch.autograd in the dtype asked for: O.warp, O.flow_interp_inputs, O.synthesize, O.upsample2x_bilinear and O.avg_pool2
+take float64 tensors as they stand.  The recurrent cells are the formulas of O.convlstm_cell / O.convgru_cell without their
+convolutions (the kernels take the summed pre-activations).
+
+Inputs are always DRAWN in fp32 and cast up, so the kernel under test and the float64 reference see the same numbers.
+
+Tolerances (tests/test_hip_train_elementwise.py): err <= bar(e_ref) = max(8 * e_ref, 4 * 2**-24), where err is the largest
+error over the kept entries relative to the largest reference entry and e_ref = ref_gap(...) is the fp32 CPU oracle's own
+distance from the float64 oracle on the same inputs - never a figure of the code under test.
+"""
+import torch
+
+from oracle import ssm_oracle as O
+
+COORD_WINDOW = 1e-4     # px: a sampling coordinate this close to an integer may floor() differently in fp32 and float64
+L1_WINDOW = 1e-5        # an L1 argument this small may take a different sign() in fp32 and float64
+ULP4 = 4 * 2.0 ** -24   # four fp32 unit roundoffs: expf / division / tanhf of the device vs libm, one each, where e_ref ~ 0
+
+# (B, H, W), flow scale: the smallest shapes that exercise each indexing decision of the 64 x 4 pixel blocks
+SAMPLER_CASES = (
+    ((2, 20, 28), 2.0),      # the shape tests/test_hip_backward.py already runs
+    ((3, 9, 70), 3.0),       # second 64-wide block column, ragged 4-row block, three distinct t / c_rec / c_warp
+    ((1, 4, 64), 2.0),       # exactly one block
+    ((1, 5, 65), 2.0),       # one pixel past the block on both axes
+    ((2, 1, 5), 1.0),        # H = 1: the max(H - 1, 1) normalisation
+    ((1, 37, 1), 1.0),       # W = 1: the max(W - 1, 1) normalisation
+    ((2, 5, 3), 6.0),        # most taps outside the image
+)
+# sizes for the loss sums only: H * W below the 64 chunks (some chunks empty), H * W no multiple of 64
+LOSS_ONLY_CASES = (((2, 3, 5), 1.0), ((1, 7, 19), 2.0))
+SEED = 11
+
+
+def bar(e_ref, ratio=8.0):
+    return max(ratio * e_ref, ULP4)
+
+
+def make_case(shape, flow_scale, seed=SEED):
+    """fp32 inputs of one sampler / loss case (the distributions of tests/test_hip_backward.py's case, any shape)."""
+    B, H, W = shape
+    g = torch.Generator().manual_seed(seed)
+    c = {
+        "img6": torch.randn(B, 6, H, W, generator=g),
+        "flow4": torch.randn(B, 4, H, W, generator=g) * flow_scale,
+        "out5": torch.randn(B, 5, H, W, generator=g) * 1.5,
+        "target": torch.randn(B, 3, H, W, generator=g),
+        "r16": torch.randn(B, 16, H, W, generator=g) * 0.01,
+        "dy_extra": torch.randn(B, 3, H, W, generator=g) * 0.5,
+        "t": torch.tensor([0.25, 0.625, 0.875])[:B].clone(),
+        "c_rec": torch.tensor([0.7, 1.3, 0.2])[:B].clone(),
+        "c_warp": torch.tensor([0.4, 0.9, 1.6])[:B].clone(),
+    }
+    return c
+
+
+def _per(z):
+    return z.abs().flatten(1).sum(1)
+
+
+def loss_and_grads(img6, flow4, out5, target, t, c_rec, c_warp, r16, dy_extra, s1_terms, s2_terms, dtype=torch.float64):
+    """The scalar  sum_b [ c_rec |pred - I_t|_1 + c_warp (enabled warp terms) ] + <in16, r16> + <pred, dy_extra>  and everything
+    the kernels are held to.  Returns a dict:
+      sums    [B,2]  sum |pred - target|, sum of the enabled warp maps          (what ssm_train_loss_sums returns)
+      dout5, dflow4  gradients wrt stage 2's output and stage 1's flows        (ssm_synthesize_bwd + ssm_flowinterp_inputs_bwd)
+      in16, pred     forward values (est4 = in16[:, 6:10])
+      flows          every flow a sampler used: Ft1^, Ft0^, refined Ft1, Ft0, then F01, F10 if s1_terms
+      l1_args        every tensor an abs() was taken of
+    """
+    c = lambda z: None if z is None else z.detach().to(dtype)     # noqa: E731
+    img6, target, r16, dy_extra, c_rec, c_warp = c(img6), c(target), c(r16), c(dy_extra), c(c_rec), c(c_warp)
+    B = img6.shape[0]
+    tt = c(t).view(B, 1, 1, 1)
+    flow4, out5 = c(flow4).requires_grad_(), c(out5).requires_grad_()
+    in16 = O.flow_interp_inputs(img6, flow4, tt)
+    pred = O.synthesize(img6, in16, out5, tt)
+    i0, i1 = img6[:, 0:3], img6[:, 3:6]
+    ft1, ft0 = in16[:, 6:8] + out5[:, 1:3], in16[:, 8:10] + out5[:, 3:5]
+    l1 = [pred - target]
+    flows = [in16[:, 6:8], in16[:, 8:10], ft1, ft0]
+    rec = _per(l1[0])
+    loss = (c_rec * rec).sum()
+    if r16 is not None:
+        loss = loss + (in16 * r16).sum()
+    if dy_extra is not None:
+        loss = loss + (pred * dy_extra).sum()
+    wrp = torch.zeros(B, dtype=dtype)
+    if s2_terms:
+        l1 += [O.warp(i0, ft0) - target, O.warp(i1, ft1) - target]
+        wrp = wrp + _per(l1[-2]) + _per(l1[-1])
+    if s1_terms:
+        flows += [flow4[:, 0:2], flow4[:, 2:4]]
+        l1 += [O.warp(i1, flow4[:, 0:2]) - i0, O.warp(i0, flow4[:, 2:4]) - i1]
+        wrp = wrp + _per(l1[-2]) + _per(l1[-1])
+    loss = loss + (c_warp * wrp).sum()
+    loss.backward()
+    return {"sums": torch.stack([rec, wrp], 1).detach(), "dout5": out5.grad, "dflow4": flow4.grad, "in16": in16.detach(),
+            "pred": pred.detach(), "flows": [f.detach() for f in flows], "l1_args": [a.detach() for a in l1]}
+
+
+def warp_grads(img, flow, dy, dtype=torch.float64):
+    """Autograd of <O.warp(img, flow), dy>: (dflow, dimg)."""
+    img, flow = img.detach().to(dtype).requires_grad_(), flow.detach().to(dtype).requires_grad_()
+    (O.warp(img, flow) * dy.to(dtype)).sum().backward()
+    return flow.grad, img.grad
+
+
+def keep_mask(flows, l1_args=()):
+    """[B,H,W] bool: pixels at which the loss is smooth enough to compare gradients.  A pixel is dropped when, in the evaluation
+    handed in (float64), a sampling coordinate x + u or y + v of any flow lies within COORD_WINDOW of an integer (floor decides the
+    taps, and the reference itself rounds coordinates in fp32: O.warp's docstring) or any L1 argument is below L1_WINDOW in
+    magnitude (sign decides the gradient).  An axis of size 1 is left out: there the sampling coordinate is 0 * (...) = 0 whatever
+    the flow (the max(W - 1, 1) normalisation), the sample does not depend on that flow component and nothing is discontinuous."""
+    B, _, H, W = flows[0].shape
+    keep = torch.ones(B, H, W, dtype=torch.bool)
+    xx = torch.arange(W, dtype=torch.float64).view(1, 1, W)
+    yy = torch.arange(H, dtype=torch.float64).view(1, H, 1)
+    for f in flows:
+        f = f.to(torch.float64)
+        for coord, n in ((xx + f[:, 0], W), (yy + f[:, 1], H)):
+            if n > 1:
+                keep &= (coord - torch.round(coord)).abs() >= COORD_WINDOW
+    for a in l1_args:
+        keep &= (a.abs() >= L1_WINDOW).all(dim=1)
+    return keep
+
+
+def excluded_share(keep):
+    return 1.0 - float(keep.double().mean())
+
+
+def rel_err(got, want, keep=None):
+    """Largest |got - want| over the kept entries, relative to the largest kept reference entry.  keep: [B,H,W] pixels (applied
+    to every channel), a mask of want's own shape, or None."""
+    got, want = got.detach().to(torch.float64).cpu(), want.detach().to(torch.float64)
+    if keep is not None:
+        if keep.dim() == want.dim() - 1:
+            keep = keep.unsqueeze(1).expand_as(want)
+        got, want = got[keep], want[keep]
+    if want.numel() == 0:
+        return 0.0
+    return float((got - want).abs().max() / want.abs().max().clamp_min(1e-300))
+
+
+def ref_gap(fn, keep=None):
+    """fn(dtype) -> tensor or tuple of tensors.  The fp32 CPU evaluation's rel_err against the float64 one (one figure per
+    tensor): the yardstick of a tolerance."""
+    lo, hi = fn(torch.float32), fn(torch.float64)
+    if isinstance(hi, torch.Tensor):
+        return rel_err(lo, hi, keep)
+    return tuple(rel_err(a, b, keep) for a, b in zip(lo, hi))
+
+
+# ---- recurrent cells without their convolutions (O.convlstm_cell / O.convgru_cell) -----------------------------------------
+def lstm_cell(pre, c_prev):
+    """pre [B,4*Hc,H,W] = summed pre-activations [i|f|o|g]; c_prev or None (zero state).  Returns (h, c_next)."""
+    hc = pre.shape[1] // 4
+    i, f, o, g = torch.split(pre, hc, dim=1)
+    c_next = torch.sigmoid(i) * torch.tanh(g)
+    if c_prev is not None:
+        c_next = torch.sigmoid(f) * c_prev + c_next
+    return torch.sigmoid(o) * torch.tanh(c_next), c_next
+
+
+def gru_reset(gates, h_prev):
+    """gates [B,2*Hc,H,W] = [gamma|beta]: reset * h, the input of the candidate convolution."""
+    hc = gates.shape[1] // 2
+    return torch.sigmoid(gates[:, :hc]) * h_prev
+
+
+def gru_update(gates, cand, h_prev):
+    """h' = (1 - update) h + update tanh(cand); h_prev None = zero state."""
+    hc = gates.shape[1] // 2
+    u = torch.sigmoid(gates[:, hc:])
+    out = u * torch.tanh(cand)
+    return out if h_prev is None else (1 - u) * h_prev + out
+
+
+def grads(fn, inputs, cots, dtype):
+    """Autograd of sum_k <out_k, cot_k> for fn(*inputs) -> tuple of outputs: (outputs, gradients), inputs that are None skipped
+    (their gradient is None)."""
+    xs = [None if x is None else x.detach().to(dtype).requires_grad_() for x in inputs]
+    outs = fn(*xs)
+    outs = outs if isinstance(outs, tuple) else (outs,)
+    tot = sum((o * c.to(dtype)).sum() for o, c in zip(outs, cots) if c is not None)
+    tot.backward()
+    return tuple(o.detach() for o in outs), tuple(None if x is None else (x.grad if x.grad is not None else torch.zeros_like(x)) for x in xs)
