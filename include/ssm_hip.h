@@ -255,6 +255,29 @@ int ssm_wino4_conv2d_shuffle_fwd(ssm_view x1, int C1, ssm_view x2, int C2, const
 int ssm_wino4_conv2d_ups_border_fwd(ssm_view a, int C1, ssm_view b, int C2, const float *w_packed, const float *bias_packed, ssm_view y, int B,
                                     int H, int W, int Cout, float slope, int flags, void *stream);
 
+/* ---- conv3x3(upsample2x(cat[a, b])) as a 1x1 GEMM at low resolution, taps after the upsample (v_mfma_f32_32x32x2_f32) ---------
+ * The decoder step of scripts/models/flow_computation.py:244-247 (layers.conv, scripts/models/layers.py:21-33).  Bilinear upsampling acts
+ * per channel, a filter tap's channel mixing is a matrix, and the two commute:
+ *   conv3x3(up(x))(Y, X) = bias + sum_{u,v} [ (Y+u-1, X+v-1) inside the map ] up(W[:, :, u, v] . x)(Y+u-1, X+v-1)
+ * so the layer is one GEMM Cin -> 9 Cout over the LOW-res pixels (9/36 of the direct form's multiply-adds, no transforms) into a scratch set of
+ * planes [B][9 Cout][H/2][.], and a memory-bound pass that gathers the nine shifted bilinear samples (ATen's half-pixel rule, edge-clamped;
+ * zero where the tap lies outside the map), adds bias and the optional pre-activation addend [B / add_div] and applies LeakyReLU.  All
+ * arithmetic fp32; a single layer sits ~2e-6 from a float64 evaluation at unit output scale.  Cout a multiple of 32, H and W (the OUTPUT
+ * size) even, any Cin / C1 (whole 16-channel chunks take the fast loader).  a, b: LOW-res padded-plane views as for ssm_conv2d_ups_add_fwd
+ * (b may be batch-broadcast, sb = 0); tile overshoot is read from the frame / the tail slack and never stored.  Only interiors of scratch
+ * and y are written; no scratch element is read that the same call did not write.  `bias` is the layer's plain [Cout] bias.          */
+int ssm_upgemm_supported(int Cin, int Cout, int H, int W, int k);      /* flow_computation.py:244-247: can the layer (H x W output) run in this form? */
+int ssm_upgemm_preferred(int Cin, int Cout, int B, int h, int w);      /* flow_computation.py:244-247: 1 where GEMM + combine measured faster than F(4x4,3x3); h x w = the LOW-res map */
+int ssm_upgemm_force_kind(int kind);      /* flow_computation.py:244-247: tests / tuning only, the GEMM's tile configuration (-1 = automatic); returns their number */
+size_t ssm_upgemm_packed_weight_floats(int Cout, int Cin);      /* flow_computation.py:244-247 */
+/* flow_computation.py:244-247: OIHW fp32 3x3 filter -> the GEMM's A operand [9 Cout / 128][Cin rounded up to 16][128], row = tap Cout + cout */
+int ssm_upgemm_pack_weights(const float *w_oihw, float *w_packed, int Cout, int Cin, void *stream);
+/* flow_computation.py:244-247: floats of the scratch planes [B][9 Cout][h][w rounded up to 4] of a launch with a h x w LOW-res map */
+size_t ssm_upgemm_scratch_floats(int Cout, int B, int h, int w);
+/* flow_computation.py:244-247: both launches on `stream`; scratch: view {ptr, sb >= 9 Cout sc, sc >= h sh, sh >= w, all multiples of 4} */
+int ssm_upgemm_conv2d_ups_add_fwd(ssm_view a, int C1, ssm_view b, int C2, const float *w_packed, const float *bias, ssm_view scratch, ssm_view y,
+                                  ssm_view add, int add_div, int B, int H, int W, int Cout, float slope, int flags, void *stream);
+
 /* ---- the 7x7 / 5x5 convolutions as one-dimensional Winograd along x, all arithmetic fp32 (v_mfma_f32_32x32x2_f32) ----------
  * Same operator and operand layout as ssm_conv2d_add_fwd for k = 7 / 5 (layers.conv, scripts/models/layers.py:21-33; the layers
  * conv1a/conv1b (k = 7) and conv2a/conv2b (k = 5) of both U-Nets, scripts/models/flow_computation.py:36-45 and

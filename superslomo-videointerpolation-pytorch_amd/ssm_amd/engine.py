@@ -112,6 +112,15 @@ TRAIN_FWD_BLOCKED = os.environ.get("SSM_TRAIN_FWD_BLOCKED", "1")
 WINO4_SUBPIXEL = tuple(n for n in os.environ.get("SSM_WINO4_SUBPIXEL", "conv11a").split(",") if n not in ("", "0"))
 
 
+# fused-upsample 3x3 layers of an f32w INFERENCE plan as a 1x1 GEMM at low resolution + the taps after the upsample (csrc/ssm_upgemm.hip,
+# hb.PackedUpGemm): $SSM_UPGEMM=0 off, 1 = where the library's measured rule prefers it (hb.upgemm_preferred), a comma list forces layers
+UPGEMM = os.environ.get("SSM_UPGEMM", "1")
+
+
+def upgemm_enabled(name):
+    return UPGEMM not in ("0", "") and (UPGEMM == "1" or name in UPGEMM.split(","))
+
+
 def wino4_enabled(name):
     return WINO4 not in ("0", "") and (WINO4 == "1" or name in WINO4.split(","))
 
@@ -121,9 +130,10 @@ def wino1d_enabled(k):
     return k in (5, 7) and str(k) in WINO1D
 
 
-def choose_algo(name, ci, co, k, nb, h, w, ups, wino, wino1d, wino4=None, blocked2d=None):
+def choose_algo(name, ci, co, k, nb, h, w, ups, wino, wino1d, wino4=None, blocked2d=None, upgemm=True):
     """Algorithm of one convolution of an fp32 plan: "direct" (csrc/ssm_conv.hip), "wino" = F(2x2,3x3) (ssm_wino.hip), "wino4" =
-    F(4x4,3x3) (ssm_wino4.hip), "wino1d" = F(2,7) / F(4,5) along x (ssm_wino1d.hip), "wino7" = the 7x7 layers as 2x2 blocks of F(4x4,4x4) (ssm_wino7.hip).  wino: the plan is mode f32w; wino1d: it is an
+    F(4x4,3x3) (ssm_wino4.hip), "wino1d" = F(2,7) / F(4,5) along x (ssm_wino1d.hip), "wino7" = the 7x7 layers as 2x2 blocks of F(4x4,4x4) (ssm_wino7.hip), "upgemm" = a fused-upsample 3x3 layer as low-res
+    1x1 GEMM + combine pass (ssm_upgemm.hip; upgemm=False: not considered).  wino: the plan is mode f32w; wino1d: it is an
     inference plan (the 8-frequency forms stay out of the training plans).  Pure function of the problem: bench.py uses it to count the
     multiply-adds the matrix cores issue."""
     skip = name in WINO_SKIP or "all" in WINO_SKIP or name == "final_conv"
@@ -132,6 +142,10 @@ def choose_algo(name, ci, co, k, nb, h, w, ups, wino, wino1d, wino4=None, blocke
     # are switched off, in the 1-D forms (inference plans only: a training plan takes wino7 / wino5 or else the direct form - the 1-D
     # forms miss its gradient bar, TRAIN_FWD_BLOCKED above)
     blocked2d = wino1d if blocked2d is None else blocked2d
+    # (h, w: the layer's OUTPUT map; ci of a hoisted conv7a is the whole concat - the rule sees the layer, not its per-t half)
+    if (upgemm and wino and wino1d and ups and not skip and k == 3 and upgemm_enabled(name) and hb.upgemm_supported(ci, co, h, w, k)
+            and (UPGEMM != "1" or hb.upgemm_preferred(ci, co, nb, h, w))):
+        return "upgemm"
     if blocked2d and not skip and k == 7 and WINO7 not in ("0", "") and hb.wino7_supported(ci, co, h, w, k):
         return "wino7"
     if blocked2d and not skip and k == 5 and WINO5 not in ("0", "") and ci % 4 == 0 and hb.wino5_supported(ci, co, h, w, k):
@@ -147,11 +161,11 @@ def choose_algo(name, ci, co, k, nb, h, w, ups, wino, wino1d, wino4=None, blocke
 
 
 _ALGO_CLASS = {"direct": lambda: hb.PackedConv, "wino": lambda: hb.PackedWino, "wino4": lambda: hb.PackedWino4, "wino1d": lambda: hb.PackedWino1d,
-               "wino7": lambda: hb.PackedWino7, "wino5": lambda: hb.PackedWino5}
+               "wino7": lambda: hb.PackedWino7, "wino5": lambda: hb.PackedWino5, "upgemm": lambda: hb.PackedUpGemm}
 # multiply-adds issued on the matrix cores per direct-form multiply-add, by algorithm and kernel size
 ISSUED_FACTOR = {"direct": lambda k: 1.0, "wino": lambda k: 16.0 / 36.0, "wino4": lambda k: 36.0 / 144.0,
                  "wino1d": lambda k: 8.0 / 14.0 if k == 7 else 8.0 / 20.0, "wino7": lambda k: 196.0 / 784.0,
-                 "wino5": lambda k: 64.0 / 400.0}
+                 "wino5": lambda k: 64.0 / 400.0, "upgemm": lambda k: 9.0 / 36.0}
 
 
 def issued_factor(pk):
@@ -161,6 +175,9 @@ def issued_factor(pk):
 
 def conv_fn(pk, ups=False):
     """The launcher that goes with a packed filter's algorithm."""
+    if pk.algo == "upgemm":
+        assert ups, "the low-res GEMM form is for the fused-upsample layers"
+        return hb.conv2d_ups_upgemm
     if pk.algo == "wino7":
         return hb.conv2d_wino7
     if pk.algo == "wino5":
@@ -340,7 +357,12 @@ class UNetPlan:
             else:
                 nb = self.Bd if name in self.DECODER else self.B
                 ups = self.fuse_up and name in self.UPS
-                cls = _ALGO_CLASS[choose_algo(name, ci, co, k, nb, self.H // s, self.W // s, ups, self.wino, self.wino1d, self.wino4, self.blocked2d)]()
+                algo_args = (name, ci, co, k, nb, self.H // s, self.W // s, ups, self.wino, self.wino1d, self.wino4, self.blocked2d)
+                cls = _ALGO_CLASS[choose_algo(*algo_args)]()
+                pair_cls = cls          # (the hoisted per-pair parts keep their present kernel where the per-t launch is GEMM + combine)
+                if cls is hb.PackedUpGemm:
+                    pair_cls = _ALGO_CLASS[choose_algo(*algo_args, upgemm=False)]()
+                    batch32 = False          # (its slabs are not part of the one-launch repack)
                 if self.hoist and name == "conv1a":
                     # per-t part: channels 3:13 (warped frames + estimated flows); per-pair part: the frames themselves in stage 1's
                     # input order (I0 = channels 13:16, I1 = channels 0:3), no bias, no activation
@@ -350,7 +372,7 @@ class UNetPlan:
                 elif self.hoist and name == "conv7a" and self.cross:
                     zb = torch.zeros_like(b)
                     self.pk[name] = cls(w[:, :512].contiguous(), b, nb, self.H // s, self.W // s, ups=ups)
-                    self.pk_pair[name] = cls(w[:, 512:].contiguous(), zb, self.hoist[0], self.H // s, self.W // s, ups=ups)
+                    self.pk_pair[name] = pair_cls(w[:, 512:].contiguous(), zb, self.hoist[0], self.H // s, self.W // s, ups=ups)
                 elif (ups and cls is hb.PackedWino4 and name in WINO4_SUBPIXEL and not self.twins
                       and hb.subpixel_wino4_supported(ci, co, self.H // s, self.W // s)):
                     self.pk[name] = hb.PackedSubpixelWino4(w, b, nb, self.H // s, self.W // s)
@@ -362,6 +384,14 @@ class UNetPlan:
         for pkk in list(self.pk.values()) + list(getattr(self, "pk_pair", {}).values()):
             if self.wino and isinstance(pkk, hb.PackedConv):
                 pkk.split_ok = True
+        # one scratch plane set for the plan's low-res GEMM layers, sized for the largest (they run in order on one stream)
+        ug = [(pkk, name) for name, pkk in self.pk.items() if isinstance(pkk, hb.PackedUpGemm)]
+        if ug:
+            need = max(pkk.scratch_floats(self.Bd, self.H // layer_scale(name), self.W // layer_scale(name)) for pkk, name in ug)
+            if getattr(self, "_upgemm_scratch", None) is None or self._upgemm_scratch.numel() < need:
+                self._upgemm_scratch = torch.empty(need, dtype=torch.float32, device=self.device)
+            for pkk, _ in ug:
+                pkk.scratch = self._upgemm_scratch
         self._pack32 = None
         if batch32:
             entries = [(self.pk[name], state_dict[param_key(name, "weight")], state_dict[param_key(name, "bias")], False)

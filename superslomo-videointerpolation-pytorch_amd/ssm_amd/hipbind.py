@@ -82,6 +82,14 @@ SIGNATURES = {
                                           _c_int, _c_int, _c_float, _c_int, _vp]),
     "ssm_wino4_conv2d_ups_add_fwd": (_c_int, [SsmView, _c_int, SsmView, _c_int, _vp, _vp, SsmView, SsmView, _c_int, _c_int, _c_int, _c_int,
                                               _c_int, _c_float, _c_int, _vp]),
+    "ssm_upgemm_supported": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "ssm_upgemm_preferred": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "ssm_upgemm_force_kind": (_c_int, [_c_int]),
+    "ssm_upgemm_packed_weight_floats": (_sz, [_c_int, _c_int]),
+    "ssm_upgemm_pack_weights": (_c_int, [_vp, _vp, _c_int, _c_int, _vp]),
+    "ssm_upgemm_scratch_floats": (_sz, [_c_int, _c_int, _c_int, _c_int]),
+    "ssm_upgemm_conv2d_ups_add_fwd": (_c_int, [SsmView, _c_int, SsmView, _c_int, _vp, _vp, SsmView, SsmView, SsmView, _c_int, _c_int, _c_int,
+                                               _c_int, _c_int, _c_float, _c_int, _vp]),
     "ssm_wino4_conv2d_shuffle_fwd": (_c_int, [SsmView, _c_int, SsmView, _c_int, _vp, _vp, SsmView, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _vp]),
     "ssm_wino4_conv2d_ups_border_fwd": (_c_int, [SsmView, _c_int, SsmView, _c_int, _vp, _vp, SsmView, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int,
                                                  _vp]),
@@ -712,6 +720,62 @@ def conv2d_ups_subpixel_wino4(a_view, c1, b_view, c2, pk, y_view, B, H, W, lrelu
                                            pk.inner.b.data_ptr(), y_view(2 * y0, 2 * x0), B, h, w, 4 * pk.cout, slope, flags, stream_ptr()))
     check(lib.ssm_wino4_conv2d_ups_border_fwd(a_view(0, 0), c1, b_view(0, 0) if b_view is not None else NULL_VIEW, c2, pk.border.w.data_ptr(),
                                               pk.border.b.data_ptr(), y_view(0, 0), B, H, W, pk.cout, slope, flags, stream_ptr()))
+
+
+# ---- conv3x3(upsample2x(cat[a, b])) as a 1x1 GEMM at low resolution + the taps after the upsample (csrc/ssm_upgemm.hip) ----------------
+def upgemm_supported(cin, cout, H, W, k=3):
+    """Can the fused-upsample layer with a H x W OUTPUT run as low-res GEMM + combine pass?  (3x3, Cout a multiple of 32, even H, W)"""
+    return bool(load().ssm_upgemm_supported(cin, cout, H, W, k))
+
+
+def upgemm_preferred(cin, cout, B, H, W):
+    """Does the library's measured rule put GEMM + combine ahead of F(4x4,3x3) for the layer with a H x W OUTPUT?"""
+    return bool(load().ssm_upgemm_preferred(cin, cout, B, H // 2, W // 2))
+
+
+def upgemm_scratch_view(buf, cout, h, w):
+    """ssm_view of the scratch planes [B][9 cout][h][w rounded up to 4] at the start of the fp32 tensor `buf`."""
+    wr = (w + 3) // 4 * 4
+    return SsmView(buf.data_ptr(), 9 * cout * h * wr, h * wr, wr)
+
+
+class PackedUpGemm:
+    """3x3 filter of a fused-upsample layer as the A operand of the low-res GEMM Cin -> 9 Cout ([9 Cout / 128][Cin][128] slabs, row = tap Cout +
+    cout) beside the layer's plain bias; an explicit handle owned by the Python side like PackedConv.  `scratch`: the fp32 tensor the GEMM's
+    9 Cout-channel output goes through - a plan assigns one tensor to all its layers (they run in order on one stream); a handle used on its
+    own allocates what its launch needs."""
+
+    algo = "upgemm"
+
+    def __init__(self, weight, bias, B, H, W, pool=False, ups=True):
+        require_device(weight, "conv weight")
+        require_device(bias, "conv bias")
+        assert ups and not pool, "the low-res GEMM form is for the fused-upsample layers"
+        self.cout, self.cin, self.k = weight.shape[0], weight.shape[1], weight.shape[2]
+        if not upgemm_supported(self.cin, self.cout, H, W, self.k):
+            raise RuntimeError("low-res GEMM form: unsupported layer (%d -> %d, k = %d, output %d x %d)" % (self.cin, self.cout, self.k, H, W))
+        self.ups, self.cin_p, self.bn, self.ck = True, self.cin, 128, 16
+        lib = load()
+        self.w = torch.empty(lib.ssm_upgemm_packed_weight_floats(self.cout, self.cin), dtype=torch.float32, device=weight.device)
+        self.b = bias.detach().contiguous().clone()
+        check(lib.ssm_upgemm_pack_weights(weight.detach().contiguous().data_ptr(), self.w.data_ptr(), self.cout, self.cin, stream_ptr()))
+        self.scratch = None
+
+    def scratch_floats(self, B, H, W):
+        return load().ssm_upgemm_scratch_floats(self.cout, B, H // 2, W // 2)
+
+
+def conv2d_ups_upgemm(a, c1, b, c2, pk, y, B, H, W, lrelu=True, slope=0.1, add=None, add_div=1):
+    """conv3x3(upsample2x(cat[a, b])) as low-res GEMM + combine pass: a, b LOW-res padded-plane views, H, W the OUTPUT size."""
+    lib = load()
+    assert pk.cin == c1 + c2, "packed filter expects %d input channels, got %d" % (pk.cin, c1 + c2)
+    need = pk.scratch_floats(B, H, W)
+    if pk.scratch is None or pk.scratch.numel() < need:
+        pk.scratch = torch.empty(need, dtype=torch.float32, device=pk.w.device)
+    check(lib.ssm_upgemm_conv2d_ups_add_fwd(a, c1, b if b is not None else NULL_VIEW, c2, pk.w.data_ptr(), pk.b.data_ptr(),
+                                            upgemm_scratch_view(pk.scratch, pk.cout, H // 2, W // 2), y,
+                                            add if add is not None else NULL_VIEW, add_div, B, H, W, pk.cout, slope,
+                                            SSM_FLAG_LRELU if lrelu else 0, stream_ptr()))
 
 
 # ---- 7x7 / 5x5 convolutions as 1-D Winograd along x, F(2,7) / F(4,5), in fp32 (csrc/ssm_wino1d.hip) -----------------
