@@ -32,7 +32,7 @@
 // beside the chunk's MFMAs (the other workgroup of the CU keeps the pipe busy
 // meanwhile), and the concatenated, upsampled tensor - the largest activation of
 // every decoder level - never touches HBM.
-#include "ssm_common.h"
+#include "ssm_conv_host.h"
 #include "ssm_device.h"
 
 #include <atomic>
@@ -500,7 +500,9 @@ constexpr KindInfo kInfo[NKIND] = {
 #undef X
 };
 
-std::atomic<int> g_force_kind{-1};    // tests / tuning only (ssm_conv_force_kind)
+ssm::ForcedKind g_force_kind;    // tests / tuning only (ssm_conv_force_kind)
+// (scalar stores: no alignment rule on the output side, no `vec` member; no mask path)
+constexpr ssm::OutRules kConvRules = {/*mask*/ false, /*piece*/ 0, /*required*/ false};
 
 // Resident workgroups per CU of every kernel instance (registers / LDS), asked from the runtime once; 2 where there is no device
 // (the plan then is still a pure function of the problem - nothing is launched there).
@@ -556,8 +558,8 @@ double estimate_cycles(const KindInfo &ki, int occ, int cin8, int Cout, int B, i
 
 int pick_kind(int k, int Cin, int Cout, int B, int H, int W, int pool, int ups) {
     if (k != 3 && k != 5 && k != 7) return -1;
-    const int forced = g_force_kind.load();
-    if (forced >= 0 && forced < NKIND && kInfo[forced].ks == k) return forced;
+    const int forced = g_force_kind.get(NKIND);
+    if (forced >= 0 && kInfo[forced].ks == k) return forced;
     const int cin8 = (Cin + 7) / 8 * 8;
     int best = -1;
     double bt = 0.0;
@@ -592,10 +594,7 @@ int launch(ConvParams &p, int B, hipStream_t st) {
         return SSM_E_UNSUPPORTED;
     }
     const long long blocks = (long long)p.tilesX * p.tilesY * p.NB * B * p.NSPLIT;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) {
-        ssm::set_error("conv: grid of %lld workgroups out of range", blocks);
-        return SSM_E_ARG;
-    }
+    SSM_TRY(ssm::check_grid("conv", blocks));
     if constexpr (UPS && !C::UPS_OK) {
         ssm::set_error("conv: this tile configuration has no fused-upsample form");
         return SSM_E_UNSUPPORTED;
@@ -649,18 +648,12 @@ __global__ void pack_weights_kernel(const float *__restrict__ w, const float *__
 }
 
 int fill_common(ConvParams &p, ssm_view x1, int C1, ssm_view x2, int C2, const float *w_packed, const float *bias_packed,
-                ssm_view y, int H, int W, int Cout, float slope, int flags, int CK, int srcW) {
+                ssm_view y, ssm_view add, int add_div, int B, int H, int W, int Cout, float slope, int flags, int CK, int srcW) {
     SSM_REQUIRE(H > 0 && W > 0 && Cout > 0 && C1 > 0 && C2 >= 0, "conv: bad sizes");
     SSM_REQUIRE(x1.ptr && y.ptr && w_packed && bias_packed, "conv: null pointer");
     SSM_REQUIRE(C1 % CK == 0 && C2 % CK == 0, "conv: channel counts (%d,%d) must be multiples of %d", C1, C2, CK);
-    SSM_REQUIRE(ssm::aligned16(x1.ptr) && x1.sh % 4 == 0 && x1.sc % 4 == 0 && x1.sb % 4 == 0,
-                "conv: input 1 is not a padded-plane view (16-byte alignment)");
-    SSM_REQUIRE(x1.sh >= srcW + 2 * SSM_PADX, "conv: input 1 row stride %d leaves no zero frame for W=%d", x1.sh, srcW);
-    SSM_REQUIRE(ssm::aligned16(w_packed), "conv: packed filter must be 16-byte aligned");
-    if (C2 > 0) {
-        SSM_REQUIRE(x2.ptr && ssm::aligned16(x2.ptr) && x2.sb % 4 == 0, "conv: input 2 is not a padded-plane view");
-        SSM_REQUIRE(x2.sh == x1.sh && x2.sc == x1.sc, "conv: cat sources must share row/channel strides");
-    }
+    SSM_TRY(ssm::check_source("conv", true, x1, srcW, w_packed));
+    SSM_TRY(ssm::check_source2("conv", x1, x2, C2));
     SSM_REQUIRE((long long)CK * x1.sc < 0x7fffffffLL, "conv: channel stride too large");
     p.src1 = x1.ptr;
     p.src2 = C2 > 0 ? x2.ptr : x1.ptr;
@@ -672,31 +665,17 @@ int fill_common(ConvParams &p, ssm_view x1, int C1, ssm_view x2, int C2, const f
     p.Cin = C1 + C2;
     p.wpk = w_packed;
     p.bias = bias_packed;
-    p.dst = y.ptr;
-    p.dsb = y.sb;
-    p.dsc = y.sc;
-    p.dsh = y.sh;
-    p.pool = nullptr;
-    p.psb = p.psc = 0;
-    p.psh = 0;
-    p.H = H;
-    p.W = W;
     p.hs = H / 2;
     p.ws = W / 2;
-    p.Cout = Cout;
-    p.slope = slope;
-    p.lrelu = (flags & SSM_FLAG_LRELU) ? 1 : 0;
     p.abl = 0;
-    p.add = nullptr;
-    p.asb = p.asc = 0;
-    p.ash = 0;
-    p.adiv = 1;
     p.NSPLIT = 1;
     p.ksB = 0;
 #ifdef SSM_CONV_ABLATE
     if (const char *e = getenv("SSM_CONV_ABL")) p.abl = atoi(e);
 #endif
-    return SSM_OK;
+    // (the pooled view is bound by the entry point, after the addend checks of check_add below)
+    const ssm_view none = {nullptr, 0, 0, 0};
+    return ssm::bind_outputs("conv", kConvRules, p, y, none, add, add_div, B, H, W, Cout, slope, flags);
 }
 
 }  // namespace
@@ -714,8 +693,7 @@ extern "C" int ssm_conv_plan(int k, int Cin, int Cout, int B, int H, int W, int 
 }
 
 extern "C" int ssm_conv_force_kind(int kind) {
-    g_force_kind.store(kind >= 0 && kind < NKIND ? kind : -1);
-    return NKIND;
+    return g_force_kind.set(kind, NKIND);
 }
 
 extern "C" int ssm_conv_config(int k, int Cout, int B, int H, int W, int pool, int *BN, int *CK) {
@@ -743,17 +721,12 @@ extern "C" int ssm_pack_weights(const float *w, const float *bias, float *wp, fl
 }
 
 namespace {
-int set_add(ConvParams &p, ssm_view add, int add_div, int B, int BN) {
+// what the direct kernel asks of a bound addend beyond the shared checks
+int check_add(const ConvParams &p, ssm_view add, int BN) {
     if (!add.ptr) return SSM_OK;
-    SSM_REQUIRE(add_div >= 1 && B % add_div == 0, "conv: the addend serves %d batch entries each, batch %d is no multiple", add_div, B);
     // the kernel loads the addend for every cout of its block without predicates: no padded couts allowed
     SSM_REQUIRE(p.Cout % BN == 0, "conv: the addend form needs Cout (%d) to be a multiple of the cout block (%d) of the tile configuration", p.Cout, BN);
     SSM_REQUIRE(4LL * (4 * add.sc + (long long)(p.H + 64) * add.sh) < 0x7fffffffLL, "conv: addend plane too large for 32-bit offsets");
-    p.add = add.ptr;
-    p.asb = add.sb;
-    p.asc = add.sc;
-    p.ash = add.sh;
-    p.adiv = add_div;
     return SSM_OK;
 }
 }  // namespace
@@ -766,17 +739,9 @@ extern "C" int ssm_conv2d_add_fwd(ssm_view x1, int C1, ssm_view x2, int C2, cons
     const int rc = ssm_conv_plan(k, C1 + C2, Cout, B, H, W, pool.ptr ? 1 : 0, 0, &kind, &BN, &CK);
     if (rc != SSM_OK) return rc;
     ConvParams p;
-    const int rf = fill_common(p, x1, C1, x2, C2, w_packed, bias_packed, y, H, W, Cout, slope, flags, CK, W);
-    if (rf != SSM_OK) return rf;
-    const int ra = set_add(p, add, add_div, B, BN);
-    if (ra != SSM_OK) return ra;
-    if (pool.ptr) {
-        SSM_REQUIRE(H % 2 == 0 && W % 2 == 0, "conv: fused pool needs even H, W");
-        p.pool = pool.ptr;
-        p.psb = pool.sb;
-        p.psc = pool.sc;
-        p.psh = pool.sh;
-    }
+    SSM_TRY(fill_common(p, x1, C1, x2, C2, w_packed, bias_packed, y, add, add_div, B, H, W, Cout, slope, flags, CK, W));
+    SSM_TRY(check_add(p, add, BN));
+    SSM_TRY(ssm::bind_pool("conv", p, pool));
     return dispatch<false>(kind, p, B, (hipStream_t)stream);
 }
 
@@ -808,8 +773,8 @@ extern "C" int ssm_conv2d_splitk_fwd(ssm_view x1, int C1, ssm_view x2, int C2, c
     SSM_REQUIRE((C1 + C2) % (KS * CK) == 0, "conv_splitk: Cin = %d is no multiple of KS x chunk = %d x %d", C1 + C2, KS, CK);
     SSM_REQUIRE(C2 == 0 || KS == 1, "conv_splitk: one source only (the kernel offsets its first source by the split's channel range)");
     ConvParams p;
-    const int rf = fill_common(p, x1, C1, x2, C2, w_packed, bias_packed, part, H, W, Cout, 0.f, 0, CK, W);
-    if (rf != SSM_OK) return rf;
+    const ssm_view none = {nullptr, 0, 0, 0};
+    SSM_TRY(fill_common(p, x1, C1, x2, C2, w_packed, bias_packed, part, none, 1, B, H, W, Cout, 0.f, 0, CK, W));
     p.NSPLIT = KS;
     p.ksB = B;
     return dispatch<false>(kind, p, B, (hipStream_t)stream);
@@ -830,10 +795,8 @@ extern "C" int ssm_conv2d_ups_add_fwd(ssm_view a, int C1, ssm_view b, int C2, co
     const int rc = ssm_conv_plan(3, C1 + C2, Cout, B, H, W, 0, 1, &kind, &BN, &CK);
     if (rc != SSM_OK) return rc;
     ConvParams p;
-    const int rf = fill_common(p, a, C1, b, C2, w_packed, bias_packed, y, H, W, Cout, slope, flags, CK, W / 2);
-    if (rf != SSM_OK) return rf;
-    const int ra = set_add(p, add, add_div, B, BN);
-    if (ra != SSM_OK) return ra;
+    SSM_TRY(fill_common(p, a, C1, b, C2, w_packed, bias_packed, y, add, add_div, B, H, W, Cout, slope, flags, CK, W / 2));
+    SSM_TRY(check_add(p, add, BN));
     return dispatch<true>(kind, p, B, (hipStream_t)stream);
 }
 

@@ -16,7 +16,7 @@
 //                          per chunk of CK input channels (the structure of conv_mfma_kernel, csrc/ssm_conv.hip, without taps / halo)
 //   upgemm_combine_kernel  out = LeakyReLU(bias + addend + the nine shifted bilinear gathers of Y)   one thread per 2 x 8 outputs
 //   upgemm_pack_kernel     OIHW filter -> [9 Cout / 128][CinP][128] slabs of the GEMM's A operand
-#include "ssm_common.h"
+#include "ssm_conv_host.h"
 #include "ssm_device.h"
 
 #include <atomic>
@@ -220,11 +220,11 @@ using G8 = GCfg<1, 2>;       //  8 x 16: maps whose height a 16-row tile oversho
 enum GemmKind { KG16, KG8, NGKIND };
 constexpr int kTH[NGKIND] = {G16::TH, G8::TH}, kTW[NGKIND] = {G16::TW, G8::TW};
 
-std::atomic<int> g_force_kind{-1};          // tests / tuning only (ssm_upgemm_force_kind)
+ssm::ForcedKind g_force_kind;          // tests / tuning only (ssm_upgemm_force_kind)
 
 int pick_kind(int h, int w) {
-    const int forced = g_force_kind.load();
-    if (forced >= 0 && forced < NGKIND) return forced;
+    const int forced = g_force_kind.get(NGKIND);
+    if (forced >= 0) return forced;
     long long best = 0;
     int kd = 0;
     for (int i = 0; i < NGKIND; ++i) {          // fewest computed pixels; the larger tile on a tie
@@ -242,10 +242,7 @@ int launch_gemm(GemmParams &p, int B, bool ragged, hipStream_t st) {
     p.tilesX = (p.w + C::TW - 1) / C::TW;
     p.tilesY = (p.h + C::TH - 1) / C::TH;
     const long long blocks = (long long)p.tilesX * p.tilesY * p.NB * B;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) {
-        ssm::set_error("upgemm: grid of %lld workgroups out of range", blocks);
-        return SSM_E_ARG;
-    }
+    SSM_TRY(ssm::check_grid("upgemm", blocks));
     if (ragged) SSM_LAUNCH((upgemm_kernel<C, true>), dim3((unsigned)blocks), dim3(256), C::BYTES, st, p);
     else SSM_LAUNCH((upgemm_kernel<C, false>), dim3((unsigned)blocks), dim3(256), C::BYTES, st, p);
     return ssm::check_launch("ssm_upgemm_conv2d_ups_add_fwd (gemm)");
@@ -441,8 +438,7 @@ extern "C" int ssm_upgemm_preferred(int Cin, int Cout, int B, int h, int w) {
 }
 
 extern "C" int ssm_upgemm_force_kind(int kind) {
-    g_force_kind.store(kind >= 0 && kind < NGKIND ? kind : -1);
-    return NGKIND;
+    return g_force_kind.set(kind, NGKIND);
 }
 
 extern "C" size_t ssm_upgemm_packed_weight_floats(int Cout, int Cin) {

@@ -27,7 +27,7 @@
 //
 // Two kernel forms share this file: wino_kernel (this description: 16 frequencies per wave, one workgroup per CU) and wino2_kernel
 // (further down: 8 frequencies per wave, two workgroups per CU - what the plan picks for most layers; profiles/DESIGN_history_r1-r3.md 3.2d says why).
-#include "ssm_common.h"
+#include "ssm_conv_host.h"
 #include "ssm_device.h"
 
 #include <cstring>
@@ -936,7 +936,9 @@ constexpr WKindInfo kWInfo[NWKIND] = {
 #undef X
 };
 
-std::atomic<int> g_force_wkind{-1};
+ssm::ForcedKind g_force_wkind;
+// (8-byte alignment is REQUIRED of output and addend: the epilogue has no element-wise path; no `vec` member)
+constexpr ssm::OutRules kWinoRules = {/*mask*/ true, /*piece*/ 2, /*required*/ true};
 
 // Estimated duration (cycles) of a launch.  The matrix work of one CU-round is mf = Cin/2 k-steps x 16 MFMAs x 64 cycles: one
 // workgroup of the first form (all 16 frequencies per wave, 256 resident workgroups), or two co-resident workgroups of the second
@@ -960,8 +962,8 @@ double estimate_wino(const WKindInfo &ki, int Cin, int Cout, int B, int H, int W
 }
 
 int pick_wkind(int Cin, int Cout, int B, int H, int W, int ups) {
-    const int forced = g_force_wkind.load();
-    if (forced >= 0 && forced < NWKIND) return forced;
+    const int forced = g_force_wkind.get(NWKIND);
+    if (forced >= 0) return forced;
     int best = -1;
     double bt = 0.0;
     for (int i = 0; i < NWKIND; ++i) {
@@ -983,22 +985,9 @@ int wlaunch(WinoParams &p, int B, hipStream_t st) {
     p.tilesY = (p.H + C::TH - 1) / C::TH;
     p.NB = (p.Cout + C::BN - 1) / C::BN;
     const long long blocks = (long long)p.tilesX * p.tilesY * p.NB * B * p.KS;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) {
-        ssm::set_error("wino conv: grid of %lld workgroups out of range", blocks);
-        return SSM_E_ARG;
-    }
-    constexpr int lds_bytes = WLds<C, UPS>::BYTES;
-    void (*kern)(const WinoParams);
-    if constexpr (C::NBLK == 4) kern = wino_kernel<C, UPS>;
-    else kern = wino2_kernel<C, UPS>;
-    static std::atomic<uint64_t> lds_reserved{0};          // one bit per device: the attribute is per (kernel, device)
-    const hipError_t attr_rc = ssm::reserve_lds(lds_reserved, (const void *)kern, lds_bytes);
-    if (attr_rc != hipSuccess) {
-        ssm::set_error("wino conv: cannot reserve %d bytes of LDS: %s", lds_bytes, hipGetErrorString(attr_rc));
-        return SSM_E_LAUNCH;
-    }
-    SSM_LAUNCH(kern, dim3((unsigned)blocks), dim3(256), lds_bytes, st, p);
-    return ssm::check_launch(UPS ? "ssm_wino_conv2d_ups_fwd" : "ssm_wino_conv2d_fwd");
+    const char *entry = UPS ? "ssm_wino_conv2d_ups_fwd" : "ssm_wino_conv2d_fwd";
+    if constexpr (C::NBLK == 4) return ssm::launch_tiles<wino_kernel<C, UPS>>("wino conv", entry, blocks, 256, WLds<C, UPS>::BYTES, st, p);
+    else return ssm::launch_tiles<wino2_kernel<C, UPS>>("wino conv", entry, blocks, 256, WLds<C, UPS>::BYTES, st, p);
 }
 
 template <bool UPS>
@@ -1043,21 +1032,14 @@ __global__ void wino_pack_kernel(const float *__restrict__ w, const float *__res
     if (i < nbias) bp[i] = (i < Cout) ? bias[i] : 0.f;
 }
 
-int wfill(WinoParams &p, ssm_view x1, int C1, ssm_view x2, int C2, const float *w_packed, const float *bias_packed, ssm_view y, int H,
-          int W, int Cout, float slope, int flags, int CK, int srcW) {
+int wfill(WinoParams &p, ssm_view x1, int C1, ssm_view x2, int C2, const float *w_packed, const float *bias_packed, ssm_view y, ssm_view pool,
+          ssm_view add, int add_div, int B, int H, int W, int Cout, float slope, int flags, int CK, int srcW) {
     SSM_REQUIRE(H > 0 && W > 0 && Cout > 0 && C1 > 0 && C2 >= 0, "wino conv: bad sizes");
     SSM_REQUIRE(x1.ptr && y.ptr && w_packed && bias_packed, "wino conv: null pointer");
     SSM_REQUIRE(C1 % CK == 0 && C2 % CK == 0, "wino conv: channel counts (%d,%d) must be multiples of %d", C1, C2, CK);
-    SSM_REQUIRE(ssm::aligned16(x1.ptr) && x1.sh % 4 == 0 && x1.sc % 4 == 0 && x1.sb % 4 == 0,
-                "wino conv: input 1 is not a padded-plane view (16-byte alignment)");
-    SSM_REQUIRE(x1.sh >= srcW + 2 * SSM_PADX, "wino conv: input 1 row stride %d leaves no zero frame for W=%d", x1.sh, srcW);
-    SSM_REQUIRE(ssm::aligned16(w_packed), "wino conv: packed filter must be 16-byte aligned");
-    SSM_REQUIRE((reinterpret_cast<size_t>(y.ptr) & 7) == 0 && y.sh % 2 == 0 && y.sc % 2 == 0 && y.sb % 2 == 0,
-                "wino conv: output view must be 8-byte aligned (2x2 pixel blocks are stored as row pairs)");
-    if (C2 > 0) {
-        SSM_REQUIRE(x2.ptr && ssm::aligned16(x2.ptr) && x2.sb % 4 == 0, "wino conv: input 2 is not a padded-plane view");
-        SSM_REQUIRE(x2.sh == x1.sh && x2.sc == x1.sc, "wino conv: cat sources must share row/channel strides");
-    }
+    SSM_TRY(ssm::check_source("wino conv", true, x1, srcW, w_packed));
+    SSM_TRY(ssm::check_output_pairs("wino conv", y));
+    SSM_TRY(ssm::check_source2("wino conv", x1, x2, C2));
     SSM_REQUIRE((long long)CK * x1.sc * 4 < 0x7fffffffLL, "wino conv: channel stride too large");
     p.src1 = x1.ptr;
     p.src2 = C2 > 0 ? x2.ptr : x1.ptr;
@@ -1069,44 +1051,15 @@ int wfill(WinoParams &p, ssm_view x1, int C1, ssm_view x2, int C2, const float *
     p.Cin = C1 + C2;
     p.wpk = w_packed;
     p.bias = bias_packed;
-    p.dst = y.ptr;
-    p.dsb = y.sb;
-    p.dsc = y.sc;
-    p.dsh = y.sh;
-    p.pool = nullptr;
-    p.psb = p.psc = 0;
-    p.psh = 0;
-    p.H = H;
-    p.W = W;
     p.hs = H / 2;
     p.ws = W / 2;
-    p.Cout = Cout;
-    p.slope = slope;
-    p.lrelu = ((flags & SSM_FLAG_LRELU) ? 1 : 0) | ((flags & SSM_FLAG_MASK) ? 2 : 0);
     p.abl = 0;
-    p.add = nullptr;
-    p.asb = p.asc = 0;
-    p.ash = 0;
-    p.adiv = 1;
     p.KS = 1;
     p.ksB = 0;
 #ifdef SSM_WINO_ABLATE
     if (const char *e = getenv("SSM_WINO_ABL")) p.abl = atoi(e);
 #endif
-    return SSM_OK;
-}
-
-int wset_add(WinoParams &p, ssm_view add, int add_div, int B) {
-    if (!add.ptr) return SSM_OK;
-    SSM_REQUIRE(add_div >= 1 && B % add_div == 0, "wino conv: the addend serves %d batch entries each, batch %d is no multiple", add_div, B);
-    SSM_REQUIRE((reinterpret_cast<size_t>(add.ptr) & 7) == 0 && add.sh % 2 == 0 && add.sc % 2 == 0 && add.sb % 2 == 0,
-                "wino conv: the addend view must be 8-byte aligned (read as row pairs)");
-    p.add = add.ptr;
-    p.asb = add.sb;
-    p.asc = add.sc;
-    p.ash = add.sh;
-    p.adiv = add_div;
-    return SSM_OK;
+    return ssm::bind_outputs("wino conv", kWinoRules, p, y, pool, add, add_div, B, H, W, Cout, slope, flags);
 }
 
 }  // namespace
@@ -1129,8 +1082,7 @@ extern "C" double ssm_wino_estimate(int Cin, int Cout, int B, int H, int W, int 
 }
 
 extern "C" int ssm_wino_force_kind(int kind) {
-    g_force_wkind.store(kind >= 0 && kind < NWKIND ? kind : -1);
-    return NWKIND;
+    return g_force_wkind.set(kind, NWKIND);
 }
 
 extern "C" size_t ssm_wino_packed_weight_floats(int Cout, int Cin, int BN) {
@@ -1157,17 +1109,7 @@ extern "C" int ssm_wino_conv2d_add_fwd(ssm_view x1, int C1, ssm_view x2, int C2,
     const int rc = ssm_wino_plan(C1 + C2, Cout, B, H, W, 0, &kind, &BN, &CK);
     if (rc != SSM_OK) return rc;
     WinoParams p;
-    const int rf = wfill(p, x1, C1, x2, C2, w_packed, bias_packed, y, H, W, Cout, slope, flags, CK, W);
-    if (rf != SSM_OK) return rf;
-    const int ra = wset_add(p, add, add_div, B);
-    if (ra != SSM_OK) return ra;
-    if (pool.ptr) {
-        SSM_REQUIRE(H % 2 == 0 && W % 2 == 0, "wino conv: fused pool needs even H, W");
-        p.pool = pool.ptr;
-        p.psb = pool.sb;
-        p.psc = pool.sc;
-        p.psh = pool.sh;
-    }
+    SSM_TRY(wfill(p, x1, C1, x2, C2, w_packed, bias_packed, y, pool, add, add_div, B, H, W, Cout, slope, flags, CK, W));
     return wdispatch<false>(kind, p, B, (hipStream_t)stream);
 }
 
@@ -1233,8 +1175,8 @@ extern "C" int ssm_wino_conv2d_splitk_fwd(ssm_view x1, int C1, ssm_view x2, int 
     const int CK = kWInfo[kind].ck;
     SSM_REQUIRE(((C1 + C2) / KS) % CK == 0, "wino conv_splitk: Cin / KS = %d is no multiple of the chunk (%d)", (C1 + C2) / KS, CK);
     WinoParams p;
-    const int rf = wfill(p, x1, C1, x2, C2, w_packed, bias_packed, part, H, W, Cout, 0.f, 0, CK, ups ? W / 2 : W);
-    if (rf != SSM_OK) return rf;
+    const ssm_view none = {nullptr, 0, 0, 0};
+    SSM_TRY(wfill(p, x1, C1, x2, C2, w_packed, bias_packed, part, none, none, 1, B, H, W, Cout, 0.f, 0, CK, ups ? W / 2 : W));
     p.KS = KS;
     p.ksB = B;
     return ups ? wdispatch<true>(kind, p, B, (hipStream_t)stream) : wdispatch<false>(kind, p, B, (hipStream_t)stream);
@@ -1254,10 +1196,8 @@ extern "C" int ssm_wino_conv2d_ups_add_fwd(ssm_view a, int C1, ssm_view b, int C
     const int rc = ssm_wino_plan(C1 + C2, Cout, B, H, W, 1, &kind, &BN, &CK);
     if (rc != SSM_OK) return rc;
     WinoParams p;
-    const int rf = wfill(p, a, C1, b, C2, w_packed, bias_packed, y, H, W, Cout, slope, flags, CK, W / 2);
-    if (rf != SSM_OK) return rf;
-    const int ra = wset_add(p, add, add_div, B);
-    if (ra != SSM_OK) return ra;
+    const ssm_view none = {nullptr, 0, 0, 0};
+    SSM_TRY(wfill(p, a, C1, b, C2, w_packed, bias_packed, y, none, add, add_div, B, H, W, Cout, slope, flags, CK, W / 2));
     return wdispatch<true>(kind, p, B, (hipStream_t)stream);
 }
 

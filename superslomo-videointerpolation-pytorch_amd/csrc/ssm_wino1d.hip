@@ -27,7 +27,7 @@
 // filter values and the raw [CK][TH+KS-1][TW+8] patch arrive by LDS-DMA (global_load_lds_dwordx4, saddr form), double-buffered; the
 // workgroup transforms the raw rows into V [CK][rows][2][tiles][4] (both operands of a macro-step are two conflict-free ds_read_b128
 // for 8 MFMAs).  The raw patch lands SHIFT floats into its LDS region so that every tile's 8-float window is 8- / 16-byte aligned.
-#include "ssm_common.h"
+#include "ssm_conv_host.h"
 #include "ssm_device.h"
 
 #include <atomic>
@@ -431,7 +431,7 @@ constexpr W1KindInfo kW1Info[NW1KIND] = {
 #undef X
 };
 
-std::atomic<int> g_force_w1kind{-1};
+ssm::ForcedKind g_force_w1kind;
 
 // Estimated duration (cycles) of a launch: two co-resident workgroups per CU share the matrix pipe; a CU-round of two workgroups
 // costs their matrix work (Cin/2 x KS x 8 MFMAs of 64 cycles each, per wave) plus what the neighbour cannot hide (per chunk: two
@@ -451,7 +451,7 @@ double estimate_w1(const W1KindInfo &ki, int Cin, int Cout, int B, int H, int W)
 }
 
 int pick_w1kind(int k, int Cin, int Cout, int B, int H, int W) {
-    const int forced = g_force_w1kind.load();
+    const int forced = g_force_w1kind.get(NW1KIND);
     int best = -1;
     double bt = 0.0;
     for (int i = 0; i < NW1KIND; ++i) {
@@ -473,20 +473,7 @@ int w1launch(W1Params &p, int B, hipStream_t st) {
     p.tilesY = (p.H + C::TH - 1) / C::TH;
     p.NB = p.Cout / C::BN;
     const long long blocks = (long long)p.tilesX * p.tilesY * p.NB * B;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) {
-        ssm::set_error("wino1d conv: grid of %lld workgroups out of range", blocks);
-        return SSM_E_ARG;
-    }
-    constexpr int lds_bytes = W1Lds<C>::BYTES;
-    auto kern = wino1d_kernel<C>;
-    static std::atomic<uint64_t> lds_reserved{0};          // one bit per device: the attribute is per (kernel, device)
-    const hipError_t attr_rc = ssm::reserve_lds(lds_reserved, (const void *)kern, lds_bytes);
-    if (attr_rc != hipSuccess) {
-        ssm::set_error("wino1d conv: cannot reserve %d bytes of LDS: %s", lds_bytes, hipGetErrorString(attr_rc));
-        return SSM_E_LAUNCH;
-    }
-    SSM_LAUNCH(kern, dim3((unsigned)blocks), dim3(256), lds_bytes, st, p);
-    return ssm::check_launch("ssm_wino1d_conv2d_fwd");
+    return ssm::launch_tiles<wino1d_kernel<C>>("wino1d conv", "ssm_wino1d_conv2d_fwd", blocks, 256, W1Lds<C>::BYTES, st, p);
 }
 
 int w1dispatch(int kind, W1Params &p, int B, hipStream_t st) {
@@ -554,8 +541,7 @@ extern "C" int ssm_wino1d_plan(int k, int Cin, int Cout, int B, int H, int W, in
 }
 
 extern "C" int ssm_wino1d_force_kind(int kind) {
-    g_force_w1kind.store(kind >= 0 && kind < NW1KIND ? kind : -1);
-    return NW1KIND;
+    return g_force_w1kind.set(kind, NW1KIND);
 }
 
 extern "C" size_t ssm_wino1d_packed_weight_floats(int Cout, int CinP, int k, int BN) {
@@ -581,13 +567,11 @@ extern "C" int ssm_wino1d_conv2d_add_fwd(ssm_view x, int Cin, const float *w_pac
     SSM_REQUIRE(B > 0 && H > 0 && W > 0 && Cout > 0 && Cin > 0, "wino1d conv: bad sizes");
     const int rc = ssm_wino1d_plan(k, Cin, Cout, B, H, W, &kind, &BN, &CK);
     if (rc != SSM_OK) return rc;
-    const int M = kW1Info[kind].m;
+    // (no mask path; the vector piece is the tile configuration's M output columns per transform: 8- or 16-byte pieces)
+    const ssm::OutRules rules = {/*mask*/ false, /*piece*/ kW1Info[kind].m, /*required*/ false};
     SSM_REQUIRE(x.ptr && y.ptr && w_packed && bias_packed, "wino1d conv: null pointer");
     SSM_REQUIRE(Cin % CK == 0, "wino1d conv: the channel count (%d) must be a multiple of %d (pad the view)", Cin, CK);
-    SSM_REQUIRE(ssm::aligned16(x.ptr) && x.sh % 4 == 0 && x.sc % 4 == 0 && x.sb % 4 == 0,
-                "wino1d conv: the input is not a padded-plane view (16-byte alignment)");
-    SSM_REQUIRE(x.sh >= W + 2 * SSM_PADX, "wino1d conv: input row stride %d leaves no zero frame for W=%d", x.sh, W);
-    SSM_REQUIRE(ssm::aligned16(w_packed), "wino1d conv: packed filter must be 16-byte aligned");
+    SSM_TRY(ssm::check_source("wino1d conv", false, x, W, w_packed));
     SSM_REQUIRE((long long)CK * x.sc * 4 < 0x7fffffffLL, "wino1d conv: channel stride too large");
     W1Params p;
     p.src = x.ptr;
@@ -597,46 +581,10 @@ extern "C" int ssm_wino1d_conv2d_add_fwd(ssm_view x, int Cin, const float *w_pac
     p.Cin = Cin;
     p.wpk = w_packed;
     p.bias = bias_packed;
-    p.dst = y.ptr;
-    p.dsb = y.sb;
-    p.dsc = y.sc;
-    p.dsh = y.sh;
-    p.pool = nullptr;
-    p.psb = p.psc = 0;
-    p.psh = 0;
-    p.H = H;
-    p.W = W;
-    p.Cout = Cout;
-    p.slope = slope;
-    p.lrelu = (flags & SSM_FLAG_LRELU) ? 1 : 0;
     p.abl = 0;
-    p.add = nullptr;
-    p.asb = p.asc = 0;
-    p.ash = 0;
-    p.adiv = 1;
 #ifdef SSM_WINO_ABLATE
     if (const char *e = getenv("SSM_WINO1D_ABL")) p.abl = atoi(e);
 #endif
-    const size_t am = (size_t)M * 4 - 1;          // M-float pieces: 8- / 16-byte alignment of every view the kernel moves them through
-    bool vec = W % M == 0 && (reinterpret_cast<size_t>(y.ptr) & am) == 0 && y.sh % M == 0 && y.sc % M == 0 && y.sb % M == 0;
-    if (add.ptr) {
-        SSM_REQUIRE(add_div >= 1 && B % add_div == 0, "wino1d conv: the addend serves %d batch entries each, batch %d is no multiple", add_div, B);
-        p.add = add.ptr;
-        p.asb = add.sb;
-        p.asc = add.sc;
-        p.ash = add.sh;
-        p.adiv = add_div;
-        vec = vec && (reinterpret_cast<size_t>(add.ptr) & am) == 0 && add.sh % M == 0 && add.sc % M == 0 && add.sb % M == 0;
-    }
-    if (pool.ptr) {
-        SSM_REQUIRE(H % 2 == 0 && W % 2 == 0, "wino1d conv: fused pool needs even H, W");
-        p.pool = pool.ptr;
-        p.psb = pool.sb;
-        p.psc = pool.sc;
-        p.psh = pool.sh;
-        const size_t pm = (size_t)(M / 2) * 4 - 1;
-        vec = vec && (reinterpret_cast<size_t>(pool.ptr) & pm) == 0 && pool.sh % (M / 2) == 0 && pool.sc % (M / 2) == 0 && pool.sb % (M / 2) == 0;
-    }
-    p.vec = vec ? 1 : 0;
+    SSM_TRY(ssm::bind_outputs("wino1d conv", rules, p, y, pool, add, add_div, B, H, W, Cout, slope, flags));
     return w1dispatch(kind, p, B, (hipStream_t)stream);
 }

@@ -36,7 +36,7 @@
 //                                     double-buffered, ONE barrier per chunk, the next chunk's transform in the slots of the matrix loop.
 // Whatever is wave-uniform at run time (which part of a (cin, tile) a thread transforms, whether later chunks exist) selects a
 // straight-line INSTANCE of the loop instead of being tested inside it: a scalar branch in front of an LDS read exposes its latency.
-#include "ssm_common.h"
+#include "ssm_conv_host.h"
 #include "ssm_device.h"
 
 #include <atomic>
@@ -997,7 +997,8 @@ constexpr W4KindInfo kW4Info[NW4KIND] = {
 #undef X
 };
 
-std::atomic<int> g_force_w4kind{-1};
+ssm::ForcedKind g_force_w4kind;
+constexpr ssm::OutRules kW4Rules = {/*mask*/ true, /*piece*/ 4, /*required*/ false};
 #if defined(SSM_WINO_ABLATE) || defined(W4_TRACE)
 std::atomic<unsigned long long *> g_w4dbg{nullptr};      // diagnostics builds only (ssm_wino4_debug_buffer; `make wabl` / `make wtrace`)
 #endif
@@ -1023,8 +1024,8 @@ double estimate_w4(const W4KindInfo &ki, int Cin, int Cout, int B, int H, int W,
 }
 
 int pick_w4kind(int Cin, int Cout, int B, int H, int W, int ups) {
-    const int forced = g_force_w4kind.load();
-    if (forced >= 0 && forced < NW4KIND) return forced;
+    const int forced = g_force_w4kind.get(NW4KIND);
+    if (forced >= 0) return forced;
     int best = -1;
     double bt = 0.0;
     static const int allow_wide = [] {
@@ -1058,13 +1059,7 @@ int w4launch(W4Params &p, int B, hipStream_t st) {
     }
     const long long ntiles = p.border ? 2LL * p.tilesX + 2LL * (p.tilesY - 2) : (long long)p.tilesX * p.tilesY;
     const long long blocks = ntiles * p.NB * B;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) {
-        ssm::set_error("wino4 conv: grid of %lld workgroups out of range", blocks);
-        return SSM_E_ARG;
-    }
-    void (*kern)(const W4Params) = wino4_kernel<C, UPS, SHUF>;
     int lds_bytes = W4Lds<C, UPS>::BYTES + (C::NCB == 2 ? C::BN * 4 : 0);          // (64-cout form: + the workgroup's biases)
-    const int threads = C::THREADS;
 #ifdef W4_TRACE
     lds_bytes += 4096;
 #endif
@@ -1072,14 +1067,8 @@ int w4launch(W4Params &p, int B, hipStream_t st) {
     if (const char *e = getenv("SSM_WINO4_SOLO"))          // diagnostics: one workgroup per CU (the LDS request leaves no room for a second)
         if (atoi(e) && lds_bytes < 100 * 1024) lds_bytes = 100 * 1024;
 #endif
-    static std::atomic<uint64_t> lds_reserved{0};          // one bit per device: the attribute is per (kernel, device)
-    const hipError_t attr_rc = ssm::reserve_lds(lds_reserved, (const void *)kern, lds_bytes);
-    if (attr_rc != hipSuccess) {
-        ssm::set_error("wino4 conv: cannot reserve %d bytes of LDS: %s", lds_bytes, hipGetErrorString(attr_rc));
-        return SSM_E_LAUNCH;
-    }
-    SSM_LAUNCH(kern, dim3((unsigned)blocks), dim3(threads), lds_bytes, st, p);
-    return ssm::check_launch(UPS ? "ssm_wino4_conv2d_ups_fwd" : "ssm_wino4_conv2d_fwd");
+    return ssm::launch_tiles<wino4_kernel<C, UPS, SHUF>>("wino4 conv", UPS ? "ssm_wino4_conv2d_ups_fwd" : "ssm_wino4_conv2d_fwd", blocks, C::THREADS,
+                                                          lds_bytes, st, p);
 }
 
 template <bool UPS>
@@ -1150,14 +1139,8 @@ int w4fill(W4Params &p, ssm_view x1, int C1, ssm_view x2, int C2, const float *w
     SSM_REQUIRE(Cout % 32 == 0, "wino4 conv: Cout (%d) must be a multiple of 32", Cout);
     SSM_REQUIRE(x1.ptr && y.ptr && w_packed && bias_packed, "wino4 conv: null pointer");
     SSM_REQUIRE(C1 % 4 == 0 && C2 % 4 == 0, "wino4 conv: channel counts (%d,%d) must be multiples of 4", C1, C2);
-    SSM_REQUIRE(ssm::aligned16(x1.ptr) && x1.sh % 4 == 0 && x1.sc % 4 == 0 && x1.sb % 4 == 0,
-                "wino4 conv: input 1 is not a padded-plane view (16-byte alignment)");
-    SSM_REQUIRE(x1.sh >= srcW + 2 * SSM_PADX, "wino4 conv: input 1 row stride %d leaves no zero frame for W=%d", x1.sh, srcW);
-    SSM_REQUIRE(ssm::aligned16(w_packed), "wino4 conv: packed filter must be 16-byte aligned");
-    if (C2 > 0) {
-        SSM_REQUIRE(x2.ptr && ssm::aligned16(x2.ptr) && x2.sb % 4 == 0, "wino4 conv: input 2 is not a padded-plane view");
-        SSM_REQUIRE(x2.sh == x1.sh && x2.sc == x1.sc, "wino4 conv: cat sources must share row/channel strides");
-    }
+    SSM_TRY(ssm::check_source("wino4 conv", true, x1, srcW, w_packed));
+    SSM_TRY(ssm::check_source2("wino4 conv", x1, x2, C2));
     SSM_REQUIRE(4LL * x1.sc * 4 < 0x7fffffffLL, "wino4 conv: channel stride too large");
     p.src1 = x1.ptr;
     p.src2 = C2 > 0 ? x2.ptr : x1.ptr;
@@ -1169,26 +1152,10 @@ int w4fill(W4Params &p, ssm_view x1, int C1, ssm_view x2, int C2, const float *w
     p.Cin = C1 + C2;
     p.wpk = w_packed;
     p.bias = bias_packed;
-    p.dst = y.ptr;
-    p.dsb = y.sb;
-    p.dsc = y.sc;
-    p.dsh = y.sh;
-    p.pool = nullptr;
-    p.psb = p.psc = 0;
-    p.psh = 0;
-    p.H = H;
-    p.W = W;
     p.hs = H / 2;
     p.ws = W / 2;
-    p.Cout = Cout;
-    p.slope = slope;
-    p.lrelu = ((flags & SSM_FLAG_LRELU) ? 1 : 0) | ((flags & SSM_FLAG_MASK) ? 2 : 0);
     p.abl = 0;
     p.border = 0;
-    p.add = nullptr;
-    p.asb = p.asc = 0;
-    p.ash = 0;
-    p.adiv = 1;
 #ifdef SSM_WINO_ABLATE
     if (const char *e = getenv("SSM_WINO4_ABL")) p.abl = atoi(e);
 #endif
@@ -1206,26 +1173,7 @@ int w4fill(W4Params &p, ssm_view x1, int C1, ssm_view x2, int C2, const float *w
 #ifdef W4_TRACE
     if (const char *e = getenv("SSM_W4_TRACE_BLOCK")) p.trace_block = atoi(e);
 #endif
-    bool vec = W % 4 == 0 && ssm::aligned16(y.ptr) && y.sh % 4 == 0 && y.sc % 4 == 0 && y.sb % 4 == 0;
-    if (add.ptr) {
-        SSM_REQUIRE(add_div >= 1 && B % add_div == 0, "wino4 conv: the addend serves %d batch entries each, batch %d is no multiple", add_div, B);
-        p.add = add.ptr;
-        p.asb = add.sb;
-        p.asc = add.sc;
-        p.ash = add.sh;
-        p.adiv = add_div;
-        vec = vec && ssm::aligned16(add.ptr) && add.sh % 4 == 0 && add.sc % 4 == 0 && add.sb % 4 == 0;
-    }
-    if (pool.ptr) {
-        SSM_REQUIRE(H % 2 == 0 && W % 2 == 0, "wino4 conv: fused pool needs even H, W");
-        p.pool = pool.ptr;
-        p.psb = pool.sb;
-        p.psc = pool.sc;
-        p.psh = pool.sh;
-        vec = vec && (reinterpret_cast<size_t>(pool.ptr) & 7) == 0 && pool.sh % 2 == 0 && pool.sc % 2 == 0 && pool.sb % 2 == 0;
-    }
-    p.vec = vec ? 1 : 0;
-    return SSM_OK;
+    return ssm::bind_outputs("wino4 conv", kW4Rules, p, y, pool, add, add_div, B, H, W, Cout, slope, flags);
 }
 
 }  // namespace
@@ -1261,8 +1209,7 @@ extern "C" int ssm_wino4_preferred(int Cin, int Cout, int B, int H, int W, int u
 }
 
 extern "C" int ssm_wino4_force_kind(int kind) {
-    g_force_w4kind.store(kind >= 0 && kind < NW4KIND ? kind : -1);
-    return NW4KIND;
+    return g_force_w4kind.set(kind, NW4KIND);
 }
 
 extern "C" size_t ssm_wino4_packed_weight_floats(int Cout, int Cin) { return (size_t)(Cout / 32) * (size_t)Cin * 9 * 32 * 4; }

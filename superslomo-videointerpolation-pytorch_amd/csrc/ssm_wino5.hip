@@ -24,7 +24,7 @@
 // the MFMAs.  A lone wave issues one vector instruction per ~5 cycles (tools/valu_rate_probe.py), so the two passes (182 vector + 44 LDS
 // instructions) cost ~2000 cycles per k-step beside 2048 of MFMA: the form runs at ~0.33 of the matrix pipe and still beats F(4,5)
 // along x (0.71 of the pipe at 2.5 x the multiplies) by 1.27 x.
-#include "ssm_common.h"
+#include "ssm_conv_host.h"
 #include "ssm_device.h"
 #include "ssm_wino5_pack.h"
 
@@ -899,7 +899,8 @@ enum W5Kind {
         NW5KIND
 };
 
-std::atomic<int> g_force_w5kind{-1};
+ssm::ForcedKind g_force_w5kind;
+constexpr ssm::OutRules kW5Rules = {/*mask*/ true, /*piece*/ 4, /*required*/ false};
 #ifdef W5_TRACE
 std::atomic<unsigned long long *> g_w5dbg{nullptr};
 #endif
@@ -911,25 +912,11 @@ int w5launch(W5Params &p, int B, hipStream_t st) {
     p.NB = p.Cout / 32;
     // (no read outside the padded plane: the per-lane DMA offsets clamp overshoot rows / pieces to the zero frame, see wino5_kernel)
     const long long blocks = (long long)p.tilesX * p.tilesY * p.NB * B;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) {
-        ssm::set_error("wino5 conv: grid of %lld workgroups out of range", blocks);
-        return SSM_E_ARG;
-    }
 #if W5_SPLIT
-    void (*kern)(const W5Params) = wino5s_kernel<C>;
-    constexpr int lds_bytes = W5SLds<C>::BYTES, threads = 512;
+    return ssm::launch_tiles<wino5s_kernel<C>>("wino5 conv", "ssm_wino5_conv2d_add_fwd", blocks, 512, W5SLds<C>::BYTES, st, p);
 #else
-    void (*kern)(const W5Params) = wino5_kernel<C>;
-    constexpr int lds_bytes = C::BYTES, threads = 256;
+    return ssm::launch_tiles<wino5_kernel<C>>("wino5 conv", "ssm_wino5_conv2d_add_fwd", blocks, 256, C::BYTES, st, p);
 #endif
-    static std::atomic<uint64_t> lds_reserved{0};          // one bit per device: the attribute is per (kernel, device)
-    const hipError_t attr_rc = ssm::reserve_lds(lds_reserved, (const void *)kern, lds_bytes);
-    if (attr_rc != hipSuccess) {
-        ssm::set_error("wino5 conv: cannot reserve %d bytes of LDS: %s", lds_bytes, hipGetErrorString(attr_rc));
-        return SSM_E_LAUNCH;
-    }
-    SSM_LAUNCH(kern, dim3((unsigned)blocks), dim3(threads), lds_bytes, st, p);
-    return ssm::check_launch("ssm_wino5_conv2d_add_fwd");
 }
 
 int w5dispatch(int kind, W5Params &p, int B, hipStream_t st) {
@@ -963,8 +950,8 @@ extern "C" int ssm_wino5_plan(int Cin, int Cout, int B, int H, int W, int *kind)
         ssm::set_error("wino5 conv: no tile configuration for Cin=%d Cout=%d (Cout a multiple of 32)", Cin, Cout);
         return SSM_E_UNSUPPORTED;
     }
-    const int forced = g_force_w5kind.load();
-    if (kind) *kind = (forced >= 0 && forced < NW5KIND) ? forced : 0;
+    const int forced = g_force_w5kind.get(NW5KIND);
+    if (kind) *kind = forced >= 0 ? forced : 0;
     return SSM_OK;
 }
 
@@ -978,8 +965,7 @@ extern "C" int ssm_wino5_debug_buffer(unsigned long long *dev_counters) {
 #endif
 
 extern "C" int ssm_wino5_force_kind(int kind) {
-    g_force_w5kind.store(kind >= 0 && kind < NW5KIND ? kind : -1);
-    return NW5KIND;
+    return g_force_w5kind.set(kind, NW5KIND);
 }
 
 extern "C" size_t ssm_wino5_packed_weight_floats(int Cout, int CinP) { return (size_t)(Cout / 32) * (size_t)(CinP / 4) * 16 * 4 * 32 * 4; }
@@ -1004,10 +990,7 @@ extern "C" int ssm_wino5_conv2d_add_fwd(ssm_view x, int Cin, const float *w_pack
     if (rc != SSM_OK) return rc;
     SSM_REQUIRE(x.ptr && y.ptr && w_packed && bias_packed, "wino5 conv: null pointer");
     SSM_REQUIRE(Cin % 4 == 0, "wino5 conv: the channel count (%d) must be a multiple of 4 (pad the view)", Cin);
-    SSM_REQUIRE(ssm::aligned16(x.ptr) && x.sh % 4 == 0 && x.sc % 4 == 0 && x.sb % 4 == 0,
-                "wino5 conv: the input is not a padded-plane view (16-byte alignment)");
-    SSM_REQUIRE(x.sh >= W + 2 * SSM_PADX, "wino5 conv: input row stride %d leaves no zero frame for W=%d", x.sh, W);
-    SSM_REQUIRE(ssm::aligned16(w_packed), "wino5 conv: packed filter must be 16-byte aligned");
+    SSM_TRY(ssm::check_source("wino5 conv", false, x, W, w_packed));
     SSM_REQUIRE(4LL * x.sc * 4 < 0x7fffffffLL, "wino5 conv: channel stride too large");
     W5Params p;
     p.src = x.ptr;
@@ -1017,41 +1000,7 @@ extern "C" int ssm_wino5_conv2d_add_fwd(ssm_view x, int Cin, const float *w_pack
     p.Cin = Cin;
     p.wpk = w_packed;
     p.bias = bias_packed;
-    p.dst = y.ptr;
-    p.dsb = y.sb;
-    p.dsc = y.sc;
-    p.dsh = y.sh;
-    p.pool = nullptr;
-    p.psb = p.psc = 0;
-    p.psh = 0;
-    p.H = H;
-    p.W = W;
-    p.Cout = Cout;
-    p.slope = slope;
-    p.lrelu = ((flags & SSM_FLAG_LRELU) ? 1 : 0) | ((flags & SSM_FLAG_MASK) ? 2 : 0);
-    p.add = nullptr;
-    p.asb = p.asc = 0;
-    p.ash = 0;
-    p.adiv = 1;
-    bool vec = W % 4 == 0 && ssm::aligned16(y.ptr) && y.sh % 4 == 0 && y.sc % 4 == 0 && y.sb % 4 == 0;
-    if (add.ptr) {
-        SSM_REQUIRE(add_div >= 1 && B % add_div == 0, "wino5 conv: the addend serves %d batch entries each, batch %d is no multiple", add_div, B);
-        p.add = add.ptr;
-        p.asb = add.sb;
-        p.asc = add.sc;
-        p.ash = add.sh;
-        p.adiv = add_div;
-        vec = vec && ssm::aligned16(add.ptr) && add.sh % 4 == 0 && add.sc % 4 == 0 && add.sb % 4 == 0;
-    }
-    if (pool.ptr) {
-        SSM_REQUIRE(H % 2 == 0 && W % 2 == 0, "wino5 conv: fused pool needs even H, W");
-        p.pool = pool.ptr;
-        p.psb = pool.sb;
-        p.psc = pool.sc;
-        p.psh = pool.sh;
-        vec = vec && (reinterpret_cast<size_t>(pool.ptr) & 7) == 0 && pool.sh % 2 == 0 && pool.sc % 2 == 0 && pool.sb % 2 == 0;
-    }
-    p.vec = vec ? 1 : 0;
+    SSM_TRY(ssm::bind_outputs("wino5 conv", kW5Rules, p, y, pool, add, add_div, B, H, W, Cout, slope, flags));
 #ifdef W5_TRACE
     p.dbg = g_w5dbg.load();
 #else

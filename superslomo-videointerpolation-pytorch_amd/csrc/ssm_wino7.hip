@@ -34,7 +34,7 @@
 //
 // Pipeline, one barrier per input channel:  [barrier]  DMA U(c+1), patch(c+3) | row pass (c+2) | column pass (c+1) | 49 MFMAs of channel c,
 // the transform pieces and the LDS-DMA instructions placed in the slots behind the MFMAs (everything double-buffered; 97 KiB of LDS).
-#include "ssm_common.h"
+#include "ssm_conv_host.h"
 #include "ssm_device.h"
 #include "ssm_wino7_pack.h"
 
@@ -1003,15 +1003,16 @@ constexpr W7KindInfo kW7Info[NW7KIND] = {
 #undef X
 };
 
-std::atomic<int> g_force_w7kind{-1};
+ssm::ForcedKind g_force_w7kind;
+constexpr ssm::OutRules kW7Rules = {/*mask*/ false, /*piece*/ 4, /*required*/ false};
 #ifdef W7_TRACE
 std::atomic<unsigned long long *> g_w7dbg{nullptr};
 #endif
 
 // the configuration with the fewest workgroup-rounds (tile overshoot included); ties go to the 16x32-pixel tile
 int pick_w7kind(int Cout, int B, int H, int W) {
-    const int forced = g_force_w7kind.load();
-    if (forced >= 0 && forced < NW7KIND) return forced;
+    const int forced = g_force_w7kind.get(NW7KIND);
+    if (forced >= 0) return forced;
     // $SSM_WINO7_SPLIT=0: the 4-wave kernel (read per call: A/B runs and the parity tests use both in one process)
     const char *env = getenv("SSM_WINO7_SPLIT");
     const int split = !(env && atoi(env) == 0);
@@ -1036,20 +1037,8 @@ int w7launch(W7Params &p, int B, hipStream_t st) {
     p.NB = p.Cout / 32;
     // (no read outside the padded plane: the per-lane DMA offsets clamp overshoot rows / pieces to the zero frame, see wino7_kernel)
     const long long blocks = (long long)p.tilesX * p.tilesY * p.NB * B;
-    if (blocks <= 0 || blocks > 0x7fffffffLL) {
-        ssm::set_error("wino7 conv: grid of %lld workgroups out of range", blocks);
-        return SSM_E_ARG;
-    }
-    void (*kern)(const W7Params) = SPLIT ? wino7s_kernel<C> : wino7_kernel<C>;
-    constexpr int lds_bytes = C::BYTES;
-    static std::atomic<uint64_t> lds_reserved{0};          // one bit per device: the attribute is per (kernel, device)
-    const hipError_t attr_rc = ssm::reserve_lds(lds_reserved, (const void *)kern, lds_bytes);
-    if (attr_rc != hipSuccess) {
-        ssm::set_error("wino7 conv: cannot reserve %d bytes of LDS: %s", lds_bytes, hipGetErrorString(attr_rc));
-        return SSM_E_LAUNCH;
-    }
-    SSM_LAUNCH(kern, dim3((unsigned)blocks), dim3(SPLIT ? 512 : 256), lds_bytes, st, p);
-    return ssm::check_launch("ssm_wino7_conv2d_add_fwd");
+    constexpr void (*kern)(const W7Params) = SPLIT ? wino7s_kernel<C> : wino7_kernel<C>;
+    return ssm::launch_tiles<kern>("wino7 conv", "ssm_wino7_conv2d_add_fwd", blocks, SPLIT ? 512 : 256, C::BYTES, st, p);
 }
 
 int w7dispatch(int kind, W7Params &p, int B, hipStream_t st) {
@@ -1097,8 +1086,7 @@ extern "C" int ssm_wino7_debug_buffer(unsigned long long *dev_counters) {
 #endif
 
 extern "C" int ssm_wino7_force_kind(int kind) {
-    g_force_w7kind.store(kind >= 0 && kind < NW7KIND ? kind : -1);
-    return NW7KIND;
+    return g_force_w7kind.set(kind, NW7KIND);
 }
 
 // (Cout rounded up to whole 32-channel blocks: the pack fills the channels beyond Cout with zeros - a caller that convolves with a
@@ -1124,10 +1112,7 @@ extern "C" int ssm_wino7_conv2d_add_fwd(ssm_view x, int Cin, const float *w_pack
     const int rc = ssm_wino7_plan(Cin, Cout, B, H, W, &kind);
     if (rc != SSM_OK) return rc;
     SSM_REQUIRE(x.ptr && y.ptr && w_packed && bias_packed, "wino7 conv: null pointer");
-    SSM_REQUIRE(ssm::aligned16(x.ptr) && x.sh % 4 == 0 && x.sc % 4 == 0 && x.sb % 4 == 0,
-                "wino7 conv: the input is not a padded-plane view (16-byte alignment)");
-    SSM_REQUIRE(x.sh >= W + 2 * SSM_PADX, "wino7 conv: input row stride %d leaves no zero frame for W=%d", x.sh, W);
-    SSM_REQUIRE(ssm::aligned16(w_packed), "wino7 conv: packed filter must be 16-byte aligned");
+    SSM_TRY(ssm::check_source("wino7 conv", false, x, W, w_packed));
     SSM_REQUIRE(64LL * x.sh * 4 < 0x7fffffffLL, "wino7 conv: row stride too large");
     W7Params p;
     p.src = x.ptr;
@@ -1137,41 +1122,7 @@ extern "C" int ssm_wino7_conv2d_add_fwd(ssm_view x, int Cin, const float *w_pack
     p.Cin = Cin;
     p.wpk = w_packed;
     p.bias = bias_packed;
-    p.dst = y.ptr;
-    p.dsb = y.sb;
-    p.dsc = y.sc;
-    p.dsh = y.sh;
-    p.pool = nullptr;
-    p.psb = p.psc = 0;
-    p.psh = 0;
-    p.H = H;
-    p.W = W;
-    p.Cout = Cout;
-    p.slope = slope;
-    p.lrelu = (flags & SSM_FLAG_LRELU) ? 1 : 0;
-    p.add = nullptr;
-    p.asb = p.asc = 0;
-    p.ash = 0;
-    p.adiv = 1;
-    bool vec = W % 4 == 0 && ssm::aligned16(y.ptr) && y.sh % 4 == 0 && y.sc % 4 == 0 && y.sb % 4 == 0;
-    if (add.ptr) {
-        SSM_REQUIRE(add_div >= 1 && B % add_div == 0, "wino7 conv: the addend serves %d batch entries each, batch %d is no multiple", add_div, B);
-        p.add = add.ptr;
-        p.asb = add.sb;
-        p.asc = add.sc;
-        p.ash = add.sh;
-        p.adiv = add_div;
-        vec = vec && ssm::aligned16(add.ptr) && add.sh % 4 == 0 && add.sc % 4 == 0 && add.sb % 4 == 0;
-    }
-    if (pool.ptr) {
-        SSM_REQUIRE(H % 2 == 0 && W % 2 == 0, "wino7 conv: fused pool needs even H, W");
-        p.pool = pool.ptr;
-        p.psb = pool.sb;
-        p.psc = pool.sc;
-        p.psh = pool.sh;
-        vec = vec && (reinterpret_cast<size_t>(pool.ptr) & 7) == 0 && pool.sh % 2 == 0 && pool.sc % 2 == 0 && pool.sb % 2 == 0;
-    }
-    p.vec = vec ? 1 : 0;
+    SSM_TRY(ssm::bind_outputs("wino7 conv", kW7Rules, p, y, pool, add, add_div, B, H, W, Cout, slope, flags));
 #ifdef W7_TRACE
     p.dbg = g_w7dbg.load();
 #else

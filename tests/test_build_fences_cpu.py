@@ -80,10 +80,18 @@ def test_no_process_wide_guard_on_a_per_device_attribute():
     for name, ctxs in callers.items():
         for ctx in ctxs:
             assert "hipGetDevice" in ctx, "%s: hipFuncSetAttribute without a device key in front of it" % name
-    # every > 64 KiB launcher goes through the per-device helper with its own per-kernel mask
+    # every > 64 KiB launcher goes through the per-device helper with its own per-kernel mask: the shared launch tail (ssm::launch_tiles,
+    # ssm_conv_host.h) is a function template over the KERNEL, its mask a static of that template, the opt-in in front of the launch ...
+    host = _strip_comments(open(os.path.join(csrc, "ssm_conv_host.h")).read())
+    tail = host[host.index("template <auto Kern"):]
+    assert "static std::atomic<uint64_t> lds_reserved" in tail and "reserve_lds(lds_reserved, (const void *)Kern" in tail
+    assert tail.index("reserve_lds(lds_reserved") < tail.index("SSM_LAUNCH(Kern")
+    # ... and the five objects launch their convolution kernels through it and nothing else (what is left are the filter repacks, no LDS)
     for name in ("ssm_wino.hip", "ssm_wino1d.hip", "ssm_wino4.hip", "ssm_wino5.hip", "ssm_wino7.hip"):
         src = _strip_comments(open(os.path.join(csrc, name)).read())
-        assert "ssm::reserve_lds(lds_reserved" in src and "static std::atomic<uint64_t> lds_reserved" in src, name
+        assert "ssm::launch_tiles<" in src and "lds_reserved" not in src and "hipLaunchKernel" not in src, name
+        direct = re.findall(r"SSM_LAUNCH\(\(?(\w+)", src)
+        assert direct and all(k.endswith("_pack_kernel") for k in direct), (name, direct)
 
 
 def test_header_states_the_device_contract_the_code_implements():
