@@ -399,7 +399,7 @@ class UNetGrad:
             with torch.cuda.stream(sd) if sd is not None else contextlib.nullcontext():
                 du = self.ww.get(name)
                 if tm is not None:
-                    e0, e1 = tm.span("wgrad", "s%d.%s" % (plan.stage, name), flops, issued=flops * (16.0 / 36.0 if du is not None else 1.0))
+                    e0, e1 = tm.span("wgrad", "s%d.%s" % (plan.stage, name), flops, issued=flops * hb.FORMS["wino" if du is not None else "direct"].issued(k))
                     e0.record()
                 off = 0
                 for sname in srcs:

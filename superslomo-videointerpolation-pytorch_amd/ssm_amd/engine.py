@@ -160,12 +160,10 @@ def choose_algo(name, ci, co, k, nb, h, w, ups, wino, wino1d, wino4=None, blocke
     return "direct"
 
 
-_ALGO_CLASS = {"direct": lambda: hb.PackedConv, "wino": lambda: hb.PackedWino, "wino4": lambda: hb.PackedWino4, "wino1d": lambda: hb.PackedWino1d,
-               "wino7": lambda: hb.PackedWino7, "wino5": lambda: hb.PackedWino5, "upgemm": lambda: hb.PackedUpGemm}
+# what each algorithm is - its packed-filter class, its launchers, what it issues - is one entry of hb.FORMS
+_ALGO_CLASS = {name: (lambda form=form: form.cls) for name, form in hb.FORMS.items()}
 # multiply-adds issued on the matrix cores per direct-form multiply-add, by algorithm and kernel size
-ISSUED_FACTOR = {"direct": lambda k: 1.0, "wino": lambda k: 16.0 / 36.0, "wino4": lambda k: 36.0 / 144.0,
-                 "wino1d": lambda k: 8.0 / 14.0 if k == 7 else 8.0 / 20.0, "wino7": lambda k: 196.0 / 784.0,
-                 "wino5": lambda k: 64.0 / 400.0, "upgemm": lambda k: 9.0 / 36.0}
+ISSUED_FACTOR = {name: form.issued for name, form in hb.FORMS.items()}
 
 
 def issued_factor(pk):
@@ -175,20 +173,9 @@ def issued_factor(pk):
 
 def conv_fn(pk, ups=False):
     """The launcher that goes with a packed filter's algorithm."""
-    if pk.algo == "upgemm":
-        assert ups, "the low-res GEMM form is for the fused-upsample layers"
-        return hb.conv2d_ups_upgemm
-    if pk.algo == "wino7":
-        return hb.conv2d_wino7
-    if pk.algo == "wino5":
-        return hb.conv2d_wino5
-    if pk.algo == "wino1d":
-        return hb.conv2d_wino1d
-    if pk.algo == "wino4":
-        return hb.conv2d_ups_wino4 if ups else hb.conv2d_wino4
-    if pk.algo == "wino":
-        return hb.conv2d_ups_wino if ups else hb.conv2d_wino
-    return hb.conv2d_ups if ups else hb.conv2d
+    form = hb.FORMS[pk.algo]
+    assert ups or form.launch is not None, "the low-res GEMM form is for the fused-upsample layers"
+    return form.launch_ups if ups and form.launch_ups is not None else form.launch
 
 
 POOLED = ("conv1b", "conv2b", "conv3b", "conv4b", "conv5b")      # 2x2 mean fused into these convs
@@ -715,8 +702,7 @@ class RecurrentBottleneck:
             hb.conv2d_hl8(src_view, cin, None, 0, pk, None, dst_view, None, batch, self.h, self.w, lrelu=False,
                           fast=self.mode == "f16")
         else:
-            fn = hb.conv2d_wino if pk.algo == "wino" else hb.conv2d
-            fn(src_view, cin, None, 0, pk, dst_view, None, batch, self.h, self.w, lrelu=False)
+            conv_fn(pk)(src_view, cin, None, 0, pk, dst_view, None, batch, self.h, self.w, lrelu=False)
 
     def _hview(self, planes, ch, slot):
         """View of `hid` channels starting at channel ch of slot `slot` in the layout the convolutions read."""

@@ -437,13 +437,61 @@ class Planes:
         return out
 
 
+# ---- the fp32 convolution forms ------------------------------------------------------------------------------------------------------
+class Form:
+    """What one fp32 convolution form IS, for the code that treats the forms alike (engine's tables, PackBatch32, the timers).  When a
+    layer gets a form is decided elsewhere (engine.choose_algo, backward.py, perceptual.py).
+    name: the handle's `algo`; job: the form's id in ssm_pack32_weights_batch (None: not part of the one-launch repack); issued(k):
+    multiply-adds issued on the matrix cores per direct-form multiply-add; tile_floats: packed floats per (cout, cin) where
+    ssm_pack32_wino_tiles_batch can repack the form (None: it cannot), tile_bn: the cout block that kernel uses (None: the handle's bn);
+    plan(pk, B, H, W): (bn, ck) of a plain launch (no pooled output) of the handle pk over B x H x W - equal to (pk.bn, pk.ck) or the
+    filter has to be packed again.  Bound at the end of the section: cls (the packed-filter class), launch / launch_ups (the plain /
+    fused-upsample launcher, None: the form has none)."""
+
+    def __init__(self, name, job, issued, plan, tile_floats=None, tile_bn=None):
+        self.name, self.job, self.issued, self.plan, self.tile_floats, self.tile_bn = name, job, issued, plan, tile_floats, tile_bn
+        self.cls = self.launch = self.launch_ups = None
+
+
+FORMS = {f.name: f for f in (
+    Form("direct", 0, lambda k: 1.0, lambda pk, B, H, W: conv_plan(pk.k, pk.cin_p, pk.cout, B, H, W)[1:], tile_floats=9),
+    Form("wino", 1, lambda k: 16.0 / 36.0, lambda pk, B, H, W: wino_plan(pk.cin, pk.cout, B, H, W)[1:], tile_floats=16),
+    Form("wino4", 3, lambda k: 36.0 / 144.0, lambda pk, B, H, W: wino4_plan(pk.cin, pk.cout, B, H, W)[1:], tile_floats=36, tile_bn=32),
+    Form("wino1d", 2, lambda k: 8.0 / 14.0 if k == 7 else 8.0 / 20.0, lambda pk, B, H, W: wino1d_plan(pk.k, pk.cin_p, pk.cout, B, H, W)[1:]),
+    Form("wino5", 5, lambda k: 64.0 / 400.0, lambda pk, B, H, W: (32, 4)),
+    Form("wino7", 4, lambda k: 196.0 / 784.0, lambda pk, B, H, W: (32, 1)),
+    Form("upgemm", None, lambda k: 9.0 / 36.0, lambda pk, B, H, W: (128, 16)),
+)}
+
+
+class _PackedFilter:
+    """What the packed fp32 filters share; an explicit handle owned by the Python side (packed-weight caches are
+    created/destroyed by the caller).  Attributes: w, b (the packed tensors), cout, cin, k, cin_p (the channels a launch passes), bn, ck
+    (the tile configuration), ups, algo and form (its entry of FORMS)."""
+
+    def _shape(self, weight, bias, ups):
+        require_device(weight, "conv weight")
+        require_device(bias, "conv bias")
+        self.cout, self.cin, self.k = weight.shape[0], weight.shape[1], weight.shape[2]
+        self.ups = bool(ups)
+
+    def _fill(self, weight, bias, nw, nb, pack, *dims):
+        """Allocate w (nw floats) and b (nb floats) and fill them: pack(w, bias, w_packed, bias_packed, *dims, stream)."""
+        self.w = torch.empty(nw, dtype=torch.float32, device=weight.device)
+        self.b = torch.empty(nb, dtype=torch.float32, device=weight.device)
+        wc, bc = weight.detach().contiguous(), bias.detach().contiguous()
+        check(pack(wc.data_ptr(), bc.data_ptr(), self.w.data_ptr(), self.b.data_ptr(), *dims, stream_ptr()))
+
+
+def _plan(fn, *args):
+    kind, bn, ck = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(fn(*args, ctypes.byref(kind), ctypes.byref(bn), ctypes.byref(ck)))
+    return kind.value, bn.value, ck.value
+
+
 def conv_plan(k, cin, cout, B, H, W, pool=False, ups=False):
     """(kind, BN, CK) of the tile configuration ssm_conv2d_fwd / ssm_conv2d_ups_fwd will use for this problem."""
-    lib = load()
-    kind, bn, ck = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-    check(lib.ssm_conv_plan(k, cin, cout, B, H, W, 1 if pool else 0, 1 if ups else 0, ctypes.byref(kind), ctypes.byref(bn),
-                            ctypes.byref(ck)))
-    return kind.value, bn.value, ck.value
+    return _plan(load().ssm_conv_plan, k, cin, cout, B, H, W, 1 if pool else 0, 1 if ups else 0)
 
 
 def conv_config(k, cout, B, H, W, pool=False):
@@ -454,7 +502,7 @@ def conv_config(k, cout, B, H, W, pool=False):
     return bn.value, ck.value
 
 
-class PackedConv:
+class PackedConv(_PackedFilter):
     """Filter + bias of one convolution repacked for the tile configuration the
     library picks for the problem (k, Cout, batch, map size, fused pool).  An explicit
     handle owned by the Python side (packed-weight caches are
@@ -464,20 +512,12 @@ class PackedConv:
 
     def __init__(self, weight, bias, B, H, W, pool=False, ups=False):
         """B, H, W: batch and OUTPUT map of the launches this filter serves; ups: it feeds ssm_conv2d_ups_fwd."""
-        require_device(weight, "conv weight")
-        require_device(bias, "conv bias")
-        self.cout, self.cin, self.k = weight.shape[0], weight.shape[1], weight.shape[2]
-        self.ups = bool(ups)
+        self._shape(weight, bias, ups)
         _, self.bn, self.ck = conv_plan(self.k, self.cin, self.cout, B, H, W, pool, ups)
         self.cin_p = (self.cin + self.ck - 1) // self.ck * self.ck
         lib = load()
-        nw = lib.ssm_packed_weight_floats(self.cout, self.cin_p, self.k, self.bn)
-        nb = lib.ssm_packed_bias_floats(self.cout, self.bn)
-        self.w = torch.empty(nw, dtype=torch.float32, device=weight.device)
-        self.b = torch.empty(nb, dtype=torch.float32, device=weight.device)
-        wc, bc = weight.detach().contiguous(), bias.detach().contiguous()
-        check(lib.ssm_pack_weights(wc.data_ptr(), bc.data_ptr(), self.w.data_ptr(), self.b.data_ptr(), self.cout,
-                                   self.cin, self.cin_p, self.k, self.bn, stream_ptr()))
+        self._fill(weight, bias, lib.ssm_packed_weight_floats(self.cout, self.cin_p, self.k, self.bn), lib.ssm_packed_bias_floats(self.cout, self.bn),
+                   lib.ssm_pack_weights, self.cout, self.cin, self.cin_p, self.k, self.bn)
 
 
 def conv2d(x1, c1, x2, c2, pk, y, pool, B, H, W, lrelu=True, slope=0.1, add=None, add_div=1):
@@ -498,17 +538,8 @@ def conv2d(x1, c1, x2, c2, pk, y, pool, B, H, W, lrelu=True, slope=0.1, add=None
             cache[key] = ks.value
         ks = cache[key]
         if ks > 1:
-            st = stream_ptr()
-            scratch = pk.__dict__.setdefault("_splitk_part", {})
-            skey = (getattr(st, "value", st), ks, B, H, W)
-            if skey not in scratch:
-                scratch[skey] = Planes(ks * B, pk.cout, H, W, pk.w.device)
-            part = scratch[skey]
-            check(lib.ssm_conv2d_splitk_fwd(x1, c1, x2 if x2 is not None else NULL_VIEW, c2, pk.w.data_ptr(), pk.b.data_ptr(), part.view(), ks,
-                                            B, H, W, pk.cout, pk.k, st))
-            check(lib.ssm_splitk_finish_fwd(part.view(), ks, y, NULL_VIEW, add if add is not None else NULL_VIEW, add_div, B, pk.cout, H, W,
-                                            slope, SSM_FLAG_LRELU if lrelu else 0, st))
-            return
+            return _splitk_launch(lib.ssm_conv2d_splitk_fwd, (B, H, W, pk.cout, pk.k), x1, c1, None, 0, pk, y, None, add, add_div, ks, B, H, W,
+                                  SSM_FLAG_LRELU if lrelu else 0, slope)
     check(lib.ssm_conv2d_add_fwd(x1, c1, x2 if x2 is not None else NULL_VIEW, c2, pk.w.data_ptr(), pk.b.data_ptr(), y,
                                  pool if pool is not None else NULL_VIEW, add if add is not None else NULL_VIEW, add_div, B, H, W,
                                  pk.cout, pk.k, slope, SSM_FLAG_LRELU if lrelu else 0, stream_ptr()))
@@ -528,10 +559,7 @@ def conv2d_ups(a, c1, b, c2, pk, y, B, H, W, lrelu=True, slope=0.1, add=None, ad
 # ---- 3x3 convolution as Winograd F(2x2,3x3) in fp32 (csrc/ssm_wino.hip) ------------------------------------
 def wino_plan(cin, cout, B, H, W, ups=False):
     """(kind, BN, CK) of the Winograd tile configuration for the problem (ups: the fused-upsample entry point)."""
-    lib = load()
-    kind, bn, ck = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-    check(lib.ssm_wino_plan(cin, cout, B, H, W, 1 if ups else 0, ctypes.byref(kind), ctypes.byref(bn), ctypes.byref(ck)))
-    return kind.value, bn.value, ck.value
+    return _plan(load().ssm_wino_plan, cin, cout, B, H, W, 1 if ups else 0)
 
 
 def wino_supported(cin, cout, H, W, k=3):
@@ -539,29 +567,21 @@ def wino_supported(cin, cout, H, W, k=3):
     return k == 3 and cin % 8 == 0          # (any map size: odd widths since r6 - the epilogue stores a tile's lone last column by itself)
 
 
-class PackedWino:
+class PackedWino(_PackedFilter):
     """3x3 filter pre-transformed (U = G g G^T) and packed for the Winograd kernel's tile configuration; an explicit handle owned
     by the Python side like PackedConv."""
 
     algo = "wino"
 
     def __init__(self, weight, bias, B, H, W, pool=False, ups=False):
-        require_device(weight, "conv weight")
-        require_device(bias, "conv bias")
-        self.cout, self.cin, self.k = weight.shape[0], weight.shape[1], weight.shape[2]
+        self._shape(weight, bias, ups)
         assert self.k == 3 and weight.shape[3] == 3, "the Winograd form is for 3x3 filters"
-        self.ups = bool(ups)
         _, self.bn, self.ck = wino_plan(self.cin, self.cout, B, H, W, self.ups)
         assert self.cin % self.ck == 0, "Cin must be a multiple of %d" % self.ck
         self.cin_p = self.cin
         lib = load()
-        nw = lib.ssm_wino_packed_weight_floats(self.cout, self.cin, self.bn)
-        nb = lib.ssm_packed_bias_floats(self.cout, self.bn)
-        self.w = torch.empty(nw, dtype=torch.float32, device=weight.device)
-        self.b = torch.empty(nb, dtype=torch.float32, device=weight.device)
-        wc, bc = weight.detach().contiguous(), bias.detach().contiguous()
-        check(lib.ssm_wino_pack_weights(wc.data_ptr(), bc.data_ptr(), self.w.data_ptr(), self.b.data_ptr(), self.cout, self.cin,
-                                        self.bn, stream_ptr()))
+        self._fill(weight, bias, lib.ssm_wino_packed_weight_floats(self.cout, self.cin, self.bn), lib.ssm_packed_bias_floats(self.cout, self.bn),
+                   lib.ssm_wino_pack_weights, self.cout, self.cin, self.bn)
 
 
 def wino_splitk(pk, B, H, W, ups=False):
@@ -584,17 +604,18 @@ def _flags(lrelu, mask, add):
     return SSM_FLAG_LRELU if lrelu else 0
 
 
-def _splitk_launch(x1, c1, x2, c2, pk, y, pool, add, add_div, ks, ups, B, H, W, lrelu, slope, mask=False):
+def _splitk_launch(fwd, dims, x1, c1, x2, c2, pk, y, pool, add, add_div, ks, B, H, W, flags, slope):
+    """The split-K path of the direct and the F(2x2,3x3) form: fwd (the form's split entry point; dims: its arguments after KS) writes KS
+    partial sums per output, ssm_splitk_finish_fwd adds them and applies bias, addend, activation / mask and the fused 2x2 mean."""
     lib, st = load(), stream_ptr()
     scratch = pk.__dict__.setdefault("_splitk_part", {})          # the partial sums: one tensor per (stream, problem) - plans on other streams run beside this one
     key = (getattr(st, "value", st), ks, B, H, W)
     if key not in scratch:
         scratch[key] = Planes(ks * B, pk.cout, H, W, pk.w.device)
     part = scratch[key]
-    check(lib.ssm_wino_conv2d_splitk_fwd(x1, c1, x2 if x2 is not None else NULL_VIEW, c2, pk.w.data_ptr(), pk.b.data_ptr(), part.view(), ks,
-                                         1 if ups else 0, B, H, W, pk.cout, pk.bn, st))
+    check(fwd(x1, c1, x2 if x2 is not None else NULL_VIEW, c2, pk.w.data_ptr(), pk.b.data_ptr(), part.view(), ks, *dims, st))
     check(lib.ssm_splitk_finish_fwd(part.view(), ks, y, pool if pool is not None else NULL_VIEW, add if add is not None else NULL_VIEW, add_div,
-                                    B, pk.cout, H, W, slope, _flags(lrelu, mask, add), st))
+                                    B, pk.cout, H, W, slope, flags, st))
 
 
 def conv2d_wino(x1, c1, x2, c2, pk, y, pool, B, H, W, lrelu=True, slope=0.1, add=None, add_div=1, mask=False):
@@ -604,7 +625,8 @@ def conv2d_wino(x1, c1, x2, c2, pk, y, pool, B, H, W, lrelu=True, slope=0.1, add
     assert (pk.bn, pk.ck) == wino_plan(c1 + c2, pk.cout, B, H, W, False)[1:], "filter was packed for another tile configuration"
     ks = wino_splitk(pk, B, H, W, False)
     if ks > 1:
-        return _splitk_launch(x1, c1, x2, c2, pk, y, pool, add, add_div, ks, False, B, H, W, lrelu, slope, mask)
+        return _splitk_launch(lib.ssm_wino_conv2d_splitk_fwd, (0, B, H, W, pk.cout, pk.bn), x1, c1, x2, c2, pk, y, pool, add, add_div, ks, B, H, W,
+                              _flags(lrelu, mask, add), slope)
     check(lib.ssm_wino_conv2d_add_fwd(x1, c1, x2 if x2 is not None else NULL_VIEW, c2, pk.w.data_ptr(), pk.b.data_ptr(), y,
                                       pool if pool is not None else NULL_VIEW, add if add is not None else NULL_VIEW, add_div, B, H, W,
                                       pk.cout, slope, _flags(lrelu, mask, add), stream_ptr()))
@@ -617,7 +639,8 @@ def conv2d_ups_wino(a, c1, b, c2, pk, y, B, H, W, lrelu=True, slope=0.1, add=Non
     assert (pk.bn, pk.ck) == wino_plan(c1 + c2, pk.cout, B, H, W, True)[1:], "filter was packed for another tile configuration"
     ks = wino_splitk(pk, B, H, W, True)
     if ks > 1:
-        return _splitk_launch(a, c1, b, c2, pk, y, None, add, add_div, ks, True, B, H, W, lrelu, slope)
+        return _splitk_launch(lib.ssm_wino_conv2d_splitk_fwd, (1, B, H, W, pk.cout, pk.bn), a, c1, b, c2, pk, y, None, add, add_div, ks, B, H, W,
+                              SSM_FLAG_LRELU if lrelu else 0, slope)
     check(lib.ssm_wino_conv2d_ups_add_fwd(a, c1, b if b is not None else NULL_VIEW, c2, pk.w.data_ptr(), pk.b.data_ptr(), y,
                                           add if add is not None else NULL_VIEW, add_div, B, H, W, pk.cout, slope,
                                           SSM_FLAG_LRELU if lrelu else 0, stream_ptr()))
@@ -625,10 +648,7 @@ def conv2d_ups_wino(a, c1, b, c2, pk, y, B, H, W, lrelu=True, slope=0.1, add=Non
 
 # ---- 3x3 convolution as Winograd F(4x4,3x3) in fp32 (csrc/ssm_wino4.hip) -------------------------------------------------
 def wino4_plan(cin, cout, B, H, W, ups=False):
-    lib = load()
-    kind, bn, ck = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-    check(lib.ssm_wino4_plan(cin, cout, B, H, W, 1 if ups else 0, ctypes.byref(kind), ctypes.byref(bn), ctypes.byref(ck)))
-    return kind.value, bn.value, ck.value
+    return _plan(load().ssm_wino4_plan, cin, cout, B, H, W, 1 if ups else 0)
 
 
 def wino4_supported(cin, cout, H, W, k=3):
@@ -641,25 +661,19 @@ def wino4_preferred(cin, cout, B, H, W, ups=False):
     return bool(load().ssm_wino4_preferred(cin, cout, B, H, W, 1 if ups else 0))
 
 
-class PackedWino4:
+class PackedWino4(_PackedFilter):
     """3x3 filter pre-transformed for F(4x4,3x3) (U = G g G^T, 36 frequencies) and packed [Cout/32][Cin][9][32][4]; an explicit
     handle owned by the Python side like PackedConv."""
 
     algo = "wino4"
 
     def __init__(self, weight, bias, B, H, W, pool=False, ups=False):
-        require_device(weight, "conv weight")
-        require_device(bias, "conv bias")
-        self.cout, self.cin, self.k = weight.shape[0], weight.shape[1], weight.shape[2]
+        self._shape(weight, bias, ups)
         assert self.k == 3 and weight.shape[3] == 3, "F(4x4,3x3) is for 3x3 filters"
-        self.ups = bool(ups)
         _, self.bn, self.ck = wino4_plan(self.cin, self.cout, B, H, W, self.ups)
         self.cin_p = self.cin
         lib = load()
-        self.w = torch.empty(lib.ssm_wino4_packed_weight_floats(self.cout, self.cin), dtype=torch.float32, device=weight.device)
-        self.b = torch.empty(self.cout, dtype=torch.float32, device=weight.device)
-        wc, bc = weight.detach().contiguous(), bias.detach().contiguous()
-        check(lib.ssm_wino4_pack_weights(wc.data_ptr(), bc.data_ptr(), self.w.data_ptr(), self.b.data_ptr(), self.cout, self.cin, stream_ptr()))
+        self._fill(weight, bias, lib.ssm_wino4_packed_weight_floats(self.cout, self.cin), self.cout, lib.ssm_wino4_pack_weights, self.cout, self.cin)
 
 
 def conv2d_wino4(x1, c1, x2, c2, pk, y, pool, B, H, W, lrelu=True, slope=0.1, add=None, add_div=1, mask=False):
@@ -739,7 +753,7 @@ def upgemm_scratch_view(buf, cout, h, w):
     return SsmView(buf.data_ptr(), 9 * cout * h * wr, h * wr, wr)
 
 
-class PackedUpGemm:
+class PackedUpGemm(_PackedFilter):
     """3x3 filter of a fused-upsample layer as the A operand of the low-res GEMM Cin -> 9 Cout ([9 Cout / 128][Cin][128] slabs, row = tap Cout +
     cout) beside the layer's plain bias; an explicit handle owned by the Python side like PackedConv.  `scratch`: the fp32 tensor the GEMM's
     9 Cout-channel output goes through - a plan assigns one tensor to all its layers (they run in order on one stream); a handle used on its
@@ -748,13 +762,11 @@ class PackedUpGemm:
     algo = "upgemm"
 
     def __init__(self, weight, bias, B, H, W, pool=False, ups=True):
-        require_device(weight, "conv weight")
-        require_device(bias, "conv bias")
+        self._shape(weight, bias, True)
         assert ups and not pool, "the low-res GEMM form is for the fused-upsample layers"
-        self.cout, self.cin, self.k = weight.shape[0], weight.shape[1], weight.shape[2]
         if not upgemm_supported(self.cin, self.cout, H, W, self.k):
             raise RuntimeError("low-res GEMM form: unsupported layer (%d -> %d, k = %d, output %d x %d)" % (self.cin, self.cout, self.k, H, W))
-        self.ups, self.cin_p, self.bn, self.ck = True, self.cin, 128, 16
+        self.cin_p, self.bn, self.ck = self.cin, 128, 16
         lib = load()
         self.w = torch.empty(lib.ssm_upgemm_packed_weight_floats(self.cout, self.cin), dtype=torch.float32, device=weight.device)
         self.b = bias.detach().contiguous().clone()
@@ -781,10 +793,7 @@ def conv2d_ups_upgemm(a, c1, b, c2, pk, y, B, H, W, lrelu=True, slope=0.1, add=N
 # ---- 7x7 / 5x5 convolutions as 1-D Winograd along x, F(2,7) / F(4,5), in fp32 (csrc/ssm_wino1d.hip) -----------------
 def wino1d_plan(k, cin, cout, B, H, W):
     """(kind, BN, CK) of the 1-D Winograd tile configuration for the problem."""
-    lib = load()
-    kind, bn, ck = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-    check(lib.ssm_wino1d_plan(k, cin, cout, B, H, W, ctypes.byref(kind), ctypes.byref(bn), ctypes.byref(ck)))
-    return kind.value, bn.value, ck.value
+    return _plan(load().ssm_wino1d_plan, k, cin, cout, B, H, W)
 
 
 def wino1d_supported(cin, cout, H, W, k):
@@ -792,29 +801,21 @@ def wino1d_supported(cin, cout, H, W, k):
     return k in (5, 7) and cout % 32 == 0
 
 
-class PackedWino1d:
+class PackedWino1d(_PackedFilter):
     """7x7 / 5x5 filter with its rows pre-transformed (U[ky] = G g[ky]) and packed for the 1-D Winograd kernel's tile
     configuration; an explicit handle owned by the Python side like PackedConv."""
 
     algo = "wino1d"
 
     def __init__(self, weight, bias, B, H, W, pool=False, ups=False):
-        require_device(weight, "conv weight")
-        require_device(bias, "conv bias")
+        self._shape(weight, bias, False)
         assert not ups, "the 7x7 / 5x5 layers have no fused-upsample form"
-        self.cout, self.cin, self.k = weight.shape[0], weight.shape[1], weight.shape[2]
         assert self.k in (5, 7) and weight.shape[3] == self.k, "the 1-D Winograd form is for 7x7 and 5x5 filters"
-        self.ups = False
         _, self.bn, self.ck = wino1d_plan(self.k, self.cin, self.cout, B, H, W)
         self.cin_p = (self.cin + self.ck - 1) // self.ck * self.ck
         lib = load()
-        nw = lib.ssm_wino1d_packed_weight_floats(self.cout, self.cin_p, self.k, self.bn)
-        nb = lib.ssm_packed_bias_floats(self.cout, self.bn)
-        self.w = torch.empty(nw, dtype=torch.float32, device=weight.device)
-        self.b = torch.empty(nb, dtype=torch.float32, device=weight.device)
-        wc, bc = weight.detach().contiguous(), bias.detach().contiguous()
-        check(lib.ssm_wino1d_pack_weights(wc.data_ptr(), bc.data_ptr(), self.w.data_ptr(), self.b.data_ptr(), self.cout, self.cin,
-                                          self.cin_p, self.k, self.bn, stream_ptr()))
+        self._fill(weight, bias, lib.ssm_wino1d_packed_weight_floats(self.cout, self.cin_p, self.k, self.bn),
+                   lib.ssm_packed_bias_floats(self.cout, self.bn), lib.ssm_wino1d_pack_weights, self.cout, self.cin, self.cin_p, self.k, self.bn)
 
 
 def conv2d_wino1d(x1, c1, x2, c2, pk, y, pool, B, H, W, lrelu=True, slope=0.1, add=None, add_div=1):
@@ -834,27 +835,21 @@ def wino5_supported(cin, cout, H, W, k):
     return k == 5 and cout % 32 == 0
 
 
-class PackedWino5:
+class PackedWino5(_PackedFilter):
     """5x5 filter pre-transformed on both axes (U = G g G^T, 64 frequencies) and packed for csrc/ssm_wino5.hip; an explicit handle
     owned by the Python side like PackedConv."""
 
     algo = "wino5"
 
     def __init__(self, weight, bias, B, H, W, pool=False, ups=False):
-        require_device(weight, "conv weight")
-        require_device(bias, "conv bias")
+        self._shape(weight, bias, False)
         assert not ups, "the 5x5 layers have no fused-upsample form"
-        self.cout, self.cin, self.k = weight.shape[0], weight.shape[1], weight.shape[2]
         assert self.k == 5 and weight.shape[3] == 5 and self.cout % 32 == 0, "the F(4x4,5x5) form is for 5x5 filters, Cout a multiple of 32"
-        self.ups = False
         self.bn, self.ck = 32, 4
         self.cin_p = (self.cin + 3) // 4 * 4
         lib = load()
-        self.w = torch.empty(lib.ssm_wino5_packed_weight_floats(self.cout, self.cin_p), dtype=torch.float32, device=weight.device)
-        self.b = torch.empty(self.cout, dtype=torch.float32, device=weight.device)
-        wc, bc = weight.detach().contiguous(), bias.detach().contiguous()
-        check(lib.ssm_wino5_pack_weights(wc.data_ptr(), bc.data_ptr(), self.w.data_ptr(), self.b.data_ptr(), self.cout, self.cin, self.cin_p,
-                                         stream_ptr()))
+        self._fill(weight, bias, lib.ssm_wino5_packed_weight_floats(self.cout, self.cin_p), self.cout, lib.ssm_wino5_pack_weights,
+                   self.cout, self.cin, self.cin_p)
 
 
 def conv2d_wino5(x1, c1, x2, c2, pk, y, pool, B, H, W, lrelu=True, slope=0.1, add=None, add_div=1, mask=False):
@@ -873,27 +868,22 @@ def wino7_supported(cin, cout, H, W, k):
     return k == 7 and cout % 32 == 0
 
 
-class PackedWino7:
+class PackedWino7(_PackedFilter):
     """7x7 filter as four pre-transformed 4x4 blocks (U_b = G g_b G^T) packed for csrc/ssm_wino7.hip; an explicit handle owned by the
     Python side like PackedConv."""
 
     algo = "wino7"
 
     def __init__(self, weight, bias, B, H, W, pool=False, ups=False):
-        require_device(weight, "conv weight")
-        require_device(bias, "conv bias")
+        self._shape(weight, bias, False)
         assert not ups, "the 7x7 layers have no fused-upsample form"
-        self.cout, self.cin, self.k = weight.shape[0], weight.shape[1], weight.shape[2]
         assert self.k == 7 and weight.shape[3] == 7, "the blocked Winograd form is for 7x7 filters"
         # cout_p: the channels the convolution writes (whole 32-channel blocks; zeros beyond cout - the output view must hold them)
         self.cout_p = (self.cout + 31) // 32 * 32
-        self.ups = False
         self.bn, self.ck, self.cin_p = 32, 1, self.cin
         lib = load()
-        self.w = torch.empty(lib.ssm_wino7_packed_weight_floats(self.cout, self.cin), dtype=torch.float32, device=weight.device)
-        self.b = torch.empty(self.cout_p, dtype=torch.float32, device=weight.device)
-        wc, bc = weight.detach().contiguous(), bias.detach().contiguous()
-        check(lib.ssm_wino7_pack_weights(wc.data_ptr(), bc.data_ptr(), self.w.data_ptr(), self.b.data_ptr(), self.cout, self.cin, stream_ptr()))
+        self._fill(weight, bias, lib.ssm_wino7_packed_weight_floats(self.cout, self.cin), self.cout_p, lib.ssm_wino7_pack_weights,
+                   self.cout, self.cin)
 
 
 def conv2d_wino7(x1, c1, x2, c2, pk, y, pool, B, H, W, lrelu=True, slope=0.1, add=None, add_div=1):
@@ -904,6 +894,14 @@ def conv2d_wino7(x1, c1, x2, c2, pk, y, pool, B, H, W, lrelu=True, slope=0.1, ad
     check(lib.ssm_wino7_conv2d_add_fwd(x1, c1, pk.w.data_ptr(), pk.b.data_ptr(), y, pool if pool is not None else NULL_VIEW,
                                        add if add is not None else NULL_VIEW, add_div, B, H, W, pk.cout_p, slope,
                                        SSM_FLAG_LRELU if lrelu else 0, stream_ptr()))
+
+
+# the class and the launchers of every form (PackedSubpixelWino4 and its launcher are a composite of two F(4x4,3x3) filters, no form)
+for _cls, _plain, _ups in ((PackedConv, conv2d, conv2d_ups), (PackedWino, conv2d_wino, conv2d_ups_wino),
+                           (PackedWino4, conv2d_wino4, conv2d_ups_wino4), (PackedWino1d, conv2d_wino1d, None), (PackedWino5, conv2d_wino5, None),
+                           (PackedWino7, conv2d_wino7, None), (PackedUpGemm, None, conv2d_ups_upgemm)):
+    _cls.form = FORMS[_cls.algo]
+    _cls.form.cls, _cls.form.launch, _cls.form.launch_ups = _cls, _plain, _ups
 
 
 # ---- HL8 (fp16 hi/lo) tensors and the fp16-MFMA convolution ------------------------------------
@@ -1049,7 +1047,7 @@ class PackBatch32:
     transposed packs the data-gradient filter of the forward parameter (no torch flip / permute / copy).  The job table holds raw
     pointers: rebuild it when `PackBatch.key()` of the parameters changes."""
 
-    ALGO = {"direct": 0, "wino": 1, "wino1d": 2, "wino4": 3, "wino7": 4, "wino5": 5}
+    ALGO = {f.name: f.job for f in FORMS.values() if f.job is not None}
 
     def __init__(self, entries, device):
         # F(2x2,3x3), direct 3x3 and (r6) F(4x4,3x3) jobs with whole tiles go to the tiled kernel (ssm_pack32_wino_tiles_batch: contiguous reads and writes), the rest to
@@ -1092,11 +1090,11 @@ class PackBatch32:
     @staticmethod
     def _tile_bn(pk):
         """Cout block of a job of the tiled kernel: F(4x4,3x3) filters are packed in 32-cout blocks whatever tile configuration launches them."""
-        return 32 if getattr(pk, "algo", "direct") == "wino4" else pk.bn
+        return FORMS[getattr(pk, "algo", "direct")].tile_bn or pk.bn
 
     @classmethod
     def _tiled(cls, pk):
-        per = {"wino": 16, "direct": 9, "wino4": 36}.get(getattr(pk, "algo", "direct"))          # packed floats per (cout, cin)
+        per = FORMS[getattr(pk, "algo", "direct")].tile_floats          # packed floats per (cout, cin)
         if per is None or type(pk).__name__ == "PackedSubpixelWino4":
             return False
         bn = cls._tile_bn(pk)

@@ -13,7 +13,7 @@ import torch
 from . import hipbind as hb
 import os
 
-from .engine import conv_fn
+from .engine import conv_fn, issued_factor
 from .backward import transposed_filter
 from .weights import _hash_uniform
 
@@ -98,9 +98,7 @@ class VGGFeatures:
         if self.q8:
             return self.pk[idx]
         pk = self.pk[idx]
-        plan = (hb.wino_plan(pk.cin, pk.cout, nb, src.H, src.W) if pk.algo == "wino" else
-                hb.wino4_plan(pk.cin, pk.cout, nb, src.H, src.W) if pk.algo == "wino4" else hb.conv_plan(3, pk.cin_p, pk.cout, nb, src.H, src.W))
-        if plan[1:] == (pk.bn, pk.ck):
+        if pk.form.plan(pk, nb, src.H, src.W) == (pk.bn, pk.ck):
             return pk
         key = (idx, nb)
         if key not in self.pk_nb:
@@ -111,8 +109,7 @@ class VGGFeatures:
         tm = VGGFeatures.timer
         if tm is None:
             return None
-        algo = getattr(pk, "algo", "") if pk is not None else ""
-        issued = flops * (16.0 / 36.0 if algo == "wino" else 0.25 if algo == "wino4" else 1.0)      # F(2x2,3x3) / F(4x4,3x3) layers
+        issued = flops * (issued_factor(pk) if pk is not None else 1.0)
         e0, e1 = tm.span(fam, name, flops, issued=issued)
         e0.record()
         return e1
