@@ -43,7 +43,15 @@
  *  once stays valid.  The DIRECT-form kernels (ssm_conv2d_*, ssm_conv2d_hl8_*)
  *  read a tile's overshoot past the map unpredicated: their inputs must be
  *  readable for SSM_TAIL_SLACK_FLOATS past the last element; what is read
- *  there only feeds outputs that are not stored.  The Winograd-form kernels
+ *  there only feeds outputs that are not stored.  The weight-gradient kernels
+ *  (ssm_conv2d_wgrad*, every output of which sums over the whole map) read
+ *  dZ inside the image only and the activations inside their plane rows only
+ *  (rows -p .. H + p - 1 with p = (k - 1) / 2, columns -4 .. roundup4(W +
+ *  SSM_PADX) - 1: the zero frame and the row's round-up padding): a staging
+ *  step that reaches further - the last pixel group of a ragged row, which
+ *  would meet nothing but zeroed dZ, and 0 * NaN is NaN - stages zeros, so
+ *  nothing behind the last plane can reach a sum
+ *  (tests/test_hip_wgrad_exact.py poisons it).  The Winograd-form kernels
  *  (ssm_wino_*, ssm_wino1d_*, ssm_wino4_*, ssm_wino5_*, ssm_wino7_*) never read
  *  outside the padded plane: a tile's transform mixes its whole input patch
  *  into every output, so overshoot rows / 16-byte pieces are fetched from the

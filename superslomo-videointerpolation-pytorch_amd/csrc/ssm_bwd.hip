@@ -138,6 +138,10 @@ __global__ __launch_bounds__(256) void bias_grad_kernel(ssm_view dz, float *__re
 //   B operand (X): every lane owns one column = (channel, filter row, filter column) and reads the staged rows at its constant offset
 //     + the pixel: four ds_read_b32 with immediate offsets per group (the filter column shifts the alignment, so no wide read);
 //     columns past Cin*k*k read a zeroed row instead of being masked.
+//   Nothing outside the padded planes reaches a sum: dZ is read inside the image only (rows < H, float4 tails past W zeroed) and the
+//     activations inside their plane rows only (rows < H + PAD, columns < roundup4(W + SSM_PADX): zero frame and the row's round-up
+//     padding; what a step stages beyond is written as zeros), so the result does not depend on the memory behind the last plane
+//     (tests/test_hip_wgrad_exact.py poisons it).
 // Everything that depends only on the thread (which float4 of a tile it stages, where it lands in LDS, its validity) is computed ONCE:
 // the first version recomputed that index arithmetic every step - 5-11 vector instructions per MFMA on the training step's layers
 // (tools/pmc_wgrad.sh), and a vector instruction beside the fp32 MFMA costs ~3 matrix cycles (profiles/DESIGN_history_r1-r3.md 3.2g).  SEG x RR = 64x2,
@@ -203,7 +207,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(ssm_view x, ssm_view
         dzq[i] = ok ? (rr | ((4 * x4) << 8)) : -1;
         if (!(f < NDZ)) dzl[i] = -1;         // (a cout past Cout still gets its zeros written: the tile row exists)
     }
-    int xo[LX], xl[LX], xq[LX];              // the same for the activation rows; xq = ry, -1: nothing to load (zeros are written)
+    int xo[LX], xl[LX], xq[LX];              // the same for the activation rows; xq = ry + (4 x4 << 8), -1: nothing to load (zeros are written)
 #pragma unroll
     for (int i = 0; i < LX; ++i) {
         const int f = tid + 256 * i;
@@ -212,7 +216,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(ssm_view x, ssm_view
         const bool ok = f < NX && c_lo + c < Cin;
         xo[i] = (int)((long long)c * x.sc) + (ry - PAD) * x.sh + 4 * x4 - 4;
         xl[i] = f < NX ? (c * XR + ry) * RS + 4 * x4 : -1;
-        xq[i] = ok ? ry : -1;
+        xq[i] = ok ? (ry | ((4 * x4) << 8)) : -1;
     }
     const float *dzb0 = dz.ptr + (long long)co0 * dz.sc;
     const float *xb0 = x.ptr + (long long)c_lo * x.sc;
@@ -246,11 +250,17 @@ __global__ __launch_bounds__(256, 2) void wgrad_mfma_kernel(ssm_view x, ssm_view
             }
             pdz[i] = v;
         }
+        const int rlim = H + 2 * PAD - y;                                        // staged rows ry < rlim lie in the plane
+        const unsigned xlim = (unsigned)(((W + SSM_PADX + 3) & ~3) + 4 - xs) << 8;      // ... and float4s 4 x4 < xlim >> 8 in the row
 #pragma unroll
         for (int i = 0; i < LX; ++i) {
             f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            // rows / columns outside the image come from the padded-plane zero frame; columns past the frame only meet zeroed dZ
-            if (xq[i] >= 0 && y + xq[i] - PAD < H + PAD) v = *reinterpret_cast<const f32x4 *>(xb + xo[i]);
+            // Rows / columns outside the image come from the padded-plane zero frame.  Columns past the row (the last pixel group of a
+            // ragged row reaches column 8 * ngrp - 1 + PAD) only meet zeroed dZ, but 0 * NaN is NaN, and past the bottom frame row of the
+            // last plane they are the tail slack, which a caller may leave unzeroed: float4s that begin at roundup4(W + SSM_PADX) or beyond
+            // are not loaded (zeros are staged).  Whole float4s, so the loaded value is not touched before commit(): the floats of the
+            // last loaded one past W + SSM_PADX are the row's own round-up padding (sh >= roundup4(W + 2 SSM_PADX)), zero by the layout.
+            if ((unsigned)xq[i] < xlim && (xq[i] & 255) < rlim) v = *reinterpret_cast<const f32x4 *>(xb + xo[i]);
             px[i] = v;
         }
     };

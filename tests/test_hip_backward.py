@@ -28,13 +28,16 @@ def test_conv_backward(dev, k, cin, cout, B, H, W, act):
     from ssm_amd import backward as Bk
     from ssm_amd import hipbind as hb
     g = torch.Generator().manual_seed(k + cin + cout + H)
-    x = torch.randn(B, cin, H, W, generator=g, requires_grad=True)
-    w = (torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5).requires_grad_()
-    bias = (torch.randn(cout, generator=g) * 0.1).requires_grad_()
+    x = torch.randn(B, cin, H, W, generator=g)
+    w = torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5
+    bias = torch.randn(cout, generator=g) * 0.1
     r = torch.randn(B, cout, H, W, generator=g)
-    y = O.conv2d_lrelu(x, w, bias) if act else O.conv2d(x, w, bias)
-    (y * r).sum().backward()
-    yp = hb.Planes(B, cout, H, W, dev).load(y.detach().to(dev))
+    # the reference: float64 autograd on the fp32-drawn inputs, cast to fp32 (every bar below as before)
+    x64, w64, bias64 = (t.double().requires_grad_() for t in (x, w, bias))
+    y = O.conv2d_lrelu(x64, w64, bias64) if act else O.conv2d(x64, w64, bias64)
+    (y * r.double()).sum().backward()
+    want_dx, want_dw, want_db = x64.grad.float(), w64.grad.float(), bias64.grad.float()
+    yp = hb.Planes(B, cout, H, W, dev).load(y.detach().float().to(dev))
     dyp = hb.Planes(B, cout, H, W, dev).load(r.to(dev))
     # dZ with the channel count padded to the data-gradient conv's chunk size
     wt = Bk.transposed_filter(w).to(dev)
@@ -43,7 +46,7 @@ def test_conv_backward(dev, k, cin, cout, B, H, W, act):
     Bk.lrelu_bwd(dyp, None, yp, dzp.slice(0, cout), has_act=act)
     dx = torch.empty(B, cin, H, W, device=dev)
     hb.conv2d(dzp.view(), pk.cin_p, None, 0, pk, hb.view_of(dx), None, B, H, W, lrelu=False)
-    xp = hb.Planes(B, cin, H, W, dev).load(x.detach().to(dev))
+    xp = hb.Planes(B, cin, H, W, dev).load(x.to(dev))
     if cin >= 32:           # two-source form: the filter's input range filled by two calls
         h = cin // 2
         dw = torch.empty(cout, cin, k, k, device=dev)
@@ -52,14 +55,14 @@ def test_conv_backward(dev, k, cin, cout, B, H, W, act):
     else:
         dw = Bk.wgrad(xp, dzp.slice(0, cout), torch.empty(cout, cin, k, k, device=dev), k)
     db = Bk.bias_grad(dzp.slice(0, cout), torch.empty(cout, device=dev))
-    assert rel_err(dx.cpu(), x.grad) < 2e-4, "dX"
-    assert rel_err(dw.cpu(), w.grad) < 2e-4, "dW"
-    assert rel_err(db.cpu(), bias.grad) < 2e-4, "db"
+    assert rel_err(dx.cpu(), want_dx) < 2e-4, "dX"
+    assert rel_err(dw.cpu(), want_dw) < 2e-4, "dW"
+    assert rel_err(db.cpu(), want_db) < 2e-4, "db"
     # the bias gradient as one more column of the weight-gradient GEMM (ssm_conv2d_wgrad_bias), accumulating like the training step
     dw2, db2 = torch.zeros(cout, cin, k, k, device=dev), torch.full((cout,), 0.25, device=dev)
     Bk.wgrad(xp, dzp.slice(0, cout), dw2, k, zero_first=False, bias_acc=db2)
-    assert rel_err(dw2.cpu(), w.grad) < 2e-4, "dW (fused bias column)"
-    assert rel_err(db2.cpu() - 0.25, bias.grad) < 2e-4, "db (fused bias column)"
+    assert rel_err(dw2.cpu(), want_dw) < 2e-4, "dW (fused bias column)"
+    assert rel_err(db2.cpu() - 0.25, want_db) < 2e-4, "db (fused bias column)"
 
 
 @pytest.mark.parametrize("k,cin,cout,B,H,W,gscale", [
@@ -75,9 +78,10 @@ def test_wgrad_bf16x3(dev, k, cin, cout, B, H, W, gscale):
     from ssm_amd import hipbind as hb
     g = torch.Generator().manual_seed(k * 1000 + cin + cout + H + W)
     x = torch.randn(B, cin, H, W, generator=g)
-    w = (torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5).requires_grad_()
+    w = (torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5).double().requires_grad_()
     r = torch.randn(B, cout, H, W, generator=g) * gscale
-    (O.conv2d(x, w, torch.zeros(cout)) * r).sum().backward()
+    # the reference: float64 autograd on the fp32-drawn inputs, cast to fp32 (the bar as before)
+    (O.conv2d(x.double(), w, torch.zeros(cout, dtype=torch.float64)) * r.double()).sum().backward()
     xp = hb.Planes(B, cin, H, W, dev).load(x.to(dev))
     dzp = hb.Planes(B, cout, H, W, dev).load(r.to(dev))
     dw = torch.full((cout, cin, k, k), 7.0, device=dev)
@@ -87,7 +91,7 @@ def test_wgrad_bf16x3(dev, k, cin, cout, B, H, W, gscale):
         Bk.wgrad(xp.slice(h, cin - h), dzp, dw, k, ci_offset=h, zero_first=False, split=True)
     else:
         Bk.wgrad(xp, dzp, dw, k, split=True)
-    assert rel_err(dw.cpu(), w.grad) < 2e-4
+    assert rel_err(dw.cpu(), w.grad.float()) < 2e-4
 
 
 @pytest.mark.parametrize("algo,cin,cout,B,H,W", [("wino", 64, 32, 2, 44, 46), ("wino", 512, 512, 2, 22, 22), ("wino4", 64, 64, 2, 48, 80),

@@ -5,6 +5,8 @@ under torch.autograd in the dtype asked for: O.warp, O.flow_interp_inputs, O.syn
 take float64 tensors as they stand.  The recurrent cells are the formulas of O.convlstm_cell / O.convgru_cell without their
 convolutions (the kernels take the summed pre-activations).
 
+The last section serves tests/test_hip_wgrad_exact.py: integer-valued inputs and the weight gradient they give exactly.
+
 Inputs are always DRAWN in fp32 and cast up, so the kernel under test and the float64 reference see the same numbers.
 
 Tolerances (tests/test_hip_train_elementwise.py): err <= bar(e_ref) = max(8 * e_ref, 4 * 2**-24), where err is the largest
@@ -187,3 +189,24 @@ def grads(fn, inputs, cots, dtype):
     tot = sum((o * c.to(dtype)).sum() for o, c in zip(outs, cots) if c is not None)
     tot.backward()
     return tuple(o.detach() for o in outs), tuple(None if x is None else (x.grad if x.grad is not None else torch.zeros_like(x)) for x in xs)
+
+
+# ---- weight gradients in the exact-integer regime (tests/test_hip_wgrad_exact.py) ---------------------------------------------
+def int_tensor(shape, gen, lo=-3, hi=3):
+    """Integer-valued fp32 tensor, uniform on {lo, ..., hi}."""
+    return torch.randint(lo, hi + 1, shape, generator=gen).to(torch.float32)
+
+
+def conv_wgrad_exact(x, dz, k):
+    """(dW, db) of y = conv_kxk(x, w) + b under the upstream gradient dz: float64 CPU autograd of O.conv2d, cast to fp32.  Asserts
+    what makes the comparison a bit comparison: the float64 result consists of integers below 2**24, so fp32 holds it - and every
+    partial sum of it, in any order - exactly."""
+    cout, cin = dz.shape[1], x.shape[1]
+    w = torch.zeros(cout, cin, k, k, dtype=torch.float64, requires_grad=True)
+    b = torch.zeros(cout, dtype=torch.float64, requires_grad=True)
+    (O.conv2d(x.double(), w, b) * dz.double()).sum().backward()
+    for g in (w.grad, b.grad):
+        assert bool((g == g.round()).all()) and float(g.abs().max()) < 2.0 ** 24, "the reference left the exact-integer regime"
+    bound = 9.0 * x.shape[0] * x.shape[2] * x.shape[3]          # sum over pixels of |dz x|: every partial sum stays below it
+    assert bound < 2.0 ** 24 and float(x.abs().max()) <= 3 and float(dz.abs().max()) <= 3
+    return w.grad.float(), b.grad.float()
