@@ -503,6 +503,20 @@ int ssm_flowinterp_inputs_t_fwd(ssm_view img6, ssm_view flow4, const float *t, s
 int ssm_synthesize_fwd(ssm_view img6, ssm_view in16, ssm_view out5, const float *t, ssm_view y3,
                        ssm_view aux, int B, int H, int W, void *stream);
 
+/* Coarse-flow synthesis (beyond the reference's operator surface; an approximation of its output, not parity): the refined flows and
+ * the visibility map come from a pass at 1/s of the frame's size, the frame is synthesised at full size from the original pixels.
+ * img6 [B,6,H,W] full size (sb = 0: one pair for every entry), aux_lo [B,5,H/s,W/s] = Ft1(u,v) | Ft0(u,v) | V0 as ssm_synthesize_fwd
+ * writes its `aux`, t[B] on the device, y3 [B,3,H,W].  s is 2 or 4, H = s*h, W = s*w; anything else is refused.  Per pixel (y, x):
+ *   1. source position per axis as F.interpolate(scale_factor=s, mode="bilinear", align_corners=False):
+ *      sy = max(0, (y + 0.5) / s - 0.5), i0 = floor(sy), i1 = min(i0 + 1, h - 1), lambda = sy - i0 (exact in fp32 for s = 2, 4);
+ *   2. the five channels of aux_lo sampled bilinearly, columns first, then rows;
+ *   3. both flows times s (pixels of the full-size frame); v0 = the sample of channel 4, v1 = 1 - v0;
+ *   4. w0 = warp(I0, s*Ft0), w1 = warp(I1, s*Ft1) at full size: layers.warp (scripts/models/layers.py:100-119: normalise with
+ *      max(size-1,1), grid_sample(align_corners=True), zeros outside), the device function ssm_synthesize_fwd uses;
+ *   5. y = ((1-t)*v0*w0 + t*v1*w1) / ((1-t)*v0 + t*v1), grouped as scripts/models/flow_interpolation.py:420-427.
+ * One fp32 operation per step, no contraction.                                                                          */
+int ssm_synthesize_upscaled_fwd(ssm_view img6, ssm_view aux_lo, const float *t, ssm_view y3, int B, int H, int W, int s, void *stream);
+
 /* final_conv [+ synthesis]: Conv2d(32 -> NC, k3, pad 1, bias), no activation (scripts/models/flow_computation.py:145-153,
  * flow_interpolation.py:149-157), exact fp32: NC = 4 / 5 (the model's two filters) as v_fma_f32 chains in (cin, ky, kx) order,
  * every other NC (and $SSM_FINAL_VALU=0) on v_mfma_f32_4x4x1_16B_f32 (4 couts x 64 pixels per instruction).  x [B,32,H,W]

@@ -106,18 +106,11 @@ __global__ __launch_bounds__(256) void flowinterp_inputs_kernel(ssm_view img6, s
     vp(out16, b, 9, y)[x] = ft0v;
 }
 
-// extract_outputs + compute_output_image, scripts/models/flow_interpolation.py:374-429, for one pixel: o5 = the five
-// channels of stage 2's final_conv at (b, y, x).  Shared by synthesize_kernel and final_conv_kernel<.., SYNTH> so the
-// two paths round identically.
-__device__ __forceinline__ void synth_pixel(const ssm_view &img6, const ssm_view &in16, const float (&o5)[5], float t, const ssm_view &y3,
-                                            const ssm_view &aux, int b, int y, int x, int H, int W) {
+// compute_output_image, scripts/models/flow_interpolation.py:420-427, for one pixel: both frames warped by their flows (in pixels of
+// img6's own size) and blended by visibility.  One copy for synth_pixel and synthesize_upscaled_kernel: one rounding per step, this order.
+__device__ __forceinline__ void blend_pixel(const ssm_view &img6, float ft0u, float ft0v, float ft1u, float ft1v, float v0, float v1, float t,
+                                            const ssm_view &y3, int b, int y, int x, int H, int W) {
     const float omt = 1.0f - t;
-    const float v1 = 1.0f / (1.0f + expf(-o5[0]));
-    const float v0 = 1.0f - v1;
-    const float ft1u = vp(in16, b, 6, y)[x] + o5[1];
-    const float ft1v = vp(in16, b, 7, y)[x] + o5[2];
-    const float ft0u = vp(in16, b, 8, y)[x] + o5[3];
-    const float ft0v = vp(in16, b, 9, y)[x] + o5[4];
     const Taps t0 = make_taps(x, y, ft0u, ft0v, H, W, img6.sh);
     const Taps t1 = make_taps(x, y, ft1u, ft1v, H, W, img6.sh);
     const float den = omt * v0 + t * v1;
@@ -127,6 +120,20 @@ __device__ __forceinline__ void synth_pixel(const ssm_view &img6, const ssm_view
         const float p1 = v1 * sample(vp(img6, b, 3 + c, 0), t1);
         vp(y3, b, c, y)[x] = (omt * p0 + t * p1) / den;
     }
+}
+
+// extract_outputs + compute_output_image, scripts/models/flow_interpolation.py:374-429, for one pixel: o5 = the five
+// channels of stage 2's final_conv at (b, y, x).  Shared by synthesize_kernel and final_conv_kernel<.., SYNTH> so the
+// two paths round identically.
+__device__ __forceinline__ void synth_pixel(const ssm_view &img6, const ssm_view &in16, const float (&o5)[5], float t, const ssm_view &y3,
+                                            const ssm_view &aux, int b, int y, int x, int H, int W) {
+    const float v1 = 1.0f / (1.0f + expf(-o5[0]));
+    const float v0 = 1.0f - v1;
+    const float ft1u = vp(in16, b, 6, y)[x] + o5[1];
+    const float ft1v = vp(in16, b, 7, y)[x] + o5[2];
+    const float ft0u = vp(in16, b, 8, y)[x] + o5[3];
+    const float ft0v = vp(in16, b, 9, y)[x] + o5[4];
+    blend_pixel(img6, ft0u, ft0v, ft1u, ft1v, v0, v1, t, y3, b, y, x, H, W);
     if (aux.ptr) {
         vp(aux, b, 0, y)[x] = ft1u;
         vp(aux, b, 1, y)[x] = ft1v;
@@ -143,6 +150,48 @@ __global__ __launch_bounds__(256) void synthesize_kernel(ssm_view img6, ssm_view
 #pragma unroll
     for (int c = 0; c < 5; ++c) o5[c] = vp(out5, b, c, y)[x];
     synth_pixel(img6, in16, o5, tarr[b], y3, aux, b, y, x, H, W);
+}
+
+// ---- coarse-flow synthesis: maps at 1/S of the frame's size (include/ssm_hip.h, ssm_synthesize_upscaled_fwd) -------------------------
+// Source taps of output index o on an axis of n source samples, the half-pixel rule of F.interpolate(scale_factor=S, mode="bilinear",
+// align_corners=False): position max(0, (o + 0.5) / S - 0.5), upper index clamped at n - 1.  S is 2 or 4: every step is exact in fp32
+// and the weights are multiples of 1/8 (ssm_amd/coarse.py upscale_taps spells the same rule on the host).
+struct UpTap {
+    int i0, i1;
+    float l0, l1;      // weights of i0, i1
+};
+
+template <int S>
+__device__ __forceinline__ UpTap up_tap(int o, int n) {
+    const float pos = fmaxf(((float)o + 0.5f) / (float)S - 0.5f, 0.0f);
+    const float f = floorf(pos);
+    UpTap t;
+    t.i0 = (int)f;
+    t.i1 = t.i0 + 1 < n ? t.i0 + 1 : n - 1;
+    t.l1 = pos - f;
+    t.l0 = 1.0f - t.l1;
+    return t;
+}
+
+// One lane = one full-size pixel: the five map channels (Ft1 | Ft0 | V0 at H/S x W/S) sampled bilinearly, columns first and then rows,
+// the flows scaled to full-size pixels, then blend_pixel on the full-size frames.  The maps are left to the caches: S neighbouring lanes
+// read the same addresses, a 64x4 block touches (64/S + 2) x (4/S + 2) x 5 floats (2.7 KB at S = 2) that S*S - 1 of S*S blocks find in
+// L2 already; the frame gathers (24 B/px) and the stores (12 B/px) carry the kernel.
+template <int S>
+__global__ __launch_bounds__(256) void synthesize_upscaled_kernel(ssm_view img6, ssm_view aux, const float *__restrict__ tarr, ssm_view y3,
+                                                                  int H, int W) {
+    SSM_PIXEL_INDEX();
+    const UpTap ty = up_tap<S>(y, H / S), tx = up_tap<S>(x, W / S);
+    float m[5];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+        const float *r0 = vp(aux, b, c, ty.i0), *r1 = vp(aux, b, c, ty.i1);
+        const float top = tx.l0 * r0[tx.i0] + tx.l1 * r0[tx.i1];
+        const float bot = tx.l0 * r1[tx.i0] + tx.l1 * r1[tx.i1];
+        m[c] = ty.l0 * top + ty.l1 * bot;
+    }
+    const float sc = (float)S;
+    blend_pixel(img6, sc * m[2], sc * m[3], sc * m[0], sc * m[1], m[4], 1.0f - m[4], tarr[b], y3, b, y, x, H, W);
 }
 
 // ---- final_conv (32 -> 4 or 5 channels, no activation) [+ synthesis] ------------------------------------------------
@@ -808,6 +857,22 @@ extern "C" int ssm_synthesize_fwd(ssm_view img6, ssm_view in16, ssm_view out5, c
     SSM_REQUIRE((long long)H * img6.sh < 0x7fffffffLL, "synthesize: plane too large");
     SSM_LAUNCH(synthesize_kernel, pix_grid(B, H, W), dim3(64, 4), 0, (hipStream_t)stream, img6, in16, out5, t, y3, aux, H, W);
     return ssm::check_launch("ssm_synthesize_fwd");
+}
+
+extern "C" int ssm_synthesize_upscaled_fwd(ssm_view img6, ssm_view aux_lo, const float *t, ssm_view y3, int B, int H, int W, int s, void *stream) {
+    SSM_CHECK_DIMS("synthesize_upscaled");
+    SSM_REQUIRE(s == 2 || s == 4, "synthesize_upscaled: s must be 2 or 4 (got %d)", s);
+    SSM_REQUIRE(H % s == 0 && W % s == 0, "synthesize_upscaled: H and W must be multiples of s (got %dx%d, s=%d)", H, W, s);
+    SSM_REQUIRE(img6.ptr, "synthesize_upscaled: img6 is a null view");
+    SSM_REQUIRE(aux_lo.ptr, "synthesize_upscaled: aux_lo is a null view");
+    SSM_REQUIRE(y3.ptr, "synthesize_upscaled: y3 is a null view");
+    SSM_REQUIRE(t, "synthesize_upscaled: t is a null pointer");
+    SSM_REQUIRE((long long)H * img6.sh < 0x7fffffffLL, "synthesize_upscaled: img6 plane too large");
+    if (s == 2)
+        SSM_LAUNCH(synthesize_upscaled_kernel<2>, pix_grid(B, H, W), dim3(64, 4), 0, (hipStream_t)stream, img6, aux_lo, t, y3, H, W);
+    else
+        SSM_LAUNCH(synthesize_upscaled_kernel<4>, pix_grid(B, H, W), dim3(64, 4), 0, (hipStream_t)stream, img6, aux_lo, t, y3, H, W);
+    return ssm::check_launch("ssm_synthesize_upscaled_fwd");
 }
 
 extern "C" int ssm_final_conv_fwd(ssm_view x, const float *w_oihw, const float *bias, int NC, ssm_view out, ssm_view img6, ssm_view in16,

@@ -11,7 +11,8 @@ input frames.  Y4M is the container every player and ffmpeg read and write witho
 Memory does not grow with the clip (scripts/visualize_interpolation.py, the PNG tool, holds the whole clip on the GPU).  Input frames
 pass to the output as their own bytes.  The output's frame rate is the input's times upsample_rate - the same duration, smoother - or,
 with --slowmo, the input's: the same frames played upsample_rate times slower.  8-bit 4:2:0 (both sitings) and 4:4:4 only; N_FRAMES must
-be 2, as for the PNG tool.
+be 2, as for the PNG tool.  --flow_scale 2|4 runs the two U-Nets at 1/2 or 1/4 of the frame size and synthesises at full size (the frame is
+then padded to x64 / x128): several times faster on UHD material, an approximation of the default output, not parity with the reference.
 """
 import argparse
 import configparser
@@ -43,6 +44,9 @@ def getargs(argv=None):
     parser.add_argument("--range", choices=sorted(V.RANGES), default=None, dest="color_range",
                         help="Code range (default: the header's XCOLORRANGE tag, else limited).")
     parser.add_argument("--slowmo", action="store_true", help="Keep the input's frame rate in the output header: slow motion.")
+    parser.add_argument("--flow_scale", type=int, choices=(1, 2, 4), default=1,
+                        help="Coarse-flow mode: run both U-Nets at 1/flow_scale of the frame size and synthesise at full size (faster on HD and "
+                             "UHD material; an approximation of the default output, not parity). Default 1: off.")
     return parser.parse_args(argv)
 
 
@@ -55,7 +59,7 @@ def main(argv=None, model=None):
     matrix = None if args.matrix is None else V.MATRICES[args.matrix]
     crange = None if args.color_range is None else V.RANGES[args.color_range]
     model = (model if model is not None else ssm.FullModel(config)).cuda().eval()
-    vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate, matrix=matrix, color_range=crange)
+    vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate, matrix=matrix, color_range=crange, flow_scale=args.flow_scale)
     with V.Y4MReader(args.input) as reader:
         rate = V.output_rate(reader.rate, args.upsample_rate, args.slowmo)
         out_range = crange if crange is not None else (reader.color_range if reader.color_range is not None else V.LIMITED)

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from ssm_amd import hipbind as hb
+from ssm_amd.coarse import check_scale
 from ssm_amd.engine import PairEngine, WindowEngine
 
 # Arithmetic of the convolutions on the planned path (ssm_amd.engine.MODES).  "f32w" (default) and "f32" are fp32 throughout
@@ -215,14 +216,41 @@ class FullModel(nn.Module):
         eng = self.window_engine_for(T, 1, t.numel(), frames.shape[3], frames.shape[4], frames.device)
         return eng.run(frames.contiguous(), t[:, None].expand(-1, T), want_aux=False).clone()
 
+    def _flow_scale(self, flow_scale):
+        """flow_scale of interpolate() / interpolate_many(): 1, 2 or 4; the coarse-flow mode is for the CONV bottleneck only."""
+        s = check_scale(flow_scale)
+        if s != 1 and self.recurrent:
+            raise NotImplementedError("flow_scale=%d is not available with a recurrent bottleneck (%s / %s): the coarse-flow mode "
+                                      "covers the CONV bottleneck only" % ((s,) + tuple(self.bottlenecks)))
+        return s
+
+    def coarse_engine_for(self, P, n_t, H, W, device, flow_scale):
+        """The CoarseFlowEngine of interpolate(..., flow_scale=2|4), cached like engine_for's plan (and in its place)."""
+        from ssm_amd.engine import CoarseFlowEngine
+        mode = self.precision or os.environ.get("SSM_PRECISION", DEFAULT_PRECISION)
+        key = ("coarse", flow_scale, P, n_t, H, W, str(device), mode, self._stamp())
+        if self._engine is None or self._engine[0] != key:
+            sd1 = {k: v.detach() for k, v in self.stage1_model.state_dict().items()}
+            sd2 = {k: v.detach() for k, v in self.stage2_model.state_dict().items()}
+            self._engine = None
+            self._engine = (key, CoarseFlowEngine(sd1, sd2, P, n_t, H, W, device, flow_scale, self.cross_skip, mode))
+        return self._engine[1]
+
     @torch.no_grad()
-    def interpolate(self, image_pair, t_values):
+    def interpolate(self, image_pair, t_values, flow_scale=1):
         """One pair [1,2,3,H,W] (or [1,6,H,W]) -> [len(t_values),3,H,W]: stage 1 once, every t
-        batched through stage 2 (the loop of evaluate_interpolation_results.py:213-244, hoisted)."""
+        batched through stage 2 (the loop of evaluate_interpolation_results.py:213-244, hoisted).
+        flow_scale = 2 or 4 (opt-in, beyond the reference; an approximation of its output, not parity): both U-Nets run on the
+        pair averaged down to 1/flow_scale of its size and the frames are synthesised at full size from the original pixels
+        (ssm_amd.engine.CoarseFlowEngine); H and W must then be multiples of 32 * flow_scale."""
         hb.require_device(image_pair, "image pair")
+        s = self._flow_scale(flow_scale)
         img6 = image_pair.reshape(image_pair.shape[0], 6, *image_pair.shape[-2:])
         assert img6.shape[0] == 1, "interpolate() takes one frame pair"
         t = _t_vector(t_values, img6.device)
+        if s != 1:
+            eng = self.coarse_engine_for(1, t.numel(), img6.shape[2], img6.shape[3], img6.device, s)
+            return eng.run(img6, t, want_aux=False).clone()
         eng = self.engine_for(1, t.numel(), img6.shape[2], img6.shape[3], img6.device)
         return eng.run(img6, t, want_aux=False).clone()
 
@@ -256,27 +284,28 @@ class FullModel(nn.Module):
         return out if want_planes else out.to_nchw()
 
     @torch.no_grad()
-    def interpolate_many(self, pairs, t_values, n_streams=2, pairs_per_batch=1):
+    def interpolate_many(self, pairs, t_values, n_streams=2, pairs_per_batch=1, flow_scale=1):
         """Throughput form of interpolate(): a list of pairs ([1,2,3,H,W] each, same size) -> list of
         [len(t_values),3,H,W] tensors.  Passes of `pairs_per_batch` pairs are dealt round-robin to `n_streams` engines on
         separate HIP streams (ssm_amd.engine.PairPipeline) so under-filled and tail phases of one pass overlap the
         MFMA-bound convolutions of another; pairs_per_batch > 1 also gives every convolution launch that many times the
         workgroups (bench.py's configuration: 3 streams x 2 pairs).  A remainder that does not fill a pass goes through
-        the one-pair engine."""
+        the one-pair engine.  flow_scale: as interpolate()."""
         from ssm_amd.engine import PairPipeline
         first = pairs[0]
         hb.require_device(first, "image pair")
+        s = self._flow_scale(flow_scale)
         H, W = first.shape[-2:]
         t = _t_vector(t_values, first.device)
         P = max(1, int(pairs_per_batch))
         mode = self.precision or os.environ.get("SSM_PRECISION", DEFAULT_PRECISION)
-        key = ("pipe", n_streams, P, t.numel(), H, W, str(first.device), mode, self._stamp())
+        key = ("pipe", n_streams, P, t.numel(), H, W, str(first.device), mode, s, self._stamp())
         if getattr(self, "_pipe", None) is None or self._pipe[0] != key:
             sd1 = {k: v.detach() for k, v in self.stage1_model.state_dict().items()}
             sd2 = {k: v.detach() for k, v in self.stage2_model.state_dict().items()}
             self._pipe = None
             self._pipe = (key, PairPipeline(sd1, sd2, t.numel(), H, W, first.device, self.cross_skip, mode, n_streams,
-                                            pairs_per_batch=P))
+                                            pairs_per_batch=P, flow_scale=s))
         pipe = self._pipe[1]
         full = len(pairs) // P * P
         outs = []
@@ -286,7 +315,7 @@ class FullModel(nn.Module):
         pipe.sync()
         res = [o for out in outs for o in (out.split(t.numel()) if P > 1 else (out,))]
         for pr in pairs[full:]:
-            res.append(self.interpolate(pr, t_values).clone())
+            res.append(self.interpolate(pr, t_values, flow_scale=s).clone())
         return res
 
     # ---- training step ------------------------------------------------------------------------------------------

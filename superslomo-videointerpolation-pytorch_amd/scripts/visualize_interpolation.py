@@ -49,6 +49,9 @@ def getargs(argv=None):
     parser.add_argument("--output_dir", required=True, help="Directory to output.")
     parser.add_argument("--flow_png", action="store_true",
                         help="With --show_intermediate_outputs: also save the flows as Middlebury colour-wheel PNGs.")
+    parser.add_argument("--flow_scale", type=int, choices=(1, 2, 4), default=1,
+                        help="Coarse-flow mode: run both U-Nets at 1/flow_scale of the frame size and synthesise at full size (an approximation "
+                             "of the default output, not parity). Not with --show_intermediate_outputs. Default 1: off.")
     return parser.parse_args(argv)
 
 
@@ -60,6 +63,10 @@ class Interpolator:
             raise NotImplementedError("N_FRAMES=%d needs the recurrent bottleneck (unpinned upstream); use N_FRAMES=2"
                                       % self.n_frames)
         self.model = (model if model is not None else ssm.FullModel(cfg)).cuda().eval()
+        self.flow_scale = int(getattr(args, "flow_scale", 1))
+        if self.flow_scale != 1 and args.show_intermediate_outputs:
+            raise NotImplementedError("--flow_scale %d with --show_intermediate_outputs: the intermediates are those of the default mode "
+                                      "(flow_scale 1)" % self.flow_scale)
         base = os.path.join(args.output_dir, args.expt)
         self.img_dir = os.path.join(base, "images")
         self.visibility_dir = os.path.join(base, "visibility_map")
@@ -102,7 +109,7 @@ class Interpolator:
         frames = self.load_frames([paths[i] for i in used]).cuda()
         pos = {i: k for k, i in enumerate(used)}
         h, w = frames.shape[1:3]
-        x = F.frames_from_u8(frames, self.cfg, pad_before_norm=True)       # visualiser convention (:76-87,:137)
+        x = F.frames_from_u8(frames, self.cfg, pad_before_norm=True, multiple=32 * self.flow_scale)       # visualiser convention (:76-87,:137)
         ts = E.t_values(a.upsample_rate)
         count = 0
         pairs = [torch.stack([x[pos[w0]], x[pos[w1]]])[None] for w0, w1 in windows]
@@ -115,7 +122,7 @@ class Interpolator:
                     per_t.append((img, inter))
                 outs.append(per_t)
         else:
-            outs = self.model.interpolate_many(pairs, ts)
+            outs = self.model.interpolate_many(pairs, ts, flow_scale=self.flow_scale)
         frames_cpu = frames.cpu().numpy()
         for k, (w0, w1) in enumerate(windows):
             self.save(frames_cpu[pos[w0]], count, self.img_dir)

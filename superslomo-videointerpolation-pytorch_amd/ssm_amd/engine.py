@@ -908,6 +908,57 @@ class PairEngine:
         return (flow[:, 0:2], flow[:, 2:4], e1, e0, self.aux[:, 0:2], self.aux[:, 2:4], self.aux[:, 4:5])
 
 
+class CoarseFlowEngine:
+    """Coarse-flow mode (an approximation of the reference's output, not parity): P pairs [P,6,H,W] are averaged down to
+    (H/s, W/s) (layers.avg_pool(2), log2(s) times), a plain PairEngine runs both U-Nets there at n_t times per pair, and
+    ssm_synthesize_upscaled_fwd synthesises the P * n_t frames at full size from the original pixels and that pass's refined flows
+    and visibility (its `aux`).  run() and intermediates() keep PairEngine's contracts, so a PairPipeline holds either kind; the
+    intermediates are the low-resolution pass's own, at (H/s, W/s) and in its pixels."""
+
+    def __init__(self, sd1, sd2, P, n_t, H, W, device, scale=2, cross_skip=True, mode="f32"):
+        from .coarse import check_scale, size_rule
+        self.s = check_scale(scale)
+        assert self.s != 1, "flow_scale=1 is the plain PairEngine, not a case of CoarseFlowEngine"
+        h, w = size_rule(H, W, self.s)
+        self.P, self.G, self.H, self.W, self.h, self.w, self.device = P, n_t, H, W, h, w, device
+        self.lo = PairEngine(sd1, sd2, P, P * n_t, h, w, device, cross_skip, mode)
+        # the downsampled pairs: [P,6,H/2,W/2] and, for s = 4, [P,6,H/4,W/4]
+        self.down = [torch.empty(P, 6, H >> (i + 1), W >> (i + 1), dtype=torch.float32, device=device) for i in range(self.s.bit_length() - 1)]
+        self.img = torch.empty(P * n_t, 3, H, W, dtype=torch.float32, device=device)
+        self.img6 = None
+
+    def run(self, img6, t, want_aux=False):
+        """img6 [P,6,H,W] device tensor (read in place), t as PairEngine.run_stage2 takes it.  Returns the engine's own [P*n_t,3,H,W]
+        output, pair-major.  The low-resolution pass always writes its aux (the synthesis reads it); want_aux is accepted for the
+        contract's sake."""
+        assert tuple(img6.shape) == (self.P, 6, self.H, self.W), "image pair tensor has shape %s" % (tuple(img6.shape),)
+        lib = hb.load()
+        st = hb.stream_ptr()
+        self.img6 = src = img6 if img6.stride(3) == 1 else img6.contiguous()
+        for d in self.down:
+            hb.check(lib.ssm_avgpool2_fwd(hb.view_of(src), hb.view_of(d), self.P, 6, src.shape[2], src.shape[3], st))
+            src = d
+        self.lo.run(src, t, want_aux=True)
+        tm = UNetPlan.timer
+        if tm is not None:   # write 3 ch, gather 6 ch of the frames, read 5 ch of the maps at 1/s^2 of the pixels
+            e0, e1 = tm.span("warp", "synthesize_upscaled", nbytes=(36.0 + 20.0 / (self.s * self.s)) * self.P * self.G * self.H * self.W)
+            e0.record()
+        tptr = self.lo.t_dev.data_ptr()
+        G = self.G
+        for p in range(self.P):      # one launch per pair: its frames are batch-broadcast over the pair's n_t entries
+            i6 = hb.view_of(self.img6[p:p + 1])
+            i6.sb = 0
+            hb.check(lib.ssm_synthesize_upscaled_fwd(i6, hb.view_of(self.lo.aux[p * G:]), tptr + 4 * p * G, hb.view_of(self.img[p * G:]),
+                                                     G, self.H, self.W, self.s, st))
+        if tm is not None:
+            e1.record()
+        return self.img
+
+    def intermediates(self):
+        """PairEngine.intermediates() of the low-resolution pass: (F01, F10, Ft1^, Ft0^, Ft1, Ft0, V0) at (H/s, W/s)."""
+        return self.lo.intermediates()
+
+
 class WindowEngine:
     """N_FRAMES-1 = T interpolation windows whose U-Nets are coupled by a recurrent bottleneck
     (BASELINE config 4; scripts/models/superslomo_r.py:152-293 with BOTTLENECK=CLSTM|CGRU).
@@ -1016,11 +1067,21 @@ class PairPipeline:
     MFMA-bound convolutions use the idle matrix cores / CUs.  Each engine owns its activations; the input
     pair is read in place.  Results of `submit` stay valid until that slot is reused (N pairs later)."""
 
-    def __init__(self, sd1, sd2, n_t, H, W, device, cross_skip=True, mode="f32", n_streams=2, graphs=False, pairs_per_batch=1):
+    def __init__(self, sd1, sd2, n_t, H, W, device, cross_skip=True, mode="f32", n_streams=2, graphs=False, pairs_per_batch=1,
+                 flow_scale=1):
         """pairs_per_batch = P: every submit() takes P pairs [P,6,H,W] through one PairEngine pass (stage 1 at batch P,
-        stage 2 at batch P * n_t) and returns [P * n_t,3,H,W], pair-major."""
+        stage 2 at batch P * n_t) and returns [P * n_t,3,H,W], pair-major.  flow_scale = 2 or 4: the engines are
+        CoarseFlowEngines (U-Nets at 1/flow_scale of the size, synthesis at full size)."""
+        from .coarse import check_scale
         self.P = P = int(pairs_per_batch)
-        self.engines = [PairEngine(sd1, sd2, P, P * n_t, H, W, device, cross_skip, mode) for _ in range(n_streams)]
+        self.flow_scale = check_scale(flow_scale)
+        if self.flow_scale == 1:
+            self.engines = [PairEngine(sd1, sd2, P, P * n_t, H, W, device, cross_skip, mode) for _ in range(n_streams)]
+        else:
+            if graphs:
+                raise NotImplementedError("PairPipeline(graphs=True) does not cover flow_scale=%d: the HIP-graph option is for flow_scale=1"
+                                          % self.flow_scale)
+            self.engines = [CoarseFlowEngine(sd1, sd2, P, n_t, H, W, device, self.flow_scale, cross_skip, mode) for _ in range(n_streams)]
         self.streams = [torch.cuda.Stream(device=device) for _ in range(n_streams)]
         self.n = n_streams
         self._i = 0

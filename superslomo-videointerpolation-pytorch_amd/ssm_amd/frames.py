@@ -34,15 +34,16 @@ def padded_dims(h, w, multiple=32):
     return (hp, wp), ((hp - h) // 2, (wp - w) // 2)
 
 
-def frames_from_u8(frames_u8, cfg=None, pad_before_norm=False):
-    """[N,H,W,3] uint8 RGB device tensor -> [N,3,Hp,Wp] normalised fp32, zero-padded to a multiple of 32.
+def frames_from_u8(frames_u8, cfg=None, pad_before_norm=False, multiple=32):
+    """[N,H,W,3] uint8 RGB device tensor -> [N,3,Hp,Wp] normalised fp32, zero-padded to a multiple of 32 (`multiple`: 32 * flow_scale
+    for the coarse-flow mode).
     pad_before_norm=False: dataloader convention (pad value 0 in normalised space);
     True: visualiser convention (black pixels padded before normalisation)."""
     assert frames_u8.is_cuda and frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[3] == 3, \
         "frames must be a [N,H,W,3] uint8 tensor on the GPU"
     f = frames_u8.contiguous()
     n, h, w, _ = f.shape
-    (hp, wp), (top, left) = padded_dims(h, w)
+    (hp, wp), (top, left) = padded_dims(h, w, multiple)
     mean, std = cfg_mean_std(cfg)
     out = torch.empty(n, 3, hp, wp, dtype=torch.float32, device=f.device)
     hb.check(hb.load().ssm_frames_from_u8_fwd(f.data_ptr(), hb.view_of(out), n, h, w, hp, wp, top, left, _f3(mean), _f3(std),

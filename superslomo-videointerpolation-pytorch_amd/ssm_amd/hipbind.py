@@ -209,6 +209,7 @@ SIGNATURES = {
     "ssm_final_conv_fwd": (_c_int, [SsmView, _vp, _vp, _c_int, SsmView, SsmView, SsmView, _vp, SsmView, SsmView, _c_int, _c_int, _c_int, _vp]),
     "ssm_flowinterp_inputs_t_fwd": (_c_int, [SsmView, SsmView, _vp, SsmView, _c_int, _c_int, _c_int, _vp]),
     "ssm_synthesize_fwd": (_c_int, [SsmView, SsmView, SsmView, _vp, SsmView, SsmView, _c_int, _c_int, _c_int, _vp]),
+    "ssm_synthesize_upscaled_fwd": (_c_int, [SsmView, SsmView, _vp, SsmView, _c_int, _c_int, _c_int, _c_int, _vp]),
 }
 
 _lib = None

@@ -175,12 +175,13 @@ def frames_to_yuv_host(x, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITE
 
 
 # ---- the kernels -------------------------------------------------------------------------------------------------------------------
-def frames_from_yuv(payload, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, cfg=None, pad_before_norm=True, out=None):
-    """[N, frame_bytes] uint8 device tensor of Y4M payloads -> [N,3,Hp,Wp] normalised fp32 (into `out` if given)."""
+def frames_from_yuv(payload, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, cfg=None, pad_before_norm=True, out=None, multiple=32):
+    """[N, frame_bytes] uint8 device tensor of Y4M payloads -> [N,3,Hp,Wp] normalised fp32 (into `out` if given); (Hp, Wp) =
+    padded_dims(h, w, multiple): 32 for the path itself, 32 * flow_scale for the coarse-flow mode."""
     assert payload.is_cuda and payload.dtype == torch.uint8 and payload.dim() == 2 and payload.is_contiguous() and \
         payload.shape[1] == frame_bytes(h, w, siting), "payloads must be a contiguous [N, frame_bytes] uint8 tensor on the GPU"
     n = payload.shape[0]
-    (hp, wp), (top, left) = padded_dims(h, w)
+    (hp, wp), (top, left) = padded_dims(h, w, multiple)
     mean, std = cfg_mean_std(cfg)
     if out is None:
         out = torch.empty(n, 3, hp, wp, dtype=torch.float32, device=payload.device)
@@ -384,7 +385,13 @@ class VideoInterpolator:
     writer thread waits for a slot's event and writes, per pair, the interpolated frames and then the right frame's own input bytes.
     Host and device memory are fixed by the frame size, n_streams and pairs_per_batch."""
 
-    def __init__(self, model, cfg, upsample_rate=8, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None):
+    def __init__(self, model, cfg, upsample_rate=8, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1):
+        """flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
+        reference's output, not parity); the canvas is then padded to multiples of 32 * flow_scale."""
+        from .coarse import check_scale
+        self.flow_scale = check_scale(flow_scale)
+        if self.flow_scale != 1 and getattr(model, "recurrent", False):
+            raise NotImplementedError("flow_scale=%d is not available with a recurrent bottleneck" % self.flow_scale)
         n_frames = cfg.getint("TRAIN", "N_FRAMES")
         if n_frames != 2:
             raise NotImplementedError("N_FRAMES=%d needs the recurrent bottleneck (unpinned upstream); use N_FRAMES=2" % n_frames)
@@ -395,18 +402,22 @@ class VideoInterpolator:
         self.matrix, self.color_range = matrix, color_range
         self._pipe = None
 
+    def canvas(self, h, w):
+        """(Hp, Wp) of the planes an h x w clip runs on: padded_dims to multiples of 32 * flow_scale."""
+        return padded_dims(h, w, 32 * self.flow_scale)[0]
+
     def _pipeline(self, hp, wp, dev):
         import os
         from .engine import PairPipeline
         m = self.model
         mode = m.precision or os.environ.get("SSM_PRECISION", sys.modules[type(m).__module__].DEFAULT_PRECISION)      # as FullModel.interpolate
-        key = (hp, wp, str(dev), mode, self.n_streams, self.pb, self.rate, m._stamp())
+        key = (hp, wp, str(dev), mode, self.n_streams, self.pb, self.rate, self.flow_scale, m._stamp())
         if self._pipe is None or self._pipe[0] != key:
             sd1 = {k: v.detach() for k, v in m.stage1_model.state_dict().items()}
             sd2 = {k: v.detach() for k, v in m.stage2_model.state_dict().items()}
             self._pipe = None
             self._pipe = (key, PairPipeline(sd1, sd2, self.rate - 1, hp, wp, dev, m.cross_skip, mode, self.n_streams,
-                                            pairs_per_batch=self.pb))
+                                            pairs_per_batch=self.pb, flow_scale=self.flow_scale))
         return self._pipe[1]
 
     @torch.no_grad()
@@ -421,7 +432,8 @@ class VideoInterpolator:
         dev = next(self.model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
-        (hp, wp), _ = padded_dims(h, w)
+        mult = 32 * self.flow_scale
+        hp, wp = self.canvas(h, w)
         pipe = self._pipeline(hp, wp, dev)
         n, pb, nt = pipe.n, self.pb, self.rate - 1
         depth = n + 2                                                  # ring slots: one per pass in flight, one being read, one being written
@@ -471,7 +483,7 @@ class VideoInterpolator:
             last = (n - 1) % n
             with torch.cuda.stream(pipe.streams[last]):
                 dev_in[last][:1].copy_(first, non_blocking=True)
-                frames_from_yuv(dev_in[last][:1], h, w, siting, matrix, crange, self.cfg, True, out=planes[last][pb:])
+                frames_from_yuv(dev_in[last][:1], h, w, siting, matrix, crange, self.cfg, True, out=planes[last][pb:], multiple=mult)
                 ingested[last].record()
             j, eof = 0, False
             while not eof and not failure:
@@ -491,7 +503,7 @@ class VideoInterpolator:
                     dev_in[k].copy_(host_in[r], non_blocking=True)
                     st.wait_event(ingested[kprev])
                     planes[k][0].copy_(planes[kprev][pb])
-                    frames_from_yuv(dev_in[k], h, w, siting, matrix, crange, self.cfg, True, out=planes[k][1:])
+                    frames_from_yuv(dev_in[k], h, w, siting, matrix, crange, self.cfg, True, out=planes[k][1:], multiple=mult)
                     ingested[k].record()
                     x = planes[k]
                     img6 = x.view(1, 6, hp, wp) if pb == 1 else x.as_strided((pb, 6, hp, wp), (3 * hp * wp, hp * wp, wp, 1))
