@@ -481,7 +481,12 @@ int ssm_upsample2x_cat_fwd(ssm_view a, int Ca, ssm_view b, int Cb, ssm_view y, i
                            void *stream);
 
 /* layers.warp (scripts/models/layers.py:73-120): backward bilinear warp,
- * zeros outside, flow = (u,v).  img [B,C,H,W], flow [B,2,H,W], out [B,C,H,W]. */
+ * zeros outside, flow = (u,v).  img [B,C,H,W], flow [B,2,H,W], out [B,C,H,W].
+ * This sampler and the entry points built on it below (ssm_flowinterp_inputs_fwd / _t_fwd, ssm_synthesize_fwd, the synthesis
+ * fused into ssm_final_conv_fwd), together with ssm_avgpool2_fwd, ssm_upsample2x_cat_fwd, ssm_splitk_finish_fwd and
+ * ssm_copy_view, are held to float64 references one by one, on contiguous tensors and on padded planes, at the sizes where
+ * the 64 x 4 pixel blocks, an axis of one pixel and the image border decide the indexing:
+ * tests/test_hip_infer_elementwise.py (references: tests/train_refs.py). */
 int ssm_warp_bilinear_fwd(ssm_view img, ssm_view flow, ssm_view out, int B, int C, int H, int W,
                           void *stream);
 

@@ -46,6 +46,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import train_refs as R  # noqa: E402
+from train_refs import Box, bits, dptr, report  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
@@ -65,52 +66,6 @@ def hb():
     from ssm_amd import hipbind
     hipbind.load()
     return hipbind
-
-
-def report(group, case, err, e_ref, share=None):
-    print("[elementwise] %-14s %-44s err %.3e  e_ref %.3e  bar %.3e%s"
-          % (group, case, err, e_ref, R.bar(e_ref), "" if share is None else "  excluded %.3f %%" % (100 * share)))
-
-
-class Box:
-    """A [B,C,H,W] fp32 device tensor as plain contiguous NCHW or as padded planes (row stride != W), behind one interface."""
-
-    def __init__(self, hb, dev, layout, x=None, shape=None, fill=NAN):
-        self.hb, self.layout = hb, layout
-        shape = tuple(x.shape) if x is not None else tuple(shape)
-        self.shape = shape
-        if layout == "planes":
-            self.p = hb.Planes(*shape, dev)
-            if x is not None:
-                self.p.load(x.to(dev).contiguous())
-            else:
-                self.p.interior.fill_(fill)
-        else:
-            self.t = x.to(dev).contiguous().clone() if x is not None else torch.full(shape, fill, device=dev)
-
-    def view(self, c0=0, b0=0):
-        if self.layout == "planes":
-            return self.p.view(c0=c0, b0=b0)
-        return self.hb.view_of(self.t[b0:, c0:])
-
-    def get(self):
-        return (self.p.interior if self.layout == "planes" else self.t).cpu()
-
-    def frame_is_zero(self):
-        """planes: the kernel wrote the interior only."""
-        if self.layout != "planes":
-            return True
-        f = self.p.full.clone()
-        f[:, :, self.hb.SSM_PADY:self.hb.SSM_PADY + self.shape[2], self.hb.SSM_PADX:self.hb.SSM_PADX + self.shape[3]] = 0
-        return not bool(f.any())
-
-
-def dptr(t):
-    return t.data_ptr()
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 # ======================================================================================================================

@@ -1,4 +1,5 @@
-"""Float64 references for the element-wise kernels of the training step (csrc/ssm_bwd.hip, csrc/ssm_rnn.hip).
+"""Float64 references for the element-wise kernels of the training step (csrc/ssm_bwd.hip, csrc/ssm_rnn.hip) and of the inference
+path (the forward kernels of csrc/ssm_elem.hip: tests/test_hip_infer_elementwise.py), and the plain helpers both GPU modules share.
 
 A plain helper module (no fixtures, no collection hooks).  Everything here is the CPU oracle (oracle/ssm_oracle.py) evaluated
 under torch.autograd in the dtype asked for: O.warp, O.flow_interp_inputs, O.synthesize, O.upsample2x_bilinear and O.avg_pool2
@@ -9,7 +10,7 @@ The last section serves tests/test_hip_wgrad_exact.py: integer-valued inputs and
 
 Inputs are always DRAWN in fp32 and cast up, so the kernel under test and the float64 reference see the same numbers.
 
-Tolerances (tests/test_hip_train_elementwise.py): err <= bar(e_ref) = max(8 * e_ref, 4 * 2**-24), where err is the largest
+Tolerances (tests/test_hip_train_elementwise.py, tests/test_hip_infer_elementwise.py): err <= bar(e_ref) = max(8 * e_ref, 4 * 2**-24), where err is the largest
 error over the kept entries relative to the largest reference entry and e_ref = ref_gap(...) is the fp32 CPU oracle's own
 distance from the float64 oracle on the same inputs - never a figure of the code under test.
 """
@@ -34,6 +35,7 @@ SAMPLER_CASES = (
 # sizes for the loss sums only: H * W below the 64 chunks (some chunks empty), H * W no multiple of 64
 LOSS_ONLY_CASES = (((2, 3, 5), 1.0), ((1, 7, 19), 2.0))
 SEED = 11
+NAN = float("nan")
 
 
 def bar(e_ref, ratio=8.0):
@@ -210,3 +212,208 @@ def conv_wgrad_exact(x, dz, k):
     bound = 9.0 * x.shape[0] * x.shape[2] * x.shape[3]          # sum over pixels of |dz x|: every partial sum stays below it
     assert bound < 2.0 ** 24 and float(x.abs().max()) <= 3 and float(dz.abs().max()) <= 3
     return w.grad.float(), b.grad.float()
+
+
+# ---- plain helpers of the GPU modules (tests/test_hip_train_elementwise.py, tests/test_hip_infer_elementwise.py) -------------------
+def report(group, case, err, e_ref, share=None):
+    print("[elementwise] %-14s %-44s err %.3e  e_ref %.3e  bar %.3e%s"
+          % (group, case, err, e_ref, bar(e_ref), "" if share is None else "  excluded %.3f %%" % (100 * share)))
+
+
+class Box:
+    """A [B,C,H,W] fp32 device tensor as plain contiguous NCHW or as padded planes (row stride != W), behind one interface."""
+
+    def __init__(self, hb, dev, layout, x=None, shape=None, fill=NAN):
+        self.hb, self.layout = hb, layout
+        shape = tuple(x.shape) if x is not None else tuple(shape)
+        self.shape = shape
+        if layout == "planes":
+            self.p = hb.Planes(*shape, dev)
+            if x is not None:
+                self.p.load(x.to(dev).contiguous())
+            else:
+                self.p.interior.fill_(fill)
+        else:
+            self.t = x.to(dev).contiguous().clone() if x is not None else torch.full(shape, fill, device=dev)
+
+    def view(self, c0=0, b0=0):
+        if self.layout == "planes":
+            return self.p.view(c0=c0, b0=b0)
+        return self.hb.view_of(self.t[b0:, c0:])
+
+    def get(self):
+        return (self.p.interior if self.layout == "planes" else self.t).cpu()
+
+    def frame_is_zero(self):
+        """planes: the kernel wrote the interior only."""
+        if self.layout != "planes":
+            return True
+        f = self.p.full.clone()
+        f[:, :, self.hb.SSM_PADY:self.hb.SSM_PADY + self.shape[2], self.hb.SSM_PADX:self.hb.SSM_PADX + self.shape[3]] = 0
+        return not bool(f.any())
+
+
+def dptr(t):
+    return t.data_ptr()
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+# ---- forward kernels of the inference path (tests/test_hip_infer_elementwise.py) ----------------------------------------------------
+LAYOUTS = ("nchw", "planes")
+CANARY = -7.5           # written into the tail slack behind the last plane of an output; a kernel must leave it alone
+CONSTRUCTED_SHAPES = ((1, 5, 65), (2, 5, 3))     # H - 1 and W - 1 are powers of two: the normalisation round trip is exact in fp32
+
+
+def plant_canary(box):
+    """planes: fill the readable slack behind the last plane of `box` with CANARY."""
+    if box.layout == "planes":
+        box.p.buf[box.p.full.numel():].fill_(CANARY)
+    return box
+
+
+def canary_intact(box):
+    if box.layout != "planes":
+        return True
+    tail = box.p.buf[box.p.full.numel():]
+    return tail.numel() > 0 and bool((bits(tail) == bits(torch.full_like(tail, CANARY))).all())
+
+
+def warp_fwd(img, flow, dtype=torch.float64):
+    return O.warp(img.to(dtype), flow.to(dtype))
+
+
+def inputs_fwd(img6, flow4, t, dtype=torch.float64):
+    """O.flow_interp_inputs: the 16-channel stage-2 input, t [B]."""
+    return O.flow_interp_inputs(img6.to(dtype), flow4.to(dtype), t.to(dtype).view(-1, 1, 1, 1))
+
+
+INPUT_GROUPS = (("I1", 0, 3), ("g(I1)", 3, 6), ("flows", 6, 10), ("g(I0)", 10, 13), ("I0", 13, 16))
+
+
+def synth_fwd(img6, in16, out5, t, dtype=torch.float64):
+    """(y3, Ft1 | Ft0, V0): O.synthesize and the three intermediates ssm_synthesize_fwd writes into `aux`."""
+    img6, in16, out5 = img6.to(dtype), in16.to(dtype), out5.to(dtype)
+    y3 = O.synthesize(img6, in16, out5, t.to(dtype).view(-1, 1, 1, 1))
+    return y3, in16[:, 6:10] + out5[:, 1:5], 1 - torch.sigmoid(out5[:, 0:1])
+
+
+def saturated_case(shape, flow_scale):
+    """make_case with the visibility logit times 40 (|logit| up to ~200): expf(-logit) overflows to inf on one side (V1 = 0), V1 rounds to 1
+    on the other (V0 = 0).  t stays inside (0, 1), so the blend's denominator (1 - t) V0 + t V1 is at least min(t, 1 - t) = 0.125."""
+    c = make_case(shape, flow_scale)
+    c["out5"][:, 0] *= 40.0
+    assert bool(((c["t"] > 0) & (c["t"] < 1)).all())
+    return c
+
+
+def sampling_positions(flow, dtype=torch.float32):
+    """(ix, iy) [B,H,W]: the sampling position of every pixel, by the steps of O.warp (normalise with max(size - 1, 1), map back)."""
+    B, _, H, W = flow.shape
+    flow = flow.to(dtype)
+    xx = torch.arange(W, dtype=torch.float32).view(1, 1, W).expand(B, H, W)
+    yy = torch.arange(H, dtype=torch.float32).view(1, H, 1).expand(B, H, W)
+    gx = 2.0 * (xx + flow[:, 0]) / max(W - 1, 1) - 1.0
+    gy = 2.0 * (yy + flow[:, 1]) / max(H - 1, 1) - 1.0
+    return ((gx + 1.0) / 2.0) * (W - 1), ((gy + 1.0) / 2.0) * (H - 1)
+
+
+def _axis_targets(cls, n):
+    """cls: int tensor of classes 0..3.  Target coordinates on an axis of n pixels, all multiples of 1/4 of small magnitude:
+    0 an integer inside the image; 1 exactly n - 1 (the upper tap is outside, with weight 0); 2 inside (-1, 0) or (n - 1, n) (one tap
+    of the axis outside); 3 at or below -1, or at or above n (both taps of the axis outside, or inside with weight 0 at exactly -1).
+    The j-th pixel of a class takes the class's j-th variant, cyclically, so six pixels of a class cover all of them."""
+    variants = (
+        [float(i) for i in range(n)],
+        [float(n - 1)],
+        [-0.75, n - 1 + 0.25, -0.5, n - 1 + 0.5, -0.25, n - 1 + 0.75],
+        [-1.0, float(n), -1.75, n + 0.75, -2.5, n + 1.5],
+    )
+    flat = cls.flatten()
+    out = torch.zeros(flat.shape, dtype=torch.float32)
+    for k, vals in enumerate(variants):
+        sel = flat == k
+        j = torch.cumsum(sel.long(), 0) - 1
+        out[sel] = torch.tensor(vals, dtype=torch.float32)[j[sel] % len(vals)]
+    return out.view(cls.shape)
+
+
+def constructed_flow(shape):
+    """A flow whose sampling positions are exactly the targets of _axis_targets: u = target - x, built in fp32.  Every combination of
+    the four classes on x and y occurs (16 <= B * H * W).  Returns (flow [B,2,H,W], tx, ty, cx, cy), the last four [B,H,W]."""
+    B, H, W = shape
+    idx = torch.arange(B * H * W).view(B, H, W)
+    cx, cy = idx % 4, (idx // 4) % 4
+    tx, ty = _axis_targets(cx, W), _axis_targets(cy, H)
+    xx = torch.arange(W, dtype=torch.float32).view(1, 1, W)
+    yy = torch.arange(H, dtype=torch.float32).view(1, H, 1)
+    return torch.stack([tx - xx, ty - yy], 1), tx, ty, cx, cy
+
+
+# exact-arithmetic kernels: integer-valued inputs, every product with 1/4, 3/4, 1/8 and every sum exact in fp32
+AVGPOOL_C = (1, 5, 8, 13)                                    # channel groups of 4: one ragged, one, two whole, three + one
+AVGPOOL_HW = ((2, 2), (4, 64), (6, 66), (10, 130))           # input sizes: one output pixel .. a second 64-wide block column
+UPSAMPLE_CH = ((3, 2), (4, 0), (8, 8), (5, 0))
+UPSAMPLE_HW = ((1, 1), (3, 3), (5, 7), (2, 33), (4, 65), (2, 34))     # low-res; (2, 34): a row's last thread owns a PAIR whose right tap clamps
+FINISH_KS = (2, 3, 8)
+FINISH_C = (5, 32, 40)
+FINISH_HW = ((4, 64), (6, 66), (11, 11), (5, 6))            # (11, 11): the one-pixel kernel; (5, 6): even width, a lone last row
+FINISH_SLOPE = 0.125
+# name -> (add_div or 0, lrelu, mask, pool, slope)
+FINISH_OPTIONS = (
+    ("bias-only", 0, False, False, False, FINISH_SLOPE),     # the bias arrives inside partial 0: the plain sum
+    ("lrelu", 0, True, False, False, FINISH_SLOPE),
+    ("pool", 0, False, False, True, FINISH_SLOPE),
+    ("lrelu+pool", 0, True, False, True, FINISH_SLOPE),
+    ("add1", 1, False, False, False, FINISH_SLOPE),
+    ("add2+lrelu", 2, True, False, False, FINISH_SLOPE),
+    ("add2+lrelu+pool", 2, True, False, True, FINISH_SLOPE),
+    ("mask1", 1, False, True, False, FINISH_SLOPE),
+    ("mask2", 2, False, True, False, FINISH_SLOPE),
+    ("lrelu-0.1", 0, True, False, False, 0.1),               # not exact: held to bar(fp32 formula vs float64)
+)
+
+
+def exact_f32(x64):
+    """The float64 result cast down, after asserting that fp32 holds it exactly (the comparison is then a bit comparison)."""
+    x32 = x64.float()
+    assert bool((x32.double() == x64).all()), "the reference left the exact regime"
+    return x32
+
+
+def avgpool_case(C, H, W, B=2):
+    return int_tensor((B, C, H, W), torch.Generator().manual_seed(C * 1000 + H * 10 + W))
+
+
+def upsample_case(Ca, Cb, h, w, B=2, bcast=False):
+    """(a, b or None, cat): b has one batch entry when bcast (every entry of the batch reads it)."""
+    g = torch.Generator().manual_seed(Ca * 100 + Cb * 10 + h + w)
+    a = int_tensor((B, Ca, h, w), g)
+    b = int_tensor((1 if bcast else B, Cb, h, w), g) if Cb else None
+    return a, b, (a if b is None else torch.cat([a, b.expand(B, -1, -1, -1)], 1))
+
+
+def finish_case(KS, C, H, W, B=2):
+    """Integer-valued partial planes [KS * B, C, H, W] and the addends / mask sources for add_div 1 and 2."""
+    g = torch.Generator().manual_seed(KS * 1000 + C * 10 + H + W)
+    return {"part": int_tensor((KS * B, C, H, W), g), 1: int_tensor((B, C, H, W), g), 2: int_tensor((B // 2, C, H, W), g)}
+
+
+def splitk_finish_ref(part, KS, add=None, add_div=1, slope=FINISH_SLOPE, lrelu=False, mask=False, pool=False, dtype=torch.float64):
+    """The contract of ssm_splitk_finish_fwd (include/ssm_hip.h): y = act(sum_ks part[ks * B + b] + add[b / add_div]), the partial maps
+    added in the order ks = 0, 1, ...; SSM_FLAG_MASK: y = sum * (add > 0 ? 1 : slope), no activation; pool = the 2x2 mean of y.
+    Returns (y, pool or None)."""
+    part = part.to(dtype)
+    B = part.shape[0] // KS
+    z = part[0:B].clone()
+    for k in range(1, KS):
+        z = z + part[k * B:(k + 1) * B]
+    sl = torch.tensor(slope, dtype=dtype)          # slope 0.1: fp32(0.1) in the fp32 formula, 0.1 in float64
+    if add is not None:
+        a = add.to(dtype).repeat_interleave(add_div, 0)
+        z = z * torch.where(a > 0, torch.ones_like(a), sl) if mask else z + a
+    if lrelu:
+        z = torch.maximum(z, z * sl)
+    return z, (O.avg_pool2(z) if pool else None)
