@@ -190,10 +190,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p) {
             const int g = 4 * k + w;
             if (w == wid && g < L::NG) {          // wave-uniform
                 const bool pure_w = g * 64 + 63 < L::NWQ, pure_p = g * 64 >= L::NWQ;
-#ifndef SSM_DMA_SADDR
-#define SSM_DMA_SADDR 1
-#endif
-                if (SSM_DMA_SADDR && (pure_w || pure_p)) {
+                if (pure_w || pure_p) {          // one base for the whole piece: the saddr form (the per-lane form costs 7 VALU per DMA)
                     const float *base = pure_w ? wb : pb;
                     const unsigned m0v = lsb + (unsigned)g * 1024u;
                     lds_dma16(base, off[k] * 4, m0v);
@@ -248,17 +245,13 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p) {
         // chunk ch has landed for every wave; every wave is done reading chunk ch-1
         wait_vmcnt<0>();
         __syncthreads();
-        // the DMA of chunk ch+1 is issued from inside the MFMA loop below, one instruction per macro-step (SSM_DMA_SPREAD): the
-        // requests do not hit the memory system as one burst behind the barrier, and the first MFMA does not wait for their issue
-#ifndef SSM_DMA_SPREAD
-#define SSM_DMA_SPREAD 1
-#endif
+        // the DMA of chunk ch+1 is issued from inside the MFMA loop below, one instruction per macro-step: the requests do not hit the
+        // memory system as one burst behind the barrier, and the first MFMA does not wait for their issue
 #ifdef SSM_CONV_ABLATE
         const bool dma_next = ch + 1 < nchunks && !((p.abl & 1) && ch >= 1);
 #else
         const bool dma_next = ch + 1 < nchunks;
 #endif
-        if (!SSM_DMA_SPREAD && dma_next) issue(ch + 1, (ch + 1) & 1);
 
         const float *stg = lds + (ch & 1) * L::STAGE;
         if constexpr (UPS) {
@@ -346,7 +339,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p) {
                             if (g == 0 && n == 0 && m == 0) {
                                 __builtin_amdgcn_sched_barrier(0);
                                 if (ms + 1 < NM) fetch(ms + 1, (ms + 1) & 1);
-                                if (SSM_DMA_SPREAD && ms < L::NI && dma_next) issue_k(ch + 1, (ch + 1) & 1, ms);
+                                if (ms < L::NI && dma_next) issue_k(ch + 1, (ch + 1) & 1, ms);
                                 __builtin_amdgcn_sched_barrier(0);
                             }
                         }
@@ -354,7 +347,7 @@ __global__ __launch_bounds__(256, 2) void conv_mfma_kernel(const ConvParams p) {
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        if constexpr (SSM_DMA_SPREAD && L::NI > NM) {
+        if constexpr (L::NI > NM) {
             if (dma_next) {
 #pragma unroll
                 for (int k = NM; k < L::NI; ++k) issue_k(ch + 1, (ch + 1) & 1, k);

@@ -31,9 +31,6 @@
 #ifndef SSM_C16_PRIO
 #define SSM_C16_PRIO 0
 #endif
-#ifndef SSM_C16_PRODUCERS   // 1: DMA-only producer waves stage the operands (0: every wave issues its share of the DMA)
-#define SSM_C16_PRODUCERS 1
-#endif
 #ifndef SSM_C16_ABL      // diagnostics (wrong results): 1 = no DMA in the loop, 2 = also no barriers, 3 = also no LDS reads
 #define SSM_C16_ABL 0
 #endif
@@ -107,7 +104,7 @@ struct Cfg16 {
     // Producer waves: NP extra waves that only issue the LDS-DMA of the next filter stage / patch slice, so the matrix
     // waves' in-order instruction streams hold nothing but ds_read_b128 and MFMA (each global_load_lds costs its
     // issuing wave 60-180 cycles; ablation in profiles/README.md r1h).
-    static constexpr int NP = (SSM_C16_PRODUCERS == 2 || (SSM_C16_PRODUCERS == 1 && NW >= 8)) ? 4 : 0;   // 4-wave tiles: iterations too short, measured slower
+    static constexpr int NP = NW >= 8 ? 4 : 0;                    // 4-wave tiles: iterations too short, measured slower (every wave issues its share)
     static constexpr int NLOAD = NP ? NP : NW;                    // waves that share the DMA instructions
     static constexpr int NTHREADS_ALL = 64 * (NW + NP);
     static constexpr int PM = (PNI + NLOAD - 1) / NLOAD;          // patch DMA instructions per loading wave

@@ -37,10 +37,6 @@
 #include <type_traits>
 #include <cstdlib>
 
-#ifndef WS_B64
-#define WS_B64 1        // B-operand rows as two aligned ds_read_b64 (patch stored one float in); 0: ds_read2_b32 on the aligned patch
-#endif
-
 namespace {
 
 struct WinoParams {
@@ -184,7 +180,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             const int g = 4 * kk + wid;
             if (g < L::NGP) {
                 const float *base = (c0 < p.C1) ? pbase1 + (long long)c0 * p.sc : pbase2 + (long long)(c0 - p.C1) * p.sc;
-                const unsigned m0v = lsb + (unsigned)(L::NGU + g) * 1024u + ((UPS || !WS_B64) ? 0u : 4u);
+                const unsigned m0v = lsb + (unsigned)(L::NGU + g) * 1024u + (UPS ? 0u : 4u);          // the patch lands one float in (ldB)
                 lds_dma16(base, poff[kk], m0v);
             }
         }
@@ -202,7 +198,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
     // per-lane operand bases (floats) inside a stage: U of (cin = 2cp + half, cout = wn*32 + l31), patch of the lane's tile
     const int aBase = half * (4 * BN) + (wn * 32 + l31);          // in f32x4 units
-    const int bBase = (half * (PH * PW) + ((wty * C::GTH + tyl) * 2) * PW + (wtx * C::GTW + txl) * 2 + 3 + WS_B64) / 2;      // f32x2 units
+    const int bBase = (half * (PH * PW) + ((wty * C::GTH + tyl) * 2) * PW + (wtx * C::GTW + txl) * 2 + 4) / 2;      // f32x2 units
 
     constexpr int S = CK / 2;                  // k-steps per chunk
     const int nchunks = p.Cin / CK;
@@ -219,12 +215,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const f32x2 *lds2 = (const f32x2 *)lds;       // B operands: 8-byte units (bi counts f32x2)
     auto ldB = [&](int bi, int h) {
         const int i = h >> 1, j = (h & 1) * 2;
-#if WS_B64
         const f32x2 t2 = lds2[bi + (i * PW + j) / 2];
         float e0 = t2[0], e1 = t2[1];
-#else
-        float e0 = lds[2 * bi + 1 + i * PW + j], e1 = lds[2 * bi + 1 + i * PW + j + 1];
-#endif
         d[4 * i + j] = e0;            // (pinned as scalars where they are consumed: transform_rows)
         d[4 * i + j + 1] = e1;
     };
@@ -290,7 +282,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 // zero frame or a neighbouring pixel - is finite.
                 const float *r0 = raw + (cg * CPT * LH + (i0 - ly0)) * LW + 3 - lx0 + j0;
                 const float *r1 = raw + (cg * CPT * LH + (i1 - ly0)) * LW + 3 - lx0 + j0;
-                float *dd = hip + (cg * CPT * PH + 2 * pi) * PW + 2 * pj + 3 + WS_B64;       // hi-res pixel x0 + 2pj - 1 -> patch column 2pj + 4 (3 without the one-float shift)
+                float *dd = hip + (cg * CPT * PH + 2 * pi) * PW + 2 * pj + 4;       // hi-res pixel x0 + 2pj - 1 -> patch column 2pj + 4
                 float v00[CPT], v01[CPT], v10[CPT], v11[CPT];
 #pragma unroll
                 for (int cc = 0; cc < CPT; ++cc) {
@@ -336,12 +328,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     // read of chunk ch has been issued and has completed (the last k-step's operands are in registers), so the stage of chunk ch is
     // free for the DMA of chunk ch+2, and chunk ch+1 - issued one chunk ago - is waited for and becomes visible to all waves; the
     // operands of its first k-step are then fetched and transformed behind the remaining MFMAs of chunk ch.
-#ifndef WS_TR0
-#define WS_TR0 13      // MFMA gap that takes the row half of the input transform (16 VALU)
-#endif
-#ifndef WS_TR1
-#define WS_TR1 13      // ... the column half (same gap: the probe prefers the VALU work in ONE gap)
-#endif
+    // The MFMA gap that takes the input transform, row half (16 VALU) then column half (16): ONE gap - tools/wave1_sched_probe.py prefers
+    // the VALU work in one gap (124 TFLOP/s issued against 112 in two gaps, 109 spread two per gap: profiles/r4d_wave1_sched_probe.txt)
+    constexpr int kTransformGap = 13;
     for (int ch = 0; ch < nchunks; ++ch) {
         const int so = (ch & 1) * L::STAGE, so_n = ((ch + 1) & 1) * L::STAGE;
         const bool dma = ch + 2 < nchunks && !WABL(1);
@@ -364,8 +353,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                         if (!WABL(4)) ldB(bi, f - 4);
                     }
                     if (!WABL(4)) {
-                        if (f == WS_TR0) transform_rows();
-                        if (f == WS_TR1) transform_cols(nxt);
+                        if (f == kTransformGap) {
+                            transform_rows();
+                            transform_cols(nxt);
+                        }
                     }
                 } else if (more) {
                     if (f == 0 && !WABL(16)) {
@@ -555,7 +546,7 @@ __device__ __forceinline__ void wino2_body(const WinoParams &p, float *lds) {
             const int g = 4 * kk + wid;
             if (g < L::NGP) {
                 const float *base = (c0 < p.C1) ? pbase1 + (long long)c0 * p.sc : pbase2 + (long long)(c0 - p.C1) * p.sc;
-                const unsigned m0v = lsb + (unsigned)(L::NGU + g) * 1024u + ((UPS || !WS_B64) ? 0u : 4u);
+                const unsigned m0v = lsb + (unsigned)(L::NGU + g) * 1024u + (UPS ? 0u : 4u);          // the patch lands one float in (ldB)
                 lds_dma16(base, poff[kk], m0v);
             }
         }
@@ -572,7 +563,7 @@ __device__ __forceinline__ void wino2_body(const WinoParams &p, float *lds) {
         for (int r = 0; r < 16; ++r) acc[f][r] = 0.f;
 
     const int aBase = half * (4 * BN) + (wn * 32 + l31) + FH * 2 * BN;           // f32x4 units; filter quads 2FH, 2FH+1
-    const int bBase = (half * (PH * PW) + ((wty * C::GTH + tyl) * 2 + FH) * PW + (wtx * C::GTW + txl) * 2 + 3 + WS_B64) / 2;   // f32x2 units; patch rows FH .. FH+2
+    const int bBase = (half * (PH * PW) + ((wty * C::GTH + tyl) * 2 + FH) * PW + (wtx * C::GTW + txl) * 2 + 4) / 2;   // f32x2 units; patch rows FH .. FH+2
 
     constexpr int S = CK / 2;
     const f32x4 *lds4 = (const f32x4 *)lds;
@@ -582,12 +573,8 @@ __device__ __forceinline__ void wino2_body(const WinoParams &p, float *lds) {
     const f32x2 *lds2 = (const f32x2 *)lds;       // B operands: 8-byte units (bi counts f32x2)
     auto ldB = [&](int bi, int h) {
         const int i = h >> 1, j = (h & 1) * 2;
-#if WS_B64
         const f32x2 t2 = lds2[bi + (i * PW + j) / 2];
         float e0 = t2[0], e1 = t2[1];
-#else
-        float e0 = lds[2 * bi + 1 + i * PW + j], e1 = lds[2 * bi + 1 + i * PW + j + 1];
-#endif
         d[4 * i + j] = e0;            // (pinned as scalars where they are consumed: transform_rows)
         d[4 * i + j + 1] = e1;
     };
@@ -637,7 +624,7 @@ __device__ __forceinline__ void wino2_body(const WinoParams &p, float *lds) {
                 const float m00 = (yt && xl) ? 1.f : 0.f, m01 = (yt && xr) ? 1.f : 0.f, m10 = (yb2 && xl) ? 1.f : 0.f, m11 = (yb2 && xr) ? 1.f : 0.f;
                 const float *r0 = raw + (cg * CPT * LH + (i0 - ly0)) * LW + 3 - lx0 + j0;
                 const float *r1 = raw + (cg * CPT * LH + (i1 - ly0)) * LW + 3 - lx0 + j0;
-                float *dd = hip + (cg * CPT * PH + 2 * pi) * PW + 2 * pj + 3 + WS_B64;       // hi-res pixel x0 + 2pj - 1 -> patch column 2pj + 4 (3 without the one-float shift)
+                float *dd = hip + (cg * CPT * PH + 2 * pi) * PW + 2 * pj + 4;       // hi-res pixel x0 + 2pj - 1 -> patch column 2pj + 4
                 float v00[CPT], v01[CPT], v10[CPT], v11[CPT];
 #pragma unroll
                 for (int cc = 0; cc < CPT; ++cc) {
@@ -713,25 +700,15 @@ __device__ __forceinline__ void wino2_body(const WinoParams &p, float *lds) {
             for (int f = 0; f < 8; ++f) {
                 acc[f] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cur][f >> 2][f & 3], v[cur][f], acc[f], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
-#ifndef WS_BFIRST
-#define WS_BFIRST 1        // patch rows first (gaps 0-2), filter quads after them: the transform in gaps 6-7 finds its operands landed
-#endif
+                // patch rows first (gaps 0-2), filter quads after them: the transform in gaps 6-7 finds its operands landed
                 if (!last) {
-                    if (WS_BFIRST) {
-                        if (f < 3) {
-                            if (!WABL(4)) {
-                                ldB(bi, 2 * f);
-                                ldB(bi, 2 * f + 1);
-                            }
-                        } else if (f < 5) {
-                            if (!WABL(8)) ldA(ai, f - 3, nxt);
+                    if (f < 3) {
+                        if (!WABL(4)) {
+                            ldB(bi, 2 * f);
+                            ldB(bi, 2 * f + 1);
                         }
-                    } else {
-                        if (f < 2) ldA(ai, f, nxt);
-                        else if (f < 5) {
-                            ldB(bi, 2 * (f - 2));
-                            ldB(bi, 2 * (f - 2) + 1);
-                        }
+                    } else if (f < 5) {
+                        if (!WABL(8)) ldA(ai, f - 3, nxt);
                     }
                     if (!WABL(4)) {
                         if (f == 6) transform_rows();
@@ -743,25 +720,15 @@ __device__ __forceinline__ void wino2_body(const WinoParams &p, float *lds) {
                         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                         __syncthreads();
                     }
-                    if (WS_BFIRST) {
-                        if (f >= 1 && f < 4) {
-                            if constexpr (!UPS) {
-                                if (!WABL(4)) {
-                                    ldB(bi, 2 * (f - 1));
-                                    ldB(bi, 2 * (f - 1) + 1);
-                                }
-                            }
-                        } else if (f >= 4 && f < 6) {
-                            if (!WABL(8)) ldA(ai, f - 4, nxt);
-                        }
-                    } else {
-                        if (f >= 1 && f < 3) ldA(ai, f - 1, nxt);
-                        else if (f >= 3 && f < 6) {
-                            if constexpr (!UPS) {
-                                ldB(bi, 2 * (f - 3));
-                                ldB(bi, 2 * (f - 3) + 1);
+                    if (f >= 1 && f < 4) {
+                        if constexpr (!UPS) {
+                            if (!WABL(4)) {
+                                ldB(bi, 2 * (f - 1));
+                                ldB(bi, 2 * (f - 1) + 1);
                             }
                         }
+                    } else if (f >= 4 && f < 6) {
+                        if (!WABL(8)) ldA(ai, f - 4, nxt);
                     }
                     if (f >= 1) {
                         constexpr int PER = (L::NI + 6) / 7;

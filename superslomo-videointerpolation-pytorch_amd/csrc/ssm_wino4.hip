@@ -130,9 +130,6 @@ struct W4Lds {
 // interpolation points 0, +-PA, +-PB, inf (PA * PB = 1); the transform matrices in the monic form:
 //   B^T rows: [a2b2 0 -(a2+b2) 0 1 0], [0 -+a b2  -b2  +-a 1 0], [0 -+b a2  -a2  +-b 1 0], [0 a2b2 0 -(a2+b2) 0 1]
 //   A^T[k][f] = p_f^k (k = 0..3; the point at infinity contributes to k = 3 only);  G[f] = [1 p p^2] / prod_{q != p}(p - q), G[inf] = [0 0 1]
-#ifndef W4_INTERLEAVE
-#define W4_INTERLEAVE 1      // 512-thread form: the next chunk's transform in the slots of the matrix loop (0: as one block behind the loop)
-#endif
 #define W4_PA 0.625
 #define W4_PB 1.6
 constexpr float kA = (float)W4_PA, kB = (float)W4_PB, kA2 = (float)(W4_PA * W4_PA), kB2 = (float)(W4_PB * W4_PB);
@@ -818,8 +815,8 @@ __global__ __launch_bounds__(C::THREADS, 2) void wino4_kernel(const W4Params p) 
         //   slots 3..8    row pass of row i - 3 (its read is three MFMAs old)
         //   slots 9..17   the three column passes, three slots each
         //   slots 18..22  the V stores
-        // so that a wave never leaves the matrix pipe without queued work for a whole vector phase.  The role (HH, HQ) is wave-uniform:
-        // the loop is instantiated per role and carries no branch.
+        // so that a wave never leaves the matrix pipe without queued work for a whole vector phase (as one block behind the loop the
+        // transform measured 1.6 % slower).  The role (HH, HQ) is wave-uniform: the loop is instantiated per role and carries no branch.
         f32x4 r4[6];
         f32x2 r2[6];
         float tX[6][3];
@@ -892,12 +889,11 @@ __global__ __launch_bounds__(C::THREADS, 2) void wino4_kernel(const W4Params p) 
                 }
             }, [&](int m) {
                 if constexpr (decltype(HQ)::value == 1) {
-                    if (W4_INTERLEAVE && m1 && !W4ABL(4)) tstep2(HH, m, tsrc, tdst);
+                    if (m1 && !W4ABL(4)) tstep2(HH, m, tsrc, tdst);
                 }
             });
             W4STAMP(3)
             W4TRACE(ch, 2)
-            if (!W4_INTERLEAVE && m1 && !W4ABL(4)) transform_as(HH, HQ, st ^ 1, st ^ 1);          // (block form: always the quarter arrangement)
             if constexpr (UPS) {
                 // waves 4..7 carried the whole transform and are the longer role of a SIMD pair: waves 0..3 expand all four channels (a
                 // 3 : 1 or 2 : 2 split of the expansion between the halves measured 17-23 % SLOWER, profiles/r8z_wino4_expand_split.txt)

@@ -9,21 +9,23 @@
 // over the eight points {0, +-1, +-2, +-1/2, inf} of the one-dimensional F(4,5) form of ssm_wino1d.hip, now on both axes: 64 multiplies
 // per 16 outputs and (cin, cout) = 4 per output instead of 10 (F(4,5) along x) or 25 (direct).  In fp32 a 64-channel layer sits 3.2e-6
 // rms / 2.8e-5 max from float64 at unit output scale (tests/emulate_winograd_5x5_2d.py; the 1-D form: 1.4e-6 / 1.1e-5) - the same
-// level as the blocked 7x7 form of ssm_wino7.hip, whose structure this kernel shares:
+// level as the blocked 7x7 form of ssm_wino7.hip, whose frequency-split kernel (wino7s_kernel) has the same structure:
 //
-// GEMM per frequency f: M_f[cout][tile] = sum_cin U_f[cout][cin] V_f[cin][tile], k-step = 4 input channels; a wave owns 16 couts x 16
-// tiles for all 64 frequencies (64 accumulators of 4 registers: one wave per SIMD), the output transform is lane-local.  One workgroup
-// of four waves = 32 couts x 32 tiles of 4x4 pixels.  Input transform with the overlap of neighbouring windows used (8 rows at stride
-// 4): a ROW pass per (channel, patch row, tile column) leaves X in LDS, a COLUMN pass per (channel, half of the column-frequencies,
-// tile) writes V [16 quads][4 channels][32 tiles][4]; wave w does both passes of channel w, every LDS access of the passes is 16 bytes
-// wide.  26 vector operations per 8-point pass.
+// GEMM per frequency f: M_f[cout][tile] = sum_cin U_f[cout][cin] V_f[cin][tile], k-step = 4 input channels.  One workgroup = 32 couts x 32
+// tiles of 4x4 pixels, EIGHT waves, two per SIMD.  The wave pair of a SIMD owns 16 couts x 16 tiles and splits the 64 frequencies by
+// column-frequency: half 0 = {0, 1, 2, 7}, half 1 = {3, 4, 5, 6} - the two halves of the 8-point transform B^T that share no
+// sub-expression (w5_bt_lo / w5_bt_hi; the packed filter follows, ssm_wino5_pack.h) - so a wave holds 32 accumulators of 4 registers and
+// a second wave fits the SIMD: the vector instructions of one wave's input transform issue BESIDE the other wave's MFMAs (a lone wave
+// cannot issue beside its own MFMAs; tools/mfma_valu_probe.py mode 1: an MFMA-only wave keeps its 32 cycles per instruction next to a
+// vector-only wave).  The halves ping-pong: while one multiplies, the other transforms - schedule and roles at wino5s_kernel below.
 //
-// Per k-step three phases, two barriers (the 160 KiB of LDS hold two filter stages of 32 KiB, two patches, ONE X and ONE V):
-//   [barrier] row pass, column pass [barrier] 64 MFMAs, the DMA of the next k-step's filter and patch one instruction per quad
-// The phases are serial on purpose: 256 accumulator registers leave no second wave per SIMD and no second V / X in LDS to run them beside
-// the MFMAs.  A lone wave issues one vector instruction per ~5 cycles (tools/valu_rate_probe.py), so the two passes (182 vector + 44 LDS
-// instructions) cost ~2000 cycles per k-step beside 2048 of MFMA: the form runs at ~0.33 of the matrix pipe and still beats F(4,5)
-// along x (0.71 of the pipe at 2.5 x the multiplies) by 1.27 x.
+// Input transform with the overlap of neighbouring windows used (8 rows at stride 4): a ROW pass per (channel, patch row, tile column)
+// leaves X in LDS, a COLUMN pass per (channel, tile, pair of the half's column-frequencies) writes V [16 quads][4 channels][32 tiles][4]
+// (quad 2 rf + half); wave w does both passes of channel w & 3.  26 vector operations per 8-point pass.  The output transform is linear
+// in the frequencies: each wave forms a partial 4x4 tile from its half, the pair exchanges partial tiles through LDS.
+//
+// LDS (W5SLds, 152 KiB): two filter stages of 32 KiB, ONE V (each half is written in the phase in which the other half is multiplied),
+// ONE X plane per channel (the halves use it in different phases), three patch buffers (requested two k-steps ahead).
 #include "ssm_conv_host.h"
 #include "ssm_device.h"
 #include "ssm_wino5_pack.h"
@@ -59,7 +61,7 @@ struct W5Params {
     unsigned long long *dbg;   // tuning build (-DW5_TRACE) only: per-wave phase sums of sampled workgroups
 };
 
-// 2 cout halves x 2 tile groups = 4 waves; a tile group = GTX x GTY tiles of 4x4 pixels (16 tiles), the groups sit WTY x WTX.
+// 2 cout halves x 2 tile groups = 4 wave pairs; a tile group = GTX x GTY tiles of 4x4 pixels (16 tiles), the groups sit WTY x WTX.
 template <int GTX_, int WTY_, int WTX_>
 struct W5Cfg {
     static constexpr int GTX = GTX_, GTY = 16 / GTX_, WTY = WTY_, WTX = WTX_;
@@ -70,23 +72,16 @@ struct W5Cfg {
     static constexpr int SHIFT = 2;                                            // floats: the window of tile column Tx starts at patch column 4 Tx + 2 + SHIFT (16-byte aligned)
     static constexpr int NFQ = 16;                                             // quads of frequencies (8 row-frequencies x 2)
     static constexpr int USZ = NFQ * CK * 32 * 4;                              // filter floats per k-step
-    // LDS strides padded against bank conflicts: the column pass reads rows 4 Ty + i of X for all tiles at once (unpadded: 4 rows = 512
-    // bytes apart = the same banks, 8-way conflicts) and writes V for two channels at once (unpadded: 512 bytes apart); measured
-    // 1500 -> cycles per k-step in the column pass (tools/wino5_phase_probe.py)
+    // V's channel stride padded against bank conflicts (unpadded the channels of a quad sit 512 bytes apart = on the same banks); the X row
+    // stride has its own rule in W5SLds
     static constexpr int NTP = NT + 2;                                         // V: f32x4 units between the channels of a quad
-    static constexpr int XRW = NTX * 4 + 4;                                    // X: floats per row
     static constexpr int VSZ = NFQ * CK * NTP * 4;                             // transformed windows of a k-step
-    static constexpr int XPL = PH * XRW;                                       // one plane (channel, half) of row-pass results
-    static constexpr int XSZ = CK * 2 * XPL;
     static constexpr int NDQ = CK * PH * PW / 4, NGP = (NDQ + 63) / 64;        // 16-byte pieces / 1-KiB DMA groups of the patch
     static constexpr int PCAP = NGP * 256 + 256;
-    static constexpr int NGU = USZ / 256, NIU = NGU / 4, NIP = (NGP + 3) / 4;  // DMA instructions per wave and k-step
+    static constexpr int NGU = USZ / 256, NIP = (NGP + 3) / 4;                 // 1-KiB DMA groups of the filter; patch DMA instructions per wave and k-step
     static constexpr int NRU = PH * NTX, NRR = (NRU + 63) / 64;                // row-pass units of a channel, rounds of one wave
-    static constexpr int UOFF = 0, VOFF = 2 * USZ, XOFF = VOFF + VSZ, POFF = XOFF + XSZ;
-    static constexpr int BYTES = (POFF + 2 * PCAP) * 4;
     static_assert(WTY * WTX == 2 && (GTX == 4 || GTX == 8 || GTX == 16), "two tile groups of 16 tiles");
-    static_assert(PW % 4 == 0 && NGU % 4 == 0, "whole DMA groups");
-    static_assert(BYTES <= 160 * 1024, "LDS budget");
+    static_assert(PW % 4 == 0, "whole DMA pieces");
 };
 
 // 8-point transform B^T over the points 0, +1, -1, +2, -2, +1/2, -1/2, inf (the matrix of ssm_wino1d.hip: it depends on the points only)
@@ -113,344 +108,17 @@ __device__ __forceinline__ void w5_at(float m0, float m1, float m2, float m3, fl
     y[3] = ((t1 + 8.f * t2) + 0.125f * t3) + m7;
 }
 
-// ---- epilogue: Y = A^T M A per accumulator register (4 couts per lane), + bias, addend, LeakyReLU, stores, fused 2x2 mean.
-// cu0: first cout of the wave's 16-cout block (this lane holds couts cu0 + 4 q + r), (px, py): the lane's 4x4 output tile.
-// FAST (chosen per wave): every tile of the wave lies inside the map and rows move as aligned 16-byte pieces - the element-wise edge
-// path, a branch per element even when no lane takes it, is not compiled in (ssm_wino7.hip: - 2.7 % on a full-resolution layer)
-template <bool FAST>
-__device__ __forceinline__ void w5_epilogue(const W5Params &p, const f32x4 (&acc)[64], const float (&bv)[4], int b, int cu0, int q, int px, int py) {
-    const float sl = (p.lrelu & 1) ? p.slope : 1.f;
-    const bool amask = (p.lrelu & 2) != 0;          // SSM_FLAG_MASK: the addend view is a mask source (see ssm_hip.h; r6: the 5x5 data gradients too)
-    float *dstb = p.dst + (long long)b * p.dsb;
-    float *poolb = p.pool ? p.pool + (long long)b * p.psb : nullptr;
-    const unsigned pb = 4u * ((unsigned)(4 * q) * (unsigned)p.dsc + (unsigned)py * (unsigned)p.dsh + (unsigned)px);
-    const unsigned qb = 4u * ((unsigned)(4 * q) * (unsigned)p.psc + (unsigned)(py >> 1) * (unsigned)p.psh + (unsigned)(px >> 1));
-    const bool vok = FAST || (py + 4 <= p.H && px + 4 <= p.W && p.vec);          // whole tile inside the map, rows as aligned 16-byte pieces
-    const float *addb = p.add ? p.add + (long long)(b / p.adiv) * p.asb + (long long)(4 * q) * p.asc + (long long)py * p.ash + px : nullptr;
-    // the addend rows of cout r + 1 are requested while cout r is transformed (four independent 16-byte loads, one cout ahead): their
-    // latency runs beside the output transform instead of in front of each cout's stores
-    f32x4 zadd[2][4];
-    const bool zvec = p.add && vok;
-    auto zload = [&](int r) {
-        if (zvec) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) zadd[r & 1][i] = *(const f32x4 *)(addb + (long long)(cu0 + r) * p.asc + (long long)i * p.ash);
-        }
-    };
-    zload(0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int cu = cu0 + r;          // uniform; this lane's cout = cu + 4 * q
-        if (r + 1 < 4) zload(r + 1);
-        float t[4][8];                   // A^T M: over the row-frequencies, for every column-frequency
-#pragma unroll
-        for (int cf = 0; cf < 8; ++cf) {
-            float y4[4];
-            w5_at(acc[cf][r], acc[8 + cf][r], acc[16 + cf][r], acc[24 + cf][r], acc[32 + cf][r], acc[40 + cf][r], acc[48 + cf][r], acc[56 + cf][r], y4);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) t[i][cf] = y4[i];
-        }
-        float y[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float y4[4];
-            w5_at(t[i][0], t[i][1], t[i][2], t[i][3], t[i][4], t[i][5], t[i][6], t[i][7], y4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) y[i][e] = y4[e] + bv[r];
-        }
-        if (p.add) {          // (uniform; addb is a per-lane pointer)
-            const float *ap = addb + (long long)cu * p.asc;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (vok) {
-                    const f32x4 z = zadd[r & 1][i];
-                    if (amask) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) y[i][e] *= z[e] > 0.f ? 1.f : p.slope;
-                    } else {
-                        y[i][0] += z[0];
-                        y[i][1] += z[1];
-                        y[i][2] += z[2];
-                        y[i][3] += z[3];
-                    }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        if (py + i < p.H && px + e < p.W) {
-                                const float z = ap[(long long)i * p.ash + e];
-                                y[i][e] = amask ? y[i][e] * (z > 0.f ? 1.f : p.slope) : y[i][e] + z;
-                            }
-                }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) y[i][e] = fmaxf(y[i][e], y[i][e] * sl);
-        // the wait for the prefetched addend rows of cout r + 1 goes in front of the inline-assembly stores, which the compiler's wait-count
-        // pass does not see (ssm_wino7.hip, w7_epilogue)
-        if (zvec && r + 1 < 4) {
-            pin(zadd[(r + 1) & 1]);
-        }
-        float *bp = dstb + (long long)cu * p.dsc;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (vok) {
-                store_sbase(bp + (long long)i * p.dsh, pb, f32x4{y[i][0], y[i][1], y[i][2], y[i][3]});
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (py + i < p.H && px + e < p.W) store_sbase(bp + (long long)i * p.dsh + e, pb, y[i][e]);
-            }
-        }
-        if (poolb) {
-            // 2x2 mean, vertical pairs first then the horizontal pair (the association of the direct kernel); H, W even (host check)
-            float *qp = poolb + (long long)cu * p.psc;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const float o0 = ((y[2 * i][0] + y[2 * i + 1][0]) + (y[2 * i][1] + y[2 * i + 1][1])) * 0.25f;
-                const float o1 = ((y[2 * i][2] + y[2 * i + 1][2]) + (y[2 * i][3] + y[2 * i + 1][3])) * 0.25f;
-                const bool rok = FAST || py + 2 * i < p.H;
-                if (FAST || (rok && px + 4 <= p.W && p.vec)) store_sbase(qp + (long long)i * p.psh, qb, f32x2{o0, o1});
-                else if (rok) {
-                    if (px + 2 <= p.W) store_sbase(qp + (long long)i * p.psh, qb, o0);
-                    if (px + 4 <= p.W) store_sbase(qp + (long long)i * p.psh + 1, qb, o1);
-                }
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-#if !W5_SPLIT
-template <class C>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void wino5_kernel(const W5Params p) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int PH = C::PH, PW = C::PW, NTX = C::NTX, CK = C::CK, NFQ = C::NFQ;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, l15 = lane & 15, q = lane >> 4;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int cb = wid & 1, tg = wid >> 1;          // cout half, tile group of this wave
-
-    int id = ssm_xcd_tile(blockIdx.x, gridDim.x);
-    const int nb = id % p.NB;
-    id /= p.NB;
-    const int tx = id % p.tilesX;
-    id /= p.tilesX;
-    const int ty = id % p.tilesY;
-    const int b = id / p.tilesY;
-    const int x0 = tx * C::TW, y0 = ty * C::TH;
-
-    const float *pbase = p.src + (long long)b * p.sb + (long long)(y0 - 2) * p.sh + (x0 - 4);
-    const float *wbase = p.wpk + (long long)nb * (p.Cin / CK) * C::USZ;
-
-    // per-lane source offsets (bytes) of the patch pieces this wave brings per k-step (piece = 16 bytes of a patch row of one channel)
-    int poff[C::NIP];
-#pragma unroll
-    for (int i = 0; i < C::NIP; ++i) {
-        const int qq = (i * 4 + wid) * 64 + lane;
-        if (qq < C::NDQ) {
-            const int c = qq / (PH * (PW / 4)), rem = qq - c * (PH * (PW / 4));
-            // rows below the bottom zero frame / pieces right of the padded row: read from the frame's last row / piece (zeros) - a tile
-            // overshoot never brings in another plane's pixels or the memory behind the last plane (see ssm_wino7.hip)
-            const int r = rem / (PW / 4), j = rem - r * (PW / 4);
-            const int re = min(r, p.H + (SSM_PADY - 1) - (y0 - 2)), fe = min(4 * j, ((p.W + 2 * SSM_PADX + 3) & ~3) - 4 - x0);
-            poff[i] = ((int)(c * p.sc) + re * p.sh + fe) * 4;
-        } else {
-            poff[i] = 0;          // tail of the last 1-KiB piece: lands in the buffer's padding
-        }
-    }
-    const int uoff = lane * 16;
-    const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void *)lds;
-    // the n-th DMA instruction of this wave for k-step s (into filter stage / patch buffer s & 1): n < NIP a patch piece, else a filter piece
-    auto issue_n = [&](int s, int n) {
-        const int buf = s & 1;
-        if (n < C::NIP) {
-            const int g = 4 * n + wid;
-            if (4 * n + 3 < C::NGP || g < C::NGP) {
-                const float *base = pbase + (long long)(s * CK) * p.sc;
-                const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(C::POFF + buf * C::PCAP + C::SHIFT) * 4u + (unsigned)g * 1024u);
-                lds_dma16(base, poff[n], m0v);
-            }
-        } else {
-            const int g = 4 * (n - C::NIP) + wid;
-            const float *base = wbase + (long long)s * C::USZ + g * 256;
-            const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(C::UOFF + buf * C::USZ) * 4u + (unsigned)g * 1024u);
-            lds_dma16(base, uoff, m0v);
-        }
-    };
-    static_assert(C::NIP + C::NIU <= 16, "one DMA slot per quad of the matrix phase");
-
-    f32x4 acc[64];
-#pragma unroll
-    for (int f = 0; f < 64; ++f) acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float bv[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) bv[r] = p.bias[nb * 32 + cb * 16 + 4 * q + r];
-
-    // ---- row pass: wave w transforms the rows of channel w of the k-step - the rows its own column pass reads, so no barrier stands
-    // between the two passes; unit = (patch row, tile column), NRR rounds of 64 lanes (lanes beyond the last unit repeat it) -----------
-    int r_src[C::NRR], r_dst[C::NRR];
-#pragma unroll
-    for (int k = 0; k < C::NRR; ++k) {
-        const int u = min(lane + 64 * k, C::NRU - 1);
-        const int c = wid, row = u / NTX, t = u - row * NTX;
-        r_src[k] = C::POFF + C::SHIFT + (c * PH + row) * PW + 4 * t + 2;          // floats; 16-byte aligned
-        r_dst[k] = C::XOFF + c * 2 * C::XPL + row * C::XRW + t * 4;               // half 0; half 1 at + XPL
-    }
-    // ---- column pass: unit = (channel = wave, half h = lane >> 5 of the column-frequencies, tile): one unit per thread.  16-byte reads
-    // and writes: the 8-byte form (a pair of column-frequencies per thread) used half of the banks per instruction and cost ~500 of the
-    // pass's 1580 cycles (profiles/r9i_wino5_first_phases_and_layers.txt) ------------------------------------------------------------
-    const int c_tile = lane & 31;
-    const int c_gx = (c_tile & 15) % C::GTX, c_gy = (c_tile & 15) / C::GTX, c_g2 = c_tile >> 4;
-    const int c_Tx = (c_g2 % C::WTX) * C::GTX + c_gx, c_Ty = (c_g2 / C::WTX) * C::GTY + c_gy;
-    const int c_src = C::XOFF + (wid * 2 + (lane >> 5)) * C::XPL + (4 * c_Ty) * C::XRW + c_Tx * 4;
-    const int c_dst = C::VOFF + (((lane >> 5) * CK + wid) * C::NTP + c_tile) * 4;                      // + rf * 2 * CK * NTP * 4
-
-    // ---- operand bases of the matrix phase (f32x4 units): U of (quad, channel q, cout cb*16 + l15), V of (quad, channel q, tile) ------
-    const f32x4 *lds4 = (const f32x4 *)lds;
-    const int aBase = C::UOFF / 4 + q * 32 + cb * 16 + l15;
-    const int bBase = C::VOFF / 4 + q * C::NTP + tg * 16 + l15;
-    const int gx = l15 % C::GTX, gy = l15 / C::GTX;
-    const int Tx = (tg % C::WTX) * C::GTX + gx, Ty = (tg / C::WTX) * C::GTY + gy;
-
-    const int nsteps = p.Cin / CK;
-#pragma unroll
-    for (int n = 0; n < C::NIP + C::NIU; ++n) issue_n(0, n);
-#ifdef W5_TRACE
-    unsigned long long tph[6] = {0, 0, 0, 0, 0, 0};
-    unsigned long long tk = __builtin_amdgcn_s_memtime();
-    const unsigned long long tstart = tk;
-#define W5STAMP(i)                                                  \
-    {                                                               \
-        const unsigned long long tn = __builtin_amdgcn_s_memtime(); \
-        tph[i] += tn - tk;                                          \
-        tk = tn;                                                    \
-    }
-#else
-#define W5STAMP(i)
-#endif
-    for (int s = 0; s < nsteps; ++s) {
-        const bool more = s + 1 < nsteps;
-        W5STAMP(3)          // [3] matrix phase (incl. the DMA issue)
-        wait_vmcnt<0>();
-        __syncthreads();          // filter and patch of k-step s landed; the MFMAs of k-step s - 1 are done with V and the other filter stage
-        W5STAMP(0)          // [0] DMA wait + top barrier
-        // ---- row pass ---------------------------------------------------------------------------------------------------------------
-        {
-            f32x4 ra[C::NRR][2];
-#pragma unroll
-            for (int k = 0; k < C::NRR; ++k) {
-                const float *src = lds + r_src[k] + (s & 1) * C::PCAP;
-                ra[k][0] = *(const f32x4 *)src;
-                ra[k][1] = *(const f32x4 *)(src + 4);
-            }
-#pragma unroll
-            for (int k = 0; k < C::NRR; ++k) {
-                const float e[8] = {ra[k][0][0], ra[k][0][1], ra[k][0][2], ra[k][0][3], ra[k][1][0], ra[k][1][1], ra[k][1][2], ra[k][1][3]};
-                float f[8];
-                w5_bt(e, f);
-                float *dst = lds + r_dst[k];
-                *(f32x4 *)dst = f32x4{f[0], f[1], f[2], f[3]};
-                *(f32x4 *)(dst + C::XPL) = f32x4{f[4], f[5], f[6], f[7]};
-            }
-        }
-        W5STAMP(1)          // [1] row pass
-        __builtin_amdgcn_wave_barrier();          // X of channel w is written and read by wave w only: the LDS serves a wave's accesses in order
-        W5STAMP(4)          // [4] (no barrier behind the row pass)
-        // ---- column pass ------------------------------------------------------------------------------------------------------------
-        {
-            f32x4 cx[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) cx[i] = *(const f32x4 *)(lds + c_src + i * C::XRW);
-            float f[4][8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float d[8] = {cx[0][e], cx[1][e], cx[2][e], cx[3][e], cx[4][e], cx[5][e], cx[6][e], cx[7][e]};
-                // the values arrive as 16-byte quads: pin each as a scalar so that no packed-fp32 arithmetic is formed on neighbours
-                // (check_isa.sh fences v_pk_*_f32; the four passes are the same arithmetic on the four elements of every quad)
-                pin(d);
-                w5_bt(d, f[e]);
-            }
-#pragma unroll
-            for (int rf = 0; rf < 8; ++rf) *(f32x4 *)(lds + c_dst + rf * 2 * CK * C::NTP * 4) = f32x4{f[0][rf], f[1][rf], f[2][rf], f[3][rf]};
-        }
-        W5STAMP(2)          // [2] column pass
-        __syncthreads();
-        W5STAMP(5)          // [5] barrier behind the column pass
-        // ---- 64 MFMAs: 16 quads of frequencies, operands of quad g + 2 fetched behind the first MFMA of quad g ------------------------
-        {
-            const int ai = aBase + (s & 1) * (C::USZ / 4), bi = bBase;
-            f32x4 a[3], bq[3];
-            a[0] = lds4[ai];
-            bq[0] = lds4[bi];
-            a[1] = lds4[ai + CK * 32];
-            bq[1] = lds4[bi + CK * C::NTP];
-#pragma unroll
-            for (int g = 0; g < NFQ; ++g) {
-                const int cur = g % 3, nxt = (g + 2) % 3;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    acc[4 * g + e] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[cur][e], bq[cur][e], acc[4 * g + e], 0, 0, 0);
-                    if (e == 0) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (g + 2 < NFQ) {
-                            a[nxt] = lds4[ai + (g + 2) * CK * 32];
-                            bq[nxt] = lds4[bi + (g + 2) * CK * C::NTP];
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                    // the DMA of the next k-step, one instruction per quad behind its second MFMA (in a burst in front of the row pass
-                    // the 11 instructions cost ~200 cycles each: 5600 cycles per k-step instead of 4300)
-                    if (e == 1 && g < C::NIP + C::NIU && more) {
-                        issue_n(s + 1, g);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-    W5STAMP(3)
-    {
-        const int px = x0 + 4 * Tx, py = y0 + 4 * Ty;
-        // one copy only: with 256 accumulator registers a second inlined copy of the epilogue (the FAST split of ssm_wino7.hip) spills 8
-        // vector registers, and the epilogue is 9 % of a 64-channel workgroup's life
-        w5_epilogue<false>(p, acc, bv, b, nb * 32 + cb * 16, q, px, py);
-    }
-#ifdef W5_TRACE
-    wait_vmcnt<0>();
-    if (p.dbg && lane == 0 && (blockIdx.x % 64) == 0) {          // a sample of the workgroups
-        const unsigned long long tn = __builtin_amdgcn_s_memtime();
-        for (int i = 0; i < 6; ++i) atomicAdd(p.dbg + wid * 8 + i, tph[i]);
-        atomicAdd(p.dbg + wid * 8 + 6, tn - tk);          // epilogue
-        atomicAdd(p.dbg + wid * 8 + 7, 1ULL);
-        (void)tstart;
-    }
-#endif
-}
-
-#endif          // !W5_SPLIT (the r4 kernel, tuning builds)
-
-#if W5_SPLIT
-// =====================================================================================================================================
-// The frequency-split form (r5, W5_SPLIT = 1, default): EIGHT waves per workgroup, two per SIMD.  The wave pair of a SIMD shares the 16
-// couts x 16 tiles of one r4 wave and splits its 64 frequencies by column-frequency: half 0 = {0, 1, 2, 7}, half 1 = {3, 4, 5, 6} - the
-// two halves of the 8-point transform B^T that share no sub-expression - 32 accumulators (128 registers) per wave.  With one wave per
-// SIMD (r4) the vector instructions of the two passes could only run in front of the MFMAs (a lone wave cannot issue beside its own
-// MFMA: 1880 + 2780 cycles per k-step for 2048 cycles of MFMA); a second wave on the SIMD issues them BESIDE the first wave's MFMAs
-// (tools/mfma_valu_probe.py mode 1: an MFMA-only wave keeps its 32 cycles per instruction next to a vector-only wave).  Per k-step s
-// two phases, two barriers:
+// ---- the kernel: per k-step s two phases, two barriers ------------------------------------------------------------------------------
 //      phase A(s):  waves of half 0: 32 MFMAs on V_0(s) + the DMA of U(s+1)      | waves of half 1: row + column pass -> V_1(s)
 //      phase B(s):  waves of half 1: 32 MFMAs on V_1(s) + the DMA of patch(s+3)  | waves of half 0: row + column pass -> V_0(s+1)
 // so V needs no second buffer (each half is written in the phase in which the other half is multiplied), X is one plane set shared
 // in time by the halves, the patch has three buffers (patch(k) is read in B(k-1) and A(k); requested two k-steps ahead), U two stages.
 // Transform work of a wave = channel (wave & 3) of the k-step: row pass = 3 rounds of (2 x 16-byte read, 14 operations, 16-byte
 // write), column pass = lane (tile, pair of the half's column-frequencies): 8 x 8-byte reads, 2 x 26 operations, 8 x 8-byte writes.
-// Epilogue: the output transform is linear in the frequencies - each wave transforms its half (all 8 row-frequencies, 4 column-
-// frequencies) into a partial 4x4 tile per cout, the pair exchanges partial tiles through LDS (each wave finishes two of the four
-// couts of a lane): y = lo + hi + bias, addend, LeakyReLU, stores, fused 2x2 mean as in the r4 epilogue.
+// Epilogue: each wave transforms its half (all 8 row-frequencies, 4 column-frequencies) into a partial 4x4 tile per cout, the pair
+// exchanges partial tiles through LDS (each wave finishes two of the four couts of a lane): y = lo + hi + bias, addend, LeakyReLU,
+// stores, fused 2x2 mean.  (Measured against the four-wave form with all 64 frequencies on one wave per SIMD and serial phases, which
+// this kernel replaced: 3.07 -> 2.96 ms at batch 14, profiles/r11h_wino5_frequency_split.txt.)
 __device__ __forceinline__ void w5_bt_lo(const float (&e)[8], float (&f)[4]) {          // frequencies 0, 1, 2, 7 (the expressions of w5_bt)
     f[0] = (e[0] - e[6]) + 5.25f * (e[4] - e[2]);
     f[3] = (e[7] - e[1]) + 5.25f * (e[3] - e[5]);
@@ -883,8 +551,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #endif
 }
 
-#endif          // W5_SPLIT
-
 // ---- tile configurations ---------------------------------------------------------------------------------------------------------
 //                     GTX WTY WTX          tiles of 4x4 px     TH   TW
 using F5A = W5Cfg<8, 2, 1>;      //          8 x 4                16   32
@@ -910,13 +576,9 @@ int w5launch(W5Params &p, int B, hipStream_t st) {
     p.tilesX = (p.W + C::TW - 1) / C::TW;
     p.tilesY = (p.H + C::TH - 1) / C::TH;
     p.NB = p.Cout / 32;
-    // (no read outside the padded plane: the per-lane DMA offsets clamp overshoot rows / pieces to the zero frame, see wino5_kernel)
+    // (no read outside the padded plane: the per-lane DMA offsets clamp overshoot rows / pieces to the zero frame, see wino5s_kernel)
     const long long blocks = (long long)p.tilesX * p.tilesY * p.NB * B;
-#if W5_SPLIT
     return ssm::launch_tiles<wino5s_kernel<C>>("wino5 conv", "ssm_wino5_conv2d_add_fwd", blocks, 512, W5SLds<C>::BYTES, st, p);
-#else
-    return ssm::launch_tiles<wino5_kernel<C>>("wino5 conv", "ssm_wino5_conv2d_add_fwd", blocks, 256, C::BYTES, st, p);
-#endif
 }
 
 int w5dispatch(int kind, W5Params &p, int B, hipStream_t st) {
@@ -956,8 +618,9 @@ extern "C" int ssm_wino5_plan(int Cin, int Cout, int B, int H, int W, int *kind)
 }
 
 #ifdef W5_TRACE
-// tuning build only (-DW5_TRACE=1; never lib/libssm_hip.so): 4 x 8 device counters, per wave of the sampled workgroups the shader cycles in
-// [top wait, row pass, column pass, matrix phase, barrier 2, barrier 3, epilogue] and the number of samples
+// tuning build only (-DW5_TRACE=1; never lib/libssm_hip.so): 8 x 8 device counters, per wave of the sampled workgroups the shader cycles in
+// [matrix phases, transform phases, wait + barrier behind a matrix phase, ... behind a transform phase, epilogue, prologue] and, in [7], the
+// number of samples
 extern "C" int ssm_wino5_debug_buffer(unsigned long long *dev_counters) {
     g_w5dbg.store(dev_counters);
     return SSM_OK;

@@ -43,10 +43,6 @@
 #include <type_traits>
 #include <cstdlib>
 
-#ifndef W7_VPAD
-#define W7_VPAD 0            // 1: position rows of V padded against the operand reads' bank conflict - measured 1 % SLOWER (profiles/r11d_wino7_vpad_ab.txt): off
-#endif
-
 namespace {
 
 struct W7Params {
@@ -86,9 +82,9 @@ struct W7Cfg {
     static constexpr int USZ = NFQ * 4 * 32 * 4;                               // filter floats per input channel
     // V [quad][position][4]: the 16 tiles of a lane group read GTY rows of GTX consecutive positions (+ the block's shift); with the rows
     // NPX = 9 units apart the 16th lane's 16 bytes fall on the first lane's banks (a 2-way conflict on every operand read of the matrix
-    // loop: LDS bank-conflict share 0.39, profiles/r10e_wino_sq_counters.txt) - position rows are stored NPV units apart, NPV = GTX mod 16
-    static constexpr int NPV = !W7_VPAD ? NPX : GTX == 8 ? 24 : GTX == 4 ? 20 : NPX;
-    static constexpr int NPT = (NPY - 1) * NPV + NPX;                          // units per quad
+    // loop: LDS bank-conflict share 0.39, profiles/r10e_wino_sq_counters.txt).  Rows padded to 24 / 20 units (= GTX mod 16) remove the
+    // conflict and measured 1 % SLOWER (profiles/r11d_wino7_vpad_ab.txt): the larger V costs the column pass's writes more
+    static constexpr int NPT = NP;                                             // units per quad
     static constexpr int VSZ = NFQ * NPT * 4;                                  // transformed windows
     static constexpr int XSZ = 2 * PH * NPX * 4;                               // row-pass results, [h][row][px][4]
     static constexpr int NDQ = PH * PW / 4, NGP = (NDQ + 63) / 64;             // 16-byte pieces / 1-KiB DMA groups of the patch
@@ -281,12 +277,6 @@ __device__ __forceinline__ void w7_tile_full(const f32x4 (&acc)[49], int r, floa
 #ifndef W7_ABL
 #define W7_ABL 0             // tuning builds (make w7alt W7FLAGS=-DW7_ABL=n): 1 no LDS-DMA, 2 no transform in the steady-state loop; 4 no epilogue
 #endif
-#ifndef W7_UNROLL2
-#define W7_UNROLL2 0
-#endif
-#ifndef W7_INTERLEAVE
-#define W7_INTERLEAVE 1      // the transform pieces and the DMA issue ride in the slots of the matrix loop (0: as blocks in front of it)
-#endif
 
 template <class C>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void wino7_kernel(const W7Params p) {
@@ -364,14 +354,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int c_pos = min(lane, NP - 1);
     const int c_py = c_pos / NPX, c_px = c_pos - c_py * NPX;
     const int c_src = C::XOFF + ((wid >> 1) * PH * NPX + (4 * c_py) * NPX + c_px) * 4 + (wid & 1) * 2;
-    const int c_dst = C::VOFF + ((wid >> 1) * C::NPT + c_py * C::NPV + c_px) * 4 + (wid & 1) * 2;    // + rf * 2 * NPT * 4 per row-frequency
+    const int c_dst = C::VOFF + ((wid >> 1) * C::NPT + c_py * C::NPX + c_px) * 4 + (wid & 1) * 2;    // + rf * 2 * NPT * 4 per row-frequency
 
     // ---- operand bases of the matrix loop (f32x4 units): U of (quad, block q, cout cb*16 + l15), V of (quad, position of the tile + block q)
     const f32x4 *lds4 = (const f32x4 *)lds;
     const int gx = l15 % C::GTX, gy = l15 / C::GTX;
     const int Tx = (tg % C::WTX) * C::GTX + gx, Ty = (tg / C::WTX) * C::GTY + gy;
     const int aBase = C::UOFF / 4 + q * 32 + cb * 16 + l15;
-    const int bBase = C::VOFF / 4 + (Ty + (q >> 1)) * C::NPV + Tx + (q & 1);
+    const int bBase = C::VOFF / 4 + (Ty + (q >> 1)) * C::NPX + Tx + (q & 1);
 
     const int n = p.Cin;
     f32x4 ra[2];                       // row pass: the window row
@@ -519,8 +509,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #define W7STAMP(i)
 #endif
     // ---- one iteration of the pipeline (c from -2): DMA U(c+1), patch(c+3) | row pass (c+2) | column pass (c+1) | matrix (c) ----------
-    // PAR: c & 1 as a compile-time fact (the steady-state loop runs two iterations per trip: every buffer then sits at an immediate offset
-    // from per-lane base addresses that never change - with a run-time parity each LDS access of the transform cost a vector add), or -1
+    // PAR: c & 1 where it is a compile-time fact (the two prologue iterations), or -1.  (A steady-state loop of two iterations per trip
+    // with the parity at compile time saves ~8 vector adds per channel, but the register allocator then routes 5 of the 49 accumulators
+    // through VGPRs every trip - 40 v_accvgpr_read / _write per channel: not kept)
     auto iter = [&](auto J, int c, auto STEADY, auto PAR) __attribute__((always_inline)) {
         constexpr bool steady = decltype(STEADY)::value;
         constexpr int par_ct = decltype(PAR)::value;
@@ -548,15 +539,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             if (k >= 0 && !(steady && (W7_ABL & 2))) tpiece(J, k, doR, doC, rbuf, xrbuf, xcbuf, vbuf);
         };
         const bool held = steady || c >= 1, hold = steady || c + 1 < n;
-        if (doM && W7_INTERLEAVE) {
+        if (doM) {          // the transform pieces and the DMA issue ride in the slots of the matrix loop
             matrix(par, held, hold, slot);
-        } else {
+        } else {            // (the two prologue iterations have no matrix loop: the same slots, one behind the other)
 #pragma unroll
             for (int m = 0; m < 49; ++m) {
                 slot(m);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (doM) matrix(par, held, hold, [](int) {});
         }
     };
 
@@ -571,15 +561,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         iter(J, -1, F{}, P1{});
         int c = 0;
         if (n > 0) iter(J, c++, F{}, PR{});          // (the steady-state copy finishes the previous channel's last quads: from channel 1 on)
-#if W7_UNROLL2          // two iterations per trip, buffer parity at compile time: saves ~8 vector adds per channel, but the register allocator then
-                        // routes 5 of the 49 accumulators through VGPRs every trip (40 v_accvgpr_read / _write per channel) - off
-        for (; c + 4 < n; c += 2) {
-            iter(J, c, T{}, P0{});
-            iter(J, c + 1, T{}, P1{});
-        }
-#else
         for (; c + 3 < n; ++c) iter(J, c, T{}, PR{});
-#endif
         for (; c < n; ++c) iter(J, c, F{}, PR{});
     };
     if (wid == 0) run(std::integral_constant<int, 0>{});
@@ -722,13 +704,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int c_pos = min(lane, NP - 1);
     const int c_py = c_pos / NPX, c_px = c_pos - c_py * NPX;
     const int c_src = C::XOFF + ((w4 >> 1) * PH * NPX + (4 * c_py) * NPX + c_px) * 4 + (w4 & 1) * 2;
-    const int c_dst = C::VOFF + ((w4 >> 1) * C::NPT + c_py * C::NPV + c_px) * 4 + (w4 & 1) * 2;
+    const int c_dst = C::VOFF + ((w4 >> 1) * C::NPT + c_py * C::NPX + c_px) * 4 + (w4 & 1) * 2;
 
     const f32x4 *lds4 = (const f32x4 *)lds;
     const int gx = l15 % C::GTX, gy = l15 / C::GTX;
     const int Tx = (tg % C::WTX) * C::GTX + gx, Ty = (tg / C::WTX) * C::GTY + gy;
     const int aBase = C::UOFF / 4 + q * 32 + cb * 16 + l15 + fh * 128;                            // this half's quads: 2 rf + fh
-    const int bBase = C::VOFF / 4 + (Ty + (q >> 1)) * C::NPV + Tx + (q & 1) + fh * C::NPT;
+    const int bBase = C::VOFF / 4 + (Ty + (q >> 1)) * C::NPX + Tx + (q & 1) + fh * C::NPT;
 
     const int n = p.Cin;
     f32x4 ra[2];

@@ -38,22 +38,14 @@ def main():
     e1.record()
     torch.cuda.synchronize()
     ns = cin // 4
-    if int(cnt[32:].abs().sum()) > 0:          # the frequency-split kernel (8 waves): matrix | transform | barrier behind each | epilogue | prologue
-        c = cnt.cpu().view(8, 8)
-        print("cin %d cout %d batch %d: %.3f ms; %d k-steps per workgroup (split kernel)" % (cin, cout, B, e0.elapsed_time(e1), ns))
-        for w in range(8):
-            n = max(int(c[w, 7]), 1)
-            v = [float(c[w, i]) / n for i in range(6)]
-            print("wave %d (half %d; %d samples), cycles per k-step: matrix %5.0f + wait/barrier %5.0f | transform %5.0f + wait/barrier %5.0f || prologue %6.0f, "
-                  "epilogue %6.0f per workgroup" % (w, w >> 2, n, v[0] / ns, v[2] / ns, v[1] / ns, v[3] / ns, v[5], v[4]))
-        return
-    c = cnt[:32].cpu().view(4, 8)
+    # 8 waves x [matrix | transform | wait + barrier behind a matrix phase | ... behind a transform phase | epilogue | prologue | - | samples]
+    c = cnt.cpu().view(8, 8)
     print("cin %d cout %d batch %d: %.3f ms; %d k-steps per workgroup" % (cin, cout, B, e0.elapsed_time(e1), ns))
-    for w in range(4):
+    for w in range(8):
         n = max(int(c[w, 7]), 1)
-        v = [float(c[w, i]) / n for i in range(7)]
-        print("wave %d (%d samples), cycles per k-step: top wait %5.0f | row pass %5.0f | barrier %4.0f | column pass %5.0f | barrier %4.0f | matrix %5.0f || "
-              "epilogue %6.0f per workgroup" % (w, n, v[0] / ns, v[1] / ns, v[4] / ns, v[2] / ns, v[5] / ns, v[3] / ns, v[6]))
+        v = [float(c[w, i]) / n for i in range(6)]
+        print("wave %d (half %d; %d samples), cycles per k-step: matrix %5.0f + wait/barrier %5.0f | transform %5.0f + wait/barrier %5.0f || prologue %6.0f, "
+              "epilogue %6.0f per workgroup" % (w, w >> 2, n, v[0] / ns, v[2] / ns, v[1] / ns, v[3] / ns, v[5], v[4]))
 
 
 if __name__ == "__main__":
