@@ -522,6 +522,28 @@ int ssm_synthesize_fwd(ssm_view img6, ssm_view in16, ssm_view out5, const float 
  * One fp32 operation per step, no contraction.                                                                          */
 int ssm_synthesize_upscaled_fwd(ssm_view img6, ssm_view aux_lo, const float *t, ssm_view y3, int B, int H, int W, int s, void *stream);
 
+/* Tiled inference (beyond the reference's operator surface; an approximation of the untiled output, not parity): the frames of one
+ * tile are stitched into the full-size frames with a cross-fade over the seams.  tile [N,C,window_h,window_w] = the frames computed on
+ * the window whose first pixel is canvas pixel (oy, ox); out [N,C,Hp,Wp].  The tile's core is rows [cy0, cy1) x columns [cx0, cx1) of the
+ * canvas; `seams` = the sides of the core that have a neighbouring tile (bit 0 top, 1 bottom, 2 left, 3 right); b = 0 (hard seams) or a
+ * power of two in 4..1024.  The call writes the tile's REGION OF INFLUENCE - the core grown by b across every side named in `seams`, cut
+ * at the canvas - and no other element of `out`.  Per pixel (y, x) of it and per (n, c), v = the tile's value there:
+ *   1. u(x; s) = clamp((x - s + b + 0.5) / (2b), 0, 1);  wx = (left ? u(x; cx0) : 1) * (right ? 1 - u(x; cx1) : 1), wy likewise from top
+ *      / bottom / cy0 / cy1; b = 0: wx = wy = 1.  Every weight is an odd multiple of 1/(4b) or 0 or 1: all of this is exact in fp32,
+ *      and the weights of the up to four tiles that reach a pixel sum to exactly 1;
+ *   2. w = wy * wx, p = w * v;
+ *   3. out = p where the pixel lies in neither the tile's left band (left and x < cx0 + b) nor its top band (top and y < cy0 + b),
+ *      else out = out + p.
+ * With the tiles of a grid stitched in RASTER ORDER on one stream, the tile of step 3's first case is the first to reach a pixel: `out`
+ * needs no zero-fill and the result depends on nothing but that order.  One fp32 operation per step, no contraction: bit for bit
+ * ssm_amd.tiles.stitch_host (tests/test_hip_tiles.py).  Refused: null pointers, a window or core outside the canvas, a window smaller
+ * than the region of influence, a seam on a canvas edge, fade bands that meet (two opposite seams and 2b > core), any other b.
+ * 16-byte accesses when both views are 16-byte aligned with strides of multiples of 4 and ox, cx0, cx1 and the region's columns are
+ * multiples of 4 (the engine's grids: everything is a multiple of 32); one pixel per lane otherwise.  Measured (profiles/tiled_bench.txt):
+ * the four launches that stitch a 2x2 tiling of 7 frames at 2176x3840 take 0.32 ms, 1.16x a device-to-device copy of the same bytes. */
+int ssm_tile_stitch_fwd(ssm_view tile, ssm_view out, int N, int C, int window_h, int window_w, int Hp, int Wp, int oy, int ox, int cy0,
+                        int cx0, int cy1, int cx1, int seams, int b, void *stream);
+
 /* final_conv [+ synthesis]: Conv2d(32 -> NC, k3, pad 1, bias), no activation (scripts/models/flow_computation.py:145-153,
  * flow_interpolation.py:149-157), exact fp32: NC = 4 / 5 (the model's two filters) as v_fma_f32 chains in (cin, ky, kx) order,
  * every other NC (and $SSM_FINAL_VALU=0) on v_mfma_f32_4x4x1_16B_f32 (4 couts x 64 pixels per instruction).  x [B,32,H,W]

@@ -13,6 +13,9 @@ pass to the output as their own bytes.  The output's frame rate is the input's t
 with --slowmo, the input's: the same frames played upsample_rate times slower.  8-bit 4:2:0 (both sitings) and 4:4:4 only; N_FRAMES must
 be 2, as for the PNG tool.  --flow_scale 2|4 runs the two U-Nets at 1/2 or 1/4 of the frame size and synthesises at full size (the frame is
 then padded to x64 / x128): several times faster on UHD material, an approximation of the default output, not parity with the reference.
+--tile HxW runs the frame in overlapping windows of tile + halo and stitches them with a cross-fade (--halo, --blend): the activations
+are those of a window instead of the frame, which is what lets 8K material, or 4K on a card shared with other work, run at all; likewise
+an approximation of the default output, not parity.
 """
 import argparse
 import configparser
@@ -26,6 +29,7 @@ for _p in (os.path.dirname(HERE), HERE):
         sys.path.insert(0, _p)
 
 from models import superslomo_r as ssm  # noqa: E402
+from ssm_amd import tiles as T  # noqa: E402
 from ssm_amd import video as V  # noqa: E402
 
 log = logging.getLogger(__name__)
@@ -47,6 +51,12 @@ def getargs(argv=None):
     parser.add_argument("--flow_scale", type=int, choices=(1, 2, 4), default=1,
                         help="Coarse-flow mode: run both U-Nets at 1/flow_scale of the frame size and synthesise at full size (faster on HD and "
                              "UHD material; an approximation of the default output, not parity). Default 1: off.")
+    parser.add_argument("--tile", type=T.parse_tile, default=None, metavar="HxW",
+                        help="Tiled mode: run the frame in overlapping windows with cores of H x W pixels (multiples of 32) and stitch them "
+                             "(less memory; an approximation of the default output, not parity). Default: off.")
+    parser.add_argument("--halo", type=int, default=T.DEFAULT_HALO, help="With --tile: pixels of context around a tile's core (multiple of 32).")
+    parser.add_argument("--blend", type=int, default=T.DEFAULT_BLEND,
+                        help="With --tile: half width of the cross-fade over a seam (0 or a power of two >= 4, at most the halo).")
     return parser.parse_args(argv)
 
 
@@ -59,7 +69,8 @@ def main(argv=None, model=None):
     matrix = None if args.matrix is None else V.MATRICES[args.matrix]
     crange = None if args.color_range is None else V.RANGES[args.color_range]
     model = (model if model is not None else ssm.FullModel(config)).cuda().eval()
-    vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate, matrix=matrix, color_range=crange, flow_scale=args.flow_scale)
+    vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate, matrix=matrix, color_range=crange, flow_scale=args.flow_scale,
+                             tile=args.tile, halo=args.halo, blend=args.blend)
     with V.Y4MReader(args.input) as reader:
         rate = V.output_rate(reader.rate, args.upsample_rate, args.slowmo)
         out_range = crange if crange is not None else (reader.color_range if reader.color_range is not None else V.LIMITED)

@@ -236,18 +236,55 @@ class FullModel(nn.Module):
             self._engine = (key, CoarseFlowEngine(sd1, sd2, P, n_t, H, W, device, flow_scale, self.cross_skip, mode))
         return self._engine[1]
 
+    def _tile(self, tile, halo, blend, flow_scale):
+        """tile / halo / blend of interpolate() / interpolate_many(): None (off), or the checked ((th, tw), halo, blend); the tiled mode
+        is for the CONV bottleneck at flow_scale 1 only."""
+        if tile is None:
+            return None
+        from ssm_amd.tiles import check_args
+        tile, halo, blend = check_args(tile, halo, blend)
+        if flow_scale != 1:
+            raise NotImplementedError("tile=%dx%d together with flow_scale=%d: tiles are not available in the coarse-flow mode"
+                                      % (tile + (flow_scale,)))
+        if self.recurrent:
+            raise NotImplementedError("tile=%dx%d is not available with a recurrent bottleneck (%s / %s): the tiled mode covers the CONV "
+                                      "bottleneck only" % (tile + tuple(self.bottlenecks)))
+        return tile, halo, blend
+
+    def tiled_engine_for(self, P, n_t, H, W, device, tile, halo, blend):
+        """The TiledEngine of interpolate(..., tile=(th, tw)), cached like engine_for's plan (and in its place)."""
+        from ssm_amd.engine import TiledEngine
+        mode = self.precision or os.environ.get("SSM_PRECISION", DEFAULT_PRECISION)
+        key = ("tiled", tile, halo, blend, P, n_t, H, W, str(device), mode, self._stamp())
+        if self._engine is None or self._engine[0] != key:
+            sd1 = {k: v.detach() for k, v in self.stage1_model.state_dict().items()}
+            sd2 = {k: v.detach() for k, v in self.stage2_model.state_dict().items()}
+            self._engine = None
+            self._engine = (key, TiledEngine(sd1, sd2, P, n_t, H, W, device, tile, halo, blend, self.cross_skip, mode))
+        return self._engine[1]
+
     @torch.no_grad()
-    def interpolate(self, image_pair, t_values, flow_scale=1):
+    def interpolate(self, image_pair, t_values, flow_scale=1, tile=None, halo=256, blend=32):
         """One pair [1,2,3,H,W] (or [1,6,H,W]) -> [len(t_values),3,H,W]: stage 1 once, every t
         batched through stage 2 (the loop of evaluate_interpolation_results.py:213-244, hoisted).
         flow_scale = 2 or 4 (opt-in, beyond the reference; an approximation of its output, not parity): both U-Nets run on the
         pair averaged down to 1/flow_scale of its size and the frames are synthesised at full size from the original pixels
-        (ssm_amd.engine.CoarseFlowEngine); H and W must then be multiples of 32 * flow_scale."""
+        (ssm_amd.engine.CoarseFlowEngine); H and W must then be multiples of 32 * flow_scale.
+        tile = (th, tw) (opt-in, beyond the reference; an approximation of the untiled output, not parity): the pair runs in overlapping
+        windows of tile + halo (one plan at the window size, activations of the window instead of the frame) and the windows' frames are
+        stitched with a cross-fade of `blend` pixels either side of a seam (ssm_amd.engine.TiledEngine, ssm_amd.tiles).  A tile that
+        covers the frame is the call without `tile`."""
         hb.require_device(image_pair, "image pair")
         s = self._flow_scale(flow_scale)
+        tiling = self._tile(tile, halo, blend, s)
         img6 = image_pair.reshape(image_pair.shape[0], 6, *image_pair.shape[-2:])
         assert img6.shape[0] == 1, "interpolate() takes one frame pair"
         t = _t_vector(t_values, img6.device)
+        if tiling is not None:
+            from ssm_amd.tiles import covers_canvas
+            if not covers_canvas(img6.shape[2:], tiling[0]):
+                eng = self.tiled_engine_for(1, t.numel(), img6.shape[2], img6.shape[3], img6.device, *tiling)
+                return eng.run(img6, t, want_aux=False).clone()
         if s != 1:
             eng = self.coarse_engine_for(1, t.numel(), img6.shape[2], img6.shape[3], img6.device, s)
             return eng.run(img6, t, want_aux=False).clone()
@@ -284,28 +321,29 @@ class FullModel(nn.Module):
         return out if want_planes else out.to_nchw()
 
     @torch.no_grad()
-    def interpolate_many(self, pairs, t_values, n_streams=2, pairs_per_batch=1, flow_scale=1):
+    def interpolate_many(self, pairs, t_values, n_streams=2, pairs_per_batch=1, flow_scale=1, tile=None, halo=256, blend=32):
         """Throughput form of interpolate(): a list of pairs ([1,2,3,H,W] each, same size) -> list of
         [len(t_values),3,H,W] tensors.  Passes of `pairs_per_batch` pairs are dealt round-robin to `n_streams` engines on
         separate HIP streams (ssm_amd.engine.PairPipeline) so under-filled and tail phases of one pass overlap the
         MFMA-bound convolutions of another; pairs_per_batch > 1 also gives every convolution launch that many times the
         workgroups (bench.py's configuration: 3 streams x 2 pairs).  A remainder that does not fill a pass goes through
-        the one-pair engine.  flow_scale: as interpolate()."""
+        the one-pair engine.  flow_scale, tile, halo, blend: as interpolate()."""
         from ssm_amd.engine import PairPipeline
         first = pairs[0]
         hb.require_device(first, "image pair")
         s = self._flow_scale(flow_scale)
+        tiling = self._tile(tile, halo, blend, s) or (None, halo, blend)
         H, W = first.shape[-2:]
         t = _t_vector(t_values, first.device)
         P = max(1, int(pairs_per_batch))
         mode = self.precision or os.environ.get("SSM_PRECISION", DEFAULT_PRECISION)
-        key = ("pipe", n_streams, P, t.numel(), H, W, str(first.device), mode, s, self._stamp())
+        key = ("pipe", n_streams, P, t.numel(), H, W, str(first.device), mode, s, tiling, self._stamp())
         if getattr(self, "_pipe", None) is None or self._pipe[0] != key:
             sd1 = {k: v.detach() for k, v in self.stage1_model.state_dict().items()}
             sd2 = {k: v.detach() for k, v in self.stage2_model.state_dict().items()}
             self._pipe = None
             self._pipe = (key, PairPipeline(sd1, sd2, t.numel(), H, W, first.device, self.cross_skip, mode, n_streams,
-                                            pairs_per_batch=P, flow_scale=s))
+                                            pairs_per_batch=P, flow_scale=s, tile=tiling[0], halo=tiling[1], blend=tiling[2]))
         pipe = self._pipe[1]
         full = len(pairs) // P * P
         outs = []
@@ -315,7 +353,7 @@ class FullModel(nn.Module):
         pipe.sync()
         res = [o for out in outs for o in (out.split(t.numel()) if P > 1 else (out,))]
         for pr in pairs[full:]:
-            res.append(self.interpolate(pr, t_values, flow_scale=s).clone())
+            res.append(self.interpolate(pr, t_values, flow_scale=s, tile=tiling[0], halo=tiling[1], blend=tiling[2]).clone())
         return res
 
     # ---- training step ------------------------------------------------------------------------------------------

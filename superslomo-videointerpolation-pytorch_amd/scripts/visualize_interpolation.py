@@ -30,6 +30,7 @@ for _p in (os.path.dirname(HERE), HERE):
 from models import superslomo_r as ssm  # noqa: E402
 from ssm_amd import evaluation as E  # noqa: E402
 from ssm_amd import frames as F  # noqa: E402
+from ssm_amd import tiles as T  # noqa: E402
 
 log = logging.getLogger(__name__)
 
@@ -52,6 +53,12 @@ def getargs(argv=None):
     parser.add_argument("--flow_scale", type=int, choices=(1, 2, 4), default=1,
                         help="Coarse-flow mode: run both U-Nets at 1/flow_scale of the frame size and synthesise at full size (an approximation "
                              "of the default output, not parity). Not with --show_intermediate_outputs. Default 1: off.")
+    parser.add_argument("--tile", type=T.parse_tile, default=None, metavar="HxW",
+                        help="Tiled mode: run the frame in overlapping windows with cores of H x W pixels (multiples of 32) and stitch them "
+                             "(less memory; an approximation of the default output, not parity). Not with --show_intermediate_outputs. Default: off.")
+    parser.add_argument("--halo", type=int, default=T.DEFAULT_HALO, help="With --tile: pixels of context around a tile's core (multiple of 32).")
+    parser.add_argument("--blend", type=int, default=T.DEFAULT_BLEND,
+                        help="With --tile: half width of the cross-fade over a seam (0 or a power of two >= 4, at most the halo).")
     return parser.parse_args(argv)
 
 
@@ -67,6 +74,14 @@ class Interpolator:
         if self.flow_scale != 1 and args.show_intermediate_outputs:
             raise NotImplementedError("--flow_scale %d with --show_intermediate_outputs: the intermediates are those of the default mode "
                                       "(flow_scale 1)" % self.flow_scale)
+        self.tile = getattr(args, "tile", None)
+        self.halo, self.blend = getattr(args, "halo", T.DEFAULT_HALO), getattr(args, "blend", T.DEFAULT_BLEND)
+        if self.tile is not None and args.show_intermediate_outputs:
+            raise NotImplementedError("--tile %dx%d with --show_intermediate_outputs: the flows of different tiles are not one field"
+                                      % tuple(self.tile))
+        if self.tile is not None and self.flow_scale != 1:
+            raise NotImplementedError("--tile %dx%d with --flow_scale %d: tiles are not available in the coarse-flow mode"
+                                      % (tuple(self.tile) + (self.flow_scale,)))
         base = os.path.join(args.output_dir, args.expt)
         self.img_dir = os.path.join(base, "images")
         self.visibility_dir = os.path.join(base, "visibility_map")
@@ -122,7 +137,7 @@ class Interpolator:
                     per_t.append((img, inter))
                 outs.append(per_t)
         else:
-            outs = self.model.interpolate_many(pairs, ts, flow_scale=self.flow_scale)
+            outs = self.model.interpolate_many(pairs, ts, flow_scale=self.flow_scale, tile=self.tile, halo=self.halo, blend=self.blend)
         frames_cpu = frames.cpu().numpy()
         for k, (w0, w1) in enumerate(windows):
             self.save(frames_cpu[pos[w0]], count, self.img_dir)

@@ -959,6 +959,50 @@ class CoarseFlowEngine:
         return self.lo.intermediates()
 
 
+class TiledEngine:
+    """Tiled inference (an approximation of the untiled output, not parity): the (H, W) canvas is cut into the tiles of
+    ssm_amd.tiles.TileGrid, ONE PairEngine planned at the window size runs every tile's window of the P pairs at n_t times per pair, and
+    ssm_tile_stitch_fwd cross-fades each tile's P * n_t frames into the engine's full-size output.  Tiles go in raster order on the
+    current stream (the stitch's accumulation order; the inner plan's tensors are reused tile after tile), nothing synchronises the host.
+    run() keeps PairEngine's contract, so a PairPipeline holds either kind.  Activations are those of the window, not of the canvas."""
+
+    def __init__(self, sd1, sd2, P, n_t, H, W, device, tile, halo=256, blend=32, cross_skip=True, mode="f32"):
+        from .tiles import TileGrid
+        self.grid = TileGrid((H, W), tile, halo, blend)
+        assert len(self.grid) > 1, "a tile that covers the canvas is the plain PairEngine, not a case of TiledEngine"
+        wh, ww = self.grid.window
+        self.P, self.G, self.H, self.W, self.device = P, n_t, H, W, device
+        self.inner = PairEngine(sd1, sd2, P, P * n_t, wh, ww, device, cross_skip, mode)
+        self.img = torch.empty(P * n_t, 3, H, W, dtype=torch.float32, device=device)
+        self.img6 = None
+
+    def run(self, img6, t, want_aux=False):
+        """img6 [P,6,H,W] device tensor (read in place: each window is a strided crop of it), t as PairEngine.run_stage2 takes it.
+        Returns the engine's own [P*n_t,3,H,W] output, pair-major.  The windows' aux maps are not kept: want_aux is accepted for
+        the contract's sake."""
+        assert tuple(img6.shape) == (self.P, 6, self.H, self.W), "image pair tensor has shape %s" % (tuple(img6.shape),)
+        self.img6 = img6 if img6.stride(3) == 1 else img6.contiguous()
+        eng, g = self.inner, self.grid
+        wh, ww = g.window
+        tm = UNetPlan.timer
+        for tl in g.tiles:
+            eng.img6 = self.img6[:, :, tl.y0:tl.y0 + wh, tl.x0:tl.x0 + ww]          # load_pair without its copy: the kernels take strided views
+            eng.s1.t["in"].load(eng.img6)
+            eng.run_stage1()
+            frames = eng.run_stage2(t, False)
+            if tm is not None:   # read 3 ch of the region, write 3 ch, read them again in the bands (counted as the one-touch 24 B/px)
+                ry0, ry1, rx0, rx1 = g.region(tl)
+                e0, e1 = tm.span("warp", "tile_stitch", nbytes=24.0 * self.P * self.G * (ry1 - ry0) * (rx1 - rx0))
+                e0.record()
+            hb.tile_stitch(frames, self.img, (tl.y0, tl.x0), (tl.cy0, tl.cx0, tl.cy1, tl.cx1), tl.seams, g.blend)
+            if tm is not None:
+                e1.record()
+        return self.img
+
+    def intermediates(self):
+        raise NotImplementedError("TiledEngine has no intermediates: the flows of different tiles are not one field")
+
+
 class WindowEngine:
     """N_FRAMES-1 = T interpolation windows whose U-Nets are coupled by a recurrent bottleneck
     (BASELINE config 4; scripts/models/superslomo_r.py:152-293 with BOTTLENECK=CLSTM|CGRU).
@@ -1068,14 +1112,28 @@ class PairPipeline:
     pair is read in place.  Results of `submit` stay valid until that slot is reused (N pairs later)."""
 
     def __init__(self, sd1, sd2, n_t, H, W, device, cross_skip=True, mode="f32", n_streams=2, graphs=False, pairs_per_batch=1,
-                 flow_scale=1):
+                 flow_scale=1, tile=None, halo=256, blend=32):
         """pairs_per_batch = P: every submit() takes P pairs [P,6,H,W] through one PairEngine pass (stage 1 at batch P,
         stage 2 at batch P * n_t) and returns [P * n_t,3,H,W], pair-major.  flow_scale = 2 or 4: the engines are
-        CoarseFlowEngines (U-Nets at 1/flow_scale of the size, synthesis at full size)."""
+        CoarseFlowEngines (U-Nets at 1/flow_scale of the size, synthesis at full size).  tile = (th, tw): the engines are
+        TiledEngines (windows of tile + halo, stitched with a cross-fade of `blend`); a tile that covers (H, W) is the plain engine."""
         from .coarse import check_scale
+        from .tiles import check_args, covers_canvas
         self.P = P = int(pairs_per_batch)
         self.flow_scale = check_scale(flow_scale)
-        if self.flow_scale == 1:
+        self.tile = None
+        if tile is not None:
+            self.tile, self.halo, self.blend = check_args(tile, halo, blend)
+            if self.flow_scale != 1:
+                raise NotImplementedError("tile=%dx%d together with flow_scale=%d: tiles are not available in the coarse-flow mode"
+                                          % (self.tile + (self.flow_scale,)))
+            if graphs:
+                raise NotImplementedError("PairPipeline(graphs=True) does not cover tile=%dx%d: the HIP-graph option is for the untiled plan"
+                                          % self.tile)
+        if self.tile is not None and not covers_canvas((H, W), self.tile):
+            self.engines = [TiledEngine(sd1, sd2, P, n_t, H, W, device, self.tile, self.halo, self.blend, cross_skip, mode)
+                            for _ in range(n_streams)]
+        elif self.flow_scale == 1:
             self.engines = [PairEngine(sd1, sd2, P, P * n_t, H, W, device, cross_skip, mode) for _ in range(n_streams)]
         else:
             if graphs:

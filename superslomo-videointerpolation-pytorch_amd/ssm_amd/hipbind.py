@@ -210,6 +210,7 @@ SIGNATURES = {
     "ssm_flowinterp_inputs_t_fwd": (_c_int, [SsmView, SsmView, _vp, SsmView, _c_int, _c_int, _c_int, _vp]),
     "ssm_synthesize_fwd": (_c_int, [SsmView, SsmView, SsmView, _vp, SsmView, SsmView, _c_int, _c_int, _c_int, _vp]),
     "ssm_synthesize_upscaled_fwd": (_c_int, [SsmView, SsmView, _vp, SsmView, _c_int, _c_int, _c_int, _c_int, _vp]),
+    "ssm_tile_stitch_fwd": (_c_int, [SsmView, SsmView] + [_c_int] * 14 + [_vp]),
 }
 
 _lib = None
@@ -378,6 +379,18 @@ def view_of(t):
     require_device(t)
     assert t.dim() == 4 and (t.shape[3] == 1 or t.stride(3) == 1), "need [B,C,H,W] with unit x-stride"
     return SsmView(t.data_ptr(), t.stride(0), t.stride(1), t.stride(2))
+
+
+def tile_stitch(tile, out, origin, core, seams, blend):
+    """ssm_tile_stitch_fwd: one tile's frames [N,C,window_h,window_w] (computed on the window whose first pixel is canvas pixel
+    origin = (oy, ox)) into the full-size frames `out` [N,C,Hp,Wp], cross-faded over the seams.  core = (cy0, cx0, cy1, cx1) in canvas
+    coordinates, seams = the ssm_amd.tiles.SEAM_* bits of the sides with a neighbour, blend = b.  Writes the tile's region of influence
+    only; tiles go in raster order on one stream (include/ssm_hip.h)."""
+    N, C, wh, ww = tile.shape
+    assert out.dim() == 4 and tuple(out.shape[:2]) == (N, C), "tile %s and output %s disagree on [N, C]" % (tuple(tile.shape), tuple(out.shape))
+    check(load().ssm_tile_stitch_fwd(view_of(tile), view_of(out), N, C, wh, ww, out.shape[2], out.shape[3], origin[0], origin[1],
+                                     core[0], core[1], core[2], core[3], seams, blend, stream_ptr()))
+    return out
 
 
 def plane_dims(h, w):

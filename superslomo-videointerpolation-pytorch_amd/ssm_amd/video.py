@@ -385,13 +385,23 @@ class VideoInterpolator:
     writer thread waits for a slot's event and writes, per pair, the interpolated frames and then the right frame's own input bytes.
     Host and device memory are fixed by the frame size, n_streams and pairs_per_batch."""
 
-    def __init__(self, model, cfg, upsample_rate=8, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1):
+    def __init__(self, model, cfg, upsample_rate=8, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
+                 tile=None, halo=256, blend=32):
         """flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
-        reference's output, not parity); the canvas is then padded to multiples of 32 * flow_scale."""
+        reference's output, not parity); the canvas is then padded to multiples of 32 * flow_scale.  tile = (th, tw): the tiled mode of
+        FullModel.interpolate (windows of tile + halo stitched with a cross-fade of `blend`; an approximation of the untiled output,
+        not parity)."""
         from .coarse import check_scale
+        from .tiles import check_args
         self.flow_scale = check_scale(flow_scale)
         if self.flow_scale != 1 and getattr(model, "recurrent", False):
             raise NotImplementedError("flow_scale=%d is not available with a recurrent bottleneck" % self.flow_scale)
+        self.tile, self.halo, self.blend = (None, halo, blend) if tile is None else check_args(tile, halo, blend)
+        if self.tile is not None and self.flow_scale != 1:
+            raise NotImplementedError("tile=%dx%d together with flow_scale=%d: tiles are not available in the coarse-flow mode"
+                                      % (self.tile + (self.flow_scale,)))
+        if self.tile is not None and getattr(model, "recurrent", False):
+            raise NotImplementedError("tile=%dx%d is not available with a recurrent bottleneck" % self.tile)
         n_frames = cfg.getint("TRAIN", "N_FRAMES")
         if n_frames != 2:
             raise NotImplementedError("N_FRAMES=%d needs the recurrent bottleneck (unpinned upstream); use N_FRAMES=2" % n_frames)
@@ -411,13 +421,14 @@ class VideoInterpolator:
         from .engine import PairPipeline
         m = self.model
         mode = m.precision or os.environ.get("SSM_PRECISION", sys.modules[type(m).__module__].DEFAULT_PRECISION)      # as FullModel.interpolate
-        key = (hp, wp, str(dev), mode, self.n_streams, self.pb, self.rate, self.flow_scale, m._stamp())
+        key = (hp, wp, str(dev), mode, self.n_streams, self.pb, self.rate, self.flow_scale, self.tile, self.halo, self.blend, m._stamp())
         if self._pipe is None or self._pipe[0] != key:
             sd1 = {k: v.detach() for k, v in m.stage1_model.state_dict().items()}
             sd2 = {k: v.detach() for k, v in m.stage2_model.state_dict().items()}
             self._pipe = None
             self._pipe = (key, PairPipeline(sd1, sd2, self.rate - 1, hp, wp, dev, m.cross_skip, mode, self.n_streams,
-                                            pairs_per_batch=self.pb, flow_scale=self.flow_scale))
+                                            pairs_per_batch=self.pb, flow_scale=self.flow_scale, tile=self.tile, halo=self.halo,
+                                            blend=self.blend))
         return self._pipe[1]
 
     @torch.no_grad()
