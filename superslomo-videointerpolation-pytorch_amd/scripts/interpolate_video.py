@@ -16,6 +16,11 @@ then padded to x64 / x128): several times faster on UHD material, an approximati
 --tile HxW runs the frame in overlapping windows of tile + halo and stitches them with a cross-fade (--halo, --blend): the activations
 are those of a window instead of the frame, which is what lets 8K material, or 4K on a card shared with other work, run at all; likewise
 an approximation of the default output, not parity.
+
+--fps N[:D] and --speed X leave the fixed grid: the output follows ssm_amd.video.Timeline, one frame every speed * input rate / fps input
+frames (24 -> 60, 25 -> 60, 23.976 -> 59.94 as --fps 60000:1001, 29.97 -> 25, --speed 0.3 or 3/10 for slow motion that is no integer
+factor).  --fps alone is speed 1, --speed alone keeps the input's rate in the header.  A frame that falls on an input frame is that
+frame's own bytes; pairs that get no frame are not run.  Neither goes together with --upsample_rate or --slowmo.
 """
 import argparse
 import configparser
@@ -35,6 +40,16 @@ from ssm_amd import video as V  # noqa: E402
 log = logging.getLogger(__name__)
 
 
+def _named(parse):
+    """An argparse type whose usage error carries the parser's own message, which names the value."""
+    def f(text):
+        try:
+            return parse(text)
+        except ValueError as e:
+            raise argparse.ArgumentTypeError(str(e)) from None
+    return f
+
+
 def getargs(argv=None):
     parser = argparse.ArgumentParser()
     parser.add_argument("-c", "--config", required=True, default="config.ini", help="Path to config.ini file.")
@@ -42,8 +57,12 @@ def getargs(argv=None):
     parser.add_argument("--log", required=True, help="Path to logfile.")
     parser.add_argument("--input", required=True, help="Input .y4m file, or - for stdin.")
     parser.add_argument("--output", required=True, help="Output .y4m file, or - for stdout.")
-    parser.add_argument("--upsample_rate", type=int, default=8,
-                        help="Integer upsampling rate. For 30FPS -> 240FP, use 8. For 1080FPS, use 36.")
+    parser.add_argument("--upsample_rate", type=int, default=None,
+                        help="Integer upsampling rate. For 30FPS -> 240FP, use 8. For 1080FPS, use 36. Default 8.")
+    parser.add_argument("--fps", type=_named(V.parse_rate), default=None, metavar="N[:D]",
+                        help="Output frame rate, written into the header as given (60, 60000:1001): any rate, not only a multiple of the input's.")
+    parser.add_argument("--speed", type=_named(V.parse_speed), default=None, metavar="X",
+                        help="Playback speed as a decimal or a fraction (0.25, 1/4, 3/10); below 1 is slow motion. Default 1.")
     parser.add_argument("--matrix", choices=sorted(V.MATRICES), default=None, help="Y'CbCr matrix (default: bt709 from 720 rows up, else bt601).")
     parser.add_argument("--range", choices=sorted(V.RANGES), default=None, dest="color_range",
                         help="Code range (default: the header's XCOLORRANGE tag, else limited).")
@@ -57,7 +76,13 @@ def getargs(argv=None):
     parser.add_argument("--halo", type=int, default=T.DEFAULT_HALO, help="With --tile: pixels of context around a tile's core (multiple of 32).")
     parser.add_argument("--blend", type=int, default=T.DEFAULT_BLEND,
                         help="With --tile: half width of the cross-fade over a seam (0 or a power of two >= 4, at most the halo).")
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    if args.fps is not None or args.speed is not None:
+        if args.upsample_rate is not None or args.slowmo:
+            parser.error("--fps / --speed set the output's timeline themselves: they do not go together with --upsample_rate or --slowmo")
+    elif args.upsample_rate is None:
+        args.upsample_rate = 8
+    return args
 
 
 def main(argv=None, model=None):
@@ -69,10 +94,16 @@ def main(argv=None, model=None):
     matrix = None if args.matrix is None else V.MATRICES[args.matrix]
     crange = None if args.color_range is None else V.RANGES[args.color_range]
     model = (model if model is not None else ssm.FullModel(config)).cuda().eval()
-    vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate, matrix=matrix, color_range=crange, flow_scale=args.flow_scale,
-                             tile=args.tile, halo=args.halo, blend=args.blend)
+    timed = args.fps is not None or args.speed is not None
+    vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate or 8, matrix=matrix, color_range=crange,
+                             flow_scale=args.flow_scale, tile=args.tile, halo=args.halo, blend=args.blend, target_rate=args.fps, speed=args.speed)
     with V.Y4MReader(args.input) as reader:
-        rate = V.output_rate(reader.rate, args.upsample_rate, args.slowmo)
+        if timed:
+            rate = args.fps or reader.rate
+            tl = vi.timeline(reader.rate)
+            log.info("[%s] timeline: step = %s input frames per output frame, slots = %d times per pair", args.expt, tl.step, tl.slots)
+        else:
+            rate = V.output_rate(reader.rate, args.upsample_rate, args.slowmo)
         out_range = crange if crange is not None else (reader.color_range if reader.color_range is not None else V.LIMITED)
         log.info("[%s] %s: %dx%d C%s at %d:%d frames/s -> %s at %d:%d", args.expt, args.input, reader.width, reader.height, reader.chroma,
                  reader.rate[0], reader.rate[1], args.output, rate[0], rate[1])

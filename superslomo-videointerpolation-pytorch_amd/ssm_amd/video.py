@@ -10,12 +10,18 @@
   VideoInterpolator       the streamed loop: every leg of a pass (H2D, ingest, the pair pipeline, egress, D2H) is queued on the pass's HIP
                           stream, a writer thread drains a ring of pinned buffers in order; memory does not depend on the clip's length
 
-Out of scope: codecs, audio, more than 8 bits per sample, the recurrent configuration (N_FRAMES > 2).
+  Timeline / PassPlanner  any output rate and speed: where each output frame sits on the input's clock, exactly (Fractions, closed form),
+                          and the bookkeeping of the passes that follow it - VideoInterpolator(target_rate=, speed=)
+
+Out of scope: codecs, audio, more than 8 bits per sample, the recurrent configuration (N_FRAMES > 2); shutter / motion-blur integration
+and frame blending when the rate goes down, variable-rate input, speeds that change within a clip.
 """
 import ctypes
 import queue
+import re
 import sys
 import threading
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -375,9 +381,175 @@ def output_rate(rate, upsample_rate, slowmo=False):
     return (rate[0], rate[1]) if slowmo else (rate[0] * int(upsample_rate), rate[1])
 
 
+# ---- the output timeline: any frame rate, any speed ----------------------------------------------------------------------------------
+# The stage-2 batch of a pass is pairs_per_batch * slots.  The widest tensor of the decoder (up-sampled 512 channels beside a 512-channel
+# skip) goes through its element-wise kernels in groups of 4 channels on the grid's z axis together with the batch: 256 groups * batch
+# has to stay within 65535, so a plan takes at most 255 stage-2 entries - the largest upsample_rate - 1 at one pair per pass.
+MAX_STAGE2_BATCH = 255
+MAX_PERIOD = 1 << 20          # min(numerator, denominator) of a step: the pattern's period, walked once to find `slots`
+
+
+def parse_rate(text):
+    """"60", "60:1" or "60000:1001" -> (num, den), as written (not reduced); anything else is a ValueError naming the text."""
+    m = re.fullmatch(r"(\d+)(?::(\d+))?", str(text).strip())
+    if not m or int(m.group(1)) < 1 or (m.group(2) is not None and int(m.group(2)) < 1):
+        raise ValueError("a frame rate is written N or N:D with positive integers, e.g. 60 or 60000:1001 (got %r)" % (text,))
+    return int(m.group(1)), int(m.group(2) or 1)
+
+
+def parse_speed(text):
+    """"0.25", "1/4" or "3/10" (or a number, or a Fraction) -> Fraction > 0; anything else is a ValueError naming the value."""
+    try:
+        s = Fraction(text.strip() if isinstance(text, str) else text)
+    except (ValueError, TypeError, ZeroDivisionError):
+        raise ValueError("a speed is written as a decimal or a fraction, e.g. 0.25, 1/4 or 3/10 (got %r)" % (text,)) from None
+    if s <= 0:
+        raise ValueError("a speed must be positive (got %r)" % (text,))
+    return s
+
+
+def timeline_step(in_rate, target_rate=None, speed=None):
+    """step = speed * in_rate / out_rate as a Fraction: how far the input clock moves per output frame.  target_rate None: the input's
+    rate; speed None: 1."""
+    in_rate = Fraction(int(in_rate[0]), int(in_rate[1]))
+    out_rate = in_rate if target_rate is None else Fraction(int(target_rate[0]), int(target_rate[1]))
+    return (Fraction(1) if speed is None else parse_speed(speed)) * in_rate / out_rate
+
+
+class Timeline:
+    """Where every output frame sits on the input's clock.  Input frame i sits at time i; output frame k at tau_k = k * step, for
+    k = 0 .. floor((n - 1) / step) of an n-frame clip.  With i = floor(tau_k) and t = tau_k - i: t == 0 is input frame i's own bytes,
+    anything else the frame synthesised between inputs i and i + 1 at t.  All of it in Fractions and in closed form from k - no time is
+    ever accumulated, so a long clip drifts by nothing.
+
+    The engine's time is t32(t) = np.float32(t.numerator / t.denominator): the exact ratio rounded once to float64 by the division and
+    once more to float32 - the rule of evaluation.t_values (idx / float(rate), then the tensor's float32), so step = 1/R gives its times
+    bit for bit.
+
+    slots: the most synthesised frames any one pair gets - the engine's times per pair.  step = a/b in lowest terms repeats every b
+    outputs (a inputs), so one period decides it.  A speed that changes within a clip would replace `step` by a function of k here."""
+
+    def __init__(self, step, max_slots=None):
+        try:
+            step = Fraction(step)
+        except (ValueError, TypeError, ZeroDivisionError):
+            raise ValueError("the timeline's step must be a number or a fraction (got %r)" % (step,)) from None
+        if step <= 0:
+            raise ValueError("the timeline's step (speed * input rate / output rate) must be positive (got %s)" % step)
+        self.step, self.a, self.b = step, step.numerator, step.denominator
+        if min(self.a, self.b) > MAX_PERIOD:
+            raise ValueError("step %s repeats only every %d frames (more than %d): round the rate or the speed" % (step, min(self.a, self.b), MAX_PERIOD))
+        if self.a <= self.b:          # one period is a input pairs ...
+            self.slots = max(self.count(i) for i in range(self.a))
+        else:                         # ... or b outputs, whichever is the shorter walk; here a pair gets one frame at the most
+            self.slots = 1 if self.b > 1 else 0
+        if max_slots is not None and self.slots > max_slots:
+            raise ValueError("step %s puts %d frames between two input frames; the plan takes at most %d (the largest upsample_rate - 1 at "
+                             "this pairs_per_batch)" % (step, self.slots, max_slots))
+        self._fed = self._k = 0
+
+    def at(self, k):
+        """(i, t) of output frame k."""
+        i, r = divmod(k * self.a, self.b)
+        return i, Fraction(r, self.b)
+
+    def n_outputs(self, n):
+        """floor((n - 1) / step) + 1 output frames for n input frames."""
+        return ((n - 1) * self.b) // self.a + 1 if n > 0 else 0
+
+    def outputs(self, n):
+        """[(i, t)] of every output frame of an n-frame clip."""
+        return [self.at(k) for k in range(self.n_outputs(n))]
+
+    def count(self, i):
+        """Synthesised frames of pair (i, i + 1): the k with i < k * step < i + 1."""
+        return -((-(i + 1) * self.b) // self.a) - (i * self.b) // self.a - 1
+
+    def times(self, i):
+        """The t of pair (i, i + 1)'s synthesised frames, increasing."""
+        k0 = (i * self.b) // self.a + 1
+        return [self.at(k0 + j)[1] for j in range(self.count(i))]
+
+    @staticmethod
+    def t32(t):
+        return np.float32(t.numerator / t.denominator)
+
+    def feed(self, end=False):
+        """The incremental form, for a pipe whose length nobody knows: call it once per frame read and once more, with end=True, at
+        the end of the input.  Returns the [(i, t)] that have just become computable - an output needs frame i + 1 read, or frame i
+        when t == 0 - so the calls of an n-frame clip return outputs(n) piece by piece.  The call at the end returns nothing (what is
+        left needs a frame that never came) and rewinds the timeline for the next clip."""
+        if end:
+            self._fed = self._k = 0
+            return []
+        self._fed += 1
+        out = []
+        while True:
+            i, t = self.at(self._k)
+            if i + (1 if t else 0) >= self._fed:
+                return out
+            out.append((i, t))
+            self._k += 1
+
+
+class PassPlanner:
+    """The bookkeeping of VideoInterpolator._run_timeline, free of the GPU: which frames of the input stay in a ring slot's `cap` rows,
+    which pairs a pass runs, and what the writer takes from the slot in the timeline's order.  The caller reads each frame into row
+    `rows` of the open slot and calls frame(); that returns None, or the closed slot as (order, pairs):
+      order   [("interp", row of the slot's output buffer) | ("orig", row of its input buffer)], by increasing k
+      pairs   [(row of the pair's first new payload, own_left, [fp32 times])] of at most pairs_per_batch pairs that run; pair p's frames
+              are rows p * slots .. of the output buffer.  own_left: the pair's left frame is that row and its right frame the next
+              one; otherwise the left frame is the right frame of the pair that ran before it (the one before in `pairs`, or the last
+              of the pass before) and the row is the right frame's.
+    end() closes what is open.  A frame that no output needs keeps no row: the next frame is read over it.  A frame that waits for its
+    right neighbour stays in one slot with it: a slot closes at pairs_per_batch pairs, at cap rows, or one row early when no frame waits."""
+
+    def __init__(self, tl, pairs_per_batch, cap):
+        assert cap >= 2
+        self.tl, self.pb, self.cap = tl, pairs_per_batch, cap
+        self.f = 0                 # frames read
+        self.prev_right = -1       # the input frame that the last running pair left on the device as its right frame
+        self._open()
+
+    def _open(self):
+        self.rows, self.order, self.pairs, self._of = 0, [], [], None
+
+    def _close(self):
+        out = (self.order, self.pairs)
+        self._open()
+        return out
+
+    def frame(self):
+        tl, f, S = self.tl, self.f, self.tl.slots
+        keep = tl.count(f) > 0          # the left frame of a pair that runs, if another frame follows
+        for i, t in tl.feed():
+            if t:                        # a frame of pair (f - 1, f)
+                if self._of != i:
+                    own_left = self.prev_right != i
+                    assert not own_left or self.rows >= 1
+                    self.pairs.append((self.rows - 1 if own_left else self.rows, own_left, []))
+                    self._of, self.prev_right = i, f
+                self.order.append(("interp", (len(self.pairs) - 1) * S + len(self.pairs[-1][2])))
+                self.pairs[-1][2].append(Timeline.t32(t))
+            else:
+                self.order.append(("orig", self.rows))
+            keep = True
+        self.rows += 1 if keep else 0
+        waits = tl.count(f) > 0 and self.prev_right != f
+        self.f += 1
+        if len(self.pairs) == self.pb or self.rows == self.cap or (self.rows == self.cap - 1 and not waits):
+            return self._close()
+        return None
+
+    def end(self):
+        self.tl.feed(end=True)
+        return self._close()
+
+
 # ---- the streamed loop -------------------------------------------------------------------------------------------------------------
 class VideoInterpolator:
-    """reader -> (upsample_rate - 1) frames between every two input frames -> writer, streamed.
+    """reader -> (upsample_rate - 1) frames between every two input frames -> writer, streamed; or, with target_rate / speed, the frames
+    of a Timeline (any output rate, any speed: _run_timeline).
 
     A pass takes `pairs_per_batch` new frames: H2D of their payloads, ingest (each frame once: its planes are the right frame of one
     pair and, carried over, the left frame of the next), the PairPipeline engine of the pass's stream, egress, D2H into the pass's slot
@@ -386,8 +558,10 @@ class VideoInterpolator:
     Host and device memory are fixed by the frame size, n_streams and pairs_per_batch."""
 
     def __init__(self, model, cfg, upsample_rate=8, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
-                 tile=None, halo=256, blend=32):
-        """flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
+                 tile=None, halo=256, blend=32, target_rate=None, speed=None):
+        """target_rate = (num, den) and / or speed (a Fraction, or what Fraction() takes; 1/4 is four times slower): the output follows
+        Timeline(speed * input rate / target_rate) instead of the fixed grid of upsample_rate, which is then not used (see
+        _run_timeline); with both None nothing changes.  flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
         reference's output, not parity); the canvas is then padded to multiples of 32 * flow_scale.  tile = (th, tw): the tiled mode of
         FullModel.interpolate (windows of tile + halo stitched with a cross-fade of `blend`; an approximation of the untiled output,
         not parity)."""
@@ -411,29 +585,40 @@ class VideoInterpolator:
         self.n_streams, self.pb = max(1, int(n_streams)), max(1, int(pairs_per_batch))
         self.matrix, self.color_range = matrix, color_range
         self._pipe = None
+        self.target_rate = None if target_rate is None else parse_rate("%s:%s" % tuple(target_rate))
+        self.speed = None if speed is None else parse_speed(speed)
+        self.timed = target_rate is not None or speed is not None
 
     def canvas(self, h, w):
         """(Hp, Wp) of the planes an h x w clip runs on: padded_dims to multiples of 32 * flow_scale."""
         return padded_dims(h, w, 32 * self.flow_scale)[0]
 
-    def _pipeline(self, hp, wp, dev):
+    def timeline(self, in_rate):
+        """The Timeline of a clip at `in_rate` (num, den); refuses a step whose slots the plan would not take."""
+        return Timeline(timeline_step(in_rate, self.target_rate, self.speed), max_slots=MAX_STAGE2_BATCH // self.pb)
+
+    def _pipeline(self, hp, wp, dev, n_t=None):
         import os
         from .engine import PairPipeline
         m = self.model
         mode = m.precision or os.environ.get("SSM_PRECISION", sys.modules[type(m).__module__].DEFAULT_PRECISION)      # as FullModel.interpolate
-        key = (hp, wp, str(dev), mode, self.n_streams, self.pb, self.rate, self.flow_scale, self.tile, self.halo, self.blend, m._stamp())
+        n_t = self.rate - 1 if n_t is None else n_t
+        key = (hp, wp, str(dev), mode, self.n_streams, self.pb, n_t, self.flow_scale, self.tile, self.halo, self.blend, m._stamp())
         if self._pipe is None or self._pipe[0] != key:
             sd1 = {k: v.detach() for k, v in m.stage1_model.state_dict().items()}
             sd2 = {k: v.detach() for k, v in m.stage2_model.state_dict().items()}
             self._pipe = None
-            self._pipe = (key, PairPipeline(sd1, sd2, self.rate - 1, hp, wp, dev, m.cross_skip, mode, self.n_streams,
+            self._pipe = (key, PairPipeline(sd1, sd2, n_t, hp, wp, dev, m.cross_skip, mode, self.n_streams,
                                             pairs_per_batch=self.pb, flow_scale=self.flow_scale, tile=self.tile, halo=self.halo,
                                             blend=self.blend))
         return self._pipe[1]
 
     @torch.no_grad()
     def run(self, reader, writer):
-        """Returns the number of frames written: (n - 1) * upsample_rate + 1 for n input frames."""
+        """Returns the number of frames written: (n - 1) * upsample_rate + 1 for n input frames (with target_rate / speed:
+        floor((n - 1) / step) + 1)."""
+        if self.timed:
+            return self._run_timeline(reader, writer)
         from .evaluation import t_values
         h, w, siting, fb = reader.height, reader.width, reader.siting, reader.frame_bytes
         if (writer.height, writer.width, writer.siting) != (h, w, siting):
@@ -525,6 +710,135 @@ class VideoInterpolator:
                 work.put((r, valid))
                 written += valid * self.rate
                 j += 1
+        finally:
+            work.put(None)
+            th.join()
+            torch.cuda.synchronize(dev)
+        if failure:
+            raise failure[0]
+        return written
+
+    @torch.no_grad()
+    def _run_timeline(self, reader, writer):
+        """run() with target_rate / speed: the output frames are those of Timeline(speed * reader.rate / target_rate).
+
+        Pairs now differ: pair (i, i + 1) gets tl.count(i) synthesised frames at its own times, and a pair that gets none is not run -
+        no upload, no ingest, no stage 1 or 2, no egress.  A pass collects up to pairs_per_batch pairs that do run.  Every engine is
+        planned for `slots` times per pair; a pair with m < slots runs with its last time repeated in the rest, only its first m
+        frames go through the egress kernel and back to the host.  The times go up from a pinned buffer of the pass's ring slot on the
+        pass's stream.  A ring slot holds `cap` input payloads - every frame read lands in one, a frame nobody needs is overwritten by
+        the next - and the list of what the writer thread takes from it, in the timeline's order: ("interp", row of host_out) or
+        ("orig", row of host_in).  Each uploaded frame is ingested once: a pair's left frame is the previous running pair's right
+        frame copied on the device, or, after a pair that did not run, ingested with the right one.  A pass short of pairs (end of
+        clip, or a slot full of frames passed through) leaves the planes of its unused entries as they are: finite, and never read
+        back.  Memory is fixed by the frame size, n_streams, pairs_per_batch and slots."""
+        h, w, siting, fb = reader.height, reader.width, reader.siting, reader.frame_bytes
+        if (writer.height, writer.width, writer.siting) != (h, w, siting):
+            raise ValueError("reader and writer disagree on the frame format")
+        matrix = default_matrix(h) if self.matrix is None else self.matrix
+        crange = self.color_range if self.color_range is not None else (reader.color_range if reader.color_range is not None else LIMITED)
+        dev = next(self.model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
+        tl = self.timeline(reader.rate)
+        S, pb, n = tl.slots, self.pb, self.n_streams
+        mult = 32 * self.flow_scale
+        hp, wp = self.canvas(h, w)
+        pipe = self._pipeline(hp, wp, dev, S) if S else None          # an integer step only picks input frames: nothing to run
+        depth, cap = n + 2, 2 * pb + 2
+        host_in = [torch.empty(cap, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
+        host_out = [torch.empty(pb * max(S, 1), fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
+        host_t = [torch.full((pb * max(S, 1),), 0.5, dtype=torch.float32).pin_memory() for _ in range(depth)]
+        np_in, np_out, np_t = [t.numpy() for t in host_in], [t.numpy() for t in host_out], [t.numpy() for t in host_t]
+        done = [torch.cuda.Event() for _ in range(depth)]
+        if pipe is not None:
+            dev_in = [torch.empty(cap, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
+            dev_out = [torch.empty(pb * S, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
+            dev_t = [torch.empty(pb * S, dtype=torch.float32, device=dev) for _ in range(n)]
+            planes = [torch.zeros(pb, 2, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [pair][left | right]
+            ingested = [torch.cuda.Event() for _ in range(n)]
+        torch.cuda.synchronize(dev)
+
+        free, work, failure = queue.Queue(), queue.Queue(), []
+        for r in range(depth):
+            free.put(r)
+
+        def drain():
+            while True:
+                item = work.get()
+                if item is None:
+                    return
+                r, order, on_gpu = item
+                try:
+                    if not failure:
+                        if on_gpu:
+                            done[r].synchronize()
+                        for kind, row in order:
+                            writer.write_frame(np_out[r][row] if kind == "interp" else np_in[r][row])
+                except BaseException as e:          # noqa: BLE001 - handed to the caller's thread; keep releasing slots
+                    failure.append(e)
+                free.put(r)
+
+        last_p = [0]          # place, in its pass, of the pair whose right frame the next pair may carry over
+
+        def submit(j, r, pairs):
+            """Pass j: `pairs` = [(first row of the pair's new payloads, the left frame is among them, its times)] of ring slot r."""
+            k = j % n
+            st = pipe.streams[k]
+            with torch.cuda.stream(st):
+                if j:
+                    st.wait_event(ingested[(j - 1) % n])          # the carried frame; and pass j - n + 1 is done with planes[k]
+                for p, (row, own_left, ts) in enumerate(pairs):
+                    rows = 2 if own_left else 1
+                    dev_in[k][row:row + rows].copy_(host_in[r][row:row + rows], non_blocking=True)
+                    if not own_left:
+                        planes[k][p, 0].copy_(planes[k][p - 1, 1] if p else planes[(j - 1) % n][last_p[0], 1])
+                    frames_from_yuv(dev_in[k][row:row + rows], h, w, siting, matrix, crange, self.cfg, True, out=planes[k][p, 2 - rows:],
+                                    multiple=mult)
+                    np_t[r][p * S:p * S + len(ts)] = ts
+                    np_t[r][p * S + len(ts):(p + 1) * S] = ts[-1]
+                np_t[r][len(pairs) * S:] = np_t[r][len(pairs) * S - 1]
+                dev_t[k].copy_(host_t[r], non_blocking=True)          # with the payloads, ahead of the kernels: see DESIGN 3.12
+                ingested[k].record()
+                last_p[0] = len(pairs) - 1
+                frames = pipe.engines[k].run(planes[k].view(pb, 6, hp, wp), dev_t[k], False)
+                if all(len(ts) == S for _, _, ts in pairs):
+                    spans = [(0, len(pairs) * S)]
+                else:
+                    spans = [(p * S, len(ts)) for p, (_, _, ts) in enumerate(pairs)]
+                for o, m in spans:
+                    frames_to_yuv(frames[o:o + m], h, w, siting, matrix, crange, self.cfg, out=dev_out[k][o:o + m])
+                    host_out[r][o:o + m].copy_(dev_out[k][o:o + m], non_blocking=True)
+                done[r].record()
+
+        th = threading.Thread(target=drain, name="y4m-writer", daemon=True)
+        th.start()
+        plan = PassPlanner(tl, pb, cap)
+        written = j = 0          # frames written, passes issued
+        r = None
+
+        def issue(r, order, pairs):
+            nonlocal written, j
+            if pairs and not failure:
+                submit(j, r, pairs)
+                j += 1
+            work.put((r, order if not failure else [], bool(pairs) and not failure))
+            written += len(order)
+
+        try:
+            while not failure:
+                if r is None:
+                    r = free.get()
+                if failure or not reader.read_frame_into(np_in[r][plan.rows]):
+                    break
+                closed = plan.frame()
+                if closed is not None:
+                    issue(r, *closed)
+                    r = None
+            if r is not None:
+                issue(r, *plan.end())
+            if plan.f == 0 and not failure:
+                raise Y4MError("the Y4M stream holds no frame")
         finally:
             work.put(None)
             th.join()

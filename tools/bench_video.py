@@ -8,8 +8,12 @@
                      reading the clip included; median and (min, max) over `--runs` runs
   png_fps            the same clip as a folder of PNGs through scripts/visualize_interpolation.py (unchanged by the video path, so this
                      measures it as it was): wall time of main(), output frames / s
-The clip (`--frames`, 65 by default) is built from synthetic_frames_u8, written below a temporary directory and deleted afterwards.
-Usage: python tools/bench_video.py [--frames 65] [--iters 20] [--windows 7] [--runs 3] [--skip-e2e] [--skip-png] [--png-frames N]"""
+  timeline_fps       the arbitrary-rate path beside the fixed grid at the same times per pair: target_rate 75:1 on the 30:1 clip (step = 2/5,
+                     the pattern of 24 -> 60, slots = 2) and upsample_rate = 3 (two times per pair as well), file to /dev/null, run in
+                     turns in one process on the same two HIP streams; SYNTHESISED frames per second (frames passed through not counted), median and (min, max)
+The clip (`--frames`, 41 by default: synthetic_frames_u8 moves its window 3 px per frame and has room for 43) is built from it, written below a temporary directory and deleted afterwards.
+Usage: python tools/bench_video.py [--frames 41] [--iters 20] [--windows 7] [--runs 3] [--skip-e2e] [--skip-png] [--skip-timeline]
+[--png-frames N]"""
 import argparse
 import json
 import os
@@ -58,15 +62,16 @@ def kernel_record(ms, nbytes):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=65)
+    ap.add_argument("--frames", type=int, default=41)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--skip-e2e", action="store_true")
     ap.add_argument("--skip-png", action="store_true")
+    ap.add_argument("--skip-timeline", action="store_true")
     ap.add_argument("--png-frames", type=int, default=0, help="frames of the clip the PNG tool gets (0 = all)")
     args = ap.parse_args()
-    assert args.frames >= 2
+    assert 2 <= args.frames <= 43, "synthetic_frames_u8 holds 43 frames of this size at the most"
     dev = torch.device("cuda:0")
     cfg = load_config("superslomo_original.ini", synthetic_weight_overrides())
     model = FullModel(cfg)
@@ -130,6 +135,29 @@ def main():
             rec["note"] = ("output frames (originals included) per second of wall time of VideoInterpolator.run, 2 streams x 1 pair, the "
                            "precision mode of FullModel.interpolate; peak device memory %d MiB" % (torch.cuda.max_memory_allocated(dev) >> 20))
             res["video_fps"] = rec
+        if not args.skip_timeline:
+            legs = {"step_2_5_target_75": (V.VideoInterpolator(model, cfg, n_streams=2, pairs_per_batch=1, target_rate=(75, 1)), (75, 1)),
+                    "upsample_rate_3": (V.VideoInterpolator(model, cfg, upsample_rate=3, n_streams=2, pairs_per_batch=1), (90, 1))}
+            synth = {"step_2_5_target_75": sum(1 for _, t in V.Timeline("2/5").outputs(args.frames) if t), "upsample_rate_3": 2 * (args.frames - 1)}
+            fps = {name: [] for name in legs}
+            for turn in range(args.runs + 2):          # turn 0: plans, pinned buffers' first touch; turn 1: the first run on the shared streams
+                if turn == 1:
+                    # both legs on the same two HIP streams: which hardware queues a pipeline's streams are dealt moves a leg by more
+                    # than 10 %, and the legs never run at the same time
+                    pipes = [vi_leg._pipe[1] for vi_leg, _ in legs.values()]
+                    pipes[1].streams = pipes[0].streams
+                for name, (vi_leg, rate) in legs.items():
+                    with V.Y4MReader(src) as r, V.Y4MWriter.like(os.devnull, r, rate=rate) as w:
+                        t0 = time.perf_counter()
+                        k = vi_leg.run(r, w)
+                        w.f.flush()
+                        dt = time.perf_counter() - t0
+                    if turn > 1:
+                        fps[name].append(synth[name] / dt)
+            res["timeline_fps"] = {name: {"synthesised_frames_per_s": round(statistics.median(v), 2), "min": round(min(v), 2),
+                                          "max": round(max(v), 2), "synthesised_frames": synth[name]} for name, v in fps.items()}
+            res["timeline_fps"]["note"] = ("both legs run two times per pair on every pair of the clip, 2 streams x 1 pair, file to /dev/null, "
+                                           "in turns, on the same two HIP streams; frames that pass through as input bytes are written but not counted")
         if not args.skip_png:
             import visualize_interpolation as viz
             from PIL import Image
