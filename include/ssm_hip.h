@@ -644,6 +644,32 @@ int ssm_frames_to_yuv_fwd(ssm_view in, unsigned char *frames_yuv, int N, int H, 
                           const float *mean3, const float *std3, const float *table, int matrix, int range,
                           int siting, void *stream);
 
+/* ---- shutter of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) ----------------------------------
+ * Definition (ssm_amd.video.Timeline(step, shutter=, samples=), everything in exact fractions).  `step` = input frames per output
+ * frame, as without a shutter; shutter = sigma in (0, 1], the open fraction of the output interval (a shutter angle of 360 sigma
+ * degrees); samples = S >= 1.  Output frame k is the mean of S sub-frames at
+ *     tau(k, j) = k step + j d,   d = sigma step / S,   j = 0 .. S-1
+ * - the shutter opens at the frame's own instant, so no sample lies before input frame 0.  With i = floor(tau), t = tau - i: t == 0 is
+ * input frame i's ingested planes, anything else the frame synthesised between i and i + 1 at Timeline.t32(t).  Output k exists iff its
+ * last sample does: tau(k, S-1) <= n - 1.  The mean is taken of the path's normalised fp32 planes - of the gamma-coded R'G'B' values, as a
+ * frame-mixing filter does; integration in linear light is out of scope.  S = 1 is the timeline without a shutter.  S = 8, the default of
+ * the streamed loop, is a convention, not backed by a measurement of quality.
+ * ssm_frames_accumulate_fwd: src [N,C,H,W], acc [1,C,H,W], both strided views (acc.sb is not read).  Per element, one rounded fp32
+ * operation per step (no fused multiply-add), in this order:
+ *   1. s = init ? src[0] : acc + src[0]
+ *   2. s = s + src[n]   for n = 1 .. N-1, in increasing n
+ *   3. acc = s * scale
+ * bit for bit ssm_amd.video.accumulate_host (tests/test_hip_shutter.py).  A launch reads `acc` at most once (not at all with init = 1) and
+ * writes it once, whatever N; nothing outside the H x W region of `acc` is written.  An output frame of the streamed loop is a chain of
+ * such calls in time order on event-ordered streams: init = 1 on the first, scale = fp32(1 / S) on the last, 1 otherwise.
+ * 16-byte accesses when both views are 16-byte aligned with strides of multiples of 4 and W % 4 == 0; one element per lane in the same
+ * kernel otherwise.  No LDS, no scratch; no packed fp32 as the library is built (-fno-slp-vectorize in csrc/Makefile, fenced by
+ * check_isa.sh: without that flag hipcc packs the four lanes of a 16-byte access into v_pk_add_f32 / v_pk_mul_f32).
+ * SSM_E_ARG (nothing is launched) for null pointers; N, C, H or W < 1; N or C > 65535; H > 262140 (a lane group takes 4 rows and the
+ * grid's y axis ends at 65535); a row stride shorter than W; init outside {0, 1}; a scale that is not finite; src and acc address ranges
+ * that overlap. */
+int ssm_frames_accumulate_fwd(ssm_view src, ssm_view acc, int N, int C, int H, int W, int init, float scale, void *stream);
+
 /* ---- training ingest (csrc/ssm_data.hip; whole decoded uint8 HWC RGB frames on the device) --------------
  * The clip loader (ssm_amd/data.py) serves the reference's training transform, RandomCrop, then RandomMirrorRotate,
  * then Normalize and ToTensor (scripts/utils/dataloaders/default_reader.py:182-207,250-286, augmentations.py:

@@ -9,12 +9,17 @@
 //   frames_to_yuv_kernel     one thread per 4 x 2 luma block = two chroma samples: denormalise, matrix, chroma filtered and subsampled
 //                            in float, range, round half to even, saturate; four Y codes of a row go out as one 32-bit store, the two
 //                            chroma codes of a plane as one 16-bit store, when the frame size allows it
-// Both are HBM-bound (1.5 B in + 12 B out per pixel, and the reverse).  The chroma siting enters as four horizontal weights (ingest)
-// or one switch (egress); matrix and range enter as one row of the constant table built by ssm_amd/video.py, which the host yardsticks
-// read too.  Inputs of the egress kernel are finite.
+//   frames_accumulate_kernel the shutter of the streamed loop: N frames summed, in increasing n, into one fp32 accumulator
+//                            that is read at most once and written once per launch; one lane = 4 consecutive pixels of a row of one
+//                            channel (16-byte loads and stores), or one pixel when a view does not allow it
+// Both conversions are HBM-bound (1.5 B in + 12 B out per pixel, and the reverse); so is the accumulation (4 (N + 1 + !init) B per
+// element).  The chroma siting enters as four horizontal weights (ingest) or one switch (egress); matrix and range enter as one row of
+// the constant table built by ssm_amd/video.py, which the host yardsticks read too.  Inputs of the egress kernel are finite.
 // NO CONTRACTION (as ssm_flow.hip): the numpy yardsticks round every operation, and so must the kernels.
 #include "ssm_common.h"
 #include "ssm_device.h"
+
+#include <cmath>
 
 #pragma clang fp contract(off)
 
@@ -252,6 +257,49 @@ __global__ __launch_bounds__(256) void frames_to_yuv_kernel(ssm_view in, unsigne
     }
 }
 
+// ---- shutter: frames summed into an accumulator ----------------------------------------------------------------------------------------
+// s = init ? src[0] : acc + src[0];  s = s + src[n], n = 1 .. N-1;  acc = s * scale - one rounded fp32 operation per step (the file is
+// compiled without contraction), the order of ssm_amd.video.accumulate_host.  The loads of the N frames do not depend on one another and
+// the one store comes last, so the unrolled loop keeps several loads in flight per lane.  The float4 arithmetic stays four scalar
+// v_add_f32 / v_mul_f32 per step only because the Makefile builds every file with -fno-slp-vectorize (check_isa.sh fails the build on any
+// v_pk_*_f32): a plain hipcc -O3 of this file packs it into v_pk_add_f32 / v_pk_mul_f32.
+template <int V>          // pixels per lane: 4 (float4 accesses) or 1
+__global__ __launch_bounds__(256) void frames_accumulate_kernel(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale) {
+    const int x = (blockIdx.x * 64 + threadIdx.x) * V, y = blockIdx.y * 4 + threadIdx.y, c = blockIdx.z;
+    if (x >= W || y >= H) return;          // V = 4: W % 4 == 0, so x + 3 < W
+    const float *s = src.ptr + (long long)c * src.sc + (long long)y * src.sh + x;
+    float *a = acc.ptr + (long long)c * acc.sc + (long long)y * acc.sh + x;
+    if constexpr (V == 4) {
+        float4 v = *reinterpret_cast<const float4 *>(s);
+        if (!init) {
+            const float4 o = *reinterpret_cast<const float4 *>(a);
+            v = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
+        }
+#pragma unroll 4
+        for (int n = 1; n < N; ++n) {
+            const float4 f = *reinterpret_cast<const float4 *>(s + (long long)n * src.sb);
+            v = make_float4(v.x + f.x, v.y + f.y, v.z + f.z, v.w + f.w);
+        }
+        *reinterpret_cast<float4 *>(a) = make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale);
+    } else {
+        float v = *s;
+        if (!init) v = *a + v;
+#pragma unroll 4
+        for (int n = 1; n < N; ++n) v = v + s[(long long)n * src.sb];
+        *a = v * scale;
+    }
+}
+
+// first and one-past-last address, in bytes, of the floats a view of [n,c,h,w] names (strides of either sign)
+inline void view_range(const ssm_view &v, int n, int c, int h, int w, long long *lo, long long *hi) {
+    long long a = 0, b = 0;
+    const long long ext[3] = {(long long)(n - 1) * v.sb, (long long)(c - 1) * v.sc, (long long)(h - 1) * v.sh};
+    for (int i = 0; i < 3; ++i) (ext[i] < 0 ? a : b) += ext[i];
+    const long long base = (long long)reinterpret_cast<size_t>(v.ptr);
+    *lo = base + 4 * a;
+    *hi = base + 4 * (b + w);
+}
+
 inline bool view_aligned(const ssm_view &v, int floats) {
     return (reinterpret_cast<size_t>(v.ptr) % (floats * sizeof(float))) == 0 && v.sh % floats == 0 && v.sc % floats == 0 && v.sb % floats == 0;
 }
@@ -329,4 +377,25 @@ extern "C" int ssm_frames_to_yuv_fwd(ssm_view in, unsigned char *frames_yuv, int
         SSM_LAUNCH(frames_to_yuv_kernel<false>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, frames_yuv, H, W, top, left, fb,
                    row_of(table, matrix, range), norm_of(mean3, std3), siting == SSM_YUV_420_COSITED ? 1 : 0, vec_in, vec_out);
     return ssm::check_launch("ssm_frames_to_yuv_fwd");
+}
+
+extern "C" int ssm_frames_accumulate_fwd(ssm_view src, ssm_view acc, int N, int C, int H, int W, int init, float scale, void *stream) {
+    SSM_REQUIRE(src.ptr && acc.ptr, "frames_accumulate: null pointer");
+    SSM_REQUIRE(N > 0 && N <= 65535 && C > 0 && C <= 65535 && H > 0 && W > 0 && (H + 3) / 4 <= 65535,
+                "frames_accumulate: bad sizes N=%d C=%d H=%d W=%d", N, C, H, W);
+    SSM_REQUIRE(src.sh >= W && acc.sh >= W, "frames_accumulate: row strides %d (src), %d (acc) shorter than W=%d", src.sh, acc.sh, W);
+    SSM_REQUIRE(init == 0 || init == 1, "frames_accumulate: init must be 0 or 1 (got %d)", init);
+    SSM_REQUIRE(std::isfinite(scale), "frames_accumulate: scale must be finite (got %g)", (double)scale);
+    long long s0, s1, a0, a1;
+    view_range(src, N, C, H, W, &s0, &s1);
+    view_range(acc, 1, C, H, W, &a0, &a1);
+    SSM_REQUIRE(s1 <= a0 || a1 <= s0, "frames_accumulate: src and acc overlap (%lld bytes apart)", a0 - s0);
+    const bool vec = W % 4 == 0 && view_aligned(src, 4) && view_aligned(acc, 4);
+    if (vec)
+        SSM_LAUNCH(frames_accumulate_kernel<4>, dim3((W / 4 + 63) / 64, (H + 3) / 4, C), dim3(64, 4), 0, (hipStream_t)stream, src, acc, N, H, W,
+                   init, scale);
+    else
+        SSM_LAUNCH(frames_accumulate_kernel<1>, dim3((W + 63) / 64, (H + 3) / 4, C), dim3(64, 4), 0, (hipStream_t)stream, src, acc, N, H, W, init,
+                   scale);
+    return ssm::check_launch("ssm_frames_accumulate_fwd");
 }

@@ -21,6 +21,12 @@ an approximation of the default output, not parity.
 frames (24 -> 60, 25 -> 60, 23.976 -> 59.94 as --fps 60000:1001, 29.97 -> 25, --speed 0.3 or 3/10 for slow motion that is no integer
 factor).  --fps alone is speed 1, --speed alone keeps the input's rate in the header.  A frame that falls on an input frame is that
 frame's own bytes; pairs that get no frame are not run.  Neither goes together with --upsample_rate or --slowmo.
+
+--shutter DEG [--shutter_samples S], with --fps or --speed: every output frame is the mean of S sub-frames (default 8, a convention) spread
+over the first DEG / 360 of its interval, as a camera at the output rate with that shutter angle would have blurred it - 60 -> 24 with
+--shutter 180 instead of dropped frames that strobe, slow motion with a chosen amount of blur, or blurred / sharp frame pairs from
+high-rate footage.  The mean is taken of the gamma-coded R'G'B' values, as a frame-mixing filter does, not in linear light; every output
+frame then comes from the GPU, input frames are no longer passed through.  The header's rate is what it is without --shutter.
 """
 import argparse
 import configparser
@@ -63,6 +69,11 @@ def getargs(argv=None):
                         help="Output frame rate, written into the header as given (60, 60000:1001): any rate, not only a multiple of the input's.")
     parser.add_argument("--speed", type=_named(V.parse_speed), default=None, metavar="X",
                         help="Playback speed as a decimal or a fraction (0.25, 1/4, 3/10); below 1 is slow motion. Default 1.")
+    parser.add_argument("--shutter", type=_named(V.parse_shutter), default=None, metavar="DEG",
+                        help="Shutter angle in degrees, above 0 and at most 360 (180, 172.8, 90): every output frame is the mean of sub-frames "
+                             "over DEG / 360 of its interval. Needs --fps or --speed. Default: off.")
+    parser.add_argument("--shutter_samples", type=int, default=8, metavar="S",
+                        help="With --shutter: sub-frames per output frame (a convention, not a measured optimum). Default 8.")
     parser.add_argument("--matrix", choices=sorted(V.MATRICES), default=None, help="Y'CbCr matrix (default: bt709 from 720 rows up, else bt601).")
     parser.add_argument("--range", choices=sorted(V.RANGES), default=None, dest="color_range",
                         help="Code range (default: the header's XCOLORRANGE tag, else limited).")
@@ -79,9 +90,16 @@ def getargs(argv=None):
     args = parser.parse_args(argv)
     if args.fps is not None or args.speed is not None:
         if args.upsample_rate is not None or args.slowmo:
-            parser.error("--fps / --speed set the output's timeline themselves: they do not go together with --upsample_rate or --slowmo")
-    elif args.upsample_rate is None:
-        args.upsample_rate = 8
+            parser.error("--fps / --speed%s set the output's timeline themselves: they do not go together with --upsample_rate or --slowmo"
+                         % ("" if args.shutter is None else " / --shutter"))
+    else:
+        if args.shutter is not None:
+            parser.error("--shutter averages over the interval of an output frame of --fps / --speed: it needs one of them, and does not go "
+                         "together with --upsample_rate or --slowmo")
+        if args.upsample_rate is None:
+            args.upsample_rate = 8
+    if args.shutter is not None and args.shutter_samples < 1:
+        parser.error("--shutter_samples must be at least 1 (got %d)" % args.shutter_samples)
     return args
 
 
@@ -96,12 +114,15 @@ def main(argv=None, model=None):
     model = (model if model is not None else ssm.FullModel(config)).cuda().eval()
     timed = args.fps is not None or args.speed is not None
     vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate or 8, matrix=matrix, color_range=crange,
-                             flow_scale=args.flow_scale, tile=args.tile, halo=args.halo, blend=args.blend, target_rate=args.fps, speed=args.speed)
+                             flow_scale=args.flow_scale, tile=args.tile, halo=args.halo, blend=args.blend, target_rate=args.fps, speed=args.speed,
+                             shutter=args.shutter, shutter_samples=args.shutter_samples)
     with V.Y4MReader(args.input) as reader:
         if timed:
             rate = args.fps or reader.rate
             tl = vi.timeline(reader.rate)
             log.info("[%s] timeline: step = %s input frames per output frame, slots = %d times per pair", args.expt, tl.step, tl.slots)
+            if tl.samples > 1:
+                log.info("[%s] shutter: %s of the interval in %d samples", args.expt, tl.shutter, tl.samples)
         else:
             rate = V.output_rate(reader.rate, args.upsample_rate, args.slowmo)
         out_range = crange if crange is not None else (reader.color_range if reader.color_range is not None else V.LIMITED)

@@ -211,6 +211,7 @@ SIGNATURES = {
     "ssm_synthesize_fwd": (_c_int, [SsmView, SsmView, SsmView, _vp, SsmView, SsmView, _c_int, _c_int, _c_int, _vp]),
     "ssm_synthesize_upscaled_fwd": (_c_int, [SsmView, SsmView, _vp, SsmView, _c_int, _c_int, _c_int, _c_int, _vp]),
     "ssm_tile_stitch_fwd": (_c_int, [SsmView, SsmView] + [_c_int] * 14 + [_vp]),
+    "ssm_frames_accumulate_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _vp]),
 }
 
 _lib = None
@@ -391,6 +392,15 @@ def tile_stitch(tile, out, origin, core, seams, blend):
     check(load().ssm_tile_stitch_fwd(view_of(tile), view_of(out), N, C, wh, ww, out.shape[2], out.shape[3], origin[0], origin[1],
                                      core[0], core[1], core[2], core[3], seams, blend, stream_ptr()))
     return out
+
+
+def frames_accumulate(src, acc, init, scale):
+    """ssm_frames_accumulate_fwd: acc [1,C,H,W] = ((init ? src[0] : acc + src[0]) + src[1] + ... + src[N-1]) * scale for src [N,C,H,W],
+    summed in increasing n, one rounded fp32 operation per step (include/ssm_hip.h; yardstick: ssm_amd.video.accumulate_host)."""
+    N, C, H, W = src.shape
+    assert acc.dim() == 4 and tuple(acc.shape) == (1, C, H, W), "frames %s and accumulator %s disagree" % (tuple(src.shape), tuple(acc.shape))
+    check(load().ssm_frames_accumulate_fwd(view_of(src), view_of(acc), N, C, H, W, int(init), float(scale), stream_ptr()))
+    return acc
 
 
 def plane_dims(h, w):

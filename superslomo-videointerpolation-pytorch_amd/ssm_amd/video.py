@@ -12,9 +12,13 @@
 
   Timeline / PassPlanner  any output rate and speed: where each output frame sits on the input's clock, exactly (Fractions, closed form),
                           and the bookkeeping of the passes that follow it - VideoInterpolator(target_rate=, speed=)
+  accumulate_host /       the shutter: an output frame as the mean of `samples` sub-frames over the open part of its interval
+  ShutterPlanner          (Timeline(step, shutter=, samples=)), summed on the GPU in time order by ssm_frames_accumulate_fwd, whose numpy
+                          yardstick accumulate_host is; the bookkeeping of its passes - VideoInterpolator(shutter=, shutter_samples=)
 
-Out of scope: codecs, audio, more than 8 bits per sample, the recurrent configuration (N_FRAMES > 2); shutter / motion-blur integration
-and frame blending when the rate goes down, variable-rate input, speeds that change within a clip.
+Out of scope: codecs, audio, more than 8 bits per sample, the recurrent configuration (N_FRAMES > 2); shutter integration in linear
+light, shutter weights other than the box, a shutter centred on the frame's instant or open for longer than the frame interval,
+variable-rate input, speeds that change within a clip.
 """
 import ctypes
 import queue
@@ -178,6 +182,20 @@ def frames_to_yuv_host(x, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITE
 
     planes = [code(yf, iys, yoff, ylo, yhi), code(sub(cb), ics, coff, clo, chi), code(sub(cr), ics, coff, clo, chi)]
     return np.concatenate([p.reshape(n, -1) for p in planes], axis=1)
+
+
+def accumulate_host(frames, acc, init, scale):
+    """Yardstick of ssm_frames_accumulate_fwd: frames [N,C,H,W] float32 (numpy) summed into acc [1,C,H,W] or [C,H,W] float32, in place:
+    s = frames[0] if init else acc + frames[0]; s = s + frames[n] for n = 1 .. N-1; acc = s * scale - every step rounded to float32."""
+    frames = np.asarray(frames, dtype=_F)
+    assert acc.dtype == _F and frames.ndim == 4 and frames.shape[0] >= 1 and init in (0, 1, False, True)
+    dst = acc[0] if acc.ndim == 4 else acc
+    assert dst.shape == frames.shape[1:] and (acc.ndim == 3 or acc.shape[0] == 1)
+    s = frames[0].copy() if init else dst + frames[0]
+    for n in range(1, frames.shape[0]):
+        s = s + frames[n]
+    dst[...] = s * _F(scale)
+    return acc
 
 
 # ---- the kernels -------------------------------------------------------------------------------------------------------------------
@@ -408,6 +426,18 @@ def parse_speed(text):
     return s
 
 
+def parse_shutter(text):
+    """A shutter angle in degrees, "180", "172.8" or "90" (or a number, or a Fraction) -> the open fraction angle / 360 as an exact
+    Fraction in (0, 1]; anything else is a ValueError naming the value."""
+    try:
+        deg = Fraction(text.strip() if isinstance(text, str) else text)
+    except (ValueError, TypeError, ZeroDivisionError):
+        raise ValueError("a shutter angle is written in degrees as a decimal or a fraction, e.g. 180, 172.8 or 90 (got %r)" % (text,)) from None
+    if not 0 < deg <= 360:
+        raise ValueError("a shutter angle lies above 0 and at most at 360 degrees (got %r)" % (text,))
+    return deg / 360
+
+
 def timeline_step(in_rate, target_rate=None, speed=None):
     """step = speed * in_rate / out_rate as a Fraction: how far the input clock moves per output frame.  target_rate None: the input's
     rate; speed None: 1."""
@@ -427,9 +457,20 @@ class Timeline:
     bit for bit.
 
     slots: the most synthesised frames any one pair gets - the engine's times per pair.  step = a/b in lowest terms repeats every b
-    outputs (a inputs), so one period decides it.  A speed that changes within a clip would replace `step` by a function of k here."""
+    outputs (a inputs), so one period decides it.  A speed that changes within a clip would replace `step` by a function of k here.
 
-    def __init__(self, step, max_slots=None):
+    The shutter (include/ssm_hip.h spells the definition): shutter = sigma in (0, 1], the open fraction of the output interval, and
+    samples = S.  Output frame k is the mean of S sub-frames at tau(k, j) = k step + j d, d = sigma step / S, j = 0 .. S - 1, and exists
+    iff its last one does: tau(k, S - 1) <= n - 1.  With sigma = p/q in lowest terms every sample sits on the uniform grid g = step / (q S):
+    tau(k, j) = (k q S + j p) g, and because (S - 1) p < q S the samples of output k all come before those of output k + 1 - the samples
+    in time order are the (k, j) in lexicographic order, sample number r is (k, j) = divmod(r, S).  The closed forms below count grid
+    points.  S = 1 is the timeline above, whatever the shutter: same outputs, counts, times and slots, of the same types.  With S > 1
+      outputs(n), feed()   deliver one tuple of S (i, t) per output frame instead of one (i, t)
+      times(i)             [(t, k, j)]: each synthesised sample with the output and the place in it that it belongs to
+      on_frame(i)          the (k, j) of the sample that is input frame i itself, or None
+      slots                the most synthesised SAMPLES any one pair gets."""
+
+    def __init__(self, step, max_slots=None, shutter=None, samples=1):
         try:
             step = Fraction(step)
         except (ValueError, TypeError, ZeroDivisionError):
@@ -439,14 +480,73 @@ class Timeline:
         self.step, self.a, self.b = step, step.numerator, step.denominator
         if min(self.a, self.b) > MAX_PERIOD:
             raise ValueError("step %s repeats only every %d frames (more than %d): round the rate or the speed" % (step, min(self.a, self.b), MAX_PERIOD))
-        if self.a <= self.b:          # one period is a input pairs ...
+        try:
+            sigma = Fraction(1) if shutter is None else Fraction(shutter.strip() if isinstance(shutter, str) else shutter)
+        except (ValueError, TypeError, ZeroDivisionError):
+            raise ValueError("the shutter must be a number or a fraction (got %r)" % (shutter,)) from None
+        if not 0 < sigma <= 1:
+            raise ValueError("the shutter is the open fraction of the output frame's interval, in (0, 1] (got %s)" % sigma)
+        if isinstance(samples, bool) or int(samples) != samples or samples < 1:
+            raise ValueError("the shutter takes a whole number of samples, at least 1 (got %r)" % (samples,))
+        self.shutter, self.samples = sigma, int(samples)
+        if self.samples > 1:          # the grid: tau = m * gn / gd for m = k * qs + j * p
+            self.p, self.qs = sigma.numerator, sigma.denominator * self.samples
+            g = step / self.qs
+            self.gn, self.gd = g.numerator, g.denominator
+            self.slots = self._shutter_slots()
+        elif self.a <= self.b:        # one period is a input pairs ...
             self.slots = max(self.count(i) for i in range(self.a))
         else:                         # ... or b outputs, whichever is the shorter walk; here a pair gets one frame at the most
             self.slots = 1 if self.b > 1 else 0
         if max_slots is not None and self.slots > max_slots:
+            if self.samples > 1:
+                raise ValueError("step %s with a shutter of %s in %d samples puts %d sub-frames between two input frames; the plan takes at "
+                                 "most %d (the largest upsample_rate - 1 at this pairs_per_batch)" % (step, sigma, self.samples, self.slots, max_slots))
             raise ValueError("step %s puts %d frames between two input frames; the plan takes at most %d (the largest upsample_rate - 1 at "
                              "this pairs_per_batch)" % (step, self.slots, max_slots))
         self._fed = self._k = 0
+
+    def _shutter_slots(self):
+        """The pattern of samples repeats every b outputs = a input frames, like the outputs themselves (every output carries the same
+        offsets j d).  Walk the shorter side: a pairs through the closed form, or the b * S samples of a period in time order."""
+        if self.a <= self.b:
+            return max(self.count(i) for i in range(self.a))
+        best = run = 0
+        pair = -1
+        for k in range(self.b):
+            for i, t in self.samples_of(k):
+                if not t:
+                    continue
+                run = run + 1 if i == pair else 1
+                pair, best = i, max(best, run)
+        return best
+
+    def sample(self, k, j):
+        """(i, t) of sub-frame j of output frame k."""
+        if self.samples == 1:
+            return self.at(k)
+        i, r = divmod((k * self.qs + j * self.p) * self.gn, self.gd)
+        return i, Fraction(r, self.gd)
+
+    def samples_of(self, k):
+        """The S (i, t) whose mean output frame k is, in time order."""
+        return [self.sample(k, j) for j in range(self.samples)]
+
+    def _upto(self, x, inclusive):
+        """Samples at tau < x (or <= x) for an integer x: the grid points m <= mmax with m = k * qs + j * p, j < S."""
+        mmax = (x * self.gd) // self.gn if inclusive else (x * self.gd - 1) // self.gn
+        if mmax < 0:
+            return 0
+        k, r = divmod(mmax, self.qs)
+        return k * self.samples + min(self.samples, r // self.p + 1)
+
+    def on_frame(self, i):
+        """(k, j) of the sample that is input frame i itself (t == 0), or None."""
+        if self.samples == 1:
+            k, r = divmod(i * self.b, self.a)
+            return None if r else (k, 0)
+        r = self._upto(i, False)
+        return divmod(r, self.samples) if self._upto(i, True) > r else None
 
     def at(self, k):
         """(i, t) of output frame k."""
@@ -454,19 +554,30 @@ class Timeline:
         return i, Fraction(r, self.b)
 
     def n_outputs(self, n):
-        """floor((n - 1) / step) + 1 output frames for n input frames."""
-        return ((n - 1) * self.b) // self.a + 1 if n > 0 else 0
+        """floor((n - 1) / step) + 1 output frames for n input frames; with a shutter, the k whose last sample is at n - 1 or before."""
+        if n <= 0:
+            return 0
+        if self.samples > 1:
+            return max(0, (((n - 1) * self.gd) // self.gn - (self.samples - 1) * self.p) // self.qs + 1)
+        return ((n - 1) * self.b) // self.a + 1
 
     def outputs(self, n):
-        """[(i, t)] of every output frame of an n-frame clip."""
+        """[(i, t)] of every output frame of an n-frame clip; with a shutter, [the tuple of its S (i, t)]."""
+        if self.samples > 1:
+            return [tuple(self.samples_of(k)) for k in range(self.n_outputs(n))]
         return [self.at(k) for k in range(self.n_outputs(n))]
 
     def count(self, i):
-        """Synthesised frames of pair (i, i + 1): the k with i < k * step < i + 1."""
+        """Synthesised frames (with a shutter: samples) of pair (i, i + 1): those with i < tau < i + 1."""
+        if self.samples > 1:
+            return self._upto(i + 1, False) - self._upto(i, True)
         return -((-(i + 1) * self.b) // self.a) - (i * self.b) // self.a - 1
 
     def times(self, i):
-        """The t of pair (i, i + 1)'s synthesised frames, increasing."""
+        """The t of pair (i, i + 1)'s synthesised frames, increasing; with a shutter, (t, k, j) per synthesised sample."""
+        if self.samples > 1:
+            r0 = self._upto(i, True)
+            return [(self.sample(*kj)[1],) + kj for kj in (divmod(r0 + m, self.samples) for m in range(self.count(i)))]
         k0 = (i * self.b) // self.a + 1
         return [self.at(k0 + j)[1] for j in range(self.count(i))]
 
@@ -477,7 +588,7 @@ class Timeline:
     def feed(self, end=False):
         """The incremental form, for a pipe whose length nobody knows: call it once per frame read and once more, with end=True, at
         the end of the input.  Returns the [(i, t)] that have just become computable - an output needs frame i + 1 read, or frame i
-        when t == 0 - so the calls of an n-frame clip return outputs(n) piece by piece.  The call at the end returns nothing (what is
+        when t == 0, of its last sample - so the calls of an n-frame clip return outputs(n) piece by piece.  The call at the end returns nothing (what is
         left needs a frame that never came) and rewinds the timeline for the next clip."""
         if end:
             self._fed = self._k = 0
@@ -485,10 +596,10 @@ class Timeline:
         self._fed += 1
         out = []
         while True:
-            i, t = self.at(self._k)
+            i, t = self.sample(self._k, self.samples - 1)          # the last sample decides: frame ceil(tau(k, S - 1)) has been read
             if i + (1 if t else 0) >= self._fed:
                 return out
-            out.append((i, t))
+            out.append(tuple(self.samples_of(self._k)) if self.samples > 1 else (i, t))
             self._k += 1
 
 
@@ -546,6 +657,105 @@ class PassPlanner:
         return self._close()
 
 
+# One output is open at a time.  The samples in time order are the (k, j) in lexicographic order (Timeline), the accumulate calls follow
+# that order within a pass and - through the event a pass waits for before its first one - from pass to pass, and an output is egressed
+# right after its last call: the first call of output k + 1 (init = 1) comes after the egress of output k.  So between an output's first
+# call and its egress no other output is touched, and the ring of accumulators needs this many entries.
+OPEN_OUTPUTS = 1
+
+
+class ShutterPlanner:
+    """The bookkeeping of VideoInterpolator._run_shutter, free of the GPU.  The caller reads each frame into row `rows` of the open ring
+    slot's input buffer and calls frame(); that returns None, or the closed pass as (rows, carry, pairs, calls, done):
+      rows    the slot's first `rows` payloads go up and are ingested, in one piece, into rows 1 .. rows of the pass's planes
+      carry   row 0 of the pass's planes is the last row of the pass before (that row's number, or None): the left frame of the first pair
+      pairs   [(row of the left frame's planes, row of the right frame's, [fp32 times])] of at most pairs_per_batch pairs; pair p's
+              synthesised frames are rows p * slots .. of the engine's output
+      calls   the accumulate calls in time order: (src, first, count, k, init, last) with src = "frame" (row `first` of the planes, count
+              1: a sample that is an input frame) or "interp" (`count` rows of the engine's output from row `first`: consecutive samples
+              of one pair and one output); init on the first call of output k, last on its last: scale = fp32(1 / S), then egress
+      done    the outputs that `calls` completes, increasing k: row o of the pass's output buffer is done[o]
+    end() closes what is open.  Every frame that a sample needs - it is one, or it is the left or right frame of a pair that has one -
+    takes a row, once; any other frame is read over by the next.  A pair runs in the pass that holds its right frame; its left frame
+    is a row of that pass or `carry`.  A frame that is up only as a left frame stays in one pass with its right neighbour, so that it does
+    not go up if that neighbour never comes: a pass closes at pairs_per_batch pairs, at cap rows, or one row early when no such frame
+    waits.  Samples past the end of a clip whose output never completes are run and dropped: a pipe's length is not known ahead."""
+
+    def __init__(self, tl, pairs_per_batch, cap):
+        assert cap >= 2 and tl.samples > 1
+        self.tl, self.pb, self.cap = tl, pairs_per_batch, cap
+        self.max_done = (pairs_per_batch * tl.slots + cap + tl.samples - 1) // tl.samples      # of a run of that many samples, those with j = S - 1
+        self.f = 0                 # frames read
+        self.last = (-1, None)     # the newest frame that has planes on the device, and their row in the pass before
+        self._rank = 0             # samples handed out: sample number r is (k, j) = divmod(r, S)
+        self._open_k = None        # the output between its first call and its egress
+        self._open()
+
+    def _open(self):
+        self.rows, self.carry, self.pairs, self.calls, self.done, self._row_of = 0, None, [], [], [], {}
+
+    def _close(self):
+        if self.rows:
+            self.last = (self.last[0], self.rows)
+        assert len(self.done) <= self.max_done and len(self.pairs) <= self.pb
+        out = (self.rows, self.carry, self.pairs, self.calls, self.done)
+        self._open()
+        return out
+
+    def _call(self, src, first, samples):
+        """One accumulate call over `samples` = consecutive (k, j) of one output."""
+        S = self.tl.samples
+        k = samples[0][0]
+        for kj in samples:
+            assert kj == divmod(self._rank, S) and kj[0] == k, "samples are handed out in time order, none left out"
+            self._rank += 1
+        init, last = samples[0][1] == 0, samples[-1][1] == S - 1
+        if init:
+            assert self._open_k is None, "at most OPEN_OUTPUTS = 1 output is open"
+            self._open_k = k
+        assert self._open_k == k
+        self.calls.append((src, first, len(samples), k, init, last))
+        if last:
+            self.done.append(k)
+            self._open_k = None
+
+    def frame(self):
+        tl, f, slots = self.tl, self.f, self.tl.slots
+        synth = tl.times(f - 1) if f else []
+        here = tl.on_frame(f)
+        if synth or here is not None or tl.count(f) > 0:
+            self.rows += 1
+            self._row_of[f] = self.rows
+            if synth:                    # pair (f - 1, f): its left frame has planes, in this pass or as the last row of the one before
+                if f - 1 not in self._row_of:
+                    assert self.last[0] == f - 1 and self.last[1] is not None and self.carry is None
+                    self.carry = self.last[1]
+                    self._row_of[f - 1] = 0
+                p = len(self.pairs)
+                self.pairs.append((self._row_of[f - 1], self.rows, [Timeline.t32(t) for t, _, _ in synth]))
+                m = 0
+                while m < len(synth):          # one call per output the pair contributes to
+                    e = m
+                    while e < len(synth) and synth[e][1] == synth[m][1]:
+                        e += 1
+                    self._call("interp", p * slots + m, [kj[1:] for kj in synth[m:e]])
+                    m = e
+            if here is not None:
+                self._call("frame", self.rows, [here])
+            self.last = (f, None)
+        waits = tl.count(f) > 0 and not synth and here is None          # up only as a left frame: it goes up with its right neighbour
+        self.f += 1
+        if len(self.pairs) == self.pb or self.rows == self.cap or (self.rows == self.cap - 1 and not waits):
+            return self._close()
+        return None
+
+    def end(self):
+        used = max([right for _, right, _ in self.pairs] + [first for src, first, _, _, _, _ in self.calls if src == "frame"], default=0)
+        assert used >= self.rows - 1          # only the last row can be a left frame whose right neighbour never came: it stays down
+        self.rows = used
+        return self._close()
+
+
 # ---- the streamed loop -------------------------------------------------------------------------------------------------------------
 class VideoInterpolator:
     """reader -> (upsample_rate - 1) frames between every two input frames -> writer, streamed; or, with target_rate / speed, the frames
@@ -558,13 +768,18 @@ class VideoInterpolator:
     Host and device memory are fixed by the frame size, n_streams and pairs_per_batch."""
 
     def __init__(self, model, cfg, upsample_rate=8, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
-                 tile=None, halo=256, blend=32, target_rate=None, speed=None):
+                 tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8):
         """target_rate = (num, den) and / or speed (a Fraction, or what Fraction() takes; 1/4 is four times slower): the output follows
         Timeline(speed * input rate / target_rate) instead of the fixed grid of upsample_rate, which is then not used (see
         _run_timeline); with both None nothing changes.  flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
         reference's output, not parity); the canvas is then padded to multiples of 32 * flow_scale.  tile = (th, tw): the tiled mode of
         FullModel.interpolate (windows of tile + halo stitched with a cross-fade of `blend`; an approximation of the untiled output,
-        not parity)."""
+        not parity).
+        shutter (a Fraction in (0, 1], or what Fraction() takes: the open fraction of the output frame's interval, 1/2 = 180 degrees),
+        beside target_rate or speed: every output frame is the mean of shutter_samples sub-frames over that part of its interval
+        (Timeline, _run_shutter).  Like the command line's --shutter it needs one of the two, since it averages over the interval of
+        their timeline; speed=1 is the input's own rate with blur.  The 8 samples of the default are a convention, not backed by a
+        measurement of quality.  shutter_samples = 1, or shutter None, is the loop without a shutter."""
         from .coarse import check_scale
         from .tiles import check_args
         self.flow_scale = check_scale(flow_scale)
@@ -587,7 +802,13 @@ class VideoInterpolator:
         self._pipe = None
         self.target_rate = None if target_rate is None else parse_rate("%s:%s" % tuple(target_rate))
         self.speed = None if speed is None else parse_speed(speed)
+        self.shutter, self.samples = (None, 1) if shutter is None else (shutter, shutter_samples)
+        if shutter is not None:
+            Timeline(1, shutter=shutter, samples=shutter_samples)          # refuses a bad value by name, here rather than at the first clip
         self.timed = target_rate is not None or speed is not None
+        if shutter is not None and not self.timed:
+            raise ValueError("a shutter averages over the interval of an output frame of target_rate / speed: give one of them (speed=1 "
+                             "keeps the input's rate)")
 
     def canvas(self, h, w):
         """(Hp, Wp) of the planes an h x w clip runs on: padded_dims to multiples of 32 * flow_scale."""
@@ -595,7 +816,8 @@ class VideoInterpolator:
 
     def timeline(self, in_rate):
         """The Timeline of a clip at `in_rate` (num, den); refuses a step whose slots the plan would not take."""
-        return Timeline(timeline_step(in_rate, self.target_rate, self.speed), max_slots=MAX_STAGE2_BATCH // self.pb)
+        return Timeline(timeline_step(in_rate, self.target_rate, self.speed), max_slots=MAX_STAGE2_BATCH // self.pb, shutter=self.shutter,
+                        samples=self.samples)
 
     def _pipeline(self, hp, wp, dev, n_t=None):
         import os
@@ -616,9 +838,9 @@ class VideoInterpolator:
     @torch.no_grad()
     def run(self, reader, writer):
         """Returns the number of frames written: (n - 1) * upsample_rate + 1 for n input frames (with target_rate / speed:
-        floor((n - 1) / step) + 1)."""
+        floor((n - 1) / step) + 1; with a shutter: Timeline.n_outputs(n))."""
         if self.timed:
-            return self._run_timeline(reader, writer)
+            return self._run_shutter(reader, writer) if self.samples > 1 else self._run_timeline(reader, writer)
         from .evaluation import t_values
         h, w, siting, fb = reader.height, reader.width, reader.siting, reader.frame_bytes
         if (writer.height, writer.width, writer.siting) != (h, w, siting):
@@ -824,6 +1046,143 @@ class VideoInterpolator:
                 j += 1
             work.put((r, order if not failure else [], bool(pairs) and not failure))
             written += len(order)
+
+        try:
+            while not failure:
+                if r is None:
+                    r = free.get()
+                if failure or not reader.read_frame_into(np_in[r][plan.rows]):
+                    break
+                closed = plan.frame()
+                if closed is not None:
+                    issue(r, *closed)
+                    r = None
+            if r is not None:
+                issue(r, *plan.end())
+            if plan.f == 0 and not failure:
+                raise Y4MError("the Y4M stream holds no frame")
+        finally:
+            work.put(None)
+            th.join()
+            torch.cuda.synchronize(dev)
+        if failure:
+            raise failure[0]
+        return written
+
+    @torch.no_grad()
+    def _run_shutter(self, reader, writer):
+        """run() with a shutter: output frame k is the mean of the S = shutter_samples sub-frames of Timeline(step, shutter=, samples=),
+        summed in time order into an fp32 accumulator by ssm_frames_accumulate_fwd and egressed from it - every output, also one whose
+        samples are all input frames.
+
+        A pass (bookkeeping: ShutterPlanner) uploads and ingests, in one piece each, the frames it holds that a sample needs; copies the
+        planes of up to pairs_per_batch pairs that get a sample side by side; runs them at their sample times padded to `slots`; and
+        then makes its accumulate calls in time order - one per pair and output the pair contributes to, over that pair's consecutive
+        frames of that output, and one of N = 1 on the ingested planes of a frame that is a sample itself - with init = 1 on an output's
+        first call and scale = fp32(1 / S) on its last, after which the output is egressed from the accumulator and copied back in the
+        same pass.  An output may span pairs, passes and streams: just before its first accumulate call a pass waits for the event that
+        the pass before recorded after its last accumulate and egress, so the engines of neighbouring passes still overlap, only these
+        short tails are serialised, and the result depends on nothing but the time order.  One output is open at a time (OPEN_OUTPUTS),
+        which sizes the ring of accumulators.  Memory is fixed by the frame size, n_streams, pairs_per_batch, slots and that bound."""
+        h, w, siting, fb = reader.height, reader.width, reader.siting, reader.frame_bytes
+        if (writer.height, writer.width, writer.siting) != (h, w, siting):
+            raise ValueError("reader and writer disagree on the frame format")
+        matrix = default_matrix(h) if self.matrix is None else self.matrix
+        crange = self.color_range if self.color_range is not None else (reader.color_range if reader.color_range is not None else LIMITED)
+        dev = next(self.model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
+        tl = self.timeline(reader.rate)
+        slots, pb, n = tl.slots, self.pb, self.n_streams
+        mult = 32 * self.flow_scale
+        hp, wp = self.canvas(h, w)
+        pipe = self._pipeline(hp, wp, dev, slots) if slots else None          # a step whose samples are all input frames: nothing to synthesise
+        streams = pipe.streams if pipe is not None else [torch.cuda.Stream(dev) for _ in range(n)]
+        depth, cap = n + 2, 2 * pb + 2
+        plan = ShutterPlanner(tl, pb, cap)
+        scale = np.float32(1.0 / tl.samples)
+        host_in = [torch.empty(cap, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
+        host_out = [torch.empty(plan.max_done, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
+        host_t = [torch.full((pb * max(slots, 1),), 0.5, dtype=torch.float32).pin_memory() for _ in range(depth)]
+        np_in, np_out, np_t = [t.numpy() for t in host_in], [t.numpy() for t in host_out], [t.numpy() for t in host_t]
+        done = [torch.cuda.Event() for _ in range(depth)]
+        dev_in = [torch.empty(cap, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
+        dev_out = [torch.empty(plan.max_done, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
+        dev_t = [torch.empty(pb * max(slots, 1), dtype=torch.float32, device=dev) for _ in range(n)]
+        planes = [torch.zeros(cap + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [carried frame | the pass's frames]
+        sides = [torch.zeros(pb, 2, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]         # [pair][left | right]
+        acc = torch.zeros(OPEN_OUTPUTS, 3, hp, wp, dtype=torch.float32, device=dev)
+        ingested, summed = [torch.cuda.Event() for _ in range(n)], [torch.cuda.Event() for _ in range(n)]
+        torch.cuda.synchronize(dev)
+
+        free, work, failure = queue.Queue(), queue.Queue(), []
+        for r in range(depth):
+            free.put(r)
+
+        def drain():
+            while True:
+                item = work.get()
+                if item is None:
+                    return
+                r, count, on_gpu = item
+                try:
+                    if not failure:
+                        if on_gpu:
+                            done[r].synchronize()
+                        for o in range(count):
+                            writer.write_frame(np_out[r][o])
+                except BaseException as e:          # noqa: BLE001 - handed to the caller's thread; keep releasing slots
+                    failure.append(e)
+                free.put(r)
+
+        def submit(j, r, rows, carry, pairs, calls):
+            """Pass j on ring slot r; the arguments are ShutterPlanner's."""
+            k, kprev = j % n, (j - 1) % n
+            st = streams[k]
+            with torch.cuda.stream(st):
+                if j:
+                    st.wait_event(ingested[kprev])          # the carried frame; and pass j - n + 1 is done with planes[k]
+                dev_in[k][:rows].copy_(host_in[r][:rows], non_blocking=True)
+                if carry is not None:
+                    planes[k][0].copy_(planes[kprev][carry])
+                frames_from_yuv(dev_in[k][:rows], h, w, siting, matrix, crange, self.cfg, True, out=planes[k][1:1 + rows], multiple=mult)
+                for p, (left, right, ts) in enumerate(pairs):
+                    sides[k][p, 0].copy_(planes[k][left])
+                    sides[k][p, 1].copy_(planes[k][right])
+                    np_t[r][p * slots:p * slots + len(ts)] = ts
+                    np_t[r][p * slots + len(ts):(p + 1) * slots] = ts[-1]
+                if pairs:
+                    np_t[r][len(pairs) * slots:] = np_t[r][len(pairs) * slots - 1]
+                    dev_t[k].copy_(host_t[r], non_blocking=True)          # with the payloads, ahead of the kernels: see DESIGN 3.12
+                ingested[k].record()
+                frames = pipe.engines[k].run(sides[k].view(pb, 6, hp, wp), dev_t[k], False) if pairs else None
+                if j:
+                    st.wait_event(summed[kprev])          # the accumulator: every call and egress of the passes before, in time order
+                o = 0
+                for src, first, count, ko, init, last in calls:
+                    a = acc[ko % OPEN_OUTPUTS:ko % OPEN_OUTPUTS + 1]
+                    hb.frames_accumulate(planes[k][first:first + 1] if src == "frame" else frames[first:first + count], a, 1 if init else 0,
+                                      scale if last else 1.0)
+                    if last:
+                        frames_to_yuv(a, h, w, siting, matrix, crange, self.cfg, out=dev_out[k][o:o + 1])
+                        host_out[r][o:o + 1].copy_(dev_out[k][o:o + 1], non_blocking=True)
+                        o += 1
+                summed[k].record()
+                done[r].record()
+
+        th = threading.Thread(target=drain, name="y4m-writer", daemon=True)
+        th.start()
+        written = j = 0          # frames written, passes issued
+        r = None
+
+        def issue(r, rows, carry, pairs, calls, finished):
+            nonlocal written, j
+            on_gpu = rows > 0 and not failure
+            if on_gpu:
+                submit(j, r, rows, carry, pairs, calls)
+                j += 1
+            work.put((r, len(finished) if on_gpu else 0, on_gpu))
+            written += len(finished)
 
         try:
             while not failure:
