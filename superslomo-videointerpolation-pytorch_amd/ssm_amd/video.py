@@ -9,6 +9,8 @@
   frames_to_yuv           convention (scripts/visualize_interpolation.py:61-88,223-268)
   VideoInterpolator       the streamed loop: every leg of a pass (H2D, ingest, the pair pipeline, egress, D2H) is queued on the pass's HIP
                           stream, a writer thread drains a ring of pinned buffers in order; memory does not depend on the clip's length
+  PassRing / read_passes  what its three modes (fixed grid, timeline, shutter) share beside the prologue: the ring with its writer thread and
+  / upload_times          failure protocol (no GPU in it), the planners' read loop, the fill and upload of a pass's times
 
   Timeline / PassPlanner  any output rate and speed: where each output frame sits on the input's clock, exactly (Fractions, closed form),
                           and the bookkeeping of the passes that follow it - VideoInterpolator(target_rate=, speed=)
@@ -20,6 +22,7 @@ Out of scope: codecs, audio, more than 8 bits per sample, the recurrent configur
 light, shutter weights other than the box, a shutter centred on the frame's instant or open for longer than the frame interval,
 variable-rate input, speeds that change within a clip.
 """
+import collections
 import ctypes
 import queue
 import re
@@ -464,7 +467,8 @@ class Timeline:
     iff its last one does: tau(k, S - 1) <= n - 1.  With sigma = p/q in lowest terms every sample sits on the uniform grid g = step / (q S):
     tau(k, j) = (k q S + j p) g, and because (S - 1) p < q S the samples of output k all come before those of output k + 1 - the samples
     in time order are the (k, j) in lexicographic order, sample number r is (k, j) = divmod(r, S).  The closed forms below count grid
-    points.  S = 1 is the timeline above, whatever the shutter: same outputs, counts, times and slots, of the same types.  With S > 1
+    points, with or without a shutter: at S = 1 the grid is g = step / q and tau(k, 0) = k q g = k step, the timeline above whatever the
+    shutter.  Only the shape of what comes back differs.  With S > 1
       outputs(n), feed()   deliver one tuple of S (i, t) per output frame instead of one (i, t)
       times(i)             [(t, k, j)]: each synthesised sample with the output and the place in it that it belongs to
       on_frame(i)          the (k, j) of the sample that is input frame i itself, or None
@@ -489,15 +493,10 @@ class Timeline:
         if isinstance(samples, bool) or int(samples) != samples or samples < 1:
             raise ValueError("the shutter takes a whole number of samples, at least 1 (got %r)" % (samples,))
         self.shutter, self.samples = sigma, int(samples)
-        if self.samples > 1:          # the grid: tau = m * gn / gd for m = k * qs + j * p
-            self.p, self.qs = sigma.numerator, sigma.denominator * self.samples
-            g = step / self.qs
-            self.gn, self.gd = g.numerator, g.denominator
-            self.slots = self._shutter_slots()
-        elif self.a <= self.b:        # one period is a input pairs ...
-            self.slots = max(self.count(i) for i in range(self.a))
-        else:                         # ... or b outputs, whichever is the shorter walk; here a pair gets one frame at the most
-            self.slots = 1 if self.b > 1 else 0
+        self.p, self.qs = sigma.numerator, sigma.denominator * self.samples          # the grid: tau = m * gn / gd for m = k * qs + j * p
+        g = step / self.qs
+        self.gn, self.gd = g.numerator, g.denominator
+        self.slots = self._slots()
         if max_slots is not None and self.slots > max_slots:
             if self.samples > 1:
                 raise ValueError("step %s with a shutter of %s in %d samples puts %d sub-frames between two input frames; the plan takes at "
@@ -506,11 +505,14 @@ class Timeline:
                              "this pairs_per_batch)" % (step, self.slots, max_slots))
         self._fed = self._k = 0
 
-    def _shutter_slots(self):
-        """The pattern of samples repeats every b outputs = a input frames, like the outputs themselves (every output carries the same
-        offsets j d).  Walk the shorter side: a pairs through the closed form, or the b * S samples of a period in time order."""
+    def _slots(self):
+        """The pattern of samples repeats every b outputs = a input frames (every output carries the same offsets j d).  Walk the shorter
+        side: a pairs through the closed form, or the b * S samples of a period in time order - which without a shutter (S = 1) needs no
+        walk: outputs more than a frame apart, a pair gets one at the most, and gets one unless every output is an input frame."""
         if self.a <= self.b:
             return max(self.count(i) for i in range(self.a))
+        if self.samples == 1:
+            return 1 if self.b > 1 else 0
         best = run = 0
         pair = -1
         for k in range(self.b):
@@ -523,8 +525,6 @@ class Timeline:
 
     def sample(self, k, j):
         """(i, t) of sub-frame j of output frame k."""
-        if self.samples == 1:
-            return self.at(k)
         i, r = divmod((k * self.qs + j * self.p) * self.gn, self.gd)
         return i, Fraction(r, self.gd)
 
@@ -542,24 +542,18 @@ class Timeline:
 
     def on_frame(self, i):
         """(k, j) of the sample that is input frame i itself (t == 0), or None."""
-        if self.samples == 1:
-            k, r = divmod(i * self.b, self.a)
-            return None if r else (k, 0)
         r = self._upto(i, False)
         return divmod(r, self.samples) if self._upto(i, True) > r else None
 
     def at(self, k):
-        """(i, t) of output frame k."""
-        i, r = divmod(k * self.a, self.b)
-        return i, Fraction(r, self.b)
+        """(i, t) of output frame k: of its first sample."""
+        return self.sample(k, 0)
 
     def n_outputs(self, n):
         """floor((n - 1) / step) + 1 output frames for n input frames; with a shutter, the k whose last sample is at n - 1 or before."""
         if n <= 0:
             return 0
-        if self.samples > 1:
-            return max(0, (((n - 1) * self.gd) // self.gn - (self.samples - 1) * self.p) // self.qs + 1)
-        return ((n - 1) * self.b) // self.a + 1
+        return max(0, (((n - 1) * self.gd) // self.gn - (self.samples - 1) * self.p) // self.qs + 1)
 
     def outputs(self, n):
         """[(i, t)] of every output frame of an n-frame clip; with a shutter, [the tuple of its S (i, t)]."""
@@ -569,17 +563,15 @@ class Timeline:
 
     def count(self, i):
         """Synthesised frames (with a shutter: samples) of pair (i, i + 1): those with i < tau < i + 1."""
-        if self.samples > 1:
-            return self._upto(i + 1, False) - self._upto(i, True)
-        return -((-(i + 1) * self.b) // self.a) - (i * self.b) // self.a - 1
+        return self._upto(i + 1, False) - self._upto(i, True)
 
     def times(self, i):
         """The t of pair (i, i + 1)'s synthesised frames, increasing; with a shutter, (t, k, j) per synthesised sample."""
+        r0 = self._upto(i, True)
+        kjs = [divmod(r0 + m, self.samples) for m in range(self.count(i))]
         if self.samples > 1:
-            r0 = self._upto(i, True)
-            return [(self.sample(*kj)[1],) + kj for kj in (divmod(r0 + m, self.samples) for m in range(self.count(i)))]
-        k0 = (i * self.b) // self.a + 1
-        return [self.at(k0 + j)[1] for j in range(self.count(i))]
+            return [(self.sample(*kj)[1],) + kj for kj in kjs]
+        return [self.sample(*kj)[1] for kj in kjs]
 
     @staticmethod
     def t32(t):
@@ -604,9 +596,9 @@ class Timeline:
 
 
 class PassPlanner:
-    """The bookkeeping of VideoInterpolator._run_timeline, free of the GPU: which frames of the input stay in a ring slot's `cap` rows,
-    which pairs a pass runs, and what the writer takes from the slot in the timeline's order.  The caller reads each frame into row
-    `rows` of the open slot and calls frame(); that returns None, or the closed slot as (order, pairs):
+    """The bookkeeping of the timeline mode (_run_timeline), free of the GPU: which frames of the input stay in a ring slot's `cap` rows,
+    which pairs a pass runs, and what the writer takes from the slot in the timeline's order.  read_passes reads each frame
+    into row `rows` of the open slot and calls frame(); that returns None, or the closed slot as (order, pairs):
       order   [("interp", row of the slot's output buffer) | ("orig", row of its input buffer)], by increasing k
       pairs   [(row of the pair's first new payload, own_left, [fp32 times])] of at most pairs_per_batch pairs that run; pair p's frames
               are rows p * slots .. of the output buffer.  own_left: the pair's left frame is that row and its right frame the next
@@ -665,8 +657,8 @@ OPEN_OUTPUTS = 1
 
 
 class ShutterPlanner:
-    """The bookkeeping of VideoInterpolator._run_shutter, free of the GPU.  The caller reads each frame into row `rows` of the open ring
-    slot's input buffer and calls frame(); that returns None, or the closed pass as (rows, carry, pairs, calls, done):
+    """The bookkeeping of the shutter mode (_run_shutter), free of the GPU.  read_passes reads each frame into row `rows` of the
+    open ring slot's input buffer and calls frame(); that returns None, or the closed pass as (rows, carry, pairs, calls, done):
       rows    the slot's first `rows` payloads go up and are ingested, in one piece, into rows 1 .. rows of the pass's planes
       carry   row 0 of the pass's planes is the last row of the pass before (that row's number, or None): the left frame of the first pair
       pairs   [(row of the left frame's planes, row of the right frame's, [fp32 times])] of at most pairs_per_batch pairs; pair p's
@@ -757,6 +749,100 @@ class ShutterPlanner:
 
 
 # ---- the streamed loop -------------------------------------------------------------------------------------------------------------
+class PassRing:
+    """The ring of `depth` slots between the loop that queues passes and the thread that writes what they made, and the loop's failure
+    protocol.  Free of the GPU: an event is anything with synchronize(), the writer anything with write_frame(buf).
+
+    The producer take()s a free slot, fills it and hand()s it over with the event that says its rows are there (None: nothing was queued
+    on the GPU for it) and the row buffers to write, in order; a slot of None is an item that holds no slot (frame 0 of the fixed grid,
+    written from a buffer of its own).  The thread (daemon, `y4m-writer`) waits for the event, writes the rows and frees the slot, item by
+    item in the order handed over.  After the first exception on the thread nothing more is written and every slot handed over still
+    comes back, so the producer never blocks in take(); it looks at `failure` and stops reading and submitting.  close() - leaving the
+    `with` block - ends the thread, calls `settle` (the loop's device synchronise) and raises the stored exception, the object itself.
+    An exception of the producer's own goes first: it propagates, and the ring shuts down under it without raising."""
+
+    def __init__(self, depth, writer, settle=None):
+        self.writer, self.settle, self.failure = writer, settle, []
+        self.free, self.work = queue.Queue(), queue.Queue()
+        for r in range(depth):
+            self.free.put(r)
+        self.thread = threading.Thread(target=self._drain, name="y4m-writer", daemon=True)
+        self.thread.start()
+
+    def _drain(self):
+        while True:
+            item = self.work.get()
+            if item is None:
+                return
+            r, event, rows = item
+            try:
+                if not self.failure:
+                    if event is not None:
+                        event.synchronize()
+                    for buf in rows:
+                        self.writer.write_frame(buf)
+            except BaseException as e:          # noqa: BLE001 - handed to the caller's thread; keep releasing slots
+                self.failure.append(e)
+            if r is not None:
+                self.free.put(r)
+
+    def take(self, timeout=None):
+        """A free slot; with a timeout (seconds), queue.Empty if none comes back in that time."""
+        return self.free.get(timeout=timeout)
+
+    def hand(self, r, event, rows):
+        self.work.put((r, event, rows))
+
+    def close(self, reraise=True):
+        self.work.put(None)
+        self.thread.join()
+        if self.settle is not None:
+            self.settle()
+        if reraise and self.failure:
+            raise self.failure[0]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        self.close(reraise=exc_type is None)
+
+
+def read_passes(reader, ring, plan, np_in, issue):
+    """The read loop of the planner-driven modes (PassPlanner, ShutterPlanner): every frame of `reader` into row plan.rows of the open ring
+    slot's input buffer; issue(slot, *closed) for every pass the planner closes, and for what is open at the end of the stream."""
+    r = None
+    while not ring.failure:
+        if r is None:
+            r = ring.take()
+        if ring.failure or not reader.read_frame_into(np_in[r][plan.rows]):
+            break
+        closed = plan.frame()
+        if closed is not None:
+            issue(r, *closed)
+            r = None
+    if r is not None:
+        issue(r, *plan.end())
+    if plan.f == 0 and not ring.failure:
+        raise Y4MError("the Y4M stream holds no frame")
+
+
+def upload_times(times, slots, np_t, host_t, dev_t):
+    """The engine's times of a pass, `slots` per pair: each pair's own (`times`: one list per pair), its last one repeated in the rest, and
+    the last entry repeated after the last pair; filled into the ring slot's pinned buffer (host_t, np_t its numpy view) and queued for
+    upload on the current stream - with the payloads, ahead of the kernels: see DESIGN 3.12."""
+    for p, ts in enumerate(times):
+        np_t[p * slots:p * slots + len(ts)] = ts
+        np_t[p * slots + len(ts):(p + 1) * slots] = ts[-1]
+    np_t[len(times) * slots:] = np_t[len(times) * slots - 1]
+    dev_t.copy_(host_t, non_blocking=True)
+
+
+# What run() works out of a reader / writer pair before it looks at the mode: frame size, chroma siting, frame_bytes, matrix, code range,
+# the device, the canvas's multiple and the canvas.
+Clip = collections.namedtuple("Clip", "h w siting fb matrix crange dev mult hp wp")
+
+
 class VideoInterpolator:
     """reader -> (upsample_rate - 1) frames between every two input frames -> writer, streamed; or, with target_rate / speed, the frames
     of a Timeline (any output rate, any speed: _run_timeline).
@@ -765,7 +851,12 @@ class VideoInterpolator:
     pair and, carried over, the left frame of the next), the PairPipeline engine of the pass's stream, egress, D2H into the pass's slot
     of a ring of pinned buffers - all queued on that stream, nothing synchronises the host inside the loop but the ring itself.  A
     writer thread waits for a slot's event and writes, per pair, the interpolated frames and then the right frame's own input bytes.
-    Host and device memory are fixed by the frame size, n_streams and pairs_per_batch."""
+    Host and device memory are fixed by the frame size, n_streams and pairs_per_batch.
+
+    The three modes (_run_fixed, _run_timeline, _run_shutter) share what is not on a stream: the prologue (_clip), the ring with its
+    writer thread and failure protocol (PassRing), the planners' read loop (read_passes) and the fill of a pass's times (upload_times).
+    Each keeps its own buffers and its own submit: what is queued on a pass's stream, call for call, is what its bytes and its measured
+    rate rest on."""
 
     def __init__(self, model, cfg, upsample_rate=8, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
                  tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8):
@@ -835,13 +926,8 @@ class VideoInterpolator:
                                             blend=self.blend))
         return self._pipe[1]
 
-    @torch.no_grad()
-    def run(self, reader, writer):
-        """Returns the number of frames written: (n - 1) * upsample_rate + 1 for n input frames (with target_rate / speed:
-        floor((n - 1) / step) + 1; with a shutter: Timeline.n_outputs(n))."""
-        if self.timed:
-            return self._run_shutter(reader, writer) if self.samples > 1 else self._run_timeline(reader, writer)
-        from .evaluation import t_values
+    def _clip(self, reader, writer):
+        """The Clip of a run, or the refusal of a writer of another format or of a model that is not on the GPU."""
         h, w, siting, fb = reader.height, reader.width, reader.siting, reader.frame_bytes
         if (writer.height, writer.width, writer.siting) != (h, w, siting):
             raise ValueError("reader and writer disagree on the frame format")
@@ -850,8 +936,22 @@ class VideoInterpolator:
         dev = next(self.model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
-        mult = 32 * self.flow_scale
-        hp, wp = self.canvas(h, w)
+        return Clip(h, w, siting, fb, matrix, crange, dev, 32 * self.flow_scale, *self.canvas(h, w))
+
+    @torch.no_grad()
+    def run(self, reader, writer):
+        """Returns the number of frames written: (n - 1) * upsample_rate + 1 for n input frames (with target_rate / speed:
+        floor((n - 1) / step) + 1; with a shutter: Timeline.n_outputs(n))."""
+        clip = self._clip(reader, writer)
+        if not self.timed:
+            return self._run_fixed(clip, reader, writer)
+        return self._run_shutter(clip, reader, writer) if self.samples > 1 else self._run_timeline(clip, reader, writer)
+
+    def _run_fixed(self, clip, reader, writer):
+        """run() on the fixed grid of upsample_rate: planes[k] is [carried left frame | pairs_per_batch new frames], the pairs an
+        overlapping view of it; the times go up once per run.  Frame 0 is written from a pinned buffer of its own before any pass."""
+        from .evaluation import t_values
+        h, w, siting, fb, matrix, crange, dev, mult, hp, wp = clip
         pipe = self._pipeline(hp, wp, dev)
         n, pb, nt = pipe.n, self.pb, self.rate - 1
         depth = n + 2                                                  # ring slots: one per pass in flight, one being read, one being written
@@ -868,35 +968,9 @@ class VideoInterpolator:
         if not reader.read_frame_into(first.numpy()[0]):
             raise Y4MError("the Y4M stream holds no frame")
         torch.cuda.synchronize(dev)
-
-        free, work, failure = queue.Queue(), queue.Queue(), []
-        for r in range(depth):
-            free.put(r)
-
-        def drain():
-            while True:
-                item = work.get()
-                if item is None:
-                    return
-                r, valid = item
-                try:
-                    if not failure:
-                        if r < 0:
-                            writer.write_frame(first.numpy()[0])
-                        else:
-                            done[r].synchronize()
-                            for kind, row in pass_order(valid, nt):
-                                writer.write_frame(np_out[r][row] if kind == "interp" else np_in[r][row])
-                except BaseException as e:          # noqa: BLE001 - handed to the caller's thread; keep releasing slots
-                    failure.append(e)
-                if r >= 0:
-                    free.put(r)
-
-        th = threading.Thread(target=drain, name="y4m-writer", daemon=True)
-        th.start()
         written = 1
-        try:
-            work.put((-1, 0))
+        with PassRing(depth, writer, lambda: torch.cuda.synchronize(dev)) as ring:
+            ring.hand(None, None, [first.numpy()[0]])
             # frame 0: ingested where pass 0 looks for its carried left frame
             last = (n - 1) % n
             with torch.cuda.stream(pipe.streams[last]):
@@ -904,15 +978,15 @@ class VideoInterpolator:
                 frames_from_yuv(dev_in[last][:1], h, w, siting, matrix, crange, self.cfg, True, out=planes[last][pb:], multiple=mult)
                 ingested[last].record()
             j, eof = 0, False
-            while not eof and not failure:
-                r = free.get()
+            while not eof and not ring.failure:
+                r = ring.take()
                 valid = 0
                 while valid < pb and reader.read_frame_into(np_in[r][valid]):
                     valid += 1
                 if valid < pb:
                     eof = True
                     if valid == 0:
-                        free.put(r)
+                        ring.hand(r, None, [])
                         break
                     np_in[r][valid:] = np_in[r][valid - 1]          # fill the pass; the extra pairs are not written
                 k, kprev = j % n, (j - 1) % n
@@ -929,19 +1003,12 @@ class VideoInterpolator:
                     frames_to_yuv(frames, h, w, siting, matrix, crange, self.cfg, out=dev_out[k])
                     host_out[r].copy_(dev_out[k], non_blocking=True)
                     done[r].record()
-                work.put((r, valid))
+                ring.hand(r, done[r], [np_out[r][row] if kind == "interp" else np_in[r][row] for kind, row in pass_order(valid, nt)])
                 written += valid * self.rate
                 j += 1
-        finally:
-            work.put(None)
-            th.join()
-            torch.cuda.synchronize(dev)
-        if failure:
-            raise failure[0]
         return written
 
-    @torch.no_grad()
-    def _run_timeline(self, reader, writer):
+    def _run_timeline(self, clip, reader, writer):
         """run() with target_rate / speed: the output frames are those of Timeline(speed * reader.rate / target_rate).
 
         Pairs now differ: pair (i, i + 1) gets tl.count(i) synthesised frames at its own times, and a pair that gets none is not run -
@@ -949,23 +1016,14 @@ class VideoInterpolator:
         planned for `slots` times per pair; a pair with m < slots runs with its last time repeated in the rest, only its first m
         frames go through the egress kernel and back to the host.  The times go up from a pinned buffer of the pass's ring slot on the
         pass's stream.  A ring slot holds `cap` input payloads - every frame read lands in one, a frame nobody needs is overwritten by
-        the next - and the list of what the writer thread takes from it, in the timeline's order: ("interp", row of host_out) or
-        ("orig", row of host_in).  Each uploaded frame is ingested once: a pair's left frame is the previous running pair's right
-        frame copied on the device, or, after a pair that did not run, ingested with the right one.  A pass short of pairs (end of
-        clip, or a slot full of frames passed through) leaves the planes of its unused entries as they are: finite, and never read
-        back.  Memory is fixed by the frame size, n_streams, pairs_per_batch and slots."""
-        h, w, siting, fb = reader.height, reader.width, reader.siting, reader.frame_bytes
-        if (writer.height, writer.width, writer.siting) != (h, w, siting):
-            raise ValueError("reader and writer disagree on the frame format")
-        matrix = default_matrix(h) if self.matrix is None else self.matrix
-        crange = self.color_range if self.color_range is not None else (reader.color_range if reader.color_range is not None else LIMITED)
-        dev = next(self.model.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
+        the next - and the writer thread takes from it, in the timeline's order, rows of host_out ("interp") and of host_in ("orig").
+        Each uploaded frame is ingested once: a pair's left frame is the previous running pair's right frame copied on the device, or,
+        after a pair that did not run, ingested with the right one.  A pass short of pairs (end of clip, or a slot full of frames passed
+        through) leaves the planes of its unused entries as they are: finite, and never read back.  Memory is fixed by the frame size,
+        n_streams, pairs_per_batch and slots."""
+        h, w, siting, fb, matrix, crange, dev, mult, hp, wp = clip
         tl = self.timeline(reader.rate)
         S, pb, n = tl.slots, self.pb, self.n_streams
-        mult = 32 * self.flow_scale
-        hp, wp = self.canvas(h, w)
         pipe = self._pipeline(hp, wp, dev, S) if S else None          # an integer step only picks input frames: nothing to run
         depth, cap = n + 2, 2 * pb + 2
         host_in = [torch.empty(cap, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
@@ -980,27 +1038,6 @@ class VideoInterpolator:
             planes = [torch.zeros(pb, 2, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [pair][left | right]
             ingested = [torch.cuda.Event() for _ in range(n)]
         torch.cuda.synchronize(dev)
-
-        free, work, failure = queue.Queue(), queue.Queue(), []
-        for r in range(depth):
-            free.put(r)
-
-        def drain():
-            while True:
-                item = work.get()
-                if item is None:
-                    return
-                r, order, on_gpu = item
-                try:
-                    if not failure:
-                        if on_gpu:
-                            done[r].synchronize()
-                        for kind, row in order:
-                            writer.write_frame(np_out[r][row] if kind == "interp" else np_in[r][row])
-                except BaseException as e:          # noqa: BLE001 - handed to the caller's thread; keep releasing slots
-                    failure.append(e)
-                free.put(r)
-
         last_p = [0]          # place, in its pass, of the pair whose right frame the next pair may carry over
 
         def submit(j, r, pairs):
@@ -1017,10 +1054,7 @@ class VideoInterpolator:
                         planes[k][p, 0].copy_(planes[k][p - 1, 1] if p else planes[(j - 1) % n][last_p[0], 1])
                     frames_from_yuv(dev_in[k][row:row + rows], h, w, siting, matrix, crange, self.cfg, True, out=planes[k][p, 2 - rows:],
                                     multiple=mult)
-                    np_t[r][p * S:p * S + len(ts)] = ts
-                    np_t[r][p * S + len(ts):(p + 1) * S] = ts[-1]
-                np_t[r][len(pairs) * S:] = np_t[r][len(pairs) * S - 1]
-                dev_t[k].copy_(host_t[r], non_blocking=True)          # with the payloads, ahead of the kernels: see DESIGN 3.12
+                upload_times([ts for _, _, ts in pairs], S, np_t[r], host_t[r], dev_t[k])
                 ingested[k].record()
                 last_p[0] = len(pairs) - 1
                 frames = pipe.engines[k].run(planes[k].view(pb, 6, hp, wp), dev_t[k], False)
@@ -1033,44 +1067,22 @@ class VideoInterpolator:
                     host_out[r][o:o + m].copy_(dev_out[k][o:o + m], non_blocking=True)
                 done[r].record()
 
-        th = threading.Thread(target=drain, name="y4m-writer", daemon=True)
-        th.start()
-        plan = PassPlanner(tl, pb, cap)
         written = j = 0          # frames written, passes issued
-        r = None
 
         def issue(r, order, pairs):
             nonlocal written, j
-            if pairs and not failure:
+            on_gpu = bool(pairs) and not ring.failure
+            if on_gpu:
                 submit(j, r, pairs)
                 j += 1
-            work.put((r, order if not failure else [], bool(pairs) and not failure))
+            ring.hand(r, done[r] if on_gpu else None, [np_out[r][row] if kind == "interp" else np_in[r][row] for kind, row in order])
             written += len(order)
 
-        try:
-            while not failure:
-                if r is None:
-                    r = free.get()
-                if failure or not reader.read_frame_into(np_in[r][plan.rows]):
-                    break
-                closed = plan.frame()
-                if closed is not None:
-                    issue(r, *closed)
-                    r = None
-            if r is not None:
-                issue(r, *plan.end())
-            if plan.f == 0 and not failure:
-                raise Y4MError("the Y4M stream holds no frame")
-        finally:
-            work.put(None)
-            th.join()
-            torch.cuda.synchronize(dev)
-        if failure:
-            raise failure[0]
+        with PassRing(depth, writer, lambda: torch.cuda.synchronize(dev)) as ring:
+            read_passes(reader, ring, PassPlanner(tl, pb, cap), np_in, issue)
         return written
 
-    @torch.no_grad()
-    def _run_shutter(self, reader, writer):
+    def _run_shutter(self, clip, reader, writer):
         """run() with a shutter: output frame k is the mean of the S = shutter_samples sub-frames of Timeline(step, shutter=, samples=),
         summed in time order into an fp32 accumulator by ssm_frames_accumulate_fwd and egressed from it - every output, also one whose
         samples are all input frames.
@@ -1084,18 +1096,9 @@ class VideoInterpolator:
         the pass before recorded after its last accumulate and egress, so the engines of neighbouring passes still overlap, only these
         short tails are serialised, and the result depends on nothing but the time order.  One output is open at a time (OPEN_OUTPUTS),
         which sizes the ring of accumulators.  Memory is fixed by the frame size, n_streams, pairs_per_batch, slots and that bound."""
-        h, w, siting, fb = reader.height, reader.width, reader.siting, reader.frame_bytes
-        if (writer.height, writer.width, writer.siting) != (h, w, siting):
-            raise ValueError("reader and writer disagree on the frame format")
-        matrix = default_matrix(h) if self.matrix is None else self.matrix
-        crange = self.color_range if self.color_range is not None else (reader.color_range if reader.color_range is not None else LIMITED)
-        dev = next(self.model.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
+        h, w, siting, fb, matrix, crange, dev, mult, hp, wp = clip
         tl = self.timeline(reader.rate)
         slots, pb, n = tl.slots, self.pb, self.n_streams
-        mult = 32 * self.flow_scale
-        hp, wp = self.canvas(h, w)
         pipe = self._pipeline(hp, wp, dev, slots) if slots else None          # a step whose samples are all input frames: nothing to synthesise
         streams = pipe.streams if pipe is not None else [torch.cuda.Stream(dev) for _ in range(n)]
         depth, cap = n + 2, 2 * pb + 2
@@ -1115,26 +1118,6 @@ class VideoInterpolator:
         ingested, summed = [torch.cuda.Event() for _ in range(n)], [torch.cuda.Event() for _ in range(n)]
         torch.cuda.synchronize(dev)
 
-        free, work, failure = queue.Queue(), queue.Queue(), []
-        for r in range(depth):
-            free.put(r)
-
-        def drain():
-            while True:
-                item = work.get()
-                if item is None:
-                    return
-                r, count, on_gpu = item
-                try:
-                    if not failure:
-                        if on_gpu:
-                            done[r].synchronize()
-                        for o in range(count):
-                            writer.write_frame(np_out[r][o])
-                except BaseException as e:          # noqa: BLE001 - handed to the caller's thread; keep releasing slots
-                    failure.append(e)
-                free.put(r)
-
         def submit(j, r, rows, carry, pairs, calls):
             """Pass j on ring slot r; the arguments are ShutterPlanner's."""
             k, kprev = j % n, (j - 1) % n
@@ -1146,14 +1129,11 @@ class VideoInterpolator:
                 if carry is not None:
                     planes[k][0].copy_(planes[kprev][carry])
                 frames_from_yuv(dev_in[k][:rows], h, w, siting, matrix, crange, self.cfg, True, out=planes[k][1:1 + rows], multiple=mult)
-                for p, (left, right, ts) in enumerate(pairs):
+                for p, (left, right, _) in enumerate(pairs):
                     sides[k][p, 0].copy_(planes[k][left])
                     sides[k][p, 1].copy_(planes[k][right])
-                    np_t[r][p * slots:p * slots + len(ts)] = ts
-                    np_t[r][p * slots + len(ts):(p + 1) * slots] = ts[-1]
                 if pairs:
-                    np_t[r][len(pairs) * slots:] = np_t[r][len(pairs) * slots - 1]
-                    dev_t[k].copy_(host_t[r], non_blocking=True)          # with the payloads, ahead of the kernels: see DESIGN 3.12
+                    upload_times([ts for _, _, ts in pairs], slots, np_t[r], host_t[r], dev_t[k])
                 ingested[k].record()
                 frames = pipe.engines[k].run(sides[k].view(pb, 6, hp, wp), dev_t[k], False) if pairs else None
                 if j:
@@ -1170,38 +1150,18 @@ class VideoInterpolator:
                 summed[k].record()
                 done[r].record()
 
-        th = threading.Thread(target=drain, name="y4m-writer", daemon=True)
-        th.start()
         written = j = 0          # frames written, passes issued
-        r = None
 
         def issue(r, rows, carry, pairs, calls, finished):
             nonlocal written, j
-            on_gpu = rows > 0 and not failure
+            on_gpu = rows > 0 and not ring.failure
             if on_gpu:
                 submit(j, r, rows, carry, pairs, calls)
                 j += 1
-            work.put((r, len(finished) if on_gpu else 0, on_gpu))
+            # not on_gpu: with no rows the planner has recorded no call, so `finished` is empty; after a failure the thread writes nothing
+            ring.hand(r, done[r] if on_gpu else None, [np_out[r][o] for o in range(len(finished))])
             written += len(finished)
 
-        try:
-            while not failure:
-                if r is None:
-                    r = free.get()
-                if failure or not reader.read_frame_into(np_in[r][plan.rows]):
-                    break
-                closed = plan.frame()
-                if closed is not None:
-                    issue(r, *closed)
-                    r = None
-            if r is not None:
-                issue(r, *plan.end())
-            if plan.f == 0 and not failure:
-                raise Y4MError("the Y4M stream holds no frame")
-        finally:
-            work.put(None)
-            th.join()
-            torch.cuda.synchronize(dev)
-        if failure:
-            raise failure[0]
+        with PassRing(depth, writer, lambda: torch.cuda.synchronize(dev)) as ring:
+            read_passes(reader, ring, plan, np_in, issue)
         return written

@@ -3,25 +3,27 @@
 scripts/interpolate_video.py --shutter) byte for byte against the composition it stands for: ingest -> FullModel.interpolate of every
 running pair at its sample times, padded to `slots` by repeating the last one -> accumulate_host over each output's samples in time
 order -> egress of the accumulator.  The reference call uses `slots` times per call for the reason tests/test_hip_video_timeline.py gives:
-a plan's tile choice depends on its batch.  Helpers re-declared from that file."""
-import io
+a plan's tile choice depends on its batch.  The clip helpers are those of tests/video_clips.py, here on a 60:1 clip."""
+import functools
 import os
+import sys
 from fractions import Fraction as Fr
 
 import numpy as np
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import video_clips  # noqa: E402
+from video_clips import V, clip_payloads, read_clip  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 H, W, N = 40, 48, 9          # canvas 64 x 64
+clip_file = functools.partial(video_clips.clip_file, rate=(60, 1))
+stream = functools.partial(video_clips.stream, rate=(60, 1))
 POISON = np.uint32(0x7FC0DEAD)
-
-
-def V():
-    from ssm_amd import video
-    return video
 
 
 def bits(a):
@@ -123,47 +125,6 @@ def model():
     m.stage1_model.load_state_dict(synthetic_state_dict(1))
     m.stage2_model.load_state_dict(synthetic_state_dict(2))
     return cfg, m.to(DEV).eval()
-
-
-def clip_payloads(n, h, w, siting, seed=5):
-    """A moving synthetic clip as Y4M payloads [n, frame_bytes] uint8 (through the yardstick's egress: legal limited-range codes)."""
-    from ssm_amd.weights import synthetic_frames_u8, IMAGENET_MEAN, IMAGENET_STD
-    v = V()
-    rgb = synthetic_frames_u8(n, h, w, seed=seed).numpy().astype(np.float32) / np.float32(255.0)
-    x = (rgb - np.float32(IMAGENET_MEAN)[None, :, None, None]) / np.float32(IMAGENET_STD)[None, :, None, None]
-    return v.frames_to_yuv_host(x, h, w, siting, v.default_matrix(h), v.LIMITED)
-
-
-def clip_file(payloads, h, w, chroma="420jpeg", rate=(60, 1)):
-    v = V()
-    buf = io.BytesIO()
-    wr = v.Y4MWriter(buf, w, h, rate=rate, aspect=(1, 1), chroma=chroma)
-    for p in payloads:
-        wr.write_frame(p)
-    buf.seek(0)
-    return buf
-
-
-def read_clip(src):
-    v = V()
-    with v.Y4MReader(src) as r:
-        frames, buf = [], np.empty(r.frame_bytes, np.uint8)
-        while r.read_frame_into(buf):
-            frames.append(buf.copy())
-        return r, np.stack(frames)
-
-
-def stream(m, cfg, payloads, h, w, rate=(60, 1), **kw):
-    """The clip through VideoInterpolator(**kw): (header of the output, its frames).  The writer's rate is the command line's rule."""
-    v = V()
-    r = v.Y4MReader(clip_file(payloads, h, w, rate=rate))
-    sink = io.BytesIO()
-    wr = v.Y4MWriter.like(sink, r, rate=kw.get("target_rate") or r.rate)
-    count = v.VideoInterpolator(m, cfg, **kw).run(r, wr)
-    assert count == wr.frames_written
-    hdr, got = read_clip(io.BytesIO(sink.getvalue()))
-    assert got.shape[0] == count
-    return hdr, got
 
 
 def expected_stream(m, cfg, payloads, h, w, step, sigma, S, **mode):

@@ -5,20 +5,19 @@ and the streamed loop (VideoInterpolator, scripts/interpolate_video.py) against 
 import io
 import itertools
 import os
+import sys
 
 import numpy as np
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from video_clips import V, clip_payloads, read_clip, write_clip  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 SIZES = ((46, 70), (45, 71), (64, 96))          # even, odd (offsets 9/13 and 9/12 in the 64 x 96 canvas), and a canvas-filling size
-
-
-def V():
-    from ssm_amd import video
-    return video
 
 
 def make_model():
@@ -35,32 +34,6 @@ def make_model():
 @pytest.fixture(scope="module")
 def model():
     return make_model()
-
-
-def clip_payloads(n, h, w, siting, seed=5):
-    """A moving synthetic clip as Y4M payloads [n, frame_bytes] uint8 (through the yardstick's egress: legal limited-range codes)."""
-    from ssm_amd.weights import synthetic_frames_u8, IMAGENET_MEAN, IMAGENET_STD
-    v = V()
-    rgb = synthetic_frames_u8(n, h, w, seed=seed).numpy().astype(np.float32) / np.float32(255.0)          # [n,3,h,w]
-    x = (rgb - np.float32(IMAGENET_MEAN)[None, :, None, None]) / np.float32(IMAGENET_STD)[None, :, None, None]
-    return v.frames_to_yuv_host(x, h, w, siting, v.default_matrix(h), v.LIMITED)
-
-
-def write_clip(path, payloads, h, w, chroma="420jpeg", rate=(30, 1), color_range=None):
-    v = V()
-    with v.Y4MWriter(path, w, h, rate=rate, aspect=(1, 1), chroma=chroma, color_range=color_range) as wr:
-        for p in payloads:
-            wr.write_frame(p)
-
-
-def read_clip(path):
-    v = V()
-    with v.Y4MReader(path) as r:
-        frames = []
-        buf = np.empty(r.frame_bytes, np.uint8)
-        while r.read_frame_into(buf):
-            frames.append(buf.copy())
-        return r, np.stack(frames)
 
 
 @pytest.mark.parametrize("siting,matrix,crange", list(itertools.product((0, 1, 2), (0, 1), (0, 1))))

@@ -2,24 +2,22 @@
 against the expected stream: for every pair that gets a frame, ingest -> FullModel.interpolate at the pair's times, padded to `slots` by
 repeating the last one -> egress of the frames the timeline asks for; frames at integer times are their input bytes.  The reference call
 uses `slots` times per call because a plan's tile choice depends on its batch: at the same number of times per call the streamed loop
-and the call run the same kernels on the same numbers, hence BYTE equality.  Helpers re-declared from tests/test_hip_video.py."""
-import io
+and the call run the same kernels on the same numbers, hence BYTE equality.  The clip helpers are those of tests/video_clips.py."""
 import os
+import sys
 from fractions import Fraction as Fr
 
 import numpy as np
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from video_clips import V, clip_file, clip_payloads, read_clip, stream  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 H, W, N = 64, 96, 6
-
-
-def V():
-    from ssm_amd import video
-    return video
 
 
 @pytest.fixture(scope="module")
@@ -32,47 +30,6 @@ def model():
     m.stage1_model.load_state_dict(synthetic_state_dict(1))
     m.stage2_model.load_state_dict(synthetic_state_dict(2))
     return cfg, m.to(DEV).eval()
-
-
-def clip_payloads(n, h, w, siting, seed=5):
-    """A moving synthetic clip as Y4M payloads [n, frame_bytes] uint8 (through the yardstick's egress: legal limited-range codes)."""
-    from ssm_amd.weights import synthetic_frames_u8, IMAGENET_MEAN, IMAGENET_STD
-    v = V()
-    rgb = synthetic_frames_u8(n, h, w, seed=seed).numpy().astype(np.float32) / np.float32(255.0)
-    x = (rgb - np.float32(IMAGENET_MEAN)[None, :, None, None]) / np.float32(IMAGENET_STD)[None, :, None, None]
-    return v.frames_to_yuv_host(x, h, w, siting, v.default_matrix(h), v.LIMITED)
-
-
-def clip_file(payloads, h, w, chroma="420jpeg", rate=(30, 1)):
-    v = V()
-    buf = io.BytesIO()
-    wr = v.Y4MWriter(buf, w, h, rate=rate, aspect=(1, 1), chroma=chroma)
-    for p in payloads:
-        wr.write_frame(p)
-    buf.seek(0)
-    return buf
-
-
-def read_clip(src):
-    v = V()
-    with v.Y4MReader(src) as r:
-        frames, buf = [], np.empty(r.frame_bytes, np.uint8)
-        while r.read_frame_into(buf):
-            frames.append(buf.copy())
-        return r, np.stack(frames)
-
-
-def stream(m, cfg, payloads, h, w, chroma="420jpeg", rate=(30, 1), **kw):
-    """The clip through VideoInterpolator(**kw): (header of the output, its frames).  The writer's rate is the command line's rule."""
-    v = V()
-    r = v.Y4MReader(clip_file(payloads, h, w, chroma, rate))
-    sink = io.BytesIO()
-    wr = v.Y4MWriter.like(sink, r, rate=kw.get("target_rate") or r.rate)
-    count = v.VideoInterpolator(m, cfg, **kw).run(r, wr)
-    assert count == wr.frames_written
-    hdr, got = read_clip(io.BytesIO(sink.getvalue()))
-    assert got.shape[0] == count
-    return hdr, got
 
 
 def expected_stream(m, cfg, payloads, h, w, siting, step, **mode):
