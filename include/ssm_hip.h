@@ -670,6 +670,31 @@ int ssm_frames_to_yuv_fwd(ssm_view in, unsigned char *frames_yuv, int N, int H, 
  * that overlap. */
 int ssm_frames_accumulate_fwd(ssm_view src, ssm_view acc, int N, int C, int H, int W, int init, float scale, void *stream);
 
+/* ---- scene cuts of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) -------------------------------
+ * Definition (ssm_amd.video.SceneCuts(threshold), everything in exact integers and fractions).  For the pair of input frames (i, i + 1)
+ * of H x W pixels, with Y the 8-bit luma planes as they stand in the payloads:
+ *     s = sum over the plane of |Y_i[y][x] - Y_(i+1)[y][x]|          (an integer, at most 255 H W)
+ *     m = s / (H W);   score = min(m, |m - m_prev|) / 255;   the pair is a cut iff score >= threshold;   then m_prev = m
+ * over the pairs in the order in which they run, m_prev = 0 before the first; a pair that a timeline skips is not fed.  The mean absolute
+ * frame difference damped by its own change: steady fast motion has a large m and a small change.  A convention, not backed by a
+ * measurement here; the threshold, a fraction in (0, 1], is the user's and has no default.  At a cut the streamed loop writes, for an
+ * output at t < 1/2 between the two frames, the left frame's own bytes, for any other the right frame's.
+ * ssm_luma_sad_fwd: a + n stride_a and b + n stride_b (strides in BYTES, of either sign) point at the Y planes of frames n = 0 .. N-1,
+ * each H x W bytes with unpadded rows - a Y4M payload starts with its Y plane, so with stride = frame_bytes this addresses payloads
+ * directly, whatever the chroma format.  sums[n] = s of (a_n, b_n), exact, in a device array of N 64-bit words.  The entry clears `sums`
+ * on `stream` itself (a memset node ahead of the kernel): the result does not depend on what the words held.  a and b are only read and
+ * may alias or overlap.  No byte outside the N planes of either operand is read.
+ *   A workgroup of 256 lanes sums a span of 16 KiB of one plane: each lane 4 pieces of 16 bytes, 4 bytes per v_sad_u8 into a 32-bit lane
+ *   sum (a span's sum is at most 255 * 16384 < 2^22), waves reduced by cross-lane shuffles, 4 wave partials through LDS, then one 64-bit
+ *   vector atomicAdd into sums[n].  Integer adds commute: the sums are the same in every run.  One 16-byte load per operand and piece
+ *   where both planes start on 16-byte boundaries; a plane that does not (odd frame sizes make n * frame_bytes odd), and the last piece
+ *   of a plane whose size is no multiple of 16, goes through byte loads in the same kernel.  No LDS beyond the wave partials, no
+ *   scratch, no packed fp32.  Reads 2 B per pixel.
+ * SSM_E_ARG (nothing is queued) for null pointers; N outside 1..65535; H or W < 1; with N > 1 a |stride| shorter than H W; `sums` not
+ * 8-byte aligned; a plane of more than 2^31 - 1 spans. */
+int ssm_luma_sad_fwd(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b, int N, int H, int W,
+                     unsigned long long *sums, void *stream);
+
 /* ---- training ingest (csrc/ssm_data.hip; whole decoded uint8 HWC RGB frames on the device) --------------
  * The clip loader (ssm_amd/data.py) serves the reference's training transform, RandomCrop, then RandomMirrorRotate,
  * then Normalize and ToTensor (scripts/utils/dataloaders/default_reader.py:182-207,250-286, augmentations.py:

@@ -12,14 +12,18 @@
 //   frames_accumulate_kernel the shutter of the streamed loop: N frames summed, in increasing n, into one fp32 accumulator
 //                            that is read at most once and written once per launch; one lane = 4 consecutive pixels of a row of one
 //                            channel (16-byte loads and stores), or one pixel when a view does not allow it
+//   luma_sad_kernel          scene cuts of the streamed loop: per frame pair the exact sum of |a - b| over the 8-bit Y planes;
+//                            one lane = 16 consecutive bytes of each plane (one 16-byte load per operand), or byte loads where a plane
+//                            does not start on a 16-byte boundary; v_sad_u8 into a 32-bit lane sum, shuffles, one 64-bit atomic per workgroup
 // Both conversions are HBM-bound (1.5 B in + 12 B out per pixel, and the reverse); so is the accumulation (4 (N + 1 + !init) B per
-// element).  The chroma siting enters as four horizontal weights (ingest) or one switch (egress); matrix and range enter as one row of
+// element) and the luma difference (2 B per pixel).  The chroma siting enters as four horizontal weights (ingest) or one switch (egress); matrix and range enter as one row of
 // the constant table built by ssm_amd/video.py, which the host yardsticks read too.  Inputs of the egress kernel are finite.
 // NO CONTRACTION (as ssm_flow.hip): the numpy yardsticks round every operation, and so must the kernels.
 #include "ssm_common.h"
 #include "ssm_device.h"
 
 #include <cmath>
+#include <cstdlib>
 
 #pragma clang fp contract(off)
 
@@ -290,6 +294,77 @@ __global__ __launch_bounds__(256) void frames_accumulate_kernel(ssm_view src, ss
     }
 }
 
+// ---- scene cuts: luma differences summed ---------------------------------------------------------------------------------------------
+// sums[n] += sum over this workgroup's span of |a_n[i] - b_n[i]|, i over the H * W bytes of plane n.  A lane takes SAD_CHUNKS pieces of 16
+// bytes, SAD_LANES * 16 bytes apart (a wave's loads are contiguous); four bytes go through one v_sad_u8 (sum of the four absolute byte
+// differences, added to the accumulator operand).  A workgroup spans SAD_SPAN = 16 KiB of a plane: its sum is at most 255 * SAD_SPAN
+// < 2^22, so lane sums, wave sums and the workgroup's sum all fit 32 bits.  The 16-byte loads need both plane starts on 16-byte
+// boundaries (the pieces then are too): decided per plane, uniform over the workgroup; any other plane, and the last piece of a plane
+// whose size is no multiple of 16, goes byte by byte, bytes past the plane's end read as 0 on both sides (never loaded).
+constexpr int SAD_LANES = 256, SAD_CHUNKS = 4;
+constexpr long long SAD_SPAN = (long long)SAD_LANES * 16 * SAD_CHUNKS;
+static_assert(255 * SAD_SPAN < (1ll << 32), "a workgroup's sum fits 32 bits");
+
+__device__ __forceinline__ unsigned bytes4(const unsigned char *p, long long left) {          // up to four bytes at p, `left` of them exist
+    unsigned v = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (i < left) v |= (unsigned)p[i] << (8 * i);
+    return v;
+}
+
+__device__ __forceinline__ unsigned sad16(i32x4 x, i32x4 y, unsigned s) {
+    s = __builtin_amdgcn_sad_u8((unsigned)x.x, (unsigned)y.x, s);
+    s = __builtin_amdgcn_sad_u8((unsigned)x.y, (unsigned)y.y, s);
+    s = __builtin_amdgcn_sad_u8((unsigned)x.z, (unsigned)y.z, s);
+    return __builtin_amdgcn_sad_u8((unsigned)x.w, (unsigned)y.w, s);
+}
+
+__global__ __launch_bounds__(SAD_LANES) void luma_sad_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
+                                                             long long plane, unsigned long long *sums) {          // a, b may alias
+    __shared__ unsigned partial[SAD_LANES / 64];
+    const int n = blockIdx.y;
+    const unsigned char *pa = a + n * stride_a, *pb = b + n * stride_b;
+    const bool vec = ((reinterpret_cast<size_t>(pa) | reinterpret_cast<size_t>(pb)) & 15) == 0;
+    const long long base = blockIdx.x * SAD_SPAN + threadIdx.x * 16;
+    unsigned s = 0;
+    if (vec && (blockIdx.x + 1) * SAD_SPAN <= plane) {          // the whole span lies inside the plane: all loads first, none guarded
+        i32x4 va[SAD_CHUNKS], vb[SAD_CHUNKS];
+#pragma unroll
+        for (int c = 0; c < SAD_CHUNKS; ++c) {
+            va[c] = *reinterpret_cast<const i32x4 *>(pa + base + (long long)c * SAD_LANES * 16);
+            vb[c] = *reinterpret_cast<const i32x4 *>(pb + base + (long long)c * SAD_LANES * 16);
+        }
+#pragma unroll
+        for (int c = 0; c < SAD_CHUNKS; ++c) s = sad16(va[c], vb[c], s);
+    } else {
+#pragma unroll
+        for (int c = 0; c < SAD_CHUNKS; ++c) {
+            const long long o = base + (long long)c * SAD_LANES * 16;
+            if (o >= plane) break;
+            if (vec && o + 16 <= plane) {
+                s = sad16(*reinterpret_cast<const i32x4 *>(pa + o), *reinterpret_cast<const i32x4 *>(pb + o), s);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const long long left = plane - (o + 4 * q);          // <= 0: the piece ends before this word
+                    s = __builtin_amdgcn_sad_u8(bytes4(pa + o + 4 * q, left), bytes4(pb + o + 4 * q, left), s);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+    if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned t = 0;
+#pragma unroll
+        for (int w = 0; w < SAD_LANES / 64; ++w) t += partial[w];
+        atomicAdd(&sums[n], (unsigned long long)t);
+    }
+}
+
 // first and one-past-last address, in bytes, of the floats a view of [n,c,h,w] names (strides of either sign)
 inline void view_range(const ssm_view &v, int n, int c, int h, int w, long long *lo, long long *hi) {
     long long a = 0, b = 0;
@@ -398,4 +473,24 @@ extern "C" int ssm_frames_accumulate_fwd(ssm_view src, ssm_view acc, int N, int 
         SSM_LAUNCH(frames_accumulate_kernel<1>, dim3((W + 63) / 64, (H + 3) / 4, C), dim3(64, 4), 0, (hipStream_t)stream, src, acc, N, H, W, init,
                    scale);
     return ssm::check_launch("ssm_frames_accumulate_fwd");
+}
+
+extern "C" int ssm_luma_sad_fwd(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b, int N, int H, int W,
+                                unsigned long long *sums, void *stream) {
+    SSM_REQUIRE(a && b && sums, "luma_sad: null pointer");
+    SSM_REQUIRE(N > 0 && N <= 65535, "luma_sad: N=%d outside 1..65535", N);
+    SSM_REQUIRE(H > 0 && W > 0, "luma_sad: bad plane size %dx%d", H, W);
+    const long long plane = (long long)H * W;
+    SSM_REQUIRE(N == 1 || (std::llabs(stride_a) >= plane && std::llabs(stride_b) >= plane),
+                "luma_sad: strides %lld (a), %lld (b) shorter than the plane's %lld bytes", stride_a, stride_b, plane);
+    SSM_REQUIRE(reinterpret_cast<size_t>(sums) % 8 == 0, "luma_sad: sums is not 8-byte aligned");
+    const long long groups = (plane + SAD_SPAN - 1) / SAD_SPAN;
+    SSM_REQUIRE(groups <= 2147483647ll, "luma_sad: a plane of %lld bytes is more than the grid takes", plane);
+    const hipError_t e = ssm::memset_async(sums, 0, sizeof(unsigned long long) * (size_t)N, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        ssm::set_error("luma_sad: memset failed: %s", hipGetErrorString(e));
+        return SSM_E_LAUNCH;
+    }
+    SSM_LAUNCH(luma_sad_kernel, dim3((unsigned)groups, N), dim3(SAD_LANES), 0, (hipStream_t)stream, a, b, stride_a, stride_b, plane, sums);
+    return ssm::check_launch("ssm_luma_sad_fwd");
 }

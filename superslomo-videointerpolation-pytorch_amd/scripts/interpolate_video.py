@@ -27,6 +27,13 @@ over the first DEG / 360 of its interval, as a camera at the output rate with th
 --shutter 180 instead of dropped frames that strobe, slow motion with a chosen amount of blur, or blurred / sharp frame pairs from
 high-rate footage.  The mean is taken of the gamma-coded R'G'B' values, as a frame-mixing filter does, not in linear light; every output
 frame then comes from the GPU, input frames are no longer passed through.  The header's rate is what it is without --shutter.
+
+--scene_cut T (a decimal or a fraction in (0, 1]; no default value - the option is off unless given): every pair of input frames is also
+scored by ssm_amd.video.SceneCuts from the sum of its absolute luma differences (taken on the GPU, beside the pair's own work), and a pair
+that scores T or more is a scene cut: instead of frames that morph one scene into the other, the output repeats the left input frame up
+to the middle of the interval and the right one from there on.  The score - the mean absolute luma difference, damped by its own change
+from the pair before, over 255 - is a convention, not backed by a measurement here; every cut is written to --log with its score, which
+is what to choose T from.  Fades and dissolves are not looked for.  Not together with --shutter.
 """
 import argparse
 import configparser
@@ -74,6 +81,10 @@ def getargs(argv=None):
                              "over DEG / 360 of its interval. Needs --fps or --speed. Default: off.")
     parser.add_argument("--shutter_samples", type=int, default=8, metavar="S",
                         help="With --shutter: sub-frames per output frame (a convention, not a measured optimum). Default 8.")
+    parser.add_argument("--scene_cut", type=_named(V.parse_scene_cut), default=None, metavar="T",
+                        help="Scene-cut threshold as a decimal or a fraction in (0, 1] (0.1, 1/10): a pair of input frames whose score reaches it "
+                             "gets copies of its input frames instead of synthesised ones. A convention, no measured optimum; no default "
+                             "value: off unless given. Not together with --shutter.")
     parser.add_argument("--matrix", choices=sorted(V.MATRICES), default=None, help="Y'CbCr matrix (default: bt709 from 720 rows up, else bt601).")
     parser.add_argument("--range", choices=sorted(V.RANGES), default=None, dest="color_range",
                         help="Code range (default: the header's XCOLORRANGE tag, else limited).")
@@ -98,6 +109,8 @@ def getargs(argv=None):
                          "together with --upsample_rate or --slowmo")
         if args.upsample_rate is None:
             args.upsample_rate = 8
+    if args.scene_cut is not None and args.shutter is not None:
+        parser.error("--scene_cut does not go together with --shutter: an average of sub-frames across a cut needs a definition of its own")
     if args.shutter is not None and args.shutter_samples < 1:
         parser.error("--shutter_samples must be at least 1 (got %d)" % args.shutter_samples)
     return args
@@ -115,7 +128,7 @@ def main(argv=None, model=None):
     timed = args.fps is not None or args.speed is not None
     vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate or 8, matrix=matrix, color_range=crange,
                              flow_scale=args.flow_scale, tile=args.tile, halo=args.halo, blend=args.blend, target_rate=args.fps, speed=args.speed,
-                             shutter=args.shutter, shutter_samples=args.shutter_samples)
+                             shutter=args.shutter, shutter_samples=args.shutter_samples, scene_cut=args.scene_cut)
     with V.Y4MReader(args.input) as reader:
         if timed:
             rate = args.fps or reader.rate
@@ -130,6 +143,9 @@ def main(argv=None, model=None):
                  reader.rate[0], reader.rate[1], args.output, rate[0], rate[1])
         with V.Y4MWriter.like(args.output, reader, rate=rate, color_range=out_range) as writer:
             n = vi.run(reader, writer)
+    for i, score in vi.cuts:
+        log.info("[%s] scene cut between input frames %d and %d: score %s = %.6f (threshold %s)", args.expt, i, i + 1, score, float(score),
+                 vi.scene_cut)
     log.info("Interpolation complete: %d frames written.", n)
     return n
 

@@ -212,6 +212,7 @@ SIGNATURES = {
     "ssm_synthesize_upscaled_fwd": (_c_int, [SsmView, SsmView, _vp, SsmView, _c_int, _c_int, _c_int, _c_int, _vp]),
     "ssm_tile_stitch_fwd": (_c_int, [SsmView, SsmView] + [_c_int] * 14 + [_vp]),
     "ssm_frames_accumulate_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _vp]),
+    "ssm_luma_sad_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_int, _vp, _vp]),
 }
 
 _lib = None

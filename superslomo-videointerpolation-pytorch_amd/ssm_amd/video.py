@@ -17,13 +17,18 @@
   accumulate_host /       the shutter: an output frame as the mean of `samples` sub-frames over the open part of its interval
   ShutterPlanner          (Timeline(step, shutter=, samples=)), summed on the GPU in time order by ssm_frames_accumulate_fwd, whose numpy
                           yardstick accumulate_host is; the bookkeeping of its passes - VideoInterpolator(shutter=, shutter_samples=)
+  luma_sad_host / luma_sad   scene cuts: per frame pair the exact sum of |difference| of the 8-bit Y planes, by numpy (the yardstick) and by
+  / SceneCuts             ssm_luma_sad_fwd on the payloads as they stand on the device; the decision from those sums in Fractions, with no
+                          GPU in it - VideoInterpolator(scene_cut=): at a cut the output repeats the nearer input frame instead of a morph
 
 Out of scope: codecs, audio, more than 8 bits per sample, the recurrent configuration (N_FRAMES > 2); shutter integration in linear
 light, shutter weights other than the box, a shutter centred on the frame's instant or open for longer than the frame interval,
-variable-rate input, speeds that change within a clip.
+variable-rate input, speeds that change within a clip; a default scene-cut threshold, fades and dissolves, cuts judged on chroma,
+skipping the GPU work of a cut pair, scene cuts together with a shutter.
 """
 import collections
 import ctypes
+import functools
 import queue
 import re
 import sys
@@ -201,6 +206,13 @@ def accumulate_host(frames, acc, init, scale):
     return acc
 
 
+def luma_sad_host(ya, yb):
+    """Yardstick of ssm_luma_sad_fwd: uint8 Y planes [N,h,w] (numpy) -> uint64 [N], sums[n] = sum of |ya[n] - yb[n]| over the plane, exact."""
+    ya, yb = np.asarray(ya), np.asarray(yb)
+    assert ya.dtype == np.uint8 and yb.dtype == np.uint8 and ya.ndim == 3 and ya.shape == yb.shape
+    return np.abs(ya.astype(np.int64) - yb.astype(np.int64)).reshape(ya.shape[0], -1).sum(axis=1).astype(np.uint64)
+
+
 # ---- the kernels -------------------------------------------------------------------------------------------------------------------
 def frames_from_yuv(payload, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, cfg=None, pad_before_norm=True, out=None, multiple=32):
     """[N, frame_bytes] uint8 device tensor of Y4M payloads -> [N,3,Hp,Wp] normalised fp32 (into `out` if given); (Hp, Wp) =
@@ -229,6 +241,23 @@ def frames_to_yuv(x, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, cf
     assert out.is_contiguous() and tuple(out.shape) == (n, frame_bytes(h, w, siting)) and out.dtype == torch.uint8
     hb.check(hb.load().ssm_frames_to_yuv_fwd(hb.view_of(x), out.data_ptr(), n, h, w, top, left, _f3(mean), _f3(std), _table_ptr(),
                                              matrix, color_range, siting, hb.stream_ptr()))
+    return out
+
+
+def luma_sad(payload_a, payload_b, h, w, out=None):
+    """ssm_luma_sad_fwd on payloads: [N, frame_bytes] uint8 device tensors (rows of at least h * w bytes, unit stride within a row, any
+    row stride: views of one buffer, frames n and n + 1, are fine) -> int64 [N] on the device (into `out` if given), out[n] = the sum
+    over the h x w Y planes of |a_n - b_n|.  The words are unsigned and below 2^63: read them on the host as numpy uint64."""
+    for t in (payload_a, payload_b):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.shape[1] >= h * w and (t.shape[1] == 1 or t.stride(1) == 1), \
+            "payloads must be [N, at least h * w] uint8 tensors on the GPU with unit stride within a frame"
+    n = payload_a.shape[0]
+    assert payload_b.shape[0] == n and payload_b.device == payload_a.device, "as many frames in a as in b, on one device"
+    if out is None:
+        out = torch.empty(n, dtype=torch.int64, device=payload_a.device)
+    assert out.is_cuda and out.dtype == torch.int64 and out.dim() == 1 and out.shape[0] == n and out.is_contiguous()
+    hb.check(hb.load().ssm_luma_sad_fwd(payload_a.data_ptr(), payload_b.data_ptr(), payload_a.stride(0), payload_b.stride(0), n, h, w,
+                                        out.data_ptr(), hb.stream_ptr()))
     return out
 
 
@@ -441,6 +470,40 @@ def parse_shutter(text):
     return deg / 360
 
 
+def parse_scene_cut(text):
+    """A scene-cut threshold, "0.1" or "1/10" (or a number, or a Fraction) -> Fraction in (0, 1]; anything else is a ValueError naming
+    the value."""
+    try:
+        th = Fraction(text.strip() if isinstance(text, str) else text)
+    except (ValueError, TypeError, ZeroDivisionError):
+        raise ValueError("a scene-cut threshold is written as a decimal or a fraction, e.g. 0.1 or 1/10 (got %r)" % (text,)) from None
+    if not 0 < th <= 1:
+        raise ValueError("a scene-cut threshold lies above 0 and at most at 1 (got %r)" % (text,))
+    return th
+
+
+class SceneCuts:
+    """Which pairs of input frames are scene cuts, from their luma sums (luma_sad / luma_sad_host); no GPU in it, every quantity an
+    integer or a Fraction.  feed(s, pixels) takes the pairs in the order in which they run - a pair that a timeline skips is not fed -
+    and returns (is a cut, score):
+        m = Fraction(s, pixels)                      the mean absolute luma difference of the pair, 0 .. 255
+        score = min(m, |m - m_prev|) / 255           m_prev: the m of the pair fed before, 0 before the first
+        a cut iff score >= threshold                 then m_prev = m
+    The mean absolute frame difference damped by its own change: steady fast motion has a large m that changes little, a cut is a spike.
+    The first pair has nothing to be compared with and scores its m.  This is a convention and NOT backed by a measurement here; the
+    threshold, a Fraction in (0, 1], has no default and is the user's to choose.  Fades and dissolves are not looked for."""
+
+    def __init__(self, threshold):
+        self.threshold = parse_scene_cut(threshold)
+        self.m_prev = Fraction(0)
+
+    def feed(self, s, pixels):
+        m = Fraction(int(s), int(pixels))
+        score = min(m, abs(m - self.m_prev)) / 255
+        self.m_prev = m
+        return score >= self.threshold, score
+
+
 def timeline_step(in_rate, target_rate=None, speed=None):
     """step = speed * in_rate / out_rate as a Fraction: how far the input clock moves per output frame.  target_rate None: the input's
     rate; speed None: 1."""
@@ -605,20 +668,23 @@ class PassPlanner:
               one; otherwise the left frame is the right frame of the pair that ran before it (the one before in `pairs`, or the last
               of the pass before) and the row is the right frame's.
     end() closes what is open.  A frame that no output needs keeps no row: the next frame is read over it.  A frame that waits for its
-    right neighbour stays in one slot with it: a slot closes at pairs_per_batch pairs, at cap rows, or one row early when no frame waits."""
+    right neighbour stays in one slot with it: a slot closes at pairs_per_batch pairs, at cap rows, or one row early when no frame waits.
+    closed_index: beside `pairs` of the slot closed last, the i of each of its pairs (i, i + 1) - what the scene cuts are reported by."""
 
     def __init__(self, tl, pairs_per_batch, cap):
         assert cap >= 2
         self.tl, self.pb, self.cap = tl, pairs_per_batch, cap
         self.f = 0                 # frames read
         self.prev_right = -1       # the input frame that the last running pair left on the device as its right frame
+        self.closed_index = []
         self._open()
 
     def _open(self):
-        self.rows, self.order, self.pairs, self._of = 0, [], [], None
+        self.rows, self.order, self.pairs, self._of, self._index = 0, [], [], None, []
 
     def _close(self):
         out = (self.order, self.pairs)
+        self.closed_index = self._index
         self._open()
         return out
 
@@ -631,6 +697,7 @@ class PassPlanner:
                     own_left = self.prev_right != i
                     assert not own_left or self.rows >= 1
                     self.pairs.append((self.rows - 1 if own_left else self.rows, own_left, []))
+                    self._index.append(i)
                     self._of, self.prev_right = i, f
                 self.order.append(("interp", (len(self.pairs) - 1) * S + len(self.pairs[-1][2])))
                 self.pairs[-1][2].append(Timeline.t32(t))
@@ -754,8 +821,9 @@ class PassRing:
     protocol.  Free of the GPU: an event is anything with synchronize(), the writer anything with write_frame(buf).
 
     The producer take()s a free slot, fills it and hand()s it over with the event that says its rows are there (None: nothing was queued
-    on the GPU for it) and the row buffers to write, in order; a slot of None is an item that holds no slot (frame 0 of the fixed grid,
-    written from a buffer of its own).  The thread (daemon, `y4m-writer`) waits for the event, writes the rows and frees the slot, item by
+    on the GPU for it) and the row buffers to write, in order - or a callable that returns them, called on the thread once the event
+    has come (the scene cuts: which rows are written depends on what the pass computed); a slot of None is an item that holds no slot
+    (frame 0 of the fixed grid, written from a buffer of its own).  The thread (daemon, `y4m-writer`) waits for the event, writes the rows and frees the slot, item by
     item in the order handed over.  After the first exception on the thread nothing more is written and every slot handed over still
     comes back, so the producer never blocks in take(); it looks at `failure` and stops reading and submitting.  close() - leaving the
     `with` block - ends the thread, calls `settle` (the loop's device synchronise) and raises the stored exception, the object itself.
@@ -779,7 +847,7 @@ class PassRing:
                 if not self.failure:
                     if event is not None:
                         event.synchronize()
-                    for buf in rows:
+                    for buf in (rows() if callable(rows) else rows):
                         self.writer.write_frame(buf)
             except BaseException as e:          # noqa: BLE001 - handed to the caller's thread; keep releasing slots
                 self.failure.append(e)
@@ -827,6 +895,23 @@ def read_passes(reader, ring, plan, np_in, issue):
         raise Y4MError("the Y4M stream holds no frame")
 
 
+def sad_runs(lefts, rights):
+    """[(first pair, count)]: the pairs of a pass in maximal runs whose left rows and whose right rows both step evenly - what one
+    ssm_luma_sad_fwd call addresses with its two strides.  One run whenever every pair of the pass follows the one before (the fixed
+    grid, any slow motion) and for any two pairs; a timeline that skips pairs inside a pass of three or more may need a second call."""
+    runs, p = [], 0
+    while p < len(lefts):
+        e = p + 1
+        if e < len(lefts):
+            da, db = lefts[e] - lefts[p], rights[e] - rights[p]
+            e += 1
+            while e < len(lefts) and (lefts[e] - lefts[e - 1], rights[e] - rights[e - 1]) == (da, db):
+                e += 1
+        runs.append((p, e - p))
+        p = e
+    return runs
+
+
 def upload_times(times, slots, np_t, host_t, dev_t):
     """The engine's times of a pass, `slots` per pair: each pair's own (`times`: one list per pair), its last one repeated in the rest, and
     the last entry repeated after the last pair; filled into the ring slot's pinned buffer (host_t, np_t its numpy view) and queued for
@@ -859,7 +944,7 @@ class VideoInterpolator:
     rate rest on."""
 
     def __init__(self, model, cfg, upsample_rate=8, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
-                 tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8):
+                 tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8, scene_cut=None):
         """target_rate = (num, den) and / or speed (a Fraction, or what Fraction() takes; 1/4 is four times slower): the output follows
         Timeline(speed * input rate / target_rate) instead of the fixed grid of upsample_rate, which is then not used (see
         _run_timeline); with both None nothing changes.  flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
@@ -870,7 +955,12 @@ class VideoInterpolator:
         beside target_rate or speed: every output frame is the mean of shutter_samples sub-frames over that part of its interval
         (Timeline, _run_shutter).  Like the command line's --shutter it needs one of the two, since it averages over the interval of
         their timeline; speed=1 is the input's own rate with blur.  The 8 samples of the default are a convention, not backed by a
-        measurement of quality.  shutter_samples = 1, or shutter None, is the loop without a shutter."""
+        measurement of quality.  shutter_samples = 1, or shutter None, is the loop without a shutter.
+        scene_cut (a Fraction in (0, 1], or what Fraction() takes; no default value): the threshold of SceneCuts.  Every pass then also
+        sums the luma differences of its pairs on the GPU, and at a pair that SceneCuts calls a cut the writer puts out, instead of the
+        synthesised frames, the left input frame's own bytes at t < 1/2 and the right one's from there on; `cuts` lists (i, score) of
+        every cut pair (i, i + 1) after run().  The pair still runs on the GPU.  Not together with a shutter: an average across a cut
+        needs a definition of its own.  None: the loop as it is without the option, launch for launch."""
         from .coarse import check_scale
         from .tiles import check_args
         self.flow_scale = check_scale(flow_scale)
@@ -897,6 +987,10 @@ class VideoInterpolator:
         if shutter is not None:
             Timeline(1, shutter=shutter, samples=shutter_samples)          # refuses a bad value by name, here rather than at the first clip
         self.timed = target_rate is not None or speed is not None
+        self.scene_cut, self.cuts = None if scene_cut is None else parse_scene_cut(scene_cut), []
+        if scene_cut is not None and shutter is not None:
+            raise ValueError("scene_cut together with shutter is not defined: an average of sub-frames across a cut needs a definition of its "
+                             "own; give one of the two")
         if shutter is not None and not self.timed:
             raise ValueError("a shutter averages over the interval of an output frame of target_rate / speed: give one of them (speed=1 "
                              "keeps the input's rate)")
@@ -938,18 +1032,52 @@ class VideoInterpolator:
             raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
         return Clip(h, w, siting, fb, matrix, crange, dev, 32 * self.flow_scale, *self.canvas(h, w))
 
+    def _cut_state(self, n, depth, pairs, clip):
+        """What the scene cuts add to a mode's buffers: SceneCuts, the sums of a pass on the device (per stream) and in the pinned ring slot
+        (per slot, with its numpy view as uint64), and the writer thread's copy of the input frame before the next pass's first pair."""
+        host = [torch.empty(pairs, dtype=torch.int64).pin_memory() for _ in range(depth)]
+        return (SceneCuts(self.scene_cut), [torch.empty(pairs, dtype=torch.int64, device=clip.dev) for _ in range(n)], host,
+                [t.numpy().view(np.uint64) for t in host], np.empty(clip.fb, np.uint8))
+
+    def _cut_rows(self, cuts, pixels, sums, pairs, order, carried):
+        """The rows of a pass under scene cuts: a generator that PassRing calls on the writer thread once the pass's event has come.
+        sums: the pass's luma sums in its ring slot; pairs: [(i, left frame's host bytes or None for `carried`, right frame's)] in the
+        order in which they ran; order: [(input frame's bytes, None) | (synthesised frame's bytes, (pair's place in `pairs`, exact t))] in
+        write order.  Feeds SceneCuts, notes the cuts, and puts the nearer input frame in the place of a cut pair's synthesised frames;
+        at the end `carried` takes the last pair's right frame, the left frame of a next pass's first pair (its slot is free by then)."""
+        verdict = []
+        for p, (i, _, _) in enumerate(pairs):
+            cut, score = cuts.feed(int(sums[p]), pixels)
+            verdict.append(cut)
+            if cut:
+                self.cuts.append((i, score))
+        for buf, at in order:
+            if at is not None and verdict[at[0]]:
+                _, lf, rt = pairs[at[0]]
+                buf = (carried if lf is None else lf) if at[1] < Fraction(1, 2) else rt
+            yield buf
+        if pairs:
+            carried[:] = pairs[-1][2]
+
     @torch.no_grad()
     def run(self, reader, writer):
         """Returns the number of frames written: (n - 1) * upsample_rate + 1 for n input frames (with target_rate / speed:
         floor((n - 1) / step) + 1; with a shutter: Timeline.n_outputs(n))."""
         clip = self._clip(reader, writer)
+        self.cuts = []
         if not self.timed:
             return self._run_fixed(clip, reader, writer)
         return self._run_shutter(clip, reader, writer) if self.samples > 1 else self._run_timeline(clip, reader, writer)
 
     def _run_fixed(self, clip, reader, writer):
         """run() on the fixed grid of upsample_rate: planes[k] is [carried left frame | pairs_per_batch new frames], the pairs an
-        overlapping view of it; the times go up once per run.  Frame 0 is written from a pinned buffer of its own before any pass."""
+        overlapping view of it; the times go up once per run.  Frame 0 is written from a pinned buffer of its own before any pass.
+
+        With scene_cut a stream's payload buffer has one row more in front: row 0 holds the Y plane of the frame before the pass's first,
+        so that the left planes of a pass's pairs are rows 0 .. pb - 1, the right ones rows 1 .. pb, and one ssm_luma_sad_fwd call takes
+        them all.  A pass puts the Y plane of its last frame into row 0 of the NEXT stream's buffer, after its own call and before it
+        records `ingested`: the pass that reads it waits for that event, and the pass that read the row before has recorded its own
+        event (after its call) earlier in the chain of waits.  The sums go back to the pass's ring slot ahead of `done`."""
         from .evaluation import t_values
         h, w, siting, fb, matrix, crange, dev, mult, hp, wp = clip
         pipe = self._pipeline(hp, wp, dev)
@@ -960,13 +1088,18 @@ class VideoInterpolator:
         host_out = [torch.empty(pb * nt, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
         np_in, np_out = [t.numpy() for t in host_in], [t.numpy() for t in host_out]
         done = [torch.cuda.Event() for _ in range(depth)]
-        dev_in = [torch.empty(pb, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
+        cuts, lead = None, 0
+        if self.scene_cut is not None:
+            (cuts, dev_sums, host_sums, np_sums, carried), lead = self._cut_state(n, depth, pb, clip), 1
+        dev_in = [torch.empty(lead + pb, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
         dev_out = [torch.empty(pb * nt, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
         planes = [torch.empty(pb + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [carried left frame | new frames]
         ingested = [torch.cuda.Event() for _ in range(n)]
         first = torch.empty(1, fb, dtype=torch.uint8).pin_memory()
         if not reader.read_frame_into(first.numpy()[0]):
             raise Y4MError("the Y4M stream holds no frame")
+        if cuts is not None:
+            carried[:] = first.numpy()[0]
         torch.cuda.synchronize(dev)
         written = 1
         with PassRing(depth, writer, lambda: torch.cuda.synchronize(dev)) as ring:
@@ -974,8 +1107,11 @@ class VideoInterpolator:
             # frame 0: ingested where pass 0 looks for its carried left frame
             last = (n - 1) % n
             with torch.cuda.stream(pipe.streams[last]):
-                dev_in[last][:1].copy_(first, non_blocking=True)
-                frames_from_yuv(dev_in[last][:1], h, w, siting, matrix, crange, self.cfg, True, out=planes[last][pb:], multiple=mult)
+                new = dev_in[last][lead:]
+                new[:1].copy_(first, non_blocking=True)
+                frames_from_yuv(new[:1], h, w, siting, matrix, crange, self.cfg, True, out=planes[last][pb:], multiple=mult)
+                if cuts is not None:
+                    dev_in[0][0, :h * w].copy_(new[0, :h * w])
                 ingested[last].record()
             j, eof = 0, False
             while not eof and not ring.failure:
@@ -992,18 +1128,31 @@ class VideoInterpolator:
                 k, kprev = j % n, (j - 1) % n
                 st = pipe.streams[k]
                 with torch.cuda.stream(st):
-                    dev_in[k].copy_(host_in[r], non_blocking=True)
+                    new = dev_in[k][lead:]
+                    new.copy_(host_in[r], non_blocking=True)
                     st.wait_event(ingested[kprev])
                     planes[k][0].copy_(planes[kprev][pb])
-                    frames_from_yuv(dev_in[k], h, w, siting, matrix, crange, self.cfg, True, out=planes[k][1:], multiple=mult)
+                    frames_from_yuv(new, h, w, siting, matrix, crange, self.cfg, True, out=planes[k][1:], multiple=mult)
+                    if cuts is not None:
+                        luma_sad(dev_in[k][:pb], dev_in[k][1:], h, w, out=dev_sums[k])
+                        dev_in[(j + 1) % n][0, :h * w].copy_(dev_in[k][pb, :h * w])
                     ingested[k].record()
                     x = planes[k]
                     img6 = x.view(1, 6, hp, wp) if pb == 1 else x.as_strided((pb, 6, hp, wp), (3 * hp * wp, hp * wp, wp, 1))
                     frames = pipe.engines[k].run(img6, t_dev, False)
                     frames_to_yuv(frames, h, w, siting, matrix, crange, self.cfg, out=dev_out[k])
                     host_out[r].copy_(dev_out[k], non_blocking=True)
+                    if cuts is not None:
+                        host_sums[r].copy_(dev_sums[k], non_blocking=True)
                     done[r].record()
-                ring.hand(r, done[r], [np_out[r][row] if kind == "interp" else np_in[r][row] for kind, row in pass_order(valid, nt)])
+                rows = [np_out[r][row] if kind == "interp" else np_in[r][row] for kind, row in pass_order(valid, nt)]
+                if cuts is not None:
+                    i0 = (written - 1) // self.rate
+                    at = [None if kind == "orig" else (row // nt, Fraction(row % nt + 1, self.rate)) for kind, row in pass_order(valid, nt)]
+                    rows = functools.partial(self._cut_rows, cuts, h * w, np_sums[r],
+                                             [(i0 + p, np_in[r][p - 1] if p else None, np_in[r][p]) for p in range(valid)],
+                                             list(zip(rows, at)), carried)
+                ring.hand(r, done[r], rows)
                 written += valid * self.rate
                 j += 1
         return written
@@ -1020,7 +1169,13 @@ class VideoInterpolator:
         Each uploaded frame is ingested once: a pair's left frame is the previous running pair's right frame copied on the device, or,
         after a pair that did not run, ingested with the right one.  A pass short of pairs (end of clip, or a slot full of frames passed
         through) leaves the planes of its unused entries as they are: finite, and never read back.  Memory is fixed by the frame size,
-        n_streams, pairs_per_batch and slots."""
+        n_streams, pairs_per_batch and slots.
+
+        With scene_cut, as on the fixed grid: row 0 in front of a stream's payloads holds the Y plane of the right frame of the pair
+        that ran last in the pass before, written by that pass behind its own calls and ahead of its `ingested`; a pair's left plane is
+        its own uploaded row, the right row of the pair before it, or row 0.  The rows of the pairs that run step evenly unless the
+        timeline skips pairs inside a pass (sad_runs): one ssm_luma_sad_fwd call then, one per run otherwise.  Only pairs that run are
+        summed and fed to SceneCuts."""
         h, w, siting, fb, matrix, crange, dev, mult, hp, wp = clip
         tl = self.timeline(reader.rate)
         S, pb, n = tl.slots, self.pb, self.n_streams
@@ -1031,8 +1186,12 @@ class VideoInterpolator:
         host_t = [torch.full((pb * max(S, 1),), 0.5, dtype=torch.float32).pin_memory() for _ in range(depth)]
         np_in, np_out, np_t = [t.numpy() for t in host_in], [t.numpy() for t in host_out], [t.numpy() for t in host_t]
         done = [torch.cuda.Event() for _ in range(depth)]
+        cuts, lead = None, 0
+        if self.scene_cut is not None and pipe is not None:
+            (cuts, dev_sums, host_sums, np_sums, carried), lead = self._cut_state(n, depth, pb, clip), 1
+        plan = PassPlanner(tl, pb, cap)
         if pipe is not None:
-            dev_in = [torch.empty(cap, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
+            dev_in = [torch.empty(lead + cap, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
             dev_out = [torch.empty(pb * S, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
             dev_t = [torch.empty(pb * S, dtype=torch.float32, device=dev) for _ in range(n)]
             planes = [torch.zeros(pb, 2, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [pair][left | right]
@@ -1047,14 +1206,23 @@ class VideoInterpolator:
             with torch.cuda.stream(st):
                 if j:
                     st.wait_event(ingested[(j - 1) % n])          # the carried frame; and pass j - n + 1 is done with planes[k]
+                new = dev_in[k][lead:]
                 for p, (row, own_left, ts) in enumerate(pairs):
                     rows = 2 if own_left else 1
-                    dev_in[k][row:row + rows].copy_(host_in[r][row:row + rows], non_blocking=True)
+                    new[row:row + rows].copy_(host_in[r][row:row + rows], non_blocking=True)
                     if not own_left:
                         planes[k][p, 0].copy_(planes[k][p - 1, 1] if p else planes[(j - 1) % n][last_p[0], 1])
-                    frames_from_yuv(dev_in[k][row:row + rows], h, w, siting, matrix, crange, self.cfg, True, out=planes[k][p, 2 - rows:],
+                    frames_from_yuv(new[row:row + rows], h, w, siting, matrix, crange, self.cfg, True, out=planes[k][p, 2 - rows:],
                                     multiple=mult)
                 upload_times([ts for _, _, ts in pairs], S, np_t[r], host_t[r], dev_t[k])
+                if cuts is not None:
+                    rights = [lead + row + (1 if own_left else 0) for row, own_left, _ in pairs]          # rows of dev_in[k]
+                    lefts = [lead + row if own_left else (rights[p - 1] if p else 0) for p, (row, own_left, _) in enumerate(pairs)]
+                    for p, m in sad_runs(lefts, rights):
+                        da, db = (lefts[p + 1] - lefts[p], rights[p + 1] - rights[p]) if m > 1 else (1, 1)
+                        luma_sad(dev_in[k][lefts[p]:lefts[p] + (m - 1) * da + 1:da], dev_in[k][rights[p]:rights[p] + (m - 1) * db + 1:db], h, w,
+                                 out=dev_sums[k][p:p + m])
+                    dev_in[(j + 1) % n][0, :h * w].copy_(dev_in[k][rights[-1], :h * w])
                 ingested[k].record()
                 last_p[0] = len(pairs) - 1
                 frames = pipe.engines[k].run(planes[k].view(pb, 6, hp, wp), dev_t[k], False)
@@ -1065,6 +1233,8 @@ class VideoInterpolator:
                 for o, m in spans:
                     frames_to_yuv(frames[o:o + m], h, w, siting, matrix, crange, self.cfg, out=dev_out[k][o:o + m])
                     host_out[r][o:o + m].copy_(dev_out[k][o:o + m], non_blocking=True)
+                if cuts is not None:
+                    host_sums[r].copy_(dev_sums[k], non_blocking=True)
                 done[r].record()
 
         written = j = 0          # frames written, passes issued
@@ -1075,11 +1245,19 @@ class VideoInterpolator:
             if on_gpu:
                 submit(j, r, pairs)
                 j += 1
-            ring.hand(r, done[r] if on_gpu else None, [np_out[r][row] if kind == "interp" else np_in[r][row] for kind, row in order])
+            rows = [np_out[r][row] if kind == "interp" else np_in[r][row] for kind, row in order]
+            if cuts is not None and on_gpu:
+                exact = [tl.times(i) for i in plan.closed_index]          # the pairs' times as Fractions, beside the planner's fp32
+                at = [None if kind == "orig" else (row // S, exact[row // S][row % S]) for kind, row in order]
+                rights = [np_in[r][row + (1 if own_left else 0)] for row, own_left, _ in pairs]
+                host_pairs = [(i, np_in[r][row] if own_left else (rights[p - 1] if p else None), rights[p])
+                              for p, (i, (row, own_left, _)) in enumerate(zip(plan.closed_index, pairs))]
+                rows = functools.partial(self._cut_rows, cuts, h * w, np_sums[r], host_pairs, list(zip(rows, at)), carried)
+            ring.hand(r, done[r] if on_gpu else None, rows)
             written += len(order)
 
         with PassRing(depth, writer, lambda: torch.cuda.synchronize(dev)) as ring:
-            read_passes(reader, ring, PassPlanner(tl, pb, cap), np_in, issue)
+            read_passes(reader, ring, plan, np_in, issue)
         return written
 
     def _run_shutter(self, clip, reader, writer):
