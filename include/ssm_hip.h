@@ -652,7 +652,7 @@ int ssm_frames_to_yuv_fwd(ssm_view in, unsigned char *frames_yuv, int N, int H, 
  * - the shutter opens at the frame's own instant, so no sample lies before input frame 0.  With i = floor(tau), t = tau - i: t == 0 is
  * input frame i's ingested planes, anything else the frame synthesised between i and i + 1 at Timeline.t32(t).  Output k exists iff its
  * last sample does: tau(k, S-1) <= n - 1.  The mean is taken of the path's normalised fp32 planes - of the gamma-coded R'G'B' values, as a
- * frame-mixing filter does; integration in linear light is out of scope.  S = 1 is the timeline without a shutter.  S = 8, the default of
+ * frame-mixing filter does - or, through ssm_frames_accumulate_light_fwd below, of the light those values stand for.  S = 1 is the timeline without a shutter.  S = 8, the default of
  * the streamed loop, is a convention, not backed by a measurement of quality.
  * ssm_frames_accumulate_fwd: src [N,C,H,W], acc [1,C,H,W], both strided views (acc.sb is not read).  Per element, one rounded fp32
  * operation per step (no fused multiply-add), in this order:
@@ -669,6 +669,40 @@ int ssm_frames_to_yuv_fwd(ssm_view in, unsigned char *frames_yuv, int N, int H, 
  * grid's y axis ends at 65535); a row stride shorter than W; init outside {0, 1}; a scale that is not finite; src and acc address ranges
  * that overlap. */
 int ssm_frames_accumulate_fwd(ssm_view src, ssm_view acc, int N, int C, int H, int W, int init, float scale, void *stream);
+
+/* ---- shutter in linear light (csrc/ssm_video.hip; beyond the reference's operator surface) ----------------------------------------------
+ * A sensor integrates light, not code values: the mean of codes 0 and 255 is 128 on the codes and 188 in light under sRGB.  A light curve
+ * maps a coded value c in [0, 1] to light L in [0, 1]; `curve` is a HOST pointer to one row of SSM_LIGHT_ROW floats, built in float64
+ * and rounded once to fp32 by ssm_amd.video.light_curve(name) from the curve's (thr, slope, a, g):
+ *   [0] thr  [1] 1/slope  [2] a  [3] 1/(1+a)  [4] g      decode(c) = c <= thr ? c * [1] : ((c + a) * [3]) ^ g
+ *   [5] thr/slope  [6] slope  [7] 1+a  [8] 1/g           encode(L) = L <= [5] ? L * slope : [7] * L ^ [8] - a
+ *   bt709   the inverse of the BT.709 camera curve (slope 4.5, exponent 0.45), with the two constants the standard prints to three digits
+ *           (0.018, 1.099) taken to the digits at which its two pieces join in value and slope: scene light, what a shutter integrates
+ *   srgb    0.04045, 12.92, 0.055, 2.4      bt1886   a pure power of 2.4 (thr = a = 0, slope = 1): the reference display with zero black
+ * ssm_frames_accumulate_light_fwd: src [N,3,H,W], acc [1,3,H,W], strided views as for ssm_frames_accumulate_fwd; mean3 / std3 as for
+ * ssm_frames_to_yuv_fwd.  Per element of plane p, in fp32, every operation rounded (no fused multiply-add), with
+ *     dec(v) = v <= black[p] ? 0 : decode(min(max(v * std[p] + mean[p], 0), 1)),   black[p] = (0 / 255 - mean[p]) / std[p]
+ *   - the egress kernel's denormalise, clamped, then the curve.  The comparison with the ingest kernels' black is the clamp's lower end
+ *   said exactly: fp32 black * std + mean need not be 0 (the config's G plane gives 2^-25), and black must add no light.
+ *   1. s = init ? dec(src[0]) : acc + dec(src[0])
+ *   2. s = s + dec(src[n])   for n = 1 .. N-1, in increasing n
+ *   3. r = s * scale
+ *   4. acc = encode ? (encode(r) - mean[p]) / std[p] : r
+ * x ^ e is 2 ^ (e * log2 x) by v_log_f32, one multiply and v_exp_f32 (1 ulp each by the ISA manual): the result is held to an error bound
+ * against the float64 evaluation ssm_amd.video.accumulate_light_host, not to bits (tests/test_video_light_cpu.py derives the bound,
+ * tests/test_hip_shutter_light.py asserts it).  Between an output's first call (init = 1) and its last (encode = 1, scale = fp32(1 / S))
+ * the accumulator holds sums of light; after the last it holds normalised coded planes that ssm_frames_to_yuv_fwd reads unchanged.
+ * The clamp is part of the definition: a synthesised value below 0 or above 1 counts as 0 or 1 before it is light, where the coded mean
+ * of ssm_frames_accumulate_fwd lets it cancel against its neighbours in time.  Two properties hold exactly: a coded value <= 0 adds
+ * exactly 0, and L = 0 encodes to exactly (0 - mean) / std, the ingest kernels' black, so a black region stays bit-identical black
+ * through any number of samples.  INPUTS MUST BE FINITE.  Reads `acc` at most once, writes it once, nothing outside its H x W region;
+ * access widths and the packed-fp32 fence as for ssm_frames_accumulate_fwd.
+ * SSM_E_ARG (nothing is launched) for null pointers; N, H or W < 1; N > 65535; H > 262140; a row stride shorter than W; init or encode
+ * outside {0, 1}; a scale, mean, std or curve constant that is not finite; a std that is not above 0; a curve row with g, 1/g, slope or 1/slope <= 0;
+ * src and acc address ranges that overlap. */
+#define SSM_LIGHT_ROW 9
+int ssm_frames_accumulate_light_fwd(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale, const float *mean3,
+                                    const float *std3, const float *curve, int encode, void *stream);
 
 /* ---- scene cuts of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) -------------------------------
  * Definition (ssm_amd.video.SceneCuts(threshold), everything in exact integers and fractions).  For the pair of input frames (i, i + 1)

@@ -12,6 +12,9 @@
 //   frames_accumulate_kernel the shutter of the streamed loop: N frames summed, in increasing n, into one fp32 accumulator
 //                            that is read at most once and written once per launch; one lane = 4 consecutive pixels of a row of one
 //                            channel (16-byte loads and stores), or one pixel when a view does not allow it
+//   frames_accumulate_light_kernel  the same sum taken in light: every value is denormalised, clamped to [0, 1] and decoded
+//                            by one of the light curves of ssm_amd.video.light_curve before it is added, and the call that closes an output
+//                            encodes and normalises the mean again; the power is v_log_f32, a multiply and v_exp_f32
 //   luma_sad_kernel          scene cuts of the streamed loop: per frame pair the exact sum of |a - b| over the 8-bit Y planes;
 //                            one lane = 16 consecutive bytes of each plane (one 16-byte load per operand), or byte loads where a plane
 //                            does not start on a 16-byte boundary; v_sad_u8 into a 32-bit lane sum, shuffles, one 64-bit atomic per workgroup
@@ -294,6 +297,70 @@ __global__ __launch_bounds__(256) void frames_accumulate_kernel(ssm_view src, ss
     }
 }
 
+// ---- shutter in linear light ----------------------------------------------------------------------------------------------------------
+// one row of ssm_amd.video.light_curve (include/ssm_hip.h: SSM_LIGHT_ROW floats)
+struct LightRow {
+    float thr, islope, a, i1a, g;          // decode: c <= thr ? c * islope : ((c + a) * i1a) ^ g
+    float lthr, slope, a1, ig;             // encode: L <= lthr ? L * slope : a1 * L ^ ig - a
+};
+static_assert(sizeof(LightRow) == SSM_LIGHT_ROW * sizeof(float), "curve row");
+
+// x ^ e for x >= 0 as 2 ^ (e log2 x): v_log_f32, v_mul_f32, v_exp_f32, each 1 ulp by the ISA manual.  x = 0 gives log2 = -inf and 2 ^ -inf = 0.
+__device__ __forceinline__ float pow_fast(float x, float e) { return __builtin_amdgcn_exp2f(e * __builtin_amdgcn_logf(x)); }
+
+// black = (0 - mean) / sd as the ingest kernels round it.  fp32 (black * sd + mean) need not be 0 (the config's G plane gives 2^-25), so a
+// value at or below black is taken as c = 0 by comparison: black stays exactly black, and sd > 0 makes the comparison the clamp's own.
+__device__ __forceinline__ float light_decode(float v, float sd, float mean, float black, const LightRow &k) {
+    const float c = v <= black ? 0.0f : clampf(v * sd + mean, 0.0f, 1.0f);          // the egress kernel's denormalise, clamped
+    const float p = pow_fast((c + k.a) * k.i1a, k.g);
+    return c <= k.thr ? c * k.islope : p;
+}
+
+__device__ __forceinline__ float light_encode(float l, float sd, float mean, const LightRow &k) {
+    const float p = k.a1 * pow_fast(l, k.ig) - k.a;
+    const float c = l <= k.lthr ? l * k.slope : p;              // l = 0: c = 0, and (0 - mean) / sd is the ingest kernel's black
+    return (c - mean) / sd;
+}
+
+// s = init ? dec(src[0]) : acc + dec(src[0]);  s = s + dec(src[n]), n = 1 .. N-1;  r = s * scale;  acc = encode ? enc(r) : r - the structure of
+// frames_accumulate_kernel: independent loads, the accumulator read at most once and written once.  Channel = blockIdx.z (three of them).
+template <int V>          // pixels per lane: 4 (float4 accesses) or 1
+__global__ __launch_bounds__(256) void frames_accumulate_light_kernel(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale,
+                                                                      Norm3 nm, LightRow k, int encode) {
+    const int x = (blockIdx.x * 64 + threadIdx.x) * V, y = blockIdx.y * 4 + threadIdx.y, c = blockIdx.z;
+    if (x >= W || y >= H) return;          // V = 4: W % 4 == 0, so x + 3 < W
+    const float mean = c == 0 ? nm.m[0] : (c == 1 ? nm.m[1] : nm.m[2]), sd = c == 0 ? nm.s[0] : (c == 1 ? nm.s[1] : nm.s[2]);
+    const float black = (0.0f / 255.0f - mean) / sd;          // the ingest kernels' expression
+    const float *s = src.ptr + (long long)c * src.sc + (long long)y * src.sh + x;
+    float *a = acc.ptr + (long long)c * acc.sc + (long long)y * acc.sh + x;
+    if constexpr (V == 4) {
+        const float4 f0 = *reinterpret_cast<const float4 *>(s);
+        float4 v = make_float4(light_decode(f0.x, sd, mean, black, k), light_decode(f0.y, sd, mean, black, k),
+                               light_decode(f0.z, sd, mean, black, k), light_decode(f0.w, sd, mean, black, k));
+        if (!init) {
+            const float4 o = *reinterpret_cast<const float4 *>(a);
+            v = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
+        }
+#pragma unroll 4
+        for (int n = 1; n < N; ++n) {
+            const float4 f = *reinterpret_cast<const float4 *>(s + (long long)n * src.sb);
+            v = make_float4(v.x + light_decode(f.x, sd, mean, black, k), v.y + light_decode(f.y, sd, mean, black, k),
+                            v.z + light_decode(f.z, sd, mean, black, k), v.w + light_decode(f.w, sd, mean, black, k));
+        }
+        v = make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale);
+        if (encode) v = make_float4(light_encode(v.x, sd, mean, k), light_encode(v.y, sd, mean, k), light_encode(v.z, sd, mean, k),
+                                    light_encode(v.w, sd, mean, k));
+        *reinterpret_cast<float4 *>(a) = v;
+    } else {
+        float v = light_decode(*s, sd, mean, black, k);
+        if (!init) v = *a + v;
+#pragma unroll 4
+        for (int n = 1; n < N; ++n) v = v + light_decode(s[(long long)n * src.sb], sd, mean, black, k);
+        v = v * scale;
+        *a = encode ? light_encode(v, sd, mean, k) : v;
+    }
+}
+
 // ---- scene cuts: luma differences summed ---------------------------------------------------------------------------------------------
 // sums[n] += sum over this workgroup's span of |a_n[i] - b_n[i]|, i over the H * W bytes of plane n.  A lane takes SAD_CHUNKS pieces of 16
 // bytes, SAD_LANES * 16 bytes apart (a wave's loads are contiguous); four bytes go through one v_sad_u8 (sum of the four absolute byte
@@ -473,6 +540,39 @@ extern "C" int ssm_frames_accumulate_fwd(ssm_view src, ssm_view acc, int N, int 
         SSM_LAUNCH(frames_accumulate_kernel<1>, dim3((W + 63) / 64, (H + 3) / 4, C), dim3(64, 4), 0, (hipStream_t)stream, src, acc, N, H, W, init,
                    scale);
     return ssm::check_launch("ssm_frames_accumulate_fwd");
+}
+
+extern "C" int ssm_frames_accumulate_light_fwd(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale, const float *mean3,
+                                               const float *std3, const float *curve, int encode, void *stream) {
+    SSM_REQUIRE(src.ptr && acc.ptr && mean3 && std3 && curve, "frames_accumulate_light: null pointer");
+    SSM_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && (H + 3) / 4 <= 65535, "frames_accumulate_light: bad sizes N=%d H=%d W=%d", N, H, W);
+    SSM_REQUIRE(src.sh >= W && acc.sh >= W, "frames_accumulate_light: row strides %d (src), %d (acc) shorter than W=%d", src.sh, acc.sh, W);
+    SSM_REQUIRE(init == 0 || init == 1, "frames_accumulate_light: init must be 0 or 1 (got %d)", init);
+    SSM_REQUIRE(encode == 0 || encode == 1, "frames_accumulate_light: encode must be 0 or 1 (got %d)", encode);
+    SSM_REQUIRE(std::isfinite(scale), "frames_accumulate_light: scale must be finite (got %g)", (double)scale);
+    for (int c = 0; c < 3; ++c)
+        SSM_REQUIRE(std::isfinite(mean3[c]) && std::isfinite(std3[c]) && std3[c] > 0.0f,
+                    "frames_accumulate_light: mean %g / std %g of channel %d: need finite values and a std above 0", (double)mean3[c],
+                    (double)std3[c], c);
+    LightRow k;
+    for (int i = 0; i < SSM_LIGHT_ROW; ++i) reinterpret_cast<float *>(&k)[i] = curve[i];
+    bool finite = true;
+    for (int i = 0; i < SSM_LIGHT_ROW; ++i) finite = finite && std::isfinite(curve[i]);
+    SSM_REQUIRE(finite && k.g > 0.0f && k.ig > 0.0f && k.slope > 0.0f && k.islope > 0.0f,
+                "frames_accumulate_light: curve row with g=%g (1/g=%g), slope=%g (1/slope=%g): need finite constants, g > 0 and slope > 0",
+                (double)k.g, (double)k.ig, (double)k.slope, (double)k.islope);
+    long long s0, s1, a0, a1;
+    view_range(src, N, 3, H, W, &s0, &s1);
+    view_range(acc, 1, 3, H, W, &a0, &a1);
+    SSM_REQUIRE(s1 <= a0 || a1 <= s0, "frames_accumulate_light: src and acc overlap (%lld bytes apart)", a0 - s0);
+    const bool vec = W % 4 == 0 && view_aligned(src, 4) && view_aligned(acc, 4);
+    if (vec)
+        SSM_LAUNCH(frames_accumulate_light_kernel<4>, dim3((W / 4 + 63) / 64, (H + 3) / 4, 3), dim3(64, 4), 0, (hipStream_t)stream, src, acc, N, H,
+                   W, init, scale, norm_of(mean3, std3), k, encode);
+    else
+        SSM_LAUNCH(frames_accumulate_light_kernel<1>, dim3((W + 63) / 64, (H + 3) / 4, 3), dim3(64, 4), 0, (hipStream_t)stream, src, acc, N, H, W,
+                   init, scale, norm_of(mean3, std3), k, encode);
+    return ssm::check_launch("ssm_frames_accumulate_light_fwd");
 }
 
 extern "C" int ssm_luma_sad_fwd(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b, int N, int H, int W,

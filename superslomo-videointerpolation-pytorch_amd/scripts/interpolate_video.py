@@ -25,8 +25,13 @@ frame's own bytes; pairs that get no frame are not run.  Neither goes together w
 --shutter DEG [--shutter_samples S], with --fps or --speed: every output frame is the mean of S sub-frames (default 8, a convention) spread
 over the first DEG / 360 of its interval, as a camera at the output rate with that shutter angle would have blurred it - 60 -> 24 with
 --shutter 180 instead of dropped frames that strobe, slow motion with a chosen amount of blur, or blurred / sharp frame pairs from
-high-rate footage.  The mean is taken of the gamma-coded R'G'B' values, as a frame-mixing filter does, not in linear light; every output
-frame then comes from the GPU, input frames are no longer passed through.  The header's rate is what it is without --shutter.
+high-rate footage.  Every output frame then comes from the GPU, input frames are no longer passed through.  The header's rate is what it
+is without --shutter.  --shutter_light coded|bt709|srgb|bt1886 says of what the mean is taken: of the gamma-coded R'G'B' values, as a
+frame-mixing filter does (coded, the default), or of the light they stand for under that curve, which is what a sensor integrates - the
+mean of codes 0 and 255 is 128 on the codes and 188 in light under sRGB, so streaks of bright objects over a dark ground keep their
+brightness.  Which curve a clip wants depends on how it was graded (bt709: camera-referred material; srgb, bt1886: material mastered on a
+display); no Y4M header says, so the choice is yours.  Values the network synthesises outside [0, 1] are clipped before they count as
+light.  The curve acts on R'G'B' after the matrix and is independent of --matrix and --range.
 
 --scene_cut T (a decimal or a fraction in (0, 1]; no default value - the option is off unless given): every pair of input frames is also
 scored by ssm_amd.video.SceneCuts from the sum of its absolute luma differences (taken on the GPU, beside the pair's own work), and a pair
@@ -81,6 +86,9 @@ def getargs(argv=None):
                              "over DEG / 360 of its interval. Needs --fps or --speed. Default: off.")
     parser.add_argument("--shutter_samples", type=int, default=8, metavar="S",
                         help="With --shutter: sub-frames per output frame (a convention, not a measured optimum). Default 8.")
+    parser.add_argument("--shutter_light", choices=V.SHUTTER_LIGHTS, default="coded",
+                        help="With --shutter: average the coded values (coded) or the light they stand for under a curve (bt709, srgb, "
+                             "bt1886); which curve fits depends on how the clip was graded. Default coded.")
     parser.add_argument("--scene_cut", type=_named(V.parse_scene_cut), default=None, metavar="T",
                         help="Scene-cut threshold as a decimal or a fraction in (0, 1] (0.1, 1/10): a pair of input frames whose score reaches it "
                              "gets copies of its input frames instead of synthesised ones. A convention, no measured optimum; no default "
@@ -109,6 +117,8 @@ def getargs(argv=None):
                          "together with --upsample_rate or --slowmo")
         if args.upsample_rate is None:
             args.upsample_rate = 8
+    if args.shutter_light != "coded" and args.shutter is None:
+        parser.error("--shutter_light %s is the light in which --shutter averages: it needs --shutter" % args.shutter_light)
     if args.scene_cut is not None and args.shutter is not None:
         parser.error("--scene_cut does not go together with --shutter: an average of sub-frames across a cut needs a definition of its own")
     if args.shutter is not None and args.shutter_samples < 1:
@@ -128,14 +138,16 @@ def main(argv=None, model=None):
     timed = args.fps is not None or args.speed is not None
     vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate or 8, matrix=matrix, color_range=crange,
                              flow_scale=args.flow_scale, tile=args.tile, halo=args.halo, blend=args.blend, target_rate=args.fps, speed=args.speed,
-                             shutter=args.shutter, shutter_samples=args.shutter_samples, scene_cut=args.scene_cut)
+                             shutter=args.shutter, shutter_samples=args.shutter_samples, scene_cut=args.scene_cut,
+                             shutter_light=args.shutter_light)
     with V.Y4MReader(args.input) as reader:
         if timed:
             rate = args.fps or reader.rate
             tl = vi.timeline(reader.rate)
             log.info("[%s] timeline: step = %s input frames per output frame, slots = %d times per pair", args.expt, tl.step, tl.slots)
             if tl.samples > 1:
-                log.info("[%s] shutter: %s of the interval in %d samples", args.expt, tl.shutter, tl.samples)
+                log.info("[%s] shutter: %s of the interval in %d samples, averaged in %s", args.expt, tl.shutter, tl.samples,
+                         "coded values" if args.shutter_light == "coded" else "light (%s)" % args.shutter_light)
         else:
             rate = V.output_rate(reader.rate, args.upsample_rate, args.slowmo)
         out_range = crange if crange is not None else (reader.color_range if reader.color_range is not None else V.LIMITED)

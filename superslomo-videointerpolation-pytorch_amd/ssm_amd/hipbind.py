@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("SSM_HIP_LIB") or os.path.join(os.path.dirname(_HERE),
 SSM_PADX = 4
 SSM_PADY = 3
 SSM_TAIL_SLACK_FLOATS = 1 << 16
+SSM_LIGHT_ROW = 9      # floats in a light curve's row (include/ssm_hip.h; ssm_amd.video.light_curve)
 SSM_FLAG_LRELU = 1
 SSM_FLAG_MASK = 8      # the `add` view is a mask source: out = conv(x) * (add > 0 ? 1 : slope) (include/ssm_hip.h)
 
@@ -212,6 +213,7 @@ SIGNATURES = {
     "ssm_synthesize_upscaled_fwd": (_c_int, [SsmView, SsmView, _vp, SsmView, _c_int, _c_int, _c_int, _c_int, _vp]),
     "ssm_tile_stitch_fwd": (_c_int, [SsmView, SsmView] + [_c_int] * 14 + [_vp]),
     "ssm_frames_accumulate_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _vp]),
+    "ssm_frames_accumulate_light_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _vp, _vp, _c_int, _vp]),
     "ssm_luma_sad_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_int, _vp, _vp]),
 }
 
@@ -401,6 +403,28 @@ def frames_accumulate(src, acc, init, scale):
     N, C, H, W = src.shape
     assert acc.dim() == 4 and tuple(acc.shape) == (1, C, H, W), "frames %s and accumulator %s disagree" % (tuple(src.shape), tuple(acc.shape))
     check(load().ssm_frames_accumulate_fwd(view_of(src), view_of(acc), N, C, H, W, int(init), float(scale), stream_ptr()))
+    return acc
+
+
+def _floats(v, n, what):
+    """A ctypes array of n floats: `v` itself when it already is one (the streamed loop builds its own once), else a copy of the sequence."""
+    if isinstance(v, ctypes.Array) and v._type_ is ctypes.c_float and len(v) == n:
+        return v
+    vals = [float(x) for x in v]
+    assert len(vals) == n, "%s takes %d floats (got %d)" % (what, n, len(vals))
+    return (ctypes.c_float * n)(*vals)
+
+
+def frames_accumulate_light(src, acc, init, scale, mean, std, curve, encode):
+    """ssm_frames_accumulate_light_fwd: ssm_frames_accumulate_fwd on light.  Every value of src [N,3,H,W] is denormalised by (mean, std),
+    clamped to [0, 1] and decoded by `curve` (a row of ssm_amd.video.light_curve) before it is added into acc [1,3,H,W]; with encode = 1
+    the scaled sum is encoded and normalised again (include/ssm_hip.h; yardstick: ssm_amd.video.accumulate_light_host)."""
+    N, C, H, W = src.shape
+    assert C == 3 and acc.dim() == 4 and tuple(acc.shape) == (1, 3, H, W), \
+        "frames %s and accumulator %s must be [N,3,H,W] and [1,3,H,W]" % (tuple(src.shape), tuple(acc.shape))
+    check(load().ssm_frames_accumulate_light_fwd(view_of(src), view_of(acc), N, H, W, int(init), float(scale), _floats(mean, 3, "mean"),
+                                                 _floats(std, 3, "std"), _floats(curve, SSM_LIGHT_ROW, "a light curve's row"), int(encode),
+                                                 stream_ptr()))
     return acc
 
 

@@ -17,12 +17,15 @@
   accumulate_host /       the shutter: an output frame as the mean of `samples` sub-frames over the open part of its interval
   ShutterPlanner          (Timeline(step, shutter=, samples=)), summed on the GPU in time order by ssm_frames_accumulate_fwd, whose numpy
                           yardstick accumulate_host is; the bookkeeping of its passes - VideoInterpolator(shutter=, shutter_samples=)
+  light_curve /           the shutter in linear light: the sub-frames decoded to light by one of LIGHT_CURVES before they are summed, the
+  accumulate_light_host   mean encoded again (ssm_frames_accumulate_light_fwd, held to an error bound against this float64 yardstick) -
+                          VideoInterpolator(shutter_light=); "coded", the default, is the mean of the coded values
   luma_sad_host / luma_sad   scene cuts: per frame pair the exact sum of |difference| of the 8-bit Y planes, by numpy (the yardstick) and by
   / SceneCuts             ssm_luma_sad_fwd on the payloads as they stand on the device; the decision from those sums in Fractions, with no
                           GPU in it - VideoInterpolator(scene_cut=): at a cut the output repeats the nearer input frame instead of a morph
 
-Out of scope: codecs, audio, more than 8 bits per sample, the recurrent configuration (N_FRAMES > 2); shutter integration in linear
-light, shutter weights other than the box, a shutter centred on the frame's instant or open for longer than the frame interval,
+Out of scope: codecs, audio, more than 8 bits per sample, the recurrent configuration (N_FRAMES > 2); shutter weights other than
+the box, a light curve chosen from the clip's tags, HDR transfer curves (PQ, HLG), a shutter centred on the frame's instant or open for longer than the frame interval,
 variable-rate input, speeds that change within a clip; a default scene-cut threshold, fades and dissolves, cuts judged on chroma,
 skipping the GPU work of a cut pair, scene cuts together with a shutter.
 """
@@ -50,6 +53,36 @@ RANGES = {"limited": LIMITED, "full": FULL}
 # Y4M colour-space tags: accepted -> siting; refused ones are named in the error
 CHROMA_TAGS = {"420": CENTRED, "420jpeg": CENTRED, "420mpeg2": COSITED, "444": C444}
 _KRKB = {BT601: (0.299, 0.114), BT709: (0.2126, 0.0722)}
+
+
+# Light curves (include/ssm_hip.h): name -> (thr, slope, a, g) of  decode(c) = c <= thr ? c / slope : ((c + a) / (1 + a)) ^ g  and
+# encode(L) = L <= thr / slope ? L * slope : (1 + a) * L ^ (1 / g) - a.  bt709 is the inverse of the BT.709 camera curve V = 4.5 L below
+# beta, alpha L^0.45 - (alpha - 1) from there on.  The standard prints beta = 0.018 and alpha = 1.099; with those three digits the two
+# pieces miss each other at the join by 5.5e-5 of L (2.5e-4 of c).  alpha and beta below are the solution of the two conditions those
+# digits were rounded from - the pieces meet in value and in slope: 4.5 beta = alpha beta^0.45 - (alpha - 1), 4.5 = 0.45 alpha beta^-0.55
+# (BT.2020 prints the same numbers as 1.0993 and 0.0181) - so thr = 4.5 beta = 0.08124..., a = alpha - 1 = 0.09930....
+_BT709_ALPHA, _BT709_BETA = 1.09929682680944, 0.018053968510807
+LIGHT_CURVES = {"bt709": (4.5 * _BT709_BETA, 4.5, _BT709_ALPHA - 1.0, 1.0 / 0.45),
+                "srgb": (0.04045, 12.92, 0.055, 2.4),
+                "bt1886": (0.0, 1.0, 0.0, 2.4)}
+LIGHT_ROW = hb.SSM_LIGHT_ROW
+SHUTTER_LIGHTS = ("coded",) + tuple(LIGHT_CURVES)          # "coded": the mean of the coded values, no curve
+
+
+def light_curve(name):
+    """The row of LIGHT_ROW float32 constants of a light curve, every one evaluated in float64 and rounded once (layout: include/ssm_hip.h):
+    thr, 1/slope, a, 1/(1+a), g, thr/slope, slope, 1+a, 1/g.  What ssm_frames_accumulate_light_fwd and accumulate_light_host both read."""
+    if name not in LIGHT_CURVES:
+        raise ValueError("unknown light curve %r: the curves are %s" % (name, ", ".join(LIGHT_CURVES)))
+    thr, slope, a, g = LIGHT_CURVES[name]
+    return np.array([thr, 1.0 / slope, a, 1.0 / (1.0 + a), g, thr / slope, slope, 1.0 + a, 1.0 / g], dtype=np.float64).astype(np.float32)
+
+
+def parse_shutter_light(name):
+    """"coded" or the name of a light curve, as given; anything else is refused by name."""
+    if name not in SHUTTER_LIGHTS:
+        raise ValueError("unknown shutter_light %r: it is one of %s" % (name, ", ".join(SHUTTER_LIGHTS)))
+    return name
 
 
 def yuv_table():
@@ -203,6 +236,69 @@ def accumulate_host(frames, acc, init, scale):
     for n in range(1, frames.shape[0]):
         s = s + frames[n]
     dst[...] = s * _F(scale)
+    return acc
+
+
+def _light_constants(curve, dt):
+    """(thr, 1/slope, a, 1/(1+a), g, thr/slope, slope, 1+a, 1/g) in `dt`.  float32: the row as it is, what the kernel multiplies by.
+    float64: the row's thr, slope, a and g - fp32 values - with the other five taken from them in float64, so that encode inverts decode to
+    float64's own precision instead of the 1e-7 by which two rounded reciprocals miss each other; the kernel's distance from that is part
+    of its bound (tests/test_video_light_cpu.py)."""
+    row = np.asarray(curve, np.float32)
+    assert row.shape == (LIGHT_ROW,), "a light curve's row holds %d floats" % LIGHT_ROW
+    if dt is np.float32:
+        return tuple(row)
+    thr, a, g, slope = (np.float64(row[i]) for i in (0, 2, 4, 6))
+    return thr, 1.0 / slope, a, 1.0 / (1.0 + a), g, thr / slope, slope, 1.0 + a, 1.0 / g
+
+
+def light_decode_host(c, curve, dtype=np.float64):
+    """decode(c) of a light curve's row, element-wise in `dtype`: c <= thr ? c * (1/slope) : ((c + a) * (1/(1+a))) ^ g."""
+    dt = np.dtype(dtype).type
+    thr, islope, a, i1a, g = _light_constants(curve, dt)[:5]
+    c = np.asarray(c, dtype=dt)
+    return np.where(c <= thr, c * islope, np.power(np.maximum((c + a) * i1a, dt(0.0)), g))
+
+
+def light_encode_host(lum, curve, dtype=np.float64):
+    """encode(L) of a light curve's row, element-wise in `dtype`: L <= thr/slope ? L * slope : (1+a) * L ^ (1/g) - a."""
+    dt = np.dtype(dtype).type
+    k = _light_constants(curve, dt)
+    a, (lthr, slope, a1, ig) = k[2], k[5:9]
+    lum = np.asarray(lum, dtype=dt)
+    return np.where(lum <= lthr, lum * slope, a1 * np.power(np.maximum(lum, dt(0.0)), ig) - a)
+
+
+def accumulate_light_host(frames, acc, init, scale, mean, std, curve, encode, dtype=np.float64):
+    """Yardstick of ssm_frames_accumulate_light_fwd: frames [N,3,H,W] float32 (numpy, finite) summed as light into acc [1,3,H,W] or
+    [3,H,W] of `dtype`, in place, the kernel's operations in the kernel's order, every one in `dtype`:
+      dec(v) = 0 if v <= black[p] else decode(clip(v * std[p] + mean[p], 0, 1)), black = (0 / 255 - mean) / std in fp32 as the ingest has it;
+      s = dec(frames[0]) if init else acc + dec(frames[0]);  s = s + dec(frames[n]), n = 1 .. N-1;  r = s * scale;
+      acc = (encode(r) - mean[p]) / std[p] if encode else r.
+    mean and std enter as the fp32 values the kernel is given, the curve's row as _light_constants says; scale is taken as it is (the
+    kernel takes an fp32 one: give np.float32(1 / S) to compare).  dtype = float64: the fixed point the kernel is held to within the
+    bound of tests/test_video_light_cpu.py (x ^ e is numpy's power).  dtype = float32: what plain fp32 arithmetic gives; it is not the
+    kernel bit for bit, whose power is 2 ^ (e log2 x) by the hardware's instructions."""
+    dt = np.dtype(dtype).type
+    assert dt in (np.float32, np.float64), "dtype is numpy's float32 or float64"
+    frames = np.asarray(frames, dtype=_F)
+    assert acc.dtype == dt and frames.ndim == 4 and frames.shape[0] >= 1 and frames.shape[1] == 3 and init in (0, 1, False, True) and \
+        encode in (0, 1, False, True)
+    dst = acc[0] if acc.ndim == 4 else acc
+    assert dst.shape == frames.shape[1:] and (acc.ndim == 3 or acc.shape[0] == 1)
+    m32, s32 = np.asarray(mean, dtype=_F).reshape(3, 1, 1), np.asarray(std, dtype=_F).reshape(3, 1, 1)
+    black = (_F(0.0) / _F(255.0) - m32) / s32
+    m, sd = m32.astype(dt), s32.astype(dt)
+
+    def dec(v):
+        c = np.where(v <= black, dt(0.0), np.clip(v.astype(dt) * sd + m, dt(0.0), dt(1.0)))
+        return light_decode_host(c, curve, dt)
+
+    s = dec(frames[0]) if init else dst + dec(frames[0])
+    for n in range(1, frames.shape[0]):
+        s = s + dec(frames[n])
+    r = s * dt(scale)
+    dst[...] = (light_encode_host(r, curve, dt) - m) / sd if encode else r
     return acc
 
 
@@ -944,7 +1040,8 @@ class VideoInterpolator:
     rate rest on."""
 
     def __init__(self, model, cfg, upsample_rate=8, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
-                 tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8, scene_cut=None):
+                 tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8, scene_cut=None,
+                 shutter_light="coded"):
         """target_rate = (num, den) and / or speed (a Fraction, or what Fraction() takes; 1/4 is four times slower): the output follows
         Timeline(speed * input rate / target_rate) instead of the fixed grid of upsample_rate, which is then not used (see
         _run_timeline); with both None nothing changes.  flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
@@ -956,6 +1053,13 @@ class VideoInterpolator:
         (Timeline, _run_shutter).  Like the command line's --shutter it needs one of the two, since it averages over the interval of
         their timeline; speed=1 is the input's own rate with blur.  The 8 samples of the default are a convention, not backed by a
         measurement of quality.  shutter_samples = 1, or shutter None, is the loop without a shutter.
+        shutter_light ("coded", or the name of one of LIGHT_CURVES: "bt709", "srgb", "bt1886"), with a shutter: "coded" is the mean of
+        the gamma-coded R'G'B' values, launch for launch the loop as it was before the option.  A curve makes it the mean of light, what
+        a sensor integrates: every sub-frame is denormalised, clamped to [0, 1] - a synthesised value outside counts as 0 or 1, where the
+        coded mean lets it cancel - and decoded before it is added, and the mean is encoded again (ssm_frames_accumulate_light_fwd).
+        Which curve is right depends on how the clip was graded (bt709 for camera-referred material, srgb or bt1886 for material
+        mastered on a display), which no Y4M header says: so the choice is the user's and the default stays "coded".  It acts on
+        R'G'B' after the matrix and is independent of matrix and color_range.
         scene_cut (a Fraction in (0, 1], or what Fraction() takes; no default value): the threshold of SceneCuts.  Every pass then also
         sums the luma differences of its pairs on the GPU, and at a pair that SceneCuts calls a cut the writer puts out, instead of the
         synthesised frames, the left input frame's own bytes at t < 1/2 and the right one's from there on; `cuts` lists (i, score) of
@@ -986,6 +1090,10 @@ class VideoInterpolator:
         self.shutter, self.samples = (None, 1) if shutter is None else (shutter, shutter_samples)
         if shutter is not None:
             Timeline(1, shutter=shutter, samples=shutter_samples)          # refuses a bad value by name, here rather than at the first clip
+        self.shutter_light = parse_shutter_light(shutter_light)
+        if self.shutter_light != "coded" and shutter is None:
+            raise ValueError("shutter_light=%r is the light in which a shutter averages: give a shutter, or leave it at \"coded\""
+                             % (shutter_light,))
         self.timed = target_rate is not None or speed is not None
         self.scene_cut, self.cuts = None if scene_cut is None else parse_scene_cut(scene_cut), []
         if scene_cut is not None and shutter is not None:
@@ -1263,7 +1371,8 @@ class VideoInterpolator:
     def _run_shutter(self, clip, reader, writer):
         """run() with a shutter: output frame k is the mean of the S = shutter_samples sub-frames of Timeline(step, shutter=, samples=),
         summed in time order into an fp32 accumulator by ssm_frames_accumulate_fwd and egressed from it - every output, also one whose
-        samples are all input frames.
+        samples are all input frames.  With shutter_light a curve every one of those calls is ssm_frames_accumulate_light_fwd instead,
+        with encode = 1 on an output's last: the accumulator holds light in between and normalised coded planes for the egress.
 
         A pass (bookkeeping: ShutterPlanner) uploads and ingests, in one piece each, the frames it holds that a sample needs; copies the
         planes of up to pairs_per_batch pairs that get a sample side by side; runs them at their sample times padded to `slots`; and
@@ -1282,6 +1391,10 @@ class VideoInterpolator:
         depth, cap = n + 2, 2 * pb + 2
         plan = ShutterPlanner(tl, pb, cap)
         scale = np.float32(1.0 / tl.samples)
+        light = None
+        if self.shutter_light != "coded":
+            mean, std = cfg_mean_std(self.cfg)
+            light = (_f3(mean), _f3(std), (ctypes.c_float * LIGHT_ROW)(*[float(x) for x in light_curve(self.shutter_light)]))
         host_in = [torch.empty(cap, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
         host_out = [torch.empty(plan.max_done, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
         host_t = [torch.full((pb * max(slots, 1),), 0.5, dtype=torch.float32).pin_memory() for _ in range(depth)]
@@ -1319,8 +1432,11 @@ class VideoInterpolator:
                 o = 0
                 for src, first, count, ko, init, last in calls:
                     a = acc[ko % OPEN_OUTPUTS:ko % OPEN_OUTPUTS + 1]
-                    hb.frames_accumulate(planes[k][first:first + 1] if src == "frame" else frames[first:first + count], a, 1 if init else 0,
-                                      scale if last else 1.0)
+                    x = planes[k][first:first + 1] if src == "frame" else frames[first:first + count]
+                    if light is None:
+                        hb.frames_accumulate(x, a, 1 if init else 0, scale if last else 1.0)
+                    else:
+                        hb.frames_accumulate_light(x, a, 1 if init else 0, scale if last else 1.0, *light, 1 if last else 0)
                     if last:
                         frames_to_yuv(a, h, w, siting, matrix, crange, self.cfg, out=dev_out[k][o:o + 1])
                         host_out[r][o:o + 1].copy_(dev_out[k][o:o + 1], non_blocking=True)
