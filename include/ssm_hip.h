@@ -597,7 +597,7 @@ int ssm_frames_from_u8_fwd(const unsigned char *frames_hwc, ssm_view out, int N,
 int ssm_frames_to_u8_fwd(ssm_view in, unsigned char *frames_hwc, int N, int H, int W, int top, int left,
                          const float *mean3, const float *std3, int mode, void *stream);
 
-/* ---- video frame formats (csrc/ssm_video.hip; 8-bit planar Y'CbCr on the device) -----------------------
+/* ---- video frame formats (csrc/ssm_video.hip; planar Y'CbCr on the device, 8 to 16 bits per sample) ------
  * The streamed video loop (ssm_amd/video.py) serves the visualiser's convention, scripts/visualize_interpolation.py:
  * 61-88 (load_batch: frames padded to a multiple of 32, then normalised) and :223-268 (save_img_from_tensor,
  * normalize_tensor, denormalize), for frames that arrive as YUV4MPEG2 payloads instead of decoded RGB files.
@@ -628,7 +628,22 @@ int ssm_frames_to_u8_fwd(ssm_view in, unsigned char *frames_hwc, int N, int H, i
  *     code = min(max(rint(Yf iys + yoff), ylo), yhi),   min(max(rint(C ics + coff), clo), chi)   (round half to even)
  * SSM_E_ARG for null pointers, N < 1 or > 65535, H or W < 1, a negative offset, a canvas smaller than the image
  * plus its offset, a row stride shorter than the canvas (ingest) or than left + W (egress), or a matrix, range
- * or siting outside the values below. */
+ * or siting outside the values below; SSM_YUV_422 is refused by these two entry points.
+ *
+ * ssm_frames_from_yuvx_fwd / ssm_frames_to_yuvx_fwd: the same two conversions for every layout below and for samples of
+ * `sample_bytes` = 1 or 2.  A 2-byte sample is a 16-bit little-endian word with the value in its low bits (`bits` = 9 .. 16
+ * significant ones: 420p10, 422p10, 444p12, ...), read and written as it stands; the payload pointer is then 2-byte
+ * aligned (SSM_E_ARG otherwise; a frame has an even number of bytes, so every frame of a call is).  The kernels keep
+ * working in 0 .. 255 units: the bit depth lives in `table` alone, ssm_amd.video.yuv_table(bits), where with s = 2^(bits-8)
+ * and peak = 2^bits - 1
+ *   limited: ys, cs = 255/(219 s), 255/(224 s); iys, ics = 219 s/255, 224 s/255; yoff, coff = 16 s, 128 s; bounds 16 s, 235 s, 16 s, 240 s
+ *   full:    ys = cs = 255/peak; iys = ics = peak/255; yoff, coff = 0, 128 s; bounds 0, peak, 0, peak
+ * (bits = 8 is the table above, bit for bit).  A word above peak is not refused: the clamp to [0, 255] bounds what it does.
+ * SSM_YUV_422: chroma planes of H x ceil(W/2), co-sited with the even luma columns, no vertical step:
+ *   ingest  c = h(y, x) of SSM_YUV_420_COSITED, (a0 a1 b1 b2) = (0 1 .5 .5), taken on row y of the chroma plane itself
+ *   egress  C[y][cx] = ((C[y][2cx-1] + 2 C[y][2cx]) + C[y][2cx+1]) .25, columns clamped to the crop
+ * With sample_bytes = 1 and a layout of the 8-bit entry points the result is theirs, bit for bit (they are this code).
+ * SSM_E_ARG as above, and for a layout outside {0, 1, 2, 3}, sample_bytes outside {1, 2} or an odd address of 2-byte samples. */
 #define SSM_YUV_ROW 20
 #define SSM_YUV_BT601 0
 #define SSM_YUV_BT709 1
@@ -637,12 +652,19 @@ int ssm_frames_to_u8_fwd(ssm_view in, unsigned char *frames_hwc, int N, int H, i
 #define SSM_YUV_420_CENTRED 0
 #define SSM_YUV_420_COSITED 1
 #define SSM_YUV_444 2
+#define SSM_YUV_422 3
 int ssm_frames_from_yuv_fwd(const unsigned char *frames_yuv, ssm_view out, int N, int H, int W, int Hp, int Wp,
                             int top, int left, const float *mean3, const float *std3, int pad_before_norm,
                             const float *table, int matrix, int range, int siting, void *stream);
 int ssm_frames_to_yuv_fwd(ssm_view in, unsigned char *frames_yuv, int N, int H, int W, int top, int left,
                           const float *mean3, const float *std3, const float *table, int matrix, int range,
                           int siting, void *stream);
+int ssm_frames_from_yuvx_fwd(const void *frames_yuv, ssm_view out, int N, int H, int W, int Hp, int Wp, int top, int left,
+                             const float *mean3, const float *std3, int pad_before_norm, const float *table,
+                             int matrix, int range, int layout, int sample_bytes, void *stream);
+int ssm_frames_to_yuvx_fwd(ssm_view in, void *frames_yuv, int N, int H, int W, int top, int left, const float *mean3,
+                           const float *std3, const float *table, int matrix, int range, int layout, int sample_bytes,
+                           void *stream);
 
 /* ---- shutter of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) ----------------------------------
  * Definition (ssm_amd.video.Timeline(step, shutter=, samples=), everything in exact fractions).  `step` = input frames per output

@@ -1,14 +1,16 @@
-// 8-bit planar Y'CbCr video frames <-> the path's normalised, padded fp32 planes: the two conversions either side of the streamed
+// Planar Y'CbCr video frames <-> the path's normalised, padded fp32 planes: the two conversions either side of the streamed
 // video loop (ssm_amd/video.py), next to frames_from_u8_kernel / frames_to_u8_kernel of ssm_elem.hip, whose geometry (centred pad to
 // x32, pad_before_norm in both conventions: scripts/visualize_interpolation.py:61-88, scripts/utils/dataloaders/augmentations.py:
 // 141-200) and whose normalise / denormalise expressions they keep.  A frame is the payload of a YUV4MPEG2 FRAME record: the Y plane
-// H x W, then U, then V, each ceil(H/2) x ceil(W/2) (4:2:0) or H x W (4:4:4), no row padding; N frames are contiguous.
+// H x W, then U, then V, each ceil(H/2) x ceil(W/2) (4:2:0), H x ceil(W/2) (4:2:2) or H x W (4:4:4), no row padding; N frames are
+// contiguous.  A sample is one byte, or (9 to 16 significant bits) a 16-bit little-endian word with the value in its low bits: the
+// sample type and the layout are the kernels' template parameters, the bit depth lives in the constant table alone.
 //   frames_from_yuv_kernel   one thread per 2 x 2 luma block: 3 x 3 chroma samples per plane (clamped at the edges) give the block's
 //                            four bilinearly upsampled chroma values; range, matrix, clamp, normalise; two floats per row and plane
 //                            go out as one 8-byte store when the view allows it
 //   frames_to_yuv_kernel     one thread per 4 x 2 luma block = two chroma samples: denormalise, matrix, chroma filtered and subsampled
-//                            in float, range, round half to even, saturate; four Y codes of a row go out as one 32-bit store, the two
-//                            chroma codes of a plane as one 16-bit store, when the frame size allows it
+//                            in float, range, round half to even, saturate; four Y codes of a row go out as one store (4 or 8 bytes),
+//                            the two chroma codes of a plane and row as one store (2 or 4 bytes), when size and alignment allow it
 //   frames_accumulate_kernel the shutter of the streamed loop: N frames summed, in increasing n, into one fp32 accumulator
 //                            that is read at most once and written once per launch; one lane = 4 consecutive pixels of a row of one
 //                            channel (16-byte loads and stores), or one pixel when a view does not allow it
@@ -18,7 +20,7 @@
 //   luma_sad_kernel          scene cuts of the streamed loop: per frame pair the exact sum of |a - b| over the 8-bit Y planes;
 //                            one lane = 16 consecutive bytes of each plane (one 16-byte load per operand), or byte loads where a plane
 //                            does not start on a 16-byte boundary; v_sad_u8 into a 32-bit lane sum, shuffles, one 64-bit atomic per workgroup
-// Both conversions are HBM-bound (1.5 B in + 12 B out per pixel, and the reverse); so is the accumulation (4 (N + 1 + !init) B per
+// Both conversions are HBM-bound (1.5 to 6 B in + 12 B out per pixel, and the reverse); so is the accumulation (4 (N + 1 + !init) B per
 // element) and the luma difference (2 B per pixel).  The chroma siting enters as four horizontal weights (ingest) or one switch (egress); matrix and range enter as one row of
 // the constant table built by ssm_amd/video.py, which the host yardsticks read too.  Inputs of the egress kernel are finite.
 // NO CONTRACTION (as ssm_flow.hip): the numpy yardsticks round every operation, and so must the kernels.
@@ -60,22 +62,25 @@ __device__ __forceinline__ float clampf(float v, float lo, float hi) { return fm
 // (centred siting .25 .75 .75 .25; co-sited with the even columns 0 1 .5 .5).  Rows are centred in both sitings.
 // Thread (bx, by) owns the luma block at source (2 by - T2, 2 bx - L2), T2 / L2 = top / left rounded up to even, so that blocks are
 // aligned with the chroma grid wherever the image sits in the canvas; canvas pixels outside the image get the pad value.
-template <bool C444>
-__global__ __launch_bounds__(256) void frames_from_yuv_kernel(const unsigned char *__restrict__ in, ssm_view out, int H, int W, int Hp, int Wp,
-                                                              int top, int left, long long frame_bytes, YuvRow k, Norm3 nm, float a0,
+// 4:2:2 takes the horizontal step alone (wx that of the co-sited case), on the luma row's own chroma row.
+enum { LAY_420 = 0, LAY_422 = 1, LAY_444 = 2 };          // the plane layouts a kernel is instantiated for
+
+template <typename S, int L>          // S: the sample, unsigned char or unsigned short
+__global__ __launch_bounds__(256) void frames_from_yuv_kernel(const S *__restrict__ in, ssm_view out, int H, int W, int Hp, int Wp,
+                                                              int top, int left, long long frame_samples, YuvRow k, Norm3 nm, float a0,
                                                               float a1, float b1, float b2, int pad_before_norm, int vec2) {
     const int bx = blockIdx.x * 64 + threadIdx.x, by = blockIdx.y * 4 + threadIdx.y, b = blockIdx.z;
     const int sx0 = 2 * bx - ((left + 1) & ~1), sy0 = 2 * by - ((top + 1) & ~1);          // source position of the block
     const int ox0 = sx0 + left, oy0 = sy0 + top;                                         // canvas position (-1 possible)
     if (ox0 >= Wp || oy0 >= Hp) return;
-    const int cw = C444 ? W : (W + 1) >> 1, ch = C444 ? H : (H + 1) >> 1;
-    const unsigned char *yp = in + (long long)b * frame_bytes;
-    const unsigned char *up = yp + (long long)H * W, *vpl = up + (long long)ch * cw;
+    const int cw = L == LAY_444 ? W : (W + 1) >> 1, ch = L == LAY_420 ? (H + 1) >> 1 : H;
+    const S *yp = in + (long long)b * frame_samples;
+    const S *up = yp + (long long)H * W, *vpl = up + (long long)ch * cw;
     float o[3][2][2];          // [plane][row][col]
     const bool any = sx0 + 1 >= 0 && sx0 < W && sy0 + 1 >= 0 && sy0 < H;
     float cu[2][2], cv[2][2];  // upsampled chroma of the block
     if (any) {
-        if (C444) {
+        if (L == LAY_444) {
 #pragma unroll
             for (int r = 0; r < 2; ++r)
 #pragma unroll
@@ -84,6 +89,22 @@ __global__ __launch_bounds__(256) void frames_from_yuv_kernel(const unsigned cha
                     cu[r][c] = (float)up[(long long)y * W + x];
                     cv[r][c] = (float)vpl[(long long)y * W + x];
                 }
+        } else if (L == LAY_422) {
+            const int j = sx0 >> 1;          // sx0 even (arithmetic shift: -2 -> -1)
+            int xs[3];
+#pragma unroll
+            for (int t = 0; t < 3; ++t) xs[t] = min(max(j - 1 + t, 0), cw - 1);
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const int y = min(max(sy0 + r, 0), H - 1);
+                const S *ur = up + (long long)y * cw, *vr = vpl + (long long)y * cw;
+                const float u0 = (float)ur[xs[0]], u1 = (float)ur[xs[1]], u2 = (float)ur[xs[2]];
+                const float v0 = (float)vr[xs[0]], v1 = (float)vr[xs[1]], v2 = (float)vr[xs[2]];
+                cu[r][0] = a0 * u0 + a1 * u1;
+                cu[r][1] = b1 * u1 + b2 * u2;
+                cv[r][0] = a0 * v0 + a1 * v1;
+                cv[r][1] = b1 * v1 + b2 * v2;
+            }
         } else {
             const int j = sx0 >> 1, i = sy0 >> 1;          // sx0, sy0 even (arithmetic shift: -2 -> -1)
             int xs[3], ys[3];
@@ -95,7 +116,7 @@ __global__ __launch_bounds__(256) void frames_from_yuv_kernel(const unsigned cha
             float hu[3][2], hv[3][2];          // horizontally interpolated: [chroma row][even | odd luma column]
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
-                const unsigned char *ur = up + (long long)ys[r] * cw, *vr = vpl + (long long)ys[r] * cw;
+                const S *ur = up + (long long)ys[r] * cw, *vr = vpl + (long long)ys[r] * cw;
                 const float u0 = (float)ur[xs[0]], u1 = (float)ur[xs[1]], u2 = (float)ur[xs[2]];
                 const float v0 = (float)vr[xs[0]], v1 = (float)vr[xs[1]], v2 = (float)vr[xs[2]];
                 hu[r][0] = a0 * u0 + a1 * u1;
@@ -172,15 +193,31 @@ __device__ __forceinline__ unsigned code_of(float v, float scale, float off, flo
     return (unsigned)(int)clampf(rintf(v * scale + off), lo, hi);
 }
 
-template <bool C444>
-__global__ __launch_bounds__(256) void frames_to_yuv_kernel(ssm_view in, unsigned char *__restrict__ out, int H, int W, int top, int left,
-                                                            long long frame_bytes, YuvRow k, Norm3 nm, int cosited, int vec_in, int vec_out) {
+// four codes of a row / two chroma codes of a plane as one store: 4 and 2 bytes of 8-bit samples, 8 and 4 bytes of 16-bit ones
+__device__ __forceinline__ void store4(unsigned char *dst, const unsigned (&q)[4]) {
+    *reinterpret_cast<unsigned *>(dst) = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+}
+__device__ __forceinline__ void store4(unsigned short *dst, const unsigned (&q)[4]) {
+    i32x2 v;
+    v.x = (int)(q[0] | (q[1] << 16));
+    v.y = (int)(q[2] | (q[3] << 16));
+    *reinterpret_cast<i32x2 *>(dst) = v;
+}
+__device__ __forceinline__ void store2(unsigned char *dst, unsigned q0, unsigned q1) {
+    *reinterpret_cast<unsigned short *>(dst) = (unsigned short)(q0 | (q1 << 8));
+}
+__device__ __forceinline__ void store2(unsigned short *dst, unsigned q0, unsigned q1) { *reinterpret_cast<unsigned *>(dst) = q0 | (q1 << 16); }
+
+template <typename S, int L>
+__global__ __launch_bounds__(256) void frames_to_yuv_kernel(ssm_view in, S *__restrict__ out, int H, int W, int top, int left,
+                                                            long long frame_samples, YuvRow k, Norm3 nm, int cosited, int vec_in, int vec_out) {
     const int bx = blockIdx.x * 64 + threadIdx.x, by = blockIdx.y * 4 + threadIdx.y, b = blockIdx.z;
     const int x0 = 4 * bx, y0 = 2 * by;
     if (x0 >= W || y0 >= H) return;
-    const int cw = C444 ? W : (W + 1) >> 1, ch = C444 ? H : (H + 1) >> 1;
-    unsigned char *yp = out + (long long)b * frame_bytes;
-    unsigned char *up = yp + (long long)H * W, *vpl = up + (long long)ch * cw;
+    const int cw = L == LAY_444 ? W : (W + 1) >> 1, ch = L == LAY_420 ? (H + 1) >> 1 : H;
+    const bool cos = L == LAY_422 || (L == LAY_420 && cosited);          // 4:2:2 is co-sited with the even luma columns
+    S *yp = out + (long long)b * frame_samples;
+    S *up = yp + (long long)H * W, *vpl = up + (long long)ch * cw;
     const bool whole = x0 + 3 < W;
     Ycc px[2][5];          // [row][column x0-1 (co-sited only), x0 .. x0+3]
 #pragma unroll
@@ -197,7 +234,7 @@ __global__ __launch_bounds__(256) void frames_to_yuv_kernel(ssm_view in, unsigne
 #pragma unroll
                 for (int c = 0; c < 4; ++c) v[p][1 + c] = row[min(x0 + c, W - 1)];
             }
-            v[p][0] = (cosited && !C444) ? row[max(x0 - 1, 0)] : 0.0f;
+            v[p][0] = cos ? row[max(x0 - 1, 0)] : 0.0f;
         }
 #pragma unroll
         for (int c = 0; c < 5; ++c)
@@ -209,57 +246,64 @@ __global__ __launch_bounds__(256) void frames_to_yuv_kernel(ssm_view in, unsigne
         const int y = y0 + r;
         if (y >= H) continue;
 #pragma unroll
-        for (int p = 0; p < (C444 ? 3 : 1); ++p) {
+        for (int p = 0; p < (L == LAY_444 ? 3 : 1); ++p) {
             unsigned q[4];
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const Ycc &s = px[r][1 + c];
                 q[c] = p == 0 ? code_of(s.y, k.iys, k.yoff, k.ylo, k.yhi) : code_of(p == 1 ? s.cb : s.cr, k.ics, k.coff, k.clo, k.chi);
             }
-            unsigned char *dst = (p == 0 ? yp : (p == 1 ? up : vpl)) + (long long)y * W + x0;
-            if (vec_out && whole) {          // vec_out: W % 4 == 0 and 4-byte aligned planes
-                *reinterpret_cast<unsigned *>(dst) = q[0] | (q[1] << 8) | (q[2] << 16) | (q[3] << 24);
+            S *dst = (p == 0 ? yp : (p == 1 ? up : vpl)) + (long long)y * W + x0;
+            if (vec_out && whole) {          // vec_out: W % 4 == 0 and planes aligned to four samples
+                store4(dst, q);
             } else {
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
-                    if (x0 + c < W) dst[c] = (unsigned char)q[c];
+                    if (x0 + c < W) dst[c] = (S)q[c];
             }
         }
     }
-    if (C444) return;
-    // the block's two chroma samples: filter in float, then range, rounding, saturation
-    unsigned qu[2], qv[2];
+    if (L == LAY_444) return;
+    // the block's two chroma samples - per row in 4:2:2: filter in float, then range, rounding, saturation
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int c = 1 + 2 * j;          // px column of luma column 2 (cx) = x0 + 2 j
-        float cb, cr;
-        if (cosited) {                    // [1 2 1] / 4 over columns 2 cx - 1 .. 2 cx + 1, then the mean of the two rows
-            float hb[2], hr[2];
+    for (int cr_ = 0; cr_ < (L == LAY_422 ? 2 : 1); ++cr_) {
+        if (L == LAY_422 && y0 + cr_ >= H) continue;
+        unsigned qu[2], qv[2];
 #pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                hb[r] = ((px[r][c - 1].cb + 2.0f * px[r][c].cb) + px[r][c + 1].cb) * 0.25f;
-                hr[r] = ((px[r][c - 1].cr + 2.0f * px[r][c].cr) + px[r][c + 1].cr) * 0.25f;
+        for (int j = 0; j < 2; ++j) {
+            const int c = 1 + 2 * j;          // px column of luma column 2 (cx) = x0 + 2 j
+            float cb, cr;
+            if (L == LAY_422) {               // [1 2 1] / 4 over columns 2 cx - 1 .. 2 cx + 1 of the row itself
+                cb = ((px[cr_][c - 1].cb + 2.0f * px[cr_][c].cb) + px[cr_][c + 1].cb) * 0.25f;
+                cr = ((px[cr_][c - 1].cr + 2.0f * px[cr_][c].cr) + px[cr_][c + 1].cr) * 0.25f;
+            } else if (cosited) {             // the same, then the mean of the two rows
+                float hb[2], hr[2];
+#pragma unroll
+                for (int r = 0; r < 2; ++r) {
+                    hb[r] = ((px[r][c - 1].cb + 2.0f * px[r][c].cb) + px[r][c + 1].cb) * 0.25f;
+                    hr[r] = ((px[r][c - 1].cr + 2.0f * px[r][c].cr) + px[r][c + 1].cr) * 0.25f;
+                }
+                cb = (hb[0] + hb[1]) * 0.5f;
+                cr = (hr[0] + hr[1]) * 0.5f;
+            } else {                          // 2 x 2 mean
+                cb = ((px[0][c].cb + px[0][c + 1].cb) + (px[1][c].cb + px[1][c + 1].cb)) * 0.25f;
+                cr = ((px[0][c].cr + px[0][c + 1].cr) + (px[1][c].cr + px[1][c + 1].cr)) * 0.25f;
             }
-            cb = (hb[0] + hb[1]) * 0.5f;
-            cr = (hr[0] + hr[1]) * 0.5f;
-        } else {                          // 2 x 2 mean
-            cb = ((px[0][c].cb + px[0][c + 1].cb) + (px[1][c].cb + px[1][c + 1].cb)) * 0.25f;
-            cr = ((px[0][c].cr + px[0][c + 1].cr) + (px[1][c].cr + px[1][c + 1].cr)) * 0.25f;
+            qu[j] = code_of(cb, k.ics, k.coff, k.clo, k.chi);
+            qv[j] = code_of(cr, k.ics, k.coff, k.clo, k.chi);
         }
-        qu[j] = code_of(cb, k.ics, k.coff, k.clo, k.chi);
-        qv[j] = code_of(cr, k.ics, k.coff, k.clo, k.chi);
-    }
-    const int cx = x0 >> 1, cy = y0 >> 1;
-    unsigned char *du = up + (long long)cy * cw + cx, *dv = vpl + (long long)cy * cw + cx;
-    if (vec_out && cx + 1 < cw) {          // W % 4 == 0: cw even, cx even
-        *reinterpret_cast<unsigned short *>(du) = (unsigned short)(qu[0] | (qu[1] << 8));
-        *reinterpret_cast<unsigned short *>(dv) = (unsigned short)(qv[0] | (qv[1] << 8));
-    } else {
-        du[0] = (unsigned char)qu[0];
-        dv[0] = (unsigned char)qv[0];
-        if (cx + 1 < cw) {
-            du[1] = (unsigned char)qu[1];
-            dv[1] = (unsigned char)qv[1];
+        const int cx = x0 >> 1, cy = L == LAY_422 ? y0 + cr_ : y0 >> 1;
+        S *du = up + (long long)cy * cw + cx, *dv = vpl + (long long)cy * cw + cx;
+        if (vec_out && cx + 1 < cw) {          // W % 4 == 0: cw even, cx even
+            store2(du, qu[0], qu[1]);
+            store2(dv, qv[0], qv[1]);
+        } else {
+            du[0] = (S)qu[0];
+            dv[0] = (S)qv[0];
+            if (cx + 1 < cw) {
+                du[1] = (S)qu[1];
+                dv[1] = (S)qv[1];
+            }
         }
     }
 }
@@ -462,63 +506,126 @@ inline YuvRow row_of(const float *table, int matrix, int range) {
 
 }  // namespace
 
-#define SSM_CHECK_YUV(name)                                                                                                       \
-    SSM_REQUIRE((matrix == SSM_YUV_BT601 || matrix == SSM_YUV_BT709) && (range == SSM_YUV_LIMITED || range == SSM_YUV_FULL),      \
-                name ": matrix %d / range %d not in {0, 1}", matrix, range);                                                      \
-    SSM_REQUIRE(siting == SSM_YUV_420_CENTRED || siting == SSM_YUV_420_COSITED || siting == SSM_YUV_444,                          \
-                name ": chroma siting %d not in {0, 1, 2}", siting)
-
-// bytes of one frame's payload
-static long long yuv_frame_bytes(int H, int W, int siting) {
-    const long long c = siting == SSM_YUV_444 ? (long long)H * W : (long long)((H + 1) / 2) * ((W + 1) / 2);
-    return (long long)H * W + 2 * c;
+// samples of one frame's payload
+static long long yuv_frame_samples(int H, int W, int layout) {
+    const long long cw = layout == SSM_YUV_444 ? W : (W + 1) / 2, ch = layout == SSM_YUV_420_CENTRED || layout == SSM_YUV_420_COSITED ? (H + 1) / 2 : H;
+    return (long long)H * W + 2 * ch * cw;
 }
 
-extern "C" int ssm_frames_from_yuv_fwd(const unsigned char *frames_yuv, ssm_view out, int N, int H, int W, int Hp, int Wp, int top, int left,
-                                       const float *mean3, const float *std3, int pad_before_norm, const float *table, int matrix,
-                                       int range, int siting, void *stream) {
-    SSM_REQUIRE(frames_yuv && out.ptr && mean3 && std3 && table, "frames_from_yuv: null pointer");
-    SSM_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && top >= 0 && left >= 0 && Hp >= H + top && Wp >= W + left && out.sh >= Wp &&
-                    (Hp + 9) / 8 <= 65535,
-                "frames_from_yuv: bad geometry %dx%d -> %dx%d at (%d,%d), row stride %d", H, W, Hp, Wp, top, left, out.sh);
-    SSM_CHECK_YUV("frames_from_yuv");
-    const bool cos = siting == SSM_YUV_420_COSITED;
+// The checks both pairs of entry points share; `name` is the entry point's, `what` says "chroma siting" (the 8-bit entry points, which
+// take SSM_YUV_420_* and SSM_YUV_444) or "layout" (the extended ones, which take SSM_YUV_422 and the sample width as well).
+static int check_yuv(const char *name, int matrix, int range, int layout, bool extended, int sample_bytes, const void *payload) {
+    SSM_REQUIRE((matrix == SSM_YUV_BT601 || matrix == SSM_YUV_BT709) && (range == SSM_YUV_LIMITED || range == SSM_YUV_FULL),
+                "%s: matrix %d / range %d not in {0, 1}", name, matrix, range);
+    if (!extended) {
+        SSM_REQUIRE(layout == SSM_YUV_420_CENTRED || layout == SSM_YUV_420_COSITED || layout == SSM_YUV_444,
+                    "%s: chroma siting %d not in {0, 1, 2}", name, layout);
+        return SSM_OK;
+    }
+    SSM_REQUIRE(layout >= SSM_YUV_420_CENTRED && layout <= SSM_YUV_422, "%s: layout %d not in {0, 1, 2, 3}", name, layout);
+    SSM_REQUIRE(sample_bytes == 1 || sample_bytes == 2, "%s: sample_bytes %d not in {1, 2}", name, sample_bytes);
+    SSM_REQUIRE(sample_bytes == 1 || reinterpret_cast<size_t>(payload) % 2 == 0, "%s: a payload of 2-byte samples is not 2-byte aligned", name);
+    return SSM_OK;
+}
+
+template <typename S>
+static void launch_from_yuv(const void *frames_yuv, ssm_view out, int N, int H, int W, int Hp, int Wp, int top, int left, const float *mean3,
+                            const float *std3, int pad_before_norm, const float *table, int matrix, int range, int layout, void *stream) {
+    const bool cos = layout != SSM_YUV_420_CENTRED;          // 4:2:2 has the co-sited case's horizontal weights (4:4:4 reads none)
     const float a0 = cos ? 0.0f : 0.25f, a1 = cos ? 1.0f : 0.75f, b1 = cos ? 0.5f : 0.75f, b2 = cos ? 0.5f : 0.25f;
     const int vec2 = (left % 2 == 0 && view_aligned(out, 2)) ? 1 : 0;
     // blocks per axis: the canvas plus the one-pixel shift of an odd offset
     const int nbx = (Wp + (left & 1) + 1) / 2, nby = (Hp + (top & 1) + 1) / 2;
     const dim3 grid((nbx + 63) / 64, (nby + 3) / 4, N);
-    const long long fb = yuv_frame_bytes(H, W, siting);
-    if (siting == SSM_YUV_444)
-        SSM_LAUNCH(frames_from_yuv_kernel<true>, grid, dim3(64, 4), 0, (hipStream_t)stream, frames_yuv, out, H, W, Hp, Wp, top, left, fb,
+    const long long fs = yuv_frame_samples(H, W, layout);
+    const S *in = static_cast<const S *>(frames_yuv);
+    if (layout == SSM_YUV_444)
+        SSM_LAUNCH(frames_from_yuv_kernel<S, LAY_444>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, out, H, W, Hp, Wp, top, left, fs,
+                   row_of(table, matrix, range), norm_of(mean3, std3), a0, a1, b1, b2, pad_before_norm ? 1 : 0, vec2);
+    else if (layout == SSM_YUV_422)
+        SSM_LAUNCH(frames_from_yuv_kernel<S, LAY_422>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, out, H, W, Hp, Wp, top, left, fs,
                    row_of(table, matrix, range), norm_of(mean3, std3), a0, a1, b1, b2, pad_before_norm ? 1 : 0, vec2);
     else
-        SSM_LAUNCH(frames_from_yuv_kernel<false>, grid, dim3(64, 4), 0, (hipStream_t)stream, frames_yuv, out, H, W, Hp, Wp, top, left, fb,
+        SSM_LAUNCH(frames_from_yuv_kernel<S, LAY_420>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, out, H, W, Hp, Wp, top, left, fs,
                    row_of(table, matrix, range), norm_of(mean3, std3), a0, a1, b1, b2, pad_before_norm ? 1 : 0, vec2);
-    return ssm::check_launch("ssm_frames_from_yuv_fwd");
+}
+
+static int frames_from_yuv(const char *name, const char *entry, bool extended, const void *frames_yuv, ssm_view out, int N, int H, int W, int Hp,
+                           int Wp, int top, int left, const float *mean3, const float *std3, int pad_before_norm, const float *table,
+                           int matrix, int range, int layout, int sample_bytes, void *stream) {
+    SSM_REQUIRE(frames_yuv && out.ptr && mean3 && std3 && table, "%s: null pointer", name);
+    SSM_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && top >= 0 && left >= 0 && Hp >= H + top && Wp >= W + left && out.sh >= Wp &&
+                    (Hp + 9) / 8 <= 65535,
+                "%s: bad geometry %dx%d -> %dx%d at (%d,%d), row stride %d", name, H, W, Hp, Wp, top, left, out.sh);
+    if (const int e = check_yuv(name, matrix, range, layout, extended, sample_bytes, frames_yuv)) return e;
+    if (sample_bytes == 1)
+        launch_from_yuv<unsigned char>(frames_yuv, out, N, H, W, Hp, Wp, top, left, mean3, std3, pad_before_norm, table, matrix, range, layout, stream);
+    else
+        launch_from_yuv<unsigned short>(frames_yuv, out, N, H, W, Hp, Wp, top, left, mean3, std3, pad_before_norm, table, matrix, range, layout, stream);
+    return ssm::check_launch(entry);
+}
+
+template <typename S>
+static void launch_to_yuv(ssm_view in, void *frames_yuv, int N, int H, int W, int top, int left, const float *mean3, const float *std3,
+                          const float *table, int matrix, int range, int layout, void *stream) {
+    const long long fs = yuv_frame_samples(H, W, layout);
+    const int vec_in = (left % 4 == 0 && view_aligned(in, 4)) ? 1 : 0;
+    // W % 4 == 0 and a base aligned to four samples keep every store aligned: a Y row starts at a multiple of 4 samples; the chroma rows are
+    // W / 2 (even) samples and a thread's pair starts at an even one; the Y plane is H W samples (a multiple of 4), a chroma plane
+    // ceil(H/2) W/2 or H W/2 (even), a frame H W + 2 chroma planes (a multiple of 4) - so every plane of every frame starts aligned too
+    const int vec_out = (W % 4 == 0 && reinterpret_cast<size_t>(frames_yuv) % (4 * sizeof(S)) == 0) ? 1 : 0;
+    const dim3 grid(((W + 3) / 4 + 63) / 64, ((H + 1) / 2 + 3) / 4, N);
+    S *dst = static_cast<S *>(frames_yuv);
+    if (layout == SSM_YUV_444)
+        SSM_LAUNCH(frames_to_yuv_kernel<S, LAY_444>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, dst, H, W, top, left, fs,
+                   row_of(table, matrix, range), norm_of(mean3, std3), 0, vec_in, vec_out);
+    else if (layout == SSM_YUV_422)
+        SSM_LAUNCH(frames_to_yuv_kernel<S, LAY_422>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, dst, H, W, top, left, fs,
+                   row_of(table, matrix, range), norm_of(mean3, std3), 1, vec_in, vec_out);
+    else
+        SSM_LAUNCH(frames_to_yuv_kernel<S, LAY_420>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, dst, H, W, top, left, fs,
+                   row_of(table, matrix, range), norm_of(mean3, std3), layout == SSM_YUV_420_COSITED ? 1 : 0, vec_in, vec_out);
+}
+
+static int frames_to_yuv(const char *name, const char *entry, bool extended, ssm_view in, void *frames_yuv, int N, int H, int W, int top, int left,
+                         const float *mean3, const float *std3, const float *table, int matrix, int range, int layout, int sample_bytes,
+                         void *stream) {
+    SSM_REQUIRE(frames_yuv && in.ptr && mean3 && std3 && table, "%s: null pointer", name);
+    SSM_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && top >= 0 && left >= 0 && in.sh >= W + left && (H + 7) / 8 <= 65535,
+                "%s: bad geometry %dx%d at (%d,%d), row stride %d", name, H, W, top, left, in.sh);
+    if (const int e = check_yuv(name, matrix, range, layout, extended, sample_bytes, frames_yuv)) return e;
+    if (sample_bytes == 1)
+        launch_to_yuv<unsigned char>(in, frames_yuv, N, H, W, top, left, mean3, std3, table, matrix, range, layout, stream);
+    else
+        launch_to_yuv<unsigned short>(in, frames_yuv, N, H, W, top, left, mean3, std3, table, matrix, range, layout, stream);
+    return ssm::check_launch(entry);
+}
+
+// The 8-bit entry points are the extended ones at sample_bytes = 1, with SSM_YUV_422 refused as it always was.
+extern "C" int ssm_frames_from_yuv_fwd(const unsigned char *frames_yuv, ssm_view out, int N, int H, int W, int Hp, int Wp, int top, int left,
+                                       const float *mean3, const float *std3, int pad_before_norm, const float *table, int matrix,
+                                       int range, int siting, void *stream) {
+    return frames_from_yuv("frames_from_yuv", "ssm_frames_from_yuv_fwd", false, frames_yuv, out, N, H, W, Hp, Wp, top, left, mean3, std3,
+                           pad_before_norm, table, matrix, range, siting, 1, stream);
+}
+
+extern "C" int ssm_frames_from_yuvx_fwd(const void *frames_yuv, ssm_view out, int N, int H, int W, int Hp, int Wp, int top, int left,
+                                        const float *mean3, const float *std3, int pad_before_norm, const float *table, int matrix,
+                                        int range, int layout, int sample_bytes, void *stream) {
+    return frames_from_yuv("frames_from_yuvx", "ssm_frames_from_yuvx_fwd", true, frames_yuv, out, N, H, W, Hp, Wp, top, left, mean3, std3,
+                           pad_before_norm, table, matrix, range, layout, sample_bytes, stream);
 }
 
 extern "C" int ssm_frames_to_yuv_fwd(ssm_view in, unsigned char *frames_yuv, int N, int H, int W, int top, int left, const float *mean3,
                                      const float *std3, const float *table, int matrix, int range, int siting, void *stream) {
-    SSM_REQUIRE(frames_yuv && in.ptr && mean3 && std3 && table, "frames_to_yuv: null pointer");
-    SSM_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && top >= 0 && left >= 0 && in.sh >= W + left && (H + 7) / 8 <= 65535,
-                "frames_to_yuv: bad geometry %dx%d at (%d,%d), row stride %d", H, W, top, left, in.sh);
-    SSM_CHECK_YUV("frames_to_yuv");
-    const long long fb = yuv_frame_bytes(H, W, siting);
-    const int vec_in = (left % 4 == 0 && view_aligned(in, 4)) ? 1 : 0;
-    // W % 4 == 0 keeps every row of every plane (chroma rows are W / 2 bytes, and 16-bit stores need only W / 2 even) and every frame aligned
-    const int vec_out = (W % 4 == 0 && reinterpret_cast<size_t>(frames_yuv) % 4 == 0 && ((long long)H * W) % 4 == 0 && fb % 4 == 0 &&
-                         (((long long)((H + 1) / 2) * (W / 2)) % 2 == 0 || siting == SSM_YUV_444))
-                            ? 1
-                            : 0;
-    const dim3 grid(((W + 3) / 4 + 63) / 64, ((H + 1) / 2 + 3) / 4, N);
-    if (siting == SSM_YUV_444)
-        SSM_LAUNCH(frames_to_yuv_kernel<true>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, frames_yuv, H, W, top, left, fb,
-                   row_of(table, matrix, range), norm_of(mean3, std3), 0, vec_in, vec_out);
-    else
-        SSM_LAUNCH(frames_to_yuv_kernel<false>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, frames_yuv, H, W, top, left, fb,
-                   row_of(table, matrix, range), norm_of(mean3, std3), siting == SSM_YUV_420_COSITED ? 1 : 0, vec_in, vec_out);
-    return ssm::check_launch("ssm_frames_to_yuv_fwd");
+    return frames_to_yuv("frames_to_yuv", "ssm_frames_to_yuv_fwd", false, in, frames_yuv, N, H, W, top, left, mean3, std3, table, matrix, range,
+                         siting, 1, stream);
+}
+
+extern "C" int ssm_frames_to_yuvx_fwd(ssm_view in, void *frames_yuv, int N, int H, int W, int top, int left, const float *mean3,
+                                      const float *std3, const float *table, int matrix, int range, int layout, int sample_bytes, void *stream) {
+    return frames_to_yuv("frames_to_yuvx", "ssm_frames_to_yuvx_fwd", true, in, frames_yuv, N, H, W, top, left, mean3, std3, table, matrix, range,
+                         layout, sample_bytes, stream);
 }
 
 extern "C" int ssm_frames_accumulate_fwd(ssm_view src, ssm_view acc, int N, int C, int H, int W, int init, float scale, void *stream) {

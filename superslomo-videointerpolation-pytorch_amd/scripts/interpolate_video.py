@@ -10,8 +10,9 @@ input frames.  Y4M is the container every player and ffmpeg read and write witho
 
 Memory does not grow with the clip (scripts/visualize_interpolation.py, the PNG tool, holds the whole clip on the GPU).  Input frames
 pass to the output as their own bytes.  The output's frame rate is the input's times upsample_rate - the same duration, smoother - or,
-with --slowmo, the input's: the same frames played upsample_rate times slower.  8-bit 4:2:0 (both sitings) and 4:4:4 only; N_FRAMES must
-be 2, as for the PNG tool.  --flow_scale 2|4 runs the two U-Nets at 1/2 or 1/4 of the frame size and synthesises at full size (the frame is
+with --slowmo, the input's: the same frames played upsample_rate times slower.  4:2:0 (both sitings), 4:2:2 and 4:4:4 at 8 bits per sample,
+and C420pB, C422pB, C444pB at B = 9, 10, 12, 14 or 16 (what `ffmpeg -f yuv4mpegpipe` hands over as C422p10, C420p10, ...); the output has
+the input's format.  N_FRAMES must be 2, as for the PNG tool.  --flow_scale 2|4 runs the two U-Nets at 1/2 or 1/4 of the frame size and synthesises at full size (the frame is
 then padded to x64 / x128): several times faster on UHD material, an approximation of the default output, not parity with the reference.
 --tile HxW runs the frame in overlapping windows of tile + halo and stitches them with a cross-fade (--halo, --blend): the activations
 are those of a window instead of the frame, which is what lets 8K material, or 4K on a card shared with other work, run at all; likewise
@@ -38,7 +39,7 @@ scored by ssm_amd.video.SceneCuts from the sum of its absolute luma differences 
 that scores T or more is a scene cut: instead of frames that morph one scene into the other, the output repeats the left input frame up
 to the middle of the interval and the right one from there on.  The score - the mean absolute luma difference, damped by its own change
 from the pair before, over 255 - is a convention, not backed by a measurement here; every cut is written to --log with its score, which
-is what to choose T from.  Fades and dissolves are not looked for.  Not together with --shutter.
+is what to choose T from.  Fades and dissolves are not looked for.  Not together with --shutter, and for 8-bit input only.
 """
 import argparse
 import configparser
@@ -140,7 +141,7 @@ def main(argv=None, model=None):
                              flow_scale=args.flow_scale, tile=args.tile, halo=args.halo, blend=args.blend, target_rate=args.fps, speed=args.speed,
                              shutter=args.shutter, shutter_samples=args.shutter_samples, scene_cut=args.scene_cut,
                              shutter_light=args.shutter_light)
-    with V.Y4MReader(args.input) as reader:
+    with V.Y4MReader(args.input, extended=True) as reader:
         if timed:
             rate = args.fps or reader.rate
             tl = vi.timeline(reader.rate)

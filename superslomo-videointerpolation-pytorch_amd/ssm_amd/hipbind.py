@@ -144,6 +144,11 @@ SIGNATURES = {
                                          _c_int, _c_int, _vp]),
     "ssm_frames_to_yuv_fwd": (_c_int, [SsmView, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_float),
                                        ctypes.POINTER(_c_float), ctypes.POINTER(_c_float), _c_int, _c_int, _c_int, _vp]),
+    "ssm_frames_from_yuvx_fwd": (_c_int, [_vp, SsmView, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                          ctypes.POINTER(_c_float), ctypes.POINTER(_c_float), _c_int, ctypes.POINTER(_c_float), _c_int,
+                                          _c_int, _c_int, _c_int, _vp]),
+    "ssm_frames_to_yuvx_fwd": (_c_int, [SsmView, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.POINTER(_c_float),
+                                        ctypes.POINTER(_c_float), ctypes.POINTER(_c_float), _c_int, _c_int, _c_int, _c_int, _vp]),
     "ssm_clip_batch_from_u8_fwd": (_c_int, [_vp, ctypes.c_longlong, _vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int,
                                             ctypes.POINTER(_c_float), ctypes.POINTER(_c_float), _vp]),
     "ssm_frame_metrics_workspace_bytes": (_sz, [_c_int, _c_int, _c_int]),

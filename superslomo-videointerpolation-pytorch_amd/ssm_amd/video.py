@@ -1,8 +1,10 @@
 """Streamed slow-motion video: YUV4MPEG2 in, YUV4MPEG2 out, colour conversion on the GPU.
 
   Y4MReader / Y4MWriter   the one video container that needs no codec (every player and ffmpeg read and write it, pipes included):
-                          a text header `YUV4MPEG2 W H F I A C X...`, then `FRAME` records of 8-bit planar Y, U, V
-  yuv_table               the conversion constants, float64 rounded once to fp32: what csrc/ssm_video.hip and the yardsticks both read
+                          a text header `YUV4MPEG2 W H F I A C X...`, then `FRAME` records of planar Y, U, V: 8-bit 4:2:0 and 4:4:4, and
+                          with extended=True also 4:2:2 and 9 to 16 bits per sample (C422, C420p10, C422p10, C444p12, ...: EXTENDED_TAGS)
+  yuv_table               the conversion constants of a bit depth, float64 rounded once to fp32: what csrc/ssm_video.hip and the
+                          yardsticks both read; `bits` (the significant bits of a sample, 8 to 16) lives in this table alone
   yuv_to_frames_host /    numpy float32 yardsticks that spell the two kernels' operations in the kernels' order: the fixed points the
   frames_to_yuv_host      kernels are held to bit for bit (as scripts/utils/flo_utils.py is for csrc/ssm_flow.hip)
   frames_from_yuv /       the kernels: payloads on the device <-> the path's normalised, padded fp32 planes, in the visualiser's
@@ -24,7 +26,14 @@
   / SceneCuts             ssm_luma_sad_fwd on the payloads as they stand on the device; the decision from those sums in Fractions, with no
                           GPU in it - VideoInterpolator(scene_cut=): at a cut the output repeats the nearer input frame instead of a morph
 
-Out of scope: codecs, audio, more than 8 bits per sample, the recurrent configuration (N_FRAMES > 2); shutter weights other than
+Formats.  A sample of more than 8 bits is a 16-bit little-endian word with the value in its low bits (ffmpeg's convention); payloads stay
+[N, frame_bytes] uint8 whatever the depth, so the ring, the pinned slots and "input frames reach the output as their own bytes" do not
+depend on it.  4:2:2 chroma is co-sited with the even luma columns, as the Y4M specification states; C420pB carries no siting and is
+read as C420 is, centred.  The fp32 pipeline between ingest and egress is the same for every format: the output has the input's format.
+
+Out of scope: codecs, audio, output in another format than the input (8-bit in, 10-bit out), mono, 4:1:1 and alpha planes, a siting
+override for C420pB, big-endian samples, scene cuts above 8 bits (ssm_luma_sad_fwd and the score's / 255 are 8-bit), the recurrent
+configuration (N_FRAMES > 2); shutter weights other than
 the box, a light curve chosen from the clip's tags, HDR transfer curves (PQ, HLG), a shutter centred on the frame's instant or open for longer than the frame interval,
 variable-rate input, speeds that change within a clip; a default scene-cut threshold, fades and dissolves, cuts judged on chroma,
 skipping the GPU work of a cut pair, scene cuts together with a shutter.
@@ -46,12 +55,38 @@ from .frames import _f3, cfg_mean_std, padded_dims
 
 BT601, BT709 = 0, 1
 LIMITED, FULL = 0, 1
-CENTRED, COSITED, C444 = 0, 1, 2          # chroma siting (include/ssm_hip.h SSM_YUV_*)
+CENTRED, COSITED, C444, C422 = 0, 1, 2, 3          # chroma siting / plane layout (include/ssm_hip.h SSM_YUV_*)
 YUV_ROW = 20
 MATRICES = {"bt601": BT601, "bt709": BT709}
 RANGES = {"limited": LIMITED, "full": FULL}
 # Y4M colour-space tags: accepted -> siting; refused ones are named in the error
 CHROMA_TAGS = {"420": CENTRED, "420jpeg": CENTRED, "420mpeg2": COSITED, "444": C444}
+# with extended=True: tag -> (layout, bits); samples of more than 8 bits are 16-bit little-endian words
+DEEP_BITS = (9, 10, 12, 14, 16)
+EXTENDED_TAGS = {tag: (lay, 8) for tag, lay in CHROMA_TAGS.items()}
+EXTENDED_TAGS["422"] = (C422, 8)
+for _b in DEEP_BITS:
+    EXTENDED_TAGS.update({"420p%d" % _b: (CENTRED, _b), "422p%d" % _b: (C422, _b), "444p%d" % _b: (C444, _b)})
+_TAGS_8BIT = "8-bit C420, C420jpeg, C420mpeg2 and C444 are"
+_TAGS_EXTENDED = "C420, C420jpeg, C420mpeg2, C422, C444 and C420pB, C422pB, C444pB with B in 9, 10, 12, 14, 16 are"
+
+
+def chroma_format(tag, extended=False):
+    """(layout, bits) of a Y4M colour-space tag; a tag outside the set - the 8-bit one, or with `extended` EXTENDED_TAGS - is refused by name."""
+    if extended:
+        if tag not in EXTENDED_TAGS:
+            raise Y4MError("Y4M colour space C%s is not supported (%s)" % (tag, _TAGS_EXTENDED))
+        return EXTENDED_TAGS[tag]
+    if tag not in CHROMA_TAGS:
+        raise Y4MError("Y4M colour space C%s is not supported (%s)" % (tag, _TAGS_8BIT))
+    return CHROMA_TAGS[tag], 8
+
+
+def sample_bytes(bits):
+    """Bytes of a sample of `bits` significant bits (8 to 16): 1, or 2 above 8."""
+    if isinstance(bits, bool) or int(bits) != bits or not 8 <= bits <= 16:
+        raise ValueError("bits = %r: a sample has 8 to 16 significant bits" % (bits,))
+    return 1 if bits == 8 else 2
 _KRKB = {BT601: (0.299, 0.114), BT709: (0.2126, 0.0722)}
 
 
@@ -85,8 +120,12 @@ def parse_shutter_light(name):
     return name
 
 
-def yuv_table():
-    """[2 matrices][2 ranges][YUV_ROW] float32: every constant evaluated in float64 and rounded once (layout: include/ssm_hip.h)."""
+def yuv_table(bits=8):
+    """[2 matrices][2 ranges][YUV_ROW] float32 for samples of `bits` significant bits: every constant evaluated in float64 and rounded
+    once (layout: include/ssm_hip.h).  With s = 2^(bits-8) and peak = 2^bits - 1 the codes map to the 0 .. 255 units the kernels work in:
+    limited 16 s .. 235 s (240 s), full 0 .. peak.  bits = 8 gives s = 1 and peak = 255: the 8-bit table, bit for bit."""
+    sample_bytes(bits)
+    s, peak = float(1 << (bits - 8)), float((1 << bits) - 1)
     t = np.zeros((2, 2, YUV_ROW), dtype=np.float64)
     for m, (kr, kb) in _KRKB.items():
         kg = 1.0 - kr - kb
@@ -95,36 +134,41 @@ def yuv_table():
             t[m, r, :19] = [kr, kg, kb,
                             2.0 * (1.0 - kr), 2.0 * (1.0 - kb) * kb / kg, 2.0 * (1.0 - kr) * kr / kg, 2.0 * (1.0 - kb),
                             1.0 / (2.0 * (1.0 - kb)), 1.0 / (2.0 * (1.0 - kr)),
-                            255.0 / 219.0 if lim else 1.0, 255.0 / 224.0 if lim else 1.0,
-                            219.0 / 255.0 if lim else 1.0, 224.0 / 255.0 if lim else 1.0,
-                            16.0 if lim else 0.0, 128.0,
-                            16.0 if lim else 0.0, 235.0 if lim else 255.0, 16.0 if lim else 0.0, 240.0 if lim else 255.0]
+                            255.0 / (219.0 * s) if lim else 255.0 / peak, 255.0 / (224.0 * s) if lim else 255.0 / peak,
+                            219.0 * s / 255.0 if lim else peak / 255.0, 224.0 * s / 255.0 if lim else peak / 255.0,
+                            16.0 * s if lim else 0.0, 128.0 * s,
+                            16.0 * s if lim else 0.0, 235.0 * s if lim else peak, 16.0 * s if lim else 0.0, 240.0 * s if lim else peak]
     return t.astype(np.float32)
 
 
-_table_c = None
+_table_c = {}
 
 
-def _table_ptr():
-    global _table_c
-    if _table_c is None:
-        flat = yuv_table().reshape(-1)
-        _table_c = (ctypes.c_float * flat.size)(*[float(v) for v in flat])
-    return _table_c
+def _table_ptr(bits=8):
+    """The table of a bit depth as the C array the entry points take; one per depth, kept."""
+    if bits not in _table_c:
+        flat = yuv_table(bits).reshape(-1)
+        _table_c[bits] = (ctypes.c_float * flat.size)(*[float(v) for v in flat])
+    return _table_c[bits]
 
 
-def chroma_dims(h, w, siting):
-    return (h, w) if siting == C444 else ((h + 1) // 2, (w + 1) // 2)
+def chroma_dims(h, w, siting, bits=8):
+    if siting == C444:
+        return h, w
+    return (h, (w + 1) // 2) if siting == C422 else ((h + 1) // 2, (w + 1) // 2)
 
 
-def frame_bytes(h, w, siting):
+def frame_bytes(h, w, siting, bits=8):
     ch, cw = chroma_dims(h, w, siting)
-    return h * w + 2 * ch * cw
+    return (h * w + 2 * ch * cw) * sample_bytes(bits)
 
 
-def split_planes(payload, h, w, siting):
-    """[N, frame_bytes] uint8 -> Y [N,h,w], U, V [N,ch,cw] (views)."""
+def split_planes(payload, h, w, siting, bits=8):
+    """[N, frame_bytes] uint8 -> Y [N,h,w], U, V [N,ch,cw] (views); with bits > 8 the payload is a numpy array and the planes are its
+    little-endian uint16 words."""
     ch, cw = chroma_dims(h, w, siting)
+    if sample_bytes(bits) == 2:
+        payload = payload.view("<u2")
     n = payload.shape[0]
     y = payload[:, :h * w].reshape(n, h, w)
     u = payload[:, h * w:h * w + ch * cw].reshape(n, ch, cw)
@@ -142,16 +186,18 @@ _F = np.float32
 
 
 def _upsample_host(c, h, w, siting):
-    """Chroma plane [N,ch,cw] float32 -> [N,h,w]: bilinear, indices clamped; columns first, then rows, as the kernel."""
+    """Chroma plane [N,ch,cw] float32 -> [N,h,w]: bilinear, indices clamped; columns first, then rows, as the kernel.  4:2:2: columns only."""
     ch, cw = c.shape[1:]
     x = np.arange(w)
     j, odd = x // 2, (x % 2) == 1
-    a0, a1, b1, b2 = (_F(0.0), _F(1.0), _F(0.5), _F(0.5)) if siting == COSITED else (_F(0.25), _F(0.75), _F(0.75), _F(0.25))
+    a0, a1, b1, b2 = (_F(0.0), _F(1.0), _F(0.5), _F(0.5)) if siting in (COSITED, C422) else (_F(0.25), _F(0.75), _F(0.75), _F(0.25))
     ia = np.clip(np.where(odd, j, j - 1), 0, cw - 1)
     ib = np.clip(np.where(odd, j + 1, j), 0, cw - 1)
     wa = np.where(odd, b1, a0).astype(_F)
     wb = np.where(odd, b2, a1).astype(_F)
     hz = wa * c[:, :, ia] + wb * c[:, :, ib]
+    if siting == C422:
+        return hz
     y = np.arange(h)
     i, odd = y // 2, (y % 2) == 1
     ia = np.clip(np.where(odd, i, i - 1), 0, ch - 1)
@@ -161,14 +207,15 @@ def _upsample_host(c, h, w, siting):
     return wa * hz[:, ia] + wb * hz[:, ib]
 
 
-def yuv_to_frames_host(payload, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, mean=None, std=None, pad_before_norm=True):
-    """Yardstick of ssm_frames_from_yuv_fwd: [N, frame_bytes] uint8 (numpy) -> [N,3,Hp,Wp] float32."""
+def yuv_to_frames_host(payload, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, mean=None, std=None, pad_before_norm=True, *,
+                       bits=8):
+    """Yardstick of ssm_frames_from_yuv_fwd / ssm_frames_from_yuvx_fwd: [N, frame_bytes] uint8 (numpy) -> [N,3,Hp,Wp] float32."""
     if mean is None:
         mean, std = cfg_mean_std(None)
-    k = yuv_table()[matrix, color_range]
+    k = yuv_table(bits)[matrix, color_range]
     kr, kg, kb, rv, gu, gv, bu, cbs, crs, ys, cs, iys, ics, yoff, coff = k[:15]
-    payload = np.ascontiguousarray(payload).reshape(-1, frame_bytes(h, w, siting))
-    yq, uq, vq = split_planes(payload, h, w, siting)
+    payload = np.ascontiguousarray(payload).reshape(-1, frame_bytes(h, w, siting, bits))
+    yq, uq, vq = split_planes(payload, h, w, siting, bits)
     yl, cu, cv = yq.astype(_F), uq.astype(_F), vq.astype(_F)
     if siting != C444:
         cu, cv = _upsample_host(cu, h, w, siting), _upsample_host(cv, h, w, siting)
@@ -186,11 +233,11 @@ def yuv_to_frames_host(payload, h, w, siting=CENTRED, matrix=BT709, color_range=
     return out
 
 
-def frames_to_yuv_host(x, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, mean=None, std=None):
-    """Yardstick of ssm_frames_to_yuv_fwd: [N,3,Hp,Wp] float32 (numpy, finite) -> [N, frame_bytes] uint8."""
+def frames_to_yuv_host(x, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, mean=None, std=None, *, bits=8):
+    """Yardstick of ssm_frames_to_yuv_fwd / ssm_frames_to_yuvx_fwd: [N,3,Hp,Wp] float32 (numpy, finite) -> [N, frame_bytes] uint8."""
     if mean is None:
         mean, std = cfg_mean_std(None)
-    k = yuv_table()[matrix, color_range]
+    k = yuv_table(bits)[matrix, color_range]
     kr, kg, kb, rv, gu, gv, bu, cbs, crs, ys, cs, iys, ics, yoff, coff, ylo, yhi, clo, chi = k[:19]
     x = np.asarray(x, dtype=_F)
     n, _, hp, wp = x.shape
@@ -211,18 +258,18 @@ def frames_to_yuv_host(x, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITE
         cx, cy = np.arange(cw), np.arange(ch)
         c0, c1 = 2 * cx, np.minimum(2 * cx + 1, w - 1)
         r0, r1 = 2 * cy, np.minimum(2 * cy + 1, h - 1)
-        if siting == COSITED:
+        if siting in (COSITED, C422):
             cl = np.maximum(2 * cx - 1, 0)
             hz = ((c[:, :, cl] + _F(2.0) * c[:, :, c0]) + c[:, :, c1]) * _F(0.25)
-            return (hz[:, r0] + hz[:, r1]) * _F(0.5)
+            return hz if siting == C422 else (hz[:, r0] + hz[:, r1]) * _F(0.5)
         t, bt = c[:, r0], c[:, r1]
         return ((t[:, :, c0] + t[:, :, c1]) + (bt[:, :, c0] + bt[:, :, c1])) * _F(0.25)
 
     def code(v, scale, off, lo, hi):
-        return np.clip(np.rint(v * scale + off), lo, hi).astype(np.uint8)
+        return np.clip(np.rint(v * scale + off), lo, hi).astype(np.uint8 if bits == 8 else "<u2")
 
     planes = [code(yf, iys, yoff, ylo, yhi), code(sub(cb), ics, coff, clo, chi), code(sub(cr), ics, coff, clo, chi)]
-    return np.concatenate([p.reshape(n, -1) for p in planes], axis=1)
+    return np.concatenate([p.reshape(n, -1) for p in planes], axis=1).view(np.uint8)
 
 
 def accumulate_host(frames, acc, init, scale):
@@ -310,33 +357,37 @@ def luma_sad_host(ya, yb):
 
 
 # ---- the kernels -------------------------------------------------------------------------------------------------------------------
-def frames_from_yuv(payload, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, cfg=None, pad_before_norm=True, out=None, multiple=32):
+def frames_from_yuv(payload, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, cfg=None, pad_before_norm=True, out=None, multiple=32,
+                    *, bits=8):
     """[N, frame_bytes] uint8 device tensor of Y4M payloads -> [N,3,Hp,Wp] normalised fp32 (into `out` if given); (Hp, Wp) =
-    padded_dims(h, w, multiple): 32 for the path itself, 32 * flow_scale for the coarse-flow mode."""
+    padded_dims(h, w, multiple): 32 for the path itself, 32 * flow_scale for the coarse-flow mode.  bits > 8: the bytes are 16-bit
+    little-endian samples (a payload that does not start on an even address is refused)."""
     assert payload.is_cuda and payload.dtype == torch.uint8 and payload.dim() == 2 and payload.is_contiguous() and \
-        payload.shape[1] == frame_bytes(h, w, siting), "payloads must be a contiguous [N, frame_bytes] uint8 tensor on the GPU"
+        payload.shape[1] == frame_bytes(h, w, siting, bits), "payloads must be a contiguous [N, frame_bytes] uint8 tensor on the GPU"
     n = payload.shape[0]
     (hp, wp), (top, left) = padded_dims(h, w, multiple)
     mean, std = cfg_mean_std(cfg)
     if out is None:
         out = torch.empty(n, 3, hp, wp, dtype=torch.float32, device=payload.device)
     assert tuple(out.shape) == (n, 3, hp, wp)
-    hb.check(hb.load().ssm_frames_from_yuv_fwd(payload.data_ptr(), hb.view_of(out), n, h, w, hp, wp, top, left, _f3(mean), _f3(std),
-                                               1 if pad_before_norm else 0, _table_ptr(), matrix, color_range, siting, hb.stream_ptr()))
+    hb.check(hb.load().ssm_frames_from_yuvx_fwd(payload.data_ptr(), hb.view_of(out), n, h, w, hp, wp, top, left, _f3(mean), _f3(std),
+                                                1 if pad_before_norm else 0, _table_ptr(bits), matrix, color_range, siting,
+                                                sample_bytes(bits), hb.stream_ptr()))
     return out
 
 
-def frames_to_yuv(x, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, cfg=None, out=None):
-    """[N,3,Hp,Wp] normalised fp32 (finite) -> [N, frame_bytes] uint8 payloads, the centred padding cropped away."""
+def frames_to_yuv(x, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, cfg=None, out=None, *, bits=8):
+    """[N,3,Hp,Wp] normalised fp32 (finite) -> [N, frame_bytes] uint8 payloads (bits > 8: of 16-bit little-endian samples), the centred
+    padding cropped away."""
     hb.require_device(x, "frame tensor")
     n, _, hp, wp = x.shape
     top, left = (hp - h) // 2, (wp - w) // 2
     mean, std = cfg_mean_std(cfg)
     if out is None:
-        out = torch.empty(n, frame_bytes(h, w, siting), dtype=torch.uint8, device=x.device)
-    assert out.is_contiguous() and tuple(out.shape) == (n, frame_bytes(h, w, siting)) and out.dtype == torch.uint8
-    hb.check(hb.load().ssm_frames_to_yuv_fwd(hb.view_of(x), out.data_ptr(), n, h, w, top, left, _f3(mean), _f3(std), _table_ptr(),
-                                             matrix, color_range, siting, hb.stream_ptr()))
+        out = torch.empty(n, frame_bytes(h, w, siting, bits), dtype=torch.uint8, device=x.device)
+    assert out.is_contiguous() and tuple(out.shape) == (n, frame_bytes(h, w, siting, bits)) and out.dtype == torch.uint8
+    hb.check(hb.load().ssm_frames_to_yuvx_fwd(hb.view_of(x), out.data_ptr(), n, h, w, top, left, _f3(mean), _f3(std), _table_ptr(bits),
+                                              matrix, color_range, siting, sample_bytes(bits), hb.stream_ptr()))
     return out
 
 
@@ -372,10 +423,12 @@ def _ratio(text, what):
 
 class Y4MReader:
     """A YUV4MPEG2 stream from a path, `-` (stdin) or a binary file object.  Attributes: width, height, rate (num, den), interlace,
-    aspect (num, den), chroma (the C tag's text, `420jpeg` when absent), siting, color_range (LIMITED / FULL from ffmpeg's
-    XCOLORRANGE tag, None when absent), xtags (every X tag as read), frame_bytes."""
+    aspect (num, den), chroma (the C tag's text, `420jpeg` when absent), siting, bits, sample_bytes, color_range (LIMITED / FULL from
+    ffmpeg's XCOLORRANGE tag, None when absent), xtags (every X tag as read), frame_bytes.  extended=True: EXTENDED_TAGS (4:2:2 and 9 to
+    16 bits per sample) beside the 8-bit 4:2:0 and 4:4:4 tags that are taken without it."""
 
-    def __init__(self, src):
+    def __init__(self, src, extended=False):
+        self.extended = bool(extended)
         self._own = isinstance(src, str) and src != "-"
         self.f = open(src, "rb") if self._own else (sys.stdin.buffer if src == "-" else src)
         line = self.f.readline(4096)
@@ -410,9 +463,8 @@ class Y4MReader:
             raise Y4MError("the Y4M header has no frame size (W, H)")
         if self.interlace not in ("p", "?"):
             raise Y4MError("interlaced Y4M input (I%s) is not supported: deinterlace first" % self.interlace)
-        if self.chroma not in CHROMA_TAGS:
-            raise Y4MError("Y4M colour space C%s is not supported (8-bit C420, C420jpeg, C420mpeg2 and C444 are)" % self.chroma)
-        self.siting = CHROMA_TAGS[self.chroma]
+        self.siting, self.bits = chroma_format(self.chroma, self.extended)
+        self.sample_bytes = sample_bytes(self.bits)
         self.color_range = None
         for x in self.xtags:
             if x.startswith("COLORRANGE="):
@@ -420,7 +472,7 @@ class Y4MReader:
                 if v not in RANGES:
                     raise Y4MError("unknown XCOLORRANGE=%s in the Y4M header" % x.split("=", 1)[1])
                 self.color_range = RANGES[v]
-        self.frame_bytes = frame_bytes(self.height, self.width, self.siting)
+        self.frame_bytes = frame_bytes(self.height, self.width, self.siting, self.bits)
         self.frames_read = 0
 
     def read_frame_into(self, buf):
@@ -455,19 +507,21 @@ class Y4MReader:
 
 
 class Y4MWriter:
-    """Writes the stream header at once, then one FRAME record per write_frame()."""
+    """Writes the stream header at once, then one FRAME record per write_frame().  extended=True: the tags of EXTENDED_TAGS, as the reader."""
 
-    def __init__(self, dst, width, height, rate=(25, 1), aspect=(0, 0), chroma="420jpeg", color_range=None, interlace="p", xtags=()):
-        if chroma not in CHROMA_TAGS:
-            raise Y4MError("Y4M colour space C%s is not supported (8-bit C420, C420jpeg, C420mpeg2 and C444 are)" % chroma)
+    def __init__(self, dst, width, height, rate=(25, 1), aspect=(0, 0), chroma="420jpeg", color_range=None, interlace="p", xtags=(),
+                 extended=False):
+        self.extended = bool(extended)
+        siting, self.bits = chroma_format(chroma, self.extended)
+        self.sample_bytes = sample_bytes(self.bits)
         self._own = isinstance(dst, str) and dst != "-"
         self.f = open(dst, "wb") if self._own else (sys.stdout.buffer if dst == "-" else dst)
         self.width, self.height, self.rate, self.aspect, self.chroma = int(width), int(height), tuple(rate), tuple(aspect), chroma
-        self.siting, self.color_range, self.interlace = CHROMA_TAGS[chroma], color_range, interlace
+        self.siting, self.color_range, self.interlace = siting, color_range, interlace
         self.xtags = [x for x in xtags if not x.startswith("COLORRANGE=")]
         if color_range is not None:
             self.xtags.append("COLORRANGE=" + ("FULL" if color_range == FULL else "LIMITED"))
-        self.frame_bytes = frame_bytes(self.height, self.width, self.siting)
+        self.frame_bytes = frame_bytes(self.height, self.width, self.siting, self.bits)
         self.frames_written = 0
         head = "YUV4MPEG2 W%d H%d F%d:%d I%s A%d:%d C%s" % (self.width, self.height, self.rate[0], self.rate[1], interlace,
                                                             self.aspect[0], self.aspect[1], chroma)
@@ -475,9 +529,9 @@ class Y4MWriter:
 
     @classmethod
     def like(cls, dst, reader, rate=None, color_range=None):
-        """A writer for frames of `reader`'s format; `rate` and `color_range` override the reader's."""
+        """A writer for frames of `reader`'s format (its `extended` flag with it); `rate` and `color_range` override the reader's."""
         return cls(dst, reader.width, reader.height, rate or reader.rate, reader.aspect, reader.chroma,
-                   reader.color_range if color_range is None else color_range, "p", reader.xtags)
+                   reader.color_range if color_range is None else color_range, "p", reader.xtags, extended=getattr(reader, "extended", False))
 
     def write_frame(self, buf):
         mv = memoryview(buf).cast("B")
@@ -1020,8 +1074,8 @@ def upload_times(times, slots, np_t, host_t, dev_t):
 
 
 # What run() works out of a reader / writer pair before it looks at the mode: frame size, chroma siting, frame_bytes, matrix, code range,
-# the device, the canvas's multiple and the canvas.
-Clip = collections.namedtuple("Clip", "h w siting fb matrix crange dev mult hp wp")
+# the device, the canvas's multiple, the canvas and the samples' significant bits.
+Clip = collections.namedtuple("Clip", "h w siting fb matrix crange dev mult hp wp bits")
 
 
 class VideoInterpolator:
@@ -1130,15 +1184,18 @@ class VideoInterpolator:
 
     def _clip(self, reader, writer):
         """The Clip of a run, or the refusal of a writer of another format or of a model that is not on the GPU."""
-        h, w, siting, fb = reader.height, reader.width, reader.siting, reader.frame_bytes
-        if (writer.height, writer.width, writer.siting) != (h, w, siting):
+        h, w, siting, fb, bits = reader.height, reader.width, reader.siting, reader.frame_bytes, getattr(reader, "bits", 8)
+        if (writer.height, writer.width, writer.siting, getattr(writer, "bits", 8)) != (h, w, siting, bits):
             raise ValueError("reader and writer disagree on the frame format")
+        if self.scene_cut is not None and bits > 8:
+            raise ValueError("scene_cut is not available for C%s: the luma differences (ssm_luma_sad_fwd) and the score's / 255 are for 8-bit "
+                             "samples, these have %d bits" % (reader.chroma, bits))
         matrix = default_matrix(h) if self.matrix is None else self.matrix
         crange = self.color_range if self.color_range is not None else (reader.color_range if reader.color_range is not None else LIMITED)
         dev = next(self.model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
-        return Clip(h, w, siting, fb, matrix, crange, dev, 32 * self.flow_scale, *self.canvas(h, w))
+        return Clip(h, w, siting, fb, matrix, crange, dev, 32 * self.flow_scale, *self.canvas(h, w), bits)
 
     def _cut_state(self, n, depth, pairs, clip):
         """What the scene cuts add to a mode's buffers: SceneCuts, the sums of a pass on the device (per stream) and in the pinned ring slot
@@ -1187,7 +1244,7 @@ class VideoInterpolator:
         records `ingested`: the pass that reads it waits for that event, and the pass that read the row before has recorded its own
         event (after its call) earlier in the chain of waits.  The sums go back to the pass's ring slot ahead of `done`."""
         from .evaluation import t_values
-        h, w, siting, fb, matrix, crange, dev, mult, hp, wp = clip
+        h, w, siting, fb, matrix, crange, dev, mult, hp, wp, bits = clip
         pipe = self._pipeline(hp, wp, dev)
         n, pb, nt = pipe.n, self.pb, self.rate - 1
         depth = n + 2                                                  # ring slots: one per pass in flight, one being read, one being written
@@ -1217,7 +1274,7 @@ class VideoInterpolator:
             with torch.cuda.stream(pipe.streams[last]):
                 new = dev_in[last][lead:]
                 new[:1].copy_(first, non_blocking=True)
-                frames_from_yuv(new[:1], h, w, siting, matrix, crange, self.cfg, True, out=planes[last][pb:], multiple=mult)
+                frames_from_yuv(new[:1], h, w, siting, matrix, crange, self.cfg, True, out=planes[last][pb:], multiple=mult, bits=bits)
                 if cuts is not None:
                     dev_in[0][0, :h * w].copy_(new[0, :h * w])
                 ingested[last].record()
@@ -1240,7 +1297,7 @@ class VideoInterpolator:
                     new.copy_(host_in[r], non_blocking=True)
                     st.wait_event(ingested[kprev])
                     planes[k][0].copy_(planes[kprev][pb])
-                    frames_from_yuv(new, h, w, siting, matrix, crange, self.cfg, True, out=planes[k][1:], multiple=mult)
+                    frames_from_yuv(new, h, w, siting, matrix, crange, self.cfg, True, out=planes[k][1:], multiple=mult, bits=bits)
                     if cuts is not None:
                         luma_sad(dev_in[k][:pb], dev_in[k][1:], h, w, out=dev_sums[k])
                         dev_in[(j + 1) % n][0, :h * w].copy_(dev_in[k][pb, :h * w])
@@ -1248,7 +1305,7 @@ class VideoInterpolator:
                     x = planes[k]
                     img6 = x.view(1, 6, hp, wp) if pb == 1 else x.as_strided((pb, 6, hp, wp), (3 * hp * wp, hp * wp, wp, 1))
                     frames = pipe.engines[k].run(img6, t_dev, False)
-                    frames_to_yuv(frames, h, w, siting, matrix, crange, self.cfg, out=dev_out[k])
+                    frames_to_yuv(frames, h, w, siting, matrix, crange, self.cfg, out=dev_out[k], bits=bits)
                     host_out[r].copy_(dev_out[k], non_blocking=True)
                     if cuts is not None:
                         host_sums[r].copy_(dev_sums[k], non_blocking=True)
@@ -1284,7 +1341,7 @@ class VideoInterpolator:
         its own uploaded row, the right row of the pair before it, or row 0.  The rows of the pairs that run step evenly unless the
         timeline skips pairs inside a pass (sad_runs): one ssm_luma_sad_fwd call then, one per run otherwise.  Only pairs that run are
         summed and fed to SceneCuts."""
-        h, w, siting, fb, matrix, crange, dev, mult, hp, wp = clip
+        h, w, siting, fb, matrix, crange, dev, mult, hp, wp, bits = clip
         tl = self.timeline(reader.rate)
         S, pb, n = tl.slots, self.pb, self.n_streams
         pipe = self._pipeline(hp, wp, dev, S) if S else None          # an integer step only picks input frames: nothing to run
@@ -1321,7 +1378,7 @@ class VideoInterpolator:
                     if not own_left:
                         planes[k][p, 0].copy_(planes[k][p - 1, 1] if p else planes[(j - 1) % n][last_p[0], 1])
                     frames_from_yuv(new[row:row + rows], h, w, siting, matrix, crange, self.cfg, True, out=planes[k][p, 2 - rows:],
-                                    multiple=mult)
+                                    multiple=mult, bits=bits)
                 upload_times([ts for _, _, ts in pairs], S, np_t[r], host_t[r], dev_t[k])
                 if cuts is not None:
                     rights = [lead + row + (1 if own_left else 0) for row, own_left, _ in pairs]          # rows of dev_in[k]
@@ -1339,7 +1396,7 @@ class VideoInterpolator:
                 else:
                     spans = [(p * S, len(ts)) for p, (_, _, ts) in enumerate(pairs)]
                 for o, m in spans:
-                    frames_to_yuv(frames[o:o + m], h, w, siting, matrix, crange, self.cfg, out=dev_out[k][o:o + m])
+                    frames_to_yuv(frames[o:o + m], h, w, siting, matrix, crange, self.cfg, out=dev_out[k][o:o + m], bits=bits)
                     host_out[r][o:o + m].copy_(dev_out[k][o:o + m], non_blocking=True)
                 if cuts is not None:
                     host_sums[r].copy_(dev_sums[k], non_blocking=True)
@@ -1383,7 +1440,7 @@ class VideoInterpolator:
         the pass before recorded after its last accumulate and egress, so the engines of neighbouring passes still overlap, only these
         short tails are serialised, and the result depends on nothing but the time order.  One output is open at a time (OPEN_OUTPUTS),
         which sizes the ring of accumulators.  Memory is fixed by the frame size, n_streams, pairs_per_batch, slots and that bound."""
-        h, w, siting, fb, matrix, crange, dev, mult, hp, wp = clip
+        h, w, siting, fb, matrix, crange, dev, mult, hp, wp, bits = clip
         tl = self.timeline(reader.rate)
         slots, pb, n = tl.slots, self.pb, self.n_streams
         pipe = self._pipeline(hp, wp, dev, slots) if slots else None          # a step whose samples are all input frames: nothing to synthesise
@@ -1419,7 +1476,7 @@ class VideoInterpolator:
                 dev_in[k][:rows].copy_(host_in[r][:rows], non_blocking=True)
                 if carry is not None:
                     planes[k][0].copy_(planes[kprev][carry])
-                frames_from_yuv(dev_in[k][:rows], h, w, siting, matrix, crange, self.cfg, True, out=planes[k][1:1 + rows], multiple=mult)
+                frames_from_yuv(dev_in[k][:rows], h, w, siting, matrix, crange, self.cfg, True, out=planes[k][1:1 + rows], multiple=mult, bits=bits)
                 for p, (left, right, _) in enumerate(pairs):
                     sides[k][p, 0].copy_(planes[k][left])
                     sides[k][p, 1].copy_(planes[k][right])
@@ -1438,7 +1495,7 @@ class VideoInterpolator:
                     else:
                         hb.frames_accumulate_light(x, a, 1 if init else 0, scale if last else 1.0, *light, 1 if last else 0)
                     if last:
-                        frames_to_yuv(a, h, w, siting, matrix, crange, self.cfg, out=dev_out[k][o:o + 1])
+                        frames_to_yuv(a, h, w, siting, matrix, crange, self.cfg, out=dev_out[k][o:o + 1], bits=bits)
                         host_out[r][o:o + 1].copy_(dev_out[k][o:o + 1], non_blocking=True)
                         o += 1
                 summed[k].record()
