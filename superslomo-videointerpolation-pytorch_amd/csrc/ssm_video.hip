@@ -13,10 +13,10 @@
 //                            the two chroma codes of a plane and row as one store (2 or 4 bytes), when size and alignment allow it
 //   frames_accumulate_kernel the shutter of the streamed loop: N frames summed, in increasing n, into one fp32 accumulator
 //                            that is read at most once and written once per launch; one lane = 4 consecutive pixels of a row of one
-//                            channel (16-byte loads and stores), or one pixel when a view does not allow it
-//   frames_accumulate_light_kernel  the same sum taken in light: every value is denormalised, clamped to [0, 1] and decoded
-//                            by one of the light curves of ssm_amd.video.light_curve before it is added, and the call that closes an output
-//                            encodes and normalises the mean again; the power is v_log_f32, a multiply and v_exp_f32
+//                            channel (16-byte loads and stores), or one pixel when a view does not allow it.  One kernel, two modes: the
+//                            sum of the coded values as they are, or the sum taken in light - every value denormalised, clamped to [0, 1]
+//                            and decoded by one of the light curves of ssm_amd.video.light_curve before it is added, the mean encoded and
+//                            normalised again by the call that closes an output; the power is v_log_f32, a multiply and v_exp_f32
 //   luma_sad_kernel          scene cuts of the streamed loop: per frame pair the exact sum of |a - b| over the 8-bit Y planes;
 //                            one lane = 16 consecutive bytes of each plane (one 16-byte load per operand), or byte loads where a plane
 //                            does not start on a 16-byte boundary; v_sad_u8 into a 32-bit lane sum, shuffles, one 64-bit atomic per workgroup
@@ -308,40 +308,7 @@ __global__ __launch_bounds__(256) void frames_to_yuv_kernel(ssm_view in, S *__re
     }
 }
 
-// ---- shutter: frames summed into an accumulator ----------------------------------------------------------------------------------------
-// s = init ? src[0] : acc + src[0];  s = s + src[n], n = 1 .. N-1;  acc = s * scale - one rounded fp32 operation per step (the file is
-// compiled without contraction), the order of ssm_amd.video.accumulate_host.  The loads of the N frames do not depend on one another and
-// the one store comes last, so the unrolled loop keeps several loads in flight per lane.  The float4 arithmetic stays four scalar
-// v_add_f32 / v_mul_f32 per step only because the Makefile builds every file with -fno-slp-vectorize (check_isa.sh fails the build on any
-// v_pk_*_f32): a plain hipcc -O3 of this file packs it into v_pk_add_f32 / v_pk_mul_f32.
-template <int V>          // pixels per lane: 4 (float4 accesses) or 1
-__global__ __launch_bounds__(256) void frames_accumulate_kernel(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale) {
-    const int x = (blockIdx.x * 64 + threadIdx.x) * V, y = blockIdx.y * 4 + threadIdx.y, c = blockIdx.z;
-    if (x >= W || y >= H) return;          // V = 4: W % 4 == 0, so x + 3 < W
-    const float *s = src.ptr + (long long)c * src.sc + (long long)y * src.sh + x;
-    float *a = acc.ptr + (long long)c * acc.sc + (long long)y * acc.sh + x;
-    if constexpr (V == 4) {
-        float4 v = *reinterpret_cast<const float4 *>(s);
-        if (!init) {
-            const float4 o = *reinterpret_cast<const float4 *>(a);
-            v = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
-        }
-#pragma unroll 4
-        for (int n = 1; n < N; ++n) {
-            const float4 f = *reinterpret_cast<const float4 *>(s + (long long)n * src.sb);
-            v = make_float4(v.x + f.x, v.y + f.y, v.z + f.z, v.w + f.w);
-        }
-        *reinterpret_cast<float4 *>(a) = make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale);
-    } else {
-        float v = *s;
-        if (!init) v = *a + v;
-#pragma unroll 4
-        for (int n = 1; n < N; ++n) v = v + s[(long long)n * src.sb];
-        *a = v * scale;
-    }
-}
-
-// ---- shutter in linear light ----------------------------------------------------------------------------------------------------------
+// ---- shutter: frames summed into an accumulator, coded or in linear light -------------------------------------------------------------
 // one row of ssm_amd.video.light_curve (include/ssm_hip.h: SSM_LIGHT_ROW floats)
 struct LightRow {
     float thr, islope, a, i1a, g;          // decode: c <= thr ? c * islope : ((c + a) * i1a) ^ g
@@ -366,43 +333,58 @@ __device__ __forceinline__ float light_encode(float l, float sd, float mean, con
     return (c - mean) / sd;
 }
 
-// s = init ? dec(src[0]) : acc + dec(src[0]);  s = s + dec(src[n]), n = 1 .. N-1;  r = s * scale;  acc = encode ? enc(r) : r - the structure of
-// frames_accumulate_kernel: independent loads, the accumulator read at most once and written once.  Channel = blockIdx.z (three of them).
-template <int V>          // pixels per lane: 4 (float4 accesses) or 1
-__global__ __launch_bounds__(256) void frames_accumulate_light_kernel(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale,
-                                                                      Norm3 nm, LightRow k, int encode) {
+// What the light mode adds to the kernel's arguments (its channels are three); the coded mode adds nothing.
+template <bool Light> struct Curve {};
+template <> struct Curve<true> { Norm3 nm; LightRow row; int encode; };
+
+// V consecutive pixels of a row as one access: 16 bytes (V = 4: W % 4 == 0 and both views 16-byte aligned) or one float
+template <int V> struct alignas(4 * V) Px { float f[V]; };
+
+// s = init ? dec(src[0]) : acc + dec(src[0]);  s = s + dec(src[n]), n = 1 .. N-1;  r = s * scale;  acc = enc(r) - one rounded fp32 operation
+// per step (the file is compiled without contraction).  Coded (Light = false): dec and enc are the identity, the order of
+// ssm_amd.video.accumulate_host, bit for bit.  Light: dec is light_decode of the channel (blockIdx.z, three of them), enc light_encode on the
+// call that closes an output (cv.encode) and the identity before.  The loads of the N frames do not depend on one another and the one
+// store comes last, so the unrolled loop keeps several loads in flight per lane; the accumulator is read at most once and written once.
+// The arithmetic on a Px<4> stays four scalar v_add_f32 / v_mul_f32 per step only because the Makefile builds every file with
+// -fno-slp-vectorize (check_isa.sh fails the build on any v_pk_*_f32): a plain hipcc -O3 of this file packs it into v_pk_add_f32 /
+// v_pk_mul_f32.
+template <int V, bool Light>          // pixels per lane: 4 or 1
+__global__ __launch_bounds__(256) void frames_accumulate_kernel(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale,
+                                                                Curve<Light> cv) {
     const int x = (blockIdx.x * 64 + threadIdx.x) * V, y = blockIdx.y * 4 + threadIdx.y, c = blockIdx.z;
     if (x >= W || y >= H) return;          // V = 4: W % 4 == 0, so x + 3 < W
-    const float mean = c == 0 ? nm.m[0] : (c == 1 ? nm.m[1] : nm.m[2]), sd = c == 0 ? nm.s[0] : (c == 1 ? nm.s[1] : nm.s[2]);
-    const float black = (0.0f / 255.0f - mean) / sd;          // the ingest kernels' expression
+    float mean = 0.0f, sd = 1.0f, black = 0.0f;          // Light alone reads them
+    if constexpr (Light) {
+        mean = c == 0 ? cv.nm.m[0] : (c == 1 ? cv.nm.m[1] : cv.nm.m[2]), sd = c == 0 ? cv.nm.s[0] : (c == 1 ? cv.nm.s[1] : cv.nm.s[2]);
+        black = (0.0f / 255.0f - mean) / sd;          // the ingest kernels' expression
+    }
+    const auto dec = [&](float v) {
+        if constexpr (Light) return light_decode(v, sd, mean, black, cv.row);
+        else return v;
+    };
     const float *s = src.ptr + (long long)c * src.sc + (long long)y * src.sh + x;
     float *a = acc.ptr + (long long)c * acc.sc + (long long)y * acc.sh + x;
-    if constexpr (V == 4) {
-        const float4 f0 = *reinterpret_cast<const float4 *>(s);
-        float4 v = make_float4(light_decode(f0.x, sd, mean, black, k), light_decode(f0.y, sd, mean, black, k),
-                               light_decode(f0.z, sd, mean, black, k), light_decode(f0.w, sd, mean, black, k));
-        if (!init) {
-            const float4 o = *reinterpret_cast<const float4 *>(a);
-            v = make_float4(o.x + v.x, o.y + v.y, o.z + v.z, o.w + v.w);
-        }
-#pragma unroll 4
-        for (int n = 1; n < N; ++n) {
-            const float4 f = *reinterpret_cast<const float4 *>(s + (long long)n * src.sb);
-            v = make_float4(v.x + light_decode(f.x, sd, mean, black, k), v.y + light_decode(f.y, sd, mean, black, k),
-                            v.z + light_decode(f.z, sd, mean, black, k), v.w + light_decode(f.w, sd, mean, black, k));
-        }
-        v = make_float4(v.x * scale, v.y * scale, v.z * scale, v.w * scale);
-        if (encode) v = make_float4(light_encode(v.x, sd, mean, k), light_encode(v.y, sd, mean, k), light_encode(v.z, sd, mean, k),
-                                    light_encode(v.w, sd, mean, k));
-        *reinterpret_cast<float4 *>(a) = v;
-    } else {
-        float v = light_decode(*s, sd, mean, black, k);
-        if (!init) v = *a + v;
-#pragma unroll 4
-        for (int n = 1; n < N; ++n) v = v + light_decode(s[(long long)n * src.sb], sd, mean, black, k);
-        v = v * scale;
-        *a = encode ? light_encode(v, sd, mean, k) : v;
+    Px<V> v = *reinterpret_cast<const Px<V> *>(s);
+#pragma unroll
+    for (int i = 0; i < V; ++i) v.f[i] = dec(v.f[i]);
+    if (!init) {
+        const Px<V> o = *reinterpret_cast<const Px<V> *>(a);
+#pragma unroll
+        for (int i = 0; i < V; ++i) v.f[i] = o.f[i] + v.f[i];
     }
+#pragma unroll 4
+    for (int n = 1; n < N; ++n) {
+        const Px<V> f = *reinterpret_cast<const Px<V> *>(s + (long long)n * src.sb);
+#pragma unroll
+        for (int i = 0; i < V; ++i) v.f[i] = v.f[i] + dec(f.f[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < V; ++i) v.f[i] = v.f[i] * scale;
+    if constexpr (Light)
+        if (cv.encode)
+#pragma unroll
+            for (int i = 0; i < V; ++i) v.f[i] = light_encode(v.f[i], sd, mean, cv.row);
+    *reinterpret_cast<Px<V> *>(a) = v;
 }
 
 // ---- scene cuts: luma differences summed ---------------------------------------------------------------------------------------------
@@ -528,6 +510,17 @@ static int check_yuv(const char *name, int matrix, int range, int layout, bool e
     return SSM_OK;
 }
 
+// f(std::integral_constant<int, LAY_*>) of a layout: the one place where SSM_YUV_* picks a kernel instantiation
+template <typename F>
+static void with_layout(int layout, F f) {
+    if (layout == SSM_YUV_444)
+        f(std::integral_constant<int, LAY_444>{});
+    else if (layout == SSM_YUV_422)
+        f(std::integral_constant<int, LAY_422>{});
+    else
+        f(std::integral_constant<int, LAY_420>{});
+}
+
 template <typename S>
 static void launch_from_yuv(const void *frames_yuv, ssm_view out, int N, int H, int W, int Hp, int Wp, int top, int left, const float *mean3,
                             const float *std3, int pad_before_norm, const float *table, int matrix, int range, int layout, void *stream) {
@@ -539,15 +532,10 @@ static void launch_from_yuv(const void *frames_yuv, ssm_view out, int N, int H, 
     const dim3 grid((nbx + 63) / 64, (nby + 3) / 4, N);
     const long long fs = yuv_frame_samples(H, W, layout);
     const S *in = static_cast<const S *>(frames_yuv);
-    if (layout == SSM_YUV_444)
-        SSM_LAUNCH(frames_from_yuv_kernel<S, LAY_444>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, out, H, W, Hp, Wp, top, left, fs,
+    with_layout(layout, [&](auto lay) {
+        SSM_LAUNCH(frames_from_yuv_kernel<S, lay()>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, out, H, W, Hp, Wp, top, left, fs,
                    row_of(table, matrix, range), norm_of(mean3, std3), a0, a1, b1, b2, pad_before_norm ? 1 : 0, vec2);
-    else if (layout == SSM_YUV_422)
-        SSM_LAUNCH(frames_from_yuv_kernel<S, LAY_422>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, out, H, W, Hp, Wp, top, left, fs,
-                   row_of(table, matrix, range), norm_of(mean3, std3), a0, a1, b1, b2, pad_before_norm ? 1 : 0, vec2);
-    else
-        SSM_LAUNCH(frames_from_yuv_kernel<S, LAY_420>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, out, H, W, Hp, Wp, top, left, fs,
-                   row_of(table, matrix, range), norm_of(mean3, std3), a0, a1, b1, b2, pad_before_norm ? 1 : 0, vec2);
+    });
 }
 
 static int frames_from_yuv(const char *name, const char *entry, bool extended, const void *frames_yuv, ssm_view out, int N, int H, int W, int Hp,
@@ -576,15 +564,11 @@ static void launch_to_yuv(ssm_view in, void *frames_yuv, int N, int H, int W, in
     const int vec_out = (W % 4 == 0 && reinterpret_cast<size_t>(frames_yuv) % (4 * sizeof(S)) == 0) ? 1 : 0;
     const dim3 grid(((W + 3) / 4 + 63) / 64, ((H + 1) / 2 + 3) / 4, N);
     S *dst = static_cast<S *>(frames_yuv);
-    if (layout == SSM_YUV_444)
-        SSM_LAUNCH(frames_to_yuv_kernel<S, LAY_444>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, dst, H, W, top, left, fs,
-                   row_of(table, matrix, range), norm_of(mean3, std3), 0, vec_in, vec_out);
-    else if (layout == SSM_YUV_422)
-        SSM_LAUNCH(frames_to_yuv_kernel<S, LAY_422>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, dst, H, W, top, left, fs,
-                   row_of(table, matrix, range), norm_of(mean3, std3), 1, vec_in, vec_out);
-    else
-        SSM_LAUNCH(frames_to_yuv_kernel<S, LAY_420>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, dst, H, W, top, left, fs,
-                   row_of(table, matrix, range), norm_of(mean3, std3), layout == SSM_YUV_420_COSITED ? 1 : 0, vec_in, vec_out);
+    const int cosited = (layout == SSM_YUV_420_COSITED || layout == SSM_YUV_422) ? 1 : 0;          // (the 4:2:2 and 4:4:4 kernels do not read it)
+    with_layout(layout, [&](auto lay) {
+        SSM_LAUNCH(frames_to_yuv_kernel<S, lay()>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, dst, H, W, top, left, fs,
+                   row_of(table, matrix, range), norm_of(mean3, std3), cosited, vec_in, vec_out);
+    });
 }
 
 static int frames_to_yuv(const char *name, const char *entry, bool extended, ssm_view in, void *frames_yuv, int N, int H, int W, int top, int left,
@@ -628,58 +612,63 @@ extern "C" int ssm_frames_to_yuvx_fwd(ssm_view in, void *frames_yuv, int N, int 
                          layout, sample_bytes, stream);
 }
 
-extern "C" int ssm_frames_accumulate_fwd(ssm_view src, ssm_view acc, int N, int C, int H, int W, int init, float scale, void *stream) {
-    SSM_REQUIRE(src.ptr && acc.ptr, "frames_accumulate: null pointer");
-    SSM_REQUIRE(N > 0 && N <= 65535 && C > 0 && C <= 65535 && H > 0 && W > 0 && (H + 3) / 4 <= 65535,
-                "frames_accumulate: bad sizes N=%d C=%d H=%d W=%d", N, C, H, W);
-    SSM_REQUIRE(src.sh >= W && acc.sh >= W, "frames_accumulate: row strides %d (src), %d (acc) shorter than W=%d", src.sh, acc.sh, W);
-    SSM_REQUIRE(init == 0 || init == 1, "frames_accumulate: init must be 0 or 1 (got %d)", init);
-    SSM_REQUIRE(std::isfinite(scale), "frames_accumulate: scale must be finite (got %g)", (double)scale);
+// What the light entry point is given beside the coded one's arguments.
+struct LightIn {
+    const float *mean3, *std3, *curve;
+    int encode;
+};
+
+// The checks and the launch of the two accumulate entry points, in one order; `light` null: the coded sum over C channels.
+static int frames_accumulate(const char *name, const char *entry, ssm_view src, ssm_view acc, int N, int C, int H, int W, int init, float scale,
+                             const LightIn *light, void *stream) {
+    SSM_REQUIRE(src.ptr && acc.ptr && (!light || (light->mean3 && light->std3 && light->curve)), "%s: null pointer", name);
+    const bool sizes = N > 0 && N <= 65535 && C > 0 && C <= 65535 && H > 0 && W > 0 && (H + 3) / 4 <= 65535;
+    if (light)
+        SSM_REQUIRE(sizes, "%s: bad sizes N=%d H=%d W=%d", name, N, H, W);
+    else
+        SSM_REQUIRE(sizes, "%s: bad sizes N=%d C=%d H=%d W=%d", name, N, C, H, W);
+    SSM_REQUIRE(src.sh >= W && acc.sh >= W, "%s: row strides %d (src), %d (acc) shorter than W=%d", name, src.sh, acc.sh, W);
+    SSM_REQUIRE(init == 0 || init == 1, "%s: init must be 0 or 1 (got %d)", name, init);
+    if (light) SSM_REQUIRE(light->encode == 0 || light->encode == 1, "%s: encode must be 0 or 1 (got %d)", name, light->encode);
+    SSM_REQUIRE(std::isfinite(scale), "%s: scale must be finite (got %g)", name, (double)scale);
+    Curve<true> cv;
+    if (light) {
+        const float *mean3 = light->mean3, *std3 = light->std3, *curve = light->curve;
+        for (int c = 0; c < 3; ++c)
+            SSM_REQUIRE(std::isfinite(mean3[c]) && std::isfinite(std3[c]) && std3[c] > 0.0f,
+                        "%s: mean %g / std %g of channel %d: need finite values and a std above 0", name, (double)mean3[c], (double)std3[c], c);
+        cv.nm = norm_of(mean3, std3), cv.encode = light->encode;
+        for (int i = 0; i < SSM_LIGHT_ROW; ++i) reinterpret_cast<float *>(&cv.row)[i] = curve[i];
+        bool finite = true;
+        for (int i = 0; i < SSM_LIGHT_ROW; ++i) finite = finite && std::isfinite(curve[i]);
+        const LightRow &k = cv.row;
+        SSM_REQUIRE(finite && k.g > 0.0f && k.ig > 0.0f && k.slope > 0.0f && k.islope > 0.0f,
+                    "%s: curve row with g=%g (1/g=%g), slope=%g (1/slope=%g): need finite constants, g > 0 and slope > 0", name, (double)k.g,
+                    (double)k.ig, (double)k.slope, (double)k.islope);
+    }
     long long s0, s1, a0, a1;
     view_range(src, N, C, H, W, &s0, &s1);
     view_range(acc, 1, C, H, W, &a0, &a1);
-    SSM_REQUIRE(s1 <= a0 || a1 <= s0, "frames_accumulate: src and acc overlap (%lld bytes apart)", a0 - s0);
+    SSM_REQUIRE(s1 <= a0 || a1 <= s0, "%s: src and acc overlap (%lld bytes apart)", name, a0 - s0);
     const bool vec = W % 4 == 0 && view_aligned(src, 4) && view_aligned(acc, 4);
-    if (vec)
-        SSM_LAUNCH(frames_accumulate_kernel<4>, dim3((W / 4 + 63) / 64, (H + 3) / 4, C), dim3(64, 4), 0, (hipStream_t)stream, src, acc, N, H, W,
-                   init, scale);
-    else
-        SSM_LAUNCH(frames_accumulate_kernel<1>, dim3((W + 63) / 64, (H + 3) / 4, C), dim3(64, 4), 0, (hipStream_t)stream, src, acc, N, H, W, init,
-                   scale);
-    return ssm::check_launch("ssm_frames_accumulate_fwd");
+    const dim3 grid(((vec ? W / 4 : W) + 63) / 64, (H + 3) / 4, C);
+    const auto go = [&](auto mode) {          // Curve<Light>
+        constexpr bool Light = std::is_same_v<decltype(mode), Curve<true>>;
+        SSM_LAUNCH(vec ? frames_accumulate_kernel<4, Light> : frames_accumulate_kernel<1, Light>, grid, dim3(64, 4), 0, (hipStream_t)stream, src,
+                   acc, N, H, W, init, scale, mode);
+    };
+    light ? go(cv) : go(Curve<false>{});
+    return ssm::check_launch(entry);
+}
+
+extern "C" int ssm_frames_accumulate_fwd(ssm_view src, ssm_view acc, int N, int C, int H, int W, int init, float scale, void *stream) {
+    return frames_accumulate("frames_accumulate", "ssm_frames_accumulate_fwd", src, acc, N, C, H, W, init, scale, nullptr, stream);
 }
 
 extern "C" int ssm_frames_accumulate_light_fwd(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale, const float *mean3,
                                                const float *std3, const float *curve, int encode, void *stream) {
-    SSM_REQUIRE(src.ptr && acc.ptr && mean3 && std3 && curve, "frames_accumulate_light: null pointer");
-    SSM_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && (H + 3) / 4 <= 65535, "frames_accumulate_light: bad sizes N=%d H=%d W=%d", N, H, W);
-    SSM_REQUIRE(src.sh >= W && acc.sh >= W, "frames_accumulate_light: row strides %d (src), %d (acc) shorter than W=%d", src.sh, acc.sh, W);
-    SSM_REQUIRE(init == 0 || init == 1, "frames_accumulate_light: init must be 0 or 1 (got %d)", init);
-    SSM_REQUIRE(encode == 0 || encode == 1, "frames_accumulate_light: encode must be 0 or 1 (got %d)", encode);
-    SSM_REQUIRE(std::isfinite(scale), "frames_accumulate_light: scale must be finite (got %g)", (double)scale);
-    for (int c = 0; c < 3; ++c)
-        SSM_REQUIRE(std::isfinite(mean3[c]) && std::isfinite(std3[c]) && std3[c] > 0.0f,
-                    "frames_accumulate_light: mean %g / std %g of channel %d: need finite values and a std above 0", (double)mean3[c],
-                    (double)std3[c], c);
-    LightRow k;
-    for (int i = 0; i < SSM_LIGHT_ROW; ++i) reinterpret_cast<float *>(&k)[i] = curve[i];
-    bool finite = true;
-    for (int i = 0; i < SSM_LIGHT_ROW; ++i) finite = finite && std::isfinite(curve[i]);
-    SSM_REQUIRE(finite && k.g > 0.0f && k.ig > 0.0f && k.slope > 0.0f && k.islope > 0.0f,
-                "frames_accumulate_light: curve row with g=%g (1/g=%g), slope=%g (1/slope=%g): need finite constants, g > 0 and slope > 0",
-                (double)k.g, (double)k.ig, (double)k.slope, (double)k.islope);
-    long long s0, s1, a0, a1;
-    view_range(src, N, 3, H, W, &s0, &s1);
-    view_range(acc, 1, 3, H, W, &a0, &a1);
-    SSM_REQUIRE(s1 <= a0 || a1 <= s0, "frames_accumulate_light: src and acc overlap (%lld bytes apart)", a0 - s0);
-    const bool vec = W % 4 == 0 && view_aligned(src, 4) && view_aligned(acc, 4);
-    if (vec)
-        SSM_LAUNCH(frames_accumulate_light_kernel<4>, dim3((W / 4 + 63) / 64, (H + 3) / 4, 3), dim3(64, 4), 0, (hipStream_t)stream, src, acc, N, H,
-                   W, init, scale, norm_of(mean3, std3), k, encode);
-    else
-        SSM_LAUNCH(frames_accumulate_light_kernel<1>, dim3((W + 63) / 64, (H + 3) / 4, 3), dim3(64, 4), 0, (hipStream_t)stream, src, acc, N, H, W,
-                   init, scale, norm_of(mean3, std3), k, encode);
-    return ssm::check_launch("ssm_frames_accumulate_light_fwd");
+    const LightIn light = {mean3, std3, curve, encode};
+    return frames_accumulate("frames_accumulate_light", "ssm_frames_accumulate_light_fwd", src, acc, N, 3, H, W, init, scale, &light, stream);
 }
 
 extern "C" int ssm_luma_sad_fwd(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b, int N, int H, int W,

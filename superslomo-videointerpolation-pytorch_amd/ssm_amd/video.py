@@ -11,17 +11,17 @@
   frames_to_yuv           convention (scripts/visualize_interpolation.py:61-88,223-268)
   VideoInterpolator       the streamed loop: every leg of a pass (H2D, ingest, the pair pipeline, egress, D2H) is queued on the pass's HIP
                           stream, a writer thread drains a ring of pinned buffers in order; memory does not depend on the clip's length
-  PassRing / read_passes  what its three modes (fixed grid, timeline, shutter) share beside the prologue: the ring with its writer thread and
-  / upload_times          failure protocol (no GPU in it), the planners' read loop, the fill and upload of a pass's times
+  PassRing / read_passes  what its three modes (fixed grid, timeline, shutter) share beside the prologue, the Clip with its two conversions and
+  / upload_times          their buffers: the ring with its writer thread and failure protocol (no GPU in it), the planners' read loop, a pass's times
 
   Timeline / PassPlanner  any output rate and speed: where each output frame sits on the input's clock, exactly (Fractions, closed form),
                           and the bookkeeping of the passes that follow it - VideoInterpolator(target_rate=, speed=)
   accumulate_host /       the shutter: an output frame as the mean of `samples` sub-frames over the open part of its interval
   ShutterPlanner          (Timeline(step, shutter=, samples=)), summed on the GPU in time order by ssm_frames_accumulate_fwd, whose numpy
                           yardstick accumulate_host is; the bookkeeping of its passes - VideoInterpolator(shutter=, shutter_samples=)
-  light_curve /           the shutter in linear light: the sub-frames decoded to light by one of LIGHT_CURVES before they are summed, the
-  accumulate_light_host   mean encoded again (ssm_frames_accumulate_light_fwd, held to an error bound against this float64 yardstick) -
-                          VideoInterpolator(shutter_light=); "coded", the default, is the mean of the coded values
+  light_curve /           the shutter in linear light: the same kernel's second mode (ssm_frames_accumulate_light_fwd, held to an error bound
+  accumulate_light_host   against this float64 yardstick), the sub-frames decoded to light by one of LIGHT_CURVES before they are summed, the
+                          mean encoded again - VideoInterpolator(shutter_light=); "coded", the default, is the mean of the coded values
   luma_sad_host / luma_sad   scene cuts: per frame pair the exact sum of |difference| of the 8-bit Y planes, by numpy (the yardstick) and by
   / SceneCuts             ssm_luma_sad_fwd on the payloads as they stand on the device; the decision from those sums in Fractions, with no
                           GPU in it - VideoInterpolator(scene_cut=): at a cut the output repeats the nearer input frame instead of a morph
@@ -38,7 +38,6 @@ the box, a light curve chosen from the clip's tags, HDR transfer curves (PQ, HLG
 variable-rate input, speeds that change within a clip; a default scene-cut threshold, fades and dissolves, cuts judged on chroma,
 skipping the GPU work of a cut pair, scene cuts together with a shutter.
 """
-import collections
 import ctypes
 import functools
 import queue
@@ -357,6 +356,29 @@ def luma_sad_host(ya, yb):
 
 
 # ---- the kernels -------------------------------------------------------------------------------------------------------------------
+class Clip:
+    """A clip's format and what its two conversions need, worked out once per run: fb = frame_bytes, the canvas (hp, wp) = padded_dims(h, w,
+    mult) unless `canvas` gives one, the centred offsets, mean, std and the bit depth's table as the C arrays the entry points take; dev: the
+    run's device.  ingest() and egress() queue the kernel on the current stream and assert nothing of their tensors: the caller's to keep."""
+
+    def __init__(self, h, w, siting, matrix, crange, cfg=None, bits=8, mult=32, canvas=None, dev=None):
+        self.h, self.w, self.fb, self.dev = h, w, frame_bytes(h, w, siting, bits), dev
+        self.hp, self.wp = padded_dims(h, w, mult)[0] if canvas is None else canvas
+        self.at = ((self.hp - h) // 2, (self.wp - w) // 2)          # top, left
+        self.norm = tuple(_f3(v) for v in cfg_mean_std(cfg))          # mean, std
+        self.coding = (_table_ptr(bits), matrix, crange, siting, sample_bytes(bits))          # the tail of both argument lists
+
+    def ingest(self, payload, out, pad_before_norm=True):
+        hb.check(hb.load().ssm_frames_from_yuvx_fwd(payload.data_ptr(), hb.view_of(out), payload.shape[0], self.h, self.w, self.hp, self.wp,
+                                                    *self.at, *self.norm, 1 if pad_before_norm else 0, *self.coding, hb.stream_ptr()))
+        return out
+
+    def egress(self, x, out):
+        hb.check(hb.load().ssm_frames_to_yuvx_fwd(hb.view_of(x), out.data_ptr(), x.shape[0], self.h, self.w, *self.at, *self.norm, *self.coding,
+                                                  hb.stream_ptr()))
+        return out
+
+
 def frames_from_yuv(payload, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, cfg=None, pad_before_norm=True, out=None, multiple=32,
                     *, bits=8):
     """[N, frame_bytes] uint8 device tensor of Y4M payloads -> [N,3,Hp,Wp] normalised fp32 (into `out` if given); (Hp, Wp) =
@@ -364,31 +386,22 @@ def frames_from_yuv(payload, h, w, siting=CENTRED, matrix=BT709, color_range=LIM
     little-endian samples (a payload that does not start on an even address is refused)."""
     assert payload.is_cuda and payload.dtype == torch.uint8 and payload.dim() == 2 and payload.is_contiguous() and \
         payload.shape[1] == frame_bytes(h, w, siting, bits), "payloads must be a contiguous [N, frame_bytes] uint8 tensor on the GPU"
-    n = payload.shape[0]
-    (hp, wp), (top, left) = padded_dims(h, w, multiple)
-    mean, std = cfg_mean_std(cfg)
+    clip = Clip(h, w, siting, matrix, color_range, cfg, bits, multiple)
     if out is None:
-        out = torch.empty(n, 3, hp, wp, dtype=torch.float32, device=payload.device)
-    assert tuple(out.shape) == (n, 3, hp, wp)
-    hb.check(hb.load().ssm_frames_from_yuvx_fwd(payload.data_ptr(), hb.view_of(out), n, h, w, hp, wp, top, left, _f3(mean), _f3(std),
-                                                1 if pad_before_norm else 0, _table_ptr(bits), matrix, color_range, siting,
-                                                sample_bytes(bits), hb.stream_ptr()))
-    return out
+        out = torch.empty(payload.shape[0], 3, clip.hp, clip.wp, dtype=torch.float32, device=payload.device)
+    assert tuple(out.shape) == (payload.shape[0], 3, clip.hp, clip.wp)
+    return clip.ingest(payload, out, pad_before_norm)
 
 
 def frames_to_yuv(x, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, cfg=None, out=None, *, bits=8):
     """[N,3,Hp,Wp] normalised fp32 (finite) -> [N, frame_bytes] uint8 payloads (bits > 8: of 16-bit little-endian samples), the centred
     padding cropped away."""
     hb.require_device(x, "frame tensor")
-    n, _, hp, wp = x.shape
-    top, left = (hp - h) // 2, (wp - w) // 2
-    mean, std = cfg_mean_std(cfg)
+    clip = Clip(h, w, siting, matrix, color_range, cfg, bits, canvas=x.shape[2:])
     if out is None:
-        out = torch.empty(n, frame_bytes(h, w, siting, bits), dtype=torch.uint8, device=x.device)
-    assert out.is_contiguous() and tuple(out.shape) == (n, frame_bytes(h, w, siting, bits)) and out.dtype == torch.uint8
-    hb.check(hb.load().ssm_frames_to_yuvx_fwd(hb.view_of(x), out.data_ptr(), n, h, w, top, left, _f3(mean), _f3(std), _table_ptr(bits),
-                                              matrix, color_range, siting, sample_bytes(bits), hb.stream_ptr()))
-    return out
+        out = torch.empty(x.shape[0], clip.fb, dtype=torch.uint8, device=x.device)
+    assert out.is_contiguous() and tuple(out.shape) == (x.shape[0], clip.fb) and out.dtype == torch.uint8
+    return clip.egress(x, out)
 
 
 def luma_sad(payload_a, payload_b, h, w, out=None):
@@ -1073,9 +1086,20 @@ def upload_times(times, slots, np_t, host_t, dev_t):
     dev_t.copy_(host_t, non_blocking=True)
 
 
-# What run() works out of a reader / writer pair before it looks at the mode: frame size, chroma siting, frame_bytes, matrix, code range,
-# the device, the canvas's multiple, the canvas and the samples' significant bits.
-Clip = collections.namedtuple("Clip", "h w siting fb matrix crange dev mult hp wp bits")
+def ring_slots(depth, fb, rows_in, rows_out, n_t=None):
+    """What a mode's `depth` ring slots hold, a list each: pinned host_in [rows_in, fb], host_out [rows_out, fb] and host_t (n_t times, 0.5
+    throughout so that entries no pass fills stay finite; None where the mode has no times), their numpy views, the `done` events."""
+    host_in, host_out = ([torch.empty(rows, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)] for rows in (rows_in, rows_out))
+    host_t = None if n_t is None else [torch.full((n_t,), 0.5, dtype=torch.float32).pin_memory() for _ in range(depth)]
+    np_in, np_out, np_t = (None if b is None else [t.numpy() for t in b] for b in (host_in, host_out, host_t))
+    return host_in, host_out, host_t, np_in, np_out, np_t, [torch.cuda.Event() for _ in range(depth)]
+
+
+def stream_buffers(n, dev, fb, rows_in, rows_out, n_t=None):
+    """What a mode's n streams hold on the device, a list each: dev_in, dev_out, dev_t (as in ring_slots; not initialised), `ingested`."""
+    dev_in, dev_out = ([torch.empty(rows, fb, dtype=torch.uint8, device=dev) for _ in range(n)] for rows in (rows_in, rows_out))
+    dev_t = None if n_t is None else [torch.empty(n_t, dtype=torch.float32, device=dev) for _ in range(n)]
+    return dev_in, dev_out, dev_t, [torch.cuda.Event() for _ in range(n)]
 
 
 class VideoInterpolator:
@@ -1088,10 +1112,10 @@ class VideoInterpolator:
     writer thread waits for a slot's event and writes, per pair, the interpolated frames and then the right frame's own input bytes.
     Host and device memory are fixed by the frame size, n_streams and pairs_per_batch.
 
-    The three modes (_run_fixed, _run_timeline, _run_shutter) share what is not on a stream: the prologue (_clip), the ring with its
-    writer thread and failure protocol (PassRing), the planners' read loop (read_passes) and the fill of a pass's times (upload_times).
-    Each keeps its own buffers and its own submit: what is queued on a pass's stream, call for call, is what its bytes and its measured
-    rate rest on."""
+    The three modes (_run_fixed, _run_timeline, _run_shutter) share what is not on a stream: the prologue (_clip) and the Clip's two
+    conversions, the allocation of what a ring slot and a stream hold (ring_slots, stream_buffers), the ring with its writer thread and
+    failure protocol (PassRing), the planners' read loop and issue of passes (read_passes, _run_passes), the fill of a pass's times
+    (upload_times).  Each keeps its own submit: what is queued on a pass's stream, call for call, is what its bytes and its rate rest on."""
 
     def __init__(self, model, cfg, upsample_rate=8, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
                  tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8, scene_cut=None,
@@ -1184,7 +1208,7 @@ class VideoInterpolator:
 
     def _clip(self, reader, writer):
         """The Clip of a run, or the refusal of a writer of another format or of a model that is not on the GPU."""
-        h, w, siting, fb, bits = reader.height, reader.width, reader.siting, reader.frame_bytes, getattr(reader, "bits", 8)
+        h, w, siting, bits = reader.height, reader.width, reader.siting, getattr(reader, "bits", 8)
         if (writer.height, writer.width, writer.siting, getattr(writer, "bits", 8)) != (h, w, siting, bits):
             raise ValueError("reader and writer disagree on the frame format")
         if self.scene_cut is not None and bits > 8:
@@ -1195,14 +1219,17 @@ class VideoInterpolator:
         dev = next(self.model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
-        return Clip(h, w, siting, fb, matrix, crange, dev, 32 * self.flow_scale, *self.canvas(h, w), bits)
+        return Clip(h, w, siting, matrix, crange, self.cfg, bits, 32 * self.flow_scale, dev=dev)
 
-    def _cut_state(self, n, depth, pairs, clip):
+    def _cut_state(self, on, n, depth, pairs, clip):
         """What the scene cuts add to a mode's buffers: SceneCuts, the sums of a pass on the device (per stream) and in the pinned ring slot
-        (per slot, with its numpy view as uint64), and the writer thread's copy of the input frame before the next pass's first pair."""
+        (per slot, with its numpy view as uint64), the writer thread's copy of the input frame before the next pass's first pair; and `lead` =
+        1, the rows they put in front of a stream's payloads.  Not `on`: None for each, and 0."""
+        if not on:
+            return (None,) * 5, 0
         host = [torch.empty(pairs, dtype=torch.int64).pin_memory() for _ in range(depth)]
         return (SceneCuts(self.scene_cut), [torch.empty(pairs, dtype=torch.int64, device=clip.dev) for _ in range(n)], host,
-                [t.numpy().view(np.uint64) for t in host], np.empty(clip.fb, np.uint8))
+                [t.numpy().view(np.uint64) for t in host], np.empty(clip.fb, np.uint8)), 1
 
     def _cut_rows(self, cuts, pixels, sums, pairs, order, carried):
         """The rows of a pass under scene cuts: a generator that PassRing calls on the writer thread once the pass's event has come.
@@ -1234,6 +1261,25 @@ class VideoInterpolator:
             return self._run_fixed(clip, reader, writer)
         return self._run_shutter(clip, reader, writer) if self.samples > 1 else self._run_timeline(clip, reader, writer)
 
+    def _run_passes(self, clip, reader, writer, plan, np_in, done, has_work, submit, rows_of):
+        """The loop of the planner-driven modes, over what the planner closes: has_work(*closed) - the pass has GPU work; submit(j, r, *closed)
+        queues it as pass j on ring slot r; rows_of(r, on_gpu, *closed) -> (the rows to write as PassRing.hand takes them, their number)."""
+        written = j = 0          # frames written, passes issued
+
+        def issue(r, *closed):
+            nonlocal written, j
+            on_gpu = has_work(*closed) and not ring.failure
+            if on_gpu:
+                submit(j, r, *closed)
+                j += 1
+            rows, count = rows_of(r, on_gpu, *closed)
+            ring.hand(r, done[r] if on_gpu else None, rows)
+            written += count
+
+        with PassRing(len(done), writer, lambda: torch.cuda.synchronize(clip.dev)) as ring:
+            read_passes(reader, ring, plan, np_in, issue)
+        return written
+
     def _run_fixed(self, clip, reader, writer):
         """run() on the fixed grid of upsample_rate: planes[k] is [carried left frame | pairs_per_batch new frames], the pairs an
         overlapping view of it; the times go up once per run.  Frame 0 is written from a pinned buffer of its own before any pass.
@@ -1244,22 +1290,15 @@ class VideoInterpolator:
         records `ingested`: the pass that reads it waits for that event, and the pass that read the row before has recorded its own
         event (after its call) earlier in the chain of waits.  The sums go back to the pass's ring slot ahead of `done`."""
         from .evaluation import t_values
-        h, w, siting, fb, matrix, crange, dev, mult, hp, wp, bits = clip
+        fb, dev, hp, wp, luma = clip.fb, clip.dev, clip.hp, clip.wp, clip.h * clip.w
         pipe = self._pipeline(hp, wp, dev)
         n, pb, nt = pipe.n, self.pb, self.rate - 1
         depth = n + 2                                                  # ring slots: one per pass in flight, one being read, one being written
         t_dev = torch.tensor(t_values(self.rate), dtype=torch.float32, device=dev)
-        host_in = [torch.empty(pb, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
-        host_out = [torch.empty(pb * nt, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
-        np_in, np_out = [t.numpy() for t in host_in], [t.numpy() for t in host_out]
-        done = [torch.cuda.Event() for _ in range(depth)]
-        cuts, lead = None, 0
-        if self.scene_cut is not None:
-            (cuts, dev_sums, host_sums, np_sums, carried), lead = self._cut_state(n, depth, pb, clip), 1
-        dev_in = [torch.empty(lead + pb, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
-        dev_out = [torch.empty(pb * nt, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
+        host_in, host_out, _, np_in, np_out, _, done = ring_slots(depth, fb, pb, pb * nt)
+        (cuts, dev_sums, host_sums, np_sums, carried), lead = self._cut_state(self.scene_cut is not None, n, depth, pb, clip)
+        dev_in, dev_out, _, ingested = stream_buffers(n, dev, fb, lead + pb, pb * nt)
         planes = [torch.empty(pb + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [carried left frame | new frames]
-        ingested = [torch.cuda.Event() for _ in range(n)]
         first = torch.empty(1, fb, dtype=torch.uint8).pin_memory()
         if not reader.read_frame_into(first.numpy()[0]):
             raise Y4MError("the Y4M stream holds no frame")
@@ -1274,9 +1313,9 @@ class VideoInterpolator:
             with torch.cuda.stream(pipe.streams[last]):
                 new = dev_in[last][lead:]
                 new[:1].copy_(first, non_blocking=True)
-                frames_from_yuv(new[:1], h, w, siting, matrix, crange, self.cfg, True, out=planes[last][pb:], multiple=mult, bits=bits)
+                clip.ingest(new[:1], planes[last][pb:])
                 if cuts is not None:
-                    dev_in[0][0, :h * w].copy_(new[0, :h * w])
+                    dev_in[0][0, :luma].copy_(new[0, :luma])
                 ingested[last].record()
             j, eof = 0, False
             while not eof and not ring.failure:
@@ -1297,15 +1336,15 @@ class VideoInterpolator:
                     new.copy_(host_in[r], non_blocking=True)
                     st.wait_event(ingested[kprev])
                     planes[k][0].copy_(planes[kprev][pb])
-                    frames_from_yuv(new, h, w, siting, matrix, crange, self.cfg, True, out=planes[k][1:], multiple=mult, bits=bits)
+                    clip.ingest(new, planes[k][1:])
                     if cuts is not None:
-                        luma_sad(dev_in[k][:pb], dev_in[k][1:], h, w, out=dev_sums[k])
-                        dev_in[(j + 1) % n][0, :h * w].copy_(dev_in[k][pb, :h * w])
+                        luma_sad(dev_in[k][:pb], dev_in[k][1:], clip.h, clip.w, out=dev_sums[k])
+                        dev_in[(j + 1) % n][0, :luma].copy_(dev_in[k][pb, :luma])
                     ingested[k].record()
                     x = planes[k]
                     img6 = x.view(1, 6, hp, wp) if pb == 1 else x.as_strided((pb, 6, hp, wp), (3 * hp * wp, hp * wp, wp, 1))
                     frames = pipe.engines[k].run(img6, t_dev, False)
-                    frames_to_yuv(frames, h, w, siting, matrix, crange, self.cfg, out=dev_out[k], bits=bits)
+                    clip.egress(frames, dev_out[k])
                     host_out[r].copy_(dev_out[k], non_blocking=True)
                     if cuts is not None:
                         host_sums[r].copy_(dev_sums[k], non_blocking=True)
@@ -1314,7 +1353,7 @@ class VideoInterpolator:
                 if cuts is not None:
                     i0 = (written - 1) // self.rate
                     at = [None if kind == "orig" else (row // nt, Fraction(row % nt + 1, self.rate)) for kind, row in pass_order(valid, nt)]
-                    rows = functools.partial(self._cut_rows, cuts, h * w, np_sums[r],
+                    rows = functools.partial(self._cut_rows, cuts, luma, np_sums[r],
                                              [(i0 + p, np_in[r][p - 1] if p else None, np_in[r][p]) for p in range(valid)],
                                              list(zip(rows, at)), carried)
                 ring.hand(r, done[r], rows)
@@ -1341,30 +1380,21 @@ class VideoInterpolator:
         its own uploaded row, the right row of the pair before it, or row 0.  The rows of the pairs that run step evenly unless the
         timeline skips pairs inside a pass (sad_runs): one ssm_luma_sad_fwd call then, one per run otherwise.  Only pairs that run are
         summed and fed to SceneCuts."""
-        h, w, siting, fb, matrix, crange, dev, mult, hp, wp, bits = clip
+        fb, dev, hp, wp, luma = clip.fb, clip.dev, clip.hp, clip.wp, clip.h * clip.w
         tl = self.timeline(reader.rate)
         S, pb, n = tl.slots, self.pb, self.n_streams
         pipe = self._pipeline(hp, wp, dev, S) if S else None          # an integer step only picks input frames: nothing to run
         depth, cap = n + 2, 2 * pb + 2
-        host_in = [torch.empty(cap, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
-        host_out = [torch.empty(pb * max(S, 1), fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
-        host_t = [torch.full((pb * max(S, 1),), 0.5, dtype=torch.float32).pin_memory() for _ in range(depth)]
-        np_in, np_out, np_t = [t.numpy() for t in host_in], [t.numpy() for t in host_out], [t.numpy() for t in host_t]
-        done = [torch.cuda.Event() for _ in range(depth)]
-        cuts, lead = None, 0
-        if self.scene_cut is not None and pipe is not None:
-            (cuts, dev_sums, host_sums, np_sums, carried), lead = self._cut_state(n, depth, pb, clip), 1
+        host_in, host_out, host_t, np_in, np_out, np_t, done = ring_slots(depth, fb, cap, pb * max(S, 1), pb * max(S, 1))
+        (cuts, dev_sums, host_sums, np_sums, carried), lead = self._cut_state(self.scene_cut is not None and pipe is not None, n, depth, pb, clip)
         plan = PassPlanner(tl, pb, cap)
         if pipe is not None:
-            dev_in = [torch.empty(lead + cap, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
-            dev_out = [torch.empty(pb * S, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
-            dev_t = [torch.empty(pb * S, dtype=torch.float32, device=dev) for _ in range(n)]
+            dev_in, dev_out, dev_t, ingested = stream_buffers(n, dev, fb, lead + cap, pb * S, pb * S)
             planes = [torch.zeros(pb, 2, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [pair][left | right]
-            ingested = [torch.cuda.Event() for _ in range(n)]
         torch.cuda.synchronize(dev)
         last_p = [0]          # place, in its pass, of the pair whose right frame the next pair may carry over
 
-        def submit(j, r, pairs):
+        def submit(j, r, order, pairs):
             """Pass j: `pairs` = [(first row of the pair's new payloads, the left frame is among them, its times)] of ring slot r."""
             k = j % n
             st = pipe.streams[k]
@@ -1377,17 +1407,16 @@ class VideoInterpolator:
                     new[row:row + rows].copy_(host_in[r][row:row + rows], non_blocking=True)
                     if not own_left:
                         planes[k][p, 0].copy_(planes[k][p - 1, 1] if p else planes[(j - 1) % n][last_p[0], 1])
-                    frames_from_yuv(new[row:row + rows], h, w, siting, matrix, crange, self.cfg, True, out=planes[k][p, 2 - rows:],
-                                    multiple=mult, bits=bits)
+                    clip.ingest(new[row:row + rows], planes[k][p, 2 - rows:])
                 upload_times([ts for _, _, ts in pairs], S, np_t[r], host_t[r], dev_t[k])
                 if cuts is not None:
                     rights = [lead + row + (1 if own_left else 0) for row, own_left, _ in pairs]          # rows of dev_in[k]
                     lefts = [lead + row if own_left else (rights[p - 1] if p else 0) for p, (row, own_left, _) in enumerate(pairs)]
                     for p, m in sad_runs(lefts, rights):
                         da, db = (lefts[p + 1] - lefts[p], rights[p + 1] - rights[p]) if m > 1 else (1, 1)
-                        luma_sad(dev_in[k][lefts[p]:lefts[p] + (m - 1) * da + 1:da], dev_in[k][rights[p]:rights[p] + (m - 1) * db + 1:db], h, w,
-                                 out=dev_sums[k][p:p + m])
-                    dev_in[(j + 1) % n][0, :h * w].copy_(dev_in[k][rights[-1], :h * w])
+                        luma_sad(dev_in[k][lefts[p]:lefts[p] + (m - 1) * da + 1:da], dev_in[k][rights[p]:rights[p] + (m - 1) * db + 1:db], clip.h,
+                                 clip.w, out=dev_sums[k][p:p + m])
+                    dev_in[(j + 1) % n][0, :luma].copy_(dev_in[k][rights[-1], :luma])
                 ingested[k].record()
                 last_p[0] = len(pairs) - 1
                 frames = pipe.engines[k].run(planes[k].view(pb, 6, hp, wp), dev_t[k], False)
@@ -1396,20 +1425,13 @@ class VideoInterpolator:
                 else:
                     spans = [(p * S, len(ts)) for p, (_, _, ts) in enumerate(pairs)]
                 for o, m in spans:
-                    frames_to_yuv(frames[o:o + m], h, w, siting, matrix, crange, self.cfg, out=dev_out[k][o:o + m], bits=bits)
+                    clip.egress(frames[o:o + m], dev_out[k][o:o + m])
                     host_out[r][o:o + m].copy_(dev_out[k][o:o + m], non_blocking=True)
                 if cuts is not None:
                     host_sums[r].copy_(dev_sums[k], non_blocking=True)
                 done[r].record()
 
-        written = j = 0          # frames written, passes issued
-
-        def issue(r, order, pairs):
-            nonlocal written, j
-            on_gpu = bool(pairs) and not ring.failure
-            if on_gpu:
-                submit(j, r, pairs)
-                j += 1
+        def rows_of(r, on_gpu, order, pairs):
             rows = [np_out[r][row] if kind == "interp" else np_in[r][row] for kind, row in order]
             if cuts is not None and on_gpu:
                 exact = [tl.times(i) for i in plan.closed_index]          # the pairs' times as Fractions, beside the planner's fp32
@@ -1417,13 +1439,10 @@ class VideoInterpolator:
                 rights = [np_in[r][row + (1 if own_left else 0)] for row, own_left, _ in pairs]
                 host_pairs = [(i, np_in[r][row] if own_left else (rights[p - 1] if p else None), rights[p])
                               for p, (i, (row, own_left, _)) in enumerate(zip(plan.closed_index, pairs))]
-                rows = functools.partial(self._cut_rows, cuts, h * w, np_sums[r], host_pairs, list(zip(rows, at)), carried)
-            ring.hand(r, done[r] if on_gpu else None, rows)
-            written += len(order)
+                rows = functools.partial(self._cut_rows, cuts, luma, np_sums[r], host_pairs, list(zip(rows, at)), carried)
+            return rows, len(order)
 
-        with PassRing(depth, writer, lambda: torch.cuda.synchronize(dev)) as ring:
-            read_passes(reader, ring, plan, np_in, issue)
-        return written
+        return self._run_passes(clip, reader, writer, plan, np_in, done, lambda order, pairs: bool(pairs), submit, rows_of)
 
     def _run_shutter(self, clip, reader, writer):
         """run() with a shutter: output frame k is the mean of the S = shutter_samples sub-frames of Timeline(step, shutter=, samples=),
@@ -1440,7 +1459,7 @@ class VideoInterpolator:
         the pass before recorded after its last accumulate and egress, so the engines of neighbouring passes still overlap, only these
         short tails are serialised, and the result depends on nothing but the time order.  One output is open at a time (OPEN_OUTPUTS),
         which sizes the ring of accumulators.  Memory is fixed by the frame size, n_streams, pairs_per_batch, slots and that bound."""
-        h, w, siting, fb, matrix, crange, dev, mult, hp, wp, bits = clip
+        fb, dev, hp, wp = clip.fb, clip.dev, clip.hp, clip.wp
         tl = self.timeline(reader.rate)
         slots, pb, n = tl.slots, self.pb, self.n_streams
         pipe = self._pipeline(hp, wp, dev, slots) if slots else None          # a step whose samples are all input frames: nothing to synthesise
@@ -1448,25 +1467,17 @@ class VideoInterpolator:
         depth, cap = n + 2, 2 * pb + 2
         plan = ShutterPlanner(tl, pb, cap)
         scale = np.float32(1.0 / tl.samples)
-        light = None
-        if self.shutter_light != "coded":
-            mean, std = cfg_mean_std(self.cfg)
-            light = (_f3(mean), _f3(std), (ctypes.c_float * LIGHT_ROW)(*[float(x) for x in light_curve(self.shutter_light)]))
-        host_in = [torch.empty(cap, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
-        host_out = [torch.empty(plan.max_done, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
-        host_t = [torch.full((pb * max(slots, 1),), 0.5, dtype=torch.float32).pin_memory() for _ in range(depth)]
-        np_in, np_out, np_t = [t.numpy() for t in host_in], [t.numpy() for t in host_out], [t.numpy() for t in host_t]
-        done = [torch.cuda.Event() for _ in range(depth)]
-        dev_in = [torch.empty(cap, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
-        dev_out = [torch.empty(plan.max_done, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
-        dev_t = [torch.empty(pb * max(slots, 1), dtype=torch.float32, device=dev) for _ in range(n)]
+        light = None if self.shutter_light == "coded" else \
+            (*clip.norm, (ctypes.c_float * LIGHT_ROW)(*[float(x) for x in light_curve(self.shutter_light)]))
+        host_in, host_out, host_t, np_in, np_out, np_t, done = ring_slots(depth, fb, cap, plan.max_done, pb * max(slots, 1))
+        dev_in, dev_out, dev_t, ingested = stream_buffers(n, dev, fb, cap, plan.max_done, pb * max(slots, 1))
         planes = [torch.zeros(cap + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [carried frame | the pass's frames]
         sides = [torch.zeros(pb, 2, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]         # [pair][left | right]
         acc = torch.zeros(OPEN_OUTPUTS, 3, hp, wp, dtype=torch.float32, device=dev)
-        ingested, summed = [torch.cuda.Event() for _ in range(n)], [torch.cuda.Event() for _ in range(n)]
+        summed = [torch.cuda.Event() for _ in range(n)]
         torch.cuda.synchronize(dev)
 
-        def submit(j, r, rows, carry, pairs, calls):
+        def submit(j, r, rows, carry, pairs, calls, finished):
             """Pass j on ring slot r; the arguments are ShutterPlanner's."""
             k, kprev = j % n, (j - 1) % n
             st = streams[k]
@@ -1476,7 +1487,7 @@ class VideoInterpolator:
                 dev_in[k][:rows].copy_(host_in[r][:rows], non_blocking=True)
                 if carry is not None:
                     planes[k][0].copy_(planes[kprev][carry])
-                frames_from_yuv(dev_in[k][:rows], h, w, siting, matrix, crange, self.cfg, True, out=planes[k][1:1 + rows], multiple=mult, bits=bits)
+                clip.ingest(dev_in[k][:rows], planes[k][1:1 + rows])
                 for p, (left, right, _) in enumerate(pairs):
                     sides[k][p, 0].copy_(planes[k][left])
                     sides[k][p, 1].copy_(planes[k][right])
@@ -1495,24 +1506,12 @@ class VideoInterpolator:
                     else:
                         hb.frames_accumulate_light(x, a, 1 if init else 0, scale if last else 1.0, *light, 1 if last else 0)
                     if last:
-                        frames_to_yuv(a, h, w, siting, matrix, crange, self.cfg, out=dev_out[k][o:o + 1], bits=bits)
+                        clip.egress(a, dev_out[k][o:o + 1])
                         host_out[r][o:o + 1].copy_(dev_out[k][o:o + 1], non_blocking=True)
                         o += 1
                 summed[k].record()
                 done[r].record()
 
-        written = j = 0          # frames written, passes issued
-
-        def issue(r, rows, carry, pairs, calls, finished):
-            nonlocal written, j
-            on_gpu = rows > 0 and not ring.failure
-            if on_gpu:
-                submit(j, r, rows, carry, pairs, calls)
-                j += 1
-            # not on_gpu: with no rows the planner has recorded no call, so `finished` is empty; after a failure the thread writes nothing
-            ring.hand(r, done[r] if on_gpu else None, [np_out[r][o] for o in range(len(finished))])
-            written += len(finished)
-
-        with PassRing(depth, writer, lambda: torch.cuda.synchronize(dev)) as ring:
-            read_passes(reader, ring, plan, np_in, issue)
-        return written
+        # a pass without GPU work: with no rows the planner has recorded no call, so `finished` is empty; after a failure the thread writes nothing
+        return self._run_passes(clip, reader, writer, plan, np_in, done, lambda rows, *_: rows > 0, submit,
+                                lambda r, on_gpu, *closed: ([np_out[r][o] for o in range(len(closed[-1]))], len(closed[-1])))

@@ -22,29 +22,14 @@ from fractions import Fraction
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "superslomo-videointerpolation-pytorch_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "scripts")):
+for p in (ROOT, PKG, os.path.join(PKG, "scripts"), os.path.join(ROOT, "tools")):
     sys.path.insert(0, p)
+from bench_shutter import call_ms  # noqa: E402
+
 
 STEPS = (("kernel", 180), ("fps", 600))          # step, its time limit in seconds
 H, W = 720, 1280
 THRESHOLD = Fraction(1, 10)          # a value for the run, not a recommendation: the synthetic clip moves steadily and holds no cut
-
-
-def call_ms(fn, iters, windows):
-    import torch
-    for _ in range(5):
-        fn()
-    out = []
-    for _ in range(windows):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / iters)
-    return statistics.median(out)
 
 
 def bench_kernel(dev, iters, windows):

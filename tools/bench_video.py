@@ -25,8 +25,10 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "superslomo-videointerpolation-pytorch_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "scripts")):
+for p in (ROOT, PKG, os.path.join(PKG, "scripts"), os.path.join(ROOT, "tools")):
     sys.path.insert(0, p)
+from bench_shutter import call_ms  # noqa: E402
+
 import torch  # noqa: E402
 
 from models.superslomo_r import FullModel  # noqa: E402
@@ -37,22 +39,6 @@ from ssm_amd.weights import synthetic_frames_u8, synthetic_state_dict  # noqa: E
 
 COPY_CEILING_BYTES_PER_S = 6.29e12
 H, W, RATE = 720, 1280, 8
-
-
-def call_ms(fn, iters, windows):
-    for _ in range(5):
-        fn()
-    out = []
-    for _ in range(windows):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / iters)
-    return statistics.median(out)
 
 
 def kernel_record(ms, nbytes):

@@ -19,23 +19,10 @@ import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from bench_shutter import call_ms  # noqa: E402  (here, so that main() still puts --pkg in front of the path)
+
 H, W, RATE = 720, 1280, 8
-
-
-def call_ms(torch, fn, iters, windows):
-    for _ in range(5):
-        fn()
-    out = []
-    for _ in range(windows):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / iters)
-    return statistics.median(out)
 
 
 def main():
@@ -91,7 +78,7 @@ def main():
             for side in ("from", "to"):
                 half = sizes[side] // 2          # a copy reads and writes: half the bytes moved each way touch the call's bytes once
                 a, b = torch.empty(half, dtype=torch.uint8, device=dev), torch.empty(half, dtype=torch.uint8, device=dev)
-                ms, copy_ms = call_ms(torch, calls[side], args.iters, args.windows), call_ms(torch, lambda: b.copy_(a), args.iters, args.windows)
+                ms, copy_ms = call_ms(calls[side], args.iters, args.windows), call_ms(lambda: b.copy_(a), args.iters, args.windows)
                 rec[tag]["ssm_frames_%s_yuvx_fwd" % side] = {"ms": round(ms, 4), "one_touch_bytes": sizes[side], "copy_ms": round(copy_ms, 4),
                                                              "ratio_to_copy": round(ms / copy_ms, 2)}
                 del a, b
