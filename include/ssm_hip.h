@@ -372,8 +372,15 @@ int ssm_pack32_wino_tiles_batch(const ssm_pack32_job *jobs_device, int n_jobs, l
  * Filters are packed once with ssm_pack16_weights (scaled by a power of two `scale`;
  * pass wscale = 1/scale to the convolution).  Cin is padded to a multiple of 16.
  * Outputs: y_hl8 (ptr NULL = off) and/or y_f32 (ptr NULL = off), optional fused 2x2 mean
- * pool_hl8.                                                                               */
+ * pool_hl8.
+ * tests/test_hip_conv16_kinds.py runs every tile configuration in every operand mode on exact-integer and random data;
+ * tests/test_hip_hl8_layout.py holds the layout, gather and HL8 element-wise kernels to float64 references.               */
 int ssm_conv16_config(int k, int Cout, int W, int *BN, int *KYS);
+/* Which tile configuration ssm_conv2d_hl8_fwd (ups = 0) / ssm_conv2d_ups_hl8_fwd (ups = 1; k = 3, W = output width) launches for
+ * Cin = C1 + C2 input channels, with the packing dimensions the matching *_config call reports (flags: SSM_FLAG_Q8 selects the Q8
+ * ones).  kind (diagnostics, tests): ups = 0: 0 H7, 1 H5, 2 H3N32, 3 H3N32D, 4 H3N64, 5 H3N128, 6 H3N128S, 7 H3N32V, 8 H3N32W;
+ * ups = 1: 0 U3N32, 1 U3N64, 2 U3N128, 3 U3N128S.  Reads nothing but its arguments.                                            */
+int ssm_conv16_plan(int k, int Cin, int Cout, int W, int ups, int flags, int *kind, int *BN, int *KYS);
 size_t ssm_packed16_weight_halves(int Cout, int Cin_padded, int k, int BN);
 int ssm_pack16_weights(const float *w_oihw, const float *bias, void *w_packed, float *bias_packed, int Cout,
                        int Cin, int Cin_padded, int k, int BN, int KYS, float scale, void *stream);

@@ -1540,6 +1540,32 @@ extern "C" int ssm_conv16q_ups_config(int Cout, int W, int *BN, int *KYS) {
     return SSM_OK;
 }
 
+// What dispatch16 / dispatch16_ups launch for this problem (they evaluate the same pick16 call), with the packing dimensions of the
+// matching *_config entry point.  Reads nothing but its arguments.
+extern "C" int ssm_conv16_plan(int k, int Cin, int Cout, int W, int ups, int flags, int *kind, int *BN, int *KYS) {
+    SSM_REQUIRE(kind && BN && KYS && Cin > 0 && Cout > 0 && W > 0, "conv16_plan: bad arguments");
+    const bool q8 = (flags & SSM_FLAG_Q8) != 0;
+    if (!ups) {
+        const int rc = q8 ? ssm_conv16q_config(k, Cout, W, BN, KYS) : ssm_conv16_config(k, Cout, W, BN, KYS);
+        if (rc != SSM_OK) return rc;
+        *kind = pick16(k, Cout, W, Cin);
+        return SSM_OK;
+    }
+    if (k != 3) {
+        ssm::set_error("conv16_plan: the fused-upsample form is 3x3 only (got k = %d)", k);
+        return SSM_E_UNSUPPORTED;
+    }
+    const int rc = q8 ? ssm_conv16q_ups_config(Cout, W, BN, KYS) : ssm_conv16_ups_config(Cout, W, BN, KYS);
+    if (rc != SSM_OK) return rc;
+    switch (pick16(3, Cout, W, Cin)) {      // the cases of dispatch16_ups
+        case H3N64: *kind = 1; break;
+        case H3N128: *kind = 2; break;
+        case H3N128S: *kind = 3; break;
+        default: *kind = 0; break;
+    }
+    return SSM_OK;
+}
+
 extern "C" int ssm_conv2d_ups_hl8_fwd(ssm_hview a, int C1, ssm_hview b, int C2, const void *w_packed, const float *bias_packed,
                                       float wscale, ssm_hview y_hl8, ssm_view y_f32, int B, int H, int W, int Cout, float slope,
                                       int flags, void *stream) {

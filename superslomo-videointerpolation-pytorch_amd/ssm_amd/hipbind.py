@@ -117,6 +117,7 @@ SIGNATURES = {
     "ssm_wino_conv2d_ups_fwd": (_c_int, [SsmView, _c_int, SsmView, _c_int, _vp, _vp, SsmView, _c_int, _c_int, _c_int, _c_int,
                                          _c_float, _c_int, _vp]),
     "ssm_conv16_config": (_c_int, [_c_int, _c_int, _c_int, _ip, _ip]),
+    "ssm_conv16_plan": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _ip, _ip, _ip]),
     "ssm_packed16_weight_halves": (_sz, [_c_int, _c_int, _c_int, _c_int]),
     "ssm_pack16_weights": (_c_int, [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _vp]),
     "ssm_conv2d_hl8_fwd": (_c_int, [SsmHView, _c_int, SsmHView, _c_int, _vp, _vp, _c_float, SsmHView, SsmView, SsmHView,
@@ -1198,6 +1199,18 @@ class WgradWinoFinish:
 
     def run(self, scale=1.0):
         check(load().ssm_wgrad_wino_finish(self.table.data_ptr(), self.n, self.max_n, float(scale), stream_ptr()))
+
+
+CONV16_KINDS = ("H7", "H5", "H3N32", "H3N32D", "H3N64", "H3N128", "H3N128S", "H3N32V", "H3N32W")
+CONV16_UPS_KINDS = ("U3N32", "U3N64", "U3N128", "U3N128S")
+
+
+def conv16_plan(k, cin, cout, W, ups=False, q8=False, fast=False):
+    """(kind name, BN, KYS) of the tile configuration ssm_conv2d_hl8_fwd / ssm_conv2d_ups_hl8_fwd (ups: W = output width) launches
+    for cin = c1 + c2 (padded) input channels, with the packing dimensions of the matching *_config call."""
+    flags = (SSM_FLAG_FP16_FAST if fast else 0) | (SSM_FLAG_Q8 if q8 else 0)
+    kind, bn, kys = _plan(load().ssm_conv16_plan, k, cin, cout, W, 1 if ups else 0, flags)
+    return (CONV16_UPS_KINDS if ups else CONV16_KINDS)[kind], bn, kys
 
 
 def conv2d_hl8(x1, c1, x2, c2, pk, y_hl8, y_f32, pool, B, H, W, lrelu=True, slope=0.1, fast=False):

@@ -32,6 +32,8 @@ CASES = [
     (3, 256, 64, 1, 16, 64), (3, 64, 64, 2, 11, 70),
     (3, 64, 128, 1, 8, 64), (3, 128, 256, 1, 12, 128), (3, 512, 512, 1, 23, 40), (3, 1024, 256, 1, 8, 96),
 ]
+# the tile kind ssm_conv16_plan reports for each case, in the order of CASES (every kind in every mode: tests/test_hip_conv16_kinds.py)
+KINDS = dict(zip(CASES, ("H7", "H7", "H5", "H5", "H3N32D", "H3N32V", "H3N32", "H3N64", "H3N64", "H3N128", "H3N128", "H3N32W", "H3N128S")))
 
 
 @pytest.mark.parametrize("k,cin,cout,B,H,W", CASES)
@@ -39,6 +41,7 @@ CASES = [
 def test_conv16_vs_oracle(dev, k, cin, cout, B, H, W, fast):
     from oracle import ssm_oracle as O
     from ssm_amd import hipbind as hb
+    assert hb.conv16_plan(k, (cin + 15) // 16 * 16, cout, W, fast=fast)[0] == KINDS[(k, cin, cout, B, H, W)]
     g = torch.Generator().manual_seed(k * 1000 + cin + cout + H + W)
     x = torch.randn(B, cin, H, W, generator=g)
     w = torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5
@@ -84,12 +87,14 @@ def test_conv16_fused_pool_and_cat(dev):
 
 
 UPS_CASES = [
-    # c1, c2, cout, B, h (low), w (low)      -> every fused tile configuration, image borders, ragged tiles, 1 source
+    # c1, c2, cout, B, h (low), w (low)      -> image borders, ragged tiles, 1 source
     (32, 32, 32, 1, 8, 32), (64, 64, 32, 2, 12, 36), (128, 0, 32, 1, 4, 32),
     (128, 128, 64, 1, 8, 32), (64, 64, 64, 2, 5, 40),
     (256, 256, 128, 1, 6, 64), (64, 64, 128, 1, 10, 32),
     (512, 512, 256, 1, 6, 16), (128, 128, 512, 2, 3, 8), (16, 16, 128, 1, 2, 2),
 ]
+# the fused tile kind of each case, in the order of UPS_CASES (U3N128S: tests/test_hip_conv16_kinds.py)
+UPS_KINDS = dict(zip(UPS_CASES, ("U3N32", "U3N32", "U3N32", "U3N64", "U3N64", "U3N128", "U3N128", "U3N32", "U3N32", "U3N32")))
 
 
 @pytest.mark.parametrize("c1,c2,cout,B,h,w", UPS_CASES)
@@ -107,6 +112,7 @@ def test_conv16_fused_upsample_vs_oracle(dev, c1, c2, cout, B, h, w):
     cat = a if b is None else torch.cat([a, b.expand(B, -1, -1, -1)], 1)
     want = O.conv2d_lrelu(O.upsample2x_bilinear(cat), wt, bias)
     H, W = 2 * h, 2 * w
+    assert hb.conv16_plan(3, cin, cout, W, ups=True)[0] == UPS_KINDS[(c1, c2, cout, B, h, w)]
     pk = hb.PackedConv16(wt.to(dev), bias.to(dev), W)
     pa = hb.HPlanes(B, c1, h, w, dev).load(a.to(dev))
     pb = hb.HPlanes(1, c2, h, w, dev).load(b.to(dev)) if c2 else None

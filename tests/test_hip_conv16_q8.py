@@ -37,21 +37,27 @@ def test_q8_layout_round_trip_and_guards(dev):
         hb.check(lib.ssm_hq8_from_f32(hb.view_of(torch.zeros(1, 8, 4, 4, device=dev)), odd.view(), 1, 8, 1, 4, 4, hb.stream_ptr()))
 
 
-@pytest.mark.parametrize("k,cin,cout,B,H,W,pool", [
-    (3, 128, 128, 2, 24, 70, False),      # N128 tile, ragged width
+Q8_CASES = [
+    (3, 128, 128, 2, 24, 70, False),      # N128S tile (W in 65..96: 32-wide tiles, single patch buffer), ragged width
     (3, 64, 64, 1, 40, 64, True),         # N64 tile + fused 2x2 mean
     (3, 32, 32, 1, 32, 96, False),        # N32 tile (2 workgroups per CU)
-    (3, 256, 256, 1, 12, 40, False),      # N128 narrow tile (single patch buffer)
-    (3, 512, 256, 1, 8, 24, False),       # deep K, two cout blocks
-    (3, 64, 32, 2, 16, 64, False),        # N32 deep-K tile
+    (3, 256, 256, 1, 12, 40, False),      # narrow map (W <= 48), Cin >= 128: the 32-cout tile with all filter rows per stage, 8 cout blocks
+    (3, 512, 256, 1, 8, 24, False),       # deep K, eight cout blocks
+    (3, 64, 32, 2, 16, 64, False),        # N32 tile, four chunks (the deep-K tile H3N32D needs Cin >= 128)
     (5, 64, 64, 2, 24, 64, True),         # k = 5: second tap group holds one real tap
     (7, 32, 32, 1, 24, 64, True),         # k = 7
     (7, 16, 32, 1, 16, 40, False),        # one 16-channel chunk
     (3, 6, 32, 1, 16, 32, False),         # channels padded to a chunk
     (3, 32, 5, 1, 16, 64, False),         # bare final_conv shape: fp32 output, no activation
-])
+]
+# the tile kind ssm_conv16_plan reports for each case, in the order of Q8_CASES (all kinds: tests/test_hip_conv16_kinds.py)
+Q8_KINDS = dict(zip(Q8_CASES, ("H3N128S", "H3N64", "H3N32", "H3N32W", "H3N32W", "H3N32", "H5", "H7", "H7", "H3N32V", "H3N32")))
+
+
+@pytest.mark.parametrize("k,cin,cout,B,H,W,pool", Q8_CASES)
 def test_q8_conv_vs_oracle(dev, k, cin, cout, B, H, W, pool):
     from ssm_amd import hipbind as hb
+    assert hb.conv16_plan(k, (cin + 15) // 16 * 16, cout, W, q8=True)[0] == Q8_KINDS[(k, cin, cout, B, H, W, pool)]
     torch.manual_seed(k * 1000 + cin + cout)
     w = torch.randn(cout, cin, k, k) / (cin * k * k) ** 0.5
     b = torch.randn(cout) * 0.1
@@ -86,10 +92,16 @@ def test_q8_two_source_concat(dev):
     assert float((yp.to_nchw().cpu() - O.conv2d_lrelu(torch.cat([a, c], 1), w, b)).abs().max()) < TOL
 
 
-@pytest.mark.parametrize("ca,cb,cout,B,h,w", [(64, 64, 32, 1, 16, 40), (128, 128, 64, 2, 12, 32), (256, 256, 128, 1, 8, 24),
-                                             (512, 512, 256, 1, 6, 10), (512, 0, 512, 1, 4, 6), (64, 64, 32, 1, 9, 17)])
+Q8_UPS_CASES = [(64, 64, 32, 1, 16, 40), (128, 128, 64, 2, 12, 32), (256, 256, 128, 1, 8, 24),
+                (512, 512, 256, 1, 6, 10), (512, 0, 512, 1, 4, 6), (64, 64, 32, 1, 9, 17)]
+# the fused tile kind of each case (U3N128 / U3N128S in Q8: tests/test_hip_conv16_kinds.py)
+Q8_UPS_KINDS = dict(zip(Q8_UPS_CASES, ("U3N32", "U3N64", "U3N32", "U3N32", "U3N32", "U3N32")))
+
+
+@pytest.mark.parametrize("ca,cb,cout,B,h,w", Q8_UPS_CASES)
 def test_q8_fused_upsample_conv_vs_oracle(dev, ca, cb, cout, B, h, w):
     from ssm_amd import hipbind as hb
+    assert hb.conv16_plan(3, ca + cb, cout, 2 * w, ups=True, q8=True)[0] == Q8_UPS_KINDS[(ca, cb, cout, B, h, w)]
     torch.manual_seed(ca + cb + cout)
     wt = torch.randn(cout, ca + cb, 3, 3) / ((ca + cb) * 9) ** 0.5
     bs = torch.randn(cout) * 0.1
