@@ -758,6 +758,36 @@ int ssm_frames_accumulate_light_fwd(ssm_view src, ssm_view acc, int N, int H, in
 int ssm_luma_sad_fwd(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b, int N, int H, int W,
                      unsigned long long *sums, void *stream);
 
+/* ---- hold-out scoring of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) -------------------------
+ * Definition (ssm_amd.video_score.HoldOutScorer(hold)).  Of a high-rate clip, input frames 0, hold, 2 hold, ... are KEPT and every frame
+ * strictly between two kept ones is HELD OUT: frame i = g hold + k, 0 < k < hold, is synthesised at t = k / hold from kept frames g hold
+ * and (g + 1) hold by the pipeline that the fixed grid of upsample_rate = hold runs, egressed to the clip's own format, and compared
+ * with the held-out payload as it was read - the codes the tool would write, after quantisation ("model") - and the held-out payload is
+ * compared with the nearer kept frame's, the left one for k / hold < 1/2 and the right one otherwise ("nearest", the do-nothing
+ * baseline).  A comparison is, per plane p of Y, U, V:  sse_p = sum over the plane's samples of (a - b)^2, an integer;  mse = sse /
+ * samples;  PSNR = 10 log10(peak^2 / mse) with peak = 2^bits - 1 whatever the code range (ffmpeg's `psnr` filter's convention), inf at
+ * sse = 0.  Planes and frames are pooled by their sums: PSNR of (sum of sse) / (sum of samples), never a mean of dB.
+ * ssm_plane_sse_fwd: a + n stride_a and b + n stride_b (strides in BYTES, of either sign, or 0: one payload against N) point at whole
+ * Y4M payloads n = 0 .. N-1: the Y plane H x W, then U, then V, each of the layout's chroma size (SSM_YUV_420_*: ceil(H/2) x ceil(W/2),
+ * SSM_YUV_422: H x ceil(W/2), SSM_YUV_444: H x W), unpadded.  sample_bytes = 1: bytes.  sample_bytes = 2: 16-bit little-endian words,
+ * ALL 16 BITS COUNT (the bit depth does not enter).  sums[3 n + p] = sse_p of (a_n, b_n), exact, in a device array of 3 N 64-bit
+ * words (exact while it is below 2^64: beyond 2^32 samples a plane).  The entry clears `sums` on `stream` itself (a memset node ahead of the kernel): the
+ * result does not depend on what the words held.  a and b are only read and may alias or overlap.  No byte outside the N payloads of
+ * either operand is read.
+ *   A workgroup of 256 lanes sums a span of 16 KiB of ONE plane (the grid's x axis counts the Y plane's spans, then U's, then V's: no span
+ *   crosses a plane boundary): each lane 4 pieces of 16 bytes.  Bytes: a.a + b.b - 2 a.b over four packed samples by three v_dot4_u32_u8,
+ *   32-bit lane and workgroup sums (a span's sum is at most 65025 * 16384 < 2^30).  Words: (a - b)^2 reaches 2^32 - 131071, so the lane
+ *   sum is 64-bit from the first add.  Waves reduced by cross-lane shuffles, 4 wave partials through LDS, one 64-bit vector atomicAdd per
+ *   workgroup; integer adds commute: the sums are the same in every run.  One 16-byte load per operand and piece where both planes
+ *   start on 16-byte boundaries; a plane that does not (odd H or W put U and V anywhere), and the last piece of a plane whose size is no
+ *   multiple of a piece, goes sample by sample in the same kernel.  No LDS beyond the wave partials, no scratch, no packed fp32.  Reads
+ *   2 sample_bytes per pair of samples, writes nothing but the sums.
+ * SSM_E_ARG (nothing is queued) for null pointers; N outside 1..65535; H or W < 1; a layout outside SSM_YUV_*; sample_bytes outside
+ * {1, 2}; a stride that is neither 0 nor at least the frame's bytes in magnitude; with sample_bytes = 2 an odd address or an odd stride;
+ * `sums` not 8-byte aligned; a frame of more than 2^31 - 1 spans. */
+int ssm_plane_sse_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int layout, int sample_bytes,
+                      unsigned long long *sums, void *stream);
+
 /* ---- training ingest (csrc/ssm_data.hip; whole decoded uint8 HWC RGB frames on the device) --------------
  * The clip loader (ssm_amd/data.py) serves the reference's training transform, RandomCrop, then RandomMirrorRotate,
  * then Normalize and ToTensor (scripts/utils/dataloaders/default_reader.py:182-207,250-286, augmentations.py:

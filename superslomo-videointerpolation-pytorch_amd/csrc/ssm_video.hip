@@ -20,8 +20,12 @@
 //   luma_sad_kernel          scene cuts of the streamed loop: per frame pair the exact sum of |a - b| over the 8-bit Y planes;
 //                            one lane = 16 consecutive bytes of each plane (one 16-byte load per operand), or byte loads where a plane
 //                            does not start on a 16-byte boundary; v_sad_u8 into a 32-bit lane sum, shuffles, one 64-bit atomic per workgroup
+//   plane_sse_kernel         hold-out scoring of the streamed loop: per frame pair and plane (Y, U, V) the exact sum of (a - b)^2
+//                            over the samples as they stand in the payloads, 8-bit or 16-bit; a workgroup sums 16 KiB of ONE plane, a lane 4
+//                            pieces of 16 bytes per operand (sample by sample where a plane does not start on a 16-byte boundary);
+//                            bytes through v_dot4_u32_u8 into 32-bit lane sums, words into 64-bit ones; one 64-bit atomic per workgroup
 // Both conversions are HBM-bound (1.5 to 6 B in + 12 B out per pixel, and the reverse); so is the accumulation (4 (N + 1 + !init) B per
-// element) and the luma difference (2 B per pixel).  The chroma siting enters as four horizontal weights (ingest) or one switch (egress); matrix and range enter as one row of
+// element), the luma difference (2 B per pixel) and the squared differences (2 B per pair of samples).  The chroma siting enters as four horizontal weights (ingest) or one switch (egress); matrix and range enter as one row of
 // the constant table built by ssm_amd/video.py, which the host yardsticks read too.  Inputs of the egress kernel are finite.
 // NO CONTRACTION (as ssm_flow.hip): the numpy yardsticks round every operation, and so must the kernels.
 #include "ssm_common.h"
@@ -458,6 +462,122 @@ __global__ __launch_bounds__(SAD_LANES) void luma_sad_kernel(const unsigned char
     }
 }
 
+// ---- hold-out scoring: squared differences summed per plane ----------------------------------------------------------------------------
+// sums[3 n + p] += sum over this workgroup's span of (a_n[i] - b_n[i])^2, i over the samples of plane p (Y, U, V) of payload n.  The grid's
+// x axis is g0 workgroups of the Y plane, then g1 of U, then g1 of V: a workgroup belongs to ONE plane and its span never leaves it.  A span
+// is SSE_SPAN_BYTES = 16 KiB of a plane, a lane takes SSE_CHUNKS pieces of 16 bytes, SSE_LANES * 16 bytes apart, as luma_sad_kernel does.
+//   bytes: (a - b)^2 summed over four packed samples is  a.a + b.b - 2 a.b,  three v_dot4_u32_u8 per pair of words and no unpacking: `sq`
+//     takes a.a + b.b, `ab` takes a.b, and sq - 2 ab is the sum, exact (every term is an integer and sq >= 2 ab).  A lane sees 16 *
+//     SSE_CHUNKS samples: sq <= 2 * 65025 * 64 < 2^24.  A workgroup's sum is at most 65025 * 16384 < 2^30: lane, wave and workgroup sums fit
+//     32 bits (static_assert below).
+//   16-bit words: d^2 reaches 65535^2 = 2^32 - 131071, two of them overflow 32 bits: the lane sum is 64-bit from the first add
+//     (|d| * |d| + s as one 32 x 32 + 64 multiply-add), and so is everything after it.
+// The 16-byte loads need both planes' starts on 16-byte boundaries - decided per (n, plane), uniform over the workgroup.  Any other plane
+// (odd H or W put U and V anywhere; 4:2:0 at 45 x 71 starts U at an odd byte), and the last piece of a plane whose size is no multiple of
+// a piece, goes sample by sample, samples past the plane's end never loaded.  One 64-bit vector atomic per workgroup.
+constexpr int SSE_LANES = 256, SSE_CHUNKS = 4;
+constexpr long long SSE_SPAN_BYTES = (long long)SSE_LANES * 16 * SSE_CHUNKS;
+static_assert(2ll * 65025 * 16 * SSE_CHUNKS < (1ll << 32), "a lane's sums of 8-bit products fit 32 bits");
+static_assert(65025ll * SSE_SPAN_BYTES < (1ll << 32), "a workgroup's sum of 8-bit squares fits 32 bits");
+
+template <typename S> struct SseLane;
+template <> struct SseLane<unsigned char> {
+    typedef unsigned Sum;
+    unsigned sq = 0, ab = 0, tail = 0;
+    __device__ __forceinline__ void words(unsigned x, unsigned y) {
+#if __has_builtin(__builtin_amdgcn_udot4)
+        sq = __builtin_amdgcn_udot4(x, x, sq, false);
+        sq = __builtin_amdgcn_udot4(y, y, sq, false);
+        ab = __builtin_amdgcn_udot4(x, y, ab, false);
+#else
+#pragma unroll
+        for (int i = 0; i < 4; ++i) one((x >> (8 * i)) & 255u, (y >> (8 * i)) & 255u);
+#endif
+    }
+    __device__ __forceinline__ void one(unsigned x, unsigned y) {
+        const int d = (int)x - (int)y;
+        tail += (unsigned)(d * d);
+    }
+    __device__ __forceinline__ Sum sum() const { return (sq - 2u * ab) + tail; }
+};
+template <> struct SseLane<unsigned short> {
+    typedef unsigned long long Sum;
+    unsigned long long s = 0;
+    __device__ __forceinline__ void one(unsigned x, unsigned y) {
+        const unsigned d = x > y ? x - y : y - x;
+        s += (unsigned long long)d * d;
+    }
+    __device__ __forceinline__ void words(unsigned x, unsigned y) {
+        one(x & 0xffffu, y & 0xffffu);
+        one(x >> 16, y >> 16);
+    }
+    __device__ __forceinline__ Sum sum() const { return s; }
+};
+
+template <typename S>
+__device__ __forceinline__ void sse16(SseLane<S> &acc, i32x4 x, i32x4 y) {
+    acc.words((unsigned)x.x, (unsigned)y.x);
+    acc.words((unsigned)x.y, (unsigned)y.y);
+    acc.words((unsigned)x.z, (unsigned)y.z);
+    acc.words((unsigned)x.w, (unsigned)y.w);
+}
+
+template <typename S>          // the sample: unsigned char, or unsigned short (all 16 bits count)
+__global__ __launch_bounds__(SSE_LANES) void plane_sse_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
+                                                              long long luma, long long chroma, unsigned g0, unsigned g1,
+                                                              unsigned long long *sums) {          // a, b may alias; luma, chroma in samples
+    typedef typename SseLane<S>::Sum Sum;
+    constexpr int V = 16 / (int)sizeof(S);                             // samples of a piece
+    constexpr long long SPAN = SSE_SPAN_BYTES / (long long)sizeof(S);          // samples of a span
+    __shared__ Sum partial[SSE_LANES / 64];
+    const int n = blockIdx.y;
+    unsigned g = blockIdx.x;
+    int p = 0;
+    if (g >= g0) {
+        g -= g0, p = 1;
+        if (g >= g1) g -= g1, p = 2;
+    }
+    const long long plane = p == 0 ? luma : chroma, first = p == 0 ? 0 : luma + (p - 1) * chroma;          // the plane's samples, its first one
+    const S *pa = reinterpret_cast<const S *>(a + n * stride_a) + first, *pb = reinterpret_cast<const S *>(b + n * stride_b) + first;
+    const bool vec = ((reinterpret_cast<size_t>(pa) | reinterpret_cast<size_t>(pb)) & 15) == 0;
+    const long long base = g * SPAN + threadIdx.x * V;
+    SseLane<S> acc;
+    if (vec && (g + 1) * SPAN <= plane) {          // the whole span lies inside the plane: all loads first, none guarded
+        i32x4 va[SSE_CHUNKS], vb[SSE_CHUNKS];
+#pragma unroll
+        for (int c = 0; c < SSE_CHUNKS; ++c) {
+            va[c] = *reinterpret_cast<const i32x4 *>(pa + base + (long long)c * SSE_LANES * V);
+            vb[c] = *reinterpret_cast<const i32x4 *>(pb + base + (long long)c * SSE_LANES * V);
+        }
+#pragma unroll
+        for (int c = 0; c < SSE_CHUNKS; ++c) sse16(acc, va[c], vb[c]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < SSE_CHUNKS; ++c) {
+            const long long o = base + (long long)c * SSE_LANES * V;
+            if (o >= plane) break;
+            if (vec && o + V <= plane) {
+                sse16(acc, *reinterpret_cast<const i32x4 *>(pa + o), *reinterpret_cast<const i32x4 *>(pb + o));
+            } else {
+#pragma unroll
+                for (int i = 0; i < V; ++i)
+                    if (o + i < plane) acc.one(pa[o + i], pb[o + i]);
+            }
+        }
+    }
+    Sum s = acc.sum();
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+    if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        Sum t = 0;
+#pragma unroll
+        for (int w = 0; w < SSE_LANES / 64; ++w) t += partial[w];
+        atomicAdd(&sums[3 * n + p], (unsigned long long)t);
+    }
+}
+
 // first and one-past-last address, in bytes, of the floats a view of [n,c,h,w] names (strides of either sign)
 inline void view_range(const ssm_view &v, int n, int c, int h, int w, long long *lo, long long *hi) {
     long long a = 0, b = 0;
@@ -689,4 +809,44 @@ extern "C" int ssm_luma_sad_fwd(const unsigned char *a, const unsigned char *b, 
     }
     SSM_LAUNCH(luma_sad_kernel, dim3((unsigned)groups, N), dim3(SAD_LANES), 0, (hipStream_t)stream, a, b, stride_a, stride_b, plane, sums);
     return ssm::check_launch("ssm_luma_sad_fwd");
+}
+
+// samples of one chroma plane
+static long long yuv_chroma_samples(int H, int W, int layout) {
+    const long long cw = layout == SSM_YUV_444 ? W : (W + 1) / 2, ch = layout == SSM_YUV_420_CENTRED || layout == SSM_YUV_420_COSITED ? (H + 1) / 2 : H;
+    return ch * cw;
+}
+
+extern "C" int ssm_plane_sse_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int layout,
+                                 int sample_bytes, unsigned long long *sums, void *stream) {
+    SSM_REQUIRE(a && b && sums, "plane_sse: null pointer");
+    SSM_REQUIRE(N > 0 && N <= 65535, "plane_sse: N=%d outside 1..65535", N);
+    SSM_REQUIRE(H > 0 && W > 0, "plane_sse: bad frame size %dx%d", H, W);
+    SSM_REQUIRE(layout >= SSM_YUV_420_CENTRED && layout <= SSM_YUV_422, "plane_sse: layout %d not in {0, 1, 2, 3}", layout);
+    SSM_REQUIRE(sample_bytes == 1 || sample_bytes == 2, "plane_sse: sample_bytes %d not in {1, 2}", sample_bytes);
+    const long long luma = (long long)H * W, chroma = yuv_chroma_samples(H, W, layout), frame = yuv_frame_samples(H, W, layout) * sample_bytes;
+    SSM_REQUIRE((stride_a == 0 || std::llabs(stride_a) >= frame) && (stride_b == 0 || std::llabs(stride_b) >= frame),
+                "plane_sse: strides %lld (a), %lld (b) neither 0 nor at least the frame's %lld bytes", stride_a, stride_b, frame);
+    if (sample_bytes == 2) {
+        SSM_REQUIRE(reinterpret_cast<size_t>(a) % 2 == 0 && reinterpret_cast<size_t>(b) % 2 == 0,
+                    "plane_sse: a payload of 2-byte samples (a or b) is not 2-byte aligned");
+        SSM_REQUIRE(stride_a % 2 == 0 && stride_b % 2 == 0, "plane_sse: strides %lld (a), %lld (b) of 2-byte samples must be even", stride_a, stride_b);
+    }
+    SSM_REQUIRE(reinterpret_cast<size_t>(sums) % 8 == 0, "plane_sse: sums is not 8-byte aligned");
+    const long long span = SSE_SPAN_BYTES / sample_bytes, g0 = (luma + span - 1) / span, g1 = (chroma + span - 1) / span;
+    SSM_REQUIRE(g0 + 2 * g1 <= 2147483647ll, "plane_sse: a frame of %lld bytes is more than the grid takes", frame);
+    const hipError_t e = ssm::memset_async(sums, 0, sizeof(unsigned long long) * 3 * (size_t)N, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        ssm::set_error("plane_sse: memset failed: %s", hipGetErrorString(e));
+        return SSM_E_LAUNCH;
+    }
+    const unsigned char *pa = static_cast<const unsigned char *>(a), *pb = static_cast<const unsigned char *>(b);
+    const dim3 grid((unsigned)(g0 + 2 * g1), N);
+    if (sample_bytes == 1)
+        SSM_LAUNCH(plane_sse_kernel<unsigned char>, grid, dim3(SSE_LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b, luma, chroma,
+                   (unsigned)g0, (unsigned)g1, sums);
+    else
+        SSM_LAUNCH(plane_sse_kernel<unsigned short>, grid, dim3(SSE_LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b, luma, chroma,
+                   (unsigned)g0, (unsigned)g1, sums);
+    return ssm::check_launch("ssm_plane_sse_fwd");
 }

@@ -25,6 +25,8 @@
   luma_sad_host / luma_sad   scene cuts: per frame pair the exact sum of |difference| of the 8-bit Y planes, by numpy (the yardstick) and by
   / SceneCuts             ssm_luma_sad_fwd on the payloads as they stand on the device; the decision from those sums in Fractions, with no
                           GPU in it - VideoInterpolator(scene_cut=): at a cut the output repeats the nearer input frame instead of a morph
+  (ssm_amd/video_score.py) hold-out scoring: the clip against its own held-out frames, plane_sse / HoldOutScorer on this loop's ring, Clip and
+                          buffers; the PSNR of what VideoInterpolator(upsample_rate=hold) would write - this module is unchanged by it
 
 Formats.  A sample of more than 8 bits is a 16-bit little-endian word with the value in its low bits (ffmpeg's convention); payloads stay
 [N, frame_bytes] uint8 whatever the depth, so the ring, the pinned slots and "input frames reach the output as their own bytes" do not
@@ -36,7 +38,8 @@ override for C420pB, big-endian samples, scene cuts above 8 bits (ssm_luma_sad_f
 configuration (N_FRAMES > 2); shutter weights other than
 the box, a light curve chosen from the clip's tags, HDR transfer curves (PQ, HLG), a shutter centred on the frame's instant or open for longer than the frame interval,
 variable-rate input, speeds that change within a clip; a default scene-cut threshold, fades and dissolves, cuts judged on chroma,
-skipping the GPU work of a cut pair, scene cuts together with a shutter.
+skipping the GPU work of a cut pair, scene cuts together with a shutter; a measure of quality other than video_score's PSNR against
+held-out frames (SSIM, VMAF), and that score for the timeline, shutter and scene-cut outputs.
 """
 import ctypes
 import functools
@@ -979,6 +982,16 @@ class ShutterPlanner:
 
 
 # ---- the streamed loop -------------------------------------------------------------------------------------------------------------
+class _Drop:
+    """The sink of a ring without a writer: the rows are taken and go nowhere."""
+
+    def write_frame(self, buf):
+        pass
+
+
+_DROP = _Drop()
+
+
 class PassRing:
     """The ring of `depth` slots between the loop that queues passes and the thread that writes what they made, and the loop's failure
     protocol.  Free of the GPU: an event is anything with synchronize(), the writer anything with write_frame(buf).
@@ -990,10 +1003,11 @@ class PassRing:
     item in the order handed over.  After the first exception on the thread nothing more is written and every slot handed over still
     comes back, so the producer never blocks in take(); it looks at `failure` and stops reading and submitting.  close() - leaving the
     `with` block - ends the thread, calls `settle` (the loop's device synchronise) and raises the stored exception, the object itself.
-    An exception of the producer's own goes first: it propagates, and the ring shuts down under it without raising."""
+    An exception of the producer's own goes first: it propagates, and the ring shuts down under it without raising.
+    writer None: the rows are taken, in order, and dropped (the hold-out scorer without an output, ssm_amd/video_score.py)."""
 
     def __init__(self, depth, writer, settle=None):
-        self.writer, self.settle, self.failure = writer, settle, []
+        self.writer, self.settle, self.failure = _DROP if writer is None else writer, settle, []
         self.free, self.work = queue.Queue(), queue.Queue()
         for r in range(depth):
             self.free.put(r)
