@@ -788,6 +788,57 @@ int ssm_luma_sad_fwd(const unsigned char *a, const unsigned char *b, long long s
 int ssm_plane_sse_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int layout, int sample_bytes,
                       unsigned long long *sums, void *stream);
 
+/* SSIM of the same comparisons, in fixed point (ssm_amd.video_score.plane_ssim_host is the definition in numpy).  The construction is that
+ * of x264 and of ffmpeg's `ssim` filter.  Take a plane of rows x cols samples as it stands in the payload (row pitch cols, no padding):
+ *   blocks   block (bx, by) is the 4 x 4 samples at (4 bx, 4 by), bx < cols >> 2, by < rows >> 2; the trailing cols & 3 columns and rows & 3
+ *            rows belong to no block.  Per block  s1 = sum a,  s2 = sum b,  ss = sum (a^2 + b^2),  s12 = sum a b.
+ *   windows  window (wx, wy) is the 8 x 8 area of blocks (wx .. wx + 1, wy .. wy + 1), at stride 4: it exists for wx < (cols >> 2) - 1 and
+ *            wy < (rows >> 2) - 1;  count = max(0, (cols >> 2) - 1) max(0, (rows >> 2) - 1);  a plane of fewer than 8 rows or columns has
+ *            none.  A window's four sums are the sums of its four blocks' sums.
+ *   per window, in integers:  vars = 64 ss - s1^2 - s2^2;  covar = 64 s12 - s1 s2;
+ *            f0 = 2 s1 s2 + c1;  f1 = 2 covar + c2;  f2 = s1^2 + s2^2 + c1;  f3 = vars + c2
+ *            with c1 = floor(.01^2 peak^2 64 + .5), c2 = floor(.03^2 peak^2 64 63 + .5), peak = 2^bits - 1 of the clip's SIGNIFICANT bits
+ *            (as in the PSNR, not the width of the word); the host passes c1 and c2 (ssm_amd.video_score.ssim_constants).  All four
+ *            factors are below 2^45 at 16 bits and 2^29 at 8: exact in int64 and exact as doubles.
+ *   in float64, one rounded operation each and no contraction:  q = (double(f0) double(f1)) / (double(f2) double(f3));
+ *            fx = rint(q 2^32), half to even, as int64.
+ *   result   sums[3 n + p] = sum over the windows of plane p (Y, U, V) of payload pair n of fx: a SIGNED 64-bit integer.  The SSIM of a
+ *            plane is sums / (2^32 count); frames, positions and planes pool by sums and counts, as the PSNR does - "avg" is the sum over
+ *            the planes of sums over 2^32 times the sum of their counts, pooled by WINDOWS, not ffmpeg's weighting by plane size; in dB,
+ *            -10 log10(1 - ssim), inf at 1.
+ * Fixed point makes the sum an integer: independent of the order of the atomics, the same in every run, and EQUAL to numpy's - which rests
+ * on `/` of doubles being the correctly rounded IEEE quotient on the device (it is: the v_div_scale_f64 / v_rcp_f64 / v_fma_f64 /
+ * v_div_fmas_f64 / v_div_fixup_f64 expansion, no fast-math flag in csrc/Makefile).
+ * ssm_plane_ssim_fwd: a, b, the strides, N, H, W, layout and sample_bytes as for ssm_plane_sse_fwd; with sample_bytes = 2 all 16 bits of a
+ * word enter the sums and the depth enters through c1 and c2 alone.  The entry clears the 3 N words of `sums` on `stream` itself, then the
+ * kernel adds; a plane without a window keeps the cleared 0 (a frame without any window queues the clear alone).  a and b are only read
+ * and may alias or overlap.  No byte outside the N payloads is read.
+ *   A workgroup of 256 lanes owns a tile of 31 x 15 windows of ONE plane (the grid's x axis counts Y's tiles, then U's, then V's) and
+ *   computes the 32 x 16 blocks under them, the last block column and row again in the neighbouring tile.  A lane takes two whole blocks:
+ *   per row and operand one 4-byte word (bytes) or one 8-byte load (words) where plane start and cols make every row address aligned -
+ *   decided per (n, plane) - and sample by sample otherwise, in the same kernel.  Bytes go through v_dot4_u32_u8 into 32-bit block sums;
+ *   of words, ss and s12 are 64-bit from the first add.  Block sums go to LDS (8 or 12 KiB); after one barrier a lane forms two windows
+ *   from four entries each, evaluates fx and adds to a 64-bit lane sum; shuffles, 4 wave partials through LDS, one 64-bit vector atomicAdd
+ *   per workgroup.  No scratch, no packed fp32.
+ * SSM_E_ARG (nothing is queued) as for ssm_plane_sse_fwd, under the name plane_ssim, and for c1 or c2 outside 1..2^40. */
+int ssm_plane_ssim_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int layout, int sample_bytes,
+                       long long c1, long long c2, long long *sums, void *stream);
+
+/* The cross-fade of two payloads, the baseline `mix` of the hold-out score (what frame blending writes between two kept frames).
+ * ssm_payload_mix_fwd: rows n = 0 .. N-1 of `samples` samples (bytes, or 16-bit little-endian words: sample_bytes = 1 or 2; planes need no
+ * telling apart) at a + n stride_a, b + n stride_b (BYTES, either sign, or 0: one row for all n) and out + n stride_out.  With
+ * k = num0 + n num_step every sample of row n is
+ *     out = (a (den - k) + b k + (den >> 1)) / den          an integer division: the exact rational rounded half up
+ * in 32-bit unsigned arithmetic (65535 * 65535 + 32767 < 2^32).  The division by the launch-constant den is Granlund and Montgomery's
+ * multiply-shift with a host-computed pair, exact for every 32-bit numerator (csrc/ssm_video.hip; ssm_amd.video_score.mix_divisor is the
+ * same pair, proven over the reachable numerators in tests/test_video_ssim_cpu.py).  16-byte loads and stores where the three rows of an n
+ * start on 16-byte boundaries, sample by sample otherwise and at a row's end; nothing past `samples` is read or written.
+ * SSM_E_ARG (nothing is queued) for null pointers; N outside 1..65535; samples < 1; sample_bytes outside {1, 2}; den outside 2..65535; a
+ * k outside 0..den; a stride of a or b that is neither 0 nor at least the row's bytes; with N > 1 a |stride_out| shorter than the row;
+ * with sample_bytes = 2 an odd address or stride; `out` overlapping a or b; a row of more than 2^31 - 1 spans of 16 KiB. */
+int ssm_payload_mix_fwd(const void *a, const void *b, long long stride_a, long long stride_b, void *out, long long stride_out, int N,
+                        long long samples, int sample_bytes, int num0, int num_step, int den, void *stream);
+
 /* ---- training ingest (csrc/ssm_data.hip; whole decoded uint8 HWC RGB frames on the device) --------------
  * The clip loader (ssm_amd/data.py) serves the reference's training transform, RandomCrop, then RandomMirrorRotate,
  * then Normalize and ToTensor (scripts/utils/dataloaders/default_reader.py:182-207,250-286, augmentations.py:

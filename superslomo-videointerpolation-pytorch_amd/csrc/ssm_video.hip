@@ -24,6 +24,11 @@
 //                            over the samples as they stand in the payloads, 8-bit or 16-bit; a workgroup sums 16 KiB of ONE plane, a lane 4
 //                            pieces of 16 bytes per operand (sample by sample where a plane does not start on a 16-byte boundary);
 //                            bytes through v_dot4_u32_u8 into 32-bit lane sums, words into 64-bit ones; one 64-bit atomic per workgroup
+//   plane_ssim_kernel        hold-out scoring: per frame pair and plane the SSIM of x264 / ffmpeg's ssim filter in fixed point - 4 x 4 block
+//                            sums (bytes through v_dot4_u32_u8) to LDS, 8 x 8 windows at stride 4 from four blocks, integer factors, one
+//                            float64 quotient per window rounded to a multiple of 2^-32, signed 64-bit sums; a workgroup owns 31 x 15 windows
+//   payload_mix_kernel       hold-out scoring: the cross-fade (a (den - k) + b k + den / 2) / den of two payloads, the frame-blend baseline;
+//                            exact division by multiply-shift, 16-byte loads and stores where the rows allow it
 // Both conversions are HBM-bound (1.5 to 6 B in + 12 B out per pixel, and the reverse); so is the accumulation (4 (N + 1 + !init) B per
 // element), the luma difference (2 B per pixel) and the squared differences (2 B per pair of samples).  The chroma siting enters as four horizontal weights (ingest) or one switch (egress); matrix and range enter as one row of
 // the constant table built by ssm_amd/video.py, which the host yardsticks read too.  Inputs of the egress kernel are finite.
@@ -578,6 +583,213 @@ __global__ __launch_bounds__(SSE_LANES) void plane_sse_kernel(const unsigned cha
     }
 }
 
+// ---- hold-out scoring: SSIM in fixed point, summed per plane ---------------------------------------------------------------------------
+// The definition is in include/ssm_hip.h (x264's and ffmpeg's construction: 4 x 4 blocks, 8 x 8 windows at stride 4, integer factors, ONE
+// float64 quotient per window, rounded to a multiple of 2^-32).  sums[3 n + p] += sum over this workgroup's windows of fx.
+// A workgroup owns a tile of SSIM_TW x SSIM_TH windows of ONE plane of one payload and computes the SSIM_BW x SSIM_BH = (TW + 1) x (TH + 1)
+// blocks they stand on; the extra block column and row are computed again by the neighbouring tile (33 x 17 / (32 x 16) - 1 < 10 % more
+// loads).  The grid's x axis counts Y's tiles (row-major), then U's, then V's; a plane without a window has no tile.
+//   blocks  lane (lx, ly) of 32 x 8 takes blocks (lx, ly) and (lx, ly + 8) of the tile: four rows of four samples per operand.  Bytes: one
+//           32-bit word per row where every row address of both operands is 4-byte aligned (plane start and cols multiples of 4 - per
+//           (n, plane), uniform), else four byte loads; s1, s2 by udot4(x, 0x01010101), ss by udot4(x, x) + udot4(y, y), s12 by udot4(x, y):
+//           a block's ss is at most 16 * 2 * 65025 < 2^22.  Words: one 8-byte load per row where the addresses are 8-byte aligned, else
+//           four 2-byte loads; s1, s2 <= 16 * 65535 < 2^20 in 32 bits, ss and s12 (up to 2^37) in 64 bits from the first add.
+//   windows after one barrier lane (lx, ly) forms windows (lx, ly) and (lx, ly + 8) from four LDS entries each (lx < TW, wy < TH, inside
+//           the plane's window grid), evaluates fx and adds it to a signed 64-bit lane sum.  A 32-lane row of the wave reads consecutive
+//           entries: no bank conflict beyond the entry's own width.
+// The factors are exact in int64 (below 2^45 + c) and exact as doubles; the quotient is `/` on doubles - hipcc expands it to the IEEE
+// sequence (v_div_scale_f64, v_rcp_f64, v_fma_f64 ..., v_div_fmas_f64, v_div_fixup_f64), correctly rounded as numpy's - and this file is
+// compiled without contraction.  f2 f3 > 0 (c1, c2 > 0 and 64 ss >= s1^2 + s2^2), |q| <= 1 up to rounding: rint(q 2^32) fits int64.
+constexpr int SSIM_LANES = 256, SSIM_BW = 32, SSIM_BH = 16, SSIM_TW = SSIM_BW - 1, SSIM_TH = SSIM_BH - 1;
+static_assert(SSIM_BW * SSIM_BH == 2 * SSIM_LANES, "a lane takes two blocks, SSIM_BH / 2 block rows apart");
+static_assert(16ll * 2 * 65025 < (1ll << 32) && 16ll * 65535 < (1ll << 32), "the block sums of bytes, and s1, s2 of words, fit 32 bits");
+static_assert(64ll * (64ll * 2 * 65535 * 65535) < (1ll << 46), "64 ss of a window of words stays far inside int64 and exact as a double");
+
+template <typename S> struct SsimBlock;
+template <> struct SsimBlock<unsigned char> {
+    unsigned s1, s2, ss, s12;
+    __device__ __forceinline__ void clear() { s1 = s2 = ss = s12 = 0; }
+    __device__ __forceinline__ void row(const unsigned char *pa, const unsigned char *pb, bool vec) {
+        unsigned x, y;
+        if (vec) {
+            x = *reinterpret_cast<const unsigned *>(pa), y = *reinterpret_cast<const unsigned *>(pb);
+        } else {
+            x = pa[0] | (pa[1] << 8) | (pa[2] << 16) | ((unsigned)pa[3] << 24);
+            y = pb[0] | (pb[1] << 8) | (pb[2] << 16) | ((unsigned)pb[3] << 24);
+        }
+#if __has_builtin(__builtin_amdgcn_udot4)
+        s1 = __builtin_amdgcn_udot4(x, 0x01010101u, s1, false);
+        s2 = __builtin_amdgcn_udot4(y, 0x01010101u, s2, false);
+        ss = __builtin_amdgcn_udot4(x, x, ss, false);
+        ss = __builtin_amdgcn_udot4(y, y, ss, false);
+        s12 = __builtin_amdgcn_udot4(x, y, s12, false);
+#else
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const unsigned u = (x >> (8 * i)) & 255u, v = (y >> (8 * i)) & 255u;
+            s1 += u, s2 += v, ss += u * u + v * v, s12 += u * v;
+        }
+#endif
+    }
+};
+template <> struct SsimBlock<unsigned short> {
+    unsigned long long ss, s12;
+    unsigned s1, s2;
+    __device__ __forceinline__ void clear() { s1 = s2 = 0, ss = s12 = 0; }
+    __device__ __forceinline__ void one(unsigned u, unsigned v) {
+        s1 += u, s2 += v;
+        ss += (unsigned long long)u * u;
+        ss += (unsigned long long)v * v;
+        s12 += (unsigned long long)u * v;
+    }
+    __device__ __forceinline__ void row(const unsigned short *pa, const unsigned short *pb, bool vec) {
+        if (vec) {
+            const i32x2 x = *reinterpret_cast<const i32x2 *>(pa), y = *reinterpret_cast<const i32x2 *>(pb);
+            one((unsigned)x.x & 0xffffu, (unsigned)y.x & 0xffffu);
+            one((unsigned)x.x >> 16, (unsigned)y.x >> 16);
+            one((unsigned)x.y & 0xffffu, (unsigned)y.y & 0xffffu);
+            one((unsigned)x.y >> 16, (unsigned)y.y >> 16);
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) one(pa[i], pb[i]);
+        }
+    }
+};
+
+// fx of one window from the sums of its four blocks (header: the order of operations is the definition)
+__device__ __forceinline__ long long ssim_fx(unsigned s1, unsigned s2, unsigned long long ss, unsigned long long s12, long long c1, long long c2) {
+    const long long p11 = (long long)((unsigned long long)s1 * s1), p22 = (long long)((unsigned long long)s2 * s2),
+                    p12 = (long long)((unsigned long long)s1 * s2);
+    const long long vars = 64ll * (long long)ss - p11 - p22, covar = 64ll * (long long)s12 - p12;
+    const long long f0 = 2 * p12 + c1, f1 = 2 * covar + c2, f2 = p11 + p22 + c1, f3 = vars + c2;
+    const double num = (double)f0 * (double)f1, den = (double)f2 * (double)f3;
+    const double q = num / den;
+    return (long long)__builtin_rint(q * 4294967296.0);
+}
+
+template <typename S>          // the sample: unsigned char, or unsigned short (all 16 bits count; the depth is in c1, c2 alone)
+__global__ __launch_bounds__(SSIM_LANES) void plane_ssim_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
+                                                                int rows0, int cols0, int rows1, int cols1, unsigned tx0, unsigned tx1,
+                                                                unsigned g0, unsigned g1, long long c1, long long c2,
+                                                                unsigned long long *sums) {          // a, b may alias
+    __shared__ SsimBlock<S> blk[SSIM_BH][SSIM_BW];
+    __shared__ long long partial[SSIM_LANES / 64];
+    const int n = blockIdx.y;
+    unsigned g = blockIdx.x;
+    int p = 0;
+    if (g >= g0) {
+        g -= g0, p = 1;
+        if (g >= g1) g -= g1, p = 2;
+    }
+    const int rows = p == 0 ? rows0 : rows1, cols = p == 0 ? cols0 : cols1;
+    const unsigned tx = p == 0 ? tx0 : tx1;
+    const long long luma = (long long)rows0 * cols0, chroma = (long long)rows1 * cols1;
+    const long long first = p == 0 ? 0 : luma + (p - 1) * chroma;          // the plane's first sample
+    const S *pa = reinterpret_cast<const S *>(a + n * stride_a) + first, *pb = reinterpret_cast<const S *>(b + n * stride_b) + first;
+    const int nbx = cols >> 2, nby = rows >> 2;                            // the plane's blocks; its windows are (nbx - 1) x (nby - 1)
+    const int bx0 = (int)(g % tx) * SSIM_TW, by0 = (int)(g / tx) * SSIM_TH;          // the tile's first block = its first window
+    constexpr size_t ALIGN = 4 * sizeof(S);                                // a block row: 4 bytes, or 8
+    const bool vec = ((reinterpret_cast<size_t>(pa) | reinterpret_cast<size_t>(pb)) % ALIGN) == 0 && (cols & 3) == 0;
+    const int lx = threadIdx.x & (SSIM_BW - 1), ly = threadIdx.x / SSIM_BW;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int by = ly + h * (SSIM_BH / 2);
+        if (bx0 + lx < nbx && by0 + by < nby) {          // a block of the plane: its 16 samples lie inside rows x cols
+            SsimBlock<S> s;
+            s.clear();
+            const long long o = (long long)(4 * (by0 + by)) * cols + 4 * (bx0 + lx);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s.row(pa + o + (long long)r * cols, pb + o + (long long)r * cols, vec);
+            blk[by][lx] = s;
+        }
+    }
+    __syncthreads();
+    long long s = 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int wy = ly + h * (SSIM_BH / 2);
+        if (lx < SSIM_TW && wy < SSIM_TH && bx0 + lx + 1 < nbx && by0 + wy + 1 < nby) {
+            const SsimBlock<S> &q00 = blk[wy][lx], &q01 = blk[wy][lx + 1], &q10 = blk[wy + 1][lx], &q11 = blk[wy + 1][lx + 1];
+            s += ssim_fx(q00.s1 + q01.s1 + q10.s1 + q11.s1, q00.s2 + q01.s2 + q10.s2 + q11.s2,
+                         (unsigned long long)q00.ss + q01.ss + q10.ss + q11.ss, (unsigned long long)q00.s12 + q01.s12 + q10.s12 + q11.s12, c1, c2);
+        }
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+    if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        long long t = 0;
+#pragma unroll
+        for (int w = 0; w < SSIM_LANES / 64; ++w) t += partial[w];
+        atomicAdd(&sums[3 * n + p], (unsigned long long)t);          // two's complement: the wrapped adds are the signed sum
+    }
+}
+
+// ---- hold-out scoring: the cross-fade of two payloads ---------------------------------------------------------------------------------
+// out_n[i] = (a_n[i] (den - k) + b_n[i] k + (den >> 1)) / den with k = num0 + n num_step, i over the `samples` samples of a row: the
+// frame-blend baseline, rounded half up.  The numerator is below 65535 * 65535 + 32768 < 2^32.  THE DIVISION is the multiply-shift of
+// Granlund and Montgomery for an invariant divisor, exact for every 32-bit numerator and every den >= 2: with l = ceil(log2 den) and
+// m = floor(2^32 (2^l - den) / den) + 1 (host, MixDivisor),  t = mulhi(m, x);  x / den = (t + ((x - t) >> 1)) >> (l - 1).
+// ssm_amd.video_score.mix_divisor is the same pair, and tests/test_video_ssim_cpu.py proves it over the numerators the scorer can reach.
+// A workgroup takes MIX_SPAN_BYTES of a row, a lane MIX_CHUNKS pieces of 16 bytes, MIX_LANES * 16 bytes apart; 16-byte loads and stores
+// where the three rows start on 16-byte boundaries (per n, uniform), sample by sample otherwise and in the last piece of a row that is
+// no multiple of a piece.  Nothing past `samples` is loaded or stored.
+constexpr int MIX_LANES = 256, MIX_CHUNKS = 4;
+constexpr long long MIX_SPAN_BYTES = (long long)MIX_LANES * 16 * MIX_CHUNKS;
+static_assert(65535ll * 65535 + 32767 < (1ll << 32), "the numerator fits 32 bits unsigned");
+
+struct MixDivisor {
+    unsigned m, shift, half;          // shift = l - 1; half = den >> 1
+};
+
+__device__ __forceinline__ unsigned mix_one(unsigned x, unsigned y, unsigned wa, unsigned wb, MixDivisor d) {
+    const unsigned v = x * wa + y * wb + d.half, t = __umulhi(d.m, v);
+    return (t + ((v - t) >> 1)) >> d.shift;
+}
+
+template <typename S>
+__device__ __forceinline__ unsigned mix_word(unsigned x, unsigned y, unsigned wa, unsigned wb, MixDivisor d) {          // 4 bytes, or 2 words
+    constexpr int B = 8 * (int)sizeof(S), C = 32 / B;
+    constexpr unsigned M = sizeof(S) == 1 ? 0xffu : 0xffffu;
+    unsigned o = 0;
+#pragma unroll
+    for (int i = 0; i < C; ++i) o |= mix_one((x >> (B * i)) & M, (y >> (B * i)) & M, wa, wb, d) << (B * i);
+    return o;
+}
+
+template <typename S>
+__global__ __launch_bounds__(MIX_LANES) void payload_mix_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
+                                                                unsigned char *out, long long stride_out, long long samples, int num0,
+                                                                int num_step, int den, MixDivisor d) {
+    constexpr int V = 16 / (int)sizeof(S);
+    constexpr long long SPAN = MIX_SPAN_BYTES / (long long)sizeof(S);
+    const int n = blockIdx.y;
+    const unsigned wb = (unsigned)(num0 + n * num_step), wa = (unsigned)den - wb;
+    const S *pa = reinterpret_cast<const S *>(a + n * stride_a), *pb = reinterpret_cast<const S *>(b + n * stride_b);
+    S *po = reinterpret_cast<S *>(out + n * stride_out);
+    const bool vec = ((reinterpret_cast<size_t>(pa) | reinterpret_cast<size_t>(pb) | reinterpret_cast<size_t>(po)) & 15) == 0;
+    const long long base = (long long)blockIdx.x * SPAN + threadIdx.x * V;
+#pragma unroll
+    for (int c = 0; c < MIX_CHUNKS; ++c) {
+        const long long o = base + (long long)c * MIX_LANES * V;
+        if (o >= samples) break;
+        if (vec && o + V <= samples) {
+            const i32x4 x = *reinterpret_cast<const i32x4 *>(pa + o), y = *reinterpret_cast<const i32x4 *>(pb + o);
+            i32x4 r;
+            r.x = (int)mix_word<S>((unsigned)x.x, (unsigned)y.x, wa, wb, d);
+            r.y = (int)mix_word<S>((unsigned)x.y, (unsigned)y.y, wa, wb, d);
+            r.z = (int)mix_word<S>((unsigned)x.z, (unsigned)y.z, wa, wb, d);
+            r.w = (int)mix_word<S>((unsigned)x.w, (unsigned)y.w, wa, wb, d);
+            *reinterpret_cast<i32x4 *>(po + o) = r;
+        } else {
+#pragma unroll
+            for (int i = 0; i < V; ++i)
+                if (o + i < samples) po[o + i] = (S)mix_one(pa[o + i], pb[o + i], wa, wb, d);
+        }
+    }
+}
+
 // first and one-past-last address, in bytes, of the floats a view of [n,c,h,w] names (strides of either sign)
 inline void view_range(const ssm_view &v, int n, int c, int h, int w, long long *lo, long long *hi) {
     long long a = 0, b = 0;
@@ -849,4 +1061,97 @@ extern "C" int ssm_plane_sse_fwd(const void *a, const void *b, long long stride_
         SSM_LAUNCH(plane_sse_kernel<unsigned short>, grid, dim3(SSE_LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b, luma, chroma,
                    (unsigned)g0, (unsigned)g1, sums);
     return ssm::check_launch("ssm_plane_sse_fwd");
+}
+
+// the windows of a plane of rows x cols samples along one axis: (samples >> 2) - 1 blocks' worth, 0 below 8 samples
+static long long ssim_windows(int samples) { return (samples >> 2) > 1 ? (samples >> 2) - 1 : 0; }
+
+extern "C" int ssm_plane_ssim_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int layout,
+                                  int sample_bytes, long long c1, long long c2, long long *sums, void *stream) {
+    SSM_REQUIRE(a && b && sums, "plane_ssim: null pointer");
+    SSM_REQUIRE(N > 0 && N <= 65535, "plane_ssim: N=%d outside 1..65535", N);
+    SSM_REQUIRE(H > 0 && W > 0, "plane_ssim: bad frame size %dx%d", H, W);
+    SSM_REQUIRE(layout >= SSM_YUV_420_CENTRED && layout <= SSM_YUV_422, "plane_ssim: layout %d not in {0, 1, 2, 3}", layout);
+    SSM_REQUIRE(sample_bytes == 1 || sample_bytes == 2, "plane_ssim: sample_bytes %d not in {1, 2}", sample_bytes);
+    SSM_REQUIRE(c1 > 0 && c2 > 0 && c1 <= (1ll << 40) && c2 <= (1ll << 40), "plane_ssim: c1=%lld, c2=%lld outside 1..2^40", c1, c2);
+    const long long frame = yuv_frame_samples(H, W, layout) * sample_bytes;
+    SSM_REQUIRE((stride_a == 0 || std::llabs(stride_a) >= frame) && (stride_b == 0 || std::llabs(stride_b) >= frame),
+                "plane_ssim: strides %lld (a), %lld (b) neither 0 nor at least the frame's %lld bytes", stride_a, stride_b, frame);
+    if (sample_bytes == 2) {
+        SSM_REQUIRE(reinterpret_cast<size_t>(a) % 2 == 0 && reinterpret_cast<size_t>(b) % 2 == 0,
+                    "plane_ssim: a payload of 2-byte samples (a or b) is not 2-byte aligned");
+        SSM_REQUIRE(stride_a % 2 == 0 && stride_b % 2 == 0, "plane_ssim: strides %lld (a), %lld (b) of 2-byte samples must be even", stride_a, stride_b);
+    }
+    SSM_REQUIRE(reinterpret_cast<size_t>(sums) % 8 == 0, "plane_ssim: sums is not 8-byte aligned");
+    const int cw = layout == SSM_YUV_444 ? W : (W + 1) / 2, ch = layout == SSM_YUV_420_CENTRED || layout == SSM_YUV_420_COSITED ? (H + 1) / 2 : H;
+    const long long tx0 = (ssim_windows(W) + SSIM_TW - 1) / SSIM_TW, ty0 = (ssim_windows(H) + SSIM_TH - 1) / SSIM_TH;
+    const long long tx1 = (ssim_windows(cw) + SSIM_TW - 1) / SSIM_TW, ty1 = (ssim_windows(ch) + SSIM_TH - 1) / SSIM_TH;
+    const long long g0 = tx0 * ty0, g1 = tx1 * ty1;
+    SSM_REQUIRE(g0 + 2 * g1 <= 2147483647ll, "plane_ssim: a frame of %lld bytes is more than the grid takes", frame);
+    const hipError_t e = ssm::memset_async(sums, 0, sizeof(long long) * 3 * (size_t)N, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        ssm::set_error("plane_ssim: memset failed: %s", hipGetErrorString(e));
+        return SSM_E_LAUNCH;
+    }
+    if (g0 + 2 * g1 == 0) return SSM_OK;          // no plane has a window: the cleared sums are the result
+    const unsigned char *pa = static_cast<const unsigned char *>(a), *pb = static_cast<const unsigned char *>(b);
+    unsigned long long *out = reinterpret_cast<unsigned long long *>(sums);
+    const dim3 grid((unsigned)(g0 + 2 * g1), N);
+    if (sample_bytes == 1)
+        SSM_LAUNCH(plane_ssim_kernel<unsigned char>, grid, dim3(SSIM_LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b, H, W, ch, cw,
+                   (unsigned)tx0, (unsigned)tx1, (unsigned)g0, (unsigned)g1, c1, c2, out);
+    else
+        SSM_LAUNCH(plane_ssim_kernel<unsigned short>, grid, dim3(SSIM_LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b, H, W, ch, cw,
+                   (unsigned)tx0, (unsigned)tx1, (unsigned)g0, (unsigned)g1, c1, c2, out);
+    return ssm::check_launch("ssm_plane_ssim_fwd");
+}
+
+// first and one-past-last byte address of N rows of `row` bytes, `stride` bytes apart (either sign, or 0)
+static void rows_range(const void *p, long long stride, int N, long long row, long long *lo, long long *hi) {
+    const long long base = (long long)reinterpret_cast<size_t>(p), ext = (long long)(N - 1) * stride;
+    *lo = base + (ext < 0 ? ext : 0);
+    *hi = base + (ext > 0 ? ext : 0) + row;
+}
+
+extern "C" int ssm_payload_mix_fwd(const void *a, const void *b, long long stride_a, long long stride_b, void *out, long long stride_out, int N,
+                                   long long samples, int sample_bytes, int num0, int num_step, int den, void *stream) {
+    SSM_REQUIRE(a && b && out, "payload_mix: null pointer");
+    SSM_REQUIRE(N > 0 && N <= 65535, "payload_mix: N=%d outside 1..65535", N);
+    SSM_REQUIRE(samples > 0, "payload_mix: samples=%lld must be positive", samples);
+    SSM_REQUIRE(sample_bytes == 1 || sample_bytes == 2, "payload_mix: sample_bytes %d not in {1, 2}", sample_bytes);
+    SSM_REQUIRE(den >= 2 && den <= 65535, "payload_mix: den=%d outside 2..65535", den);
+    const long long k_last = (long long)num0 + (long long)(N - 1) * num_step;
+    SSM_REQUIRE(num0 >= 0 && num0 <= den && k_last >= 0 && k_last <= den, "payload_mix: k = %d + n * %d leaves 0..den=%d within N=%d rows", num0,
+                num_step, den, N);
+    const long long row = samples * sample_bytes;
+    SSM_REQUIRE((stride_a == 0 || std::llabs(stride_a) >= row) && (stride_b == 0 || std::llabs(stride_b) >= row),
+                "payload_mix: strides %lld (a), %lld (b) neither 0 nor at least the row's %lld bytes", stride_a, stride_b, row);
+    SSM_REQUIRE(N == 1 || std::llabs(stride_out) >= row, "payload_mix: stride %lld (out) shorter than the row's %lld bytes", stride_out, row);
+    if (sample_bytes == 2) {
+        SSM_REQUIRE(reinterpret_cast<size_t>(a) % 2 == 0 && reinterpret_cast<size_t>(b) % 2 == 0 && reinterpret_cast<size_t>(out) % 2 == 0,
+                    "payload_mix: a row of 2-byte samples (a, b or out) is not 2-byte aligned");
+        SSM_REQUIRE(stride_a % 2 == 0 && stride_b % 2 == 0 && stride_out % 2 == 0,
+                    "payload_mix: strides %lld (a), %lld (b), %lld (out) of 2-byte samples must be even", stride_a, stride_b, stride_out);
+    }
+    long long o0, o1, a0, a1, b0, b1;
+    rows_range(out, stride_out, N, row, &o0, &o1);
+    rows_range(a, stride_a, N, row, &a0, &a1);
+    rows_range(b, stride_b, N, row, &b0, &b1);
+    SSM_REQUIRE((a1 <= o0 || o1 <= a0) && (b1 <= o0 || o1 <= b0), "payload_mix: out overlaps a or b");
+    const long long span = MIX_SPAN_BYTES / sample_bytes, groups = (samples + span - 1) / span;
+    SSM_REQUIRE(groups <= 2147483647ll, "payload_mix: a row of %lld bytes is more than the grid takes", row);
+    int l = 0;
+    while ((1ll << l) < den) ++l;          // ceil(log2 den) >= 1
+    MixDivisor d;
+    d.m = (unsigned)((((1ull << l) - (unsigned long long)den) << 32) / (unsigned long long)den + 1ull);
+    d.shift = (unsigned)(l - 1), d.half = (unsigned)(den >> 1);
+    const unsigned char *pa = static_cast<const unsigned char *>(a), *pb = static_cast<const unsigned char *>(b);
+    const dim3 grid((unsigned)groups, N);
+    if (sample_bytes == 1)
+        SSM_LAUNCH(payload_mix_kernel<unsigned char>, grid, dim3(MIX_LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b,
+                   static_cast<unsigned char *>(out), stride_out, samples, num0, num_step, den, d);
+    else
+        SSM_LAUNCH(payload_mix_kernel<unsigned short>, grid, dim3(MIX_LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b,
+                   static_cast<unsigned char *>(out), stride_out, samples, num0, num_step, den, d);
+    return ssm::check_launch("ssm_payload_mix_fwd");
 }

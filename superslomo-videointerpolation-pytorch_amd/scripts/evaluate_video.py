@@ -14,6 +14,12 @@ model that does not beat it on a clip is not interpolating.  PSNR is 10 log10(pe
 range, the convention of `ffmpeg -lavfi psnr`; frames and planes are pooled by their sums of squares, never by their dB.  The frames after
 the last kept one ((n - 1) mod HOLD of them) are read and not scored; their number is reported.
 
+--mix adds the baseline an interpolator really has to beat: the held-out frame against the cross-fade of its two kept frames at k / HOLD,
+which is what frame blending and every cheap rate converter writes (ssm_payload_mix_fwd, on the GPU).  --ssim adds, for every column, the
+SSIM of x264 and of ffmpeg's `ssim` filter (8 x 8 windows at stride 4, per plane; ssm_plane_ssim_fwd), pooled over frames and planes by
+window counts - `avg` is therefore not ffmpeg's plane-size weighted "All".  Both append to the table and to the --stats lines; without
+them the report is unchanged.
+
 --stats FILE writes one line per scored frame (n: the input frame's index, k: its place between the kept frames, t = k / HOLD), in the
 manner of the psnr filter's stats_file.  --output FILE writes the clip that interpolate_video.py would write for the decimated input:
 kept frames as their own bytes, synthesised frames between, at the input's rate.  The summary goes to --log and to stdout.
@@ -57,6 +63,9 @@ def getargs(argv=None):
     parser.add_argument("--hold", required=True, type=_hold, metavar="N",
                         help="Keep every N-th frame and score the N - 1 frames synthesised between two kept ones against the frames left out.")
     parser.add_argument("--stats", default=None, metavar="FILE", help="Write one line per scored frame to FILE.")
+    parser.add_argument("--ssim", action="store_true", help="Also report SSIM (8 x 8 windows at stride 4, per plane) for every column.")
+    parser.add_argument("--mix", action="store_true",
+                        help="Also score the cross-fade of the two kept frames against the held-out frame: the frame-blending baseline.")
     parser.add_argument("--output", default=None, help="Also write the interpolated decimated clip as .y4m (- for stdout). Default: frames are dropped.")
     parser.add_argument("--matrix", choices=sorted(V.MATRICES), default=None, help="Y'CbCr matrix (default: bt709 from 720 rows up, else bt601).")
     parser.add_argument("--range", choices=sorted(V.RANGES), default=None, dest="color_range",
@@ -85,7 +94,7 @@ def main(argv=None, model=None):
     crange = None if args.color_range is None else V.RANGES[args.color_range]
     model = (model if model is not None else ssm.FullModel(config)).cuda().eval()
     scorer = VS.HoldOutScorer(model, config, args.hold, matrix=matrix, color_range=crange, flow_scale=args.flow_scale, tile=args.tile,
-                              halo=args.halo, blend=args.blend)
+                              halo=args.halo, blend=args.blend, ssim=args.ssim, mix=args.mix)
     with V.Y4MReader(args.input, extended=True) as reader:
         out_range = crange if crange is not None else (reader.color_range if reader.color_range is not None else V.LIMITED)
         log.info("[%s] %s: %dx%d C%s at %d:%d frames/s, hold = %d -> %s", args.expt, args.input, reader.width, reader.height, reader.chroma,

@@ -15,11 +15,22 @@ clip's length.
                                payload against the held-out one: the codes the tool would write, after quantisation) and of `nearest` (the
                                held-out payload against the nearer kept frame's: the do-nothing baseline a model has to beat), per position
                                k and overall the PSNR of the pooled MSE, the worst frame
+  plane_ssim_host / plane_ssim   per frame pair and plane the SSIM of x264 and of ffmpeg's `ssim` filter (4 x 4 blocks, 8 x 8 windows at
+                               stride 4) as an exact integer: every window's quotient, one float64 division, is rounded to a multiple of
+                               2^-32 and the windows are summed in int64 - by numpy (the yardstick; include/ssm_hip.h has the definition)
+                               and by ssm_plane_ssim_fwd.  ssim_constants, plane_windows, ssim_value, ssim_db go with it.  Planes, frames
+                               and positions pool by sums and window counts: "avg" is pooled by WINDOWS, not ffmpeg's plane-size weighting
+  payload_mix_host / payload_mix   the cross-fade (a (den - k) + b k + den // 2) // den of two payloads, by numpy and by ssm_payload_mix_fwd
+  HoldOutScorer(ssim=True, mix=True)   `mix`: a third column, the held-out payload against the cross-fade of its two kept frames at
+                               k / hold - what frame blending, and every cheap rate converter, writes; on slow motion it beats `nearest`
+                               by several dB, so it is the baseline an interpolator has to beat.  `ssim`: the SSIM sums of every column
+                               that is on, beside its squared differences
 
 With the repository's synthetic weights the numbers say nothing about quality: they show that the instrument works.
 
-Out of scope: a frame-blend baseline, SSIM and VMAF, scoring the timeline and shutter modes (target_rate, speed, shutter) or scene cuts -
-none has a held-out counterpart on the fixed grid -, the recurrent configuration.
+Out of scope: VMAF, ffmpeg's plane-size weighting for the SSIM of "All", scoring the timeline and shutter modes (target_rate, speed,
+shutter) or scene cuts - none has a held-out counterpart on the fixed grid -, the recurrent configuration.  Open: the fixed cost of the
+clear-plus-kernel pair that every sum call queues.
 """
 import functools
 import math
@@ -100,6 +111,151 @@ def psnr_avg(sse3, samples3, bits):
     return psnr(sum(int(s) for s in sse3), sum(int(s) for s in samples3), bits)
 
 
+# ---- SSIM in fixed point ----------------------------------------------------------------------------------------------------------------
+SSIM_ONE = 1 << 32          # fx of a window whose quotient is 1
+
+
+def ssim_constants(bits):
+    """(c1, c2) = (floor(.01^2 peak^2 64 + .5), floor(.03^2 peak^2 64 63 + .5)) with peak = 2^bits - 1, in exact integer arithmetic: x264's
+    ssim_c1 and ssim_c2 (416 and 235963 at 8 bits).  The one function behind the yardstick and the device call."""
+    V.sample_bytes(bits)
+    peak2 = ((1 << int(bits)) - 1) ** 2
+    return (2 * 64 * peak2 + 10000) // 20000, (2 * 9 * 64 * 63 * peak2 + 10000) // 20000
+
+
+def _windows(rows, cols):
+    return max(0, (rows >> 2) - 1) * max(0, (cols >> 2) - 1)
+
+
+def plane_windows(h, w, siting):
+    """(windows of Y, of U, of V) of one frame: max(0, (cols >> 2) - 1) max(0, (rows >> 2) - 1) of each plane."""
+    ch, cw = V.chroma_dims(h, w, siting)
+    return _windows(h, w), _windows(ch, cw), _windows(ch, cw)
+
+
+def _block_sums(x):
+    """[n, rows, cols] int64 -> [n, rows >> 2, cols >> 2]: the sums of the 4 x 4 blocks; trailing rows and columns belong to none."""
+    n, rows, cols = x.shape
+    by, bx = rows >> 2, cols >> 2
+    return x[:, :4 * by, :4 * bx].reshape(n, by, 4, bx, 4).sum(axis=(2, 4))
+
+
+def _window_sums(s):
+    """Block sums -> the sums of the 2 x 2 blocks of every window, at stride one block."""
+    return s[:, :-1, :-1] + s[:, :-1, 1:] + s[:, 1:, :-1] + s[:, 1:, 1:]
+
+
+def plane_ssim_host(payload_a, payload_b, h, w, siting, bits=8):
+    """Yardstick of ssm_plane_ssim_fwd (include/ssm_hip.h has the definition): payloads as for plane_sse_host -> int64 [N,3], out[n][p] =
+    the sum over the windows of plane p of fx = rint(q 2^32), q = (double(f0) double(f1)) / (double(f2) double(f3)).  The factors are
+    int64 throughout (below 2^45 at 16 bits); the three float64 operations and the scaling are numpy's, one rounding each; np.rint rounds
+    half to even.  A plane without a window gives 0."""
+    fb = V.frame_bytes(h, w, siting, bits)
+    a = np.ascontiguousarray(payload_a).reshape(-1, fb)
+    b = np.ascontiguousarray(payload_b).reshape(-1, fb)
+    assert a.dtype == np.uint8 and b.dtype == np.uint8
+    n = max(a.shape[0], b.shape[0])
+    assert a.shape[0] in (1, n) and b.shape[0] in (1, n), "as many payloads in a as in b, or one"
+    c1, c2 = (np.int64(c) for c in ssim_constants(bits))
+    out = np.zeros((n, 3), dtype=np.int64)
+    for p, (pa, pb) in enumerate(zip(V.split_planes(a, h, w, siting, bits), V.split_planes(b, h, w, siting, bits))):
+        if _windows(pa.shape[1], pa.shape[2]) == 0:
+            continue
+        x, y = pa.astype(np.int64), pb.astype(np.int64)
+        s1, s2 = _window_sums(_block_sums(x)), _window_sums(_block_sums(y))                 # [n | 1, wy, wx], broadcast over n below
+        ss = _window_sums(_block_sums(x * x)) + _window_sums(_block_sums(y * y))
+        s12 = _window_sums(_block_sums(x * y))
+        var = 64 * ss - s1 * s1 - s2 * s2
+        covar = 64 * s12 - s1 * s2
+        f0, f1, f2, f3 = 2 * s1 * s2 + c1, 2 * covar + c2, s1 * s1 + s2 * s2 + c1, var + c2
+        q = (f0.astype(np.float64) * f1.astype(np.float64)) / (f2.astype(np.float64) * f3.astype(np.float64))
+        fx = np.rint(q * np.float64(SSIM_ONE)).astype(np.int64)
+        out[:, p] = np.broadcast_to(fx, (n,) + fx.shape[1:]).reshape(n, -1).sum(axis=1)
+    return out
+
+
+def plane_ssim(payload_a, payload_b, h, w, siting, bits=8, out=None):
+    """ssm_plane_ssim_fwd on payloads, shaped like plane_sse -> int64 [N,3] on the device (into `out` if given): signed sums of fx."""
+    fb = V.frame_bytes(h, w, siting, bits)
+    for t in (payload_a, payload_b):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.shape[1] >= fb and (t.shape[1] == 1 or t.stride(1) == 1), \
+            "payloads must be [N, at least frame_bytes] uint8 tensors on the GPU with unit stride within a frame"
+    n = payload_a.shape[0]
+    assert payload_b.shape[0] == n and payload_b.device == payload_a.device, "as many frames in a as in b, on one device"
+    if out is None:
+        out = torch.empty(n, 3, dtype=torch.int64, device=payload_a.device)
+    assert out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == (n, 3) and out.is_contiguous()
+    sa, sb = (t.stride(0) if n > 1 else 0 for t in (payload_a, payload_b))
+    c1, c2 = ssim_constants(bits)
+    hb.check(hb.load().ssm_plane_ssim_fwd(payload_a.data_ptr(), payload_b.data_ptr(), sa, sb, n, h, w, siting, V.sample_bytes(bits), c1, c2,
+                                          out.data_ptr(), hb.stream_ptr()))
+    return out
+
+
+def ssim_value(total, count):
+    """The SSIM of `count` windows whose fx sum to `total`: total / (2^32 count) in float64; nan where there is no window."""
+    total, count = int(total), int(count)
+    assert count >= 0
+    return math.nan if count == 0 else total / (SSIM_ONE * count)          # Python's int / int: the correctly rounded quotient
+
+
+def ssim_db(ssim):
+    """-10 log10(1 - ssim), ffmpeg's dB of an SSIM; inf at 1."""
+    return math.inf if ssim >= 1.0 else -10.0 * math.log10(1.0 - ssim)
+
+
+# ---- the cross-fade ---------------------------------------------------------------------------------------------------------------------
+def mix_divisor(den):
+    """(m, shift) of the kernel's division by den (Granlund and Montgomery): with l = ceil(log2 den), m = floor(2^32 (2^l - den) / den) + 1
+    and shift = l - 1;  x // den = (t + ((x - t) >> 1)) >> shift  with t = (m x) >> 32, for every x below 2^32."""
+    den = int(den)
+    assert 2 <= den <= 65535
+    l = (den - 1).bit_length()
+    return (((1 << l) - den) << 32) // den + 1, l - 1
+
+
+def mix_divide(x, den):
+    """The kernel's quotient of numpy uint64 numerators below 2^32 by den: mix_divisor's pair applied as the kernel applies it."""
+    m, shift = mix_divisor(den)
+    x = np.asarray(x, dtype=np.uint64)
+    t = (np.uint64(m) * x) >> np.uint64(32)
+    return (t + ((x - t) >> np.uint64(1))) >> np.uint64(shift)
+
+
+def payload_mix_host(payload_a, payload_b, n, num0, num_step, den, bits=8):
+    """Yardstick of ssm_payload_mix_fwd: [n | 1, row bytes] uint8 payloads -> [n, row bytes] uint8, row i = (a (den - k) + b k + den // 2)
+    // den with k = num0 + i num_step over the samples (bytes, or little-endian words above 8 bits), in int64 with numpy's floor division."""
+    a, b = np.ascontiguousarray(payload_a), np.ascontiguousarray(payload_b)
+    assert a.dtype == np.uint8 and b.dtype == np.uint8 and a.ndim == 2 and b.ndim == 2 and a.shape[1] == b.shape[1]
+    assert a.shape[0] in (1, n) and b.shape[0] in (1, n) and 2 <= den <= 65535
+    dt = np.uint8 if V.sample_bytes(bits) == 1 else "<u2"
+    k = (num0 + num_step * np.arange(n, dtype=np.int64))[:, None]
+    assert k.min() >= 0 and k.max() <= den
+    x, y = a.view(dt).astype(np.int64), b.view(dt).astype(np.int64)
+    return np.ascontiguousarray(((x * (den - k) + y * k + den // 2) // den).astype(dt)).view(np.uint8).reshape(n, -1)
+
+
+def payload_mix(payload_a, payload_b, num0, num_step, den, bits=8, out=None, samples=None):
+    """ssm_payload_mix_fwd: [N, L] uint8 device tensors with unit stride within a row and any row stride (0: one payload for every row) ->
+    `out` [N, at least L] (made if None); `samples`: how many samples of a row are mixed (default: all L bytes of it)."""
+    sb = V.sample_bytes(bits)
+    n, length = payload_a.shape
+    for t in (payload_a, payload_b):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and tuple(t.shape) == (n, length) and (length == 1 or t.stride(1) == 1)
+    if samples is None:
+        assert length % sb == 0
+        samples = length // sb
+    assert 0 < samples * sb <= length
+    if out is None:
+        out = torch.empty(n, length, dtype=torch.uint8, device=payload_a.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == n and out.shape[1] >= samples * sb
+    assert out.shape[1] == 1 or out.stride(1) == 1
+    sa, sb_, so = (t.stride(0) if n > 1 else 0 for t in (payload_a, payload_b, out))
+    hb.check(hb.load().ssm_payload_mix_fwd(payload_a.data_ptr(), payload_b.data_ptr(), sa, sb_, out.data_ptr(), so, n, samples, sb, num0, num_step,
+                                           den, hb.stream_ptr()))
+    return out
+
+
 # ---- which frames -----------------------------------------------------------------------------------------------------------------------
 def hold_out_plan(n, hold):
     """(kept, held, trailing) of an n-frame clip: the kept frames 0, hold, 2 hold, ... below n; the held-out frames, every one strictly
@@ -121,13 +277,31 @@ def nearest_split(hold):
 class HoldOutResult:
     """What HoldOutScorer.run() returns.  frames: [(i, k, sse_model (y, u, v), sse_nearest (y, u, v))] of every scored frame, Python ints,
     in clip order; frames_read, kept, trailing (frames after the last kept one: read, not scored), written (frames handed to the writer,
-    or dropped without one); samples: (Y, U, V) of a frame; hold, bits."""
+    or dropped without one); samples: (Y, U, V) of a frame; hold, bits.
+
+    With HoldOutScorer(ssim=True) and / or (mix=True) - the flags `ssim` and `mix` here - the rows of `frames` keep their four fields and
+    `more`, a list parallel to `frames`, holds the further sums of each scored frame by metric and column:
+    more[j] = {"sse": {"mix": (y, u, v)}, "ssim": {"model": (y, u, v), "nearest": ..., "mix": ...}}, only the metrics and columns that
+    are on.  SSIM sums are the signed fixed-point sums of plane_ssim_host over `windows`, the (Y, U, V) window counts of a frame."""
 
     PLANES = ("y", "u", "v", "avg")
 
-    def __init__(self, hold, bits, samples):
+    def __init__(self, hold, bits, samples, windows=(0, 0, 0), ssim=False, mix=False):
         self.hold, self.bits, self.samples = hold, bits, tuple(samples)
+        self.windows, self.ssim, self.mix = tuple(windows), bool(ssim), bool(mix)
         self.frames, self.frames_read, self.kept, self.trailing, self.written = [], 0, 0, 0, 0
+        self.more = []
+
+    @property
+    def columns(self):
+        """The columns that are on, in report order."""
+        return ("model", "nearest") + (("mix",) if self.mix else ())
+
+    def _ssim4(self, rows, col):
+        """{y, u, v, avg} of the SSIM of column `col` pooled over the rows of `more`: sums over sums of window counts."""
+        tot = [sum(m["ssim"][col][p] for m in rows) for p in range(3)]
+        cnt = [c * len(rows) for c in self.windows]
+        return dict(zip(self.PLANES, [ssim_value(tot[p], cnt[p]) for p in range(3)] + [ssim_value(sum(tot), sum(cnt))]))
 
     @property
     def scored(self):
@@ -144,6 +318,13 @@ class HoldOutResult:
             sse = [sum(f[col][p] for f in rows) for p in range(3)]
             smp = [s * len(rows) for s in self.samples]
             out[name] = dict(zip(self.PLANES, [psnr(sse[p], smp[p], self.bits) for p in range(3)] + [psnr_avg(sse, smp, self.bits)]))
+        if self.mix or self.ssim:          # "mix": the PSNR of the third column; "ssim": {column: {y, u, v, avg}}, pooled by windows
+            more = [m for f, m in zip(self.frames, self.more) if k is None or f[1] == k]
+            if self.mix:
+                sse = [sum(m["sse"]["mix"][p] for m in more) for p in range(3)]
+                out["mix"] = dict(zip(self.PLANES, [psnr(sse[p], smp[p], self.bits) for p in range(3)] + [psnr_avg(sse, smp, self.bits)]))
+            if self.ssim:
+                out["ssim"] = {col: self._ssim4(more, col) for col in self.columns}
         return out
 
     def worst(self):
@@ -159,6 +340,14 @@ class HoldOutResult:
             lines.append("n:%d k:%d mse_y %.6f psnr_y %.4f psnr_u %.4f psnr_v %.4f psnr_avg %.4f nearest_psnr_y %.4f" % (
                 i, k, m[0] / self.samples[0], psnr(m[0], self.samples[0], self.bits), psnr(m[1], self.samples[1], self.bits),
                 psnr(m[2], self.samples[2], self.bits), psnr_avg(m, self.samples, self.bits), psnr(nr[0], self.samples[0], self.bits)))
+        for j, more in enumerate(self.more if self.mix or self.ssim else ()):          # further fields, appended
+            if self.mix:
+                lines[j] += " mix_psnr_y %.4f mix_psnr_avg %.4f" % (psnr(more["sse"]["mix"][0], self.samples[0], self.bits),
+                                                                   psnr_avg(more["sse"]["mix"], self.samples, self.bits))
+            if self.ssim:
+                s4 = {col: self._ssim4([more], col) for col in self.columns}
+                lines[j] += " ssim_y %.6f ssim_u %.6f ssim_v %.6f ssim_avg %.6f" % tuple(s4["model"][p] for p in self.PLANES)
+                lines[j] += "".join(" %s_ssim_y %.6f" % (col, s4[col]["y"]) for col in self.columns[1:])
         return lines
 
     def table(self):
@@ -180,6 +369,23 @@ class HoldOutResult:
                                                 " ".join("%8.3f" % r["nearest"][p] for p in self.PLANES)))
         db, i = self.worst()
         lines.append("worst frame: PSNR-Y %.3f dB at input frame %d" % (db, i))
+        if self.mix or self.ssim:          # further blocks, appended: the lines above are the default table's
+            keys = [(k, self.pooled(k)) for k in list(range(1, self.hold)) + [None]]
+            keys = [("all" if k is None else "%d/%d" % (k, self.hold), r) for k, r in keys if r is not None]
+        if self.mix:
+            lines.append("mix: the held-out frame against the cross-fade of its two kept frames at k / hold (PSNR in dB of the pooled MSE)")
+            lines.append("%-6s %6s | %8s %8s %8s %8s" % (("k", "frames") + tuple("mix_" + p for p in self.PLANES)))
+            lines += ["%-6s %6d | %s" % (name, r["frames"], " ".join("%8.3f" % r["mix"][p] for p in self.PLANES)) for name, r in keys]
+        if self.ssim:
+            short = {"model": "model_", "nearest": "near_", "mix": "mix_"}
+            lines.append("SSIM (8 x 8 windows at stride 4, as x264 and ffmpeg's ssim filter; sums pooled by windows - `avg` is not ffmpeg's "
+                         "plane-size weighting; %d + %d + %d windows a frame)" % self.windows)
+            lines.append("%-6s %6s | %s" % ("k", "frames", " | ".join(" ".join("%10s" % (short[c] + p) for p in self.PLANES) for c in self.columns)))
+            lines += ["%-6s %6d | %s" % (name, r["frames"], " | ".join(" ".join("%10.6f" % r["ssim"][c][p] for p in self.PLANES)
+                                                                           for c in self.columns)) for name, r in keys]
+            allr = keys[-1][1]["ssim"]
+            lines.append("SSIM of all frames in dB, -10 log10(1 - ssim): " + ", ".join(
+                "%s Y %.3f avg %.3f" % (c, ssim_db(allr[c]["y"]), ssim_db(allr[c]["avg"])) for c in self.columns))
         return "\n".join(lines)
 
 
@@ -199,28 +405,39 @@ class HoldOutScorer:
     as the scene cuts' do, and the writer thread turns them into the result's rows.  Nothing synchronises the host inside the loop but
     the ring.  Host and device memory are fixed by the frame size, hold, n_streams and pairs_per_batch.
 
+    mix=True adds the column `mix`: per group one ssm_payload_mix_fwd call - N = hold - 1 rows, both kept payloads at stride 0, k = 1 ..
+    hold - 1 over den = hold - into a per-stream buffer of the held-out payloads' shape, then one ssm_plane_sse_fwd call over the pass
+    against the held-out payloads.  ssim=True adds one ssm_plane_ssim_fwd call beside every ssm_plane_sse_fwd call, over the same operands,
+    for every column that is on.  With both off the loop queues what it queued before they existed, launch for launch.
+
     The left kept payload of a pass's first pair is carried on the device the way the scene cuts carry their luma row: row 0 in front of a
-    stream's kept payloads, written by the pass before into the NEXT stream's buffer.  That is why the `nearest` calls sit ahead of
+    stream's kept payloads, written by the pass before into the NEXT stream's buffer.  That is why the `nearest` and `mix` calls - both read row 0 - sit ahead of
     `ingested` and not behind the egress: the pass that writes row 0 does so after its own calls and before it records `ingested`, the
     pass that reads it waits for that event, and the pass that read the row before recorded its own event - after its calls - earlier in
-    the chain of waits.  They need nothing that the engine makes."""
+    the chain of waits.  They need nothing that the engine makes.  The model's SSIM call sits beside the model's squared differences, after
+    the egress.  (`blend` is the tiles' seam width, which is why the baseline is called `mix`.)"""
 
     def __init__(self, model, cfg, hold, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1, tile=None, halo=256,
-                 blend=32):
+                 blend=32, ssim=False, mix=False):
         hold_out_plan(0, hold)          # refuses a bad hold by name
         self.hold = int(hold)
+        self.ssim, self.mix = bool(ssim), bool(mix)
         self.vi = V.VideoInterpolator(model, cfg, upsample_rate=self.hold, n_streams=n_streams, pairs_per_batch=pairs_per_batch,
                                       matrix=matrix, color_range=color_range, flow_scale=flow_scale, tile=tile, halo=halo, blend=blend)
 
     @torch.no_grad()
-    def run(self, reader, writer=None, on_frame=None):
+    def run(self, reader, writer=None, on_frame=None, on_scores=None):
         """Scores the clip and returns a HoldOutResult.  writer: a Y4MWriter of the reader's format, or None to drop the frames;
-        on_frame(i, k, sse_model, sse_nearest): called on the writer thread for every scored frame as its pass completes, in clip order."""
+        on_frame(i, k, sse_model, sse_nearest): called on the writer thread for every scored frame as its pass completes, in clip order;
+        on_scores(i, k, more): with ssim or mix on, called right after it with the frame's entry of HoldOutResult.more."""
         from .evaluation import t_values
         vi, hold = self.vi, self.hold
         clip = vi._clip(reader, reader if writer is None else writer)
         h, w, siting, bits = reader.height, reader.width, reader.siting, getattr(reader, "bits", 8)
-        res = HoldOutResult(hold, bits, plane_samples(h, w, siting))
+        ssim, mix = self.ssim, self.mix
+        res = HoldOutResult(hold, bits, plane_samples(h, w, siting), plane_windows(h, w, siting), ssim, mix)
+        cols = 3 if mix else 2          # rows of the sums: sse of model, nearest[, mix], then ssim of the same columns
+        names = ("model", "nearest", "mix")[:cols]
         fb, dev, hp, wp = clip.fb, clip.dev, clip.hp, clip.wp
         pipe = vi._pipeline(hp, wp, dev)
         n, pb, nt, nl = pipe.n, vi.pb, hold - 1, nearest_split(hold)
@@ -229,11 +446,13 @@ class HoldOutScorer:
         host_in, host_out, _, np_in, np_out, _, done = V.ring_slots(depth, fb, pb, pb * nt)
         host_held = [torch.empty(pb * nt, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)]
         np_held = [t.numpy() for t in host_held]
-        host_sums = [torch.empty(2, pb * nt, 3, dtype=torch.int64).pin_memory() for _ in range(depth)]          # [model | nearest]
-        np_sums = [t.numpy().view(np.uint64) for t in host_sums]
+        host_sums = [torch.empty(cols * (2 if ssim else 1), pb * nt, 3, dtype=torch.int64).pin_memory() for _ in range(depth)]
+        np_sums = [t.numpy().view(np.uint64) for t in host_sums]          # [model | nearest]: squared differences are unsigned
+        np_signed = [t.numpy() for t in host_sums]                        # the SSIM rows are signed
         dev_in, dev_out, _, ingested = V.stream_buffers(n, dev, fb, 1 + pb, pb * nt)          # row 0: the carried left kept payload
         dev_held = [torch.empty(pb * nt, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
-        dev_sums = [torch.zeros(2, pb * nt, 3, dtype=torch.int64, device=dev) for _ in range(n)]
+        dev_sums = [torch.zeros(cols * (2 if ssim else 1), pb * nt, 3, dtype=torch.int64, device=dev) for _ in range(n)]
+        dev_mix = [torch.empty(pb * nt, fb, dtype=torch.uint8, device=dev) for _ in range(n)] if mix else None
         planes = [torch.empty(pb + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]
         first = torch.empty(1, fb, dtype=torch.uint8).pin_memory()
         if not reader.read_frame_into(first.numpy()[0]):
@@ -250,6 +469,15 @@ class HoldOutScorer:
                     res.frames.append(row)
                     if on_frame is not None:
                         on_frame(*row)
+                    if ssim or mix:
+                        more = {}
+                        if mix:
+                            more["sse"] = {"mix": tuple(int(x) for x in np_sums[r][2, o])}
+                        if ssim:
+                            more["ssim"] = {c: tuple(int(x) for x in np_signed[r][cols + ci, o]) for ci, c in enumerate(names)}
+                        res.more.append(more)
+                        if on_scores is not None:
+                            on_scores(row[0], row[1], more)
             for kind, row in V.pass_order(valid, nt):
                 yield np_out[r][row] if kind == "interp" else np_in[r][row]
 
@@ -296,6 +524,16 @@ class HoldOutScorer:
                         lo, hi = max(0, (q - 1) * nt + nl), min(m, q * nt + nl)
                         if hi > lo:
                             plane_sse(dev_held[k][lo:hi], dev_in[k][q:q + 1].expand(hi - lo, fb), h, w, siting, bits, out=dev_sums[k][1, lo:hi])
+                            if ssim:
+                                plane_ssim(dev_held[k][lo:hi], dev_in[k][q:q + 1].expand(hi - lo, fb), h, w, siting, bits,
+                                           out=dev_sums[k][cols + 1, lo:hi])
+                    if mix:
+                        for q in range(valid):          # group q: kept rows q (left) and q + 1 (right) of dev_in[k], k = 1 .. hold - 1
+                            payload_mix(dev_in[k][q:q + 1].expand(nt, fb), dev_in[k][q + 1:q + 2].expand(nt, fb), 1, 1, hold, bits,
+                                        out=dev_mix[k][q * nt:(q + 1) * nt])
+                        plane_sse(dev_mix[k][:m], dev_held[k][:m], h, w, siting, bits, out=dev_sums[k][2, :m])
+                        if ssim:
+                            plane_ssim(dev_mix[k][:m], dev_held[k][:m], h, w, siting, bits, out=dev_sums[k][cols + 2, :m])
                     dev_in[(j + 1) % n][0].copy_(dev_in[k][pb])
                     ingested[k].record()
                     x = planes[k]
@@ -304,6 +542,8 @@ class HoldOutScorer:
                     clip.egress(frames, dev_out[k])
                     host_out[r].copy_(dev_out[k], non_blocking=True)
                     plane_sse(dev_out[k][:m], dev_held[k][:m], h, w, siting, bits, out=dev_sums[k][0, :m])
+                    if ssim:
+                        plane_ssim(dev_out[k][:m], dev_held[k][:m], h, w, siting, bits, out=dev_sums[k][cols, :m])
                     host_sums[r].copy_(dev_sums[k], non_blocking=True)
                     done[r].record()
                 ring.hand(r, done[r], functools.partial(rows_of, r, valid, (res.kept - 1) - valid))
