@@ -17,18 +17,23 @@
 //                            sum of the coded values as they are, or the sum taken in light - every value denormalised, clamped to [0, 1]
 //                            and decoded by one of the light curves of ssm_amd.video.light_curve before it is added, the mean encoded and
 //                            normalised again by the call that closes an output; the power is v_log_f32, a multiply and v_exp_f32
-//   luma_sad_kernel          scene cuts of the streamed loop: per frame pair the exact sum of |a - b| over the 8-bit Y planes;
-//                            one lane = 16 consecutive bytes of each plane (one 16-byte load per operand), or byte loads where a plane
-//                            does not start on a 16-byte boundary; v_sad_u8 into a 32-bit lane sum, shuffles, one 64-bit atomic per workgroup
-//   plane_sse_kernel         hold-out scoring of the streamed loop: per frame pair and plane (Y, U, V) the exact sum of (a - b)^2
-//                            over the samples as they stand in the payloads, 8-bit or 16-bit; a workgroup sums 16 KiB of ONE plane, a lane 4
-//                            pieces of 16 bytes per operand (sample by sample where a plane does not start on a 16-byte boundary);
-//                            bytes through v_dot4_u32_u8 into 32-bit lane sums, words into 64-bit ones; one 64-bit atomic per workgroup
+//   span_sum_kernel          the sums over pairs of payloads, one kernel under two entry points: per pair and plane the exact sum of a
+//                            lane accumulator's term over the samples as they stand in the payloads.  A workgroup sums SPAN_BYTES = 16 KiB of
+//                            ONE plane, a lane CHUNKS = 4 pieces of 16 bytes per operand (one 16-byte load each; sample by sample where a
+//                            plane does not start on a 16-byte boundary and at a plane's ragged end); workgroup_add closes it: shuffles, LDS
+//                            partials, one 64-bit atomic per workgroup.  PlaneOf turns the grid's x index into (plane, workgroup within it).
+//                              SadLane      scene cuts, ssm_luma_sad_fwd: |a - b| over the 8-bit Y plane alone (one plane per payload), four
+//                                           bytes per v_sad_u8 into a 32-bit lane sum
+//                              SseLane<S>   hold-out scoring, ssm_plane_sse_fwd: (a - b)^2 over Y, U and V, 8-bit or 16-bit; bytes through
+//                                           v_dot4_u32_u8 into 32-bit lane sums, words into 64-bit ones
 //   plane_ssim_kernel        hold-out scoring: per frame pair and plane the SSIM of x264 / ffmpeg's ssim filter in fixed point - 4 x 4 block
 //                            sums (bytes through v_dot4_u32_u8) to LDS, 8 x 8 windows at stride 4 from four blocks, integer factors, one
 //                            float64 quotient per window rounded to a multiple of 2^-32, signed 64-bit sums; a workgroup owns 31 x 15 windows
+//                            of one plane (PlaneOf) and ends in workgroup_add
 //   payload_mix_kernel       hold-out scoring: the cross-fade (a (den - k) + b k + den / 2) / den of two payloads, the frame-blend baseline;
-//                            exact division by multiply-shift, 16-byte loads and stores where the rows allow it
+//                            exact division by multiply-shift, the span walk's pieces with a 16-byte store in place of the sum
+// On the host the four pair entry points share pair_given and check_pair (operands, strides, alignment), grid_fits and clear_sums; yuv_planes is the one
+// place that knows the plane sizes of 4:2:0, 4:2:2 and 4:4:4, with_layout and with_sample pick a kernel's two template parameters.
 // Both conversions are HBM-bound (1.5 to 6 B in + 12 B out per pixel, and the reverse); so is the accumulation (4 (N + 1 + !init) B per
 // element), the luma difference (2 B per pixel) and the squared differences (2 B per pair of samples).  The chroma siting enters as four horizontal weights (ingest) or one switch (egress); matrix and range enter as one row of
 // the constant table built by ssm_amd/video.py, which the host yardsticks read too.  Inputs of the egress kernel are finite.
@@ -396,97 +401,77 @@ __global__ __launch_bounds__(256) void frames_accumulate_kernel(ssm_view src, ss
     *reinterpret_cast<Px<V> *>(a) = v;
 }
 
-// ---- scene cuts: luma differences summed ---------------------------------------------------------------------------------------------
-// sums[n] += sum over this workgroup's span of |a_n[i] - b_n[i]|, i over the H * W bytes of plane n.  A lane takes SAD_CHUNKS pieces of 16
-// bytes, SAD_LANES * 16 bytes apart (a wave's loads are contiguous); four bytes go through one v_sad_u8 (sum of the four absolute byte
-// differences, added to the accumulator operand).  A workgroup spans SAD_SPAN = 16 KiB of a plane: its sum is at most 255 * SAD_SPAN
-// < 2^22, so lane sums, wave sums and the workgroup's sum all fit 32 bits.  The 16-byte loads need both plane starts on 16-byte
-// boundaries (the pieces then are too): decided per plane, uniform over the workgroup; any other plane, and the last piece of a plane
-// whose size is no multiple of 16, goes byte by byte, bytes past the plane's end read as 0 on both sides (never loaded).
-constexpr int SAD_LANES = 256, SAD_CHUNKS = 4;
-constexpr long long SAD_SPAN = (long long)SAD_LANES * 16 * SAD_CHUNKS;
-static_assert(255 * SAD_SPAN < (1ll << 32), "a workgroup's sum fits 32 bits");
+// ---- sums over pairs of payloads: what the kernels share -------------------------------------------------------------------------------
+// A workgroup of LANES lanes takes a span of SPAN_BYTES = 16 KiB of one plane (span_sum_kernel) or row (payload_mix_kernel): a lane CHUNKS
+// pieces of 16 bytes, LANES * 16 bytes apart (a wave's loads are contiguous).  The bounds that keep the 8-bit sums in 32 bits:
+//   |a - b|    a workgroup's sum is at most 255 * SPAN_BYTES < 2^22, so lane sums, wave sums and the workgroup's sum fit
+//   (a - b)^2  summed over four packed bytes as a.a + b.b - 2 a.b (SseLane): a lane sees 16 * CHUNKS samples, a.a + b.b <= 2 * 65025 * 64
+//              < 2^24; a workgroup's sum is at most 65025 * 16384 < 2^30
+constexpr int LANES = 256, CHUNKS = 4;
+constexpr long long SPAN_BYTES = (long long)LANES * 16 * CHUNKS;
+static_assert(255 * SPAN_BYTES < (1ll << 32), "a workgroup's sum of absolute byte differences fits 32 bits");
+static_assert(2ll * 65025 * 16 * CHUNKS < (1ll << 32), "a lane's sums of 8-bit products fit 32 bits");
+static_assert(65025ll * SPAN_BYTES < (1ll << 32), "a workgroup's sum of 8-bit squares fits 32 bits");
 
-__device__ __forceinline__ unsigned bytes4(const unsigned char *p, long long left) {          // up to four bytes at p, `left` of them exist
-    unsigned v = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        if (i < left) v |= (unsigned)p[i] << (8 * i);
-    return v;
-}
-
-__device__ __forceinline__ unsigned sad16(i32x4 x, i32x4 y, unsigned s) {
-    s = __builtin_amdgcn_sad_u8((unsigned)x.x, (unsigned)y.x, s);
-    s = __builtin_amdgcn_sad_u8((unsigned)x.y, (unsigned)y.y, s);
-    s = __builtin_amdgcn_sad_u8((unsigned)x.z, (unsigned)y.z, s);
-    return __builtin_amdgcn_sad_u8((unsigned)x.w, (unsigned)y.w, s);
-}
-
-__global__ __launch_bounds__(SAD_LANES) void luma_sad_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
-                                                             long long plane, unsigned long long *sums) {          // a, b may alias
-    __shared__ unsigned partial[SAD_LANES / 64];
-    const int n = blockIdx.y;
-    const unsigned char *pa = a + n * stride_a, *pb = b + n * stride_b;
-    const bool vec = ((reinterpret_cast<size_t>(pa) | reinterpret_cast<size_t>(pb)) & 15) == 0;
-    const long long base = blockIdx.x * SAD_SPAN + threadIdx.x * 16;
-    unsigned s = 0;
-    if (vec && (blockIdx.x + 1) * SAD_SPAN <= plane) {          // the whole span lies inside the plane: all loads first, none guarded
-        i32x4 va[SAD_CHUNKS], vb[SAD_CHUNKS];
-#pragma unroll
-        for (int c = 0; c < SAD_CHUNKS; ++c) {
-            va[c] = *reinterpret_cast<const i32x4 *>(pa + base + (long long)c * SAD_LANES * 16);
-            vb[c] = *reinterpret_cast<const i32x4 *>(pb + base + (long long)c * SAD_LANES * 16);
-        }
-#pragma unroll
-        for (int c = 0; c < SAD_CHUNKS; ++c) s = sad16(va[c], vb[c], s);
-    } else {
-#pragma unroll
-        for (int c = 0; c < SAD_CHUNKS; ++c) {
-            const long long o = base + (long long)c * SAD_LANES * 16;
-            if (o >= plane) break;
-            if (vec && o + 16 <= plane) {
-                s = sad16(*reinterpret_cast<const i32x4 *>(pa + o), *reinterpret_cast<const i32x4 *>(pb + o), s);
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const long long left = plane - (o + 4 * q);          // <= 0: the piece ends before this word
-                    s = __builtin_amdgcn_sad_u8(bytes4(pa + o + 4 * q, left), bytes4(pb + o + 4 * q, left), s);
-                }
-            }
-        }
-    }
+// *dst += the sum of lane_sum over the workgroup's LANES lanes: the 64 lanes of a wave by shuffles, the waves' partials through LDS, then
+// ONE 64-bit vector atomic, issued by lane 0.  Integer adds commute: the total is the same in every run.  Every lane of the workgroup
+// calls it (there is a barrier inside), once per kernel.
+template <typename Sum>
+__device__ __forceinline__ void workgroup_add(Sum s, unsigned long long *dst) {
+    __shared__ Sum partial[LANES / 64];
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
     if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
-        unsigned t = 0;
+        Sum t = 0;
 #pragma unroll
-        for (int w = 0; w < SAD_LANES / 64; ++w) t += partial[w];
-        atomicAdd(&sums[n], (unsigned long long)t);
+        for (int w = 0; w < LANES / 64; ++w) t += partial[w];
+        atomicAdd(dst, (unsigned long long)t);
     }
 }
 
-// ---- hold-out scoring: squared differences summed per plane ----------------------------------------------------------------------------
-// sums[3 n + p] += sum over this workgroup's span of (a_n[i] - b_n[i])^2, i over the samples of plane p (Y, U, V) of payload n.  The grid's
-// x axis is g0 workgroups of the Y plane, then g1 of U, then g1 of V: a workgroup belongs to ONE plane and its span never leaves it.  A span
-// is SSE_SPAN_BYTES = 16 KiB of a plane, a lane takes SSE_CHUNKS pieces of 16 bytes, SSE_LANES * 16 bytes apart, as luma_sad_kernel does.
-//   bytes: (a - b)^2 summed over four packed samples is  a.a + b.b - 2 a.b,  three v_dot4_u32_u8 per pair of words and no unpacking: `sq`
-//     takes a.a + b.b, `ab` takes a.b, and sq - 2 ab is the sum, exact (every term is an integer and sq >= 2 ab).  A lane sees 16 *
-//     SSE_CHUNKS samples: sq <= 2 * 65025 * 64 < 2^24.  A workgroup's sum is at most 65025 * 16384 < 2^30: lane, wave and workgroup sums fit
-//     32 bits (static_assert below).
-//   16-bit words: d^2 reaches 65535^2 = 2^32 - 131071, two of them overflow 32 bits: the lane sum is 64-bit from the first add
-//     (|d| * |d| + s as one 32 x 32 + 64 multiply-add), and so is everything after it.
-// The 16-byte loads need both planes' starts on 16-byte boundaries - decided per (n, plane), uniform over the workgroup.  Any other plane
-// (odd H or W put U and V anywhere; 4:2:0 at 45 x 71 starts U at an odd byte), and the last piece of a plane whose size is no multiple of
-// a piece, goes sample by sample, samples past the plane's end never loaded.  One 64-bit vector atomic per workgroup.
-constexpr int SSE_LANES = 256, SSE_CHUNKS = 4;
-constexpr long long SSE_SPAN_BYTES = (long long)SSE_LANES * 16 * SSE_CHUNKS;
-static_assert(2ll * 65025 * 16 * SSE_CHUNKS < (1ll << 32), "a lane's sums of 8-bit products fit 32 bits");
-static_assert(65025ll * SSE_SPAN_BYTES < (1ll << 32), "a workgroup's sum of 8-bit squares fits 32 bits");
+// The grid's x axis counts g0 workgroups of the Y plane, then g1 of U, then g1 of V, so a workgroup belongs to ONE plane and what it
+// reads never leaves it: p is the plane, g the workgroup's index inside it, `first` the plane's first sample within the payload.  luma and
+// chroma are the planes' sizes in samples.  (g1 = 0: every workgroup is Y's.)
+struct PlaneOf {
+    int p;
+    unsigned g;
+    long long first;
+    __device__ __forceinline__ PlaneOf(unsigned block, unsigned g0, unsigned g1, long long luma, long long chroma) : p(0), g(block) {
+        if (g >= g0) {
+            g -= g0, p = 1;
+            if (g >= g1) g -= g1, p = 2;
+        }
+        first = p == 0 ? 0 : luma + (p - 1) * chroma;
+    }
+};
 
+// ---- the span sums: absolute differences (scene cuts) and squared differences (hold-out scoring) ---------------------------------------
+// sums[planes n + p] += sum over this workgroup's span of the lane accumulator's term of (a_n[i], b_n[i]), i over the samples of plane p
+// of payload n.  planes = 1 (ssm_luma_sad_fwd: the Y plane alone, g1 = 0) or 3 (ssm_plane_sse_fwd: Y, U, V).  A lane accumulator has the
+// Sample it reads, the Sum it ends in, words(x, y) for 32 bits of each operand, one(x, y) for a single sample, and sum():
+//   SadLane                    |a - b|: four bytes through one v_sad_u8 (the sum of the four absolute byte differences, added to the
+//                              accumulator operand), a 32-bit sum
+//   SseLane<unsigned char>     (a - b)^2 over four packed bytes is  a.a + b.b - 2 a.b,  three v_dot4_u32_u8 per pair of words and no
+//                              unpacking: `sq` takes a.a + b.b, `ab` takes a.b, and sq - 2 ab is the sum, exact (every term is an integer
+//                              and sq >= 2 ab); a 32-bit sum
+//   SseLane<unsigned short>    d^2 reaches 65535^2 = 2^32 - 131071, two of them overflow 32 bits: the lane sum is 64-bit from the first
+//                              add (|d| * |d| + s as one 32 x 32 + 64 multiply-add), and so is everything after it
+// The 16-byte loads need both planes' starts on 16-byte boundaries - decided per (n, plane), uniform over the workgroup.  Any other plane
+// (odd frame sizes make n * frame_bytes odd, odd H or W put U and V anywhere; 4:2:0 at 45 x 71 starts U at an odd byte), and the last
+// piece of a plane whose size is no multiple of a piece, goes sample by sample, samples past the plane's end never loaded.
+struct SadLane {
+    typedef unsigned char Sample;
+    typedef unsigned Sum;
+    unsigned s = 0;
+    __device__ __forceinline__ void words(unsigned x, unsigned y) { s = __builtin_amdgcn_sad_u8(x, y, s); }
+    __device__ __forceinline__ void one(unsigned x, unsigned y) { s += x > y ? x - y : y - x; }
+    __device__ __forceinline__ Sum sum() const { return s; }
+};
 template <typename S> struct SseLane;
 template <> struct SseLane<unsigned char> {
+    typedef unsigned char Sample;
     typedef unsigned Sum;
     unsigned sq = 0, ab = 0, tail = 0;
     __device__ __forceinline__ void words(unsigned x, unsigned y) {
@@ -506,6 +491,7 @@ template <> struct SseLane<unsigned char> {
     __device__ __forceinline__ Sum sum() const { return (sq - 2u * ab) + tail; }
 };
 template <> struct SseLane<unsigned short> {
+    typedef unsigned short Sample;
     typedef unsigned long long Sum;
     unsigned long long s = 0;
     __device__ __forceinline__ void one(unsigned x, unsigned y) {
@@ -519,50 +505,44 @@ template <> struct SseLane<unsigned short> {
     __device__ __forceinline__ Sum sum() const { return s; }
 };
 
-template <typename S>
-__device__ __forceinline__ void sse16(SseLane<S> &acc, i32x4 x, i32x4 y) {
+template <typename Lane>
+__device__ __forceinline__ void lane16(Lane &acc, i32x4 x, i32x4 y) {
     acc.words((unsigned)x.x, (unsigned)y.x);
     acc.words((unsigned)x.y, (unsigned)y.y);
     acc.words((unsigned)x.z, (unsigned)y.z);
     acc.words((unsigned)x.w, (unsigned)y.w);
 }
 
-template <typename S>          // the sample: unsigned char, or unsigned short (all 16 bits count)
-__global__ __launch_bounds__(SSE_LANES) void plane_sse_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
-                                                              long long luma, long long chroma, unsigned g0, unsigned g1,
-                                                              unsigned long long *sums) {          // a, b may alias; luma, chroma in samples
-    typedef typename SseLane<S>::Sum Sum;
-    constexpr int V = 16 / (int)sizeof(S);                             // samples of a piece
-    constexpr long long SPAN = SSE_SPAN_BYTES / (long long)sizeof(S);          // samples of a span
-    __shared__ Sum partial[SSE_LANES / 64];
+template <typename Lane>
+__global__ __launch_bounds__(LANES) void span_sum_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
+                                                         long long luma, long long chroma, unsigned g0, unsigned g1, int planes,
+                                                         unsigned long long *sums) {          // a, b may alias; luma, chroma in samples
+    typedef typename Lane::Sample S;
+    constexpr int V = 16 / (int)sizeof(S);                                 // samples of a piece
+    constexpr long long SPAN = SPAN_BYTES / (long long)sizeof(S);          // samples of a span
     const int n = blockIdx.y;
-    unsigned g = blockIdx.x;
-    int p = 0;
-    if (g >= g0) {
-        g -= g0, p = 1;
-        if (g >= g1) g -= g1, p = 2;
-    }
-    const long long plane = p == 0 ? luma : chroma, first = p == 0 ? 0 : luma + (p - 1) * chroma;          // the plane's samples, its first one
-    const S *pa = reinterpret_cast<const S *>(a + n * stride_a) + first, *pb = reinterpret_cast<const S *>(b + n * stride_b) + first;
+    const PlaneOf at(blockIdx.x, g0, g1, luma, chroma);
+    const long long plane = at.p == 0 ? luma : chroma;
+    const S *pa = reinterpret_cast<const S *>(a + n * stride_a) + at.first, *pb = reinterpret_cast<const S *>(b + n * stride_b) + at.first;
     const bool vec = ((reinterpret_cast<size_t>(pa) | reinterpret_cast<size_t>(pb)) & 15) == 0;
-    const long long base = g * SPAN + threadIdx.x * V;
-    SseLane<S> acc;
-    if (vec && (g + 1) * SPAN <= plane) {          // the whole span lies inside the plane: all loads first, none guarded
-        i32x4 va[SSE_CHUNKS], vb[SSE_CHUNKS];
+    const long long base = at.g * SPAN + threadIdx.x * V;
+    Lane acc;
+    if (vec && (at.g + 1) * SPAN <= plane) {          // the whole span lies inside the plane: all loads first, none guarded
+        i32x4 va[CHUNKS], vb[CHUNKS];
 #pragma unroll
-        for (int c = 0; c < SSE_CHUNKS; ++c) {
-            va[c] = *reinterpret_cast<const i32x4 *>(pa + base + (long long)c * SSE_LANES * V);
-            vb[c] = *reinterpret_cast<const i32x4 *>(pb + base + (long long)c * SSE_LANES * V);
+        for (int c = 0; c < CHUNKS; ++c) {
+            va[c] = *reinterpret_cast<const i32x4 *>(pa + base + (long long)c * LANES * V);
+            vb[c] = *reinterpret_cast<const i32x4 *>(pb + base + (long long)c * LANES * V);
         }
 #pragma unroll
-        for (int c = 0; c < SSE_CHUNKS; ++c) sse16(acc, va[c], vb[c]);
+        for (int c = 0; c < CHUNKS; ++c) lane16(acc, va[c], vb[c]);
     } else {
 #pragma unroll
-        for (int c = 0; c < SSE_CHUNKS; ++c) {
-            const long long o = base + (long long)c * SSE_LANES * V;
+        for (int c = 0; c < CHUNKS; ++c) {
+            const long long o = base + (long long)c * LANES * V;
             if (o >= plane) break;
             if (vec && o + V <= plane) {
-                sse16(acc, *reinterpret_cast<const i32x4 *>(pa + o), *reinterpret_cast<const i32x4 *>(pb + o));
+                lane16(acc, *reinterpret_cast<const i32x4 *>(pa + o), *reinterpret_cast<const i32x4 *>(pb + o));
             } else {
 #pragma unroll
                 for (int i = 0; i < V; ++i)
@@ -570,17 +550,7 @@ __global__ __launch_bounds__(SSE_LANES) void plane_sse_kernel(const unsigned cha
             }
         }
     }
-    Sum s = acc.sum();
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
-    if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        Sum t = 0;
-#pragma unroll
-        for (int w = 0; w < SSE_LANES / 64; ++w) t += partial[w];
-        atomicAdd(&sums[3 * n + p], (unsigned long long)t);
-    }
+    workgroup_add(acc.sum(), &sums[planes * n + at.p]);
 }
 
 // ---- hold-out scoring: SSIM in fixed point, summed per plane ---------------------------------------------------------------------------
@@ -600,7 +570,7 @@ __global__ __launch_bounds__(SSE_LANES) void plane_sse_kernel(const unsigned cha
 // The factors are exact in int64 (below 2^45 + c) and exact as doubles; the quotient is `/` on doubles - hipcc expands it to the IEEE
 // sequence (v_div_scale_f64, v_rcp_f64, v_fma_f64 ..., v_div_fmas_f64, v_div_fixup_f64), correctly rounded as numpy's - and this file is
 // compiled without contraction.  f2 f3 > 0 (c1, c2 > 0 and 64 ss >= s1^2 + s2^2), |q| <= 1 up to rounding: rint(q 2^32) fits int64.
-constexpr int SSIM_LANES = 256, SSIM_BW = 32, SSIM_BH = 16, SSIM_TW = SSIM_BW - 1, SSIM_TH = SSIM_BH - 1;
+constexpr int SSIM_LANES = LANES, SSIM_BW = 32, SSIM_BH = 16, SSIM_TW = SSIM_BW - 1, SSIM_TH = SSIM_BH - 1;
 static_assert(SSIM_BW * SSIM_BH == 2 * SSIM_LANES, "a lane takes two blocks, SSIM_BH / 2 block rows apart");
 static_assert(16ll * 2 * 65025 < (1ll << 32) && 16ll * 65535 < (1ll << 32), "the block sums of bytes, and s1, s2 of words, fit 32 bits");
 static_assert(64ll * (64ll * 2 * 65535 * 65535) < (1ll << 46), "64 ss of a window of words stays far inside int64 and exact as a double");
@@ -673,19 +643,13 @@ __global__ __launch_bounds__(SSIM_LANES) void plane_ssim_kernel(const unsigned c
                                                                 unsigned g0, unsigned g1, long long c1, long long c2,
                                                                 unsigned long long *sums) {          // a, b may alias
     __shared__ SsimBlock<S> blk[SSIM_BH][SSIM_BW];
-    __shared__ long long partial[SSIM_LANES / 64];
     const int n = blockIdx.y;
-    unsigned g = blockIdx.x;
-    int p = 0;
-    if (g >= g0) {
-        g -= g0, p = 1;
-        if (g >= g1) g -= g1, p = 2;
-    }
+    const PlaneOf at(blockIdx.x, g0, g1, (long long)rows0 * cols0, (long long)rows1 * cols1);
+    const int p = at.p;
+    const unsigned g = at.g;
     const int rows = p == 0 ? rows0 : rows1, cols = p == 0 ? cols0 : cols1;
     const unsigned tx = p == 0 ? tx0 : tx1;
-    const long long luma = (long long)rows0 * cols0, chroma = (long long)rows1 * cols1;
-    const long long first = p == 0 ? 0 : luma + (p - 1) * chroma;          // the plane's first sample
-    const S *pa = reinterpret_cast<const S *>(a + n * stride_a) + first, *pb = reinterpret_cast<const S *>(b + n * stride_b) + first;
+    const S *pa = reinterpret_cast<const S *>(a + n * stride_a) + at.first, *pb = reinterpret_cast<const S *>(b + n * stride_b) + at.first;
     const int nbx = cols >> 2, nby = rows >> 2;                            // the plane's blocks; its windows are (nbx - 1) x (nby - 1)
     const int bx0 = (int)(g % tx) * SSIM_TW, by0 = (int)(g / tx) * SSIM_TH;          // the tile's first block = its first window
     constexpr size_t ALIGN = 4 * sizeof(S);                                // a block row: 4 bytes, or 8
@@ -714,16 +678,7 @@ __global__ __launch_bounds__(SSIM_LANES) void plane_ssim_kernel(const unsigned c
                          (unsigned long long)q00.ss + q01.ss + q10.ss + q11.ss, (unsigned long long)q00.s12 + q01.s12 + q10.s12 + q11.s12, c1, c2);
         }
     }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
-    if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        long long t = 0;
-#pragma unroll
-        for (int w = 0; w < SSIM_LANES / 64; ++w) t += partial[w];
-        atomicAdd(&sums[3 * n + p], (unsigned long long)t);          // two's complement: the wrapped adds are the signed sum
-    }
+    workgroup_add(s, &sums[3 * n + p]);          // two's complement: the wrapped unsigned adds are the signed sum
 }
 
 // ---- hold-out scoring: the cross-fade of two payloads ---------------------------------------------------------------------------------
@@ -732,11 +687,9 @@ __global__ __launch_bounds__(SSIM_LANES) void plane_ssim_kernel(const unsigned c
 // Granlund and Montgomery for an invariant divisor, exact for every 32-bit numerator and every den >= 2: with l = ceil(log2 den) and
 // m = floor(2^32 (2^l - den) / den) + 1 (host, MixDivisor),  t = mulhi(m, x);  x / den = (t + ((x - t) >> 1)) >> (l - 1).
 // ssm_amd.video_score.mix_divisor is the same pair, and tests/test_video_ssim_cpu.py proves it over the numerators the scorer can reach.
-// A workgroup takes MIX_SPAN_BYTES of a row, a lane MIX_CHUNKS pieces of 16 bytes, MIX_LANES * 16 bytes apart; 16-byte loads and stores
-// where the three rows start on 16-byte boundaries (per n, uniform), sample by sample otherwise and in the last piece of a row that is
-// no multiple of a piece.  Nothing past `samples` is loaded or stored.
-constexpr int MIX_LANES = 256, MIX_CHUNKS = 4;
-constexpr long long MIX_SPAN_BYTES = (long long)MIX_LANES * 16 * MIX_CHUNKS;
+// A workgroup takes SPAN_BYTES of a row, a lane CHUNKS pieces of 16 bytes, LANES * 16 bytes apart, as span_sum_kernel does; 16-byte loads
+// and stores where the three rows start on 16-byte boundaries (per n, uniform), sample by sample otherwise and in the last piece of a row
+// that is no multiple of a piece.  Nothing past `samples` is loaded or stored.
 static_assert(65535ll * 65535 + 32767 < (1ll << 32), "the numerator fits 32 bits unsigned");
 
 struct MixDivisor {
@@ -759,11 +712,11 @@ __device__ __forceinline__ unsigned mix_word(unsigned x, unsigned y, unsigned wa
 }
 
 template <typename S>
-__global__ __launch_bounds__(MIX_LANES) void payload_mix_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
+__global__ __launch_bounds__(LANES) void payload_mix_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
                                                                 unsigned char *out, long long stride_out, long long samples, int num0,
                                                                 int num_step, int den, MixDivisor d) {
     constexpr int V = 16 / (int)sizeof(S);
-    constexpr long long SPAN = MIX_SPAN_BYTES / (long long)sizeof(S);
+    constexpr long long SPAN = SPAN_BYTES / (long long)sizeof(S);
     const int n = blockIdx.y;
     const unsigned wb = (unsigned)(num0 + n * num_step), wa = (unsigned)den - wb;
     const S *pa = reinterpret_cast<const S *>(a + n * stride_a), *pb = reinterpret_cast<const S *>(b + n * stride_b);
@@ -771,8 +724,8 @@ __global__ __launch_bounds__(MIX_LANES) void payload_mix_kernel(const unsigned c
     const bool vec = ((reinterpret_cast<size_t>(pa) | reinterpret_cast<size_t>(pb) | reinterpret_cast<size_t>(po)) & 15) == 0;
     const long long base = (long long)blockIdx.x * SPAN + threadIdx.x * V;
 #pragma unroll
-    for (int c = 0; c < MIX_CHUNKS; ++c) {
-        const long long o = base + (long long)c * MIX_LANES * V;
+    for (int c = 0; c < CHUNKS; ++c) {
+        const long long o = base + (long long)c * LANES * V;
         if (o >= samples) break;
         if (vec && o + V <= samples) {
             const i32x4 x = *reinterpret_cast<const i32x4 *>(pa + o), y = *reinterpret_cast<const i32x4 *>(pb + o);
@@ -820,10 +773,16 @@ inline YuvRow row_of(const float *table, int matrix, int range) {
 
 }  // namespace
 
-// samples of one frame's payload
-static long long yuv_frame_samples(int H, int W, int layout) {
-    const long long cw = layout == SSM_YUV_444 ? W : (W + 1) / 2, ch = layout == SSM_YUV_420_CENTRED || layout == SSM_YUV_420_COSITED ? (H + 1) / 2 : H;
-    return (long long)H * W + 2 * ch * cw;
+// The planes of one frame's payload: Y is h x w, U and V ch x cw each.  The one place on the host that knows the three layouts.
+struct YuvPlanes {
+    int h, w, ch, cw;
+    long long luma() const { return (long long)h * w; }
+    long long chroma() const { return (long long)ch * cw; }
+    long long frame() const { return luma() + 2 * chroma(); }          // samples of the payload
+};
+static YuvPlanes yuv_planes(int H, int W, int layout) {
+    const bool c420 = layout == SSM_YUV_420_CENTRED || layout == SSM_YUV_420_COSITED;
+    return {H, W, c420 ? (H + 1) / 2 : H, layout == SSM_YUV_444 ? W : (W + 1) / 2};
 }
 
 // The checks both pairs of entry points share; `name` is the entry point's, `what` says "chroma siting" (the 8-bit entry points, which
@@ -853,6 +812,15 @@ static void with_layout(int layout, F f) {
         f(std::integral_constant<int, LAY_420>{});
 }
 
+// f(S{}) of a checked sample width, S = unsigned char or unsigned short: the one place where sample_bytes picks a kernel instantiation
+template <typename F>
+static void with_sample(int sample_bytes, F f) {
+    if (sample_bytes == 1)
+        f((unsigned char)0);
+    else
+        f((unsigned short)0);
+}
+
 template <typename S>
 static void launch_from_yuv(const void *frames_yuv, ssm_view out, int N, int H, int W, int Hp, int Wp, int top, int left, const float *mean3,
                             const float *std3, int pad_before_norm, const float *table, int matrix, int range, int layout, void *stream) {
@@ -862,7 +830,7 @@ static void launch_from_yuv(const void *frames_yuv, ssm_view out, int N, int H, 
     // blocks per axis: the canvas plus the one-pixel shift of an odd offset
     const int nbx = (Wp + (left & 1) + 1) / 2, nby = (Hp + (top & 1) + 1) / 2;
     const dim3 grid((nbx + 63) / 64, (nby + 3) / 4, N);
-    const long long fs = yuv_frame_samples(H, W, layout);
+    const long long fs = yuv_planes(H, W, layout).frame();
     const S *in = static_cast<const S *>(frames_yuv);
     with_layout(layout, [&](auto lay) {
         SSM_LAUNCH(frames_from_yuv_kernel<S, lay()>, grid, dim3(64, 4), 0, (hipStream_t)stream, in, out, H, W, Hp, Wp, top, left, fs,
@@ -878,17 +846,16 @@ static int frames_from_yuv(const char *name, const char *entry, bool extended, c
                     (Hp + 9) / 8 <= 65535,
                 "%s: bad geometry %dx%d -> %dx%d at (%d,%d), row stride %d", name, H, W, Hp, Wp, top, left, out.sh);
     if (const int e = check_yuv(name, matrix, range, layout, extended, sample_bytes, frames_yuv)) return e;
-    if (sample_bytes == 1)
-        launch_from_yuv<unsigned char>(frames_yuv, out, N, H, W, Hp, Wp, top, left, mean3, std3, pad_before_norm, table, matrix, range, layout, stream);
-    else
-        launch_from_yuv<unsigned short>(frames_yuv, out, N, H, W, Hp, Wp, top, left, mean3, std3, pad_before_norm, table, matrix, range, layout, stream);
+    with_sample(sample_bytes, [&](auto s) {
+        launch_from_yuv<decltype(s)>(frames_yuv, out, N, H, W, Hp, Wp, top, left, mean3, std3, pad_before_norm, table, matrix, range, layout, stream);
+    });
     return ssm::check_launch(entry);
 }
 
 template <typename S>
 static void launch_to_yuv(ssm_view in, void *frames_yuv, int N, int H, int W, int top, int left, const float *mean3, const float *std3,
                           const float *table, int matrix, int range, int layout, void *stream) {
-    const long long fs = yuv_frame_samples(H, W, layout);
+    const long long fs = yuv_planes(H, W, layout).frame();
     const int vec_in = (left % 4 == 0 && view_aligned(in, 4)) ? 1 : 0;
     // W % 4 == 0 and a base aligned to four samples keep every store aligned: a Y row starts at a multiple of 4 samples; the chroma rows are
     // W / 2 (even) samples and a thread's pair starts at an even one; the Y plane is H W samples (a multiple of 4), a chroma plane
@@ -910,10 +877,9 @@ static int frames_to_yuv(const char *name, const char *entry, bool extended, ssm
     SSM_REQUIRE(N > 0 && N <= 65535 && H > 0 && W > 0 && top >= 0 && left >= 0 && in.sh >= W + left && (H + 7) / 8 <= 65535,
                 "%s: bad geometry %dx%d at (%d,%d), row stride %d", name, H, W, top, left, in.sh);
     if (const int e = check_yuv(name, matrix, range, layout, extended, sample_bytes, frames_yuv)) return e;
-    if (sample_bytes == 1)
-        launch_to_yuv<unsigned char>(in, frames_yuv, N, H, W, top, left, mean3, std3, table, matrix, range, layout, stream);
-    else
-        launch_to_yuv<unsigned short>(in, frames_yuv, N, H, W, top, left, mean3, std3, table, matrix, range, layout, stream);
+    with_sample(sample_bytes, [&](auto s) {
+        launch_to_yuv<decltype(s)>(in, frames_yuv, N, H, W, top, left, mean3, std3, table, matrix, range, layout, stream);
+    });
     return ssm::check_launch(entry);
 }
 
@@ -1003,63 +969,103 @@ extern "C" int ssm_frames_accumulate_light_fwd(ssm_view src, ssm_view acc, int N
     return frames_accumulate("frames_accumulate_light", "ssm_frames_accumulate_light_fwd", src, acc, N, 3, H, W, init, scale, &light, stream);
 }
 
-extern "C" int ssm_luma_sad_fwd(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b, int N, int H, int W,
-                                unsigned long long *sums, void *stream) {
-    SSM_REQUIRE(a && b && sums, "luma_sad: null pointer");
-    SSM_REQUIRE(N > 0 && N <= 65535, "luma_sad: N=%d outside 1..65535", N);
-    SSM_REQUIRE(H > 0 && W > 0, "luma_sad: bad plane size %dx%d", H, W);
-    const long long plane = (long long)H * W;
-    SSM_REQUIRE(N == 1 || (std::llabs(stride_a) >= plane && std::llabs(stride_b) >= plane),
-                "luma_sad: strides %lld (a), %lld (b) shorter than the plane's %lld bytes", stride_a, stride_b, plane);
-    SSM_REQUIRE(reinterpret_cast<size_t>(sums) % 8 == 0, "luma_sad: sums is not 8-byte aligned");
-    const long long groups = (plane + SAD_SPAN - 1) / SAD_SPAN;
-    SSM_REQUIRE(groups <= 2147483647ll, "luma_sad: a plane of %lld bytes is more than the grid takes", plane);
-    const hipError_t e = ssm::memset_async(sums, 0, sizeof(unsigned long long) * (size_t)N, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        ssm::set_error("luma_sad: memset failed: %s", hipGetErrorString(e));
-        return SSM_E_LAUNCH;
-    }
-    SSM_LAUNCH(luma_sad_kernel, dim3((unsigned)groups, N), dim3(SAD_LANES), 0, (hipStream_t)stream, a, b, stride_a, stride_b, plane, sums);
-    return ssm::check_launch("ssm_luma_sad_fwd");
+
+// ---- the pair entry points: two payloads in, sums or a third payload out -------------------------------------------------------------
+// ssm_luma_sad_fwd, ssm_plane_sse_fwd, ssm_plane_ssim_fwd and ssm_payload_mix_fwd refuse in one order: pair_given (pointers, N), the
+// entry's own sizes, check_pair (strides, alignment), what only that entry asks, grid_fits - and only then queue anything: a refused call
+// queues nothing, not even the clear.
+struct PairEntry {
+    const char *name, *unit;          // the entry's short name; what a stride steps over: "plane", "frame" or "row"
+    long long unit_bytes;             // and its size
+};
+
+static int pair_given(const char *name, const void *a, const void *b, const void *third, int N) {          // third: `sums`, or `out`
+    SSM_REQUIRE(a && b && third, "%s: null pointer", name);
+    SSM_REQUIRE(N > 0 && N <= 65535, "%s: N=%d outside 1..65535", name, N);
+    return SSM_OK;
 }
 
-// samples of one chroma plane
-static long long yuv_chroma_samples(int H, int W, int layout) {
-    const long long cw = layout == SSM_YUV_444 ? W : (W + 1) / 2, ch = layout == SSM_YUV_420_CENTRED || layout == SSM_YUV_420_COSITED ? (H + 1) / 2 : H;
-    return ch * cw;
+// The operands of a pair entry point once its unit is sized: the strides of a and b, of `out`, 2-byte samples, `sums`.  zero_ok: a
+// stride of 0 - one payload against N - is allowed on a and b; one_waives: with N = 1 no stride of a or b is looked at.  An entry has
+// either `sums`, its N or 3 N 64-bit words, or (payload_mix) `out`, a third row per n that is written: never at stride 0, and with N = 1
+// its stride names nothing.
+static int check_pair(const PairEntry &k, bool zero_ok, bool one_waives, const void *a, const void *b, long long stride_a, long long stride_b,
+                      int N, int sample_bytes, const void *sums, const void *out = nullptr, long long stride_out = 0) {
+    const char *name = k.name;
+    const auto reaches = [&](long long s, bool zero) { return (zero && s == 0) || std::llabs(s) >= k.unit_bytes; };
+    const bool ab_ok = (one_waives && N == 1) || (reaches(stride_a, zero_ok) && reaches(stride_b, zero_ok));
+    if (zero_ok)
+        SSM_REQUIRE(ab_ok, "%s: strides %lld (a), %lld (b) neither 0 nor at least the %s's %lld bytes", name, stride_a, stride_b, k.unit, k.unit_bytes);
+    else
+        SSM_REQUIRE(ab_ok, "%s: strides %lld (a), %lld (b) shorter than the %s's %lld bytes", name, stride_a, stride_b, k.unit, k.unit_bytes);
+    if (out) SSM_REQUIRE(N == 1 || reaches(stride_out, false), "%s: stride %lld (out) shorter than the %s's %lld bytes", name, stride_out, k.unit, k.unit_bytes);
+    if (sample_bytes == 2) {
+        const auto odd = [](const void *p) { return reinterpret_cast<size_t>(p) % 2 != 0; };
+        SSM_REQUIRE(!odd(a) && !odd(b) && !odd(out), "%s: a %s of 2-byte samples (%s) is not 2-byte aligned", name, out ? "row" : "payload",
+                    out ? "a, b or out" : "a or b");
+        const bool even = stride_a % 2 == 0 && stride_b % 2 == 0 && stride_out % 2 == 0;
+        if (out)
+            SSM_REQUIRE(even, "%s: strides %lld (a), %lld (b), %lld (out) of 2-byte samples must be even", name, stride_a, stride_b, stride_out);
+        else
+            SSM_REQUIRE(even, "%s: strides %lld (a), %lld (b) of 2-byte samples must be even", name, stride_a, stride_b);
+    }
+    if (sums) SSM_REQUIRE(reinterpret_cast<size_t>(sums) % 8 == 0, "%s: sums is not 8-byte aligned", name);
+    return SSM_OK;
+}
+
+static int grid_fits(const PairEntry &k, long long groups) {
+    SSM_REQUIRE(groups <= 2147483647ll, "%s: a %s of %lld bytes is more than the grid takes", k.name, k.unit, k.unit_bytes);
+    return SSM_OK;
+}
+
+// The entry's clear of its `words` 64-bit sums, on the caller's stream ahead of the kernel; called after every check.
+static int clear_sums(const char *name, void *sums, size_t words, void *stream) {
+    const hipError_t e = ssm::memset_async(sums, 0, sizeof(unsigned long long) * words, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        ssm::set_error("%s: memset failed: %s", name, hipGetErrorString(e));
+        return SSM_E_LAUNCH;
+    }
+    return SSM_OK;
+}
+
+// what the two scoring entry points check of a frame before they size it
+static int check_frame(const char *name, int H, int W, int layout, int sample_bytes) {
+    SSM_REQUIRE(H > 0 && W > 0, "%s: bad frame size %dx%d", name, H, W);
+    SSM_REQUIRE(layout >= SSM_YUV_420_CENTRED && layout <= SSM_YUV_422, "%s: layout %d not in {0, 1, 2, 3}", name, layout);
+    SSM_REQUIRE(sample_bytes == 1 || sample_bytes == 2, "%s: sample_bytes %d not in {1, 2}", name, sample_bytes);
+    return SSM_OK;
+}
+
+extern "C" int ssm_luma_sad_fwd(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b, int N, int H, int W,
+                                unsigned long long *sums, void *stream) {
+    if (const int e = pair_given("luma_sad", a, b, sums, N)) return e;
+    SSM_REQUIRE(H > 0 && W > 0, "luma_sad: bad plane size %dx%d", H, W);
+    const long long plane = (long long)H * W, groups = (plane + SPAN_BYTES - 1) / SPAN_BYTES;
+    const PairEntry k = {"luma_sad", "plane", plane};
+    if (const int e = check_pair(k, false, true, a, b, stride_a, stride_b, N, 1, sums)) return e;
+    if (const int e = grid_fits(k, groups)) return e;
+    if (const int e = clear_sums(k.name, sums, (size_t)N, stream)) return e;
+    // one plane per payload: every workgroup is Y's (g1 = 0), sums[n]
+    SSM_LAUNCH(span_sum_kernel<SadLane>, dim3((unsigned)groups, N), dim3(LANES), 0, (hipStream_t)stream, a, b, stride_a, stride_b, plane, 0ll,
+               (unsigned)groups, 0u, 1, sums);
+    return ssm::check_launch("ssm_luma_sad_fwd");
 }
 
 extern "C" int ssm_plane_sse_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int layout,
                                  int sample_bytes, unsigned long long *sums, void *stream) {
-    SSM_REQUIRE(a && b && sums, "plane_sse: null pointer");
-    SSM_REQUIRE(N > 0 && N <= 65535, "plane_sse: N=%d outside 1..65535", N);
-    SSM_REQUIRE(H > 0 && W > 0, "plane_sse: bad frame size %dx%d", H, W);
-    SSM_REQUIRE(layout >= SSM_YUV_420_CENTRED && layout <= SSM_YUV_422, "plane_sse: layout %d not in {0, 1, 2, 3}", layout);
-    SSM_REQUIRE(sample_bytes == 1 || sample_bytes == 2, "plane_sse: sample_bytes %d not in {1, 2}", sample_bytes);
-    const long long luma = (long long)H * W, chroma = yuv_chroma_samples(H, W, layout), frame = yuv_frame_samples(H, W, layout) * sample_bytes;
-    SSM_REQUIRE((stride_a == 0 || std::llabs(stride_a) >= frame) && (stride_b == 0 || std::llabs(stride_b) >= frame),
-                "plane_sse: strides %lld (a), %lld (b) neither 0 nor at least the frame's %lld bytes", stride_a, stride_b, frame);
-    if (sample_bytes == 2) {
-        SSM_REQUIRE(reinterpret_cast<size_t>(a) % 2 == 0 && reinterpret_cast<size_t>(b) % 2 == 0,
-                    "plane_sse: a payload of 2-byte samples (a or b) is not 2-byte aligned");
-        SSM_REQUIRE(stride_a % 2 == 0 && stride_b % 2 == 0, "plane_sse: strides %lld (a), %lld (b) of 2-byte samples must be even", stride_a, stride_b);
-    }
-    SSM_REQUIRE(reinterpret_cast<size_t>(sums) % 8 == 0, "plane_sse: sums is not 8-byte aligned");
-    const long long span = SSE_SPAN_BYTES / sample_bytes, g0 = (luma + span - 1) / span, g1 = (chroma + span - 1) / span;
-    SSM_REQUIRE(g0 + 2 * g1 <= 2147483647ll, "plane_sse: a frame of %lld bytes is more than the grid takes", frame);
-    const hipError_t e = ssm::memset_async(sums, 0, sizeof(unsigned long long) * 3 * (size_t)N, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        ssm::set_error("plane_sse: memset failed: %s", hipGetErrorString(e));
-        return SSM_E_LAUNCH;
-    }
+    if (const int e = pair_given("plane_sse", a, b, sums, N)) return e;
+    if (const int e = check_frame("plane_sse", H, W, layout, sample_bytes)) return e;
+    const YuvPlanes pl = yuv_planes(H, W, layout);
+    const PairEntry k = {"plane_sse", "frame", pl.frame() * sample_bytes};
+    if (const int e = check_pair(k, true, false, a, b, stride_a, stride_b, N, sample_bytes, sums)) return e;
+    const long long span = SPAN_BYTES / sample_bytes, g0 = (pl.luma() + span - 1) / span, g1 = (pl.chroma() + span - 1) / span;
+    if (const int e = grid_fits(k, g0 + 2 * g1)) return e;
+    if (const int e = clear_sums(k.name, sums, 3 * (size_t)N, stream)) return e;
     const unsigned char *pa = static_cast<const unsigned char *>(a), *pb = static_cast<const unsigned char *>(b);
-    const dim3 grid((unsigned)(g0 + 2 * g1), N);
-    if (sample_bytes == 1)
-        SSM_LAUNCH(plane_sse_kernel<unsigned char>, grid, dim3(SSE_LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b, luma, chroma,
-                   (unsigned)g0, (unsigned)g1, sums);
-    else
-        SSM_LAUNCH(plane_sse_kernel<unsigned short>, grid, dim3(SSE_LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b, luma, chroma,
-                   (unsigned)g0, (unsigned)g1, sums);
+    with_sample(sample_bytes, [&](auto s) {
+        SSM_LAUNCH(span_sum_kernel<SseLane<decltype(s)>>, dim3((unsigned)(g0 + 2 * g1), N), dim3(LANES), 0, (hipStream_t)stream, pa, pb, stride_a,
+                   stride_b, pl.luma(), pl.chroma(), (unsigned)g0, (unsigned)g1, 3, sums);
+    });
     return ssm::check_launch("ssm_plane_sse_fwd");
 }
 
@@ -1068,41 +1074,24 @@ static long long ssim_windows(int samples) { return (samples >> 2) > 1 ? (sample
 
 extern "C" int ssm_plane_ssim_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int layout,
                                   int sample_bytes, long long c1, long long c2, long long *sums, void *stream) {
-    SSM_REQUIRE(a && b && sums, "plane_ssim: null pointer");
-    SSM_REQUIRE(N > 0 && N <= 65535, "plane_ssim: N=%d outside 1..65535", N);
-    SSM_REQUIRE(H > 0 && W > 0, "plane_ssim: bad frame size %dx%d", H, W);
-    SSM_REQUIRE(layout >= SSM_YUV_420_CENTRED && layout <= SSM_YUV_422, "plane_ssim: layout %d not in {0, 1, 2, 3}", layout);
-    SSM_REQUIRE(sample_bytes == 1 || sample_bytes == 2, "plane_ssim: sample_bytes %d not in {1, 2}", sample_bytes);
+    if (const int e = pair_given("plane_ssim", a, b, sums, N)) return e;
+    if (const int e = check_frame("plane_ssim", H, W, layout, sample_bytes)) return e;
     SSM_REQUIRE(c1 > 0 && c2 > 0 && c1 <= (1ll << 40) && c2 <= (1ll << 40), "plane_ssim: c1=%lld, c2=%lld outside 1..2^40", c1, c2);
-    const long long frame = yuv_frame_samples(H, W, layout) * sample_bytes;
-    SSM_REQUIRE((stride_a == 0 || std::llabs(stride_a) >= frame) && (stride_b == 0 || std::llabs(stride_b) >= frame),
-                "plane_ssim: strides %lld (a), %lld (b) neither 0 nor at least the frame's %lld bytes", stride_a, stride_b, frame);
-    if (sample_bytes == 2) {
-        SSM_REQUIRE(reinterpret_cast<size_t>(a) % 2 == 0 && reinterpret_cast<size_t>(b) % 2 == 0,
-                    "plane_ssim: a payload of 2-byte samples (a or b) is not 2-byte aligned");
-        SSM_REQUIRE(stride_a % 2 == 0 && stride_b % 2 == 0, "plane_ssim: strides %lld (a), %lld (b) of 2-byte samples must be even", stride_a, stride_b);
-    }
-    SSM_REQUIRE(reinterpret_cast<size_t>(sums) % 8 == 0, "plane_ssim: sums is not 8-byte aligned");
-    const int cw = layout == SSM_YUV_444 ? W : (W + 1) / 2, ch = layout == SSM_YUV_420_CENTRED || layout == SSM_YUV_420_COSITED ? (H + 1) / 2 : H;
-    const long long tx0 = (ssim_windows(W) + SSIM_TW - 1) / SSIM_TW, ty0 = (ssim_windows(H) + SSIM_TH - 1) / SSIM_TH;
-    const long long tx1 = (ssim_windows(cw) + SSIM_TW - 1) / SSIM_TW, ty1 = (ssim_windows(ch) + SSIM_TH - 1) / SSIM_TH;
+    const YuvPlanes pl = yuv_planes(H, W, layout);
+    const PairEntry k = {"plane_ssim", "frame", pl.frame() * sample_bytes};
+    if (const int e = check_pair(k, true, false, a, b, stride_a, stride_b, N, sample_bytes, sums)) return e;
+    const long long tx0 = (ssim_windows(pl.w) + SSIM_TW - 1) / SSIM_TW, ty0 = (ssim_windows(pl.h) + SSIM_TH - 1) / SSIM_TH;
+    const long long tx1 = (ssim_windows(pl.cw) + SSIM_TW - 1) / SSIM_TW, ty1 = (ssim_windows(pl.ch) + SSIM_TH - 1) / SSIM_TH;
     const long long g0 = tx0 * ty0, g1 = tx1 * ty1;
-    SSM_REQUIRE(g0 + 2 * g1 <= 2147483647ll, "plane_ssim: a frame of %lld bytes is more than the grid takes", frame);
-    const hipError_t e = ssm::memset_async(sums, 0, sizeof(long long) * 3 * (size_t)N, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        ssm::set_error("plane_ssim: memset failed: %s", hipGetErrorString(e));
-        return SSM_E_LAUNCH;
-    }
+    if (const int e = grid_fits(k, g0 + 2 * g1)) return e;
+    if (const int e = clear_sums(k.name, sums, 3 * (size_t)N, stream)) return e;
     if (g0 + 2 * g1 == 0) return SSM_OK;          // no plane has a window: the cleared sums are the result
     const unsigned char *pa = static_cast<const unsigned char *>(a), *pb = static_cast<const unsigned char *>(b);
-    unsigned long long *out = reinterpret_cast<unsigned long long *>(sums);
-    const dim3 grid((unsigned)(g0 + 2 * g1), N);
-    if (sample_bytes == 1)
-        SSM_LAUNCH(plane_ssim_kernel<unsigned char>, grid, dim3(SSIM_LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b, H, W, ch, cw,
-                   (unsigned)tx0, (unsigned)tx1, (unsigned)g0, (unsigned)g1, c1, c2, out);
-    else
-        SSM_LAUNCH(plane_ssim_kernel<unsigned short>, grid, dim3(SSIM_LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b, H, W, ch, cw,
-                   (unsigned)tx0, (unsigned)tx1, (unsigned)g0, (unsigned)g1, c1, c2, out);
+    with_sample(sample_bytes, [&](auto s) {
+        SSM_LAUNCH(plane_ssim_kernel<decltype(s)>, dim3((unsigned)(g0 + 2 * g1), N), dim3(SSIM_LANES), 0, (hipStream_t)stream, pa, pb, stride_a,
+                   stride_b, pl.h, pl.w, pl.ch, pl.cw, (unsigned)tx0, (unsigned)tx1, (unsigned)g0, (unsigned)g1, c1, c2,
+                   reinterpret_cast<unsigned long long *>(sums));
+    });
     return ssm::check_launch("ssm_plane_ssim_fwd");
 }
 
@@ -1115,8 +1104,7 @@ static void rows_range(const void *p, long long stride, int N, long long row, lo
 
 extern "C" int ssm_payload_mix_fwd(const void *a, const void *b, long long stride_a, long long stride_b, void *out, long long stride_out, int N,
                                    long long samples, int sample_bytes, int num0, int num_step, int den, void *stream) {
-    SSM_REQUIRE(a && b && out, "payload_mix: null pointer");
-    SSM_REQUIRE(N > 0 && N <= 65535, "payload_mix: N=%d outside 1..65535", N);
+    if (const int e = pair_given("payload_mix", a, b, out, N)) return e;
     SSM_REQUIRE(samples > 0, "payload_mix: samples=%lld must be positive", samples);
     SSM_REQUIRE(sample_bytes == 1 || sample_bytes == 2, "payload_mix: sample_bytes %d not in {1, 2}", sample_bytes);
     SSM_REQUIRE(den >= 2 && den <= 65535, "payload_mix: den=%d outside 2..65535", den);
@@ -1124,34 +1112,24 @@ extern "C" int ssm_payload_mix_fwd(const void *a, const void *b, long long strid
     SSM_REQUIRE(num0 >= 0 && num0 <= den && k_last >= 0 && k_last <= den, "payload_mix: k = %d + n * %d leaves 0..den=%d within N=%d rows", num0,
                 num_step, den, N);
     const long long row = samples * sample_bytes;
-    SSM_REQUIRE((stride_a == 0 || std::llabs(stride_a) >= row) && (stride_b == 0 || std::llabs(stride_b) >= row),
-                "payload_mix: strides %lld (a), %lld (b) neither 0 nor at least the row's %lld bytes", stride_a, stride_b, row);
-    SSM_REQUIRE(N == 1 || std::llabs(stride_out) >= row, "payload_mix: stride %lld (out) shorter than the row's %lld bytes", stride_out, row);
-    if (sample_bytes == 2) {
-        SSM_REQUIRE(reinterpret_cast<size_t>(a) % 2 == 0 && reinterpret_cast<size_t>(b) % 2 == 0 && reinterpret_cast<size_t>(out) % 2 == 0,
-                    "payload_mix: a row of 2-byte samples (a, b or out) is not 2-byte aligned");
-        SSM_REQUIRE(stride_a % 2 == 0 && stride_b % 2 == 0 && stride_out % 2 == 0,
-                    "payload_mix: strides %lld (a), %lld (b), %lld (out) of 2-byte samples must be even", stride_a, stride_b, stride_out);
-    }
+    const PairEntry k = {"payload_mix", "row", row};
+    if (const int e = check_pair(k, true, false, a, b, stride_a, stride_b, N, sample_bytes, nullptr, out, stride_out)) return e;
     long long o0, o1, a0, a1, b0, b1;
     rows_range(out, stride_out, N, row, &o0, &o1);
     rows_range(a, stride_a, N, row, &a0, &a1);
     rows_range(b, stride_b, N, row, &b0, &b1);
     SSM_REQUIRE((a1 <= o0 || o1 <= a0) && (b1 <= o0 || o1 <= b0), "payload_mix: out overlaps a or b");
-    const long long span = MIX_SPAN_BYTES / sample_bytes, groups = (samples + span - 1) / span;
-    SSM_REQUIRE(groups <= 2147483647ll, "payload_mix: a row of %lld bytes is more than the grid takes", row);
+    const long long span = SPAN_BYTES / sample_bytes, groups = (samples + span - 1) / span;
+    if (const int e = grid_fits(k, groups)) return e;
     int l = 0;
     while ((1ll << l) < den) ++l;          // ceil(log2 den) >= 1
     MixDivisor d;
     d.m = (unsigned)((((1ull << l) - (unsigned long long)den) << 32) / (unsigned long long)den + 1ull);
     d.shift = (unsigned)(l - 1), d.half = (unsigned)(den >> 1);
     const unsigned char *pa = static_cast<const unsigned char *>(a), *pb = static_cast<const unsigned char *>(b);
-    const dim3 grid((unsigned)groups, N);
-    if (sample_bytes == 1)
-        SSM_LAUNCH(payload_mix_kernel<unsigned char>, grid, dim3(MIX_LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b,
+    with_sample(sample_bytes, [&](auto s) {
+        SSM_LAUNCH(payload_mix_kernel<decltype(s)>, dim3((unsigned)groups, N), dim3(LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b,
                    static_cast<unsigned char *>(out), stride_out, samples, num0, num_step, den, d);
-    else
-        SSM_LAUNCH(payload_mix_kernel<unsigned short>, grid, dim3(MIX_LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b,
-                   static_cast<unsigned char *>(out), stride_out, samples, num0, num_step, den, d);
+    });
     return ssm::check_launch("ssm_payload_mix_fwd");
 }

@@ -407,20 +407,29 @@ def frames_to_yuv(x, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITED, cf
     return clip.egress(x, out)
 
 
+def _pair_operands(payload_a, payload_b, row_bytes, row_name, out, per_pair):
+    """What the calls on two sets of payloads (luma_sad here, video_score.plane_sse and plane_ssim) ask of their tensors: [N, at least
+    row_bytes] uint8 on the GPU with unit stride within a row, as many rows in a as in b, on one device.  -> (N, `out`: a contiguous int64
+    [N, *per_pair] on the device, made if None, and the two row strides as the entry points take them).  The stride of a single row names
+    nothing: with N = 1 it goes as 0, which every entry takes."""
+    for t in (payload_a, payload_b):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.shape[1] >= row_bytes and (t.shape[1] == 1 or t.stride(1) == 1), \
+            "payloads must be [N, at least %s] uint8 tensors on the GPU with unit stride within a frame" % row_name
+    n = payload_a.shape[0]
+    assert payload_b.shape[0] == n and payload_b.device == payload_a.device, "as many frames in a as in b, on one device"
+    if out is None:
+        out = torch.empty((n,) + per_pair, dtype=torch.int64, device=payload_a.device)
+    assert out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == (n,) + per_pair and out.is_contiguous()
+    sa, sb = (t.stride(0) if n > 1 else 0 for t in (payload_a, payload_b))
+    return n, out, sa, sb
+
+
 def luma_sad(payload_a, payload_b, h, w, out=None):
     """ssm_luma_sad_fwd on payloads: [N, frame_bytes] uint8 device tensors (rows of at least h * w bytes, unit stride within a row, any
     row stride: views of one buffer, frames n and n + 1, are fine) -> int64 [N] on the device (into `out` if given), out[n] = the sum
     over the h x w Y planes of |a_n - b_n|.  The words are unsigned and below 2^63: read them on the host as numpy uint64."""
-    for t in (payload_a, payload_b):
-        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.shape[1] >= h * w and (t.shape[1] == 1 or t.stride(1) == 1), \
-            "payloads must be [N, at least h * w] uint8 tensors on the GPU with unit stride within a frame"
-    n = payload_a.shape[0]
-    assert payload_b.shape[0] == n and payload_b.device == payload_a.device, "as many frames in a as in b, on one device"
-    if out is None:
-        out = torch.empty(n, dtype=torch.int64, device=payload_a.device)
-    assert out.is_cuda and out.dtype == torch.int64 and out.dim() == 1 and out.shape[0] == n and out.is_contiguous()
-    hb.check(hb.load().ssm_luma_sad_fwd(payload_a.data_ptr(), payload_b.data_ptr(), payload_a.stride(0), payload_b.stride(0), n, h, w,
-                                        out.data_ptr(), hb.stream_ptr()))
+    n, out, sa, sb = _pair_operands(payload_a, payload_b, h * w, "h * w", out, ())
+    hb.check(hb.load().ssm_luma_sad_fwd(payload_a.data_ptr(), payload_b.data_ptr(), sa, sb, n, h, w, out.data_ptr(), hb.stream_ptr()))
     return out
 
 

@@ -49,18 +49,30 @@ def plane_samples(h, w, siting):
     return h * w, ch * cw, ch * cw
 
 
-def plane_sse_host(payload_a, payload_b, h, w, siting, bits=8):
-    """Yardstick of ssm_plane_sse_fwd: [N, frame_bytes] uint8 payloads (numpy; either may have one row, compared against all of the
-    other's) -> uint64 [N,3], out[n][p] = the sum over plane p (Y, U, V) of (a - b)^2, exact.  8-bit planes are summed in int64.  Samples of
-    more than 8 bits are 16-bit words of which ALL 16 bits count, as in the kernel: a row of a plane is summed in int64 (a difference
-    squared is below 2^32, a row of fewer than 2^31 samples cannot overflow), the rows as Python integers.  The result is exact while a
-    sum is below 2^64, which only a plane of more than 2^32 samples can reach: beyond any real frame."""
+def _host_pair(payload_a, payload_b, h, w, siting, bits):
+    """The operands of a host yardstick: each as uint8 [its payloads, frame_bytes], and n, the pairs they make - as many payloads in a
+    as in b, or one that is compared against all of the other's."""
     fb = V.frame_bytes(h, w, siting, bits)
     a = np.ascontiguousarray(payload_a).reshape(-1, fb)
     b = np.ascontiguousarray(payload_b).reshape(-1, fb)
     assert a.dtype == np.uint8 and b.dtype == np.uint8
     n = max(a.shape[0], b.shape[0])
     assert a.shape[0] in (1, n) and b.shape[0] in (1, n), "as many payloads in a as in b, or one"
+    return a, b, n
+
+
+def _pair_operands(payload_a, payload_b, h, w, siting, bits, out):
+    """video._pair_operands for whole payloads and sums per plane: (N, out [N,3], stride of a, of b)."""
+    return V._pair_operands(payload_a, payload_b, V.frame_bytes(h, w, siting, bits), "frame_bytes", out, (3,))
+
+
+def plane_sse_host(payload_a, payload_b, h, w, siting, bits=8):
+    """Yardstick of ssm_plane_sse_fwd: [N, frame_bytes] uint8 payloads (numpy; either may have one row, compared against all of the
+    other's) -> uint64 [N,3], out[n][p] = the sum over plane p (Y, U, V) of (a - b)^2, exact.  8-bit planes are summed in int64.  Samples of
+    more than 8 bits are 16-bit words of which ALL 16 bits count, as in the kernel: a row of a plane is summed in int64 (a difference
+    squared is below 2^32, a row of fewer than 2^31 samples cannot overflow), the rows as Python integers.  The result is exact while a
+    sum is below 2^64, which only a plane of more than 2^32 samples can reach: beyond any real frame."""
+    a, b, n = _host_pair(payload_a, payload_b, h, w, siting, bits)
     out = np.zeros((n, 3), dtype=np.uint64)
     for p, (pa, pb) in enumerate(zip(V.split_planes(a, h, w, siting, bits), V.split_planes(b, h, w, siting, bits))):
         d = pa.astype(np.int64) - pb.astype(np.int64)          # [n | 1, rows, cols], broadcast over n
@@ -79,16 +91,7 @@ def plane_sse(payload_a, payload_b, h, w, siting, bits=8, out=None):
     views of one buffer, frames n and n + 1, a negative step through as_strided, or a 0-stride expand of one row: one payload against N -
     -> int64 [N,3] on the device (into `out` if given), out[n][p] = the sum over plane p (Y, U, V) of (a_n - b_n)^2.  The words are
     unsigned: read them on the host as numpy uint64.  bits > 8: the bytes are 16-bit little-endian samples, all 16 bits count."""
-    fb = V.frame_bytes(h, w, siting, bits)
-    for t in (payload_a, payload_b):
-        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.shape[1] >= fb and (t.shape[1] == 1 or t.stride(1) == 1), \
-            "payloads must be [N, at least frame_bytes] uint8 tensors on the GPU with unit stride within a frame"
-    n = payload_a.shape[0]
-    assert payload_b.shape[0] == n and payload_b.device == payload_a.device, "as many frames in a as in b, on one device"
-    if out is None:
-        out = torch.empty(n, 3, dtype=torch.int64, device=payload_a.device)
-    assert out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == (n, 3) and out.is_contiguous()
-    sa, sb = (t.stride(0) if n > 1 else 0 for t in (payload_a, payload_b))          # the stride of a single row names nothing
+    n, out, sa, sb = _pair_operands(payload_a, payload_b, h, w, siting, bits, out)
     hb.check(hb.load().ssm_plane_sse_fwd(payload_a.data_ptr(), payload_b.data_ptr(), sa, sb, n, h, w, siting, V.sample_bytes(bits),
                                          out.data_ptr(), hb.stream_ptr()))
     return out
@@ -150,12 +153,7 @@ def plane_ssim_host(payload_a, payload_b, h, w, siting, bits=8):
     the sum over the windows of plane p of fx = rint(q 2^32), q = (double(f0) double(f1)) / (double(f2) double(f3)).  The factors are
     int64 throughout (below 2^45 at 16 bits); the three float64 operations and the scaling are numpy's, one rounding each; np.rint rounds
     half to even.  A plane without a window gives 0."""
-    fb = V.frame_bytes(h, w, siting, bits)
-    a = np.ascontiguousarray(payload_a).reshape(-1, fb)
-    b = np.ascontiguousarray(payload_b).reshape(-1, fb)
-    assert a.dtype == np.uint8 and b.dtype == np.uint8
-    n = max(a.shape[0], b.shape[0])
-    assert a.shape[0] in (1, n) and b.shape[0] in (1, n), "as many payloads in a as in b, or one"
+    a, b, n = _host_pair(payload_a, payload_b, h, w, siting, bits)
     c1, c2 = (np.int64(c) for c in ssim_constants(bits))
     out = np.zeros((n, 3), dtype=np.int64)
     for p, (pa, pb) in enumerate(zip(V.split_planes(a, h, w, siting, bits), V.split_planes(b, h, w, siting, bits))):
@@ -176,16 +174,7 @@ def plane_ssim_host(payload_a, payload_b, h, w, siting, bits=8):
 
 def plane_ssim(payload_a, payload_b, h, w, siting, bits=8, out=None):
     """ssm_plane_ssim_fwd on payloads, shaped like plane_sse -> int64 [N,3] on the device (into `out` if given): signed sums of fx."""
-    fb = V.frame_bytes(h, w, siting, bits)
-    for t in (payload_a, payload_b):
-        assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.shape[1] >= fb and (t.shape[1] == 1 or t.stride(1) == 1), \
-            "payloads must be [N, at least frame_bytes] uint8 tensors on the GPU with unit stride within a frame"
-    n = payload_a.shape[0]
-    assert payload_b.shape[0] == n and payload_b.device == payload_a.device, "as many frames in a as in b, on one device"
-    if out is None:
-        out = torch.empty(n, 3, dtype=torch.int64, device=payload_a.device)
-    assert out.is_cuda and out.dtype == torch.int64 and tuple(out.shape) == (n, 3) and out.is_contiguous()
-    sa, sb = (t.stride(0) if n > 1 else 0 for t in (payload_a, payload_b))
+    n, out, sa, sb = _pair_operands(payload_a, payload_b, h, w, siting, bits, out)
     c1, c2 = ssim_constants(bits)
     hb.check(hb.load().ssm_plane_ssim_fwd(payload_a.data_ptr(), payload_b.data_ptr(), sa, sb, n, h, w, siting, V.sample_bytes(bits), c1, c2,
                                           out.data_ptr(), hb.stream_ptr()))
@@ -275,114 +264,141 @@ def nearest_split(hold):
 
 
 class HoldOutResult:
-    """What HoldOutScorer.run() returns.  frames: [(i, k, sse_model (y, u, v), sse_nearest (y, u, v))] of every scored frame, Python ints,
-    in clip order; frames_read, kept, trailing (frames after the last kept one: read, not scored), written (frames handed to the writer,
-    or dropped without one); samples: (Y, U, V) of a frame; hold, bits.
+    """What HoldOutScorer.run() returns.  records: one (i, k, sums) per scored frame, in clip order, sums[metric][column] = (y, u, v) as
+    Python ints - metric "sse" and, with ssim on, "ssim" (the signed fixed-point sums of plane_ssim_host over `windows`, the (Y, U, V)
+    window counts of a frame); column "model", "nearest" and, with mix on, "mix".  frames_read, kept, trailing (frames after the last
+    kept one: read, not scored), written (frames handed to the writer, or dropped without one); samples: (Y, U, V) of a frame; hold, bits.
 
-    With HoldOutScorer(ssim=True) and / or (mix=True) - the flags `ssim` and `mix` here - the rows of `frames` keep their four fields and
-    `more`, a list parallel to `frames`, holds the further sums of each scored frame by metric and column:
-    more[j] = {"sse": {"mix": (y, u, v)}, "ssim": {"model": (y, u, v), "nearest": ..., "mix": ...}}, only the metrics and columns that
-    are on.  SSIM sums are the signed fixed-point sums of plane_ssim_host over `windows`, the (Y, U, V) window counts of a frame."""
+    Two views of the records, readable and assignable (frames first): frames = [(i, k, sse_model (y, u, v), sse_nearest (y, u, v))],
+    and more, a list parallel to it with what those four fields leave out: more[j] = {"sse": {"mix": (y, u, v)}, "ssim": {"model":
+    (y, u, v), "nearest": ..., "mix": ...}}, only the metrics and columns that are on, and [] when neither ssim nor mix is."""
 
     PLANES = ("y", "u", "v", "avg")
+    SHORT = {"model": "model_", "nearest": "near_", "mix": "mix_"}          # the table's column heads
+    # a stats line: per metric its name, its format, and the planes it shows of each column
+    STATS = {"sse": ("psnr", "%.4f", {"model": PLANES, "nearest": ("y",), "mix": ("y", "avg")}),
+             "ssim": ("ssim", "%.6f", {"model": PLANES, "nearest": ("y",), "mix": ("y",)})}
 
     def __init__(self, hold, bits, samples, windows=(0, 0, 0), ssim=False, mix=False):
         self.hold, self.bits, self.samples = hold, bits, tuple(samples)
         self.windows, self.ssim, self.mix = tuple(windows), bool(ssim), bool(mix)
-        self.frames, self.frames_read, self.kept, self.trailing, self.written = [], 0, 0, 0, 0
-        self.more = []
+        self.records, self.frames_read, self.kept, self.trailing, self.written = [], 0, 0, 0, 0
 
     @property
     def columns(self):
         """The columns that are on, in report order."""
         return ("model", "nearest") + (("mix",) if self.mix else ())
 
-    def _ssim4(self, rows, col):
-        """{y, u, v, avg} of the SSIM of column `col` pooled over the rows of `more`: sums over sums of window counts."""
-        tot = [sum(m["ssim"][col][p] for m in rows) for p in range(3)]
-        cnt = [c * len(rows) for c in self.windows]
-        return dict(zip(self.PLANES, [ssim_value(tot[p], cnt[p]) for p in range(3)] + [ssim_value(sum(tot), sum(cnt))]))
+    @property
+    def metrics(self):
+        return ("sse",) + (("ssim",) if self.ssim else ())
+
+    @staticmethod
+    def _row(rec):
+        return rec[0], rec[1], rec[2]["sse"]["model"], rec[2]["sse"]["nearest"]
+
+    @staticmethod
+    def _more(rec):
+        rest = {m: {c: v for c, v in by.items() if m != "sse" or c not in ("model", "nearest")} for m, by in rec[2].items()}
+        return {m: by for m, by in rest.items() if by}
+
+    def add(self, i, k, sums):
+        """Appends a scored frame's record; -> (its row of `frames`, its entry of `more`: {} with ssim and mix off)."""
+        self.records.append((i, k, sums))
+        return self._row(self.records[-1]), self._more(self.records[-1])
+
+    @property
+    def frames(self):
+        return [self._row(rec) for rec in self.records]
+
+    @frames.setter
+    def frames(self, rows):
+        self.records = [(i, k, {"sse": {"model": m, "nearest": nr}}) for i, k, m, nr in rows]
+
+    @property
+    def more(self):
+        return [m for m in map(self._more, self.records) if m]
+
+    @more.setter
+    def more(self, entries):
+        assert len(entries) == len(self.records), "one entry per row of frames"
+        for (_, _, sums), entry in zip(self.records, entries):
+            for metric, by in entry.items():
+                sums.setdefault(metric, {}).update(by)
 
     @property
     def scored(self):
-        return len(self.frames)
+        return len(self.records)
+
+    def _pool4(self, recs, metric, col):
+        """{y, u, v, avg} of column `col` pooled over the records: the PSNR of the summed squared differences over the summed samples,
+        or the SSIM of the summed fx over the summed windows; avg pools the three planes the same way."""
+        tot = [sum(rec[2][metric][col][p] for rec in recs) for p in range(3)]
+        cnt = [c * len(recs) for c in (self.samples if metric == "sse" else self.windows)]
+        value = (lambda t, c: psnr(t, c, self.bits)) if metric == "sse" else ssim_value
+        return dict(zip(self.PLANES, [value(tot[p], cnt[p]) for p in range(3)] + [value(sum(tot), sum(cnt))]))
 
     def pooled(self, k=None):
-        """{"frames": count, "model": {y, u, v, avg}, "nearest": {...}} at position k (None: every position): PSNR of the pooled MSE,
-        sum of sse over the frames / sum of samples; None when no frame is scored there."""
-        rows = [f for f in self.frames if k is None or f[1] == k]
-        if not rows:
+        """{"frames": count, column: {y, u, v, avg}, ...} at position k (None: every position) for every column that is on: PSNR of the
+        pooled MSE, sum of sse over the frames / sum of samples; with ssim on, "ssim": {column: {y, u, v, avg}}, pooled by windows.
+        None when no frame is scored there."""
+        recs = [rec for rec in self.records if k is None or rec[1] == k]
+        if not recs:
             return None
-        out = {"frames": len(rows)}
-        for name, col in (("model", 2), ("nearest", 3)):
-            sse = [sum(f[col][p] for f in rows) for p in range(3)]
-            smp = [s * len(rows) for s in self.samples]
-            out[name] = dict(zip(self.PLANES, [psnr(sse[p], smp[p], self.bits) for p in range(3)] + [psnr_avg(sse, smp, self.bits)]))
-        if self.mix or self.ssim:          # "mix": the PSNR of the third column; "ssim": {column: {y, u, v, avg}}, pooled by windows
-            more = [m for f, m in zip(self.frames, self.more) if k is None or f[1] == k]
-            if self.mix:
-                sse = [sum(m["sse"]["mix"][p] for m in more) for p in range(3)]
-                out["mix"] = dict(zip(self.PLANES, [psnr(sse[p], smp[p], self.bits) for p in range(3)] + [psnr_avg(sse, smp, self.bits)]))
-            if self.ssim:
-                out["ssim"] = {col: self._ssim4(more, col) for col in self.columns}
+        out = {"frames": len(recs)}
+        out.update((col, self._pool4(recs, "sse", col)) for col in self.columns)
+        if self.ssim:
+            out["ssim"] = {col: self._pool4(recs, "ssim", col) for col in self.columns}
         return out
 
     def worst(self):
         """(PSNR-Y of `model`, frame index) of the frame where it is least; None when nothing is scored."""
-        if not self.frames:
+        if not self.records:
             return None
-        return min((psnr(f[2][0], self.samples[0], self.bits), f[0]) for f in self.frames)
+        return min((psnr(sums["sse"]["model"][0], self.samples[0], self.bits), i) for i, _, sums in self.records)
 
     def stats_lines(self):
-        """One line per scored frame, in the manner of ffmpeg's psnr stats file."""
+        """One line per scored frame, in the manner of ffmpeg's psnr stats file: per metric all of `model`, then STATS' planes of the
+        other columns under their names."""
         lines = []
-        for i, k, m, nr in self.frames:
-            lines.append("n:%d k:%d mse_y %.6f psnr_y %.4f psnr_u %.4f psnr_v %.4f psnr_avg %.4f nearest_psnr_y %.4f" % (
-                i, k, m[0] / self.samples[0], psnr(m[0], self.samples[0], self.bits), psnr(m[1], self.samples[1], self.bits),
-                psnr(m[2], self.samples[2], self.bits), psnr_avg(m, self.samples, self.bits), psnr(nr[0], self.samples[0], self.bits)))
-        for j, more in enumerate(self.more if self.mix or self.ssim else ()):          # further fields, appended
-            if self.mix:
-                lines[j] += " mix_psnr_y %.4f mix_psnr_avg %.4f" % (psnr(more["sse"]["mix"][0], self.samples[0], self.bits),
-                                                                   psnr_avg(more["sse"]["mix"], self.samples, self.bits))
-            if self.ssim:
-                s4 = {col: self._ssim4([more], col) for col in self.columns}
-                lines[j] += " ssim_y %.6f ssim_u %.6f ssim_v %.6f ssim_avg %.6f" % tuple(s4["model"][p] for p in self.PLANES)
-                lines[j] += "".join(" %s_ssim_y %.6f" % (col, s4[col]["y"]) for col in self.columns[1:])
+        for rec in self.records:
+            line = "n:%d k:%d mse_y %.6f" % (rec[0], rec[1], rec[2]["sse"]["model"][0] / self.samples[0])
+            for metric in self.metrics:
+                name, fmt, shown = self.STATS[metric]
+                for col in self.columns:
+                    v4 = self._pool4([rec], metric, col)
+                    line += "".join((" %s%s_%s " + fmt) % ("" if col == "model" else col + "_", name, p, v4[p]) for p in shown[col])
+            lines.append(line)
+        return lines
+
+    def _block(self, keys, metric, cols, width, digits):
+        """Lines of the table: a head, then per position the {y, u, v, avg} of the columns `cols` side by side."""
+        cell = "%%%d.%df" % (width, digits)
+        lines = ["%-6s %6s | %s" % ("k", "frames", " | ".join(" ".join("%*s" % (width, self.SHORT[c] + p) for p in self.PLANES) for c in cols))]
+        for name, r in keys:
+            by = r if metric == "sse" else r[metric]
+            lines.append("%-6s %6d | %s" % (name, r["frames"], " | ".join(" ".join(cell % by[c][p] for p in self.PLANES) for c in cols)))
         return lines
 
     def table(self):
-        """The summary as text: a row per position k and one for all, model beside nearest; the worst frame; what was not scored."""
-        head = "%-6s %6s | %8s %8s %8s %8s | %8s %8s %8s %8s" % (("k", "frames") + tuple("model_" + p for p in self.PLANES)[:4]
-                                                                   + tuple("near_" + p for p in self.PLANES))
+        """The summary as text: a row per position k and one for all, model beside nearest; the worst frame; what was not scored; then a
+        block for the PSNR of `mix` and one for the SSIM of every column, where they are on."""
         lines = ["hold-out score, hold = %d: %d frames read, %d kept, %d scored, %d trailing and not scored (PSNR in dB of the pooled MSE, "
                  "peak %d)" % (self.hold, self.frames_read, self.kept, self.scored, self.trailing, (1 << self.bits) - 1)]
-        if not self.frames:
+        if not self.records:
             return "\n".join(lines + ["nothing scored: a held-out frame needs a kept frame on either side, a clip of more than hold = %d "
                                       "frames" % self.hold])
-        lines.append(head)
-        for k in list(range(1, self.hold)) + [None]:
-            r = self.pooled(k)
-            if r is None:
-                continue
-            lines.append("%-6s %6d | %s | %s" % ("all" if k is None else "%d/%d" % (k, self.hold), r["frames"],
-                                                " ".join("%8.3f" % r["model"][p] for p in self.PLANES),
-                                                " ".join("%8.3f" % r["nearest"][p] for p in self.PLANES)))
-        db, i = self.worst()
-        lines.append("worst frame: PSNR-Y %.3f dB at input frame %d" % (db, i))
-        if self.mix or self.ssim:          # further blocks, appended: the lines above are the default table's
-            keys = [(k, self.pooled(k)) for k in list(range(1, self.hold)) + [None]]
-            keys = [("all" if k is None else "%d/%d" % (k, self.hold), r) for k, r in keys if r is not None]
-        if self.mix:
+        keys = [(k, self.pooled(k)) for k in list(range(1, self.hold)) + [None]]
+        keys = [("all" if k is None else "%d/%d" % (k, self.hold), r) for k, r in keys if r is not None]
+        lines += self._block(keys, "sse", self.columns[:2], 8, 3)
+        lines.append("worst frame: PSNR-Y %.3f dB at input frame %d" % self.worst())
+        if self.columns[2:]:
             lines.append("mix: the held-out frame against the cross-fade of its two kept frames at k / hold (PSNR in dB of the pooled MSE)")
-            lines.append("%-6s %6s | %8s %8s %8s %8s" % (("k", "frames") + tuple("mix_" + p for p in self.PLANES)))
-            lines += ["%-6s %6d | %s" % (name, r["frames"], " ".join("%8.3f" % r["mix"][p] for p in self.PLANES)) for name, r in keys]
+            lines += self._block(keys, "sse", self.columns[2:], 8, 3)
         if self.ssim:
-            short = {"model": "model_", "nearest": "near_", "mix": "mix_"}
             lines.append("SSIM (8 x 8 windows at stride 4, as x264 and ffmpeg's ssim filter; sums pooled by windows - `avg` is not ffmpeg's "
                          "plane-size weighting; %d + %d + %d windows a frame)" % self.windows)
-            lines.append("%-6s %6s | %s" % ("k", "frames", " | ".join(" ".join("%10s" % (short[c] + p) for p in self.PLANES) for c in self.columns)))
-            lines += ["%-6s %6d | %s" % (name, r["frames"], " | ".join(" ".join("%10.6f" % r["ssim"][c][p] for p in self.PLANES)
-                                                                           for c in self.columns)) for name, r in keys]
+            lines += self._block(keys, "ssim", self.columns, 10, 6)
             allr = keys[-1][1]["ssim"]
             lines.append("SSIM of all frames in dB, -10 log10(1 - ssim): " + ", ".join(
                 "%s Y %.3f avg %.3f" % (c, ssim_db(allr[c]["y"]), ssim_db(allr[c]["avg"])) for c in self.columns))
@@ -465,21 +481,23 @@ class HoldOutScorer:
             for p in range(valid):
                 for k in range(1, hold):
                     o = p * nt + k - 1
-                    row = ((g0 + p) * hold + k, k, tuple(int(x) for x in np_sums[r][0, o]), tuple(int(x) for x in np_sums[r][1, o]))
-                    res.frames.append(row)
+                    sums = {"sse": {c: tuple(int(x) for x in np_sums[r][ci, o]) for ci, c in enumerate(names)}}
+                    if ssim:
+                        sums["ssim"] = {c: tuple(int(x) for x in np_signed[r][cols + ci, o]) for ci, c in enumerate(names)}
+                    row, more = res.add((g0 + p) * hold + k, k, sums)
                     if on_frame is not None:
                         on_frame(*row)
-                    if ssim or mix:
-                        more = {}
-                        if mix:
-                            more["sse"] = {"mix": tuple(int(x) for x in np_sums[r][2, o])}
-                        if ssim:
-                            more["ssim"] = {c: tuple(int(x) for x in np_signed[r][cols + ci, o]) for ci, c in enumerate(names)}
-                        res.more.append(more)
-                        if on_scores is not None:
-                            on_scores(row[0], row[1], more)
+                    if more and on_scores is not None:
+                        on_scores(row[0], row[1], more)
             for kind, row in V.pass_order(valid, nt):
                 yield np_out[r][row] if kind == "interp" else np_in[r][row]
+
+        def compare(column, a, b, rows):
+            """Queues, on the current stream, the squared differences of payloads a against b into rows `rows` of column `column` of the
+            running pass's sums (stream k), and with ssim on their SSIM into the same rows of the column's SSIM block."""
+            plane_sse(a, b, h, w, siting, bits, out=dev_sums[k][column, rows])
+            if ssim:
+                plane_ssim(a, b, h, w, siting, bits, out=dev_sums[k][cols + column, rows])
 
         res.written = 1
         with V.PassRing(depth, writer, lambda: torch.cuda.synchronize(dev)) as ring:
@@ -523,17 +541,12 @@ class HoldOutScorer:
                     for q in range(valid + 1):          # kept row q of dev_in[k]: the right frame of group q - 1, the left one of group q
                         lo, hi = max(0, (q - 1) * nt + nl), min(m, q * nt + nl)
                         if hi > lo:
-                            plane_sse(dev_held[k][lo:hi], dev_in[k][q:q + 1].expand(hi - lo, fb), h, w, siting, bits, out=dev_sums[k][1, lo:hi])
-                            if ssim:
-                                plane_ssim(dev_held[k][lo:hi], dev_in[k][q:q + 1].expand(hi - lo, fb), h, w, siting, bits,
-                                           out=dev_sums[k][cols + 1, lo:hi])
+                            compare(1, dev_held[k][lo:hi], dev_in[k][q:q + 1].expand(hi - lo, fb), slice(lo, hi))
                     if mix:
                         for q in range(valid):          # group q: kept rows q (left) and q + 1 (right) of dev_in[k], k = 1 .. hold - 1
                             payload_mix(dev_in[k][q:q + 1].expand(nt, fb), dev_in[k][q + 1:q + 2].expand(nt, fb), 1, 1, hold, bits,
                                         out=dev_mix[k][q * nt:(q + 1) * nt])
-                        plane_sse(dev_mix[k][:m], dev_held[k][:m], h, w, siting, bits, out=dev_sums[k][2, :m])
-                        if ssim:
-                            plane_ssim(dev_mix[k][:m], dev_held[k][:m], h, w, siting, bits, out=dev_sums[k][cols + 2, :m])
+                        compare(2, dev_mix[k][:m], dev_held[k][:m], slice(m))
                     dev_in[(j + 1) % n][0].copy_(dev_in[k][pb])
                     ingested[k].record()
                     x = planes[k]
@@ -541,9 +554,7 @@ class HoldOutScorer:
                     frames = pipe.engines[k].run(img6, t_dev, False)
                     clip.egress(frames, dev_out[k])
                     host_out[r].copy_(dev_out[k], non_blocking=True)
-                    plane_sse(dev_out[k][:m], dev_held[k][:m], h, w, siting, bits, out=dev_sums[k][0, :m])
-                    if ssim:
-                        plane_ssim(dev_out[k][:m], dev_held[k][:m], h, w, siting, bits, out=dev_sums[k][cols, :m])
+                    compare(0, dev_out[k][:m], dev_held[k][:m], slice(m))
                     host_sums[r].copy_(dev_sums[k], non_blocking=True)
                     done[r].record()
                 ring.hand(r, done[r], functools.partial(rows_of, r, valid, (res.kept - 1) - valid))

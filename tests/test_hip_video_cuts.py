@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import video_cut_clips as C  # noqa: E402
-from video_clips import V, clip_file, read_clip  # noqa: E402
+from video_clips import S, V, clip_file, random_payloads, read_clip, synthetic_model  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -23,8 +23,11 @@ DEV = torch.device("cuda:0")
 # (h, w) with N = 3 planes each.  64 x 96: every plane on a 16-byte boundary, whole 16-byte pieces.  4 x 6: less than one piece.
 # 130 x 1030: 133900 bytes = 8 spans of 16 KiB and a part, the last piece 12 bytes; frame 0 takes the unguarded whole-span loads, frames 1
 # and 2 (200850 bytes apart) the byte loads.  45 x 71: frame_bytes = 4851 is odd, frame 1 starts at an odd address.  46 x 70: even, no
-# multiple of 16.
-KERNEL_SIZES = ((64, 96), (4, 6), (130, 1030), (45, 71), (46, 70))
+# multiple of 16.  Then the span cases of tests/test_hip_video_score.py, for the one-plane form of the kernel the two entry points share:
+# 128 x 256 = two spans exactly, 99 x 331 = two spans and one byte, 129 x 127 = a span less one byte.
+SPAN = 16384
+assert 128 * 256 == 2 * SPAN and 99 * 331 == 2 * SPAN + 1 and 129 * 127 == SPAN - 1
+KERNEL_SIZES = ((64, 96), (4, 6), (130, 1030), (45, 71), (46, 70), (128, 256), (99, 331), (129, 127))
 ONES = (1 << 64) - 1
 
 
@@ -84,6 +87,31 @@ def test_operands_may_be_views_of_one_buffer(h, w):
     assert v.luma_sad(wide, buf[1::2], h, w).cpu().numpy().view(np.uint64).tolist() == want(a[::2], a[1::2], h, w)
 
 
+@pytest.mark.parametrize("h,w", [(45, 71), (99, 331)])
+def test_one_kernel_under_luma_sad_and_plane_sse(h, w):
+    """ssm_luma_sad_fwd and ssm_plane_sse_fwd launch one span-sum kernel: with one plane per payload, sums[n], and with three, sums[3 n +
+    p].  On the same 8-bit 4:2:0 operands - three payloads against three, against one row of b, and one row of a against three, which
+    plane_sse takes as a 0-stride expand and luma_sad, which refuses stride 0, as three calls of N = 1 - each equals its own numpy
+    yardstick.  The two meet through the yardsticks alone: over the Y plane sum |d| <= sum d^2 <= 255 sum |d|, of one parity."""
+    v, s = V(), S()
+    a, b = random_payloads(h, w, 0, 1), random_payloads(h, w, 0, 1, seed=1)
+    fb = a.shape[1]
+    ta, tb = torch.from_numpy(a).to(DEV), torch.from_numpy(b).to(DEV)
+    for xa, xb, ha, hb_ in ((ta, tb, a, b), (ta, tb[1:2].expand(3, fb), a, b[[1, 1, 1]]), (ta[2:3].expand(3, fb), tb, a[[2, 2, 2]], b)):
+        want_sad, want_sse = want(ha, hb_, h, w), s.plane_sse_host(ha, hb_, h, w, 0, 8).tolist()
+        assert len(set(want_sad)) == 3 and len({row[0] for row in want_sse}) == 3, "a pair booked under another n would show"
+        sse = torch.full((3, 3), -1, dtype=torch.int64, device=DEV)
+        s.plane_sse(xa, xb, h, w, 0, 8, out=sse)
+        assert sse.cpu().numpy().view(np.uint64).tolist() == want_sse
+        if xa.stride(0) and xb.stride(0):
+            got = v.luma_sad(xa, xb, h, w, out=torch.full((3,), -1, dtype=torch.int64, device=DEV))
+        else:
+            got = torch.cat([v.luma_sad(xa[n:n + 1], xb[n:n + 1], h, w, out=torch.full((1,), -1, dtype=torch.int64, device=DEV)) for n in range(3)])
+        assert got.cpu().numpy().view(np.uint64).tolist() == want_sad
+        for sad_n, (sse_y, _, _) in zip(want_sad, want_sse):
+            assert sad_n <= sse_y <= 255 * sad_n and (sse_y - sad_n) % 2 == 0
+
+
 def test_refusals_by_name():
     from ssm_amd import hipbind as hb
     lib = hb.load()
@@ -121,14 +149,7 @@ RATE = 4
 
 @pytest.fixture(scope="module")
 def model():
-    from models.superslomo_r import FullModel
-    from ssm_amd.config import load_config, synthetic_weight_overrides
-    from ssm_amd.weights import synthetic_state_dict
-    cfg = load_config("superslomo_original.ini", synthetic_weight_overrides())
-    m = FullModel(cfg)
-    m.stage1_model.load_state_dict(synthetic_state_dict(1))
-    m.stage2_model.load_state_dict(synthetic_state_dict(2))
-    return cfg, m.to(DEV).eval()
+    return synthetic_model(DEV)
 
 
 def run(m, cfg, payloads, h, w, **kw):

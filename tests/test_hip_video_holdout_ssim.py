@@ -3,7 +3,6 @@ nothing else: `frames` and the written bytes are those of a run with both off; t
 plane_sse_host and plane_ssim_host) applied on the host to the INPUT payloads; the SSIM sums of `model` are plane_ssim_host on the output of
 the existing VideoInterpolator(upsample_rate=hold) run on the decimated clip, those of `nearest` the yardstick on the input bytes.  Every
 sum is an integer and must be EQUAL.  Synthetic weights: the numbers say nothing about quality."""
-import io
 import os
 import sys
 
@@ -12,77 +11,16 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from video_clips import V, clip_payloads  # noqa: E402
+from video_clips import S, V, clip_payloads, deep_payloads, reference, score, synthetic_model, y4m  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
 
 
-def S():
-    from ssm_amd import video_score
-    return video_score
-
-
 @pytest.fixture(scope="module")
 def model():
-    from models.superslomo_r import FullModel
-    from ssm_amd.config import load_config, synthetic_weight_overrides
-    from ssm_amd.weights import synthetic_state_dict
-    cfg = load_config("superslomo_original.ini", synthetic_weight_overrides())
-    m = FullModel(cfg)
-    m.stage1_model.load_state_dict(synthetic_state_dict(1))
-    m.stage2_model.load_state_dict(synthetic_state_dict(2))
-    return cfg, m.to(DEV).eval()
-
-
-def deep_payloads(n, h, w, tag, seed=5):
-    """A moving synthetic clip in the format of an extended tag (as tests/test_hip_video_holdout.py makes it)."""
-    from ssm_amd.weights import IMAGENET_MEAN, IMAGENET_STD, synthetic_frames_u8
-    v = V()
-    layout, bits = v.EXTENDED_TAGS[tag]
-    rgb = synthetic_frames_u8(n, h, w, seed=seed).numpy().astype(np.float32) / np.float32(255.0)
-    x = (rgb - np.float32(IMAGENET_MEAN)[None, :, None, None]) / np.float32(IMAGENET_STD)[None, :, None, None]
-    return v.frames_to_yuv_host(x, h, w, layout, v.default_matrix(h), v.LIMITED, bits=bits)
-
-
-def y4m(payloads, h, w, tag):
-    v = V()
-    buf = io.BytesIO()
-    with v.Y4MWriter(buf, w, h, rate=(240, 1), aspect=(1, 1), chroma=tag, extended=True) as wr:
-        for p in payloads:
-            wr.write_frame(p)
-    return io.BytesIO(buf.getvalue())
-
-
-def frames_of(data):
-    v = V()
-    r = v.Y4MReader(io.BytesIO(data), extended=True)
-    out, buf = [], np.empty(r.frame_bytes, np.uint8)
-    while r.read_frame_into(buf):
-        out.append(buf.copy())
-    return np.stack(out) if out else np.zeros((0, r.frame_bytes), np.uint8)
-
-
-def score(m, cfg, payloads, h, w, tag, hold, callbacks=None, **kw):
-    """The clip through HoldOutScorer with a writer: (the result, the frames it wrote)."""
-    v = V()
-    r = v.Y4MReader(y4m(payloads, h, w, tag), extended=True)
-    sink = io.BytesIO()
-    wr = v.Y4MWriter.like(sink, r)
-    res = S().HoldOutScorer(m, cfg, hold, **kw).run(r, wr, **(callbacks or {}))
-    assert wr.frames_written == res.written
-    return res, frames_of(sink.getvalue())
-
-
-def reference(m, cfg, payloads, h, w, tag, hold, **kw):
-    """The existing tool on the decimated clip: its output frames."""
-    v = V()
-    groups = (len(payloads) - 1) // hold
-    r = v.Y4MReader(y4m(payloads[:groups * hold + 1:hold], h, w, tag), extended=True)
-    sink = io.BytesIO()
-    v.VideoInterpolator(m, cfg, upsample_rate=hold, **kw).run(r, v.Y4MWriter.like(sink, r))
-    return frames_of(sink.getvalue())
+    return synthetic_model(DEV)
 
 
 def three(x):

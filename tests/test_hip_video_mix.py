@@ -2,28 +2,25 @@
 (ssm_amd.video_score.payload_mix_host).  Integer arithmetic: the bytes must be EQUAL.  What the cases aim at: the division by multiply-shift
 at small, odd and the largest den, rows that start at no particular alignment (the sample-by-sample path), the last piece of a row, a store
 past `samples` or past row N, stride 0 on both operands (the scorer's call), and the refusals."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from video_clips import S, bits_of  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-# A workgroup takes a span of 16 KiB of a row: 16384 samples of one byte, 8192 of two (csrc/ssm_video.hip MIX_SPAN_BYTES).
+# A workgroup takes a span of 16 KiB of a row: 16384 samples of one byte, 8192 of two (csrc/ssm_video.hip SPAN_BYTES).
 SPAN = 16384
 FILL = 0xa7
 # samples of a row: 1; either side of a 16-byte piece; 4851 = a 45 x 71 4:2:0 frame, odd, so that rows 1, 3, ... of bytes start unaligned;
 # either side of a span (of bytes; two spans of words)
 SAMPLES = (1, 15, 16, 17, 4851, SPAN - 1, SPAN, SPAN + 1)
-
-
-def S():
-    from ssm_amd import video_score
-    return video_score
-
-
-def bits_of(sb):
-    return 8 if sb == 1 else 16
 
 
 def rows(n, samples, sb, seed):

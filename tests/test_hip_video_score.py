@@ -2,19 +2,22 @@
 kernel is integer arithmetic: every sum must be EQUAL.  What the cases aim at: a workgroup's span that crosses a plane boundary (single
 samples poked at either end of every plane), planes that start at no particular alignment, a 32-bit sum where 64 bits are needed (the
 16-bit extremes), strides of either sign and of 0, and the refusals."""
+import os
+import sys
 import threading
 
 import numpy as np
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from video_clips import CENTRED, C422, C444, LAYOUTS, S, bits_of, fbytes, random_payloads  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-CENTRED, COSITED, C444, C422 = 0, 1, 2, 3
-LAYOUTS = (CENTRED, COSITED, C444, C422)
 ONES = (1 << 64) - 1
-# A workgroup sums a span of 16 KiB of one plane: 16384 samples of one byte, 8192 of two (csrc/ssm_video.hip SSE_SPAN_BYTES).
+# A workgroup sums a span of 16 KiB of one plane: 16384 samples of one byte, 8192 of two (csrc/ssm_video.hip SPAN_BYTES).
 SPAN = 16384
 # (h, w), N = 3 payloads each.  2 x 2: the chroma of 4:2:0 is 1 x 1.  4 x 6: less than one 16-byte piece per chroma plane.  45 x 71: odd frame
 # bytes at 8 bits in 4:2:0 (4851) - frame 1 and the U plane (at byte 3195) start at odd bytes; at 16 bits the same counts in words.
@@ -24,26 +27,6 @@ SPAN = 16384
 # unaligned.  129 x 127 = 16383 = a span - 1 sample (two spans - 1 in words).
 assert 99 * 331 == 2 * SPAN + 1 and 129 * 127 == SPAN - 1 and 128 * 256 == 2 * SPAN
 SIZES = ((2, 2), (4, 6), (45, 71), (46, 70), (64, 96), (128, 256), (99, 331), (129, 127))
-
-
-def S():
-    from ssm_amd import video_score
-    return video_score
-
-
-def fbytes(h, w, layout, sb):
-    from ssm_amd import video as V
-    return V.frame_bytes(h, w, layout, 8 if sb == 1 else 16)
-
-
-def bits_of(sb):
-    return 8 if sb == 1 else 16
-
-
-def random_payloads(h, w, layout, sb, n=3, seed=0):
-    """n payloads of random bytes: every code of a byte, every one of the 65536 codes of a word."""
-    rng = np.random.RandomState(1000 * h + 10 * w + layout + 7 * sb + seed)
-    return rng.randint(0, 256, size=(n, fbytes(h, w, layout, sb))).astype(np.uint8)
 
 
 def sse(a, b, h, w, layout, sb):

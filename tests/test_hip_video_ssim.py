@@ -3,17 +3,20 @@ The sums are fixed-point integers: every one must be EQUAL.  What the cases aim 
 or misses its last block column or row (single samples poked at either end of the covered area of every plane), trailing rows and columns
 that must not count, planes at no particular alignment (the sample-by-sample loads), 32-bit block sums where 64 bits are needed, the
 signed sum, strides of either sign and of 0, and the refusals."""
+import os
+import sys
 import threading
 
 import numpy as np
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from video_clips import CENTRED, COSITED, C422, C444, LAYOUTS, S, bits_of, fbytes, random_payloads  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda:0")
-CENTRED, COSITED, C444, C422 = 0, 1, 2, 3
-LAYOUTS = (CENTRED, COSITED, C444, C422)
 ONE = 1 << 32
 # A workgroup owns a tile of 31 x 15 windows of one plane, on 32 x 16 blocks of 4 x 4 samples (csrc/ssm_video.hip SSIM_TW, SSIM_TH).
 TW, TH = 31, 15
@@ -32,26 +35,6 @@ SIZES = ((2, 2), (4, 6), (12, 20), (8, 8), (45, 71), (46, 70),
          plane(TW - 1, TH - 1), plane(TW, TH), plane(TW + 1, TH + 1), plane(TW + 1, TH - 1, extra=1), plane(TW - 1, TH + 1, extra=3),
          plane(2 * TW + 1, 2 * TH + 1, extra=2))
 assert plane(TW, TH) == (64, 128) and plane(2 * TW + 1, 2 * TH + 1, extra=2) == (130, 258)
-
-
-def S():
-    from ssm_amd import video_score
-    return video_score
-
-
-def bits_of(sb):
-    return 8 if sb == 1 else 16
-
-
-def fbytes(h, w, layout, sb):
-    from ssm_amd import video as V
-    return V.frame_bytes(h, w, layout, bits_of(sb))
-
-
-def random_payloads(h, w, layout, sb, n=3, seed=0):
-    """n payloads of random bytes: every code of a byte, every one of the 65536 codes of a word."""
-    rng = np.random.RandomState(1000 * h + 10 * w + layout + 7 * sb + seed)
-    return rng.randint(0, 256, size=(n, fbytes(h, w, layout, sb))).astype(np.uint8)
 
 
 def ssim(a, b, h, w, layout, sb, bits=None):
