@@ -650,7 +650,12 @@ int ssm_frames_to_u8_fwd(ssm_view in, unsigned char *frames_hwc, int N, int H, i
  *   ingest  c = h(y, x) of SSM_YUV_420_COSITED, (a0 a1 b1 b2) = (0 1 .5 .5), taken on row y of the chroma plane itself
  *   egress  C[y][cx] = ((C[y][2cx-1] + 2 C[y][2cx]) + C[y][2cx+1]) .25, columns clamped to the crop
  * With sample_bytes = 1 and a layout of the 8-bit entry points the result is theirs, bit for bit (they are this code).
- * SSM_E_ARG as above, and for a layout outside {0, 1, 2, 3}, sample_bytes outside {1, 2} or an odd address of 2-byte samples. */
+ * SSM_E_ARG as above, and for a layout outside {0, 1, 2, 3}, sample_bytes outside {1, 2} or an odd address of 2-byte samples.
+ *
+ * Other matrices.  `matrix` is an index into the caller's table and stays within {0, 1}; the kernels read nothing of a matrix but its
+ * row.  BT.2020 (non-constant luminance, Kr = 0.2627, Kb = 0.0593) comes as a table of its own, ssm_amd.video.yuv_table(bits,
+ * BT2020): [1 matrix][2 ranges][SSM_YUV_ROW] of the same layout, built the same way, its rows at matrix index 0
+ * (ssm_amd.video.table_index).  No Y4M header names the matrix: BT.2020 is the user's choice alone. */
 #define SSM_YUV_ROW 20
 #define SSM_YUV_BT601 0
 #define SSM_YUV_BT709 1
@@ -732,6 +737,39 @@ int ssm_frames_accumulate_fwd(ssm_view src, ssm_view acc, int N, int C, int H, i
 #define SSM_LIGHT_ROW 9
 int ssm_frames_accumulate_light_fwd(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale, const float *mean3,
                                     const float *std3, const float *curve, int encode, void *stream);
+
+/* ---- shutter in the light of HDR clips: BT.2100 PQ and HLG (csrc/ssm_video.hip; beyond the reference's operator surface) ---------------
+ * Camera material of 10 and 12 bits is BT.2020 with a PQ (SMPTE ST 2084) or HLG (ARIB STD-B67) transfer function; neither is a power law
+ * with a linear toe, so they have an entry point and rows of their own.  Both act per channel on R'G'B' after the matrix, on c in [0, 1].
+ * `consts` is a HOST pointer to one row of SSM_HDR_ROW floats, every one evaluated in float64 and rounded once to fp32 by
+ * ssm_amd.video.hdr_light(name); `kind` says which of the two layouts it has.
+ *   SSM_HDR_PQ   the BT.2100 PQ EOTF and its inverse; L in [0, 1] is DISPLAY light as a fraction of 10000 cd/m2 (no OOTF is applied):
+ *       m1 = 2610/16384, m2 = 2523/4096 * 128, c1 = 3424/4096, c2 = 2413/4096 * 32, c3 = 2392/4096 * 32
+ *       [0] 1/m2  [1] c1  [2] c2  [3] c3  [4] 1/m1     decode(c): p = c ^ [0];  L = (max(p - c1, 0) / (c2 - c3 * p)) ^ [4]
+ *       [5] m1  [6] m2  [7] 0                          encode(L): y = L ^ m1;  c = L <= 0 ? 0 : ((c1 + c2 * y) / (1 + c3 * y)) ^ m2
+ *     The formula at L = 0 gives c1 ^ m2 = 7.3e-7, one of the codes in [0, 7.3e-7] that all decode to L = 0 (p <= c1); of those, L <= 0
+ *     encodes to 0: black comes back as black.
+ *   SSM_HDR_HLG  the inverse of the BT.2100 HLG OETF and the OETF; E in [0, 1] is SCENE light, what a shutter integrates (no OOTF):
+ *       a = 0.17883277, b = 1 - 4 a, cc = 0.5 - a ln(4 a)  (b and cc evaluated in float64 from a)
+ *       [0] 1/3  [1] log2(e)/a  [2] cc  [3] b  [4] 1/12    decode(c) = c <= 1/2 ? (c * c) * [0] : (2 ^ ((c - cc) * [1]) + b) * [4]
+ *       [5] a ln 2  [6] 0  [7] 0                           encode(E) = E <= [4] ? sqrt(3 * max(E, 0)) : [5] * log2(12 * E - b) + cc
+ *     The two pieces meet in value and in slope at c = 1/2, E = 1/12; decode(1) = 1 to the digits of a.
+ * ssm_frames_accumulate_hdr_fwd: ssm_frames_accumulate_light_fwd with these curves in place of its own - the same views, the same dec(v)
+ * with its comparison against black, the same steps 1 to 4, the same kernel skeleton, access widths and launch geometry.  Every step
+ * written above is one rounded fp32 operation (no fused multiply-add): x ^ e is 2 ^ (e * log2 x) by v_log_f32, a multiply and
+ * v_exp_f32; n / d is n * v_rcp_f32(d), d within [0.16, 20]; sqrt is v_sqrt_f32; all four 1 ulp instructions by the ISA manual.  The result
+ * is held to an error bound against the float64 evaluation ssm_amd.video.accumulate_hdr_host (tests/test_video_hdr_cpu.py derives it,
+ * tests/test_hip_video_hdr.py asserts it).  Exact, as there: a coded value <= 0 adds exactly 0 (PQ: p = 0, no numerator; HLG: 0 * 0 / 3),
+ * and L = 0 encodes to exactly (0 - mean) / std.  INPUTS MUST BE FINITE.
+ * SSM_E_ARG (nothing is launched) for everything ssm_frames_accumulate_light_fwd refuses - null pointers (consts among them), the sizes,
+ * a row stride shorter than W, init or encode outside {0, 1}, a scale, mean, std or constant that is not finite, a std that is not above
+ * 0, overlapping address ranges - and for a kind outside the two below, a PQ row with an exponent or its reciprocal <= 0, c1 < 0, c3 < 0 or
+ * c2 <= c3, an HLG row with [0], [1], [4] or [5] <= 0. */
+#define SSM_HDR_ROW 8
+#define SSM_HDR_PQ 0
+#define SSM_HDR_HLG 1
+int ssm_frames_accumulate_hdr_fwd(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale, const float *mean3,
+                                  const float *std3, int kind, const float *consts, int encode, void *stream);
 
 /* ---- scene cuts of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) -------------------------------
  * Definition (ssm_amd.video.SceneCuts(threshold), everything in exact integers and fractions).  For the pair of input frames (i, i + 1)

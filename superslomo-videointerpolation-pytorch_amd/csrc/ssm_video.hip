@@ -13,10 +13,12 @@
 //                            the two chroma codes of a plane and row as one store (2 or 4 bytes), when size and alignment allow it
 //   frames_accumulate_kernel the shutter of the streamed loop: N frames summed, in increasing n, into one fp32 accumulator
 //                            that is read at most once and written once per launch; one lane = 4 consecutive pixels of a row of one
-//                            channel (16-byte loads and stores), or one pixel when a view does not allow it.  One kernel, two modes: the
+//                            channel (16-byte loads and stores), or one pixel when a view does not allow it.  Two modes: the
 //                            sum of the coded values as they are, or the sum taken in light - every value denormalised, clamped to [0, 1]
 //                            and decoded by one of the light curves of ssm_amd.video.light_curve before it is added, the mean encoded and
 //                            normalised again by the call that closes an output; the power is v_log_f32, a multiply and v_exp_f32
+//   frames_accumulate_hdr_kernel  the same skeleton (accumulate_lane) with the transfer functions of HDR clips in place of a light curve: the
+//                            BT.2100 PQ EOTF and the inverse HLG OETF and their inverses, by v_log_f32, v_exp_f32, v_rcp_f32, v_sqrt_f32
 //   span_sum_kernel          the sums over pairs of payloads, one kernel under two entry points: per pair and plane the exact sum of a
 //                            lane accumulator's term over the samples as they stand in the payloads.  A workgroup sums SPAN_BYTES = 16 KiB of
 //                            ONE plane, a lane CHUNKS = 4 pieces of 16 bytes per operand (one 16-byte load each; sample by sample where a
@@ -347,24 +349,79 @@ __device__ __forceinline__ float light_encode(float l, float sd, float mean, con
     return (c - mean) / sd;
 }
 
-// What the light mode adds to the kernel's arguments (its channels are three); the coded mode adds nothing.
+// ---- HDR transfer functions as the shutter's light: BT.2100 PQ and HLG (include/ssm_hip.h: SSM_HDR_ROW floats per kind) ------------------
+// Each step below is one rounded fp32 operation; x ^ e is pow_fast, a quotient n / d is n * v_rcp_f32(d) (d stays in [0.16, 20]), the
+// square root v_sqrt_f32, exp and ln are v_exp_f32 and v_log_f32 with log2 e and ln 2 folded into the row's constants on the host.
+struct PqRow {
+    float im2, c1, c2, c3, im1;          // decode: p = c ^ im2;  L = (max(p - c1, 0) / (c2 - c3 p)) ^ im1
+    float m1, m2, pad;                   // encode: y = L ^ m1;  c = ((c1 + c2 y) / (1 + c3 y)) ^ m2, and L <= 0 gives c = 0
+};
+struct HlgRow {
+    float third, kexp, cc, b, twelfth;   // decode: c <= 1/2 ? (c c) third : (2 ^ ((c - cc) kexp) + b) twelfth,  kexp = log2(e) / a
+    float aln2, pad0, pad1;              // encode: L <= twelfth ? sqrt(3 max(L, 0)) : aln2 log2(12 L - b) + cc,  aln2 = a ln 2
+};
+static_assert(sizeof(PqRow) == SSM_HDR_ROW * sizeof(float) && sizeof(HlgRow) == SSM_HDR_ROW * sizeof(float), "HDR row");
+
+__device__ __forceinline__ float quot_fast(float n, float d) { return n * __builtin_amdgcn_rcpf(d); }
+
+// c = 0 gives p = 2 ^ -inf = 0, no numerator and L = 0: black adds no light.
+__device__ __forceinline__ float light_decode(float v, float sd, float mean, float black, const PqRow &k) {
+    const float c = v <= black ? 0.0f : clampf(v * sd + mean, 0.0f, 1.0f);
+    const float p = pow_fast(c, k.im2);
+    const float n = fmaxf(p - k.c1, 0.0f);
+    const float d = k.c2 - k.c3 * p;
+    return pow_fast(quot_fast(n, d), k.im1);
+}
+
+// The formula at L = 0 is c1 ^ m2 = 7.3e-7, a code that decodes to no light as every code below it does: of those codes L <= 0 takes 0,
+// and (0 - mean) / sd is the ingest kernels' black.
+__device__ __forceinline__ float light_encode(float l, float sd, float mean, const PqRow &k) {
+    const float y = pow_fast(l, k.m1);
+    const float n = k.c1 + k.c2 * y;
+    const float d = 1.0f + k.c3 * y;
+    const float p = pow_fast(quot_fast(n, d), k.m2);
+    const float c = l <= 0.0f ? 0.0f : p;
+    return (c - mean) / sd;
+}
+
+__device__ __forceinline__ float light_decode(float v, float sd, float mean, float black, const HlgRow &k) {
+    const float c = v <= black ? 0.0f : clampf(v * sd + mean, 0.0f, 1.0f);
+    const float lo = (c * c) * k.third;
+    const float e = __builtin_amdgcn_exp2f((c - k.cc) * k.kexp);
+    const float hi = (e + k.b) * k.twelfth;
+    return c <= 0.5f ? lo : hi;
+}
+
+__device__ __forceinline__ float light_encode(float l, float sd, float mean, const HlgRow &k) {
+    const float lo = __builtin_amdgcn_sqrtf(3.0f * fmaxf(l, 0.0f));          // l = 0: c = 0
+    const float hi = k.aln2 * __builtin_amdgcn_logf(12.0f * l - k.b) + k.cc;
+    const float c = l <= k.twelfth ? lo : hi;
+    return (c - mean) / sd;
+}
+
+// What a mode in light adds to the kernel's arguments (its channels are three); the coded mode adds nothing.  Row is the curve's row and
+// picks light_decode / light_encode by its type: LightRow (Curve<true>), PqRow or HlgRow (HdrCurve).
+template <typename Row> struct InLight { Norm3 nm; Row row; int encode; };
 template <bool Light> struct Curve {};
-template <> struct Curve<true> { Norm3 nm; LightRow row; int encode; };
+template <> struct Curve<true> : InLight<LightRow> {};
+template <int Kind> struct HdrCurve;
+template <> struct HdrCurve<SSM_HDR_PQ> : InLight<PqRow> {};
+template <> struct HdrCurve<SSM_HDR_HLG> : InLight<HlgRow> {};
 
 // V consecutive pixels of a row as one access: 16 bytes (V = 4: W % 4 == 0 and both views 16-byte aligned) or one float
 template <int V> struct alignas(4 * V) Px { float f[V]; };
 
 // s = init ? dec(src[0]) : acc + dec(src[0]);  s = s + dec(src[n]), n = 1 .. N-1;  r = s * scale;  acc = enc(r) - one rounded fp32 operation
-// per step (the file is compiled without contraction).  Coded (Light = false): dec and enc are the identity, the order of
-// ssm_amd.video.accumulate_host, bit for bit.  Light: dec is light_decode of the channel (blockIdx.z, three of them), enc light_encode on the
+// per step (the file is compiled without contraction).  Coded (Cv = Curve<false>): dec and enc are the identity, the order of
+// ssm_amd.video.accumulate_host, bit for bit.  In light: dec is light_decode of the channel (blockIdx.z, three of them), enc light_encode on the
 // call that closes an output (cv.encode) and the identity before.  The loads of the N frames do not depend on one another and the one
 // store comes last, so the unrolled loop keeps several loads in flight per lane; the accumulator is read at most once and written once.
 // The arithmetic on a Px<4> stays four scalar v_add_f32 / v_mul_f32 per step only because the Makefile builds every file with
 // -fno-slp-vectorize (check_isa.sh fails the build on any v_pk_*_f32): a plain hipcc -O3 of this file packs it into v_pk_add_f32 /
 // v_pk_mul_f32.
-template <int V, bool Light>          // pixels per lane: 4 or 1
-__global__ __launch_bounds__(256) void frames_accumulate_kernel(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale,
-                                                                Curve<Light> cv) {
+template <int V, typename Cv>          // pixels per lane: 4 or 1; the mode's arguments
+__device__ __forceinline__ void accumulate_lane(const ssm_view &src, const ssm_view &acc, int N, int H, int W, int init, float scale, const Cv &cv) {
+    constexpr bool Light = !std::is_same_v<Cv, Curve<false>>;
     const int x = (blockIdx.x * 64 + threadIdx.x) * V, y = blockIdx.y * 4 + threadIdx.y, c = blockIdx.z;
     if (x >= W || y >= H) return;          // V = 4: W % 4 == 0, so x + 3 < W
     float mean = 0.0f, sd = 1.0f, black = 0.0f;          // Light alone reads them
@@ -399,6 +456,19 @@ __global__ __launch_bounds__(256) void frames_accumulate_kernel(ssm_view src, ss
 #pragma unroll
             for (int i = 0; i < V; ++i) v.f[i] = light_encode(v.f[i], sd, mean, cv.row);
     *reinterpret_cast<Px<V> *>(a) = v;
+}
+
+// One skeleton, two kernels: the coded sum and the power-law curves, and the HDR transfer functions (Kind: SSM_HDR_PQ or SSM_HDR_HLG).
+template <int V, bool Light>
+__global__ __launch_bounds__(256) void frames_accumulate_kernel(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale,
+                                                                Curve<Light> cv) {
+    accumulate_lane<V>(src, acc, N, H, W, init, scale, cv);
+}
+
+template <int V, int Kind>
+__global__ __launch_bounds__(256) void frames_accumulate_hdr_kernel(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale,
+                                                                    HdrCurve<Kind> cv) {
+    accumulate_lane<V>(src, acc, N, H, W, init, scale, cv);
 }
 
 // ---- sums over pairs of payloads: what the kernels share -------------------------------------------------------------------------------
@@ -910,13 +980,42 @@ extern "C" int ssm_frames_to_yuvx_fwd(ssm_view in, void *frames_yuv, int N, int 
                          layout, sample_bytes, stream);
 }
 
-// What the light entry point is given beside the coded one's arguments.
+// What the entry points in light are given beside the coded one's arguments.  kind: CURVE_ROW for a row of SSM_LIGHT_ROW floats (the
+// power-law curves), or what the caller of ssm_frames_accumulate_hdr_fwd gave (SSM_HDR_*: a row of SSM_HDR_ROW floats).
+enum { CURVE_ROW = -1 };
 struct LightIn {
     const float *mean3, *std3, *curve;
-    int encode;
+    int encode, kind;
 };
 
-// The checks and the launch of the two accumulate entry points, in one order; `light` null: the coded sum over C channels.
+// The rows' own conditions: finite constants, and the signs that keep every logarithm's and quotient's operand where the curve is defined.
+static int check_curve(const char *name, const LightRow &k) {
+    bool finite = true;
+    for (int i = 0; i < SSM_LIGHT_ROW; ++i) finite = finite && std::isfinite(reinterpret_cast<const float *>(&k)[i]);
+    SSM_REQUIRE(finite && k.g > 0.0f && k.ig > 0.0f && k.slope > 0.0f && k.islope > 0.0f,
+                "%s: curve row with g=%g (1/g=%g), slope=%g (1/slope=%g): need finite constants, g > 0 and slope > 0", name, (double)k.g,
+                (double)k.ig, (double)k.slope, (double)k.islope);
+    return SSM_OK;
+}
+static bool finite_row(const void *row) {
+    bool finite = true;
+    for (int i = 0; i < SSM_HDR_ROW; ++i) finite = finite && std::isfinite(static_cast<const float *>(row)[i]);
+    return finite;
+}
+static int check_curve(const char *name, const PqRow &k) {
+    SSM_REQUIRE(finite_row(&k) && k.m1 > 0.0f && k.im1 > 0.0f && k.m2 > 0.0f && k.im2 > 0.0f && k.c1 >= 0.0f && k.c3 >= 0.0f && k.c2 > k.c3,
+                "%s: pq row with m1=%g (1/m1=%g), m2=%g (1/m2=%g), c1=%g, c2=%g, c3=%g: need finite constants, exponents > 0, c1 >= 0 and "
+                "c2 > c3 >= 0", name, (double)k.m1, (double)k.im1, (double)k.m2, (double)k.im2, (double)k.c1, (double)k.c2, (double)k.c3);
+    return SSM_OK;
+}
+static int check_curve(const char *name, const HlgRow &k) {
+    SSM_REQUIRE(finite_row(&k) && k.third > 0.0f && k.kexp > 0.0f && k.twelfth > 0.0f && k.aln2 > 0.0f,
+                "%s: hlg row with 1/3=%g, log2(e)/a=%g, 1/12=%g, a ln 2=%g: need finite constants and these four > 0", name, (double)k.third,
+                (double)k.kexp, (double)k.twelfth, (double)k.aln2);
+    return SSM_OK;
+}
+
+// The checks and the launch of the three accumulate entry points, in one order; `light` null: the coded sum over C channels.
 static int frames_accumulate(const char *name, const char *entry, ssm_view src, ssm_view acc, int N, int C, int H, int W, int init, float scale,
                              const LightIn *light, void *stream) {
     SSM_REQUIRE(src.ptr && acc.ptr && (!light || (light->mean3 && light->std3 && light->curve)), "%s: null pointer", name);
@@ -929,20 +1028,23 @@ static int frames_accumulate(const char *name, const char *entry, ssm_view src, 
     SSM_REQUIRE(init == 0 || init == 1, "%s: init must be 0 or 1 (got %d)", name, init);
     if (light) SSM_REQUIRE(light->encode == 0 || light->encode == 1, "%s: encode must be 0 or 1 (got %d)", name, light->encode);
     SSM_REQUIRE(std::isfinite(scale), "%s: scale must be finite (got %g)", name, (double)scale);
+    const int kind = light ? light->kind : CURVE_ROW;
+    SSM_REQUIRE(kind == CURVE_ROW || kind == SSM_HDR_PQ || kind == SSM_HDR_HLG, "%s: kind %d not in {0 (pq), 1 (hlg)}", name, kind);
     Curve<true> cv;
+    HdrCurve<SSM_HDR_PQ> pq;
+    HdrCurve<SSM_HDR_HLG> hlg;
     if (light) {
-        const float *mean3 = light->mean3, *std3 = light->std3, *curve = light->curve;
+        const float *mean3 = light->mean3, *std3 = light->std3;
         for (int c = 0; c < 3; ++c)
             SSM_REQUIRE(std::isfinite(mean3[c]) && std::isfinite(std3[c]) && std3[c] > 0.0f,
                         "%s: mean %g / std %g of channel %d: need finite values and a std above 0", name, (double)mean3[c], (double)std3[c], c);
-        cv.nm = norm_of(mean3, std3), cv.encode = light->encode;
-        for (int i = 0; i < SSM_LIGHT_ROW; ++i) reinterpret_cast<float *>(&cv.row)[i] = curve[i];
-        bool finite = true;
-        for (int i = 0; i < SSM_LIGHT_ROW; ++i) finite = finite && std::isfinite(curve[i]);
-        const LightRow &k = cv.row;
-        SSM_REQUIRE(finite && k.g > 0.0f && k.ig > 0.0f && k.slope > 0.0f && k.islope > 0.0f,
-                    "%s: curve row with g=%g (1/g=%g), slope=%g (1/slope=%g): need finite constants, g > 0 and slope > 0", name, (double)k.g,
-                    (double)k.ig, (double)k.slope, (double)k.islope);
+        const auto fill = [&](auto &to, int floats) {          // the mode's arguments from the caller's; then the row's own conditions
+            to.nm = norm_of(mean3, std3), to.encode = light->encode;
+            for (int i = 0; i < floats; ++i) reinterpret_cast<float *>(&to.row)[i] = light->curve[i];
+            return check_curve(name, to.row);
+        };
+        if (const int e = kind == CURVE_ROW ? fill(cv, SSM_LIGHT_ROW) : (kind == SSM_HDR_PQ ? fill(pq, SSM_HDR_ROW) : fill(hlg, SSM_HDR_ROW)))
+            return e;
     }
     long long s0, s1, a0, a1;
     view_range(src, N, C, H, W, &s0, &s1);
@@ -950,12 +1052,17 @@ static int frames_accumulate(const char *name, const char *entry, ssm_view src, 
     SSM_REQUIRE(s1 <= a0 || a1 <= s0, "%s: src and acc overlap (%lld bytes apart)", name, a0 - s0);
     const bool vec = W % 4 == 0 && view_aligned(src, 4) && view_aligned(acc, 4);
     const dim3 grid(((vec ? W / 4 : W) + 63) / 64, (H + 3) / 4, C);
-    const auto go = [&](auto mode) {          // Curve<Light>
-        constexpr bool Light = std::is_same_v<decltype(mode), Curve<true>>;
-        SSM_LAUNCH(vec ? frames_accumulate_kernel<4, Light> : frames_accumulate_kernel<1, Light>, grid, dim3(64, 4), 0, (hipStream_t)stream, src,
-                   acc, N, H, W, init, scale, mode);
+    const auto go = [&](auto k4, auto k1, auto mode) {          // the kernel at four pixels and at one pixel per lane, its mode's arguments
+        SSM_LAUNCH(vec ? k4 : k1, grid, dim3(64, 4), 0, (hipStream_t)stream, src, acc, N, H, W, init, scale, mode);
     };
-    light ? go(cv) : go(Curve<false>{});
+    if (!light)
+        go(frames_accumulate_kernel<4, false>, frames_accumulate_kernel<1, false>, Curve<false>{});
+    else if (kind == CURVE_ROW)
+        go(frames_accumulate_kernel<4, true>, frames_accumulate_kernel<1, true>, cv);
+    else if (kind == SSM_HDR_PQ)
+        go(frames_accumulate_hdr_kernel<4, SSM_HDR_PQ>, frames_accumulate_hdr_kernel<1, SSM_HDR_PQ>, pq);
+    else
+        go(frames_accumulate_hdr_kernel<4, SSM_HDR_HLG>, frames_accumulate_hdr_kernel<1, SSM_HDR_HLG>, hlg);
     return ssm::check_launch(entry);
 }
 
@@ -965,8 +1072,15 @@ extern "C" int ssm_frames_accumulate_fwd(ssm_view src, ssm_view acc, int N, int 
 
 extern "C" int ssm_frames_accumulate_light_fwd(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale, const float *mean3,
                                                const float *std3, const float *curve, int encode, void *stream) {
-    const LightIn light = {mean3, std3, curve, encode};
+    const LightIn light = {mean3, std3, curve, encode, CURVE_ROW};
     return frames_accumulate("frames_accumulate_light", "ssm_frames_accumulate_light_fwd", src, acc, N, 3, H, W, init, scale, &light, stream);
+}
+
+extern "C" int ssm_frames_accumulate_hdr_fwd(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale, const float *mean3,
+                                             const float *std3, int kind, const float *consts, int encode, void *stream) {
+    const LightIn light = {mean3, std3, consts, encode, kind};
+    SSM_REQUIRE(kind != CURVE_ROW, "frames_accumulate_hdr: kind %d not in {0 (pq), 1 (hlg)}", kind);
+    return frames_accumulate("frames_accumulate_hdr", "ssm_frames_accumulate_hdr_fwd", src, acc, N, 3, H, W, init, scale, &light, stream);
 }
 
 

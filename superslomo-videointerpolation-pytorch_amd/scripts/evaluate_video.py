@@ -67,7 +67,7 @@ def getargs(argv=None):
     parser.add_argument("--mix", action="store_true",
                         help="Also score the cross-fade of the two kept frames against the held-out frame: the frame-blending baseline.")
     parser.add_argument("--output", default=None, help="Also write the interpolated decimated clip as .y4m (- for stdout). Default: frames are dropped.")
-    parser.add_argument("--matrix", choices=sorted(V.MATRICES), default=None, help="Y'CbCr matrix (default: bt709 from 720 rows up, else bt601).")
+    parser.add_argument("--matrix", choices=sorted(V.MATRICES), default=None, help="Y'CbCr matrix (default: bt709 from 720 rows up, else bt601; bt2020, non-constant luminance, only when asked for).")
     parser.add_argument("--range", choices=sorted(V.RANGES), default=None, dest="color_range",
                         help="Code range (default: the header's XCOLORRANGE tag, else limited).")
     parser.add_argument("--flow_scale", type=int, choices=(1, 2, 4), default=1,

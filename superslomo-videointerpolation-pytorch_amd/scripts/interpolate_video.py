@@ -27,12 +27,15 @@ frame's own bytes; pairs that get no frame are not run.  Neither goes together w
 over the first DEG / 360 of its interval, as a camera at the output rate with that shutter angle would have blurred it - 60 -> 24 with
 --shutter 180 instead of dropped frames that strobe, slow motion with a chosen amount of blur, or blurred / sharp frame pairs from
 high-rate footage.  Every output frame then comes from the GPU, input frames are no longer passed through.  The header's rate is what it
-is without --shutter.  --shutter_light coded|bt709|srgb|bt1886 says of what the mean is taken: of the gamma-coded R'G'B' values, as a
+is without --shutter.  --shutter_light coded|bt709|srgb|bt1886|pq|hlg says of what the mean is taken: of the gamma-coded R'G'B' values, as a
 frame-mixing filter does (coded, the default), or of the light they stand for under that curve, which is what a sensor integrates - the
 mean of codes 0 and 255 is 128 on the codes and 188 in light under sRGB, so streaks of bright objects over a dark ground keep their
 brightness.  Which curve a clip wants depends on how it was graded (bt709: camera-referred material; srgb, bt1886: material mastered on a
 display); no Y4M header says, so the choice is yours.  Values the network synthesises outside [0, 1] are clipped before they count as
-light.  The curve acts on R'G'B' after the matrix and is independent of --matrix and --range.
+light.  The curve acts on R'G'B' after the matrix and is independent of --matrix and --range.  --shutter_light pq|hlg are the transfer
+functions of HDR clips (BT.2100; what phones and cameras record as 10-bit HLG, and graded HDR masters as PQ, usually with --matrix
+bt2020): pq is the PQ EOTF, display light up to 10000 cd/m2, hlg the inverse of the HLG OETF, scene light; no OOTF is applied to either.
+The coded mean darkens a PQ highlight's streak by more than a factor of 20 in cd/m2, where it costs 128 against 188 codes under sRGB.
 
 --scene_cut T (a decimal or a fraction in (0, 1]; no default value - the option is off unless given): every pair of input frames is also
 scored by ssm_amd.video.SceneCuts from the sum of its absolute luma differences (taken on the GPU, beside the pair's own work), and a pair
@@ -87,14 +90,14 @@ def getargs(argv=None):
                              "over DEG / 360 of its interval. Needs --fps or --speed. Default: off.")
     parser.add_argument("--shutter_samples", type=int, default=8, metavar="S",
                         help="With --shutter: sub-frames per output frame (a convention, not a measured optimum). Default 8.")
-    parser.add_argument("--shutter_light", choices=V.SHUTTER_LIGHTS, default="coded",
+    parser.add_argument("--shutter_light", choices=V.SHUTTER_LIGHTS + V.HDR_LIGHTS, default="coded",
                         help="With --shutter: average the coded values (coded) or the light they stand for under a curve (bt709, srgb, "
-                             "bt1886); which curve fits depends on how the clip was graded. Default coded.")
+                             "bt1886; for HDR clips pq, hlg); which curve fits depends on how the clip was graded. Default coded.")
     parser.add_argument("--scene_cut", type=_named(V.parse_scene_cut), default=None, metavar="T",
                         help="Scene-cut threshold as a decimal or a fraction in (0, 1] (0.1, 1/10): a pair of input frames whose score reaches it "
                              "gets copies of its input frames instead of synthesised ones. A convention, no measured optimum; no default "
                              "value: off unless given. Not together with --shutter.")
-    parser.add_argument("--matrix", choices=sorted(V.MATRICES), default=None, help="Y'CbCr matrix (default: bt709 from 720 rows up, else bt601).")
+    parser.add_argument("--matrix", choices=sorted(V.MATRICES), default=None, help="Y'CbCr matrix (default: bt709 from 720 rows up, else bt601; bt2020, non-constant luminance, only when asked for).")
     parser.add_argument("--range", choices=sorted(V.RANGES), default=None, dest="color_range",
                         help="Code range (default: the header's XCOLORRANGE tag, else limited).")
     parser.add_argument("--slowmo", action="store_true", help="Keep the input's frame rate in the output header: slow motion.")

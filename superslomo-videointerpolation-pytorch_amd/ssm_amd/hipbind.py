@@ -17,6 +17,8 @@ SSM_PADX = 4
 SSM_PADY = 3
 SSM_TAIL_SLACK_FLOATS = 1 << 16
 SSM_LIGHT_ROW = 9      # floats in a light curve's row (include/ssm_hip.h; ssm_amd.video.light_curve)
+SSM_HDR_ROW = 8        # floats in an HDR transfer function's row, and its two kinds (include/ssm_hip.h; ssm_amd.video.hdr_light)
+SSM_HDR_PQ, SSM_HDR_HLG = 0, 1
 SSM_FLAG_LRELU = 1
 SSM_FLAG_MASK = 8      # the `add` view is a mask source: out = conv(x) * (add > 0 ? 1 : slope) (include/ssm_hip.h)
 
@@ -220,6 +222,7 @@ SIGNATURES = {
     "ssm_tile_stitch_fwd": (_c_int, [SsmView, SsmView] + [_c_int] * 14 + [_vp]),
     "ssm_frames_accumulate_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _vp]),
     "ssm_frames_accumulate_light_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _vp, _vp, _c_int, _vp]),
+    "ssm_frames_accumulate_hdr_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _vp, _c_int, _vp, _c_int, _vp]),
     "ssm_luma_sad_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_int, _vp, _vp]),
     "ssm_plane_sse_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "ssm_plane_ssim_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_longlong,
@@ -436,6 +439,19 @@ def frames_accumulate_light(src, acc, init, scale, mean, std, curve, encode):
     check(load().ssm_frames_accumulate_light_fwd(view_of(src), view_of(acc), N, H, W, int(init), float(scale), _floats(mean, 3, "mean"),
                                                  _floats(std, 3, "std"), _floats(curve, SSM_LIGHT_ROW, "a light curve's row"), int(encode),
                                                  stream_ptr()))
+    return acc
+
+
+def frames_accumulate_hdr(src, acc, init, scale, mean, std, kind, consts, encode):
+    """ssm_frames_accumulate_hdr_fwd: frames_accumulate_light with a BT.2100 transfer function in place of a power-law curve.  kind is
+    SSM_HDR_PQ or SSM_HDR_HLG and `consts` that kind's row (ssm_amd.video.hdr_light(name) gives both); include/ssm_hip.h has the
+    definitions; yardstick: ssm_amd.video.accumulate_hdr_host."""
+    N, C, H, W = src.shape
+    assert C == 3 and acc.dim() == 4 and tuple(acc.shape) == (1, 3, H, W), \
+        "frames %s and accumulator %s must be [N,3,H,W] and [1,3,H,W]" % (tuple(src.shape), tuple(acc.shape))
+    check(load().ssm_frames_accumulate_hdr_fwd(view_of(src), view_of(acc), N, H, W, int(init), float(scale), _floats(mean, 3, "mean"),
+                                               _floats(std, 3, "std"), int(kind), _floats(consts, SSM_HDR_ROW, "an HDR light's row"),
+                                               int(encode), stream_ptr()))
     return acc
 
 

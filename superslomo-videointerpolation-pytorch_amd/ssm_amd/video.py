@@ -5,6 +5,7 @@
                           with extended=True also 4:2:2 and 9 to 16 bits per sample (C422, C420p10, C422p10, C444p12, ...: EXTENDED_TAGS)
   yuv_table               the conversion constants of a bit depth, float64 rounded once to fp32: what csrc/ssm_video.hip and the
                           yardsticks both read; `bits` (the significant bits of a sample, 8 to 16) lives in this table alone
+  table_index             BT.2020 (MATRICES["bt2020"]) has a table of its own, yuv_table(bits, BT2020): the index of a matrix's rows in its table
   yuv_to_frames_host /    numpy float32 yardsticks that spell the two kernels' operations in the kernels' order: the fixed points the
   frames_to_yuv_host      kernels are held to bit for bit (as scripts/utils/flo_utils.py is for csrc/ssm_flow.hip)
   frames_from_yuv /       the kernels: payloads on the device <-> the path's normalised, padded fp32 planes, in the visualiser's
@@ -22,6 +23,9 @@
   light_curve /           the shutter in linear light: the same kernel's second mode (ssm_frames_accumulate_light_fwd, held to an error bound
   accumulate_light_host   against this float64 yardstick), the sub-frames decoded to light by one of LIGHT_CURVES before they are summed, the
                           mean encoded again - VideoInterpolator(shutter_light=); "coded", the default, is the mean of the coded values
+  hdr_light               the shutter in the light of HDR clips, "pq" and "hlg" (HDR_LIGHTS): the kind and row ssm_frames_accumulate_hdr_fwd takes
+  hdr_decode_host / hdr_encode_host   the BT.2100 PQ EOTF and inverse HLG OETF and their inverses, in float64 or in the kernel's fp32 steps
+  accumulate_hdr_host     the float64 yardstick of ssm_frames_accumulate_hdr_fwd, accumulate_light_host with those in place of a curve's row
   luma_sad_host / luma_sad   scene cuts: per frame pair the exact sum of |difference| of the 8-bit Y planes, by numpy (the yardstick) and by
   / SceneCuts             ssm_luma_sad_fwd on the payloads as they stand on the device; the decision from those sums in Fractions, with no
                           GPU in it - VideoInterpolator(scene_cut=): at a cut the output repeats the nearer input frame instead of a morph
@@ -36,7 +40,7 @@ read as C420 is, centred.  The fp32 pipeline between ingest and egress is the sa
 Out of scope: codecs, audio, output in another format than the input (8-bit in, 10-bit out), mono, 4:1:1 and alpha planes, a siting
 override for C420pB, big-endian samples, scene cuts above 8 bits (ssm_luma_sad_fwd and the score's / 255 are 8-bit), the recurrent
 configuration (N_FRAMES > 2); shutter weights other than
-the box, a light curve chosen from the clip's tags, HDR transfer curves (PQ, HLG), a shutter centred on the frame's instant or open for longer than the frame interval,
+the box, a light curve chosen from the clip's tags, an OOTF for the HDR lights (PQ display light and HLG scene light are taken as they are), BT.2020 constant luminance, a shutter centred on the frame's instant or open for longer than the frame interval,
 variable-rate input, speeds that change within a clip; a default scene-cut threshold, fades and dissolves, cuts judged on chroma,
 skipping the GPU work of a cut pair, scene cuts together with a shutter; a measure of quality other than video_score's PSNR against
 held-out frames (SSIM, VMAF), and that score for the timeline, shutter and scene-cut outputs.
@@ -55,11 +59,11 @@ import torch
 from . import hipbind as hb
 from .frames import _f3, cfg_mean_std, padded_dims
 
-BT601, BT709 = 0, 1
+BT601, BT709, BT2020 = 0, 1, 2          # BT2020: non-constant luminance; a name of this module, not an index the entry points take
 LIMITED, FULL = 0, 1
 CENTRED, COSITED, C444, C422 = 0, 1, 2, 3          # chroma siting / plane layout (include/ssm_hip.h SSM_YUV_*)
 YUV_ROW = 20
-MATRICES = {"bt601": BT601, "bt709": BT709}
+MATRICES = {"bt601": BT601, "bt709": BT709, "bt2020": BT2020}
 RANGES = {"limited": LIMITED, "full": FULL}
 # Y4M colour-space tags: accepted -> siting; refused ones are named in the error
 CHROMA_TAGS = {"420": CENTRED, "420jpeg": CENTRED, "420mpeg2": COSITED, "444": C444}
@@ -89,7 +93,8 @@ def sample_bytes(bits):
     if isinstance(bits, bool) or int(bits) != bits or not 8 <= bits <= 16:
         raise ValueError("bits = %r: a sample has 8 to 16 significant bits" % (bits,))
     return 1 if bits == 8 else 2
-_KRKB = {BT601: (0.299, 0.114), BT709: (0.2126, 0.0722)}
+_KRKB = {BT601: (0.299, 0.114), BT709: (0.2126, 0.0722)}          # the rows of the table every entry point has always been given
+_KRKB_OWN = {BT2020: (0.2627, 0.0593)}                            # matrices with a table of their own: one matrix, its rows at index 0
 
 
 # Light curves (include/ssm_hip.h): name -> (thr, slope, a, g) of  decode(c) = c <= thr ? c / slope : ((c + a) / (1 + a)) ^ g  and
@@ -115,21 +120,62 @@ def light_curve(name):
     return np.array([thr, 1.0 / slope, a, 1.0 / (1.0 + a), g, thr / slope, slope, 1.0 + a, 1.0 / g], dtype=np.float64).astype(np.float32)
 
 
+# HDR transfer functions as the shutter's light (include/ssm_hip.h): BT.2100 PQ - display light as a fraction of 10000 cd/m2 - and HLG -
+# scene light - neither with an OOTF.  They are no power laws with a linear toe, so they have a table, a row layout and an entry point of
+# their own (ssm_frames_accumulate_hdr_fwd); LIGHT_CURVES and SHUTTER_LIGHTS stay what they were.  The PQ constants are dyadic fractions,
+# exact in fp32; HLG's b and cc are evaluated in float64 from a, not taken from their printed digits.
+PQ_M1, PQ_M2 = 2610.0 / 16384.0, 2523.0 / 4096.0 * 128.0
+PQ_C1, PQ_C2, PQ_C3 = 3424.0 / 4096.0, 2413.0 / 4096.0 * 32.0, 2392.0 / 4096.0 * 32.0
+HLG_A = 0.17883277
+HLG_B = 1.0 - 4.0 * HLG_A
+HLG_CC = 0.5 - HLG_A * float(np.log(4.0 * HLG_A))
+HDR_ROW = hb.SSM_HDR_ROW
+HDR_KINDS = {"pq": hb.SSM_HDR_PQ, "hlg": hb.SSM_HDR_HLG}
+HDR_LIGHTS = tuple(HDR_KINDS)
+
+
+def hdr_light(name):
+    """(kind, row) of an HDR light: the kind ssm_frames_accumulate_hdr_fwd takes and its HDR_ROW float32 constants, every one evaluated in
+    float64 and rounded once (layout: include/ssm_hip.h).  pq: 1/m2, c1, c2, c3, 1/m1, m1, m2, 0.  hlg: 1/3, log2(e)/a, cc, b, 1/12,
+    a ln 2, 0, 0."""
+    if name not in HDR_KINDS:
+        raise ValueError("unknown HDR light %r: the HDR lights are %s" % (name, ", ".join(HDR_LIGHTS)))
+    if name == "pq":
+        row = [1.0 / PQ_M2, PQ_C1, PQ_C2, PQ_C3, 1.0 / PQ_M1, PQ_M1, PQ_M2, 0.0]
+    else:
+        row = [1.0 / 3.0, float(np.log2(np.e)) / HLG_A, HLG_CC, HLG_B, 1.0 / 12.0, HLG_A * float(np.log(2.0)), 0.0, 0.0]
+    return HDR_KINDS[name], np.array(row, dtype=np.float64).astype(np.float32)
+
+
 def parse_shutter_light(name):
-    """"coded" or the name of a light curve, as given; anything else is refused by name."""
-    if name not in SHUTTER_LIGHTS:
-        raise ValueError("unknown shutter_light %r: it is one of %s" % (name, ", ".join(SHUTTER_LIGHTS)))
+    """"coded", the name of a light curve or of an HDR light, as given; anything else is refused by name."""
+    if name not in SHUTTER_LIGHTS + HDR_LIGHTS:
+        raise ValueError("unknown shutter_light %r: it is one of %s" % (name, ", ".join(SHUTTER_LIGHTS + HDR_LIGHTS)))
     return name
 
 
-def yuv_table(bits=8):
+def table_index(matrix):
+    """The index at which a matrix's rows sit in its table: what the entry points take as `matrix` (they refuse anything but 0 and 1).
+    BT601 and BT709 share yuv_table(bits) at their own numbers; BT2020 has yuv_table(bits, BT2020) to itself, at 0."""
+    if matrix in _KRKB:
+        return matrix
+    if matrix in _KRKB_OWN:
+        return 0
+    raise ValueError("unknown matrix %r: the matrices are %s" % (matrix, ", ".join(MATRICES)))
+
+
+def yuv_table(bits=8, matrix=None):
     """[2 matrices][2 ranges][YUV_ROW] float32 for samples of `bits` significant bits: every constant evaluated in float64 and rounded
     once (layout: include/ssm_hip.h).  With s = 2^(bits-8) and peak = 2^bits - 1 the codes map to the 0 .. 255 units the kernels work in:
-    limited 16 s .. 235 s (240 s), full 0 .. peak.  bits = 8 gives s = 1 and peak = 255: the 8-bit table, bit for bit."""
+    limited 16 s .. 235 s (240 s), full 0 .. peak.  bits = 8 gives s = 1 and peak = 255: the 8-bit table, bit for bit.
+    matrix = None, BT601 or BT709: that table, the one of BT.601 and BT.709.  matrix = BT2020: [1][2 ranges][YUV_ROW], the table of
+    BT.2020 alone, the same expressions on its Kr and Kb; table_index says where a matrix's rows sit."""
     sample_bytes(bits)
     s, peak = float(1 << (bits - 8)), float((1 << bits) - 1)
-    t = np.zeros((2, 2, YUV_ROW), dtype=np.float64)
-    for m, (kr, kb) in _KRKB.items():
+    own = matrix is not None and matrix not in _KRKB
+    table_index(BT601 if matrix is None else matrix)
+    t = np.zeros((1 if own else 2, 2, YUV_ROW), dtype=np.float64)
+    for m, (kr, kb) in ({0: _KRKB_OWN[matrix]} if own else _KRKB).items():
         kg = 1.0 - kr - kb
         for r in (LIMITED, FULL):
             lim = r == LIMITED
@@ -146,12 +192,13 @@ def yuv_table(bits=8):
 _table_c = {}
 
 
-def _table_ptr(bits=8):
-    """The table of a bit depth as the C array the entry points take; one per depth, kept."""
-    if bits not in _table_c:
-        flat = yuv_table(bits).reshape(-1)
-        _table_c[bits] = (ctypes.c_float * flat.size)(*[float(v) for v in flat])
-    return _table_c[bits]
+def _table_ptr(bits=8, matrix=None):
+    """The table of a bit depth (and of the matrix, where it has one of its own) as the C array the entry points take; one each, kept."""
+    key = bits if matrix is None or matrix in _KRKB else (bits, matrix)
+    if key not in _table_c:
+        flat = yuv_table(bits, matrix).reshape(-1)
+        _table_c[key] = (ctypes.c_float * flat.size)(*[float(v) for v in flat])
+    return _table_c[key]
 
 
 def chroma_dims(h, w, siting, bits=8):
@@ -214,7 +261,7 @@ def yuv_to_frames_host(payload, h, w, siting=CENTRED, matrix=BT709, color_range=
     """Yardstick of ssm_frames_from_yuv_fwd / ssm_frames_from_yuvx_fwd: [N, frame_bytes] uint8 (numpy) -> [N,3,Hp,Wp] float32."""
     if mean is None:
         mean, std = cfg_mean_std(None)
-    k = yuv_table(bits)[matrix, color_range]
+    k = yuv_table(bits, matrix)[table_index(matrix), color_range]
     kr, kg, kb, rv, gu, gv, bu, cbs, crs, ys, cs, iys, ics, yoff, coff = k[:15]
     payload = np.ascontiguousarray(payload).reshape(-1, frame_bytes(h, w, siting, bits))
     yq, uq, vq = split_planes(payload, h, w, siting, bits)
@@ -239,7 +286,7 @@ def frames_to_yuv_host(x, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITE
     """Yardstick of ssm_frames_to_yuv_fwd / ssm_frames_to_yuvx_fwd: [N,3,Hp,Wp] float32 (numpy, finite) -> [N, frame_bytes] uint8."""
     if mean is None:
         mean, std = cfg_mean_std(None)
-    k = yuv_table(bits)[matrix, color_range]
+    k = yuv_table(bits, matrix)[table_index(matrix), color_range]
     kr, kg, kb, rv, gu, gv, bu, cbs, crs, ys, cs, iys, ics, yoff, coff, ylo, yhi, clo, chi = k[:19]
     x = np.asarray(x, dtype=_F)
     n, _, hp, wp = x.shape
@@ -351,6 +398,78 @@ def accumulate_light_host(frames, acc, init, scale, mean, std, curve, encode, dt
     return acc
 
 
+def _pow_host(x, e, dt):
+    """x ^ e for x >= 0 in `dt`.  float64: numpy's power.  float32: 2 ^ (e log2 x) in three rounded steps, as the kernel's pow_fast
+    (numpy's log2 and exp2 in place of the hardware's instructions); x = 0 gives 2 ^ -inf = 0."""
+    if dt is np.float64:
+        return np.power(x, e)
+    with np.errstate(divide="ignore"):
+        return np.exp2(dt(e) * np.log2(x))
+
+
+def hdr_decode_host(c, name, dtype=np.float64):
+    """decode(c) of an HDR light (include/ssm_hip.h), element-wise in `dtype`, c in [0, 1].  float64: the defining formulas on the float64
+    constants.  float32: the kernel's steps on hdr_light(name)'s row, one rounded operation each."""
+    dt = np.dtype(dtype).type
+    c = np.asarray(c, dtype=dt)
+    if dt is np.float64:
+        if name == "pq":
+            p = np.power(c, 1.0 / PQ_M2)
+            return np.power(np.maximum(p - PQ_C1, 0.0) / (PQ_C2 - PQ_C3 * p), 1.0 / PQ_M1)
+        return np.where(c <= 0.5, c * c / 3.0, (np.exp((c - HLG_CC) / HLG_A) + HLG_B) / 12.0)
+    k = hdr_light(name)[1]
+    if name == "pq":
+        p = _pow_host(c, k[0], dt)
+        return _pow_host(np.maximum(p - k[1], dt(0.0)) * (dt(1.0) / (k[2] - k[3] * p)), k[4], dt)
+    return np.where(c <= dt(0.5), (c * c) * k[0], (np.exp2((c - k[2]) * k[1]) + k[3]) * k[4])
+
+
+def hdr_encode_host(lum, name, dtype=np.float64):
+    """encode(L) of an HDR light, element-wise in `dtype`; as hdr_decode_host.  pq takes L <= 0 to c = 0 (include/ssm_hip.h says why)."""
+    dt = np.dtype(dtype).type
+    lum = np.asarray(lum, dtype=dt)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        if dt is np.float64:
+            if name == "pq":
+                y = np.power(np.maximum(lum, 0.0), PQ_M1)
+                return np.where(lum <= 0.0, 0.0, np.power((PQ_C1 + PQ_C2 * y) / (1.0 + PQ_C3 * y), PQ_M2))
+            return np.where(lum <= 1.0 / 12.0, np.sqrt(3.0 * np.maximum(lum, 0.0)), HLG_A * np.log(12.0 * lum - HLG_B) + HLG_CC)
+        k = hdr_light(name)[1]
+        if name == "pq":
+            y = _pow_host(np.maximum(lum, dt(0.0)), k[5], dt)
+            return np.where(lum <= dt(0.0), dt(0.0), _pow_host((k[1] + k[2] * y) * (dt(1.0) / (dt(1.0) + k[3] * y)), k[6], dt))
+        return np.where(lum <= k[4], np.sqrt(dt(3.0) * np.maximum(lum, dt(0.0))), k[5] * np.log2(dt(12.0) * lum - k[3]) + k[2])
+
+
+def accumulate_hdr_host(frames, acc, init, scale, mean, std, name, encode, dtype=np.float64):
+    """Yardstick of ssm_frames_accumulate_hdr_fwd: accumulate_light_host with hdr_decode_host / hdr_encode_host of `name` ("pq", "hlg") in
+    place of a curve's row - the same black comparison, clamp, order of the sum, scale and closing normalisation, in `dtype`.
+    dtype = float64: the fixed point the kernel is held to within the bound of tests/test_video_hdr_cpu.py.  dtype = float32: plain fp32
+    arithmetic in the kernel's steps; not the kernel bit for bit, whose log2, exp2, reciprocal and square root are the hardware's."""
+    dt = np.dtype(dtype).type
+    assert dt in (np.float32, np.float64), "dtype is numpy's float32 or float64"
+    assert name in HDR_KINDS, "an HDR light is one of %s" % ", ".join(HDR_LIGHTS)
+    frames = np.asarray(frames, dtype=_F)
+    assert acc.dtype == dt and frames.ndim == 4 and frames.shape[0] >= 1 and frames.shape[1] == 3 and init in (0, 1, False, True) and \
+        encode in (0, 1, False, True)
+    dst = acc[0] if acc.ndim == 4 else acc
+    assert dst.shape == frames.shape[1:] and (acc.ndim == 3 or acc.shape[0] == 1)
+    m32, s32 = np.asarray(mean, dtype=_F).reshape(3, 1, 1), np.asarray(std, dtype=_F).reshape(3, 1, 1)
+    black = (_F(0.0) / _F(255.0) - m32) / s32
+    m, sd = m32.astype(dt), s32.astype(dt)
+
+    def dec(v):
+        c = np.where(v <= black, dt(0.0), np.clip(v.astype(dt) * sd + m, dt(0.0), dt(1.0)))
+        return hdr_decode_host(c, name, dt)
+
+    s = dec(frames[0]) if init else dst + dec(frames[0])
+    for n in range(1, frames.shape[0]):
+        s = s + dec(frames[n])
+    r = s * dt(scale)
+    dst[...] = (hdr_encode_host(r, name, dt) - m) / sd if encode else r
+    return acc
+
+
 def luma_sad_host(ya, yb):
     """Yardstick of ssm_luma_sad_fwd: uint8 Y planes [N,h,w] (numpy) -> uint64 [N], sums[n] = sum of |ya[n] - yb[n]| over the plane, exact."""
     ya, yb = np.asarray(ya), np.asarray(yb)
@@ -369,7 +488,7 @@ class Clip:
         self.hp, self.wp = padded_dims(h, w, mult)[0] if canvas is None else canvas
         self.at = ((self.hp - h) // 2, (self.wp - w) // 2)          # top, left
         self.norm = tuple(_f3(v) for v in cfg_mean_std(cfg))          # mean, std
-        self.coding = (_table_ptr(bits), matrix, crange, siting, sample_bytes(bits))          # the tail of both argument lists
+        self.coding = (_table_ptr(bits, matrix), table_index(matrix), crange, siting, sample_bytes(bits))          # the tail of both argument lists
 
     def ingest(self, payload, out, pad_before_norm=True):
         hb.check(hb.load().ssm_frames_from_yuvx_fwd(payload.data_ptr(), hb.view_of(out), payload.shape[0], self.h, self.w, self.hp, self.wp,
@@ -1160,7 +1279,11 @@ class VideoInterpolator:
         coded mean lets it cancel - and decoded before it is added, and the mean is encoded again (ssm_frames_accumulate_light_fwd).
         Which curve is right depends on how the clip was graded (bt709 for camera-referred material, srgb or bt1886 for material
         mastered on a display), which no Y4M header says: so the choice is the user's and the default stays "coded".  It acts on
-        R'G'B' after the matrix and is independent of matrix and color_range.
+        R'G'B' after the matrix and is independent of matrix and color_range.  "pq" and "hlg" (HDR_LIGHTS) are the BT.2100 transfer
+        functions of HDR clips, the same way through ssm_frames_accumulate_hdr_fwd: pq the PQ EOTF (display light as a fraction of
+        10000 cd/m2), hlg the inverse of the HLG OETF (scene light), neither with an OOTF.
+        matrix (None: default_matrix(h) per clip; BT601, BT709 or BT2020 = MATRICES' values): BT2020 is never a default, since no Y4M
+        header names the matrix.
         scene_cut (a Fraction in (0, 1], or what Fraction() takes; no default value): the threshold of SceneCuts.  Every pass then also
         sums the luma differences of its pairs on the GPU, and at a pair that SceneCuts calls a cut the writer puts out, instead of the
         synthesised frames, the left input frame's own bytes at t < 1/2 and the right one's from there on; `cuts` lists (i, score) of
@@ -1184,6 +1307,8 @@ class VideoInterpolator:
             raise ValueError("upsample_rate must be at least 2")
         self.model, self.cfg, self.rate = model, cfg, int(upsample_rate)
         self.n_streams, self.pb = max(1, int(n_streams)), max(1, int(pairs_per_batch))
+        if matrix is not None:
+            table_index(matrix)          # refuses an unknown matrix by name, here rather than at the first clip
         self.matrix, self.color_range = matrix, color_range
         self._pipe = None
         self.target_rate = None if target_rate is None else parse_rate("%s:%s" % tuple(target_rate))
@@ -1470,7 +1595,8 @@ class VideoInterpolator:
     def _run_shutter(self, clip, reader, writer):
         """run() with a shutter: output frame k is the mean of the S = shutter_samples sub-frames of Timeline(step, shutter=, samples=),
         summed in time order into an fp32 accumulator by ssm_frames_accumulate_fwd and egressed from it - every output, also one whose
-        samples are all input frames.  With shutter_light a curve every one of those calls is ssm_frames_accumulate_light_fwd instead,
+        samples are all input frames.  With shutter_light a curve every one of those calls is ssm_frames_accumulate_light_fwd instead
+        (ssm_frames_accumulate_hdr_fwd for "pq" and "hlg"),
         with encode = 1 on an output's last: the accumulator holds light in between and normalised coded planes for the egress.
 
         A pass (bookkeeping: ShutterPlanner) uploads and ingests, in one piece each, the frames it holds that a sample needs; copies the
@@ -1490,8 +1616,12 @@ class VideoInterpolator:
         depth, cap = n + 2, 2 * pb + 2
         plan = ShutterPlanner(tl, pb, cap)
         scale = np.float32(1.0 / tl.samples)
-        light = None if self.shutter_light == "coded" else \
-            (*clip.norm, (ctypes.c_float * LIGHT_ROW)(*[float(x) for x in light_curve(self.shutter_light)]))
+        light = hdr = None
+        if self.shutter_light in HDR_KINDS:
+            kind, row = hdr_light(self.shutter_light)
+            hdr = (*clip.norm, kind, (ctypes.c_float * HDR_ROW)(*[float(x) for x in row]))
+        elif self.shutter_light != "coded":
+            light = (*clip.norm, (ctypes.c_float * LIGHT_ROW)(*[float(x) for x in light_curve(self.shutter_light)]))
         host_in, host_out, host_t, np_in, np_out, np_t, done = ring_slots(depth, fb, cap, plan.max_done, pb * max(slots, 1))
         dev_in, dev_out, dev_t, ingested = stream_buffers(n, dev, fb, cap, plan.max_done, pb * max(slots, 1))
         planes = [torch.zeros(cap + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [carried frame | the pass's frames]
@@ -1524,7 +1654,9 @@ class VideoInterpolator:
                 for src, first, count, ko, init, last in calls:
                     a = acc[ko % OPEN_OUTPUTS:ko % OPEN_OUTPUTS + 1]
                     x = planes[k][first:first + 1] if src == "frame" else frames[first:first + count]
-                    if light is None:
+                    if hdr is not None:
+                        hb.frames_accumulate_hdr(x, a, 1 if init else 0, scale if last else 1.0, *hdr, 1 if last else 0)
+                    elif light is None:
                         hb.frames_accumulate(x, a, 1 if init else 0, scale if last else 1.0)
                     else:
                         hb.frames_accumulate_light(x, a, 1 if init else 0, scale if last else 1.0, *light, 1 if last else 0)
