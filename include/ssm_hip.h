@@ -877,6 +877,41 @@ int ssm_plane_ssim_fwd(const void *a, const void *b, long long stride_a, long lo
 int ssm_payload_mix_fwd(const void *a, const void *b, long long stride_a, long long stride_b, void *out, long long stride_out, int N,
                         long long samples, int sample_bytes, int num0, int num_step, int den, void *stream);
 
+/* ---- interlaced clips of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) -------------------------
+ * Definition (ssm_amd.video.VideoInterpolator(deinterlace=); split_fields_host and weave_fields_host are the two entry points in numpy).
+ * An interlaced frame of H x W weaves two FIELDS: in every plane the rows of parity 0 (0, 2, ...) are the TOP field's and the rows of parity 1
+ * the BOTTOM field's - for SSM_YUV_420_* that includes the H/2-row chroma planes, chroma row r belongs to field r mod 2.  A field is
+ * itself a payload of the frame's layout and sample size at H/2 x W, rows unpadded: its Y plane H/2 x W, then U, then V of the layout's
+ * chroma size for H/2 rows.  H is even, and a multiple of 4 for SSM_YUV_420_*, so that both chroma fields have H/4 rows.  Field order
+ * tff: frame m holds fields 2m (top, the earlier) and 2m + 1 (bottom) of the clip's 2n fields g_0 .. g_2n-1; bff: the bottom field is the
+ * earlier one.  The output is 2n progressive frames: frame f has, in every plane, field g_f's bytes on the rows of g_f's parity; the other
+ * rows are, for 0 < f < 2n - 1, those of the payload the fixed grid of upsample_rate = 2 writes at t = 1/2 between fields g_f-1 and
+ * g_f+1 (same parity and line positions as the missing rows), and for f = 0 and f = 2n - 1 LINE AVERAGES of g_f itself: per plane a
+ * missing row y is (a + b + 1) >> 1 per sample, in integers, a = kept row y - 1 and b = kept row y + 1 of the frame's plane; where one of
+ * the two lies outside the plane, both are the other one.
+ * ssm_fields_split_fwd: N contiguous frame payloads -> 2N contiguous field payloads, the top field of frame n at 2n and its bottom field
+ * at 2n + 1: storage order is by row parity, not by time (the host maps field order to time).  Bytes are moved as they stand; a 2-byte
+ * sample is moved whole, whatever its value.
+ * ssm_fields_weave_fwd: output frame n (at frames + n stride_frames) takes its rows of parity (parity0 + n) & 1 from the field payload at
+ * kept + n stride_kept; fill = 0: the other rows from the field payload at made + n stride_made; fill = 1: the other rows are the line
+ * averages above of the kept field (`made` is not read and may be null).  Strides in BYTES of either sign; with N = 1 they name nothing.
+ * kept and made are only read and may alias each other.
+ *   Both kernels are one launch for the three planes: the grid's x axis counts 16-byte pieces of the frame's rows, Y's, then U's, then
+ *   V's; a workgroup of 256 lanes takes 1024 of them, a lane 4, neighbouring lanes neighbouring pieces of a row; the grid's y axis is n.
+ *   A piece is one 16-byte load (two for a line average) and one 16-byte store where it is whole and source and destination sit on
+ *   16-byte boundaries, and moves sample by sample otherwise: a row's last piece when the row is no multiple of 16 bytes, rows that start
+ *   anywhere (odd widths, a payload at an odd offset) - decided per piece, in the same kernel.  The average of packed samples is
+ *   (a | b) - (((a ^ b) >> 1) & 0x7f7f7f7f) (0x7fff7fff for words).  No LDS, no scratch.  Each byte is read once (twice by a line average)
+ *   and written once; nothing outside the payloads' rows is read or written.
+ * SSM_E_ARG (nothing is queued), each with its own message and in this order: null pointers (made only with fill = 0); N outside
+ * 1..65535; H or W < 1; a layout outside SSM_YUV_*; sample_bytes outside {1, 2}; an odd H; for SSM_YUV_420_* an H that is no multiple of
+ * 4; a frame of more than 2^31 - 1 pieces; (weave) parity0 outside {0, 1}; fill outside {0, 1}; with sample_bytes = 2 an odd address,
+ * (weave, N > 1) an odd stride; (weave, N > 1) a |stride| of kept or made shorter than a field, of frames shorter than a frame; an
+ * output that overlaps an input. */
+int ssm_fields_split_fwd(const void *frames, void *fields, int N, int H, int W, int layout, int sample_bytes, void *stream);
+int ssm_fields_weave_fwd(const void *kept, long long stride_kept, const void *made, long long stride_made, void *frames, long long stride_frames,
+                         int N, int H, int W, int layout, int sample_bytes, int parity0, int fill, void *stream);
+
 /* ---- training ingest (csrc/ssm_data.hip; whole decoded uint8 HWC RGB frames on the device) --------------
  * The clip loader (ssm_amd/data.py) serves the reference's training transform, RandomCrop, then RandomMirrorRotate,
  * then Normalize and ToTensor (scripts/utils/dataloaders/default_reader.py:182-207,250-286, augmentations.py:

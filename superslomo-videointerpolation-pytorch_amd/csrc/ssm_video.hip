@@ -34,6 +34,9 @@
 //                            of one plane (PlaneOf) and ends in workgroup_add
 //   payload_mix_kernel       hold-out scoring: the cross-fade (a (den - k) + b k + den / 2) / den of two payloads, the frame-blend baseline;
 //                            exact division by multiply-shift, the span walk's pieces with a 16-byte store in place of the sum
+//   fields_split_kernel /    interlaced clips: N frames -> their 2N fields (even rows of every plane, odd rows), and N fields with
+//   fields_weave_kernel      N synthesised fields (or, fill = 1, with integer line averages of the kept field itself) -> N frames; bytes moved
+//                            as they stand, 16-byte pieces of a row where the addresses allow, one launch for the three planes
 // On the host the four pair entry points share pair_given and check_pair (operands, strides, alignment), grid_fits and clear_sums; yuv_planes is the one
 // place that knows the plane sizes of 4:2:0, 4:2:2 and 4:4:4, with_layout and with_sample pick a kernel's two template parameters.
 // Both conversions are HBM-bound (1.5 to 6 B in + 12 B out per pixel, and the reverse); so is the accumulation (4 (N + 1 + !init) B per
@@ -813,6 +816,117 @@ __global__ __launch_bounds__(LANES) void payload_mix_kernel(const unsigned char 
     }
 }
 
+// ---- interlaced clips: fields out of frames, frames out of fields ----------------------------------------------------------------------
+// A frame of H x W weaves two fields: per plane, rows of parity 0 are the top field's and rows of parity 1 the bottom field's; a field is a
+// payload of the frame's layout at H/2 x W.  Both kernels walk the FRAME's rows in pieces of 16 bytes: piece `id` of a frame counts the Y
+// plane's rows x pieces per row, then U's, then V's (FieldGeom::locate), so a wave's lanes take neighbouring pieces of a row and one launch
+// covers the three planes.  A lane takes CHUNKS pieces, LANES pieces apart.  A piece moves as one 16-byte load and store where it is whole and
+// every address involved sits on a 16-byte boundary, sample by sample otherwise (a row's ragged end; rows that start anywhere: odd widths, a
+// payload at an odd offset) - decided per piece in the same kernel.  Nothing outside a row's `cols` samples is read or written.
+struct FieldGeom {
+    unsigned rows[3], cols[3], pieces[3];          // of the frame's planes: rows, samples per row, 16-byte pieces per row
+    unsigned start[3], total;                      // first piece of a plane; pieces of a frame
+    long long off[3];                              // first sample of a plane in the frame's payload; in a field's it is off / 2
+};
+
+struct FieldPiece {
+    unsigned y, count;            // the frame row; samples of the piece, V or fewer at a row's end
+    long long frame, field;       // byte offsets of the piece in the frame's payload and in the payload of the field that holds row y
+    long long row;                // bytes of a row of the plane
+    unsigned rows;                // of the frame's plane
+};
+
+template <typename S>
+__device__ __forceinline__ FieldPiece field_piece(const FieldGeom &g, unsigned id) {
+    constexpr unsigned V = 16 / sizeof(S);
+    const int p = id >= g.start[2] ? 2 : id >= g.start[1] ? 1 : 0;
+    const unsigned local = id - g.start[p], y = local / g.pieces[p], k = local - y * g.pieces[p];
+    FieldPiece f;
+    f.y = y, f.rows = g.rows[p];
+    f.count = min(V, g.cols[p] - k * V);
+    f.row = (long long)g.cols[p] * (long long)sizeof(S);
+    f.frame = (g.off[p] + (long long)y * g.cols[p]) * (long long)sizeof(S) + 16ll * k;
+    f.field = ((g.off[p] >> 1) + (long long)(y >> 1) * g.cols[p]) * (long long)sizeof(S) + 16ll * k;
+    return f;
+}
+
+__device__ __forceinline__ bool on16(const void *a, const void *b, const void *c) {
+    return ((reinterpret_cast<size_t>(a) | reinterpret_cast<size_t>(b) | reinterpret_cast<size_t>(c)) & 15) == 0;
+}
+
+// (a + b + 1) >> 1 of four packed bytes or two packed words: (a | b) - ((a ^ b) >> 1), the shifted bits kept inside their sample
+template <typename S>
+__device__ __forceinline__ unsigned avg_up(unsigned a, unsigned b) {
+    constexpr unsigned M = sizeof(S) == 1 ? 0x7f7f7f7fu : 0x7fff7fffu;
+    return (a | b) - (((a ^ b) >> 1) & M);
+}
+
+// dst = the piece at a, or with b != a the line average of the pieces at a and b
+template <typename S>
+__device__ __forceinline__ void move_piece(unsigned char *dst, const unsigned char *a, const unsigned char *b, unsigned count) {
+    constexpr unsigned V = 16 / sizeof(S);
+    if (count == V && on16(dst, a, b)) {
+        i32x4 x = *reinterpret_cast<const i32x4 *>(a);
+        if (b != a) {
+            const i32x4 y = *reinterpret_cast<const i32x4 *>(b);
+            x.x = (int)avg_up<S>((unsigned)x.x, (unsigned)y.x), x.y = (int)avg_up<S>((unsigned)x.y, (unsigned)y.y);
+            x.z = (int)avg_up<S>((unsigned)x.z, (unsigned)y.z), x.w = (int)avg_up<S>((unsigned)x.w, (unsigned)y.w);
+        }
+        *reinterpret_cast<i32x4 *>(dst) = x;
+    } else {
+        const S *sa = reinterpret_cast<const S *>(a), *sb = reinterpret_cast<const S *>(b);
+        S *sd = reinterpret_cast<S *>(dst);
+        for (unsigned i = 0; i < count; ++i) sd[i] = (S)(((unsigned)sa[i] + (unsigned)sb[i] + 1u) >> 1);          // b == a: the sample itself
+    }
+}
+
+template <typename S>
+__global__ __launch_bounds__(LANES) void fields_split_kernel(const unsigned char *frames, unsigned char *fields, long long frame_bytes, FieldGeom g) {
+    const int n = blockIdx.y;
+    const unsigned base = blockIdx.x * (unsigned)(LANES * CHUNKS) + threadIdx.x;
+    const unsigned char *src = frames + n * frame_bytes;
+    unsigned char *dst = fields + n * frame_bytes;          // the frame's two fields: top at 2 n, bottom at 2 n + 1, half a frame each
+#pragma unroll
+    for (int c = 0; c < CHUNKS; ++c) {
+        const unsigned id = base + (unsigned)c * LANES;
+        if (id >= g.total) break;
+        const FieldPiece f = field_piece<S>(g, id);
+        const unsigned char *a = src + f.frame;
+        move_piece<S>(dst + (f.y & 1) * (frame_bytes >> 1) + f.field, a, a, f.count);
+    }
+}
+
+template <typename S>
+__global__ __launch_bounds__(LANES) void fields_weave_kernel(const unsigned char *kept, long long stride_kept, const unsigned char *made,
+                                                                 long long stride_made, unsigned char *frames, long long stride_frames, FieldGeom g,
+                                                                 int parity0, int fill) {
+    const int n = blockIdx.y;
+    const unsigned own = (unsigned)(parity0 + n) & 1u;
+    const unsigned base = blockIdx.x * (unsigned)(LANES * CHUNKS) + threadIdx.x;
+    const unsigned char *pk = kept + n * stride_kept, *pm = fill ? pk : made + n * stride_made;
+    unsigned char *dst = frames + n * stride_frames;
+#pragma unroll
+    for (int c = 0; c < CHUNKS; ++c) {
+        const unsigned id = base + (unsigned)c * LANES;
+        if (id >= g.total) break;
+        const FieldPiece f = field_piece<S>(g, id);
+        const unsigned char *a, *b;
+        if ((f.y & 1u) == own) {
+            a = b = pk + f.field;
+        } else if (!fill) {
+            a = b = pm + f.field;
+        } else {
+            // kept rows y - 1 and y + 1 of the frame are rows (y - 1) >> 1 and (y + 1) >> 1 of the field; f.field points at row y >> 1.
+            // own = 0: y odd, the rows are y >> 1 and (y >> 1) + 1;  own = 1: y even, the rows are (y >> 1) - 1 and y >> 1.
+            const long long up = own ? -f.row : 0, down = own ? 0 : f.row;
+            const bool has_up = f.y >= 1, has_down = f.y + 1 < f.rows;          // a plane has at least two rows: one of them holds
+            a = pk + f.field + (has_up ? up : down);
+            b = pk + f.field + (has_down ? down : up);
+        }
+        move_piece<S>(dst + f.frame, a, b, f.count);
+    }
+}
+
 // first and one-past-last address, in bytes, of the floats a view of [n,c,h,w] names (strides of either sign)
 inline void view_range(const ssm_view &v, int n, int c, int h, int w, long long *lo, long long *hi) {
     long long a = 0, b = 0;
@@ -1246,4 +1360,85 @@ extern "C" int ssm_payload_mix_fwd(const void *a, const void *b, long long strid
                    static_cast<unsigned char *>(out), stride_out, samples, num0, num_step, den, d);
     });
     return ssm::check_launch("ssm_payload_mix_fwd");
+}
+
+// ---- interlaced clips -------------------------------------------------------------------------------------------------------------------
+// ssm_fields_split_fwd and ssm_fields_weave_fwd refuse in one order: pointers, N, the frame (size, layout, sample width), the rows the
+// layout asks of an interlaced frame, the grid, parity0 and fill, 2-byte alignment, strides, overlap - and only then queue the one launch.
+static int fields_frame(const char *name, int N, int H, int W, int layout, int sample_bytes, FieldGeom *g) {
+    SSM_REQUIRE(N > 0 && N <= 65535, "%s: N=%d outside 1..65535", name, N);
+    if (const int e = check_frame(name, H, W, layout, sample_bytes)) return e;
+    const bool c420 = layout == SSM_YUV_420_CENTRED || layout == SSM_YUV_420_COSITED;
+    SSM_REQUIRE(H % 2 == 0, "%s: an interlaced frame has an even number of rows (H=%d)", name, H);
+    SSM_REQUIRE(!c420 || H % 4 == 0, "%s: an interlaced 4:2:0 frame has a multiple of 4 rows, two chroma fields of H/4 (H=%d)", name, H);
+    const YuvPlanes pl = yuv_planes(H, W, layout);
+    const long long per = 16 / sample_bytes;
+    long long at = 0, pieces = 0;
+    for (int p = 0; p < 3; ++p) {
+        const long long rows = p ? pl.ch : pl.h, cols = p ? pl.cw : pl.w, pp = (cols + per - 1) / per;
+        g->rows[p] = (unsigned)rows, g->cols[p] = (unsigned)cols, g->pieces[p] = (unsigned)pp;
+        g->off[p] = at;
+        at += rows * cols;
+        SSM_REQUIRE(pieces + rows * pp <= 2147483647ll, "%s: a frame of %lld bytes is more than the grid takes", name, pl.frame() * sample_bytes);
+        g->start[p] = (unsigned)pieces;
+        pieces += rows * pp;
+    }
+    g->total = (unsigned)pieces;
+    return SSM_OK;
+}
+
+static bool apart(long long a0, long long a1, long long b0, long long b1) { return a1 <= b0 || b1 <= a0; }
+
+extern "C" int ssm_fields_split_fwd(const void *frames, void *fields, int N, int H, int W, int layout, int sample_bytes, void *stream) {
+    const char *name = "fields_split";
+    SSM_REQUIRE(frames && fields, "%s: null pointer", name);
+    FieldGeom g;
+    if (const int e = fields_frame(name, N, H, W, layout, sample_bytes, &g)) return e;
+    const auto odd = [](const void *p) { return reinterpret_cast<size_t>(p) % 2 != 0; };
+    SSM_REQUIRE(sample_bytes == 1 || (!odd(frames) && !odd(fields)), "%s: a payload of 2-byte samples (frames or fields) is not 2-byte aligned", name);
+    const long long fb = yuv_planes(H, W, layout).frame() * sample_bytes;
+    long long i0, i1, o0, o1;
+    rows_range(frames, fb, N, fb, &i0, &i1);
+    rows_range(fields, fb, N, fb, &o0, &o1);
+    SSM_REQUIRE(apart(i0, i1, o0, o1), "%s: fields overlaps frames", name);
+    const unsigned groups = (g.total + LANES * CHUNKS - 1) / (LANES * CHUNKS);
+    with_sample(sample_bytes, [&](auto s) {
+        SSM_LAUNCH(fields_split_kernel<decltype(s)>, dim3(groups, N), dim3(LANES), 0, (hipStream_t)stream, static_cast<const unsigned char *>(frames),
+                   static_cast<unsigned char *>(fields), fb, g);
+    });
+    return ssm::check_launch("ssm_fields_split_fwd");
+}
+
+extern "C" int ssm_fields_weave_fwd(const void *kept, long long stride_kept, const void *made, long long stride_made, void *frames,
+                                    long long stride_frames, int N, int H, int W, int layout, int sample_bytes, int parity0, int fill, void *stream) {
+    const char *name = "fields_weave";
+    SSM_REQUIRE(kept && frames && (made || fill == 1), "%s: null pointer", name);
+    FieldGeom g;
+    if (const int e = fields_frame(name, N, H, W, layout, sample_bytes, &g)) return e;
+    SSM_REQUIRE(parity0 == 0 || parity0 == 1, "%s: parity0 %d not in {0, 1}", name, parity0);
+    SSM_REQUIRE(fill == 0 || fill == 1, "%s: fill %d not in {0, 1}", name, fill);
+    if (fill) made = nullptr, stride_made = 0;          // not read: what it points at, and how, is not looked at
+    const long long fb = yuv_planes(H, W, layout).frame() * sample_bytes, hb = fb / 2;
+    if (sample_bytes == 2) {
+        const auto odd = [](const void *p) { return reinterpret_cast<size_t>(p) % 2 != 0; };
+        SSM_REQUIRE(!odd(kept) && !odd(made) && !odd(frames), "%s: a payload of 2-byte samples (kept, made or frames) is not 2-byte aligned", name);
+        SSM_REQUIRE(N == 1 || (stride_kept % 2 == 0 && stride_made % 2 == 0 && stride_frames % 2 == 0),
+                    "%s: strides %lld (kept), %lld (made), %lld (frames) of 2-byte samples must be even", name, stride_kept, stride_made, stride_frames);
+    }
+    if (N == 1) stride_kept = stride_made = stride_frames = 0;          // the stride of a single payload names nothing
+    SSM_REQUIRE(N == 1 || (std::llabs(stride_kept) >= hb && (fill || std::llabs(stride_made) >= hb)),
+                "%s: strides %lld (kept), %lld (made) shorter than the field's %lld bytes", name, stride_kept, stride_made, hb);
+    SSM_REQUIRE(N == 1 || std::llabs(stride_frames) >= fb, "%s: stride %lld (frames) shorter than the frame's %lld bytes", name, stride_frames, fb);
+    long long k0, k1, m0 = 0, m1 = 0, o0, o1;
+    rows_range(kept, stride_kept, N, hb, &k0, &k1);
+    if (made) rows_range(made, stride_made, N, hb, &m0, &m1);
+    rows_range(frames, stride_frames, N, fb, &o0, &o1);
+    SSM_REQUIRE(apart(k0, k1, o0, o1) && (!made || apart(m0, m1, o0, o1)), "%s: frames overlaps kept or made", name);
+    const unsigned groups = (g.total + LANES * CHUNKS - 1) / (LANES * CHUNKS);
+    with_sample(sample_bytes, [&](auto s) {
+        SSM_LAUNCH(fields_weave_kernel<decltype(s)>, dim3(groups, N), dim3(LANES), 0, (hipStream_t)stream, static_cast<const unsigned char *>(kept),
+                   stride_kept, static_cast<const unsigned char *>(made), stride_made, static_cast<unsigned char *>(frames), stride_frames, g,
+                   parity0, fill);
+    });
+    return ssm::check_launch("ssm_fields_weave_fwd");
 }

@@ -43,6 +43,14 @@ that scores T or more is a scene cut: instead of frames that morph one scene int
 to the middle of the interval and the right one from there on.  The score - the mean absolute luma difference, damped by its own change
 from the pair before, over 255 - is a convention, not backed by a measurement here; every cut is written to --log with its score, which
 is what to choose T from.  Fades and dissolves are not looked for.  Not together with --shutter, and for 8-bit input only.
+
+--deinterlace auto|tff|bff: the input is interlaced (1080i50, 576i50, ...; `It` / `Ib` in the header), and its n frames come out as 2n
+progressive frames at twice the rate.  Every output frame has one field's lines as their own bytes; the lines between them are the field
+the network synthesises at t = 1/2 between the field before and the field after, which were sampled at those very line positions (the
+clip's first and last output have no such neighbour and get line averages).  auto takes the field order from the header and refuses a
+header that does not name one; tff / bff say it (ffmpeg writes `Ip` for interlaced material whose order it does not know).  It goes with
+--matrix, --range, --flow_scale and --tile, not with --upsample_rate, --slowmo, --fps, --speed, --shutter or --scene_cut: to retime as
+well, chain two runs,  ... --deinterlace auto --output - | interpolate_video.py ... --input - --fps 60 .
 """
 import argparse
 import configparser
@@ -110,7 +118,17 @@ def getargs(argv=None):
     parser.add_argument("--halo", type=int, default=T.DEFAULT_HALO, help="With --tile: pixels of context around a tile's core (multiple of 32).")
     parser.add_argument("--blend", type=int, default=T.DEFAULT_BLEND,
                         help="With --tile: half width of the cross-fade over a seam (0 or a power of two >= 4, at most the halo).")
+    parser.add_argument("--deinterlace", choices=V.DEINTERLACE, default=None,
+                        help="The input is interlaced: write its 2n fields as progressive frames at twice the rate, the missing lines "
+                             "synthesised from the neighbouring fields. auto: the field order of the header; tff, bff: as said. Default: off.")
     args = parser.parse_args(argv)
+    if args.deinterlace is not None:
+        for flag, given in (("--upsample_rate", args.upsample_rate is not None), ("--slowmo", args.slowmo), ("--fps", args.fps is not None),
+                            ("--speed", args.speed is not None), ("--shutter", args.shutter is not None),
+                            ("--scene_cut", args.scene_cut is not None)):
+            if given:
+                parser.error("--deinterlace does not go together with %s: it writes the clip's fields as frames at twice its rate and nothing "
+                             "else; pipe its output into a second run to retime it" % flag)
     if args.fps is not None or args.speed is not None:
         if args.upsample_rate is not None or args.slowmo:
             parser.error("--fps / --speed%s set the output's timeline themselves: they do not go together with --upsample_rate or --slowmo"
@@ -119,7 +137,7 @@ def getargs(argv=None):
         if args.shutter is not None:
             parser.error("--shutter averages over the interval of an output frame of --fps / --speed: it needs one of them, and does not go "
                          "together with --upsample_rate or --slowmo")
-        if args.upsample_rate is None:
+        if args.upsample_rate is None and args.deinterlace is None:
             args.upsample_rate = 8
     if args.shutter_light != "coded" and args.shutter is None:
         parser.error("--shutter_light %s is the light in which --shutter averages: it needs --shutter" % args.shutter_light)
@@ -140,12 +158,15 @@ def main(argv=None, model=None):
     crange = None if args.color_range is None else V.RANGES[args.color_range]
     model = (model if model is not None else ssm.FullModel(config)).cuda().eval()
     timed = args.fps is not None or args.speed is not None
-    vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate or 8, matrix=matrix, color_range=crange,
+    vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate, matrix=matrix, color_range=crange,
                              flow_scale=args.flow_scale, tile=args.tile, halo=args.halo, blend=args.blend, target_rate=args.fps, speed=args.speed,
                              shutter=args.shutter, shutter_samples=args.shutter_samples, scene_cut=args.scene_cut,
-                             shutter_light=args.shutter_light)
-    with V.Y4MReader(args.input, extended=True) as reader:
-        if timed:
+                             shutter_light=args.shutter_light, deinterlace=args.deinterlace)
+    with V.Y4MReader(args.input, extended=True, interlaced=args.deinterlace is not None) as reader:
+        if args.deinterlace is not None:
+            rate = V.output_rate(reader.rate, 2)
+            log.info("[%s] deinterlace: %s, fields as frames", args.expt, V.field_order(args.deinterlace, reader.interlace))
+        elif timed:
             rate = args.fps or reader.rate
             tl = vi.timeline(reader.rate)
             log.info("[%s] timeline: step = %s input frames per output frame, slots = %d times per pair", args.expt, tl.step, tl.slots)

@@ -229,6 +229,9 @@ SIGNATURES = {
                                     ctypes.c_longlong, _vp, _vp]),
     "ssm_payload_mix_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, ctypes.c_longlong, _c_int, ctypes.c_longlong, _c_int,
                                      _c_int, _c_int, _c_int, _vp]),
+    "ssm_fields_split_fwd": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp]),
+    "ssm_fields_weave_fwd": (_c_int, [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int,
+                                      _c_int, _c_int, _c_int, _vp]),
 }
 
 _lib = None

@@ -12,7 +12,7 @@
   frames_to_yuv           convention (scripts/visualize_interpolation.py:61-88,223-268)
   VideoInterpolator       the streamed loop: every leg of a pass (H2D, ingest, the pair pipeline, egress, D2H) is queued on the pass's HIP
                           stream, a writer thread drains a ring of pinned buffers in order; memory does not depend on the clip's length
-  PassRing / read_passes  what its three modes (fixed grid, timeline, shutter) share beside the prologue, the Clip with its two conversions and
+  PassRing / read_passes  what its four modes (fixed grid, timeline, shutter, fields) share beside the prologue, the Clip with its two conversions and
   / upload_times          their buffers: the ring with its writer thread and failure protocol (no GPU in it), the planners' read loop, a pass's times
 
   Timeline / PassPlanner  any output rate and speed: where each output frame sits on the input's clock, exactly (Fractions, closed form),
@@ -29,6 +29,10 @@
   luma_sad_host / luma_sad   scene cuts: per frame pair the exact sum of |difference| of the 8-bit Y planes, by numpy (the yardstick) and by
   / SceneCuts             ssm_luma_sad_fwd on the payloads as they stand on the device; the decision from those sums in Fractions, with no
                           GPU in it - VideoInterpolator(scene_cut=): at a cut the output repeats the nearer input frame instead of a morph
+  split_fields_host /     interlaced clips: a frame's two fields (the even and the odd rows of every plane) as payloads of their own, and frames
+  weave_fields_host       woven from kept fields and synthesised ones or integer line averages - the numpy definitions ssm_fields_split_fwd
+  / field_outputs         and ssm_fields_weave_fwd (fields_split, fields_weave) are held to bit for bit; which field is which time under
+                          tff / bff and which pairs run - VideoInterpolator(deinterlace=): 2n progressive frames of an n-frame clip (_run_fields)
   (ssm_amd/video_score.py) hold-out scoring: the clip against its own held-out frames, plane_sse / HoldOutScorer on this loop's ring, Clip and
                           buffers; the PSNR of what VideoInterpolator(upsample_rate=hold) would write - this module is unchanged by it
 
@@ -43,7 +47,9 @@ configuration (N_FRAMES > 2); shutter weights other than
 the box, a light curve chosen from the clip's tags, an OOTF for the HDR lights (PQ display light and HLG scene light are taken as they are), BT.2020 constant luminance, a shutter centred on the frame's instant or open for longer than the frame interval,
 variable-rate input, speeds that change within a clip; a default scene-cut threshold, fades and dissolves, cuts judged on chroma,
 skipping the GPU work of a cut pair, scene cuts together with a shutter; a measure of quality other than video_score's PSNR against
-held-out frames (SSIM, VMAF), and that score for the timeline, shutter and scene-cut outputs.
+held-out frames (SSIM, VMAF), and that score for the timeline, shutter and scene-cut outputs; of interlaced clips: mixed field order (Im),
+telecine and pulldown removal, scene cuts between fields, deinterlacing and retiming in one pass (chain two runs), the true vertical
+chroma siting of a 4:2:0 field (a quarter line off the layout's rule, which is what the fields are converted with).
 """
 import ctypes
 import functools
@@ -552,6 +558,127 @@ def luma_sad(payload_a, payload_b, h, w, out=None):
     return out
 
 
+# ---- interlaced clips: fields ----------------------------------------------------------------------------------------------------------
+TOP, BOTTOM = 0, 1                              # a field's parity: the rows of every plane of the frame it holds
+FIELD_ORDERS = {"t": "tff", "b": "bff"}         # the Y4M header's I tag -> field order; tff: a frame's top field is the earlier one
+DEINTERLACE = ("auto", "tff", "bff")
+
+
+def field_dims(h, w, siting, what="an interlaced frame"):
+    """(h / 2, w) of the fields of an h x w frame: h is even, and for the two 4:2:0 layouts a multiple of 4, so that both chroma fields
+    have h / 4 rows; anything else is refused by name."""
+    if h % 2:
+        raise Y4MError("%s has an even number of rows: H=%d is odd" % (what, h))
+    if siting in (CENTRED, COSITED) and h % 4:
+        raise Y4MError("%s in 4:2:0 has a multiple of 4 rows, two chroma fields of H/4: H=%d is not" % (what, h))
+    return h // 2, w
+
+
+def split_fields_host(frames, h, w, siting=CENTRED, bits=8):
+    """Yardstick of ssm_fields_split_fwd: [N, frame_bytes(h, w)] uint8 (numpy) -> [2N, frame_bytes(h / 2, w)] uint8, the top field of frame
+    n (the even rows of every plane) at 2n and its bottom field (the odd rows) at 2n + 1.  Storage order is by parity, not by time."""
+    fh, _ = field_dims(h, w, siting)
+    frames = np.ascontiguousarray(frames).reshape(-1, frame_bytes(h, w, siting, bits))
+    out = np.empty((2 * frames.shape[0], frame_bytes(fh, w, siting, bits)), np.uint8)
+    for src, dst in zip(split_planes(frames, h, w, siting, bits), split_planes(out, fh, w, siting, bits)):
+        dst[0::2], dst[1::2] = src[:, 0::2], src[:, 1::2]
+    return out
+
+
+def weave_fields_host(kept, made, h, w, siting=CENTRED, bits=8, parity0=TOP, fill=0):
+    """Yardstick of ssm_fields_weave_fwd: kept, made [N, frame_bytes(h / 2, w)] uint8 (numpy) -> [N, frame_bytes(h, w)] uint8.  Frame n has
+    kept[n] on its rows of parity (parity0 + n) & 1 of every plane.  fill = 0: made[n] on the other rows.  fill = 1 (made is not looked
+    at): a missing row y of a plane is (a + b + 1) >> 1 per sample, in integers, a = kept row y - 1 and b = kept row y + 1 of the frame's
+    plane; where one of them lies outside the plane, both are the other one."""
+    assert parity0 in (0, 1) and fill in (0, 1)
+    fh, _ = field_dims(h, w, siting)
+    kept = np.ascontiguousarray(kept).reshape(-1, frame_bytes(fh, w, siting, bits))
+    out = np.empty((kept.shape[0], frame_bytes(h, w, siting, bits)), np.uint8)
+    made = [None] * 3 if fill else split_planes(np.ascontiguousarray(made).reshape(kept.shape), fh, w, siting, bits)
+    for k, m, dst in zip(split_planes(kept, fh, w, siting, bits), made, split_planes(out, h, w, siting, bits)):
+        for n in range(kept.shape[0]):
+            own = (parity0 + n) & 1
+            dst[n, own::2] = k[n]
+            if not fill:
+                dst[n, 1 - own::2] = m[n]
+                continue
+            wide = k[n].astype(np.uint32)
+            up, down = (wide, np.concatenate([wide[1:], wide[-1:]])) if own == TOP else (np.concatenate([wide[:1], wide[:-1]]), wide)
+            dst[n, 1 - own::2] = ((up + down + 1) >> 1).astype(dst.dtype)
+    return out
+
+
+def _field_operand(t, n, row, name):
+    assert t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and t.shape[0] == n and t.shape[1] >= row and (t.shape[1] == 1 or t.stride(1) == 1), \
+        "%s must be a [%d, at least %d] uint8 tensor on the GPU with unit stride within a payload" % (name, n, row)
+    return t.stride(0) if n > 1 else 0
+
+
+def fields_split(frames, h, w, siting=CENTRED, bits=8, out=None):
+    """ssm_fields_split_fwd: a contiguous [N, frame_bytes(h, w)] uint8 device tensor -> [2N, frame_bytes(h / 2, w)] (into `out`, contiguous,
+    if given): frame n's top field at 2n, its bottom field at 2n + 1."""
+    fb = frame_bytes(h, w, siting, bits)
+    assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 2 and frames.shape[1] == fb and frames.is_contiguous(), \
+        "frames must be a contiguous [N, frame_bytes] uint8 tensor on the GPU"
+    n = frames.shape[0]
+    if out is None:
+        out = torch.empty(2 * n, fb // 2, dtype=torch.uint8, device=frames.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (2 * n, fb // 2) and out.is_contiguous()
+    hb.check(hb.load().ssm_fields_split_fwd(frames.data_ptr(), out.data_ptr(), n, h, w, siting, sample_bytes(bits), hb.stream_ptr()))
+    return out
+
+
+def fields_weave(kept, made, h, w, siting=CENTRED, bits=8, parity0=TOP, fill=0, out=None):
+    """ssm_fields_weave_fwd: kept, made [N, at least frame_bytes(h / 2, w)] uint8 device tensors (unit stride within a payload, any row
+    stride; made None with fill = 1) -> [N, at least frame_bytes(h, w)] (into `out` if given), as weave_fields_host."""
+    fb = frame_bytes(h, w, siting, bits)
+    n = kept.shape[0]
+    sk = _field_operand(kept, n, fb // 2, "kept")
+    sm = 0 if made is None else _field_operand(made, n, fb // 2, "made")
+    if out is None:
+        out = torch.empty(n, fb, dtype=torch.uint8, device=kept.device)
+    so = _field_operand(out, n, fb, "out")
+    hb.check(hb.load().ssm_fields_weave_fwd(kept.data_ptr(), sk, None if made is None else made.data_ptr(), sm, out.data_ptr(), so, n, h, w, siting,
+                                            sample_bytes(bits), parity0, fill, hb.stream_ptr()))
+    return out
+
+
+def parse_deinterlace(value):
+    """None, "auto", "tff" or "bff", as given; anything else is refused by name."""
+    if value is not None and value not in DEINTERLACE:
+        raise ValueError("unknown deinterlace %r: it is one of %s" % (value, ", ".join(DEINTERLACE)))
+    return value
+
+
+def field_order(deinterlace, interlace):
+    """The field order of a run, "tff" or "bff": what deinterlace says, or with "auto" what the header's I tag says - Ip and I? are then
+    refused (ffmpeg writes Ip for interlaced material whose order it does not know: say tff or bff)."""
+    if deinterlace != "auto":
+        return deinterlace
+    if interlace not in FIELD_ORDERS:
+        raise ValueError("deinterlace=\"auto\" takes the field order from the Y4M header, and this one says I%s: give deinterlace=\"tff\" or "
+                         "\"bff\" for interlaced material whose header does not say" % interlace)
+    return FIELD_ORDERS[interlace]
+
+
+def field_of(f, order):
+    """(frame, parity) of field g_f, the field at time f: frame f // 2 holds fields 2m and 2m + 1, under tff the top one first."""
+    assert order in ("tff", "bff")
+    return f // 2, (f & 1) ^ (1 if order == "bff" else 0)
+
+
+def field_outputs(n, order):
+    """The 2n output frames of an n-frame interlaced clip: per output f, (kept, left, right) as (frame, parity) each.  kept = g_f, whose
+    bytes are the rows of its parity; the other rows come from the field synthesised at t = 1/2 between left = g_f-1 and right = g_f+1,
+    which have the other parity - the missing rows' own; left = right = None for f = 0 and f = 2n - 1, whose missing rows are line
+    averages of the kept field (fill = 1)."""
+    out = []
+    for f in range(2 * n):
+        inner = 0 < f < 2 * n - 1
+        out.append((field_of(f, order), field_of(f - 1, order) if inner else None, field_of(f + 1, order) if inner else None))
+    return out
+
+
 # ---- YUV4MPEG2 ---------------------------------------------------------------------------------------------------------------------
 class Y4MError(ValueError):
     pass
@@ -569,10 +696,12 @@ class Y4MReader:
     """A YUV4MPEG2 stream from a path, `-` (stdin) or a binary file object.  Attributes: width, height, rate (num, den), interlace,
     aspect (num, den), chroma (the C tag's text, `420jpeg` when absent), siting, bits, sample_bytes, color_range (LIMITED / FULL from
     ffmpeg's XCOLORRANGE tag, None when absent), xtags (every X tag as read), frame_bytes.  extended=True: EXTENDED_TAGS (4:2:2 and 9 to
-    16 bits per sample) beside the 8-bit 4:2:0 and 4:4:4 tags that are taken without it."""
+    16 bits per sample) beside the 8-bit 4:2:0 and 4:4:4 tags that are taken without it.  interlaced=True: It and Ib are taken (Im and
+    anything else unknown stay refused); field_order is then "tff" / "bff" (None for Ip and I?) and field_bytes the payload of one field,
+    frame_bytes at H/2; a frame is still read whole.  Without it an interlaced header is refused, as ever."""
 
-    def __init__(self, src, extended=False):
-        self.extended = bool(extended)
+    def __init__(self, src, extended=False, interlaced=False):
+        self.extended, self.interlaced = bool(extended), bool(interlaced)
         self._own = isinstance(src, str) and src != "-"
         self.f = open(src, "rb") if self._own else (sys.stdin.buffer if src == "-" else src)
         line = self.f.readline(4096)
@@ -605,8 +734,9 @@ class Y4MReader:
                 raise Y4MError("unknown Y4M header field %r" % t)
         if not self.width or not self.height or self.width < 1 or self.height < 1:
             raise Y4MError("the Y4M header has no frame size (W, H)")
-        if self.interlace not in ("p", "?"):
+        if self.interlace not in ("p", "?") and not (self.interlaced and self.interlace in FIELD_ORDERS):
             raise Y4MError("interlaced Y4M input (I%s) is not supported: deinterlace first" % self.interlace)
+        self.field_order = FIELD_ORDERS.get(self.interlace)
         self.siting, self.bits = chroma_format(self.chroma, self.extended)
         self.sample_bytes = sample_bytes(self.bits)
         self.color_range = None
@@ -617,6 +747,10 @@ class Y4MReader:
                     raise Y4MError("unknown XCOLORRANGE=%s in the Y4M header" % x.split("=", 1)[1])
                 self.color_range = RANGES[v]
         self.frame_bytes = frame_bytes(self.height, self.width, self.siting, self.bits)
+        self.field_bytes = None
+        if self.field_order is not None:
+            self.field_bytes = frame_bytes(*field_dims(self.height, self.width, self.siting, "interlaced Y4M input (I%s)" % self.interlace),
+                                           self.siting, self.bits)
         self.frames_read = 0
 
     def read_frame_into(self, buf):
@@ -1254,14 +1388,14 @@ class VideoInterpolator:
     writer thread waits for a slot's event and writes, per pair, the interpolated frames and then the right frame's own input bytes.
     Host and device memory are fixed by the frame size, n_streams and pairs_per_batch.
 
-    The three modes (_run_fixed, _run_timeline, _run_shutter) share what is not on a stream: the prologue (_clip) and the Clip's two
+    The four modes (_run_fixed, _run_timeline, _run_shutter, _run_fields) share what is not on a stream: the prologue (_clip) and the Clip's two
     conversions, the allocation of what a ring slot and a stream hold (ring_slots, stream_buffers), the ring with its writer thread and
     failure protocol (PassRing), the planners' read loop and issue of passes (read_passes, _run_passes), the fill of a pass's times
     (upload_times).  Each keeps its own submit: what is queued on a pass's stream, call for call, is what its bytes and its rate rest on."""
 
-    def __init__(self, model, cfg, upsample_rate=8, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
+    def __init__(self, model, cfg, upsample_rate=None, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
                  tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8, scene_cut=None,
-                 shutter_light="coded"):
+                 shutter_light="coded", deinterlace=None):
         """target_rate = (num, den) and / or speed (a Fraction, or what Fraction() takes; 1/4 is four times slower): the output follows
         Timeline(speed * input rate / target_rate) instead of the fixed grid of upsample_rate, which is then not used (see
         _run_timeline); with both None nothing changes.  flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
@@ -1288,7 +1422,14 @@ class VideoInterpolator:
         sums the luma differences of its pairs on the GPU, and at a pair that SceneCuts calls a cut the writer puts out, instead of the
         synthesised frames, the left input frame's own bytes at t < 1/2 and the right one's from there on; `cuts` lists (i, score) of
         every cut pair (i, i + 1) after run().  The pair still runs on the GPU.  Not together with a shutter: an average across a cut
-        needs a definition of its own.  None: the loop as it is without the option, launch for launch."""
+        needs a definition of its own.  None: the loop as it is without the option, launch for launch.
+        upsample_rate None is 8.
+        deinterlace ("auto", "tff", "bff"; _run_fields): the clip is interlaced, and its n frames come out as 2n progressive frames at twice
+        the rate (field_outputs).  "auto" takes the field order from the reader's header (a Y4MReader(interlaced=True)) and refuses Ip and
+        I?; "tff" and "bff" override any header.  The fields run through the fixed grid of upsample_rate = 2 at t = 1/2, at half the
+        frame's height: matrix (None: default_matrix of the FRAME's height), color_range, flow_scale and tile / halo / blend act as
+        they do there.  It does not go together with an upsample_rate, target_rate, speed, shutter, scene_cut or a recurrent model
+        (chain a second run to retime the progressive output).  None: every other mode as it is."""
         from .coarse import check_scale
         from .tiles import check_args
         self.flow_scale = check_scale(flow_scale)
@@ -1303,6 +1444,15 @@ class VideoInterpolator:
         n_frames = cfg.getint("TRAIN", "N_FRAMES")
         if n_frames != 2:
             raise NotImplementedError("N_FRAMES=%d needs the recurrent bottleneck (unpinned upstream); use N_FRAMES=2" % n_frames)
+        self.deinterlace = parse_deinterlace(deinterlace)
+        if self.deinterlace is not None:
+            for name, given in (("upsample_rate", upsample_rate is not None), ("target_rate", target_rate is not None), ("speed", speed is not None),
+                                ("shutter", shutter is not None), ("scene_cut", scene_cut is not None),
+                                ("a recurrent model", getattr(model, "recurrent", False))):
+                if given:
+                    raise ValueError("deinterlace together with %s is not available: deinterlacing writes the clip's fields as frames at twice "
+                                     "its rate and nothing else; retime its progressive output in a second run" % name)
+        upsample_rate = 8 if upsample_rate is None else upsample_rate
         if int(upsample_rate) < 2:
             raise ValueError("upsample_rate must be at least 2")
         self.model, self.cfg, self.rate = model, cfg, int(upsample_rate)
@@ -1338,7 +1488,7 @@ class VideoInterpolator:
         return Timeline(timeline_step(in_rate, self.target_rate, self.speed), max_slots=MAX_STAGE2_BATCH // self.pb, shutter=self.shutter,
                         samples=self.samples)
 
-    def _pipeline(self, hp, wp, dev, n_t=None):
+    def _pipeline(self, hp, wp, dev, n_t=None):          # n_t None: the fixed grid's upsample_rate - 1
         import os
         from .engine import PairPipeline
         m = self.model
@@ -1402,9 +1552,11 @@ class VideoInterpolator:
     @torch.no_grad()
     def run(self, reader, writer):
         """Returns the number of frames written: (n - 1) * upsample_rate + 1 for n input frames (with target_rate / speed:
-        floor((n - 1) / step) + 1; with a shutter: Timeline.n_outputs(n))."""
+        floor((n - 1) / step) + 1; with a shutter: Timeline.n_outputs(n); with deinterlace: 2 n)."""
         clip = self._clip(reader, writer)
         self.cuts = []
+        if self.deinterlace is not None:
+            return self._run_fields(clip, reader, writer)
         if not self.timed:
             return self._run_fixed(clip, reader, writer)
         return self._run_shutter(clip, reader, writer) if self.samples > 1 else self._run_timeline(clip, reader, writer)
@@ -1507,6 +1659,121 @@ class VideoInterpolator:
                 ring.hand(r, done[r], rows)
                 written += valid * self.rate
                 j += 1
+        return written
+
+    def _run_fields(self, clip, reader, writer):
+        """run() with deinterlace: the n interlaced frames come out as the 2n progressive frames of field_outputs - the fixed grid of
+        upsample_rate = 2 run on the clip's two parity streams, between two byte-moving kernels.
+
+        A pass takes pairs_per_batch new frames and makes two outputs per frame.  On its stream: H2D of the frames (once); the field
+        payloads of the pass, rows [2 carried | top, bottom of every new frame], by one ssm_fields_split_fwd; every new field ingested
+        once at half the frame's height into fplanes[k][parity] = [carried left field | the new ones] - it is the right operand of one
+        pair now, the left one of the next pass's after the copy on the device, and its payload is the kept half of one output; per parity
+        one engine run at t = 1/2 over the pass's pairs of that parity, exactly the fixed grid's call, and the egress of its frames into
+        the rows of `made` of the outputs they belong to; then ssm_fields_weave_fwd from the field payloads (kept) and `made` into whole
+        frames, and D2H.  Output 2m - 1 keeps the later field of frame m - 1 and takes the other rows from the pair of the EARLIER
+        fields of frames m - 1 and m; output 2m keeps the earlier field of frame m and takes the pair of the later fields.  Under tff
+        the kept fields of a pass are consecutive rows and one weave call takes them; under bff they are, per frame, rows 3 apart: one
+        call of N = 2 per frame.  Output 0 (with frame 0, ahead of the passes) and output 2n - 1 (after the last) are woven with
+        fill = 1 from their own field alone.  Every output frame comes from the GPU; memory is fixed by the frame size, n_streams and
+        pairs_per_batch."""
+        from .evaluation import t_values
+        h, w, bits = clip.h, clip.w, getattr(reader, "bits", 8)
+        crange, siting = clip.coding[2:4]
+        order = field_order(self.deinterlace, reader.interlace)
+        fh, _ = field_dims(h, w, siting)
+        matrix = default_matrix(h) if self.matrix is None else self.matrix          # of the frame's height, not the field's
+        fclip = Clip(fh, w, siting, matrix, crange, self.cfg, bits, 32 * self.flow_scale, dev=clip.dev)
+        fb, hfb, dev, hp, wp = clip.fb, fclip.fb, clip.dev, fclip.hp, fclip.wp
+        pipe = self._pipeline(hp, wp, dev, 1)
+        n, pb = pipe.n, self.pb
+        depth = n + 2
+        early, late = field_of(0, order)[1], field_of(1, order)[1]          # the parities of a frame's earlier and later field
+        t_dev = torch.tensor(t_values(2), dtype=torch.float32, device=dev)
+        host_in, host_out, _, np_in, np_out, _, done = ring_slots(depth, fb, pb, 2 * pb)
+        dev_in, dev_out, _, ingested = stream_buffers(n, dev, fb, pb, 2 * pb)
+        fields = [torch.empty(2 + 2 * pb, hfb, dtype=torch.uint8, device=dev) for _ in range(n)]      # row 2 (1 + i) + parity: frame i of the pass; i = -1 carried
+        made = [torch.empty(2 * pb, hfb, dtype=torch.uint8, device=dev) for _ in range(n)]
+        fplanes = [torch.empty(2, pb + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [parity][carried left field | new ones]
+        # the kept fields of a pass's outputs as (first row of `fields`, rows between one and the next, count, first output): see above
+        runs = [(1, 1, 2 * pb, 0)] if order == "tff" else [(2 * i, 3, 2, 2 * i) for i in range(pb)]
+
+        def weave(kept, mk, out, parity0, fill):
+            fields_weave(kept, mk, h, w, siting, bits, parity0, fill, out=out)
+
+        def split_ingest(k, frames, i0):
+            """The frames' fields into rows 2 (1 + i0) .. of fields[k], and their planes behind the carried ones."""
+            rows = fields[k][2 * (1 + i0):2 * (1 + i0 + frames.shape[0])]
+            fields_split(frames, h, w, siting, bits, out=rows)
+            for i in range(frames.shape[0]):
+                for q in (TOP, BOTTOM):
+                    fclip.ingest(rows[2 * i + q:2 * i + q + 1], fplanes[k][q, 1 + i0 + i:2 + i0 + i])
+
+        first_in, first_out = (torch.empty(1, fb, dtype=torch.uint8).pin_memory() for _ in range(2))
+        if not reader.read_frame_into(first_in.numpy()[0]):
+            raise Y4MError("the Y4M stream holds no frame")
+        torch.cuda.synchronize(dev)
+        written = 0
+        with PassRing(depth, writer, lambda: torch.cuda.synchronize(dev)) as ring:
+            # frame 0: split and ingested where pass 0 looks for its carried fields; output 0 from its earlier field alone
+            last = (n - 1) % n
+            tail = (last, pb - 1)          # stream and place of the newest frame: its later field closes the clip
+            first_done = torch.cuda.Event()
+            with torch.cuda.stream(pipe.streams[last]):
+                dev_in[last][pb - 1:].copy_(first_in, non_blocking=True)
+                split_ingest(last, dev_in[last][pb - 1:], pb - 1)
+                weave(fields[last][2 * pb + early:2 * pb + early + 1], None, dev_out[last][:1], early, 1)
+                first_out.copy_(dev_out[last][:1], non_blocking=True)
+                ingested[last].record()
+                first_done.record()
+            ring.hand(None, first_done, [first_out.numpy()[0]])
+            written += 1
+            j, eof = 0, False
+            while not eof and not ring.failure:
+                r = ring.take()
+                valid = 0
+                while valid < pb and reader.read_frame_into(np_in[r][valid]):
+                    valid += 1
+                if valid < pb:
+                    eof = True
+                    if valid == 0:
+                        ring.hand(r, None, [])
+                        break
+                    np_in[r][valid:] = np_in[r][valid - 1]          # fill the pass; the extra outputs are not written
+                k, kprev = j % n, (j - 1) % n
+                st = pipe.streams[k]
+                with torch.cuda.stream(st):
+                    dev_in[k].copy_(host_in[r], non_blocking=True)
+                    st.wait_event(ingested[kprev])          # the carried fields; and pass j - n + 1 is done with fields[k] and fplanes[k]
+                    fields[k][late].copy_(fields[kprev][2 * pb + late])
+                    fplanes[k][:, 0].copy_(fplanes[kprev][:, pb])
+                    split_ingest(k, dev_in[k], 0)
+                    ingested[k].record()
+                    for s, q in enumerate((early, late)):          # the pairs of the earlier fields make outputs 0, 2, .. of the pass
+                        x = fplanes[k][q]
+                        img6 = x.view(1, 6, hp, wp) if pb == 1 else x.as_strided((pb, 6, hp, wp), (3 * hp * wp, hp * wp, wp, 1))
+                        frames = pipe.engines[k].run(img6, t_dev, False)
+                        for i in range(pb):
+                            fclip.egress(frames[i:i + 1], made[k][2 * i + s:2 * i + s + 1])
+                    for row, step, count, o in runs:
+                        weave(fields[k][row:row + (count - 1) * step + 1:step], made[k][o:o + count], dev_out[k][o:o + count],
+                              field_of(2 * j * pb + 1 + o, order)[1], 0)
+                    host_out[r].copy_(dev_out[k], non_blocking=True)
+                    done[r].record()
+                ring.hand(r, done[r], [np_out[r][o] for o in range(2 * valid)])
+                written += 2 * valid
+                tail = (k, valid - 1)
+                j += 1
+            if not ring.failure:
+                # output 2n - 1: the later field of the last frame, alone
+                r = ring.take()
+                k, i = tail
+                with torch.cuda.stream(pipe.streams[k]):
+                    weave(fields[k][2 * (1 + i) + late:2 * (1 + i) + late + 1], None, dev_out[k][:1], late, 1)
+                    host_out[r][:1].copy_(dev_out[k][:1], non_blocking=True)
+                    done[r].record()
+                ring.hand(r, done[r], [np_out[r][0]])
+                written += 1
         return written
 
     def _run_timeline(self, clip, reader, writer):
