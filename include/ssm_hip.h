@@ -912,6 +912,50 @@ int ssm_fields_split_fwd(const void *frames, void *fields, int N, int H, int W, 
 int ssm_fields_weave_fwd(const void *kept, long long stride_kept, const void *made, long long stride_made, void *frames, long long stride_frames,
                          int N, int H, int W, int layout, int sample_bytes, int parity0, int fill, void *stream);
 
+/* ---- 3:2 pulldown removal of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) ----------------------
+ * Definition (ssm_amd.video.detelecine_host is all of it in numpy, Cadence the decision, TelecineSource the streamed form).  Film at 24
+ * frames/s is carried in 30 frames/s video by 3:2 pulldown: four film frames A B C D become five video frames, fields as above (a frame's
+ * top field T_n is the rows of parity 0 of every plane, its bottom field B_n the rows of parity 1).
+ *   differences  per input frame n >= 1, over the LUMA plane only, two exact integers:
+ *                dT[n] = sum |T_n - T_(n-1)|,  dB[n] = sum |B_n - B_(n-1)|.
+ *   hypotheses   h = 5 pattern + phi, pattern in {0, 1}, phi in 0..4; frame n sits at cadence position q = (n - phi) mod 5, and the video
+ *                frames are, as (top, bottom):
+ *                    q            0       1       2       3       4
+ *                    pattern 0  (A, A)  (B, B)  (B, C)  (C, D)  (D, D)      top field first: T repeats at q = 2, B at q = 4
+ *                    pattern 1  (A, A)  (B, B)  (C, B)  (D, C)  (D, D)      bottom field first: B repeats at q = 2, T at q = 4
+ *                No pattern-1 hypothesis shares both repeat positions with a pattern-0 one: the field order falls out of the data and the
+ *                header's I tag is not looked at.
+ *   windows      window j is frames 5 j + 1 .. 5 j + 5.  The score of h on it is dT[n2] + dB[n4] (pattern 0) or dB[n2] + dT[n4] (pattern 1),
+ *                n2 and n4 the window's frames at q = 2 and q = 4.  The window takes the h of least score; on a tie at the minimum the
+ *                previous window's h if it is among the tied ones, else the lowest h.  Frame 0 takes window 0's h; the frames after the
+ *                last full window keep the last h.  A clip of fewer than 6 frames has no window and is refused.  There is no threshold: a
+ *                convention, not backed by a measurement on compressed material; each window's (first frame, h, best, second-best score)
+ *                is kept for the log.
+ *   output       per frame n under its window's h:  q = 0, 1, 4: the frame's own bytes;  q = 2: nothing, the frame is dropped;  q = 3: a
+ *                weave in EVERY plane, rows by parity - pattern 0: the top rows of frame n and the bottom rows of frame n - 1; pattern 1:
+ *                the top rows of frame n - 1 and the bottom rows of frame n.  q = 3 at n = 0 has no predecessor: written as it stands.
+ *                Every window holds exactly one q = 2 frame: four frames out per five in, rate (4 num, 5 den) reduced, 30000:1001 ->
+ *                24000:1001, progressive.  H is even, a multiple of 4 for SSM_YUV_420_* (as for the interlaced clips above).
+ * ssm_field_diff_fwd: a + n stride_a and b + n stride_b (strides in BYTES, of either sign, or 0: one plane against N) point at luma planes
+ * n = 0 .. N-1 of H x W samples, rows unpadded.  sample_bytes = 1: bytes.  sample_bytes = 2: 16-bit little-endian words, ALL 16 BITS COUNT.
+ *     sums[2 n + p] = sum over rows y = p (mod 2) of sum over x of |a_n[y][x] - b_n[y][x]|,   p = 0: the top fields, p = 1: the bottom fields
+ * exact, in a device array of 2 N 64-bit words.  The entry clears them on `stream` itself (a memset node ahead of the kernel).  Odd H is
+ * fine: parity 0 has one row more; with H = 1 the parity-1 word stays 0.  a and b are only read and may alias or overlap.  No byte outside
+ * the N planes of either operand is read.
+ *   The grid's x axis counts 16-byte pieces of the plane's rows, row by row (a row of W sample_bytes bytes has ceil of that / 16, the last
+ *   one ragged); a workgroup of 256 lanes takes 1024 of them, a lane 4, 256 apart, neighbouring lanes neighbouring pieces of a row; the y
+ *   axis is n.  Bytes go four per v_sad_u8, words two per v_sad_u16, into the 32-bit lane sum of the row's parity: a workgroup sees at
+ *   most 16 KiB per operand, so every sum up to the workgroup's two is at most 65535 * 8192 < 2^29.  One 16-byte load per operand and piece
+ *   where the piece is whole and both addresses sit on 16-byte boundaries, sample by sample otherwise and at a row's end, decided in the
+ *   same kernel (uniformly for a workgroup where both planes and the row pitch are multiples of 16 bytes).  Waves reduced by cross-lane
+ *   shuffles, 2 x 4 wave partials through LDS, then one 64-bit vector atomicAdd per parity and workgroup.  Integer adds commute: the sums
+ *   are the same in every run.  No scratch, no packed fp32.  Reads 2 sample_bytes per pixel.
+ * SSM_E_ARG (nothing is queued), each with its own message and in this order: null pointers; N outside 1..65535; H or W < 1; sample_bytes
+ * outside {1, 2}; a stride that is neither 0 nor at least the plane's bytes in magnitude; with sample_bytes = 2 an odd address, then an
+ * odd stride; `sums` not 8-byte aligned; a plane of more than 2^31 - 1 pieces. */
+int ssm_field_diff_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int sample_bytes,
+                       unsigned long long *sums, void *stream);
+
 /* ---- training ingest (csrc/ssm_data.hip; whole decoded uint8 HWC RGB frames on the device) --------------
  * The clip loader (ssm_amd/data.py) serves the reference's training transform, RandomCrop, then RandomMirrorRotate,
  * then Normalize and ToTensor (scripts/utils/dataloaders/default_reader.py:182-207,250-286, augmentations.py:

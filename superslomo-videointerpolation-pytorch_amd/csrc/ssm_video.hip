@@ -28,6 +28,9 @@
 //                                           bytes per v_sad_u8 into a 32-bit lane sum
 //                              SseLane<S>   hold-out scoring, ssm_plane_sse_fwd: (a - b)^2 over Y, U and V, 8-bit or 16-bit; bytes through
 //                                           v_dot4_u32_u8 into 32-bit lane sums, words into 64-bit ones
+//   field_diff_kernel        pulldown removal, ssm_field_diff_fwd: |a - b| over a luma plane summed per ROW PARITY, the differences of the top
+//                            and of the bottom fields of two frames; the same workgroup and lane work walked by rows (FieldWalk), bytes
+//                            through v_sad_u8 (SadLane), words through v_sad_u16 (SadWordLane), two 64-bit atomics per workgroup
 //   plane_ssim_kernel        hold-out scoring: per frame pair and plane the SSIM of x264 / ffmpeg's ssim filter in fixed point - 4 x 4 block
 //                            sums (bytes through v_dot4_u32_u8) to LDS, 8 x 8 windows at stride 4 from four blocks, integer factors, one
 //                            float64 quotient per window rounded to a multiple of 2^-32, signed 64-bit sums; a workgroup owns 31 x 15 windows
@@ -37,7 +40,7 @@
 //   fields_split_kernel /    interlaced clips: N frames -> their 2N fields (even rows of every plane, odd rows), and N fields with
 //   fields_weave_kernel      N synthesised fields (or, fill = 1, with integer line averages of the kept field itself) -> N frames; bytes moved
 //                            as they stand, 16-byte pieces of a row where the addresses allow, one launch for the three planes
-// On the host the four pair entry points share pair_given and check_pair (operands, strides, alignment), grid_fits and clear_sums; yuv_planes is the one
+// On the host the five pair entry points share pair_given and check_pair (operands, strides, alignment), grid_fits and clear_sums; yuv_planes is the one
 // place that knows the plane sizes of 4:2:0, 4:2:2 and 4:4:4, with_layout and with_sample pick a kernel's two template parameters.
 // Both conversions are HBM-bound (1.5 to 6 B in + 12 B out per pixel, and the reverse); so is the accumulation (4 (N + 1 + !init) B per
 // element), the luma difference (2 B per pixel) and the squared differences (2 B per pair of samples).  The chroma siting enters as four horizontal weights (ingest) or one switch (egress); matrix and range enter as one row of
@@ -626,6 +629,113 @@ __global__ __launch_bounds__(LANES) void span_sum_kernel(const unsigned char *a,
     workgroup_add(acc.sum(), &sums[planes * n + at.p]);
 }
 
+// ---- pulldown removal: absolute differences per field -----------------------------------------------------------------------------------
+// sums[2 n + p] += sum over this workgroup's pieces in rows y = p (mod 2) of |a_n[y][x] - b_n[y][x]|: the top fields' difference at 2 n, the
+// bottom fields' at 2 n + 1 (ssm_field_diff_fwd; the definition is in include/ssm_hip.h).  The rows of the two fields alternate, so the
+// walk is by ROWS: piece `id` of a plane is piece k = id mod pieces of row y = id / pieces, `pieces` 16-byte pieces to a row, the last one
+// ragged where the row is no multiple of 16 bytes.  The workgroup shape and the lane's work are span_sum_kernel's: LANES lanes, a lane
+// CHUNKS pieces, LANES pieces apart, so a wave's lanes read neighbouring pieces of a row.  One division per lane finds its first piece;
+// the next one is LANES further on, which is (y + LANES / pieces, k + LANES mod pieces) with one carry (FieldWalk, from the host).
+//   |a - b|   bytes: SadLane, four per v_sad_u8; words: SadWordLane, two per v_sad_u16.  A piece's sum (at most 16 * 255, or 8 * 65535
+//             < 2^19) goes to the lane's sum of the row's parity; a lane sees CHUNKS pieces and a workgroup LANES * CHUNKS, at most
+//             65535 * 8 * 1024 < 2^29: both lane sums, the wave sums and the workgroup's two sums fit 32 bits.
+//   loads     where both planes start on 16-byte boundaries, a row is a multiple of 16 bytes and all the workgroup's pieces exist (uniform),
+//             every piece is whole and aligned: all loads first, none guarded.  Otherwise per piece: one 16-byte load per operand where
+//             the piece is whole and both addresses sit on 16-byte boundaries, sample by sample where not (a row's ragged end, rows that
+//             start anywhere), samples past the row's end never loaded.
+//   sums      workgroup_add's steps for two sums at once: shuffles, wave partials through LDS, then lanes 0 and 1 issue ONE 64-bit vector
+//             atomic each, to neighbouring words.  Integer adds: the same result in every run.
+static_assert(65535ll * (16 / 2) * LANES * CHUNKS < (1ll << 32), "a workgroup's sum of absolute word differences fits 32 bits");
+
+struct SadWordLane {
+    typedef unsigned short Sample;
+    typedef unsigned Sum;
+    unsigned s = 0;
+    __device__ __forceinline__ void one(unsigned x, unsigned y) { s += x > y ? x - y : y - x; }
+    __device__ __forceinline__ void words(unsigned x, unsigned y) {
+#if __has_builtin(__builtin_amdgcn_sad_u16)
+        s = __builtin_amdgcn_sad_u16(x, y, s);
+#else
+        one(x & 0xffffu, y & 0xffffu);
+        one(x >> 16, y >> 16);
+#endif
+    }
+    __device__ __forceinline__ Sum sum() const { return s; }
+};
+
+struct FieldWalk {
+    unsigned rows, cols;          // of the plane, cols in samples
+    unsigned pieces, total;       // 16-byte pieces of a row (the last one may be ragged); of the plane
+    unsigned dy, dk;              // LANES / pieces, LANES % pieces: from a lane's piece to its next one
+};
+
+template <typename Lane>
+__global__ __launch_bounds__(LANES) void field_diff_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
+                                                           FieldWalk g, unsigned long long *sums) {          // a, b may alias
+    typedef typename Lane::Sample S;
+    constexpr unsigned V = 16 / sizeof(S);
+    const int n = blockIdx.y;
+    const unsigned char *pa = a + n * stride_a, *pb = b + n * stride_b;
+    const long long row = (long long)g.cols * (long long)sizeof(S);
+    const unsigned group = blockIdx.x * (unsigned)(LANES * CHUNKS), first = group + threadIdx.x;
+    unsigned y = first / g.pieces, k = first - y * g.pieces;
+    const auto next = [&]() {
+        y += g.dy, k += g.dk;
+        if (k >= g.pieces) k -= g.pieces, ++y;
+    };
+    unsigned s0 = 0, s1 = 0;          // the lane's sums over rows of parity 0 and 1
+    const auto add = [&](const Lane &t, unsigned parity) {
+        s0 += parity ? 0u : t.sum();
+        s1 += parity ? t.sum() : 0u;
+    };
+    const bool even = ((reinterpret_cast<size_t>(pa) | reinterpret_cast<size_t>(pb) | (size_t)row) & 15) == 0;
+    if (even && group + (unsigned)(LANES * CHUNKS) <= g.total) {
+        i32x4 va[CHUNKS], vb[CHUNKS];
+        unsigned parity[CHUNKS];
+#pragma unroll
+        for (int c = 0; c < CHUNKS; ++c) {
+            const long long o = (long long)y * row + 16ll * k;
+            va[c] = *reinterpret_cast<const i32x4 *>(pa + o);
+            vb[c] = *reinterpret_cast<const i32x4 *>(pb + o);
+            parity[c] = y & 1u;
+            next();
+        }
+#pragma unroll
+        for (int c = 0; c < CHUNKS; ++c) {
+            Lane t;
+            lane16(t, va[c], vb[c]);
+            add(t, parity[c]);
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < CHUNKS; ++c) {
+            if (y >= g.rows) break;          // pieces are counted in row order: every later one of this lane lies past the plane too
+            const long long o = (long long)y * row + 16ll * k;
+            const unsigned count = min(V, g.cols - k * V);
+            Lane t;
+            if (count == V && ((reinterpret_cast<size_t>(pa + o) | reinterpret_cast<size_t>(pb + o)) & 15) == 0) {
+                lane16(t, *reinterpret_cast<const i32x4 *>(pa + o), *reinterpret_cast<const i32x4 *>(pb + o));
+            } else {
+                const S *sa = reinterpret_cast<const S *>(pa + o), *sb = reinterpret_cast<const S *>(pb + o);
+                for (unsigned i = 0; i < count; ++i) t.one(sa[i], sb[i]);
+            }
+            add(t, y & 1u);
+            next();
+        }
+    }
+    __shared__ unsigned partial[2][LANES / 64];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) s0 += __shfl_xor(s0, d), s1 += __shfl_xor(s1, d);
+    if ((threadIdx.x & 63) == 0) partial[0][threadIdx.x >> 6] = s0, partial[1][threadIdx.x >> 6] = s1;
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        unsigned t = 0;
+#pragma unroll
+        for (int w = 0; w < LANES / 64; ++w) t += partial[threadIdx.x][w];
+        atomicAdd(&sums[2 * n + threadIdx.x], (unsigned long long)t);
+    }
+}
+
 // ---- hold-out scoring: SSIM in fixed point, summed per plane ---------------------------------------------------------------------------
 // The definition is in include/ssm_hip.h (x264's and ffmpeg's construction: 4 x 4 blocks, 8 x 8 windows at stride 4, integer factors, ONE
 // float64 quotient per window, rounded to a multiple of 2^-32).  sums[3 n + p] += sum over this workgroup's windows of fx.
@@ -1199,7 +1309,7 @@ extern "C" int ssm_frames_accumulate_hdr_fwd(ssm_view src, ssm_view acc, int N, 
 
 
 // ---- the pair entry points: two payloads in, sums or a third payload out -------------------------------------------------------------
-// ssm_luma_sad_fwd, ssm_plane_sse_fwd, ssm_plane_ssim_fwd and ssm_payload_mix_fwd refuse in one order: pair_given (pointers, N), the
+// ssm_luma_sad_fwd, ssm_field_diff_fwd, ssm_plane_sse_fwd, ssm_plane_ssim_fwd and ssm_payload_mix_fwd refuse in one order: pair_given (pointers, N), the
 // entry's own sizes, check_pair (strides, alignment), what only that entry asks, grid_fits - and only then queue anything: a refused call
 // queues nothing, not even the clear.
 struct PairEntry {
@@ -1277,6 +1387,26 @@ extern "C" int ssm_luma_sad_fwd(const unsigned char *a, const unsigned char *b, 
     SSM_LAUNCH(span_sum_kernel<SadLane>, dim3((unsigned)groups, N), dim3(LANES), 0, (hipStream_t)stream, a, b, stride_a, stride_b, plane, 0ll,
                (unsigned)groups, 0u, 1, sums);
     return ssm::check_launch("ssm_luma_sad_fwd");
+}
+
+extern "C" int ssm_field_diff_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int sample_bytes,
+                                  unsigned long long *sums, void *stream) {
+    if (const int e = pair_given("field_diff", a, b, sums, N)) return e;
+    SSM_REQUIRE(H > 0 && W > 0, "field_diff: bad plane size %dx%d", H, W);
+    SSM_REQUIRE(sample_bytes == 1 || sample_bytes == 2, "field_diff: sample_bytes %d not in {1, 2}", sample_bytes);
+    const long long row = (long long)W * sample_bytes, pieces = (row + 15) / 16, total = pieces * H;
+    const PairEntry k = {"field_diff", "plane", row * H};
+    if (const int e = check_pair(k, true, false, a, b, stride_a, stride_b, N, sample_bytes, sums)) return e;
+    if (const int e = grid_fits(k, total)) return e;          // a piece's index, and the last workgroup's past the plane, fit 32 bits
+    if (const int e = clear_sums(k.name, sums, 2 * (size_t)N, stream)) return e;
+    const FieldWalk g = {(unsigned)H, (unsigned)W, (unsigned)pieces, (unsigned)total, (unsigned)(LANES / pieces), (unsigned)(LANES % pieces)};
+    const long long groups = (total + LANES * CHUNKS - 1) / (LANES * CHUNKS);
+    const unsigned char *pa = static_cast<const unsigned char *>(a), *pb = static_cast<const unsigned char *>(b);
+    with_sample(sample_bytes, [&](auto s) {
+        typedef std::conditional_t<sizeof(s) == 1, SadLane, SadWordLane> Lane;
+        SSM_LAUNCH(field_diff_kernel<Lane>, dim3((unsigned)groups, N), dim3(LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b, g, sums);
+    });
+    return ssm::check_launch("ssm_field_diff_fwd");
 }
 
 extern "C" int ssm_plane_sse_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int layout,

@@ -51,6 +51,14 @@ clip's first and last output have no such neighbour and get line averages).  aut
 header that does not name one; tff / bff say it (ffmpeg writes `Ip` for interlaced material whose order it does not know).  It goes with
 --matrix, --range, --flow_scale and --tile, not with --upsample_rate, --slowmo, --fps, --speed, --shutter or --scene_cut: to retime as
 well, chain two runs,  ... --deinterlace auto --output - | interpolate_video.py ... --input - --fps 60 .
+
+--detelecine: the input is film carried in 29.97 frames/s video by 3:2 pulldown (DVDs, NTSC broadcast masters, archive transfers), and the
+pulldown is undone before anything else: the cadence is found from the differences of same-parity fields of neighbouring frames (summed on
+the GPU, ssm_field_diff_fwd), per window of five frames the frame that holds nothing new is dropped and the two split fields are paired
+again.  What follows sees the film's own frames, byte for byte, as a progressive clip at 4/5 of the rate (30000:1001 -> 24000:1001), so it
+goes with every option but --deinterlace: --detelecine --fps 60000:1001 is 24 -> 60 without the 2-3 judder.  The field order falls out of
+the data: It, Ib, Ip and I? headers are all taken.  There is no threshold; the windows whose cadence changed go to --log with their best
+and second-best score.  2:2 and mixed cadences, soft telecine and the orphan field at an edit inside a cycle are out of scope.
 """
 import argparse
 import configparser
@@ -121,7 +129,13 @@ def getargs(argv=None):
     parser.add_argument("--deinterlace", choices=V.DEINTERLACE, default=None,
                         help="The input is interlaced: write its 2n fields as progressive frames at twice the rate, the missing lines "
                              "synthesised from the neighbouring fields. auto: the field order of the header; tff, bff: as said. Default: off.")
+    parser.add_argument("--detelecine", action="store_true",
+                        help="The input is film in 3:2 pulldown: find the cadence, drop the repeated fields and pair the split ones again "
+                             "before anything else; the clip then runs as progressive at 4/5 of its rate. Not together with --deinterlace.")
     args = parser.parse_args(argv)
+    if args.detelecine and args.deinterlace is not None:
+        parser.error("--detelecine does not go together with --deinterlace: pulldown removal pairs the fields of a film frame again, "
+                     "deinterlacing writes every field as a frame of its own")
     if args.deinterlace is not None:
         for flag, given in (("--upsample_rate", args.upsample_rate is not None), ("--slowmo", args.slowmo), ("--fps", args.fps is not None),
                             ("--speed", args.speed is not None), ("--shutter", args.shutter is not None),
@@ -162,7 +176,10 @@ def main(argv=None, model=None):
                              flow_scale=args.flow_scale, tile=args.tile, halo=args.halo, blend=args.blend, target_rate=args.fps, speed=args.speed,
                              shutter=args.shutter, shutter_samples=args.shutter_samples, scene_cut=args.scene_cut,
                              shutter_light=args.shutter_light, deinterlace=args.deinterlace)
-    with V.Y4MReader(args.input, extended=True, interlaced=args.deinterlace is not None) as reader:
+    with V.Y4MReader(args.input, extended=True, interlaced=args.deinterlace is not None or args.detelecine) as reader:
+        if args.detelecine:
+            log.info("[%s] detelecine: %d:%d frames/s in, film at %d:%d", args.expt, *reader.rate, *V.detelecine_rate(reader.rate))
+            reader = V.TelecineSource(reader, next(model.parameters()).device)
         if args.deinterlace is not None:
             rate = V.output_rate(reader.rate, 2)
             log.info("[%s] deinterlace: %s, fields as frames", args.expt, V.field_order(args.deinterlace, reader.interlace))
@@ -180,6 +197,16 @@ def main(argv=None, model=None):
                  reader.rate[0], reader.rate[1], args.output, rate[0], rate[1])
         with V.Y4MWriter.like(args.output, reader, rate=rate, color_range=out_range) as writer:
             n = vi.run(reader, writer)
+    if args.detelecine:
+        if reader.combed_first:
+            log.info("[%s] detelecine: frame 0 sits at cadence position 3 and has no predecessor: written as it stands", args.expt)
+        last = None
+        for first, h, best, second in reader.cadence:
+            if h != last:
+                log.info("[%s] detelecine: from input frame %d cadence h = %d (%s field first, phase %d): score %d, second best %d", args.expt,
+                         0 if last is None else first, h, "bottom" if h >= 5 else "top", h % 5, best, second)
+            last = h
+        log.info("[%s] detelecine: %d windows, %d input frames dropped", args.expt, len(reader.cadence), reader.dropped)
     for i, score in vi.cuts:
         log.info("[%s] scene cut between input frames %d and %d: score %s = %.6f (threshold %s)", args.expt, i, i + 1, score, float(score),
                  vi.scene_cut)

@@ -224,6 +224,7 @@ SIGNATURES = {
     "ssm_frames_accumulate_light_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _vp, _vp, _c_int, _vp]),
     "ssm_frames_accumulate_hdr_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _vp, _c_int, _vp, _c_int, _vp]),
     "ssm_luma_sad_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_int, _vp, _vp]),
+    "ssm_field_diff_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "ssm_plane_sse_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "ssm_plane_ssim_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_longlong,
                                     ctypes.c_longlong, _vp, _vp]),

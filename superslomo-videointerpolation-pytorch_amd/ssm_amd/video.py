@@ -33,6 +33,10 @@
   weave_fields_host       woven from kept fields and synthesised ones or integer line averages - the numpy definitions ssm_fields_split_fwd
   / field_outputs         and ssm_fields_weave_fwd (fields_split, fields_weave) are held to bit for bit; which field is which time under
                           tff / bff and which pairs run - VideoInterpolator(deinterlace=): 2n progressive frames of an n-frame clip (_run_fields)
+  telecine_host /         film in 3:2 pulldown: the pulldown and its removal in numpy, the per-field luma differences by numpy and by
+  detelecine_host /       ssm_field_diff_fwd, the cadence decision from those sums in Python ints (Cadence), and the reader that undoes the
+  field_diff / Cadence    pulldown in front of the loop - TelecineSource(reader, dev): downstream sees the film's frames as a progressive clip at
+  / TelecineSource        detelecine_rate; every mode of VideoInterpolator is unchanged by it
   (ssm_amd/video_score.py) hold-out scoring: the clip against its own held-out frames, plane_sse / HoldOutScorer on this loop's ring, Clip and
                           buffers; the PSNR of what VideoInterpolator(upsample_rate=hold) would write - this module is unchanged by it
 
@@ -48,8 +52,9 @@ the box, a light curve chosen from the clip's tags, an OOTF for the HDR lights (
 variable-rate input, speeds that change within a clip; a default scene-cut threshold, fades and dissolves, cuts judged on chroma,
 skipping the GPU work of a cut pair, scene cuts together with a shutter; a measure of quality other than video_score's PSNR against
 held-out frames (SSIM, VMAF), and that score for the timeline, shutter and scene-cut outputs; of interlaced clips: mixed field order (Im),
-telecine and pulldown removal, scene cuts between fields, deinterlacing and retiming in one pass (chain two runs), the true vertical
-chroma siting of a 4:2:0 field (a quarter line off the layout's rule, which is what the fields are converted with).
+scene cuts between fields, deinterlacing and retiming in one pass (chain two runs), the true vertical
+chroma siting of a 4:2:0 field (a quarter line off the layout's rule, which is what the fields are converted with); of pulldown removal:
+2:2, 2:3:3:2 and mixed cadences, soft telecine, the orphan field at an edit inside a cycle, comb metrics, noisy or compressed sources.
 """
 import ctypes
 import functools
@@ -823,6 +828,234 @@ class Y4MWriter:
         self.f.flush()
         if self._own:
             self.f.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+# ---- 3:2 pulldown removal ----------------------------------------------------------------------------------------------------------------
+# The definition is in include/ssm_hip.h and DESIGN 3.12: film frames A B C D in five video frames, per pattern and cadence position q the
+# film frames (by their place in the cycle) on a video frame's top and bottom rows.
+PULLDOWN = (((0, 0), (1, 1), (1, 2), (2, 3), (3, 3)),          # pattern 0, top field first: the top field repeats at q = 2, the bottom at q = 4
+            ((0, 0), (1, 1), (2, 1), (3, 2), (3, 3)))          # pattern 1, bottom field first
+HYPOTHESES = 10                                                 # h = 5 * pattern + phi, frame n at q = (n - phi) % 5
+
+
+def _luma_of(payload, h, w, bits):
+    sb = sample_bytes(bits)
+    payload = np.asarray(payload)
+    assert payload.dtype == np.uint8 and payload.ndim == 2 and payload.shape[1] >= h * w * sb, "payloads are [N, at least the luma plane] uint8"
+    y = np.ascontiguousarray(payload[:, :h * w * sb])
+    return (y.view("<u2") if sb == 2 else y).reshape(-1, h, w).astype(np.int64)
+
+
+def field_diff_host(a, b, h, w, bits=8):
+    """Yardstick of ssm_field_diff_fwd: payloads a, b [N, at least h * w samples] uint8 (numpy; one of them may have a single row) ->
+    uint64 [N, 2], out[n, p] = the sum over the luma rows of parity p of |a_n - b_n|, exact; with bits > 8 over the 16-bit words."""
+    d = np.abs(_luma_of(a, h, w, bits) - _luma_of(b, h, w, bits))
+    return np.stack([d[:, 0::2].reshape(d.shape[0], -1).sum(axis=1), d[:, 1::2].reshape(d.shape[0], -1).sum(axis=1)], axis=1).astype(np.uint64)
+
+
+def field_diff(payload_a, payload_b, h, w, bits=8, out=None):
+    """ssm_field_diff_fwd on payloads: [N, at least h * w samples] uint8 device tensors (unit stride within a row, any row stride: frames
+    n + 1 and n of one buffer are fine) -> int64 [N, 2] on the device (into `out` if given): per pair the sums of |a_n - b_n| over the luma
+    rows of parity 0 (the top fields) and 1 (the bottom fields).  The words are unsigned and below 2^63."""
+    sb = sample_bytes(bits)
+    n, out, sa, sb_stride = _pair_operands(payload_a, payload_b, h * w * sb, "h * w samples", out, (2,))
+    hb.check(hb.load().ssm_field_diff_fwd(payload_a.data_ptr(), payload_b.data_ptr(), sa, sb_stride, n, h, w, sb, out.data_ptr(), hb.stream_ptr()))
+    return out
+
+
+def _weave_rows(dst, top, bottom, h, w, siting, bits):
+    """dst = the rows of parity 0 of every plane of `top` and the rows of parity 1 of `bottom`: payloads of one frame, as numpy rows."""
+    for d, t, b in zip(*(split_planes(p.reshape(1, -1), h, w, siting, bits) for p in (dst, top, bottom))):
+        d[0, 0::2], d[0, 1::2] = t[0, 0::2], b[0, 1::2]
+
+
+def telecine_host(film, h, w, siting=CENTRED, bits=8, pattern=0, phase=0):
+    """3:2 pulldown of progressive payloads film [F, frame_bytes] (numpy) -> the video clip [n, frame_bytes]: frame m sits at cadence
+    position q = (phase + m) % 5 of PULLDOWN[pattern] and weaves the rows of two film frames.  The clip is a cut out of the endless
+    pulldown: film[0] is the first film frame any of its fields shows (A at phase 0, B at 1 and 2, C at 3, D at 4), and it ends before
+    the first video frame that would need film[F].  The maker of test and benchmark clips."""
+    assert pattern in (0, 1) and 0 <= phase < 5
+    field_dims(h, w, siting, "a telecined frame")
+    film = np.ascontiguousarray(film).reshape(-1, frame_bytes(h, w, siting, bits))
+    first = min(PULLDOWN[pattern][phase])
+    out = []
+    for m in range(5 * len(film)):
+        c, q = divmod(phase + m, 5)
+        t, b = (4 * c + x - first for x in PULLDOWN[pattern][q])
+        if max(t, b) >= len(film):
+            break
+        frame = np.empty_like(film[0])
+        _weave_rows(frame, film[t], film[b], h, w, siting, bits)
+        out.append(frame)
+    return np.stack(out) if out else np.zeros((0, film.shape[1]), np.uint8)
+
+
+class Cadence:
+    """The cadence decision, in Python ints and free of the GPU.  feed(dT, dB) takes the field differences of the next frame n = 1, 2, ...
+    against frame n - 1 and returns the frames that this closes, [] until a window of five is full: [(n, action)] with action None (the
+    frame is dropped) or (t, b), the frames whose top rows and bottom rows make the output - (n, n) is the frame's own bytes, (n, n - 1)
+    and (n - 1, n) the weaves of patterns 0 and 1 at q = 3.  Window 0 closes frames 0 .. 5, window j > 0 frames 5 j + 1 .. 5 j + 5; end()
+    closes the frames after the last full window under the last hypothesis, and refuses a clip without a window.  `log`: per window (first
+    frame, h, best score, second-best score); `dropped`: the frames dropped so far; `combed_first`: frame 0 sat at q = 3 and went out as it
+    stands."""
+
+    def __init__(self):
+        self.h, self.log, self.dropped, self.combed_first = None, [], 0, False
+        self._fed, self._window = 0, []
+
+    @staticmethod
+    def position(n, h):
+        return (n - h % 5) % 5
+
+    def _action(self, n):
+        q, pattern = self.position(n, self.h), self.h // 5
+        if q == 2:
+            self.dropped += 1
+            return n, None
+        if q == 3 and n == 0:
+            self.combed_first = True
+        if q != 3 or n == 0:
+            return n, (n, n)
+        return n, ((n, n - 1) if pattern == 0 else (n - 1, n))
+
+    def feed(self, dt, db):
+        self._fed += 1
+        self._window.append((int(dt), int(db)))
+        if len(self._window) < 5:
+            return []
+        first = self._fed - 4
+        at = {n: d for n, d in zip(range(first, first + 5), self._window)}
+        scores = []
+        for h in range(HYPOTHESES):
+            n2, n4 = (next(n for n in at if self.position(n, h) == q) for q in (2, 4))
+            scores.append(at[n2][h // 5] + at[n4][1 - h // 5])          # pattern 0: dT[n2] + dB[n4]; pattern 1: dB[n2] + dT[n4]
+        best = min(scores)
+        self.h = self.h if self.h is not None and scores[self.h] == best else scores.index(best)
+        self.log.append((first, self.h, best, sorted(scores)[1]))
+        self._window = []
+        return [self._action(n) for n in range(0 if first == 1 else first, first + 5)]
+
+    def end(self):
+        if self.h is None:
+            raise Y4MError("pulldown removal needs one cadence window, frames 1 .. 5 after frame 0: the clip has %d frames, fewer than 6"
+                           % (self._fed + 1))
+        tail, self._window = len(self._window), []
+        return [self._action(n) for n in range(self._fed - tail + 1, self._fed + 1)]
+
+
+def detelecine_rate(rate):
+    """The output rate of pulldown removal, (num, den) reduced: four frames out per five in, 30000:1001 -> 24000:1001."""
+    r = Fraction(4 * rate[0], 5 * rate[1])
+    return r.numerator, r.denominator
+
+
+def detelecine_host(frames, h, w, siting=CENTRED, bits=8):
+    """The whole definition in numpy, the yardstick of TelecineSource: video payloads [n, frame_bytes] -> (the film payloads [m,
+    frame_bytes], the Cadence that decided, for its log)."""
+    field_dims(h, w, siting, "a telecined frame")
+    frames = np.ascontiguousarray(frames).reshape(-1, frame_bytes(h, w, siting, bits))
+    cadence, actions = Cadence(), []
+    if len(frames) > 1:
+        for dt, db in field_diff_host(frames[1:], frames[:-1], h, w, bits):
+            actions += cadence.feed(dt, db)
+    actions += cadence.end()
+    out = []
+    for n, act in actions:
+        if act is not None:
+            out.append(np.empty_like(frames[0]))
+            _weave_rows(out[-1], frames[act[0]], frames[act[1]], h, w, siting, bits)
+    return np.stack(out), cadence
+
+
+class TelecineSource:
+    """A reader that undoes 3:2 pulldown: wraps a Y4MReader (or anything with its attributes) of telecined video and hands out the film's
+    frames, so that everything downstream sees a progressive clip at detelecine_rate(reader.rate).  It has the reader's format attributes,
+    interlace "p", frames_read (film frames handed out), and of the decision so far `cadence` (Cadence.log: per window its first frame, h,
+    best and second-best score), `dropped` and `combed_first`.
+
+    A chunk is 5 * windows_per_chunk new frames behind the carried last frame of the chunk before, in one pinned buffer and one device
+    buffer that are made once.  Per chunk, on a stream of its own: one H2D, one ssm_field_diff_fwd (row n + 1 against row n, one stride
+    each), one D2H of the sums, one event wait; never a wait per frame.  Three film frames in four are straight copies out of the pinned
+    buffer, the fourth a row-strided numpy copy per plane.  The bytes handed out do not depend on windows_per_chunk."""
+
+    def __init__(self, reader, dev, windows_per_chunk=2):
+        assert windows_per_chunk >= 1
+        self.reader, self.dev = reader, torch.device(dev)
+        if self.dev.type != "cuda":
+            raise RuntimeError("pulldown removal takes its field differences on the GPU (the HIP path has no CPU fallback)")
+        for name in ("width", "height", "siting", "chroma", "color_range", "aspect", "xtags", "frame_bytes"):
+            setattr(self, name, getattr(reader, name))
+        self.bits, self.extended = getattr(reader, "bits", 8), getattr(reader, "extended", False)
+        self.sample_bytes = sample_bytes(self.bits)
+        field_dims(self.height, self.width, self.siting, "a telecined frame")
+        self.interlace, self.field_order, self.field_bytes, self.rate = "p", None, None, detelecine_rate(reader.rate)
+        self.frames_read, self._cadence = 0, Cadence()
+        rows = 5 * windows_per_chunk
+        self._host = torch.empty(rows + 1, self.frame_bytes, dtype=torch.uint8).pin_memory()
+        self._np = self._host.numpy()
+        self._dev = torch.empty(rows + 1, self.frame_bytes, dtype=torch.uint8, device=self.dev)
+        self._sums = torch.empty(rows, 2, dtype=torch.int64, device=self.dev)
+        self._host_sums = torch.empty(rows, 2, dtype=torch.int64).pin_memory()
+        self._np_sums = self._host_sums.numpy().view(np.uint64)
+        self._stream, self._event = torch.cuda.Stream(self.dev), torch.cuda.Event()
+        self._base = None          # the clip's frame in row 0 of the buffers; None before the first chunk
+        self._pending, self._eof = [], False
+
+    def _chunk(self):
+        """The next chunk: its frames into the buffer behind the carried one, their field differences, and what the cadence closes."""
+        if self._base is None:
+            if not self.reader.read_frame_into(self._np[0]):
+                raise Y4MError("the Y4M stream holds no frame")
+            self._base = 0
+        else:
+            self._base += self._np.shape[0] - 1          # a chunk that is not the last one is full: its last row is carried
+            self._np[0] = self._np[-1]
+        k = 0
+        while k < self._np.shape[0] - 1 and self.reader.read_frame_into(self._np[1 + k]):
+            k += 1
+        self._eof = k < self._np.shape[0] - 1
+        if k:
+            with torch.cuda.stream(self._stream):
+                self._dev[:k + 1].copy_(self._host[:k + 1], non_blocking=True)
+                field_diff(self._dev[1:k + 1], self._dev[:k], self.height, self.width, self.bits, out=self._sums[:k])
+                self._host_sums[:k].copy_(self._sums[:k], non_blocking=True)
+                self._event.record()
+            self._event.synchronize()
+            for dt, db in self._np_sums[:k]:
+                self._pending += self._cadence.feed(dt, db)
+        if self._eof:
+            self._pending += self._cadence.end()
+        self._pending = [act for _, act in self._pending if act is not None]
+
+    def read_frame_into(self, buf):
+        """The next film frame's payload into `buf`; False at the end of the clip."""
+        while not self._pending:
+            if self._eof:
+                return False
+            self._chunk()
+        t, b = self._pending.pop(0)
+        out = np.frombuffer(memoryview(buf).cast("B"), np.uint8)
+        if out.size != self.frame_bytes:
+            raise ValueError("buffer of %d bytes for frames of %d" % (out.size, self.frame_bytes))
+        if t == b:
+            out[:] = self._np[t - self._base]
+        else:
+            _weave_rows(out, self._np[t - self._base], self._np[b - self._base], self.height, self.width, self.siting, self.bits)
+        self.frames_read += 1
+        return True
+
+    cadence = property(lambda self: self._cadence.log)
+    dropped = property(lambda self: self._cadence.dropped)
+    combed_first = property(lambda self: self._cadence.combed_first)
+
+    def close(self):
+        self.reader.close()
 
     def __enter__(self):
         return self
