@@ -956,6 +956,50 @@ int ssm_fields_weave_fwd(const void *kept, long long stride_kept, const void *ma
 int ssm_field_diff_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int sample_bytes,
                        unsigned long long *sums, void *stream);
 
+/* ---- repeated frames of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) ---------------------------
+ * Definition (ssm_amd.video.dedup_host is all of it in numpy, Repeats the decision, RepeatSource and GapTimeline the streamed form).
+ * Animation on twos or threes, 24 or 25 frames/s brought to 50 or 60 by repetition, screen recordings and captures that filled a dropped
+ * frame hold frames that repeat the one before.  Everything below is in exact integers and fractions.
+ *   blocks    a plane of rows x cols samples as it stands in a payload, rows unpadded: block (bx, by) is the 8 x 8 samples at (8 bx, 8 by),
+ *             bx < cols >> 3, by < rows >> 3; the trailing cols & 7 columns and rows & 7 rows belong to no block (the rule of the SSIM
+ *             blocks above), and a plane with fewer than 8 rows or columns has no block.  For payloads (a, b):
+ *             d(block) = sum over the block of |a - b|; with 16-bit words all 16 bits count, d <= 64 * 65535 < 2^22.
+ *   measure   per pair n and plane p (Y, U, V) over the plane's blocks:  max[n][p] = the largest d (0 for a plane without blocks),
+ *             over[n][p] = the number of blocks with d > lo.  A small moving object cannot hide in it as it does in a whole-plane sum.
+ *   test      frame n >= 1 is a REPEAT of frame n - 1 iff for every plane p that has blocks  max[n][p] <= hi  and
+ *             over[n][p] <= floor(frac * blocks_p).  Frame 0 is never one.  The comparison is always with the frame directly before.
+ *             Defaults hi = 768 * 2^(bits - 8), lo = 320 * 2^(bits - 8), frac = 33/100: the numbers of ffmpeg's mpdecimate (64 * 12,
+ *             64 * 5, 0.33), NOT its construction - its blocks overlap at stride 4 and it counts against a quarter as many - so nothing
+ *             here claims its decisions frame for frame; ffmpeg is not compared.  A convention, not backed by a measurement on compressed
+ *             footage.  hi = lo = 0, frac = 0: exact repeats only.
+ *   runs      a run is a maximal sequence of consecutive repeats, frames r + 1 .. r + m.  It is REPAIRED iff m <= D (dedup_max, default
+ *             2: "on threes", 2:3 repetition) and frame r + m + 1 exists.  A longer run is a still, a run at the clip's end has no right
+ *             neighbour: both stay as they are, every frame an ordinary input frame.
+ *   output    the grid of upsample_rate N without the option: output k at input time k / N, k = 0 .. (n - 1) N.  For a repaired run
+ *             frames r and r + m + 1 form ONE pair with gap g = m + 1; every output strictly between them, at input time r + j / N,
+ *             j = 1 .. g N - 1, is the frame synthesised between r and r + m + 1 at t = j / (g N) (the engine's fp32 time: Timeline.t32).
+ *             The repeats' own bytes are never written; the pairs inside the run do not run.  Every other frame at an integer time is
+ *             its own bytes.  N = 1 is repair only.
+ * ssm_block_sad_fwd: a + n stride_a and b + n stride_b (strides in BYTES, of either sign, or 0: one payload against N; rows n + 1 and n of
+ * one buffer are fine) point at whole payloads n = 0 .. N-1 of H x W frames in `layout` (SSM_YUV_*), as for ssm_plane_sse_fwd.
+ * sample_bytes = 1: bytes.  sample_bytes = 2: 16-bit little-endian words, ALL 16 BITS COUNT.
+ *     out[6 n + 2 p] = max[n][p],   out[6 n + 2 p + 1] = over[n][p] with the given lo,   p = 0, 1, 2 for Y, U, V
+ * exact, in a device array of 6 N 64-bit words.  The entry clears them on `stream` itself (a memset node ahead of the kernel).  a and b are
+ * only read and may alias or overlap.  No byte outside the N payloads of either operand is read.
+ *   A workgroup of 256 lanes owns a tile of 32 x 8 blocks of ONE plane, a lane one block; the grid's x axis counts Y's tiles (row-major),
+ *   then U's, then V's, the y axis is n; a plane without a block has no tile, a frame without one no launch.  A lane loads the block's
+ *   eight rows of both operands - bytes: one 8-byte load per row and operand, two v_sad_u8; words: one 16-byte load, four v_sad_u16 -
+ *   into a 32-bit block sum; the 32 lanes of a tile row read neighbouring blocks.  The vector loads are used where the plane's start in
+ *   both operands and its row pitch are multiples of the load (cols a multiple of 8), decided per (n, plane); otherwise the same kernel
+ *   goes sample by sample (17 x 23 in 4:2:0 starts U at an odd byte).  Per-lane (d, d > lo) reduced by cross-lane shuffles, 2 x 4 wave
+ *   partials through LDS, then ONE 64-bit vector atomicMax and ONE 64-bit vector atomicAdd per workgroup.  Both commute: the words are the
+ *   same in every run.  No scratch, no packed fp32.  Reads 2 sample_bytes per sample of the blocks.
+ * SSM_E_ARG (nothing is queued), each with its own message and in this order: null pointers; N outside 1..65535; H or W < 1; a layout
+ * outside SSM_YUV_*; sample_bytes outside {1, 2}; a stride that is neither 0 nor at least the frame's bytes in magnitude; with
+ * sample_bytes = 2 an odd address, then an odd stride; lo outside 0..2^22; `out` not 8-byte aligned; a frame of more than 2^31 - 1 tiles. */
+int ssm_block_sad_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int layout, int sample_bytes,
+                      int lo, unsigned long long *out, void *stream);
+
 /* ---- training ingest (csrc/ssm_data.hip; whole decoded uint8 HWC RGB frames on the device) --------------
  * The clip loader (ssm_amd/data.py) serves the reference's training transform, RandomCrop, then RandomMirrorRotate,
  * then Normalize and ToTensor (scripts/utils/dataloaders/default_reader.py:182-207,250-286, augmentations.py:

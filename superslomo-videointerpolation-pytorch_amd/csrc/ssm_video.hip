@@ -35,12 +35,16 @@
 //                            sums (bytes through v_dot4_u32_u8) to LDS, 8 x 8 windows at stride 4 from four blocks, integer factors, one
 //                            float64 quotient per window rounded to a multiple of 2^-32, signed 64-bit sums; a workgroup owns 31 x 15 windows
 //                            of one plane (PlaneOf) and ends in workgroup_add
+//   block_sad_kernel         repeated frames, ssm_block_sad_fwd: |a - b| summed per 8 x 8 block of Y, U and V, per pair and plane the largest
+//                            block sum and the number of blocks above `lo`; a workgroup owns 32 x 8 blocks of one plane (PlaneOf), a lane
+//                            one block - eight 8- or 16-byte loads per operand, v_sad_u8 / v_sad_u16 - and ends in one 64-bit atomicMax and
+//                            one 64-bit atomicAdd
 //   payload_mix_kernel       hold-out scoring: the cross-fade (a (den - k) + b k + den / 2) / den of two payloads, the frame-blend baseline;
 //                            exact division by multiply-shift, the span walk's pieces with a 16-byte store in place of the sum
 //   fields_split_kernel /    interlaced clips: N frames -> their 2N fields (even rows of every plane, odd rows), and N fields with
 //   fields_weave_kernel      N synthesised fields (or, fill = 1, with integer line averages of the kept field itself) -> N frames; bytes moved
 //                            as they stand, 16-byte pieces of a row where the addresses allow, one launch for the three planes
-// On the host the five pair entry points share pair_given and check_pair (operands, strides, alignment), grid_fits and clear_sums; yuv_planes is the one
+// On the host the six pair entry points share pair_given and check_pair (operands, strides, alignment), grid_fits and clear_sums; yuv_planes is the one
 // place that knows the plane sizes of 4:2:0, 4:2:2 and 4:4:4, with_layout and with_sample pick a kernel's two template parameters.
 // Both conversions are HBM-bound (1.5 to 6 B in + 12 B out per pixel, and the reverse); so is the accumulation (4 (N + 1 + !init) B per
 // element), the luma difference (2 B per pixel) and the squared differences (2 B per pair of samples).  The chroma siting enters as four horizontal weights (ingest) or one switch (egress); matrix and range enter as one row of
@@ -864,6 +868,88 @@ __global__ __launch_bounds__(SSIM_LANES) void plane_ssim_kernel(const unsigned c
     workgroup_add(s, &sums[3 * n + p]);          // two's complement: the wrapped unsigned adds are the signed sum
 }
 
+// ---- repeated frames: absolute differences per 8 x 8 block, their maximum and a count per plane -----------------------------------------
+// The definition is in include/ssm_hip.h: block (bx, by) of a plane is its 8 x 8 samples at (8 bx, 8 by), d = the block's sum of |a - b|;
+// out[6 n + 2 p] = the largest d of plane p, out[6 n + 2 p + 1] = the number of its blocks with d > lo (ssm_block_sad_fwd).
+// A workgroup owns a tile of SAD_BW x SAD_BH blocks of ONE plane of one payload, a lane one block: lane (lx, ly) of 32 x 8 takes block
+// (lx, ly) of the tile, so the 32 lanes of a tile row read 32 neighbouring block rows - 256 or 512 contiguous bytes of a plane row per
+// operand.  The grid's x axis counts Y's tiles (row-major), then U's, then V's; a plane without a block has no tile.
+//   rows    a block row is 8 samples per operand.  Bytes: one 8-byte load, two v_sad_u8; words: one 16-byte load, four v_sad_u16 - where
+//           every row address of both operands is aligned to the load (plane start and cols multiples of 8 samples - per (n, plane),
+//           uniform); else sample by sample.  All eight rows of both operands are loaded before the first sum.  d <= 64 * 65535 < 2^22.
+//   result  the lane's (d, d > lo) - (0, 0) where the tile leaves the plane - reduced by shuffles (max and add), 2 x 4 wave partials through
+//           LDS, then lane 0 issues ONE 64-bit vector atomicMax and ONE 64-bit vector atomicAdd.  Both commute: the same words in every run.
+constexpr int SAD_LANES = LANES, SAD_BW = 32, SAD_BH = 8;
+static_assert(SAD_BW * SAD_BH == SAD_LANES, "a lane takes one block");
+static_assert(64ll * 65535 <= (1ll << 22), "a block's sum of absolute word differences is at most 2^22");
+
+template <typename S> struct SadRow;
+template <> struct SadRow<unsigned char> {
+    typedef i32x2 Vec;
+    typedef SadLane Lane;
+    static __device__ __forceinline__ void add(Lane &acc, Vec x, Vec y) {
+        acc.words((unsigned)x.x, (unsigned)y.x);
+        acc.words((unsigned)x.y, (unsigned)y.y);
+    }
+};
+template <> struct SadRow<unsigned short> {
+    typedef i32x4 Vec;
+    typedef SadWordLane Lane;
+    static __device__ __forceinline__ void add(Lane &acc, Vec x, Vec y) { lane16(acc, x, y); }
+};
+
+template <typename S>          // the sample: unsigned char, or unsigned short (all 16 bits count)
+__global__ __launch_bounds__(SAD_LANES) void block_sad_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
+                                                              int rows0, int cols0, int rows1, int cols1, unsigned tx0, unsigned tx1,
+                                                              unsigned g0, unsigned g1, unsigned lo,
+                                                              unsigned long long *out) {          // a, b may alias
+    typedef typename SadRow<S>::Vec Vec;
+    const int n = blockIdx.y;
+    const PlaneOf at(blockIdx.x, g0, g1, (long long)rows0 * cols0, (long long)rows1 * cols1);
+    const int p = at.p;
+    const int rows = p == 0 ? rows0 : rows1, cols = p == 0 ? cols0 : cols1;
+    const unsigned tx = p == 0 ? tx0 : tx1;
+    const S *pa = reinterpret_cast<const S *>(a + n * stride_a) + at.first, *pb = reinterpret_cast<const S *>(b + n * stride_b) + at.first;
+    const int bx = (int)(at.g % tx) * SAD_BW + (int)(threadIdx.x & (SAD_BW - 1)), by = (int)(at.g / tx) * SAD_BH + (int)(threadIdx.x / SAD_BW);
+    constexpr size_t ALIGN = 8 * sizeof(S);                                // a block row: 8 bytes, or 16
+    const bool vec = ((reinterpret_cast<size_t>(pa) | reinterpret_cast<size_t>(pb)) % ALIGN) == 0 && (cols & 7) == 0;
+    unsigned d = 0, over = 0;
+    if (bx < (cols >> 3) && by < (rows >> 3)) {          // a block of the plane: its 64 samples lie inside rows x cols
+        const long long o = (long long)(8 * by) * cols + 8 * bx;
+        typename SadRow<S>::Lane acc;
+        if (vec) {
+            Vec va[8], vb[8];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                va[r] = *reinterpret_cast<const Vec *>(pa + o + (long long)r * cols);
+                vb[r] = *reinterpret_cast<const Vec *>(pb + o + (long long)r * cols);
+            }
+#pragma unroll
+            for (int r = 0; r < 8; ++r) SadRow<S>::add(acc, va[r], vb[r]);
+        } else {
+            for (int r = 0; r < 8; ++r) {
+                const S *ra = pa + o + (long long)r * cols, *rb = pb + o + (long long)r * cols;
+#pragma unroll
+                for (int i = 0; i < 8; ++i) acc.one(ra[i], rb[i]);
+            }
+        }
+        d = acc.sum();
+        over = d > lo ? 1u : 0u;
+    }
+    __shared__ unsigned partial[2][SAD_LANES / 64];
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) d = max(d, (unsigned)__shfl_xor(d, s)), over += __shfl_xor(over, s);
+    if ((threadIdx.x & 63) == 0) partial[0][threadIdx.x >> 6] = d, partial[1][threadIdx.x >> 6] = over;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned m = 0, c = 0;
+#pragma unroll
+        for (int w = 0; w < SAD_LANES / 64; ++w) m = max(m, partial[0][w]), c += partial[1][w];
+        atomicMax(&out[6 * n + 2 * p], (unsigned long long)m);
+        atomicAdd(&out[6 * n + 2 * p + 1], (unsigned long long)c);
+    }
+}
+
 // ---- hold-out scoring: the cross-fade of two payloads ---------------------------------------------------------------------------------
 // out_n[i] = (a_n[i] (den - k) + b_n[i] k + (den >> 1)) / den with k = num0 + n num_step, i over the `samples` samples of a row: the
 // frame-blend baseline, rounded half up.  The numerator is below 65535 * 65535 + 32768 < 2^32.  THE DIVISION is the multiply-shift of
@@ -1309,7 +1395,7 @@ extern "C" int ssm_frames_accumulate_hdr_fwd(ssm_view src, ssm_view acc, int N, 
 
 
 // ---- the pair entry points: two payloads in, sums or a third payload out -------------------------------------------------------------
-// ssm_luma_sad_fwd, ssm_field_diff_fwd, ssm_plane_sse_fwd, ssm_plane_ssim_fwd and ssm_payload_mix_fwd refuse in one order: pair_given (pointers, N), the
+// ssm_luma_sad_fwd, ssm_field_diff_fwd, ssm_plane_sse_fwd, ssm_plane_ssim_fwd, ssm_block_sad_fwd and ssm_payload_mix_fwd refuse in one order: pair_given (pointers, N), the
 // entry's own sizes, check_pair (strides, alignment), what only that entry asks, grid_fits - and only then queue anything: a refused call
 // queues nothing, not even the clear.
 struct PairEntry {
@@ -1451,6 +1537,29 @@ extern "C" int ssm_plane_ssim_fwd(const void *a, const void *b, long long stride
                    reinterpret_cast<unsigned long long *>(sums));
     });
     return ssm::check_launch("ssm_plane_ssim_fwd");
+}
+
+extern "C" int ssm_block_sad_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int layout,
+                                 int sample_bytes, int lo, unsigned long long *out, void *stream) {
+    if (const int e = pair_given("block_sad", a, b, out, N)) return e;
+    if (const int e = check_frame("block_sad", H, W, layout, sample_bytes)) return e;
+    const YuvPlanes pl = yuv_planes(H, W, layout);
+    const PairEntry k = {"block_sad", "frame", pl.frame() * sample_bytes};
+    if (const int e = check_pair(k, true, false, a, b, stride_a, stride_b, N, sample_bytes, nullptr)) return e;
+    SSM_REQUIRE(lo >= 0 && lo <= (1 << 22), "block_sad: lo=%d outside 0..2^22", lo);
+    SSM_REQUIRE(reinterpret_cast<size_t>(out) % 8 == 0, "block_sad: out is not 8-byte aligned");
+    const auto tiles = [](int samples, int per) { return (long long)((samples >> 3) + per - 1) / per; };
+    const long long tx0 = tiles(pl.w, SAD_BW), tx1 = tiles(pl.cw, SAD_BW);
+    const long long g0 = tx0 * tiles(pl.h, SAD_BH), g1 = tx1 * tiles(pl.ch, SAD_BH);
+    if (const int e = grid_fits(k, g0 + 2 * g1)) return e;
+    if (const int e = clear_sums(k.name, out, 6 * (size_t)N, stream)) return e;
+    if (g0 + 2 * g1 == 0) return SSM_OK;          // no plane has a block: the cleared words are the result
+    const unsigned char *pa = static_cast<const unsigned char *>(a), *pb = static_cast<const unsigned char *>(b);
+    with_sample(sample_bytes, [&](auto s) {
+        SSM_LAUNCH(block_sad_kernel<decltype(s)>, dim3((unsigned)(g0 + 2 * g1), N), dim3(SAD_LANES), 0, (hipStream_t)stream, pa, pb, stride_a,
+                   stride_b, pl.h, pl.w, pl.ch, pl.cw, (unsigned)tx0, (unsigned)tx1, (unsigned)g0, (unsigned)g1, (unsigned)lo, out);
+    });
+    return ssm::check_launch("ssm_block_sad_fwd");
 }
 
 // first and one-past-last byte address of N rows of `row` bytes, `stride` bytes apart (either sign, or 0)

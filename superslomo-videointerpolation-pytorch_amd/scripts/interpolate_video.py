@@ -59,6 +59,19 @@ again.  What follows sees the film's own frames, byte for byte, as a progressive
 goes with every option but --deinterlace: --detelecine --fps 60000:1001 is 24 -> 60 without the 2-3 judder.  The field order falls out of
 the data: It, Ib, Ip and I? headers are all taken.  There is no threshold; the windows whose cadence changed go to --log with their best
 and second-best score.  2:2 and mixed cadences, soft telecine and the orphan field at an edit inside a cycle are out of scope.
+
+--dedup [HI:LO:FRAC] [--dedup_max D]: the input holds frames that repeat the one before - animation drawn on twos or threes, 24 or 25
+frames/s brought to 50 or 60 by repetition, screen recordings, captures that filled a dropped frame with a copy - and runs of up to D
+(default 2) such frames are repaired: the output keeps the grid of --upsample_rate (frame count and rate are what they are without the
+option), but the places of the repeats, and of everything between the run's two neighbours, are filled by frames synthesised between
+those two, so slow motion of such a clip no longer stutters as its source did.  --upsample_rate 1 is legal here and means repair only.
+A frame is a repeat when, in every plane, no 8 x 8 block differs from the frame before by more than HI in its sum of absolute
+differences, and at most the fraction FRAC of the blocks by more than LO (summed on the GPU, ssm_block_sad_fwd, a chunk ahead of the
+loop).  The defaults, 768:320:0.33 scaled to the clip's bit depth, are the numbers of ffmpeg's mpdecimate, not its construction, and
+not measured on compressed footage: a convention; 0:0:0 takes exact repeats only.  A longer run is a still and a run at the clip's end
+has no right neighbour: both stay as they are.  Every run goes to --log with its length, whether it was repaired, and its worst block
+sum and count.  It goes with --slowmo, --matrix, --range, --flow_scale, --tile and --detelecine (which runs first), not with --fps,
+--speed, --shutter, --scene_cut or --deinterlace: chain two runs,  ... --dedup --upsample_rate 1 --output - | interpolate_video.py ... .
 """
 import argparse
 import configparser
@@ -132,7 +145,21 @@ def getargs(argv=None):
     parser.add_argument("--detelecine", action="store_true",
                         help="The input is film in 3:2 pulldown: find the cadence, drop the repeated fields and pair the split ones again "
                              "before anything else; the clip then runs as progressive at 4/5 of its rate. Not together with --deinterlace.")
+    parser.add_argument("--dedup", type=_named(V.parse_dedup), nargs="?", const=True, default=None, metavar="HI:LO:FRAC",
+                        help="Repair runs of frames that repeat the one before: their places are filled by frames synthesised between the "
+                             "run's neighbours. HI:LO:FRAC: per plane no 8x8 block sum of absolute differences above HI and at most FRAC of "
+                             "the blocks above LO; default 768:320:0.33 at 8 bits (a convention), 0:0:0 exact repeats only. Default: off.")
+    parser.add_argument("--dedup_max", type=_named(V.parse_dedup_max_text), default=V.DEDUP_MAX, metavar="D",
+                        help="With --dedup: the longest run of repeats that is repaired; longer runs are stills and stay. Default 2.")
     args = parser.parse_args(argv)
+    if args.dedup is not None:
+        for flag, given in (("--fps", args.fps is not None), ("--speed", args.speed is not None), ("--shutter", args.shutter is not None),
+                            ("--scene_cut", args.scene_cut is not None), ("--deinterlace", args.deinterlace is not None)):
+            if given:
+                parser.error("--dedup does not go together with %s: it repairs repeated frames on the grid of --upsample_rate and nothing "
+                             "else; pipe the output of --dedup --upsample_rate 1 into a second run" % flag)
+        if args.upsample_rate is not None and args.upsample_rate < 1:
+            parser.error("--upsample_rate must be at least 1 with --dedup (got %d)" % args.upsample_rate)
     if args.detelecine and args.deinterlace is not None:
         parser.error("--detelecine does not go together with --deinterlace: pulldown removal pairs the fields of a film frame again, "
                      "deinterlacing writes every field as a frame of its own")
@@ -175,7 +202,7 @@ def main(argv=None, model=None):
     vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate, matrix=matrix, color_range=crange,
                              flow_scale=args.flow_scale, tile=args.tile, halo=args.halo, blend=args.blend, target_rate=args.fps, speed=args.speed,
                              shutter=args.shutter, shutter_samples=args.shutter_samples, scene_cut=args.scene_cut,
-                             shutter_light=args.shutter_light, deinterlace=args.deinterlace)
+                             shutter_light=args.shutter_light, deinterlace=args.deinterlace, dedup=args.dedup, dedup_max=args.dedup_max)
     with V.Y4MReader(args.input, extended=True, interlaced=args.deinterlace is not None or args.detelecine) as reader:
         if args.detelecine:
             log.info("[%s] detelecine: %d:%d frames/s in, film at %d:%d", args.expt, *reader.rate, *V.detelecine_rate(reader.rate))
@@ -192,6 +219,9 @@ def main(argv=None, model=None):
                          "coded values" if args.shutter_light == "coded" else "light (%s)" % args.shutter_light)
         else:
             rate = V.output_rate(reader.rate, args.upsample_rate, args.slowmo)
+            if args.dedup is not None:
+                log.info("[%s] dedup: hi:lo:frac = %s:%s:%s, runs of up to %d repeats are repaired, slots = %d times per pair", args.expt,
+                         *V.dedup_thresholds(args.dedup, getattr(reader, "bits", 8)), args.dedup_max, vi.gap_timeline().slots)
         out_range = crange if crange is not None else (reader.color_range if reader.color_range is not None else V.LIMITED)
         log.info("[%s] %s: %dx%d C%s at %d:%d frames/s -> %s at %d:%d", args.expt, args.input, reader.width, reader.height, reader.chroma,
                  reader.rate[0], reader.rate[1], args.output, rate[0], rate[1])
@@ -207,6 +237,12 @@ def main(argv=None, model=None):
                          0 if last is None else first, h, "bottom" if h >= 5 else "top", h % 5, best, second)
             last = h
         log.info("[%s] detelecine: %d windows, %d input frames dropped", args.expt, len(reader.cadence), reader.dropped)
+    for first, m, repaired, worst_max, worst_over in vi.repeats:
+        log.info("[%s] dedup: %d repeat%s from input frame %d: %s; worst block sum %d, most blocks over lo %d", args.expt, m, "" if m == 1 else "s",
+                 first, "repaired" if repaired else "left as they are (%s)" % ("a still" if m > args.dedup_max else "the clip ends"), worst_max,
+                 worst_over)
+    if args.dedup is not None:
+        log.info("[%s] dedup: %d runs, %d repaired", args.expt, len(vi.repeats), sum(1 for r in vi.repeats if r[2]))
     for i, score in vi.cuts:
         log.info("[%s] scene cut between input frames %d and %d: score %s = %.6f (threshold %s)", args.expt, i, i + 1, score, float(score),
                  vi.scene_cut)

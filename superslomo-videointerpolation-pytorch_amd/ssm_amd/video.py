@@ -37,6 +37,11 @@
   detelecine_host /       ssm_field_diff_fwd, the cadence decision from those sums in Python ints (Cadence), and the reader that undoes the
   field_diff / Cadence    pulldown in front of the loop - TelecineSource(reader, dev): downstream sees the film's frames as a progressive clip at
   / TelecineSource        detelecine_rate; every mode of VideoInterpolator is unchanged by it
+  block_sad_host /        repeated frames (animation on twos and threes, 24 -> 60 by repetition, filled drops): per pair and plane the largest
+  block_sad / Repeats /   8 x 8 block sum of |difference| and the number of blocks above `lo`, by numpy and by ssm_block_sad_fwd; the repeat
+  dedup_host /            decision and the runs in Python ints and Fractions; the reader that takes the repaired repeats out in front of the
+  RepeatSource /          loop and the timeline over the frames that stay, which puts synthesised frames where the repeats stood -
+  GapTimeline             VideoInterpolator(dedup=, dedup_max=): the fixed grid's frame count and rate, every other mode unchanged
   (ssm_amd/video_score.py) hold-out scoring: the clip against its own held-out frames, plane_sse / HoldOutScorer on this loop's ring, Clip and
                           buffers; the PSNR of what VideoInterpolator(upsample_rate=hold) would write - this module is unchanged by it
 
@@ -54,7 +59,10 @@ skipping the GPU work of a cut pair, scene cuts together with a shutter; a measu
 held-out frames (SSIM, VMAF), and that score for the timeline, shutter and scene-cut outputs; of interlaced clips: mixed field order (Im),
 scene cuts between fields, deinterlacing and retiming in one pass (chain two runs), the true vertical
 chroma siting of a 4:2:0 field (a quarter line off the layout's rule, which is what the fields are converted with); of pulldown removal:
-2:2, 2:3:3:2 and mixed cadences, soft telecine, the orphan field at an edit inside a cycle, comb metrics, noisy or compressed sources.
+2:2, 2:3:3:2 and mixed cadences, soft telecine, the orphan field at an edit inside a cycle, comb metrics, noisy or compressed sources;
+of repeated frames: timestamps (timecode files), dropping repeats instead of repairing them, dedup together with target_rate, speed,
+shutter, scene_cut or deinterlace (chain two runs), a scene cut on the frame after a run, comparison against a run's first frame,
+agreement with ffmpeg's mpdecimate frame for frame, noisy or compressed footage.
 """
 import ctypes
 import functools
@@ -1064,6 +1072,272 @@ class TelecineSource:
         self.close()
 
 
+# ---- repeated frames ------------------------------------------------------------------------------------------------------------------
+# The definition is in include/ssm_hip.h and DESIGN 3.12: 8 x 8 blocks of every plane, per pair and plane the largest block sum of |a - b|
+# and the number of blocks above `lo`; a frame repeats the one before iff every plane that has blocks stays within (hi, floor(frac blocks)).
+# The numbers are ffmpeg's mpdecimate defaults at 8 bits (64 * 12, 64 * 5, 0.33), the construction is not: a convention.
+DEDUP_HI, DEDUP_LO, DEDUP_FRAC = 768, 320, Fraction(33, 100)
+DEDUP_MAX = 2                      # the longest run that is repaired: animation on threes, 2:3 repetition
+BLOCK_SAD_MAX = 1 << 22            # above every block sum (64 * 65535): the largest `lo` ssm_block_sad_fwd takes
+
+
+def block_counts(h, w, siting):
+    """The 8 x 8 blocks of the Y, U and V plane of an h x w frame: (rows >> 3) * (cols >> 3) each; 0 for a plane below 8 rows or columns."""
+    ch, cw = chroma_dims(h, w, siting)
+    return ((h >> 3) * (w >> 3), (ch >> 3) * (cw >> 3), (ch >> 3) * (cw >> 3))
+
+
+def parse_dedup(text=None):
+    """The thresholds of the repeat test: "HI:LO:FRAC" (two integers >= 0 in codes of the clip's depth, LO at most 2^22, and a decimal or
+    a fraction in [0, 1]: "768:320:0.33", "0:0:0" for exact repeats only), or such a triple -> (hi, lo, Fraction frac); None, "" or True
+    -> True, the defaults DEDUP_HI, DEDUP_LO scaled to the clip's depth and DEDUP_FRAC (dedup_thresholds).  Anything else is a ValueError
+    naming the value."""
+    if text is None or text is True or (isinstance(text, str) and not text.strip()):
+        return True
+    try:
+        hi, lo, frac = text.strip().split(":") if isinstance(text, str) else text
+        if any(isinstance(x, bool) or (not isinstance(x, str) and int(x) != x) for x in (hi, lo)):
+            raise ValueError
+        hi, lo = int(hi), int(lo)
+        frac = Fraction(frac.strip() if isinstance(frac, str) else frac)
+    except (ValueError, TypeError, ZeroDivisionError):
+        raise ValueError("the repeat thresholds are written HI:LO:FRAC, two integers and a decimal or a fraction, e.g. 768:320:0.33 or 0:0:0 "
+                         "(got %r)" % (text,)) from None
+    if hi < 0 or not 0 <= lo <= BLOCK_SAD_MAX or not 0 <= frac <= 1:
+        raise ValueError("the repeat thresholds HI:LO:FRAC want HI >= 0, LO in 0 .. 2^22 and FRAC in [0, 1] (got %r)" % (text,))
+    return hi, lo, frac
+
+
+def dedup_thresholds(dedup, bits=8):
+    """(hi, lo, frac) of a parsed `dedup` for samples of `bits` bits: the triple as given, or the defaults at that depth."""
+    dedup = parse_dedup(dedup)
+    return (DEDUP_HI << (bits - 8), DEDUP_LO << (bits - 8), DEDUP_FRAC) if dedup is True else dedup
+
+
+def parse_dedup_max(value):
+    if isinstance(value, bool) or int(value) != value or value < 1:
+        raise ValueError("dedup_max, the longest run of repeats that is repaired, is a whole number of at least 1 (got %r)" % (value,))
+    return int(value)
+
+
+def parse_dedup_max_text(text):
+    """parse_dedup_max of a command line's text."""
+    try:
+        return parse_dedup_max(int(str(text).strip()))
+    except ValueError:
+        raise ValueError("dedup_max, the longest run of repeats that is repaired, is a whole number of at least 1 (got %r)" % (text,)) from None
+
+
+def block_sad_host(a, b, h, w, siting, bits=8, lo=None):
+    """Yardstick of ssm_block_sad_fwd: payloads a, b [N, at least frame_bytes] uint8 (numpy; one of them may have a single row) -> uint64
+    [N, 3, 2]: per pair and plane (Y, U, V) the largest 8 x 8 block sum of |a_n - b_n| and the number of blocks whose sum is above `lo`
+    (None: the default DEDUP_LO at this depth); (0, 0) for a plane without blocks.  With bits > 8 over the 16-bit words."""
+    lo = DEDUP_LO << (bits - 8) if lo is None else int(lo)
+    fb = frame_bytes(h, w, siting, bits)
+    planes = []
+    for p in (a, b):
+        p = np.asarray(p)
+        assert p.dtype == np.uint8 and p.ndim == 2 and p.shape[1] >= fb, "payloads are [N, at least frame_bytes] uint8"
+        planes.append(split_planes(np.ascontiguousarray(p[:, :fb]), h, w, siting, bits))
+    n = max(planes[0][0].shape[0], planes[1][0].shape[0])
+    out = np.zeros((n, 3, 2), np.uint64)
+    for p, (x, y) in enumerate(zip(*planes)):
+        by, bx = x.shape[1] >> 3, x.shape[2] >> 3
+        if by and bx:
+            d = np.abs(x[:, :8 * by, :8 * bx].astype(np.int64) - y[:, :8 * by, :8 * bx].astype(np.int64))
+            d = d.reshape(d.shape[0], by, 8, bx, 8).sum(axis=(2, 4)).reshape(d.shape[0], -1)
+            out[:, p, 0], out[:, p, 1] = d.max(axis=1), (d > lo).sum(axis=1)
+    return out
+
+
+def block_sad(payload_a, payload_b, h, w, siting, bits=8, lo=None, out=None):
+    """ssm_block_sad_fwd on payloads: [N, at least frame_bytes] uint8 device tensors (unit stride within a row, any row stride: frames
+    n + 1 and n of one buffer are fine; a single row goes against N) -> int64 [N, 3, 2] on the device (into `out` if given): per pair and
+    plane the largest 8 x 8 block sum of |a_n - b_n| and the number of blocks above `lo` (None: DEDUP_LO at this depth).  The words are
+    unsigned and below 2^63."""
+    lo = DEDUP_LO << (bits - 8) if lo is None else int(lo)
+    sb = sample_bytes(bits)
+    n, out, sa, sb_stride = _pair_operands(payload_a, payload_b, frame_bytes(h, w, siting, bits), "frame_bytes", out, (3, 2))
+    hb.check(hb.load().ssm_block_sad_fwd(payload_a.data_ptr(), payload_b.data_ptr(), sa, sb_stride, n, h, w, siting, sb, lo, out.data_ptr(),
+                                         hb.stream_ptr()))
+    return out
+
+
+class Repeats:
+    """The repeat decision, in Python ints and Fractions and free of the GPU.  blocks: block_counts of the frame.  feed(words) takes the
+    six words (max, over of Y, U, V: a row of block_sad / block_sad_host taken with this `lo`) of the next frame n = 1, 2, ... against
+    frame n - 1 and returns the frames that this closes, in order: (n, None) for a frame that stays - an ordinary input frame - or
+    (n, (r, right, t)) for a repaired repeat: its place is taken by the frame synthesised between frames r and right at the Fraction t.
+    The first call also closes frame 0, which is never a repeat.  A frame that is no repeat closes itself and the run before it; a repeat
+    waits until its run ends or outgrows dedup_max - so at most dedup_max frames wait.  end() closes the trailing run, every frame of it
+    an ordinary one (and frame 0 of a one-frame clip).  `log`: per run (first repeat, m, repaired or not, worst max, worst over) over
+    the run's frames and planes."""
+
+    def __init__(self, hi, lo, frac, blocks, dedup_max=DEDUP_MAX):
+        self.hi, self.lo, self.frac = int(hi), int(lo), Fraction(frac)
+        self.blocks, self.dedup_max = tuple(int(x) for x in blocks), parse_dedup_max(dedup_max)
+        assert len(self.blocks) == 3
+        self.allowed = tuple((self.frac * x).__floor__() for x in self.blocks)
+        self.log = []
+        self._fed, self._wait, self._run = 0, [], None          # frames fed; the repeats that wait; the open run as [first, m, max, over]
+
+    def is_repeat(self, words):
+        w = [int(x) for x in np.asarray(words).reshape(-1)]
+        assert len(w) == 6
+        return all(w[2 * p] <= self.hi and w[2 * p + 1] <= self.allowed[p] for p in range(3) if self.blocks[p])
+
+    def _end_run(self, repaired):
+        first, m, worst_max, worst_over = self._run
+        self.log.append((first, m, repaired, worst_max, worst_over))
+        self._run = None
+
+    def feed(self, words):
+        self._fed += 1
+        n = self._fed
+        out = [(0, None)] if n == 1 else []
+        w = [int(x) for x in np.asarray(words).reshape(-1)]
+        if self.is_repeat(w):
+            if self._run is None:
+                self._run = [n, 0, 0, 0]
+            self._run[1] += 1
+            self._run[2], self._run[3] = max(self._run[2], *w[0::2]), max(self._run[3], *w[1::2])
+            self._wait.append(n)
+            if self._run[1] > self.dedup_max:          # a still: what waited, and every further frame of the run, stays
+                out += [(k, None) for k in self._wait]
+                self._wait = []
+            return out
+        if self._run is not None:
+            r, g = self._run[0] - 1, self._run[1] + 1
+            out += [(k, (r, n, Fraction(k - r, g))) for k in self._wait]
+            self._end_run(bool(self._wait))
+            self._wait = []
+        return out + [(n, None)]
+
+    def end(self):
+        out = [(0, None)] if self._fed == 0 else []
+        out += [(k, None) for k in self._wait]
+        self._wait = []
+        if self._run is not None:
+            self._end_run(False)
+        return out
+
+
+def dedup_host(frames, h, w, siting=CENTRED, bits=8, dedup=True, dedup_max=DEDUP_MAX):
+    """The whole definition in numpy, the yardstick of RepeatSource: payloads [n, frame_bytes] -> (the action of every frame, [(n, None |
+    (r, right, t))] as Repeats hands them out, the Repeats that decided, for its log)."""
+    frames = np.ascontiguousarray(frames).reshape(-1, frame_bytes(h, w, siting, bits))
+    hi, lo, frac = dedup_thresholds(dedup, bits)
+    rep, actions = Repeats(hi, lo, frac, block_counts(h, w, siting), dedup_max), []
+    if len(frames) > 1:
+        for words in block_sad_host(frames[1:], frames[:-1], h, w, siting, bits, lo):
+            actions += rep.feed(words)
+    actions += rep.end()
+    return actions, rep
+
+
+class RepeatSource:
+    """A reader that takes the repaired repeats out of a clip: wraps a Y4MReader (or anything with its attributes, a TelecineSource for
+    one) and hands out the frames that stay, each with the gap before it - `gap` after read_frame_into: 0 for frame 0, 1 after an
+    ordinary neighbour, m + 1 behind a repaired run of m repeats - and, a frame ahead, `next_gap`: the gap of the frame that the next
+    call will hand out, 0 at the end of the clip (it is what tells a planner whether the pair to the right runs).  on_gap(g), if set, is
+    called once per frame that stays, in order, when its gap is known.  It has the reader's format attributes and rate, frames_read
+    (frames handed out), and of the decision so far `repeats` (Repeats.log).
+
+    A chunk is frames_per_chunk new frames behind the carried last dedup_max + 1 frames of the chunk before, in one pinned buffer, and
+    with the last of those in one device buffer; both are made once.  Per chunk, on a stream of its own: one H2D, one ssm_block_sad_fwd
+    (row n + 1 against row n, one stride each), one D2H of the words, one event wait; never a wait per frame.  dedup_max + 1 frames are
+    carried because that many may still be wanted: the repeats that wait for the end of their run, and in front of them the frame that
+    stays and waits to be handed out until its right neighbour's gap is known.  The repeats' bytes go nowhere; the bytes handed out do
+    not depend on frames_per_chunk."""
+
+    def __init__(self, reader, dev, dedup=True, dedup_max=DEDUP_MAX, frames_per_chunk=8):
+        assert frames_per_chunk >= 1
+        self.reader, self.dev = reader, torch.device(dev)
+        if self.dev.type != "cuda":
+            raise RuntimeError("the repeat test takes its block differences on the GPU (the HIP path has no CPU fallback)")
+        for name in ("width", "height", "siting", "chroma", "color_range", "aspect", "xtags", "frame_bytes", "rate"):
+            setattr(self, name, getattr(reader, name))
+        self.bits, self.extended = getattr(reader, "bits", 8), getattr(reader, "extended", False)
+        self.sample_bytes = sample_bytes(self.bits)
+        self.interlace, self.field_order, self.field_bytes = getattr(reader, "interlace", "p"), None, None
+        hi, self.lo, frac = dedup_thresholds(dedup, self.bits)
+        self._repeats = Repeats(hi, self.lo, frac, block_counts(self.height, self.width, self.siting), dedup_max)
+        self.frames_read, self.gap, self.on_gap = 0, None, None
+        self._rows, self._carry = frames_per_chunk, self._repeats.dedup_max + 1
+        self._host = torch.empty(self._carry + self._rows, self.frame_bytes, dtype=torch.uint8).pin_memory()      # [carried | the chunk]
+        self._np = self._host.numpy()
+        self._dev = torch.empty(self._rows + 1, self.frame_bytes, dtype=torch.uint8, device=self.dev)
+        self._words = torch.empty(self._rows, 3, 2, dtype=torch.int64, device=self.dev)
+        self._host_words = torch.empty(self._rows, 3, 2, dtype=torch.int64).pin_memory()
+        self._np_words = self._host_words.numpy().view(np.uint64)
+        self._stream, self._event = torch.cuda.Stream(self.dev), torch.cuda.Event()
+        self._base = None          # the clip's frame in row 0 of the pinned buffer (below 0 in the first chunk); None before it
+        self._pending, self._eof = [], False          # [(a frame that stays, its gap)], not yet handed out
+        self._last_kept = 0
+
+    def _chunk(self):
+        """The next chunk: its frames into the buffer behind the carried ones, their block differences, and what the decision closes."""
+        rows, c = self._rows, self._carry
+        if self._base is None:
+            if not self.reader.read_frame_into(self._np[c - 1]):
+                raise Y4MError("the Y4M stream holds no frame")
+            self._base = 1 - c
+        else:
+            self._base += rows          # a chunk that is not the last one is full
+            self._np[:c] = self._np[rows:rows + c].copy()
+        k = 0
+        while k < rows and self.reader.read_frame_into(self._np[c + k]):
+            k += 1
+        self._eof = k < rows
+        closed = []
+        if k:
+            with torch.cuda.stream(self._stream):
+                self._dev[:k + 1].copy_(self._host[c - 1:c + k], non_blocking=True)
+                block_sad(self._dev[1:k + 1], self._dev[:k], self.height, self.width, self.siting, self.bits, self.lo, out=self._words[:k])
+                self._host_words[:k].copy_(self._words[:k], non_blocking=True)
+                self._event.record()
+            self._event.synchronize()
+            for words in self._np_words[:k]:
+                closed += self._repeats.feed(words)
+        if self._eof:
+            closed += self._repeats.end()
+        for n, act in closed:
+            if act is None:          # a frame that stays
+                g = n - self._last_kept
+                self._pending.append((n, g))
+                self._last_kept = n
+                if self.on_gap is not None:
+                    self.on_gap(g)
+
+    next_gap = property(lambda self: self._pending[0][1] if self._pending else 0)
+
+    def read_frame_into(self, buf):
+        """The next frame that stays into `buf`; False at the end of the clip.  `gap` is then its gap, `next_gap` the next one's."""
+        while len(self._pending) < 2 and not self._eof:
+            self._chunk()
+        if not self._pending:
+            return False
+        n, self.gap = self._pending.pop(0)
+        out = np.frombuffer(memoryview(buf).cast("B"), np.uint8)
+        if out.size != self.frame_bytes:
+            raise ValueError("buffer of %d bytes for frames of %d" % (out.size, self.frame_bytes))
+        assert 0 <= n - self._base < self._np.shape[0], "a frame that stays is among the carried frames or in the chunk"
+        out[:] = self._np[n - self._base]
+        self.frames_read += 1
+        return True
+
+    repeats = property(lambda self: self._repeats.log)
+
+    def close(self):
+        self.reader.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 # ---- output order -------------------------------------------------------------------------------------------------------------------
 def pass_order(valid, nt):
     """Write order of one pass of `valid` pairs with nt interpolated frames each: ("interp", row of the pass's output buffer) for the
@@ -1377,6 +1651,60 @@ class PassPlanner:
         return self._close()
 
 
+class GapTimeline:
+    """The timeline of a clip whose repaired repeats are taken out (RepeatSource), over the frames that stay: frame i sits gap(i) input
+    frames behind frame i - 1, and the output keeps the fixed grid of upsample_rate N on the INPUT's clock.  Pair (i - 1, i) with gap g
+    gets g N - 1 synthesised frames at t = j / (g N), j = 1 .. g N - 1, and frame i follows as its own bytes: an ordinary pair (g = 1)
+    gets the fixed grid's N - 1, a pair across a repaired run of m = g - 1 repeats fills the run's places as well.  It offers what
+    PassPlanner asks of a Timeline - slots, count, times, feed - and nothing else of it; Timeline stays as it is.
+
+    The gaps come in as they are decided: gap(g) once per frame that stays, in order, 0 for frame 0 (RepeatSource.on_gap), each before
+    the frame to its left is fed - a planner asks count(i) when frame i has just been read, and a pair runs iff it gets a frame.  A gap
+    not yet given counts as the end of the clip.  slots = (dedup_max + 1) N - 1, the most any pair can get; a plan that takes fewer is
+    refused by D and N.  Memory: the gaps of the frames not yet fed, and one more."""
+
+    def __init__(self, rate, dedup_max=DEDUP_MAX, max_slots=None):
+        if isinstance(rate, bool) or int(rate) != rate or rate < 1:
+            raise ValueError("with dedup the upsample_rate is a whole number of at least 1 (1: repair only; got %r)" % (rate,))
+        self.rate, self.dedup_max = int(rate), parse_dedup_max(dedup_max)
+        self.slots = (self.dedup_max + 1) * self.rate - 1
+        if max_slots is not None and self.slots > max_slots:
+            raise ValueError("dedup_max D = %d at upsample_rate N = %d puts up to (D + 1) N - 1 = %d frames between two input frames; the "
+                             "plan takes at most %d (the largest upsample_rate - 1 at this pairs_per_batch): lower D or N"
+                             % (self.dedup_max, self.rate, self.slots, max_slots))
+        self._gaps, self._given, self._fed = {}, 0, 0
+
+    def gap(self, g):
+        """The gap in front of the next frame that stays: 0 for frame 0, then 1 .. dedup_max + 1."""
+        assert (g == 0) == (self._given == 0) and 0 <= g <= self.dedup_max + 1, (g, self._given)
+        self._gaps[self._given] = int(g)
+        self._given += 1
+
+    def count(self, i):
+        """Synthesised frames of pair (i, i + 1): g N - 1 for its gap g; 0 where frame i + 1 is not known (the end of the clip)."""
+        g = self._gaps.get(i + 1)
+        return g * self.rate - 1 if g else 0
+
+    def times(self, i):
+        """The t of pair (i, i + 1)'s synthesised frames, increasing."""
+        gn = self._gaps.get(i + 1, 0) * self.rate
+        return [Fraction(j, gn) for j in range(1, gn)]
+
+    t32 = staticmethod(Timeline.t32)
+
+    def feed(self, end=False):
+        """Timeline.feed over the frames that stay: once per frame read, the [(i, t)] that frame closes - the synthesised frames of the
+        pair to its left, then the frame itself; end=True rewinds for the next clip."""
+        if end:
+            self._gaps, self._given, self._fed = {}, 0, 0
+            return []
+        f = self._fed
+        out = [(f - 1, t) for t in self.times(f - 1)] if f else []
+        self._gaps.pop(f - 1, None)
+        self._fed += 1
+        return out + [(f, Fraction(0))]
+
+
 # One output is open at a time.  The samples in time order are the (k, j) in lexicographic order (Timeline), the accumulate calls follow
 # that order within a pass and - through the event a pass waits for before its first one - from pass to pass, and an output is egressed
 # right after its last call: the first call of output k + 1 (init = 1) comes after the egress of output k.  So between an output's first
@@ -1628,7 +1956,7 @@ class VideoInterpolator:
 
     def __init__(self, model, cfg, upsample_rate=None, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
                  tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8, scene_cut=None,
-                 shutter_light="coded", deinterlace=None):
+                 shutter_light="coded", deinterlace=None, dedup=None, dedup_max=DEDUP_MAX):
         """target_rate = (num, den) and / or speed (a Fraction, or what Fraction() takes; 1/4 is four times slower): the output follows
         Timeline(speed * input rate / target_rate) instead of the fixed grid of upsample_rate, which is then not used (see
         _run_timeline); with both None nothing changes.  flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
@@ -1662,7 +1990,15 @@ class VideoInterpolator:
         I?; "tff" and "bff" override any header.  The fields run through the fixed grid of upsample_rate = 2 at t = 1/2, at half the
         frame's height: matrix (None: default_matrix of the FRAME's height), color_range, flow_scale and tile / halo / blend act as
         they do there.  It does not go together with an upsample_rate, target_rate, speed, shutter, scene_cut or a recurrent model
-        (chain a second run to retime the progressive output).  None: every other mode as it is."""
+        (chain a second run to retime the progressive output).  None: every other mode as it is.
+        dedup (True: the default thresholds at the clip's depth; or (hi, lo, frac) / "HI:LO:FRAC", parse_dedup) with dedup_max = D:
+        frames that repeat the one before (Repeats, from the 8 x 8 block differences of ssm_block_sad_fwd) in runs of at most D are
+        repaired - the output keeps the fixed grid of upsample_rate, and the places of a run's repeats and of the frames around them
+        are filled by frames synthesised between the run's two neighbours (GapTimeline; a RepeatSource in front of the timeline
+        mode's loop).  upsample_rate = 1 is then legal and means repair only.  `repeats` lists the runs after run(): (first repeat, m,
+        repaired, worst max, worst over).  The defaults are the numbers of ffmpeg's mpdecimate, a convention, not its construction and
+        not backed by a measurement on compressed footage.  It does not go together with target_rate, speed, shutter, scene_cut or
+        deinterlace (chain two runs).  None: every mode as it is, launch for launch."""
         from .coarse import check_scale
         from .tiles import check_args
         self.flow_scale = check_scale(flow_scale)
@@ -1677,6 +2013,15 @@ class VideoInterpolator:
         n_frames = cfg.getint("TRAIN", "N_FRAMES")
         if n_frames != 2:
             raise NotImplementedError("N_FRAMES=%d needs the recurrent bottleneck (unpinned upstream); use N_FRAMES=2" % n_frames)
+        self.dedup = None if dedup is None or dedup is False else parse_dedup(dedup)
+        self.dedup_max, self.repeats = parse_dedup_max(dedup_max), []
+        if self.dedup is not None:
+            for name, given in (("target_rate", target_rate is not None), ("speed", speed is not None), ("shutter", shutter is not None),
+                                ("scene_cut", scene_cut is not None), ("deinterlace", deinterlace is not None),
+                                ("a recurrent model", getattr(model, "recurrent", False))):
+                if given:
+                    raise ValueError("dedup together with %s is not available: it repairs repeated frames on the fixed grid of upsample_rate "
+                                     "and nothing else; chain two runs (dedup with upsample_rate=1 first, then the other)" % name)
         self.deinterlace = parse_deinterlace(deinterlace)
         if self.deinterlace is not None:
             for name, given in (("upsample_rate", upsample_rate is not None), ("target_rate", target_rate is not None), ("speed", speed is not None),
@@ -1686,8 +2031,8 @@ class VideoInterpolator:
                     raise ValueError("deinterlace together with %s is not available: deinterlacing writes the clip's fields as frames at twice "
                                      "its rate and nothing else; retime its progressive output in a second run" % name)
         upsample_rate = 8 if upsample_rate is None else upsample_rate
-        if int(upsample_rate) < 2:
-            raise ValueError("upsample_rate must be at least 2")
+        if int(upsample_rate) < (2 if self.dedup is None else 1):
+            raise ValueError("upsample_rate must be at least 2" if self.dedup is None else "upsample_rate must be at least 1 with dedup")
         self.model, self.cfg, self.rate = model, cfg, int(upsample_rate)
         self.n_streams, self.pb = max(1, int(n_streams)), max(1, int(pairs_per_batch))
         if matrix is not None:
@@ -1720,6 +2065,10 @@ class VideoInterpolator:
         """The Timeline of a clip at `in_rate` (num, den); refuses a step whose slots the plan would not take."""
         return Timeline(timeline_step(in_rate, self.target_rate, self.speed), max_slots=MAX_STAGE2_BATCH // self.pb, shutter=self.shutter,
                         samples=self.samples)
+
+    def gap_timeline(self):
+        """The GapTimeline of a run with dedup; refuses a dedup_max and upsample_rate whose slots the plan would not take."""
+        return GapTimeline(self.rate, self.dedup_max, max_slots=MAX_STAGE2_BATCH // self.pb)
 
     def _pipeline(self, hp, wp, dev, n_t=None):          # n_t None: the fixed grid's upsample_rate - 1
         import os
@@ -1785,9 +2134,14 @@ class VideoInterpolator:
     @torch.no_grad()
     def run(self, reader, writer):
         """Returns the number of frames written: (n - 1) * upsample_rate + 1 for n input frames (with target_rate / speed:
-        floor((n - 1) / step) + 1; with a shutter: Timeline.n_outputs(n); with deinterlace: 2 n)."""
+        floor((n - 1) / step) + 1; with a shutter: Timeline.n_outputs(n); with deinterlace: 2 n; with dedup the fixed grid's count)."""
         clip = self._clip(reader, writer)
-        self.cuts = []
+        self.cuts, self.repeats = [], []
+        if self.dedup is not None:
+            tl = self.gap_timeline()
+            source = RepeatSource(reader, clip.dev, self.dedup, self.dedup_max)
+            source.on_gap, self.repeats = tl.gap, source.repeats
+            return self._run_timeline(clip, source, writer, tl)
         if self.deinterlace is not None:
             return self._run_fields(clip, reader, writer)
         if not self.timed:
@@ -2009,8 +2363,9 @@ class VideoInterpolator:
                 written += 1
         return written
 
-    def _run_timeline(self, clip, reader, writer):
-        """run() with target_rate / speed: the output frames are those of Timeline(speed * reader.rate / target_rate).
+    def _run_timeline(self, clip, reader, writer, tl=None):
+        """run() with target_rate / speed: the output frames are those of Timeline(speed * reader.rate / target_rate); with dedup those of
+        the GapTimeline `tl` over the frames that the RepeatSource `reader` hands on.
 
         Pairs now differ: pair (i, i + 1) gets tl.count(i) synthesised frames at its own times, and a pair that gets none is not run -
         no upload, no ingest, no stage 1 or 2, no egress.  A pass collects up to pairs_per_batch pairs that do run.  Every engine is
@@ -2029,7 +2384,7 @@ class VideoInterpolator:
         timeline skips pairs inside a pass (sad_runs): one ssm_luma_sad_fwd call then, one per run otherwise.  Only pairs that run are
         summed and fed to SceneCuts."""
         fb, dev, hp, wp, luma = clip.fb, clip.dev, clip.hp, clip.wp, clip.h * clip.w
-        tl = self.timeline(reader.rate)
+        tl = self.timeline(reader.rate) if tl is None else tl
         S, pb, n = tl.slots, self.pb, self.n_streams
         pipe = self._pipeline(hp, wp, dev, S) if S else None          # an integer step only picks input frames: nothing to run
         depth, cap = n + 2, 2 * pb + 2
