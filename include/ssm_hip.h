@@ -1000,6 +1000,56 @@ int ssm_field_diff_fwd(const void *a, const void *b, long long stride_a, long lo
 int ssm_block_sad_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int layout, int sample_bytes,
                       int lo, unsigned long long *out, void *stream);
 
+/* ---- letterboxed clips of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) --------------------------
+ * Definition (ssm_amd.video: active_counts_host, ActiveArea, cut_window_host and paste_window_host are all of it in numpy and Python ints,
+ * ActiveSource the streamed form).  A 2.39:1 picture inside a 16:9 frame leaves bars that hold, at most, a subtitle or a logo.
+ *   counts     rows[y] = the number of luma samples of row y whose value is above `limit`, cols[x] likewise of column x.  Chroma is not
+ *              looked at; with 16-bit words all 16 bits count.
+ *   lines      row y is ACTIVE in a frame iff rows[y] > frac * W, column x iff cols[x] > frac * H, compared exactly (integers against a
+ *              fraction).  Defaults limit = 24 * 2^(bits - 8), frac = 1/64: 24 is the NUMBER of ffmpeg cropdetect's `limit`, NOT its
+ *              construction (cropdetect averages a line), 1/64 is this project's own.  Conventions, not backed by a measurement on
+ *              compressed footage, whose bars are noisy; every clip here is synthetic.
+ *   rectangle  over the first P frames (active_probe, default 48; the whole clip if it is shorter) the smallest rectangle that holds every
+ *              active row and column of every probed frame, aligned OUTWARD to (ay, ax) = (2, 2) for SSM_YUV_420_*, (1, 2) for
+ *              SSM_YUV_422, (1, 1) for SSM_YUV_444: y0 and x0 multiples of it, the far edges multiples of it or the frame's own edge.
+ *   fallback   the run is the one without the option, byte for byte, if the rectangle is the whole frame, no probed frame has an active
+ *              row and column, or the rectangle is under 32 samples in a direction.
+ *   window     the rectangle (w, h, x0, y0) of a payload as a payload of its own, a genuine h x w frame of the same layout: luma rows
+ *              y0 .. y0 + h, columns x0 .. x0 + w; chroma rows y0 / ay .. ceil((y0 + h) / ay), columns x0 / ax .. ceil((x0 + w) / ax) with
+ *              (ay, ax) the layout's subsampling - the planes of yuv_planes(h, w), since y0 and x0 are aligned.
+ *   output     an output that coincides with an input frame is that frame's own bytes, whole.  A frame synthesised in pair (i, i + 1) at
+ *              exact time t is, inside the rectangle, the frame the pipeline makes of the two cut windows - canvas, plan and launches of
+ *              the cropped clip - and outside it the bytes of input i if t < 1/2, else of input i + 1: the rule of the scene cuts.
+ * ssm_luma_counts_fwd: frames + n stride (stride in BYTES, of either sign; with N = 1 it names nothing) points at the luma plane of frame
+ * n = 0 .. N-1, H x W samples, rows unpadded - a payload's first plane.  sample_bytes = 1: bytes; 2: 16-bit little-endian words.
+ *     rows[n H + y], cols[n W + x] = the counts above, exact, 32-bit words in device arrays of N H and N W
+ * Whatever the arrays held before, the call leaves them fully defined: the entry clears both on `stream` itself (two memset nodes ahead
+ * of the kernel).  No byte outside the N planes is read.
+ *   A workgroup of 256 lanes owns 256 columns x 32 rows of one frame (grid: column tiles, row bands, n): a lane four neighbouring columns -
+ *   one 4- or 8-byte load where the plane's start and W are multiples of four samples (per n, uniform), sample by sample otherwise and
+ *   never past a row's end - wave v of the four the rows v, v + 4, ... of the band.  Row counts: the lane's four flags, 64 lanes by
+ *   cross-lane shuffles, one 32-bit vector atomicAdd per row and column tile.  Column counts: four lane counters over the wave's eight
+ *   rows, the four waves' through LDS, one 32-bit vector atomicAdd per column and band.  Zero sums issue no atomic.  Integer adds
+ *   commute: the words are the same in every run.  Vector atomics only; no scratch, no packed fp32.  Reads sample_bytes per pixel.
+ * SSM_E_ARG (nothing is queued), each with its own message and in this order: null pointers; N outside 1..65535; H or W < 1; sample_bytes
+ * outside {1, 2}; with N > 1 a stride below the plane's bytes in magnitude; with sample_bytes = 2 an odd address, then an odd stride;
+ * limit outside 0..65535; rows or cols not 4-byte aligned; more than 65535 row bands (H > 2097120).
+ * ssm_window_cut_fwd: frames + n stride_in points at whole payloads of H x W frames in `layout`, windows + n stride_out at the packed
+ * windows of h x w at (y0, x0) that it writes (strides in BYTES, of either sign; with N = 1 they name nothing).  A byte mover: equal to
+ * cut_window_host byte for byte, bytes or 16-bit words as they stand.  Nothing outside the window's samples is read, nothing outside the
+ * N packed windows written.
+ *   The walk of ssm_fields_split_fwd over the WINDOW's rows: 16-byte pieces, Y's rows, then U's, then V's, a lane 4 pieces 256 apart; a
+ *   piece is one 16-byte load and store where it is whole and both addresses sit on 16-byte boundaries, sample by sample otherwise,
+ *   decided per piece.  One launch for the three planes.  Reads and writes the window's bytes once each.
+ * SSM_E_ARG (nothing is queued), in this order: null pointers; N outside 1..65535; H or W < 1; a layout outside SSM_YUV_*; sample_bytes
+ * outside {1, 2}; a window that is empty or leaves the frame; one that is not aligned to the layout's (ay, ax) - the message names them;
+ * a window of more than 2^31 - 1 pieces; with sample_bytes = 2 an odd address, then an odd stride; a stride below the frame's or the
+ * window's bytes; windows overlapping frames. */
+int ssm_luma_counts_fwd(const void *frames, long long stride, int N, int H, int W, int sample_bytes, int limit, unsigned *rows, unsigned *cols,
+                        void *stream);
+int ssm_window_cut_fwd(const void *frames, long long stride_in, void *windows, long long stride_out, int N, int H, int W, int y0, int x0, int h,
+                       int w, int layout, int sample_bytes, void *stream);
+
 /* ---- training ingest (csrc/ssm_data.hip; whole decoded uint8 HWC RGB frames on the device) --------------
  * The clip loader (ssm_amd/data.py) serves the reference's training transform, RandomCrop, then RandomMirrorRotate,
  * then Normalize and ToTensor (scripts/utils/dataloaders/default_reader.py:182-207,250-286, augmentations.py:

@@ -44,6 +44,11 @@
 //   fields_split_kernel /    interlaced clips: N frames -> their 2N fields (even rows of every plane, odd rows), and N fields with
 //   fields_weave_kernel      N synthesised fields (or, fill = 1, with integer line averages of the kept field itself) -> N frames; bytes moved
 //                            as they stand, 16-byte pieces of a row where the addresses allow, one launch for the three planes
+//   luma_counts_kernel       letterboxed clips, ssm_luma_counts_fwd: per frame the luma samples above a limit of every row and of every column; a
+//                            workgroup owns 256 columns x 32 rows, a lane four columns, a wave every fourth row; shuffles and LDS, then one
+//                            32-bit atomic per row and column tile and one per column and band
+//   window_cut_kernel        letterboxed clips, ssm_window_cut_fwd: the window of a rectangle of N payloads as packed payloads, the field
+//                            kernels' 16-byte pieces walked over the window's rows of the three planes
 // On the host the six pair entry points share pair_given and check_pair (operands, strides, alignment), grid_fits and clear_sums; yuv_planes is the one
 // place that knows the plane sizes of 4:2:0, 4:2:2 and 4:4:4, with_layout and with_sample pick a kernel's two template parameters.
 // Both conversions are HBM-bound (1.5 to 6 B in + 12 B out per pixel, and the reverse); so is the accumulation (4 (N + 1 + !init) B per
@@ -1123,6 +1128,111 @@ __global__ __launch_bounds__(LANES) void fields_weave_kernel(const unsigned char
     }
 }
 
+// ---- letterboxed clips: luma samples above a limit per row and per column, and the cut of a window ---------------------------------------
+// The definition is in include/ssm_hip.h.  rows[n H + y] += the samples of luma row y of frame n above `limit`, cols[n W + x] += those of
+// column x (ssm_luma_counts_fwd; the entry clears both arrays ahead of the kernel).  A workgroup of LANES lanes owns COUNT_COLS = 256
+// columns x COUNT_BAND = 32 rows of ONE frame: a lane four neighbouring columns (one 4- or 8-byte load where the plane's start and the row
+// pitch are multiples of it - per n, uniform - and the four lie inside the row; sample by sample otherwise, nothing past the row's end
+// loaded), wave v of the four the rows v, v + 4, ... of the band, so a wave's load is 256 or 512 contiguous bytes of a row.
+//   rows   the lane's four flags summed, the wave's 64 sums by shuffles, then lane 0 issues ONE 32-bit vector atomic per row and column
+//          tile (none where the sum is 0)
+//   cols   four 32-bit lane counters over the wave's rows, the four waves' through LDS, then lane t issues ONE 32-bit vector atomic for
+//          column t of the tile per band (none where the sum is 0)
+// A count is at most H or W < 2^31.  Integer adds commute: the same words in every run.
+constexpr int COUNT_COLS = 4 * 64, COUNT_BAND = 32, COUNT_WAVES = LANES / 64;
+static_assert(COUNT_COLS == LANES && COUNT_BAND % COUNT_WAVES == 0, "a lane closes one column of the tile; the waves share the band's rows evenly");
+
+template <typename S> struct Quad;          // four samples as one load
+template <> struct Quad<unsigned char> {
+    static __device__ __forceinline__ void load(const unsigned char *p, unsigned (&v)[4]) {
+        const unsigned q = *reinterpret_cast<const unsigned *>(p);
+        v[0] = q & 255u, v[1] = (q >> 8) & 255u, v[2] = (q >> 16) & 255u, v[3] = q >> 24;
+    }
+};
+template <> struct Quad<unsigned short> {
+    static __device__ __forceinline__ void load(const unsigned short *p, unsigned (&v)[4]) {
+        const i32x2 q = *reinterpret_cast<const i32x2 *>(p);
+        v[0] = (unsigned)q.x & 0xffffu, v[1] = (unsigned)q.x >> 16, v[2] = (unsigned)q.y & 0xffffu, v[3] = (unsigned)q.y >> 16;
+    }
+};
+
+template <typename S>
+__global__ __launch_bounds__(LANES) void luma_counts_kernel(const unsigned char *frames, long long stride, int H, int W, unsigned limit,
+                                                            unsigned *rows, unsigned *cols) {
+    __shared__ unsigned part[COUNT_WAVES][COUNT_COLS];
+    const int n = blockIdx.z, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const S *plane = reinterpret_cast<const S *>(frames + n * stride);
+    const long long x0 = (long long)blockIdx.x * COUNT_COLS + 4 * lane;
+    const int y0 = blockIdx.y * COUNT_BAND;
+    const bool vec = (reinterpret_cast<size_t>(plane) % (4 * sizeof(S))) == 0 && (W & 3) == 0;          // then x0 + 3 < W wherever x0 < W
+    unsigned c[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int k = 0; k < COUNT_BAND / COUNT_WAVES; ++k) {
+        const int y = y0 + wave + k * COUNT_WAVES;
+        if (y >= H) break;          // uniform over the wave
+        unsigned r = 0;
+        if (x0 < W) {
+            const S *row = plane + (long long)y * W + x0;
+            unsigned v[4] = {0u, 0u, 0u, 0u};          // 0 is above no limit
+            if (vec) {
+                Quad<S>::load(row, v);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (x0 + i < W) v[i] = row[i];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const unsigned f = v[i] > limit ? 1u : 0u;
+                c[i] += f, r += f;
+            }
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) r += __shfl_xor(r, d);
+        if (lane == 0 && r) atomicAdd(&rows[(long long)n * H + y], r);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) part[wave][4 * lane + i] = c[i];
+    __syncthreads();
+    unsigned t = 0;
+#pragma unroll
+    for (int w = 0; w < COUNT_WAVES; ++w) t += part[w][threadIdx.x];
+    const long long x = (long long)blockIdx.x * COUNT_COLS + threadIdx.x;
+    if (x < W && t) atomicAdd(&cols[(long long)n * W + x], t);
+}
+
+// windows_n = the h x w window at (y0, x0) of frames_n, a packed payload of the same layout (ssm_window_cut_fwd): the walk of the field
+// kernels over the WINDOW's rows - piece `id` counts the Y plane's rows x 16-byte pieces per row, then U's, then V's, a lane CHUNKS pieces
+// LANES apart - with the source piece in the frame's plane at the plane's own origin and row pitch.  move_piece decides per piece: one
+// 16-byte load and store where it is whole and both addresses sit on 16-byte boundaries, sample by sample otherwise.  Nothing outside the
+// window's samples is read, nothing outside the packed window written.
+struct WindowGeom {
+    unsigned rows[3], cols[3], pieces[3];          // of the window's planes: rows, samples per row, 16-byte pieces per row
+    unsigned start[3], total;                      // first piece of a plane; pieces of a window
+    long long dst[3];                              // first sample of a plane in the window's payload
+    long long src[3], pitch[3];                    // first sample of the window's part of a plane in the frame's payload; the frame plane's row
+};
+
+template <typename S>
+__global__ __launch_bounds__(LANES) void window_cut_kernel(const unsigned char *frames, long long stride_in, unsigned char *windows,
+                                                           long long stride_out, WindowGeom g) {
+    constexpr unsigned V = 16 / sizeof(S);
+    const int n = blockIdx.y;
+    const unsigned base = blockIdx.x * (unsigned)(LANES * CHUNKS) + threadIdx.x;
+    const unsigned char *src = frames + n * stride_in;
+    unsigned char *dst = windows + n * stride_out;
+#pragma unroll
+    for (int c = 0; c < CHUNKS; ++c) {
+        const unsigned id = base + (unsigned)c * LANES;
+        if (id >= g.total) break;
+        const int p = id >= g.start[2] ? 2 : id >= g.start[1] ? 1 : 0;
+        const unsigned local = id - g.start[p], y = local / g.pieces[p], k = local - y * g.pieces[p];
+        const unsigned count = min(V, g.cols[p] - k * V);
+        const unsigned char *a = src + (g.src[p] + (long long)y * g.pitch[p]) * (long long)sizeof(S) + 16ll * k;
+        move_piece<S>(dst + (g.dst[p] + (long long)y * g.cols[p]) * (long long)sizeof(S) + 16ll * k, a, a, count);
+    }
+}
+
 // first and one-past-last address, in bytes, of the floats a view of [n,c,h,w] names (strides of either sign)
 inline void view_range(const ssm_view &v, int n, int c, int h, int w, long long *lo, long long *hi) {
     long long a = 0, b = 0;
@@ -1680,4 +1790,89 @@ extern "C" int ssm_fields_weave_fwd(const void *kept, long long stride_kept, con
                    parity0, fill);
     });
     return ssm::check_launch("ssm_fields_weave_fwd");
+}
+
+// ---- letterboxed clips -------------------------------------------------------------------------------------------------------------------
+// ssm_luma_counts_fwd refuses in the order of ssm_block_sad_fwd - pointers, N, the plane, sample_bytes, the stride, 2-byte alignment, limit,
+// the arrays' alignment, the grid - and only then queues its two clears and the launch.
+extern "C" int ssm_luma_counts_fwd(const void *frames, long long stride, int N, int H, int W, int sample_bytes, int limit, unsigned *rows,
+                                   unsigned *cols, void *stream) {
+    const char *name = "luma_counts";
+    SSM_REQUIRE(frames && rows && cols, "%s: null pointer", name);
+    SSM_REQUIRE(N > 0 && N <= 65535, "%s: N=%d outside 1..65535", name, N);
+    SSM_REQUIRE(H > 0 && W > 0, "%s: bad plane size %dx%d", name, H, W);
+    SSM_REQUIRE(sample_bytes == 1 || sample_bytes == 2, "%s: sample_bytes %d not in {1, 2}", name, sample_bytes);
+    const long long plane = (long long)H * W * sample_bytes;
+    SSM_REQUIRE(N == 1 || std::llabs(stride) >= plane, "%s: stride %lld shorter than the plane's %lld bytes", name, stride, plane);
+    if (sample_bytes == 2) {
+        SSM_REQUIRE(reinterpret_cast<size_t>(frames) % 2 == 0, "%s: a plane of 2-byte samples is not 2-byte aligned", name);
+        SSM_REQUIRE(N == 1 || stride % 2 == 0, "%s: stride %lld of 2-byte samples must be even", name, stride);
+    }
+    SSM_REQUIRE(limit >= 0 && limit <= 65535, "%s: limit=%d outside 0..65535", name, limit);
+    SSM_REQUIRE(reinterpret_cast<size_t>(rows) % 4 == 0 && reinterpret_cast<size_t>(cols) % 4 == 0, "%s: rows or cols is not 4-byte aligned", name);
+    const long long gx = ((long long)W + COUNT_COLS - 1) / COUNT_COLS, gy = ((long long)H + COUNT_BAND - 1) / COUNT_BAND;
+    SSM_REQUIRE(gy <= 65535, "%s: a plane of %d rows is more than the grid takes", name, H);
+    if (N == 1) stride = 0;          // the stride of a single plane names nothing
+    const hipError_t e0 = ssm::memset_async(rows, 0, sizeof(unsigned) * (size_t)N * (size_t)H, (hipStream_t)stream);
+    const hipError_t e1 = e0 != hipSuccess ? e0 : ssm::memset_async(cols, 0, sizeof(unsigned) * (size_t)N * (size_t)W, (hipStream_t)stream);
+    if (e1 != hipSuccess) {
+        ssm::set_error("%s: memset failed: %s", name, hipGetErrorString(e1));
+        return SSM_E_LAUNCH;
+    }
+    with_sample(sample_bytes, [&](auto s) {
+        SSM_LAUNCH(luma_counts_kernel<decltype(s)>, dim3((unsigned)gx, (unsigned)gy, N), dim3(LANES), 0, (hipStream_t)stream,
+                   static_cast<const unsigned char *>(frames), stride, H, W, (unsigned)limit, rows, cols);
+    });
+    return ssm::check_launch("ssm_luma_counts_fwd");
+}
+
+// ssm_window_cut_fwd refuses in one order: pointers, N, the frame (size, layout, sample width), the rectangle (inside the frame, then
+// aligned for the layout), the grid, 2-byte alignment, strides, overlap - and only then queues the one launch.
+extern "C" int ssm_window_cut_fwd(const void *frames, long long stride_in, void *windows, long long stride_out, int N, int H, int W, int y0, int x0,
+                                  int h, int w, int layout, int sample_bytes, void *stream) {
+    const char *name = "window_cut";
+    SSM_REQUIRE(frames && windows, "%s: null pointer", name);
+    SSM_REQUIRE(N > 0 && N <= 65535, "%s: N=%d outside 1..65535", name, N);
+    if (const int e = check_frame(name, H, W, layout, sample_bytes)) return e;
+    SSM_REQUIRE(h > 0 && w > 0 && y0 >= 0 && x0 >= 0 && (long long)y0 + h <= H && (long long)x0 + w <= W,
+                "%s: the window %dx%d at (%d,%d) (h x w at y, x) lies outside the %dx%d frame", name, h, w, y0, x0, H, W);
+    const int ay = (layout == SSM_YUV_420_CENTRED || layout == SSM_YUV_420_COSITED) ? 2 : 1, ax = layout == SSM_YUV_444 ? 1 : 2;
+    SSM_REQUIRE(y0 % ay == 0 && x0 % ax == 0 && ((y0 + h) % ay == 0 || y0 + h == H) && ((x0 + w) % ax == 0 || x0 + w == W),
+                "%s: the window %dx%d at (%d,%d) is not aligned to (%d,%d) rows and columns, as layout %d asks: its origin a multiple, its far "
+                "edges a multiple or the frame's own", name, h, w, y0, x0, ay, ax, layout);
+    const YuvPlanes fr = yuv_planes(H, W, layout), wi = yuv_planes(h, w, layout);
+    WindowGeom g;
+    const long long per = 16 / sample_bytes;
+    long long pieces = 0;
+    for (int p = 0; p < 3; ++p) {
+        const long long rows = p ? wi.ch : wi.h, cols = p ? wi.cw : wi.w, pp = (cols + per - 1) / per;
+        g.rows[p] = (unsigned)rows, g.cols[p] = (unsigned)cols, g.pieces[p] = (unsigned)pp;
+        g.dst[p] = p == 0 ? 0 : wi.luma() + (p - 1) * wi.chroma();
+        g.pitch[p] = p ? fr.cw : fr.w;
+        g.src[p] = (p == 0 ? 0 : fr.luma() + (p - 1) * fr.chroma()) + (long long)(p ? y0 / ay : y0) * g.pitch[p] + (p ? x0 / ax : x0);
+        SSM_REQUIRE(pieces + rows * pp <= 2147483647ll, "%s: a window of %lld bytes is more than the grid takes", name, wi.frame() * sample_bytes);
+        g.start[p] = (unsigned)pieces;
+        pieces += rows * pp;
+    }
+    g.total = (unsigned)pieces;
+    const long long fb = fr.frame() * sample_bytes, wb = wi.frame() * sample_bytes;
+    if (sample_bytes == 2) {
+        const auto odd = [](const void *p) { return reinterpret_cast<size_t>(p) % 2 != 0; };
+        SSM_REQUIRE(!odd(frames) && !odd(windows), "%s: a payload of 2-byte samples (frames or windows) is not 2-byte aligned", name);
+        SSM_REQUIRE(N == 1 || (stride_in % 2 == 0 && stride_out % 2 == 0), "%s: strides %lld (frames), %lld (windows) of 2-byte samples must be even",
+                    name, stride_in, stride_out);
+    }
+    if (N == 1) stride_in = stride_out = 0;          // the stride of a single payload names nothing
+    SSM_REQUIRE(N == 1 || std::llabs(stride_in) >= fb, "%s: stride %lld (frames) shorter than the frame's %lld bytes", name, stride_in, fb);
+    SSM_REQUIRE(N == 1 || std::llabs(stride_out) >= wb, "%s: stride %lld (windows) shorter than the window's %lld bytes", name, stride_out, wb);
+    long long i0, i1, o0, o1;
+    rows_range(frames, stride_in, N, fb, &i0, &i1);
+    rows_range(windows, stride_out, N, wb, &o0, &o1);
+    SSM_REQUIRE(apart(i0, i1, o0, o1), "%s: windows overlaps frames", name);
+    const unsigned groups = (g.total + LANES * CHUNKS - 1) / (LANES * CHUNKS);
+    with_sample(sample_bytes, [&](auto s) {
+        SSM_LAUNCH(window_cut_kernel<decltype(s)>, dim3(groups, N), dim3(LANES), 0, (hipStream_t)stream, static_cast<const unsigned char *>(frames),
+                   stride_in, static_cast<unsigned char *>(windows), stride_out, g);
+    });
+    return ssm::check_launch("ssm_window_cut_fwd");
 }

@@ -72,6 +72,22 @@ not measured on compressed footage: a convention; 0:0:0 takes exact repeats only
 has no right neighbour: both stay as they are.  Every run goes to --log with its length, whether it was repaired, and its worst block
 sum and count.  It goes with --slowmo, --matrix, --range, --flow_scale, --tile and --detelecine (which runs first), not with --fps,
 --speed, --shutter, --scene_cut or --deinterlace: chain two runs,  ... --dedup --upsample_rate 1 --output - | interpolate_video.py ... .
+
+--active auto[:LIM[:FRAC]] | W:H:X:Y [--active_probe P]: the input is letterboxed or pillarboxed (a 2.39:1 picture in a 1920x1080 frame),
+and the run is that of the picture alone: the rectangle is cut out of every frame on the GPU, the network runs on the canvas of the
+cropped clip (804 rows pad to 832, not to 1088), and each synthesised picture is pasted into the bars of the nearer input frame - the
+left one before the middle of the interval, the right one from there on.  The bars of every output frame are then some input frame's own
+bytes: their edge no longer pulses between clean input frames and synthesised ones, and a subtitle or a logo in a bar steps with its
+own frames instead of being warped.  Input frames pass through whole, as ever.  W:H:X:Y is the order `ffmpeg -vf cropdetect` prints, so
+its crop=... can be pasted; it has to sit on the chroma grid (even X, W, and in 4:2:0 even Y, H, or the frame's edge).  auto finds the
+smallest such rectangle that holds every active row and column of the first P frames (default 48): a luma sample counts when it is above
+LIM (default 24 at 8 bits, scaled to the depth), a row or column is active when more than FRAC (default 1/64) of its samples count
+(counted on the GPU, ssm_luma_counts_fwd).  24 is the number of cropdetect's limit, not its construction, and 1/64 is this tool's own:
+conventions, not measured on compressed footage, whose bars are noisy.  If the rectangle is the whole frame, nothing is active, or it is
+under 32 samples in a direction, the run is the one without the option, byte for byte, and --log says so.  A later frame with active
+lines outside the rectangle goes to --log and changes nothing: a rectangle that changes inside a clip, coloured bars and re-planning are
+out of scope.  It goes with --upsample_rate, --slowmo, --fps, --speed, --scene_cut, --matrix (whose default stays that of the FRAME's
+height), --range, --flow_scale, --tile and --detelecine (which runs first), not with --shutter, --deinterlace or --dedup: chain two runs.
 """
 import argparse
 import configparser
@@ -151,7 +167,19 @@ def getargs(argv=None):
                              "the blocks above LO; default 768:320:0.33 at 8 bits (a convention), 0:0:0 exact repeats only. Default: off.")
     parser.add_argument("--dedup_max", type=_named(V.parse_dedup_max_text), default=V.DEDUP_MAX, metavar="D",
                         help="With --dedup: the longest run of repeats that is repaired; longer runs are stills and stay. Default 2.")
+    parser.add_argument("--active", type=_named(V.parse_active), default=None, metavar="auto[:LIM[:FRAC]]|W:H:X:Y",
+                        help="The input is letterboxed: run on the picture alone and keep the bars of the nearer input frame. auto finds the "
+                             "rectangle from the first --active_probe frames (luma above LIM, default 24 at 8 bits, in more than FRAC, default "
+                             "1/64, of a line: conventions); W:H:X:Y gives it, in the order ffmpeg's cropdetect prints. Default: off.")
+    parser.add_argument("--active_probe", type=_named(V.parse_active_probe), default=V.ACTIVE_PROBE, metavar="P",
+                        help="With --active auto: the frames the rectangle is decided on. Default 48.")
     args = parser.parse_args(argv)
+    if args.active is not None:
+        for flag, given in (("--shutter", args.shutter is not None), ("--deinterlace", args.deinterlace is not None),
+                            ("--dedup", args.dedup is not None)):
+            if given:
+                parser.error("--active does not go together with %s: the picture is cut out and the bars are pasted back around frames "
+                             "synthesised between two input frames, and nothing else; chain two runs" % flag)
     if args.dedup is not None:
         for flag, given in (("--fps", args.fps is not None), ("--speed", args.speed is not None), ("--shutter", args.shutter is not None),
                             ("--scene_cut", args.scene_cut is not None), ("--deinterlace", args.deinterlace is not None)):
@@ -202,7 +230,8 @@ def main(argv=None, model=None):
     vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate, matrix=matrix, color_range=crange,
                              flow_scale=args.flow_scale, tile=args.tile, halo=args.halo, blend=args.blend, target_rate=args.fps, speed=args.speed,
                              shutter=args.shutter, shutter_samples=args.shutter_samples, scene_cut=args.scene_cut,
-                             shutter_light=args.shutter_light, deinterlace=args.deinterlace, dedup=args.dedup, dedup_max=args.dedup_max)
+                             shutter_light=args.shutter_light, deinterlace=args.deinterlace, dedup=args.dedup, dedup_max=args.dedup_max,
+                             active=args.active, active_probe=args.active_probe)
     with V.Y4MReader(args.input, extended=True, interlaced=args.deinterlace is not None or args.detelecine) as reader:
         if args.detelecine:
             log.info("[%s] detelecine: %d:%d frames/s in, film at %d:%d", args.expt, *reader.rate, *V.detelecine_rate(reader.rate))
@@ -243,6 +272,11 @@ def main(argv=None, model=None):
                  worst_over)
     if args.dedup is not None:
         log.info("[%s] dedup: %d runs, %d repaired", args.expt, len(vi.repeats), sum(1 for r in vi.repeats if r[2]))
+    if args.active is not None:
+        log.info("[%s] active: %s%s", args.expt, vi.active_note, "" if vi.active is not None else "; the run is whole-frame, as without --active")
+        for i, rows, cols in vi.active_excess:
+            log.info("[%s] active: input frame %d has %d active rows and %d active columns outside the rectangle; nothing changes", args.expt, i,
+                     rows, cols)
     for i, score in vi.cuts:
         log.info("[%s] scene cut between input frames %d and %d: score %s = %.6f (threshold %s)", args.expt, i, i + 1, score, float(score),
                  vi.scene_cut)

@@ -234,6 +234,8 @@ SIGNATURES = {
     "ssm_fields_split_fwd": (_c_int, [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp]),
     "ssm_fields_weave_fwd": (_c_int, [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int,
                                       _c_int, _c_int, _c_int, _vp]),
+    "ssm_luma_counts_fwd": (_c_int, [_vp, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp]),
+    "ssm_window_cut_fwd": (_c_int, [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong] + [_c_int] * 9 + [_vp]),
 }
 
 _lib = None

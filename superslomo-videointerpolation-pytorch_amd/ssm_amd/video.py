@@ -42,6 +42,11 @@
   dedup_host /            decision and the runs in Python ints and Fractions; the reader that takes the repaired repeats out in front of the
   RepeatSource /          loop and the timeline over the frames that stay, which puts synthesised frames where the repeats stood -
   GapTimeline             VideoInterpolator(dedup=, dedup_max=): the fixed grid's frame count and rate, every other mode unchanged
+  active_counts_host /    letterboxed clips: per frame the luma samples above a limit of every row and column, by numpy and by
+  luma_counts / ActiveArea ssm_luma_counts_fwd; the rectangle that holds every active line of the probed frames, in Python ints and Fractions;
+  / cut_window_host /     a rectangle of a payload as a payload of its own and back (ssm_window_cut_fwd, window_cut, is held to the cut byte
+  paste_window_host /     for byte); the reader that probes, decides and watches in front of the loop - VideoInterpolator(active=,
+  ActiveSource            active_probe=): the run is the cropped clip's, the bars of a synthesised frame are the nearer input frame's bytes
   (ssm_amd/video_score.py) hold-out scoring: the clip against its own held-out frames, plane_sse / HoldOutScorer on this loop's ring, Clip and
                           buffers; the PSNR of what VideoInterpolator(upsample_rate=hold) would write - this module is unchanged by it
 
@@ -62,7 +67,9 @@ chroma siting of a 4:2:0 field (a quarter line off the layout's rule, which is w
 2:2, 2:3:3:2 and mixed cadences, soft telecine, the orphan field at an edit inside a cycle, comb metrics, noisy or compressed sources;
 of repeated frames: timestamps (timecode files), dropping repeats instead of repairing them, dedup together with target_rate, speed,
 shutter, scene_cut or deinterlace (chain two runs), a scene cut on the frame after a run, comparison against a run's first frame,
-agreement with ffmpeg's mpdecimate frame for frame, noisy or compressed footage.
+agreement with ffmpeg's mpdecimate frame for frame, noisy or compressed footage; of letterboxed clips: a rectangle that changes inside a
+clip, coloured bars, re-planning when a later frame exceeds the rectangle, active together with shutter, deinterlace or dedup (chain two
+runs), noisy or compressed bars.
 """
 import ctypes
 import functools
@@ -500,16 +507,27 @@ def luma_sad_host(ya, yb):
 class Clip:
     """A clip's format and what its two conversions need, worked out once per run: fb = frame_bytes, the canvas (hp, wp) = padded_dims(h, w,
     mult) unless `canvas` gives one, the centred offsets, mean, std and the bit depth's table as the C arrays the entry points take; dev: the
-    run's device.  ingest() and egress() queue the kernel on the current stream and assert nothing of their tensors: the caller's to keep."""
+    run's device.  ingest() and egress() queue the kernel on the current stream and assert nothing of their tensors: the caller's to keep.
+    window = (w', h', x, y), a checked rectangle of the h x w frame (letterboxed clips): h, w, the canvas and both conversions are then the
+    window's, `frame` keeps the frame's (h, w); fb_in = fb is the frame's size, what comes up from the host, fb_out the window's, what goes
+    back.  ingest() then queues ssm_window_cut_fwd into `scratch` ([N, fb_out], the caller's, per stream) and the conversion on that.
+    Without a window fb_in = fb_out = fb and nothing changes."""
 
-    def __init__(self, h, w, siting, matrix, crange, cfg=None, bits=8, mult=32, canvas=None, dev=None):
-        self.h, self.w, self.fb, self.dev = h, w, frame_bytes(h, w, siting, bits), dev
+    def __init__(self, h, w, siting, matrix, crange, cfg=None, bits=8, mult=32, canvas=None, dev=None, window=None):
+        self.frame, self.window, self.siting, self.bits = (h, w), window, siting, bits
+        self.fb = self.fb_in = self.fb_out = frame_bytes(h, w, siting, bits)
+        if window is not None:
+            w, h = check_active(window, h, w, siting)[:2]
+            self.fb_out = frame_bytes(h, w, siting, bits)
+        self.h, self.w, self.dev = h, w, dev
         self.hp, self.wp = padded_dims(h, w, mult)[0] if canvas is None else canvas
         self.at = ((self.hp - h) // 2, (self.wp - w) // 2)          # top, left
         self.norm = tuple(_f3(v) for v in cfg_mean_std(cfg))          # mean, std
         self.coding = (_table_ptr(bits, matrix), table_index(matrix), crange, siting, sample_bytes(bits))          # the tail of both argument lists
 
-    def ingest(self, payload, out, pad_before_norm=True):
+    def ingest(self, payload, out, pad_before_norm=True, scratch=None):
+        if self.window is not None:
+            payload = window_cut(payload, *self.frame, self.siting, self.bits, self.window, out=scratch)
         hb.check(hb.load().ssm_frames_from_yuvx_fwd(payload.data_ptr(), hb.view_of(out), payload.shape[0], self.h, self.w, self.hp, self.wp,
                                                     *self.at, *self.norm, 1 if pad_before_norm else 0, *self.coding, hb.stream_ptr()))
         return out
@@ -1338,6 +1356,364 @@ class RepeatSource:
         self.close()
 
 
+# ---- letterboxed clips: the active area ------------------------------------------------------------------------------------------------
+# The definition is in include/ssm_hip.h and DESIGN 3.12: per frame the luma samples above `limit` of every row and column; a line is
+# active iff more than FRAC of its samples are; the rectangle is the smallest one that holds every active line of the probed frames,
+# aligned outward to the layout's chroma grid.  LIM is the NUMBER of ffmpeg cropdetect's `limit` (24 at 8 bits), not its construction -
+# cropdetect averages a line - and FRAC = 1/64 is this module's own: conventions, not backed by a measurement on compressed footage.
+ACTIVE_LIMIT, ACTIVE_FRAC = 24, Fraction(1, 64)
+ACTIVE_PROBE = 48                  # frames the rectangle is decided on
+ACTIVE_MIN = 32                    # a rectangle below this many samples in either direction is no picture: the run goes whole-frame
+
+
+def active_align(siting):
+    """(ay, ax): the rows and columns a rectangle is aligned to in a layout - the luma samples one chroma sample covers."""
+    return {CENTRED: (2, 2), COSITED: (2, 2), C422: (1, 2), C444: (1, 1)}[siting]
+
+
+def active_limit(bits=8, limit=None):
+    """The luma code a sample has to exceed to count: `limit` as given, or ACTIVE_LIMIT scaled to the depth."""
+    return ACTIVE_LIMIT << (bits - 8) if limit is None else int(limit)
+
+
+def parse_active(value):
+    """The active-area option: None -> None; "auto", "auto:LIM" or "auto:LIM:FRAC" (LIM an integer >= 0 in codes of the clip's depth,
+    FRAC a decimal or a fraction in [0, 1)) -> ("auto", LIM or None for the default at the clip's depth, Fraction FRAC); "W:H:X:Y" - the
+    order ffmpeg's cropdetect prints, `crop=` in front is fine - or a (w, h, x, y) of whole numbers -> that tuple.  Anything else is a
+    ValueError naming the value."""
+    if value is None:
+        return None
+    bad = ValueError("the active area is written auto, auto:LIM, auto:LIM:FRAC or W:H:X:Y (the order of ffmpeg's cropdetect), e.g. auto:24:1/64 "
+                     "or 1920:800:0:140 (got %r)" % (value,))
+    try:
+        if isinstance(value, str):
+            parts = value.strip().split(":")
+            if parts[0] == "auto":
+                if len(parts) > 3:
+                    raise bad
+                limit = int(parts[1]) if len(parts) > 1 and parts[1] != "" else None
+                frac = Fraction(parts[2]) if len(parts) > 2 else ACTIVE_FRAC
+                if (limit is not None and not 0 <= limit <= 65535) or not 0 <= frac < 1:
+                    raise bad
+                return "auto", limit, frac
+            if parts[0].startswith("crop="):
+                parts[0] = parts[0][5:]
+            value = [int(p) for p in parts]
+        elif isinstance(value, tuple) and len(value) == 3 and value[0] == "auto":
+            return parse_active("auto:%s:%s" % ("" if value[1] is None else value[1], value[2]))
+        if len(value) != 4 or any(isinstance(v, bool) or int(v) != v for v in value):
+            raise bad
+        w, h, x, y = (int(v) for v in value)
+    except (ValueError, TypeError, ZeroDivisionError):
+        raise bad from None
+    if w < 1 or h < 1 or x < 0 or y < 0:
+        raise bad
+    return w, h, x, y
+
+
+def parse_active_probe(value):
+    """The number of frames the active area is decided on: a whole number of at least 1, or its text."""
+    try:
+        n = int(value.strip()) if isinstance(value, str) else value
+        if isinstance(n, bool) or int(n) != n or n < 1:
+            raise ValueError
+    except (ValueError, TypeError):
+        raise ValueError("active_probe, the frames the active area is decided on, is a whole number of at least 1 (got %r)" % (value,)) from None
+    return int(n)
+
+
+def check_active(rect, h, w, siting):
+    """(w', h', x, y) inside an h x w frame of a layout, or the refusal that names the alignment: the origin a multiple of
+    active_align(siting), the far edges a multiple of it or the frame's own edge."""
+    rw, rh, x, y = rect
+    ay, ax = active_align(siting)
+    if rw < 1 or rh < 1 or x < 0 or y < 0 or x + rw > w or y + rh > h:
+        raise ValueError("the active area %d:%d:%d:%d (W:H:X:Y) lies outside the %dx%d frame (it is aligned to %d columns and %d rows)"
+                         % (rw, rh, x, y, w, h, ax, ay))
+    if x % ax or y % ay or ((x + rw) % ax and x + rw != w) or ((y + rh) % ay and y + rh != h):
+        raise ValueError("the active area %d:%d:%d:%d (W:H:X:Y) is not aligned to %d columns and %d rows, as this chroma layout asks: X and Y "
+                         "are multiples of them, X + W and Y + H multiples or the frame's own edge" % (rw, rh, x, y, ax, ay))
+    return rw, rh, x, y
+
+
+def active_counts_host(payload, h, w, bits=8, limit=None):
+    """Yardstick of ssm_luma_counts_fwd: payloads [N, at least h * w samples] uint8 (numpy) -> (rows [N, h], cols [N, w]) uint32, the
+    number of luma samples of each row and column whose value is above `limit` (None: the default at this depth); a single payload [bytes]
+    gives (rows [h], cols [w]).  With bits > 8 over the 16-bit words, all 16 bits.  Chroma is not looked at."""
+    payload = np.asarray(payload)
+    one = payload.ndim == 1
+    above = _luma_of(payload.reshape(1, -1) if one else payload, h, w, bits) > active_limit(bits, limit)
+    rows, cols = above.sum(axis=2).astype(np.uint32), above.sum(axis=1).astype(np.uint32)
+    return (rows[0], cols[0]) if one else (rows, cols)
+
+
+class ActiveArea:
+    """The decision, in Python ints and Fractions and free of the GPU.  feed(rows, cols) takes one frame's counts (active_counts_host /
+    luma_counts) and widens the bounds by the frame's active lines: row r is active iff rows[r] > frac * w, column c iff cols[c] > frac * h,
+    exactly.  decide() -> (w', h', x, y): the smallest rectangle that holds every active line fed so far, aligned outward to
+    active_align(siting) (origin a multiple, far edges a multiple or the frame's edge) - or None, the whole-frame fallback, with `note`
+    saying why: the result is the whole frame, no frame had an active row or column, or it is under ACTIVE_MIN samples in a direction.
+    outside(rows, cols, rect) -> (active rows outside the rectangle, active columns outside it) of one frame."""
+
+    def __init__(self, h, w, siting, frac=ACTIVE_FRAC):
+        self.h, self.w, self.siting, self.frac = int(h), int(w), siting, Fraction(frac)
+        self.bounds, self.fed, self.note = None, 0, None          # [y0, y1, x0, x1), y1 and x1 one past the last active line
+
+    def lines(self, rows, cols):
+        """(active rows, active columns) of one frame as bool arrays: count * den > num * length, in Python ints."""
+        num, den = self.frac.numerator, self.frac.denominator
+        rows, cols = (np.asarray(v).reshape(-1).astype(object) for v in (rows, cols))
+        assert rows.size == self.h and cols.size == self.w, "one frame's counts: rows [h] and cols [w]"
+        return (rows * den > num * self.w).astype(bool), (cols * den > num * self.h).astype(bool)
+
+    def feed(self, rows, cols):
+        self.fed += 1
+        ar, ac = (np.flatnonzero(v) for v in self.lines(rows, cols))
+        if ar.size == 0 or ac.size == 0:          # a row above the limit puts a sample in some column; a frame with neither has no picture
+            return
+        b = [int(ar[0]), int(ar[-1]) + 1, int(ac[0]), int(ac[-1]) + 1]
+        self.bounds = b if self.bounds is None else [min(self.bounds[0], b[0]), max(self.bounds[1], b[1]), min(self.bounds[2], b[2]),
+                                                     max(self.bounds[3], b[3])]
+
+    def decide(self):
+        if self.bounds is None:
+            self.note = "no active row or column in the %d probed frame%s" % (self.fed, "" if self.fed == 1 else "s")
+            return None
+        ay, ax = active_align(self.siting)
+        y0, y1, x0, x1 = self.bounds
+        y0, x0 = y0 - y0 % ay, x0 - x0 % ax
+        y1, x1 = min(self.h, -(-y1 // ay) * ay), min(self.w, -(-x1 // ax) * ax)
+        rect = (x1 - x0, y1 - y0, x0, y0)
+        if rect == (self.w, self.h, 0, 0):
+            self.note = "the active area is the whole frame"
+            return None
+        if rect[0] < ACTIVE_MIN or rect[1] < ACTIVE_MIN:
+            self.note = "the active area %d:%d:%d:%d is under %d samples in a direction" % (rect + (ACTIVE_MIN,))
+            return None
+        self.note = "the active area is %d:%d:%d:%d (W:H:X:Y) of the %dx%d frame, from %d frame%s" % (rect + (self.w, self.h, self.fed,
+                                                                                                  "" if self.fed == 1 else "s"))
+        return rect
+
+    def outside(self, rows, cols, rect):
+        rw, rh, x, y = rect
+        ar, ac = self.lines(rows, cols)
+        return int(ar[:y].sum() + ar[y + rh:].sum()), int(ac[:x].sum() + ac[x + rw:].sum())
+
+
+def active_area_host(frames, h, w, siting=CENTRED, bits=8, limit=None, frac=ACTIVE_FRAC, probe=ACTIVE_PROBE):
+    """The whole decision in numpy, the yardstick of ActiveSource: payloads [n, frame_bytes] -> ((w', h', x, y) or None, the ActiveArea
+    that decided) over the first `probe` frames, or the whole clip if it is shorter."""
+    frames = np.ascontiguousarray(frames).reshape(-1, frame_bytes(h, w, siting, bits))
+    area = ActiveArea(h, w, siting, frac)
+    for rows, cols in zip(*active_counts_host(frames[:probe], h, w, bits, limit)):
+        area.feed(rows, cols)
+    return area.decide(), area
+
+
+def _window_slices(h, w, siting, rect):
+    """Per plane (Y, U, V) the (row slice, column slice) of a checked rectangle: chroma from y / ay to ceil((y + h') / ay), likewise in x."""
+    rw, rh, x, y = check_active(rect, h, w, siting)
+    ay, ax = active_align(siting)
+    cay, cax = (1, 1) if siting == C444 else ((1, 2) if siting == C422 else (2, 2))          # the chroma subsampling itself
+    luma = (slice(y, y + rh), slice(x, x + rw))
+    chroma = (slice(y // cay, -(-(y + rh) // cay)), slice(x // cax, -(-(x + rw) // cax)))
+    assert (cay, cax) == (ay, ax)
+    return luma, chroma, chroma
+
+
+def cut_window_host(payload, h, w, siting, bits, rect):
+    """Yardstick of ssm_window_cut_fwd: payloads [N, frame_bytes(h, w)] uint8 (numpy; a single payload [bytes] gives [bytes]) -> the packed
+    payloads of the rectangle (w', h', x, y), [N, frame_bytes(h', w')]: a genuine h' x w' frame of the same layout."""
+    payload = np.asarray(payload)
+    one = payload.ndim == 1
+    src = np.ascontiguousarray(payload).reshape(-1, frame_bytes(h, w, siting, bits))
+    out = np.empty((src.shape[0], frame_bytes(rect[1], rect[0], siting, bits)), np.uint8)
+    for s, d, (ys, xs) in zip(split_planes(src, h, w, siting, bits), split_planes(out, rect[1], rect[0], siting, bits),
+                              _window_slices(h, w, siting, rect)):
+        d[...] = s[:, ys, xs]
+    return out[0] if one else out
+
+
+def paste_window_host(window, bars_from, h, w, siting, bits, rect, out=None):
+    """The inverse of cut_window_host: a full payload (into `out` if given, which may be bars_from itself) with `window`'s samples inside the
+    rectangle and bars_from's bytes outside it, in all three planes.  One payload each, [bytes], or [N, bytes]."""
+    window, bars_from = np.asarray(window), np.asarray(bars_from)
+    fb = frame_bytes(h, w, siting, bits)
+    win = np.ascontiguousarray(window).reshape(-1, frame_bytes(rect[1], rect[0], siting, bits))
+    if out is None:
+        out = np.empty(bars_from.shape, np.uint8)
+    full = out.reshape(-1, fb)          # a view: out is contiguous
+    if out is not bars_from:
+        full[...] = bars_from.reshape(-1, fb)
+    for s, d, (ys, xs) in zip(split_planes(win, rect[1], rect[0], siting, bits), split_planes(full, h, w, siting, bits),
+                              _window_slices(h, w, siting, rect)):
+        d[:, ys, xs] = s
+    return out
+
+
+def luma_counts(payload, h, w, bits=8, limit=None, rows=None, cols=None):
+    """ssm_luma_counts_fwd on payloads: [N, at least h * w samples] uint8 device tensor (unit stride within a row, any row stride) -> (rows
+    int32 [N, h], cols int32 [N, w]) on the device (into `rows`, `cols` if given, contiguous): per frame the luma samples of every row and
+    column above `limit` (None: the default at this depth).  Whatever the two held before, the call leaves them fully defined."""
+    sb = sample_bytes(bits)
+    assert payload.is_cuda and payload.dtype == torch.uint8 and payload.dim() == 2 and payload.shape[1] >= h * w * sb and \
+        (payload.shape[1] == 1 or payload.stride(1) == 1), "payloads must be a [N, at least h * w samples] uint8 tensor on the GPU with unit stride within a frame"
+    n = payload.shape[0]
+    rows = torch.empty(n, h, dtype=torch.int32, device=payload.device) if rows is None else rows
+    cols = torch.empty(n, w, dtype=torch.int32, device=payload.device) if cols is None else cols
+    for t, m in ((rows, h), (cols, w)):
+        assert t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == (n, m) and t.is_contiguous()
+    hb.check(hb.load().ssm_luma_counts_fwd(payload.data_ptr(), payload.stride(0) if n > 1 else 0, n, h, w, sb, active_limit(bits, limit),
+                                           rows.data_ptr(), cols.data_ptr(), hb.stream_ptr()))
+    return rows, cols
+
+
+def window_cut(frames, h, w, siting, bits, rect, out=None):
+    """ssm_window_cut_fwd: [N, at least frame_bytes(h, w)] uint8 device tensor (unit stride within a payload, any row stride) -> the packed
+    windows [N, at least frame_bytes(h', w')] of the rectangle (w', h', x, y) (into `out` if given), as cut_window_host."""
+    rw, rh, x, y = rect
+    n = frames.shape[0]
+    si = _field_operand(frames, n, frame_bytes(h, w, siting, bits), "frames")
+    wb = frame_bytes(rh, rw, siting, bits) if rw > 0 and rh > 0 else 0
+    if out is None:
+        out = torch.empty(n, wb, dtype=torch.uint8, device=frames.device)
+    so = _field_operand(out, n, wb, "out")
+    hb.check(hb.load().ssm_window_cut_fwd(frames.data_ptr(), si, out.data_ptr(), so, n, h, w, y, x, rh, rw, siting, sample_bytes(bits),
+                                          hb.stream_ptr()))
+    return out
+
+
+class ActiveSource:
+    """A reader that finds and watches the active area of a letterboxed clip: wraps a Y4MReader (or anything with its attributes, a
+    TelecineSource for one) and hands out its frames as they are.  `active`: what parse_active returns - ("auto", limit, frac) or an
+    explicit (w, h, x, y), checked against the frame.  decide() -> `area`, the rectangle or None for a whole-frame run, and `note`, one
+    line that says which and why; with "auto" it reads the first `probe` frames (or the whole clip if it is shorter) into a host buffer,
+    counts them on the GPU, decides (ActiveArea) and replays them.  With an area, every later frame is counted a chunk ahead of the loop,
+    and a frame with active rows or columns outside the rectangle goes to `excess` as (frame index, rows outside, columns outside); it
+    changes nothing else.  Without one (the fallback) the frames behind the probe come straight from the reader.
+
+    A chunk is frames_per_chunk frames in one pinned buffer and one device buffer, made once.  Per chunk, on a stream of its own: one H2D,
+    one ssm_luma_counts_fwd, one D2H of the counts, one event wait; never a wait per frame.  The bytes handed out do not depend on
+    frames_per_chunk or probe."""
+
+    def __init__(self, reader, dev, active=("auto", None, ACTIVE_FRAC), probe=ACTIVE_PROBE, frames_per_chunk=8):
+        assert frames_per_chunk >= 1
+        self.reader, self.dev = reader, torch.device(dev)
+        if self.dev.type != "cuda":
+            raise RuntimeError("the active area takes its luma counts on the GPU (the HIP path has no CPU fallback)")
+        for name in ("width", "height", "siting", "chroma", "color_range", "aspect", "xtags", "frame_bytes", "rate"):
+            setattr(self, name, getattr(reader, name))
+        self.bits, self.extended = getattr(reader, "bits", 8), getattr(reader, "extended", False)
+        self.sample_bytes = sample_bytes(self.bits)
+        self.interlace, self.field_order, self.field_bytes = getattr(reader, "interlace", "p"), None, None
+        active = parse_active(active)
+        assert active is not None
+        self.auto = active[0] == "auto"
+        self.limit = active_limit(self.bits, active[1] if self.auto else None)
+        self._area = ActiveArea(self.height, self.width, self.siting, active[2] if self.auto else ACTIVE_FRAC)
+        self._given = None if self.auto else check_active(active, self.height, self.width, self.siting)
+        self.probe, self.area, self.note, self.excess, self.frames_read = parse_active_probe(probe), None, None, [], 0
+        self._rows, self._decided = frames_per_chunk, False
+        self._replay, self._pending, self._eof, self._counted = [], [], False, 0          # probed frames; counted frames not yet handed out
+        self._host = self._np = None
+
+    def _buffers(self):
+        if self._host is None:
+            c, h, w = self._rows, self.height, self.width
+            self._host = torch.empty(c, self.frame_bytes, dtype=torch.uint8).pin_memory()
+            self._np = self._host.numpy()
+            self._dev = torch.empty(c, self.frame_bytes, dtype=torch.uint8, device=self.dev)
+            self._dev_counts = (torch.empty(c, h, dtype=torch.int32, device=self.dev), torch.empty(c, w, dtype=torch.int32, device=self.dev))
+            self._host_counts = tuple(torch.empty(t.shape, dtype=torch.int32).pin_memory() for t in self._dev_counts)
+            self._np_counts = tuple(t.numpy().view(np.uint32) for t in self._host_counts)
+            self._stream, self._event = torch.cuda.Stream(self.dev), torch.cuda.Event()
+
+    def _count(self, k):
+        """The counts of the first k rows of the pinned buffer: (rows [k, h], cols [k, w]) uint32, views of pinned memory."""
+        with torch.cuda.stream(self._stream):
+            self._dev[:k].copy_(self._host[:k], non_blocking=True)
+            luma_counts(self._dev[:k], self.height, self.width, self.bits, self.limit, self._dev_counts[0][:k], self._dev_counts[1][:k])
+            for hc, dc in zip(self._host_counts, self._dev_counts):
+                hc[:k].copy_(dc[:k], non_blocking=True)
+            self._event.record()
+        self._event.synchronize()
+        return self._np_counts[0][:k], self._np_counts[1][:k]
+
+    def _watch(self, rows, cols):
+        for r, c in zip(rows, cols):
+            out = self._area.outside(r, c, self.area)
+            if out != (0, 0):
+                self.excess.append((self._counted,) + out)
+            self._counted += 1
+
+    def decide(self):
+        """The rectangle of the run, (w, h, x, y), or None: a whole-frame run; `note` says why.  Reads the probe frames on the first call."""
+        if self._decided:
+            return self.area
+        self._decided = True
+        if not self.auto:
+            whole = self._given == (self.width, self.height, 0, 0)
+            self.area = None if whole else self._given
+            self.note = "the active area is the whole frame" if whole else "the active area is %d:%d:%d:%d (W:H:X:Y), as given" % self._given
+            return self.area
+        self._buffers()
+        probe = np.empty((self.probe, self.frame_bytes), np.uint8)
+        n = 0
+        while n < self.probe and self.reader.read_frame_into(probe[n]):
+            n += 1
+        self._eof = n < self.probe
+        for at in range(0, n, self._rows):
+            k = min(self._rows, n - at)
+            self._np[:k] = probe[at:at + k]
+            for r, c in zip(*self._count(k)):
+                self._area.feed(r, c)
+        self.area, self.note = self._area.decide(), self._area.note
+        self._replay = [probe[i] for i in range(n)]
+        self._counted = n          # inside the rectangle by construction
+        return self.area
+
+    def _chunk(self):
+        """The next chunk behind the probe: its frames into the pinned buffer, their counts, the frames that leave the rectangle."""
+        self._buffers()
+        k = 0
+        while k < self._rows and self.reader.read_frame_into(self._np[k]):
+            k += 1
+        self._eof = k < self._rows
+        if k:
+            self._watch(*self._count(k))
+            self._pending = list(range(k))
+
+    def read_frame_into(self, buf):
+        """The next frame's payload into `buf`; False at the end of the clip."""
+        self.decide()
+        out = np.frombuffer(memoryview(buf).cast("B"), np.uint8)
+        if out.size != self.frame_bytes:
+            raise ValueError("buffer of %d bytes for frames of %d" % (out.size, self.frame_bytes))
+        if self._replay:
+            out[:] = self._replay.pop(0)
+        elif self.area is None:
+            if self._eof or not self.reader.read_frame_into(out):
+                self._eof = True
+                return False
+        else:
+            while not self._pending:
+                if self._eof:
+                    return False
+                self._chunk()
+            out[:] = self._np[self._pending.pop(0)]
+        self.frames_read += 1
+        return True
+
+    def close(self):
+        self.reader.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 # ---- output order -------------------------------------------------------------------------------------------------------------------
 def pass_order(valid, nt):
     """Write order of one pass of `valid` pairs with nt interpolated frames each: ("interp", row of the pass's output buffer) for the
@@ -1923,18 +2299,26 @@ def upload_times(times, slots, np_t, host_t, dev_t):
     dev_t.copy_(host_t, non_blocking=True)
 
 
-def ring_slots(depth, fb, rows_in, rows_out, n_t=None):
-    """What a mode's `depth` ring slots hold, a list each: pinned host_in [rows_in, fb], host_out [rows_out, fb] and host_t (n_t times, 0.5
+def ring_slots(depth, fb, rows_in, rows_out, n_t=None, fb_out=None):
+    """What a mode's `depth` ring slots hold, a list each: pinned host_in [rows_in, fb], host_out [rows_out, fb_out] (None: fb, one frame
+    size for both) and host_t (n_t times, 0.5
     throughout so that entries no pass fills stay finite; None where the mode has no times), their numpy views, the `done` events."""
-    host_in, host_out = ([torch.empty(rows, fb, dtype=torch.uint8).pin_memory() for _ in range(depth)] for rows in (rows_in, rows_out))
+    host_in, host_out = ([torch.empty(rows, size, dtype=torch.uint8).pin_memory() for _ in range(depth)]
+                         for rows, size in ((rows_in, fb), (rows_out, fb if fb_out is None else fb_out)))
     host_t = None if n_t is None else [torch.full((n_t,), 0.5, dtype=torch.float32).pin_memory() for _ in range(depth)]
     np_in, np_out, np_t = (None if b is None else [t.numpy() for t in b] for b in (host_in, host_out, host_t))
     return host_in, host_out, host_t, np_in, np_out, np_t, [torch.cuda.Event() for _ in range(depth)]
 
 
-def stream_buffers(n, dev, fb, rows_in, rows_out, n_t=None):
-    """What a mode's n streams hold on the device, a list each: dev_in, dev_out, dev_t (as in ring_slots; not initialised), `ingested`."""
-    dev_in, dev_out = ([torch.empty(rows, fb, dtype=torch.uint8, device=dev) for _ in range(n)] for rows in (rows_in, rows_out))
+def stream_buffers(n, dev, fb, rows_in, rows_out, n_t=None, fb_out=None):
+    """What a mode's n streams hold on the device, a list each: dev_in, dev_out, dev_t (as in ring_slots; not initialised), `ingested`.
+    With fb_out, the window's size of a letterboxed clip, a fifth list: dev_win [rows_in, fb_out], the scratch the cut windows of dev_in's
+    rows go to, row for row."""
+    dev_in, dev_out = ([torch.empty(rows, size, dtype=torch.uint8, device=dev) for _ in range(n)]
+                       for rows, size in ((rows_in, fb), (rows_out, fb if fb_out is None else fb_out)))
+    if fb_out is not None:
+        dev_t = None if n_t is None else [torch.empty(n_t, dtype=torch.float32, device=dev) for _ in range(n)]
+        return dev_in, dev_out, dev_t, [torch.cuda.Event() for _ in range(n)], [torch.empty(rows_in, fb_out, dtype=torch.uint8, device=dev) for _ in range(n)]
     dev_t = None if n_t is None else [torch.empty(n_t, dtype=torch.float32, device=dev) for _ in range(n)]
     return dev_in, dev_out, dev_t, [torch.cuda.Event() for _ in range(n)]
 
@@ -1956,7 +2340,7 @@ class VideoInterpolator:
 
     def __init__(self, model, cfg, upsample_rate=None, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
                  tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8, scene_cut=None,
-                 shutter_light="coded", deinterlace=None, dedup=None, dedup_max=DEDUP_MAX):
+                 shutter_light="coded", deinterlace=None, dedup=None, dedup_max=DEDUP_MAX, active=None, active_probe=ACTIVE_PROBE):
         """target_rate = (num, den) and / or speed (a Fraction, or what Fraction() takes; 1/4 is four times slower): the output follows
         Timeline(speed * input rate / target_rate) instead of the fixed grid of upsample_rate, which is then not used (see
         _run_timeline); with both None nothing changes.  flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
@@ -1998,7 +2382,22 @@ class VideoInterpolator:
         mode's loop).  upsample_rate = 1 is then legal and means repair only.  `repeats` lists the runs after run(): (first repeat, m,
         repaired, worst max, worst over).  The defaults are the numbers of ffmpeg's mpdecimate, a convention, not its construction and
         not backed by a measurement on compressed footage.  It does not go together with target_rate, speed, shutter, scene_cut or
-        deinterlace (chain two runs).  None: every mode as it is, launch for launch."""
+        deinterlace (chain two runs).  None: every mode as it is, launch for launch.
+        active ("auto", "auto:LIM[:FRAC]", "W:H:X:Y" or (w, h, x, y); parse_active) with active_probe = P: the clip is letterboxed, and
+        the run is that of its picture alone.  The rectangle is the one given, or with "auto" the smallest aligned one that holds every
+        active row and column of the first P frames (ActiveArea, from the counts of ssm_luma_counts_fwd; an ActiveSource in front of the
+        loop).  Every pass cuts the rectangle out of its uploaded frames on the device (ssm_window_cut_fwd) and runs canvas, plan and
+        launches of the cropped clip; only window bytes come back, and the writer thread pastes each synthesised window into the bytes
+        of the nearer input frame (t < 1/2: the left one), so the bars - and a subtitle in them - step with their own frames, the rule of
+        the scene cuts.  Input frames stay their own bytes, whole.  The default matrix is that of the FRAME's height.  After run():
+        `active` is the rectangle used, (w, h, x, y), or None where the run went whole-frame (the rectangle is the frame, no probed frame
+        has an active line, or it is under 32 samples in a direction - then byte for byte the run without the option), `active_note` one
+        line that says which and why, `active_excess` [(frame index, active rows outside, active columns outside)] of later frames that
+        leave the rectangle; they are reported and change nothing.  LIM = 24 at 8 bits is the number of ffmpeg cropdetect's limit, not
+        its construction, FRAC = 1/64 this module's own: conventions, not backed by a measurement on compressed footage.  It goes with
+        upsample_rate, target_rate, speed, scene_cut, matrix, color_range, flow_scale and tile; not with shutter (every output comes from
+        the accumulator, none has one input frame's bars), deinterlace, dedup or a recurrent model (chain two runs).  None: every mode
+        as it is, launch for launch."""
         from .coarse import check_scale
         from .tiles import check_args
         self.flow_scale = check_scale(flow_scale)
@@ -2022,6 +2421,14 @@ class VideoInterpolator:
                 if given:
                     raise ValueError("dedup together with %s is not available: it repairs repeated frames on the fixed grid of upsample_rate "
                                      "and nothing else; chain two runs (dedup with upsample_rate=1 first, then the other)" % name)
+        self.active_option, self.active_probe = parse_active(active), parse_active_probe(active_probe)
+        self.active, self.active_note, self.active_excess = None, None, []
+        if self.active_option is not None:
+            for name, given in (("shutter", shutter is not None), ("deinterlace", deinterlace is not None),
+                                ("dedup", dedup is not None and dedup is not False), ("a recurrent model", getattr(model, "recurrent", False))):
+                if given:
+                    raise ValueError("active together with %s is not available: the picture is cut out and the bars are pasted back around "
+                                     "frames synthesised between two input frames, and nothing else; chain two runs" % name)
         self.deinterlace = parse_deinterlace(deinterlace)
         if self.deinterlace is not None:
             for name, given in (("upsample_rate", upsample_rate is not None), ("target_rate", target_rate is not None), ("speed", speed is not None),
@@ -2086,8 +2493,9 @@ class VideoInterpolator:
                                             blend=self.blend))
         return self._pipe[1]
 
-    def _clip(self, reader, writer):
-        """The Clip of a run, or the refusal of a writer of another format or of a model that is not on the GPU."""
+    def _clip(self, reader, writer, window=None):
+        """The Clip of a run, or the refusal of a writer of another format or of a model that is not on the GPU.  window: the active area of
+        a letterboxed clip; the default matrix stays the one of the frame's height."""
         h, w, siting, bits = reader.height, reader.width, reader.siting, getattr(reader, "bits", 8)
         if (writer.height, writer.width, writer.siting, getattr(writer, "bits", 8)) != (h, w, siting, bits):
             raise ValueError("reader and writer disagree on the frame format")
@@ -2099,7 +2507,7 @@ class VideoInterpolator:
         dev = next(self.model.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
-        return Clip(h, w, siting, matrix, crange, self.cfg, bits, 32 * self.flow_scale, dev=dev)
+        return Clip(h, w, siting, matrix, crange, self.cfg, bits, 32 * self.flow_scale, dev=dev, window=window)
 
     def _cut_state(self, on, n, depth, pairs, clip):
         """What the scene cuts add to a mode's buffers: SceneCuts, the sums of a pass on the device (per stream) and in the pinned ring slot
@@ -2111,22 +2519,44 @@ class VideoInterpolator:
         return (SceneCuts(self.scene_cut), [torch.empty(pairs, dtype=torch.int64, device=clip.dev) for _ in range(n)], host,
                 [t.numpy().view(np.uint64) for t in host], np.empty(clip.fb, np.uint8)), 1
 
-    def _cut_rows(self, cuts, pixels, sums, pairs, order, carried):
+    @staticmethod
+    def _paster(clip):
+        """paste(window's bytes, an input frame's bytes) -> a full frame for the writer thread, or None for a clip without a window.  The
+        frame it returns is one buffer, written before the next is asked for (PassRing writes row by row)."""
+        if clip.window is None:
+            return None
+        out = np.empty(clip.fb_in, np.uint8)
+        return lambda window, near: paste_window_host(window, near, *clip.frame, clip.siting, clip.bits, clip.window, out=out)
+
+    def _cut_rows(self, cuts, pixels, sums, pairs, order, carried, paste=None):
         """The rows of a pass under scene cuts: a generator that PassRing calls on the writer thread once the pass's event has come.
         sums: the pass's luma sums in its ring slot; pairs: [(i, left frame's host bytes or None for `carried`, right frame's)] in the
         order in which they ran; order: [(input frame's bytes, None) | (synthesised frame's bytes, (pair's place in `pairs`, exact t))] in
         write order.  Feeds SceneCuts, notes the cuts, and puts the nearer input frame in the place of a cut pair's synthesised frames;
-        at the end `carried` takes the last pair's right frame, the left frame of a next pass's first pair (its slot is free by then)."""
+        at the end `carried` takes the last pair's right frame, the left frame of a next pass's first pair (its slot is free by then).
+        paste: of a letterboxed clip (_paste_rows), for the synthesised frames of the pairs that are no cut."""
         verdict = []
         for p, (i, _, _) in enumerate(pairs):
             cut, score = cuts.feed(int(sums[p]), pixels)
             verdict.append(cut)
             if cut:
                 self.cuts.append((i, score))
+        return self._near_rows(verdict, paste, pairs, order, carried)
+
+    def _paste_rows(self, paste, pairs, order, carried):
+        """The rows of a pass of a letterboxed clip without scene cuts, beside _cut_rows and with its `pairs`, `order` and `carried`: every
+        synthesised window goes out as paste(window, the nearer input frame's bytes) - the left frame's at t < 1/2, else the right one's."""
+        return self._near_rows([False] * len(pairs), paste, pairs, order, carried)
+
+    @staticmethod
+    def _near_rows(verdict, paste, pairs, order, carried):
+        """What _cut_rows and _paste_rows yield: an input frame as it is; a synthesised frame of a cut pair replaced by the nearer input
+        frame, whole; any other synthesised frame as it is or, with `paste` (a letterboxed clip), pasted into the nearer input frame's bars."""
         for buf, at in order:
-            if at is not None and verdict[at[0]]:
+            if at is not None and (verdict[at[0]] or paste is not None):
                 _, lf, rt = pairs[at[0]]
-                buf = (carried if lf is None else lf) if at[1] < Fraction(1, 2) else rt
+                near = (carried if lf is None else lf) if at[1] < Fraction(1, 2) else rt
+                buf = near if verdict[at[0]] else paste(buf, near)
             yield buf
         if pairs:
             carried[:] = pairs[-1][2]
@@ -2135,8 +2565,14 @@ class VideoInterpolator:
     def run(self, reader, writer):
         """Returns the number of frames written: (n - 1) * upsample_rate + 1 for n input frames (with target_rate / speed:
         floor((n - 1) / step) + 1; with a shutter: Timeline.n_outputs(n); with deinterlace: 2 n; with dedup the fixed grid's count)."""
-        clip = self._clip(reader, writer)
-        self.cuts, self.repeats = [], []
+        self.cuts, self.repeats, self.active, self.active_note, self.active_excess = [], [], None, None, []
+        if self.active_option is not None:
+            dev = next(self.model.parameters()).device
+            if dev.type != "cuda":
+                raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
+            reader = ActiveSource(reader, dev, self.active_option, self.active_probe)
+            self.active, self.active_note, self.active_excess = reader.decide(), reader.note, reader.excess
+        clip = self._clip(reader, writer, self.active)
         if self.dedup is not None:
             tl = self.gap_timeline()
             source = RepeatSource(reader, clip.dev, self.dedup, self.dedup_max)
@@ -2182,14 +2618,20 @@ class VideoInterpolator:
         n, pb, nt = pipe.n, self.pb, self.rate - 1
         depth = n + 2                                                  # ring slots: one per pass in flight, one being read, one being written
         t_dev = torch.tensor(t_values(self.rate), dtype=torch.float32, device=dev)
-        host_in, host_out, _, np_in, np_out, _, done = ring_slots(depth, fb, pb, pb * nt)
+        host_in, host_out, _, np_in, np_out, _, done = ring_slots(depth, fb, pb, pb * nt, fb_out=clip.fb_out)
         (cuts, dev_sums, host_sums, np_sums, carried), lead = self._cut_state(self.scene_cut is not None, n, depth, pb, clip)
-        dev_in, dev_out, _, ingested = stream_buffers(n, dev, fb, lead + pb, pb * nt)
+        paste = self._paster(clip)
+        if paste is None:
+            dev_in, dev_out, _, ingested = stream_buffers(n, dev, fb, lead + pb, pb * nt)
+            dev_up = dev_in
+        else:          # a letterboxed clip: frames come up into dev_up, their windows are cut into dev_in, and everything below reads those
+            dev_up, dev_out, _, ingested, dev_in = stream_buffers(n, dev, fb, lead + pb, pb * nt, fb_out=clip.fb_out)
+            carried = np.empty(fb, np.uint8) if carried is None else carried
         planes = [torch.empty(pb + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [carried left frame | new frames]
         first = torch.empty(1, fb, dtype=torch.uint8).pin_memory()
         if not reader.read_frame_into(first.numpy()[0]):
             raise Y4MError("the Y4M stream holds no frame")
-        if cuts is not None:
+        if carried is not None:
             carried[:] = first.numpy()[0]
         torch.cuda.synchronize(dev)
         written = 1
@@ -2199,8 +2641,8 @@ class VideoInterpolator:
             last = (n - 1) % n
             with torch.cuda.stream(pipe.streams[last]):
                 new = dev_in[last][lead:]
-                new[:1].copy_(first, non_blocking=True)
-                clip.ingest(new[:1], planes[last][pb:])
+                dev_up[last][lead:lead + 1].copy_(first, non_blocking=True)
+                clip.ingest(dev_up[last][lead:lead + 1], planes[last][pb:], scratch=new[:1])
                 if cuts is not None:
                     dev_in[0][0, :luma].copy_(new[0, :luma])
                 ingested[last].record()
@@ -2220,10 +2662,10 @@ class VideoInterpolator:
                 st = pipe.streams[k]
                 with torch.cuda.stream(st):
                     new = dev_in[k][lead:]
-                    new.copy_(host_in[r], non_blocking=True)
+                    dev_up[k][lead:].copy_(host_in[r], non_blocking=True)
                     st.wait_event(ingested[kprev])
                     planes[k][0].copy_(planes[kprev][pb])
-                    clip.ingest(new, planes[k][1:])
+                    clip.ingest(dev_up[k][lead:], planes[k][1:], scratch=new)
                     if cuts is not None:
                         luma_sad(dev_in[k][:pb], dev_in[k][1:], clip.h, clip.w, out=dev_sums[k])
                         dev_in[(j + 1) % n][0, :luma].copy_(dev_in[k][pb, :luma])
@@ -2237,12 +2679,14 @@ class VideoInterpolator:
                         host_sums[r].copy_(dev_sums[k], non_blocking=True)
                     done[r].record()
                 rows = [np_out[r][row] if kind == "interp" else np_in[r][row] for kind, row in pass_order(valid, nt)]
-                if cuts is not None:
+                if cuts is not None or paste is not None:
                     i0 = (written - 1) // self.rate
                     at = [None if kind == "orig" else (row // nt, Fraction(row % nt + 1, self.rate)) for kind, row in pass_order(valid, nt)]
-                    rows = functools.partial(self._cut_rows, cuts, luma, np_sums[r],
-                                             [(i0 + p, np_in[r][p - 1] if p else None, np_in[r][p]) for p in range(valid)],
-                                             list(zip(rows, at)), carried)
+                    host_pairs = [(i0 + p, np_in[r][p - 1] if p else None, np_in[r][p]) for p in range(valid)]
+                    if cuts is not None:
+                        rows = functools.partial(self._cut_rows, cuts, luma, np_sums[r], host_pairs, list(zip(rows, at)), carried, paste)
+                    else:
+                        rows = functools.partial(self._paste_rows, paste, host_pairs, list(zip(rows, at)), carried)
                 ring.hand(r, done[r], rows)
                 written += valid * self.rate
                 j += 1
@@ -2388,11 +2832,17 @@ class VideoInterpolator:
         S, pb, n = tl.slots, self.pb, self.n_streams
         pipe = self._pipeline(hp, wp, dev, S) if S else None          # an integer step only picks input frames: nothing to run
         depth, cap = n + 2, 2 * pb + 2
-        host_in, host_out, host_t, np_in, np_out, np_t, done = ring_slots(depth, fb, cap, pb * max(S, 1), pb * max(S, 1))
+        host_in, host_out, host_t, np_in, np_out, np_t, done = ring_slots(depth, fb, cap, pb * max(S, 1), pb * max(S, 1), fb_out=clip.fb_out)
         (cuts, dev_sums, host_sums, np_sums, carried), lead = self._cut_state(self.scene_cut is not None and pipe is not None, n, depth, pb, clip)
+        paste = self._paster(clip)
         plan = PassPlanner(tl, pb, cap)
-        if pipe is not None:
+        if pipe is not None and paste is not None:          # a letterboxed clip, as on the fixed grid: frames up into dev_up, their windows in dev_in
+            dev_up, dev_out, dev_t, ingested, dev_in = stream_buffers(n, dev, fb, lead + cap, pb * S, pb * S, fb_out=clip.fb_out)
+            carried = np.empty(fb, np.uint8) if carried is None else carried
+        elif pipe is not None:
             dev_in, dev_out, dev_t, ingested = stream_buffers(n, dev, fb, lead + cap, pb * S, pb * S)
+            dev_up = dev_in
+        if pipe is not None:
             planes = [torch.zeros(pb, 2, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [pair][left | right]
         torch.cuda.synchronize(dev)
         last_p = [0]          # place, in its pass, of the pair whose right frame the next pair may carry over
@@ -2404,13 +2854,13 @@ class VideoInterpolator:
             with torch.cuda.stream(st):
                 if j:
                     st.wait_event(ingested[(j - 1) % n])          # the carried frame; and pass j - n + 1 is done with planes[k]
-                new = dev_in[k][lead:]
+                new, up = dev_in[k][lead:], dev_up[k][lead:]
                 for p, (row, own_left, ts) in enumerate(pairs):
                     rows = 2 if own_left else 1
-                    new[row:row + rows].copy_(host_in[r][row:row + rows], non_blocking=True)
+                    up[row:row + rows].copy_(host_in[r][row:row + rows], non_blocking=True)
                     if not own_left:
                         planes[k][p, 0].copy_(planes[k][p - 1, 1] if p else planes[(j - 1) % n][last_p[0], 1])
-                    clip.ingest(new[row:row + rows], planes[k][p, 2 - rows:])
+                    clip.ingest(up[row:row + rows], planes[k][p, 2 - rows:], scratch=new[row:row + rows])
                 upload_times([ts for _, _, ts in pairs], S, np_t[r], host_t[r], dev_t[k])
                 if cuts is not None:
                     rights = [lead + row + (1 if own_left else 0) for row, own_left, _ in pairs]          # rows of dev_in[k]
@@ -2436,13 +2886,16 @@ class VideoInterpolator:
 
         def rows_of(r, on_gpu, order, pairs):
             rows = [np_out[r][row] if kind == "interp" else np_in[r][row] for kind, row in order]
-            if cuts is not None and on_gpu:
+            if (cuts is not None or paste is not None) and on_gpu:
                 exact = [tl.times(i) for i in plan.closed_index]          # the pairs' times as Fractions, beside the planner's fp32
                 at = [None if kind == "orig" else (row // S, exact[row // S][row % S]) for kind, row in order]
                 rights = [np_in[r][row + (1 if own_left else 0)] for row, own_left, _ in pairs]
                 host_pairs = [(i, np_in[r][row] if own_left else (rights[p - 1] if p else None), rights[p])
                               for p, (i, (row, own_left, _)) in enumerate(zip(plan.closed_index, pairs))]
-                rows = functools.partial(self._cut_rows, cuts, luma, np_sums[r], host_pairs, list(zip(rows, at)), carried)
+                if cuts is not None:
+                    rows = functools.partial(self._cut_rows, cuts, luma, np_sums[r], host_pairs, list(zip(rows, at)), carried, paste)
+                else:
+                    rows = functools.partial(self._paste_rows, paste, host_pairs, list(zip(rows, at)), carried)
             return rows, len(order)
 
         return self._run_passes(clip, reader, writer, plan, np_in, done, lambda order, pairs: bool(pairs), submit, rows_of)
