@@ -771,6 +771,36 @@ int ssm_frames_accumulate_light_fwd(ssm_view src, ssm_view acc, int N, int H, in
 int ssm_frames_accumulate_hdr_fwd(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale, const float *mean3,
                                   const float *std3, int kind, const float *consts, int encode, void *stream);
 
+/* ---- shutter windows: weighted sub-frame sums (csrc/ssm_video.hip; beyond the reference's operator surface) ----------------------------
+ * The three entry points above weigh every sub-frame alike (a box: scale = fp32(1 / S) on an output's last call).  A window gives sample
+ * j of an output, at u_j = (j + 1/2) / S of the open interval, a weight w_j that falls off towards the ends of the exposure
+ * (ssm_amd.video.shutter_window(name, S): triangle, hann, gauss[:K]; symmetric in j, so the blur's centre of mass stays where the box has
+ * it) and closes the output with scale = fp32(1 / sum_j w_j), the sum of the fp32 weights taken in float64.
+ * ssm_frames_accumulate_weighted_fwd, ssm_frames_accumulate_light_weighted_fwd, ssm_frames_accumulate_hdr_weighted_fwd: the sibling's
+ * arguments, views, modes, dec and encode, and `weights`, a HOST pointer to N floats, weights[n] the weight of src[n] - for a call over the
+ * samples j0 .. j0 + N - 1 of an output the slice w[j0 .. j0 + N - 1] of its window.  Per element, with p_n = weights[n] * dec(src[n])
+ * (dec the identity in the coded form), every multiply and every add one rounded fp32 operation (no fused multiply-add), in this order:
+ *   1. s = init ? p_0 : acc + p_0
+ *   2. s = s + p_n   for n = 1 .. N-1, in increasing n
+ *   3. r = s * scale
+ *   4. acc = enc(r)   (coded: r; light and HDR: encode ? (encode(r) - mean[p]) / std[p] : r, as their siblings)
+ * The coded form is bit for bit ssm_amd.video.accumulate_host(..., weights=) (tests/test_hip_shutter_window.py); with weights of 1 it is
+ * bit for bit ssm_frames_accumulate_fwd (1 * x is x).  A sum issued in consecutive pieces - init on the first, scale and encode on the
+ * last - is the same additions in the same order, so the same bits.  The light and HDR forms are held to bounds against the float64
+ * yardsticks accumulate_light_host / accumulate_hdr_host(..., weights=), derived for weights in [0, 1] with scale * sum(weights) <= 1
+ * in tests/test_video_window_cpu.py; their two exact properties stay: a coded value <= 0 adds w * 0 = 0, and black stays bit-identical black.
+ * The weights travel by value in the kernel's arguments (SSM_ACC_WEIGHTS_MAX floats: no device buffer, no copy on the stream) and are read
+ * as scalar operands; a longer sum is issued in pieces.  Access widths, launch geometry and the packed-fp32 fence as for the siblings.
+ * SSM_E_ARG (nothing is launched) for everything the sibling refuses, and for a null `weights`, N > SSM_ACC_WEIGHTS_MAX, and a weight
+ * that is not finite. */
+#define SSM_ACC_WEIGHTS_MAX 64
+int ssm_frames_accumulate_weighted_fwd(ssm_view src, ssm_view acc, int N, int C, int H, int W, int init, float scale,
+                                       const float *weights, void *stream);
+int ssm_frames_accumulate_light_weighted_fwd(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale, const float *weights,
+                                             const float *mean3, const float *std3, const float *curve, int encode, void *stream);
+int ssm_frames_accumulate_hdr_weighted_fwd(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale, const float *weights,
+                                           const float *mean3, const float *std3, int kind, const float *consts, int encode, void *stream);
+
 /* ---- scene cuts of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) -------------------------------
  * Definition (ssm_amd.video.SceneCuts(threshold), everything in exact integers and fractions).  For the pair of input frames (i, i + 1)
  * of H x W pixels, with Y the 8-bit luma planes as they stand in the payloads:

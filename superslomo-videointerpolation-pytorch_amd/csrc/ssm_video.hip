@@ -19,6 +19,9 @@
 //                            normalised again by the call that closes an output; the power is v_log_f32, a multiply and v_exp_f32
 //   frames_accumulate_hdr_kernel  the same skeleton (accumulate_lane) with the transfer functions of HDR clips in place of a light curve: the
 //                            BT.2100 PQ EOTF and the inverse HLG OETF and their inverses, by v_log_f32, v_exp_f32, v_rcp_f32, v_sqrt_f32
+//   frames_accumulate_weighted_kernel / frames_accumulate_hdr_weighted_kernel  the shutter windows: the two kernels above with a weight per
+//                            frame, multiplied into the decoded sample before it is added (accumulate_lane<.., Weighted = true>); at most
+//                            SSM_ACC_WEIGHTS_MAX weights, by value in the kernel's arguments, read as scalar operands
 //   span_sum_kernel          the sums over pairs of payloads, one kernel under two entry points: per pair and plane the exact sum of a
 //                            lane accumulator's term over the samples as they stand in the payloads.  A workgroup sums SPAN_BYTES = 16 KiB of
 //                            ONE plane, a lane CHUNKS = 4 pieces of 16 bytes per operand (one 16-byte load each; sample by sample where a
@@ -434,8 +437,17 @@ template <int V> struct alignas(4 * V) Px { float f[V]; };
 // The arithmetic on a Px<4> stays four scalar v_add_f32 / v_mul_f32 per step only because the Makefile builds every file with
 // -fno-slp-vectorize (check_isa.sh fails the build on any v_pk_*_f32): a plain hipcc -O3 of this file packs it into v_pk_add_f32 /
 // v_pk_mul_f32.
-template <int V, typename Cv>          // pixels per lane: 4 or 1; the mode's arguments
-__device__ __forceinline__ void accumulate_lane(const ssm_view &src, const ssm_view &acc, int N, int H, int W, int init, float scale, const Cv &cv) {
+// Weighted (the shutter windows of ssm_amd.video.shutter_window): p_n = w[n] * dec(src[n]) stands where dec(src[n]) stood, one more
+// rounded multiply per sample and nothing else - s = init ? p_0 : acc + p_0;  s = s + p_n;  r = s * scale;  acc = enc(r).  The weights come
+// by value in the kernel's arguments (Weights<true>, SSM_ACC_WEIGHTS_MAX floats: no device buffer, no copy on the pass's stream); n is
+// wave-uniform, so w[n] is a scalar load from the argument segment and the multiply takes it as a scalar operand.  Weights<false> is empty
+// and the unweighted instantiations are the code they were before the template parameter.
+template <bool Weighted> struct Weights {};
+template <> struct Weights<true> { float w[SSM_ACC_WEIGHTS_MAX]; };
+
+template <int V, typename Cv, bool Weighted>          // pixels per lane: 4 or 1; the mode's arguments; a weight per sample
+__device__ __forceinline__ void accumulate_lane(const ssm_view &src, const ssm_view &acc, int N, int H, int W, int init, float scale, const Cv &cv,
+                                                const Weights<Weighted> &wt) {
     constexpr bool Light = !std::is_same_v<Cv, Curve<false>>;
     const int x = (blockIdx.x * 64 + threadIdx.x) * V, y = blockIdx.y * 4 + threadIdx.y, c = blockIdx.z;
     if (x >= W || y >= H) return;          // V = 4: W % 4 == 0, so x + 3 < W
@@ -448,11 +460,15 @@ __device__ __forceinline__ void accumulate_lane(const ssm_view &src, const ssm_v
         if constexpr (Light) return light_decode(v, sd, mean, black, cv.row);
         else return v;
     };
+    const auto term = [&](float v, int n) {          // sample n's summand
+        if constexpr (Weighted) return wt.w[n] * dec(v);
+        else return dec(v);
+    };
     const float *s = src.ptr + (long long)c * src.sc + (long long)y * src.sh + x;
     float *a = acc.ptr + (long long)c * acc.sc + (long long)y * acc.sh + x;
     Px<V> v = *reinterpret_cast<const Px<V> *>(s);
 #pragma unroll
-    for (int i = 0; i < V; ++i) v.f[i] = dec(v.f[i]);
+    for (int i = 0; i < V; ++i) v.f[i] = term(v.f[i], 0);
     if (!init) {
         const Px<V> o = *reinterpret_cast<const Px<V> *>(a);
 #pragma unroll
@@ -462,7 +478,7 @@ __device__ __forceinline__ void accumulate_lane(const ssm_view &src, const ssm_v
     for (int n = 1; n < N; ++n) {
         const Px<V> f = *reinterpret_cast<const Px<V> *>(s + (long long)n * src.sb);
 #pragma unroll
-        for (int i = 0; i < V; ++i) v.f[i] = v.f[i] + dec(f.f[i]);
+        for (int i = 0; i < V; ++i) v.f[i] = v.f[i] + term(f.f[i], n);
     }
 #pragma unroll
     for (int i = 0; i < V; ++i) v.f[i] = v.f[i] * scale;
@@ -473,17 +489,30 @@ __device__ __forceinline__ void accumulate_lane(const ssm_view &src, const ssm_v
     *reinterpret_cast<Px<V> *>(a) = v;
 }
 
-// One skeleton, two kernels: the coded sum and the power-law curves, and the HDR transfer functions (Kind: SSM_HDR_PQ or SSM_HDR_HLG).
+// One skeleton, two kernels and their weighted forms: the coded sum and the power-law curves, and the HDR transfer functions (Kind: SSM_HDR_PQ or SSM_HDR_HLG).
 template <int V, bool Light>
 __global__ __launch_bounds__(256) void frames_accumulate_kernel(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale,
                                                                 Curve<Light> cv) {
-    accumulate_lane<V>(src, acc, N, H, W, init, scale, cv);
+    accumulate_lane<V>(src, acc, N, H, W, init, scale, cv, Weights<false>{});
 }
 
 template <int V, int Kind>
 __global__ __launch_bounds__(256) void frames_accumulate_hdr_kernel(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale,
                                                                     HdrCurve<Kind> cv) {
-    accumulate_lane<V>(src, acc, N, H, W, init, scale, cv);
+    accumulate_lane<V>(src, acc, N, H, W, init, scale, cv, Weights<false>{});
+}
+
+// The weighted forms of the two: the same arguments and the N <= SSM_ACC_WEIGHTS_MAX weights after them.
+template <int V, bool Light>
+__global__ __launch_bounds__(256) void frames_accumulate_weighted_kernel(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale,
+                                                                         Curve<Light> cv, Weights<true> wt) {
+    accumulate_lane<V>(src, acc, N, H, W, init, scale, cv, wt);
+}
+
+template <int V, int Kind>
+__global__ __launch_bounds__(256) void frames_accumulate_hdr_weighted_kernel(ssm_view src, ssm_view acc, int N, int H, int W, int init,
+                                                                             float scale, HdrCurve<Kind> cv, Weights<true> wt) {
+    accumulate_lane<V>(src, acc, N, H, W, init, scale, cv, wt);
 }
 
 // ---- sums over pairs of payloads: what the kernels share -------------------------------------------------------------------------------
@@ -1435,15 +1464,31 @@ static int check_curve(const char *name, const HlgRow &k) {
     return SSM_OK;
 }
 
-// The checks and the launch of the three accumulate entry points, in one order; `light` null: the coded sum over C channels.
+// What a weighted entry point is given beside its unweighted sibling's arguments: N host floats.
+struct WeightsIn {
+    const float *w;
+};
+
+// The checks and the launch of the six accumulate entry points, in one order; `light` null: the coded sum over C channels; `weighted` null:
+// no weights, the kernels and the launches as they were before there were any.
 static int frames_accumulate(const char *name, const char *entry, ssm_view src, ssm_view acc, int N, int C, int H, int W, int init, float scale,
-                             const LightIn *light, void *stream) {
-    SSM_REQUIRE(src.ptr && acc.ptr && (!light || (light->mean3 && light->std3 && light->curve)), "%s: null pointer", name);
+                             const LightIn *light, const WeightsIn *weighted, void *stream) {
+    SSM_REQUIRE(src.ptr && acc.ptr && (!light || (light->mean3 && light->std3 && light->curve)) && (!weighted || weighted->w),
+                "%s: null pointer", name);
     const bool sizes = N > 0 && N <= 65535 && C > 0 && C <= 65535 && H > 0 && W > 0 && (H + 3) / 4 <= 65535;
     if (light)
         SSM_REQUIRE(sizes, "%s: bad sizes N=%d H=%d W=%d", name, N, H, W);
     else
         SSM_REQUIRE(sizes, "%s: bad sizes N=%d C=%d H=%d W=%d", name, N, C, H, W);
+    Weights<true> wt = {};
+    if (weighted) {
+        SSM_REQUIRE(N <= SSM_ACC_WEIGHTS_MAX, "%s: N=%d frames in one weighted call: at most SSM_ACC_WEIGHTS_MAX = %d (issue the sum in pieces)",
+                    name, N, SSM_ACC_WEIGHTS_MAX);
+        for (int n = 0; n < N; ++n) {
+            SSM_REQUIRE(std::isfinite(weighted->w[n]), "%s: weight %d must be finite (got %g)", name, n, (double)weighted->w[n]);
+            wt.w[n] = weighted->w[n];
+        }
+    }
     SSM_REQUIRE(src.sh >= W && acc.sh >= W, "%s: row strides %d (src), %d (acc) shorter than W=%d", name, src.sh, acc.sh, W);
     SSM_REQUIRE(init == 0 || init == 1, "%s: init must be 0 or 1 (got %d)", name, init);
     if (light) SSM_REQUIRE(light->encode == 0 || light->encode == 1, "%s: encode must be 0 or 1 (got %d)", name, light->encode);
@@ -1472,35 +1517,71 @@ static int frames_accumulate(const char *name, const char *entry, ssm_view src, 
     SSM_REQUIRE(s1 <= a0 || a1 <= s0, "%s: src and acc overlap (%lld bytes apart)", name, a0 - s0);
     const bool vec = W % 4 == 0 && view_aligned(src, 4) && view_aligned(acc, 4);
     const dim3 grid(((vec ? W / 4 : W) + 63) / 64, (H + 3) / 4, C);
-    const auto go = [&](auto k4, auto k1, auto mode) {          // the kernel at four pixels and at one pixel per lane, its mode's arguments
-        SSM_LAUNCH(vec ? k4 : k1, grid, dim3(64, 4), 0, (hipStream_t)stream, src, acc, N, H, W, init, scale, mode);
+    // the kernel at four pixels and at one pixel per lane, unweighted (k4, k1) and weighted (w4, w1), and its mode's arguments
+    const auto go = [&](auto k4, auto k1, auto w4, auto w1, auto mode) {
+        if (weighted)
+            SSM_LAUNCH(vec ? w4 : w1, grid, dim3(64, 4), 0, (hipStream_t)stream, src, acc, N, H, W, init, scale, mode, wt);
+        else
+            SSM_LAUNCH(vec ? k4 : k1, grid, dim3(64, 4), 0, (hipStream_t)stream, src, acc, N, H, W, init, scale, mode);
     };
     if (!light)
-        go(frames_accumulate_kernel<4, false>, frames_accumulate_kernel<1, false>, Curve<false>{});
+        go(frames_accumulate_kernel<4, false>, frames_accumulate_kernel<1, false>, frames_accumulate_weighted_kernel<4, false>,
+           frames_accumulate_weighted_kernel<1, false>, Curve<false>{});
     else if (kind == CURVE_ROW)
-        go(frames_accumulate_kernel<4, true>, frames_accumulate_kernel<1, true>, cv);
+        go(frames_accumulate_kernel<4, true>, frames_accumulate_kernel<1, true>, frames_accumulate_weighted_kernel<4, true>,
+           frames_accumulate_weighted_kernel<1, true>, cv);
     else if (kind == SSM_HDR_PQ)
-        go(frames_accumulate_hdr_kernel<4, SSM_HDR_PQ>, frames_accumulate_hdr_kernel<1, SSM_HDR_PQ>, pq);
+        go(frames_accumulate_hdr_kernel<4, SSM_HDR_PQ>, frames_accumulate_hdr_kernel<1, SSM_HDR_PQ>,
+           frames_accumulate_hdr_weighted_kernel<4, SSM_HDR_PQ>, frames_accumulate_hdr_weighted_kernel<1, SSM_HDR_PQ>, pq);
     else
-        go(frames_accumulate_hdr_kernel<4, SSM_HDR_HLG>, frames_accumulate_hdr_kernel<1, SSM_HDR_HLG>, hlg);
+        go(frames_accumulate_hdr_kernel<4, SSM_HDR_HLG>, frames_accumulate_hdr_kernel<1, SSM_HDR_HLG>,
+           frames_accumulate_hdr_weighted_kernel<4, SSM_HDR_HLG>, frames_accumulate_hdr_weighted_kernel<1, SSM_HDR_HLG>, hlg);
     return ssm::check_launch(entry);
 }
 
 extern "C" int ssm_frames_accumulate_fwd(ssm_view src, ssm_view acc, int N, int C, int H, int W, int init, float scale, void *stream) {
-    return frames_accumulate("frames_accumulate", "ssm_frames_accumulate_fwd", src, acc, N, C, H, W, init, scale, nullptr, stream);
+    return frames_accumulate("frames_accumulate", "ssm_frames_accumulate_fwd", src, acc, N, C, H, W, init, scale, nullptr, nullptr, stream);
 }
 
 extern "C" int ssm_frames_accumulate_light_fwd(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale, const float *mean3,
                                                const float *std3, const float *curve, int encode, void *stream) {
     const LightIn light = {mean3, std3, curve, encode, CURVE_ROW};
-    return frames_accumulate("frames_accumulate_light", "ssm_frames_accumulate_light_fwd", src, acc, N, 3, H, W, init, scale, &light, stream);
+    return frames_accumulate("frames_accumulate_light", "ssm_frames_accumulate_light_fwd", src, acc, N, 3, H, W, init, scale, &light, nullptr,
+                             stream);
 }
 
 extern "C" int ssm_frames_accumulate_hdr_fwd(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale, const float *mean3,
                                              const float *std3, int kind, const float *consts, int encode, void *stream) {
     const LightIn light = {mean3, std3, consts, encode, kind};
     SSM_REQUIRE(kind != CURVE_ROW, "frames_accumulate_hdr: kind %d not in {0 (pq), 1 (hlg)}", kind);
-    return frames_accumulate("frames_accumulate_hdr", "ssm_frames_accumulate_hdr_fwd", src, acc, N, 3, H, W, init, scale, &light, stream);
+    return frames_accumulate("frames_accumulate_hdr", "ssm_frames_accumulate_hdr_fwd", src, acc, N, 3, H, W, init, scale, &light, nullptr, stream);
+}
+
+// The weighted siblings: the same arguments with `weights` (host memory, N floats) after `scale`, through the same checks and launch.
+extern "C" int ssm_frames_accumulate_weighted_fwd(ssm_view src, ssm_view acc, int N, int C, int H, int W, int init, float scale,
+                                                  const float *weights, void *stream) {
+    const WeightsIn wt = {weights};
+    return frames_accumulate("frames_accumulate_weighted", "ssm_frames_accumulate_weighted_fwd", src, acc, N, C, H, W, init, scale, nullptr, &wt,
+                             stream);
+}
+
+extern "C" int ssm_frames_accumulate_light_weighted_fwd(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale,
+                                                        const float *weights, const float *mean3, const float *std3, const float *curve,
+                                                        int encode, void *stream) {
+    const LightIn light = {mean3, std3, curve, encode, CURVE_ROW};
+    const WeightsIn wt = {weights};
+    return frames_accumulate("frames_accumulate_light_weighted", "ssm_frames_accumulate_light_weighted_fwd", src, acc, N, 3, H, W, init, scale,
+                             &light, &wt, stream);
+}
+
+extern "C" int ssm_frames_accumulate_hdr_weighted_fwd(ssm_view src, ssm_view acc, int N, int H, int W, int init, float scale,
+                                                      const float *weights, const float *mean3, const float *std3, int kind,
+                                                      const float *consts, int encode, void *stream) {
+    const LightIn light = {mean3, std3, consts, encode, kind};
+    const WeightsIn wt = {weights};
+    SSM_REQUIRE(kind != CURVE_ROW, "frames_accumulate_hdr_weighted: kind %d not in {0 (pq), 1 (hlg)}", kind);
+    return frames_accumulate("frames_accumulate_hdr_weighted", "ssm_frames_accumulate_hdr_weighted_fwd", src, acc, N, 3, H, W, init, scale,
+                             &light, &wt, stream);
 }
 
 

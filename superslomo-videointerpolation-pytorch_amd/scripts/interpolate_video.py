@@ -36,6 +36,10 @@ light.  The curve acts on R'G'B' after the matrix and is independent of --matrix
 functions of HDR clips (BT.2100; what phones and cameras record as 10-bit HLG, and graded HDR masters as PQ, usually with --matrix
 bt2020): pq is the PQ EOTF, display light up to 10000 cd/m2, hlg the inverse of the HLG OETF, scene light; no OOTF is applied to either.
 The coded mean darkens a PQ highlight's streak by more than a factor of 20 in cd/m2, where it costs 128 against 188 codes under sRGB.
+--shutter_window box|triangle|hann|gauss[:K] gives the S sub-frames their weights: box (the default) weighs them alike, so a fast object
+is S evenly bright copies with hard ends; the others fall off towards the ends of the exposure (ssm_amd.video.shutter_window, sample j at
+(j + 1/2) / S of the open interval), and the streak fades in and out at the same S and the same cost.  gauss spans +-K standard
+deviations, K = 2 unless given (a convention).  It goes with every --shutter_light; --log names the window, its weights and its scale.
 
 --scene_cut T (a decimal or a fraction in (0, 1]; no default value - the option is off unless given): every pair of input frames is also
 scored by ssm_amd.video.SceneCuts from the sum of its absolute luma differences (taken on the GPU, beside the pair's own work), and a pair
@@ -138,6 +142,10 @@ def getargs(argv=None):
     parser.add_argument("--shutter_light", choices=V.SHUTTER_LIGHTS + V.HDR_LIGHTS, default="coded",
                         help="With --shutter: average the coded values (coded) or the light they stand for under a curve (bt709, srgb, "
                              "bt1886; for HDR clips pq, hlg); which curve fits depends on how the clip was graded. Default coded.")
+    parser.add_argument("--shutter_window", type=_named(V.parse_shutter_window), default=V.parse_shutter_window("box"),
+                        metavar="box|triangle|hann|gauss[:K]",
+                        help="With --shutter: the weights of the sub-frames. box: all alike; triangle, hann, gauss[:K] (+-K standard deviations, "
+                             "default 2, a convention) fall off towards the ends of the exposure. Default box.")
     parser.add_argument("--scene_cut", type=_named(V.parse_scene_cut), default=None, metavar="T",
                         help="Scene-cut threshold as a decimal or a fraction in (0, 1] (0.1, 1/10): a pair of input frames whose score reaches it "
                              "gets copies of its input frames instead of synthesised ones. A convention, no measured optimum; no default "
@@ -210,6 +218,9 @@ def getargs(argv=None):
             args.upsample_rate = 8
     if args.shutter_light != "coded" and args.shutter is None:
         parser.error("--shutter_light %s is the light in which --shutter averages: it needs --shutter" % args.shutter_light)
+    if args.shutter_window[0] != "box" and args.shutter is None:
+        parser.error("--shutter_window %s is the window of the sub-frames that --shutter averages: it needs --shutter"
+                     % V.window_name(args.shutter_window))
     if args.scene_cut is not None and args.shutter is not None:
         parser.error("--scene_cut does not go together with --shutter: an average of sub-frames across a cut needs a definition of its own")
     if args.shutter is not None and args.shutter_samples < 1:
@@ -230,7 +241,7 @@ def main(argv=None, model=None):
     vi = V.VideoInterpolator(model, config, upsample_rate=args.upsample_rate, matrix=matrix, color_range=crange,
                              flow_scale=args.flow_scale, tile=args.tile, halo=args.halo, blend=args.blend, target_rate=args.fps, speed=args.speed,
                              shutter=args.shutter, shutter_samples=args.shutter_samples, scene_cut=args.scene_cut,
-                             shutter_light=args.shutter_light, deinterlace=args.deinterlace, dedup=args.dedup, dedup_max=args.dedup_max,
+                             shutter_light=args.shutter_light, shutter_window=args.shutter_window, deinterlace=args.deinterlace, dedup=args.dedup, dedup_max=args.dedup_max,
                              active=args.active, active_probe=args.active_probe)
     with V.Y4MReader(args.input, extended=True, interlaced=args.deinterlace is not None or args.detelecine) as reader:
         if args.detelecine:
@@ -246,6 +257,10 @@ def main(argv=None, model=None):
             if tl.samples > 1:
                 log.info("[%s] shutter: %s of the interval in %d samples, averaged in %s", args.expt, tl.shutter, tl.samples,
                          "coded values" if args.shutter_light == "coded" else "light (%s)" % args.shutter_light)
+                w, scale = V.shutter_window(args.shutter_window, tl.samples)
+                log.info("[%s] shutter window: %s, weights %s, scale %.9g%s", args.expt, V.window_name(args.shutter_window),
+                         " ".join("%.9g" % x for x in w), scale,
+                         " (the unweighted calls)" if args.shutter_window[0] == "box" else "")
         else:
             rate = V.output_rate(reader.rate, args.upsample_rate, args.slowmo)
             if args.dedup is not None:

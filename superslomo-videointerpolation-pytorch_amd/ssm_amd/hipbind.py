@@ -19,6 +19,7 @@ SSM_TAIL_SLACK_FLOATS = 1 << 16
 SSM_LIGHT_ROW = 9      # floats in a light curve's row (include/ssm_hip.h; ssm_amd.video.light_curve)
 SSM_HDR_ROW = 8        # floats in an HDR transfer function's row, and its two kinds (include/ssm_hip.h; ssm_amd.video.hdr_light)
 SSM_HDR_PQ, SSM_HDR_HLG = 0, 1
+SSM_ACC_WEIGHTS_MAX = 64          # weights of one weighted accumulate call (include/ssm_hip.h; ssm_amd.video.shutter_window)
 SSM_FLAG_LRELU = 1
 SSM_FLAG_MASK = 8      # the `add` view is a mask source: out = conv(x) * (add > 0 ? 1 : slope) (include/ssm_hip.h)
 
@@ -223,6 +224,11 @@ SIGNATURES = {
     "ssm_frames_accumulate_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _vp]),
     "ssm_frames_accumulate_light_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _vp, _vp, _c_int, _vp]),
     "ssm_frames_accumulate_hdr_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _vp, _c_int, _vp, _c_int, _vp]),
+    "ssm_frames_accumulate_weighted_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _vp]),
+    "ssm_frames_accumulate_light_weighted_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _vp, _vp, _vp, _c_int,
+                                                          _vp]),
+    "ssm_frames_accumulate_hdr_weighted_fwd": (_c_int, [SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_float, _vp, _vp, _vp, _c_int, _vp,
+                                                        _c_int, _vp]),
     "ssm_luma_sad_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_int, _vp, _vp]),
     "ssm_field_diff_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
     "ssm_plane_sse_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _vp]),
@@ -418,12 +424,18 @@ def tile_stitch(tile, out, origin, core, seams, blend):
     return out
 
 
-def frames_accumulate(src, acc, init, scale):
+def frames_accumulate(src, acc, init, scale, weights=None):
     """ssm_frames_accumulate_fwd: acc [1,C,H,W] = ((init ? src[0] : acc + src[0]) + src[1] + ... + src[N-1]) * scale for src [N,C,H,W],
-    summed in increasing n, one rounded fp32 operation per step (include/ssm_hip.h; yardstick: ssm_amd.video.accumulate_host)."""
+    summed in increasing n, one rounded fp32 operation per step (include/ssm_hip.h; yardstick: ssm_amd.video.accumulate_host).
+    weights (N floats, at most SSM_ACC_WEIGHTS_MAX): ssm_frames_accumulate_weighted_fwd, weights[n] * src[n] in place of src[n], one
+    more rounded multiply per frame; None is the call as it was."""
     N, C, H, W = src.shape
     assert acc.dim() == 4 and tuple(acc.shape) == (1, C, H, W), "frames %s and accumulator %s disagree" % (tuple(src.shape), tuple(acc.shape))
-    check(load().ssm_frames_accumulate_fwd(view_of(src), view_of(acc), N, C, H, W, int(init), float(scale), stream_ptr()))
+    if weights is None:
+        check(load().ssm_frames_accumulate_fwd(view_of(src), view_of(acc), N, C, H, W, int(init), float(scale), stream_ptr()))
+    else:
+        check(load().ssm_frames_accumulate_weighted_fwd(view_of(src), view_of(acc), N, C, H, W, int(init), float(scale),
+                                                        _floats(weights, N, "a call's weights"), stream_ptr()))
     return acc
 
 
@@ -436,29 +448,38 @@ def _floats(v, n, what):
     return (ctypes.c_float * n)(*vals)
 
 
-def frames_accumulate_light(src, acc, init, scale, mean, std, curve, encode):
+def frames_accumulate_light(src, acc, init, scale, mean, std, curve, encode, weights=None):
     """ssm_frames_accumulate_light_fwd: ssm_frames_accumulate_fwd on light.  Every value of src [N,3,H,W] is denormalised by (mean, std),
     clamped to [0, 1] and decoded by `curve` (a row of ssm_amd.video.light_curve) before it is added into acc [1,3,H,W]; with encode = 1
-    the scaled sum is encoded and normalised again (include/ssm_hip.h; yardstick: ssm_amd.video.accumulate_light_host)."""
+    the scaled sum is encoded and normalised again (include/ssm_hip.h; yardstick: ssm_amd.video.accumulate_light_host).
+    weights (N floats): ssm_frames_accumulate_light_weighted_fwd, weights[n] times the decoded light of src[n]; None is the call as it was."""
     N, C, H, W = src.shape
     assert C == 3 and acc.dim() == 4 and tuple(acc.shape) == (1, 3, H, W), \
         "frames %s and accumulator %s must be [N,3,H,W] and [1,3,H,W]" % (tuple(src.shape), tuple(acc.shape))
-    check(load().ssm_frames_accumulate_light_fwd(view_of(src), view_of(acc), N, H, W, int(init), float(scale), _floats(mean, 3, "mean"),
-                                                 _floats(std, 3, "std"), _floats(curve, SSM_LIGHT_ROW, "a light curve's row"), int(encode),
-                                                 stream_ptr()))
+    rest = (_floats(mean, 3, "mean"), _floats(std, 3, "std"), _floats(curve, SSM_LIGHT_ROW, "a light curve's row"), int(encode), stream_ptr())
+    if weights is None:
+        check(load().ssm_frames_accumulate_light_fwd(view_of(src), view_of(acc), N, H, W, int(init), float(scale), *rest))
+    else:
+        check(load().ssm_frames_accumulate_light_weighted_fwd(view_of(src), view_of(acc), N, H, W, int(init), float(scale),
+                                                              _floats(weights, N, "a call's weights"), *rest))
     return acc
 
 
-def frames_accumulate_hdr(src, acc, init, scale, mean, std, kind, consts, encode):
+def frames_accumulate_hdr(src, acc, init, scale, mean, std, kind, consts, encode, weights=None):
     """ssm_frames_accumulate_hdr_fwd: frames_accumulate_light with a BT.2100 transfer function in place of a power-law curve.  kind is
     SSM_HDR_PQ or SSM_HDR_HLG and `consts` that kind's row (ssm_amd.video.hdr_light(name) gives both); include/ssm_hip.h has the
-    definitions; yardstick: ssm_amd.video.accumulate_hdr_host."""
+    definitions; yardstick: ssm_amd.video.accumulate_hdr_host.  weights (N floats): ssm_frames_accumulate_hdr_weighted_fwd, as
+    frames_accumulate_light's; None is the call as it was."""
     N, C, H, W = src.shape
     assert C == 3 and acc.dim() == 4 and tuple(acc.shape) == (1, 3, H, W), \
         "frames %s and accumulator %s must be [N,3,H,W] and [1,3,H,W]" % (tuple(src.shape), tuple(acc.shape))
-    check(load().ssm_frames_accumulate_hdr_fwd(view_of(src), view_of(acc), N, H, W, int(init), float(scale), _floats(mean, 3, "mean"),
-                                               _floats(std, 3, "std"), int(kind), _floats(consts, SSM_HDR_ROW, "an HDR light's row"),
-                                               int(encode), stream_ptr()))
+    rest = (_floats(mean, 3, "mean"), _floats(std, 3, "std"), int(kind), _floats(consts, SSM_HDR_ROW, "an HDR light's row"), int(encode),
+            stream_ptr())
+    if weights is None:
+        check(load().ssm_frames_accumulate_hdr_fwd(view_of(src), view_of(acc), N, H, W, int(init), float(scale), *rest))
+    else:
+        check(load().ssm_frames_accumulate_hdr_weighted_fwd(view_of(src), view_of(acc), N, H, W, int(init), float(scale),
+                                                            _floats(weights, N, "a call's weights"), *rest))
     return acc
 
 

@@ -26,6 +26,10 @@
   hdr_light               the shutter in the light of HDR clips, "pq" and "hlg" (HDR_LIGHTS): the kind and row ssm_frames_accumulate_hdr_fwd takes
   hdr_decode_host / hdr_encode_host   the BT.2100 PQ EOTF and inverse HLG OETF and their inverses, in float64 or in the kernel's fp32 steps
   accumulate_hdr_host     the float64 yardstick of ssm_frames_accumulate_hdr_fwd, accumulate_light_host with those in place of a curve's row
+  shutter_window /        the weights of a shutter's sub-frames: "box" (all alike: the calls above, untouched), "triangle", "hann", "gauss[:K]",
+  parse_shutter_window    sample j at (j + 1/2) / S of the open interval, and the scale 1 / sum that closes an output; the three yardsticks take
+                          weights= and are then those of the ssm_frames_accumulate*_weighted_fwd siblings (coded: bit for bit; light and HDR:
+                          bounds of tests/test_video_window_cpu.py) - VideoInterpolator(shutter_window=)
   luma_sad_host / luma_sad   scene cuts: per frame pair the exact sum of |difference| of the 8-bit Y planes, by numpy (the yardstick) and by
   / SceneCuts             ssm_luma_sad_fwd on the payloads as they stand on the device; the decision from those sums in Fractions, with no
                           GPU in it - VideoInterpolator(scene_cut=): at a cut the output repeats the nearer input frame instead of a morph
@@ -57,8 +61,8 @@ read as C420 is, centred.  The fp32 pipeline between ingest and egress is the sa
 
 Out of scope: codecs, audio, output in another format than the input (8-bit in, 10-bit out), mono, 4:1:1 and alpha planes, a siting
 override for C420pB, big-endian samples, scene cuts above 8 bits (ssm_luma_sad_fwd and the score's / 255 are 8-bit), the recurrent
-configuration (N_FRAMES > 2); shutter weights other than
-the box, a light curve chosen from the clip's tags, an OOTF for the HDR lights (PQ display light and HLG scene light are taken as they are), BT.2020 constant luminance, a shutter centred on the frame's instant or open for longer than the frame interval,
+configuration (N_FRAMES > 2); asymmetric or user-supplied shutter weights, shutter windows on the fixed grid
+(upsample_rate, slowmo), any statement about which window looks best, a light curve chosen from the clip's tags, an OOTF for the HDR lights (PQ display light and HLG scene light are taken as they are), BT.2020 constant luminance, a shutter centred on the frame's instant or open for longer than the frame interval,
 variable-rate input, speeds that change within a clip; a default scene-cut threshold, fades and dissolves, cuts judged on chroma,
 skipping the GPU work of a cut pair, scene cuts together with a shutter; a measure of quality other than video_score's PSNR against
 held-out frames (SSIM, VMAF), and that score for the timeline, shutter and scene-cut outputs; of interlaced clips: mixed field order (Im),
@@ -347,16 +351,31 @@ def frames_to_yuv_host(x, h, w, siting=CENTRED, matrix=BT709, color_range=LIMITE
     return np.concatenate([p.reshape(n, -1) for p in planes], axis=1).view(np.uint8)
 
 
-def accumulate_host(frames, acc, init, scale):
+def _call_weights(weights, n, dt):
+    """A weighted call's N weights as `dt` values of the fp32 weights the kernel is given."""
+    w = np.asarray(weights, dtype=_F)
+    assert w.shape == (n,) and np.all(np.isfinite(w)), "a weighted call takes one finite weight per frame (%d frames, weights %r)" % (n, weights)
+    return w.astype(dt)
+
+
+def accumulate_host(frames, acc, init, scale, weights=None):
     """Yardstick of ssm_frames_accumulate_fwd: frames [N,C,H,W] float32 (numpy) summed into acc [1,C,H,W] or [C,H,W] float32, in place:
-    s = frames[0] if init else acc + frames[0]; s = s + frames[n] for n = 1 .. N-1; acc = s * scale - every step rounded to float32."""
+    s = frames[0] if init else acc + frames[0]; s = s + frames[n] for n = 1 .. N-1; acc = s * scale - every step rounded to float32.
+    weights (N floats): the yardstick of ssm_frames_accumulate_weighted_fwd, p_n = weights[n] * frames[n] in place of frames[n], the
+    product one more rounded float32 operation; None is the arithmetic above, line for line."""
     frames = np.asarray(frames, dtype=_F)
     assert acc.dtype == _F and frames.ndim == 4 and frames.shape[0] >= 1 and init in (0, 1, False, True)
     dst = acc[0] if acc.ndim == 4 else acc
     assert dst.shape == frames.shape[1:] and (acc.ndim == 3 or acc.shape[0] == 1)
-    s = frames[0].copy() if init else dst + frames[0]
-    for n in range(1, frames.shape[0]):
-        s = s + frames[n]
+    if weights is None:
+        s = frames[0].copy() if init else dst + frames[0]
+        for n in range(1, frames.shape[0]):
+            s = s + frames[n]
+    else:
+        w = _call_weights(weights, frames.shape[0], _F)
+        s = w[0] * frames[0] if init else dst + w[0] * frames[0]
+        for n in range(1, frames.shape[0]):
+            s = s + w[n] * frames[n]
     dst[...] = s * _F(scale)
     return acc
 
@@ -391,7 +410,7 @@ def light_encode_host(lum, curve, dtype=np.float64):
     return np.where(lum <= lthr, lum * slope, a1 * np.power(np.maximum(lum, dt(0.0)), ig) - a)
 
 
-def accumulate_light_host(frames, acc, init, scale, mean, std, curve, encode, dtype=np.float64):
+def accumulate_light_host(frames, acc, init, scale, mean, std, curve, encode, dtype=np.float64, weights=None):
     """Yardstick of ssm_frames_accumulate_light_fwd: frames [N,3,H,W] float32 (numpy, finite) summed as light into acc [1,3,H,W] or
     [3,H,W] of `dtype`, in place, the kernel's operations in the kernel's order, every one in `dtype`:
       dec(v) = 0 if v <= black[p] else decode(clip(v * std[p] + mean[p], 0, 1)), black = (0 / 255 - mean) / std in fp32 as the ingest has it;
@@ -400,7 +419,9 @@ def accumulate_light_host(frames, acc, init, scale, mean, std, curve, encode, dt
     mean and std enter as the fp32 values the kernel is given, the curve's row as _light_constants says; scale is taken as it is (the
     kernel takes an fp32 one: give np.float32(1 / S) to compare).  dtype = float64: the fixed point the kernel is held to within the
     bound of tests/test_video_light_cpu.py (x ^ e is numpy's power).  dtype = float32: what plain fp32 arithmetic gives; it is not the
-    kernel bit for bit, whose power is 2 ^ (e log2 x) by the hardware's instructions."""
+    kernel bit for bit, whose power is 2 ^ (e log2 x) by the hardware's instructions.
+    weights (N floats): the yardstick of ssm_frames_accumulate_light_weighted_fwd, weights[n] * dec(frames[n]) in place of dec(frames[n]),
+    the fp32 weights taken to `dtype` as they are (bounds: tests/test_video_window_cpu.py); None is the arithmetic above, line for line."""
     dt = np.dtype(dtype).type
     assert dt in (np.float32, np.float64), "dtype is numpy's float32 or float64"
     frames = np.asarray(frames, dtype=_F)
@@ -416,9 +437,15 @@ def accumulate_light_host(frames, acc, init, scale, mean, std, curve, encode, dt
         c = np.where(v <= black, dt(0.0), np.clip(v.astype(dt) * sd + m, dt(0.0), dt(1.0)))
         return light_decode_host(c, curve, dt)
 
-    s = dec(frames[0]) if init else dst + dec(frames[0])
-    for n in range(1, frames.shape[0]):
-        s = s + dec(frames[n])
+    if weights is None:
+        s = dec(frames[0]) if init else dst + dec(frames[0])
+        for n in range(1, frames.shape[0]):
+            s = s + dec(frames[n])
+    else:
+        w = _call_weights(weights, frames.shape[0], dt)
+        s = w[0] * dec(frames[0]) if init else dst + w[0] * dec(frames[0])
+        for n in range(1, frames.shape[0]):
+            s = s + w[n] * dec(frames[n])
     r = s * dt(scale)
     dst[...] = (light_encode_host(r, curve, dt) - m) / sd if encode else r
     return acc
@@ -467,11 +494,12 @@ def hdr_encode_host(lum, name, dtype=np.float64):
         return np.where(lum <= k[4], np.sqrt(dt(3.0) * np.maximum(lum, dt(0.0))), k[5] * np.log2(dt(12.0) * lum - k[3]) + k[2])
 
 
-def accumulate_hdr_host(frames, acc, init, scale, mean, std, name, encode, dtype=np.float64):
+def accumulate_hdr_host(frames, acc, init, scale, mean, std, name, encode, dtype=np.float64, weights=None):
     """Yardstick of ssm_frames_accumulate_hdr_fwd: accumulate_light_host with hdr_decode_host / hdr_encode_host of `name` ("pq", "hlg") in
     place of a curve's row - the same black comparison, clamp, order of the sum, scale and closing normalisation, in `dtype`.
     dtype = float64: the fixed point the kernel is held to within the bound of tests/test_video_hdr_cpu.py.  dtype = float32: plain fp32
-    arithmetic in the kernel's steps; not the kernel bit for bit, whose log2, exp2, reciprocal and square root are the hardware's."""
+    arithmetic in the kernel's steps; not the kernel bit for bit, whose log2, exp2, reciprocal and square root are the hardware's.
+    weights: as accumulate_light_host's, the yardstick of ssm_frames_accumulate_hdr_weighted_fwd."""
     dt = np.dtype(dtype).type
     assert dt in (np.float32, np.float64), "dtype is numpy's float32 or float64"
     assert name in HDR_KINDS, "an HDR light is one of %s" % ", ".join(HDR_LIGHTS)
@@ -488,9 +516,15 @@ def accumulate_hdr_host(frames, acc, init, scale, mean, std, name, encode, dtype
         c = np.where(v <= black, dt(0.0), np.clip(v.astype(dt) * sd + m, dt(0.0), dt(1.0)))
         return hdr_decode_host(c, name, dt)
 
-    s = dec(frames[0]) if init else dst + dec(frames[0])
-    for n in range(1, frames.shape[0]):
-        s = s + dec(frames[n])
+    if weights is None:
+        s = dec(frames[0]) if init else dst + dec(frames[0])
+        for n in range(1, frames.shape[0]):
+            s = s + dec(frames[n])
+    else:
+        w = _call_weights(weights, frames.shape[0], dt)
+        s = w[0] * dec(frames[0]) if init else dst + w[0] * dec(frames[0])
+        for n in range(1, frames.shape[0]):
+            s = s + w[n] * dec(frames[n])
     r = s * dt(scale)
     dst[...] = (hdr_encode_host(r, name, dt) - m) / sd if encode else r
     return acc
@@ -1781,6 +1815,69 @@ def parse_shutter(text):
     return deg / 360
 
 
+# Shutter windows: the weights of an output's S sub-frames.  Sample j sits at u_j = (j + 1/2) / S of the open interval - symmetric in j, so
+# the blur's centre of mass stays where the box puts it.  "box" is no weighted call at all: the loop as it was before there were windows.
+SHUTTER_WINDOWS = ("box", "triangle", "hann", "gauss")
+GAUSS_K = Fraction(2)          # gauss spans +-K standard deviations over the open interval; 2 is a convention, not a measured optimum
+ACC_WEIGHTS_MAX = hb.SSM_ACC_WEIGHTS_MAX
+
+
+def parse_shutter_window(text):
+    """"box", "triangle", "hann", "gauss" or "gauss:K" with K a positive decimal or fraction ("gauss" is "gauss:2") -> (name, K or None);
+    anything else is a ValueError naming the value."""
+    names = "box, triangle, hann, gauss[:K]"
+    if isinstance(text, tuple) and len(text) == 2 and text[0] in SHUTTER_WINDOWS:
+        text = text[0] if text[1] is None else "%s:%s" % text
+    if not isinstance(text, str):
+        raise ValueError("unknown shutter_window %r: it is one of %s" % (text, names))
+    name, colon, arg = text.strip().partition(":")
+    if name not in SHUTTER_WINDOWS or (colon and name != "gauss"):
+        raise ValueError("unknown shutter_window %r: it is one of %s" % (text, names))
+    if name != "gauss":
+        return name, None
+    if not colon:
+        return name, GAUSS_K
+    try:
+        k = Fraction(arg.strip())
+    except (ValueError, ZeroDivisionError):
+        raise ValueError("shutter_window %r: K of gauss:K is written as a decimal or a fraction, e.g. 2, 2.5 or 5/2" % (text,)) from None
+    if k <= 0:
+        raise ValueError("shutter_window %r: K of gauss:K must be positive" % (text,))
+    return name, k
+
+
+def window_name(window):
+    """A parsed window as it is written: "hann", "gauss:2", "gauss:5/2"."""
+    name, k = parse_shutter_window(window)
+    return name if k is None else "%s:%s" % (name, k)
+
+
+def shutter_window(name, S):
+    """(w, scale) of a shutter window over S samples: w the S float32 weights, scale = float32(1 / sum of float64(w_j)) - the sum of the
+    fp32 weights taken in float64, one division, rounded once.  With u_j = (j + 1/2) / S:
+      box        w_j = 1: what the unweighted calls compute, here for the record - the streamed loop makes no weighted call for it
+      triangle   w_j = min(2 j + 1, 2 (S - j) - 1): odd integers, exact in fp32, proportional to 1 - |2 u_j - 1|
+      hann       w_j = float32(sin^2(pi u_j)), evaluated in float64
+      gauss[:K]  w_j = float32(exp(-1/2 (K (2 u_j - 1))^2)), evaluated in float64: the window spans +-K standard deviations (default 2)
+    `name` is what parse_shutter_window takes or returns."""
+    name, k = parse_shutter_window(name)
+    if isinstance(S, bool) or int(S) != S or S < 1:
+        raise ValueError("a shutter window has at least 1 sample (got %r)" % (S,))
+    S = int(S)
+    j = np.arange(S, dtype=np.float64)
+    u = (j + 0.5) / S
+    if name == "box":
+        w = np.ones(S)
+    elif name == "triangle":
+        w = np.minimum(2 * j + 1, 2 * (S - j) - 1)
+    elif name == "hann":
+        w = np.sin(np.pi * u) ** 2
+    else:
+        w = np.exp(-0.5 * (float(k) * (2.0 * u - 1.0)) ** 2)
+    w = w.astype(_F)
+    return w, _F(1.0 / w.astype(np.float64).sum())
+
+
 def parse_scene_cut(text):
     """A scene-cut threshold, "0.1" or "1/10" (or a number, or a Fraction) -> Fraction in (0, 1]; anything else is a ValueError naming
     the value."""
@@ -2340,7 +2437,8 @@ class VideoInterpolator:
 
     def __init__(self, model, cfg, upsample_rate=None, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
                  tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8, scene_cut=None,
-                 shutter_light="coded", deinterlace=None, dedup=None, dedup_max=DEDUP_MAX, active=None, active_probe=ACTIVE_PROBE):
+                 shutter_light="coded", deinterlace=None, dedup=None, dedup_max=DEDUP_MAX, active=None, active_probe=ACTIVE_PROBE,
+                 shutter_window="box"):
         """target_rate = (num, den) and / or speed (a Fraction, or what Fraction() takes; 1/4 is four times slower): the output follows
         Timeline(speed * input rate / target_rate) instead of the fixed grid of upsample_rate, which is then not used (see
         _run_timeline); with both None nothing changes.  flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
@@ -2361,6 +2459,13 @@ class VideoInterpolator:
         R'G'B' after the matrix and is independent of matrix and color_range.  "pq" and "hlg" (HDR_LIGHTS) are the BT.2100 transfer
         functions of HDR clips, the same way through ssm_frames_accumulate_hdr_fwd: pq the PQ EOTF (display light as a fraction of
         10000 cd/m2), hlg the inverse of the HLG OETF (scene light), neither with an OOTF.
+        shutter_window ("box", "triangle", "hann", "gauss" or "gauss:K"; parse_shutter_window), with a shutter: the weights of an
+        output's sub-frames.  "box" weighs them alike and is, launch for launch, the loop as it was before the option.  The others fall
+        off towards the ends of the exposure (shutter_window(name, shutter_samples)): the S evenly bright copies of a fast object become
+        a streak that fades in and out, at the same S and so the same stage-2 cost; every accumulate call is then the weighted sibling
+        of the one above (ssm_frames_accumulate_weighted_fwd and its light and HDR forms) with its slice of the window, and the output
+        closes with the window's scale in place of 1 / S.  It goes with every shutter_light.  gauss spans +-K standard deviations;
+        K = 2, like the 8 samples, is a convention.  With shutter_samples = 1 any window is the loop without a shutter.
         matrix (None: default_matrix(h) per clip; BT601, BT709 or BT2020 = MATRICES' values): BT2020 is never a default, since no Y4M
         header names the matrix.
         scene_cut (a Fraction in (0, 1], or what Fraction() takes; no default value): the threshold of SceneCuts.  Every pass then also
@@ -2455,6 +2560,10 @@ class VideoInterpolator:
         if self.shutter_light != "coded" and shutter is None:
             raise ValueError("shutter_light=%r is the light in which a shutter averages: give a shutter, or leave it at \"coded\""
                              % (shutter_light,))
+        self.shutter_window = parse_shutter_window(shutter_window)
+        if self.shutter_window[0] != "box" and shutter is None:
+            raise ValueError("shutter_window=%r is the window of a shutter's sub-frames: give a shutter, or leave it at \"box\""
+                             % (shutter_window,))
         self.timed = target_rate is not None or speed is not None
         self.scene_cut, self.cuts = None if scene_cut is None else parse_scene_cut(scene_cut), []
         if scene_cut is not None and shutter is not None:
@@ -2906,6 +3015,10 @@ class VideoInterpolator:
         samples are all input frames.  With shutter_light a curve every one of those calls is ssm_frames_accumulate_light_fwd instead
         (ssm_frames_accumulate_hdr_fwd for "pq" and "hlg"),
         with encode = 1 on an output's last: the accumulator holds light in between and normalised coded planes for the egress.
+        With a shutter_window other than "box" every call is the weighted sibling instead and carries w[j0 : j0 + count] of
+        shutter_window(name, S), j0 the samples of the open output that earlier calls took (0 on init), and the last call the window's
+        scale; a call of more than ACC_WEIGHTS_MAX samples goes out as consecutive pieces of at most that many - init on the first, scale
+        and encode on the last - which is the same sum in the same order.  "box" makes none of these: today's calls, launch for launch.
 
         A pass (bookkeeping: ShutterPlanner) uploads and ingests, in one piece each, the frames it holds that a sample needs; copies the
         planes of up to pairs_per_batch pairs that get a sample side by side; runs them at their sample times padded to `slots`; and
@@ -2924,6 +3037,9 @@ class VideoInterpolator:
         depth, cap = n + 2, 2 * pb + 2
         plan = ShutterPlanner(tl, pb, cap)
         scale = np.float32(1.0 / tl.samples)
+        window = None          # "box": no weighted call
+        if self.shutter_window[0] != "box":
+            window, scale = shutter_window(self.shutter_window, tl.samples)
         light = hdr = None
         if self.shutter_light in HDR_KINDS:
             kind, row = hdr_light(self.shutter_light)
@@ -2937,6 +3053,21 @@ class VideoInterpolator:
         acc = torch.zeros(OPEN_OUTPUTS, 3, hp, wp, dtype=torch.float32, device=dev)
         summed = [torch.cuda.Event() for _ in range(n)]
         torch.cuda.synchronize(dev)
+
+        taken = [0]          # samples of the open output that the calls so far took: where the next call's weights start in the window
+
+        def accumulate_pieces(x, a, init, last, w):
+            """One planner call with a window: the weighted entry point of the light, in pieces of at most ACC_WEIGHTS_MAX frames."""
+            assert len(w) == x.shape[0], "a call's samples (%d) leave the window (%d weights left)" % (x.shape[0], len(w))
+            for p0 in range(0, x.shape[0], ACC_WEIGHTS_MAX):
+                p1 = min(p0 + ACC_WEIGHTS_MAX, x.shape[0])
+                i, e, sc = 1 if init and p0 == 0 else 0, 1 if last and p1 == x.shape[0] else 0, scale if last and p1 == x.shape[0] else 1.0
+                if hdr is not None:
+                    hb.frames_accumulate_hdr(x[p0:p1], a, i, sc, *hdr, e, weights=w[p0:p1])
+                elif light is None:
+                    hb.frames_accumulate(x[p0:p1], a, i, sc, weights=w[p0:p1])
+                else:
+                    hb.frames_accumulate_light(x[p0:p1], a, i, sc, *light, e, weights=w[p0:p1])
 
         def submit(j, r, rows, carry, pairs, calls, finished):
             """Pass j on ring slot r; the arguments are ShutterPlanner's."""
@@ -2962,7 +3093,11 @@ class VideoInterpolator:
                 for src, first, count, ko, init, last in calls:
                     a = acc[ko % OPEN_OUTPUTS:ko % OPEN_OUTPUTS + 1]
                     x = planes[k][first:first + 1] if src == "frame" else frames[first:first + count]
-                    if hdr is not None:
+                    if window is not None:
+                        taken[0] = 0 if init else taken[0]
+                        accumulate_pieces(x, a, init, last, window[taken[0]:taken[0] + x.shape[0]])
+                        taken[0] += x.shape[0]
+                    elif hdr is not None:
                         hb.frames_accumulate_hdr(x, a, 1 if init else 0, scale if last else 1.0, *hdr, 1 if last else 0)
                     elif light is None:
                         hb.frames_accumulate(x, a, 1 if init else 0, scale if last else 1.0)
