@@ -986,6 +986,50 @@ int ssm_fields_weave_fwd(const void *kept, long long stride_kept, const void *ma
 int ssm_field_diff_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int sample_bytes,
                        unsigned long long *sums, void *stream);
 
+/* ---- field order from the data, for the interlaced clips of the streamed video loop (csrc/ssm_video.hip; beyond the reference's surface) --
+ * Definition (ssm_amd.video.field_order_sums_host is all of it in numpy, field_kind the kind of a frame, FieldVerdict the decision over a
+ * probe, FieldOrderSource the streamed form).  A Y4M header may say Ip or I? over interlaced material (ffmpeg writes Ip where it does not
+ * know the order), and nothing refuses a wrong tff / bff: the fields are then woven in the wrong temporal order.  The operands are three
+ * luma planes p, c, n - the frame before, the frame, the frame after - of H x W samples.  Everything is exact integers, over the rows
+ * y = 1 .. H - 2 and all x:
+ *     s[y][x] = c[y-1][x] + c[y+1][x]
+ *     E_r[y]  = sum over x of |s[y][x] - 2 r[y][x]|          for r in {p, n, c}
+ *     A0 = sum over even y of E_p[y] + sum over odd y of E_n[y]
+ *     A1 = sum over odd y of E_p[y]  + sum over even y of E_n[y]
+ *     D  = sum over y of E_c[y]
+ *   why       under top-field-first an odd row of c lies half a frame AFTER its neighbours c[y +- 1]: row y of p is half a frame away from
+ *             them and row y of n one and a half frames; for the even rows it is the other way round.  So A1 collects the near comparisons
+ *             and A0 the far ones: tff gives A0 > A1, bff A1 > A0.  A progressive clip in motion gives A0 ~ A1 >> D, a still A0 = A1 = D.
+ *             H < 3 has no such row: three zeros.
+ *   kind      of a frame, in integers:  T if 25 A0 > 26 A1;  else B if 25 A1 > 26 A0;  else P if 2 min(A0, A1) > 3 D;  else U.
+ *   verdict   over the kinds of frames 1 .. m - 2 of m probed frames, counts nT, nB, nP, nU and d = nT + nB + nP:  "tff" if 2 nT > d,
+ *             "bff" if 2 nB > d, "progressive" if 2 nP > d, else none; fewer than 3 probed frames give none.
+ *             The ratios 26/25 and 3/2 are conventions in the spirit of ffmpeg's idet, NOT its construction, and nothing here claims its
+ *             decisions frame for frame; ffmpeg is not compared.  Not backed by a measurement on noisy or compressed footage.  A hard-edged
+ *             shape that moves by whole rows biases one parity through its vertical edges: a progressive clip of one can come out B.
+ * ssm_field_order_sums_fwd: p + i stride_p, c + i stride_c and n + i stride_n (strides in BYTES, of either sign, or 0) point at luma planes
+ * i = 0 .. N-1 of H x W samples, rows unpadded.  sample_bytes = 1: bytes.  sample_bytes = 2: 16-bit little-endian words, ALL 16 BITS COUNT.
+ *     sums[3 i + 0] = A0,  sums[3 i + 1] = A1,  sums[3 i + 2] = D          of (p_i, c_i, n_i)
+ * exact, in a device array of 3 N 64-bit words.  The entry clears them on `stream` itself (a memset node ahead of the kernel; with H < 3
+ * it is all that is queued).  Odd H and W = 1 are fine.  The operands are only read and may alias or overlap - frames i - 1, i, i + 1 of
+ * one buffer are one pointer each and one stride.  No byte outside the N planes of an operand is read.
+ *   The grid's x axis counts units: a unit is one 16-byte piece of the rows (a row of W sample_bytes bytes has ceil of that / 16, the last
+ *   one ragged) over a band of 8 rows, bands from row 1 on; unit id is piece id mod pieces of band id / pieces, a workgroup of 256 lanes
+ *   takes 256 of them, a lane one, neighbouring lanes neighbouring pieces of the same rows; the y axis is i.  A lane walks down its band
+ *   with c[y-1], c[y], c[y+1] in registers.  Bytes are widened to pairs of packed 16-bit numbers (s <= 510) and go two per v_sad_u16,
+ *   words one per 32-bit subtract.  |s - 2 r| <= 131070 per sample: a lane's three sums are at most 8 rows x 8 words x 131070 < 2^23
+ *   each, a workgroup's 256 times that, 2147450880 < 2^31 - everything up to the workgroup's three sums fits 32 bits.  One 16-byte load
+ *   per piece where it is whole and its address sits on a 16-byte boundary, sample by sample otherwise and at a row's end, decided in the
+ *   same kernel (per lane without a test where the three planes and the row pitch are multiples of 16 bytes and the band is whole: all
+ *   26 loads first).  Waves reduced by cross-lane shuffles, 3 x 4 wave partials through LDS, then one 64-bit vector atomicAdd per sum
+ *   and workgroup.  Integer adds commute: the sums are the same in every run.  No scratch, no packed fp32.  Reads 3 sample_bytes per
+ *   pixel and the two rows around a band of c again: 3.25.
+ * SSM_E_ARG (nothing is queued), each with its own message and in this order: null pointers; N outside 1..65535; H or W < 1; sample_bytes
+ * outside {1, 2}; a stride that is neither 0 nor at least the plane's bytes in magnitude; with sample_bytes = 2 an odd address, then an
+ * odd stride; `sums` not 8-byte aligned; a plane of more than 2^31 - 1 pieces. */
+int ssm_field_order_sums_fwd(const void *p, const void *c, const void *n, long long stride_p, long long stride_c, long long stride_n, int N,
+                             int H, int W, int sample_bytes, unsigned long long *sums, void *stream);
+
 /* ---- repeated frames of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) ---------------------------
  * Definition (ssm_amd.video.dedup_host is all of it in numpy, Repeats the decision, RepeatSource and GapTimeline the streamed form).
  * Animation on twos or threes, 24 or 25 frames/s brought to 50 or 60 by repetition, screen recordings and captures that filled a dropped

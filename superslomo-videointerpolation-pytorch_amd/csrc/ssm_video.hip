@@ -34,6 +34,10 @@
 //   field_diff_kernel        pulldown removal, ssm_field_diff_fwd: |a - b| over a luma plane summed per ROW PARITY, the differences of the top
 //                            and of the bottom fields of two frames; the same workgroup and lane work walked by rows (FieldWalk), bytes
 //                            through v_sad_u8 (SadLane), words through v_sad_u16 (SadWordLane), two 64-bit atomics per workgroup
+//   field_order_sums_kernel  field order from the data, ssm_field_order_sums_fwd: per frame the comb sums A0, A1, D of its luma plane against the
+//                            frame before and the frame after, |c[y-1] + c[y+1] - 2 r[y]| for r = p, n, c; a lane owns a 16-byte column piece
+//                            and walks a band of rows with three rows of c in registers, bytes as packed 16-bit pairs through v_sad_u16,
+//                            words in 32 bits, three 64-bit atomics per workgroup
 //   plane_ssim_kernel        hold-out scoring: per frame pair and plane the SSIM of x264 / ffmpeg's ssim filter in fixed point - 4 x 4 block
 //                            sums (bytes through v_dot4_u32_u8) to LDS, 8 x 8 windows at stride 4 from four blocks, integer factors, one
 //                            float64 quotient per window rounded to a multiple of 2^-32, signed 64-bit sums; a workgroup owns 31 x 15 windows
@@ -771,6 +775,176 @@ __global__ __launch_bounds__(LANES) void field_diff_kernel(const unsigned char *
 #pragma unroll
         for (int w = 0; w < LANES / 64; ++w) t += partial[threadIdx.x][w];
         atomicAdd(&sums[2 * n + threadIdx.x], (unsigned long long)t);
+    }
+}
+
+// ---- field order: comb sums of a frame against the frame before and the frame after ------------------------------------------------------
+// sums[3 n + {0, 1, 2}] += this workgroup's share of A0, A1, D of planes (p_n, c_n, n_n) (ssm_field_order_sums_fwd; the definition is in
+// include/ssm_hip.h): over rows y = 1 .. H - 2,  s = c[y-1] + c[y+1]  and  E_r[y] = sum over x of |s - 2 r[y]|  for r = p, n, c.
+// The walk is by COLUMN PIECES: a lane owns one 16-byte piece k of the rows and a band of COMB_BAND rows, y0 = 1 + COMB_BAND band, and
+// goes down the band with c[y-1], c[y], c[y+1] in registers: per row one new piece of c, one of p, one of n.  Unit `id` of a plane is piece
+// id mod pieces of band id / pieces, so neighbouring lanes take neighbouring pieces of the same rows; a workgroup takes LANES units.
+// A band reads its two neighbour rows of c again: (COMB_BAND + 2) / COMB_BAND of c, 3.25 sample_bytes per pixel in all.
+//   pieces    a piece is held as eight 32-bit registers (CombPiece): sixteen bytes widened to eight PAIRS of packed 16-bit numbers (byte
+//             j of a word beside byte j + 2), eight words as one number each.  s is one add per register (510 fits a packed half), 2 r
+//             one shift.  Bytes: |s - 2 r| of a pair through one v_sad_u16; words: 32-bit subtract and select, s <= 131070.
+//   bounds    |s - 2 r| <= 2 * 65535 = 131070 per sample.  A row of a piece adds its E_p to one of A0, A1 and its E_n to the other, so
+//             each of a lane's three sums takes at most COMB_BAND rows of 8 words: 8 * 8 * 131070 < 2^23, and a workgroup's sum of LANES of
+//             them 64 * 131070 * 256 = 2147450880 < 2^31: lane sums, wave sums and the workgroup's three sums fit 32 bits.
+//   loads     where the three planes start on 16-byte boundaries, a row is a multiple of 16 bytes and the lane's band is whole: every
+//             piece by one 16-byte load, none guarded, all of a band's 3 COMB_BAND + 2 loads free to be in flight at once.  Otherwise per
+//             piece one 16-byte load where it is whole and its address sits on a 16-byte boundary, sample by sample where not (rows that
+//             start anywhere, a row's ragged end); samples past the row's end are never loaded and count as 0 in s and in r alike.
+//   sums      field_diff_kernel's steps for three sums: shuffles, wave partials through LDS, then lanes 0, 1, 2 issue ONE 64-bit vector
+//             atomic each.  Integer adds: the same result in every run.
+constexpr int COMB_BAND = 8;
+static_assert(COMB_BAND % 2 == 0, "a band starts on an odd row: the parity of row y0 + j is that of j + 1");
+static_assert(131070ll * (16 / 2) * COMB_BAND * LANES < (1ll << 32), "a workgroup's comb sums of full 16-bit words fit 32 bits");
+
+struct CombWalk {
+    unsigned rows, cols;          // of the plane, cols in samples
+    unsigned pieces, units;       // 16-byte pieces of a row (the last one may be ragged); pieces * bands
+};
+
+template <typename S> struct CombPiece {
+    unsigned u[8];
+    __device__ __forceinline__ CombPiece() {}
+    __device__ __forceinline__ explicit CombPiece(i32x4 v) {
+        const unsigned w[4] = {(unsigned)v.x, (unsigned)v.y, (unsigned)v.z, (unsigned)v.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (sizeof(S) == 1)
+                u[2 * i] = w[i] & 0x00ff00ffu, u[2 * i + 1] = (w[i] >> 8) & 0x00ff00ffu;
+            else
+                u[2 * i] = w[i] & 0xffffu, u[2 * i + 1] = w[i] >> 16;
+        }
+    }
+    // s = the row above + the row below
+    __device__ __forceinline__ CombPiece plus(const CombPiece &o) const {
+        CombPiece s;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) s.u[i] = u[i] + o.u[i];
+        return s;
+    }
+    // the sum over the piece of |s - 2 r|, *this = s
+    __device__ __forceinline__ unsigned comb(const CombPiece &r) const {
+        unsigned e = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const unsigned twice = r.u[i] << 1;
+#if __has_builtin(__builtin_amdgcn_sad_u16)
+            if (sizeof(S) == 1) {
+                e = __builtin_amdgcn_sad_u16(u[i], twice, e);
+                continue;
+            }
+#else
+            if (sizeof(S) == 1) {
+                const unsigned a = u[i] & 0xffffu, b = twice & 0xffffu, c = u[i] >> 16, d = twice >> 16;
+                e += (a > b ? a - b : b - a) + (c > d ? c - d : d - c);
+                continue;
+            }
+#endif
+            e += u[i] > twice ? u[i] - twice : twice - u[i];
+        }
+        return e;
+    }
+};
+
+// `count` samples at `at` as the 16 bytes of a piece, the samples past them 0
+template <typename S>
+__device__ __forceinline__ i32x4 comb_load(const unsigned char *at, unsigned count) {
+    constexpr unsigned V = 16 / sizeof(S), PER = 4 / sizeof(S);
+    if ((count == V && (reinterpret_cast<size_t>(at) & 15) == 0)) return *reinterpret_cast<const i32x4 *>(at);
+    const S *s = reinterpret_cast<const S *>(at);
+    unsigned w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (unsigned i = 0; i < V; ++i)
+        if (i < count) w[i / PER] |= (unsigned)s[i] << (8 * sizeof(S) * (i % PER));
+    i32x4 v;
+    v.x = (int)w[0], v.y = (int)w[1], v.z = (int)w[2], v.w = (int)w[3];
+    return v;
+}
+
+// One lane's band: rows y0 .. y0 + COMB_BAND - 1 (up to rows - 2) of piece k.  a0, a1, d take the band's share of A0, A1, D.
+// y0 is odd: row y0 + j is even iff j is odd.  A0 takes E_p of the even rows and E_n of the odd ones, A1 the other two.
+template <typename S>
+__device__ __forceinline__ void comb_row(unsigned j, const CombPiece<S> &up, const CombPiece<S> &mid, const CombPiece<S> &down, const CombPiece<S> &rp,
+                                         const CombPiece<S> &rn, unsigned &a0, unsigned &a1, unsigned &d) {
+    const CombPiece<S> s = up.plus(down);
+    const unsigned ep = s.comb(rp), en = s.comb(rn);
+    a0 += (j & 1u) ? ep : en;
+    a1 += (j & 1u) ? en : ep;
+    d += s.comb(mid);
+}
+
+// a whole band of whole, aligned pieces: all 3 COMB_BAND + 2 loads first, none guarded
+template <typename S>
+__device__ __forceinline__ void comb_band_whole(const unsigned char *pp, const unsigned char *pc, const unsigned char *pn, long long row, unsigned y0,
+                                                unsigned k, unsigned &a0, unsigned &a1, unsigned &d) {
+    const long long o = (long long)(y0 - 1) * row + 16ll * k;
+    i32x4 vc[COMB_BAND + 2], vp[COMB_BAND], vn[COMB_BAND];
+#pragma unroll
+    for (int j = 0; j < COMB_BAND + 2; ++j) vc[j] = *reinterpret_cast<const i32x4 *>(pc + o + j * row);
+#pragma unroll
+    for (int j = 0; j < COMB_BAND; ++j) {
+        vp[j] = *reinterpret_cast<const i32x4 *>(pp + o + (j + 1) * row);
+        vn[j] = *reinterpret_cast<const i32x4 *>(pn + o + (j + 1) * row);
+    }
+    __builtin_amdgcn_sched_barrier(0);          // the scheduler otherwise sinks the loads between the sums, three or four in flight
+    CombPiece<S> up(vc[0]), mid(vc[1]);
+#pragma unroll
+    for (int j = 0; j < COMB_BAND; ++j) {
+        const CombPiece<S> down(vc[j + 2]);
+        comb_row<S>((unsigned)j, up, mid, down, CombPiece<S>(vp[j]), CombPiece<S>(vn[j]), a0, a1, d);
+        up = mid, mid = down;
+    }
+}
+
+// any other band, row by row: its pieces may be ragged or off a 16-byte boundary, and it may end at row rows - 2
+template <typename S>
+__device__ __forceinline__ void comb_band_guarded(const unsigned char *pp, const unsigned char *pc, const unsigned char *pn, long long row,
+                                                  unsigned y0, unsigned k, const CombWalk &g, unsigned &a0, unsigned &a1, unsigned &d) {
+    constexpr unsigned V = 16 / sizeof(S);
+    const unsigned count = min(V, g.cols - k * V);
+    const auto piece = [&](const unsigned char *plane, unsigned y) {
+        return CombPiece<S>(comb_load<S>(plane + (long long)y * row + 16ll * k, count));
+    };
+    CombPiece<S> up = piece(pc, y0 - 1), mid = piece(pc, y0);
+#pragma unroll 1
+    for (unsigned j = 0; j < (unsigned)COMB_BAND && y0 + j + 1 < g.rows; ++j) {          // the last row with a row below it is rows - 2
+        const CombPiece<S> down = piece(pc, y0 + j + 1);
+        comb_row<S>(j, up, mid, down, piece(pp, y0 + j), piece(pn, y0 + j), a0, a1, d);
+        up = mid, mid = down;
+    }
+}
+
+template <typename S>          // the sample: unsigned char, or unsigned short (all 16 bits count)
+__global__ __launch_bounds__(LANES) void field_order_sums_kernel(const unsigned char *p, const unsigned char *c, const unsigned char *nx,
+                                                                 long long stride_p, long long stride_c, long long stride_n, CombWalk g,
+                                                                 unsigned long long *sums) {          // p, c, nx may alias
+    const int n = blockIdx.y;
+    const unsigned char *pp = p + n * stride_p, *pc = c + n * stride_c, *pn = nx + n * stride_n;
+    const long long row = (long long)g.cols * (long long)sizeof(S);
+    const unsigned id = blockIdx.x * (unsigned)LANES + threadIdx.x;
+    unsigned a0 = 0, a1 = 0, d = 0;
+    if (id < g.units) {
+        const unsigned band = id / g.pieces, k = id - band * g.pieces, y0 = 1u + band * (unsigned)COMB_BAND;
+        const bool even = ((reinterpret_cast<size_t>(pp) | reinterpret_cast<size_t>(pc) | reinterpret_cast<size_t>(pn) | (size_t)row) & 15) == 0;
+        if (even && y0 + (unsigned)COMB_BAND < g.rows)          // rows y0 - 1 .. y0 + COMB_BAND all exist
+            comb_band_whole<S>(pp, pc, pn, row, y0, k, a0, a1, d);
+        else
+            comb_band_guarded<S>(pp, pc, pn, row, y0, k, g, a0, a1, d);
+    }
+    __shared__ unsigned partial[3][LANES / 64];
+#pragma unroll
+    for (int x = 32; x > 0; x >>= 1) a0 += __shfl_xor(a0, x), a1 += __shfl_xor(a1, x), d += __shfl_xor(d, x);
+    if ((threadIdx.x & 63) == 0) partial[0][threadIdx.x >> 6] = a0, partial[1][threadIdx.x >> 6] = a1, partial[2][threadIdx.x >> 6] = d;
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        unsigned t = 0;
+#pragma unroll
+        for (int w = 0; w < LANES / 64; ++w) t += partial[threadIdx.x][w];
+        atomicAdd(&sums[3 * n + threadIdx.x], (unsigned long long)t);
     }
 }
 
@@ -1586,7 +1760,7 @@ extern "C" int ssm_frames_accumulate_hdr_weighted_fwd(ssm_view src, ssm_view acc
 
 
 // ---- the pair entry points: two payloads in, sums or a third payload out -------------------------------------------------------------
-// ssm_luma_sad_fwd, ssm_field_diff_fwd, ssm_plane_sse_fwd, ssm_plane_ssim_fwd, ssm_block_sad_fwd and ssm_payload_mix_fwd refuse in one order: pair_given (pointers, N), the
+// ssm_luma_sad_fwd, ssm_field_diff_fwd, ssm_field_order_sums_fwd (three operands: check_triple), ssm_plane_sse_fwd, ssm_plane_ssim_fwd, ssm_block_sad_fwd and ssm_payload_mix_fwd refuse in one order: pair_given (pointers, N), the
 // entry's own sizes, check_pair (strides, alignment), what only that entry asks, grid_fits - and only then queue anything: a refused call
 // queues nothing, not even the clear.
 struct PairEntry {
@@ -1684,6 +1858,48 @@ extern "C" int ssm_field_diff_fwd(const void *a, const void *b, long long stride
         SSM_LAUNCH(field_diff_kernel<Lane>, dim3((unsigned)groups, N), dim3(LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b, g, sums);
     });
     return ssm::check_launch("ssm_field_diff_fwd");
+}
+
+// Three operands that are only read: check_pair's questions in its order and words, asked of p, c and n.
+static int check_triple(const PairEntry &k, const void *p, const void *c, const void *n, long long stride_p, long long stride_c,
+                        long long stride_n, int sample_bytes, const void *sums) {
+    const char *name = k.name;
+    const auto reaches = [&](long long s) { return s == 0 || std::llabs(s) >= k.unit_bytes; };
+    SSM_REQUIRE(reaches(stride_p) && reaches(stride_c) && reaches(stride_n),
+                "%s: strides %lld (p), %lld (c), %lld (n) neither 0 nor at least the %s's %lld bytes", name, stride_p, stride_c, stride_n, k.unit,
+                k.unit_bytes);
+    if (sample_bytes == 2) {
+        const auto odd = [](const void *q) { return reinterpret_cast<size_t>(q) % 2 != 0; };
+        SSM_REQUIRE(!odd(p) && !odd(c) && !odd(n), "%s: a payload of 2-byte samples (p, c or n) is not 2-byte aligned", name);
+        SSM_REQUIRE(stride_p % 2 == 0 && stride_c % 2 == 0 && stride_n % 2 == 0,
+                    "%s: strides %lld (p), %lld (c), %lld (n) of 2-byte samples must be even", name, stride_p, stride_c, stride_n);
+    }
+    SSM_REQUIRE(reinterpret_cast<size_t>(sums) % 8 == 0, "%s: sums is not 8-byte aligned", name);
+    return SSM_OK;
+}
+
+extern "C" int ssm_field_order_sums_fwd(const void *p, const void *c, const void *n, long long stride_p, long long stride_c, long long stride_n,
+                                        int N, int H, int W, int sample_bytes, unsigned long long *sums, void *stream) {
+    SSM_REQUIRE(p, "field_order_sums: null pointer");
+    if (const int e = pair_given("field_order_sums", c, n, sums, N)) return e;
+    SSM_REQUIRE(H > 0 && W > 0, "field_order_sums: bad plane size %dx%d", H, W);
+    SSM_REQUIRE(sample_bytes == 1 || sample_bytes == 2, "field_order_sums: sample_bytes %d not in {1, 2}", sample_bytes);
+    const long long row = (long long)W * sample_bytes, pieces = (row + 15) / 16;
+    const long long bands = H < 3 ? 0 : (H - 2 + COMB_BAND - 1) / COMB_BAND, units = pieces * bands;
+    const PairEntry k = {"field_order_sums", "plane", row * H};
+    if (const int e = check_triple(k, p, c, n, stride_p, stride_c, stride_n, sample_bytes, sums)) return e;
+    if (const int e = grid_fits(k, pieces * H)) return e;          // a unit's index, and the last workgroup's past the plane, fit 32 bits
+    if (const int e = clear_sums(k.name, sums, 3 * (size_t)N, stream)) return e;
+    if (units == 0) return SSM_OK;          // H < 3: no row has a row above and a row below, three zeros
+    const CombWalk g = {(unsigned)H, (unsigned)W, (unsigned)pieces, (unsigned)units};
+    const long long groups = (units + LANES - 1) / LANES;
+    const unsigned char *pp = static_cast<const unsigned char *>(p), *pc = static_cast<const unsigned char *>(c),
+                        *pn = static_cast<const unsigned char *>(n);
+    with_sample(sample_bytes, [&](auto s) {
+        SSM_LAUNCH(field_order_sums_kernel<decltype(s)>, dim3((unsigned)groups, N), dim3(LANES), 0, (hipStream_t)stream, pp, pc, pn, stride_p,
+                   stride_c, stride_n, g, sums);
+    });
+    return ssm::check_launch("ssm_field_order_sums_fwd");
 }
 
 extern "C" int ssm_plane_sse_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int layout,

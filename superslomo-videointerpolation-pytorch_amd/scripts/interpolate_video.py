@@ -92,6 +92,21 @@ under 32 samples in a direction, the run is the one without the option, byte for
 lines outside the rectangle goes to --log and changes nothing: a rectangle that changes inside a clip, coloured bars and re-planning are
 out of scope.  It goes with --upsample_rate, --slowmo, --fps, --speed, --scene_cut, --matrix (whose default stays that of the FRAME's
 height), --range, --flow_scale, --tile and --detelecine (which runs first), not with --shutter, --deinterlace or --dedup: chain two runs.
+
+--field_probe [P]: the field order is looked for in the data.  `ffmpeg -f yuv4mpegpipe` writes `Ip` for interlaced material whose order it
+does not know, and nothing refuses a wrong tff / bff: the fields are then woven in the wrong temporal order and every second output steps
+back in time.  Per frame of the first P (default 48) the luma rows are compared with the mean of their two neighbours, in the frame
+before, the frame after and the frame itself (three exact sums A0, A1, D on the GPU, ssm_field_order_sums_fwd); a frame is top field
+first when 25 A0 > 26 A1, bottom field first when 25 A1 > 26 A0, progressive in motion when twice the smaller exceeds 3 D, else
+undetermined, and the verdict is the kind of more than half of the determined frames (ssm_amd.video.FieldVerdict).  With --deinterlace
+auto and a header that says Ip or I? the verdict is the run's field order; a verdict of progressive or none is refused before anything is
+written, with the four counts, and asks for tff or bff.  With an It / Ib header, and with --deinterlace tff|bff, the order is what it is
+without the option and a verdict that contradicts it is a warning in --log that changes nothing.  Without --deinterlace it is a report:
+the clip runs as it does without the option, and a clip that looks interlaced gets one line in --log that names --deinterlace tff|bff.
+The ratios 26/25 and 3/2 are conventions in the spirit of ffmpeg's idet, not its construction - nothing claims its decisions frame for
+frame, ffmpeg is not compared - and not measured on noisy or compressed footage; a hard-edged shape that moves by whole rows can read as
+bottom field first.  Frames behind the probe are not watched; Im, a per-frame order and chroma are out of scope.  Not with --detelecine
+(a telecined clip is a mixture by construction) or a recurrent model.
 """
 import argparse
 import configparser
@@ -181,7 +196,13 @@ def getargs(argv=None):
                              "1/64, of a line: conventions); W:H:X:Y gives it, in the order ffmpeg's cropdetect prints. Default: off.")
     parser.add_argument("--active_probe", type=_named(V.parse_active_probe), default=V.ACTIVE_PROBE, metavar="P",
                         help="With --active auto: the frames the rectangle is decided on. Default 48.")
+    parser.add_argument("--field_probe", type=_named(V.parse_field_probe), nargs="?", const=V.FIELD_PROBE, default=None, metavar="P",
+                        help="Look for the field order in the first P frames (default 48; comb sums on the GPU). With --deinterlace auto and a "
+                             "header that says Ip or I? the verdict is the run's order; else a warning or a report. Default: off.")
     args = parser.parse_args(argv)
+    if args.field_probe is not None and args.detelecine:
+        parser.error("--field_probe does not go together with --detelecine: a telecined clip is a mixture of progressive and combed frames by "
+                     "construction, and pulldown removal finds its field order itself")
     if args.active is not None:
         for flag, given in (("--shutter", args.shutter is not None), ("--deinterlace", args.deinterlace is not None),
                             ("--dedup", args.dedup is not None)):
@@ -242,14 +263,22 @@ def main(argv=None, model=None):
                              flow_scale=args.flow_scale, tile=args.tile, halo=args.halo, blend=args.blend, target_rate=args.fps, speed=args.speed,
                              shutter=args.shutter, shutter_samples=args.shutter_samples, scene_cut=args.scene_cut,
                              shutter_light=args.shutter_light, shutter_window=args.shutter_window, deinterlace=args.deinterlace, dedup=args.dedup, dedup_max=args.dedup_max,
-                             active=args.active, active_probe=args.active_probe)
+                             active=args.active, active_probe=args.active_probe, field_probe=args.field_probe)
     with V.Y4MReader(args.input, extended=True, interlaced=args.deinterlace is not None or args.detelecine) as reader:
         if args.detelecine:
             log.info("[%s] detelecine: %d:%d frames/s in, film at %d:%d", args.expt, *reader.rate, *V.detelecine_rate(reader.rate))
             reader = V.TelecineSource(reader, next(model.parameters()).device)
+        if args.field_probe is not None:          # ahead of the writer: a refused verdict leaves no output behind
+            reader = vi.probe_fields(reader)
+            log.info("[%s] %s", args.expt, vi.field_probe.note)
+            if vi.field_probe.warning is not None:
+                log.warning("[%s] %s", args.expt, vi.field_probe.warning)
+            if vi.field_probe.advice is not None:
+                log.info("[%s] %s", args.expt, vi.field_probe.advice)
         if args.deinterlace is not None:
             rate = V.output_rate(reader.rate, 2)
-            log.info("[%s] deinterlace: %s, fields as frames", args.expt, V.field_order(args.deinterlace, reader.interlace))
+            order = vi.field_probe.order if args.field_probe is not None else V.field_order(args.deinterlace, reader.interlace)
+            log.info("[%s] deinterlace: %s, fields as frames", args.expt, order)
         elif timed:
             rate = args.fps or reader.rate
             tl = vi.timeline(reader.rate)

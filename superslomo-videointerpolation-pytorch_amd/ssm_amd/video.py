@@ -37,6 +37,10 @@
   weave_fields_host       woven from kept fields and synthesised ones or integer line averages - the numpy definitions ssm_fields_split_fwd
   / field_outputs         and ssm_fields_weave_fwd (fields_split, fields_weave) are held to bit for bit; which field is which time under
                           tff / bff and which pairs run - VideoInterpolator(deinterlace=): 2n progressive frames of an n-frame clip (_run_fields)
+  field_order_sums_host / interlaced clips, the field order from the data: per frame the comb sums A0, A1, D of its luma plane against the frame
+  field_order_sums /      before and the frame after, by numpy and by ssm_field_order_sums_fwd; the kind of a frame (field_kind) and the verdict
+  FieldVerdict /          of a probe in Python ints; the reader that probes and replays in front of the loop - VideoInterpolator(field_probe=):
+  FieldOrderSource        the order of a deinterlace="auto" run whose header says Ip or I?, a warning or a report everywhere else
   telecine_host /         film in 3:2 pulldown: the pulldown and its removal in numpy, the per-field luma differences by numpy and by
   detelecine_host /       ssm_field_diff_fwd, the cadence decision from those sums in Python ints (Cadence), and the reader that undoes the
   field_diff / Cadence    pulldown in front of the loop - TelecineSource(reader, dev): downstream sees the film's frames as a progressive clip at
@@ -73,7 +77,8 @@ of repeated frames: timestamps (timecode files), dropping repeats instead of rep
 shutter, scene_cut or deinterlace (chain two runs), a scene cut on the frame after a run, comparison against a run's first frame,
 agreement with ffmpeg's mpdecimate frame for frame, noisy or compressed footage; of letterboxed clips: a rectangle that changes inside a
 clip, coloured bars, re-planning when a later frame exceeds the rectangle, active together with shutter, deinterlace or dedup (chain two
-runs), noisy or compressed bars.
+runs), noisy or compressed bars; of the field probe: watching frames behind the probe, Im, a per-frame order, detection on chroma, noisy
+or compressed footage (every clip it was tried on is synthetic), agreement with ffmpeg's idet frame for frame.
 """
 import ctypes
 import functools
@@ -81,6 +86,7 @@ import queue
 import re
 import sys
 import threading
+from collections import namedtuple
 from fractions import Fraction
 
 import numpy as np
@@ -742,6 +748,181 @@ def field_outputs(n, order):
         inner = 0 < f < 2 * n - 1
         out.append((field_of(f, order), field_of(f - 1, order) if inner else None, field_of(f + 1, order) if inner else None))
     return out
+
+
+# ---- interlaced clips: the field order from the data --------------------------------------------------------------------------------------
+# The definition is in include/ssm_hip.h and DESIGN 3.12: per frame the comb sums A0, A1, D of its luma plane against the frame before and
+# the frame after, the kind of the frame from them, the verdict of a probe from the kinds.  The ratios are conventions in the spirit of
+# ffmpeg's idet, not its construction: nothing claims its decisions frame for frame, and nothing was measured on compressed footage.
+FIELD_PROBE = 48                   # frames the field order is decided on
+FIELD_KINDS = "TBPU"               # top field first, bottom field first, progressive in motion, undetermined
+
+
+def parse_field_probe(value):
+    """The number of frames the field order is decided on: a whole number of at least 1, or its text."""
+    try:
+        n = int(value.strip()) if isinstance(value, str) else value
+        if isinstance(n, bool) or int(n) != n or n < 1:
+            raise ValueError
+    except (ValueError, TypeError):
+        raise ValueError("field_probe, the frames the field order is decided on, is a whole number of at least 1 (got %r)" % (value,)) from None
+    return int(n)
+
+
+def field_order_sums_host(prev, cur, nxt, h, w, bits=8):
+    """Yardstick of ssm_field_order_sums_fwd: payloads prev, cur, nxt [N, at least h * w samples] uint8 (numpy; any of them may have a
+    single row) -> uint64 [N, 3], out[n] = (A0, A1, D) of the luma planes, exact; with bits > 8 over the 16-bit words.  h < 3: zeros."""
+    p, c, n = (_luma_of(x, h, w, bits) for x in (prev, cur, nxt))
+    count = max(p.shape[0], c.shape[0], n.shape[0])
+    p, c, n = (np.broadcast_to(x, (count, h, w)) for x in (p, c, n))
+    if h < 3:
+        return np.zeros((count, 3), np.uint64)
+    s = c[:, :-2] + c[:, 2:]                                                              # rows y = 1 .. h - 2
+    ep, en, ec = (np.abs(s - 2 * r[:, 1:-1]).sum(axis=2) for r in (p, n, c))          # [N, h - 2], row y at index y - 1
+    even, odd = slice(1, None, 2), slice(0, None, 2)
+    a0 = ep[:, even].sum(axis=1) + en[:, odd].sum(axis=1)
+    a1 = ep[:, odd].sum(axis=1) + en[:, even].sum(axis=1)
+    return np.stack([a0, a1, ec.sum(axis=1)], axis=1).astype(np.uint64)
+
+
+def field_kind(a0, a1, d):
+    """The kind of a frame from its comb sums, in integers: "T" if 25 A0 > 26 A1, else "B" if 25 A1 > 26 A0, else "P" (progressive, in
+    motion) if 2 min(A0, A1) > 3 D, else "U"."""
+    a0, a1, d = int(a0), int(a1), int(d)
+    if 25 * a0 > 26 * a1:
+        return "T"
+    if 25 * a1 > 26 * a0:
+        return "B"
+    return "P" if 2 * min(a0, a1) > 3 * d else "U"
+
+
+class FieldVerdict:
+    """The decision over a probe: `kinds`, the kinds of its INNER frames 1 .. m - 2 (a frame needs the one before and the one after) as a
+    string over FIELD_KINDS; `counts` = (nT, nB, nP, nU); `verdict` = "tff" if 2 nT > d, "bff" if 2 nB > d, "progressive" if 2 nP > d with
+    d = nT + nB + nP, else None - also for a probe of fewer than 3 frames, which has no inner frame; `note`, one line with the counts."""
+    NAMES = (("T", "tff"), ("B", "bff"), ("P", "progressive"))
+
+    def __init__(self, kinds):
+        self.kinds = "".join(kinds)
+        assert set(self.kinds) <= set(FIELD_KINDS)
+        self.counts = tuple(self.kinds.count(k) for k in FIELD_KINDS)
+        d = sum(self.counts[:3])
+        self.verdict = None
+        for (_, name), n in zip(self.NAMES, self.counts):
+            if 2 * n > d:
+                self.verdict = name
+        self.note = "field probe: %d inner frames, %d top field first, %d bottom field first, %d progressive, %d undetermined: %s" % (
+            (len(self.kinds),) + self.counts + ("no verdict" if self.verdict is None else self.verdict,))
+
+    @classmethod
+    def of_sums(cls, sums):
+        """From the [m - 2, 3] comb sums of a probe's inner frames."""
+        return cls(field_kind(*row) for row in np.asarray(sums).reshape(-1, 3).tolist())
+
+
+def field_order_sums(prev, cur, nxt, h, w, bits=8, out=None):
+    """ssm_field_order_sums_fwd on payloads: three [N, at least h * w samples] uint8 device tensors (unit stride within a row, any row
+    stride: frames n - 1, n, n + 1 of one buffer are fine) -> int64 [N, 3] on the device (into `out` if given): per frame (A0, A1, D), the
+    comb sums of `cur` against `prev` and `nxt`.  The words are unsigned and below 2^63: read them on the host as numpy uint64."""
+    sb = sample_bytes(bits)
+    n, out, sp, sc = _pair_operands(prev, cur, h * w * sb, "h * w samples", out, (3,))
+    _, _, _, sn = _pair_operands(cur, nxt, h * w * sb, "h * w samples", out, (3,))
+    hb.check(hb.load().ssm_field_order_sums_fwd(prev.data_ptr(), cur.data_ptr(), nxt.data_ptr(), sp, sc, sn, n, h, w, sb, out.data_ptr(),
+                                                hb.stream_ptr()))
+    return out
+
+
+class FieldOrderSource:
+    """A reader that probes the field order of a clip: wraps a Y4MReader (or anything with its attributes) and hands out its frames as they
+    are.  decide() reads the first `probe` frames (or the whole clip if it is shorter) into a host buffer, takes the comb sums of the inner
+    ones on the GPU, and sets `kinds`, `counts`, `verdict` ("tff", "bff", "progressive" or None: FieldVerdict) and `note`, one log line with
+    the four counts; then the probed frames are replayed, and the frames behind the probe come straight from the reader: nothing watches
+    them.
+
+    A chunk is frames_per_chunk new frames behind the two frames before them, in one pinned buffer and one device buffer, made once.  Per
+    chunk, on a stream of its own: one H2D, one ssm_field_order_sums_fwd - the frame before, the frame and the frame after are rows
+    b - 1, b, b + 1 of the device buffer, one pointer each and one stride - one D2H of the sums, one event wait.  The bytes handed out are
+    the reader's; neither they nor the verdict depend on frames_per_chunk."""
+
+    def __init__(self, reader, dev, probe=FIELD_PROBE, frames_per_chunk=8):
+        assert frames_per_chunk >= 1
+        self.reader, self.dev = reader, torch.device(dev)
+        if self.dev.type != "cuda":
+            raise RuntimeError("the field probe takes its comb sums on the GPU (the HIP path has no CPU fallback)")
+        for name in ("width", "height", "siting", "chroma", "color_range", "aspect", "xtags", "frame_bytes", "rate"):
+            setattr(self, name, getattr(reader, name))
+        self.bits, self.extended = getattr(reader, "bits", 8), getattr(reader, "extended", False)
+        self.sample_bytes = sample_bytes(self.bits)
+        self.interlace = getattr(reader, "interlace", "p")
+        self.field_order, self.field_bytes = getattr(reader, "field_order", None), getattr(reader, "field_bytes", None)
+        self.probe, self.frames_read = parse_field_probe(probe), 0
+        self.kinds = self.counts = self.verdict = self.note = None
+        self._rows, self._decided, self._replay, self._eof = frames_per_chunk, False, [], False
+
+    def _sums(self, frames):
+        """The comb sums of frames 1 .. m - 2 of `frames` [m, frame_bytes]: uint64 [m - 2, 3]."""
+        m, c, h, w = frames.shape[0], self._rows, self.height, self.width
+        host = torch.empty(c + 2, self.frame_bytes, dtype=torch.uint8).pin_memory()
+        dev = torch.empty(c + 2, self.frame_bytes, dtype=torch.uint8, device=self.dev)
+        dev_sums = torch.empty(c, 3, dtype=torch.int64, device=self.dev)
+        host_sums = torch.empty(c, 3, dtype=torch.int64).pin_memory()
+        stream, event = torch.cuda.Stream(self.dev), torch.cuda.Event()
+        out = np.zeros((max(m - 2, 0), 3), np.uint64)
+        for at in range(0, m, c):          # the chunk's new frames are at .. at + k - 1; it closes the inner frames whose next frame is new
+            k, lo = min(c, m - at), max(0, at - 2)
+            first, last = max(1, at - 1), at + k - 2
+            if last < first:
+                continue
+            cnt = last - first + 1
+            host.numpy()[:at + k - lo] = frames[lo:at + k]
+            b = first - lo
+            with torch.cuda.stream(stream):
+                dev[:at + k - lo].copy_(host[:at + k - lo], non_blocking=True)
+                field_order_sums(dev[b - 1:b - 1 + cnt], dev[b:b + cnt], dev[b + 1:b + 1 + cnt], h, w, self.bits, out=dev_sums[:cnt])
+                host_sums[:cnt].copy_(dev_sums[:cnt], non_blocking=True)
+                event.record()
+            event.synchronize()
+            out[first - 1:last] = host_sums.numpy().view(np.uint64)[:cnt]
+        return out
+
+    def decide(self):
+        """The verdict of the probe: "tff", "bff", "progressive" or None.  Reads the probe frames on the first call."""
+        if self._decided:
+            return self.verdict
+        self._decided = True
+        probe = np.empty((self.probe, self.frame_bytes), np.uint8)
+        n = 0
+        while n < self.probe and self.reader.read_frame_into(probe[n]):
+            n += 1
+        self._eof = n < self.probe
+        self.sums = self._sums(probe[:n])
+        v = FieldVerdict.of_sums(self.sums)
+        self.kinds, self.counts, self.verdict, self.note = v.kinds, v.counts, v.verdict, v.note
+        self._replay = [probe[i] for i in range(n)]
+        return self.verdict
+
+    def read_frame_into(self, buf):
+        """The next frame's payload into `buf`; False at the end of the clip."""
+        self.decide()
+        out = np.frombuffer(memoryview(buf).cast("B"), np.uint8)
+        if out.size != self.frame_bytes:
+            raise ValueError("buffer of %d bytes for frames of %d" % (out.size, self.frame_bytes))
+        if self._replay:
+            out[:] = self._replay.pop(0)
+        elif self._eof or not self.reader.read_frame_into(out):
+            self._eof = True
+            return False
+        self.frames_read += 1
+        return True
+
+    def close(self):
+        self.reader.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 # ---- YUV4MPEG2 ---------------------------------------------------------------------------------------------------------------------
@@ -2420,6 +2601,9 @@ def stream_buffers(n, dev, fb, rows_in, rows_out, n_t=None, fb_out=None):
     return dev_in, dev_out, dev_t, [torch.cuda.Event() for _ in range(n)]
 
 
+FieldProbe = namedtuple("FieldProbe", "verdict counts kinds order note warning advice")          # VideoInterpolator.field_probe
+
+
 class VideoInterpolator:
     """reader -> (upsample_rate - 1) frames between every two input frames -> writer, streamed; or, with target_rate / speed, the frames
     of a Timeline (any output rate, any speed: _run_timeline).
@@ -2438,7 +2622,7 @@ class VideoInterpolator:
     def __init__(self, model, cfg, upsample_rate=None, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
                  tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8, scene_cut=None,
                  shutter_light="coded", deinterlace=None, dedup=None, dedup_max=DEDUP_MAX, active=None, active_probe=ACTIVE_PROBE,
-                 shutter_window="box"):
+                 shutter_window="box", field_probe=None):
         """target_rate = (num, den) and / or speed (a Fraction, or what Fraction() takes; 1/4 is four times slower): the output follows
         Timeline(speed * input rate / target_rate) instead of the fixed grid of upsample_rate, which is then not used (see
         _run_timeline); with both None nothing changes.  flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
@@ -2502,7 +2686,20 @@ class VideoInterpolator:
         its construction, FRAC = 1/64 this module's own: conventions, not backed by a measurement on compressed footage.  It goes with
         upsample_rate, target_rate, speed, scene_cut, matrix, color_range, flow_scale and tile; not with shutter (every output comes from
         the accumulator, none has one input frame's bars), deinterlace, dedup or a recurrent model (chain two runs).  None: every mode
-        as it is, launch for launch."""
+        as it is, launch for launch.
+        field_probe (True: FIELD_PROBE = 48 frames; or P, parse_field_probe): the field order is looked for in the data.  A
+        FieldOrderSource in front of the loop takes the comb sums of the first P frames on the GPU (ssm_field_order_sums_fwd) and decides
+        "tff", "bff", "progressive" or nothing (FieldVerdict).  With deinterlace="auto" and a header that says Ip or I? the run takes the
+        verdict as its field order, and refuses by name, before anything is written, a verdict of "progressive" or none - the message
+        carries the four counts and says to give "tff" or "bff".  With a header that says It or Ib, and with "tff" / "bff", the order is
+        what it is without the option, and a verdict that contradicts it is a warning that changes nothing.  Without deinterlace it is a
+        report, and the clip runs as it does without the option.  After run() (or probe_fields()): `field_probe`, a FieldProbe of
+        verdict, counts (nT, nB, nP, nU), kinds, order (the order in use, None without deinterlace), note (one line with the counts),
+        warning (the contradiction, or None) and advice (a report-only run on a clip that looks interlaced: the line that names
+        deinterlace="tff" / "bff"; else None).  The ratios are conventions in the spirit of ffmpeg's idet, not its construction, and not
+        backed by a measurement on noisy or compressed footage.  Frames behind the probe are not watched.  Not with a recurrent model,
+        and not on a TelecineSource: a telecined clip is a mixture of both kinds of frame by construction.  None: every mode as it is,
+        launch for launch."""
         from .coarse import check_scale
         from .tiles import check_args
         self.flow_scale = check_scale(flow_scale)
@@ -2534,6 +2731,11 @@ class VideoInterpolator:
                 if given:
                     raise ValueError("active together with %s is not available: the picture is cut out and the bars are pasted back around "
                                      "frames synthesised between two input frames, and nothing else; chain two runs" % name)
+        self.field_probe_option = None if field_probe is None or field_probe is False else (
+            FIELD_PROBE if field_probe is True else parse_field_probe(field_probe))
+        self.field_probe, self._probed, self._probed_order = None, None, None
+        if self.field_probe_option is not None and getattr(model, "recurrent", False):
+            raise ValueError("field_probe together with a recurrent model is not available")
         self.deinterlace = parse_deinterlace(deinterlace)
         if self.deinterlace is not None:
             for name, given in (("upsample_rate", upsample_rate is not None), ("target_rate", target_rate is not None), ("speed", speed is not None),
@@ -2670,11 +2872,48 @@ class VideoInterpolator:
         if pairs:
             carried[:] = pairs[-1][2]
 
+    def probe_fields(self, reader):
+        """The reader behind a FieldOrderSource that has decided (the option field_probe), for run(): sets `field_probe` and the field
+        order of a deinterlace="auto" run on a header without one, or refuses it.  run() calls it on a reader that has not been through
+        it; a caller that opens its writer only after the refusals calls it first."""
+        assert self.field_probe_option is not None, "probe_fields is the option field_probe's"
+        if isinstance(reader, TelecineSource):
+            raise ValueError("field_probe together with detelecine is not available: a telecined clip is a mixture of progressive and "
+                             "combed frames by construction, and pulldown removal finds its field order itself")
+        dev = next(self.model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
+        source = FieldOrderSource(reader, dev, self.field_probe_option)
+        verdict = source.decide()
+        order = warning = advice = None
+        self._probed_order = None
+        if self.deinterlace is not None:
+            if self.deinterlace == "auto" and source.interlace not in FIELD_ORDERS:
+                if verdict not in ("tff", "bff"):
+                    raise ValueError("deinterlace=\"auto\" on a header that says I%s takes the field order from the field probe, and the probe "
+                                     "says %s (%s): give deinterlace=\"tff\" or \"bff\""
+                                     % (source.interlace, "the clip is progressive" if verdict == "progressive" else "nothing", source.note))
+                order = self._probed_order = verdict
+            else:
+                order = field_order(self.deinterlace, source.interlace)
+                if verdict is not None and verdict != order:
+                    warning = "field probe: the data says %s, the run is %s as %s says; nothing changes" % (
+                        verdict, order, "the header (I%s)" % source.interlace if self.deinterlace == "auto" else "the option")
+        elif verdict in ("tff", "bff"):
+            advice = "field probe: the clip looks interlaced, %s: --deinterlace %s (deinterlace=\"%s\") writes its fields as frames" % (
+                "top field first" if verdict == "tff" else "bottom field first", verdict, verdict)
+        self.field_probe = FieldProbe(verdict, source.counts, source.kinds, order, source.note, warning, advice)
+        self._probed = source
+        return source
+
     @torch.no_grad()
     def run(self, reader, writer):
         """Returns the number of frames written: (n - 1) * upsample_rate + 1 for n input frames (with target_rate / speed:
         floor((n - 1) / step) + 1; with a shutter: Timeline.n_outputs(n); with deinterlace: 2 n; with dedup the fixed grid's count)."""
         self.cuts, self.repeats, self.active, self.active_note, self.active_excess = [], [], None, None, []
+        if self.field_probe_option is not None and reader is not self._probed:
+            reader = self.probe_fields(reader)
+        self._probed = None          # one run per probe
         if self.active_option is not None:
             dev = next(self.model.parameters()).device
             if dev.type != "cuda":
@@ -2820,7 +3059,7 @@ class VideoInterpolator:
         from .evaluation import t_values
         h, w, bits = clip.h, clip.w, getattr(reader, "bits", 8)
         crange, siting = clip.coding[2:4]
-        order = field_order(self.deinterlace, reader.interlace)
+        order = (self._probed_order if self.field_probe_option is not None else None) or field_order(self.deinterlace, reader.interlace)
         fh, _ = field_dims(h, w, siting)
         matrix = default_matrix(h) if self.matrix is None else self.matrix          # of the frame's height, not the field's
         fclip = Clip(fh, w, siting, matrix, crange, self.cfg, bits, 32 * self.flow_scale, dev=clip.dev)
