@@ -1074,6 +1074,50 @@ int ssm_field_order_sums_fwd(const void *p, const void *c, const void *n, long l
 int ssm_block_sad_fwd(const void *a, const void *b, long long stride_a, long long stride_b, int N, int H, int W, int layout, int sample_bytes,
                       int lo, unsigned long long *out, void *stream);
 
+/* ---- blocks that do not change, of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) -----------------
+ * Definition (ssm_amd.video.static_paste_host is all of it in numpy).  A channel logo, burnt-in subtitles, the static parts of a screen
+ * recording and a locked-off background are the same samples in both frames of a pair; synthesised, they come out re-quantised and pulled by
+ * the flow of what moves beside them, and pulse against the input frames' own bytes.  Everything below is in exact integers.
+ *   blocks    block (bx, by) of a FRAME is the 8 x 8 luma samples at (8 bx, 8 by), bx < W >> 3, by < H >> 3, together with the chroma samples
+ *             under them, in U and in V: 4 x 4 at (4 bx, 4 by) for SSM_YUV_420_*, 8 rows x 4 columns at (4 bx, 8 by) for SSM_YUV_422, 8 x 8
+ *             at (8 bx, 8 by) for SSM_YUV_444.  The trailing W & 7 columns and H & 7 rows, with the chroma under them, belong to no block
+ *             (the rule of the blocks above); a frame with fewer than 8 rows or columns has none.
+ *   measure   for the payloads (a, b) of a pair, d(block) = the sum of |a - b| over the block's luma, U and V samples; with 16-bit words
+ *             all 16 bits count, d <= 192 * 65535 < 2^24.
+ *   test      a block is STATIC in the pair iff d <= lo, lo an integer in 0 .. 2^24 - 1.  lo = 0: the two frames agree on every sample of
+ *             the block.
+ *   action    in every output strictly between the two frames the samples of a static block, luma and chroma, are the LEFT frame's (at
+ *             lo = 0 the right frame's too); every other sample is what the run without the option writes.  Outputs that are input frames
+ *             pass as their own bytes.
+ *   count     per pair the number of static blocks.
+ *   At lo = 0 this is no heuristic: where both neighbours hold the same samples no honest in-between frame differs.  NOT claimed: a block that
+ *   agrees in both frames while something crossed it in between is kept (nothing can tell); seams between kept and synthesised blocks are
+ *   not smoothed; a non-zero lo is the user's number, there is no default - the NUMBER in the spirit of mpdecimate's lo would be 320 at 8
+ *   bits and is not backed by any measurement.
+ * ssm_static_paste_fwd: a + n stride_a and b + n stride_b (strides in BYTES, of either sign; frames n and n + 1 of one buffer are fine; with
+ * N = 1 they name nothing) point at the whole payloads of pair n = 0 .. N-1, H x W frames in `layout` (SSM_YUV_*), as for ssm_block_sad_fwd;
+ * the T outputs of pair n are the payloads at out + (n T + j) stride_out, j < T (with N T = 1 the stride names nothing).  sample_bytes = 1:
+ * bytes; 2: 16-bit little-endian words.  The outputs are read-modify-write: the only samples written are those of static blocks, which take
+ * the samples of a_n; nothing outside the N T payloads is touched, a and b are only read and may alias or overlap each other.
+ *     counts[n] = the number of static blocks of pair n
+ * exact, N 64-bit words on the device, cleared by the entry itself on `stream` (a memset node ahead of the kernel).  A frame without blocks
+ * queues the clear alone.
+ *   A workgroup of 256 lanes owns a strip of 256 blocks of one pair, consecutive in row-major order, and takes them 32 at a time (grid:
+ *   strips, n); 8 neighbouring lanes own a block, lane r of them its luma row r - bytes: one 8-byte load per operand, two v_sad_u8; words: one 16-byte load, four v_sad_u16 -
+ *   and the chroma rows that fall to it: in 4:2:0 one row of 4 samples (U for r < 4, V above), in 4:2:2 row r of U and of V (4 samples), in
+ *   4:4:4 row r of U and of V (8 samples), one load of 4, 8 or 16 bytes each.  A piece whose address does not sit on a boundary of its own
+ *   size (odd widths, a payload at an odd offset) goes sample by sample, decided per piece in the same kernel.  The 8 lane sums are added by
+ *   cross-lane shuffles, which leave d in all 8 lanes; where d <= lo every lane stores the pieces of `a` it loaded into the T outputs, by
+ *   the same rule.  One flag per block, summed over the strip, through shuffles and LDS, then ONE 64-bit vector atomicAdd per workgroup.  Integer adds commute: the
+ *   same words in every run.  Vector stores and vector atomics only; no scratch, no packed fp32.  Reads 2 sample_bytes per sample of the
+ *   blocks, writes T sample_bytes per sample of the static ones.
+ * SSM_E_ARG (nothing is queued), each with its own message and in this order: null pointers; N, then T, outside 1..65535; H or W < 1; a
+ * layout outside SSM_YUV_*; sample_bytes outside {1, 2}; lo >= 2^24; with N > 1 a stride of a or b below the frame's bytes in magnitude; with
+ * N T > 1 a |stride_out| below them; with sample_bytes = 2 an odd address, then an odd stride; `out` overlapping a or b; `counts` not 8-byte
+ * aligned; a frame of more than 2^31 - 1 strips. */
+int ssm_static_paste_fwd(const void *a, const void *b, long long stride_a, long long stride_b, void *out, long long stride_out, int N, int T,
+                         int H, int W, int layout, int sample_bytes, unsigned int lo, unsigned long long *counts, void *stream);
+
 /* ---- letterboxed clips of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) --------------------------
  * Definition (ssm_amd.video: active_counts_host, ActiveArea, cut_window_host and paste_window_host are all of it in numpy and Python ints,
  * ActiveSource the streamed form).  A 2.39:1 picture inside a 16:9 frame leaves bars that hold, at most, a subtitle or a logo.

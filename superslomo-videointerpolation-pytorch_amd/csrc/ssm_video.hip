@@ -46,6 +46,10 @@
 //                            block sum and the number of blocks above `lo`; a workgroup owns 32 x 8 blocks of one plane (PlaneOf), a lane
 //                            one block - eight 8- or 16-byte loads per operand, v_sad_u8 / v_sad_u16 - and ends in one 64-bit atomicMax and
 //                            one 64-bit atomicAdd
+//   static_paste_kernel      blocks that do not change, ssm_static_paste_fwd: |a - b| summed per 8 x 8 block of the FRAME - its luma and the U and V
+//                            samples under it - and where the sum is at most `lo` the block's samples of `a` stored into the T outputs of the
+//                            pair; a workgroup owns 256 blocks, 32 at a time, 8 neighbouring lanes a block, a lane one luma row and its share of the
+//                            chroma rows (one load per piece where its address allows); shuffles, then one 64-bit atomicAdd of the count
 //   payload_mix_kernel       hold-out scoring: the cross-fade (a (den - k) + b k + den / 2) / den of two payloads, the frame-blend baseline;
 //                            exact division by multiply-shift, the span walk's pieces with a 16-byte store in place of the sum
 //   fields_split_kernel /    interlaced clips: N frames -> their 2N fields (even rows of every plane, odd rows), and N fields with
@@ -1158,6 +1162,133 @@ __global__ __launch_bounds__(SAD_LANES) void block_sad_kernel(const unsigned cha
     }
 }
 
+// ---- blocks that do not change: the left frame's samples kept in the outputs of a pair ---------------------------------------------------
+// The definition is in include/ssm_hip.h: block (bx, by) of a FRAME is the 8 x 8 luma samples at (8 bx, 8 by) with the U and V samples under
+// them, d = the sum of |a - b| over all of them; where d <= lo the block's samples of a_n are stored into the T outputs of pair n, and
+// counts[n] is the number of such blocks (ssm_static_paste_fwd).
+// A workgroup owns a strip of PASTE_STEPS x PASTE_BLOCKS = 256 blocks of one pair, consecutive in row-major order, and takes them 32 at a
+// time (one atomic per 256 blocks: the counts of a pair share ONE word, and a workgroup per 32 blocks made 450 adders queue on it at 720p);
+// the 8 lanes of a block are neighbours, lane r of them takes luma row r of the block and the chroma rows that fall to it:
+//   4:2:0   one row of 4 samples: row r & 3 of the 4 x 4 under the block, of U for r < 4 and of V for r >= 4
+//   4:2:2   rows r of the 8 x 4 of U and of V;   4:4:4   rows r of the 8 x 8 of U and of V
+//   rows    a piece (RowPiece) is 4 or 8 samples as 1, 2 or 4 32-bit words: ONE load of its size where its address sits on a boundary of
+//           that size, sample by sample into the same words where not (odd widths, a payload at an odd offset) - decided per piece, in the
+//           same kernel; the store likewise.  The sums are v_sad_u8 / v_sad_u16 on the words either way.  d <= 192 * 65535 < 2^24.
+//   verdict the 8 lane sums by three xor shuffles, which leave d in all 8 lanes: every lane knows its block's verdict and, where it is
+//           static, stores the pieces of `a` that it loaded into the T outputs.  Nothing else is written.
+//   count   one flag per block (its lane 0) through workgroup_add: shuffles, LDS partials, ONE 64-bit vector atomic per workgroup.
+constexpr int PASTE_BLOCKS = LANES / 8, PASTE_STEPS = 8;
+static_assert(192ll * 65535 < (1ll << 24), "a block's sum of absolute word differences over Y, U and V is below 2^24");
+
+template <typename S, int K>          // K 32-bit words of samples S, as they stand in memory
+struct RowPiece {
+    unsigned w[K];
+    static constexpr int PER = 4 / (int)sizeof(S), BITS = 8 * (int)sizeof(S);
+    static __device__ __forceinline__ bool whole(const void *p) { return (reinterpret_cast<size_t>(p) & (size_t)(4 * K - 1)) == 0; }
+    __device__ __forceinline__ void load(const unsigned char *p) {
+        if (whole(p)) {
+            if constexpr (K == 1) {
+                w[0] = *reinterpret_cast<const unsigned *>(p);
+            } else if constexpr (K == 2) {
+                const i32x2 v = *reinterpret_cast<const i32x2 *>(p);
+                w[0] = (unsigned)v.x, w[1] = (unsigned)v.y;
+            } else {
+                const i32x4 v = *reinterpret_cast<const i32x4 *>(p);
+                w[0] = (unsigned)v.x, w[1] = (unsigned)v.y, w[2] = (unsigned)v.z, w[3] = (unsigned)v.w;
+            }
+        } else {
+            const S *s = reinterpret_cast<const S *>(p);
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+                unsigned x = 0;
+#pragma unroll
+                for (int k = 0; k < PER; ++k) x |= (unsigned)s[PER * i + k] << (BITS * k);
+                w[i] = x;
+            }
+        }
+    }
+    __device__ __forceinline__ void store(unsigned char *p) const {
+        if (whole(p)) {
+            if constexpr (K == 1) {
+                *reinterpret_cast<unsigned *>(p) = w[0];
+            } else if constexpr (K == 2) {
+                i32x2 v;
+                v.x = (int)w[0], v.y = (int)w[1];
+                *reinterpret_cast<i32x2 *>(p) = v;
+            } else {
+                i32x4 v;
+                v.x = (int)w[0], v.y = (int)w[1], v.z = (int)w[2], v.w = (int)w[3];
+                *reinterpret_cast<i32x4 *>(p) = v;
+            }
+        } else {
+            S *s = reinterpret_cast<S *>(p);
+#pragma unroll
+            for (int i = 0; i < K; ++i)
+#pragma unroll
+                for (int k = 0; k < PER; ++k) s[PER * i + k] = (S)(w[i] >> (BITS * k));
+        }
+    }
+    template <typename Lane>
+    __device__ __forceinline__ void sad(Lane &acc, const RowPiece &o) const {
+#pragma unroll
+        for (int i = 0; i < K; ++i) acc.words(w[i], o.w[i]);
+    }
+};
+
+template <typename S, int L>          // the sample and the layout (LAY_*)
+__global__ __launch_bounds__(LANES) void static_paste_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
+                                                             unsigned char *out, long long stride_out, int T, int W, int cw, long long luma,
+                                                             long long chroma, unsigned nbx, unsigned blocks, unsigned lo,
+                                                             unsigned long long *counts) {          // a, b may alias; luma, chroma in samples
+    constexpr int SB = (int)sizeof(S);
+    constexpr int CS = L == LAY_444 ? 8 : 4;                     // chroma samples under a block row
+    constexpr int KY = 8 * SB / 4, KC = CS * SB / 4;             // words of a luma piece, of a chroma piece
+    constexpr int NC = L == LAY_420 ? 1 : 2;                     // chroma pieces of a lane
+    const int n = blockIdx.y;
+    const unsigned r = threadIdx.x & 7u;
+    const unsigned char *pa = a + n * stride_a, *pb = b + n * stride_b;
+    unsigned kept = 0;
+    for (int step = 0; step < PASTE_STEPS; ++step) {
+        const unsigned blk = (blockIdx.x * (unsigned)PASTE_STEPS + step) * (unsigned)PASTE_BLOCKS + (threadIdx.x >> 3);
+        const bool live = blk < blocks;          // the same in the 8 lanes of a block
+        RowPiece<S, KY> ya = {}, yb = {};
+        RowPiece<S, KC> ca[NC] = {}, cb[NC] = {};
+        long long oy = 0, oc[NC] = {};           // byte offsets of the lane's pieces in a payload
+        unsigned d = 0;
+        if (live) {          // a block of the frame: its luma rows lie inside H x W, its chroma rows inside the chroma planes
+            const unsigned by = blk / nbx, bx = blk - by * nbx;
+            oy = ((long long)(8 * by + r) * W + 8 * bx) * SB;
+            const long long crow = L == LAY_420 ? 4 * by + (r & 3u) : 8 * by + r;
+#pragma unroll
+            for (int i = 0; i < NC; ++i) {
+                const long long plane = L == LAY_420 ? (long long)(r >> 2) : (long long)i;
+                oc[i] = (luma + plane * chroma + crow * cw + (long long)(CS * bx)) * SB;
+            }
+            ya.load(pa + oy), yb.load(pb + oy);
+#pragma unroll
+            for (int i = 0; i < NC; ++i) ca[i].load(pa + oc[i]), cb[i].load(pb + oc[i]);
+            typename SadRow<S>::Lane acc;
+            ya.sad(acc, yb);
+#pragma unroll
+            for (int i = 0; i < NC; ++i) ca[i].sad(acc, cb[i]);
+            d = acc.sum();
+        }
+#pragma unroll
+        for (int s = 1; s < 8; s <<= 1) d += __shfl_xor(d, s);          // the block's d, in its 8 lanes
+        const bool keep = live && d <= lo;
+        if (keep) {
+            for (int j = 0; j < T; ++j) {
+                unsigned char *po = out + ((long long)n * T + j) * stride_out;
+                ya.store(po + oy);
+#pragma unroll
+                for (int i = 0; i < NC; ++i) ca[i].store(po + oc[i]);
+            }
+        }
+        kept += keep && r == 0 ? 1u : 0u;
+    }
+    workgroup_add(kept, &counts[n]);
+}
+
 // ---- hold-out scoring: the cross-fade of two payloads ---------------------------------------------------------------------------------
 // out_n[i] = (a_n[i] (den - k) + b_n[i] k + (den >> 1)) / den with k = num0 + n num_step, i over the `samples` samples of a row: the
 // frame-blend baseline, rounded half up.  The numerator is below 65535 * 65535 + 32768 < 2^32.  THE DIVISION is the multiply-shift of
@@ -1970,8 +2101,8 @@ extern "C" int ssm_block_sad_fwd(const void *a, const void *b, long long stride_
 }
 
 // first and one-past-last byte address of N rows of `row` bytes, `stride` bytes apart (either sign, or 0)
-static void rows_range(const void *p, long long stride, int N, long long row, long long *lo, long long *hi) {
-    const long long base = (long long)reinterpret_cast<size_t>(p), ext = (long long)(N - 1) * stride;
+static void rows_range(const void *p, long long stride, long long N, long long row, long long *lo, long long *hi) {
+    const long long base = (long long)reinterpret_cast<size_t>(p), ext = (N - 1) * stride;
     *lo = base + (ext < 0 ? ext : 0);
     *hi = base + (ext > 0 ? ext : 0) + row;
 }
@@ -2006,6 +2137,49 @@ extern "C" int ssm_payload_mix_fwd(const void *a, const void *b, long long strid
                    static_cast<unsigned char *>(out), stride_out, samples, num0, num_step, den, d);
     });
     return ssm::check_launch("ssm_payload_mix_fwd");
+}
+
+// ssm_static_paste_fwd refuses in the order of its header section - pointers, N and T, the frame, lo, the strides of a and b, of out, 2-byte
+// alignment, overlap, counts, the grid - and only then queues the clear and, for a frame that has blocks, the one launch.
+extern "C" int ssm_static_paste_fwd(const void *a, const void *b, long long stride_a, long long stride_b, void *out, long long stride_out, int N,
+                                    int T, int H, int W, int layout, int sample_bytes, unsigned int lo, unsigned long long *counts, void *stream) {
+    const char *name = "static_paste";
+    SSM_REQUIRE(a && b && out && counts, "%s: null pointer", name);
+    SSM_REQUIRE(N > 0 && N <= 65535, "%s: N=%d outside 1..65535", name, N);
+    SSM_REQUIRE(T > 0 && T <= 65535, "%s: T=%d outside 1..65535", name, T);
+    if (const int e = check_frame(name, H, W, layout, sample_bytes)) return e;
+    SSM_REQUIRE(lo < (1u << 24), "%s: lo=%u outside 0..2^24-1", name, lo);
+    const YuvPlanes pl = yuv_planes(H, W, layout);
+    const long long fb = pl.frame() * sample_bytes, outs = (long long)N * T;
+    const PairEntry k = {name, "frame", fb};
+    SSM_REQUIRE(N == 1 || (std::llabs(stride_a) >= fb && std::llabs(stride_b) >= fb), "%s: strides %lld (a), %lld (b) shorter than the frame's %lld bytes",
+                name, stride_a, stride_b, fb);
+    SSM_REQUIRE(outs == 1 || std::llabs(stride_out) >= fb, "%s: stride %lld (out) shorter than the frame's %lld bytes", name, stride_out, fb);
+    if (sample_bytes == 2) {
+        const auto odd = [](const void *p) { return reinterpret_cast<size_t>(p) % 2 != 0; };
+        SSM_REQUIRE(!odd(a) && !odd(b) && !odd(out), "%s: a payload of 2-byte samples (a, b or out) is not 2-byte aligned", name);
+        SSM_REQUIRE(stride_a % 2 == 0 && stride_b % 2 == 0 && stride_out % 2 == 0, "%s: strides %lld (a), %lld (b), %lld (out) of 2-byte samples must be even",
+                    name, stride_a, stride_b, stride_out);
+    }
+    long long o0, o1, a0, a1, b0, b1;
+    rows_range(out, stride_out, outs, fb, &o0, &o1);
+    rows_range(a, stride_a, N, fb, &a0, &a1);
+    rows_range(b, stride_b, N, fb, &b0, &b1);
+    SSM_REQUIRE((a1 <= o0 || o1 <= a0) && (b1 <= o0 || o1 <= b0), "%s: out overlaps a or b", name);
+    SSM_REQUIRE(reinterpret_cast<size_t>(counts) % 8 == 0, "%s: counts is not 8-byte aligned", name);
+    const long long nbx = W >> 3, blocks = nbx * (H >> 3), strip = PASTE_BLOCKS * PASTE_STEPS, groups = (blocks + strip - 1) / strip;
+    if (const int e = grid_fits(k, groups)) return e;
+    if (const int e = clear_sums(name, counts, (size_t)N, stream)) return e;
+    if (blocks == 0) return SSM_OK;          // a frame without a block: the cleared counts are the result, no output is touched
+    const unsigned char *pa = static_cast<const unsigned char *>(a), *pb = static_cast<const unsigned char *>(b);
+    with_sample(sample_bytes, [&](auto s) {
+        with_layout(layout, [&](auto lay) {
+            SSM_LAUNCH((static_paste_kernel<decltype(s), decltype(lay)::value>), dim3((unsigned)groups, N), dim3(LANES), 0, (hipStream_t)stream, pa, pb,
+                       stride_a, stride_b, static_cast<unsigned char *>(out), stride_out, T, W, pl.cw, pl.luma(), pl.chroma(), (unsigned)nbx,
+                       (unsigned)blocks, lo, counts);
+        });
+    });
+    return ssm::check_launch("ssm_static_paste_fwd");
 }
 
 // ---- interlaced clips -------------------------------------------------------------------------------------------------------------------

@@ -107,6 +107,20 @@ The ratios 26/25 and 3/2 are conventions in the spirit of ffmpeg's idet, not its
 frame, ffmpeg is not compared - and not measured on noisy or compressed footage; a hard-edged shape that moves by whole rows can read as
 bottom field first.  Frames behind the probe are not watched; Im, a per-frame order and chroma are out of scope.  Not with --detelecine
 (a telecined clip is a mixture by construction) or a recurrent model.
+
+--static LO: blocks that do not change keep their bytes.  A channel logo over moving picture, burnt-in subtitles or a timecode, the static
+parts of a screen recording or of animation and a locked-off background are the same samples in both input frames of a pair, yet they
+come out of the network re-quantised and pulled by the flow of what moves beside them, and every upsample_rate-th output is an input
+frame's own bytes: such areas pulse.  With the option, where the two frames of a pair agree on an 8 x 8 block - the sum of absolute
+differences over its luma and the chroma under it is at most LO, in codes of the clip's depth - every frame between them carries the left
+frame's samples of that block (decided and pasted on the GPU, ssm_static_paste_fwd, behind the colour conversion of every pass).
+--static 0 is exact, not a heuristic: both neighbours hold those samples, and no honest in-between frame differs there.  Any other LO is
+your number: there is no default, and the 320 at 8 bits that mpdecimate's lo would suggest is not backed by any measurement.  A block
+that agrees in both frames while something crossed it in between is kept (nothing can tell), and the seams between kept and synthesised
+blocks are not smoothed.  --log gets one line with the pairs, the blocks kept of all and the largest and smallest share, and one line for
+every pair without a static block when others had some.  It goes with --upsample_rate, --slowmo, --fps, --speed, --scene_cut (a cut
+pair's frames are replaced whole, as without it), --matrix, --range, --flow_scale, --tile and --detelecine (which runs first), and with
+every format; not with --shutter (every output comes from the accumulator), --deinterlace, --dedup or --active: chain two runs.
 """
 import argparse
 import configparser
@@ -199,7 +213,17 @@ def getargs(argv=None):
     parser.add_argument("--field_probe", type=_named(V.parse_field_probe), nargs="?", const=V.FIELD_PROBE, default=None, metavar="P",
                         help="Look for the field order in the first P frames (default 48; comb sums on the GPU). With --deinterlace auto and a "
                              "header that says Ip or I? the verdict is the run's order; else a warning or a report. Default: off.")
+    parser.add_argument("--static", type=_named(V.parse_static), default=None, metavar="LO",
+                        help="Blocks that do not change keep their bytes: where the two frames of a pair differ by at most LO in the sum of "
+                             "absolute differences over an 8x8 block (luma and the chroma under it), the frames between them carry the left "
+                             "frame's samples. 0: only blocks that are the same in both, exact. No default value: off unless given.")
     args = parser.parse_args(argv)
+    if args.static is not None:
+        for flag, given in (("--shutter", args.shutter is not None), ("--deinterlace", args.deinterlace is not None),
+                            ("--dedup", args.dedup is not None), ("--active", args.active is not None)):
+            if given:
+                parser.error("--static does not go together with %s: blocks that do not change are kept in frames synthesised between two "
+                             "input frames as they were read, and nothing else; chain two runs" % flag)
     if args.field_probe is not None and args.detelecine:
         parser.error("--field_probe does not go together with --detelecine: a telecined clip is a mixture of progressive and combed frames by "
                      "construction, and pulldown removal finds its field order itself")
@@ -249,6 +273,22 @@ def getargs(argv=None):
     return args
 
 
+def static_lines(static, lo):
+    """What --log gets of a run with --static: `static` = [(i, static blocks, blocks)] of the pairs that got outputs.  One summary line,
+    and one line for every pair without a static block when others had some."""
+    if not static:
+        return ["static: lo = %d, no pair got a synthesised frame" % lo]
+    kept, of = sum(s for _, s, _ in static), sum(b for _, _, b in static)
+    if of == 0:
+        return ["static: lo = %d, %d pairs, the frame has no 8 x 8 block: nothing is kept" % (lo, len(static))]
+    shares = [s / b for _, s, b in static]
+    lines = ["static: lo = %d, %d pairs, %d of %d blocks kept (%.2f%%), per pair at most %.2f%% and at least %.2f%%"
+             % (lo, len(static), kept, of, 100.0 * kept / of, 100.0 * max(shares), 100.0 * min(shares))]
+    if kept:
+        lines += ["static: no static block between input frames %d and %d" % (i, i + 1) for i, s, _ in static if s == 0]
+    return lines
+
+
 def main(argv=None, model=None):
     args = getargs(argv)
     config = configparser.RawConfigParser()
@@ -263,7 +303,7 @@ def main(argv=None, model=None):
                              flow_scale=args.flow_scale, tile=args.tile, halo=args.halo, blend=args.blend, target_rate=args.fps, speed=args.speed,
                              shutter=args.shutter, shutter_samples=args.shutter_samples, scene_cut=args.scene_cut,
                              shutter_light=args.shutter_light, shutter_window=args.shutter_window, deinterlace=args.deinterlace, dedup=args.dedup, dedup_max=args.dedup_max,
-                             active=args.active, active_probe=args.active_probe, field_probe=args.field_probe)
+                             active=args.active, active_probe=args.active_probe, field_probe=args.field_probe, static=args.static)
     with V.Y4MReader(args.input, extended=True, interlaced=args.deinterlace is not None or args.detelecine) as reader:
         if args.detelecine:
             log.info("[%s] detelecine: %d:%d frames/s in, film at %d:%d", args.expt, *reader.rate, *V.detelecine_rate(reader.rate))
@@ -321,6 +361,9 @@ def main(argv=None, model=None):
         for i, rows, cols in vi.active_excess:
             log.info("[%s] active: input frame %d has %d active rows and %d active columns outside the rectangle; nothing changes", args.expt, i,
                      rows, cols)
+    if args.static is not None:
+        for line in static_lines(vi.static, args.static):
+            log.info("[%s] %s", args.expt, line)
     for i, score in vi.cuts:
         log.info("[%s] scene cut between input frames %d and %d: score %s = %.6f (threshold %s)", args.expt, i, i + 1, score, float(score),
                  vi.scene_cut)

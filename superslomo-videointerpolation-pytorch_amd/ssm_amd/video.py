@@ -55,6 +55,10 @@
   / cut_window_host /     a rectangle of a payload as a payload of its own and back (ssm_window_cut_fwd, window_cut, is held to the cut byte
   paste_window_host /     for byte); the reader that probes, decides and watches in front of the loop - VideoInterpolator(active=,
   ActiveSource            active_probe=): the run is the cropped clip's, the bars of a synthesised frame are the nearer input frame's bytes
+  static_paste_host /     blocks that do not change (a logo, subtitles, a timecode, a locked-off background): where the two frames of a pair agree
+  static_paste /          on an 8 x 8 block - luma and the chroma under it, sum of |difference| at most `lo` - every frame between them carries the
+  parse_static            left frame's samples of that block, by numpy and by ssm_static_paste_fwd on the pass's stream; the number of such
+                          blocks per pair - VideoInterpolator(static=): the fixed grid and the timeline, every other mode unchanged
   (ssm_amd/video_score.py) hold-out scoring: the clip against its own held-out frames, plane_sse / HoldOutScorer on this loop's ring, Clip and
                           buffers; the PSNR of what VideoInterpolator(upsample_rate=hold) would write - this module is unchanged by it
 
@@ -78,7 +82,10 @@ shutter, scene_cut or deinterlace (chain two runs), a scene cut on the frame aft
 agreement with ffmpeg's mpdecimate frame for frame, noisy or compressed footage; of letterboxed clips: a rectangle that changes inside a
 clip, coloured bars, re-planning when a later frame exceeds the rectangle, active together with shutter, deinterlace or dedup (chain two
 runs), noisy or compressed bars; of the field probe: watching frames behind the probe, Im, a per-frame order, detection on chroma, noisy
-or compressed footage (every clip it was tried on is synthetic), agreement with ffmpeg's idet frame for frame.
+or compressed footage (every clip it was tried on is synthetic), agreement with ffmpeg's idet frame for frame; of static blocks: smoothing the
+seams between kept and synthesised blocks, growing or eroding the static set, per-pixel masks, a default lo, noisy or compressed footage
+(where no block agrees exactly), static together with shutter, deinterlace, dedup, active or a recurrent model (chain two runs), skipping
+the network on frames that are static throughout.
 """
 import ctypes
 import functools
@@ -1929,6 +1936,89 @@ class ActiveSource:
         self.close()
 
 
+# ---- blocks that do not change ---------------------------------------------------------------------------------------------------------
+# The definition is in include/ssm_hip.h and DESIGN 3.12: block (bx, by) of a frame is its 8 x 8 luma samples at (8 bx, 8 by) with the U and
+# V samples under them; it is static in a pair iff the sum of |a - b| over all of them is at most `lo`, and every frame between the two
+# then carries the left frame's samples of the block.  lo = 0 - the two frames agree - is exact; any other lo is the user's number.
+STATIC_MAX = (1 << 24) - 1         # the largest `lo` ssm_static_paste_fwd takes: above every block sum (192 * 65535)
+
+
+def parse_static(text):
+    """The threshold of the static-block test, a whole number in 0 .. 2^24 - 1 in codes of the clip's depth (0: the block is the same in
+    both frames), as an int or a command line's text -> int.  Anything else is a ValueError naming the value."""
+    try:
+        if isinstance(text, bool) or (not isinstance(text, str) and int(text) != text):
+            raise ValueError
+        lo = int(text.strip() if isinstance(text, str) else text)
+    except (ValueError, TypeError, OverflowError):
+        raise ValueError("static, the largest block sum of |difference| that counts as unchanged, is a whole number in 0 .. 2^24 - 1 "
+                         "(got %r)" % (text,)) from None
+    if not 0 <= lo <= STATIC_MAX:
+        raise ValueError("static, the largest block sum of |difference| that counts as unchanged, is a whole number in 0 .. 2^24 - 1 "
+                         "(got %r)" % (text,))
+    return lo
+
+
+def static_blocks(h, w):
+    """The 8 x 8 blocks of an h x w frame: (h >> 3) * (w >> 3), 0 for a frame below 8 rows or columns."""
+    return (h >> 3) * (w >> 3)
+
+
+def _chroma_block(siting):
+    """(rows, columns) of the chroma samples under an 8 x 8 luma block."""
+    return (8, 8) if siting == C444 else (8, 4) if siting == C422 else (4, 4)
+
+
+def static_paste_host(outputs, a, b, h, w, siting, bits=8, lo=0):
+    """Yardstick of ssm_static_paste_fwd: outputs [N, T, at least frame_bytes] uint8 (numpy), the T frames between the payloads a[n] and
+    b[n] ([N, at least frame_bytes] uint8) -> (a copy of `outputs` in which the samples of every block that is static in pair n - the sum
+    of |a - b| over its luma, U and V samples at most `lo` - are a[n]'s, uint64 [N]: the static blocks of every pair).  With bits > 8
+    over the 16-bit words, all 16 bits."""
+    lo, fb = int(lo), frame_bytes(h, w, siting, bits)
+    outputs, a, b = (np.asarray(x) for x in (outputs, a, b))
+    assert outputs.dtype == np.uint8 and outputs.ndim == 3 and outputs.shape[2] >= fb, "outputs are [N, T, at least frame_bytes] uint8"
+    n, t = outputs.shape[:2]
+    for p in (a, b):
+        assert p.dtype == np.uint8 and p.shape == (n, p.shape[1]) and p.shape[1] >= fb, "payloads are [N, at least frame_bytes] uint8"
+    res, counts = outputs.copy(), np.zeros(n, np.uint64)
+    by, bx = h >> 3, w >> 3
+    if not (by and bx and n and t):
+        return res, counts
+    pa, pb = (split_planes(np.ascontiguousarray(x[:, :fb]), h, w, siting, bits) for x in (a, b))
+    cr, cc = _chroma_block(siting)
+    shapes = ((8, 8), (cr, cc), (cr, cc))
+    d = np.zeros((n, by, bx), np.int64)
+    for (x, y), (rr, rc) in zip(zip(pa, pb), shapes):
+        diff = np.abs(x[:, :rr * by, :rc * bx].astype(np.int64) - y[:, :rr * by, :rc * bx].astype(np.int64))
+        d += diff.reshape(n, by, rr, bx, rc).sum(axis=(2, 4))
+    keep = d <= lo                                   # [N, by, bx]
+    counts[:] = keep.reshape(n, -1).sum(axis=1)
+    frames = np.ascontiguousarray(res[:, :, :fb]).reshape(n * t, fb)
+    for plane, src, (rr, rc) in zip(split_planes(frames, h, w, siting, bits), pa, shapes):
+        mask = np.repeat(np.repeat(keep, rr, axis=1), rc, axis=2)          # [N, rr by, rc bx]
+        dst = plane.reshape((n, t) + plane.shape[1:])[:, :, :rr * by, :rc * bx]
+        np.copyto(dst, src[:, None, :rr * by, :rc * bx], where=mask[:, None])
+    res[:, :, :fb] = frames.reshape(n, t, fb)
+    return res, counts
+
+
+def static_paste(payload_a, payload_b, outputs, h, w, siting, bits=8, lo=0, counts=None):
+    """ssm_static_paste_fwd on payloads: a, b [N, at least frame_bytes] uint8 device tensors (unit stride within a row, any row stride:
+    frames n and n + 1 of one buffer are fine) and outputs [N * T, at least frame_bytes], the T frames of pair n in rows n T .. n T + T - 1,
+    changed in place: the samples of every block that is static in pair n become a[n]'s.  -> int64 [N] on the device (into `counts` if
+    given): the static blocks of every pair.  Queued on the current stream."""
+    fb = frame_bytes(h, w, siting, bits)
+    n, counts, sa, sb_stride = _pair_operands(payload_a, payload_b, fb, "frame_bytes", counts, ())
+    assert outputs.is_cuda and outputs.dtype == torch.uint8 and outputs.dim() == 2 and outputs.shape[1] >= fb and outputs.device == payload_a.device \
+        and (outputs.shape[1] == 1 or outputs.stride(1) == 1), "outputs must be [N * T, at least frame_bytes] uint8 on the payloads' device"
+    assert outputs.shape[0] >= n and outputs.shape[0] % n == 0, "outputs hold T rows per pair"
+    t = outputs.shape[0] // n
+    hb.check(hb.load().ssm_static_paste_fwd(payload_a.data_ptr(), payload_b.data_ptr(), sa, sb_stride, outputs.data_ptr(),
+                                            outputs.stride(0) if n * t > 1 else 0, n, t, h, w, siting, sample_bytes(bits), int(lo),
+                                            counts.data_ptr(), hb.stream_ptr()))
+    return counts
+
+
 # ---- output order -------------------------------------------------------------------------------------------------------------------
 def pass_order(valid, nt):
     """Write order of one pass of `valid` pairs with nt interpolated frames each: ("interp", row of the pass's output buffer) for the
@@ -2622,7 +2712,7 @@ class VideoInterpolator:
     def __init__(self, model, cfg, upsample_rate=None, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
                  tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8, scene_cut=None,
                  shutter_light="coded", deinterlace=None, dedup=None, dedup_max=DEDUP_MAX, active=None, active_probe=ACTIVE_PROBE,
-                 shutter_window="box", field_probe=None):
+                 shutter_window="box", field_probe=None, static=None):
         """target_rate = (num, den) and / or speed (a Fraction, or what Fraction() takes; 1/4 is four times slower): the output follows
         Timeline(speed * input rate / target_rate) instead of the fixed grid of upsample_rate, which is then not used (see
         _run_timeline); with both None nothing changes.  flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
@@ -2699,7 +2789,19 @@ class VideoInterpolator:
         deinterlace="tff" / "bff"; else None).  The ratios are conventions in the spirit of ffmpeg's idet, not its construction, and not
         backed by a measurement on noisy or compressed footage.  Frames behind the probe are not watched.  Not with a recurrent model,
         and not on a TelecineSource: a telecined clip is a mixture of both kinds of frame by construction.  None: every mode as it is,
-        launch for launch."""
+        launch for launch.
+        static (LO, a whole number in 0 .. 2^24 - 1, or its text; parse_static; no default value): blocks that do not change keep their
+        bytes.  Where the two frames of a pair agree on an 8 x 8 block - the sum of |difference| over its luma and the chroma under it is
+        at most LO, in codes of the clip's depth - every frame synthesised between them carries the LEFT frame's samples of that block
+        (static_paste_host is the definition; ssm_static_paste_fwd does it on the pass's stream, behind the egress and ahead of the copy
+        to the host, on the payloads as they were uploaded).  0 is exact: both neighbours hold those samples, so no honest in-between
+        frame differs there - a logo, subtitles, a timecode, a locked-off background stop pulsing against the input frames' own bytes.
+        Any other LO is the user's number.  Not claimed: a block that agrees in both frames while something crossed it in between is
+        kept; the seams between kept and synthesised blocks are not smoothed.  After run(): `static` lists (i, static blocks, blocks) of
+        every pair (i, i + 1) that got outputs.  It goes with upsample_rate, target_rate, speed, scene_cut (a cut pair's outputs are
+        replaced whole, as without it), matrix, color_range, flow_scale and tile, and with every format; not with shutter (every output
+        is an accumulator's), deinterlace, dedup, active or a recurrent model (chain two runs).  None: every mode as it is, launch for
+        launch."""
         from .coarse import check_scale
         from .tiles import check_args
         self.flow_scale = check_scale(flow_scale)
@@ -2731,6 +2833,14 @@ class VideoInterpolator:
                 if given:
                     raise ValueError("active together with %s is not available: the picture is cut out and the bars are pasted back around "
                                      "frames synthesised between two input frames, and nothing else; chain two runs" % name)
+        self.static_lo, self.static = None if static is None else parse_static(static), []
+        if self.static_lo is not None:
+            for name, given in (("shutter", shutter is not None), ("deinterlace", deinterlace is not None),
+                                ("dedup", dedup is not None and dedup is not False), ("active", active is not None),
+                                ("a recurrent model", getattr(model, "recurrent", False))):
+                if given:
+                    raise ValueError("static together with %s is not available: blocks that do not change are kept in frames synthesised "
+                                     "between two input frames as they were read, and nothing else; chain two runs" % name)
         self.field_probe_option = None if field_probe is None or field_probe is False else (
             FIELD_PROBE if field_probe is True else parse_field_probe(field_probe))
         self.field_probe, self._probed, self._probed_order = None, None, None
@@ -2830,6 +2940,21 @@ class VideoInterpolator:
         return (SceneCuts(self.scene_cut), [torch.empty(pairs, dtype=torch.int64, device=clip.dev) for _ in range(n)], host,
                 [t.numpy().view(np.uint64) for t in host], np.empty(clip.fb, np.uint8)), 1
 
+    def _static_state(self, n, depth, pairs, clip):
+        """What static blocks add to a mode's buffers: the counts of a pass on the device (per stream) and in the pinned ring slot (per slot,
+        with its numpy view as uint64).  Without the option: None for each."""
+        if self.static_lo is None:
+            return None, None, None
+        host = [torch.empty(pairs, dtype=torch.int64).pin_memory() for _ in range(depth)]
+        return [torch.empty(pairs, dtype=torch.int64, device=clip.dev) for _ in range(n)], host, [t.numpy().view(np.uint64) for t in host]
+
+    def _static_rows(self, counts, index, blocks, rows):
+        """The rows of a pass with static blocks, called by PassRing on the writer thread once the pass's event has come: notes the counts of
+        the pass's pairs (`index`: their clip indices, in the order of `counts`) in `static`, then hands on `rows` - a list, or the
+        callable of the scene cuts, whose replacement of a cut pair's frames stands."""
+        self.static.extend((i, int(counts[p]), blocks) for p, i in enumerate(index))
+        return rows() if callable(rows) else rows
+
     @staticmethod
     def _paster(clip):
         """paste(window's bytes, an input frame's bytes) -> a full frame for the writer thread, or None for a clip without a window.  The
@@ -2910,7 +3035,7 @@ class VideoInterpolator:
     def run(self, reader, writer):
         """Returns the number of frames written: (n - 1) * upsample_rate + 1 for n input frames (with target_rate / speed:
         floor((n - 1) / step) + 1; with a shutter: Timeline.n_outputs(n); with deinterlace: 2 n; with dedup the fixed grid's count)."""
-        self.cuts, self.repeats, self.active, self.active_note, self.active_excess = [], [], None, None, []
+        self.cuts, self.repeats, self.active, self.active_note, self.active_excess, self.static = [], [], None, None, [], []
         if self.field_probe_option is not None and reader is not self._probed:
             reader = self.probe_fields(reader)
         self._probed = None          # one run per probe
@@ -2959,7 +3084,15 @@ class VideoInterpolator:
         so that the left planes of a pass's pairs are rows 0 .. pb - 1, the right ones rows 1 .. pb, and one ssm_luma_sad_fwd call takes
         them all.  A pass puts the Y plane of its last frame into row 0 of the NEXT stream's buffer, after its own call and before it
         records `ingested`: the pass that reads it waits for that event, and the pass that read the row before has recorded its own
-        event (after its call) earlier in the chain of waits.  The sums go back to the pass's ring slot ahead of `done`."""
+        event (after its call) earlier in the chain of waits.  The sums go back to the pass's ring slot ahead of `done`.
+
+        With static the row in front holds the WHOLE frame before the pass's first, and one ssm_static_paste_fwd call takes the pass's pairs
+        (rows 0 .. pb - 1 against rows 1 .. pb, T = upsample_rate - 1 outputs each) behind the egress and ahead of the D2H copy.  That call
+        reads row 0 long after the pass has recorded `ingested`, so the row cannot be written by another stream as the scene cuts' is: the
+        pass FETCHES it, on its own stream, from the last row of the stream before - behind its wait for that stream's `ingested` and ahead
+        of its own upload (with one stream the source is its own last row).  The source row is next written by the upload of pass j + n - 1,
+        which stands behind a chain of waits that ends at this pass's `ingested`, recorded after the fetch.  With both options the
+        fetched row serves the luma sums too.  The counts go back to the pass's ring slot ahead of `done`."""
         from .evaluation import t_values
         fb, dev, hp, wp, luma = clip.fb, clip.dev, clip.hp, clip.wp, clip.h * clip.w
         pipe = self._pipeline(hp, wp, dev)
@@ -2968,6 +3101,9 @@ class VideoInterpolator:
         t_dev = torch.tensor(t_values(self.rate), dtype=torch.float32, device=dev)
         host_in, host_out, _, np_in, np_out, _, done = ring_slots(depth, fb, pb, pb * nt, fb_out=clip.fb_out)
         (cuts, dev_sums, host_sums, np_sums, carried), lead = self._cut_state(self.scene_cut is not None, n, depth, pb, clip)
+        static, blocks = self.static_lo, static_blocks(clip.h, clip.w)
+        dev_counts, host_counts, np_counts = self._static_state(n, depth, pb, clip)
+        lead = 1 if static is not None else lead
         paste = self._paster(clip)
         if paste is None:
             dev_in, dev_out, _, ingested = stream_buffers(n, dev, fb, lead + pb, pb * nt)
@@ -2991,7 +3127,9 @@ class VideoInterpolator:
                 new = dev_in[last][lead:]
                 dev_up[last][lead:lead + 1].copy_(first, non_blocking=True)
                 clip.ingest(dev_up[last][lead:lead + 1], planes[last][pb:], scratch=new[:1])
-                if cuts is not None:
+                if static is not None and pb > 1:
+                    dev_in[last][pb].copy_(new[0])          # where pass 0 fetches its carried frame
+                elif cuts is not None and static is None:
                     dev_in[0][0, :luma].copy_(new[0, :luma])
                 ingested[last].record()
             j, eof = 0, False
@@ -3010,18 +3148,25 @@ class VideoInterpolator:
                 st = pipe.streams[k]
                 with torch.cuda.stream(st):
                     new = dev_in[k][lead:]
+                    if static is not None:
+                        st.wait_event(ingested[kprev])
+                        dev_in[k][0].copy_(dev_in[kprev][pb])
                     dev_up[k][lead:].copy_(host_in[r], non_blocking=True)
                     st.wait_event(ingested[kprev])
                     planes[k][0].copy_(planes[kprev][pb])
                     clip.ingest(dev_up[k][lead:], planes[k][1:], scratch=new)
                     if cuts is not None:
                         luma_sad(dev_in[k][:pb], dev_in[k][1:], clip.h, clip.w, out=dev_sums[k])
-                        dev_in[(j + 1) % n][0, :luma].copy_(dev_in[k][pb, :luma])
+                        if static is None:
+                            dev_in[(j + 1) % n][0, :luma].copy_(dev_in[k][pb, :luma])
                     ingested[k].record()
                     x = planes[k]
                     img6 = x.view(1, 6, hp, wp) if pb == 1 else x.as_strided((pb, 6, hp, wp), (3 * hp * wp, hp * wp, wp, 1))
                     frames = pipe.engines[k].run(img6, t_dev, False)
                     clip.egress(frames, dev_out[k])
+                    if static is not None:
+                        static_paste(dev_in[k][:pb], dev_in[k][1:], dev_out[k], clip.h, clip.w, clip.siting, clip.bits, static, counts=dev_counts[k])
+                        host_counts[r].copy_(dev_counts[k], non_blocking=True)
                     host_out[r].copy_(dev_out[k], non_blocking=True)
                     if cuts is not None:
                         host_sums[r].copy_(dev_sums[k], non_blocking=True)
@@ -3035,6 +3180,9 @@ class VideoInterpolator:
                         rows = functools.partial(self._cut_rows, cuts, luma, np_sums[r], host_pairs, list(zip(rows, at)), carried, paste)
                     else:
                         rows = functools.partial(self._paste_rows, paste, host_pairs, list(zip(rows, at)), carried)
+                if static is not None:
+                    i0 = (written - 1) // self.rate
+                    rows = functools.partial(self._static_rows, np_counts[r], range(i0, i0 + valid), blocks, rows)
                 ring.hand(r, done[r], rows)
                 written += valid * self.rate
                 j += 1
@@ -3174,7 +3322,11 @@ class VideoInterpolator:
         that ran last in the pass before, written by that pass behind its own calls and ahead of its `ingested`; a pair's left plane is
         its own uploaded row, the right row of the pair before it, or row 0.  The rows of the pairs that run step evenly unless the
         timeline skips pairs inside a pass (sad_runs): one ssm_luma_sad_fwd call then, one per run otherwise.  Only pairs that run are
-        summed and fed to SceneCuts."""
+        summed and fed to SceneCuts.
+
+        With static, as on the fixed grid: row 0 holds the whole right frame of the pair that ran last in the pass before, fetched by the
+        pass itself from that pass's stream, behind its wait for `ingested` and ahead of its own uploads; one ssm_static_paste_fwd call
+        per pair, with T the number of its outputs, behind the pair's egress and ahead of its D2H copy; the counts go back with `done`."""
         fb, dev, hp, wp, luma = clip.fb, clip.dev, clip.hp, clip.wp, clip.h * clip.w
         tl = self.timeline(reader.rate) if tl is None else tl
         S, pb, n = tl.slots, self.pb, self.n_streams
@@ -3182,6 +3334,10 @@ class VideoInterpolator:
         depth, cap = n + 2, 2 * pb + 2
         host_in, host_out, host_t, np_in, np_out, np_t, done = ring_slots(depth, fb, cap, pb * max(S, 1), pb * max(S, 1), fb_out=clip.fb_out)
         (cuts, dev_sums, host_sums, np_sums, carried), lead = self._cut_state(self.scene_cut is not None and pipe is not None, n, depth, pb, clip)
+        static, blocks = (self.static_lo if pipe is not None else None), static_blocks(clip.h, clip.w)
+        dev_counts, host_counts, np_counts = self._static_state(n, depth, pb, clip) if static is not None else (None, None, None)
+        lead = 1 if static is not None else lead
+        last_right = [0]          # row of dev_in, in the pass before, of the frame the next pass's first pair may carry over
         paste = self._paster(clip)
         plan = PassPlanner(tl, pb, cap)
         if pipe is not None and paste is not None:          # a letterboxed clip, as on the fixed grid: frames up into dev_up, their windows in dev_in
@@ -3202,6 +3358,8 @@ class VideoInterpolator:
             with torch.cuda.stream(st):
                 if j:
                     st.wait_event(ingested[(j - 1) % n])          # the carried frame; and pass j - n + 1 is done with planes[k]
+                    if static is not None:
+                        dev_in[k][0].copy_(dev_in[(j - 1) % n][last_right[0]])
                 new, up = dev_in[k][lead:], dev_up[k][lead:]
                 for p, (row, own_left, ts) in enumerate(pairs):
                     rows = 2 if own_left else 1
@@ -3210,14 +3368,17 @@ class VideoInterpolator:
                         planes[k][p, 0].copy_(planes[k][p - 1, 1] if p else planes[(j - 1) % n][last_p[0], 1])
                     clip.ingest(up[row:row + rows], planes[k][p, 2 - rows:], scratch=new[row:row + rows])
                 upload_times([ts for _, _, ts in pairs], S, np_t[r], host_t[r], dev_t[k])
-                if cuts is not None:
+                if cuts is not None or static is not None:
                     rights = [lead + row + (1 if own_left else 0) for row, own_left, _ in pairs]          # rows of dev_in[k]
                     lefts = [lead + row if own_left else (rights[p - 1] if p else 0) for p, (row, own_left, _) in enumerate(pairs)]
+                    last_right[0] = rights[-1]
+                if cuts is not None:
                     for p, m in sad_runs(lefts, rights):
                         da, db = (lefts[p + 1] - lefts[p], rights[p + 1] - rights[p]) if m > 1 else (1, 1)
                         luma_sad(dev_in[k][lefts[p]:lefts[p] + (m - 1) * da + 1:da], dev_in[k][rights[p]:rights[p] + (m - 1) * db + 1:db], clip.h,
                                  clip.w, out=dev_sums[k][p:p + m])
-                    dev_in[(j + 1) % n][0, :luma].copy_(dev_in[k][rights[-1], :luma])
+                    if static is None:
+                        dev_in[(j + 1) % n][0, :luma].copy_(dev_in[k][rights[-1], :luma])
                 ingested[k].record()
                 last_p[0] = len(pairs) - 1
                 frames = pipe.engines[k].run(planes[k].view(pb, 6, hp, wp), dev_t[k], False)
@@ -3227,7 +3388,15 @@ class VideoInterpolator:
                     spans = [(p * S, len(ts)) for p, (_, _, ts) in enumerate(pairs)]
                 for o, m in spans:
                     clip.egress(frames[o:o + m], dev_out[k][o:o + m])
-                    host_out[r][o:o + m].copy_(dev_out[k][o:o + m], non_blocking=True)
+                    if static is None:
+                        host_out[r][o:o + m].copy_(dev_out[k][o:o + m], non_blocking=True)
+                if static is not None:
+                    for p, (_, _, ts) in enumerate(pairs):
+                        static_paste(dev_in[k][lefts[p]:lefts[p] + 1], dev_in[k][rights[p]:rights[p] + 1], dev_out[k][p * S:p * S + len(ts)],
+                                     clip.h, clip.w, clip.siting, clip.bits, static, counts=dev_counts[k][p:p + 1])
+                    for o, m in spans:
+                        host_out[r][o:o + m].copy_(dev_out[k][o:o + m], non_blocking=True)
+                    host_counts[r].copy_(dev_counts[k], non_blocking=True)
                 if cuts is not None:
                     host_sums[r].copy_(dev_sums[k], non_blocking=True)
                 done[r].record()
@@ -3244,6 +3413,8 @@ class VideoInterpolator:
                     rows = functools.partial(self._cut_rows, cuts, luma, np_sums[r], host_pairs, list(zip(rows, at)), carried, paste)
                 else:
                     rows = functools.partial(self._paste_rows, paste, host_pairs, list(zip(rows, at)), carried)
+            if static is not None and on_gpu:
+                rows = functools.partial(self._static_rows, np_counts[r], list(plan.closed_index), blocks, rows)
             return rows, len(order)
 
         return self._run_passes(clip, reader, writer, plan, np_in, done, lambda order, pairs: bool(pairs), submit, rows_of)
