@@ -37,6 +37,10 @@
   weave_fields_host       woven from kept fields and synthesised ones or integer line averages - the numpy definitions ssm_fields_split_fwd
   / field_outputs         and ssm_fields_weave_fwd (fields_split, fields_weave) are held to bit for bit; which field is which time under
                           tff / bff and which pairs run - VideoInterpolator(deinterlace=): 2n progressive frames of an n-frame clip (_run_fields)
+  LookAheadSource         what the four readers in front of the loop share (FieldOrderSource, TelecineSource, RepeatSource, ActiveSource): the
+                          mirrored format attributes, the chunk's pinned and device buffers made once, the measuring step of a chunk on a
+                          stream of its own (one H2D, one kernel entry, one D2H per result, one event wait), the read loop with its carried
+                          frames, probe and replay, and the one hand-out path; a source adds its kernel, its carry, its decider, its frames
   field_order_sums_host / interlaced clips, the field order from the data: per frame the comb sums A0, A1, D of its luma plane against the frame
   field_order_sums /      before and the frame after, by numpy and by ssm_field_order_sums_fwd; the kind of a frame (field_kind) and the verdict
   FieldVerdict /          of a probe in Python ints; the reader that probes and replays in front of the loop - VideoInterpolator(field_probe=):
@@ -839,84 +843,109 @@ def field_order_sums(prev, cur, nxt, h, w, bits=8, out=None):
     return out
 
 
-class FieldOrderSource:
-    """A reader that probes the field order of a clip: wraps a Y4MReader (or anything with its attributes) and hands out its frames as they
-    are.  decide() reads the first `probe` frames (or the whole clip if it is shorter) into a host buffer, takes the comb sums of the inner
-    ones on the GPU, and sets `kinds`, `counts`, `verdict` ("tff", "bff", "progressive" or None: FieldVerdict) and `note`, one log line with
-    the four counts; then the probed frames are replayed, and the frames behind the probe come straight from the reader: nothing watches
-    them.
+# ---- the readers in front of the loop -----------------------------------------------------------------------------------------------------
+FORMAT_ATTRS = ("width", "height", "siting", "chroma", "color_range", "aspect", "xtags", "frame_bytes", "rate")          # a reader's, mirrored
 
-    A chunk is frames_per_chunk new frames behind the two frames before them, in one pinned buffer and one device buffer, made once.  Per
-    chunk, on a stream of its own: one H2D, one ssm_field_order_sums_fwd - the frame before, the frame and the frame after are rows
-    b - 1, b, b + 1 of the device buffer, one pointer each and one stride - one D2H of the sums, one event wait.  The bytes handed out are
-    the reader's; neither they nor the verdict depend on frames_per_chunk."""
 
-    def __init__(self, reader, dev, probe=FIELD_PROBE, frames_per_chunk=8):
-        assert frames_per_chunk >= 1
+class LookAheadSource:
+    """What FieldOrderSource, TelecineSource, RepeatSource and ActiveSource share: a reader that wraps a Y4MReader (or anything with its
+    attributes, another source for one), reads the clip a chunk ahead of the loop, measures the chunk on the GPU, decides on the host and
+    hands frames on.  It has the reader's format attributes (FORMAT_ATTRS, bits, extended, sample_bytes, interlace; field_order and
+    field_bytes with fields=True, else None), frames_read (frames handed out), close() and the context manager.
+
+    A chunk is `rows` new frames behind `carry` carried frames of the chunk before, in one pinned buffer, and behind the last `dev_carry` of
+    those in one device buffer; both are made once (_window), with the results on the device and pinned.  Per chunk, on a stream of its
+    own (_measure): one H2D, one kernel entry, one D2H per result tensor, one event wait; never a wait per frame.  _fill reads a chunk and
+    carries, _probe reads the frames a decision is taken on and keeps them for replay, read_frame_into hands out the replayed frames,
+    then what the source's _ahead() left in _pending (_take) or, with _straight, the reader's frames as they come."""
+    _straight = False          # True: the frames behind the replayed ones come straight from the reader, nothing looks at them
+
+    def __init__(self, reader, dev, takes, fields=False):
         self.reader, self.dev = reader, torch.device(dev)
         if self.dev.type != "cuda":
-            raise RuntimeError("the field probe takes its comb sums on the GPU (the HIP path has no CPU fallback)")
-        for name in ("width", "height", "siting", "chroma", "color_range", "aspect", "xtags", "frame_bytes", "rate"):
+            raise RuntimeError("%s on the GPU (the HIP path has no CPU fallback)" % takes)
+        for name in FORMAT_ATTRS:
             setattr(self, name, getattr(reader, name))
         self.bits, self.extended = getattr(reader, "bits", 8), getattr(reader, "extended", False)
         self.sample_bytes = sample_bytes(self.bits)
         self.interlace = getattr(reader, "interlace", "p")
-        self.field_order, self.field_bytes = getattr(reader, "field_order", None), getattr(reader, "field_bytes", None)
-        self.probe, self.frames_read = parse_field_probe(probe), 0
-        self.kinds = self.counts = self.verdict = self.note = None
-        self._rows, self._decided, self._replay, self._eof = frames_per_chunk, False, [], False
+        self.field_order, self.field_bytes = (getattr(reader, "field_order", None), getattr(reader, "field_bytes", None)) if fields else (None, None)
+        self.frames_read = 0
+        self._replay, self._pending, self._eof = [], [], False          # probed frames; what _take hands out next; the reader has ended
+        self._base = None          # the clip's frame in row 0 of the pinned buffer (below 0 in the first chunk); None before it
+        self._np = None
 
-    def _sums(self, frames):
-        """The comb sums of frames 1 .. m - 2 of `frames` [m, frame_bytes]: uint64 [m - 2, 3]."""
-        m, c, h, w = frames.shape[0], self._rows, self.height, self.width
-        host = torch.empty(c + 2, self.frame_bytes, dtype=torch.uint8).pin_memory()
-        dev = torch.empty(c + 2, self.frame_bytes, dtype=torch.uint8, device=self.dev)
-        dev_sums = torch.empty(c, 3, dtype=torch.int64, device=self.dev)
-        host_sums = torch.empty(c, 3, dtype=torch.int64).pin_memory()
-        stream, event = torch.cuda.Stream(self.dev), torch.cuda.Event()
-        out = np.zeros((max(m - 2, 0), 3), np.uint64)
-        for at in range(0, m, c):          # the chunk's new frames are at .. at + k - 1; it closes the inner frames whose next frame is new
-            k, lo = min(c, m - at), max(0, at - 2)
-            first, last = max(1, at - 1), at + k - 2
-            if last < first:
-                continue
-            cnt = last - first + 1
-            host.numpy()[:at + k - lo] = frames[lo:at + k]
-            b = first - lo
-            with torch.cuda.stream(stream):
-                dev[:at + k - lo].copy_(host[:at + k - lo], non_blocking=True)
-                field_order_sums(dev[b - 1:b - 1 + cnt], dev[b:b + cnt], dev[b + 1:b + 1 + cnt], h, w, self.bits, out=dev_sums[:cnt])
-                host_sums[:cnt].copy_(dev_sums[:cnt], non_blocking=True)
-                event.record()
-            event.synchronize()
-            out[first - 1:last] = host_sums.numpy().view(np.uint64)[:cnt]
-        return out
+    def _window(self, rows, carry, dev_carry, results):
+        """The buffers of a chunk: pinned [carry + rows, frame_bytes] (_np its numpy view), device [dev_carry + rows, frame_bytes], and per
+        (trailing shape, dtype) of `results` a [rows, ...] tensor on the device and a pinned one, read on the host as unsigned words."""
+        self._rows, self._carry = rows, carry
+        self._host = torch.empty(carry + rows, self.frame_bytes, dtype=torch.uint8).pin_memory()
+        self._np = self._host.numpy()
+        self._dev = torch.empty(dev_carry + rows, self.frame_bytes, dtype=torch.uint8, device=self.dev)
+        self._dev_results = [torch.empty((rows,) + tuple(shape), dtype=dtype, device=self.dev) for shape, dtype in results]
+        self._host_results = [torch.empty(t.shape, dtype=t.dtype).pin_memory() for t in self._dev_results]
+        self._np_results = [t.numpy().view("u%d" % t.element_size()) for t in self._host_results]
+        self._stream, self._event = torch.cuda.Stream(self.dev), torch.cuda.Event()
 
-    def decide(self):
-        """The verdict of the probe: "tff", "bff", "progressive" or None.  Reads the probe frames on the first call."""
-        if self._decided:
-            return self.verdict
-        self._decided = True
-        probe = np.empty((self.probe, self.frame_bytes), np.uint8)
-        n = 0
-        while n < self.probe and self.reader.read_frame_into(probe[n]):
-            n += 1
-        self._eof = n < self.probe
-        self.sums = self._sums(probe[:n])
-        v = FieldVerdict.of_sums(self.sums)
-        self.kinds, self.counts, self.verdict, self.note = v.kinds, v.counts, v.verdict, v.note
-        self._replay = [probe[i] for i in range(n)]
-        return self.verdict
+    def _measure(self, k, rows, launch):
+        """The pinned rows of the slice `rows` to the front of the device buffer, launch(those device rows, the first k rows of every
+        device result), the results back: per result its first k rows, unsigned, views of pinned memory that the next call overwrites."""
+        dev = self._dev[:rows.stop - rows.start]
+        with torch.cuda.stream(self._stream):
+            dev.copy_(self._host[rows], non_blocking=True)
+            launch(dev, *(t[:k] for t in self._dev_results))
+            for hr, dr in zip(self._host_results, self._dev_results):
+                hr[:k].copy_(dr[:k], non_blocking=True)
+            self._event.record()
+        self._event.synchronize()
+        return [r[:k] for r in self._np_results]
+
+    def _fill(self):
+        """The next chunk: up to `rows` frames of the reader into the pinned buffer behind the carried ones -> how many; fewer than `rows`
+        is the end of the clip (_eof).  A source that carries has the clip's first frame in its last carried row, so that every new row
+        has the row before it, and refuses a stream without one."""
+        rows, c = self._rows, self._carry
+        if self._base is None:
+            if c and not self.reader.read_frame_into(self._np[c - 1]):
+                raise Y4MError("the Y4M stream holds no frame")
+            self._base = 1 - c if c else 0
+        else:
+            self._base += rows          # a chunk that is not the last one is full
+            self._np[:c] = self._np[rows:rows + c].copy()          # the two overlap where rows < carry
+        k = 0
+        while k < rows and self.reader.read_frame_into(self._np[c + k]):
+            k += 1
+        self._eof = k < rows
+        return k
+
+    def _probe(self, n):
+        """The first n frames of the reader (or the whole clip if it is shorter) [m, frame_bytes], kept to be handed out first."""
+        probe = np.empty((n, self.frame_bytes), np.uint8)
+        m = 0
+        while m < n and self.reader.read_frame_into(probe[m]):
+            m += 1
+        self._eof = m < n
+        self._replay = [probe[i] for i in range(m)]
+        return probe[:m]
+
+    def _ahead(self):
+        """Before a frame is handed out: the source decides, or reads chunks until _pending holds what it needs or the clip has ended."""
+
+    def _take(self, n, out):
+        """Hands out an entry of _pending: clip frame n, a row of the pinned buffer."""
+        out[:] = self._np[n - self._base]
 
     def read_frame_into(self, buf):
         """The next frame's payload into `buf`; False at the end of the clip."""
-        self.decide()
+        self._ahead()
         out = np.frombuffer(memoryview(buf).cast("B"), np.uint8)
         if out.size != self.frame_bytes:
             raise ValueError("buffer of %d bytes for frames of %d" % (out.size, self.frame_bytes))
         if self._replay:
             out[:] = self._replay.pop(0)
-        elif self._eof or not self.reader.read_frame_into(out):
+        elif self._pending:
+            self._take(self._pending.pop(0), out)
+        elif self._eof or not self._straight or not self.reader.read_frame_into(out):
             self._eof = True
             return False
         self.frames_read += 1
@@ -930,6 +959,55 @@ class FieldOrderSource:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class FieldOrderSource(LookAheadSource):
+    """A reader that probes the field order of a clip and hands out the wrapped reader's frames as they are.  decide() reads the first
+    `probe` frames (or the whole clip if it is shorter), takes the comb sums of the inner ones on the GPU, and sets `kinds`, `counts`,
+    `verdict` ("tff", "bff", "progressive" or None: FieldVerdict) and `note`, one log line with the four counts; then the probed frames are
+    replayed, and the frames behind the probe come straight from the reader: nothing watches them.
+
+    A chunk carries two frames, on the host and on the device: ssm_field_order_sums_fwd takes the frame before, the frame and the frame
+    after as rows b - 1, b, b + 1 of the device buffer, one pointer each and one stride.  The bytes handed out are the reader's; neither
+    they nor the verdict depend on frames_per_chunk."""
+    _straight = True
+
+    def __init__(self, reader, dev, probe=FIELD_PROBE, frames_per_chunk=8):
+        assert frames_per_chunk >= 1
+        super().__init__(reader, dev, "the field probe takes its comb sums", fields=True)
+        self.probe = parse_field_probe(probe)
+        self.kinds = self.counts = self.verdict = self.note = None
+        self._rows, self._decided = frames_per_chunk, False
+
+    def _sums(self, frames):
+        """The comb sums of frames 1 .. m - 2 of `frames` [m, frame_bytes]: uint64 [m - 2, 3]."""
+        m, c, h, w = frames.shape[0], self._rows, self.height, self.width
+        self._window(c, 2, 2, [((3,), torch.int64)])
+        out = np.zeros((max(m - 2, 0), 3), np.uint64)
+        for at in range(0, m, c):          # the chunk's new frames are at .. at + k - 1; it closes the inner frames whose next frame is new
+            k, lo = min(c, m - at), max(0, at - 2)
+            first, last = max(1, at - 1), at + k - 2
+            if last < first:
+                continue
+            cnt, b = last - first + 1, first - lo
+            self._np[:at + k - lo] = frames[lo:at + k]
+            (sums,) = self._measure(cnt, slice(0, at + k - lo), lambda dev, res: field_order_sums(
+                dev[b - 1:b - 1 + cnt], dev[b:b + cnt], dev[b + 1:b + 1 + cnt], h, w, self.bits, out=res))
+            out[first - 1:last] = sums
+        # nothing is measured behind the probe: the buffers go back to the allocators, where the run's pinned ring finds them
+        self._host = self._np = self._dev = self._dev_results = self._host_results = self._np_results = None
+        return out
+
+    def decide(self):
+        """The verdict of the probe: "tff", "bff", "progressive" or None.  Reads the probe frames on the first call."""
+        if not self._decided:
+            self._decided = True
+            self.sums = self._sums(self._probe(self.probe))
+            v = FieldVerdict.of_sums(self.sums)
+            self.kinds, self.counts, self.verdict, self.note = v.kinds, v.counts, v.verdict, v.note
+        return self.verdict
+
+    _ahead = decide
 
 
 # ---- YUV4MPEG2 ---------------------------------------------------------------------------------------------------------------------
@@ -1221,95 +1299,50 @@ def detelecine_host(frames, h, w, siting=CENTRED, bits=8):
     return np.stack(out), cadence
 
 
-class TelecineSource:
-    """A reader that undoes 3:2 pulldown: wraps a Y4MReader (or anything with its attributes) of telecined video and hands out the film's
-    frames, so that everything downstream sees a progressive clip at detelecine_rate(reader.rate).  It has the reader's format attributes,
-    interlace "p", frames_read (film frames handed out), and of the decision so far `cadence` (Cadence.log: per window its first frame, h,
-    best and second-best score), `dropped` and `combed_first`.
+class TelecineSource(LookAheadSource):
+    """A reader that undoes 3:2 pulldown: wraps a reader of telecined video and hands out the film's frames, so that everything
+    downstream sees a progressive clip at detelecine_rate(reader.rate).  It has interlace "p", frames_read (film frames handed out), and
+    of the decision so far `cadence` (Cadence.log: per window its first frame, h, best and second-best score), `dropped` and
+    `combed_first`.
 
-    A chunk is 5 * windows_per_chunk new frames behind the carried last frame of the chunk before, in one pinned buffer and one device
-    buffer that are made once.  Per chunk, on a stream of its own: one H2D, one ssm_field_diff_fwd (row n + 1 against row n, one stride
-    each), one D2H of the sums, one event wait; never a wait per frame.  Three film frames in four are straight copies out of the pinned
-    buffer, the fourth a row-strided numpy copy per plane.  The bytes handed out do not depend on windows_per_chunk."""
+    A chunk is 5 * windows_per_chunk new frames behind one carried frame: ssm_field_diff_fwd takes row n + 1 against row n, one stride
+    each.  Three film frames in four are straight copies out of the pinned buffer, the fourth a row-strided numpy copy per plane.  The
+    bytes handed out do not depend on windows_per_chunk."""
 
     def __init__(self, reader, dev, windows_per_chunk=2):
         assert windows_per_chunk >= 1
-        self.reader, self.dev = reader, torch.device(dev)
-        if self.dev.type != "cuda":
-            raise RuntimeError("pulldown removal takes its field differences on the GPU (the HIP path has no CPU fallback)")
-        for name in ("width", "height", "siting", "chroma", "color_range", "aspect", "xtags", "frame_bytes"):
-            setattr(self, name, getattr(reader, name))
-        self.bits, self.extended = getattr(reader, "bits", 8), getattr(reader, "extended", False)
-        self.sample_bytes = sample_bytes(self.bits)
+        super().__init__(reader, dev, "pulldown removal takes its field differences")
         field_dims(self.height, self.width, self.siting, "a telecined frame")
-        self.interlace, self.field_order, self.field_bytes, self.rate = "p", None, None, detelecine_rate(reader.rate)
-        self.frames_read, self._cadence = 0, Cadence()
-        rows = 5 * windows_per_chunk
-        self._host = torch.empty(rows + 1, self.frame_bytes, dtype=torch.uint8).pin_memory()
-        self._np = self._host.numpy()
-        self._dev = torch.empty(rows + 1, self.frame_bytes, dtype=torch.uint8, device=self.dev)
-        self._sums = torch.empty(rows, 2, dtype=torch.int64, device=self.dev)
-        self._host_sums = torch.empty(rows, 2, dtype=torch.int64).pin_memory()
-        self._np_sums = self._host_sums.numpy().view(np.uint64)
-        self._stream, self._event = torch.cuda.Stream(self.dev), torch.cuda.Event()
-        self._base = None          # the clip's frame in row 0 of the buffers; None before the first chunk
-        self._pending, self._eof = [], False
+        self.interlace, self.rate = "p", detelecine_rate(reader.rate)
+        self._cadence = Cadence()
+        self._window(5 * windows_per_chunk, 1, 1, [((2,), torch.int64)])
 
     def _chunk(self):
-        """The next chunk: its frames into the buffer behind the carried one, their field differences, and what the cadence closes."""
-        if self._base is None:
-            if not self.reader.read_frame_into(self._np[0]):
-                raise Y4MError("the Y4M stream holds no frame")
-            self._base = 0
-        else:
-            self._base += self._np.shape[0] - 1          # a chunk that is not the last one is full: its last row is carried
-            self._np[0] = self._np[-1]
-        k = 0
-        while k < self._np.shape[0] - 1 and self.reader.read_frame_into(self._np[1 + k]):
-            k += 1
-        self._eof = k < self._np.shape[0] - 1
+        """The next chunk: its frames' field differences and what the cadence closes, as (top rows' frame, bottom rows' frame)."""
+        k = self._fill()
+        closed = []
         if k:
-            with torch.cuda.stream(self._stream):
-                self._dev[:k + 1].copy_(self._host[:k + 1], non_blocking=True)
-                field_diff(self._dev[1:k + 1], self._dev[:k], self.height, self.width, self.bits, out=self._sums[:k])
-                self._host_sums[:k].copy_(self._sums[:k], non_blocking=True)
-                self._event.record()
-            self._event.synchronize()
-            for dt, db in self._np_sums[:k]:
-                self._pending += self._cadence.feed(dt, db)
+            (sums,) = self._measure(k, slice(0, k + 1), lambda dev, res: field_diff(dev[1:], dev[:-1], self.height, self.width, self.bits, out=res))
+            for dt, db in sums:
+                closed += self._cadence.feed(dt, db)
         if self._eof:
-            self._pending += self._cadence.end()
-        self._pending = [act for _, act in self._pending if act is not None]
+            closed += self._cadence.end()
+        self._pending += [act for _, act in closed if act is not None]
 
-    def read_frame_into(self, buf):
-        """The next film frame's payload into `buf`; False at the end of the clip."""
-        while not self._pending:
-            if self._eof:
-                return False
+    def _ahead(self):
+        while not self._pending and not self._eof:
             self._chunk()
-        t, b = self._pending.pop(0)
-        out = np.frombuffer(memoryview(buf).cast("B"), np.uint8)
-        if out.size != self.frame_bytes:
-            raise ValueError("buffer of %d bytes for frames of %d" % (out.size, self.frame_bytes))
+
+    def _take(self, act, out):
+        t, b = act
         if t == b:
             out[:] = self._np[t - self._base]
         else:
             _weave_rows(out, self._np[t - self._base], self._np[b - self._base], self.height, self.width, self.siting, self.bits)
-        self.frames_read += 1
-        return True
 
     cadence = property(lambda self: self._cadence.log)
     dropped = property(lambda self: self._cadence.dropped)
     combed_first = property(lambda self: self._cadence.combed_first)
-
-    def close(self):
-        self.reader.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 # ---- repeated frames ------------------------------------------------------------------------------------------------------------------
@@ -1475,70 +1508,36 @@ def dedup_host(frames, h, w, siting=CENTRED, bits=8, dedup=True, dedup_max=DEDUP
     return actions, rep
 
 
-class RepeatSource:
-    """A reader that takes the repaired repeats out of a clip: wraps a Y4MReader (or anything with its attributes, a TelecineSource for
-    one) and hands out the frames that stay, each with the gap before it - `gap` after read_frame_into: 0 for frame 0, 1 after an
-    ordinary neighbour, m + 1 behind a repaired run of m repeats - and, a frame ahead, `next_gap`: the gap of the frame that the next
-    call will hand out, 0 at the end of the clip (it is what tells a planner whether the pair to the right runs).  on_gap(g), if set, is
-    called once per frame that stays, in order, when its gap is known.  It has the reader's format attributes and rate, frames_read
-    (frames handed out), and of the decision so far `repeats` (Repeats.log).
+class RepeatSource(LookAheadSource):
+    """A reader that takes the repaired repeats out of a clip: wraps a reader (a TelecineSource for one) and hands out the frames that
+    stay, each with the gap before it - `gap` after read_frame_into: 0 for frame 0, 1 after an ordinary neighbour, m + 1 behind a repaired
+    run of m repeats - and, a frame ahead, `next_gap`: the gap of the frame that the next call will hand out, 0 at the end of the clip (it
+    is what tells a planner whether the pair to the right runs).  on_gap(g), if set, is called once per frame that stays, in order, when
+    its gap is known.  It has frames_read (frames handed out), and of the decision so far `repeats` (Repeats.log).
 
-    A chunk is frames_per_chunk new frames behind the carried last dedup_max + 1 frames of the chunk before, in one pinned buffer, and
-    with the last of those in one device buffer; both are made once.  Per chunk, on a stream of its own: one H2D, one ssm_block_sad_fwd
-    (row n + 1 against row n, one stride each), one D2H of the words, one event wait; never a wait per frame.  dedup_max + 1 frames are
-    carried because that many may still be wanted: the repeats that wait for the end of their run, and in front of them the frame that
-    stays and waits to be handed out until its right neighbour's gap is known.  The repeats' bytes go nowhere; the bytes handed out do
-    not depend on frames_per_chunk."""
+    A chunk is frames_per_chunk new frames behind dedup_max + 1 carried frames on the host and one on the device: ssm_block_sad_fwd takes
+    row n + 1 against row n, one stride each.  dedup_max + 1 frames are carried because that many may still be wanted: the repeats that
+    wait for the end of their run, and in front of them the frame that stays and waits to be handed out until its right neighbour's gap
+    is known.  The repeats' bytes go nowhere; the bytes handed out do not depend on frames_per_chunk."""
 
     def __init__(self, reader, dev, dedup=True, dedup_max=DEDUP_MAX, frames_per_chunk=8):
         assert frames_per_chunk >= 1
-        self.reader, self.dev = reader, torch.device(dev)
-        if self.dev.type != "cuda":
-            raise RuntimeError("the repeat test takes its block differences on the GPU (the HIP path has no CPU fallback)")
-        for name in ("width", "height", "siting", "chroma", "color_range", "aspect", "xtags", "frame_bytes", "rate"):
-            setattr(self, name, getattr(reader, name))
-        self.bits, self.extended = getattr(reader, "bits", 8), getattr(reader, "extended", False)
-        self.sample_bytes = sample_bytes(self.bits)
-        self.interlace, self.field_order, self.field_bytes = getattr(reader, "interlace", "p"), None, None
+        super().__init__(reader, dev, "the repeat test takes its block differences")
         hi, self.lo, frac = dedup_thresholds(dedup, self.bits)
         self._repeats = Repeats(hi, self.lo, frac, block_counts(self.height, self.width, self.siting), dedup_max)
-        self.frames_read, self.gap, self.on_gap = 0, None, None
-        self._rows, self._carry = frames_per_chunk, self._repeats.dedup_max + 1
-        self._host = torch.empty(self._carry + self._rows, self.frame_bytes, dtype=torch.uint8).pin_memory()      # [carried | the chunk]
-        self._np = self._host.numpy()
-        self._dev = torch.empty(self._rows + 1, self.frame_bytes, dtype=torch.uint8, device=self.dev)
-        self._words = torch.empty(self._rows, 3, 2, dtype=torch.int64, device=self.dev)
-        self._host_words = torch.empty(self._rows, 3, 2, dtype=torch.int64).pin_memory()
-        self._np_words = self._host_words.numpy().view(np.uint64)
-        self._stream, self._event = torch.cuda.Stream(self.dev), torch.cuda.Event()
-        self._base = None          # the clip's frame in row 0 of the pinned buffer (below 0 in the first chunk); None before it
-        self._pending, self._eof = [], False          # [(a frame that stays, its gap)], not yet handed out
-        self._last_kept = 0
+        self.gap, self.on_gap = None, None
+        self._window(frames_per_chunk, self._repeats.dedup_max + 1, 1, [((3, 2), torch.int64)])
+        self._last_kept = 0          # _pending: [(a frame that stays, its gap)]
 
     def _chunk(self):
-        """The next chunk: its frames into the buffer behind the carried ones, their block differences, and what the decision closes."""
-        rows, c = self._rows, self._carry
-        if self._base is None:
-            if not self.reader.read_frame_into(self._np[c - 1]):
-                raise Y4MError("the Y4M stream holds no frame")
-            self._base = 1 - c
-        else:
-            self._base += rows          # a chunk that is not the last one is full
-            self._np[:c] = self._np[rows:rows + c].copy()
-        k = 0
-        while k < rows and self.reader.read_frame_into(self._np[c + k]):
-            k += 1
-        self._eof = k < rows
+        """The next chunk: its frames' block differences and what the decision closes."""
+        k, c = self._fill(), self._carry
         closed = []
         if k:
-            with torch.cuda.stream(self._stream):
-                self._dev[:k + 1].copy_(self._host[c - 1:c + k], non_blocking=True)
-                block_sad(self._dev[1:k + 1], self._dev[:k], self.height, self.width, self.siting, self.bits, self.lo, out=self._words[:k])
-                self._host_words[:k].copy_(self._words[:k], non_blocking=True)
-                self._event.record()
-            self._event.synchronize()
-            for words in self._np_words[:k]:
-                closed += self._repeats.feed(words)
+            (words,) = self._measure(k, slice(c - 1, c + k), lambda dev, res: block_sad(
+                dev[1:], dev[:-1], self.height, self.width, self.siting, self.bits, self.lo, out=res))
+            for six in words:
+                closed += self._repeats.feed(six)
         if self._eof:
             closed += self._repeats.end()
         for n, act in closed:
@@ -1551,31 +1550,17 @@ class RepeatSource:
 
     next_gap = property(lambda self: self._pending[0][1] if self._pending else 0)
 
-    def read_frame_into(self, buf):
-        """The next frame that stays into `buf`; False at the end of the clip.  `gap` is then its gap, `next_gap` the next one's."""
+    def _ahead(self):          # a frame ahead: `next_gap` is known when a frame goes out
         while len(self._pending) < 2 and not self._eof:
             self._chunk()
-        if not self._pending:
-            return False
-        n, self.gap = self._pending.pop(0)
-        out = np.frombuffer(memoryview(buf).cast("B"), np.uint8)
-        if out.size != self.frame_bytes:
-            raise ValueError("buffer of %d bytes for frames of %d" % (out.size, self.frame_bytes))
+
+    def _take(self, kept, out):
+        """A frame that stays into `out`; `gap` is then its gap, `next_gap` the next one's."""
+        n, self.gap = kept
         assert 0 <= n - self._base < self._np.shape[0], "a frame that stays is among the carried frames or in the chunk"
         out[:] = self._np[n - self._base]
-        self.frames_read += 1
-        return True
 
     repeats = property(lambda self: self._repeats.log)
-
-    def close(self):
-        self.reader.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 # ---- letterboxed clips: the active area ------------------------------------------------------------------------------------------------
@@ -1805,135 +1790,76 @@ def window_cut(frames, h, w, siting, bits, rect, out=None):
     return out
 
 
-class ActiveSource:
-    """A reader that finds and watches the active area of a letterboxed clip: wraps a Y4MReader (or anything with its attributes, a
-    TelecineSource for one) and hands out its frames as they are.  `active`: what parse_active returns - ("auto", limit, frac) or an
-    explicit (w, h, x, y), checked against the frame.  decide() -> `area`, the rectangle or None for a whole-frame run, and `note`, one
-    line that says which and why; with "auto" it reads the first `probe` frames (or the whole clip if it is shorter) into a host buffer,
-    counts them on the GPU, decides (ActiveArea) and replays them.  With an area, every later frame is counted a chunk ahead of the loop,
-    and a frame with active rows or columns outside the rectangle goes to `excess` as (frame index, rows outside, columns outside); it
-    changes nothing else.  Without one (the fallback) the frames behind the probe come straight from the reader.
+class ActiveSource(LookAheadSource):
+    """A reader that finds and watches the active area of a letterboxed clip: wraps a reader (a TelecineSource for one) and hands out its
+    frames as they are.  `active`: what parse_active returns - ("auto", limit, frac) or an explicit (w, h, x, y), checked against the
+    frame.  decide() -> `area`, the rectangle or None for a whole-frame run, and `note`, one line that says which and why; with "auto" it
+    reads the first `probe` frames (or the whole clip if it is shorter), counts them on the GPU, decides (ActiveArea) and replays them.
+    With an area, every later frame is counted a chunk ahead of the loop, and a frame with active rows or columns outside the rectangle
+    goes to `excess` as (frame index, rows outside, columns outside); it changes nothing else.  Without one (the fallback) the frames
+    behind the probe come straight from the reader.
 
-    A chunk is frames_per_chunk frames in one pinned buffer and one device buffer, made once.  Per chunk, on a stream of its own: one H2D,
-    one ssm_luma_counts_fwd, one D2H of the counts, one event wait; never a wait per frame.  The bytes handed out do not depend on
-    frames_per_chunk or probe."""
+    A chunk is frames_per_chunk frames, none carried, for one ssm_luma_counts_fwd; its buffers are made when the first frame is counted,
+    so a whole-frame run with an explicit rectangle makes none.  The bytes handed out do not depend on frames_per_chunk or probe."""
 
     def __init__(self, reader, dev, active=("auto", None, ACTIVE_FRAC), probe=ACTIVE_PROBE, frames_per_chunk=8):
         assert frames_per_chunk >= 1
-        self.reader, self.dev = reader, torch.device(dev)
-        if self.dev.type != "cuda":
-            raise RuntimeError("the active area takes its luma counts on the GPU (the HIP path has no CPU fallback)")
-        for name in ("width", "height", "siting", "chroma", "color_range", "aspect", "xtags", "frame_bytes", "rate"):
-            setattr(self, name, getattr(reader, name))
-        self.bits, self.extended = getattr(reader, "bits", 8), getattr(reader, "extended", False)
-        self.sample_bytes = sample_bytes(self.bits)
-        self.interlace, self.field_order, self.field_bytes = getattr(reader, "interlace", "p"), None, None
+        super().__init__(reader, dev, "the active area takes its luma counts")
         active = parse_active(active)
         assert active is not None
         self.auto = active[0] == "auto"
         self.limit = active_limit(self.bits, active[1] if self.auto else None)
         self._area = ActiveArea(self.height, self.width, self.siting, active[2] if self.auto else ACTIVE_FRAC)
         self._given = None if self.auto else check_active(active, self.height, self.width, self.siting)
-        self.probe, self.area, self.note, self.excess, self.frames_read = parse_active_probe(probe), None, None, [], 0
-        self._rows, self._decided = frames_per_chunk, False
-        self._replay, self._pending, self._eof, self._counted = [], [], False, 0          # probed frames; counted frames not yet handed out
-        self._host = self._np = None
-
-    def _buffers(self):
-        if self._host is None:
-            c, h, w = self._rows, self.height, self.width
-            self._host = torch.empty(c, self.frame_bytes, dtype=torch.uint8).pin_memory()
-            self._np = self._host.numpy()
-            self._dev = torch.empty(c, self.frame_bytes, dtype=torch.uint8, device=self.dev)
-            self._dev_counts = (torch.empty(c, h, dtype=torch.int32, device=self.dev), torch.empty(c, w, dtype=torch.int32, device=self.dev))
-            self._host_counts = tuple(torch.empty(t.shape, dtype=torch.int32).pin_memory() for t in self._dev_counts)
-            self._np_counts = tuple(t.numpy().view(np.uint32) for t in self._host_counts)
-            self._stream, self._event = torch.cuda.Stream(self.dev), torch.cuda.Event()
+        self.probe, self.area, self.note, self.excess = parse_active_probe(probe), None, None, []
+        self._rows, self._decided, self._counted = frames_per_chunk, False, 0          # _counted: the clip's frames counted so far
 
     def _count(self, k):
         """The counts of the first k rows of the pinned buffer: (rows [k, h], cols [k, w]) uint32, views of pinned memory."""
-        with torch.cuda.stream(self._stream):
-            self._dev[:k].copy_(self._host[:k], non_blocking=True)
-            luma_counts(self._dev[:k], self.height, self.width, self.bits, self.limit, self._dev_counts[0][:k], self._dev_counts[1][:k])
-            for hc, dc in zip(self._host_counts, self._dev_counts):
-                hc[:k].copy_(dc[:k], non_blocking=True)
-            self._event.record()
-        self._event.synchronize()
-        return self._np_counts[0][:k], self._np_counts[1][:k]
+        return self._measure(k, slice(0, k), lambda dev, rows, cols: luma_counts(dev, self.height, self.width, self.bits, self.limit, rows, cols))
 
-    def _watch(self, rows, cols):
-        for r, c in zip(rows, cols):
-            out = self._area.outside(r, c, self.area)
-            if out != (0, 0):
-                self.excess.append((self._counted,) + out)
-            self._counted += 1
+    def _buffers(self):
+        if self._np is None:
+            self._window(self._rows, 0, 0, [((self.height,), torch.int32), ((self.width,), torch.int32)])
 
     def decide(self):
         """The rectangle of the run, (w, h, x, y), or None: a whole-frame run; `note` says why.  Reads the probe frames on the first call."""
         if self._decided:
             return self.area
         self._decided = True
-        if not self.auto:
+        if self.auto:
+            self._buffers()
+            probe = self._probe(self.probe)
+            for at in range(0, len(probe), self._rows):
+                k = min(self._rows, len(probe) - at)
+                self._np[:k] = probe[at:at + k]
+                for r, c in zip(*self._count(k)):
+                    self._area.feed(r, c)
+            self.area, self.note = self._area.decide(), self._area.note
+            self._counted = len(probe)          # inside the rectangle by construction
+        else:
             whole = self._given == (self.width, self.height, 0, 0)
             self.area = None if whole else self._given
             self.note = "the active area is the whole frame" if whole else "the active area is %d:%d:%d:%d (W:H:X:Y), as given" % self._given
-            return self.area
-        self._buffers()
-        probe = np.empty((self.probe, self.frame_bytes), np.uint8)
-        n = 0
-        while n < self.probe and self.reader.read_frame_into(probe[n]):
-            n += 1
-        self._eof = n < self.probe
-        for at in range(0, n, self._rows):
-            k = min(self._rows, n - at)
-            self._np[:k] = probe[at:at + k]
-            for r, c in zip(*self._count(k)):
-                self._area.feed(r, c)
-        self.area, self.note = self._area.decide(), self._area.note
-        self._replay = [probe[i] for i in range(n)]
-        self._counted = n          # inside the rectangle by construction
+        self._straight = self.area is None
         return self.area
 
     def _chunk(self):
-        """The next chunk behind the probe: its frames into the pinned buffer, their counts, the frames that leave the rectangle."""
+        """The next chunk behind the probe: its frames' counts, and the frames that leave the rectangle to `excess`."""
         self._buffers()
-        k = 0
-        while k < self._rows and self.reader.read_frame_into(self._np[k]):
-            k += 1
-        self._eof = k < self._rows
+        k = self._fill()
         if k:
-            self._watch(*self._count(k))
-            self._pending = list(range(k))
+            for r, c in zip(*self._count(k)):
+                out = self._area.outside(r, c, self.area)
+                if out != (0, 0):
+                    self.excess.append((self._counted,) + out)
+                self._counted += 1
+            self._pending = list(range(self._base, self._base + k))
 
-    def read_frame_into(self, buf):
-        """The next frame's payload into `buf`; False at the end of the clip."""
-        self.decide()
-        out = np.frombuffer(memoryview(buf).cast("B"), np.uint8)
-        if out.size != self.frame_bytes:
-            raise ValueError("buffer of %d bytes for frames of %d" % (out.size, self.frame_bytes))
-        if self._replay:
-            out[:] = self._replay.pop(0)
-        elif self.area is None:
-            if self._eof or not self.reader.read_frame_into(out):
-                self._eof = True
-                return False
-        else:
-            while not self._pending:
-                if self._eof:
-                    return False
+    def _ahead(self):
+        if self.decide() is not None and not self._replay:
+            while not self._pending and not self._eof:
                 self._chunk()
-            out[:] = self._np[self._pending.pop(0)]
-        self.frames_read += 1
-        return True
-
-    def close(self):
-        self.reader.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
 
 # ---- blocks that do not change ---------------------------------------------------------------------------------------------------------
@@ -2914,6 +2840,12 @@ class VideoInterpolator:
                                             blend=self.blend))
         return self._pipe[1]
 
+    def _model_device(self):
+        dev = next(self.model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
+        return dev
+
     def _clip(self, reader, writer, window=None):
         """The Clip of a run, or the refusal of a writer of another format or of a model that is not on the GPU.  window: the active area of
         a letterboxed clip; the default matrix stays the one of the frame's height."""
@@ -2925,10 +2857,7 @@ class VideoInterpolator:
                              "samples, these have %d bits" % (reader.chroma, bits))
         matrix = default_matrix(h) if self.matrix is None else self.matrix
         crange = self.color_range if self.color_range is not None else (reader.color_range if reader.color_range is not None else LIMITED)
-        dev = next(self.model.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
-        return Clip(h, w, siting, matrix, crange, self.cfg, bits, 32 * self.flow_scale, dev=dev, window=window)
+        return Clip(h, w, siting, matrix, crange, self.cfg, bits, 32 * self.flow_scale, dev=self._model_device(), window=window)
 
     def _cut_state(self, on, n, depth, pairs, clip):
         """What the scene cuts add to a mode's buffers: SceneCuts, the sums of a pass on the device (per stream) and in the pinned ring slot
@@ -3005,10 +2934,7 @@ class VideoInterpolator:
         if isinstance(reader, TelecineSource):
             raise ValueError("field_probe together with detelecine is not available: a telecined clip is a mixture of progressive and "
                              "combed frames by construction, and pulldown removal finds its field order itself")
-        dev = next(self.model.parameters()).device
-        if dev.type != "cuda":
-            raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
-        source = FieldOrderSource(reader, dev, self.field_probe_option)
+        source = FieldOrderSource(reader, self._model_device(), self.field_probe_option)
         verdict = source.decide()
         order = warning = advice = None
         self._probed_order = None
@@ -3040,10 +2966,7 @@ class VideoInterpolator:
             reader = self.probe_fields(reader)
         self._probed = None          # one run per probe
         if self.active_option is not None:
-            dev = next(self.model.parameters()).device
-            if dev.type != "cuda":
-                raise RuntimeError("the model must be on the GPU (the HIP path has no CPU fallback)")
-            reader = ActiveSource(reader, dev, self.active_option, self.active_probe)
+            reader = ActiveSource(reader, self._model_device(), self.active_option, self.active_probe)
             self.active, self.active_note, self.active_excess = reader.decide(), reader.note, reader.excess
         clip = self._clip(reader, writer, self.active)
         if self.dedup is not None:
