@@ -13,7 +13,10 @@
   VideoInterpolator       the streamed loop: every leg of a pass (H2D, ingest, the pair pipeline, egress, D2H) is queued on the pass's HIP
                           stream, a writer thread drains a ring of pinned buffers in order; memory does not depend on the clip's length
   PassRing / read_passes  what its four modes (fixed grid, timeline, shutter, fields) share beside the prologue, the Clip with its two conversions and
-  / upload_times          their buffers: the ring with its writer thread and failure protocol (no GPU in it), the planners' read loop, a pass's times
+  / read_blocks /         their buffers: the ring with its writer thread and failure protocol (no GPU in it), the planners' read loop and the
+  upload_times            block modes' (pairs_per_batch new units behind a carried one: fixed grid, fields, video_score's scorer), a pass's times
+  PairOptions             the per-pair options of the fixed grid and the timeline in one per-run object: scene cuts, static blocks, the window
+                          of a letterboxed clip - their buffers, the carry of row 0 (two protocols, argued there), their calls, the writer's rows
 
   Timeline / PassPlanner  any output rate and speed: where each output frame sits on the input's clock, exactly (Fractions, closed form),
                           and the bookkeeping of the passes that follow it - VideoInterpolator(target_rate=, speed=)
@@ -2565,6 +2568,30 @@ def read_passes(reader, ring, plan, np_in, issue):
         raise Y4MError("the Y4M stream holds no frame")
 
 
+def first_frame(reader, buf):
+    """Frame 0 of a block mode into `buf`, ahead of its passes; a stream without one is refused."""
+    if not reader.read_frame_into(buf):
+        raise Y4MError("the Y4M stream holds no frame")
+
+
+def read_blocks(ring, pb, np_in, read_unit, issue):
+    """The read loop of the block modes (the fixed grid, the fields, video_score's hold-out scorer), whose passes are `pb` new units behind
+    a carried one, frame 0 being the mode's own business: per pass a ring slot r and read_unit(r, i), i = 0 .. pb - 1, until it says that
+    the stream has ended (for the interpolator one frame into np_in[r][i]; for the scorer a group of frames, the last of them there);
+    then issue(r, valid) - also for the pass that found nothing, whose slot goes back empty.  A pass short of units is the last one, and
+    its input rows are filled with copies of its last unit's: the engine runs on whole passes, what the extra pairs make is not written."""
+    while not ring.failure:
+        r = ring.take()
+        valid = 0
+        while valid < pb and read_unit(r, valid):
+            valid += 1
+        if 0 < valid < pb:
+            np_in[r][valid:] = np_in[r][valid - 1]
+        issue(r, valid)
+        if valid < pb:
+            return
+
+
 def sad_runs(lefts, rights):
     """[(first pair, count)]: the pairs of a pass in maximal runs whose left rows and whose right rows both step evenly - what one
     ssm_luma_sad_fwd call addresses with its two strides.  One run whenever every pair of the pass follows the one before (the fixed
@@ -2593,28 +2620,170 @@ def upload_times(times, slots, np_t, host_t, dev_t):
     dev_t.copy_(host_t, non_blocking=True)
 
 
+RingSlots = namedtuple("RingSlots", "host_in host_out host_t np_in np_out np_t done")
+StreamBuffers = namedtuple("StreamBuffers", "dev_in dev_out dev_t ingested dev_win")
+
+
 def ring_slots(depth, fb, rows_in, rows_out, n_t=None, fb_out=None):
-    """What a mode's `depth` ring slots hold, a list each: pinned host_in [rows_in, fb], host_out [rows_out, fb_out] (None: fb, one frame
-    size for both) and host_t (n_t times, 0.5
-    throughout so that entries no pass fills stay finite; None where the mode has no times), their numpy views, the `done` events."""
+    """What a mode's `depth` ring slots hold, a RingSlots of lists: pinned host_in [rows_in, fb], host_out [rows_out, fb_out] (None: fb, one
+    frame size for both) and host_t (n_t times, 0.5 throughout so that entries no pass fills stay finite; None where the mode has no
+    times), their numpy views, the `done` events."""
     host_in, host_out = ([torch.empty(rows, size, dtype=torch.uint8).pin_memory() for _ in range(depth)]
                          for rows, size in ((rows_in, fb), (rows_out, fb if fb_out is None else fb_out)))
     host_t = None if n_t is None else [torch.full((n_t,), 0.5, dtype=torch.float32).pin_memory() for _ in range(depth)]
     np_in, np_out, np_t = (None if b is None else [t.numpy() for t in b] for b in (host_in, host_out, host_t))
-    return host_in, host_out, host_t, np_in, np_out, np_t, [torch.cuda.Event() for _ in range(depth)]
+    return RingSlots(host_in, host_out, host_t, np_in, np_out, np_t, [torch.cuda.Event() for _ in range(depth)])
 
 
 def stream_buffers(n, dev, fb, rows_in, rows_out, n_t=None, fb_out=None):
-    """What a mode's n streams hold on the device, a list each: dev_in, dev_out, dev_t (as in ring_slots; not initialised), `ingested`.
-    With fb_out, the window's size of a letterboxed clip, a fifth list: dev_win [rows_in, fb_out], the scratch the cut windows of dev_in's
-    rows go to, row for row."""
+    """What a mode's n streams hold on the device, a StreamBuffers of lists: dev_in, dev_out, dev_t (as in ring_slots; not initialised),
+    `ingested`, and dev_win - None, or with fb_out, the window's size of a letterboxed clip, [rows_in, fb_out]: the scratch the cut windows
+    of dev_in's rows go to, row for row; dev_out's rows are then of that size too."""
     dev_in, dev_out = ([torch.empty(rows, size, dtype=torch.uint8, device=dev) for _ in range(n)]
                        for rows, size in ((rows_in, fb), (rows_out, fb if fb_out is None else fb_out)))
-    if fb_out is not None:
-        dev_t = None if n_t is None else [torch.empty(n_t, dtype=torch.float32, device=dev) for _ in range(n)]
-        return dev_in, dev_out, dev_t, [torch.cuda.Event() for _ in range(n)], [torch.empty(rows_in, fb_out, dtype=torch.uint8, device=dev) for _ in range(n)]
     dev_t = None if n_t is None else [torch.empty(n_t, dtype=torch.float32, device=dev) for _ in range(n)]
-    return dev_in, dev_out, dev_t, [torch.cuda.Event() for _ in range(n)]
+    dev_win = None if fb_out is None else [torch.empty(rows_in, fb_out, dtype=torch.uint8, device=dev) for _ in range(n)]
+    return StreamBuffers(dev_in, dev_out, dev_t, [torch.cuda.Event() for _ in range(n)], dev_win)
+
+
+class PairOptions:
+    """The per-pair options of one run of the fixed grid or of the timeline - scene cuts, static blocks, the window of a letterboxed clip -
+    in one place: what they add to the run's buffers, what they queue on a pass's stream, and what they decide on the writer thread.  With
+    an option off nothing of it is allocated or queued, and with all three off a pass is, launch for launch, the loop without them.
+    log: the VideoInterpolator whose `cuts` and `static` take the notes.
+
+    Buffers (buffers()).  With scene cuts or static blocks a stream's payload buffer has `lead` = 1 row in front of the pass's frames.  A pass
+    names its pairs by rows of that buffer - pairs(k, lefts, rights): the fixed grid's are rows 0 .. pb - 1 against 1 .. pb, the timeline's
+    whatever its planner kept - and row 0 stands for the right frame of the pair that ran last in the pass before, the left frame of this
+    pass's first pair unless that pair brought its own.  The luma sums and the block counts of a pass sit per stream on the device and per
+    ring slot in pinned memory; the counts go back behind the paste calls, the sums (download()) behind the pass's frames, both ahead of `done`.  With a window the frames
+    come up into dev_up and Clip.ingest cuts their windows into dev_in, row for row, which is what everything here reads; without one
+    dev_up is dev_in.
+
+    Row 0 is carried by one of two protocols; why each is safe is said here and nowhere else.
+      Scene cuts alone FORWARD it: ssm_luma_sad_fwd runs ahead of the pass's `ingested`, and behind its calls - still ahead of that
+      record - pairs() copies the Y plane of the pass's last right frame into row 0 of the NEXT stream's buffer.  The pass that reads the
+      row waits for that `ingested` before it ingests; the pass that read the row before, on that same next stream, recorded its own
+      `ingested` - behind its calls - earlier in the chain of waits that this pass stands behind.  The fixed grid seeds it from frame 0.
+      Static blocks FETCH it (and with both options the fetched row serves the luma sums too): ssm_static_paste_fwd reads a pair's
+      payloads behind the egress, long after the pass has recorded `ingested`, so no other stream may write the row.  carry_in() copies
+      the whole frame on the pass's own stream from row `last_right` of the stream before - behind a wait for that stream's `ingested`,
+      ahead of the pass's own uploads; with one stream the source is the stream's own row, read before the uploads overwrite it.  The source
+      row is next written by the upload of pass j + n - 1, which stands behind a chain of waits that ends at this pass's `ingested`,
+      recorded after the fetch.
+
+    The writer thread (rows() -> written()): PassRing calls it once the pass's event has come.  It notes the pass's block counts in
+    `static`, feeds SceneCuts the luma sums in the order the pairs ran and notes the cuts, then yields the pass's rows: an input frame as
+    it is; a synthesised frame of a cut pair replaced, whole, by the nearer input frame (t < 1/2: the left one); any other synthesised
+    frame as it is or, with a window, pasted into the nearer input frame's bars (one buffer, written before the next is asked for).  At
+    the end `carried`, the writer thread's copy of the frame that row 0 stands for, takes the last pair's right frame: its ring slot is
+    free by the time the next pass's rows are written."""
+
+    def __init__(self, log, clip, scene_cut=None, static=None):
+        self.log, self.clip, self.static = log, clip, static
+        self.cuts = None if scene_cut is None else SceneCuts(scene_cut)
+        self.pixels, self.blocks = clip.h * clip.w, static_blocks(clip.h, clip.w)
+        self.lead = 0 if self.cuts is None and static is None else 1
+        self.near = self.cuts is not None or clip.window is not None          # the writer thread looks at a pair's input frames
+        self.carried = np.empty(clip.fb, np.uint8) if self.near else None
+        self.paste, self.last_right = None, 0
+        if clip.window is not None:
+            out = np.empty(clip.fb_in, np.uint8)
+            self.paste = lambda window, near: paste_window_host(window, near, *clip.frame, clip.siting, clip.bits, clip.window, out=out)
+
+    def buffers(self, n, depth, pairs, rows_in, rows_out, n_t=None):
+        """-> the StreamBuffers of n streams whose passes take rows_in payload rows (behind `lead`) and `pairs` pairs, on `depth` ring slots."""
+        clip = self.clip
+        sb = stream_buffers(n, clip.dev, clip.fb, self.lead + rows_in, rows_out, n_t, None if clip.window is None else clip.fb_out)
+        self.n, self.ingested, self.dev_up, self.dev_in = n, sb.ingested, sb.dev_in, sb.dev_in if sb.dev_win is None else sb.dev_win
+
+        def words():
+            host = [torch.empty(pairs, dtype=torch.int64).pin_memory() for _ in range(depth)]
+            return [torch.empty(pairs, dtype=torch.int64, device=clip.dev) for _ in range(n)], host, [t.numpy().view(np.uint64) for t in host]
+
+        if self.cuts is not None:
+            self.dev_sums, self.host_sums, self.np_sums = words()
+        if self.static is not None:
+            self.dev_counts, self.host_counts, self.np_counts = words()
+        return sb
+
+    def seed(self, frame, k, row, fetch_row):
+        """Frame 0 of the fixed grid - `frame` on the host, row `row` of dev_in[k] on the current stream, ahead of `ingested` - as the
+        frame that pass 0's row 0 stands for: where pass 0 fetches it (fetch_row: the last row, where every later pass leaves its own),
+        or forwarded."""
+        if self.carried is not None:
+            self.carried[:] = frame
+        if self.static is not None:
+            if fetch_row != row:
+                self.dev_in[k][fetch_row].copy_(self.dev_in[k][row])
+            self.last_right = fetch_row
+        elif self.cuts is not None:
+            self.dev_in[(k + 1) % self.n][0, :self.pixels].copy_(self.dev_in[k][row, :self.pixels])
+
+    def carry_in(self, st, k, kprev, waited=False):
+        """Ahead of the pass's uploads, the fetch of row 0; waited: the stream stands behind ingested[kprev] already."""
+        if self.static is not None:
+            if not waited:
+                st.wait_event(self.ingested[kprev])
+            self.dev_in[k][0].copy_(self.dev_in[kprev][self.last_right])
+
+    def pairs(self, k, lefts, rights):
+        """Behind the pass's ingest and ahead of its `ingested`: the pass's pairs as rows of dev_in[k]; one ssm_luma_sad_fwd call per
+        sad_runs run, and the forwarding of row 0."""
+        self.lefts, self.rights, self.last_right = lefts, rights, rights[-1]
+        if self.cuts is not None:
+            d = self.dev_in[k]
+            for p, m in sad_runs(lefts, rights):
+                da, db = (lefts[p + 1] - lefts[p], rights[p + 1] - rights[p]) if m > 1 else (1, 1)
+                luma_sad(d[lefts[p]:lefts[p] + (m - 1) * da + 1:da], d[rights[p]:rights[p] + (m - 1) * db + 1:db], self.clip.h, self.clip.w,
+                         out=self.dev_sums[k][p:p + m])
+            if self.static is None:
+                self.dev_in[(k + 1) % self.n][0, :self.pixels].copy_(d[rights[-1], :self.pixels])
+
+    def paste_static(self, r, k, groups):
+        """Behind the egress and ahead of the D2H copies of the frames: one ssm_static_paste_fwd call per group (first pair, pairs whose
+        rows follow one another, their outputs [pairs * T, frame bytes]) that the mode names, then the counts' way back to ring slot r."""
+        if self.static is not None:
+            clip, d = self.clip, self.dev_in[k]
+            for p, m, outputs in groups:
+                static_paste(d[self.lefts[p]:self.lefts[p] + m], d[self.rights[p]:self.rights[p] + m], outputs, clip.h, clip.w, clip.siting,
+                             clip.bits, self.static, counts=self.dev_counts[k][p:p + m])
+            self.host_counts[r].copy_(self.dev_counts[k], non_blocking=True)
+
+    def download(self, r, k):
+        """Behind the D2H copies of the frames and ahead of `done`: the luma sums' way back to ring slot r."""
+        if self.cuts is not None:
+            self.host_sums[r].copy_(self.dev_sums[k], non_blocking=True)
+
+    def rows(self, r, index, rows, near):
+        """What PassRing.hand takes for a pass on ring slot r.  index: the clip's i of its pairs (i, i + 1) in the order they ran; rows: its
+        buffers in write order; near() -> (pairs, at), asked for only where the writer thread looks at input frames: [(i, the left frame's
+        host bytes or None for `carried`, the right frame's)] and per row None for an input frame or (pair's place in `pairs`, exact t).
+        With every option off: `rows` itself."""
+        if not self.near and self.static is None:
+            return rows
+        pairs, at = near() if self.near else ((), [None] * len(rows))
+        return functools.partial(self.written, list(index), self.np_sums[r] if self.cuts is not None else None,
+                                 self.np_counts[r] if self.static is not None else None, pairs, list(zip(rows, at)))
+
+    def written(self, index, sums, counts, pairs, order):
+        """The generator behind rows(); sums, counts: the pass's words in its ring slot, None with the option off."""
+        if counts is not None:
+            self.log.static.extend((i, int(counts[p]), self.blocks) for p, i in enumerate(index))
+        verdict = [False] * len(pairs)
+        if sums is not None:
+            for p, i in enumerate(index):
+                verdict[p], score = self.cuts.feed(int(sums[p]), self.pixels)
+                if verdict[p]:
+                    self.log.cuts.append((i, score))
+        for buf, at in order:
+            if at is not None and (verdict[at[0]] or self.paste is not None):
+                _, lf, rt = pairs[at[0]]
+                near = (self.carried if lf is None else lf) if at[1] < Fraction(1, 2) else rt
+                buf = near if verdict[at[0]] else self.paste(buf, near)
+            yield buf
+        if pairs:
+            self.carried[:] = pairs[-1][2]
 
 
 FieldProbe = namedtuple("FieldProbe", "verdict counts kinds order note warning advice")          # VideoInterpolator.field_probe
@@ -2632,8 +2801,9 @@ class VideoInterpolator:
 
     The four modes (_run_fixed, _run_timeline, _run_shutter, _run_fields) share what is not on a stream: the prologue (_clip) and the Clip's two
     conversions, the allocation of what a ring slot and a stream hold (ring_slots, stream_buffers), the ring with its writer thread and
-    failure protocol (PassRing), the planners' read loop and issue of passes (read_passes, _run_passes), the fill of a pass's times
-    (upload_times).  Each keeps its own submit: what is queued on a pass's stream, call for call, is what its bytes and its rate rest on."""
+    failure protocol (PassRing), the read loops (read_passes for the planners, read_blocks for the fixed grid and the fields) and the
+    issue of passes (_run_passes), the fill of a pass's times (upload_times); the fixed grid and the timeline drive one PairOptions for
+    scene cuts, static blocks and the letterbox window.  Each keeps its own submit: what is queued on a pass's stream, call for call, is what its bytes and its rate rest on."""
 
     def __init__(self, model, cfg, upsample_rate=None, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
                  tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8, scene_cut=None,
@@ -2859,73 +3029,6 @@ class VideoInterpolator:
         crange = self.color_range if self.color_range is not None else (reader.color_range if reader.color_range is not None else LIMITED)
         return Clip(h, w, siting, matrix, crange, self.cfg, bits, 32 * self.flow_scale, dev=self._model_device(), window=window)
 
-    def _cut_state(self, on, n, depth, pairs, clip):
-        """What the scene cuts add to a mode's buffers: SceneCuts, the sums of a pass on the device (per stream) and in the pinned ring slot
-        (per slot, with its numpy view as uint64), the writer thread's copy of the input frame before the next pass's first pair; and `lead` =
-        1, the rows they put in front of a stream's payloads.  Not `on`: None for each, and 0."""
-        if not on:
-            return (None,) * 5, 0
-        host = [torch.empty(pairs, dtype=torch.int64).pin_memory() for _ in range(depth)]
-        return (SceneCuts(self.scene_cut), [torch.empty(pairs, dtype=torch.int64, device=clip.dev) for _ in range(n)], host,
-                [t.numpy().view(np.uint64) for t in host], np.empty(clip.fb, np.uint8)), 1
-
-    def _static_state(self, n, depth, pairs, clip):
-        """What static blocks add to a mode's buffers: the counts of a pass on the device (per stream) and in the pinned ring slot (per slot,
-        with its numpy view as uint64).  Without the option: None for each."""
-        if self.static_lo is None:
-            return None, None, None
-        host = [torch.empty(pairs, dtype=torch.int64).pin_memory() for _ in range(depth)]
-        return [torch.empty(pairs, dtype=torch.int64, device=clip.dev) for _ in range(n)], host, [t.numpy().view(np.uint64) for t in host]
-
-    def _static_rows(self, counts, index, blocks, rows):
-        """The rows of a pass with static blocks, called by PassRing on the writer thread once the pass's event has come: notes the counts of
-        the pass's pairs (`index`: their clip indices, in the order of `counts`) in `static`, then hands on `rows` - a list, or the
-        callable of the scene cuts, whose replacement of a cut pair's frames stands."""
-        self.static.extend((i, int(counts[p]), blocks) for p, i in enumerate(index))
-        return rows() if callable(rows) else rows
-
-    @staticmethod
-    def _paster(clip):
-        """paste(window's bytes, an input frame's bytes) -> a full frame for the writer thread, or None for a clip without a window.  The
-        frame it returns is one buffer, written before the next is asked for (PassRing writes row by row)."""
-        if clip.window is None:
-            return None
-        out = np.empty(clip.fb_in, np.uint8)
-        return lambda window, near: paste_window_host(window, near, *clip.frame, clip.siting, clip.bits, clip.window, out=out)
-
-    def _cut_rows(self, cuts, pixels, sums, pairs, order, carried, paste=None):
-        """The rows of a pass under scene cuts: a generator that PassRing calls on the writer thread once the pass's event has come.
-        sums: the pass's luma sums in its ring slot; pairs: [(i, left frame's host bytes or None for `carried`, right frame's)] in the
-        order in which they ran; order: [(input frame's bytes, None) | (synthesised frame's bytes, (pair's place in `pairs`, exact t))] in
-        write order.  Feeds SceneCuts, notes the cuts, and puts the nearer input frame in the place of a cut pair's synthesised frames;
-        at the end `carried` takes the last pair's right frame, the left frame of a next pass's first pair (its slot is free by then).
-        paste: of a letterboxed clip (_paste_rows), for the synthesised frames of the pairs that are no cut."""
-        verdict = []
-        for p, (i, _, _) in enumerate(pairs):
-            cut, score = cuts.feed(int(sums[p]), pixels)
-            verdict.append(cut)
-            if cut:
-                self.cuts.append((i, score))
-        return self._near_rows(verdict, paste, pairs, order, carried)
-
-    def _paste_rows(self, paste, pairs, order, carried):
-        """The rows of a pass of a letterboxed clip without scene cuts, beside _cut_rows and with its `pairs`, `order` and `carried`: every
-        synthesised window goes out as paste(window, the nearer input frame's bytes) - the left frame's at t < 1/2, else the right one's."""
-        return self._near_rows([False] * len(pairs), paste, pairs, order, carried)
-
-    @staticmethod
-    def _near_rows(verdict, paste, pairs, order, carried):
-        """What _cut_rows and _paste_rows yield: an input frame as it is; a synthesised frame of a cut pair replaced by the nearer input
-        frame, whole; any other synthesised frame as it is or, with `paste` (a letterboxed clip), pasted into the nearer input frame's bars."""
-        for buf, at in order:
-            if at is not None and (verdict[at[0]] or paste is not None):
-                _, lf, rt = pairs[at[0]]
-                near = (carried if lf is None else lf) if at[1] < Fraction(1, 2) else rt
-                buf = near if verdict[at[0]] else paste(buf, near)
-            yield buf
-        if pairs:
-            carried[:] = pairs[-1][2]
-
     def probe_fields(self, reader):
         """The reader behind a FieldOrderSource that has decided (the option field_probe), for run(): sets `field_probe` and the field
         order of a deinterlace="auto" run on a header without one, or refuses it.  run() calls it on a reader that has not been through
@@ -2980,9 +3083,11 @@ class VideoInterpolator:
             return self._run_fixed(clip, reader, writer)
         return self._run_shutter(clip, reader, writer) if self.samples > 1 else self._run_timeline(clip, reader, writer)
 
-    def _run_passes(self, clip, reader, writer, plan, np_in, done, has_work, submit, rows_of):
-        """The loop of the planner-driven modes, over what the planner closes: has_work(*closed) - the pass has GPU work; submit(j, r, *closed)
-        queues it as pass j on ring slot r; rows_of(r, on_gpu, *closed) -> (the rows to write as PassRing.hand takes them, their number)."""
+    def _run_passes(self, clip, writer, done, read, has_work, submit, rows_of, first=None, last=None):
+        """The loop of every mode, over the passes that read(ring, issue) closes - read_passes with a mode's planner, read_blocks with its
+        unit reader: has_work(*closed) - the pass has GPU work; submit(j, r, *closed) queues it as pass j on ring slot r; rows_of(r, on_gpu,
+        *closed) -> (the rows to write as PassRing.hand takes them, their number).  first(ring), last(ring): what a mode hands to the ring
+        ahead of pass 0 and, unless the writer has failed, behind the last pass; each returns the number of its frames."""
         written = j = 0          # frames written, passes issued
 
         def issue(r, *closed):
@@ -2996,120 +3101,84 @@ class VideoInterpolator:
             written += count
 
         with PassRing(len(done), writer, lambda: torch.cuda.synchronize(clip.dev)) as ring:
-            read_passes(reader, ring, plan, np_in, issue)
+            if first is not None:
+                written += first(ring)
+            read(ring, issue)
+            if last is not None and not ring.failure:
+                written += last(ring)
         return written
 
     def _run_fixed(self, clip, reader, writer):
         """run() on the fixed grid of upsample_rate: planes[k] is [carried left frame | pairs_per_batch new frames], the pairs an
-        overlapping view of it; the times go up once per run.  Frame 0 is written from a pinned buffer of its own before any pass.
+        overlapping view of it; the times go up once per run.  Frame 0 is written from a pinned buffer of its own before any pass, and
+        ingested where pass 0 looks for its carried left frame.  The passes are read_blocks': a short last one runs whole, its extra
+        pairs are not written.
 
-        With scene_cut a stream's payload buffer has one row more in front: row 0 holds the Y plane of the frame before the pass's first,
-        so that the left planes of a pass's pairs are rows 0 .. pb - 1, the right ones rows 1 .. pb, and one ssm_luma_sad_fwd call takes
-        them all.  A pass puts the Y plane of its last frame into row 0 of the NEXT stream's buffer, after its own call and before it
-        records `ingested`: the pass that reads it waits for that event, and the pass that read the row before has recorded its own
-        event (after its call) earlier in the chain of waits.  The sums go back to the pass's ring slot ahead of `done`.
-
-        With static the row in front holds the WHOLE frame before the pass's first, and one ssm_static_paste_fwd call takes the pass's pairs
-        (rows 0 .. pb - 1 against rows 1 .. pb, T = upsample_rate - 1 outputs each) behind the egress and ahead of the D2H copy.  That call
-        reads row 0 long after the pass has recorded `ingested`, so the row cannot be written by another stream as the scene cuts' is: the
-        pass FETCHES it, on its own stream, from the last row of the stream before - behind its wait for that stream's `ingested` and ahead
-        of its own upload (with one stream the source is its own last row).  The source row is next written by the upload of pass j + n - 1,
-        which stands behind a chain of waits that ends at this pass's `ingested`, recorded after the fetch.  With both options the
-        fetched row serves the luma sums too.  The counts go back to the pass's ring slot ahead of `done`."""
+        The per-pair options are PairOptions': with scene_cut or static a stream's payload buffer has one row in front, the left payloads
+        of a pass's pairs are rows 0 .. pb - 1 and the right ones rows 1 .. pb, so one ssm_luma_sad_fwd call and one ssm_static_paste_fwd
+        call (T = upsample_rate - 1 outputs a pair) take them all; a pass fetches its row 0 from row pb of the stream before."""
         from .evaluation import t_values
-        fb, dev, hp, wp, luma = clip.fb, clip.dev, clip.hp, clip.wp, clip.h * clip.w
+        fb, dev, hp, wp = clip.fb, clip.dev, clip.hp, clip.wp
         pipe = self._pipeline(hp, wp, dev)
         n, pb, nt = pipe.n, self.pb, self.rate - 1
         depth = n + 2                                                  # ring slots: one per pass in flight, one being read, one being written
         t_dev = torch.tensor(t_values(self.rate), dtype=torch.float32, device=dev)
-        host_in, host_out, _, np_in, np_out, _, done = ring_slots(depth, fb, pb, pb * nt, fb_out=clip.fb_out)
-        (cuts, dev_sums, host_sums, np_sums, carried), lead = self._cut_state(self.scene_cut is not None, n, depth, pb, clip)
-        static, blocks = self.static_lo, static_blocks(clip.h, clip.w)
-        dev_counts, host_counts, np_counts = self._static_state(n, depth, pb, clip)
-        lead = 1 if static is not None else lead
-        paste = self._paster(clip)
-        if paste is None:
-            dev_in, dev_out, _, ingested = stream_buffers(n, dev, fb, lead + pb, pb * nt)
-            dev_up = dev_in
-        else:          # a letterboxed clip: frames come up into dev_up, their windows are cut into dev_in, and everything below reads those
-            dev_up, dev_out, _, ingested, dev_in = stream_buffers(n, dev, fb, lead + pb, pb * nt, fb_out=clip.fb_out)
-            carried = np.empty(fb, np.uint8) if carried is None else carried
+        slots = ring_slots(depth, fb, pb, pb * nt, fb_out=clip.fb_out)
+        np_in, np_out = slots.np_in, slots.np_out
+        opt = PairOptions(self, clip, self.scene_cut, self.static_lo)
+        lead, lefts, rights = opt.lead, list(range(pb)), list(range(1, pb + 1))
+        _, dev_out, _, ingested, _ = opt.buffers(n, depth, pb, pb, pb * nt)
         planes = [torch.empty(pb + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [carried left frame | new frames]
         first = torch.empty(1, fb, dtype=torch.uint8).pin_memory()
-        if not reader.read_frame_into(first.numpy()[0]):
-            raise Y4MError("the Y4M stream holds no frame")
-        if carried is not None:
-            carried[:] = first.numpy()[0]
+        first_frame(reader, first.numpy()[0])
         torch.cuda.synchronize(dev)
-        written = 1
-        with PassRing(depth, writer, lambda: torch.cuda.synchronize(dev)) as ring:
+        pairs_done = 0
+
+        def frame0(ring):
             ring.hand(None, None, [first.numpy()[0]])
-            # frame 0: ingested where pass 0 looks for its carried left frame
             last = (n - 1) % n
             with torch.cuda.stream(pipe.streams[last]):
-                new = dev_in[last][lead:]
-                dev_up[last][lead:lead + 1].copy_(first, non_blocking=True)
-                clip.ingest(dev_up[last][lead:lead + 1], planes[last][pb:], scratch=new[:1])
-                if static is not None and pb > 1:
-                    dev_in[last][pb].copy_(new[0])          # where pass 0 fetches its carried frame
-                elif cuts is not None and static is None:
-                    dev_in[0][0, :luma].copy_(new[0, :luma])
+                up, new = opt.dev_up[last][lead:lead + 1], opt.dev_in[last][lead:lead + 1]
+                up.copy_(first, non_blocking=True)
+                clip.ingest(up, planes[last][pb:], scratch=new)
+                opt.seed(first.numpy()[0], last, lead, pb)
                 ingested[last].record()
-            j, eof = 0, False
-            while not eof and not ring.failure:
-                r = ring.take()
-                valid = 0
-                while valid < pb and reader.read_frame_into(np_in[r][valid]):
-                    valid += 1
-                if valid < pb:
-                    eof = True
-                    if valid == 0:
-                        ring.hand(r, None, [])
-                        break
-                    np_in[r][valid:] = np_in[r][valid - 1]          # fill the pass; the extra pairs are not written
-                k, kprev = j % n, (j - 1) % n
-                st = pipe.streams[k]
-                with torch.cuda.stream(st):
-                    new = dev_in[k][lead:]
-                    if static is not None:
-                        st.wait_event(ingested[kprev])
-                        dev_in[k][0].copy_(dev_in[kprev][pb])
-                    dev_up[k][lead:].copy_(host_in[r], non_blocking=True)
-                    st.wait_event(ingested[kprev])
-                    planes[k][0].copy_(planes[kprev][pb])
-                    clip.ingest(dev_up[k][lead:], planes[k][1:], scratch=new)
-                    if cuts is not None:
-                        luma_sad(dev_in[k][:pb], dev_in[k][1:], clip.h, clip.w, out=dev_sums[k])
-                        if static is None:
-                            dev_in[(j + 1) % n][0, :luma].copy_(dev_in[k][pb, :luma])
-                    ingested[k].record()
-                    x = planes[k]
-                    img6 = x.view(1, 6, hp, wp) if pb == 1 else x.as_strided((pb, 6, hp, wp), (3 * hp * wp, hp * wp, wp, 1))
-                    frames = pipe.engines[k].run(img6, t_dev, False)
-                    clip.egress(frames, dev_out[k])
-                    if static is not None:
-                        static_paste(dev_in[k][:pb], dev_in[k][1:], dev_out[k], clip.h, clip.w, clip.siting, clip.bits, static, counts=dev_counts[k])
-                        host_counts[r].copy_(dev_counts[k], non_blocking=True)
-                    host_out[r].copy_(dev_out[k], non_blocking=True)
-                    if cuts is not None:
-                        host_sums[r].copy_(dev_sums[k], non_blocking=True)
-                    done[r].record()
-                rows = [np_out[r][row] if kind == "interp" else np_in[r][row] for kind, row in pass_order(valid, nt)]
-                if cuts is not None or paste is not None:
-                    i0 = (written - 1) // self.rate
-                    at = [None if kind == "orig" else (row // nt, Fraction(row % nt + 1, self.rate)) for kind, row in pass_order(valid, nt)]
-                    host_pairs = [(i0 + p, np_in[r][p - 1] if p else None, np_in[r][p]) for p in range(valid)]
-                    if cuts is not None:
-                        rows = functools.partial(self._cut_rows, cuts, luma, np_sums[r], host_pairs, list(zip(rows, at)), carried, paste)
-                    else:
-                        rows = functools.partial(self._paste_rows, paste, host_pairs, list(zip(rows, at)), carried)
-                if static is not None:
-                    i0 = (written - 1) // self.rate
-                    rows = functools.partial(self._static_rows, np_counts[r], range(i0, i0 + valid), blocks, rows)
-                ring.hand(r, done[r], rows)
-                written += valid * self.rate
-                j += 1
-        return written
+            return 1
+
+        def submit(j, r, valid):
+            k, kprev = j % n, (j - 1) % n
+            st = pipe.streams[k]
+            with torch.cuda.stream(st):
+                opt.carry_in(st, k, kprev)
+                opt.dev_up[k][lead:].copy_(slots.host_in[r], non_blocking=True)
+                st.wait_event(ingested[kprev])
+                planes[k][0].copy_(planes[kprev][pb])
+                clip.ingest(opt.dev_up[k][lead:], planes[k][1:], scratch=opt.dev_in[k][lead:])
+                opt.pairs(k, lefts, rights)
+                ingested[k].record()
+                x = planes[k]
+                img6 = x.view(1, 6, hp, wp) if pb == 1 else x.as_strided((pb, 6, hp, wp), (3 * hp * wp, hp * wp, wp, 1))
+                frames = pipe.engines[k].run(img6, t_dev, False)
+                clip.egress(frames, dev_out[k])
+                opt.paste_static(r, k, [(0, pb, dev_out[k])])
+                slots.host_out[r].copy_(dev_out[k], non_blocking=True)
+                opt.download(r, k)
+                slots.done[r].record()
+
+        def rows_of(r, on_gpu, valid):
+            nonlocal pairs_done
+            i0, pairs_done = pairs_done, pairs_done + valid
+            order = list(pass_order(valid, nt))
+            rows = [np_out[r][row] if kind == "interp" else np_in[r][row] for kind, row in order]
+
+            def near():
+                return ([(i0 + p, np_in[r][p - 1] if p else None, np_in[r][p]) for p in range(valid)],
+                        [None if kind == "orig" else (row // nt, Fraction(row % nt + 1, self.rate)) for kind, row in order])
+
+            return (opt.rows(r, range(i0, i0 + valid), rows, near) if on_gpu else rows), valid * self.rate
+
+        return self._run_passes(clip, writer, slots.done, lambda ring, issue: read_blocks(
+            ring, pb, np_in, lambda r, i: reader.read_frame_into(np_in[r][i]), issue), lambda valid: valid > 0, submit, rows_of, first=frame0)
 
     def _run_fields(self, clip, reader, writer):
         """run() with deinterlace: the n interlaced frames come out as the 2n progressive frames of field_outputs - the fixed grid of
@@ -3141,7 +3210,7 @@ class VideoInterpolator:
         early, late = field_of(0, order)[1], field_of(1, order)[1]          # the parities of a frame's earlier and later field
         t_dev = torch.tensor(t_values(2), dtype=torch.float32, device=dev)
         host_in, host_out, _, np_in, np_out, _, done = ring_slots(depth, fb, pb, 2 * pb)
-        dev_in, dev_out, _, ingested = stream_buffers(n, dev, fb, pb, 2 * pb)
+        dev_in, dev_out, _, ingested, _ = stream_buffers(n, dev, fb, pb, 2 * pb)
         fields = [torch.empty(2 + 2 * pb, hfb, dtype=torch.uint8, device=dev) for _ in range(n)]      # row 2 (1 + i) + parity: frame i of the pass; i = -1 carried
         made = [torch.empty(2 * pb, hfb, dtype=torch.uint8, device=dev) for _ in range(n)]
         fplanes = [torch.empty(2, pb + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [parity][carried left field | new ones]
@@ -3160,14 +3229,13 @@ class VideoInterpolator:
                     fclip.ingest(rows[2 * i + q:2 * i + q + 1], fplanes[k][q, 1 + i0 + i:2 + i0 + i])
 
         first_in, first_out = (torch.empty(1, fb, dtype=torch.uint8).pin_memory() for _ in range(2))
-        if not reader.read_frame_into(first_in.numpy()[0]):
-            raise Y4MError("the Y4M stream holds no frame")
+        first_frame(reader, first_in.numpy()[0])
         torch.cuda.synchronize(dev)
-        written = 0
-        with PassRing(depth, writer, lambda: torch.cuda.synchronize(dev)) as ring:
-            # frame 0: split and ingested where pass 0 looks for its carried fields; output 0 from its earlier field alone
-            last = (n - 1) % n
-            tail = (last, pb - 1)          # stream and place of the newest frame: its later field closes the clip
+        tail = ((n - 1) % n, pb - 1)          # stream and place of the newest frame: its later field closes the clip
+
+        def frame0(ring):
+            """Frame 0: split and ingested where pass 0 looks for its carried fields; output 0 from its earlier field alone."""
+            last = tail[0]
             first_done = torch.cuda.Event()
             with torch.cuda.stream(pipe.streams[last]):
                 dev_in[last][pb - 1:].copy_(first_in, non_blocking=True)
@@ -3177,54 +3245,46 @@ class VideoInterpolator:
                 ingested[last].record()
                 first_done.record()
             ring.hand(None, first_done, [first_out.numpy()[0]])
-            written += 1
-            j, eof = 0, False
-            while not eof and not ring.failure:
-                r = ring.take()
-                valid = 0
-                while valid < pb and reader.read_frame_into(np_in[r][valid]):
-                    valid += 1
-                if valid < pb:
-                    eof = True
-                    if valid == 0:
-                        ring.hand(r, None, [])
-                        break
-                    np_in[r][valid:] = np_in[r][valid - 1]          # fill the pass; the extra outputs are not written
-                k, kprev = j % n, (j - 1) % n
-                st = pipe.streams[k]
-                with torch.cuda.stream(st):
-                    dev_in[k].copy_(host_in[r], non_blocking=True)
-                    st.wait_event(ingested[kprev])          # the carried fields; and pass j - n + 1 is done with fields[k] and fplanes[k]
-                    fields[k][late].copy_(fields[kprev][2 * pb + late])
-                    fplanes[k][:, 0].copy_(fplanes[kprev][:, pb])
-                    split_ingest(k, dev_in[k], 0)
-                    ingested[k].record()
-                    for s, q in enumerate((early, late)):          # the pairs of the earlier fields make outputs 0, 2, .. of the pass
-                        x = fplanes[k][q]
-                        img6 = x.view(1, 6, hp, wp) if pb == 1 else x.as_strided((pb, 6, hp, wp), (3 * hp * wp, hp * wp, wp, 1))
-                        frames = pipe.engines[k].run(img6, t_dev, False)
-                        for i in range(pb):
-                            fclip.egress(frames[i:i + 1], made[k][2 * i + s:2 * i + s + 1])
-                    for row, step, count, o in runs:
-                        weave(fields[k][row:row + (count - 1) * step + 1:step], made[k][o:o + count], dev_out[k][o:o + count],
-                              field_of(2 * j * pb + 1 + o, order)[1], 0)
-                    host_out[r].copy_(dev_out[k], non_blocking=True)
-                    done[r].record()
-                ring.hand(r, done[r], [np_out[r][o] for o in range(2 * valid)])
-                written += 2 * valid
-                tail = (k, valid - 1)
-                j += 1
-            if not ring.failure:
-                # output 2n - 1: the later field of the last frame, alone
-                r = ring.take()
-                k, i = tail
-                with torch.cuda.stream(pipe.streams[k]):
-                    weave(fields[k][2 * (1 + i) + late:2 * (1 + i) + late + 1], None, dev_out[k][:1], late, 1)
-                    host_out[r][:1].copy_(dev_out[k][:1], non_blocking=True)
-                    done[r].record()
-                ring.hand(r, done[r], [np_out[r][0]])
-                written += 1
-        return written
+            return 1
+
+        def submit(j, r, valid):
+            nonlocal tail
+            k, kprev = j % n, (j - 1) % n
+            st = pipe.streams[k]
+            with torch.cuda.stream(st):
+                dev_in[k].copy_(host_in[r], non_blocking=True)
+                st.wait_event(ingested[kprev])          # the carried fields; and pass j - n + 1 is done with fields[k] and fplanes[k]
+                fields[k][late].copy_(fields[kprev][2 * pb + late])
+                fplanes[k][:, 0].copy_(fplanes[kprev][:, pb])
+                split_ingest(k, dev_in[k], 0)
+                ingested[k].record()
+                for s, q in enumerate((early, late)):          # the pairs of the earlier fields make outputs 0, 2, .. of the pass
+                    x = fplanes[k][q]
+                    img6 = x.view(1, 6, hp, wp) if pb == 1 else x.as_strided((pb, 6, hp, wp), (3 * hp * wp, hp * wp, wp, 1))
+                    frames = pipe.engines[k].run(img6, t_dev, False)
+                    for i in range(pb):
+                        fclip.egress(frames[i:i + 1], made[k][2 * i + s:2 * i + s + 1])
+                for row, step, count, o in runs:
+                    weave(fields[k][row:row + (count - 1) * step + 1:step], made[k][o:o + count], dev_out[k][o:o + count],
+                          field_of(2 * j * pb + 1 + o, order)[1], 0)
+                host_out[r].copy_(dev_out[k], non_blocking=True)
+                done[r].record()
+            tail = (k, valid - 1)
+
+        def closing(ring):
+            """Output 2n - 1: the later field of the last frame, alone."""
+            r = ring.take()
+            k, i = tail
+            with torch.cuda.stream(pipe.streams[k]):
+                weave(fields[k][2 * (1 + i) + late:2 * (1 + i) + late + 1], None, dev_out[k][:1], late, 1)
+                host_out[r][:1].copy_(dev_out[k][:1], non_blocking=True)
+                done[r].record()
+            ring.hand(r, done[r], [np_out[r][0]])
+            return 1
+
+        return self._run_passes(clip, writer, done, lambda ring, issue: read_blocks(
+            ring, pb, np_in, lambda r, i: reader.read_frame_into(np_in[r][i]), issue), lambda valid: valid > 0, submit,
+            lambda r, on_gpu, valid: ([np_out[r][o] for o in range(2 * valid)], 2 * valid), first=frame0, last=closing)
 
     def _run_timeline(self, clip, reader, writer, tl=None):
         """run() with target_rate / speed: the output frames are those of Timeline(speed * reader.rate / target_rate); with dedup those of
@@ -3241,67 +3301,45 @@ class VideoInterpolator:
         through) leaves the planes of its unused entries as they are: finite, and never read back.  Memory is fixed by the frame size,
         n_streams, pairs_per_batch and slots.
 
-        With scene_cut, as on the fixed grid: row 0 in front of a stream's payloads holds the Y plane of the right frame of the pair
-        that ran last in the pass before, written by that pass behind its own calls and ahead of its `ingested`; a pair's left plane is
-        its own uploaded row, the right row of the pair before it, or row 0.  The rows of the pairs that run step evenly unless the
-        timeline skips pairs inside a pass (sad_runs): one ssm_luma_sad_fwd call then, one per run otherwise.  Only pairs that run are
-        summed and fed to SceneCuts.
-
-        With static, as on the fixed grid: row 0 holds the whole right frame of the pair that ran last in the pass before, fetched by the
-        pass itself from that pass's stream, behind its wait for `ingested` and ahead of its own uploads; one ssm_static_paste_fwd call
-        per pair, with T the number of its outputs, behind the pair's egress and ahead of its D2H copy; the counts go back with `done`."""
-        fb, dev, hp, wp, luma = clip.fb, clip.dev, clip.hp, clip.wp, clip.h * clip.w
+        The per-pair options are PairOptions', as on the fixed grid: row 0 in front of a stream's payloads stands for the right frame of the
+        pair that ran last in the pass before; a pair's left payload is its own uploaded row, the right row of the pair before it, or row
+        0.  The rows of the pairs that run step evenly unless the timeline skips pairs inside a pass (sad_runs): one ssm_luma_sad_fwd call
+        then, one per run otherwise; only pairs that run are summed and fed to SceneCuts.  With static one ssm_static_paste_fwd call per
+        pair, with T the number of its outputs, behind the pass's egress calls and ahead of its D2H copies."""
+        fb, dev, hp, wp = clip.fb, clip.dev, clip.hp, clip.wp
         tl = self.timeline(reader.rate) if tl is None else tl
         S, pb, n = tl.slots, self.pb, self.n_streams
         pipe = self._pipeline(hp, wp, dev, S) if S else None          # an integer step only picks input frames: nothing to run
         depth, cap = n + 2, 2 * pb + 2
         host_in, host_out, host_t, np_in, np_out, np_t, done = ring_slots(depth, fb, cap, pb * max(S, 1), pb * max(S, 1), fb_out=clip.fb_out)
-        (cuts, dev_sums, host_sums, np_sums, carried), lead = self._cut_state(self.scene_cut is not None and pipe is not None, n, depth, pb, clip)
-        static, blocks = (self.static_lo if pipe is not None else None), static_blocks(clip.h, clip.w)
-        dev_counts, host_counts, np_counts = self._static_state(n, depth, pb, clip) if static is not None else (None, None, None)
-        lead = 1 if static is not None else lead
-        last_right = [0]          # row of dev_in, in the pass before, of the frame the next pass's first pair may carry over
-        paste = self._paster(clip)
         plan = PassPlanner(tl, pb, cap)
-        if pipe is not None and paste is not None:          # a letterboxed clip, as on the fixed grid: frames up into dev_up, their windows in dev_in
-            dev_up, dev_out, dev_t, ingested, dev_in = stream_buffers(n, dev, fb, lead + cap, pb * S, pb * S, fb_out=clip.fb_out)
-            carried = np.empty(fb, np.uint8) if carried is None else carried
-        elif pipe is not None:
-            dev_in, dev_out, dev_t, ingested = stream_buffers(n, dev, fb, lead + cap, pb * S, pb * S)
-            dev_up = dev_in
         if pipe is not None:
+            opt = PairOptions(self, clip, self.scene_cut, self.static_lo)
+            lead = opt.lead
+            _, dev_out, dev_t, ingested, _ = opt.buffers(n, depth, pb, cap, pb * S, pb * S)
             planes = [torch.zeros(pb, 2, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [pair][left | right]
         torch.cuda.synchronize(dev)
         last_p = [0]          # place, in its pass, of the pair whose right frame the next pair may carry over
 
         def submit(j, r, order, pairs):
             """Pass j: `pairs` = [(first row of the pair's new payloads, the left frame is among them, its times)] of ring slot r."""
-            k = j % n
+            k, kprev = j % n, (j - 1) % n
             st = pipe.streams[k]
             with torch.cuda.stream(st):
                 if j:
-                    st.wait_event(ingested[(j - 1) % n])          # the carried frame; and pass j - n + 1 is done with planes[k]
-                    if static is not None:
-                        dev_in[k][0].copy_(dev_in[(j - 1) % n][last_right[0]])
-                new, up = dev_in[k][lead:], dev_up[k][lead:]
+                    st.wait_event(ingested[kprev])          # the carried frame; and pass j - n + 1 is done with planes[k]
+                    opt.carry_in(st, k, kprev, waited=True)
+                new, up = opt.dev_in[k][lead:], opt.dev_up[k][lead:]
                 for p, (row, own_left, ts) in enumerate(pairs):
                     rows = 2 if own_left else 1
                     up[row:row + rows].copy_(host_in[r][row:row + rows], non_blocking=True)
                     if not own_left:
-                        planes[k][p, 0].copy_(planes[k][p - 1, 1] if p else planes[(j - 1) % n][last_p[0], 1])
+                        planes[k][p, 0].copy_(planes[k][p - 1, 1] if p else planes[kprev][last_p[0], 1])
                     clip.ingest(up[row:row + rows], planes[k][p, 2 - rows:], scratch=new[row:row + rows])
                 upload_times([ts for _, _, ts in pairs], S, np_t[r], host_t[r], dev_t[k])
-                if cuts is not None or static is not None:
-                    rights = [lead + row + (1 if own_left else 0) for row, own_left, _ in pairs]          # rows of dev_in[k]
-                    lefts = [lead + row if own_left else (rights[p - 1] if p else 0) for p, (row, own_left, _) in enumerate(pairs)]
-                    last_right[0] = rights[-1]
-                if cuts is not None:
-                    for p, m in sad_runs(lefts, rights):
-                        da, db = (lefts[p + 1] - lefts[p], rights[p + 1] - rights[p]) if m > 1 else (1, 1)
-                        luma_sad(dev_in[k][lefts[p]:lefts[p] + (m - 1) * da + 1:da], dev_in[k][rights[p]:rights[p] + (m - 1) * db + 1:db], clip.h,
-                                 clip.w, out=dev_sums[k][p:p + m])
-                    if static is None:
-                        dev_in[(j + 1) % n][0, :luma].copy_(dev_in[k][rights[-1], :luma])
+                rights = [lead + row + (1 if own_left else 0) for row, own_left, _ in pairs]          # rows of dev_in[k]
+                lefts = [lead + row if own_left else (rights[p - 1] if p else 0) for p, (row, own_left, _) in enumerate(pairs)]
+                opt.pairs(k, lefts, rights)
                 ingested[k].record()
                 last_p[0] = len(pairs) - 1
                 frames = pipe.engines[k].run(planes[k].view(pb, 6, hp, wp), dev_t[k], False)
@@ -3309,38 +3347,35 @@ class VideoInterpolator:
                     spans = [(0, len(pairs) * S)]
                 else:
                     spans = [(p * S, len(ts)) for p, (_, _, ts) in enumerate(pairs)]
+                late = opt.static is not None          # the static blocks stand between the egress calls and the copies of what they made
                 for o, m in spans:
                     clip.egress(frames[o:o + m], dev_out[k][o:o + m])
-                    if static is None:
+                    if not late:
                         host_out[r][o:o + m].copy_(dev_out[k][o:o + m], non_blocking=True)
-                if static is not None:
-                    for p, (_, _, ts) in enumerate(pairs):
-                        static_paste(dev_in[k][lefts[p]:lefts[p] + 1], dev_in[k][rights[p]:rights[p] + 1], dev_out[k][p * S:p * S + len(ts)],
-                                     clip.h, clip.w, clip.siting, clip.bits, static, counts=dev_counts[k][p:p + 1])
+                if late:
+                    opt.paste_static(r, k, [(p, 1, dev_out[k][p * S:p * S + len(ts)]) for p, (_, _, ts) in enumerate(pairs)])
                     for o, m in spans:
                         host_out[r][o:o + m].copy_(dev_out[k][o:o + m], non_blocking=True)
-                    host_counts[r].copy_(dev_counts[k], non_blocking=True)
-                if cuts is not None:
-                    host_sums[r].copy_(dev_sums[k], non_blocking=True)
+                opt.download(r, k)
                 done[r].record()
 
         def rows_of(r, on_gpu, order, pairs):
             rows = [np_out[r][row] if kind == "interp" else np_in[r][row] for kind, row in order]
-            if (cuts is not None or paste is not None) and on_gpu:
-                exact = [tl.times(i) for i in plan.closed_index]          # the pairs' times as Fractions, beside the planner's fp32
-                at = [None if kind == "orig" else (row // S, exact[row // S][row % S]) for kind, row in order]
-                rights = [np_in[r][row + (1 if own_left else 0)] for row, own_left, _ in pairs]
-                host_pairs = [(i, np_in[r][row] if own_left else (rights[p - 1] if p else None), rights[p])
-                              for p, (i, (row, own_left, _)) in enumerate(zip(plan.closed_index, pairs))]
-                if cuts is not None:
-                    rows = functools.partial(self._cut_rows, cuts, luma, np_sums[r], host_pairs, list(zip(rows, at)), carried, paste)
-                else:
-                    rows = functools.partial(self._paste_rows, paste, host_pairs, list(zip(rows, at)), carried)
-            if static is not None and on_gpu:
-                rows = functools.partial(self._static_rows, np_counts[r], list(plan.closed_index), blocks, rows)
-            return rows, len(order)
+            if not on_gpu:
+                return rows, len(order)
+            index = list(plan.closed_index)
 
-        return self._run_passes(clip, reader, writer, plan, np_in, done, lambda order, pairs: bool(pairs), submit, rows_of)
+            def near():
+                exact = [tl.times(i) for i in index]          # the pairs' times as Fractions, beside the planner's fp32
+                rights = [np_in[r][row + (1 if own_left else 0)] for row, own_left, _ in pairs]
+                return ([(i, np_in[r][row] if own_left else (rights[p - 1] if p else None), rights[p])
+                         for p, (i, (row, own_left, _)) in enumerate(zip(index, pairs))],
+                        [None if kind == "orig" else (row // S, exact[row // S][row % S]) for kind, row in order])
+
+            return opt.rows(r, index, rows, near), len(order)
+
+        return self._run_passes(clip, writer, done, lambda ring, issue: read_passes(reader, ring, plan, np_in, issue),
+                                lambda order, pairs: bool(pairs), submit, rows_of)
 
     def _run_shutter(self, clip, reader, writer):
         """run() with a shutter: output frame k is the mean of the S = shutter_samples sub-frames of Timeline(step, shutter=, samples=),
@@ -3380,7 +3415,7 @@ class VideoInterpolator:
         elif self.shutter_light != "coded":
             light = (*clip.norm, (ctypes.c_float * LIGHT_ROW)(*[float(x) for x in light_curve(self.shutter_light)]))
         host_in, host_out, host_t, np_in, np_out, np_t, done = ring_slots(depth, fb, cap, plan.max_done, pb * max(slots, 1))
-        dev_in, dev_out, dev_t, ingested = stream_buffers(n, dev, fb, cap, plan.max_done, pb * max(slots, 1))
+        dev_in, dev_out, dev_t, ingested, _ = stream_buffers(n, dev, fb, cap, plan.max_done, pb * max(slots, 1))
         planes = [torch.zeros(cap + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [carried frame | the pass's frames]
         sides = [torch.zeros(pb, 2, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]         # [pair][left | right]
         acc = torch.zeros(OPEN_OUTPUTS, 3, hp, wp, dtype=torch.float32, device=dev)
@@ -3444,5 +3479,6 @@ class VideoInterpolator:
                 done[r].record()
 
         # a pass without GPU work: with no rows the planner has recorded no call, so `finished` is empty; after a failure the thread writes nothing
-        return self._run_passes(clip, reader, writer, plan, np_in, done, lambda rows, *_: rows > 0, submit,
+        return self._run_passes(clip, writer, done, lambda ring, issue: read_passes(reader, ring, plan, np_in, issue),
+                                lambda rows, *_: rows > 0, submit,
                                 lambda r, on_gpu, *closed: ([np_out[r][o] for o in range(len(closed[-1]))], len(closed[-1])))

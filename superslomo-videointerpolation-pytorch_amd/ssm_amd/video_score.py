@@ -413,8 +413,10 @@ class HoldOutScorer:
     The options are VideoInterpolator's where they have a held-out counterpart; target_rate, speed, shutter and scene_cut have none and
     are not offered.  The pair pipeline is the one VideoInterpolator(upsample_rate=hold, ...) builds: it is built by one.
 
-    A pass takes pairs_per_batch groups of the clip: the group's hold - 1 held-out payloads and the kept frame that closes it.  For the
-    kept frames it is VideoInterpolator._run_fixed's pass call for call - H2D, ingest of the kept payloads only, the engine, egress, D2H.
+    A pass takes pairs_per_batch groups of the clip: the group's hold - 1 held-out payloads and the kept frame that closes it (group_reader,
+    the unit reader of video.read_blocks: the passes, the short and the empty last one and the ring's failure protocol are the fixed
+    grid's, through VideoInterpolator._run_passes).  For the kept frames what a pass queues is VideoInterpolator._run_fixed's without
+    options, call for call - H2D, ingest of the kept payloads only, the engine, egress, D2H.
     On top: the H2D of the held-out payloads, which never go through ingest; the `nearest` calls - one ssm_plane_sse_fwd per kept frame
     of the pass, its payload (stride 0) against the run of held-out payloads it is the nearer one of; and, after egress, one `model`
     call over the pass's synthesised payloads against its held-out ones.  The sums go back to the pass's pinned ring slot ahead of `done`,
@@ -465,18 +467,18 @@ class HoldOutScorer:
         host_sums = [torch.empty(cols * (2 if ssim else 1), pb * nt, 3, dtype=torch.int64).pin_memory() for _ in range(depth)]
         np_sums = [t.numpy().view(np.uint64) for t in host_sums]          # [model | nearest]: squared differences are unsigned
         np_signed = [t.numpy() for t in host_sums]                        # the SSIM rows are signed
-        dev_in, dev_out, _, ingested = V.stream_buffers(n, dev, fb, 1 + pb, pb * nt)          # row 0: the carried left kept payload
+        dev_in, dev_out, _, ingested, _ = V.stream_buffers(n, dev, fb, 1 + pb, pb * nt)          # row 0: the carried left kept payload
         dev_held = [torch.empty(pb * nt, fb, dtype=torch.uint8, device=dev) for _ in range(n)]
         dev_sums = [torch.zeros(cols * (2 if ssim else 1), pb * nt, 3, dtype=torch.int64, device=dev) for _ in range(n)]
         dev_mix = [torch.empty(pb * nt, fb, dtype=torch.uint8, device=dev) for _ in range(n)] if mix else None
         planes = [torch.empty(pb + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]
         first = torch.empty(1, fb, dtype=torch.uint8).pin_memory()
-        if not reader.read_frame_into(first.numpy()[0]):
-            raise V.Y4MError("the Y4M stream holds no frame")
+        V.first_frame(reader, first.numpy()[0])
         res.frames_read = res.kept = 1
         torch.cuda.synchronize(dev)
+        read_group = group_reader(reader, res, hold, np_held, np_in)
 
-        def rows_of(r, valid, g0):
+        def scored(r, valid, g0):
             """On the writer thread, once the pass has come: the result's rows of its `valid` groups from group g0 on, then the frames."""
             for p in range(valid):
                 for k in range(1, hold):
@@ -492,15 +494,7 @@ class HoldOutScorer:
             for kind, row in V.pass_order(valid, nt):
                 yield np_out[r][row] if kind == "interp" else np_in[r][row]
 
-        def compare(column, a, b, rows):
-            """Queues, on the current stream, the squared differences of payloads a against b into rows `rows` of column `column` of the
-            running pass's sums (stream k), and with ssim on their SSIM into the same rows of the column's SSIM block."""
-            plane_sse(a, b, h, w, siting, bits, out=dev_sums[k][column, rows])
-            if ssim:
-                plane_ssim(a, b, h, w, siting, bits, out=dev_sums[k][cols + column, rows])
-
-        res.written = 1
-        with V.PassRing(depth, writer, lambda: torch.cuda.synchronize(dev)) as ring:
+        def frame0(ring):
             ring.hand(None, None, [first.numpy()[0]])
             last = (n - 1) % n
             with torch.cuda.stream(pipe.streams[last]):
@@ -509,56 +503,66 @@ class HoldOutScorer:
                 clip.ingest(new[:1], planes[last][pb:])
                 dev_in[0][0].copy_(new[0])
                 ingested[last].record()
-            j, eof = 0, False
-            while not eof and not ring.failure:
-                r = ring.take()
-                valid = pending = 0          # whole groups read into the slot; held-out frames of a group that is not whole yet
-                while valid < pb:
-                    into = np_held[r][valid * nt + pending] if pending < nt else np_in[r][valid]
-                    if not reader.read_frame_into(into):
-                        break
-                    res.frames_read += 1
-                    pending += 1
-                    if pending == hold:
-                        valid, pending = valid + 1, 0
-                if valid < pb:
-                    eof = True
-                    res.trailing = pending
-                    if valid == 0:
-                        ring.hand(r, None, [])
-                        break
-                    np_in[r][valid:] = np_in[r][valid - 1]          # fill the pass; the extra pairs are neither scored nor written
-                res.kept += valid
-                k, kprev, m = j % n, (j - 1) % n, valid * nt
-                st = pipe.streams[k]
-                with torch.cuda.stream(st):
-                    new = dev_in[k][1:]
-                    new.copy_(host_in[r], non_blocking=True)
-                    dev_held[k][:m].copy_(host_held[r][:m], non_blocking=True)
-                    st.wait_event(ingested[kprev])
-                    planes[k][0].copy_(planes[kprev][pb])
-                    clip.ingest(new, planes[k][1:])
-                    for q in range(valid + 1):          # kept row q of dev_in[k]: the right frame of group q - 1, the left one of group q
-                        lo, hi = max(0, (q - 1) * nt + nl), min(m, q * nt + nl)
-                        if hi > lo:
-                            compare(1, dev_held[k][lo:hi], dev_in[k][q:q + 1].expand(hi - lo, fb), slice(lo, hi))
-                    if mix:
-                        for q in range(valid):          # group q: kept rows q (left) and q + 1 (right) of dev_in[k], k = 1 .. hold - 1
-                            payload_mix(dev_in[k][q:q + 1].expand(nt, fb), dev_in[k][q + 1:q + 2].expand(nt, fb), 1, 1, hold, bits,
-                                        out=dev_mix[k][q * nt:(q + 1) * nt])
-                        compare(2, dev_mix[k][:m], dev_held[k][:m], slice(m))
-                    dev_in[(j + 1) % n][0].copy_(dev_in[k][pb])
-                    ingested[k].record()
-                    x = planes[k]
-                    img6 = x.view(1, 6, hp, wp) if pb == 1 else x.as_strided((pb, 6, hp, wp), (3 * hp * wp, hp * wp, wp, 1))
-                    frames = pipe.engines[k].run(img6, t_dev, False)
-                    clip.egress(frames, dev_out[k])
-                    host_out[r].copy_(dev_out[k], non_blocking=True)
-                    compare(0, dev_out[k][:m], dev_held[k][:m], slice(m))
-                    host_sums[r].copy_(dev_sums[k], non_blocking=True)
-                    done[r].record()
-                ring.hand(r, done[r], functools.partial(rows_of, r, valid, (res.kept - 1) - valid))
-                res.written += valid * hold
-                j += 1
+            return 1
+
+        def submit(j, r, valid):
+            k, kprev, m = j % n, (j - 1) % n, valid * nt
+            st = pipe.streams[k]
+
+            def compare(column, a, b, rows):
+                """Queues the squared differences of payloads a against b into rows `rows` of column `column` of the pass's sums, and
+                with ssim on their SSIM into the same rows of the column's SSIM block."""
+                plane_sse(a, b, h, w, siting, bits, out=dev_sums[k][column, rows])
+                if ssim:
+                    plane_ssim(a, b, h, w, siting, bits, out=dev_sums[k][cols + column, rows])
+
+            with torch.cuda.stream(st):
+                new = dev_in[k][1:]
+                new.copy_(host_in[r], non_blocking=True)
+                dev_held[k][:m].copy_(host_held[r][:m], non_blocking=True)
+                st.wait_event(ingested[kprev])
+                planes[k][0].copy_(planes[kprev][pb])
+                clip.ingest(new, planes[k][1:])
+                for q in range(valid + 1):          # kept row q of dev_in[k]: the right frame of group q - 1, the left one of group q
+                    lo, hi = max(0, (q - 1) * nt + nl), min(m, q * nt + nl)
+                    if hi > lo:
+                        compare(1, dev_held[k][lo:hi], dev_in[k][q:q + 1].expand(hi - lo, fb), slice(lo, hi))
+                if mix:
+                    for q in range(valid):          # group q: kept rows q (left) and q + 1 (right) of dev_in[k], k = 1 .. hold - 1
+                        payload_mix(dev_in[k][q:q + 1].expand(nt, fb), dev_in[k][q + 1:q + 2].expand(nt, fb), 1, 1, hold, bits,
+                                    out=dev_mix[k][q * nt:(q + 1) * nt])
+                    compare(2, dev_mix[k][:m], dev_held[k][:m], slice(m))
+                dev_in[(j + 1) % n][0].copy_(dev_in[k][pb])
+                ingested[k].record()
+                x = planes[k]
+                img6 = x.view(1, 6, hp, wp) if pb == 1 else x.as_strided((pb, 6, hp, wp), (3 * hp * wp, hp * wp, wp, 1))
+                frames = pipe.engines[k].run(img6, t_dev, False)
+                clip.egress(frames, dev_out[k])
+                host_out[r].copy_(dev_out[k], non_blocking=True)
+                compare(0, dev_out[k][:m], dev_held[k][:m], slice(m))
+                host_sums[r].copy_(dev_sums[k], non_blocking=True)
+                done[r].record()
+
+        def rows_of(r, on_gpu, valid):
+            res.kept += valid
+            return functools.partial(scored, r, valid if on_gpu else 0, (res.kept - 1) - valid), valid * hold
+
+        res.written = vi._run_passes(clip, writer, done, lambda ring, issue: V.read_blocks(ring, pb, np_in, read_group, issue),
+                                     lambda valid: valid > 0, submit, rows_of, first=frame0)
         return res
 
+
+def group_reader(reader, res, hold, np_held, np_in):
+    """The unit reader HoldOutScorer hands to video.read_blocks: read_group(r, i) reads group i of the pass on ring slot r - its hold - 1
+    held-out frames into rows i (hold - 1) .. of np_held[r], then the kept frame that closes it into np_in[r][i] - and says whether the
+    group is whole.  It keeps res.frames_read, and res.trailing: the frames of the group that the end of the stream cut short."""
+    def read_group(r, i):
+        for pending in range(hold):
+            into = np_held[r][i * (hold - 1) + pending] if pending < hold - 1 else np_in[r][i]
+            if not reader.read_frame_into(into):
+                res.trailing = pending
+                return False
+            res.frames_read += 1
+        return True
+
+    return read_group

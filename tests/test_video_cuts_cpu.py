@@ -177,12 +177,13 @@ def test_ring_calls_a_callable_for_its_rows_after_the_event():
 
 
 def test_rows_of_a_pass_under_cuts():
-    """_cut_rows without a GPU: two passes of two pairs at upsample_rate 4, the cut in the first pair of the second pass - its left frame is
-    the one the first pass carried over."""
-    from ssm_amd.video import SceneCuts, VideoInterpolator
+    """PairOptions.written, the writer thread's callable, without a GPU: two passes of two pairs at upsample_rate 4, the cut in the first
+    pair of the second pass - its left frame is the one the first pass carried over."""
+    from ssm_amd.video import C444, LIMITED, BT601, Clip, PairOptions, VideoInterpolator
     vi = VideoInterpolator(None, cfg(), upsample_rate=4, pairs_per_batch=2, scene_cut=Fr(1, 10))
-    cuts, px = SceneCuts(vi.scene_cut), 10
-    carried = np.array([0], np.uint8)
+    opt = PairOptions(vi, Clip(1, 10, C444, BT601, LIMITED), vi.scene_cut)          # a luma plane of 10 pixels
+    assert opt.pixels == 10 and opt.lead == 1 and opt.paste is None
+    carried = opt.carried = np.array([0], np.uint8)
     frames = [np.array([10 + i], np.uint8) for i in range(5)]          # input frames 0 .. 4 as one-byte payloads; `carried` starts as frame 0
     carried[:] = frames[0]
     synth = {(i, s): np.array([100 + 10 * i + s], np.uint8) for i in range(4) for s in (1, 2, 3)}
@@ -192,7 +193,7 @@ def test_rows_of_a_pass_under_cuts():
         order = []
         for p in range(2):
             order += [(synth[(i0 + p, s)], (p, Fr(s, 4))) for s in (1, 2, 3)] + [(frames[i0 + p + 1], None)]
-        got += [int(b[0]) for b in vi._cut_rows(cuts, px, np.array(sums, np.uint64), pairs, order, carried)]
+        got += [int(b[0]) for b in opt.written([i for i, _, _ in pairs], np.array(sums, np.uint64), None, pairs, order)]
         assert int(carried[0]) == 10 + i0 + 2
     assert got == [101, 102, 103, 11, 111, 112, 113, 12,          # pairs 0 and 1 as synthesised
                    12, 13, 13, 13, 131, 132, 133, 14]            # pair 2 is the cut: frame 2 at t = 1/4, frame 3 at t = 1/2 and 3/4
