@@ -1,5 +1,5 @@
-"""Letterboxed clips of the streamed video path (ssm_amd/video.py) on synthetic frames, in the manner of
-tools/bench_dedup.py: three steps, each a child process under its own `timeout`, chained - the first one that fails (or runs into its
+"""Letterboxed clips of the streamed video path (ssm_amd/video.py) on synthetic frames.  Driver, timers and fixture are
+tools/video_bench.py's: three steps, each a child process under its own `timeout`, chained - the first one that fails (or runs into its
 limit) ends the run.  Each step prints one JSON line:
   kernel_bytes, kernel_words
            event-timed ssm_luma_counts_fwd and ssm_window_cut_fwd (the 1920 x 800 picture at row 140) on 7 frames of 1080 x 1920, 420jpeg
@@ -13,21 +13,13 @@ limit) ends the run.  Each step prints one JSON line:
            alone.  with_active over alone is the cost of cut, paste and probe; with_active over without is what the option saves.
 Nothing is asserted on the numbers.  With synthetic weights nothing can be said about quality.
 Usage: python tools/bench_active.py [--out profiles/active_bench.txt] [--only STEP] [--iters 20] [--windows 7] [--runs 3]"""
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "superslomo-videointerpolation-pytorch_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "scripts"), os.path.join(ROOT, "tools")):
-    sys.path.insert(0, p)
-
-from bench_fields import alternated_ms  # noqa: E402
+from video_bench import alternated_ms, drive, parser, per_s, run_only, synthetic_model, synthetic_payloads, timed_legs, write_y4m
 
 STEPS = (("kernel_bytes", 180), ("kernel_words", 180), ("fps", 900))          # step, its time limit in seconds
 H, W, FRAMES = 1080, 1920, 65
@@ -75,25 +67,12 @@ def bench_kernel(dev, tag, iters, windows):
 
 def bench_fps(dev, runs):
     import numpy as np
-    import torch
-    from models.superslomo_r import FullModel
-    from ssm_amd import frames as F
     from ssm_amd import video as V
-    from ssm_amd.config import load_config, synthetic_weight_overrides
-    from ssm_amd.weights import synthetic_frames_u8, synthetic_state_dict
-    cfg = load_config("superslomo_original.ini", synthetic_weight_overrides())
-    model = FullModel(cfg)
-    model.stage1_model.load_state_dict(synthetic_state_dict(1))
-    model.stage2_model.load_state_dict(synthetic_state_dict(2))
-    model = model.to(dev).eval()
+    model, cfg = synthetic_model(dev)
     pw, ph = RECT[:2]
-    matrix, crange, siting = V.default_matrix(H), V.LIMITED, V.CENTRED
+    matrix, siting = V.default_matrix(H), V.CENTRED          # the picture's 800 rows get the frame's matrix either way
     half = FRAMES // 2 + 1          # the synthetic clip moves (3, 2) pixels a frame and has room for 42 frames: there and back again
-    picture, frames_u8 = [], synthetic_frames_u8(half, ph, pw, seed=42)
-    for i in range(0, half, 8):
-        rgb = frames_u8[i:i + 8].permute(0, 2, 3, 1).contiguous()
-        picture.append(V.frames_to_yuv(F.frames_from_u8(rgb.to(dev), cfg, True), ph, pw, siting, matrix, crange, cfg).cpu())
-    picture = torch.cat(picture).numpy()
+    picture = synthetic_payloads(half, ph, pw, dev, cfg)
     picture = np.concatenate([picture, picture[-2::-1]])
     assert len(picture) == FRAMES
     bars = np.zeros((FRAMES, V.frame_bytes(H, W, siting)), np.uint8)
@@ -105,31 +84,25 @@ def bench_fps(dev, runs):
     kw = dict(upsample_rate=8, n_streams=2, pairs_per_batch=1, matrix=matrix)
     vis = dict(zip(legs, (V.VideoInterpolator(model, cfg, active="auto", **kw), V.VideoInterpolator(model, cfg, **kw),
                           V.VideoInterpolator(model, cfg, **kw))))
-    secs, count = {k: [] for k in legs}, {}
+    count, turns = {}, []
     with tempfile.TemporaryDirectory(prefix="bench_active_") as tmp:
         paths = dict(zip(legs, (os.path.join(tmp, "boxed.y4m"), os.path.join(tmp, "boxed.y4m"), os.path.join(tmp, "picture.y4m"))))
         for name, clip, (h, w) in ((legs[0], boxed, (H, W)), (legs[2], picture, (ph, pw))):
-            with V.Y4MWriter(paths[name], w, h, rate=(24, 1), aspect=(1, 1), chroma="420jpeg") as wr:
-                for p in clip:
-                    wr.write_frame(p)
-        for turn in range(runs + 1):          # turn 0: plans, pinned buffers' first touch
-            for name in legs:
-                t0 = time.perf_counter()
-                with V.Y4MReader(paths[name]) as r:
-                    with V.Y4MWriter.like(os.devnull, r) as w:
-                        count[name] = vis[name].run(r, w)
-                        w.f.flush()
-                dt = time.perf_counter() - t0
-                print("turn %d, %s: %.2f s" % (turn, name, dt), file=sys.stderr, flush=True)
-                if turn > 0:
-                    secs[name].append(dt)
+            write_y4m(paths[name], clip, w, h, (24, 1))
+
+        def run(name):          # the clock runs while the files are opened and closed
+            t0 = time.perf_counter()
+            with V.Y4MReader(paths[name]) as r:
+                with V.Y4MWriter.like(os.devnull, r) as w:
+                    count[name] = vis[name].run(r, w)
+                    w.f.flush()
+            dt = time.perf_counter() - t0
+            print("turn %d, %s: %.2f s" % (turns[-1], name, dt), file=sys.stderr, flush=True)
+            return dt
+
+        secs = timed_legs(legs, run, runs, between=turns.append)
     assert vis[legs[0]].active == RECT and vis[legs[0]].active_excess == [] and len(set(count.values())) == 1
     med = {k: statistics.median(ts) for k, ts in secs.items()}
-
-    def per_s(c, ts):
-        v = [c / t for t in ts]
-        return {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
-
     hp, wp = vis[legs[0]].canvas(ph, pw), vis[legs[0]].canvas(H, W)
     return {"output_frames_per_s": {k: per_s(count[k], ts) for k, ts in secs.items()},
             "seconds_per_run": {k: [round(t, 3) for t in ts] for k, ts in secs.items()},
@@ -148,35 +121,16 @@ def run_step(step, args):
     return bench_fps(dev, args.runs) if step == "fps" else bench_kernel(dev, TAGS[step], args.iters, args.windows)
 
 
+HEAD = ("Letterboxed clips of the streamed video path (ssm_luma_counts_fwd, ssm_window_cut_fwd, ActiveSource, --active; DESIGN 3.12).\nOne "
+        "MI355X, the default precision, synthetic weights and frames.  Tool: tools/bench_active.py (each step a process under its own "
+        "time limit).\nNothing is asserted; with synthetic weights nothing can be said about quality.\n")
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=[s for s, _ in STEPS], default=None, help="run this step in this process (what the driver starts)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "active_bench.txt"))
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=7)
-    ap.add_argument("--runs", type=int, default=3)
-    args = ap.parse_args()
+    args = parser("active_bench.txt", STEPS).parse_args()
     if args.only:
-        print(json.dumps({args.only: run_step(args.only, args)}))
-        return 0
-    head = ("Letterboxed clips of the streamed video path (ssm_luma_counts_fwd, ssm_window_cut_fwd, ActiveSource, --active; DESIGN 3.12).\nOne "
-            "MI355X, the default precision, synthetic weights and frames.  Tool: tools/bench_active.py (each step a process under its own "
-            "time limit).\nNothing is asserted; with synthetic weights nothing can be said about quality.\n")
-    with open(args.out, "w") as f:
-        f.write(head)
-    for step, limit in STEPS:
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--only", step, "--iters", str(args.iters),
-               "--windows", str(args.windows), "--runs", str(args.runs)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        line = r.stdout.strip().splitlines()[-1] if r.stdout.strip() else ""
-        with open(args.out, "a") as f:
-            f.write("\n== %s: `python tools/bench_active.py --only %s` (limit %d s, exit status %d) ==\n" % (step, step, limit, r.returncode))
-            if r.returncode == 0:
-                f.write(json.dumps(json.loads(line), indent=1) + "\n")
-        print("%s: exit status %d %s" % (step, r.returncode, line), flush=True)
-        if r.returncode != 0:          # a failure, a fault or a time limit: nothing more is started on the GPU
-            return r.returncode
-    return 0
+        return run_only(args.only, lambda: run_step(args.only, args))
+    return drive(__file__, HEAD, STEPS, args)
 
 
 if __name__ == "__main__":

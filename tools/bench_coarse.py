@@ -17,15 +17,11 @@ Usage: python tools/bench_coarse.py [--only kernels|fps|closeness] [--iters 20] 
 import argparse
 import gc
 import json
-import os
 import statistics
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "superslomo-videointerpolation-pytorch_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "scripts")):
-    sys.path.insert(0, p)
+from video_bench import COPY_CEILING_BYTES_PER_S, call_ms          # and the import path
+
 import torch  # noqa: E402
 
 from ssm_amd import hipbind as hb  # noqa: E402
@@ -33,25 +29,8 @@ from ssm_amd.engine import PairPipeline  # noqa: E402
 from ssm_amd.frames import padded_dims  # noqa: E402
 from ssm_amd.weights import IMAGENET_MEAN, IMAGENET_STD, synthetic_frames, synthetic_state_dict  # noqa: E402
 
-COPY_CEILING_BYTES_PER_S = 6.29e12
 NT = 7
 SCALES = (1, 2, 4)
-
-
-def call_ms(fn, iters, windows):
-    for _ in range(5):
-        fn()
-    out = []
-    for _ in range(windows):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / iters)
-    return statistics.median(out)
 
 
 def kernel_record(ms, nbytes, pixels):

@@ -1,5 +1,5 @@
-"""3:2 pulldown removal of the streamed video path (ssm_amd/video.py) on synthetic frames, in the manner of
-tools/bench_fields.py: three steps, each a child process under its own `timeout`, chained - the first one that fails (or runs into its
+"""3:2 pulldown removal of the streamed video path (ssm_amd/video.py) on synthetic frames.  Driver, timers and fixture are
+tools/video_bench.py's: three steps, each a child process under its own `timeout`, chained - the first one that fails (or runs into its
 limit) ends the run.  Each step prints one JSON line:
   kernel_bytes, kernel_words
            event-timed ssm_field_diff_fwd on 7 frame pairs (rows n + 1 against rows n of 8 payloads of 720 x 1280, 4:2:0, 8-bit or 10-bit in
@@ -13,21 +13,14 @@ limit) ends the run.  Each step prints one JSON line:
            buffers included.
 Nothing is asserted on the numbers.  With synthetic weights nothing can be said about quality.
 Usage: python tools/bench_detelecine.py [--out profiles/detelecine_bench.txt] [--only STEP] [--iters 20] [--windows 7] [--runs 3]"""
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "superslomo-videointerpolation-pytorch_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "scripts"), os.path.join(ROOT, "tools")):
-    sys.path.insert(0, p)
-
-from bench_fields import COPY_CEILING_BYTES_PER_S, alternated_ms  # noqa: E402
+from video_bench import (COPY_CEILING_BYTES_PER_S, alternated_ms, drive, parser, per_s, run_only, synthetic_model, synthetic_payloads,
+                         timed_legs, write_y4m)
 
 STEPS = (("kernel_bytes", 180), ("kernel_words", 180), ("fps", 600))          # step, its time limit in seconds
 H, W, FILM_FRAMES = 720, 1280, 52
@@ -70,22 +63,11 @@ def bench_kernel(dev, tag, iters, windows):
 
 
 def bench_fps(dev, runs):
-    import torch
-    from models.superslomo_r import FullModel
-    from ssm_amd import frames as F
     from ssm_amd import video as V
-    from ssm_amd.config import load_config, synthetic_weight_overrides
-    from ssm_amd.weights import synthetic_frames_u8, synthetic_state_dict
-    cfg = load_config("superslomo_original.ini", synthetic_weight_overrides())
-    model = FullModel(cfg)
-    model.stage1_model.load_state_dict(synthetic_state_dict(1))
-    model.stage2_model.load_state_dict(synthetic_state_dict(2))
-    model = model.to(dev).eval()
+    model, cfg = synthetic_model(dev)
     base = 43          # synthetic_frames_u8 holds 43 frames at the most: the film plays them forth and back
-    rgb = synthetic_frames_u8(base, H, W, seed=42).permute(0, 2, 3, 1).contiguous()
-    matrix, crange, siting = V.default_matrix(H), V.LIMITED, V.CENTRED
-    made = torch.cat([V.frames_to_yuv(F.frames_from_u8(rgb[i:i + 8].to(dev), cfg, True), H, W, siting, matrix, crange, cfg).cpu()
-                      for i in range(0, base, 8)]).numpy()
+    matrix, siting = V.default_matrix(H), V.CENTRED
+    made = synthetic_payloads(base, H, W, dev, cfg)
     period = 2 * (base - 1)
     film = made[[i % period if i % period < base else period - i % period for i in range(FILM_FRAMES)]]
     video = V.telecine_host(film, H, W, siting, 8, 0, 0)
@@ -93,33 +75,27 @@ def bench_fps(dev, runs):
     rate = (30000, 1001)
     vi = V.VideoInterpolator(model, cfg, upsample_rate=2, n_streams=2, pairs_per_batch=1, matrix=matrix)
     legs = ("detelecine_upsample_rate_2_65_frames_720p", "upsample_rate_2_52_film_frames_720p")
-    secs, count, cadence = {k: [] for k in legs}, {}, None
+    count, cadence = {}, {}
     with tempfile.TemporaryDirectory(prefix="bench_detelecine_") as tmp:
         paths = dict(zip(legs, (os.path.join(tmp, "telecined.y4m"), os.path.join(tmp, "film.y4m"))))
         for name, clip, r in zip(legs, (video, film), (rate, V.detelecine_rate(rate))):
-            with V.Y4MWriter(paths[name], W, H, rate=r, aspect=(1, 1), chroma="420jpeg") as wr:
-                for p in clip:
-                    wr.write_frame(p)
-        for turn in range(runs + 1):          # turn 0: plans, pinned buffers' first touch
-            for name in legs:
-                t0 = time.perf_counter()
-                with V.Y4MReader(paths[name], interlaced=True) as r:
-                    if name == legs[0]:
-                        r = V.TelecineSource(r, dev)
-                    with V.Y4MWriter.like(os.devnull, r, rate=V.output_rate(r.rate, 2)) as w:
-                        count[name] = vi.run(r, w)
-                        w.f.flush()
-                dt = time.perf_counter() - t0
+            write_y4m(paths[name], clip, W, H, r)
+
+        def run(name):          # the clock runs while the files are opened and closed and the TelecineSource is made
+            t0 = time.perf_counter()
+            with V.Y4MReader(paths[name], interlaced=True) as r:
                 if name == legs[0]:
-                    cadence = {"windows": len(r.cadence), "hypotheses": sorted({h for _, h, _, _ in r.cadence}), "dropped": r.dropped}
-                if turn > 0:
-                    secs[name].append(dt)
+                    r = V.TelecineSource(r, dev)
+                with V.Y4MWriter.like(os.devnull, r, rate=V.output_rate(r.rate, 2)) as w:
+                    count[name] = vi.run(r, w)
+                    w.f.flush()
+            dt = time.perf_counter() - t0
+            if name == legs[0]:
+                cadence.update(windows=len(r.cadence), hypotheses=sorted({h for _, h, _, _ in r.cadence}), dropped=r.dropped)
+            return dt
+
+        secs = timed_legs(legs, run, runs)
     assert count == {k: 2 * FILM_FRAMES - 1 for k in legs} and cadence == {"windows": 12, "hypotheses": [0], "dropped": 13}
-
-    def per_s(c, ts):
-        v = [c / t for t in ts]
-        return {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
-
     return {"output_frames_per_s": {k: per_s(count[k], ts) for k, ts in secs.items()},
             "seconds_per_run": {k: [round(t, 3) for t in ts] for k, ts in secs.items()},
             "outputs": count, "cadence": cadence,
@@ -136,35 +112,16 @@ def run_step(step, args):
     return bench_fps(dev, args.runs) if step == "fps" else bench_kernel(dev, TAGS[step], args.iters, args.windows)
 
 
+HEAD = ("3:2 pulldown removal of the streamed video path (ssm_field_diff_fwd, TelecineSource, --detelecine; DESIGN 3.12).\nOne MI355X, the "
+        "default precision, synthetic weights and frames.  Tool: tools/bench_detelecine.py (each step a process under its own time "
+        "limit).\nNothing is asserted; with synthetic weights nothing can be said about quality.\n")
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=[s for s, _ in STEPS], default=None, help="run this step in this process (what the driver starts)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "detelecine_bench.txt"))
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=7)
-    ap.add_argument("--runs", type=int, default=3)
-    args = ap.parse_args()
+    args = parser("detelecine_bench.txt", STEPS).parse_args()
     if args.only:
-        print(json.dumps({args.only: run_step(args.only, args)}))
-        return 0
-    head = ("3:2 pulldown removal of the streamed video path (ssm_field_diff_fwd, TelecineSource, --detelecine; DESIGN 3.12).\nOne MI355X, the "
-            "default precision, synthetic weights and frames.  Tool: tools/bench_detelecine.py (each step a process under its own time "
-            "limit).\nNothing is asserted; with synthetic weights nothing can be said about quality.\n")
-    with open(args.out, "w") as f:
-        f.write(head)
-    for step, limit in STEPS:
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--only", step, "--iters", str(args.iters),
-               "--windows", str(args.windows), "--runs", str(args.runs)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        line = r.stdout.strip().splitlines()[-1] if r.stdout.strip() else ""
-        with open(args.out, "a") as f:
-            f.write("\n== %s: `python tools/bench_detelecine.py --only %s` (limit %d s, exit status %d) ==\n" % (step, step, limit, r.returncode))
-            if r.returncode == 0:
-                f.write(json.dumps(json.loads(line), indent=1) + "\n")
-        print("%s: exit status %d %s" % (step, r.returncode, line), flush=True)
-        if r.returncode != 0:          # a failure, a fault or a time limit: nothing more is started on the GPU
-            return r.returncode
-    return 0
+        return run_only(args.only, lambda: run_step(args.only, args))
+    return drive(__file__, HEAD, STEPS, args)
 
 
 if __name__ == "__main__":

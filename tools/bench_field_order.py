@@ -1,5 +1,5 @@
-"""The field probe of the streamed video path (ssm_amd/video.py) on synthetic frames, in the manner of
-tools/bench_detelecine.py: three steps, each a child process under its own `timeout`, chained - the first one that fails (or runs into its
+"""The field probe of the streamed video path (ssm_amd/video.py) on synthetic frames.  Driver, timers and model are
+tools/video_bench.py's: three steps, each a child process under its own `timeout`, chained - the first one that fails (or runs into its
 limit) ends the run.  Each step prints one JSON line:
   kernel_bytes, kernel_words
            event-timed ssm_field_order_sums_fwd on 7 frames (rows n - 1, n, n + 1 of 9 payloads of 720 x 1280, 4:2:0, 8-bit or 10-bit in
@@ -13,21 +13,13 @@ limit) ends the run.  Each step prints one JSON line:
 Nothing is asserted on the numbers.  With synthetic weights nothing can be said about quality.  Nothing was traced: no kernel trace, no
 counters; the times are device events (kernels) and the host's clock around whole runs (stream).
 Usage: python tools/bench_field_order.py [--out profiles/field_order_bench.txt] [--only STEP] [--iters 20] [--windows 7] [--runs 3]"""
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "superslomo-videointerpolation-pytorch_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "scripts"), os.path.join(ROOT, "tools")):
-    sys.path.insert(0, p)
-
-from bench_fields import COPY_CEILING_BYTES_PER_S, alternated_ms  # noqa: E402
+from video_bench import COPY_CEILING_BYTES_PER_S, alternated_ms, drive, parser, per_s, run_only, synthetic_model, timed_legs, write_y4m
 
 STEPS = (("kernel_bytes", 180), ("kernel_words", 180), ("fps", 600))          # step, its time limit in seconds
 H, W, CLIP_FRAMES = 720, 1280, 64
@@ -70,15 +62,8 @@ def bench_kernel(dev, tag, iters, windows):
 
 def bench_fps(dev, runs):
     import numpy as np
-    from models.superslomo_r import FullModel
     from ssm_amd import video as V
-    from ssm_amd.config import load_config, synthetic_weight_overrides
-    from ssm_amd.weights import synthetic_state_dict
-    cfg = load_config("superslomo_original.ini", synthetic_weight_overrides())
-    model = FullModel(cfg)
-    model.stage1_model.load_state_dict(synthetic_state_dict(1))
-    model.stage2_model.load_state_dict(synthetic_state_dict(2))
-    model = model.to(dev).eval()
+    model, cfg = synthetic_model(dev)
     matrix, siting = V.default_matrix(H), V.CENTRED
     # the moving texture of the field-order tests (tests/field_clips.py), top field first: frame i's even rows at field time 2i, its odd
     # rows at 2i + 1; chroma at mid-grey
@@ -94,29 +79,22 @@ def bench_fps(dev, runs):
     legs = {"deinterlace_auto_field_probe_64_frames_720p": dict(deinterlace="auto", field_probe=True),
             "deinterlace_tff_64_frames_720p": dict(deinterlace="tff")}
     vis = {k: V.VideoInterpolator(model, cfg, n_streams=2, pairs_per_batch=1, matrix=matrix, **kw) for k, kw in legs.items()}
-    secs, count = {k: [] for k in legs}, {}
+    count = {}
     with tempfile.TemporaryDirectory(prefix="bench_field_order_") as tmp:
         path = os.path.join(tmp, "ip.y4m")
-        with V.Y4MWriter(path, W, H, rate=rate, aspect=(1, 1), chroma="420jpeg", interlace="p") as wr:
-            for p in clip:
-                wr.write_frame(p)
-        for turn in range(runs + 1):          # turn 0: plans, pinned buffers' first touch
-            for name in legs:
-                t0 = time.perf_counter()
-                with V.Y4MReader(path, interlaced=True) as r:
-                    with V.Y4MWriter.like(os.devnull, r, rate=V.output_rate(r.rate, 2)) as w:
-                        count[name] = vis[name].run(r, w)
-                        w.f.flush()
-                dt = time.perf_counter() - t0
-                if turn > 0:
-                    secs[name].append(dt)
+        write_y4m(path, clip, W, H, rate, interlace="p")
+
+        def run(name):          # the clock runs while the files are opened and closed
+            t0 = time.perf_counter()
+            with V.Y4MReader(path, interlaced=True) as r:
+                with V.Y4MWriter.like(os.devnull, r, rate=V.output_rate(r.rate, 2)) as w:
+                    count[name] = vis[name].run(r, w)
+                    w.f.flush()
+            return time.perf_counter() - t0
+
+        secs = timed_legs(legs, run, runs)
     probe = vis["deinterlace_auto_field_probe_64_frames_720p"].field_probe
     assert count == {k: 2 * CLIP_FRAMES for k in legs} and (probe.verdict, probe.order) == ("tff", "tff"), (count, probe)
-
-    def per_s(c, ts):
-        v = [c / t for t in ts]
-        return {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
-
     a, b = legs
     return {"output_frames_per_s": {k: per_s(count[k], ts) for k, ts in secs.items()},
             "seconds_per_run": {k: [round(t, 3) for t in ts] for k, ts in secs.items()},
@@ -134,36 +112,17 @@ def run_step(step, args):
     return bench_fps(dev, args.runs) if step == "fps" else bench_kernel(dev, TAGS[step], args.iters, args.windows)
 
 
+HEAD = ("The field probe of the streamed video path (ssm_field_order_sums_fwd, FieldOrderSource, --field_probe; DESIGN 3.12).\nOne MI355X, "
+        "the default precision, synthetic weights and frames.  Tool: tools/bench_field_order.py (each step a process under its own time "
+        "limit).\nNothing is asserted; nothing was traced (no kernel trace, no counters); with synthetic weights nothing can be said about "
+        "quality.\n")
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=[s for s, _ in STEPS], default=None, help="run this step in this process (what the driver starts)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "field_order_bench.txt"))
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=7)
-    ap.add_argument("--runs", type=int, default=3)
-    args = ap.parse_args()
+    args = parser("field_order_bench.txt", STEPS).parse_args()
     if args.only:
-        print(json.dumps({args.only: run_step(args.only, args)}))
-        return 0
-    head = ("The field probe of the streamed video path (ssm_field_order_sums_fwd, FieldOrderSource, --field_probe; DESIGN 3.12).\nOne MI355X, "
-            "the default precision, synthetic weights and frames.  Tool: tools/bench_field_order.py (each step a process under its own time "
-            "limit).\nNothing is asserted; nothing was traced (no kernel trace, no counters); with synthetic weights nothing can be said about "
-            "quality.\n")
-    with open(args.out, "w") as f:
-        f.write(head)
-    for step, limit in STEPS:
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--only", step, "--iters", str(args.iters),
-               "--windows", str(args.windows), "--runs", str(args.runs)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        line = r.stdout.strip().splitlines()[-1] if r.stdout.strip() else ""
-        with open(args.out, "a") as f:
-            f.write("\n== %s: `python tools/bench_field_order.py --only %s` (limit %d s, exit status %d) ==\n" % (step, step, limit, r.returncode))
-            if r.returncode == 0:
-                f.write(json.dumps(json.loads(line), indent=1) + "\n")
-        print("%s: exit status %d %s" % (step, r.returncode, line), flush=True)
-        if r.returncode != 0:          # a failure, a fault or a time limit: nothing more is started on the GPU
-            return r.returncode
-    return 0
+        return run_only(args.only, lambda: run_step(args.only, args))
+    return drive(__file__, HEAD, STEPS, args)
 
 
 if __name__ == "__main__":

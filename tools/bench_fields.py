@@ -1,6 +1,6 @@
-"""Interlaced clips of the streamed video path (ssm_amd/video.py) on synthetic frames, in the manner of tools/bench_ssim.py:
-three steps, each a child process under its own `timeout`, chained - the first one that fails (or runs into its limit) ends the run.
-Each step prints one JSON line:
+"""Interlaced clips of the streamed video path (ssm_amd/video.py) on synthetic frames.  Driver, timers and model are
+tools/video_bench.py's: three steps, each a child process under its own `timeout`, chained - the first one that fails (or runs into its
+limit) ends the run.  Each step prints one JSON line:
   kernel_420jpeg, kernel_422p10
            event-timed ssm_fields_split_fwd (7 frames -> 14 fields) and ssm_fields_weave_fwd (7 kept and 7 synthesised fields -> 7 frames;
            and fill = 1: 7 kept fields -> 7 frames with line averages) at 720 x 1280, beside a device-to-device copy of the same 7
@@ -13,47 +13,17 @@ Each step prints one JSON line:
            same work per pair, without split and weave; 2 streams x 1 pair.  Compare per PAIR: pairs_per_s.
 Nothing is asserted on the numbers.  With synthetic weights nothing can be said about quality.
 Usage: python tools/bench_fields.py [--out profiles/fields_bench.txt] [--only STEP] [--iters 20] [--windows 7] [--runs 3]"""
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "superslomo-videointerpolation-pytorch_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "scripts"), os.path.join(ROOT, "tools")):
-    sys.path.insert(0, p)
+from video_bench import (COPY_CEILING_BYTES_PER_S, alternated_ms, drive, parser, per_s, run_only, share_streams, synthetic_model, timed_legs,
+                         write_y4m)
 
 STEPS = (("kernel_420jpeg", 180), ("kernel_422p10", 180), ("fps", 600))          # step, its time limit in seconds
 H, W, CLIP_FRAMES = 720, 1280, 64
-COPY_CEILING_BYTES_PER_S = 6.29e12          # tools/bench_video.py
-
-
-def window_ms(fn, iters):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters
-
-
-def alternated_ms(calls, iters, windows):
-    """{name: {median, min, max}} of the per-call time in ms: `windows` rounds, each timing every call once in turn."""
-    for fn in calls.values():
-        for _ in range(5):
-            fn()
-    out = {k: [] for k in calls}
-    for _ in range(windows):
-        for k, fn in calls.items():
-            out[k].append(window_ms(fn, iters))
-    return {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)} for k, v in out.items()}
 
 
 def bench_kernel(dev, tag, iters, windows):
@@ -93,20 +63,14 @@ def bench_kernel(dev, tag, iters, windows):
 def bench_fps(dev, runs):
     import numpy as np
     import torch
-    from models.superslomo_r import FullModel
     from ssm_amd import frames as F
     from ssm_amd import video as V
-    from ssm_amd.config import load_config, synthetic_weight_overrides
-    from ssm_amd.weights import synthetic_frames_u8, synthetic_state_dict
-    cfg = load_config("superslomo_original.ini", synthetic_weight_overrides())
-    model = FullModel(cfg)
-    model.stage1_model.load_state_dict(synthetic_state_dict(1))
-    model.stage2_model.load_state_dict(synthetic_state_dict(2))
-    model = model.to(dev).eval()
+    from ssm_amd.weights import synthetic_frames_u8
+    model, cfg = synthetic_model(dev)
     fh, n_fields = H // 2, 2 * CLIP_FRAMES
     base = 43          # synthetic_frames_u8 holds 43 frames at the most: the clip plays them forth and back
     rgb = synthetic_frames_u8(base, fh, W, seed=42).permute(0, 2, 3, 1).contiguous()
-    matrix, crange, siting = V.default_matrix(H), V.LIMITED, V.CENTRED
+    matrix, crange, siting = V.default_matrix(H), V.LIMITED, V.CENTRED          # the FRAME's matrix for the 360-row fields: not synthetic_payloads
     made = torch.cat([V.frames_to_yuv(F.frames_from_u8(rgb[i:i + 8].to(dev), cfg, True), fh, W, siting, matrix, crange, cfg).cpu()
                       for i in range(0, base, 8)]).numpy()
     period = 2 * (base - 1)
@@ -114,37 +78,26 @@ def bench_fps(dev, runs):
     woven = np.concatenate([V.weave_fields_host(fields[f:f + 1], fields[f + 1:f + 2], H, W, siting, 8, V.TOP, 0) for f in range(0, n_fields, 2)])
     legs = {"deinterlace_auto_64_frames_720p_It": V.VideoInterpolator(model, cfg, n_streams=2, pairs_per_batch=1, matrix=matrix, deinterlace="auto"),
             "upsample_rate_2_128_frames_360x1280": V.VideoInterpolator(model, cfg, upsample_rate=2, n_streams=2, pairs_per_batch=1, matrix=matrix)}
-    secs, count = {k: [] for k in legs}, {}
+    count = {}
     with tempfile.TemporaryDirectory(prefix="bench_fields_") as tmp:
         paths = {"deinterlace_auto_64_frames_720p_It": os.path.join(tmp, "interlaced.y4m"),
                  "upsample_rate_2_128_frames_360x1280": os.path.join(tmp, "progressive.y4m")}
-        with V.Y4MWriter(paths["deinterlace_auto_64_frames_720p_It"], W, H, rate=(25, 1), aspect=(1, 1), chroma="420jpeg", interlace="t") as wr:
-            for p in woven:
-                wr.write_frame(p)
-        with V.Y4MWriter(paths["upsample_rate_2_128_frames_360x1280"], W, fh, rate=(50, 1), aspect=(1, 1), chroma="420jpeg") as wr:
-            for p in fields:
-                wr.write_frame(p)
-        for turn in range(runs + 2):          # turn 0: plans, pinned buffers' first touch; turn 1: the first run on the shared streams
-            if turn == 1:
-                legs["deinterlace_auto_64_frames_720p_It"]._pipe[1].streams = legs["upsample_rate_2_128_frames_360x1280"]._pipe[1].streams
-            for name, vi in legs.items():
-                with V.Y4MReader(paths[name], interlaced=True) as r, V.Y4MWriter.like(os.devnull, r, rate=V.output_rate(r.rate, 2)) as w:
-                    t0 = time.perf_counter()
-                    count[name] = vi.run(r, w)
-                    w.f.flush()
-                    dt = time.perf_counter() - t0
-                if turn > 1:
-                    secs[name].append(dt)
+        write_y4m(paths["deinterlace_auto_64_frames_720p_It"], woven, W, H, (25, 1), interlace="t")
+        write_y4m(paths["upsample_rate_2_128_frames_360x1280"], fields, W, fh, (50, 1))
+
+        def run(name):          # the clock starts with the files open
+            with V.Y4MReader(paths[name], interlaced=True) as r, V.Y4MWriter.like(os.devnull, r, rate=V.output_rate(r.rate, 2)) as w:
+                t0 = time.perf_counter()
+                count[name] = legs[name].run(r, w)
+                w.f.flush()
+                return time.perf_counter() - t0
+
+        secs = timed_legs(legs, run, runs, warmup=2, between=share_streams(list(legs.values())[::-1]))          # on the progressive leg's streams
     assert count == {"deinterlace_auto_64_frames_720p_It": n_fields, "upsample_rate_2_128_frames_360x1280": 2 * n_fields - 1}
     pairs = {"deinterlace_auto_64_frames_720p_It": n_fields - 2, "upsample_rate_2_128_frames_360x1280": n_fields - 1}
-
-    def rate(c, ts):
-        v = [c / t for t in ts]
-        return {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
-
     per_pair = {k: statistics.median(ts) / pairs[k] for k, ts in secs.items()}
-    return {"output_frames_per_s": {k: rate(count[k], ts) for k, ts in secs.items()},
-            "pairs_per_s": {k: rate(pairs[k], ts) for k, ts in secs.items()},
+    return {"output_frames_per_s": {k: per_s(count[k], ts) for k, ts in secs.items()},
+            "pairs_per_s": {k: per_s(pairs[k], ts) for k, ts in secs.items()},
             "seconds_per_run": {k: [round(t, 3) for t in ts] for k, ts in secs.items()},
             "outputs": count, "pairs": pairs,
             "deinterlace_over_progressive_time_per_pair": round(per_pair["deinterlace_auto_64_frames_720p_It"] /
@@ -161,35 +114,16 @@ def run_step(step, args):
     return bench_fps(dev, args.runs) if step == "fps" else bench_kernel(dev, step.split("_", 1)[1], args.iters, args.windows)
 
 
+HEAD = ("Interlaced clips of the streamed video path (ssm_fields_split_fwd, ssm_fields_weave_fwd, VideoInterpolator(deinterlace=); DESIGN "
+        "3.12).\nOne MI355X, the default precision, synthetic weights and frames.  Tool: tools/bench_fields.py (each step a process under "
+        "its own time limit).\nNothing is asserted; with synthetic weights nothing can be said about quality.\n")
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=[s for s, _ in STEPS], default=None, help="run this step in this process (what the driver starts)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fields_bench.txt"))
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=7)
-    ap.add_argument("--runs", type=int, default=3)
-    args = ap.parse_args()
+    args = parser("fields_bench.txt", STEPS).parse_args()
     if args.only:
-        print(json.dumps({args.only: run_step(args.only, args)}))
-        return 0
-    head = ("Interlaced clips of the streamed video path (ssm_fields_split_fwd, ssm_fields_weave_fwd, VideoInterpolator(deinterlace=); DESIGN "
-            "3.12).\nOne MI355X, the default precision, synthetic weights and frames.  Tool: tools/bench_fields.py (each step a process under "
-            "its own time limit).\nNothing is asserted; with synthetic weights nothing can be said about quality.\n")
-    with open(args.out, "w") as f:
-        f.write(head)
-    for step, limit in STEPS:
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--only", step, "--iters", str(args.iters),
-               "--windows", str(args.windows), "--runs", str(args.runs)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        line = r.stdout.strip().splitlines()[-1] if r.stdout.strip() else ""
-        with open(args.out, "a") as f:
-            f.write("\n== %s: `python tools/bench_fields.py --only %s` (limit %d s, exit status %d) ==\n" % (step, step, limit, r.returncode))
-            if r.returncode == 0:
-                f.write(json.dumps(json.loads(line), indent=1) + "\n")
-        print("%s: exit status %d %s" % (step, r.returncode, line), flush=True)
-        if r.returncode != 0:          # a failure, a fault or a time limit: nothing more is started on the GPU
-            return r.returncode
-    return 0
+        return run_only(args.only, lambda: run_step(args.only, args))
+    return drive(__file__, HEAD, STEPS, args)
 
 
 if __name__ == "__main__":

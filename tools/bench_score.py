@@ -1,5 +1,6 @@
-"""Hold-out scoring of the streamed video path (ssm_amd/video_score.py) on synthetic frames.  Three steps, each a child process
-under its own `timeout`, chained: the first one that fails (or runs into its limit) ends the run.  Each step prints one JSON line:
+"""Hold-out scoring of the streamed video path (ssm_amd/video_score.py) on synthetic frames.  Driver, timer and fixture
+are tools/video_bench.py's.  Three steps, each a child process under its own `timeout`, chained: the first one that fails (or runs into
+its limit) ends the run.  Each step prints one JSON line:
   kernel_420jpeg, kernel_422p10
            event-timed ssm_plane_sse_fwd (its memset included) on 7 frame pairs at 720p - frames n and n + 1 of 8 payloads in one buffer -
            beside device-to-device copies in the same run: one of N frame_bytes, which reads and writes together the 2 N frame_bytes the
@@ -13,24 +14,17 @@ under its own `timeout`, chained: the first one that fails (or runs into its lim
            own passes is 2 + 1 small calls per pass.
 Nothing is asserted on the numbers; no one had measured either.  With synthetic weights the PSNR values say nothing about quality.
 Usage: python tools/bench_score.py [--out profiles/video_score_bench.txt] [--only STEP] [--iters 20] [--windows 7] [--runs 3]"""
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "superslomo-videointerpolation-pytorch_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "scripts"), os.path.join(ROOT, "tools")):
-    sys.path.insert(0, p)
-from bench_shutter import call_ms  # noqa: E402
+from video_bench import (COPY_CEILING_BYTES_PER_S, call_ms, drive, parser, per_s, run_only, share_streams, synthetic_model,
+                         synthetic_payloads, timed_legs, write_y4m)
 
 STEPS = (("kernel_420jpeg", 180), ("kernel_422p10", 180), ("fps", 600))          # step, its time limit in seconds
 H, W, HOLD, CLIP_FRAMES = 720, 1280, 8, 65
-COPY_CEILING_BYTES_PER_S = 6.29e12          # tools/bench_video.py
 
 
 def bench_kernel(dev, tag, iters, windows):
@@ -63,64 +57,37 @@ def bench_kernel(dev, tag, iters, windows):
 
 
 def bench_fps(dev, runs):
-    import torch
-    from models.superslomo_r import FullModel
-    from ssm_amd import frames as F
     from ssm_amd import video as V
     from ssm_amd import video_score as S
-    from ssm_amd.config import load_config, synthetic_weight_overrides
-    from ssm_amd.weights import synthetic_frames_u8, synthetic_state_dict
-    cfg = load_config("superslomo_original.ini", synthetic_weight_overrides())
-    model = FullModel(cfg)
-    model.stage1_model.load_state_dict(synthetic_state_dict(1))
-    model.stage2_model.load_state_dict(synthetic_state_dict(2))
-    model = model.to(dev).eval()
+    model, cfg = synthetic_model(dev)
     base = 43          # synthetic_frames_u8 holds 43 frames of this size at the most: the clip plays them forth and back
-    rgb = synthetic_frames_u8(base, H, W, seed=42).permute(0, 2, 3, 1).contiguous()
-    matrix, crange, siting = V.default_matrix(H), V.LIMITED, V.CENTRED
-    made = torch.cat([V.frames_to_yuv(F.frames_from_u8(rgb[i:i + 8].to(dev), cfg, True), H, W, siting, matrix, crange, cfg).cpu()
-                      for i in range(0, base, 8)]).numpy()
+    made = synthetic_payloads(base, H, W, dev, cfg)
     order = [i if i < base else 2 * (base - 1) - i for i in range(CLIP_FRAMES)]
     payloads = made[order]
     scorer = S.HoldOutScorer(model, cfg, HOLD, n_streams=2, pairs_per_batch=1)
     tool = V.VideoInterpolator(model, cfg, upsample_rate=HOLD, n_streams=2, pairs_per_batch=1)
-    secs, last = {"hold_out_scorer": [], "video_interpolator": []}, {}
+    last = {}
     with tempfile.TemporaryDirectory(prefix="bench_score_") as tmp:
         full, kept = os.path.join(tmp, "clip.y4m"), os.path.join(tmp, "kept.y4m")
-        for path, rows, rate in ((full, payloads, (240, 1)), (kept, payloads[::HOLD], (30, 1))):
-            with V.Y4MWriter(path, W, H, rate=rate, aspect=(1, 1), chroma="420jpeg") as wr:
-                for p in rows:
-                    wr.write_frame(p)
-        for turn in range(runs + 2):          # turn 0: plans, pinned buffers' first touch; turn 1: the first run on the shared streams
-            if turn == 1:
-                scorer.vi._pipe[1].streams = tool._pipe[1].streams
-            with V.Y4MReader(full) as r, V.Y4MWriter.like(os.devnull, r) as w:
+        write_y4m(full, payloads, W, H, (240, 1))
+        write_y4m(kept, payloads[::HOLD], W, H, (30, 1))
+        legs = {"hold_out_scorer": (scorer, full, {}), "video_interpolator": (tool, kept, {"rate": (240, 1)})}
+
+        def run(name):          # the clock starts with the files open
+            runner, path, kw = legs[name]
+            with V.Y4MReader(path) as r, V.Y4MWriter.like(os.devnull, r, **kw) as w:
                 t0 = time.perf_counter()
-                res = scorer.run(r, w)
+                last[name] = runner.run(r, w)
                 w.f.flush()
-                dt = time.perf_counter() - t0
-            last["hold_out_scorer"] = res
-            if turn > 1:
-                secs["hold_out_scorer"].append(dt)
-            with V.Y4MReader(kept) as r, V.Y4MWriter.like(os.devnull, r, rate=(240, 1)) as w:
-                t0 = time.perf_counter()
-                k = tool.run(r, w)
-                w.f.flush()
-                dt = time.perf_counter() - t0
-            last["video_interpolator"] = k
-            if turn > 1:
-                secs["video_interpolator"].append(dt)
+                return time.perf_counter() - t0
+
+        secs = timed_legs(legs, run, runs, warmup=2, between=share_streams([tool, scorer.vi]))          # on the tool's streams
     res = last["hold_out_scorer"]
     assert res.written == last["video_interpolator"] == CLIP_FRAMES and res.scored == (CLIP_FRAMES - 1) // HOLD * (HOLD - 1)
-
-    def rate(count, ts):
-        v = [count / t for t in ts]
-        return {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
-
-    rec = {"hold_out_scorer": {"input_frames_read_per_s": rate(res.frames_read, secs["hold_out_scorer"]),
-                               "output_frames_per_s": rate(res.written, secs["hold_out_scorer"]),
+    rec = {"hold_out_scorer": {"input_frames_read_per_s": per_s(res.frames_read, secs["hold_out_scorer"]),
+                               "output_frames_per_s": per_s(res.written, secs["hold_out_scorer"]),
                                "frames_read": res.frames_read, "scored": res.scored, "trailing": res.trailing},
-           "video_interpolator_on_the_decimated_clip": {"output_frames_per_s": rate(last["video_interpolator"], secs["video_interpolator"]),
+           "video_interpolator_on_the_decimated_clip": {"output_frames_per_s": per_s(last["video_interpolator"], secs["video_interpolator"]),
                                                         "frames_written": last["video_interpolator"]},
            "scorer_over_tool_time_per_output_frame": round(statistics.median(secs["hold_out_scorer"]) / statistics.median(secs["video_interpolator"]), 4),
            "pooled_psnr_db_synthetic_weights_no_statement_on_quality": {k: {p: round(v, 3) for p, v in d.items()}
@@ -137,35 +104,16 @@ def run_step(step, args):
     return bench_fps(dev, args.runs) if step == "fps" else bench_kernel(dev, step.split("_", 1)[1], args.iters, args.windows)
 
 
+HEAD = ("Hold-out scoring of the streamed video path (squared differences summed per plane on the GPU, rows made on the writer thread; "
+        "DESIGN 3.12).\nOne MI355X, the default precision, synthetic weights and frames.  Tool: tools/bench_score.py (each step a process "
+        "under its own time limit).\nNothing is asserted; the PSNR values of synthetic weights say nothing about quality.\n")
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=[s for s, _ in STEPS], default=None, help="run this step in this process (what the driver starts)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "video_score_bench.txt"))
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=7)
-    ap.add_argument("--runs", type=int, default=3)
-    args = ap.parse_args()
+    args = parser("video_score_bench.txt", STEPS).parse_args()
     if args.only:
-        print(json.dumps({args.only: run_step(args.only, args)}))
-        return 0
-    head = ("Hold-out scoring of the streamed video path (squared differences summed per plane on the GPU, rows made on the writer thread; "
-            "DESIGN 3.12).\nOne MI355X, the default precision, synthetic weights and frames.  Tool: tools/bench_score.py (each step a process "
-            "under its own time limit).\nNothing is asserted; the PSNR values of synthetic weights say nothing about quality.\n")
-    with open(args.out, "w") as f:
-        f.write(head)
-    for step, limit in STEPS:
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--only", step, "--iters", str(args.iters),
-               "--windows", str(args.windows), "--runs", str(args.runs)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        line = r.stdout.strip().splitlines()[-1] if r.stdout.strip() else ""
-        with open(args.out, "a") as f:
-            f.write("\n== %s: `python tools/bench_score.py --only %s` (limit %d s, exit status %d) ==\n" % (step, step, limit, r.returncode))
-            if r.returncode == 0:
-                f.write(json.dumps(json.loads(line), indent=1) + "\n")
-        print("%s: exit status %d %s" % (step, r.returncode, line), flush=True)
-        if r.returncode != 0:          # a failure, a fault or a time limit: nothing more is started on the GPU
-            return r.returncode
-    return 0
+        return run_only(args.only, lambda: run_step(args.only, args))
+    return drive(__file__, HEAD, STEPS, args)
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
-"""The shutter in the light of HDR clips (VideoInterpolator(shutter_light="pq"|"hlg")) on synthetic frames, in the manner of
-tools/bench_shutter_light.py.  One step, a child process under its own `timeout`; a failure (or the limit) ends the run.  It prints one
+"""The shutter in the light of HDR clips (VideoInterpolator(shutter_light="pq"|"hlg")) on synthetic frames.  Driver and timer are
+tools/video_bench.py's.  One step, a child process under its own `timeout`; a failure (or the limit) ends the run.  It prints one
 JSON line:
   kernel   event-timed ssm_frames_accumulate_hdr_fwd on 8 frames at 736x1280 (init = 1, scale = 1/8: 8 planes read, one written), for pq
            and hlg with encode = 0 and 1, and three reference calls alternated with them in the same run: ssm_frames_accumulate_light_fwd
@@ -11,20 +11,11 @@ JSON line:
 Nothing is asserted on the numbers.  The expectation they are there to test: the call stays bandwidth-bound, close to the srgb kernel's
 time, although PQ has four powers where sRGB has two.
 Usage: python tools/bench_shutter_hdr.py [--out profiles/shutter_hdr_bench.txt] [--only kernel] [--iters 20] [--windows 5] [--rounds 3]"""
-import argparse
 import ctypes
-import json
-import os
 import statistics
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "superslomo-videointerpolation-pytorch_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "scripts"), os.path.join(ROOT, "tools")):
-    sys.path.insert(0, p)
-
-from bench_shutter import COPY_CEILING_BYTES_PER_S, call_ms  # noqa: E402
+from video_bench import COPY_CEILING_BYTES_PER_S, call_ms, drive, parser, run_only
 
 STEPS = (("kernel", 300),)          # step, its time limit in seconds
 NAMES = ("pq", "hlg")
@@ -77,38 +68,23 @@ def bench_kernel(dev, iters, windows, rounds):
     return rec
 
 
+def run_step(step, args):
+    import torch
+    assert torch.cuda.is_available(), "bench_shutter_hdr.py measures on the GPU; there is no CPU path"
+    return bench_kernel(torch.device("cuda:0"), args.iters, args.windows, args.rounds)
+
+
+HEAD = ("Shutter in the light of HDR clips in the streamed video path (sub-frames decoded by the BT.2100 PQ EOTF or the inverse HLG OETF before "
+        "they are averaged on the GPU; DESIGN 3.12).\nOne MI355X, synthetic frames.  Tool: tools/bench_shutter_hdr.py (the step is a process "
+        "under its own time limit).\nExpected: the call close to the srgb light kernel's time in the same run, bandwidth-bound.  Nothing is "
+        "asserted.\n")
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=[s for s, _ in STEPS], default=None, help="run this step in this process (what the driver starts)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "shutter_hdr_bench.txt"))
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=5)
-    ap.add_argument("--rounds", type=int, default=3)
-    args = ap.parse_args()
+    args = parser("shutter_hdr_bench.txt", STEPS, windows=5, runs=None, rounds=3).parse_args()          # whole runs are not timed: no --runs
     if args.only:
-        import torch
-        assert torch.cuda.is_available(), "bench_shutter_hdr.py measures on the GPU; there is no CPU path"
-        print(json.dumps({args.only: bench_kernel(torch.device("cuda:0"), args.iters, args.windows, args.rounds)}))
-        return 0
-    head = ("Shutter in the light of HDR clips in the streamed video path (sub-frames decoded by the BT.2100 PQ EOTF or the inverse HLG OETF before "
-            "they are averaged on the GPU; DESIGN 3.12).\nOne MI355X, synthetic frames.  Tool: tools/bench_shutter_hdr.py (the step is a process "
-            "under its own time limit).\nExpected: the call close to the srgb light kernel's time in the same run, bandwidth-bound.  Nothing is "
-            "asserted.\n")
-    with open(args.out, "w") as f:
-        f.write(head)
-    for step, limit in STEPS:
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--only", step, "--iters", str(args.iters),
-               "--windows", str(args.windows), "--rounds", str(args.rounds)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        line = r.stdout.strip().splitlines()[-1] if r.stdout.strip() else ""
-        with open(args.out, "a") as f:
-            f.write("\n== %s: `python tools/bench_shutter_hdr.py --only %s` (limit %d s, exit status %d) ==\n" % (step, step, limit, r.returncode))
-            if r.returncode == 0:
-                f.write(json.dumps(json.loads(line), indent=1) + "\n")
-        print("%s: exit status %d %s" % (step, r.returncode, line), flush=True)
-        if r.returncode != 0:          # a failure, a fault or a time limit: nothing more is started on the GPU
-            return r.returncode
-    return 0
+        return run_only(args.only, lambda: run_step(args.only, args))
+    return drive(__file__, HEAD, STEPS, args)
 
 
 if __name__ == "__main__":

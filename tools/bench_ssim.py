@@ -1,5 +1,5 @@
-"""SSIM and the frame-mix baseline of the hold-out score (ssm_amd/video_score.py) on synthetic frames, in the manner of
-tools/bench_score.py: three steps, each a child process under its own `timeout`, chained - the first one that fails (or runs into its
+"""SSIM and the frame-mix baseline of the hold-out score (ssm_amd/video_score.py) on synthetic frames.  Driver, timers and fixture are
+tools/video_bench.py's: three steps, each a child process under its own `timeout`, chained - the first one that fails (or runs into its
 limit) ends the run.  Each step prints one JSON line:
   kernel_420jpeg, kernel_422p10
            event-timed ssm_plane_ssim_fwd and ssm_payload_mix_fwd on 7 frame pairs at 720p - frames n and n + 1 of 8 payloads in one
@@ -13,40 +13,21 @@ limit) ends the run.  Each step prints one JSON line:
            options is the comparison, never the scorer with itself; 2 streams x 1 pair.
 Nothing is asserted on the numbers.  With synthetic weights the SSIM values say nothing about quality.
 Usage: python tools/bench_ssim.py [--out profiles/video_ssim_bench.txt] [--only STEP] [--iters 20] [--windows 7] [--runs 3]"""
-import argparse
-import json
 import os
 import statistics
-import subprocess
 import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "superslomo-videointerpolation-pytorch_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "scripts"), os.path.join(ROOT, "tools")):
-    sys.path.insert(0, p)
+from video_bench import alternated_ms, drive, parser, per_s, run_only, share_streams, synthetic_model, synthetic_payloads, timed_legs, write_y4m
 
 STEPS = (("kernel_420jpeg", 180), ("kernel_422p10", 180), ("fps", 600))          # step, its time limit in seconds
 H, W, HOLD, CLIP_FRAMES = 720, 1280, 8, 65
 
 
 def call_ms(fn, iters, windows):
-    """{median, min, max} of the per-call time in ms over `windows` event-timed windows of `iters` back-to-back calls."""
-    import torch
-    for _ in range(5):
-        fn()
-    out = []
-    for _ in range(windows):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / iters)
-    return {"median": round(statistics.median(out), 4), "min": round(min(out), 4), "max": round(max(out), 4)}
+    """{median, min, max} of the per-call time in ms of ONE call, its windows back to back: alternated_ms with nothing to alternate with."""
+    return alternated_ms({"call": fn}, iters, windows)["call"]
 
 
 def bench_kernel(dev, tag, iters, windows):
@@ -86,52 +67,32 @@ def bench_kernel(dev, tag, iters, windows):
 
 
 def bench_fps(dev, runs):
-    import torch
-    from models.superslomo_r import FullModel
-    from ssm_amd import frames as F
     from ssm_amd import video as V
     from ssm_amd import video_score as S
-    from ssm_amd.config import load_config, synthetic_weight_overrides
-    from ssm_amd.weights import synthetic_frames_u8, synthetic_state_dict
-    cfg = load_config("superslomo_original.ini", synthetic_weight_overrides())
-    model = FullModel(cfg)
-    model.stage1_model.load_state_dict(synthetic_state_dict(1))
-    model.stage2_model.load_state_dict(synthetic_state_dict(2))
-    model = model.to(dev).eval()
+    model, cfg = synthetic_model(dev)
     base = 43          # synthetic_frames_u8 holds 43 frames of this size at the most: the clip plays them forth and back
-    rgb = synthetic_frames_u8(base, H, W, seed=42).permute(0, 2, 3, 1).contiguous()
-    matrix, crange, siting = V.default_matrix(H), V.LIMITED, V.CENTRED
-    made = torch.cat([V.frames_to_yuv(F.frames_from_u8(rgb[i:i + 8].to(dev), cfg, True), H, W, siting, matrix, crange, cfg).cpu()
-                      for i in range(0, base, 8)]).numpy()
+    made = synthetic_payloads(base, H, W, dev, cfg)
     payloads = made[[i if i < base else 2 * (base - 1) - i for i in range(CLIP_FRAMES)]]
     legs = {"with_ssim_and_mix": S.HoldOutScorer(model, cfg, HOLD, n_streams=2, pairs_per_batch=1, ssim=True, mix=True),
             "without_the_options": S.HoldOutScorer(model, cfg, HOLD, n_streams=2, pairs_per_batch=1)}
-    secs, last = {k: [] for k in legs}, {}
+    last = {}
     with tempfile.TemporaryDirectory(prefix="bench_ssim_") as tmp:
         full = os.path.join(tmp, "clip.y4m")
-        with V.Y4MWriter(full, W, H, rate=(240, 1), aspect=(1, 1), chroma="420jpeg") as wr:
-            for p in payloads:
-                wr.write_frame(p)
-        for turn in range(runs + 2):          # turn 0: plans, pinned buffers' first touch; turn 1: the first run on the shared streams
-            if turn == 1:
-                legs["with_ssim_and_mix"].vi._pipe[1].streams = legs["without_the_options"].vi._pipe[1].streams
-            for name, scorer in legs.items():
-                with V.Y4MReader(full) as r, V.Y4MWriter.like(os.devnull, r) as w:
-                    t0 = time.perf_counter()
-                    last[name] = scorer.run(r, w)
-                    w.f.flush()
-                    dt = time.perf_counter() - t0
-                if turn > 1:
-                    secs[name].append(dt)
+        write_y4m(full, payloads, W, H, (240, 1))
+
+        def run(name):          # the clock starts with the files open
+            with V.Y4MReader(full) as r, V.Y4MWriter.like(os.devnull, r) as w:
+                t0 = time.perf_counter()
+                last[name] = legs[name].run(r, w)
+                w.f.flush()
+                return time.perf_counter() - t0
+
+        secs = timed_legs(legs, run, runs, warmup=2,          # on the streams of the scorer without the options
+                          between=share_streams([legs["without_the_options"].vi, legs["with_ssim_and_mix"].vi]))
     on, off = last["with_ssim_and_mix"], last["without_the_options"]
     assert on.frames == off.frames and on.written == off.written == CLIP_FRAMES and len(on.more) == on.scored
-
-    def rate(count, ts):
-        v = [count / t for t in ts]
-        return {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
-
     pooled = on.pooled()
-    return {"input_frames_read_per_s": {k: rate(on.frames_read, ts) for k, ts in secs.items()},
+    return {"input_frames_read_per_s": {k: per_s(on.frames_read, ts) for k, ts in secs.items()},
             "seconds_per_run": {k: [round(t, 3) for t in ts] for k, ts in secs.items()},
             "with_over_without_time": round(statistics.median(secs["with_ssim_and_mix"]) / statistics.median(secs["without_the_options"]), 4),
             "frames_read": on.frames_read, "scored": on.scored,
@@ -149,35 +110,16 @@ def run_step(step, args):
     return bench_fps(dev, args.runs) if step == "fps" else bench_kernel(dev, step.split("_", 1)[1], args.iters, args.windows)
 
 
+HEAD = ("SSIM and the frame-mix baseline of the hold-out score (ssm_plane_ssim_fwd, ssm_payload_mix_fwd, HoldOutScorer(ssim=True, mix=True); "
+        "DESIGN 3.12).\nOne MI355X, the default precision, synthetic weights and frames.  Tool: tools/bench_ssim.py (each step a process "
+        "under its own time limit).\nNothing is asserted; the SSIM and PSNR values of synthetic weights say nothing about quality.\n")
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=[s for s, _ in STEPS], default=None, help="run this step in this process (what the driver starts)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "video_ssim_bench.txt"))
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=7)
-    ap.add_argument("--runs", type=int, default=3)
-    args = ap.parse_args()
+    args = parser("video_ssim_bench.txt", STEPS).parse_args()
     if args.only:
-        print(json.dumps({args.only: run_step(args.only, args)}))
-        return 0
-    head = ("SSIM and the frame-mix baseline of the hold-out score (ssm_plane_ssim_fwd, ssm_payload_mix_fwd, HoldOutScorer(ssim=True, mix=True); "
-            "DESIGN 3.12).\nOne MI355X, the default precision, synthetic weights and frames.  Tool: tools/bench_ssim.py (each step a process "
-            "under its own time limit).\nNothing is asserted; the SSIM and PSNR values of synthetic weights say nothing about quality.\n")
-    with open(args.out, "w") as f:
-        f.write(head)
-    for step, limit in STEPS:
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--only", step, "--iters", str(args.iters),
-               "--windows", str(args.windows), "--runs", str(args.runs)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        line = r.stdout.strip().splitlines()[-1] if r.stdout.strip() else ""
-        with open(args.out, "a") as f:
-            f.write("\n== %s: `python tools/bench_ssim.py --only %s` (limit %d s, exit status %d) ==\n" % (step, step, limit, r.returncode))
-            if r.returncode == 0:
-                f.write(json.dumps(json.loads(line), indent=1) + "\n")
-        print("%s: exit status %d %s" % (step, r.returncode, line), flush=True)
-        if r.returncode != 0:          # a failure, a fault or a time limit: nothing more is started on the GPU
-            return r.returncode
-    return 0
+        return run_only(args.only, lambda: run_step(args.only, args))
+    return drive(__file__, HEAD, STEPS, args)
 
 
 if __name__ == "__main__":

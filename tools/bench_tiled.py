@@ -1,6 +1,7 @@
 """The tiled mode (tile = (th, tw): the frame runs in overlapping windows, the windows' frames are stitched on the GPU; an
-approximation of the untiled output, not parity) on synthetic frames.  Four steps, each a child process under its own `timeout`, chained:
-the first one that fails (or runs into its limit) ends the run.  Each step prints one JSON line:
+approximation of the untiled output, not parity) on synthetic frames.  Driver and timer are tools/video_bench.py's; the fps loop, which
+builds and frees a pipeline per run, is this tool's own.  Four steps, each a child process under its own `timeout`, chained: the first
+one that fails (or runs into its limit) ends the run.  Each step prints one JSON line:
   stitch   event-timed ssm_tile_stitch_fwd over the four tiles of a 2x2 tiling (tile 1088x1920, halo 256, blend 32) of 7 frames at
            2176x3840 - the four launches that stitch one pass - beside a device-to-device copy of the same bytes on the same box:
            median over `--windows` windows of `--iters` back-to-back calls, per call; the one-touch bytes (every pixel of every region of
@@ -16,41 +17,16 @@ the first one that fails (or runs into its limit) ends the run.  Each step print
            two synthetic frame families.  With synthetic weights this says how the seam error falls with the halo and nothing about
            visual quality: reported, not asserted
 Usage: python tools/bench_tiled.py [--out profiles/tiled_bench.txt] [--only stitch|fps|8k|seam] [--iters 20] [--windows 7] [--runs 3] [--passes 12]"""
-import argparse
 import gc
-import json
-import os
 import statistics
-import subprocess
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "superslomo-videointerpolation-pytorch_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "scripts")):
-    sys.path.insert(0, p)
+from video_bench import COPY_CEILING_BYTES_PER_S, call_ms, drive, parser, run_only
 
-COPY_CEILING_BYTES_PER_S = 6.29e12
 NT = 7
 STEPS = (("stitch", 240), ("fps", 600), ("8k", 420), ("seam", 600))          # step, its time limit in seconds
 TILE_4K, TILE_8K, HALO, BLEND = (1088, 1920), (2176, 3840), 256, 32
-
-
-def call_ms(fn, iters, windows):
-    import torch
-    for _ in range(5):
-        fn()
-    out = []
-    for _ in range(windows):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(iters):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        out.append(e0.elapsed_time(e1) / iters)
-    return statistics.median(out)
 
 
 def bench_stitch(dev, iters, windows):
@@ -229,35 +205,15 @@ def run_step(step, args):
     return bench_seam(dev)
 
 
+HEAD = ("Tiled mode (tile = HxW; DESIGN 3.15) - approximation of the untiled output, not parity.\n"
+        "One MI355X, f32w, synthetic weights and frames.  Tool: tools/bench_tiled.py (each step a process under its own time limit).\n")
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=[s for s, _ in STEPS], default=None, help="run this step in this process (what the driver starts)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tiled_bench.txt"))
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=7)
-    ap.add_argument("--runs", type=int, default=3)
-    ap.add_argument("--passes", type=int, default=12)
-    args = ap.parse_args()
+    args = parser("tiled_bench.txt", STEPS, passes=12).parse_args()
     if args.only:
-        print(json.dumps({args.only: run_step(args.only, args)}))
-        return 0
-    head = ("Tiled mode (tile = HxW; DESIGN 3.15) - approximation of the untiled output, not parity.\n"
-            "One MI355X, f32w, synthetic weights and frames.  Tool: tools/bench_tiled.py (each step a process under its own time limit).\n")
-    with open(args.out, "w") as f:
-        f.write(head)
-    for step, limit in STEPS:
-        cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__), "--only", step, "--iters", str(args.iters),
-               "--windows", str(args.windows), "--runs", str(args.runs), "--passes", str(args.passes)]
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
-        line = r.stdout.strip().splitlines()[-1] if r.stdout.strip() else ""
-        with open(args.out, "a") as f:
-            f.write("\n== %s: `python tools/bench_tiled.py --only %s` (limit %d s, exit status %d) ==\n" % (step, step, limit, r.returncode))
-            if r.returncode == 0:
-                f.write(json.dumps(json.loads(line), indent=1) + "\n")
-        print("%s: exit status %d %s" % (step, r.returncode, line), flush=True)
-        if r.returncode != 0:          # a failure, a fault or a time limit: nothing more is started on the GPU
-            return r.returncode
-    return 0
+        return run_only(args.only, lambda: run_step(args.only, args))
+    return drive(__file__, HEAD, STEPS, args)
 
 
 if __name__ == "__main__":

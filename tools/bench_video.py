@@ -19,25 +19,18 @@ import json
 import os
 import shutil
 import statistics
-import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "superslomo-videointerpolation-pytorch_amd")
-for p in (ROOT, PKG, os.path.join(PKG, "scripts"), os.path.join(ROOT, "tools")):
-    sys.path.insert(0, p)
-from bench_shutter import call_ms  # noqa: E402
+from video_bench import (COPY_CEILING_BYTES_PER_S, call_ms, per_s, share_streams, synthetic_model, timed_legs,          # and the import path
+                         write_y4m)
 
 import torch  # noqa: E402
 
-from models.superslomo_r import FullModel  # noqa: E402
 from ssm_amd import frames as F  # noqa: E402
 from ssm_amd import video as V  # noqa: E402
-from ssm_amd.config import load_config, synthetic_weight_overrides  # noqa: E402
-from ssm_amd.weights import synthetic_frames_u8, synthetic_state_dict  # noqa: E402
+from ssm_amd.weights import synthetic_frames_u8  # noqa: E402
 
-COPY_CEILING_BYTES_PER_S = 6.29e12
 H, W, RATE = 720, 1280, 8
 
 
@@ -59,12 +52,9 @@ def main():
     args = ap.parse_args()
     assert 2 <= args.frames <= 43, "synthetic_frames_u8 holds 43 frames of this size at the most"
     dev = torch.device("cuda:0")
-    cfg = load_config("superslomo_original.ini", synthetic_weight_overrides())
-    model = FullModel(cfg)
-    model.stage1_model.load_state_dict(synthetic_state_dict(1))
-    model.stage2_model.load_state_dict(synthetic_state_dict(2))
-    model = model.to(dev).eval()
+    model, cfg = synthetic_model(dev)
 
+    # the payloads of video_bench.synthetic_payloads, made here because the kernels and the PNG leg below take the RGB frames too
     rgb = synthetic_frames_u8(args.frames, H, W, seed=42).permute(0, 2, 3, 1).contiguous()          # [n,H,W,3] uint8, host
     matrix, crange, siting = V.default_matrix(H), V.LIMITED, V.CENTRED
     payloads = torch.cat([V.frames_to_yuv(F.frames_from_u8(rgb[i:i + 8].to(dev), cfg, True), H, W, siting, matrix, crange, cfg).cpu()
@@ -96,9 +86,7 @@ def main():
     tmp = tempfile.mkdtemp(prefix="bench_video_")
     try:
         src = os.path.join(tmp, "clip.y4m")
-        with V.Y4MWriter(src, W, H, rate=(30, 1), aspect=(1, 1), chroma="420jpeg") as wr:
-            for p in payloads:
-                wr.write_frame(p)
+        write_y4m(src, payloads, W, H, (30, 1))
         if not args.skip_e2e:
             vi = V.VideoInterpolator(model, cfg, upsample_rate=RATE, n_streams=2, pairs_per_batch=1)
 
@@ -125,23 +113,20 @@ def main():
             legs = {"step_2_5_target_75": (V.VideoInterpolator(model, cfg, n_streams=2, pairs_per_batch=1, target_rate=(75, 1)), (75, 1)),
                     "upsample_rate_3": (V.VideoInterpolator(model, cfg, upsample_rate=3, n_streams=2, pairs_per_batch=1), (90, 1))}
             synth = {"step_2_5_target_75": sum(1 for _, t in V.Timeline("2/5").outputs(args.frames) if t), "upsample_rate_3": 2 * (args.frames - 1)}
-            fps = {name: [] for name in legs}
-            for turn in range(args.runs + 2):          # turn 0: plans, pinned buffers' first touch; turn 1: the first run on the shared streams
-                if turn == 1:
-                    # both legs on the same two HIP streams: which hardware queues a pipeline's streams are dealt moves a leg by more
-                    # than 10 %, and the legs never run at the same time
-                    pipes = [vi_leg._pipe[1] for vi_leg, _ in legs.values()]
-                    pipes[1].streams = pipes[0].streams
-                for name, (vi_leg, rate) in legs.items():
-                    with V.Y4MReader(src) as r, V.Y4MWriter.like(os.devnull, r, rate=rate) as w:
-                        t0 = time.perf_counter()
-                        k = vi_leg.run(r, w)
-                        w.f.flush()
-                        dt = time.perf_counter() - t0
-                    if turn > 1:
-                        fps[name].append(synth[name] / dt)
-            res["timeline_fps"] = {name: {"synthesised_frames_per_s": round(statistics.median(v), 2), "min": round(min(v), 2),
-                                          "max": round(max(v), 2), "synthesised_frames": synth[name]} for name, v in fps.items()}
+            def run_leg(name):          # the clock starts with the files open
+                vi_leg, rate = legs[name]
+                with V.Y4MReader(src) as r, V.Y4MWriter.like(os.devnull, r, rate=rate) as w:
+                    t0 = time.perf_counter()
+                    vi_leg.run(r, w)
+                    w.f.flush()
+                    return time.perf_counter() - t0
+
+            secs = timed_legs(legs, run_leg, args.runs, warmup=2, between=share_streams([vi_leg for vi_leg, _ in legs.values()]))
+            res["timeline_fps"] = {}
+            for name, ts in secs.items():
+                v = per_s(synth[name], ts)
+                res["timeline_fps"][name] = {"synthesised_frames_per_s": v["median"], "min": v["min"], "max": v["max"],
+                                             "synthesised_frames": synth[name]}
             res["timeline_fps"]["note"] = ("both legs run two times per pair on every pair of the clip, 2 streams x 1 pair, file to /dev/null, "
                                            "in turns, on the same two HIP streams; frames that pass through as input bytes are written but not counted")
         if not args.skip_png:

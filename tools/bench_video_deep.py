@@ -18,9 +18,7 @@ import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-from bench_shutter import call_ms  # noqa: E402  (here, so that main() still puts --pkg in front of the path)
+from video_bench import PKG, ROOT, call_ms          # it also puts this checkout's package on the path: main() takes that off again
 
 H, W, RATE = 720, 1280, 8
 
@@ -37,6 +35,8 @@ def main():
     ap.add_argument("--pkg", default=os.path.join(ROOT, "superslomo-videointerpolation-pytorch_amd"), help="the package directory to import")
     args = ap.parse_args()
     assert 2 <= args.frames <= 43, "synthetic_frames_u8 holds 43 frames of this size at the most"
+    # --pkg alone is the package on the path: a module the other checkout lacks is an ImportError, never this checkout's copy
+    sys.path[:] = [p for p in sys.path if p not in (PKG, os.path.join(PKG, "scripts"))]
     for p in (ROOT, args.pkg, os.path.join(args.pkg, "scripts")):
         sys.path.insert(0, p)
     import torch
