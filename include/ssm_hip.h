@@ -1269,6 +1269,40 @@ size_t ssm_flow_to_rgb_workspace_bytes(int N, int H, int W);
 int ssm_flow_to_rgb_fwd(ssm_view flow, unsigned char *rgb_hwc, int N, int H, int W, int top, int left,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- forward-backward consistency of a pair's two flows (csrc/ssm_flow.hip) ----------------------------------
+ * flow4: planar fp32 [N,4,*,*] as stage 1 leaves it, F01.u | F01.v | F10.u | F10.v, cropped at (top, left) to
+ * H x W.  Where following one field and then the other does not lead back, the pixel is occluded or a flow is
+ * wrong.  The definition, in fp32, one rounded operation per step, no fused multiply-add; F is one field
+ * (planes u, v), G the other, (x, y) a pixel of the crop:
+ *     u = F.u(y,x); v = F.v(y,x)
+ *     px = (float)x + u;  py = (float)y + v
+ *     leaves  iff  !(px >= 0 && px <= W-1 && py >= 0 && py <= H-1)              a NaN leaves
+ *     x0 = floorf(px); y0 = floorf(py); fx = px - x0; fy = py - y0
+ *     xi0 = (int)x0; xi1 = min(xi0 + 1, W-1); yi0, yi1 likewise                  only taps inside the crop are read
+ *     for each plane g of G:  a = g(yi0,xi0) + fx * (g(yi0,xi1) - g(yi0,xi0))
+ *                             b = g(yi1,xi0) + fx * (g(yi1,xi1) - g(yi1,xi0))
+ *                             g' = a + fy * (b - a)
+ *     rx = u + u'; ry = v + v'
+ *     e2 = rx*rx + ry*ry
+ *     m2 = ((u*u + v*v) + u'*u') + v'*v'
+ *     inconsistent  iff  e2 > alpha * m2 + beta                                  judged pixels only; strict
+ *     residual = sqrtf(e2)                                                       correctly rounded
+ *   Direction 0 is F = F01, G = F10; direction 1 the roles swapped.  alpha = 0.01 and beta = 0.5 are the numbers
+ *   of Sundaram, Brox and Keutzer (2010) as most later work uses them: a convention, not backed by a measurement
+ *   here, and no default of this entry point.
+ *   out is a DEVICE array [N][2][4] of float64, per pair and direction:
+ *     [0] judged: pixels that do not leave    [1] inconsistent    [2] leaves          (exact integers)
+ *     [3] the sum of the judged pixels' residuals, in fp64
+ *   mask (DEVICE, or null): uint8 [N][2][H][W], 0 consistent, 1 inconsistent, 2 leaves.
+ *   Both directions in one launch, a second sums the workgroups' slots: no atomics, bitwise repeatable, pair n's
+ *   result does not depend on N, the stream or the run.  Nothing outside the crop is read.  The workspace is
+ *   device memory of the caller, ssm_flow_consistency_workspace_bytes(N, H, W) bytes at least, 8-byte aligned.
+ *   SSM_E_ARG for null pointers (the view's, workspace, out), N < 1 or > 65535, H or W < 1, a negative crop
+ *   origin, a row stride shorter than left + W, a misaligned workspace or out. */
+size_t ssm_flow_consistency_workspace_bytes(int N, int H, int W);
+int ssm_flow_consistency_fwd(ssm_view flow4, int N, int H, int W, int top, int left, float alpha, float beta,
+                             void *workspace, double *out, unsigned char *mask, void *stream);
+
 /* ---- backward kernels of the training step (fp32 planes; BASELINE config 3) ------------------------------
  * The data gradient of a convolution is ssm_conv2d_fwd on the transposed, spatially flipped filter.
  * ssm_lrelu_bwd           dz = (dy + 1/4 dpool[y/2][x/2]) * (y > 0 ? 1 : slope)   (dy or dpool may be NULL views;

@@ -8,6 +8,12 @@
 //   flow_maxrad_kernel  the chunk's maximum fp32 radius into its slot (a float max does not depend on the order: exact);
 //   flow_rgb_kernel     every workgroup takes the maximum over its field's slots, then normalises, looks the angle up in the colour
 //                       wheel, interpolates and writes uint8 RGB - in fp64, as the reference's map runs on numpy >= 2.
+// And the forward-backward consistency of the two fields stage 1 leaves side by side (F01 | F10, four planes), which has no reference
+// code: its definition stands in include/ssm_hip.h and its yardstick is ssm_amd.flow_eval.flow_consistency_host.
+//   flow_consistency_kernel  FL_PIX consecutive pixels of one pair per workgroup, both directions: per pixel the state (consistent,
+//                            inconsistent, leaves) in fp32, a fixed-order workgroup sum of the three counts (integers) and the residuals
+//                            (fp64) per direction into the chunk's slot; optionally the state into a uint8 mask;
+//   flow_consistency_finish  one workgroup per pair: the pair's slots summed in a fixed order into out[n][2][4].
 // Every partial result has one writer and is combined in a fixed order, so the bits depend only on the field's values and size, not
 // on N, the stream or the run.
 // NO CONTRACTION.  hipcc fuses a*b + c into one fma by default; numpy rounds every operation.  The two decisions of this file - error
@@ -221,6 +227,131 @@ __global__ __launch_bounds__(FL_THREADS) void flow_rgb_kernel(ssm_view flow, int
     }
 }
 
+// ---- forward-backward consistency ------------------------------------------------------------------------------------------------------
+// The definition of include/ssm_hip.h (ssm_flow_consistency_fwd), one rounded fp32 operation per step: pixel (x, y) of the crop follows
+// F to (px, py); where that point stays on the crop, G is sampled there bilinearly - taps inside the crop only, the canvas around it
+// holds whatever the U-Net left - and F + G' should vanish.  Returns 0 consistent, 1 inconsistent, 2 leaves; `residual` only for 0 / 1.
+// fu, fv, gu, gv: the planes of the two fields at the crop's origin.
+constexpr int FC_WORDS = 8;                        // a workspace slot: [direction][judged, inconsistent, leaves] as integers, then [direction] fp64 residual sums
+
+__device__ __forceinline__ unsigned fc_pixel(float u, float v, const float *__restrict__ gu, const float *__restrict__ gv, int sh, int x,
+                                             int y, int H, int W, float alpha, float beta, float &residual) {
+    const float px = (float)x + u, py = (float)y + v;
+    if (!(px >= 0.0f && px <= (float)(W - 1) && py >= 0.0f && py <= (float)(H - 1))) return 2u;          // a NaN leaves
+    const float x0 = floorf(px), y0 = floorf(py);
+    const float fx = px - x0, fy = py - y0;
+    const int xi0 = (int)x0, yi0 = (int)y0;          // in [0, W - 1] x [0, H - 1] by the test above
+    const int xi1 = xi0 + 1 < W ? xi0 + 1 : W - 1, yi1 = yi0 + 1 < H ? yi0 + 1 : H - 1;
+    const size_t r0 = (size_t)yi0 * sh, r1 = (size_t)yi1 * sh;
+    float s[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const float *g = c == 0 ? gu : gv;
+        const float g00 = g[r0 + xi0], g01 = g[r0 + xi1], g10 = g[r1 + xi0], g11 = g[r1 + xi1];
+        const float a = g00 + fx * (g01 - g00);
+        const float b = g10 + fx * (g11 - g10);
+        s[c] = a + fy * (b - a);
+    }
+    const float rx = u + s[0], ry = v + s[1];
+    const float e2 = rx * rx + ry * ry;
+    const float m2 = ((u * u + v * v) + s[0] * s[0]) + s[1] * s[1];
+    residual = __builtin_sqrtf(e2);
+    return e2 > alpha * m2 + beta ? 1u : 0u;
+}
+
+// FL_PIX consecutive pixels of one pair per workgroup, lane = pixel along x: the four plane reads of a wave are contiguous row segments,
+// the gathers of the other field land a few pixels from them.  Both directions of a pixel in one thread; a fixed-order workgroup sum
+// into the chunk's slot.
+__global__ __launch_bounds__(FL_THREADS) void flow_consistency_kernel(ssm_view flow4, int HW, int H, int W, int top, int left, float alpha,
+                                                                      float beta, unsigned long long *__restrict__ ws,
+                                                                      unsigned char *__restrict__ mask) {
+    __shared__ double red_e[2][FL_THREADS];
+    __shared__ unsigned red_c[6][FL_THREADS];
+    const int tid = threadIdx.x, n = blockIdx.y;
+    const float *base = flow4.ptr + (size_t)n * flow4.sb + (size_t)top * flow4.sh + (size_t)left;
+    const float *pl[4] = {base, base + flow4.sc, base + 2 * flow4.sc, base + 3 * flow4.sc};          // u01, v01, u10, v10
+    double e[2] = {0.0, 0.0};
+    unsigned cnt[2][3] = {{0, 0, 0}, {0, 0, 0}};
+#pragma unroll 2
+    for (int i = 0; i < FL_PER; ++i) {
+        const long long p_ = (long long)blockIdx.x * FL_PIX + i * FL_THREADS + tid;
+        if (p_ >= HW) continue;
+        const int p = (int)p_, y = p / W, x = p - y * W;
+        const size_t off = (size_t)y * flow4.sh + (size_t)x;
+        const float f[4] = {pl[0][off], pl[1][off], pl[2][off], pl[3][off]};
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+            float res = 0.0f;
+            const unsigned state = fc_pixel(f[2 * d], f[2 * d + 1], pl[2 - 2 * d], pl[3 - 2 * d], flow4.sh, x, y, H, W, alpha, beta, res);
+            if (state != 2u) {
+                e[d] += (double)res;
+                cnt[d][0] += 1u;
+                cnt[d][1] += state;
+            } else {
+                cnt[d][2] += 1u;
+            }
+            if (mask) mask[((size_t)n * 2 + d) * HW + p] = (unsigned char)state;
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < 2; ++d) {
+        red_e[d][tid] = e[d];
+#pragma unroll
+        for (int m = 0; m < 3; ++m) red_c[3 * d + m][tid] = cnt[d][m];
+    }
+    __syncthreads();
+    for (int s = FL_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            red_e[0][tid] += red_e[0][tid + s];
+            red_e[1][tid] += red_e[1][tid + s];
+#pragma unroll
+            for (int m = 0; m < 6; ++m) red_c[m][tid] += red_c[m][tid + s];
+        }
+        __syncthreads();
+    }
+    unsigned long long *slot = ws + ((size_t)n * gridDim.x + blockIdx.x) * FC_WORDS;
+    if (tid < 6) slot[tid] = red_c[tid][0];
+    if (tid == 6 || tid == 7) reinterpret_cast<double *>(slot)[tid] = red_e[tid - 6][0];
+}
+
+// one workgroup per pair: its slots summed in a fixed order - the counts as integers, the residuals in fp64 - into out[n][2][4]
+__global__ __launch_bounds__(FL_THREADS) void flow_consistency_finish(const unsigned long long *__restrict__ ws, int chunks,
+                                                                      double *__restrict__ out) {
+    __shared__ unsigned long long red_c[6][FL_THREADS];
+    __shared__ double red_e[2][FL_THREADS];
+    const int tid = threadIdx.x, n = blockIdx.x;
+    unsigned long long c[6] = {0, 0, 0, 0, 0, 0};
+    double e[2] = {0.0, 0.0};
+    for (int t = tid; t < chunks; t += FL_THREADS) {
+        const unsigned long long *slot = ws + ((size_t)n * chunks + t) * FC_WORDS;
+#pragma unroll
+        for (int m = 0; m < 6; ++m) c[m] += slot[m];
+        e[0] += reinterpret_cast<const double *>(slot)[6];
+        e[1] += reinterpret_cast<const double *>(slot)[7];
+    }
+#pragma unroll
+    for (int m = 0; m < 6; ++m) red_c[m][tid] = c[m];
+    red_e[0][tid] = e[0];
+    red_e[1][tid] = e[1];
+    __syncthreads();
+    for (int s = FL_THREADS / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+#pragma unroll
+            for (int m = 0; m < 6; ++m) red_c[m][tid] += red_c[m][tid + s];
+            red_e[0][tid] += red_e[0][tid + s];
+            red_e[1][tid] += red_e[1][tid + s];
+        }
+        __syncthreads();
+    }
+    if (tid < 2) {
+        double *o = out + ((size_t)n * 2 + tid) * 4;
+        o[0] = (double)red_c[3 * tid][0];
+        o[1] = (double)red_c[3 * tid + 1][0];
+        o[2] = (double)red_c[3 * tid + 2][0];
+        o[3] = red_e[tid][0];
+    }
+}
+
 int check_field(const char *who, ssm_view flow, int N, int H, int W, int top, int left) {
     SSM_REQUIRE(flow.ptr, "%s: null pointer (flow)", who);
     SSM_REQUIRE(N >= 1 && N <= 65535, "%s: N = %d outside [1, 65535]", who, N);
@@ -269,4 +400,23 @@ extern "C" int ssm_flow_to_rgb_fwd(ssm_view flow, unsigned char *rgb_hwc, int N,
     SSM_LAUNCH(flow_maxrad_kernel, dim3(chunks, N), dim3(FL_THREADS), 0, st, flow, H * W, W, top, left, (float *)workspace);
     SSM_LAUNCH(flow_rgb_kernel, dim3(chunks, N), dim3(FL_THREADS), 0, st, flow, H * W, W, top, left, (const float *)workspace, rgb_hwc);
     return ssm::check_launch("ssm_flow_to_rgb_fwd");
+}
+
+extern "C" size_t ssm_flow_consistency_workspace_bytes(int N, int H, int W) {
+    if (N < 1 || H < 1 || W < 1) return 0;
+    return (size_t)N * chunks_of(H, W) * FC_WORDS * sizeof(unsigned long long);
+}
+
+extern "C" int ssm_flow_consistency_fwd(ssm_view flow4, int N, int H, int W, int top, int left, float alpha, float beta, void *workspace,
+                                        double *out, unsigned char *mask, void *stream) {
+    SSM_REQUIRE(workspace && out, "flow_consistency: null pointer");
+    if (int rc = check_field("flow_consistency", flow4, N, H, W, top, left)) return rc;
+    SSM_REQUIRE((reinterpret_cast<size_t>(workspace) & 7) == 0 && (reinterpret_cast<size_t>(out) & 7) == 0,
+                "flow_consistency: workspace and out must be 8-byte aligned");
+    const hipStream_t st = (hipStream_t)stream;
+    const int chunks = chunks_of(H, W);
+    SSM_LAUNCH(flow_consistency_kernel, dim3(chunks, N), dim3(FL_THREADS), 0, st, flow4, H * W, H, W, top, left, alpha, beta,
+               (unsigned long long *)workspace, mask);
+    SSM_LAUNCH(flow_consistency_finish, dim3(N), dim3(FL_THREADS), 0, st, (const unsigned long long *)workspace, chunks, out);
+    return ssm::check_launch("ssm_flow_consistency_fwd");
 }

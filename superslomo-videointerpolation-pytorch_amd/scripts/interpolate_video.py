@@ -121,6 +121,18 @@ blocks are not smoothed.  --log gets one line with the pairs, the blocks kept of
 every pair without a static block when others had some.  It goes with --upsample_rate, --slowmo, --fps, --speed, --scene_cut (a cut
 pair's frames are replaced whole, as without it), --matrix, --range, --flow_scale, --tile and --detelecine (which runs first), and with
 every format; not with --shutter (every output comes from the accumulator), --deinterlace, --dedup or --active: chain two runs.
+
+--flow_check [T[:ALPHA:BETA]]: the network's own opinion of its flows.  Stage 1 estimates the motion 0 -> 1 and the motion 1 -> 0
+independently; where following one and then the other does not lead back, the pixel is occluded or a flow is wrong - where interpolated
+footage tears and ghosts.  Every pass scores that on the GPU (ssm_flow_consistency_fwd on the two fields where stage 1 left them; the
+definition stands in include/ssm_hip.h): a pixel is inconsistent when |F + G'|^2 > ALPHA (|F|^2 + |G'|^2) + BETA, a pair's score is the
+larger share of inconsistent pixels of its two directions.  --log gets one line with the pairs scored, the least, median and largest
+score and the largest mean residual.  With T a pair whose score reaches T gets the nearer input frame's bytes instead of its synthesised
+frames, the rule of --scene_cut, and a line in --log.  ALPHA:BETA default to 0.01:0.5, the numbers of Sundaram, Brox and Keutzer (2010)
+as most later work uses them: a convention, not backed by a measurement here; there is no default T, and with the synthetic weights of
+this repository a score says nothing about quality.  It goes with --upsample_rate, --slowmo, --fps, --speed, --scene_cut, --static,
+--active, --matrix, --range and --detelecine; not with --shutter, --deinterlace, --dedup, --flow_scale other than 1, --tile or a
+recurrent model.
 """
 import argparse
 import configparser
@@ -134,6 +146,7 @@ for _p in (os.path.dirname(HERE), HERE):
         sys.path.insert(0, _p)
 
 from models import superslomo_r as ssm  # noqa: E402
+from ssm_amd import flow_eval as FE  # noqa: E402
 from ssm_amd import tiles as T  # noqa: E402
 from ssm_amd import video as V  # noqa: E402
 
@@ -217,7 +230,19 @@ def getargs(argv=None):
                         help="Blocks that do not change keep their bytes: where the two frames of a pair differ by at most LO in the sum of "
                              "absolute differences over an 8x8 block (luma and the chroma under it), the frames between them carry the left "
                              "frame's samples. 0: only blocks that are the same in both, exact. No default value: off unless given.")
+    parser.add_argument("--flow_check", type=_named(FE.parse_flow_check), nargs="?", const=(None, None, None), default=None,
+                        metavar="T[:ALPHA:BETA]",
+                        help="Score every pair's two flows against each other on the GPU (forward-backward consistency) and log the scores. "
+                             "With T, a decimal or a fraction: a pair whose share of inconsistent pixels reaches T gets copies of its input "
+                             "frames, like a scene cut. ALPHA:BETA default to 0.01:0.5, a convention of the literature; no default T.")
     args = parser.parse_args(argv)
+    if args.flow_check is not None:
+        for flag, given in (("--shutter", args.shutter is not None), ("--deinterlace", args.deinterlace is not None),
+                            ("--dedup", args.dedup is not None), ("--flow_scale %d" % args.flow_scale, args.flow_scale != 1),
+                            ("--tile", args.tile is not None)):
+            if given:
+                parser.error("--flow_check does not go together with %s: it scores the two full-size stage-1 flows of a pair whose frames "
+                             "are synthesised between two input frames, and nothing else" % flag)
     if args.static is not None:
         for flag, given in (("--shutter", args.shutter is not None), ("--deinterlace", args.deinterlace is not None),
                             ("--dedup", args.dedup is not None), ("--active", args.active is not None)):
@@ -289,6 +314,23 @@ def static_lines(static, lo):
     return lines
 
 
+def flow_check_lines(checks, failed, option):
+    """What --log gets of a run with --flow_check: `checks` = [(i, FlowCheck)] of the pairs that ran, `failed` those that reached the
+    threshold, option = (T or None, alpha, beta).  One summary line - the pairs scored, the least, median and largest score, the largest
+    mean residual - and one line per failed pair."""
+    t, alpha, beta = option
+    head = "flow check: alpha = %g, beta = %g%s" % (alpha, beta, "" if t is None else ", threshold %s" % t)
+    if not checks:
+        return [head + ", no pair ran"]
+    scores = sorted(c.score for _, c in checks)
+    lines = [head + ", %d pairs scored: score at least %.6f, median %.6f, at most %.6f; largest mean residual %.4f px%s"
+             % (len(checks), float(scores[0]), float(scores[(len(scores) - 1) // 2]), float(scores[-1]),
+                max(c.mean_residual for _, c in checks), "" if t is None else "; %d pairs fell back to input frames" % len(failed))]
+    lines += ["flow check failed between input frames %d and %d: score %s = %.6f (threshold %s), mean residual %.4f px"
+              % (i, i + 1, c.score, float(c.score), t, c.mean_residual) for i, c in failed]
+    return lines
+
+
 def main(argv=None, model=None):
     args = getargs(argv)
     config = configparser.RawConfigParser()
@@ -303,7 +345,9 @@ def main(argv=None, model=None):
                              flow_scale=args.flow_scale, tile=args.tile, halo=args.halo, blend=args.blend, target_rate=args.fps, speed=args.speed,
                              shutter=args.shutter, shutter_samples=args.shutter_samples, scene_cut=args.scene_cut,
                              shutter_light=args.shutter_light, shutter_window=args.shutter_window, deinterlace=args.deinterlace, dedup=args.dedup, dedup_max=args.dedup_max,
-                             active=args.active, active_probe=args.active_probe, field_probe=args.field_probe, static=args.static)
+                             active=args.active, active_probe=args.active_probe, field_probe=args.field_probe, static=args.static,
+                             flow_check=None if args.flow_check is None else (True if args.flow_check[0] is None else args.flow_check[0]),
+                             flow_alpha=args.flow_check and args.flow_check[1], flow_beta=args.flow_check and args.flow_check[2])
     with V.Y4MReader(args.input, extended=True, interlaced=args.deinterlace is not None or args.detelecine) as reader:
         if args.detelecine:
             log.info("[%s] detelecine: %d:%d frames/s in, film at %d:%d", args.expt, *reader.rate, *V.detelecine_rate(reader.rate))
@@ -363,6 +407,9 @@ def main(argv=None, model=None):
                      rows, cols)
     if args.static is not None:
         for line in static_lines(vi.static, args.static):
+            log.info("[%s] %s", args.expt, line)
+    if args.flow_check is not None:
+        for line in flow_check_lines(vi.flow_checks, vi.flow_failed, vi.flow_check):
             log.info("[%s] %s", args.expt, line)
     for i, score in vi.cuts:
         log.info("[%s] scene cut between input frames %d and %d: score %s = %.6f (threshold %s)", args.expt, i, i + 1, score, float(score),

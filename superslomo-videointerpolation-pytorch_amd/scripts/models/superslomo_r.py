@@ -321,6 +321,27 @@ class FullModel(nn.Module):
         return out if want_planes else out.to_nchw()
 
     @torch.no_grad()
+    def flow_consistency(self, image_pair, size=None, alpha=None, beta=None, want_mask=False):
+        """Forward-backward consistency of the pairs' stage-1 flows (ssm_amd.flow_eval.flow_consistency on estimate_flow's planes, where
+        stage 1 left them; stage 2 never runs): pairs [B,2,3,Hp,Wp] (or [B,6,Hp,Wp]) -> [FlowCheck] per pair; with want_mask also the
+        uint8 mask [B,2,h,w] on the device (0 consistent, 1 inconsistent, 2 leaves).  size = (h, w): the picture inside a padded canvas,
+        cropped as FlowEvaluator crops (the centred padding of frames.padded_dims); None: the whole canvas.  alpha, beta: None is
+        flow_eval.FLOW_ALPHA, FLOW_BETA = 0.01, 0.5 - a convention of the literature, not backed by a measurement here.  Synchronises."""
+        from ssm_amd import flow_eval as FE
+        from ssm_amd.frames import padded_dims
+        hp, wp = image_pair.shape[-2:]
+        h, w = (hp, wp) if size is None else size
+        top, left = (0, 0) if size is None else padded_dims(h, w)[1]
+        assert size is None or padded_dims(h, w)[0] == (hp, wp), "a %dx%d picture pads to %s, the pairs are %dx%d" % (
+            h, w, padded_dims(h, w)[0], hp, wp)
+        planes = self.estimate_flow(image_pair, want_planes=True)
+        got = FE.flow_consistency(planes, h, w, top, left, FE.FLOW_ALPHA if alpha is None else alpha, FE.FLOW_BETA if beta is None else beta,
+                                  want_mask=want_mask)
+        record = (got[0] if want_mask else got).cpu().numpy()
+        checks = [FE.FlowCheck.of(r) for r in record]
+        return (checks, got[1]) if want_mask else checks
+
+    @torch.no_grad()
     def interpolate_many(self, pairs, t_values, n_streams=2, pairs_per_batch=1, flow_scale=1, tile=None, halo=256, blend=32):
         """Throughput form of interpolate(): a list of pairs ([1,2,3,H,W] each, same size) -> list of
         [len(t_values),3,H,W] tensors.  Passes of `pairs_per_batch` pairs are dealt round-robin to `n_streams` engines on

@@ -50,6 +50,9 @@ def getargs(argv=None):
     parser.add_argument("--output_dir", required=True, help="Directory to output.")
     parser.add_argument("--flow_png", action="store_true",
                         help="With --show_intermediate_outputs: also save the flows as Middlebury colour-wheel PNGs.")
+    parser.add_argument("--consistency_png", action="store_true",
+                        help="With --show_intermediate_outputs: also save the forward-backward consistency masks of each pair's two "
+                             "stage-1 flows as grey PNGs (0 consistent, 255 inconsistent, 128 leaves the picture), beside the flow maps.")
     parser.add_argument("--flow_scale", type=int, choices=(1, 2, 4), default=1,
                         help="Coarse-flow mode: run both U-Nets at 1/flow_scale of the frame size and synthesise at full size (an approximation "
                              "of the default output, not parity). Not with --show_intermediate_outputs. Default 1: off.")
@@ -97,6 +100,12 @@ class Interpolator:
         if self.flow_png:
             for d in self.flow_png_dirs.values():
                 os.makedirs(d, exist_ok=True)
+        # the forward-backward consistency masks of a pair's two stage-1 flows (ssm_amd.flow_eval.flow_consistency), opt-in
+        self.consistency_png = bool(getattr(args, "consistency_png", False)) and args.show_intermediate_outputs
+        self.consistency_dirs = {d: os.path.join(base, name) for d, name in enumerate(("flow_consistency_01", "flow_consistency_10"))}
+        if self.consistency_png:
+            for d in self.consistency_dirs.values():
+                os.makedirs(d, exist_ok=True)
 
     @staticmethod
     def load_frames(paths):
@@ -111,6 +120,15 @@ class Interpolator:
         """save_img_from_tensor(..., flo_img=True) (visualize_interpolation.py:223-232): the cropped [1,2,*,*] flow as a colour map."""
         from ssm_amd.flow_eval import flow_to_rgb
         self.save(flow_to_rgb(flow, h, w, top, left)[0].cpu().numpy(), count, self.flow_png_dirs[name], prefix)
+
+    def save_consistency_png(self, flow01, flow10, h, w, top, left, count):
+        """The two masks of a pair - 0 consistent, 1 inconsistent, 2 leaves - as grey 0 / 255 / 128, at the defaults FLOW_ALPHA, FLOW_BETA
+        (a convention of the literature, not backed by a measurement here)."""
+        from ssm_amd.flow_eval import flow_consistency
+        _, mask = flow_consistency(torch.cat([flow01, flow10], 1).contiguous(), h, w, top, left, want_mask=True)
+        grey = torch.tensor([0, 255, 128], dtype=torch.uint8, device=mask.device)[mask[0].long()].cpu().numpy()
+        for d, prefix in enumerate(("Consistency_01", "Consistency_10")):
+            self.save(grey[d], count, self.consistency_dirs[d], prefix)
 
     @torch.no_grad()
     def interpolate_frames(self):
@@ -162,6 +180,10 @@ class Interpolator:
                     top, left = (inter[0].shape[2] - h) // 2, (inter[0].shape[3] - w) // 2
                     self.save_flow_png(inter[0], h, w, top, left, count, "estimated_flow_01", "Flow_01")
                     self.save_flow_png(inter[1], h, w, top, left, count, "estimated_flow_10", "Flow_10")
+                if self.consistency_png and outs[k]:          # beside the pair's stage-1 flow maps, under the same number
+                    inter = outs[k][-1][1]
+                    top, left = (inter[0].shape[2] - h) // 2, (inter[0].shape[3] - w) // 2
+                    self.save_consistency_png(inter[0], inter[1], h, w, top, left, count)
             else:
                 u8 = F.frames_to_u8(outs[k], h, w, self.cfg).cpu().numpy()
                 for j in range(u8.shape[0]):

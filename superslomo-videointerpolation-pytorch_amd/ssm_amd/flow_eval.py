@@ -3,8 +3,13 @@ scripts/utils/dataloaders/sintel_opticalflow.py do around `FullModel`, restated 
 
   * `FullModel.estimate_flow` runs stage 1 alone (the reference runs the full model and keeps `intermediate_outputs[0]`);
   * `flow_metrics` / `flow_to_rgb` score and colour-code a flow field on the GPU where stage 1 left it (csrc/ssm_flow.hip);
-  * `compute_metrics_host` and scripts/utils/flo_utils.py stay the yardsticks, and `FlowEvaluator(metrics="host")` the default.
+  * `compute_metrics_host` and scripts/utils/flo_utils.py stay the yardsticks, and `FlowEvaluator(metrics="host")` the default;
+  * `flow_consistency` scores a pair's two flows against each other on the GPU (forward-backward consistency: no ground truth needed),
+    `flow_consistency_host` is its numpy yardstick, `FlowCheck` one pair's record, `parse_flow_check` the streamed option's parser.
 """
+from collections import namedtuple
+from fractions import Fraction
+
 import numpy as np
 import torch
 
@@ -96,6 +101,144 @@ def flow_to_rgb(flow, h, w, top=0, left=0):
         rgb = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
         hb.check(lib.ssm_flow_to_rgb_fwd(view, rgb.data_ptr(), n, h, w, top, left, ws.data_ptr(), nbytes, hb.stream_ptr()))
     return rgb
+
+
+# ---- forward-backward consistency of a pair's two flows (include/ssm_hip.h: ssm_flow_consistency_fwd) -------------------------------------
+# alpha and beta: the numbers of Sundaram, Brox and Keutzer (2010) as most later work uses them.  A convention, NOT backed by a measurement
+# here - and with this repository's synthetic weights the scores say nothing about quality.
+FLOW_ALPHA, FLOW_BETA = 0.01, 0.5
+CONSISTENT, INCONSISTENT, LEAVES = 0, 1, 2          # the mask's codes
+
+
+class FlowCheck(namedtuple("FlowCheck", "judged inconsistent leaves residual_sum")):
+    """One pair's record of ssm_flow_consistency_fwd / flow_consistency_host: per direction (0: F01 followed, F10 sampled; 1: the roles
+    swapped) the pixels judged (they do not leave the crop), those of them that are inconsistent, the pixels that leave, and the fp64 sum
+    of the judged pixels' residuals.  The counts are integers and every share a Fraction: the verdict of a threshold depends on no rounding."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, record):
+        """record: [2][4] float64 of one pair, as the entry point writes it."""
+        r = np.asarray(record, dtype=np.float64).reshape(2, 4)
+        return cls(*(tuple(int(r[d, m]) for d in (0, 1)) for m in range(3)), tuple(float(r[d, 3]) for d in (0, 1)))
+
+    def share(self, d):
+        """Inconsistent among the judged pixels of direction d; 1 when nothing was judged - a field that leaves everywhere vouches for nothing."""
+        return Fraction(self.inconsistent[d], self.judged[d]) if self.judged[d] else Fraction(1)
+
+    @property
+    def score(self):
+        return max(self.share(0), self.share(1))
+
+    @property
+    def mean_residual(self):
+        """The mean residual, in pixels, over the judged pixels of both directions; 0.0 when nothing was judged."""
+        n = self.judged[0] + self.judged[1]
+        return (self.residual_sum[0] + self.residual_sum[1]) / n if n else 0.0
+
+
+def flow_consistency_host(flow4, top, left, H, W, alpha=FLOW_ALPHA, beta=FLOW_BETA):
+    """The numpy float32 yardstick of ssm_flow_consistency_fwd, op for op the definition of include/ssm_hip.h: flow4 [N,4,*,*] float32
+    (F01.u | F01.v | F10.u | F10.v) cropped at (top, left) to H x W -> (record float64 [N,2,4] = judged, inconsistent, leaves, fp64 sum
+    of the judged residuals per direction; mask uint8 [N,2,H,W] = 0 consistent, 1 inconsistent, 2 leaves).  Nothing outside the crop is read."""
+    f32 = np.float32
+    flow4 = np.asarray(flow4, dtype=f32)
+    assert flow4.ndim == 4 and flow4.shape[1] == 4, "flow4 must be [N,4,*,*]; got %s" % (flow4.shape,)
+    assert H >= 1 and W >= 1 and top >= 0 and left >= 0 and top + H <= flow4.shape[2] and left + W <= flow4.shape[3], \
+        "crop %dx%d at (%d, %d) does not fit the %dx%d flow" % (H, W, top, left, flow4.shape[2], flow4.shape[3])
+    crop = flow4[:, :, top:top + H, left:left + W]
+    n = crop.shape[0]
+    alpha, beta = f32(alpha), f32(beta)
+    xs, ys = np.arange(W, dtype=f32)[None, None, :], np.arange(H, dtype=f32)[None, :, None]
+    rows = np.arange(n)[:, None, None]
+    record, mask = np.zeros((n, 2, 4), np.float64), np.zeros((n, 2, H, W), np.uint8)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for d in (0, 1):
+            u, v = crop[:, 2 * d], crop[:, 2 * d + 1]
+            g = crop[:, 2 - 2 * d:4 - 2 * d]
+            px, py = xs + u, ys + v
+            leaves = ~((px >= 0) & (px <= f32(W - 1)) & (py >= 0) & (py <= f32(H - 1)))
+            px, py = np.where(leaves, f32(0), px), np.where(leaves, f32(0), py)          # a pixel that leaves takes no tap
+            x0, y0 = np.floor(px), np.floor(py)
+            fx, fy = px - x0, py - y0
+            xi0, yi0 = x0.astype(np.int64), y0.astype(np.int64)
+            xi1, yi1 = np.minimum(xi0 + 1, W - 1), np.minimum(yi0 + 1, H - 1)
+            s = []
+            for c in (0, 1):
+                gc = g[:, c]
+                g00, g01, g10, g11 = gc[rows, yi0, xi0], gc[rows, yi0, xi1], gc[rows, yi1, xi0], gc[rows, yi1, xi1]
+                a = g00 + fx * (g01 - g00)
+                b = g10 + fx * (g11 - g10)
+                s.append(a + fy * (b - a))
+            rx, ry = u + s[0], v + s[1]
+            e2 = rx * rx + ry * ry
+            m2 = ((u * u + v * v) + s[0] * s[0]) + s[1] * s[1]
+            bad = ~leaves & (e2 > alpha * m2 + beta)
+            residual = np.sqrt(e2)
+            assert residual.dtype == f32
+            mask[:, d] = np.where(leaves, LEAVES, np.where(bad, INCONSISTENT, CONSISTENT))
+            record[:, d, 0] = (~leaves).reshape(n, -1).sum(axis=1)
+            record[:, d, 1] = bad.reshape(n, -1).sum(axis=1)
+            record[:, d, 2] = leaves.reshape(n, -1).sum(axis=1)
+            record[:, d, 3] = np.where(leaves, 0.0, residual.astype(np.float64)).reshape(n, -1).sum(axis=1)
+    return record, mask
+
+
+def flow_consistency(flow, h, w, top=0, left=0, alpha=FLOW_ALPHA, beta=FLOW_BETA, want_mask=False, out=None, workspace=None):
+    """ssm_flow_consistency_fwd on the h x w crop at (top, left) of a [N,4,*,*] flow - a float32 device tensor with unit x-stride, or the
+    4-channel hipbind.Planes stage 1 leaves (FullModel.estimate_flow(..., want_planes=True), PairEngine.s1.t["out"]) -> float64 [N,2,4]
+    on the device (into `out` if given), FlowCheck.of(row) on the host; with want_mask (record, uint8 [N,2,h,w] mask).  workspace: a
+    uint8 device tensor of ssm_flow_consistency_workspace_bytes(N, h, w) bytes at least, the caller's (a loop that allocates nothing);
+    None: made here.  Launched on the current stream; no synchronisation."""
+    if isinstance(flow, hb.Planes):
+        view, shape, dev, keep = flow.view(), (flow.B, flow.C, flow.H, flow.W), flow.buf.device, flow
+    else:
+        if not (isinstance(flow, torch.Tensor) and flow.is_cuda and flow.dtype == torch.float32 and flow.dim() == 4):
+            raise RuntimeError("flow must be a [N,4,H,W] float32 tensor on the GPU (or hipbind.Planes); got %s %s on %s"
+                               % (getattr(flow, "dtype", type(flow)), tuple(getattr(flow, "shape", ())), getattr(flow, "device", "?")))
+        keep = flow if flow.stride(3) == 1 else flow.contiguous()
+        view, shape, dev = hb.view_of(keep), tuple(keep.shape), keep.device
+    if shape[1] != 4:
+        raise RuntimeError("flow must hold the four planes F01 | F10; got %d channels" % shape[1])
+    if not (h >= 1 and w >= 1 and top >= 0 and left >= 0 and top + h <= shape[2] and left + w <= shape[3]):
+        raise RuntimeError("crop %dx%d at (%d, %d) does not fit the %dx%d flow" % (h, w, top, left, shape[2], shape[3]))
+    n = shape[0]
+    lib = hb.load()
+    with torch.cuda.device(dev):
+        nbytes = lib.ssm_flow_consistency_workspace_bytes(n, h, w)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if workspace is None else workspace
+        assert ws.is_cuda and ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= nbytes, "workspace of %d bytes needed" % nbytes
+        if out is None:
+            out = torch.empty(n, 2, 4, dtype=torch.float64, device=dev)
+        assert out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (n, 2, 4) and out.is_contiguous()
+        mask = torch.empty(n, 2, h, w, dtype=torch.uint8, device=dev) if want_mask else None
+        hb.check(lib.ssm_flow_consistency_fwd(view, n, h, w, top, left, float(alpha), float(beta), ws.data_ptr(), out.data_ptr(),
+                                              None if mask is None else mask.data_ptr(), hb.stream_ptr()))
+    return (out, mask) if want_mask else out
+
+
+def parse_flow_check(value, alpha=None, beta=None):
+    """The option flow_check -> (T or None, alpha or None, beta or None), exact Fractions: True is the report alone; a threshold is "T"
+    or "T:ALPHA:BETA" (or a number, a Fraction, or such a triple), each written as a decimal or a fraction, T >= 0 (a pair falls back
+    iff its score >= T; scores lie in [0, 1], so T = 0 condemns every pair and any T > 1 none), ALPHA and BETA >= 0.  alpha, beta: the
+    same numbers given on their own, which go before the triple's.  There is no default T, and None for alpha or beta means the
+    convention FLOW_ALPHA, FLOW_BETA.  Anything else is a ValueError naming the value."""
+    parts = [] if value is True else (value.strip().split(":") if isinstance(value, str) else (
+        list(value) if isinstance(value, (tuple, list)) else [value]))
+    if len(parts) not in (0, 1, 3) or any(p is None or isinstance(p, bool) for p in parts):
+        raise ValueError("a flow check is written T or T:ALPHA:BETA, e.g. 0.2 or 1/5:0.01:0.5 (got %r)" % (value,))
+    parts = (parts + [None] * 3)[:3]
+    parts = [parts[0], parts[1] if alpha is None else alpha, parts[2] if beta is None else beta]
+    nums = []
+    for name, p in zip(("threshold", "alpha", "beta"), parts):
+        try:
+            x = None if p is None else Fraction(p.strip() if isinstance(p, str) else p)
+        except (ValueError, TypeError, ZeroDivisionError, OverflowError):
+            raise ValueError("a flow check's %s is written as a decimal or a fraction, e.g. 0.2 or 1/5 (got %r)" % (name, p)) from None
+        if isinstance(p, bool) or (x is not None and x < 0):
+            raise ValueError("a flow check's %s is a number that is not negative (got %r)" % (name, p))
+        nums.append(x)
+    return tuple(nums)
 
 
 def compute_metrics_host(flow_hw2, gt_hw2):

@@ -161,6 +161,8 @@ SIGNATURES = {
     "ssm_flow_metrics_fwd": (_c_int, [SsmView, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _sz, _vp, _vp]),
     "ssm_flow_to_rgb_workspace_bytes": (_sz, [_c_int, _c_int, _c_int]),
     "ssm_flow_to_rgb_fwd": (_c_int, [SsmView, _vp, _c_int, _c_int, _c_int, _c_int, _c_int, _vp, _sz, _vp]),
+    "ssm_flow_consistency_workspace_bytes": (_sz, [_c_int, _c_int, _c_int]),
+    "ssm_flow_consistency_fwd": (_c_int, [SsmView, _c_int, _c_int, _c_int, _c_int, _c_int, _c_float, _c_float, _vp, _vp, _vp, _vp]),
     "ssm_warp_bilinear_bwd": (_c_int, [SsmView, SsmView, SsmView, SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _vp]),
     "ssm_lrelu_bwd": (_c_int, [SsmView, SsmView, SsmView, SsmView, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _vp]),
     "ssm_lrelu_bwd_q8": (_c_int, [SsmView, SsmView, SsmView, SsmView, SsmHView, _c_int, _c_int, _c_int, _c_int, _c_float, _c_int, _vp]),

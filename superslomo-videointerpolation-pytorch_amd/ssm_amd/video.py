@@ -2647,9 +2647,13 @@ def stream_buffers(n, dev, fb, rows_in, rows_out, n_t=None, fb_out=None):
 
 
 class PairOptions:
-    """The per-pair options of one run of the fixed grid or of the timeline - scene cuts, static blocks, the window of a letterboxed clip -
-    in one place: what they add to the run's buffers, what they queue on a pass's stream, and what they decide on the writer thread.  With
-    an option off nothing of it is allocated or queued, and with all three off a pass is, launch for launch, the loop without them.
+    """The per-pair options of one run of the fixed grid or of the timeline - scene cuts, static blocks, the window of a letterboxed clip,
+    the flow check - in one place: what they add to the run's buffers, what they queue on a pass's stream, and what they decide on the
+    writer thread.  With an option off nothing of it is allocated or queued, and with all of them off a pass is, launch for launch, the
+    loop without them.
+    flow_check = (T or None, alpha, beta): check_flow() scores the pass's pairs on the engine's own stage-1 planes behind the engine's run
+    (ssm_flow_consistency_fwd), the eight words per pair go back to the ring slot like the block counts, and the writer thread notes
+    every pair in the log's `flow_checks` and lets a pair with score >= T fall back like a cut pair (`flow_failed`).  It needs no row 0.
     log: the VideoInterpolator whose `cuts` and `static` take the notes.
 
     Buffers (buffers()).  With scene cuts or static blocks a stream's payload buffer has `lead` = 1 row in front of the pass's frames.  A pass
@@ -2679,12 +2683,13 @@ class PairOptions:
     the end `carried`, the writer thread's copy of the frame that row 0 stands for, takes the last pair's right frame: its ring slot is
     free by the time the next pass's rows are written."""
 
-    def __init__(self, log, clip, scene_cut=None, static=None):
-        self.log, self.clip, self.static = log, clip, static
+    def __init__(self, log, clip, scene_cut=None, static=None, flow_check=None):
+        self.log, self.clip, self.static, self.flow = log, clip, static, flow_check
         self.cuts = None if scene_cut is None else SceneCuts(scene_cut)
         self.pixels, self.blocks = clip.h * clip.w, static_blocks(clip.h, clip.w)
         self.lead = 0 if self.cuts is None and static is None else 1
-        self.near = self.cuts is not None or clip.window is not None          # the writer thread looks at a pair's input frames
+        # the writer thread looks at a pair's input frames
+        self.near = self.cuts is not None or clip.window is not None or (flow_check is not None and flow_check[0] is not None)
         self.carried = np.empty(clip.fb, np.uint8) if self.near else None
         self.paste, self.last_right = None, 0
         if clip.window is not None:
@@ -2705,6 +2710,12 @@ class PairOptions:
             self.dev_sums, self.host_sums, self.np_sums = words()
         if self.static is not None:
             self.dev_counts, self.host_counts, self.np_counts = words()
+        if self.flow is not None:
+            self.dev_flow = [torch.empty(pairs, 2, 4, dtype=torch.float64, device=clip.dev) for _ in range(n)]
+            self.host_flow = [torch.empty(pairs, 2, 4, dtype=torch.float64).pin_memory() for _ in range(depth)]
+            self.np_flow = [t.numpy() for t in self.host_flow]
+            nbytes = hb.load().ssm_flow_consistency_workspace_bytes(pairs, clip.h, clip.w)
+            self.flow_ws = [torch.empty(nbytes, dtype=torch.uint8, device=clip.dev) for _ in range(n)]
         return sb
 
     def seed(self, frame, k, row, fetch_row):
@@ -2750,6 +2761,16 @@ class PairOptions:
                              clip.bits, self.static, counts=self.dev_counts[k][p:p + m])
             self.host_counts[r].copy_(self.dev_counts[k], non_blocking=True)
 
+    def check_flow(self, r, k, flow4):
+        """Behind the engine's run and ahead of the D2H copies of the frames: one ssm_flow_consistency_fwd call over the pass's pairs on
+        flow4, the four planes F01 | F10 where the engine's stage 1 left them (PairEngine.s1.t["out"]), on the clip's picture inside the
+        canvas; then the eight words per pair on their way back to ring slot r."""
+        if self.flow is not None:
+            from .flow_eval import flow_consistency
+            clip, (_, alpha, beta) = self.clip, self.flow
+            flow_consistency(flow4, clip.h, clip.w, *clip.at, alpha, beta, out=self.dev_flow[k], workspace=self.flow_ws[k])
+            self.host_flow[r].copy_(self.dev_flow[k], non_blocking=True)
+
     def download(self, r, k):
         """Behind the D2H copies of the frames and ahead of `done`: the luma sums' way back to ring slot r."""
         if self.cuts is not None:
@@ -2760,22 +2781,32 @@ class PairOptions:
         buffers in write order; near() -> (pairs, at), asked for only where the writer thread looks at input frames: [(i, the left frame's
         host bytes or None for `carried`, the right frame's)] and per row None for an input frame or (pair's place in `pairs`, exact t).
         With every option off: `rows` itself."""
-        if not self.near and self.static is None:
+        if not self.near and self.static is None and self.flow is None:
             return rows
         pairs, at = near() if self.near else ((), [None] * len(rows))
         return functools.partial(self.written, list(index), self.np_sums[r] if self.cuts is not None else None,
-                                 self.np_counts[r] if self.static is not None else None, pairs, list(zip(rows, at)))
+                                 self.np_counts[r] if self.static is not None else None, pairs, list(zip(rows, at)),
+                                 self.np_flow[r] if self.flow is not None else None)
 
-    def written(self, index, sums, counts, pairs, order):
-        """The generator behind rows(); sums, counts: the pass's words in its ring slot, None with the option off."""
+    def written(self, index, sums, counts, pairs, order, flows=None):
+        """The generator behind rows(); sums, counts, flows: the pass's words in its ring slot, None with the option off.  A pair's
+        synthesised frames fall back to the nearer input frame if it is a cut or fails the flow check."""
         if counts is not None:
             self.log.static.extend((i, int(counts[p]), self.blocks) for p, i in enumerate(index))
-        verdict = [False] * len(pairs)
+        verdict = [False] * len(index)
         if sums is not None:
             for p, i in enumerate(index):
                 verdict[p], score = self.cuts.feed(int(sums[p]), self.pixels)
                 if verdict[p]:
                     self.log.cuts.append((i, score))
+        if flows is not None:
+            from .flow_eval import FlowCheck
+            for p, i in enumerate(index):
+                check = FlowCheck.of(flows[p])
+                self.log.flow_checks.append((i, check))
+                if self.flow[0] is not None and check.score >= self.flow[0]:
+                    verdict[p] = True
+                    self.log.flow_failed.append((i, check))
         for buf, at in order:
             if at is not None and (verdict[at[0]] or self.paste is not None):
                 _, lf, rt = pairs[at[0]]
@@ -2808,7 +2839,7 @@ class VideoInterpolator:
     def __init__(self, model, cfg, upsample_rate=None, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
                  tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8, scene_cut=None,
                  shutter_light="coded", deinterlace=None, dedup=None, dedup_max=DEDUP_MAX, active=None, active_probe=ACTIVE_PROBE,
-                 shutter_window="box", field_probe=None, static=None):
+                 shutter_window="box", field_probe=None, static=None, flow_check=None, flow_alpha=None, flow_beta=None):
         """target_rate = (num, den) and / or speed (a Fraction, or what Fraction() takes; 1/4 is four times slower): the output follows
         Timeline(speed * input rate / target_rate) instead of the fixed grid of upsample_rate, which is then not used (see
         _run_timeline); with both None nothing changes.  flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
@@ -2897,8 +2928,21 @@ class VideoInterpolator:
         every pair (i, i + 1) that got outputs.  It goes with upsample_rate, target_rate, speed, scene_cut (a cut pair's outputs are
         replaced whole, as without it), matrix, color_range, flow_scale and tile, and with every format; not with shutter (every output
         is an accumulator's), deinterlace, dedup, active or a recurrent model (chain two runs).  None: every mode as it is, launch for
-        launch."""
+        launch.
+        flow_check (True: a report; or a threshold T >= 0, a Fraction or what flow_eval.parse_flow_check takes, "T" or "T:ALPHA:BETA"; no
+        default T) with flow_alpha, flow_beta (None: flow_eval.FLOW_ALPHA, FLOW_BETA = 0.01 and 0.5, the numbers of Sundaram, Brox and
+        Keutzer 2010 - a convention, not backed by a measurement here): every pass then also scores the forward-backward consistency of
+        its pairs' two stage-1 flows on the GPU (ssm_flow_consistency_fwd on the engine's own planes, on the clip's picture, behind the
+        engine's run and ahead of the copies to the host), eight words per pair.  After run(): `flow_checks` lists (i, FlowCheck) of every
+        pair (i, i + 1) that ran.  With a threshold a pair whose FlowCheck.score - the larger share of inconsistent among the judged
+        pixels of the two directions, a Fraction - is >= T falls back like a cut pair: the left input frame's bytes at t < 1/2, the right
+        one's from there on; `flow_failed` lists those pairs.  Scores lie in [0, 1]: T = 0 condemns every pair, any T > 1 none.  The
+        pair still runs on the GPU.  With this repository's synthetic weights a score says nothing about quality.  It goes with
+        upsample_rate, target_rate, speed, scene_cut (a pair falls back if it is a cut or fails the check), static, active, matrix,
+        color_range and every format; not with shutter, deinterlace, dedup, flow_scale other than 1, tile or a recurrent model.  None:
+        every mode as it is, launch for launch - nothing is allocated or queued."""
         from .coarse import check_scale
+        from .flow_eval import FLOW_ALPHA, FLOW_BETA, parse_flow_check
         from .tiles import check_args
         self.flow_scale = check_scale(flow_scale)
         if self.flow_scale != 1 and getattr(model, "recurrent", False):
@@ -2937,6 +2981,18 @@ class VideoInterpolator:
                 if given:
                     raise ValueError("static together with %s is not available: blocks that do not change are kept in frames synthesised "
                                      "between two input frames as they were read, and nothing else; chain two runs" % name)
+        self.flow_check, self.flow_checks, self.flow_failed = None, [], []
+        if flow_check is not None and flow_check is not False:
+            for name, given in (("shutter", shutter is not None), ("deinterlace", deinterlace is not None),
+                                ("dedup", dedup is not None and dedup is not False), ("flow_scale=%d" % self.flow_scale, self.flow_scale != 1),
+                                ("tile", self.tile is not None), ("a recurrent model", getattr(model, "recurrent", False))):
+                if given:
+                    raise ValueError("flow_check together with %s is not available: it scores the two full-size stage-1 flows of a pair "
+                                     "whose frames are synthesised between two input frames, and nothing else" % name)
+            t, a, b = parse_flow_check(flow_check, flow_alpha, flow_beta)
+            self.flow_check = (t, float(FLOW_ALPHA if a is None else a), float(FLOW_BETA if b is None else b))
+        elif flow_alpha is not None or flow_beta is not None:
+            raise ValueError("flow_alpha / flow_beta are the flow check's numbers: give flow_check, or leave them out")
         self.field_probe_option = None if field_probe is None or field_probe is False else (
             FIELD_PROBE if field_probe is True else parse_field_probe(field_probe))
         self.field_probe, self._probed, self._probed_order = None, None, None
@@ -3065,6 +3121,7 @@ class VideoInterpolator:
         """Returns the number of frames written: (n - 1) * upsample_rate + 1 for n input frames (with target_rate / speed:
         floor((n - 1) / step) + 1; with a shutter: Timeline.n_outputs(n); with deinterlace: 2 n; with dedup the fixed grid's count)."""
         self.cuts, self.repeats, self.active, self.active_note, self.active_excess, self.static = [], [], None, None, [], []
+        self.flow_checks, self.flow_failed = [], []
         if self.field_probe_option is not None and reader is not self._probed:
             reader = self.probe_fields(reader)
         self._probed = None          # one run per probe
@@ -3125,7 +3182,7 @@ class VideoInterpolator:
         t_dev = torch.tensor(t_values(self.rate), dtype=torch.float32, device=dev)
         slots = ring_slots(depth, fb, pb, pb * nt, fb_out=clip.fb_out)
         np_in, np_out = slots.np_in, slots.np_out
-        opt = PairOptions(self, clip, self.scene_cut, self.static_lo)
+        opt = PairOptions(self, clip, self.scene_cut, self.static_lo, self.flow_check)
         lead, lefts, rights = opt.lead, list(range(pb)), list(range(1, pb + 1))
         _, dev_out, _, ingested, _ = opt.buffers(n, depth, pb, pb, pb * nt)
         planes = [torch.empty(pb + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [carried left frame | new frames]
@@ -3159,6 +3216,7 @@ class VideoInterpolator:
                 x = planes[k]
                 img6 = x.view(1, 6, hp, wp) if pb == 1 else x.as_strided((pb, 6, hp, wp), (3 * hp * wp, hp * wp, wp, 1))
                 frames = pipe.engines[k].run(img6, t_dev, False)
+                opt.check_flow(r, k, pipe.engines[k].s1.t["out"] if opt.flow is not None else None)
                 clip.egress(frames, dev_out[k])
                 opt.paste_static(r, k, [(0, pb, dev_out[k])])
                 slots.host_out[r].copy_(dev_out[k], non_blocking=True)
@@ -3314,7 +3372,7 @@ class VideoInterpolator:
         host_in, host_out, host_t, np_in, np_out, np_t, done = ring_slots(depth, fb, cap, pb * max(S, 1), pb * max(S, 1), fb_out=clip.fb_out)
         plan = PassPlanner(tl, pb, cap)
         if pipe is not None:
-            opt = PairOptions(self, clip, self.scene_cut, self.static_lo)
+            opt = PairOptions(self, clip, self.scene_cut, self.static_lo, self.flow_check)
             lead = opt.lead
             _, dev_out, dev_t, ingested, _ = opt.buffers(n, depth, pb, cap, pb * S, pb * S)
             planes = [torch.zeros(pb, 2, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [pair][left | right]
@@ -3343,6 +3401,7 @@ class VideoInterpolator:
                 ingested[k].record()
                 last_p[0] = len(pairs) - 1
                 frames = pipe.engines[k].run(planes[k].view(pb, 6, hp, wp), dev_t[k], False)
+                opt.check_flow(r, k, pipe.engines[k].s1.t["out"] if opt.flow is not None else None)
                 if all(len(ts) == S for _, _, ts in pairs):
                     spans = [(0, len(pairs) * S)]
                 else:
