@@ -60,7 +60,7 @@ well, chain two runs,  ... --deinterlace auto --output - | interpolate_video.py 
 pulldown is undone before anything else: the cadence is found from the differences of same-parity fields of neighbouring frames (summed on
 the GPU, ssm_field_diff_fwd), per window of five frames the frame that holds nothing new is dropped and the two split fields are paired
 again.  What follows sees the film's own frames, byte for byte, as a progressive clip at 4/5 of the rate (30000:1001 -> 24000:1001), so it
-goes with every option but --deinterlace: --detelecine --fps 60000:1001 is 24 -> 60 without the 2-3 judder.  The field order falls out of
+goes with every option but --deinterlace and --field_probe: --detelecine --fps 60000:1001 is 24 -> 60 without the 2-3 judder.  The field order falls out of
 the data: It, Ib, Ip and I? headers are all taken.  There is no threshold; the windows whose cadence changed go to --log with their best
 and second-best score.  2:2 and mixed cadences, soft telecine and the orphan field at an edit inside a cycle are out of scope.
 
@@ -236,65 +236,16 @@ def getargs(argv=None):
                              "With T, a decimal or a fraction: a pair whose share of inconsistent pixels reaches T gets copies of its input "
                              "frames, like a scene cut. ALPHA:BETA default to 0.01:0.5, a convention of the literature; no default T.")
     args = parser.parse_args(argv)
-    if args.flow_check is not None:
-        for flag, given in (("--shutter", args.shutter is not None), ("--deinterlace", args.deinterlace is not None),
-                            ("--dedup", args.dedup is not None), ("--flow_scale %d" % args.flow_scale, args.flow_scale != 1),
-                            ("--tile", args.tile is not None)):
-            if given:
-                parser.error("--flow_check does not go together with %s: it scores the two full-size stage-1 flows of a pair whose frames "
-                             "are synthesised between two input frames, and nothing else" % flag)
-    if args.static is not None:
-        for flag, given in (("--shutter", args.shutter is not None), ("--deinterlace", args.deinterlace is not None),
-                            ("--dedup", args.dedup is not None), ("--active", args.active is not None)):
-            if given:
-                parser.error("--static does not go together with %s: blocks that do not change are kept in frames synthesised between two "
-                             "input frames as they were read, and nothing else; chain two runs" % flag)
-    if args.field_probe is not None and args.detelecine:
-        parser.error("--field_probe does not go together with --detelecine: a telecined clip is a mixture of progressive and combed frames by "
-                     "construction, and pulldown removal finds its field order itself")
-    if args.active is not None:
-        for flag, given in (("--shutter", args.shutter is not None), ("--deinterlace", args.deinterlace is not None),
-                            ("--dedup", args.dedup is not None)):
-            if given:
-                parser.error("--active does not go together with %s: the picture is cut out and the bars are pasted back around frames "
-                             "synthesised between two input frames, and nothing else; chain two runs" % flag)
-    if args.dedup is not None:
-        for flag, given in (("--fps", args.fps is not None), ("--speed", args.speed is not None), ("--shutter", args.shutter is not None),
-                            ("--scene_cut", args.scene_cut is not None), ("--deinterlace", args.deinterlace is not None)):
-            if given:
-                parser.error("--dedup does not go together with %s: it repairs repeated frames on the grid of --upsample_rate and nothing "
-                             "else; pipe the output of --dedup --upsample_rate 1 into a second run" % flag)
-        if args.upsample_rate is not None and args.upsample_rate < 1:
-            parser.error("--upsample_rate must be at least 1 with --dedup (got %d)" % args.upsample_rate)
-    if args.detelecine and args.deinterlace is not None:
-        parser.error("--detelecine does not go together with --deinterlace: pulldown removal pairs the fields of a film frame again, "
-                     "deinterlacing writes every field as a frame of its own")
-    if args.deinterlace is not None:
-        for flag, given in (("--upsample_rate", args.upsample_rate is not None), ("--slowmo", args.slowmo), ("--fps", args.fps is not None),
-                            ("--speed", args.speed is not None), ("--shutter", args.shutter is not None),
-                            ("--scene_cut", args.scene_cut is not None)):
-            if given:
-                parser.error("--deinterlace does not go together with %s: it writes the clip's fields as frames at twice its rate and nothing "
-                             "else; pipe its output into a second run to retime it" % flag)
-    if args.fps is not None or args.speed is not None:
-        if args.upsample_rate is not None or args.slowmo:
-            parser.error("--fps / --speed%s set the output's timeline themselves: they do not go together with --upsample_rate or --slowmo"
-                         % ("" if args.shutter is None else " / --shutter"))
-    else:
-        if args.shutter is not None:
-            parser.error("--shutter averages over the interval of an output frame of --fps / --speed: it needs one of them, and does not go "
-                         "together with --upsample_rate or --slowmo")
-        if args.upsample_rate is None and args.deinterlace is None:
-            args.upsample_rate = 8
-    if args.shutter_light != "coded" and args.shutter is None:
-        parser.error("--shutter_light %s is the light in which --shutter averages: it needs --shutter" % args.shutter_light)
-    if args.shutter_window[0] != "box" and args.shutter is None:
-        parser.error("--shutter_window %s is the window of the sub-frames that --shutter averages: it needs --shutter"
-                     % V.window_name(args.shutter_window))
-    if args.scene_cut is not None and args.shutter is not None:
-        parser.error("--scene_cut does not go together with --shutter: an average of sub-frames across a cut needs a definition of its own")
+    refusal = V.flag_refusal(dict(vars(args), target_rate=args.fps,
+                                  shutter_window=None if args.shutter_window[0] == "box" else V.window_name(args.shutter_window)))
+    if refusal is not None:
+        parser.error(refusal)
+    if args.dedup is not None and args.upsample_rate is not None and args.upsample_rate < 1:
+        parser.error("--upsample_rate must be at least 1 with --dedup (got %d)" % args.upsample_rate)
     if args.shutter is not None and args.shutter_samples < 1:
         parser.error("--shutter_samples must be at least 1 (got %d)" % args.shutter_samples)
+    if args.upsample_rate is None and args.fps is None and args.speed is None and args.deinterlace is None:
+        args.upsample_rate = 8
     return args
 
 

@@ -2820,6 +2820,89 @@ class PairOptions:
 FieldProbe = namedtuple("FieldProbe", "verdict counts kinds order note warning advice")          # VideoInterpolator.field_probe
 
 
+# Which options go together: one table for VideoInterpolator and for scripts/interpolate_video.py.
+# OPTIONS, option: (as VideoInterpolator's messages spell it, as the command line's do, the value that says "not given" besides None).
+# A spelling of None: that front end cannot be given the option; one with a % carries the value.
+OPTIONS = {k: (k, "--" + k, None) for k in ("upsample_rate", "speed", "shutter", "scene_cut", "deinterlace", "dedup", "active", "field_probe",
+                                            "static", "flow_check", "tile")}
+OPTIONS.update({
+    "target_rate": ("target_rate", "--fps", None), "slowmo": (None, "--slowmo", False), "recurrent": ("a recurrent model", None, False),
+    "detelecine": ("detelecine", "--detelecine", False),          # no argument of the constructor: probe_fields meets it as a TelecineSource
+    "shutter_light": ("shutter_light=%r", "--shutter_light %s", "coded"),
+    "shutter_window": ("shutter_window=%r", "--shutter_window %s", None),          # both front ends hand a box over as None
+    "flow_alpha": ("flow_alpha", None, None), "flow_beta": ("flow_beta", None, None), "flow_scale": ("flow_scale=%d", "--flow_scale %d", 1)})
+_API, _FLAG = "{x} together with {y} is not available", "{x} does not go together with {y}"
+_BETWEEN = "synthesised between two input frames"
+_ACTIVE = ": the picture is cut out and the bars are pasted back around frames %s, and nothing else; chain two runs" % _BETWEEN
+_STATIC = ": blocks that do not change are kept in frames %s as they were read, and nothing else; chain two runs" % _BETWEEN
+_FLOW = ": it scores the two full-size stage-1 flows of a pair whose frames are %s, and nothing else" % _BETWEEN
+_PROBE = ": a telecined clip is a mixture of progressive and combed frames by construction, and pulldown removal finds its field order itself"
+_TIMELINE = " set the output's timeline themselves: they do not go together with --upsample_rate or --slowmo"
+# OPTION_RULES, row: (options, others, needs, VideoInterpolator's message, the command line's).  With needs False the row refuses: it
+# speaks when one of its options is given together with one of the others - {x} and {y} are the first given of each, as OPTIONS spells
+# them.  With needs True it speaks when one of its options is given and none of the others.  A message of None: that front end has no
+# such rule.  The first row that speaks supplies the message, so a pair may stand in one direction only (static names active, active
+# does not name static) and a row may rest on the rows before it (shutter_timeline on shutter).  The rows are in the order in which
+# VideoInterpolator asks them; FLAG_ORDER is the command line's.
+OPTION_RULES = {
+    "dedup": (("dedup",), ("target_rate", "speed", "shutter", "scene_cut", "deinterlace", "recurrent"), False,
+              _API + ": it repairs repeated frames on the fixed grid of upsample_rate and nothing else; chain two runs (dedup with "
+              "upsample_rate=1 first, then the other)",
+              _FLAG + ": it repairs repeated frames on the grid of --upsample_rate and nothing else; pipe the output of --dedup "
+              "--upsample_rate 1 into a second run"),
+    "active": (("active",), ("shutter", "deinterlace", "dedup", "recurrent"), False, _API + _ACTIVE, _FLAG + _ACTIVE),
+    "static": (("static",), ("shutter", "deinterlace", "dedup", "active", "recurrent"), False, _API + _STATIC, _FLAG + _STATIC),
+    "flow_check": (("flow_check",), ("shutter", "deinterlace", "dedup", "flow_scale", "tile", "recurrent"), False, _API + _FLOW, _FLAG + _FLOW),
+    "flow_numbers": (("flow_alpha", "flow_beta"), ("flow_check",), True,
+                     "flow_alpha / flow_beta are the flow check's numbers: give flow_check, or leave them out", None),
+    "field_probe": (("field_probe",), ("recurrent",), False, _API, None),
+    "field_probe_detelecine": (("field_probe",), ("detelecine",), False, _API + _PROBE, _FLAG + _PROBE),
+    "detelecine": (("detelecine",), ("deinterlace",), False, None,
+                   _FLAG + ": pulldown removal pairs the fields of a film frame again, deinterlacing writes every field as a frame of its own"),
+    "deinterlace": (("deinterlace",), ("upsample_rate", "slowmo", "target_rate", "speed", "shutter", "scene_cut", "recurrent"), False,
+                    _API + ": deinterlacing writes the clip's fields as frames at twice its rate and nothing else; retime its progressive "
+                    "output in a second run",
+                    _FLAG + ": it writes the clip's fields as frames at twice its rate and nothing else; pipe its output into a second run "
+                    "to retime it"),
+    "shutter_light": (("shutter_light",), ("shutter",), True,
+                      "{x} is the light in which a shutter averages: give a shutter, or leave it at \"coded\"",
+                      "{x} is the light in which --shutter averages: it needs --shutter"),
+    "shutter_window": (("shutter_window",), ("shutter",), True,
+                       "{x} is the window of a shutter's sub-frames: give a shutter, or leave it at \"box\"",
+                       "{x} is the window of the sub-frames that --shutter averages: it needs --shutter"),
+    "scene_cut": (("scene_cut",), ("shutter",), False,
+                  "{x} together with {y} is not defined: an average of sub-frames across a cut needs a definition of its own; give one of the two",
+                  _FLAG + ": an average of sub-frames across a cut needs a definition of its own"),
+    "shutter": (("shutter",), ("target_rate", "speed"), True,
+                "a shutter averages over the interval of an output frame of target_rate / speed: give one of them (speed=1 keeps the "
+                "input's rate)",
+                "--shutter averages over the interval of an output frame of --fps / --speed: it needs one of them, and does not go together "
+                "with --upsample_rate or --slowmo"),
+    "shutter_timeline": (("shutter",), ("upsample_rate", "slowmo"), False, None, "--fps / --speed / --shutter" + _TIMELINE),   # behind "shutter"
+    "timeline": (("target_rate", "speed"), ("upsample_rate", "slowmo"), False, None, "--fps / --speed" + _TIMELINE),
+}
+FLAG_ORDER = ("flow_check", "static", "field_probe_detelecine", "active", "dedup", "detelecine", "deinterlace", "shutter", "shutter_timeline",
+              "timeline", "shutter_light", "shutter_window", "scene_cut")
+
+
+def api_refusal(values, front=0, order=OPTION_RULES):
+    """Why VideoInterpolator does not take the options `values` = {option of OPTIONS: value} together - the message of the first row
+    that speaks - or None.  An option is given unless its value is None or the one OPTIONS names."""
+    given = {k: OPTIONS[k][front] % (v,) if "%" in OPTIONS[k][front] else OPTIONS[k][front]          # option: as the message spells it
+             for k, v in values.items() if k in OPTIONS and OPTIONS[k][front] is not None and v is not None and v != OPTIONS[k][2]}
+    for row in order:
+        options, others, needs, *texts = OPTION_RULES[row]
+        x, y = (next((given[k] for k in names if k in given), None) for names in (options, others))
+        if texts[front] is not None and x is not None and (y is None) == needs:
+            return texts[front].format(x=x, y=y)
+    return None
+
+
+def flag_refusal(values):
+    """The same for the command line's flags, in its own order of asking."""
+    return api_refusal(values, 1, FLAG_ORDER)
+
+
 class VideoInterpolator:
     """reader -> (upsample_rate - 1) frames between every two input frames -> writer, streamed; or, with target_rate / speed, the frames
     of a Timeline (any output rate, any speed: _run_timeline).
@@ -2879,16 +2962,14 @@ class VideoInterpolator:
         the rate (field_outputs).  "auto" takes the field order from the reader's header (a Y4MReader(interlaced=True)) and refuses Ip and
         I?; "tff" and "bff" override any header.  The fields run through the fixed grid of upsample_rate = 2 at t = 1/2, at half the
         frame's height: matrix (None: default_matrix of the FRAME's height), color_range, flow_scale and tile / halo / blend act as
-        they do there.  It does not go together with an upsample_rate, target_rate, speed, shutter, scene_cut or a recurrent model
-        (chain a second run to retime the progressive output).  None: every other mode as it is.
+        they do there.  To retime the progressive output, chain a second run.  None: every other mode as it is.
         dedup (True: the default thresholds at the clip's depth; or (hi, lo, frac) / "HI:LO:FRAC", parse_dedup) with dedup_max = D:
         frames that repeat the one before (Repeats, from the 8 x 8 block differences of ssm_block_sad_fwd) in runs of at most D are
         repaired - the output keeps the fixed grid of upsample_rate, and the places of a run's repeats and of the frames around them
         are filled by frames synthesised between the run's two neighbours (GapTimeline; a RepeatSource in front of the timeline
         mode's loop).  upsample_rate = 1 is then legal and means repair only.  `repeats` lists the runs after run(): (first repeat, m,
         repaired, worst max, worst over).  The defaults are the numbers of ffmpeg's mpdecimate, a convention, not its construction and
-        not backed by a measurement on compressed footage.  It does not go together with target_rate, speed, shutter, scene_cut or
-        deinterlace (chain two runs).  None: every mode as it is, launch for launch.
+        not backed by a measurement on compressed footage.  None: every mode as it is, launch for launch.
         active ("auto", "auto:LIM[:FRAC]", "W:H:X:Y" or (w, h, x, y); parse_active) with active_probe = P: the clip is letterboxed, and
         the run is that of its picture alone.  The rectangle is the one given, or with "auto" the smallest aligned one that holds every
         active row and column of the first P frames (ActiveArea, from the counts of ssm_luma_counts_fwd; an ActiveSource in front of the
@@ -2900,10 +2981,9 @@ class VideoInterpolator:
         has an active line, or it is under 32 samples in a direction - then byte for byte the run without the option), `active_note` one
         line that says which and why, `active_excess` [(frame index, active rows outside, active columns outside)] of later frames that
         leave the rectangle; they are reported and change nothing.  LIM = 24 at 8 bits is the number of ffmpeg cropdetect's limit, not
-        its construction, FRAC = 1/64 this module's own: conventions, not backed by a measurement on compressed footage.  It goes with
-        upsample_rate, target_rate, speed, scene_cut, matrix, color_range, flow_scale and tile; not with shutter (every output comes from
-        the accumulator, none has one input frame's bars), deinterlace, dedup or a recurrent model (chain two runs).  None: every mode
-        as it is, launch for launch.
+        its construction, FRAC = 1/64 this module's own: conventions, not backed by a measurement on compressed footage.  With a
+        shutter every output comes from the accumulator, and none has one input frame's bars.  None: every mode as it is, launch for
+        launch.
         field_probe (True: FIELD_PROBE = 48 frames; or P, parse_field_probe): the field order is looked for in the data.  A
         FieldOrderSource in front of the loop takes the comb sums of the first P frames on the GPU (ssm_field_order_sums_fwd) and decides
         "tff", "bff", "progressive" or nothing (FieldVerdict).  With deinterlace="auto" and a header that says Ip or I? the run takes the
@@ -2914,9 +2994,9 @@ class VideoInterpolator:
         verdict, counts (nT, nB, nP, nU), kinds, order (the order in use, None without deinterlace), note (one line with the counts),
         warning (the contradiction, or None) and advice (a report-only run on a clip that looks interlaced: the line that names
         deinterlace="tff" / "bff"; else None).  The ratios are conventions in the spirit of ffmpeg's idet, not its construction, and not
-        backed by a measurement on noisy or compressed footage.  Frames behind the probe are not watched.  Not with a recurrent model,
-        and not on a TelecineSource: a telecined clip is a mixture of both kinds of frame by construction.  None: every mode as it is,
-        launch for launch.
+        backed by a measurement on noisy or compressed footage.  Frames behind the probe are not watched.  probe_fields refuses a
+        TelecineSource: a telecined clip is a mixture of both kinds of frame by construction.  None: every mode as it is, launch for
+        launch.
         static (LO, a whole number in 0 .. 2^24 - 1, or its text; parse_static; no default value): blocks that do not change keep their
         bytes.  Where the two frames of a pair agree on an 8 x 8 block - the sum of |difference| over its luma and the chroma under it is
         at most LO, in codes of the clip's depth - every frame synthesised between them carries the LEFT frame's samples of that block
@@ -2925,10 +3005,8 @@ class VideoInterpolator:
         frame differs there - a logo, subtitles, a timecode, a locked-off background stop pulsing against the input frames' own bytes.
         Any other LO is the user's number.  Not claimed: a block that agrees in both frames while something crossed it in between is
         kept; the seams between kept and synthesised blocks are not smoothed.  After run(): `static` lists (i, static blocks, blocks) of
-        every pair (i, i + 1) that got outputs.  It goes with upsample_rate, target_rate, speed, scene_cut (a cut pair's outputs are
-        replaced whole, as without it), matrix, color_range, flow_scale and tile, and with every format; not with shutter (every output
-        is an accumulator's), deinterlace, dedup, active or a recurrent model (chain two runs).  None: every mode as it is, launch for
-        launch.
+        every pair (i, i + 1) that got outputs.  With scene_cut a cut pair's outputs are replaced whole, as without static; with a shutter
+        every output is an accumulator's.  Every format is taken.  None: every mode as it is, launch for launch.
         flow_check (True: a report; or a threshold T >= 0, a Fraction or what flow_eval.parse_flow_check takes, "T" or "T:ALPHA:BETA"; no
         default T) with flow_alpha, flow_beta (None: flow_eval.FLOW_ALPHA, FLOW_BETA = 0.01 and 0.5, the numbers of Sundaram, Brox and
         Keutzer 2010 - a convention, not backed by a measurement here): every pass then also scores the forward-backward consistency of
@@ -2937,10 +3015,11 @@ class VideoInterpolator:
         pair (i, i + 1) that ran.  With a threshold a pair whose FlowCheck.score - the larger share of inconsistent among the judged
         pixels of the two directions, a Fraction - is >= T falls back like a cut pair: the left input frame's bytes at t < 1/2, the right
         one's from there on; `flow_failed` lists those pairs.  Scores lie in [0, 1]: T = 0 condemns every pair, any T > 1 none.  The
-        pair still runs on the GPU.  With this repository's synthetic weights a score says nothing about quality.  It goes with
-        upsample_rate, target_rate, speed, scene_cut (a pair falls back if it is a cut or fails the check), static, active, matrix,
-        color_range and every format; not with shutter, deinterlace, dedup, flow_scale other than 1, tile or a recurrent model.  None:
-        every mode as it is, launch for launch - nothing is allocated or queued."""
+        pair still runs on the GPU.  With this repository's synthetic weights a score says nothing about quality.  With scene_cut a pair
+        falls back if it is a cut or fails the check.  Every format is taken.  None: every mode as it is, launch for launch - nothing
+        is allocated or queued.
+        Which of these options do not go together, which need another, and what each refusal says is one table, OPTION_RULES (above
+        the class; api_refusal asks it here, flag_refusal for the command line), not a list kept per option."""
         from .coarse import check_scale
         from .flow_eval import FLOW_ALPHA, FLOW_BETA, parse_flow_check
         from .tiles import check_args
@@ -2957,59 +3036,21 @@ class VideoInterpolator:
         if n_frames != 2:
             raise NotImplementedError("N_FRAMES=%d needs the recurrent bottleneck (unpinned upstream); use N_FRAMES=2" % n_frames)
         self.dedup = None if dedup is None or dedup is False else parse_dedup(dedup)
-        self.dedup_max, self.repeats = parse_dedup_max(dedup_max), []
-        if self.dedup is not None:
-            for name, given in (("target_rate", target_rate is not None), ("speed", speed is not None), ("shutter", shutter is not None),
-                                ("scene_cut", scene_cut is not None), ("deinterlace", deinterlace is not None),
-                                ("a recurrent model", getattr(model, "recurrent", False))):
-                if given:
-                    raise ValueError("dedup together with %s is not available: it repairs repeated frames on the fixed grid of upsample_rate "
-                                     "and nothing else; chain two runs (dedup with upsample_rate=1 first, then the other)" % name)
+        self.dedup_max = parse_dedup_max(dedup_max)
         self.active_option, self.active_probe = parse_active(active), parse_active_probe(active_probe)
-        self.active, self.active_note, self.active_excess = None, None, []
-        if self.active_option is not None:
-            for name, given in (("shutter", shutter is not None), ("deinterlace", deinterlace is not None),
-                                ("dedup", dedup is not None and dedup is not False), ("a recurrent model", getattr(model, "recurrent", False))):
-                if given:
-                    raise ValueError("active together with %s is not available: the picture is cut out and the bars are pasted back around "
-                                     "frames synthesised between two input frames, and nothing else; chain two runs" % name)
-        self.static_lo, self.static = None if static is None else parse_static(static), []
-        if self.static_lo is not None:
-            for name, given in (("shutter", shutter is not None), ("deinterlace", deinterlace is not None),
-                                ("dedup", dedup is not None and dedup is not False), ("active", active is not None),
-                                ("a recurrent model", getattr(model, "recurrent", False))):
-                if given:
-                    raise ValueError("static together with %s is not available: blocks that do not change are kept in frames synthesised "
-                                     "between two input frames as they were read, and nothing else; chain two runs" % name)
-        self.flow_check, self.flow_checks, self.flow_failed = None, [], []
+        self.static_lo = None if static is None else parse_static(static)
+        self.flow_check = None
         if flow_check is not None and flow_check is not False:
-            for name, given in (("shutter", shutter is not None), ("deinterlace", deinterlace is not None),
-                                ("dedup", dedup is not None and dedup is not False), ("flow_scale=%d" % self.flow_scale, self.flow_scale != 1),
-                                ("tile", self.tile is not None), ("a recurrent model", getattr(model, "recurrent", False))):
-                if given:
-                    raise ValueError("flow_check together with %s is not available: it scores the two full-size stage-1 flows of a pair "
-                                     "whose frames are synthesised between two input frames, and nothing else" % name)
             t, a, b = parse_flow_check(flow_check, flow_alpha, flow_beta)
             self.flow_check = (t, float(FLOW_ALPHA if a is None else a), float(FLOW_BETA if b is None else b))
-        elif flow_alpha is not None or flow_beta is not None:
-            raise ValueError("flow_alpha / flow_beta are the flow check's numbers: give flow_check, or leave them out")
         self.field_probe_option = None if field_probe is None or field_probe is False else (
             FIELD_PROBE if field_probe is True else parse_field_probe(field_probe))
         self.field_probe, self._probed, self._probed_order = None, None, None
-        if self.field_probe_option is not None and getattr(model, "recurrent", False):
-            raise ValueError("field_probe together with a recurrent model is not available")
         self.deinterlace = parse_deinterlace(deinterlace)
-        if self.deinterlace is not None:
-            for name, given in (("upsample_rate", upsample_rate is not None), ("target_rate", target_rate is not None), ("speed", speed is not None),
-                                ("shutter", shutter is not None), ("scene_cut", scene_cut is not None),
-                                ("a recurrent model", getattr(model, "recurrent", False))):
-                if given:
-                    raise ValueError("deinterlace together with %s is not available: deinterlacing writes the clip's fields as frames at twice "
-                                     "its rate and nothing else; retime its progressive output in a second run" % name)
-        upsample_rate = 8 if upsample_rate is None else upsample_rate
-        if int(upsample_rate) < (2 if self.dedup is None else 1):
+        rate = 8 if upsample_rate is None else upsample_rate
+        if int(rate) < (2 if self.dedup is None else 1):
             raise ValueError("upsample_rate must be at least 2" if self.dedup is None else "upsample_rate must be at least 1 with dedup")
-        self.model, self.cfg, self.rate = model, cfg, int(upsample_rate)
+        self.model, self.cfg, self.rate = model, cfg, int(rate)
         self.n_streams, self.pb = max(1, int(n_streams)), max(1, int(pairs_per_batch))
         if matrix is not None:
             table_index(matrix)          # refuses an unknown matrix by name, here rather than at the first clip
@@ -3021,21 +3062,23 @@ class VideoInterpolator:
         if shutter is not None:
             Timeline(1, shutter=shutter, samples=shutter_samples)          # refuses a bad value by name, here rather than at the first clip
         self.shutter_light = parse_shutter_light(shutter_light)
-        if self.shutter_light != "coded" and shutter is None:
-            raise ValueError("shutter_light=%r is the light in which a shutter averages: give a shutter, or leave it at \"coded\""
-                             % (shutter_light,))
         self.shutter_window = parse_shutter_window(shutter_window)
-        if self.shutter_window[0] != "box" and shutter is None:
-            raise ValueError("shutter_window=%r is the window of a shutter's sub-frames: give a shutter, or leave it at \"box\""
-                             % (shutter_window,))
         self.timed = target_rate is not None or speed is not None
-        self.scene_cut, self.cuts = None if scene_cut is None else parse_scene_cut(scene_cut), []
-        if scene_cut is not None and shutter is not None:
-            raise ValueError("scene_cut together with shutter is not defined: an average of sub-frames across a cut needs a definition of its "
-                             "own; give one of the two")
-        if shutter is not None and not self.timed:
-            raise ValueError("a shutter averages over the interval of an output frame of target_rate / speed: give one of them (speed=1 "
-                             "keeps the input's rate)")
+        self.scene_cut = None if scene_cut is None else parse_scene_cut(scene_cut)
+        refusal = api_refusal(dict(
+            upsample_rate=upsample_rate, target_rate=target_rate, speed=speed, shutter=shutter, scene_cut=self.scene_cut,
+            shutter_light=shutter_light, shutter_window=None if self.shutter_window[0] == "box" else shutter_window,
+            deinterlace=self.deinterlace, dedup=self.dedup, active=self.active_option, field_probe=self.field_probe_option,
+            static=self.static_lo, flow_check=self.flow_check, flow_alpha=flow_alpha, flow_beta=flow_beta, flow_scale=self.flow_scale,
+            tile=self.tile, recurrent=getattr(model, "recurrent", False)))
+        if refusal is not None:          # every value has been through its own check: what is left is which options go together
+            raise ValueError(refusal)
+        self._new_log()
+
+    def _new_log(self):
+        """What a run reports (the constructor's docstring names each), empty: the state before a run and at the start of every run()."""
+        self.cuts, self.repeats, self.static, self.flow_checks, self.flow_failed = [], [], [], [], []
+        self.active, self.active_note, self.active_excess = None, None, []
 
     def canvas(self, h, w):
         """(Hp, Wp) of the planes an h x w clip runs on: padded_dims to multiples of 32 * flow_scale."""
@@ -3091,8 +3134,7 @@ class VideoInterpolator:
         it; a caller that opens its writer only after the refusals calls it first."""
         assert self.field_probe_option is not None, "probe_fields is the option field_probe's"
         if isinstance(reader, TelecineSource):
-            raise ValueError("field_probe together with detelecine is not available: a telecined clip is a mixture of progressive and "
-                             "combed frames by construction, and pulldown removal finds its field order itself")
+            raise ValueError(api_refusal({"field_probe": self.field_probe_option, "detelecine": True}))
         source = FieldOrderSource(reader, self._model_device(), self.field_probe_option)
         verdict = source.decide()
         order = warning = advice = None
@@ -3120,8 +3162,7 @@ class VideoInterpolator:
     def run(self, reader, writer):
         """Returns the number of frames written: (n - 1) * upsample_rate + 1 for n input frames (with target_rate / speed:
         floor((n - 1) / step) + 1; with a shutter: Timeline.n_outputs(n); with deinterlace: 2 n; with dedup the fixed grid's count)."""
-        self.cuts, self.repeats, self.active, self.active_note, self.active_excess, self.static = [], [], None, None, [], []
-        self.flow_checks, self.flow_failed = [], []
+        self._new_log()
         if self.field_probe_option is not None and reader is not self._probed:
             reader = self.probe_fields(reader)
         self._probed = None          # one run per probe
