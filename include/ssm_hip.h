@@ -1118,6 +1118,50 @@ int ssm_block_sad_fwd(const void *a, const void *b, long long stride_a, long lon
 int ssm_static_paste_fwd(const void *a, const void *b, long long stride_a, long long stride_b, void *out, long long stride_out, int N, int T,
                          int H, int W, int layout, int sample_bytes, unsigned int lo, unsigned long long *counts, void *stream);
 
+/* ---- the flow check's per-block fallback, of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) -------
+ * Definition (ssm_amd.video.flow_paste_host is all of it in numpy).  The flow check scores a whole pair; one smeared object should not cost
+ * the whole frame, and one bad region should not hide under a pair's score.  Everything below is in exact integers.
+ *   blocks    the blocks of ssm_static_paste_fwd above: 8 x 8 luma samples at (8 bx, 8 by) with the chroma under them in U and V; the
+ *             trailing W & 7 columns and H & 7 rows belong to no block, a frame with fewer than 8 rows or columns has none.
+ *   measure   mask is what ssm_flow_consistency_fwd writes for the pair: uint8 [2][H][W], one plane per direction.  n(block) = the number
+ *             of the block's 64 luma positions (y, x) at which bit 0 of mask[0][y][x] | mask[1][y][x] is set - for the bytes that kernel
+ *             writes (0 consistent, 1 inconsistent, 2 leaves): inconsistent in at least one direction.  A pixel inconsistent in both
+ *             directions counts once; a pixel that only leaves counts nothing.
+ *   test      a block FAILS in the pair iff n > K, K an integer in 0 .. 64.  K = 64 fails nothing: the run without the option, byte for
+ *             byte.  K = 0 fails every block that has one inconsistent pixel.
+ *   action    in an output strictly between the two frames a failed block's samples, luma and chroma, are the NEARER input frame's: the
+ *             left frame's at t < 1/2, the right frame's from there on - the rule of the cuts and of the pair-level fallback.  Every other
+ *             sample is what the run without the option writes.  Outputs that are input frames pass as their own bytes.
+ *   count     per pair the number of failed blocks.
+ *   NOT claimed: K has no default; seams between pasted and synthesised blocks are not smoothed; a block from the nearer frame inside a
+ *   moving region steps rather than moves; with this repository's synthetic weights nothing can be said about quality.
+ * ssm_flow_paste_fwd: a + n stride_a and b + n stride_b (strides in BYTES, of either sign; frames n and n + 1 of one buffer are fine; with
+ * N = 1 they name nothing) point at the whole payloads of pair n = 0 .. N-1, H x W frames in `layout` (SSM_YUV_*); pair n's two dense mask
+ * planes are at mask + n stride_mask; its T outputs are the payloads at out + (n T + j) stride_out, j < T (with N T = 1 the stride names
+ * nothing).  Outputs j < split take a_n's samples in failed blocks, outputs j >= split b_n's, 0 <= split <= T: the side is a launch scalar,
+ * nothing is uploaded per call.  sample_bytes = 1: bytes; 2: 16-bit little-endian words.  The outputs are read-modify-write: the only
+ * samples written are those of failed blocks; nothing outside the N T payloads is touched; a, b and mask are only read, and a and b may alias
+ * or overlap each other.
+ *     counts[n] = the number of failed blocks of pair n
+ * exact, N 64-bit words on the device, cleared by the entry itself on `stream` (a memset node ahead of the kernel).  A frame without blocks
+ * queues the clear alone.
+ *   The skeleton is ssm_static_paste_fwd's: a workgroup of 256 lanes owns a strip of 256 blocks of one pair and takes them 32 at a time
+ *   (grid: strips, n); 8 neighbouring lanes own a block, lane r of them luma row r and the chroma rows that fall to it.  Lane r loads its 8
+ *   mask bytes of each direction - one 8-byte load where the address sits on an 8-byte boundary, byte by byte where not, decided per piece
+ *   in the same kernel - ORs the two, keeps bit 0 of every byte and pop-counts; three cross-lane shuffles leave n in all 8 lanes.  Where
+ *   n > K every lane loads its pieces of a (if split > 0) and of b (if split < T) and stores them into the outputs of that side, by the
+ *   sibling's piece rule (4-, 8- or 16-byte accesses where aligned, sample by sample where not).  One flag per block, summed over the strip
+ *   through shuffles and LDS, then ONE 64-bit vector atomicAdd per workgroup.  Vector stores and vector atomics only; no scratch, no
+ *   floating point.  Reads 2 bytes of mask per luma sample and sample_bytes per sample and side of the failed blocks, writes T sample_bytes
+ *   per sample of the failed ones.
+ * SSM_E_ARG (nothing is queued), each with its own message and in this order: null pointers; N, then T, outside 1..65535; split outside
+ * 0..T; H or W < 1; a layout outside SSM_YUV_*; sample_bytes outside {1, 2}; K outside 0..64; with N > 1 a stride of a or b below the
+ * frame's bytes in magnitude; with N T > 1 a |stride_out| below them; with N > 1 a |stride_mask| below 2 H W; with sample_bytes = 2 an odd
+ * address, then an odd stride; `out` overlapping a, b or mask; `counts` not 8-byte aligned; a frame of more than 2^31 - 1 strips. */
+int ssm_flow_paste_fwd(const void *a, const void *b, long long stride_a, long long stride_b, void *out, long long stride_out, int N, int T,
+                       int split, int H, int W, int layout, int sample_bytes, const unsigned char *mask, long long stride_mask, int K,
+                       unsigned long long *counts, void *stream);
+
 /* ---- letterboxed clips of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) --------------------------
  * Definition (ssm_amd.video: active_counts_host, ActiveArea, cut_window_host and paste_window_host are all of it in numpy and Python ints,
  * ActiveSource the streamed form).  A 2.39:1 picture inside a 16:9 frame leaves bars that hold, at most, a subtitle or a logo.

@@ -50,6 +50,9 @@
 //                            samples under it - and where the sum is at most `lo` the block's samples of `a` stored into the T outputs of the
 //                            pair; a workgroup owns 256 blocks, 32 at a time, 8 neighbouring lanes a block, a lane one luma row and its share of the
 //                            chroma rows (one load per piece where its address allows); shuffles, then one 64-bit atomicAdd of the count
+//   flow_paste_kernel        the flow check's per-block fallback, ssm_flow_paste_fwd: per 8 x 8 block the luma positions that the pair's two mask
+//                            planes call inconsistent, pop-counted, and where they are more than K the block's samples of the nearer frame
+//                            stored into the pair's outputs (a below `split`, b from there on); static_paste_kernel's strips, lanes and pieces
 //   payload_mix_kernel       hold-out scoring: the cross-fade (a (den - k) + b k + den / 2) / den of two payloads, the frame-blend baseline;
 //                            exact division by multiply-shift, the span walk's pieces with a 16-byte store in place of the sum
 //   fields_split_kernel /    interlaced clips: N frames -> their 2N fields (even rows of every plane, odd rows), and N fields with
@@ -1289,6 +1292,76 @@ __global__ __launch_bounds__(LANES) void static_paste_kernel(const unsigned char
     workgroup_add(kept, &counts[n]);
 }
 
+// ---- the flow check's per-block fallback: the nearer frame's samples where a pair's two flows contradict each other ----------------------
+// The definition is in include/ssm_hip.h: the blocks are static_paste_kernel's; n(block) = the number of its 64 luma positions at which bit
+// 0 of mask[0] | mask[1] is set (ssm_flow_consistency_fwd's bytes: inconsistent in at least one direction); where n > K the block's samples
+// of a_n are stored into the outputs j < split of pair n and those of b_n into the outputs j >= split, and counts[n] is the number of such
+// blocks (ssm_flow_paste_fwd).  The skeleton is the sibling's: strips of PASTE_STEPS x PASTE_BLOCKS blocks, 8 neighbouring lanes a block.
+//   measure lane r takes the 8 mask bytes of luma row r of each direction as a RowPiece of bytes - ONE 8-byte load where the address sits on
+//           an 8-byte boundary (W a multiple of 8 and an aligned plane), byte by byte where not, per piece - ORs the two, keeps bit 0 of every
+//           byte and pop-counts the two words; three xor shuffles leave n <= 64 in all 8 lanes.
+//   paste   where n > K every lane loads its pieces of the side's payload - a if split > 0, then b if split < T, one side after the other
+//           through the same registers - and stores them into that side's outputs, by RowPiece's rule.  Nothing else is written.
+//   count   one flag per block (its lane 0) through workgroup_add: ONE 64-bit vector atomic per workgroup.
+template <typename S, int L>          // the sample and the layout (LAY_*)
+__global__ __launch_bounds__(LANES) void flow_paste_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
+                                                           unsigned char *out, long long stride_out, int T, int split, int W, int cw,
+                                                           long long luma, long long chroma, unsigned nbx, unsigned blocks,
+                                                           const unsigned char *mask, long long stride_mask, unsigned K,
+                                                           unsigned long long *counts) {          // a, b may alias; luma, chroma in samples
+    constexpr int SB = (int)sizeof(S);
+    constexpr int CS = L == LAY_444 ? 8 : 4;                     // chroma samples under a block row
+    constexpr int KY = 8 * SB / 4, KC = CS * SB / 4;             // words of a luma piece, of a chroma piece
+    constexpr int NC = L == LAY_420 ? 1 : 2;                     // chroma pieces of a lane
+    const int n = blockIdx.y;
+    const unsigned r = threadIdx.x & 7u;
+    const unsigned char *pm = mask + n * stride_mask;            // direction 0; direction 1 is `luma` bytes on
+    unsigned failed = 0;
+    for (int step = 0; step < PASTE_STEPS; ++step) {
+        const unsigned blk = (blockIdx.x * (unsigned)PASTE_STEPS + step) * (unsigned)PASTE_BLOCKS + (threadIdx.x >> 3);
+        const bool live = blk < blocks;          // the same in the 8 lanes of a block
+        long long oy = 0, oc[NC] = {};           // byte offsets of the lane's pieces in a payload
+        unsigned bad = 0;
+        if (live) {          // a block of the frame: its luma rows lie inside H x W, its chroma rows inside the chroma planes
+            const unsigned by = blk / nbx, bx = blk - by * nbx;
+            const long long om = (long long)(8 * by + r) * W + 8 * bx;
+            oy = om * SB;
+            const long long crow = L == LAY_420 ? 4 * by + (r & 3u) : 8 * by + r;
+#pragma unroll
+            for (int i = 0; i < NC; ++i) {
+                const long long plane = L == LAY_420 ? (long long)(r >> 2) : (long long)i;
+                oc[i] = (luma + plane * chroma + crow * cw + (long long)(CS * bx)) * SB;
+            }
+            RowPiece<unsigned char, 2> m0, m1;
+            m0.load(pm + om), m1.load(pm + luma + om);
+            bad = (unsigned)__popc((m0.w[0] | m1.w[0]) & 0x01010101u) + (unsigned)__popc((m0.w[1] | m1.w[1]) & 0x01010101u);
+        }
+#pragma unroll
+        for (int s = 1; s < 8; s <<= 1) bad += __shfl_xor(bad, s);          // the block's n, in its 8 lanes
+        const bool fail = live && bad > K;
+        if (fail) {
+            for (int side = 0; side < 2; ++side) {
+                const int j0 = side == 0 ? 0 : split, j1 = side == 0 ? split : T;
+                if (j0 >= j1) continue;
+                const unsigned char *ps = side == 0 ? a + n * stride_a : b + n * stride_b;
+                RowPiece<S, KY> y;
+                RowPiece<S, KC> c[NC];
+                y.load(ps + oy);
+#pragma unroll
+                for (int i = 0; i < NC; ++i) c[i].load(ps + oc[i]);
+                for (int j = j0; j < j1; ++j) {
+                    unsigned char *po = out + ((long long)n * T + j) * stride_out;
+                    y.store(po + oy);
+#pragma unroll
+                    for (int i = 0; i < NC; ++i) c[i].store(po + oc[i]);
+                }
+            }
+        }
+        failed += fail && r == 0 ? 1u : 0u;
+    }
+    workgroup_add(failed, &counts[n]);
+}
+
 // ---- hold-out scoring: the cross-fade of two payloads ---------------------------------------------------------------------------------
 // out_n[i] = (a_n[i] (den - k) + b_n[i] k + (den >> 1)) / den with k = num0 + n num_step, i over the `samples` samples of a row: the
 // frame-blend baseline, rounded half up.  The numerator is below 65535 * 65535 + 32768 < 2^32.  THE DIVISION is the multiply-shift of
@@ -2180,6 +2253,53 @@ extern "C" int ssm_static_paste_fwd(const void *a, const void *b, long long stri
         });
     });
     return ssm::check_launch("ssm_static_paste_fwd");
+}
+
+// ssm_flow_paste_fwd refuses in the order of its header section - pointers, N and T, split, the frame, K, the strides of a and b, of out, of
+// the masks, 2-byte alignment, overlap, counts, the grid - and only then queues the clear and, for a frame that has blocks, the one launch.
+extern "C" int ssm_flow_paste_fwd(const void *a, const void *b, long long stride_a, long long stride_b, void *out, long long stride_out, int N,
+                                  int T, int split, int H, int W, int layout, int sample_bytes, const unsigned char *mask, long long stride_mask,
+                                  int K, unsigned long long *counts, void *stream) {
+    const char *name = "flow_paste";
+    SSM_REQUIRE(a && b && out && mask && counts, "%s: null pointer", name);
+    SSM_REQUIRE(N > 0 && N <= 65535, "%s: N=%d outside 1..65535", name, N);
+    SSM_REQUIRE(T > 0 && T <= 65535, "%s: T=%d outside 1..65535", name, T);
+    SSM_REQUIRE(split >= 0 && split <= T, "%s: split=%d outside 0..T=%d", name, split, T);
+    if (const int e = check_frame(name, H, W, layout, sample_bytes)) return e;
+    SSM_REQUIRE(K >= 0 && K <= 64, "%s: K=%d outside 0..64", name, K);
+    const YuvPlanes pl = yuv_planes(H, W, layout);
+    const long long fb = pl.frame() * sample_bytes, outs = (long long)N * T, mb = 2 * pl.luma();
+    const PairEntry k = {name, "frame", fb};
+    SSM_REQUIRE(N == 1 || (std::llabs(stride_a) >= fb && std::llabs(stride_b) >= fb), "%s: strides %lld (a), %lld (b) shorter than the frame's %lld bytes",
+                name, stride_a, stride_b, fb);
+    SSM_REQUIRE(outs == 1 || std::llabs(stride_out) >= fb, "%s: stride %lld (out) shorter than the frame's %lld bytes", name, stride_out, fb);
+    SSM_REQUIRE(N == 1 || std::llabs(stride_mask) >= mb, "%s: stride %lld (mask) shorter than a pair's two planes, %lld bytes", name, stride_mask, mb);
+    if (sample_bytes == 2) {
+        const auto odd = [](const void *p) { return reinterpret_cast<size_t>(p) % 2 != 0; };
+        SSM_REQUIRE(!odd(a) && !odd(b) && !odd(out), "%s: a payload of 2-byte samples (a, b or out) is not 2-byte aligned", name);
+        SSM_REQUIRE(stride_a % 2 == 0 && stride_b % 2 == 0 && stride_out % 2 == 0, "%s: strides %lld (a), %lld (b), %lld (out) of 2-byte samples must be even",
+                    name, stride_a, stride_b, stride_out);
+    }
+    long long o0, o1, a0, a1, b0, b1, m0, m1;
+    rows_range(out, stride_out, outs, fb, &o0, &o1);
+    rows_range(a, stride_a, N, fb, &a0, &a1);
+    rows_range(b, stride_b, N, fb, &b0, &b1);
+    rows_range(mask, stride_mask, N, mb, &m0, &m1);
+    SSM_REQUIRE((a1 <= o0 || o1 <= a0) && (b1 <= o0 || o1 <= b0) && (m1 <= o0 || o1 <= m0), "%s: out overlaps a, b or mask", name);
+    SSM_REQUIRE(reinterpret_cast<size_t>(counts) % 8 == 0, "%s: counts is not 8-byte aligned", name);
+    const long long nbx = W >> 3, blocks = nbx * (H >> 3), strip = PASTE_BLOCKS * PASTE_STEPS, groups = (blocks + strip - 1) / strip;
+    if (const int e = grid_fits(k, groups)) return e;
+    if (const int e = clear_sums(name, counts, (size_t)N, stream)) return e;
+    if (blocks == 0) return SSM_OK;          // a frame without a block: the cleared counts are the result, no output is touched
+    const unsigned char *pa = static_cast<const unsigned char *>(a), *pb = static_cast<const unsigned char *>(b);
+    with_sample(sample_bytes, [&](auto s) {
+        with_layout(layout, [&](auto lay) {
+            SSM_LAUNCH((flow_paste_kernel<decltype(s), decltype(lay)::value>), dim3((unsigned)groups, N), dim3(LANES), 0, (hipStream_t)stream, pa, pb,
+                       stride_a, stride_b, static_cast<unsigned char *>(out), stride_out, T, split, W, pl.cw, pl.luma(), pl.chroma(), (unsigned)nbx,
+                       (unsigned)blocks, mask, stride_mask, (unsigned)K, counts);
+        });
+    });
+    return ssm::check_launch("ssm_flow_paste_fwd");
 }
 
 // ---- interlaced clips -------------------------------------------------------------------------------------------------------------------

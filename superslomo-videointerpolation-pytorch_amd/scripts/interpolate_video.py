@@ -133,6 +133,17 @@ as most later work uses them: a convention, not backed by a measurement here; th
 this repository a score says nothing about quality.  It goes with --upsample_rate, --slowmo, --fps, --speed, --scene_cut, --static,
 --active, --matrix, --range and --detelecine; not with --shutter, --deinterlace, --dedup, --flow_scale other than 1, --tile or a
 recurrent model.
+
+--flow_blocks K (with --flow_check): the check's fallback per 8 x 8 block instead of per pair.  The blocks are those of --static.  Where
+more than K of a block's 64 luma pixels are inconsistent in at least one direction, every frame synthesised between the pair carries the
+NEARER input frame's samples of that block, luma and chroma - the left frame's below t = 1/2, the right one's from there on (decided and
+pasted on the GPU, ssm_flow_paste_fwd, behind the colour conversion of every pass and ahead of --static's paste).  K = 64 fails nothing
+and is the run without it, byte for byte; K = 0 fails every block with one inconsistent pixel; there is no default K.  --log gets one
+line with the pairs, the blocks replaced of all and the largest and smallest share per pair, and one line per pair in which every block
+failed.  --flow_check without T and --flow_blocks is the report plus the per-block fallback; with T a pair that reaches it is still
+replaced whole.  Not claimed: the seams between pasted and synthesised blocks are not smoothed, a block from the nearer frame inside a
+moving region steps rather than moves, and with the synthetic weights of this repository nothing can be said about quality.  Not with
+--active: chain two runs.
 """
 import argparse
 import configparser
@@ -235,11 +246,20 @@ def getargs(argv=None):
                         help="Score every pair's two flows against each other on the GPU (forward-backward consistency) and log the scores. "
                              "With T, a decimal or a fraction: a pair whose share of inconsistent pixels reaches T gets copies of its input "
                              "frames, like a scene cut. ALPHA:BETA default to 0.01:0.5, a convention of the literature; no default T.")
+    parser.add_argument("--flow_blocks", type=_named(lambda text: V.parse_flow_blocks(text, "--flow_blocks")), default=None, metavar="K",
+                        help="With --flow_check: fall back per 8x8 block instead of per pair. A block of a synthesised frame in which more "
+                             "than K of the 64 luma pixels are inconsistent in at least one direction takes the nearer input frame's "
+                             "samples. 0 .. 64; 64 changes nothing. No default value: off unless given. Not together with --active.")
     args = parser.parse_args(argv)
     refusal = V.flag_refusal(dict(vars(args), target_rate=args.fps,
                                   shutter_window=None if args.shutter_window[0] == "box" else V.window_name(args.shutter_window)))
     if refusal is not None:
         parser.error(refusal)
+    if args.flow_blocks is not None and args.flow_check is None:          # a sub-option of --flow_check: after the table has spoken
+        parser.error("--flow_blocks is --flow_check's per-block fallback: it needs --flow_check")
+    if args.flow_blocks is not None and args.active is not None:
+        parser.error("--flow_blocks does not go together with --active: the blocks of the per-block fallback are the whole frame's, not a "
+                     "cut window's; chain two runs")
     if args.dedup is not None and args.upsample_rate is not None and args.upsample_rate < 1:
         parser.error("--upsample_rate must be at least 1 with --dedup (got %d)" % args.upsample_rate)
     if args.shutter is not None and args.shutter_samples < 1:
@@ -282,6 +302,21 @@ def flow_check_lines(checks, failed, option):
     return lines
 
 
+def flow_blocks_lines(repaired, k):
+    """What --log gets of a run with --flow_blocks: `repaired` = [(i, failed blocks, blocks)] of the pairs that got outputs.  One summary
+    line, and one line for every pair in which every block failed."""
+    if not repaired:
+        return ["flow blocks: K = %d, no pair got a synthesised frame" % k]
+    failed, of = sum(f for _, f, _ in repaired), sum(b for _, _, b in repaired)
+    if of == 0:
+        return ["flow blocks: K = %d, %d pairs, the frame has no 8 x 8 block: nothing is replaced" % (k, len(repaired))]
+    shares = [f / b for _, f, b in repaired]
+    lines = ["flow blocks: K = %d, %d pairs, %d of %d blocks replaced (%.2f%%), per pair at most %.2f%% and at least %.2f%%"
+             % (k, len(repaired), failed, of, 100.0 * failed / of, 100.0 * max(shares), 100.0 * min(shares))]
+    lines += ["flow blocks: every block failed between input frames %d and %d" % (i, i + 1) for i, f, b in repaired if f == b]
+    return lines
+
+
 def main(argv=None, model=None):
     args = getargs(argv)
     config = configparser.RawConfigParser()
@@ -298,7 +333,8 @@ def main(argv=None, model=None):
                              shutter_light=args.shutter_light, shutter_window=args.shutter_window, deinterlace=args.deinterlace, dedup=args.dedup, dedup_max=args.dedup_max,
                              active=args.active, active_probe=args.active_probe, field_probe=args.field_probe, static=args.static,
                              flow_check=None if args.flow_check is None else (True if args.flow_check[0] is None else args.flow_check[0]),
-                             flow_alpha=args.flow_check and args.flow_check[1], flow_beta=args.flow_check and args.flow_check[2])
+                             flow_alpha=args.flow_check and args.flow_check[1], flow_beta=args.flow_check and args.flow_check[2],
+                             flow_blocks=args.flow_blocks)
     with V.Y4MReader(args.input, extended=True, interlaced=args.deinterlace is not None or args.detelecine) as reader:
         if args.detelecine:
             log.info("[%s] detelecine: %d:%d frames/s in, film at %d:%d", args.expt, *reader.rate, *V.detelecine_rate(reader.rate))
@@ -361,6 +397,9 @@ def main(argv=None, model=None):
             log.info("[%s] %s", args.expt, line)
     if args.flow_check is not None:
         for line in flow_check_lines(vi.flow_checks, vi.flow_failed, vi.flow_check):
+            log.info("[%s] %s", args.expt, line)
+    if args.flow_blocks is not None:
+        for line in flow_blocks_lines(vi.flow_repaired, args.flow_blocks):
             log.info("[%s] %s", args.expt, line)
     for i, score in vi.cuts:
         log.info("[%s] scene cut between input frames %d and %d: score %s = %.6f (threshold %s)", args.expt, i, i + 1, score, float(score),

@@ -187,7 +187,8 @@ def flow_consistency_host(flow4, top, left, H, W, alpha=FLOW_ALPHA, beta=FLOW_BE
 def flow_consistency(flow, h, w, top=0, left=0, alpha=FLOW_ALPHA, beta=FLOW_BETA, want_mask=False, out=None, workspace=None):
     """ssm_flow_consistency_fwd on the h x w crop at (top, left) of a [N,4,*,*] flow - a float32 device tensor with unit x-stride, or the
     4-channel hipbind.Planes stage 1 leaves (FullModel.estimate_flow(..., want_planes=True), PairEngine.s1.t["out"]) -> float64 [N,2,4]
-    on the device (into `out` if given), FlowCheck.of(row) on the host; with want_mask (record, uint8 [N,2,h,w] mask).  workspace: a
+    on the device (into `out` if given), FlowCheck.of(row) on the host; with want_mask (True, or the caller's own contiguous uint8
+    [N,2,h,w] device tensor to write it into) (record, uint8 [N,2,h,w] mask).  workspace: a
     uint8 device tensor of ssm_flow_consistency_workspace_bytes(N, h, w) bytes at least, the caller's (a loop that allocates nothing);
     None: made here.  Launched on the current stream; no synchronisation."""
     if isinstance(flow, hb.Planes):
@@ -211,10 +212,14 @@ def flow_consistency(flow, h, w, top=0, left=0, alpha=FLOW_ALPHA, beta=FLOW_BETA
         if out is None:
             out = torch.empty(n, 2, 4, dtype=torch.float64, device=dev)
         assert out.is_cuda and out.dtype == torch.float64 and tuple(out.shape) == (n, 2, 4) and out.is_contiguous()
-        mask = torch.empty(n, 2, h, w, dtype=torch.uint8, device=dev) if want_mask else None
+        if isinstance(want_mask, torch.Tensor):          # the caller's own mask, as `out` and `workspace` are the caller's
+            mask = want_mask
+            assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (n, 2, h, w) and mask.is_contiguous()
+        else:
+            mask = torch.empty(n, 2, h, w, dtype=torch.uint8, device=dev) if want_mask else None
         hb.check(lib.ssm_flow_consistency_fwd(view, n, h, w, top, left, float(alpha), float(beta), ws.data_ptr(), out.data_ptr(),
                                               None if mask is None else mask.data_ptr(), hb.stream_ptr()))
-    return (out, mask) if want_mask else out
+    return (out, mask) if mask is not None else out
 
 
 def parse_flow_check(value, alpha=None, beta=None):

@@ -66,6 +66,10 @@
   static_paste /          on an 8 x 8 block - luma and the chroma under it, sum of |difference| at most `lo` - every frame between them carries the
   parse_static            left frame's samples of that block, by numpy and by ssm_static_paste_fwd on the pass's stream; the number of such
                           blocks per pair - VideoInterpolator(static=): the fixed grid and the timeline, every other mode unchanged
+  flow_paste_host /       the flow check's per-block fallback: where more than K of an 8 x 8 block's 64 luma pixels are inconsistent in at least
+  flow_paste /            one direction of a pair's mask (flow_eval.flow_consistency), every frame between the pair carries the NEARER frame's
+  parse_flow_blocks       samples of that block, by numpy and by ssm_flow_paste_fwd on the pass's stream; the number of such blocks per pair -
+                          VideoInterpolator(flow_check=, flow_blocks=): the fixed grid and the timeline, every other mode unchanged
   (ssm_amd/video_score.py) hold-out scoring: the clip against its own held-out frames, plane_sse / HoldOutScorer on this loop's ring, Clip and
                           buffers; the PSNR of what VideoInterpolator(upsample_rate=hold) would write - this module is unchanged by it
 
@@ -1948,6 +1952,99 @@ def static_paste(payload_a, payload_b, outputs, h, w, siting, bits=8, lo=0, coun
     return counts
 
 
+# ---- the flow check's per-block fallback -------------------------------------------------------------------------------------------------
+# The definition is in include/ssm_hip.h and DESIGN 3.12: the blocks are static_blocks'; a block fails in a pair iff more than K of its 64
+# luma positions are inconsistent in at least one direction of the pair's mask (ssm_flow_consistency_fwd), and an output between the two
+# frames then carries the NEARER frame's samples of the block.  K has no default.
+FLOW_BLOCKS_MAX = 64               # a block has 64 luma positions: K = 64 fails nothing
+
+
+def parse_flow_blocks(value, spelt="flow_blocks"):
+    """The K of the per-block fallback, a whole number in 0 .. 64, as an int or a command line's text -> int.  Anything else is a
+    ValueError naming the value."""
+    text = "%s, the most inconsistent pixels of an 8 x 8 block that still passes, is a whole number in 0 .. 64 (got %r)" % (spelt, value)
+    try:
+        if isinstance(value, bool) or (not isinstance(value, str) and int(value) != value):
+            raise ValueError
+        k = int(value.strip() if isinstance(value, str) else value)
+    except (ValueError, TypeError, OverflowError):
+        raise ValueError(text) from None
+    if not 0 <= k <= FLOW_BLOCKS_MAX:
+        raise ValueError(text)
+    return k
+
+
+def fixed_split(rate):
+    """Of the upsample_rate - 1 outputs of a pair on the fixed grid, t = (j + 1) / rate, the number below 1/2: they take the left frame."""
+    return sum(1 for j in range(rate - 1) if 2 * (j + 1) < rate)
+
+
+def times_split(times):
+    """The same for a pair's exact times (Fractions, ascending - asserted: the outputs below 1/2 are then the first rows)."""
+    times = list(times)
+    assert all(x < y for x, y in zip(times, times[1:])), "a pair's times ascend in its output rows"
+    return sum(1 for t in times if t < Fraction(1, 2))
+
+
+def flow_block_counts_host(mask, h, w):
+    """n of every block: mask [N, 2, h, w] uint8 -> int64 [N, h >> 3, w >> 3], the luma positions with bit 0 of mask[0] | mask[1] set."""
+    mask = np.asarray(mask)
+    assert mask.dtype == np.uint8 and mask.ndim == 4 and mask.shape[1:] == (2, h, w), "mask is [N, 2, h, w] uint8"
+    by, bx = h >> 3, w >> 3
+    bad = ((mask[:, 0] | mask[:, 1]) & 1)[:, :8 * by, :8 * bx].astype(np.int64)
+    return bad.reshape(mask.shape[0], by, 8, bx, 8).sum(axis=(2, 4))
+
+
+def flow_paste_host(outputs, a, b, mask, h, w, siting, bits=8, k=FLOW_BLOCKS_MAX, split=0):
+    """Yardstick of ssm_flow_paste_fwd: outputs [N, T, at least frame_bytes] uint8 (numpy), the T frames between the payloads a[n] and
+    b[n] ([N, at least frame_bytes] uint8), mask [N, 2, h, w] uint8 as flow_consistency_host writes it -> (a copy of `outputs` in which
+    the samples of every block that fails in pair n - more than k of its 64 luma positions have bit 0 of mask[n, 0] | mask[n, 1] set -
+    are a[n]'s in the outputs j < split and b[n]'s in the outputs j >= split, uint64 [N]: the failed blocks of every pair)."""
+    k, split, fb = int(k), int(split), frame_bytes(h, w, siting, bits)
+    outputs, a, b = (np.asarray(x) for x in (outputs, a, b))
+    assert outputs.dtype == np.uint8 and outputs.ndim == 3 and outputs.shape[2] >= fb, "outputs are [N, T, at least frame_bytes] uint8"
+    n, t = outputs.shape[:2]
+    assert 0 <= k <= FLOW_BLOCKS_MAX and 0 <= split <= t, "k in 0 .. 64, split in 0 .. T"
+    for p in (a, b):
+        assert p.dtype == np.uint8 and p.shape == (n, p.shape[1]) and p.shape[1] >= fb, "payloads are [N, at least frame_bytes] uint8"
+    res, counts = outputs.copy(), np.zeros(n, np.uint64)
+    by, bx = h >> 3, w >> 3
+    if not (by and bx and n and t):
+        return res, counts
+    fail = flow_block_counts_host(np.asarray(mask)[:n], h, w) > k          # [N, by, bx]
+    counts[:] = fail.reshape(n, -1).sum(axis=1)
+    pa, pb = (split_planes(np.ascontiguousarray(x[:, :fb]), h, w, siting, bits) for x in (a, b))
+    cr, cc = _chroma_block(siting)
+    frames = np.ascontiguousarray(res[:, :, :fb]).reshape(n * t, fb)
+    for plane, sa, sb, (rr, rc) in zip(split_planes(frames, h, w, siting, bits), pa, pb, ((8, 8), (cr, cc), (cr, cc))):
+        where = np.repeat(np.repeat(fail, rr, axis=1), rc, axis=2)[:, None]          # [N, 1, rr by, rc bx]
+        dst = plane.reshape((n, t) + plane.shape[1:])[:, :, :rr * by, :rc * bx]
+        np.copyto(dst[:, :split], sa[:, None, :rr * by, :rc * bx], where=where)
+        np.copyto(dst[:, split:], sb[:, None, :rr * by, :rc * bx], where=where)
+    res[:, :, :fb] = frames.reshape(n, t, fb)
+    return res, counts
+
+
+def flow_paste(payload_a, payload_b, outputs, mask, h, w, siting, bits, k, split, counts=None):
+    """ssm_flow_paste_fwd on payloads: a, b [N, at least frame_bytes] uint8 device tensors (unit stride within a row, any row stride:
+    frames n and n + 1 of one buffer are fine), outputs [N * T, at least frame_bytes], the T frames of pair n in rows n T .. n T + T - 1,
+    changed in place, and mask, uint8 [N, 2, h, w] on the device with dense planes (flow_consistency(..., want_mask=True)): the samples
+    of every block that fails in pair n become a[n]'s in its outputs j < split and b[n]'s from there on.  -> int64 [N] on the device (into
+    `counts` if given): the failed blocks of every pair.  Queued on the current stream."""
+    fb = frame_bytes(h, w, siting, bits)
+    n, counts, sa, sb_stride = _pair_operands(payload_a, payload_b, fb, "frame_bytes", counts, ())
+    assert outputs.is_cuda and outputs.dtype == torch.uint8 and outputs.dim() == 2 and outputs.shape[1] >= fb and outputs.device == payload_a.device \
+        and (outputs.shape[1] == 1 or outputs.stride(1) == 1), "outputs must be [N * T, at least frame_bytes] uint8 on the payloads' device"
+    assert outputs.shape[0] >= n and outputs.shape[0] % n == 0, "outputs hold T rows per pair"
+    assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (n, 2, h, w) and mask.device == payload_a.device \
+        and mask[0].is_contiguous(), "mask must be [N, 2, h, w] uint8 on the payloads' device, a pair's two planes dense"
+    t = outputs.shape[0] // n
+    hb.check(hb.load().ssm_flow_paste_fwd(payload_a.data_ptr(), payload_b.data_ptr(), sa, sb_stride, outputs.data_ptr(),
+                                          outputs.stride(0) if n * t > 1 else 0, n, t, int(split), h, w, siting, sample_bytes(bits),
+                                          mask.data_ptr(), mask.stride(0) if n > 1 else 0, int(k), counts.data_ptr(), hb.stream_ptr()))
+    return counts
+
+
 # ---- output order -------------------------------------------------------------------------------------------------------------------
 def pass_order(valid, nt):
     """Write order of one pass of `valid` pairs with nt interpolated frames each: ("interp", row of the pass's output buffer) for the
@@ -2654,9 +2751,14 @@ class PairOptions:
     flow_check = (T or None, alpha, beta): check_flow() scores the pass's pairs on the engine's own stage-1 planes behind the engine's run
     (ssm_flow_consistency_fwd), the eight words per pair go back to the ring slot like the block counts, and the writer thread notes
     every pair in the log's `flow_checks` and lets a pair with score >= T fall back like a cut pair (`flow_failed`).  It needs no row 0.
+    flow_blocks = K (the flow check's per-block fallback): check_flow() also asks for the pairs' masks, one device mask [pairs, 2, h, w]
+    per stream, and paste_flow() - behind the egress, ahead of paste_static() and of the copies to the host - lets ssm_flow_paste_fwd put
+    the nearer frame's samples into every block with more than K inconsistent pixels; the failed blocks per pair go back to the ring
+    slot like the static counts and the writer thread notes them in the log's `flow_repaired`.  It reads the pairs' payloads, so it
+    needs row 0 as static blocks do.
     log: the VideoInterpolator whose `cuts` and `static` take the notes.
 
-    Buffers (buffers()).  With scene cuts or static blocks a stream's payload buffer has `lead` = 1 row in front of the pass's frames.  A pass
+    Buffers (buffers()).  With scene cuts, static blocks or flow_blocks a stream's payload buffer has `lead` = 1 row in front of the pass's frames.  A pass
     names its pairs by rows of that buffer - pairs(k, lefts, rights): the fixed grid's are rows 0 .. pb - 1 against 1 .. pb, the timeline's
     whatever its planner kept - and row 0 stands for the right frame of the pair that ran last in the pass before, the left frame of this
     pass's first pair unless that pair brought its own.  The luma sums and the block counts of a pass sit per stream on the device and per
@@ -2669,8 +2771,10 @@ class PairOptions:
       record - pairs() copies the Y plane of the pass's last right frame into row 0 of the NEXT stream's buffer.  The pass that reads the
       row waits for that `ingested` before it ingests; the pass that read the row before, on that same next stream, recorded its own
       `ingested` - behind its calls - earlier in the chain of waits that this pass stands behind.  The fixed grid seeds it from frame 0.
-      Static blocks FETCH it (and with both options the fetched row serves the luma sums too): ssm_static_paste_fwd reads a pair's
-      payloads behind the egress, long after the pass has recorded `ingested`, so no other stream may write the row.  carry_in() copies
+      Static blocks and flow_blocks FETCH it (and with scene cuts too the fetched row serves the luma sums as well): ssm_static_paste_fwd
+      and ssm_flow_paste_fwd read a pair's payloads behind the egress, long after the pass has recorded `ingested`, so no other stream
+      may write the row.  Both pastes run on the pass's own stream and only read dev_in: the flow paste adds a reader of the row, at the
+      same place in the stream's order as the static paste's, and no writer - so what makes the fetch safe for one makes it safe for both.  carry_in() copies
       the whole frame on the pass's own stream from row `last_right` of the stream before - behind a wait for that stream's `ingested`,
       ahead of the pass's own uploads; with one stream the source is the stream's own row, read before the uploads overwrite it.  The source
       row is next written by the upload of pass j + n - 1, which stands behind a chain of waits that ends at this pass's `ingested`,
@@ -2683,11 +2787,13 @@ class PairOptions:
     the end `carried`, the writer thread's copy of the frame that row 0 stands for, takes the last pair's right frame: its ring slot is
     free by the time the next pass's rows are written."""
 
-    def __init__(self, log, clip, scene_cut=None, static=None, flow_check=None):
-        self.log, self.clip, self.static, self.flow = log, clip, static, flow_check
+    def __init__(self, log, clip, scene_cut=None, static=None, flow_check=None, flow_blocks=None):
+        self.log, self.clip, self.static, self.flow, self.flow_blocks = log, clip, static, flow_check, flow_blocks
+        assert flow_blocks is None or flow_check is not None, "flow_blocks is the flow check's"
+        self.fetch = static is not None or flow_blocks is not None          # a paste behind the egress reads the pair's payloads: row 0 is fetched
         self.cuts = None if scene_cut is None else SceneCuts(scene_cut)
         self.pixels, self.blocks = clip.h * clip.w, static_blocks(clip.h, clip.w)
-        self.lead = 0 if self.cuts is None and static is None else 1
+        self.lead = 0 if self.cuts is None and not self.fetch else 1
         # the writer thread looks at a pair's input frames
         self.near = self.cuts is not None or clip.window is not None or (flow_check is not None and flow_check[0] is not None)
         self.carried = np.empty(clip.fb, np.uint8) if self.near else None
@@ -2716,6 +2822,10 @@ class PairOptions:
             self.np_flow = [t.numpy() for t in self.host_flow]
             nbytes = hb.load().ssm_flow_consistency_workspace_bytes(pairs, clip.h, clip.w)
             self.flow_ws = [torch.empty(nbytes, dtype=torch.uint8, device=clip.dev) for _ in range(n)]
+        self.dev_mask = None
+        if self.flow_blocks is not None:
+            self.dev_mask = [torch.empty(pairs, 2, clip.h, clip.w, dtype=torch.uint8, device=clip.dev) for _ in range(n)]
+            self.dev_failed, self.host_failed, self.np_failed = words()
         return sb
 
     def seed(self, frame, k, row, fetch_row):
@@ -2724,7 +2834,7 @@ class PairOptions:
         or forwarded."""
         if self.carried is not None:
             self.carried[:] = frame
-        if self.static is not None:
+        if self.fetch:
             if fetch_row != row:
                 self.dev_in[k][fetch_row].copy_(self.dev_in[k][row])
             self.last_right = fetch_row
@@ -2733,7 +2843,7 @@ class PairOptions:
 
     def carry_in(self, st, k, kprev, waited=False):
         """Ahead of the pass's uploads, the fetch of row 0; waited: the stream stands behind ingested[kprev] already."""
-        if self.static is not None:
+        if self.fetch:
             if not waited:
                 st.wait_event(self.ingested[kprev])
             self.dev_in[k][0].copy_(self.dev_in[kprev][self.last_right])
@@ -2748,7 +2858,7 @@ class PairOptions:
                 da, db = (lefts[p + 1] - lefts[p], rights[p + 1] - rights[p]) if m > 1 else (1, 1)
                 luma_sad(d[lefts[p]:lefts[p] + (m - 1) * da + 1:da], d[rights[p]:rights[p] + (m - 1) * db + 1:db], self.clip.h, self.clip.w,
                          out=self.dev_sums[k][p:p + m])
-            if self.static is None:
+            if not self.fetch:
                 self.dev_in[(k + 1) % self.n][0, :self.pixels].copy_(d[rights[-1], :self.pixels])
 
     def paste_static(self, r, k, groups):
@@ -2761,6 +2871,18 @@ class PairOptions:
                              clip.bits, self.static, counts=self.dev_counts[k][p:p + m])
             self.host_counts[r].copy_(self.dev_counts[k], non_blocking=True)
 
+    def paste_flow(self, r, k, groups):
+        """Behind the egress, ahead of paste_static and of the D2H copies of the frames: one ssm_flow_paste_fwd call per group (first
+        pair, pairs whose rows follow one another, their outputs [pairs * T, frame bytes], the outputs of a pair that take the left
+        frame) on the masks check_flow left, then the counts' way back to ring slot r.  With static too the static paste comes last:
+        a static block's samples are the left frame's."""
+        if self.flow_blocks is not None:
+            clip, d = self.clip, self.dev_in[k]
+            for p, m, outputs, split in groups:
+                flow_paste(d[self.lefts[p]:self.lefts[p] + m], d[self.rights[p]:self.rights[p] + m], outputs, self.dev_mask[k][p:p + m],
+                           clip.h, clip.w, clip.siting, clip.bits, self.flow_blocks, split, counts=self.dev_failed[k][p:p + m])
+            self.host_failed[r].copy_(self.dev_failed[k], non_blocking=True)
+
     def check_flow(self, r, k, flow4):
         """Behind the engine's run and ahead of the D2H copies of the frames: one ssm_flow_consistency_fwd call over the pass's pairs on
         flow4, the four planes F01 | F10 where the engine's stage 1 left them (PairEngine.s1.t["out"]), on the clip's picture inside the
@@ -2768,7 +2890,8 @@ class PairOptions:
         if self.flow is not None:
             from .flow_eval import flow_consistency
             clip, (_, alpha, beta) = self.clip, self.flow
-            flow_consistency(flow4, clip.h, clip.w, *clip.at, alpha, beta, out=self.dev_flow[k], workspace=self.flow_ws[k])
+            flow_consistency(flow4, clip.h, clip.w, *clip.at, alpha, beta, out=self.dev_flow[k], workspace=self.flow_ws[k],
+                             want_mask=False if self.dev_mask is None else self.dev_mask[k])
             self.host_flow[r].copy_(self.dev_flow[k], non_blocking=True)
 
     def download(self, r, k):
@@ -2786,13 +2909,16 @@ class PairOptions:
         pairs, at = near() if self.near else ((), [None] * len(rows))
         return functools.partial(self.written, list(index), self.np_sums[r] if self.cuts is not None else None,
                                  self.np_counts[r] if self.static is not None else None, pairs, list(zip(rows, at)),
-                                 self.np_flow[r] if self.flow is not None else None)
+                                 self.np_flow[r] if self.flow is not None else None,
+                                 self.np_failed[r] if self.flow_blocks is not None else None)
 
-    def written(self, index, sums, counts, pairs, order, flows=None):
+    def written(self, index, sums, counts, pairs, order, flows=None, failed=None):
         """The generator behind rows(); sums, counts, flows: the pass's words in its ring slot, None with the option off.  A pair's
         synthesised frames fall back to the nearer input frame if it is a cut or fails the flow check."""
         if counts is not None:
             self.log.static.extend((i, int(counts[p]), self.blocks) for p, i in enumerate(index))
+        if failed is not None:
+            self.log.flow_repaired.extend((i, int(failed[p]), self.blocks) for p, i in enumerate(index))
         verdict = [False] * len(index)
         if sums is not None:
             for p, i in enumerate(index):
@@ -2922,7 +3048,8 @@ class VideoInterpolator:
     def __init__(self, model, cfg, upsample_rate=None, n_streams=2, pairs_per_batch=1, matrix=None, color_range=None, flow_scale=1,
                  tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8, scene_cut=None,
                  shutter_light="coded", deinterlace=None, dedup=None, dedup_max=DEDUP_MAX, active=None, active_probe=ACTIVE_PROBE,
-                 shutter_window="box", field_probe=None, static=None, flow_check=None, flow_alpha=None, flow_beta=None):
+                 shutter_window="box", field_probe=None, static=None, flow_check=None, flow_alpha=None, flow_beta=None,
+                 flow_blocks=None):
         """target_rate = (num, den) and / or speed (a Fraction, or what Fraction() takes; 1/4 is four times slower): the output follows
         Timeline(speed * input rate / target_rate) instead of the fixed grid of upsample_rate, which is then not used (see
         _run_timeline); with both None nothing changes.  flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
@@ -3018,6 +3145,17 @@ class VideoInterpolator:
         pair still runs on the GPU.  With this repository's synthetic weights a score says nothing about quality.  With scene_cut a pair
         falls back if it is a cut or fails the check.  Every format is taken.  None: every mode as it is, launch for launch - nothing
         is allocated or queued.
+        flow_blocks (K, a whole number in 0 .. 64; parse_flow_blocks; no default value), a sub-option of flow_check like dedup_max of
+        dedup: the per-block fallback.  Every pass then also takes the pairs' masks from the check and, behind the egress and ahead of
+        the copy to the host (and ahead of the static paste), ssm_flow_paste_fwd puts the NEARER input frame's samples - the left
+        frame's at t < 1/2, the right one's from there on - into every 8 x 8 block (static's blocks) of a synthesised frame in which
+        more than K of the 64 luma pixels are inconsistent in at least one direction (flow_paste_host is the definition).  K = 64 fails
+        nothing and is the run without it, byte for byte; K = 0 fails every block with one inconsistent pixel.  After run():
+        `flow_repaired` lists (i, failed blocks, blocks) of every pair (i, i + 1) that got outputs.  flow_check=True with flow_blocks is
+        the report plus the per-block fallback, no pair-level T; with a T a pair that reaches it - or, with scene_cut, a cut pair - is
+        still replaced whole.  Not claimed: K has no default; seams between pasted and synthesised blocks are not smoothed; a block from
+        the nearer frame inside a moving region steps rather than moves; with this repository's synthetic weights nothing can be said
+        about quality.  Not together with active (chain two runs).  None: the run with flow_check as it is, launch for launch.
         Which of these options do not go together, which need another, and what each refusal says is one table, OPTION_RULES (above
         the class; api_refusal asks it here, flag_refusal for the command line), not a list kept per option."""
         from .coarse import check_scale
@@ -3073,11 +3211,19 @@ class VideoInterpolator:
             tile=self.tile, recurrent=getattr(model, "recurrent", False)))
         if refusal is not None:          # every value has been through its own check: what is left is which options go together
             raise ValueError(refusal)
+        self.flow_blocks = None          # a sub-option of the flow check, not a row of the table: its own refusals, after the table's
+        if flow_blocks is not None:
+            if self.flow_check is None:
+                raise ValueError("flow_blocks is the flow check's per-block fallback: give flow_check, or leave it out")
+            if self.active_option is not None:
+                raise ValueError("flow_blocks together with active is not available: the blocks of the per-block fallback are the whole "
+                                 "frame's, not a cut window's; chain two runs")
+            self.flow_blocks = parse_flow_blocks(flow_blocks)
         self._new_log()
 
     def _new_log(self):
         """What a run reports (the constructor's docstring names each), empty: the state before a run and at the start of every run()."""
-        self.cuts, self.repeats, self.static, self.flow_checks, self.flow_failed = [], [], [], [], []
+        self.cuts, self.repeats, self.static, self.flow_checks, self.flow_failed, self.flow_repaired = [], [], [], [], [], []
         self.active, self.active_note, self.active_excess = None, None, []
 
     def canvas(self, h, w):
@@ -3223,8 +3369,8 @@ class VideoInterpolator:
         t_dev = torch.tensor(t_values(self.rate), dtype=torch.float32, device=dev)
         slots = ring_slots(depth, fb, pb, pb * nt, fb_out=clip.fb_out)
         np_in, np_out = slots.np_in, slots.np_out
-        opt = PairOptions(self, clip, self.scene_cut, self.static_lo, self.flow_check)
-        lead, lefts, rights = opt.lead, list(range(pb)), list(range(1, pb + 1))
+        opt = PairOptions(self, clip, self.scene_cut, self.static_lo, self.flow_check, self.flow_blocks)
+        lead, lefts, rights, split = opt.lead, list(range(pb)), list(range(1, pb + 1)), fixed_split(self.rate)
         _, dev_out, _, ingested, _ = opt.buffers(n, depth, pb, pb, pb * nt)
         planes = [torch.empty(pb + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [carried left frame | new frames]
         first = torch.empty(1, fb, dtype=torch.uint8).pin_memory()
@@ -3259,6 +3405,7 @@ class VideoInterpolator:
                 frames = pipe.engines[k].run(img6, t_dev, False)
                 opt.check_flow(r, k, pipe.engines[k].s1.t["out"] if opt.flow is not None else None)
                 clip.egress(frames, dev_out[k])
+                opt.paste_flow(r, k, [(0, pb, dev_out[k], split)])
                 opt.paste_static(r, k, [(0, pb, dev_out[k])])
                 slots.host_out[r].copy_(dev_out[k], non_blocking=True)
                 opt.download(r, k)
@@ -3413,7 +3560,7 @@ class VideoInterpolator:
         host_in, host_out, host_t, np_in, np_out, np_t, done = ring_slots(depth, fb, cap, pb * max(S, 1), pb * max(S, 1), fb_out=clip.fb_out)
         plan = PassPlanner(tl, pb, cap)
         if pipe is not None:
-            opt = PairOptions(self, clip, self.scene_cut, self.static_lo, self.flow_check)
+            opt = PairOptions(self, clip, self.scene_cut, self.static_lo, self.flow_check, self.flow_blocks)
             lead = opt.lead
             _, dev_out, dev_t, ingested, _ = opt.buffers(n, depth, pb, cap, pb * S, pb * S)
             planes = [torch.zeros(pb, 2, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [pair][left | right]
@@ -3447,12 +3594,16 @@ class VideoInterpolator:
                     spans = [(0, len(pairs) * S)]
                 else:
                     spans = [(p * S, len(ts)) for p, (_, _, ts) in enumerate(pairs)]
-                late = opt.static is not None          # the static blocks stand between the egress calls and the copies of what they made
+                late = opt.fetch          # the pasted blocks stand between the egress calls and the copies of what they made
                 for o, m in spans:
                     clip.egress(frames[o:o + m], dev_out[k][o:o + m])
                     if not late:
                         host_out[r][o:o + m].copy_(dev_out[k][o:o + m], non_blocking=True)
                 if late:
+                    if opt.flow_blocks is not None:          # exact times, as the writer thread's rule asks: t < 1/2 takes the left frame
+                        exact = [tl.times(i) for i in plan.closed_index]
+                        opt.paste_flow(r, k, [(p, 1, dev_out[k][p * S:p * S + len(ts)], times_split(exact[p][:len(ts)]))
+                                              for p, (_, _, ts) in enumerate(pairs)])
                     opt.paste_static(r, k, [(p, 1, dev_out[k][p * S:p * S + len(ts)]) for p, (_, _, ts) in enumerate(pairs)])
                     for o, m in spans:
                         host_out[r][o:o + m].copy_(dev_out[k][o:o + m], non_blocking=True)
