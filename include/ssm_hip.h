@@ -1162,6 +1162,41 @@ int ssm_flow_paste_fwd(const void *a, const void *b, long long stride_a, long lo
                        int split, int H, int W, int layout, int sample_bytes, const unsigned char *mask, long long stride_mask, int K,
                        unsigned long long *counts, void *stream);
 
+/* ---- the per-block fallback as a cross-fade, of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) ------
+ * Definition (ssm_amd.video.flow_mix_host is all of it in numpy and Python ints).  Inside a scene the nearer frame is the weakest fallback
+ * there is: at eight outputs a pair a failed block shows the left frame four times and the right frame three times - it stands still and
+ * then jumps while the picture around it moves.  A cross-fade of the two frames moves with it.  Everything below is in exact integers.
+ *   blocks, measure, test, count   those of ssm_flow_paste_fwd above, word for word: n(block) > K fails, counts[n] the failed blocks.
+ *   action    in output j of pair n every sample of a failed block, luma and chroma, is
+ *                 (a (den - k_j) + b k_j + (den >> 1)) / den,   k_j = num0 + j num_step,   integer division,
+ *             a and b the samples of a_n and b_n at its place: a (1 - t) + b t at the exact t_j = k_j / den, rounded half up.  Because it is
+ *             the exact rational rounded half up, the value does not depend on which fraction names t: 2/5 and 400/1000 give the same
+ *             bytes.  k_j = 0 gives a's samples, k_j = den gives b's.  16-bit words mix as words, all 16 bits; a mix of two codes <= 1023
+ *             is <= 1023.  Every other sample is what the run without the option writes.
+ *   NOT claimed: where the nearer frame steps, the cross-fade ghosts - both frames show through each other; which of the two looks better
+ *   is not known, and with this repository's synthetic weights nothing can be said about quality; K has no default; seams between mixed and
+ *   synthesised blocks are not smoothed.
+ * ssm_flow_mix_fwd: a, b, out, mask, the strides, N, T, the frame and K as for ssm_flow_paste_fwd.  den in 2..65535 and every k_j, j < T, in
+ * 0..den; the weights of output j are k_j and den - k_j, launch scalars: nothing is uploaded per call.  The numerator is at most
+ * 65535 * 65535 + 32767 < 2^32; the division is ssm_payload_mix_fwd's multiply-shift, exact for every 32-bit numerator, its constants
+ * computed on the host once per launch.  The outputs are read-modify-write: the only samples written are those of failed blocks; nothing
+ * outside the N T payloads is touched; a, b and mask are only read, and a and b may alias or overlap each other.
+ *     counts[n] = the number of failed blocks of pair n
+ * exact, N 64-bit words on the device, cleared by the entry itself on `stream` (a memset node ahead of the kernel).  A frame without blocks
+ * queues the clear alone.
+ *   The skeleton and the measure are ssm_flow_paste_fwd's: strips of 256 blocks, 32 at a time, 8 neighbouring lanes a block, lane r of them
+ *   luma row r and the chroma rows that fall to it; two 8-byte mask loads, OR, bit 0, pop-count, three cross-lane shuffles.  Where n > K
+ *   a lane loads its pieces of a AND of b once and, per output, forms the mixed pieces word by word and stores them, by the sibling's piece
+ *   rule (4-, 8- or 16-byte accesses where aligned, sample by sample where not).  ONE 64-bit vector atomicAdd per workgroup.  Vector loads,
+ *   vector stores and vector atomics only; no scratch, no floating point.  Reads 2 bytes of mask per luma sample and 2 sample_bytes per
+ *   sample of the failed blocks, writes T sample_bytes per sample of the failed ones.
+ * SSM_E_ARG (nothing is queued), each with its own message and in this order: null pointers; N, then T, outside 1..65535; den outside
+ * 2..65535; num0 or num0 + (T - 1) num_step outside 0..den (k_j is monotone in j: the two ends bound them all); then as
+ * ssm_flow_paste_fwd from H or W < 1 on. */
+int ssm_flow_mix_fwd(const void *a, const void *b, long long stride_a, long long stride_b, void *out, long long stride_out, int N, int T,
+                     int num0, int num_step, int den, int H, int W, int layout, int sample_bytes, const unsigned char *mask,
+                     long long stride_mask, int K, unsigned long long *counts, void *stream);
+
 /* ---- letterboxed clips of the streamed video loop (csrc/ssm_video.hip; beyond the reference's operator surface) --------------------------
  * Definition (ssm_amd.video: active_counts_host, ActiveArea, cut_window_host and paste_window_host are all of it in numpy and Python ints,
  * ActiveSource the streamed form).  A 2.39:1 picture inside a 16:9 frame leaves bars that hold, at most, a subtitle or a logo.

@@ -55,6 +55,9 @@
 //                            stored into the pair's outputs (a below `split`, b from there on); static_paste_kernel's strips, lanes and pieces
 //   payload_mix_kernel       hold-out scoring: the cross-fade (a (den - k) + b k + den / 2) / den of two payloads, the frame-blend baseline;
 //                            exact division by multiply-shift, the span walk's pieces with a 16-byte store in place of the sum
+//   flow_mix_kernel          the per-block fallback as a cross-fade, ssm_flow_mix_fwd: flow_paste_kernel's blocks, measure (flow_block_bad) and
+//                            count; where a block fails, its pieces of a AND of b loaded once and payload_mix_kernel's exact mix of them
+//                            (mix_word) stored into every output of the pair under that output's weights
 //   fields_split_kernel /    interlaced clips: N frames -> their 2N fields (even rows of every plane, odd rows), and N fields with
 //   fields_weave_kernel      N synthesised fields (or, fill = 1, with integer line averages of the kept field itself) -> N frames; bytes moved
 //                            as they stand, 16-byte pieces of a row where the addresses allow, one launch for the three planes
@@ -1303,6 +1306,20 @@ __global__ __launch_bounds__(LANES) void static_paste_kernel(const unsigned char
 //   paste   where n > K every lane loads its pieces of the side's payload - a if split > 0, then b if split < T, one side after the other
 //           through the same registers - and stores them into that side's outputs, by RowPiece's rule.  Nothing else is written.
 //   count   one flag per block (its lane 0) through workgroup_add: ONE 64-bit vector atomic per workgroup.
+// n of the block that the lane's 8 neighbours own, in all 8 of them (flow_paste_kernel, flow_mix_kernel): om is the lane's luma row in a
+// mask plane, direction 1 `luma` bytes on; a lane that is not live adds nothing.  Every lane of the wave takes part in the shuffles.
+__device__ __forceinline__ unsigned flow_block_bad(bool live, const unsigned char *pm, long long luma, long long om) {
+    unsigned bad = 0;
+    if (live) {
+        RowPiece<unsigned char, 2> m0, m1;
+        m0.load(pm + om), m1.load(pm + luma + om);
+        bad = (unsigned)__popc((m0.w[0] | m1.w[0]) & 0x01010101u) + (unsigned)__popc((m0.w[1] | m1.w[1]) & 0x01010101u);
+    }
+#pragma unroll
+    for (int s = 1; s < 8; s <<= 1) bad += __shfl_xor(bad, s);
+    return bad;
+}
+
 template <typename S, int L>          // the sample and the layout (LAY_*)
 __global__ __launch_bounds__(LANES) void flow_paste_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
                                                            unsigned char *out, long long stride_out, int T, int split, int W, int cw,
@@ -1320,11 +1337,10 @@ __global__ __launch_bounds__(LANES) void flow_paste_kernel(const unsigned char *
     for (int step = 0; step < PASTE_STEPS; ++step) {
         const unsigned blk = (blockIdx.x * (unsigned)PASTE_STEPS + step) * (unsigned)PASTE_BLOCKS + (threadIdx.x >> 3);
         const bool live = blk < blocks;          // the same in the 8 lanes of a block
-        long long oy = 0, oc[NC] = {};           // byte offsets of the lane's pieces in a payload
-        unsigned bad = 0;
+        long long om = 0, oy = 0, oc[NC] = {};   // the lane's luma row in a mask plane; byte offsets of its pieces in a payload
         if (live) {          // a block of the frame: its luma rows lie inside H x W, its chroma rows inside the chroma planes
             const unsigned by = blk / nbx, bx = blk - by * nbx;
-            const long long om = (long long)(8 * by + r) * W + 8 * bx;
+            om = (long long)(8 * by + r) * W + 8 * bx;
             oy = om * SB;
             const long long crow = L == LAY_420 ? 4 * by + (r & 3u) : 8 * by + r;
 #pragma unroll
@@ -1332,12 +1348,8 @@ __global__ __launch_bounds__(LANES) void flow_paste_kernel(const unsigned char *
                 const long long plane = L == LAY_420 ? (long long)(r >> 2) : (long long)i;
                 oc[i] = (luma + plane * chroma + crow * cw + (long long)(CS * bx)) * SB;
             }
-            RowPiece<unsigned char, 2> m0, m1;
-            m0.load(pm + om), m1.load(pm + luma + om);
-            bad = (unsigned)__popc((m0.w[0] | m1.w[0]) & 0x01010101u) + (unsigned)__popc((m0.w[1] | m1.w[1]) & 0x01010101u);
         }
-#pragma unroll
-        for (int s = 1; s < 8; s <<= 1) bad += __shfl_xor(bad, s);          // the block's n, in its 8 lanes
+        const unsigned bad = flow_block_bad(live, pm, luma, om);          // the block's n, in its 8 lanes
         const bool fail = live && bad > K;
         if (fail) {
             for (int side = 0; side < 2; ++side) {
@@ -1422,6 +1434,73 @@ __global__ __launch_bounds__(LANES) void payload_mix_kernel(const unsigned char 
                 if (o + i < samples) po[o + i] = (S)mix_one(pa[o + i], pb[o + i], wa, wb, d);
         }
     }
+}
+
+// ---- the flow check's per-block fallback as a cross-fade: a (1 - t) + b t where a pair's two flows contradict each other -----------------
+// The definition is in include/ssm_hip.h: blocks, n(block), the test n > K and counts[n] are flow_paste_kernel's; in output j of pair n
+// every sample of a failed block becomes (a (den - k_j) + b k_j + (den >> 1)) / den with k_j = num0 + j num_step - mix_one above, the exact
+// rational rounded half up, so the fraction that names t does not matter (ssm_flow_mix_fwd).  The skeleton is flow_paste_kernel's: strips
+// of PASTE_STEPS x PASTE_BLOCKS blocks, 8 neighbouring lanes a block, the measure through flow_block_bad.
+//   mix     where n > K every lane loads its pieces of a AND of b once; per output it forms the pieces word by word (mix_word, the weights
+//           two launch scalars and j) and stores them by RowPiece's rule.  Nothing else is written.  Integer multiplies only.
+//   count   one flag per block (its lane 0) through workgroup_add: ONE 64-bit vector atomic per workgroup.
+template <typename S, int K>
+__device__ __forceinline__ RowPiece<S, K> mix_piece(const RowPiece<S, K> &x, const RowPiece<S, K> &y, unsigned wa, unsigned wb, MixDivisor d) {
+    RowPiece<S, K> o;
+#pragma unroll
+    for (int i = 0; i < K; ++i) o.w[i] = mix_word<S>(x.w[i], y.w[i], wa, wb, d);
+    return o;
+}
+
+template <typename S, int L>          // the sample and the layout (LAY_*)
+__global__ __launch_bounds__(LANES) void flow_mix_kernel(const unsigned char *a, const unsigned char *b, long long stride_a, long long stride_b,
+                                                         unsigned char *out, long long stride_out, int T, int num0, int num_step, int den,
+                                                         MixDivisor d, int W, int cw, long long luma, long long chroma, unsigned nbx,
+                                                         unsigned blocks, const unsigned char *mask, long long stride_mask, unsigned K,
+                                                         unsigned long long *counts) {          // a, b may alias; luma, chroma in samples
+    constexpr int SB = (int)sizeof(S);
+    constexpr int CS = L == LAY_444 ? 8 : 4;                     // chroma samples under a block row
+    constexpr int KY = 8 * SB / 4, KC = CS * SB / 4;             // words of a luma piece, of a chroma piece
+    constexpr int NC = L == LAY_420 ? 1 : 2;                     // chroma pieces of a lane
+    const int n = blockIdx.y;
+    const unsigned r = threadIdx.x & 7u;
+    const unsigned char *pa = a + n * stride_a, *pb = b + n * stride_b;
+    const unsigned char *pm = mask + n * stride_mask;            // direction 0; direction 1 is `luma` bytes on
+    unsigned failed = 0;
+    for (int step = 0; step < PASTE_STEPS; ++step) {
+        const unsigned blk = (blockIdx.x * (unsigned)PASTE_STEPS + step) * (unsigned)PASTE_BLOCKS + (threadIdx.x >> 3);
+        const bool live = blk < blocks;          // the same in the 8 lanes of a block
+        long long om = 0, oy = 0, oc[NC] = {};   // the lane's luma row in a mask plane; byte offsets of its pieces in a payload
+        if (live) {          // a block of the frame: its luma rows lie inside H x W, its chroma rows inside the chroma planes
+            const unsigned by = blk / nbx, bx = blk - by * nbx;
+            om = (long long)(8 * by + r) * W + 8 * bx;
+            oy = om * SB;
+            const long long crow = L == LAY_420 ? 4 * by + (r & 3u) : 8 * by + r;
+#pragma unroll
+            for (int i = 0; i < NC; ++i) {
+                const long long plane = L == LAY_420 ? (long long)(r >> 2) : (long long)i;
+                oc[i] = (luma + plane * chroma + crow * cw + (long long)(CS * bx)) * SB;
+            }
+        }
+        const unsigned bad = flow_block_bad(live, pm, luma, om);          // the block's n, in its 8 lanes
+        const bool fail = live && bad > K;
+        if (fail) {
+            RowPiece<S, KY> ya, yb;
+            RowPiece<S, KC> ca[NC], cb[NC];
+            ya.load(pa + oy), yb.load(pb + oy);
+#pragma unroll
+            for (int i = 0; i < NC; ++i) ca[i].load(pa + oc[i]), cb[i].load(pb + oc[i]);
+            for (int j = 0; j < T; ++j) {
+                const unsigned wb = (unsigned)(num0 + j * num_step), wa = (unsigned)den - wb;
+                unsigned char *po = out + ((long long)n * T + j) * stride_out;
+                mix_piece(ya, yb, wa, wb, d).store(po + oy);
+#pragma unroll
+                for (int i = 0; i < NC; ++i) mix_piece(ca[i], cb[i], wa, wb, d).store(po + oc[i]);
+            }
+        }
+        failed += fail && r == 0 ? 1u : 0u;
+    }
+    workgroup_add(failed, &counts[n]);
 }
 
 // ---- interlaced clips: fields out of frames, frames out of fields ----------------------------------------------------------------------
@@ -2180,6 +2259,16 @@ static void rows_range(const void *p, long long stride, long long N, long long r
     *hi = base + (ext > 0 ? ext : 0) + row;
 }
 
+// the divisor of mix_one for den in 2..65535 (the header of payload_mix_kernel spells the construction)
+static MixDivisor mix_divisor(int den) {
+    int l = 0;
+    while ((1ll << l) < den) ++l;          // ceil(log2 den) >= 1
+    MixDivisor d;
+    d.m = (unsigned)((((1ull << l) - (unsigned long long)den) << 32) / (unsigned long long)den + 1ull);
+    d.shift = (unsigned)(l - 1), d.half = (unsigned)(den >> 1);
+    return d;
+}
+
 extern "C" int ssm_payload_mix_fwd(const void *a, const void *b, long long stride_a, long long stride_b, void *out, long long stride_out, int N,
                                    long long samples, int sample_bytes, int num0, int num_step, int den, void *stream) {
     if (const int e = pair_given("payload_mix", a, b, out, N)) return e;
@@ -2199,11 +2288,7 @@ extern "C" int ssm_payload_mix_fwd(const void *a, const void *b, long long strid
     SSM_REQUIRE((a1 <= o0 || o1 <= a0) && (b1 <= o0 || o1 <= b0), "payload_mix: out overlaps a or b");
     const long long span = SPAN_BYTES / sample_bytes, groups = (samples + span - 1) / span;
     if (const int e = grid_fits(k, groups)) return e;
-    int l = 0;
-    while ((1ll << l) < den) ++l;          // ceil(log2 den) >= 1
-    MixDivisor d;
-    d.m = (unsigned)((((1ull << l) - (unsigned long long)den) << 32) / (unsigned long long)den + 1ull);
-    d.shift = (unsigned)(l - 1), d.half = (unsigned)(den >> 1);
+    const MixDivisor d = mix_divisor(den);
     const unsigned char *pa = static_cast<const unsigned char *>(a), *pb = static_cast<const unsigned char *>(b);
     with_sample(sample_bytes, [&](auto s) {
         SSM_LAUNCH(payload_mix_kernel<decltype(s)>, dim3((unsigned)groups, N), dim3(LANES), 0, (hipStream_t)stream, pa, pb, stride_a, stride_b,
@@ -2255,16 +2340,24 @@ extern "C" int ssm_static_paste_fwd(const void *a, const void *b, long long stri
     return ssm::check_launch("ssm_static_paste_fwd");
 }
 
-// ssm_flow_paste_fwd refuses in the order of its header section - pointers, N and T, split, the frame, K, the strides of a and b, of out, of
-// the masks, 2-byte alignment, overlap, counts, the grid - and only then queues the clear and, for a frame that has blocks, the one launch.
-extern "C" int ssm_flow_paste_fwd(const void *a, const void *b, long long stride_a, long long stride_b, void *out, long long stride_out, int N,
-                                  int T, int split, int H, int W, int layout, int sample_bytes, const unsigned char *mask, long long stride_mask,
-                                  int K, unsigned long long *counts, void *stream) {
-    const char *name = "flow_paste";
+// ssm_flow_paste_fwd and ssm_flow_mix_fwd refuse in the order of their header sections - pointers, N and T, the entry's own scalars (split;
+// den, then the k_j), and from there on as one (flow_block_call): the frame, K, the strides of a and b, of out, of the masks, 2-byte
+// alignment, overlap, counts, the grid - and only then queue the clear and, for a frame that has blocks, the one launch.
+struct FlowBlockGrid {
+    YuvPlanes pl;
+    long long nbx, blocks, groups;          // blocks per row, blocks, strips of PASTE_BLOCKS x PASTE_STEPS of them
+};
+
+static int flow_block_given(const char *name, const void *a, const void *b, const void *out, const void *mask, const void *counts, int N, int T) {
     SSM_REQUIRE(a && b && out && mask && counts, "%s: null pointer", name);
     SSM_REQUIRE(N > 0 && N <= 65535, "%s: N=%d outside 1..65535", name, N);
     SSM_REQUIRE(T > 0 && T <= 65535, "%s: T=%d outside 1..65535", name, T);
-    SSM_REQUIRE(split >= 0 && split <= T, "%s: split=%d outside 0..T=%d", name, split, T);
+    return SSM_OK;
+}
+
+static int flow_block_call(const char *name, const void *a, const void *b, long long stride_a, long long stride_b, const void *out,
+                           long long stride_out, int N, int T, int H, int W, int layout, int sample_bytes, const unsigned char *mask,
+                           long long stride_mask, int K, const unsigned long long *counts, FlowBlockGrid *g) {
     if (const int e = check_frame(name, H, W, layout, sample_bytes)) return e;
     SSM_REQUIRE(K >= 0 && K <= 64, "%s: K=%d outside 0..64", name, K);
     const YuvPlanes pl = yuv_planes(H, W, layout);
@@ -2287,19 +2380,59 @@ extern "C" int ssm_flow_paste_fwd(const void *a, const void *b, long long stride
     rows_range(mask, stride_mask, N, mb, &m0, &m1);
     SSM_REQUIRE((a1 <= o0 || o1 <= a0) && (b1 <= o0 || o1 <= b0) && (m1 <= o0 || o1 <= m0), "%s: out overlaps a, b or mask", name);
     SSM_REQUIRE(reinterpret_cast<size_t>(counts) % 8 == 0, "%s: counts is not 8-byte aligned", name);
-    const long long nbx = W >> 3, blocks = nbx * (H >> 3), strip = PASTE_BLOCKS * PASTE_STEPS, groups = (blocks + strip - 1) / strip;
-    if (const int e = grid_fits(k, groups)) return e;
+    const long long nbx = W >> 3, blocks = nbx * (H >> 3), strip = PASTE_BLOCKS * PASTE_STEPS;
+    *g = {pl, nbx, blocks, (blocks + strip - 1) / strip};
+    return grid_fits(k, g->groups);
+}
+
+extern "C" int ssm_flow_paste_fwd(const void *a, const void *b, long long stride_a, long long stride_b, void *out, long long stride_out, int N,
+                                  int T, int split, int H, int W, int layout, int sample_bytes, const unsigned char *mask, long long stride_mask,
+                                  int K, unsigned long long *counts, void *stream) {
+    const char *name = "flow_paste";
+    if (const int e = flow_block_given(name, a, b, out, mask, counts, N, T)) return e;
+    SSM_REQUIRE(split >= 0 && split <= T, "%s: split=%d outside 0..T=%d", name, split, T);
+    FlowBlockGrid g;
+    if (const int e = flow_block_call(name, a, b, stride_a, stride_b, out, stride_out, N, T, H, W, layout, sample_bytes, mask, stride_mask, K,
+                                      counts, &g))
+        return e;
     if (const int e = clear_sums(name, counts, (size_t)N, stream)) return e;
-    if (blocks == 0) return SSM_OK;          // a frame without a block: the cleared counts are the result, no output is touched
+    if (g.blocks == 0) return SSM_OK;          // a frame without a block: the cleared counts are the result, no output is touched
     const unsigned char *pa = static_cast<const unsigned char *>(a), *pb = static_cast<const unsigned char *>(b);
     with_sample(sample_bytes, [&](auto s) {
         with_layout(layout, [&](auto lay) {
-            SSM_LAUNCH((flow_paste_kernel<decltype(s), decltype(lay)::value>), dim3((unsigned)groups, N), dim3(LANES), 0, (hipStream_t)stream, pa, pb,
-                       stride_a, stride_b, static_cast<unsigned char *>(out), stride_out, T, split, W, pl.cw, pl.luma(), pl.chroma(), (unsigned)nbx,
-                       (unsigned)blocks, mask, stride_mask, (unsigned)K, counts);
+            SSM_LAUNCH((flow_paste_kernel<decltype(s), decltype(lay)::value>), dim3((unsigned)g.groups, N), dim3(LANES), 0, (hipStream_t)stream, pa,
+                       pb, stride_a, stride_b, static_cast<unsigned char *>(out), stride_out, T, split, W, g.pl.cw, g.pl.luma(), g.pl.chroma(),
+                       (unsigned)g.nbx, (unsigned)g.blocks, mask, stride_mask, (unsigned)K, counts);
         });
     });
     return ssm::check_launch("ssm_flow_paste_fwd");
+}
+
+extern "C" int ssm_flow_mix_fwd(const void *a, const void *b, long long stride_a, long long stride_b, void *out, long long stride_out, int N,
+                                int T, int num0, int num_step, int den, int H, int W, int layout, int sample_bytes, const unsigned char *mask,
+                                long long stride_mask, int K, unsigned long long *counts, void *stream) {
+    const char *name = "flow_mix";
+    if (const int e = flow_block_given(name, a, b, out, mask, counts, N, T)) return e;
+    SSM_REQUIRE(den >= 2 && den <= 65535, "%s: den=%d outside 2..65535", name, den);
+    const long long k_last = (long long)num0 + (long long)(T - 1) * num_step;
+    SSM_REQUIRE(num0 >= 0 && num0 <= den && k_last >= 0 && k_last <= den, "%s: k = %d + j * %d leaves 0..den=%d within T=%d outputs", name, num0,
+                num_step, den, T);
+    FlowBlockGrid g;
+    if (const int e = flow_block_call(name, a, b, stride_a, stride_b, out, stride_out, N, T, H, W, layout, sample_bytes, mask, stride_mask, K,
+                                      counts, &g))
+        return e;
+    if (const int e = clear_sums(name, counts, (size_t)N, stream)) return e;
+    if (g.blocks == 0) return SSM_OK;          // a frame without a block: the cleared counts are the result, no output is touched
+    const MixDivisor d = mix_divisor(den);
+    const unsigned char *pa = static_cast<const unsigned char *>(a), *pb = static_cast<const unsigned char *>(b);
+    with_sample(sample_bytes, [&](auto s) {
+        with_layout(layout, [&](auto lay) {
+            SSM_LAUNCH((flow_mix_kernel<decltype(s), decltype(lay)::value>), dim3((unsigned)g.groups, N), dim3(LANES), 0, (hipStream_t)stream, pa, pb,
+                       stride_a, stride_b, static_cast<unsigned char *>(out), stride_out, T, num0, num_step, den, d, W, g.pl.cw, g.pl.luma(),
+                       g.pl.chroma(), (unsigned)g.nbx, (unsigned)g.blocks, mask, stride_mask, (unsigned)K, counts);
+        });
+    });
+    return ssm::check_launch("ssm_flow_mix_fwd");
 }
 
 // ---- interlaced clips -------------------------------------------------------------------------------------------------------------------

@@ -144,6 +144,15 @@ failed.  --flow_check without T and --flow_blocks is the report plus the per-blo
 replaced whole.  Not claimed: the seams between pasted and synthesised blocks are not smoothed, a block from the nearer frame inside a
 moving region steps rather than moves, and with the synthetic weights of this repository nothing can be said about quality.  Not with
 --active: chain two runs.
+
+--flow_fallback nearer|mix (with --flow_blocks): what a failed block carries.  nearer is the rule above and the default.  mix: the
+cross-fade of the pair's two frames at the output's exact time, a (1 - t) + b t rounded half up in exact integers (ssm_flow_mix_fwd in
+place of ssm_flow_paste_fwd; the definition stands in include/ssm_hip.h) - a failed block inside a moving region then changes with every
+output instead of standing still and jumping at t = 1/2.  With --fps / --speed the times are whole numbers over the denominator of the
+timeline's step, which may be at most 65535 (24 -> 59.94 gives 2500, 29.97 -> 25 gives 1001); a larger one is refused before anything is
+written.  A pair that reaches --flow_check's T, and a cut pair, are still replaced whole by the nearer frame.  Not claimed: where nearer
+steps, mix ghosts; which looks better is not known, and cannot be with the synthetic weights of this repository; there is still no
+default K; the seams are not smoothed.
 """
 import argparse
 import configparser
@@ -250,6 +259,10 @@ def getargs(argv=None):
                         help="With --flow_check: fall back per 8x8 block instead of per pair. A block of a synthesised frame in which more "
                              "than K of the 64 luma pixels are inconsistent in at least one direction takes the nearer input frame's "
                              "samples. 0 .. 64; 64 changes nothing. No default value: off unless given. Not together with --active.")
+    parser.add_argument("--flow_fallback", type=_named(lambda text: V.parse_flow_fallback(text, "--flow_fallback")), default="nearer",
+                        metavar="nearer|mix",
+                        help="With --flow_blocks: what a failed block takes. nearer: the nearer input frame's samples. mix: the cross-fade "
+                             "of the two input frames at the output's exact time, rounded half up, on the GPU. Default: nearer.")
     args = parser.parse_args(argv)
     refusal = V.flag_refusal(dict(vars(args), target_rate=args.fps,
                                   shutter_window=None if args.shutter_window[0] == "box" else V.window_name(args.shutter_window)))
@@ -260,6 +273,8 @@ def getargs(argv=None):
     if args.flow_blocks is not None and args.active is not None:
         parser.error("--flow_blocks does not go together with --active: the blocks of the per-block fallback are the whole frame's, not a "
                      "cut window's; chain two runs")
+    if args.flow_fallback != "nearer" and args.flow_blocks is None:          # a sub-option of --flow_blocks
+        parser.error("--flow_fallback %s is what a failed block of --flow_blocks carries: it needs --flow_blocks" % args.flow_fallback)
     if args.dedup is not None and args.upsample_rate is not None and args.upsample_rate < 1:
         parser.error("--upsample_rate must be at least 1 with --dedup (got %d)" % args.upsample_rate)
     if args.shutter is not None and args.shutter_samples < 1:
@@ -302,17 +317,18 @@ def flow_check_lines(checks, failed, option):
     return lines
 
 
-def flow_blocks_lines(repaired, k):
+def flow_blocks_lines(repaired, k, fallback="nearer"):
     """What --log gets of a run with --flow_blocks: `repaired` = [(i, failed blocks, blocks)] of the pairs that got outputs.  One summary
-    line, and one line for every pair in which every block failed."""
+    line, which names a --flow_fallback other than nearer, and one line for every pair in which every block failed."""
+    head = "flow blocks: K = %d" % k + ("" if fallback == "nearer" else ", fallback %s" % fallback)
     if not repaired:
-        return ["flow blocks: K = %d, no pair got a synthesised frame" % k]
+        return [head + ", no pair got a synthesised frame"]
     failed, of = sum(f for _, f, _ in repaired), sum(b for _, _, b in repaired)
     if of == 0:
-        return ["flow blocks: K = %d, %d pairs, the frame has no 8 x 8 block: nothing is replaced" % (k, len(repaired))]
+        return [head + ", %d pairs, the frame has no 8 x 8 block: nothing is replaced" % len(repaired)]
     shares = [f / b for _, f, b in repaired]
-    lines = ["flow blocks: K = %d, %d pairs, %d of %d blocks replaced (%.2f%%), per pair at most %.2f%% and at least %.2f%%"
-             % (k, len(repaired), failed, of, 100.0 * failed / of, 100.0 * max(shares), 100.0 * min(shares))]
+    lines = [head + ", %d pairs, %d of %d blocks replaced (%.2f%%), per pair at most %.2f%% and at least %.2f%%"
+             % (len(repaired), failed, of, 100.0 * failed / of, 100.0 * max(shares), 100.0 * min(shares))]
     lines += ["flow blocks: every block failed between input frames %d and %d" % (i, i + 1) for i, f, b in repaired if f == b]
     return lines
 
@@ -334,7 +350,7 @@ def main(argv=None, model=None):
                              active=args.active, active_probe=args.active_probe, field_probe=args.field_probe, static=args.static,
                              flow_check=None if args.flow_check is None else (True if args.flow_check[0] is None else args.flow_check[0]),
                              flow_alpha=args.flow_check and args.flow_check[1], flow_beta=args.flow_check and args.flow_check[2],
-                             flow_blocks=args.flow_blocks)
+                             flow_blocks=args.flow_blocks, flow_fallback=args.flow_fallback)
     with V.Y4MReader(args.input, extended=True, interlaced=args.deinterlace is not None or args.detelecine) as reader:
         if args.detelecine:
             log.info("[%s] detelecine: %d:%d frames/s in, film at %d:%d", args.expt, *reader.rate, *V.detelecine_rate(reader.rate))
@@ -399,7 +415,7 @@ def main(argv=None, model=None):
         for line in flow_check_lines(vi.flow_checks, vi.flow_failed, vi.flow_check):
             log.info("[%s] %s", args.expt, line)
     if args.flow_blocks is not None:
-        for line in flow_blocks_lines(vi.flow_repaired, args.flow_blocks):
+        for line in flow_blocks_lines(vi.flow_repaired, args.flow_blocks, args.flow_fallback):
             log.info("[%s] %s", args.expt, line)
     for i, score in vi.cuts:
         log.info("[%s] scene cut between input frames %d and %d: score %s = %.6f (threshold %s)", args.expt, i, i + 1, score, float(score),

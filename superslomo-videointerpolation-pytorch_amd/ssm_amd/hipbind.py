@@ -241,6 +241,8 @@ SIGNATURES = {
                                       _c_int, _c_int, ctypes.c_uint, _vp, _vp]),
     "ssm_flow_paste_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int,
                                     _c_int, _c_int, _c_int, _vp, ctypes.c_longlong, _c_int, _vp, _vp]),
+    "ssm_flow_mix_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int,
+                                  _c_int, _c_int, _c_int, _c_int, _c_int, _vp, ctypes.c_longlong, _c_int, _vp, _vp]),
     "ssm_plane_ssim_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _c_int, _c_int, _c_int, _c_int, _c_int, ctypes.c_longlong,
                                     ctypes.c_longlong, _vp, _vp]),
     "ssm_payload_mix_fwd": (_c_int, [_vp, _vp, ctypes.c_longlong, ctypes.c_longlong, _vp, ctypes.c_longlong, _c_int, ctypes.c_longlong, _c_int,

@@ -70,6 +70,9 @@
   flow_paste /            one direction of a pair's mask (flow_eval.flow_consistency), every frame between the pair carries the NEARER frame's
   parse_flow_blocks       samples of that block, by numpy and by ssm_flow_paste_fwd on the pass's stream; the number of such blocks per pair -
                           VideoInterpolator(flow_check=, flow_blocks=): the fixed grid and the timeline, every other mode unchanged
+  flow_mix_host /         the same blocks carrying the cross-fade a (1 - t) + b t of the pair's two frames at the output's exact time, rounded
+  flow_mix /              half up, by numpy and by ssm_flow_mix_fwd; fixed_mix, times_mix and flow_mix_den name a pair's times as three
+  parse_flow_fallback     launch scalars - VideoInterpolator(flow_blocks=, flow_fallback="mix"); "nearer" is the run without it
   (ssm_amd/video_score.py) hold-out scoring: the clip against its own held-out frames, plane_sse / HoldOutScorer on this loop's ring, Clip and
                           buffers; the PSNR of what VideoInterpolator(upsample_rate=hold) would write - this module is unchanged by it
 
@@ -2045,6 +2048,100 @@ def flow_paste(payload_a, payload_b, outputs, mask, h, w, siting, bits, k, split
     return counts
 
 
+# The fallback of a failed block: "nearer" is the rule above; "mix" is the cross-fade a (1 - t) + b t of the pair's two frames at the
+# output's exact time, rounded half up (include/ssm_hip.h, ssm_flow_mix_fwd).  The times of a pair's outputs reach the kernel as
+# k_j / den with k_j = num0 + j num_step, three launch scalars; den is at most FLOW_MIX_DEN_MAX (the numerator then fits 32 bits).
+FLOW_FALLBACKS = ("nearer", "mix")
+FLOW_MIX_DEN_MAX = 65535
+
+
+def parse_flow_fallback(value, spelt="flow_fallback"):
+    """What a failed block of the per-block fallback carries, "nearer" or "mix".  Anything else is a ValueError naming the value."""
+    name = value.strip().lower() if isinstance(value, str) else value
+    if name not in FLOW_FALLBACKS:
+        raise ValueError("%s, what a failed block of the per-block fallback carries, is \"nearer\" (the nearer input frame's samples) or "
+                         "\"mix\" (the cross-fade of the two frames at the output's time) (got %r)" % (spelt, value))
+    return name
+
+
+def flow_mix_den(tl):
+    """The den of ssm_flow_mix_fwd for a clip on the Timeline `tl`: the denominator of its step, which every output's t = frac(k step)
+    is a multiple of.  A denominator above FLOW_MIX_DEN_MAX is a ValueError that names it and the limit."""
+    den = tl.step.denominator
+    if den > FLOW_MIX_DEN_MAX:
+        raise ValueError("flow_fallback=\"mix\" takes the outputs' times as whole numbers over the denominator of the timeline's step, and the "
+                         "step %s has the denominator %d, more than %d: round the rate or the speed, or use the fallback \"nearer\""
+                         % (tl.step, den, FLOW_MIX_DEN_MAX))
+    return den
+
+
+def fixed_mix(rate):
+    """(num0, num_step, den) of the upsample_rate - 1 outputs of a pair on the fixed grid, t = (j + 1) / rate."""
+    return 1, 1, int(rate)
+
+
+def times_mix(times, den):
+    """The same for a pair's exact times (Fractions over `den`, an arithmetic progression - asserted: the kernel makes them of three
+    scalars); one output has the step 0.  den = 1 (an integer step) has no synthesised frame and no times."""
+    ks = [t * den for t in times]
+    assert ks and all(k.denominator == 1 and 0 <= k <= den for k in ks), "a pair's times are whole numbers over den, in 0 .. 1"
+    num0, num_step = int(ks[0]), int(ks[1] - ks[0]) if len(ks) > 1 else 0
+    assert all(k == num0 + j * num_step for j, k in enumerate(ks)), "a pair's times step evenly in its output rows"
+    return num0, num_step, int(den)
+
+
+def flow_mix_host(outputs, a, b, mask, h, w, siting, bits=8, k=FLOW_BLOCKS_MAX, num0=1, num_step=1, den=2):
+    """Yardstick of ssm_flow_mix_fwd: the operands of flow_paste_host -> (a copy of `outputs` in which every sample of every block that
+    fails in pair n - flow_paste_host's blocks and test, by flow_block_counts_host - is, in output j,
+    (a (den - k_j) + b k_j + (den >> 1)) // den with k_j = num0 + j num_step, over the samples of a[n] and b[n] (bytes, or the 16-bit
+    words above 8 bits) in int64 with numpy's floor division, uint64 [N]: the failed blocks of every pair)."""
+    k, num0, num_step, den, fb = int(k), int(num0), int(num_step), int(den), frame_bytes(h, w, siting, bits)
+    outputs, a, b = (np.asarray(x) for x in (outputs, a, b))
+    assert outputs.dtype == np.uint8 and outputs.ndim == 3 and outputs.shape[2] >= fb, "outputs are [N, T, at least frame_bytes] uint8"
+    n, t = outputs.shape[:2]
+    ks = [num0 + j * num_step for j in range(t)]
+    assert 0 <= k <= FLOW_BLOCKS_MAX and 2 <= den <= FLOW_MIX_DEN_MAX and all(0 <= kj <= den for kj in ks), \
+        "k in 0 .. 64, den in 2 .. 65535, every num0 + j num_step in 0 .. den"
+    for p in (a, b):
+        assert p.dtype == np.uint8 and p.shape == (n, p.shape[1]) and p.shape[1] >= fb, "payloads are [N, at least frame_bytes] uint8"
+    res, counts = outputs.copy(), np.zeros(n, np.uint64)
+    by, bx = h >> 3, w >> 3
+    if not (by and bx and n and t):
+        return res, counts
+    fail = flow_block_counts_host(np.asarray(mask)[:n], h, w) > k          # [N, by, bx]
+    counts[:] = fail.reshape(n, -1).sum(axis=1)
+    pa, pb = (split_planes(np.ascontiguousarray(x[:, :fb]), h, w, siting, bits) for x in (a, b))
+    cr, cc = _chroma_block(siting)
+    frames = np.ascontiguousarray(res[:, :, :fb]).reshape(n * t, fb)
+    for plane, sa, sb, (rr, rc) in zip(split_planes(frames, h, w, siting, bits), pa, pb, ((8, 8), (cr, cc), (cr, cc))):
+        where = np.repeat(np.repeat(fail, rr, axis=1), rc, axis=2)          # [N, rr by, rc bx]
+        dst = plane.reshape((n, t) + plane.shape[1:])[:, :, :rr * by, :rc * bx]
+        xa, xb = (s[:, :rr * by, :rc * bx].astype(np.int64) for s in (sa, sb))
+        for j, kj in enumerate(ks):
+            np.copyto(dst[:, j], ((xa * (den - kj) + xb * kj + (den >> 1)) // den).astype(plane.dtype), where=where)
+    res[:, :, :fb] = frames.reshape(n, t, fb)
+    return res, counts
+
+
+def flow_mix(payload_a, payload_b, outputs, mask, h, w, siting, bits, k, num0, num_step, den, counts=None):
+    """ssm_flow_mix_fwd on payloads: the operands of flow_paste; the samples of every block that fails in pair n become, in its output j,
+    the cross-fade of a[n]'s and b[n]'s at k_j / den, k_j = num0 + j num_step, rounded half up (flow_mix_host).  -> int64 [N] on the
+    device (into `counts` if given): the failed blocks of every pair.  Queued on the current stream."""
+    fb = frame_bytes(h, w, siting, bits)
+    n, counts, sa, sb_stride = _pair_operands(payload_a, payload_b, fb, "frame_bytes", counts, ())
+    assert outputs.is_cuda and outputs.dtype == torch.uint8 and outputs.dim() == 2 and outputs.shape[1] >= fb and outputs.device == payload_a.device \
+        and (outputs.shape[1] == 1 or outputs.stride(1) == 1), "outputs must be [N * T, at least frame_bytes] uint8 on the payloads' device"
+    assert outputs.shape[0] >= n and outputs.shape[0] % n == 0, "outputs hold T rows per pair"
+    assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (n, 2, h, w) and mask.device == payload_a.device \
+        and mask[0].is_contiguous(), "mask must be [N, 2, h, w] uint8 on the payloads' device, a pair's two planes dense"
+    t = outputs.shape[0] // n
+    hb.check(hb.load().ssm_flow_mix_fwd(payload_a.data_ptr(), payload_b.data_ptr(), sa, sb_stride, outputs.data_ptr(),
+                                        outputs.stride(0) if n * t > 1 else 0, n, t, int(num0), int(num_step), int(den), h, w, siting,
+                                        sample_bytes(bits), mask.data_ptr(), mask.stride(0) if n > 1 else 0, int(k), counts.data_ptr(),
+                                        hb.stream_ptr()))
+    return counts
+
+
 # ---- output order -------------------------------------------------------------------------------------------------------------------
 def pass_order(valid, nt):
     """Write order of one pass of `valid` pairs with nt interpolated frames each: ("interp", row of the pass's output buffer) for the
@@ -2753,7 +2850,8 @@ class PairOptions:
     every pair in the log's `flow_checks` and lets a pair with score >= T fall back like a cut pair (`flow_failed`).  It needs no row 0.
     flow_blocks = K (the flow check's per-block fallback): check_flow() also asks for the pairs' masks, one device mask [pairs, 2, h, w]
     per stream, and paste_flow() - behind the egress, ahead of paste_static() and of the copies to the host - lets ssm_flow_paste_fwd put
-    the nearer frame's samples into every block with more than K inconsistent pixels; the failed blocks per pair go back to the ring
+    the nearer frame's samples (flow_fallback "mix": ssm_flow_mix_fwd the cross-fade of the pair's two frames at the output's time) into
+    every block with more than K inconsistent pixels; the failed blocks per pair go back to the ring
     slot like the static counts and the writer thread notes them in the log's `flow_repaired`.  It reads the pairs' payloads, so it
     needs row 0 as static blocks do.
     log: the VideoInterpolator whose `cuts` and `static` take the notes.
@@ -2787,9 +2885,11 @@ class PairOptions:
     the end `carried`, the writer thread's copy of the frame that row 0 stands for, takes the last pair's right frame: its ring slot is
     free by the time the next pass's rows are written."""
 
-    def __init__(self, log, clip, scene_cut=None, static=None, flow_check=None, flow_blocks=None):
+    def __init__(self, log, clip, scene_cut=None, static=None, flow_check=None, flow_blocks=None, flow_fallback="nearer"):
         self.log, self.clip, self.static, self.flow, self.flow_blocks = log, clip, static, flow_check, flow_blocks
         assert flow_blocks is None or flow_check is not None, "flow_blocks is the flow check's"
+        assert flow_fallback in FLOW_FALLBACKS and (flow_blocks is not None or flow_fallback == "nearer"), "flow_fallback is flow_blocks'"
+        self.flow_mix = flow_fallback == "mix"          # a launch of another kernel on the same operands: nothing more is allocated
         self.fetch = static is not None or flow_blocks is not None          # a paste behind the egress reads the pair's payloads: row 0 is fetched
         self.cuts = None if scene_cut is None else SceneCuts(scene_cut)
         self.pixels, self.blocks = clip.h * clip.w, static_blocks(clip.h, clip.w)
@@ -2874,13 +2974,18 @@ class PairOptions:
     def paste_flow(self, r, k, groups):
         """Behind the egress, ahead of paste_static and of the D2H copies of the frames: one ssm_flow_paste_fwd call per group (first
         pair, pairs whose rows follow one another, their outputs [pairs * T, frame bytes], the outputs of a pair that take the left
-        frame) on the masks check_flow left, then the counts' way back to ring slot r.  With static too the static paste comes last:
-        a static block's samples are the left frame's."""
+        frame) on the masks check_flow left, then the counts' way back to ring slot r.  With the fallback "mix" the call is
+        ssm_flow_mix_fwd and a group's last entry the (num0, num_step, den) of a pair's times in place of the split.  With static too
+        the static paste comes last: a static block's samples are the left frame's."""
         if self.flow_blocks is not None:
             clip, d = self.clip, self.dev_in[k]
-            for p, m, outputs, split in groups:
-                flow_paste(d[self.lefts[p]:self.lefts[p] + m], d[self.rights[p]:self.rights[p] + m], outputs, self.dev_mask[k][p:p + m],
-                           clip.h, clip.w, clip.siting, clip.bits, self.flow_blocks, split, counts=self.dev_failed[k][p:p + m])
+            for p, m, outputs, at in groups:
+                a, b, mask, counts = d[self.lefts[p]:self.lefts[p] + m], d[self.rights[p]:self.rights[p] + m], self.dev_mask[k][p:p + m], \
+                    self.dev_failed[k][p:p + m]
+                if self.flow_mix:
+                    flow_mix(a, b, outputs, mask, clip.h, clip.w, clip.siting, clip.bits, self.flow_blocks, *at, counts=counts)
+                else:
+                    flow_paste(a, b, outputs, mask, clip.h, clip.w, clip.siting, clip.bits, self.flow_blocks, at, counts=counts)
             self.host_failed[r].copy_(self.dev_failed[k], non_blocking=True)
 
     def check_flow(self, r, k, flow4):
@@ -3049,7 +3154,7 @@ class VideoInterpolator:
                  tile=None, halo=256, blend=32, target_rate=None, speed=None, shutter=None, shutter_samples=8, scene_cut=None,
                  shutter_light="coded", deinterlace=None, dedup=None, dedup_max=DEDUP_MAX, active=None, active_probe=ACTIVE_PROBE,
                  shutter_window="box", field_probe=None, static=None, flow_check=None, flow_alpha=None, flow_beta=None,
-                 flow_blocks=None):
+                 flow_blocks=None, flow_fallback="nearer"):
         """target_rate = (num, den) and / or speed (a Fraction, or what Fraction() takes; 1/4 is four times slower): the output follows
         Timeline(speed * input rate / target_rate) instead of the fixed grid of upsample_rate, which is then not used (see
         _run_timeline); with both None nothing changes.  flow_scale = 2 or 4: the coarse-flow mode of FullModel.interpolate (U-Nets at 1/flow_scale of the size; an approximation of the
@@ -3156,6 +3261,15 @@ class VideoInterpolator:
         still replaced whole.  Not claimed: K has no default; seams between pasted and synthesised blocks are not smoothed; a block from
         the nearer frame inside a moving region steps rather than moves; with this repository's synthetic weights nothing can be said
         about quality.  Not together with active (chain two runs).  None: the run with flow_check as it is, launch for launch.
+        flow_fallback ("nearer" or "mix"; parse_flow_fallback), a sub-option of flow_blocks: what a failed block carries.  "nearer" is
+        the run as described above, launch for launch.  "mix": ssm_flow_mix_fwd in place of ssm_flow_paste_fwd, on the same masks, at
+        the same place in the pass - every sample of a failed block is a (1 - t) + b t of the pair's two frames at the output's EXACT
+        time t, rounded half up (flow_mix_host is the definition): (j + 1) / upsample_rate on the fixed grid, on a timeline the
+        output's own Fraction over the denominator of the timeline's step, which is at most 65535 (flow_mix_den; a larger one is
+        refused by name before anything is written; 24 -> 59.94 gives 2500, 29.97 -> 25 gives 1001).  A pair that reaches flow_check's
+        T, and a cut pair, are still replaced whole by the NEARER frame; with static the static paste still comes last;
+        `flow_repaired` keeps its meaning.  Not claimed: where "nearer" steps, "mix" ghosts; which looks better is not known, and
+        cannot be with synthetic weights; there is still no default K; seams are not smoothed.  Without flow_blocks "mix" is refused.
         Which of these options do not go together, which need another, and what each refusal says is one table, OPTION_RULES (above
         the class; api_refusal asks it here, flag_refusal for the command line), not a list kept per option."""
         from .coarse import check_scale
@@ -3219,6 +3333,10 @@ class VideoInterpolator:
                 raise ValueError("flow_blocks together with active is not available: the blocks of the per-block fallback are the whole "
                                  "frame's, not a cut window's; chain two runs")
             self.flow_blocks = parse_flow_blocks(flow_blocks)
+        self.flow_fallback = parse_flow_fallback(flow_fallback)          # flow_blocks' own sub-option: what a failed block carries
+        if self.flow_fallback != "nearer" and self.flow_blocks is None:
+            raise ValueError("flow_fallback=\"%s\" is what a failed block of flow_blocks carries: give flow_blocks, or leave it out"
+                             % self.flow_fallback)
         self._new_log()
 
     def _new_log(self):
@@ -3231,9 +3349,13 @@ class VideoInterpolator:
         return padded_dims(h, w, 32 * self.flow_scale)[0]
 
     def timeline(self, in_rate):
-        """The Timeline of a clip at `in_rate` (num, den); refuses a step whose slots the plan would not take."""
-        return Timeline(timeline_step(in_rate, self.target_rate, self.speed), max_slots=MAX_STAGE2_BATCH // self.pb, shutter=self.shutter,
-                        samples=self.samples)
+        """The Timeline of a clip at `in_rate` (num, den); refuses a step whose slots the plan would not take and, with
+        flow_fallback="mix", one whose denominator ssm_flow_mix_fwd does not take (flow_mix_den)."""
+        tl = Timeline(timeline_step(in_rate, self.target_rate, self.speed), max_slots=MAX_STAGE2_BATCH // self.pb, shutter=self.shutter,
+                      samples=self.samples)
+        if self.flow_fallback == "mix":
+            flow_mix_den(tl)
+        return tl
 
     def gap_timeline(self):
         """The GapTimeline of a run with dedup; refuses a dedup_max and upsample_rate whose slots the plan would not take."""
@@ -3309,6 +3431,8 @@ class VideoInterpolator:
         """Returns the number of frames written: (n - 1) * upsample_rate + 1 for n input frames (with target_rate / speed:
         floor((n - 1) / step) + 1; with a shutter: Timeline.n_outputs(n); with deinterlace: 2 n; with dedup the fixed grid's count)."""
         self._new_log()
+        if self.flow_fallback == "mix" and self.timed:
+            self.timeline(reader.rate)          # a denominator that ssm_flow_mix_fwd does not take: refused before a frame is read or written
         if self.field_probe_option is not None and reader is not self._probed:
             reader = self.probe_fields(reader)
         self._probed = None          # one run per probe
@@ -3369,8 +3493,9 @@ class VideoInterpolator:
         t_dev = torch.tensor(t_values(self.rate), dtype=torch.float32, device=dev)
         slots = ring_slots(depth, fb, pb, pb * nt, fb_out=clip.fb_out)
         np_in, np_out = slots.np_in, slots.np_out
-        opt = PairOptions(self, clip, self.scene_cut, self.static_lo, self.flow_check, self.flow_blocks)
-        lead, lefts, rights, split = opt.lead, list(range(pb)), list(range(1, pb + 1)), fixed_split(self.rate)
+        opt = PairOptions(self, clip, self.scene_cut, self.static_lo, self.flow_check, self.flow_blocks, self.flow_fallback)
+        lead, lefts, rights = opt.lead, list(range(pb)), list(range(1, pb + 1))
+        flow_at = fixed_mix(self.rate) if opt.flow_mix else fixed_split(self.rate)          # what a failed block takes in a pair's outputs
         _, dev_out, _, ingested, _ = opt.buffers(n, depth, pb, pb, pb * nt)
         planes = [torch.empty(pb + 1, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [carried left frame | new frames]
         first = torch.empty(1, fb, dtype=torch.uint8).pin_memory()
@@ -3405,7 +3530,7 @@ class VideoInterpolator:
                 frames = pipe.engines[k].run(img6, t_dev, False)
                 opt.check_flow(r, k, pipe.engines[k].s1.t["out"] if opt.flow is not None else None)
                 clip.egress(frames, dev_out[k])
-                opt.paste_flow(r, k, [(0, pb, dev_out[k], split)])
+                opt.paste_flow(r, k, [(0, pb, dev_out[k], flow_at)])
                 opt.paste_static(r, k, [(0, pb, dev_out[k])])
                 slots.host_out[r].copy_(dev_out[k], non_blocking=True)
                 opt.download(r, k)
@@ -3560,7 +3685,7 @@ class VideoInterpolator:
         host_in, host_out, host_t, np_in, np_out, np_t, done = ring_slots(depth, fb, cap, pb * max(S, 1), pb * max(S, 1), fb_out=clip.fb_out)
         plan = PassPlanner(tl, pb, cap)
         if pipe is not None:
-            opt = PairOptions(self, clip, self.scene_cut, self.static_lo, self.flow_check, self.flow_blocks)
+            opt = PairOptions(self, clip, self.scene_cut, self.static_lo, self.flow_check, self.flow_blocks, self.flow_fallback)
             lead = opt.lead
             _, dev_out, dev_t, ingested, _ = opt.buffers(n, depth, pb, cap, pb * S, pb * S)
             planes = [torch.zeros(pb, 2, 3, hp, wp, dtype=torch.float32, device=dev) for _ in range(n)]      # [pair][left | right]
@@ -3602,7 +3727,8 @@ class VideoInterpolator:
                 if late:
                     if opt.flow_blocks is not None:          # exact times, as the writer thread's rule asks: t < 1/2 takes the left frame
                         exact = [tl.times(i) for i in plan.closed_index]
-                        opt.paste_flow(r, k, [(p, 1, dev_out[k][p * S:p * S + len(ts)], times_split(exact[p][:len(ts)]))
+                        at = (lambda ts: times_mix(ts, tl.step.denominator)) if opt.flow_mix else times_split
+                        opt.paste_flow(r, k, [(p, 1, dev_out[k][p * S:p * S + len(ts)], at(exact[p][:len(ts)]))
                                               for p, (_, _, ts) in enumerate(pairs)])
                     opt.paste_static(r, k, [(p, 1, dev_out[k][p * S:p * S + len(ts)]) for p, (_, _, ts) in enumerate(pairs)])
                     for o, m in spans:
